@@ -3,7 +3,12 @@
 ResNet-50, 600x1000 synthetic image, anchor scales 128/256/512, 300 proposals, 21 classes,
 fp32 (BASELINE.json configs[1]) on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given, and prints
+the result line (metric, value, unit, higher_is_better, dtype, ms_per_step, config).  Everything else the line can carry
+(the legs listed below, the other BASELINE configs, other matrix paths and pass shapes, host I/O, the reference's entry
+point, the data-parallel training steps) runs only with --full.
+
 N > 1: one rank per GPU.  Under `python -m torch.distributed.run --nproc-per-node N ...` (RANK / WORLD_SIZE in the
 environment) this process IS a rank; started plainly as `python bench.py --gpus N`, it starts the N ranks itself
 (fresh child processes, before this process has touched the GPU), relays rank 0's JSON line and exits non-zero if any
@@ -17,7 +22,7 @@ through the whole device-resident path (backbone convs, RPN heads,
 decode, top-8000 ordering, NMS to 300, RoI crop-resize, stage-5 head, softmax, detection
 post-process), replayed from a hipGraph.  The input is resident in HBM when timing starts.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      the MFMA conv kernel: algorithmic FLOP of every conv launch of one image /
                 their summed HIP-event durations, against the 157.3 TFLOP/s fp32 matrix peak.
   cpu_baseline  the oracle's torch-CPU restatement of the reference graph ("port"), timed on
@@ -1067,8 +1072,8 @@ _JSON_OUT = None
 # finished BEFORE this process makes its first HIP call (a process that has initialised the runtime starts no GPU children), one after
 # the other, so each has the chip to itself exactly as when run by hand.
 EXTRA_LEGS = (
-    ("c0_vgg16_rpn", ["bench.py", "--config", "c1", "--no-extra", "--no-cpu-baseline", "--no-io", "--steps", "30", "--warmup", "5"]),
-    ("c3_r101_bf16", ["bench.py", "--config", "c4", "--no-extra", "--no-cpu-baseline", "--no-io", "--steps", "12", "--warmup", "3"]),
+    ("c0_vgg16_rpn", ["bench.py", "--full", "--config", "c1", "--no-extra", "--no-cpu-baseline", "--no-io", "--steps", "30", "--warmup", "5"]),
+    ("c3_r101_bf16", ["bench.py", "--full", "--config", "c4", "--no-extra", "--no-cpu-baseline", "--no-io", "--steps", "12", "--warmup", "3"]),
     ("train_steps_f32", [os.path.join("scripts", "bench_train.py"), "--through-loop", "--no-host-feed", "--steps", "60", "--warmup", "40"]),
     ("train_steps_mixed_bf16", [os.path.join("scripts", "bench_train.py"), "--bf16", "--through-loop", "--no-host-feed", "--steps", "60", "--warmup", "40"]),
 )
@@ -1162,11 +1167,43 @@ def default_pass_shape(config, bf16_run, batch=0, streams=0, no_graph=False):
     return batch, streams
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(outs, outdir, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every tensor of the dict each timed pass returned in the last step (what a caller of the pass receives),
+    stacked over the passes of the step: DIR/<key>.npy with shape (passes, [images per pass,] tensor shape...).  Integer and
+    float64 tensors are written as float64 (exact), the other floats as float32.  The outputs share `budget` bytes, smallest
+    first: one that does not fit its share whole (the conv4 feature map) is written as a 1-D sample of as many values as fit,
+    taken at sorted indices drawn by np.random.RandomState(0) from the flattened array.  The inputs are seeded, so two runs with
+    the same arguments write the same files."""
+    os.makedirs(outdir, exist_ok=True)
+    stacked = {k: torch.stack([torch.stack(o[k]) if isinstance(o[k], list) else o[k] for o in outs]) for k in outs[0]}
+    left, report = budget, []
+    for i, (key, t) in enumerate(sorted(stacked.items(), key=lambda kv: kv[1].numel())):
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        share = (left // (len(stacked) - i) - 256) // (8 if wide else 4)        # (256 bytes: room for the .npy header)
+        if t.numel() > share:
+            idx = np.sort(np.random.RandomState(0).randint(0, t.numel(), share))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            report.append("%s: %d sampled values" % (key, share))
+        path = os.path.join(outdir, key + ".npy")
+        np.save(path, (t.double() if wide else t.float()).cpu().numpy())
+        left -= os.path.getsize(path)
+    sys.stderr.write("bench.py: %d outputs written to %s (%.1f MB%s)\n" % (len(stacked), outdir, (budget - left) / 1e6,
+                                                                          "; " + ", ".join(report) if report else ""))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed passes returned in the last step "
+                    "as DIR/<output>.npy (float32 / float64, at most 64 MB in all: dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: roofline, cpu_baseline and parity, the other "
+                    "matrix paths and pass shapes, host I/O, the reference's entry point, the other BASELINE configs (`extra`), and "
+                    "with N > 1 the data-parallel training steps (`train_dp`); the --no-* and --conv-table options below apply to it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--shared-tiles", action="store_true", help="with --no-graph: the launch forms of the multi-image default run")
@@ -1208,10 +1245,10 @@ def main():
         return
     extra = None
     entry_child = None
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.config in ("c2", "c4") and args.dtype == "config" and not args.no_graph and not args.no_io
-            and os.environ.get("FRCNN_BENCH_FORCE_DIST", "0") == "0" and "FRCNN_BENCH_NO_ENTRY" not in os.environ and not _under_a_profiler()):
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.config in ("c2", "c4") and args.dtype == "config" and not args.no_graph
+            and not args.no_io and os.environ.get("FRCNN_BENCH_FORCE_DIST", "0") == "0" and "FRCNN_BENCH_NO_ENTRY" not in os.environ and not _under_a_profiler()):
         entry_child = entry_legs_child(args.config)  # (a child too, and first: this process has not touched the GPU yet)
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.config == "c2" and not args.no_extra and args.dtype == "config"
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.config == "c2" and not args.no_extra and args.dtype == "config"
             and not args.no_graph and args.streams <= 0 and args.batch <= 0 and os.environ.get("FRCNN_BENCH_FORCE_DIST", "0") == "0"
             and "FRCNN_BENCH_BACKEND" not in os.environ and not _under_a_profiler()):
         # (the driver's command line; a run that names a pass shape or a dev backend is somebody's experiment.  Under rocprofv3 the tool's
@@ -1295,6 +1332,7 @@ def main():
                     pl._graph.replay()
     else:
         S = 1
+        eager_out = [None]                          # the last step's outputs (--dump-outputs)
         if args.shared_tiles:
             # eager, but with the launch forms the default multi-image graphs hold (plain launches, tiles chosen for a
             # shared chip): lets the PMC passes (profile_round.sh) see those kernel instantiations one at a time
@@ -1302,9 +1340,10 @@ def main():
 
             def step():
                 with ops.conv_workspace(ops.NO_SPLIT_K), ops.tile_policy(True):
-                    pipe.forward_dev(x)
+                    eager_out[0] = pipe.forward_dev(x)
         else:
-            step = lambda: pipe.forward_dev(x)
+            def step():
+                eager_out[0] = pipe.forward_dev(x)
 
     # FRCNN_BENCH_FORCE_DIST=1 (dev / tests): take the multi-rank code path with ONE rank -- process group over the real "nccl"
     # backend, barriers, max-over-ranks timing, the `train_dp` leg with its collective forced on -- on a one-GPU box
@@ -1351,6 +1390,8 @@ def main():
         ranks_audit = {"ranks_seen": len(per_rank), "per_rank_img_s": [round(S * B * args.steps / v, 2) for v in per_rank],
                        "slowest_over_fastest_seconds": round(max(per_rank) / min(per_rank), 4),
                        "value_is": "ranks x images per step x steps / the SLOWEST rank's seconds (all ranks between the same two barriers)"}
+    if args.dump_outputs and rank == 0:
+        dump_outputs([pl._static_out for pl in pipes] if not args.no_graph else eager_out, args.dump_outputs)
 
     # ---- the same K steps on the OTHER fp32 matrix paths, when the timed graphs above run their large launches on a split engine:
     # all numbers in one line, same process, same inputs (one rank only).  `native_f32_mfma`: every convolution on
@@ -1427,7 +1468,7 @@ def main():
         torch.cuda.empty_cache()
         return res
     single = None
-    if not args.no_graph and args.f32_engine != "native" and DTYPE == "f32" and world == 1 and not force_dist and "FRCNN_BENCH_NO_NATIVE" not in os.environ:
+    if args.full and not args.no_graph and args.f32_engine != "native" and DTYPE == "f32" and world == 1 and not force_dist and "FRCNN_BENCH_NO_NATIVE" not in os.environ:
         native = time_engine("native", "the same %d steps with every fp32 convolution on v_mfma_f32_32x32x2_f32 (--f32-engine native)")
         if args.f32_engine == "f16x3":
             x6_alt = time_engine("bf16x6", "the same %d steps with the split launches on the bf16 matrix cores by EXACT three-way operand splitting, six matrix "
@@ -1442,7 +1483,7 @@ def main():
     # memory.  4*S distinct frames rotate, so no step sees the frame of the step before.  Reported beside `value`, which
     # stays the HBM-resident rate the contract asks for.
     io = None
-    if not args.no_graph and not args.no_io:
+    if args.full and not args.no_graph and not args.no_io:
         from faster_rcnn_amd import ops
         rs = np.random.RandomState(1000 + rank)
         frames = [torch.from_numpy(rs.randint(0, 256, (HEIGHT, WIDTH, 3)).astype(np.uint8)).pin_memory() for _ in range(4 * S * B)]
@@ -1497,13 +1538,13 @@ def main():
     via_entry = None
     if entry_child is not None and "error" not in entry_child:
         via_entry = entry_child                     # measured in a process of its own, under the environment voc_dets.main sets up
-    elif world == 1 and not force_dist and not args.no_graph and not args.no_io and DEPTH != 16 and "FRCNN_BENCH_NO_ENTRY" not in os.environ:
+    elif args.full and world == 1 and not force_dist and not args.no_graph and not args.no_io and DEPTH != 16 and "FRCNN_BENCH_NO_ENTRY" not in os.environ:
         via_entry = entry_legs(pipe, anchors, rank)  # (under a profiler, or the child failed: in this process, on its four hardware queues)
         if entry_child is not None:
             via_entry["child_process_error"] = entry_child["error"]
 
     train_dp = None
-    if dist is not None and args.config in ("c2", "c4") and not args.no_train_dp:
+    if args.full and dist is not None and args.config in ("c2", "c4") and not args.no_train_dp:
         try:
             from faster_rcnn_amd import util as _util
             train_anchors = _util.get_anchors([128, 256, 512])
@@ -1528,16 +1569,17 @@ def main():
     n_dets = int(first(out["n_dets"]).item()) if "n_dets" in out else None
 
     if rank == 0:
-        try:
-            roof, groups = conv_roofline(pipe, x, split_k=split_k, throughput=S > 1 or B > 1, images=B, engine=args.f32_engine)
-            if args.conv_table:                     # per distinct launch: shape, count, duration alone on the chip, rate (stderr)
-                for key, g in sorted(groups.items(), key=lambda kv: -kv[1]["ms"] * kv[1]["count"]):
-                    fl = g["rec"]["flops"]
-                    sys.stderr.write("conv %-44s M=%-7d N=%-5d K=%-5d s=%d  x%-3d %8.1f us %7.1f TFLOP/s  (%.3f ms per image)\n" % (
-                        key[0], key[1], key[2], key[3], key[4], g["count"], 1e3 * g["ms"], fl / (g["ms"] * 1e-3) / 1e12, g["ms"] * g["count"] / B))
-        except Exception as e:                          # the throughput line must survive a failed per-kernel pass
-            roof = None
-            roof_error = "%s: %s" % (type(e).__name__, e)
+        roof = None
+        if args.full:
+            try:
+                roof, groups = conv_roofline(pipe, x, split_k=split_k, throughput=S > 1 or B > 1, images=B, engine=args.f32_engine)
+                if args.conv_table:                     # per distinct launch: shape, count, duration alone on the chip, rate (stderr)
+                    for key, g in sorted(groups.items(), key=lambda kv: -kv[1]["ms"] * kv[1]["count"]):
+                        fl = g["rec"]["flops"]
+                        sys.stderr.write("conv %-44s M=%-7d N=%-5d K=%-5d s=%d  x%-3d %8.1f us %7.1f TFLOP/s  (%.3f ms per image)\n" % (
+                            key[0], key[1], key[2], key[3], key[4], g["count"], 1e3 * g["ms"], fl / (g["ms"] * 1e-3) / 1e12, g["ms"] * g["count"] / B))
+            except Exception as e:                          # the throughput line must survive a failed per-kernel pass
+                roof_error = "%s: %s" % (type(e).__name__, e)
         line = {
             "metric": ("images/sec RPN-only forward VGG16 %dx%d" % (HEIGHT, WIDTH)) if DEPTH == 16
                       else "images/sec end-to-end (RPN+det) ResNet-%d %dx%d" % (DEPTH, HEIGHT, WIDTH),
@@ -1563,8 +1605,9 @@ def main():
                        "res5a 1x1 layers on the conv4 map, then RoI resampling (algebraically equal, see DESIGN 5)" if HOIST else "reference order",
                        "n_rois_kept": n_rois, "n_detections": n_dets, "parallelism": "replicas x%d (no collective)" % world,
                        "rank0_cpu_affinity": affinity},
-            "roofline": roof,
         }
+        if args.full:
+            line["roofline"] = roof if roof is not None else {"bound": "mfma", "error": roof_error}
         if native is not None:
             line["native_f32_mfma"] = native
         if x6_alt is not None:
@@ -1581,8 +1624,6 @@ def main():
             line["train_dp"] = train_dp
         if extra is not None:
             line["extra"] = extra
-        if roof is None:
-            line["roofline"] = {"bound": "mfma", "error": roof_error}
         if roof is not None and HOIST and DEPTH != 16:   # what the same image costs in the reference's layer order (res5a_branch2a / branch1 on every crop)
             rows_cols = int(out["rpn_cls"].shape[-3] * out["rpn_cls"].shape[-2])
             saved = 2.0 * 1024 * (512 + 2048) * (PROPOSALS * 49 - rows_cols) / 1e9
@@ -1601,9 +1642,9 @@ def main():
             roof["frac"] = round(roof["achieved"] / PEAK_BF16_TFLOPS, 4)
             roof["all_conv_launches"]["frac"] = round(roof["all_conv_launches"]["achieved"] / PEAK_BF16_TFLOPS, 4)
             roof["backbone_conv"]["frac"] = round(roof["backbone_conv"]["achieved"] / PEAK_BF16_TFLOPS, 4)
-        if world == 1 and not args.no_cpu_baseline and args.config == "c1":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "c1":
             line["cpu_baseline"], line["parity"] = vgg_rpn_cpu_and_parity(pipe, weights)
-        if world == 1 and not args.no_cpu_baseline and args.config == "c4":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "c4":
             oracle_runs = []
             line["cpu_baseline"] = cpu_baseline(weights, anchors, budget_s=10.0, runs=oracle_runs, min_images=4 if DTYPE == "bf16" else 1,
                                                 alt_dense_class=getattr(pipe, "raw_dense_class", None))
@@ -1616,7 +1657,7 @@ def main():
                     line["parity"]["e2e_vs_fp32"] = e2e_drift_bf16(pipe, weights, anchors, oracle_runs)
                 except Exception as e:
                     line["parity"]["e2e_vs_fp32"] = {"ok": False, "error": repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline and args.config == "c2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "c2":
             oracle_runs = []
             line["cpu_baseline"] = cpu_baseline(weights, anchors, runs=oracle_runs, alt_dense_class=getattr(pipe, "raw_dense_class", None) if DTYPE != "f32" else None)
             if DTYPE == "f32":

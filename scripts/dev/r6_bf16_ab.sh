@@ -6,7 +6,7 @@ cd $R
 for rep in 1 2; do
 for lib in new old; do
   if [ $lib = old ]; then export FRCNN_LIB_PATH=$R/scripts/micro/_bin/libfrcnn_hip_oldbf16.so; else unset FRCNN_LIB_PATH; fi
-  python bench.py --config c4 --no-cpu-baseline --no-io --steps 20 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print('$lib c4', d['value'], d['roofline']['frac'])"
+  python bench.py --full --config c4 --no-cpu-baseline --no-io --steps 20 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print('$lib c4', d['value'], d['roofline']['frac'])"
   python scripts/bench_train.py --bf16 --steps 60 --warmup 40 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print('$lib mixed steps', d['rpn_step1']['ms_per_step'], d['det_step2']['ms_per_step'])"
 done
 done

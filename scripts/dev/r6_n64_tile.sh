@@ -18,6 +18,6 @@ PY
 for rep in 1 2; do
   for v in 87 88; do
     FRCNN_H3_N64_SHARED=$v python3 bench.py --config c1 --steps 20 --warmup 4 --no-cpu-baseline --no-io --no-extra 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); print('64-column tile $v: c0', d['value'])"
-    FRCNN_H3_N64_SHARED=$v python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-io --no-extra 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); print('64-column tile $v: c2', d['value'], d['roofline']['backbone_conv']['in_flight']['ms_per_image'])"
+    FRCNN_H3_N64_SHARED=$v python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-io --no-extra 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); print('64-column tile $v: c2', d['value'], d['roofline']['backbone_conv']['in_flight']['ms_per_image'])"
   done
 done

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 OUT=$R/gpurun_out/pmc_by_grid
 mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $OUT/$c -- python3 $R/bench.py --steps 2 --warmup 1 --streams 1 --batch 4 --no-cpu-baseline --no-graph --shared-tiles --no-extra > $OUT/$c.log 2>&1
+  rocprofv3 --pmc $c --output-format csv -d $OUT/$c -- python3 $R/bench.py --full --steps 2 --warmup 1 --streams 1 --batch 4 --no-cpu-baseline --no-graph --shared-tiles --no-extra > $OUT/$c.log 2>&1
   f=$(ls -S $(find $OUT/$c -name "*counter_collection.csv") | head -1)
   python3 - "$f" "$c" > $OUT/$c.by_grid.txt <<'PY'
 import csv, sys, collections

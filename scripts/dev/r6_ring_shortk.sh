@@ -5,7 +5,7 @@
 #  two chunks' requests: 552 / 552 against 545 / 552.)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd $R
-run() { python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-io --conv-table --no-extra > /tmp/ab.json 2> /tmp/ab.err; grep "^conv" /tmp/ab.err | head -2 | cut -c1-150; }
+run() { python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-io --conv-table --no-extra > /tmp/ab.json 2> /tmp/ab.err; grep "^conv" /tmp/ab.err | head -2 | cut -c1-150; }
 for rep in 1 2; do
   echo "== double buffer"; FRCNN_H3_RING=0 run
   echo "== ring for every plane-input launch"; FRCNN_H3_RING_MIN_CHUNKS=1 run

@@ -9,4 +9,4 @@ for v in 0 2 0 2; do
   FRCNN_BF16_VARIANT=$v python bench.py --config c4 --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('c4', d['value'], d['ms_per_step'])"
   FRCNN_BF16_VARIANT=$v python scripts/bench_train.py --bf16 --steps 30 --warmup 8 2>/dev/null | tail -2 | cut -c1-400
 done
-python bench.py --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | cut -c1-900
+python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | cut -c1-900

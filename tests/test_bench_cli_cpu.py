@@ -76,3 +76,30 @@ def test_extra_legs_are_compacted_and_survive_a_failed_child(monkeypatch):
                                  "rpn_step1": {"ms_per_step": 2.0, "img_s": 500.0, "roofline": {"frac": 0.5}, "grad_payload_MB": 47.3,
                                                "through_loop": {"fast_feed": {"ms_per_iteration": 2.1, "iterations": 64, "distinct_images": 32}}}})
     assert t["rpn_step1"]["through_train_util_loop"]["ms_per_iteration"] == 2.1 and "det_step2" not in t and "grad_payload_MB" not in t["rpn_step1"]
+
+
+def test_dump_outputs_writes_every_output_within_the_budget(tmp_path):
+    """--dump-outputs: one DIR/<key>.npy per output of the timed passes, stacked over the passes (and the images of a batched pass), integers and
+    float64 as float64, other floats as float32; an output too large for its share of the budget becomes a seeded 1-D sample, the same every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = [{"feat": torch.randn(2, 50, 40, generator=g).to(torch.bfloat16), "rois": torch.randn(2, 7, 4, generator=g),
+             "n_dets": [torch.tensor([3], dtype=torch.int32), torch.tensor([5], dtype=torch.int32)],
+             "det_prob": [torch.rand(6, generator=g, dtype=torch.float64) for _ in range(2)]} for _ in range(3)]
+    budget = 20000
+    for run in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / run), budget=budget)
+    got = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(got) == {"feat.npy", "rois.npy", "n_dets.npy", "det_prob.npy"}
+    assert got["rois.npy"].dtype == np.float32 and np.array_equal(got["rois.npy"], np.stack([o["rois"].numpy() for o in outs]))
+    assert got["n_dets.npy"].dtype == np.float64 and got["n_dets.npy"].shape == (3, 2, 1) and got["n_dets.npy"][1, 1, 0] == 5
+    assert got["det_prob.npy"].dtype == np.float64 and got["det_prob.npy"].shape == (3, 2, 6)
+    feat = got["feat.npy"]
+    whole = torch.stack([o["feat"] for o in outs]).float().reshape(-1).numpy()
+    assert feat.dtype == np.float32 and feat.ndim == 1 and 0 < feat.size < whole.size and np.isin(feat, whole).all()
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= budget
+    for name, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / name))

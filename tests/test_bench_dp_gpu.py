@@ -54,7 +54,7 @@ def _launch(script_args, world, timeout=900):
 
 
 def test_bench_two_ranks_on_one_gpu():
-    flags = ["bench.py", "--steps", "3", "--warmup", "1", "--streams", "2", "--no-cpu-baseline"]
+    flags = ["bench.py", "--full", "--steps", "3", "--warmup", "1", "--streams", "2", "--no-cpu-baseline"]
     one = _launch(flags + ["--gpus", "1"], 1)
     two = _launch(flags + ["--gpus", "2"], 2)
     for line, n in ((one, 1), (two, 2)):
@@ -96,7 +96,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     data-parallel training steps whose gradient went through the collective on both ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(FRCNN_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--streams", "2", "--no-cpu-baseline", "--no-io"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--streams", "2", "--no-cpu-baseline", "--no-io"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -116,7 +116,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     assert abs(t["img_s"] - 2 * 1e3 / t["ms_per_step"]) < 0.02 * t["img_s"]
     _check_det_leg(t["det_step2"], ranks=2, backend="gloo")
     # --gpus 1 stays a plain single-process run: no train_dp object
-    one = _launch(["bench.py", "--steps", "2", "--warmup", "1", "--streams", "2", "--no-cpu-baseline", "--no-io", "--gpus", "1"], 1)
+    one = _launch(["bench.py", "--full", "--steps", "2", "--warmup", "1", "--streams", "2", "--no-cpu-baseline", "--no-io", "--gpus", "1"], 1)
     assert one["n_gpus"] == 1 and "train_dp" not in one
 
 
@@ -135,7 +135,7 @@ def test_bench_gpus_flag_config_c4_prints_the_same_contract():
     the same line keys, and the same two training legs."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(FRCNN_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--config", "c4", "--steps", "2", "--warmup", "1", "--streams", "1", "--batch", "2",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--config", "c4", "--steps", "2", "--warmup", "1", "--streams", "1", "--batch", "2",
                         "--no-cpu-baseline", "--no-io"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -155,7 +155,7 @@ def test_bench_multi_rank_path_over_real_rccl():
     backend, with one rank on this box's one GPU (FRCNN_BENCH_FORCE_DIST=1): what a node run does per rank, minus the peers."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "FRCNN_BENCH_BACKEND")}
     env.update(FRCNN_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--streams", "2", "--no-cpu-baseline", "--no-io"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--streams", "2", "--no-cpu-baseline", "--no-io"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     out_lines = r.stdout.strip().splitlines()

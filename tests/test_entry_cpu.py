@@ -374,7 +374,9 @@ def test_full_collections_before_captures_are_throttled(monkeypatch):
     from faster_rcnn_amd import pipeline
     calls = []
     monkeypatch.setattr(pipeline._gc, "collect", lambda *a: calls.append(1) or 0)
-    monkeypatch.setattr(pipeline, "_LAST_COLLECT", [0.0])
+    # never collected before (not 0.0: the monotonic clock starts near zero at boot, and a host up for less than the interval would then
+    # have "collected" too recently)
+    monkeypatch.setattr(pipeline, "_LAST_COLLECT", [float("-inf")])
     for _ in range(5):
         pipeline.collect_before_capture(min_interval_s=60.0)
     assert len(calls) == 1
