@@ -17,7 +17,7 @@ class FrcnnError(RuntimeError):
     pass
 
 
-ABI_VERSION = 108       # include/frcnn_hip.h FRCNN_ABI_VERSION (tests/test_abi.py holds the two together)
+ABI_VERSION = 109       # include/frcnn_hip.h FRCNN_ABI_VERSION (tests/test_abi.py holds the two together)
 P = c_void_p
 I = c_int
 # name -> (restype, argtypes).  Must list every symbol include/frcnn_hip.h declares
@@ -141,6 +141,7 @@ SIGNATURES = {
     "frcnn_roi_crop_resize_fwd_bf16_batch": (I, [P, I, I, I, I, P, I, I, P, I, I, P, P]),
     "frcnn_detections": (I, [P, P, I, P, P, I, I, c_double, c_double, c_double, c_double, P, P, P, P, P, P]),
     "frcnn_detections_dyn": (I, [P, P, I, I, P, P, I, I, c_double, c_double, P, P, P, P, P, P, P]),
+    "frcnn_annotate_u8": (I, [P, I, I, P, P, P, P, I, P, P, I, I, P, P]),
 }
 
 

@@ -1,0 +1,266 @@
+"""Mirror of the reference's annotate_video.py (annotate_video.py:15-82): detections drawn on a directory of frames.
+
+``get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max)`` draws into ``frame`` in place and
+returns it; ``annotate_images(...)`` walks ``image_filenames`` of ``input_dir`` and writes each annotated frame to ``out_dir``
+under its own name, printing what the reference prints ("processing <path>", "num rois: N", every drawn det).
+
+What is drawn (annotate_video.py:32-41): every det except classes 'DontCare' / 'Misc' and boxes with x1 < 0, x2 > width,
+y1 < 0 or y2 > height of the ORIGINAL frame; a 3-pixel (0,255,0) box and the label "{} {:6.2f}".format(cls_name, prob) at
+(x1, y2 + 16).  The pixels are this project's rule (ops.annotate_u8): square box corners and a 5x7 bitmap font
+at scale 2 instead of cv2's Hershey strokes -- the same primitives in the same places, not cv2's pixels.
+
+On the captured path the drawing is part of the detection pass: the frame is already on the device, the draw runs after the
+post-process inside the same hipGraph, and the annotated frame comes back with the detections.  ``annotate_images`` decodes
+PNGs ahead on threads, uploads them in the decoder's RGB order (green is (0,255,0) in either order), groups frames of one
+geometry into ``entry.default_batch`` passes with ``entry.default_in_flight`` of them in flight, and writes PNGs on a few
+threads (PIL, compress_level=1) in list order.  PNGs that are not 8-bit RGB (grey, palette, 16-bit, alpha) are read through
+PIL's ``convert("RGB")``; cv2.imread's colour conversion may differ from it for 16-bit files.
+"""
+import os
+import pathlib
+
+import numpy as np
+
+from . import entry, ops, shapes, voc_dets
+from .util import resize_imgs
+
+STRIDE = 16                                       # get_dets' default: annotate_video.py:29 passes none
+DET_THRESHOLD = 0.0                               # annotate_video.py:30
+DECODE_THREADS = int(os.environ.get("FRCNN_ANNOTATE_DECODE_THREADS", "4"))
+# PNG writers: PIL releases the interpreter lock while it encodes; KITTI frames (44 ms each on one thread) run at 78 frames/s on four
+# writers and 125 on eight (scripts/bench_annotate.py)
+WRITE_THREADS = int(os.environ.get("FRCNN_ANNOTATE_WRITE_THREADS", "8"))
+PNG_COMPRESS_LEVEL = 1
+
+
+def drawn(det, width, height):
+    """The reference's filter (annotate_video.py:33-38): is this det drawn on a frame of (width, height)?"""
+    if det["cls_name"] in ops.ANNOTATE_SKIP:
+        return False
+    x1, y1, x2, y2 = det["bbox"]
+    return not (x1 < 0 or x2 > width or y1 < 0 or y2 > height)
+
+
+def png_filenames(input_dir):
+    """annotate_video.py:69: the ``*.png`` names of ``input_dir``, sorted."""
+    return sorted(f for f in os.listdir(input_dir) if f.endswith(".png"))
+
+
+def _engine(training_manager, detector, in_flight):
+    if not voc_dets.FAST_ENTRY:
+        return None
+    eng = entry.for_models(training_manager, detector, 64, STRIDE, in_flight=in_flight)
+    return eng if eng is not None and eng.device_preprocess else None
+
+
+def _pack_dets(dets, class_mapping):
+    """Host dets -> the post-process's packed layout (ops.split_detections), for an eager draw."""
+    rows = max(1, len(dets))
+    packed = np.zeros(4 + 7 * rows, dtype=np.int32)
+    packed[0] = len(dets)
+    for k, d in enumerate(dets):
+        packed[4 + 4 * k:8 + 4 * k] = np.asarray(d["bbox"], dtype=np.int64).astype(np.int32)
+        packed[4 + 4 * rows + k] = class_mapping[d["cls_name"]]
+        packed[4 + 5 * rows + k] = np.float32(d["prob"]).view(np.int32)
+    return packed
+
+
+_EAGER_TABLES = {}
+
+
+def draw_eager(frame, dets, class_mapping):
+    """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place."""
+    import torch
+    key = tuple(sorted(class_mapping.items()))
+    tables = _EAGER_TABLES.get(key)
+    if tables is None:
+        rev = {v: k for k, v in class_mapping.items()}
+        tables = _EAGER_TABLES[key] = ops.annotate_tables([rev.get(i, "") for i in range(max(rev) + 1)])
+    if dets:                                              # (nothing to draw: the frame stays as it is)
+        dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
+        ops.annotate_u8(dev, torch.from_numpy(_pack_dets(dets, class_mapping)).cuda(), tables)
+        frame[...] = dev.cpu().numpy()
+    return frame
+
+
+def _print_drawn(dets, width, height):
+    for det in dets:
+        if drawn(det, width, height):
+            print(det)
+
+
+def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max):
+    """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it."""
+    resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
+    eng = _engine(training_manager, detector, 1)
+    if eng is not None:
+        pixels = eng.host_pixels(resized_imgs[0])
+        num_rois, dets, out = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], DET_THRESHOLD, [pixels],
+                                                                 batch=1, annotate=True))[0]
+        print("num rois: {}".format(num_rois))
+        frame[...] = out
+    else:
+        dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=DET_THRESHOLD)
+        draw_eager(frame, dets, training_manager.class_mapping)
+    _print_drawn(dets, img.width, img.height)
+    return frame
+
+
+def _read_rgb(path):
+    from PIL import Image as PilImage
+    with PilImage.open(path) as im:
+        if im.mode != "RGB":
+            im = im.convert("RGB")
+        return np.asarray(im)
+
+
+def _write_png(path, rgb):
+    from PIL import Image as PilImage
+    PilImage.fromarray(rgb).save(path, compress_level=PNG_COMPRESS_LEVEL)
+
+
+class _Frame:
+    """A file-backed frame decoded ahead of time: the reference's InMemoryImage (width, height, resize) whose pixels are
+    uploaded in the decoder's RGB order (entry.DetectionEntry.host_pixels: the device resize swaps channels to BGR)."""
+
+    def __init__(self, rgb, width=None, height=None):
+        self.rgb = rgb
+        self.height = int(rgb.shape[0]) if height is None else height
+        self.width = int(rgb.shape[1]) if width is None else width
+
+    raw = property(lambda s: s.rgb[:, :, ::-1])
+    raw_rgb = property(lambda s: s.rgb)
+
+    def resize(self, scale_ratio):
+        return _Frame(self.rgb, int(round(scale_ratio * self.width)), int(round(scale_ratio * self.height)))
+
+    def resize_within_bounds(self, min_size, max_size):
+        ratio = shapes._bounds_ratio(self.width, self.height, min_size, max_size)
+        return self.resize(ratio), ratio
+
+
+def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max):
+    """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop."""
+    from concurrent.futures import ThreadPoolExecutor
+    paths = [os.path.join(input_dir, f) for f in image_filenames]
+    dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
+    eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
+    pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
+    if eng is None:                                       # eager path / foreign models: the reference's loop
+        for name, path in zip(image_filenames, paths):
+            print("processing {}".format(path))
+            frame = np.ascontiguousarray(_read_rgb(path)[:, :, ::-1])
+            img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
+            _write_png(os.path.join(out_dir, name), get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max)[:, :, ::-1])
+        return
+
+    def load(path):                                       # (decode thread) -> (frame, resized, ratio, pixels)
+        frame = _Frame(_read_rgb(path))
+        resized, ratio = frame.resize_within_bounds(resize_min, resize_max)
+        return frame, resized, ratio, eng.host_pixels(resized)
+
+    n, B = len(paths), eng.batch
+    decode = ThreadPoolExecutor(max_workers=max(1, DECODE_THREADS))
+    write = ThreadPoolExecutor(max_workers=max(1, WRITE_THREADS))
+    ahead = 2 * eng.in_flight * B
+    pending, writes, window = {}, [], []
+
+    def finish():
+        part, ticket = window[0]
+        try:
+            results = eng.collect_batch(ticket)
+        finally:
+            window.pop(0)
+        for (pos, frame), (num_rois, dets, out) in zip(part, results):
+            print("processing {}".format(paths[pos]))
+            print("num rois: {}".format(num_rois))
+            _print_drawn(dets, frame.width, frame.height)
+            writes.append(write.submit(_write_png, os.path.join(out_dir, image_filenames[pos]), out))
+        while len(writes) > 4 * WRITE_THREADS:            # (bounded: encoded frames must not pile up in memory)
+            writes.pop(0).result()
+
+    def submit(group):
+        """<= B frames of one geometry: one pass of B (padded) when they fill at least half of it (as get_dets_by_cls), else
+        one-frame passes."""
+        parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
+        for part, take in parts:
+            ticket = eng.submit_batch([g[2] for g in part], [g[3] for g in part], DET_THRESHOLD, [g[4] for g in part],
+                                      batch=take, annotate=True)
+            window.append(([(g[0], g[1]) for g in part], ticket))
+            if len(window) >= eng.in_flight:
+                finish()
+
+    try:
+        group, key = [], None
+        for i in range(n):
+            for j in range(i, min(n, i + ahead)):
+                if j not in pending:
+                    pending[j] = decode.submit(load, paths[j])
+            frame, resized, ratio, pixels = pending.pop(i).result()
+            k = eng.geometry_of(pixels)
+            if group and (k != key or len(group) == B):
+                submit(group)
+                group = []
+            group.append((i, frame, resized, ratio, pixels))
+            key = k
+        if group:
+            submit(group)
+        while window:
+            finish()
+        for f in writes:
+            f.result()
+    finally:
+        decode.shutdown(wait=True, cancel_futures=True)
+        for _, ticket in window:                          # an exception mid-list: no slot stays marked busy
+            ticket.slot.event.synchronize()
+            ticket.slot.busy = False
+        write.shutdown(wait=True)
+
+
+def build_parser():
+    """The reference's command line (annotate_video.py:48-64) plus voc_dets' --network / --anchor_scales: a weights file does not
+    carry the architecture."""
+    import argparse
+    p = argparse.ArgumentParser(description="Draw the detector's boxes and labels on a directory of PNG frames")
+    p.add_argument("step3_model_path", metavar="step3_model_path", type=str,
+                   help="weights of the RPN trained in step 3 (Keras .h5 or this package's .npz)")
+    p.add_argument("step4_model_path", metavar="step4_model_path", type=str,
+                   help="weights of the detector from step 4 (must be compatible with the RPN)")
+    p.add_argument("input_dir", type=str, help="directory of the video's frames as *.png")
+    p.add_argument("--kitti", dest="kitti", action="store_true", help="KITTI classes instead of Pascal VOC")
+    p.add_argument("--resize_dims", dest="resize_dims", default="600,1000",
+                   help="resize parameters, e.g. 600,1000 for a min size of 600 pixels and a max of 1000")
+    p.add_argument("--out_dir", dest="out_dir", default=".", help="where the annotated frames are written")
+    p.add_argument("--network", dest="network", choices=("vgg16", "resnet50", "resnet101"), default="resnet50")
+    p.add_argument("--anchor_scales", dest="anchor_scales", default="128,256,512")
+    return p
+
+
+def main(argv=None):
+    """annotate_video.py:47-82: load the two models, annotate every PNG of input_dir into out_dir."""
+    from . import resnet, vgg
+    from .args_util import anchor_scales_from_str, resize_dims_from_str
+    from .data.voc_data_helpers import KITTI_CLASS_MAPPING, VOC_CLASS_MAPPING
+    from .det_util import DetTrainingManager
+    from .util import get_anchors
+    args = build_parser().parse_args(argv)
+    os.environ.setdefault("GPU_MAX_HW_QUEUES", voc_dets.ENTRY_HW_QUEUES)      # (as voc_dets.main: passes in flight want > 4 queues)
+    class_mapping = KITTI_CLASS_MAPPING if args.kitti else VOC_CLASS_MAPPING
+    anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
+    if args.network == "vgg16":
+        rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors))
+        detector = vgg.det_from_h5(args.step4_model_path, num_classes=len(class_mapping))
+        preprocess = vgg.preprocess
+    else:
+        depth = 50 if args.network == "resnet50" else 101
+        rpn = resnet.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), depth=depth)
+        detector = resnet.det_from_h5(args.step4_model_path, num_classes=len(class_mapping), depth=depth)
+        preprocess = resnet.preprocess
+    manager = DetTrainingManager(rpn_model=rpn, class_mapping=class_mapping, preprocess_func=preprocess, anchor_dims=anchors)
+    resize_min, resize_max = resize_dims_from_str(args.resize_dims)
+    annotate_images(training_manager=manager, detector=detector, input_dir=args.input_dir, out_dir=args.out_dir,
+                    image_filenames=png_filenames(args.input_dir), resize_min=resize_min, resize_max=resize_max)
+
+
+if __name__ == "__main__":
+    main()

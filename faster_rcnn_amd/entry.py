@@ -208,7 +208,8 @@ def _capture_stream():
 class _Slot:
     """One captured pass for one image size, with its staging on both sides of PCIe."""
     __slots__ = ("key", "pipe", "graph", "out", "io_dev", "io_pin", "pix_host", "dyn_host", "out_pin", "event", "busy", "nbytes",
-                 "x_f32", "ws", "seq", "tabs", "u8_resized", "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw")
+                 "x_f32", "ws", "seq", "tabs", "u8_resized", "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw",
+                 "annotate", "frame_io")
 
 
 def _close_slot(s):
@@ -227,7 +228,7 @@ def _close_slot(s):
         piece = getattr(s, name, None)
         if piece is not None:
             _PinnedArena.give_back(piece)
-    for name in ("graph", "out", "out_packed", "io_dev", "x_f32", "u8_resized", "tabs", "ws", "amax", "pipe", "io_pin", "_out_raw", "out_pin", "pix_hosts", "pix_host", "dyn_host", "extents", "_ext_raw"):
+    for name in ("graph", "out", "out_packed", "io_dev", "x_f32", "u8_resized", "tabs", "ws", "amax", "pipe", "io_pin", "_out_raw", "out_pin", "pix_hosts", "pix_host", "dyn_host", "extents", "_ext_raw", "frame_io"):
         setattr(s, name, None)
 
 
@@ -344,6 +345,14 @@ class DetectionEntry:
         self._taps_dev = {}
         self._pinned = _PinnedArena()                    # (per engine: the blocks go when the engine goes)
         self.capture_breakdown = {}
+        self._annotate_tables = None
+
+    def annotate_tables(self):
+        """The drawing tables of ops.annotate_u8 for this engine's classes (uploaded once)."""
+        if self._annotate_tables is None:
+            rev = self.rev_class_mapping
+            self._annotate_tables = ops.annotate_tables([rev.get(i, "") for i in range(max(rev) + 1)])
+        return self._annotate_tables
 
     # ------------------------------------------------------------------ eligibility
     @staticmethod
@@ -357,10 +366,11 @@ class DetectionEntry:
         return 0 < n_rows <= 512                        # frcnn_detections: one workgroup, <= 512 scored rows
 
     # ------------------------------------------------------------------ capture
-    def _capture(self, H, W, src=None, flip=False, B=1):
+    def _capture(self, H, W, src=None, flip=False, B=1, annotate=False):
         """``src`` = (source height, source width): the pass starts from the decoded frame at the file's size and resizes
         (and flips) it on the device; None: the uploaded pixels are already (H, W).  ``B`` > 1: one pass over B frames of that
-        geometry (pipeline.BatchedInferencePipeline), each with its own [resize_ratio, det_threshold] pair."""
+        geometry (pipeline.BatchedInferencePipeline), each with its own [resize_ratio, det_threshold] pair.  ``annotate``: the
+        pass then draws each frame's detections into its uploaded source frame (ops.annotate_u8, annotate_video.py)."""
         import gc
         import time
         t0 = time.perf_counter()
@@ -372,7 +382,7 @@ class DetectionEntry:
         collect_before_capture()                                    # (at most one full collection per second: it costs more than the capture)
         gc.disable()
         try:
-            return self._capture_locked(H, W, src, flip, B, t0)
+            return self._capture_locked(H, W, src, flip, B, t0, annotate)
         finally:
             if gc_was_on:
                 gc.enable()
@@ -511,7 +521,7 @@ class DetectionEntry:
         s.busy = True
         return Ticket(s, list(images))
 
-    def _capture_locked(self, H, W, src, flip, B, t0):
+    def _capture_locked(self, H, W, src, flip, B, t0, annotate=False):
         import time
         m = self.manager
         kw = dict(stride=self.stride, pre_nms_top_n=PRE_NMS_TOP_N, max_proposals=MAX_PROPOSALS, roi_batch=self.num_rois, pad_to_batch=PAD_TO_BATCH,
@@ -529,7 +539,7 @@ class DetectionEntry:
         seg = (pix_bytes + 15) // 16 * 16                           # one frame's segment of the staging buffer
         off = B * seg                                               # ... then B x [resize_ratio, det_threshold]
         s = _Slot()
-        s.key, s.pipe, s.busy, s.seq, s.batch = (H, W), pipe, False, 0, B
+        s.key, s.pipe, s.busy, s.seq, s.batch, s.annotate = (H, W), pipe, False, 0, B, annotate
         s.io_dev = torch.zeros(off + 16 * B, dtype=torch.uint8, device="cuda")
         s.io_pin = self._pinned.take(off + 16 * B, zero=True)
         host = s.io_pin.numpy()
@@ -550,8 +560,11 @@ class DetectionEntry:
                 s.tabs = (torch.from_numpy(ops.resize_cubic_taps(W, in_w)).cuda(), torch.from_numpy(ops.resize_cubic_taps(H, in_h)).cuda())
                 s.u8_resized = torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
         else:
-            assert B == 1
+            assert B == 1 and not annotate
             s.x_f32 = s.io_dev[:pix_bytes].view(torch.float32).view(1, H, W, 3)
+        # annotating pass: frame i is read back from its staging segment into the slot's own pinned segment after the replay
+        s.frame_io = [(s.io_dev[i * seg:i * seg + npix], s.io_pin[i * seg:i * seg + npix]) for i in range(B)] if annotate else None
+        tables = self.annotate_tables() if annotate else None
 
         def run():
             if self.device_preprocess:
@@ -560,7 +573,12 @@ class DetectionEntry:
                     if src is not None:                             # shapes.Image.data: INTER_CUBIC resize (+ flip) of the decoded frame
                         frame = ops.resize_cubic_u8(u8[i], H, W, flip=flip, tabs=s.tabs, out=s.u8_resized)
                     ops.preprocess_u8(frame, MEAN_BGR, out=s.x_f32[i:i + 1])     # resnet.preprocess + the f32 feed cast, bit for bit
-            return pipe.forward_dev(s.x_f32, dyn=dyn_dev if B > 1 else dyn_dev[0])
+            res = pipe.forward_dev(s.x_f32, dyn=dyn_dev if B > 1 else dyn_dev[0])
+            if annotate:                                            # the detections drawn into the source frame (its only reader is done)
+                packed = res["det_packed"]
+                for i in range(B):
+                    ops.annotate_u8(u8[i], packed[i] if B > 1 else packed, tables)
+            return res
 
         shared = self.in_flight > 1
         # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -760,18 +778,28 @@ class DetectionEntry:
         """``pixels``: the result of ``host_pixels(image)`` when the caller fetched it ahead of time."""
         return self.submit_batch([image], [resize_ratio], det_threshold, [self.host_pixels(image) if pixels is None else pixels], batch=1)
 
-    def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None):
+    def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
-        copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order."""
+        copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
+        ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
+        uploaded frame and reads the frame back; ``collect_batch`` then returns (num_rois, dets, frame)."""
         self._check_epoch()
         B = self.batch if batch is None else batch
         assert 1 <= len(images) <= B and len(images) == len(pixels) == len(resize_ratios)
         _, H, W, src, flip = pixels[0]
-        key = self.geometry(pixels[0])
-        assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
-        if key[0] == "canvas":
-            return self._submit_canvas(images, resize_ratios, det_threshold, pixels, B)
-        s = self.cache.acquire(key + ((B,) if B > 1 else ()), lambda: self._capture(H, W, src, flip, B))
+        if annotate:
+            if not self.device_preprocess:
+                raise FrcnnError("annotating passes need the device-side preprocess (a foreign preprocess_func uploads float pixels)")
+            key = self.geometry_of(pixels[0])
+            assert all(self.geometry_of(p) == key for p in pixels), "one pass, one geometry"
+            key = key + ((B,) if B > 1 else ()) + ("annotate",)
+        else:
+            key = self.geometry(pixels[0])
+            assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
+            if key[0] == "canvas":
+                return self._submit_canvas(images, resize_ratios, det_threshold, pixels, B)
+            key = key + ((B,) if B > 1 else ())
+        s = self.cache.acquire(key, lambda: self._capture(H, W, src, flip, B, annotate))
         for i in range(B):
             j = i if i < len(images) else 0
             np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
@@ -786,12 +814,15 @@ class DetectionEntry:
             s.graph.replay()
             for i in range(len(images)):
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
+                if s.annotate:
+                    s.frame_io[i][1].copy_(s.frame_io[i][0], non_blocking=True)
             s.event.record(st)
         s.busy = True
         return Ticket(s, list(images))
 
     def collect_batch(self, ticket):
-        """-> [(num_rois, dets)] for the images of a ``submit_batch`` ticket."""
+        """-> [(num_rois, dets)] for the images of a ``submit_batch`` ticket; [(num_rois, dets, frame)] for an annotating one, ``frame``
+        the annotated source frame (uint8 (h, w, 3), in the channel order it was uploaded in)."""
         s = ticket.slot
         try:
             s.event.synchronize()
@@ -808,7 +839,8 @@ class DetectionEntry:
                 bbox = packed[4:4 + 4 * nd].reshape(nd, 4).astype(np.int64)
                 cls = packed[4 + 4 * rows:4 + 4 * rows + nd].copy()
                 prob = packed[4 + 5 * rows:4 + 5 * rows + nd].view(np.float32).copy()
-                res.append((n_rois, [{"bbox": bbox[k], "cls_name": rev[int(cls[k])], "prob": prob[k]} for k in range(nd)]))
+                dets = [{"bbox": bbox[k], "cls_name": rev[int(cls[k])], "prob": prob[k]} for k in range(nd)]
+                res.append((n_rois, dets, s.pix_hosts[i].copy()) if getattr(s, "annotate", False) else (n_rois, dets))
             return res
         finally:
             s.busy = False                               # whatever happened while decoding the records: the slot is free again

@@ -1021,6 +1021,44 @@ def detections_dyn(rois, n_rois, out_cls, out_reg, roi_batch, bg_idx, stride, dy
     return {"det_cls": det_cls, "det_prob": det_prob, "det_bbox": det_bbox, "det_roi": det_roi, "n_dets": n_dets, "det_packed": packed}
 
 
+# ----------------------------------------------------------------------------- annotation
+ANNOTATE_SKIP = ("DontCare", "Misc")            # classes the reference's annotate_video.py:33-34 never draws
+ANNOTATE_LABEL_STRIDE = 32                      # bytes per class name in the label table (NUL included)
+
+
+def annotate_tables(class_names, skip=ANNOTATE_SKIP):
+    """The device tables ``annotate_u8`` reads, built once per class list: ``class_names[i]`` is the name of class index i.
+    -> {"drawable": u8 [C], "labels": u8 [C][ANNOTATE_LABEL_STRIDE] NUL-terminated ASCII, "glyphs": u8 [95][7]}."""
+    from .annotate_font import GLYPHS
+    _require_gpu()
+    names = list(class_names)
+    labels = np.zeros((len(names), ANNOTATE_LABEL_STRIDE), dtype=np.uint8)
+    for i, name in enumerate(names):
+        raw = str(name).encode("ascii", "replace")
+        if len(raw) >= ANNOTATE_LABEL_STRIDE:
+            raise ValueError("class name %r longer than %d bytes" % (name, ANNOTATE_LABEL_STRIDE - 1))
+        labels[i, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+    drawable = np.array([name not in skip for name in names], dtype=np.uint8)
+    return {"drawable": torch.from_numpy(drawable).cuda(), "labels": torch.from_numpy(labels).cuda(),
+            "glyphs": torch.from_numpy(np.ascontiguousarray(GLYPHS)).cuda()}
+
+
+def annotate_u8(frame, det_packed, tables):
+    """Draw the detections of ``det_packed`` (the post-process's packed buffer, device) into ``frame`` -- an (h, w, 3) uint8 device
+    tensor, edited in place -- as the reference's annotate_video.py:32-41 does: a 3-pixel (0,255,0) box and the label
+    "{} {:6.2f}" under it (frcnn_annotate_u8; the drawing rule is DESIGN §8's).  ``tables``: ``annotate_tables``.  Reads
+    n_dets from device memory: the call can be captured in a graph."""
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.is_contiguous()
+    n_dets, det_bbox, det_cls, det_prob, _ = split_detections(det_packed)
+    labels = tables["labels"]
+    _lib.call("frcnn_annotate_u8", _p(frame), int(frame.shape[0]), int(frame.shape[1]), _p(det_bbox), _p(det_cls), _p(det_prob),
+              _p(n_dets), int(det_cls.numel()), _p(tables["drawable"]), _p(labels), int(labels.shape[1]), int(labels.shape[0]),
+              _p(tables["glyphs"]), _stream())
+    return frame
+
+
 def split_detections(packed, rows=None):
     """Views (n_dets, det_bbox, det_cls, det_prob, det_roi) into a `det_packed` buffer (device tensor or its host copy)."""
     rows = (packed.numel() - 4) // 7 if rows is None else rows

@@ -48,7 +48,7 @@ const char* frcnn_last_error(void);
  * 108 = frcnn_pool2d_fwd_planes (addition only).
  * 104 = the f16x3 engine's fences: frcnn_h3_planes.status (a THIRD field: recompile hosts that pass the struct), status word in a
  *       magnitude record, frcnn_amax_status. */
-#define FRCNN_ABI_VERSION 108
+#define FRCNN_ABI_VERSION 109
 int frcnn_version(void);
 /* number of HIP devices visible; does not initialise a context */
 int frcnn_device_count(void);
@@ -560,6 +560,19 @@ int frcnn_detections(const float* rois, const int32_t* n_rois, int max_rows, con
 int frcnn_detections_dyn(const float* rois, const int32_t* n_rois, int roi_batch, int max_rows, const float* out_cls, const float* out_reg,
                          int num_classes, int bg_idx, double stride, double nms_thresh, const double* dyn,
                          int32_t* det_cls, float* det_prob, int32_t* det_bbox, int32_t* det_roi, int32_t* counts, void* stream);
+
+/* Detections drawn into a frame (the reference's annotate_video.py:32-41, cv2.rectangle + cv2.putText in (0,255,0)), in place:
+ * frame [height][width][3] uint8 (any channel order: (0,255,0) reads the same in BGR and RGB), det_bbox / det_cls / det_prob /
+ * *n_dets as frcnn_detections(_dyn) writes them (rows >= *n_dets and rows >= max_rows are not read; max_rows <= 512).  A row is
+ * drawn unless drawable[cls] == 0 (the script skips 'DontCare' and 'Misc') or x1 < 0, x2 > width, y1 < 0, y2 > height.  Box:
+ * every frame pixel within 1 of an edge of the corner-normalised rectangle (thickness 3, square corners).  Label: labels
+ * [num_classes][label_stride] NUL-terminated names, text "{} {:6.2f}".format(name, prob) formatted on the device, glyphs [95][7]
+ * a 5x7 bitmap font for 0x20..0x7E (row bytes, bit 4 = the leftmost column; other bytes draw '?'), scale 2, advance 12, set bit
+ * (c, r) of character k painting [x1 + 12k + 2c, +1] x [y2 + 3 + 2r, +1].  Everything is clipped to the frame.  One workgroup per
+ * row, plain byte stores: no atomics, no workspace, no synchronisation; can be captured in a graph. */
+int frcnn_annotate_u8(uint8_t* frame, int height, int width, const int32_t* det_bbox, const int32_t* det_cls, const float* det_prob,
+                      const int32_t* n_dets, int max_rows, const uint8_t* drawable, const char* labels, int label_stride,
+                      int num_classes, const uint8_t* glyphs, void* stream);
 
 /* ------------------------------------------------------------------ training: losses, optimisers */
 /* The reference's four Keras loss functions (loss_functions.py:15-76) as Keras 2.0.8 evaluates them

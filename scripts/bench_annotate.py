@@ -1,0 +1,137 @@
+"""Frames/s of the annotating passes (annotate_video.py) against detection alone, on two model / frame-size pairs:
+
+  kitti_r101_bf16: ResNet-101, bf16, KITTI classes, 375x1242 frames at --resize_dims 600,1500 (BASELINE configs[3])
+  voc_r50_f32:     ResNet-50, fp32, VOC classes, 375x500 frames at 600,1000
+
+per pair (a) voc_dets.get_dets_by_cls over N in-memory frames, (b) the same frames through annotating passes (detections + the
+frame drawn and read back), (c) annotate_video.annotate_images from PNG files to PNG files, with the host's PNG decode and encode
+per frame timed on their own (one thread).  Synthetic weights, dense_class calibrated so that many classes fire.  Prints one
+JSON line.
+
+    python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32]
+"""
+import argparse
+import contextlib
+import io
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")          # as voc_dets.main / annotate_video.main (read when the runtime starts)
+
+PAIRS = {
+    "kitti_r101_bf16": dict(depth=101, dtype="bf16", kitti=True, anchors=(16, 32, 64, 128, 256, 512), hw=(375, 1242), resize=(600, 1500)),
+    "voc_r50_f32": dict(depth=50, dtype="f32", kitti=False, anchors=(128, 256, 512), hw=(375, 500), resize=(600, 1000)),
+}
+
+
+def build(cfg):
+    import numpy as np
+    import torch
+    from faster_rcnn_amd import resnet, util
+    from faster_rcnn_amd.data.voc_data_helpers import KITTI_CLASS_MAPPING, VOC_CLASS_MAPPING
+    from faster_rcnn_amd.det_util import DetTrainingManager
+    from faster_rcnn_amd.pipeline import InferencePipeline
+    from faster_rcnn_amd.weights import calibrate_classifier, synthetic_resnet
+    mapping = KITTI_CLASS_MAPPING if cfg["kitti"] else VOC_CLASS_MAPPING
+    C = len(mapping)
+    anchors = util.get_anchors(list(cfg["anchors"]))
+    dtype = cfg["dtype"] if cfg["dtype"] == "bf16" else None
+    kw = {"dtype": dtype} if dtype else {}
+    w = synthetic_resnet(cfg["depth"], anchors_per_loc=len(anchors), num_classes=C, seed=1)
+    base = (resnet.resnet50_base if cfg["depth"] == 50 else resnet.resnet101_base)(weights=w, **kw)
+    rpn = (resnet.resnet50_rpn if cfg["depth"] == 50 else resnet.resnet101_rpn)(base, include_conv=True, anchors_per_loc=len(anchors))
+    det = (resnet.resnet50_classifier if cfg["depth"] == 50 else resnet.resnet101_classifier)(64, C, weights=w, **kw)
+    x = resnet.preprocess(np.random.RandomState(99).randint(0, 256, (320, 480, 3)).astype(np.uint8))[None].astype(np.float32)
+    out = InferencePipeline(rpn, det, anchors).forward_dev(torch.from_numpy(x).cuda())
+    n = int(out["n_rois"].item())
+    det.get_layer("dense_class_%d" % C).set_weights(calibrate_classifier(w, C, out["cls"][:n].float().cpu().numpy()))
+    mgr = DetTrainingManager(rpn_model=rpn, class_mapping=mapping, preprocess_func=resnet.preprocess, anchor_dims=anchors)
+    return mgr, det
+
+
+def annotate_in_memory(eng, resized, ratios):
+    """(b): the frames through annotating passes, eng.batch per pass, eng.in_flight passes in flight (annotate_images' loop
+    without the files)."""
+    B, window, frames = eng.batch, [], []
+    for i in range(0, len(resized), B):
+        part = resized[i:i + B]
+        window.append(eng.submit_batch(part, ratios[i:i + B], 0.0, [eng.host_pixels(r) for r in part], batch=B, annotate=True))
+        if len(window) >= eng.in_flight:
+            frames += [r[2] for r in eng.collect_batch(window.pop(0))]
+    while window:
+        frames += [r[2] for r in eng.collect_batch(window.pop(0))]
+    return frames
+
+
+def run_pair(name, cfg, n_frames, reps):
+    import numpy as np
+    from PIL import Image as PilImage
+    from faster_rcnn_amd import annotate_video, entry, shapes, util, voc_dets
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+
+    def timed(fn):
+        with contextlib.redirect_stdout(io.StringIO()):
+            fn()                                                    # warm-up: captures
+            ts = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                fn()
+                ts.append(time.perf_counter() - t0)
+        return statistics.median(ts), ts
+
+    ta, tas = timed(lambda: voc_dets.get_dets_by_cls(mgr, det, ratios, resized, det_threshold=0.0))
+    tb, tbs = timed(lambda: annotate_in_memory(eng, resized, ratios))
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"],
+           "images_per_pass": eng.batch, "in_flight": eng.in_flight,
+           "a_get_dets_by_cls_fps": round(n_frames / ta, 1), "b_annotate_fps": round(n_frames / tb, 1),
+           "b_over_a": round(ta / tb, 3), "a_runs_s": [round(t, 4) for t in tas], "b_runs_s": [round(t, 4) for t in tbs]}
+    with tempfile.TemporaryDirectory() as tmp:
+        d_in, d_out = os.path.join(tmp, "in"), os.path.join(tmp, "out")
+        os.makedirs(d_in)
+        names = ["%06d.png" % i for i in range(n_frames)]
+        for nm, s in zip(names, srcs):
+            PilImage.fromarray(s[:, :, ::-1]).save(os.path.join(d_in, nm), compress_level=1)
+        tc, tcs = timed(lambda: annotate_video.annotate_images(mgr, det, d_in, d_out, names, cfg["resize"][0], cfg["resize"][1]))
+        k = min(32, n_frames)
+        t0 = time.perf_counter()
+        decoded = [annotate_video._read_rgb(os.path.join(d_in, nm)) for nm in names[:k]]
+        t_dec = (time.perf_counter() - t0) / k
+        t0 = time.perf_counter()
+        for nm, f in zip(names[:k], decoded):
+            annotate_video._write_png(os.path.join(tmp, "enc_" + nm), f)
+        t_enc = (time.perf_counter() - t0) / k
+    res.update({"c_annotate_images_fps": round(n_frames / tc, 1), "c_runs_s": [round(t, 4) for t in tcs],
+                "c_png_decode_ms_per_frame_1thread": round(t_dec * 1e3, 2), "c_png_encode_ms_per_frame_1thread": round(t_enc * 1e3, 2),
+                "c_decode_threads": annotate_video.DECODE_THREADS, "c_write_threads": annotate_video.WRITE_THREADS})
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--frames", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--pairs", default=",".join(PAIRS))
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_annotate.py needs a GPU")
+    out = {"metric": "annotate_frames_per_s", "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
+    for name in args.pairs.split(","):
+        out[name] = run_pair(name, PAIRS[name], args.frames, args.reps)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
