@@ -851,10 +851,10 @@ __global__ void k_pack_hwio_bf16(const float* w, int RS, int Cin, int Cout, int 
 }
 
 // Post-optimiser-step refresh of the bf16 device forms of MANY trainable layers in one launch (the bf16 twin of
-// conv_igemm.hip's k_refresh_packed): forward pack, input-gradient pack (transposed, flipped, scale folded) and the
+// conv_wgrad.hip's k_refresh_packed): forward pack, input-gradient pack (transposed, flipped, scale folded) and the
 // folded epilogue shift.  packed / packed_dgrad of frcnn_pack_job point at bf16 storage here.
 constexpr int REFRESH_JOBS_B = 32;
-struct RefreshTableB { frcnn_pack_job job[REFRESH_JOBS_B]; int first_block[REFRESH_JOBS_B + 1]; int n; };   // workgroups in proportion to job size (conv_igemm.hip)
+struct RefreshTableB { frcnn_pack_job job[REFRESH_JOBS_B]; int first_block[REFRESH_JOBS_B + 1]; int n; };   // workgroups in proportion to job size (conv_wgrad.hip)
 static int refresh_blocks_b(const frcnn_pack_job& j) {
     const long long elems = (long long)j.kh * j.kw * j.cin * j.cout;
     long long g = (elems + 8191) / 8192;
@@ -1103,7 +1103,7 @@ static int launch_bf16_splitk(const ConvArgsBf16& a, hipStream_t s) {
     return check_launch("conv2d_fwd_bf16 (split-K)");
 }
 
-// K-slices per tile for the 64x64 bf16 kernel: same policy as the f32 engine (conv_igemm.hip choose_splits)
+// K-slices per tile for the 64x64 bf16 kernel: same policy as the f32 engine (conv_policy.hip choose_splits)
 // the row-strip GEMM form (k_gemm_strip_bf16): eligibility of a descriptor, and the strip height it takes
 static int strip_rows_bf16(const frcnn_conv_desc* d, bool has_mask, int y_is_f32) {
     if (has_mask || y_is_f32 || d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad_top || d->pad_left) return 0;

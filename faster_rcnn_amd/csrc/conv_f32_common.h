@@ -1,7 +1,7 @@
 // Device-side pieces shared by the f32 convolution engines of libfrcnn_hip.so (gfx950): the launch argument block, the
 // XCD-aware tile map, the fused epilogues (4-byte "lane owns a column" form and the 16-byte row-piece form) and the
-// scheduling-group constants.  Included by conv_igemm.hip (v_mfma_f32_32x32x2_f32 main loops) and conv_x6.hip (the
-// same GEMM on the bf16 matrix cores by exact three-way operand splitting).
+// scheduling-group constants and the filter packing.  Included by conv_igemm.hip (v_mfma_f32_32x32x2_f32 main loops), conv_x6.hip /
+// conv_h3.hip (the same GEMM on the bf16 / fp16 matrix cores by operand splitting) and conv_wgrad.hip.
 #pragma once
 #include "common.h"
 #include <stdlib.h>
@@ -425,6 +425,27 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
     }
 }
 
+
+// ------------------------------------------------------------------------------------
+// filter packing: Keras HWIO [R][S][Cin][Cout] -> [Cout][Kpad].
+//   Cin % 32 == 0 : packed k = ((c/32)*R*S + tap)*32 + c%32   (channel chunk outer, tap inner)
+//   Cin == 3      : packed k = tap*4 + c, c == 3 and taps >= R*S zero (the stem kernel stages eight taps per chunk)
+//   otherwise     : packed k = tap*Cin + c, zero padded to Kpad  (small-Cin path decodes k itself)
+__host__ __device__ __forceinline__ int packed_k(int RS, int Cin) {
+    return ((Cin == 3 ? RS * 4 : RS * Cin) + BK - 1) / BK * BK;
+}
+__device__ __forceinline__ float pack_hwio_elem(const float* w, int RS, int Cin, int Cout, int Kpad, size_t i) {
+    const int k = (int)(i % Kpad), n = (int)(i / Kpad);
+    if ((Cin % BK) == 0) {
+        const int j = k % BK, kc = k / BK, tap = kc % RS, cc = kc / RS;
+        return w[((size_t)tap * Cin + cc * BK + j) * Cout + n];
+    }
+    if (Cin == 3) {
+        const int tap = k >> 2, c = k & 3;
+        return (c < 3 && tap < RS) ? w[((size_t)tap * 3 + c) * Cout + n] : 0.0f;
+    }
+    return k < RS * Cin ? w[(size_t)k * Cout + n] : 0.0f;
+}
 
 // conv_x6.hip: the same GEMM on the bf16 matrix cores (exact three-way operand split); `a.w` = the three filter planes
 int launch_conv_x6(const ConvArgs& a, int cfg, hipStream_t s);

@@ -523,18 +523,18 @@ def _split_engine(d, pc, tile):
     same choices; memoised on the cached descriptor."""
     key = ("engine", F32_ENGINE, _CONV_WS is not NO_SPLIT_K)
     memo = getattr(d, "_ws", None)
-    if memo is not None and d.tile == tile and d.cout == pc.cout and d.cin == pc.cin:
-        got = memo.get(key)
-        if got is None:
-            got = memo[key] = _lib.load().frcnn_conv2d_engine(ctypes.byref(d), _ENGINE_CODE[F32_ENGINE], 1 if key[2] else 0)
-            if got < 0:
-                _lib.check(got, "frcnn_conv2d_engine")
-    else:
-        q = _lib.ConvDesc.from_buffer_copy(d)                 # (a caller asking about another tile code / filter than the descriptor's)
-        q.tile, q.cin, q.cout = tile, pc.cin, pc.cout
+    own = memo is not None and d.tile == tile and d.cout == pc.cout and d.cin == pc.cin
+    got = memo.get(key) if own else None
+    if got is None:
+        q = d
+        if not own:
+            q = _lib.ConvDesc.from_buffer_copy(d)             # (a caller asking about another tile code / filter than the descriptor's)
+            q.tile, q.cin, q.cout = tile, pc.cin, pc.cout
         got = _lib.load().frcnn_conv2d_engine(ctypes.byref(q), _ENGINE_CODE[F32_ENGINE], 1 if key[2] else 0)
         if got < 0:
             _lib.check(got, "frcnn_conv2d_engine")
+        if own:
+            memo[key] = got
     if got == 2 and not (81 <= tile <= 88) and getattr(pc, "_h3_spread_log2", 0.0) > H3_MAX_SPREAD_LOG2:
         return "x6"                                           # an ill-scaled filter (H3_MAX_SPREAD_LOG2): the exact split (an explicit 8x tile code stands)
     return _ENGINE_TAG[got]
@@ -714,6 +714,36 @@ CONV_KERNEL_NAMES = {1: "k_conv_igemm_f32<2,2,false>", 2: "k_conv_igemm_f32<1,1,
                      30: "k_conv_igemm_f32_v2<1,1,2> stem", 32: "k_conv_igemm_f32_v2<1,1,1> stem", 61: "k_conv_igemm_f32_sk<2,2>", 62: "k_conv_igemm_f32_sk<1,1>", 41: "k_conv_igemm_f32_v2<1,2,1,4,2>", 42: "k_conv_igemm_f32_v2<2,1,1,2,4>", 43: "k_conv_igemm_f32_v2<1,1,1,4,2>"}
 
 
+def _record_launch(kernel, shape, fn, args, keep, **extra):
+    """Appends a launch to CONV_PROFILE when it is set: ``kernel()`` names its kernel (looked up only then), ``shape`` is the GEMM
+    (rows, columns, k, stride) the FLOPs come from, and ``relaunch`` re-issues entry point ``fn`` with ``args`` (``keep``: what the
+    re-launches need alive).  ``extra``: further keys of the record."""
+    if CONV_PROFILE is None:
+        return
+    CONV_PROFILE.append({"kernel": kernel(), **extra, "flops": 2.0 * shape[0] * shape[1] * shape[2], "shape": shape,
+                         "relaunch": lambda fn=fn, args=args, keep=keep: _lib.call(fn, *args, _stream())})
+
+
+def _gemm_shape(d, pc, stride):
+    return (d.n * d.ho * d.wo, pc.cout, pc.kh * pc.kw * pc.cin, stride)
+
+
+def _kernel_name(d, eng, ws, n1=None):
+    """The kernel an f32 forward launch on engine ``eng`` ("x6", "h3", None: native) ran, with split-K workspace ``ws``
+    (n1: a two-layer launch whose first layer has n1 columns)."""
+    if eng is not None:
+        if ws is not None:
+            return f"k_conv_igemm_{eng}<1,1,2,2> split-K"
+        return (_h3_name if eng == "h3" else _x6_name)(d, n1 or 0)
+    if n1 is not None:
+        cfg = _lib.load().frcnn_conv2d_dual_config(ctypes.byref(d), 1 if ws is not None else 0)     # the remapped code the launch ran (ADVICE r3)
+        return CONV_KERNEL_NAMES.get(cfg, "?") + (" split-K" if ws is not None else "")
+    cfg = _lib.load().frcnn_conv2d_config(ctypes.byref(d))
+    if cfg in (61, 62) and ws is None:
+        cfg -= 40                                                # balanced form needs a workspace: the plain tile ran
+    return CONV_KERNEL_NAMES.get(cfg, "?") + (" split-K" if ws is not None and cfg not in (61, 62) else "")
+
+
 class ConvWorkspace:
     """Split-K workspace (arrival tickets + f32 partial tiles) of frcnn_conv2d_fwd_ws.
 
@@ -812,13 +842,9 @@ def _conv2d_h3_planes(d, x, pc, residual, oshape, planes_out, act):
             ctypes.byref(yp) if planes_out else None, bc, bd)
     _lib.call("frcnn_conv2d_fwd_h3_planes_res", *args, _stream())
     y._amax = ya
-    if CONV_PROFILE is not None:
-        keep = (d, x, pc, residual, y, ya, xp, yp, xa, ra, rp)
-        # (the instantiation that reads planes is a kernel of its own; writing planes is a run-time branch of either's epilogue)
-        CONV_PROFILE.append({"kernel": _h3_planes_in_name(d, pc) if x_in else _h3_name(d), "planes_out": bool(planes_out),
-                             "flops": 2.0 * d.n * d.ho * d.wo * pc.cout * pc.kh * pc.kw * pc.cin,
-                             "shape": (d.n * d.ho * d.wo, pc.cout, pc.kh * pc.kw * pc.cin, d.stride),
-                             "relaunch": lambda args=args, keep=keep: _lib.call("frcnn_conv2d_fwd_h3_planes_res", *args, _stream())})
+    # (the instantiation that reads planes is a kernel of its own; writing planes is a run-time branch of either's epilogue)
+    _record_launch(lambda: _h3_planes_in_name(d, pc) if x_in else _h3_name(d), _gemm_shape(d, pc, d.stride), "frcnn_conv2d_fwd_h3_planes_res",
+                   args, (d, x, pc, residual, y, ya, xp, yp, xa, ra, rp), planes_out=bool(planes_out))
     return y
 
 
@@ -863,47 +889,24 @@ def conv2d(x, pc, stride=1, padding="valid", act=None, residual=None, out=None, 
     if residual is not None:
         assert residual.shape == out.shape and residual.is_contiguous()
     eng = _split_engine(d, pc, tile or AUTO_TILE)
-    if eng == "h3":
-        ws = _split_k_ws(_ws_need(d, "frcnn_conv2d_h3_workspace_bytes"))
-        ya, xa = _amax_new(), amax_of(x)
-        args = (ctypes.byref(d), _p(x), _p(xa), _p(pc.h3_planes()), _p(pc.scale), _p(pc.shift), _p(residual), None, _p(out), _p(ya),
-                _p(ws), ws.numel() if ws is not None else 0)
-        _lib.call("frcnn_conv2d_fwd_h3", *args, _stream())
-        out._amax = ya
-        if CONV_PROFILE is not None:
-            keep = (d, x, pc, residual, out, ws, ya, xa)
-            CONV_PROFILE.append({"kernel": "k_conv_igemm_h3<1,1,2,2> split-K" if ws is not None else _h3_name(d),
-                                 "flops": 2.0 * n * ho * wo * pc.cout * pc.kh * pc.kw * pc.cin,
-                                 "shape": (n * ho * wo, pc.cout, pc.kh * pc.kw * pc.cin, stride),
-                                 "relaunch": lambda args=args, keep=keep: _lib.call("frcnn_conv2d_fwd_h3", *args, _stream())})
-        return out
-    if eng == "x6":
-        ws = _split_k_ws(_ws_need(d, "frcnn_conv2d_x6_workspace_bytes"))
-        args = (ctypes.byref(d), _p(x), _p(pc.x6_planes()), _p(pc.scale), _p(pc.shift), _p(residual), None, _p(out),
-                _p(ws), ws.numel() if ws is not None else 0)
-        _lib.call("frcnn_conv2d_fwd_x6", *args, _stream())
-        if getattr(out, "_amax", None) is not None:
-            out._amax = None
-        if CONV_PROFILE is not None:
-            keep = (d, x, pc, residual, out, ws)
-            CONV_PROFILE.append({"kernel": "k_conv_igemm_x6<1,1,2,2> split-K" if ws is not None else _x6_name(d),
-                                 "flops": 2.0 * n * ho * wo * pc.cout * pc.kh * pc.kw * pc.cin,
-                                 "shape": (n * ho * wo, pc.cout, pc.kh * pc.kw * pc.cin, stride),
-                                 "relaunch": lambda args=args, keep=keep: _lib.call("frcnn_conv2d_fwd_x6", *args, _stream())})
-        return out
-    ya = _amax_new(optional=True) if (_tracking() and pc.cout >= 32) else None      # a native layer in an f16x3 pass leaves max|y| for the layer behind it
-    (fn, args), ws = _conv_launch(d, x, pc.w, pc.scale, pc.shift, residual, None, out, ya)
+    ya = xa = None
+    if eng is None:
+        ya = _amax_new(optional=True) if (_tracking() and pc.cout >= 32) else None      # a native layer in an f16x3 pass leaves max|y| for the layer behind it
+        (fn, args), ws = _conv_launch(d, x, pc.w, pc.scale, pc.shift, residual, None, out, ya)
+    else:
+        fn = "frcnn_conv2d_fwd_" + eng
+        ws = _split_k_ws(_ws_need(d, f"frcnn_conv2d_{eng}_workspace_bytes"))
+        tail = (_p(pc.scale), _p(pc.shift), _p(residual), None, _p(out))
+        if eng == "h3":
+            ya, xa = _amax_new(), amax_of(x)
+            args = (ctypes.byref(d), _p(x), _p(xa), _p(pc.h3_planes())) + tail + (_p(ya),)
+        else:
+            args = (ctypes.byref(d), _p(x), _p(pc.x6_planes())) + tail
+        args += (_p(ws), ws.numel() if ws is not None else 0)
+        _lib.call(fn, *args, _stream())
     if ya is not None or getattr(out, "_amax", None) is not None:
         out._amax = ya                                           # (an `out=` buffer must not keep the record of what it held before)
-    if CONV_PROFILE is not None:
-        flops = 2.0 * n * ho * wo * pc.cout * pc.kh * pc.kw * pc.cin
-        cfg = _lib.load().frcnn_conv2d_config(ctypes.byref(d))
-        if cfg in (61, 62) and ws is None:
-            cfg -= 40                                            # balanced form needs a workspace: the plain tile ran
-        kname = CONV_KERNEL_NAMES.get(cfg, "?") + (" split-K" if ws is not None and cfg not in (61, 62) else "")
-        keep = (d, x, pc, residual, out, ws, ya)
-        CONV_PROFILE.append({"kernel": kname, "flops": flops, "shape": (n * ho * wo, pc.cout, pc.kh * pc.kw * pc.cin, stride),
-                             "relaunch": lambda args=args, keep=keep, fn=fn: _lib.call(fn, *args, _stream())})
+    _record_launch(lambda: _kernel_name(d, eng, ws), _gemm_shape(d, pc, stride), fn, args, (d, x, pc, residual, out, ws, ya, xa))
     return out
 
 
@@ -917,38 +920,22 @@ def conv2d_dual(x, pc, n1, stride=1, padding="valid", act1=None, act2=None, layo
     y1 = torch.empty(lead + (n1,), dtype=torch.float32, device="cuda")
     y2 = torch.empty(lead + (pc.cout - n1,), dtype=torch.float32, device="cuda")
     eng = _split_engine(d, pc, tile or AUTO_TILE)
+    ws = a1 = a2 = xa = None
+    outs = (_p(y1), n1, ACT[act1], _p(y2), ACT[act2])
     if eng == "h3":
         a1, a2, xa = _amax_new(), _amax_new(), amax_of(x)
         args = (ctypes.byref(d), _p(x), _p(xa), _p(pc.h3_planes()), _p(pc.scale), _p(pc.shift), _p(y1), n1, ACT[act1], _p(a1),
                 _p(y2), ACT[act2], _p(a2))
-        _lib.call("frcnn_conv2d_fwd_dual_h3", *args, _stream())
+    elif eng == "x6":
+        args = (ctypes.byref(d), _p(x), _p(pc.x6_planes()), _p(pc.scale), _p(pc.shift)) + outs
+    else:
+        ws = _split_k_ws(_ws_need(d, "frcnn_conv2d_dual_workspace_bytes"))
+        args = (ctypes.byref(d), _p(x), _p(pc.w), _p(pc.scale), _p(pc.shift)) + outs + (_p(ws), ws.numel() if ws is not None else 0)
+    fn = "frcnn_conv2d_fwd_dual" + (f"_{eng}" if eng else "")
+    _lib.call(fn, *args, _stream())
+    if eng == "h3":
         y1._amax, y2._amax = a1, a2
-        if CONV_PROFILE is not None:
-            keep = (d, x, pc, y1, y2, a1, a2, xa)
-            CONV_PROFILE.append({"kernel": _h3_name(d, n1), "flops": 2.0 * d.n * d.ho * d.wo * pc.cout * pc.kh * pc.kw * pc.cin,
-                                 "shape": (d.n * d.ho * d.wo, pc.cout, pc.kh * pc.kw * pc.cin, stride),
-                                 "relaunch": lambda args=args, keep=keep: _lib.call("frcnn_conv2d_fwd_dual_h3", *args, _stream())})
-        return y1, y2
-    if eng == "x6":
-        args = (ctypes.byref(d), _p(x), _p(pc.x6_planes()), _p(pc.scale), _p(pc.shift), _p(y1), n1, ACT[act1], _p(y2), ACT[act2])
-        _lib.call("frcnn_conv2d_fwd_dual_x6", *args, _stream())
-        if CONV_PROFILE is not None:
-            keep = (d, x, pc, y1, y2)
-            CONV_PROFILE.append({"kernel": _x6_name(d, n1), "flops": 2.0 * d.n * d.ho * d.wo * pc.cout * pc.kh * pc.kw * pc.cin,
-                                 "shape": (d.n * d.ho * d.wo, pc.cout, pc.kh * pc.kw * pc.cin, stride),
-                                 "relaunch": lambda args=args, keep=keep: _lib.call("frcnn_conv2d_fwd_dual_x6", *args, _stream())})
-        return y1, y2
-    ws = _split_k_ws(_ws_need(d, "frcnn_conv2d_dual_workspace_bytes"))
-    args = (ctypes.byref(d), _p(x), _p(pc.w), _p(pc.scale), _p(pc.shift), _p(y1), n1, ACT[act1], _p(y2), ACT[act2],
-            _p(ws), ws.numel() if ws is not None else 0)
-    _lib.call("frcnn_conv2d_fwd_dual", *args, _stream())
-    if CONV_PROFILE is not None:
-        flops = 2.0 * d.n * d.ho * d.wo * pc.cout * pc.kh * pc.kw * pc.cin
-        cfg = _lib.load().frcnn_conv2d_dual_config(ctypes.byref(d), 1 if ws is not None else 0)     # the remapped code the launch ran
-        kname = CONV_KERNEL_NAMES.get(cfg, "?") + (" split-K" if ws is not None else "")
-        keep = (d, x, pc, y1, y2, ws)
-        CONV_PROFILE.append({"kernel": kname, "flops": flops, "shape": (d.n * d.ho * d.wo, pc.cout, pc.kh * pc.kw * pc.cin, stride),
-                             "relaunch": lambda args=args, keep=keep: _lib.call("frcnn_conv2d_fwd_dual", *args, _stream())})
+    _record_launch(lambda: _kernel_name(d, eng, ws, n1), _gemm_shape(d, pc, stride), fn, args, (d, x, pc, y1, y2, ws, a1, a2, xa))
     return y1, y2
 
 
@@ -1164,7 +1151,7 @@ def conv2d_dgrad(gy, pd, padding="valid", residual=None, mask=None, out=None):
 
 
 # Weight gradients of f32 layers: "native" = v_mfma_f32_32x32x2_f32; "bf16x6" = both operands split exactly into three bf16 pieces
-# inside the kernel, six partial products on the bf16 matrix cores (conv_igemm.hip wgrad_body_x6_big; layers with cin, cout >= 128,
+# inside the kernel, six partial products on the bf16 matrix cores (conv_wgrad.hip wgrad_body_x6_big; layers with cin, cout >= 128,
 # the others stay native).  Same slabs and fixed-order reduction: runs are bitwise reproducible either way, the two engines agree
 # to f32 rounding.  The library default stays "native"; train.py opts in.
 WGRAD_ENGINE = os.environ.get("FRCNN_WGRAD_ENGINE", "native")
@@ -1312,11 +1299,7 @@ def conv2d_bf16(x, pc, stride=1, padding="valid", act=None, residual=None, out_f
     args = (ctypes.byref(d), _p(x), _p(pc.w), _p(pc.scale), _p(pc.shift), _p(residual), _p(out), 1 if out_f32 else 0,
             _p(ws), ws.numel() if ws is not None else 0)
     _lib.call("frcnn_conv2d_fwd_bf16_ws", *args, _stream())
-    if CONV_PROFILE is not None:
-        flops = 2.0 * d.n * d.ho * d.wo * pc.cout * pc.kh * pc.kw * pc.cin
-        keep = (d, x, pc, residual, out, ws)
-        CONV_PROFILE.append({"kernel": "k_conv_igemm_bf16", "flops": flops, "shape": (d.n * d.ho * d.wo, pc.cout, pc.kh * pc.kw * pc.cin, stride),
-                             "relaunch": lambda args=args, keep=keep: _lib.call("frcnn_conv2d_fwd_bf16_ws", *args, _stream())})
+    _record_launch(lambda: "k_conv_igemm_bf16", _gemm_shape(d, pc, stride), "frcnn_conv2d_fwd_bf16_ws", args, (d, x, pc, residual, out, ws))
     return out
 
 
@@ -1412,8 +1395,5 @@ def stem_h3(x, ps):
     args = (_p(x), _p(xa), n, h, w, _p(ps.w), _p(ps.scale), _p(ps.shift), _p(out), _p(ya))
     _lib.call("frcnn_stem_h3_fwd", *args, _stream())
     out._amax = ya
-    if CONV_PROFILE is not None:
-        keep = (x, ps, out, ya, xa)
-        CONV_PROFILE.append({"kernel": "k_stem_h3", "flops": 2.0 * n * ho * wo * 64 * 147, "shape": (n * ho * wo, 64, 147, 2),
-                             "relaunch": lambda args=args, keep=keep: _lib.call("frcnn_stem_h3_fwd", *args, _stream())})
+    _record_launch(lambda: "k_stem_h3", (n * ho * wo, 64, 147, 2), "frcnn_stem_h3_fwd", args, (x, ps, out, ya, xa))
     return out

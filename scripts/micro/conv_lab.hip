@@ -1,8 +1,9 @@
 // Conv-engine lab: the product conv source compiled into a standalone program, timed without Python in the
 // launch path, optionally with per-workgroup phase timestamps (FRCNN_LAB_STAMPS).  Dev tool, GPU box only.
 //
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 scripts/micro/conv_lab.hip -o gpurun_out/conv_lab
-//   hipcc ... -DFRCNN_LAB_STAMPS scripts/micro/conv_lab.hip -o gpurun_out/conv_lab_stamps
+//   mkdir -p scripts/micro/_bin && hipcc --offload-arch=gfx950 -O3 -std=c++17 scripts/micro/conv_lab.hip faster_rcnn_amd/csrc/{conv_policy,conv_x6,conv_h3}.hip -o scripts/micro/_bin/conv_lab
+//   hipcc ... -DFRCNN_LAB_STAMPS scripts/micro/conv_lab.hip faster_rcnn_amd/csrc/{conv_policy,conv_x6,conv_h3}.hip -o scripts/micro/_bin/conv_lab_stamps
+// (conv_igemm.hip is included below; the policy and the two split engines it dispatches to link beside it)
 //   conv_lab time  <set> <tile,tile,...>        per-shape table, us per launch (20 launches in one hipGraph, best of 4)
 //   conv_lab_stamps stamps <layer> <tile>       one launch with timestamps: phase medians + start/end distribution
 // <set>: trunk | head | all
@@ -156,9 +157,10 @@ static int cmd_time(int argc, char** argv) {
         std::vector<double> best(tiles.size(), -1.0);
         std::vector<std::string> note(tiles.size());
         // reference output: the product's auto choice with the plain 4-byte epilogue
-        g_scalar_epilogue = true;
+        const bool scalar = conv_knobs().scalar_epilogue;
+        conv_knobs().scalar_epilogue = true;
         launch(p, 0, p.yref, s); CK(hipStreamSynchronize(s));
-        g_scalar_epilogue = getenv("FRCNN_SCALAR_EPILOGUE") != nullptr;
+        conv_knobs().scalar_epilogue = scalar;
         for (size_t i = 0; i < tiles.size(); ++i) {
             CK(hipMemsetAsync(p.y, 0xff, p.M * sh.cout * 4, s));
             if (launch(p, tiles[i], p.y, s) != 0) { note[i] = "refused"; continue; }
