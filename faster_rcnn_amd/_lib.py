@@ -17,7 +17,7 @@ class FrcnnError(RuntimeError):
     pass
 
 
-ABI_VERSION = 109       # include/frcnn_hip.h FRCNN_ABI_VERSION (tests/test_abi.py holds the two together)
+ABI_VERSION = 110       # include/frcnn_hip.h FRCNN_ABI_VERSION (tests/test_abi.py holds the two together)
 P = c_void_p
 I = c_int
 # name -> (restype, argtypes).  Must list every symbol include/frcnn_hip.h declares
@@ -142,6 +142,10 @@ SIGNATURES = {
     "frcnn_detections": (I, [P, P, I, P, P, I, I, c_double, c_double, c_double, c_double, P, P, P, P, P, P]),
     "frcnn_detections_dyn": (I, [P, P, I, I, P, P, I, I, c_double, c_double, P, P, P, P, P, P, P]),
     "frcnn_annotate_u8": (I, [P, I, I, P, P, P, P, I, P, P, I, I, P, P]),
+    "frcnn_vgg_conv1_bf16_packed_elems": (I, []),
+    "frcnn_pack_vgg_conv1_weights_bf16": (I, [P, P, P]),
+    "frcnn_vgg_conv1_bf16_fwd": (I, [P, I, I, I, P, P, P, P]),
+    "frcnn_pool2d_fwd_bf16": (I, [P, I, I, I, I, I, I, P, P]),
 }
 
 

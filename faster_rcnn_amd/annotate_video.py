@@ -233,6 +233,8 @@ def build_parser():
     p.add_argument("--out_dir", dest="out_dir", default=".", help="where the annotated frames are written")
     p.add_argument("--network", dest="network", choices=("vgg16", "resnet50", "resnet101"), default="resnet50")
     p.add_argument("--anchor_scales", dest="anchor_scales", default="128,256,512")
+    p.add_argument("--dtype", dest="dtype", choices=("f32", "bf16"), default="f32",
+                   help="precision the networks are served in: bf16 = the bf16 conv path on the matrix cores (the reference has no such flag: it runs fp32 only)")
     return p
 
 
@@ -248,13 +250,13 @@ def main(argv=None):
     class_mapping = KITTI_CLASS_MAPPING if args.kitti else VOC_CLASS_MAPPING
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
-        rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors))
-        detector = vgg.det_from_h5(args.step4_model_path, num_classes=len(class_mapping))
+        rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)
+        detector = vgg.det_from_h5(args.step4_model_path, num_classes=len(class_mapping), dtype=args.dtype)
         preprocess = vgg.preprocess
     else:
         depth = 50 if args.network == "resnet50" else 101
-        rpn = resnet.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), depth=depth)
-        detector = resnet.det_from_h5(args.step4_model_path, num_classes=len(class_mapping), depth=depth)
+        rpn = resnet.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), depth=depth, dtype=args.dtype)
+        detector = resnet.det_from_h5(args.step4_model_path, num_classes=len(class_mapping), depth=depth, dtype=args.dtype)
         preprocess = resnet.preprocess
     manager = DetTrainingManager(rpn_model=rpn, class_mapping=class_mapping, preprocess_func=preprocess, anchor_dims=anchors)
     resize_min, resize_max = resize_dims_from_str(args.resize_dims)

@@ -55,8 +55,16 @@ class _Model:
     def _new_trainer(self):
         raise NotImplementedError
 
+    def _check_trainable(self):
+        """The bf16 VGG16 path is inference only (VggBaseTrain / _VggHeadTrain are f32): say so here, not three layers down."""
+        for m in self._modules():
+            if isinstance(m, (nets.VggBase, nets.VggHead)) and getattr(m, "dtype", "f32") == "bf16":
+                from ._lib import FrcnnError
+                raise FrcnnError("VGG16 trains in f32; build the model with dtype='f32'")
+
     def compile(self, optimizer, loss=None):
         """Keras ``compile``: a fresh train function, i.e. fresh optimiser slots (train_util.py:31-33, 95)."""
+        self._check_trainable()
         if self._trainer is None:
             self._trainer = self._new_trainer()
         self._trainer.compile(optimizer, loss)
@@ -67,6 +75,7 @@ class _Model:
         """Keras' train_on_batch: [total, loss 1, loss 2].  ``defer=True`` (not in Keras) only ENQUEUES the step and
         returns a train.PendingLosses; its ``result()`` is that list.  The training loops use it to prepare the next
         image while the GPU runs this step."""
+        self._check_trainable()
         self._dirty = True
         return self._trainer.train_on_batch(x, y, skip=skip, defer=defer)
 

@@ -304,13 +304,21 @@ class ResNetBase:
 
 
 class VggBase:
-    """13 conv + 4 pools, no pool5 (vgg16_base vgg.py:91-141)."""
+    """13 conv + 4 pools, no pool5 (vgg16_base vgg.py:91-141).
+
+    ``dtype="bf16"``: block1_conv1 (3 input channels: the one layer the bf16 conv engine refuses) runs on its own kernel
+    (frcnn_vgg_conv1_bf16_fwd: f32 image in, bf16 map out), the other twelve layers are ``conv2d_bf16`` launches (bias in ``shift``,
+    ReLU in the epilogue) and the four pools ``pool2d_bf16``; every stored activation is bf16, the output map too."""
     stride = 16
     out_channels = 512
 
-    def __init__(self, weights):
-        self.weights = weights
-        self.convs = [(name, ConvUnit(weights, name, padding="same", act="relu")) for name, _, _ in VGG_CONVS]
+    def __init__(self, weights, dtype="f32"):
+        assert dtype in ("f32", "bf16"), dtype
+        self.weights, self.dtype = weights, dtype
+        # (block1_conv1 stays an f32 unit on a bf16 base: only its folded() is used there, by the conv1 kernel's packed holder)
+        self.convs = [(name, ConvUnit(weights, name, padding="same", act="relu", dtype="f32" if name == "block1_conv1" else dtype))
+                      for name, _, _ in VGG_CONVS]
+        self._conv1_bf16 = None
 
     def units(self):
         for _, u in self.convs:
@@ -318,10 +326,33 @@ class VggBase:
 
     POOLED = ("block1_conv2", "block2_conv2", "block3_conv3", "block4_conv3")
 
+    def invalidate_fused(self, only=None):
+        """models._Model.invalidate: drop the conv1 kernel's packed filter when block1_conv1 changed (as ResNetBase drops its stems)."""
+        if only is None or self.convs[0][0] in only:
+            self._conv1_bf16 = None
+
+    def lower_conv1_bf16(self):
+        """The packed form frcnn_vgg_conv1_bf16_fwd reads; built once per generation of block1_conv1's arrays."""
+        src = tuple(id(a) for a in self.weights[self.convs[0][0]])
+        if self._conv1_bf16 is None or self._conv1_src != src:
+            kernel, _, shift = self.convs[0][1].folded()             # (no BatchNorm: scale is 1, shift the bias)
+            self._conv1_bf16, self._conv1_src = ops.PackedVggConv1Bf16(kernel, shift), src
+        return self._conv1_bf16
+
+    def _forward_bf16(self, x):
+        x = ops.vgg_conv1_bf16(x, self.lower_conv1_bf16())
+        for name, u in self.convs[1:]:
+            x = u(x)
+            if name in self.POOLED:
+                x = ops.pool2d_bf16(x, 2, 2)
+        return x
+
     def __call__(self, x):
         """Round 6: a convolution whose output has ONE reader, the next convolution of its block, hands it on as the fp16 planes that one
         multiplies where both launches run on the f16x3 engine's 256x128 tile (ops.PlaneTensor, as inside the ResNet head's blocks): the
         reader's loader splits nothing and, its reduction being 36-144 chunks long, walks the direct-to-LDS ring."""
+        if self.dtype == "bf16":
+            return self._forward_bf16(x)
         for k, (name, u) in enumerate(self.convs):
             nxt = self.convs[k + 1][1] if (k + 1 < len(self.convs) and name not in self.POOLED) else None
             planes = VGG_PLANES and nxt is not None and _reads_planes(nxt, tuple(x.shape[:-1]) + (_cout(u),), 0)
@@ -496,23 +527,48 @@ class ResNetHead:
 
 
 class VggHead:
-    """RoiResizeConv -> Flatten (h,w,c order) -> fc1, fc2 (ReLU) -> dense x2 (vgg.py:226-255)."""
+    """RoiResizeConv -> Flatten (h,w,c order) -> fc1, fc2 (ReLU) -> dense x2 (vgg.py:226-255).
+
+    ``dtype="bf16"``: bf16 crops in the [roi][7][7][c] layout (Keras' Flatten order), fc1 / fc2 as bf16 1x1 convolutions (25 088 and
+    4 096 input channels), fc2's rows widened exactly to f32 for the merged dense layer, which stays an f32 unit as in the bf16 ResNet
+    head.  Only this form has ``forward_batched``: fc1 is a 25 088 x 4 096 matrix that every pass re-reads whatever its row count, so
+    one pass over the RoIs of B images reads it once for all of them.  ``hoist`` is what entry.DetectionEntry and
+    pipeline.BatchedInferencePipeline ask a head before they batch it (there is nothing to hoist here: it says "forward_batched
+    serves this head"), so it is False on the f32 form, which keeps one image per pass."""
     pool = 7
 
-    def __init__(self, weights, num_classes):
-        self.fc1 = ConvUnit(weights, "fc1", act="relu")
-        self.fc2 = ConvUnit(weights, "fc2", act="relu")
+    def __init__(self, weights, num_classes, dtype="f32"):
+        assert dtype in ("f32", "bf16"), dtype
+        self.dtype, self.hoist = dtype, dtype == "bf16"
+        # (fc1's tile stays the bf16 launch policy's: 64x64 tiles, cut over k when a workspace is at hand, at one image's 64-300 rows,
+        # 128x128 over a batch's -- no explicit code of the engine beat them on the 25 088-deep GEMM)
+        self.fc1 = ConvUnit(weights, "fc1", act="relu", dtype=dtype)
+        self.fc2 = ConvUnit(weights, "fc2", act="relu", dtype=dtype)
         self.dense = _MergedDense(weights, num_classes)
 
     def units(self):
         return [self.fc1, self.fc2, self.dense.unit]
 
-    def __call__(self, feat, rois):
-        x = ops.roi_crop_resize(feat, rois, self.pool)      # (n,7,7,512)
+    def _fc(self, x):
+        """crops (n,7,7,512) -> (class probabilities, regressions)."""
         n = x.shape[0]
-        x = self.fc1(x.reshape(n, 1, 1, -1))
-        x = self.fc2(x)
+        x = self.fc2(self.fc1(x.reshape(n, 1, 1, -1)))
+        if self.dtype == "bf16":
+            x = ops.cast_f32(x)                             # exact widening: the dense layers read f32 rows
         return self.dense(x.reshape(n, -1))
+
+    def __call__(self, feat, rois):
+        if self.dtype == "bf16":
+            return self._fc(ops.roi_crop_resize_bf16(feat, rois, self.pool))
+        return self._fc(ops.roi_crop_resize(feat, rois, self.pool))      # (n,7,7,512)
+
+    def forward_batched(self, feat, rois, n_per_img):
+        """The head over the RoIs of a BATCH of images in one pass (bf16 form only): feat (B,R,C,512) bf16, rois (B*n_per_img,4) (RoI r
+        belongs to image r // n_per_img) -> (class probabilities (B*n,C), regressions).  Per row the arithmetic of ``__call__`` launched
+        without split-K (a row's k order does not depend on the GEMM's height)."""
+        if self.dtype != "bf16":
+            raise ops._lib.FrcnnError("VggHead.forward_batched: the f32 VGG16 head runs one image per pass; build the model with dtype='bf16'")
+        return self._fc(ops.roi_crop_resize_bf16_batch(feat, rois, n_per_img, self.pool))
 
 
 def to_device_image(x):

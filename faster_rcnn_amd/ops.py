@@ -1397,3 +1397,41 @@ def stem_h3(x, ps):
     out._amax = ya
     _record_launch(lambda: "k_stem_h3", (n * ho * wo, 64, 147, 2), "frcnn_stem_h3_fwd", args, (x, ps, out, ya, xa))
     return out
+
+
+class PackedVggConv1Bf16:
+    """block1_conv1's parameters for frcnn_vgg_conv1_bf16_fwd (vgg.py:96-97): the 3x3x3x64 filter packed to bf16 as the four matrix
+    fragments the kernel keeps in registers, and the f32 bias."""
+
+    def __init__(self, w_hwio, bias):
+        _require_gpu()
+        w = _dev(w_hwio, torch.float32)
+        assert tuple(w.shape) == (3, 3, 3, 64), "the conv1 kernel is block1_conv1 of VGG16: 3x3x3 -> 64"
+        self.w = torch.empty(_lib.load().frcnn_vgg_conv1_bf16_packed_elems(), dtype=torch.bfloat16, device="cuda")
+        _lib.call("frcnn_pack_vgg_conv1_weights_bf16", _p(w), _p(self.w), _stream())
+        self.bias = _dev(bias, torch.float32)
+        torch.cuda.current_stream().synchronize()            # w may be a temporary
+
+
+def vgg_conv1_bf16(x, packed):
+    """(n,H,W,3) f32 preprocessed images -> (n,H,W,64) bf16: block1_conv1 + bias + ReLU (SAME padding), one launch."""
+    _require_gpu()
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[-1] == 3
+    n, h, w, _ = x.shape
+    out = torch.empty((n, h, w, 64), dtype=torch.bfloat16, device="cuda")
+    args = (_p(x), n, h, w, _p(packed.w), _p(packed.bias), _p(out))
+    _lib.call("frcnn_vgg_conv1_bf16_fwd", *args, _stream())
+    _record_launch(lambda: "k_vgg_conv1_bf16", (n * h * w, 64, 27, 1), "frcnn_vgg_conv1_bf16_fwd", args, (x, packed, out))
+    return out
+
+
+def pool2d_bf16(x, k, stride):
+    """MaxPooling2D((k,k), strides=(stride,stride)), VALID, on a bf16 NHWC map (the library serves k = stride = 2, c % 8 == 0)."""
+    _require_gpu()
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 4
+    n, h, w, c = x.shape
+    out = torch.empty((n, valid_out(h, k, stride), valid_out(w, k, stride), c), dtype=torch.bfloat16, device="cuda")
+    args = (_p(x), n, h, w, c, k, stride, _p(out))
+    _lib.call("frcnn_pool2d_fwd_bf16", *args, _stream())
+    _record_launch(lambda: "k_pool2_bf16", (out.numel() // c, c, k * k, 1), "frcnn_pool2d_fwd_bf16", args, (x, out))
+    return out

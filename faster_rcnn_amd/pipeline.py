@@ -190,7 +190,9 @@ class BatchedInferencePipeline(InferencePipeline):
     def __init__(self, rpn_model, det_model, anchor_dims, batch, **kw):
         super().__init__(rpn_model, det_model, anchor_dims, **kw)
         self.batch = int(batch)
-        assert hasattr(det_model.head, "forward_batched") and getattr(det_model.head, "hoist", False), "batched pipeline: a ResNet head in the hoisted order"
+        # (what it needs: a head whose forward_batched serves its form -- a ResNet head in the hoisted order, the bf16 VGG16 head)
+        assert hasattr(det_model.head, "forward_batched") and getattr(det_model.head, "hoist", False), \
+            "batched pipeline: a head with forward_batched (ResNet in the hoisted order, VGG16 in bf16)"
         # the per-image stages (proposal selection: ~10 short dependent launches; detection post-process: one workgroup) of the
         # B images are independent chains.  FRCNN_PAR_BRANCHES=1 runs each on its own stream, forked from and joined into the
         # pass's stream, so a captured graph holds them as B parallel branches: ONE graph in flight gains (B = 8: 663 -> 740

@@ -92,15 +92,15 @@ def resnet101_classifier(num_rois, num_classes, base_model=None, weight_regulari
     return m
 
 
-def rpn_from_h5(h5_path, anchors_per_loc=DEFAULT_ANCHORS_PER_LOC, depth=50):
+def rpn_from_h5(h5_path, anchors_per_loc=DEFAULT_ANCHORS_PER_LOC, depth=50, dtype="f32"):
     """resnet.rpn_from_h5 (resnet.py:32-44): a Keras 2.0.x ``.h5`` (read in-process, h5lite.py) or the
     ``.npz`` this package's ``save_weights`` writes.  Step-4 RPN models carry the conv4 map as third
-    output (train_det_step4.py:80)."""
+    output (train_det_step4.py:80).  ``dtype="bf16"`` serves the loaded weights on the bf16 conv path (not in the reference)."""
     w = load_npz(h5_path)
-    base = _base(depth, [1, 2, 3], None, None, w)
+    base = _base(depth, [1, 2, 3], None, None, w, dtype)
     return RpnModel(base, True, anchors_per_loc)
 
 
-def det_from_h5(h5_path, num_classes, depth=50):
+def det_from_h5(h5_path, num_classes, depth=50, dtype="f32"):
     w = load_npz(h5_path)
-    return DetModel(w, nets.ResNetHead(w, depth, num_classes), 64, num_classes, None)
+    return DetModel(w, nets.ResNetHead(w, depth, num_classes, dtype), 64, num_classes, None)

@@ -283,6 +283,8 @@ def build_parser():
     p.add_argument("--network", dest="network", choices=("vgg16", "resnet50", "resnet101"), default="vgg16")
     p.add_argument("--out_dir", dest="out_dir", default=".")
     p.add_argument("--det_threshold", dest="det_threshold", default=DEFAULT_DET_THRESHOLD)
+    p.add_argument("--dtype", dest="dtype", choices=("f32", "bf16"), default="f32",
+                   help="precision the networks are served in: bf16 = the bf16 conv path on the matrix cores (the reference has no such flag: it runs fp32 only)")
     return p
 
 
@@ -301,13 +303,13 @@ def main(argv=None):
     print("num test_imgs: ", len(test_imgs))
     class_mapping = KITTI_CLASS_MAPPING if args.kitti else VOC_CLASS_MAPPING
     if args.network == "vgg16":
-        model_rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors))
-        model_det = vgg.det_from_h5(args.step4_model_path, num_classes=len(class_mapping))
+        model_rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)
+        model_det = vgg.det_from_h5(args.step4_model_path, num_classes=len(class_mapping), dtype=args.dtype)
         stride, preprocess = vgg.STRIDE, vgg.preprocess
     else:
         depth = 50 if args.network == "resnet50" else 101
-        model_rpn = resnet.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), depth=depth)
-        model_det = resnet.det_from_h5(args.step4_model_path, num_classes=len(class_mapping), depth=depth)
+        model_rpn = resnet.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), depth=depth, dtype=args.dtype)
+        model_det = resnet.det_from_h5(args.step4_model_path, num_classes=len(class_mapping), depth=depth, dtype=args.dtype)
         stride, preprocess = resnet.STRIDE, resnet.preprocess
     manager = DetTrainingManager(rpn_model=model_rpn, class_mapping=class_mapping, preprocess_func=preprocess, anchor_dims=anchors)
     resize_min, resize_max = resize_dims_from_str(args.resize_dims)

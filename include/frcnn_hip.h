@@ -46,9 +46,11 @@ const char* frcnn_last_error(void);
  * 106 = frcnn_preprocess_u8_canvas takes the image's offset in the canvas (even canvases for every parity).
  * 107 = frcnn_conv2d_fwd_h3_planes_res (addition only).
  * 108 = frcnn_pool2d_fwd_planes (addition only).
+ * 110 = bf16 VGG16: frcnn_vgg_conv1_bf16_packed_elems, frcnn_pack_vgg_conv1_weights_bf16, frcnn_vgg_conv1_bf16_fwd,
+ *       frcnn_pool2d_fwd_bf16 (additions only).
  * 104 = the f16x3 engine's fences: frcnn_h3_planes.status (a THIRD field: recompile hosts that pass the struct), status word in a
  *       magnitude record, frcnn_amax_status. */
-#define FRCNN_ABI_VERSION 109
+#define FRCNN_ABI_VERSION 110
 int frcnn_version(void);
 /* number of HIP devices visible; does not initialise a context */
 int frcnn_device_count(void);
@@ -675,6 +677,19 @@ int frcnn_roi_crop_resize_fwd_bf16_ex(const void* feat_bf16, int rows, int cols,
  * (custom_layers.py:35-56). */
 int frcnn_roi_crop_resize_fwd_bf16_batch(const void* feat_bf16, int n_img, int rows, int cols, int C, const float* rois, int n_per_img, int pool,
                                          const float* fill, int relu, int layout, void* out_bf16, void* stream);
+/* VGG16's first layer on the bf16 matrix cores: Conv2D(64, (3,3), activation='relu', padding='same', name='block1_conv1')
+ * (vgg.py:96-97), the one conv of the bf16 VGG16 chain that frcnn_conv2d_fwd_bf16 refuses (cin = 3).  x [n][h][w][3] f32 (the image
+ * after vgg.preprocess, vgg.py:52-57; rounded to bf16 once inside), packed filter from frcnn_pack_vgg_conv1_weights_bf16 (HWIO f32
+ * [3][3][3][64] -> frcnn_vgg_conv1_bf16_packed_elems() bf16: the four v_mfma_f32_16x16x32_bf16 A fragments, k = (r*3 + s)*3 + c padded
+ * from 27 to 32 with zeros), bias [64] f32; out [n][h][w][64] bf16.  f32 accumulate, bias and ReLU in f32, one rounding at the store;
+ * SAME padding reads zeros.  Offsets are 64-bit; h and n at most 65535 (FRCNN_E_UNSUPPORTED beyond). */
+int frcnn_vgg_conv1_bf16_packed_elems(void);
+int frcnn_pack_vgg_conv1_weights_bf16(const float* w_hwio, void* packed_bf16, void* stream);
+int frcnn_vgg_conv1_bf16_fwd(const float* x, int n, int h, int w, const void* w_packed_bf16, const float* bias, void* out_bf16, void* stream);
+/* MaxPooling2D((2,2), strides=(2,2)) on a bf16 NHWC map (block1_pool .. block4_pool, vgg.py:100, 108, 118, 128): VALID, odd trailing
+ * rows / columns are dropped; y [n][h/2][w/2][c] bf16.  Exact (a maximum rounds nothing).  k = 2, stride = 2 and c % 8 == 0 only:
+ * anything else returns FRCNN_E_UNSUPPORTED and writes nothing. */
+int frcnn_pool2d_fwd_bf16(const void* x_bf16, int n, int h, int w, int c, int k, int stride, void* y_bf16, void* stream);
 
 #ifdef __cplusplus
 }
