@@ -141,6 +141,9 @@ __global__ void __launch_bounds__(LOSS_T) k_loss_rpn_reg_final(const float* y_tr
 
 // cls_loss_det (loss_functions.py:70-76): mean over RoIs of -sum_c y*log(clip(p/sum p)).  g w.r.t. the
 // pre-softmax logits = (p - y)/n (the renormalisation is the identity on a softmax output).
+// PRECONDITION: every row of y_true is one-hot (sums to 1).  (p - y)/n is the gradient only then: for an all-zero row the loss has no
+// gradient, yet this writes p/n.  The detector's y_class always is: det_util._one_hot_encode_cls gives each eligible RoI exactly one
+// class, 'bg' included, and sampling only selects rows.
 __global__ void __launch_bounds__(LB) k_loss_det_cls(const float* y_true, const float* p, int n_rois, int C, float* loss, float* g_logit, int ldg) {
     __shared__ double scratch[LB / 64];
     double acc = 0.0;
@@ -240,24 +243,33 @@ __global__ void k_maxpool_bwd(const float* x, const float* y, const float* gy, i
 }
 
 // Keras SGD(momentum, nesterov=False):  g += 2*l2*w;  v = momentum*v - lr*g;  w += v
+// One element's update, with the fused multiply-adds SPELLED OUT: left to the compiler's contraction, the scalar and the 16-byte kernel
+// below were fused differently (the scalar form rounded momentum*v before the subtraction, the 16-byte form did not) and disagreed in the
+// last bit.  This is the sequence the 16-byte form has always compiled to.
+__device__ __forceinline__ float sgd_momentum_step(float& w, float g, float v, float lr, float momentum, float l2, float gscale) {
+    const float gi = fmaf(2.0f * l2, w, g * gscale);
+    const float vi = fmaf(momentum, v, -(lr * gi));
+    w += vi;
+    return vi;
+}
 __global__ void k_sgd_momentum(float* w, const float* g, float* v, size_t n, float lr, float momentum, float l2, float gscale) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float gi = g[i] * gscale + 2.0f * l2 * w[i];
-        const float vi = momentum * v[i] - lr * gi;
-        v[i] = vi;
-        w[i] += vi;
+        float wi = w[i];
+        v[i] = sgd_momentum_step(wi, g[i], v[i], lr, momentum, l2, gscale);
+        w[i] = wi;
     }
 }
 // the same update, four parameters per lane (16-byte loads and stores: the 4-byte form moved the flat buffers of an RPN
-// step -- 47 MB of parameters, five passes -- at 2.7 TB/s, 88 us); per element the arithmetic is k_sgd_momentum's: bit-identical
+// step -- 47 MB of parameters, five passes -- at 2.7 TB/s, 88 us); per element the arithmetic is sgd_momentum_step: bit-identical
+// (tests/test_train_kernels_gpu.py::test_sgd_momentum runs both on equal values)
 __global__ void k_sgd_momentum_v4(float4* w, const float4* g, float4* v, size_t n4, float lr, float momentum, float l2, float gscale) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         float4 wi = w[i], vi = v[i];
         const float4 gg = g[i];
-        const float g0 = gg.x * gscale + 2.0f * l2 * wi.x, g1 = gg.y * gscale + 2.0f * l2 * wi.y;
-        const float g2 = gg.z * gscale + 2.0f * l2 * wi.z, g3 = gg.w * gscale + 2.0f * l2 * wi.w;
-        vi.x = momentum * vi.x - lr * g0; vi.y = momentum * vi.y - lr * g1; vi.z = momentum * vi.z - lr * g2; vi.w = momentum * vi.w - lr * g3;
-        wi.x += vi.x; wi.y += vi.y; wi.z += vi.z; wi.w += vi.w;
+        vi.x = sgd_momentum_step(wi.x, gg.x, vi.x, lr, momentum, l2, gscale);
+        vi.y = sgd_momentum_step(wi.y, gg.y, vi.y, lr, momentum, l2, gscale);
+        vi.z = sgd_momentum_step(wi.z, gg.z, vi.z, lr, momentum, l2, gscale);
+        vi.w = sgd_momentum_step(wi.w, gg.w, vi.w, lr, momentum, l2, gscale);
         v[i] = vi;
         w[i] = wi;
     }

@@ -585,6 +585,8 @@ int frcnn_annotate_u8(uint8_t* frame, int height, int width, const int32_t* det_
  *   rpn_reg: y_true [cells][8A] = [mask | targets], y_pred [cells][4A];
  *            loss = mean(mask)*10*S/2400 with S over ALL anchors (the reference's quirk, :44).
  *   det_cls: y_true/y_pred [n][C]; grad w.r.t. the PRE-softmax logits, written with row stride ldg (:76).
+ *            PRECONDITION: every row of y_true is one-hot (background included), as det_util builds it; the
+ *            gradient (p - y)/n is not that of a row of zeros.
  *   det_reg: y_true [n][8K] = [mask | targets], y_pred [n][4K], K = classes excl. background (:65). */
 int frcnn_loss_rpn_cls(const float* y_true, const float* y_pred, int cells, int A, float* loss, float* grad_logit, void* stream);
 int frcnn_loss_rpn_reg(const float* y_true, const float* y_pred, int cells, int A, float* loss, float* grad_pred, void* stream);
