@@ -148,6 +148,15 @@ SIGNATURES = {
     "frcnn_pool2d_fwd_bf16": (I, [P, I, I, I, I, I, I, P, P]),
 }
 
+# Extensions: entry points of the same library declared in headers of their own under include/ext/, each with its own revision (the
+# table above and ABI_VERSION are include/frcnn_hip.h's and stay as they are).  load() binds them too.
+VGG_CANVAS_VERSION = 1  # include/ext/frcnn_hip_vgg_canvas.h FRCNN_VGG_CANVAS_VERSION
+EXT_SIGNATURES = {
+    "frcnn_vgg_canvas_version": (I, []),
+    "frcnn_pool2d_fwd_extents": (I, [P, I, I, I, I, P, P, P]),
+    "frcnn_pool2d_fwd_bf16_extents": (I, [P, I, I, I, I, P, P, P]),
+    "frcnn_vgg_conv1_bf16_fwd_extents": (I, [P, I, I, I, P, P, P, P, P]),
+}
 
 
 class ConvDesc(ctypes.Structure):
@@ -207,6 +216,13 @@ def load():
         fn = getattr(lib, name)          # AttributeError here = header/library drift
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in EXT_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_vgg_canvas_version() != VGG_CANVAS_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_vgg_canvas_version()} of the VGG16 canvas extension, this binding "
+                         f"{VGG_CANVAS_VERSION} (include/ext/frcnn_hip_vgg_canvas.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_version() != ABI_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks ABI revision {lib.frcnn_version()}, this binding {ABI_VERSION} (include/frcnn_hip.h "
                          "FRCNN_ABI_VERSION): rebuild with `python -m faster_rcnn_amd.build`")

@@ -52,6 +52,8 @@ def build_library(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "frcnn_hip.h"))
+    ext = os.path.join(os.path.dirname(HERE), "include", "ext")
+    headers += [os.path.join(ext, f) for f in sorted(os.listdir(ext)) if f.endswith(".h")] if os.path.isdir(ext) else []
     hipcc = _hipcc()
     objs = []
     procs = []

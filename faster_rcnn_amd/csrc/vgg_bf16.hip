@@ -26,6 +26,7 @@
 // maximum only when it is strictly greater or a NaN, so a window that holds both -0.0 and +0.0 (and nothing positive) yields whichever
 // of the two comes FIRST in (row, column) order, and a NaN in the window propagates.
 #include "common.h"
+#include "../../include/ext/frcnn_hip_vgg_canvas.h"
 
 namespace frcnn {
 
@@ -39,12 +40,27 @@ constexpr int VC_STAGE = 3 * VC_ROW;              // 2328 values
 constexpr int VC_NP = (VC_STAGE + 255) / 256;     // staging loads per thread
 constexpr int VC_PACKED = 4 * 64 * 8;             // packed filter: [MFMA f = 2 h + t][lane][8] bf16
 
+//
+// EXT (frcnn_vgg_conv1_bf16_fwd_extents, a canvas pass): x and out are canvases [H][W]; image img occupies the top-left hw[2 img] x
+// hw[2 img + 1] cells (device words, clamped to the canvas).  Staging reads zeros at and beyond the TRUE extent -- the padding a pass of
+// the image's own size reads there, whatever the canvas holds -- so a cell inside the extent sees the operands of that pass in the same
+// k slots: bit-identical.  Every other cell of the canvas is stored as zero (block1_conv2 is a 3x3 too); a run wholly outside the
+// extent stores its zeros and leaves before the staging.  EXT = false compiles to the kernel as it was.
+template <bool EXT>
 __global__ void __launch_bounds__(256) k_vgg_conv1_bf16(const float* __restrict__ x, const bf16x8* __restrict__ wp, const float* __restrict__ bias,
-                                                        int H, int W, __bf16* __restrict__ out) {
+                                                        int H, int W, const int* __restrict__ hw, __bf16* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) unsigned short rows[VC_STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 15, g = lane >> 4;
     const int x0 = blockIdx.x * VC_RUN, y = blockIdx.y, img = blockIdx.z;
     const float* xi = x + (size_t)img * H * W * 3;
+    const int Ht = EXT ? max(0, min(hw[2 * img], H)) : H, Wt = EXT ? max(0, min(hw[2 * img + 1], W)) : W;      // the image's true extent
+    if (EXT && (y >= Ht || x0 >= Wt)) {                        // (workgroup-uniform) nothing of the image under this run: zeros only
+        u16x8* o = reinterpret_cast<u16x8*>(out + (((size_t)img * H + y) * (size_t)W + x0) * 64);
+        const int n = min(VC_RUN, W - x0) * 8;
+        const u16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int k = tid; k < n; k += 256) o[k] = z;
+        return;
+    }
 
     // ---- stage rows y - 1 .. y + 1, pixels x0 - 1 .. x0 + 256 (f32 -> bf16 once, zeros outside the image: SAME padding).  All of a
     // thread's loads are issued before the first is used (as in the stem: a load -> convert -> store loop is a chain of round trips).
@@ -54,7 +70,7 @@ __global__ void __launch_bounds__(256) k_vgg_conv1_bf16(const float* __restrict_
         const int idx = tid + q * 256;
         const int r = idx / VC_ROW, col = idx - r * VC_ROW;
         const int gy = y - 1 + r, gx = x0 - 1 + col / 3;
-        const bool ok = idx < VC_STAGE && col < (VC_RUN + 2) * 3 && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
+        const bool ok = idx < VC_STAGE && col < (VC_RUN + 2) * 3 && (unsigned)gy < (unsigned)Ht && (unsigned)gx < (unsigned)Wt;
         pv[q] = ok ? xi[((size_t)gy * W + gx) * 3 + (col - (col / 3) * 3)] : 0.0f;
     }
 #pragma unroll
@@ -103,6 +119,7 @@ __global__ void __launch_bounds__(256) k_vgg_conv1_bf16(const float* __restrict_
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
                     o[e] = __builtin_bit_cast(unsigned short, (__bf16)fmaxf(acc[2 * h + (e >> 2)][e & 3] + bs[h][e], 0.0f));
+                if (EXT && x0 + px >= Wt) o = u16x8{0, 0, 0, 0, 0, 0, 0, 0};      // on the canvas, beyond the image's last column
                 *reinterpret_cast<u16x8*>(orow + (size_t)(x0 + px) * 64 + 32 * h + 8 * g) = o;
             }
         }
@@ -161,8 +178,19 @@ int frcnn_vgg_conv1_bf16_fwd(const float* x, int n, int h, int w, const void* w_
     if ((reinterpret_cast<uintptr_t>(w_packed_bf16) | reinterpret_cast<uintptr_t>(out_bf16)) & 15) return fail(FRCNN_E_ARG, "vgg_conv1_bf16_fwd: 16-byte aligned tensors");
     if (h > 65535 || n > 65535) return fail(FRCNN_E_UNSUPPORTED, "vgg_conv1_bf16_fwd: at most 65535 rows and 65535 images per launch");
     const dim3 grid((w + VC_RUN - 1) / VC_RUN, h, n);
-    k_vgg_conv1_bf16<<<grid, 256, 0, as_stream(stream)>>>(x, (const bf16x8*)w_packed_bf16, bias, h, w, (__bf16*)out_bf16);
+    k_vgg_conv1_bf16<false><<<grid, 256, 0, as_stream(stream)>>>(x, (const bf16x8*)w_packed_bf16, bias, h, w, nullptr, (__bf16*)out_bf16);
     return check_launch("vgg_conv1_bf16_fwd");
+}
+
+int frcnn_vgg_conv1_bf16_fwd_extents(const float* x, int n, int hc, int wc, const void* w_packed_bf16, const float* bias, const int32_t* true_hw,
+                                     void* out_bf16, void* stream) {
+    if (!x || !w_packed_bf16 || !bias || !true_hw || !out_bf16) return fail(FRCNN_E_ARG, "vgg_conv1_bf16_fwd_extents: null pointer");
+    if (n <= 0 || hc <= 0 || wc <= 0) return fail(FRCNN_E_ARG, "vgg_conv1_bf16_fwd_extents: bad shape");
+    if ((reinterpret_cast<uintptr_t>(w_packed_bf16) | reinterpret_cast<uintptr_t>(out_bf16)) & 15) return fail(FRCNN_E_ARG, "vgg_conv1_bf16_fwd_extents: 16-byte aligned tensors");
+    if (hc > 65535 || n > 65535) return fail(FRCNN_E_UNSUPPORTED, "vgg_conv1_bf16_fwd_extents: at most 65535 rows and 65535 images per launch");
+    const dim3 grid((wc + VC_RUN - 1) / VC_RUN, hc, n);
+    k_vgg_conv1_bf16<true><<<grid, 256, 0, as_stream(stream)>>>(x, (const bf16x8*)w_packed_bf16, bias, hc, wc, true_hw, (__bf16*)out_bf16);
+    return check_launch("vgg_conv1_bf16_fwd_extents");
 }
 
 int frcnn_pool2d_fwd_bf16(const void* x_bf16, int n, int h, int w, int c, int k, int stride, void* y_bf16, void* stream) {

@@ -79,7 +79,8 @@ WARMUP_PASSES = max(1, int(os.environ.get("FRCNN_ENTRY_WARMUP", "1")))
 # Padded canvases (round 6): a list of MANY image sizes is served by passes captured per canvas CLASS with the images' true sizes as
 # device values (pipeline: ``extents``), instead of one capture per geometry.  A canvas has EVEN sides, multiples of CANVAS_GRANULE; an
 # image sits at offset (H & 1, W & 1) (csrc/boxes.hip: the offset stands for the extra zero row / column SAME padding puts in front of
-# an odd side).  voc_dets.get_dets_by_cls switches canvases on for a call whose list holds more than CANVAS_MIN_GEOMETRIES sizes and
+# an odd side; a VGG16 frame sits at (0, 0): no VGG16 layer's padding depends on the size -- the base's ``extents_class`` says which).
+# voc_dets.get_dets_by_cls switches canvases on for a call whose list holds more than CANVAS_MIN_GEOMETRIES sizes and
 # PLANS the classes from the list's size histogram (DetectionEntry.plan_canvases): few classes, each worth its captures.
 # file-backed frames go up in the decoder's channel order and are swapped to BGR by the device resize (0: reverse on the host as before)
 RGB_UPLOAD = os.environ.get("FRCNN_ENTRY_RGB_UPLOAD", "1") != "0"
@@ -103,6 +104,11 @@ CANVAS_EXTRA_SLOT = int(os.environ.get("FRCNN_ENTRY_WINDOW_EXTRA", "0"))      # 
 CANVAS_SLOT_FACTOR = float(os.environ.get("FRCNN_ENTRY_CANVAS_SLOT_FACTOR", "1.0"))
 CANVAS_SLOT_MIN = int(os.environ.get("FRCNN_ENTRY_CANVAS_SLOT_MIN", "2"))
 CANVAS_BYTES_PER_PIXEL = 600                             # a captured fp32 pass's memory per canvas pixel, before one of its class has been measured
+# (600 is the f32 ResNet figure and the first guess for VGG16 too; for VGG16 it is UNMEASURED.  By reckoning: a captured pass's pool
+# re-uses what the pass has freed, so its per-pixel part is about block 1's two full-resolution 64-channel maps, 2 x 256 B in f32 and
+# 2 x 128 B in bf16 -- but a part that does not scale with pixels (head, proposals, staging) sits on top and dominates small canvases,
+# so the guess may fall on either side.  Either side is safe: the guess only trims slot ALLOWANCES before the first capture of a
+# class; GraphCache evicts by the MEASURED nbytes of the passes it holds, and the next plan_canvases reads that figure instead.)
 
 
 def canvas_side(n, granule=None):
@@ -334,11 +340,15 @@ class DetectionEntry:
         self._seq = 0
         self._epoch = models.weights_epoch()
         self.capture_seconds = 0.0
-        # canvas passes need the ResNet trunk's extent masks (nets.ResNetBase) and the device-side preprocess
+        # canvas passes need the base's extent masks (nets.ResNetBase, nets.VggBase: ``extents_class`` names the table of true sizes it
+        # reads and where an image sits in its canvas) and the device-side preprocess
         net = getattr(getattr(manager.rpn_model, "base", None), "net", None)
-        # (FRCNN_ENTRY_CANVAS=0 switches them off: every geometry then gets passes of its own, as in round 5.)  Measured on bench.py's
-        # mixed_sizes legs (256 frames, 36 geometries): see DESIGN 5 / 7.
-        self.canvas_capable = self.device_preprocess and hasattr(net, "block_level") and os.environ.get("FRCNN_ENTRY_CANVAS", "1") != "0"
+        self._extents_class = getattr(net, "extents_class", None)
+        # (FRCNN_ENTRY_CANVAS=0 switches them off: every geometry then gets passes of its own, as in round 5; =1 switches them on for a base
+        # whose canvases are opt-in -- VGG16, ``canvas_by_default`` False until its mixed-list rate is measured.)  Measured on bench.py's
+        # mixed_sizes legs (256 frames, 36 geometries) for ResNet: see DESIGN 5 / 7.
+        want = os.environ.get("FRCNN_ENTRY_CANVAS", "1" if getattr(net, "canvas_by_default", False) else "0") != "0"
+        self.canvas_capable = self.device_preprocess and self._extents_class is not None and want
         self.canvas = False                              # set per call by voc_dets.get_dets_by_cls
         self._canvas_of = {}                             # (H, W) -> canvas class: the plan (plan_canvases) + sizes seen outside it
         self._canvas_slots = {}                          # canvas class -> captured passes it may hold (its share of the list x in_flight)
@@ -400,7 +410,6 @@ class DetectionEntry:
         eager launches in front of every replay), the graph holds trunk .. post-process with the images' true extents read from
         ``s.extents`` (device words)."""
         import time
-        from . import nets
         m = self.manager
         kw = dict(stride=self.stride, pre_nms_top_n=PRE_NMS_TOP_N, max_proposals=MAX_PROPOSALS, roi_batch=self.num_rois, pad_to_batch=PAD_TO_BATCH,
                   bg_idx=m.class_mapping["bg"])
@@ -429,8 +438,8 @@ class DetectionEntry:
         s.u8_resized = torch.empty((B, seg), dtype=torch.uint8, device="cuda")
         s.x_f32 = torch.zeros((B, Hc, Wc, 3), dtype=torch.float32, device="cuda")
         stamps.append(("buffers: canvases", time.perf_counter()))
-        s._ext_raw = self._pinned.take(nets.Extents.LEVELS * B * 8)
-        s.extents = nets.Extents(B, pinned=s._ext_raw)
+        s._ext_raw = self._pinned.take(self._extents_class.LEVELS * B * 8)
+        s.extents = self._extents_class(B, pinned=s._ext_raw)
         for i in range(B):
             s.extents.set(i, Hc, Wc)
         s.extents.upload()
@@ -495,11 +504,12 @@ class DetectionEntry:
             j = i if i < len(images) else 0
             arr, H, W, src, flip = pixels[j]
             arr = np.ascontiguousarray(arr)
-            assert arr.dtype == np.uint8 and arr.nbytes <= s.seg and H + (H & 1) <= Hc and W + (W & 1) <= Wc, "one pass, one canvas class"
+            oy, ox = s.extents.offset_of(H, W)                      # ResNet: (H & 1, W & 1); VGG16: (0, 0)
+            assert arr.dtype == np.uint8 and arr.nbytes <= s.seg and H + oy <= Hc and W + ox <= Wc, "one pass, one canvas class"
             s.pix_hosts[i][:arr.nbytes] = arr.reshape(-1)
             s.dyn_host[i, 0], s.dyn_host[i, 1] = float(resize_ratios[j]), float(det_threshold)
             s.extents.set(i, H, W)
-            metas.append((arr.shape[0], arr.shape[1], H, W, src, flip))
+            metas.append((arr.shape[0], arr.shape[1], H, W, src, flip, (oy, ox)))
         st = self._streams[self._seq % self.in_flight]
         self._seq += 1
         with torch.cuda.stream(st):
@@ -508,12 +518,12 @@ class DetectionEntry:
                 s.ready = None
             s.io_dev.copy_(s.io_pin, non_blocking=True)
             s.extents.upload()
-            for i, (in_h, in_w, H, W, src, flip) in enumerate(metas):
+            for i, (in_h, in_w, H, W, src, flip, offset) in enumerate(metas):
                 frame = s.io_dev[i * s.seg:i * s.seg + in_h * in_w * 3].view(in_h, in_w, 3)
                 if src is not None:                                 # shapes.Image.data: INTER_CUBIC resize (+ flip) of the decoded frame
                     frame = ops.resize_cubic_u8(frame, H, W, flip=flip, tabs=(self._device_taps(W, in_w), self._device_taps(H, in_h)),
                                                 out=s.u8_resized[i][:H * W * 3].view(H, W, 3))
-                ops.preprocess_u8_canvas(frame, MEAN_BGR, s.x_f32[i])
+                ops.preprocess_u8_canvas(frame, MEAN_BGR, s.x_f32[i], offset=offset)
             s.graph.replay()
             for i in range(len(images)):
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
@@ -853,6 +863,7 @@ class DetectionEntry:
         return {"graphs": len(c), "sizes": len(c.keys()), "bytes": c.nbytes, "byte_budget": c.byte_budget, "captures": c.captures,
                 "hits": c.hits, "evictions": c.evictions, "capture_seconds": round(self.capture_seconds, 3), "in_flight": self.in_flight,
                 "device_preprocess": self.device_preprocess, "f32_engine": self.f32_engine, "images_per_pass": self.batch,
+                "canvas_slots": {"%dx%d" % k[1:3]: v for k, v in self._canvas_slots.items()},      # canvas class "HcxWc" -> captured passes its plan allows
                 "capture_breakdown_ms": {k: round(v, 1) for k, v in self.capture_breakdown.items()}}
 
 

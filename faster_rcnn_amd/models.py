@@ -154,7 +154,7 @@ class RpnModel(_Model):
         return [self.base.net, self.head]
 
     def forward_dev(self, x, extents=None):
-        """``extents`` (nets.Extents): x holds canvases (ResNet bases; see nets.ResNetBase.__call__)."""
+        """``extents`` (nets.Extents): x holds canvases (nets.ResNetBase.__call__; a VGG16 base reads a nets.VggExtents)."""
         feat = self.base.net(x) if extents is None else self.base.net(x, extents)
         cls, reg = self.head(feat)
         return cls, reg, feat

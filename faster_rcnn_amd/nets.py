@@ -154,8 +154,16 @@ TRUNK_PLANES = _os.environ.get("FRCNN_TRUNK_PLANES", "0") != "0"
 class Extents:
     """The true extents of the images of a CANVAS pass (round 6; ops.zero_outside): a device int32 table [level][image][rows, cols] with
     levels 0 = after the stem's pool (stage 2), 1 = stage 3, 2 = stage 4 (the conv4 map) of a ResNet base.  The table's address is
-    fixed (a captured pass bakes it in); ``set(i, H, W)`` writes image i's rows of the HOST copy, ``upload()`` sends it."""
+    fixed (a captured pass bakes it in); ``set(i, H, W)`` writes image i's rows of the HOST copy, ``upload()`` sends it.  A network
+    names the table it reads as ``extents_class`` (VggBase: VggExtents); ``conv_map()`` is the level of the map the RPN reads."""
     LEVELS = 3
+    CONV_LEVEL = 2
+
+    @staticmethod
+    def offset_of(height, width):
+        """Where an image of this size sits in its canvas: the extra zero row / column SAME padding at stride 2 puts in front of an odd
+        side under conv1's 7x7 window (csrc/boxes.hip)."""
+        return height & 1, width & 1
 
     def __init__(self, batch, pinned=None):
         """``pinned``: a pinned uint8 host tensor of at least LEVELS * batch * 8 bytes to use as the host copy (entry.DetectionEntry cuts it
@@ -190,6 +198,30 @@ class Extents:
 
     def level(self, lvl):
         return self.table[lvl]
+
+    def conv_map(self):
+        """(batch, 2) device words: the true (rows, cols) of each image's conv map (what the RPN and the proposal decode read)."""
+        return self.table[self.CONV_LEVEL]
+
+
+class VggExtents(Extents):
+    """``Extents`` for a VGG16 base: five levels, 0 = the image (block 1), k = behind block k's pool, 4 = the conv map (block 5).  Every
+    VGG16 conv is 3x3 SAME at stride 1 (no padding depends on the size) and the four pools are VALID 2x2 / 2, so an image sits at
+    canvas offset (0, 0) whatever its parities and its true extent halves with floor at each pool (vgg.get_conv_rows_cols' chain)."""
+    LEVELS = 5
+    CONV_LEVEL = 4
+
+    @staticmethod
+    def offset_of(height, width):
+        return 0, 0
+
+    @staticmethod
+    def levels_of(height, width):
+        """[(rows, cols)] per level: (h, w), then (n - 2) // 2 + 1 = n // 2 per MaxPooling2D((2,2), strides=(2,2)) (vgg.py:100-128)."""
+        out = [(int(height), int(width))]
+        for _ in range(4):
+            out.append((out[-1][0] // 2, out[-1][1] // 2))
+        return out
 
 
 def run_block(u, x, layout=0, planes=False, mask=None, out_planes=False):
@@ -239,6 +271,8 @@ class ResNetBase:
     """conv1 .. stage 4 (resnet50_base resnet.py:395-448, resnet101_base :551-602)."""
     stride = 16
     out_channels = 1024
+    extents_class = Extents                                  # the table a canvas pass of this base reads (entry.DetectionEntry)
+    canvas_by_default = True                                 # (measured: DESIGN 5 / 7)
 
     def __init__(self, weights, depth, dtype="f32"):
         self.weights, self.depth, self.dtype = weights, depth, dtype
@@ -299,7 +333,7 @@ class ResNetBase:
         for b, lvl in zip(self.blocks, self.block_level):
             x = run_block(b, x, planes=planes, mask=None if extents is None else extents.level(lvl))
         if extents is not None:
-            x = ops.zero_outside(x, extents.level(2))
+            x = ops.zero_outside(x, extents.conv_map())
         return x
 
 
@@ -311,6 +345,11 @@ class VggBase:
     ReLU in the epilogue) and the four pools ``pool2d_bf16``; every stored activation is bf16, the output map too."""
     stride = 16
     out_channels = 512
+    extents_class = VggExtents                               # the table a canvas pass of this base reads (entry.DetectionEntry)
+    # canvas passes of this base are OPT-IN (FRCNN_ENTRY_CANVAS=1): they are held to the exact passes bit for bit, but their rate on a
+    # mixed list has not been measured against the exact-geometry passes yet (f32 gives up the fp16-plane hand-overs, 8 / 9 mask
+    # launches, pixels padded per class) -- scripts/bench_vgg.py --mixed [--canvas 0] is the measurement that decides the default
+    canvas_by_default = False
 
     def __init__(self, weights, dtype="f32"):
         assert dtype in ("f32", "bf16"), dtype
@@ -347,10 +386,36 @@ class VggBase:
                 x = ops.pool2d_bf16(x, 2, 2)
         return x
 
-    def __call__(self, x):
-        """Round 6: a convolution whose output has ONE reader, the next convolution of its block, hands it on as the fp16 planes that one
+    def _forward_canvas(self, x, extents):
+        """A canvas pass, f32 or bf16: a pool reads the unmasked conv map and writes a masked one, every other conv -> conv hand-over
+        (and block5_conv3 -> rpn_conv1) is a zero_outside launch at its level.  bf16: block1_conv1 stores its own zeros (8 zero_outside
+        launches are left); f32: it is an engine launch like the others (9), and every hand-over is an f32 tensor -- no fp16 planes
+        cross a mask, as in ResNetBase."""
+        assert isinstance(extents, VggExtents), "a VGG16 canvas pass reads a five-level table (nets.VggExtents)"
+        bf16 = self.dtype == "bf16"
+        pool = ops.pool2d_bf16_extents if bf16 else ops.pool2d_extents
+        convs, lvl = self.convs, 0
+        if bf16:
+            x, convs = ops.vgg_conv1_bf16_extents(x, self.lower_conv1_bf16(), extents.level(0)), convs[1:]
+        for name, u in convs:
+            x = u(x)
+            if name in self.POOLED:
+                x = pool(x, extents.level(lvl))
+                lvl += 1
+            else:
+                x = ops.zero_outside(x, extents.level(lvl))
+        return x
+
+    def __call__(self, x, extents=None):
+        """``extents`` (VggExtents): x is a batch of canvases, each image at offset (0, 0), with those true sizes: every tensor a 3x3
+        convolution reads is zero beyond its image's extent (13 masks per pass: 4 pools + 8 zero_outside + conv1 in bf16, 4 + 9 in f32),
+        the conv map at the end too (rpn_conv1 is a 3x3).  None: exactly the launches below.
+
+        Round 6: a convolution whose output has ONE reader, the next convolution of its block, hands it on as the fp16 planes that one
         multiplies where both launches run on the f16x3 engine's 256x128 tile (ops.PlaneTensor, as inside the ResNet head's blocks): the
         reader's loader splits nothing and, its reduction being 36-144 chunks long, walks the direct-to-LDS ring."""
+        if extents is not None:
+            return self._forward_canvas(x, extents)
         if self.dtype == "bf16":
             return self._forward_bf16(x)
         for k, (name, u) in enumerate(self.convs):

@@ -956,6 +956,19 @@ def pool2d(x, k, stride, is_max=True, planes_out=False):
     return amax_carry(out, x)                                    # max / mean of a window never exceeds the largest |input|
 
 
+def pool2d_extents(x, true_hw):
+    """MaxPooling2D((2,2), strides=(2,2)) on the f32 tensors of a canvas pass (frcnn_pool2d_fwd_extents): x (n,hc,wc,C) need NOT be masked;
+    true_hw = device int32 (n,2), image i's true (rows, cols) at x's level.  Inside floor(rows/2) x floor(cols/2) the result is
+    ``pool2d(x_true, 2, 2)`` bit for bit, every other cell is zero.  Always an f32 tensor (a canvas pass hands no planes across a mask)."""
+    _require_gpu()
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+    assert true_hw.dtype == torch.int32 and true_hw.is_cuda and true_hw.numel() >= 2 * x.shape[0]
+    n, h, w, c = (int(v) for v in x.shape)
+    out = torch.empty((n, h // 2, w // 2, c), dtype=torch.float32, device="cuda")
+    _lib.call("frcnn_pool2d_fwd_extents", _p(x), n, h, w, c, _p(true_hw), _p(out), _stream())
+    return amax_carry(out, x)                                    # a maximum (or a zero) never exceeds the largest |input|
+
+
 def softmax_rows(x, cols=None):
     _require_gpu()
     rows, ld = x.shape
@@ -1434,4 +1447,31 @@ def pool2d_bf16(x, k, stride):
     args = (_p(x), n, h, w, c, k, stride, _p(out))
     _lib.call("frcnn_pool2d_fwd_bf16", *args, _stream())
     _record_launch(lambda: "k_pool2_bf16", (out.numel() // c, c, k * k, 1), "frcnn_pool2d_fwd_bf16", args, (x, out))
+    return out
+
+
+def vgg_conv1_bf16_extents(x, packed, true_hw):
+    """``vgg_conv1_bf16`` on canvases (frcnn_vgg_conv1_bf16_fwd_extents): x (n,hc,wc,3) f32, true_hw = device int32 (n,2), image i's true
+    (rows, cols).  Inside the extent the map of the true-size image bit for bit, zero everywhere else."""
+    _require_gpu()
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[-1] == 3
+    assert true_hw.dtype == torch.int32 and true_hw.is_cuda and true_hw.numel() >= 2 * x.shape[0]
+    n, h, w, _ = x.shape
+    out = torch.empty((n, h, w, 64), dtype=torch.bfloat16, device="cuda")
+    args = (_p(x), n, h, w, _p(packed.w), _p(packed.bias), _p(true_hw), _p(out))
+    _lib.call("frcnn_vgg_conv1_bf16_fwd_extents", *args, _stream())
+    _record_launch(lambda: "k_vgg_conv1_bf16", (n * h * w, 64, 27, 1), "frcnn_vgg_conv1_bf16_fwd_extents", args, (x, packed, out, true_hw))
+    return out
+
+
+def pool2d_bf16_extents(x, true_hw):
+    """``pool2d_bf16(x, 2, 2)`` on the bf16 tensors of a canvas pass (frcnn_pool2d_fwd_bf16_extents): see ``pool2d_extents``."""
+    _require_gpu()
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 4
+    assert true_hw.dtype == torch.int32 and true_hw.is_cuda and true_hw.numel() >= 2 * x.shape[0]
+    n, h, w, c = (int(v) for v in x.shape)
+    out = torch.empty((n, h // 2, w // 2, c), dtype=torch.bfloat16, device="cuda")
+    args = (_p(x), n, h, w, c, _p(true_hw), _p(out))
+    _lib.call("frcnn_pool2d_fwd_bf16_extents", *args, _stream())
+    _record_launch(lambda: "k_pool2_extents", (out.numel() // c, c, 4, 1), "frcnn_pool2d_fwd_bf16_extents", args, (x, out, true_hw))
     return out

@@ -57,7 +57,7 @@ class InferencePipeline:
         scored too when the pipeline was built with ``pad_to_batch`` (voc_dets.py:42-51)."""
         ops.amax_begin()                                    # f16x3 engine: this pass's magnitude records start from zero
         cls, reg, feat = self.rpn.forward_dev(x) if extents is None else self.rpn.forward_dev(x, extents)
-        rois, n_keep, cand, keep = self.proposals_dev(cls, reg, true_rc=None if extents is None else extents.level(2)[0])
+        rois, n_keep, cand, keep = self.proposals_dev(cls, reg, true_rc=None if extents is None else extents.conv_map()[0])
         out_cls, out_reg = self.det.forward_dev(feat, rois)
         res = {"rpn_cls": cls, "rpn_reg": reg, "feat": feat, "rois": rois, "n_rois": n_keep,
                "cls": out_cls, "reg": out_reg}
@@ -230,7 +230,7 @@ class BatchedInferencePipeline(InferencePipeline):
         cls, reg, feat = self.rpn.forward_dev(x) if extents is None else self.rpn.forward_dev(x, extents)
         rois = torch.empty((B * self.n_rois, 4), dtype=torch.float32, device="cuda")
         n_keep = self._fan_out(lambda i: self.proposals_dev(cls[i], reg[i], rois_out=rois[i * self.n_rois:(i + 1) * self.n_rois],
-                                                            true_rc=None if extents is None else extents.level(2)[i])[1])
+                                                            true_rc=None if extents is None else extents.conv_map()[i])[1])
         out_cls, out_reg = self.det.head.forward_batched(feat, rois, self.n_rois)
         res = {"rpn_cls": cls, "rpn_reg": reg, "feat": feat, "rois": rois.view(B, self.n_rois, 4), "n_rois": n_keep,
                "cls": out_cls.view(B, self.n_rois, -1), "reg": out_reg.view(B, self.n_rois, -1)}

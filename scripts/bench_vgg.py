@@ -6,6 +6,8 @@ detector head + post-process) through captured passes; img/s and the per-launch 
     python scripts/bench_vgg.py --captured --dtype bf16
     python scripts/bench_vgg.py --detector --engine f16x3     # f32 detector, one image per pass
     python scripts/bench_vgg.py --detector --dtype bf16 --batch 8
+    python scripts/bench_vgg.py --mixed --dtype bf16          # a shuffled list of mixed sizes through voc_dets.get_dets_by_cls (canvas passes)
+    python scripts/bench_vgg.py --mixed --dtype bf16 --canvas 0     # ... through exact-geometry passes (what a VGG16 list got before canvases)
 """
 import argparse
 import os
@@ -29,11 +31,13 @@ ap.add_argument("--streams", type=int, default=1, help="captured passes in fligh
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--runs", type=int, default=1, help="timed runs of --steps replays each")
 ap.add_argument("--no-table", action="store_true")
+ap.add_argument("--mixed", action="store_true", help="256 frames over the geometries of bench.py's mixed_sizes leg through voc_dets.get_dets_by_cls")
+ap.add_argument("--canvas", type=int, default=1, help="--mixed: 0 = exact-geometry passes (FRCNN_ENTRY_CANVAS=0's policy)")
 args = ap.parse_args()
 engine = args.engine or ops.F32_ENGINE
 
 anchors = util.get_anchors([128, 256, 512])
-w = synthetic_vgg16(anchors_per_loc=9, seed=1, with_classifier=args.detector)
+w = synthetic_vgg16(anchors_per_loc=9, seed=1, with_classifier=args.detector or args.mixed)
 base = vgg.vgg16_base(weights=w, dtype=args.dtype)
 rpn = vgg.vgg16_rpn(base, include_conv=True, anchors_per_loc=9)
 rs = np.random.RandomState(0)
@@ -72,7 +76,67 @@ def table(forward):
     return prof
 
 
-if args.detector:
+def mixed_leg(n_images=256, seed=77):
+    """bench.py's mixed_sizes list (same histogram, seed and construction: 36 geometries after the resize within 600 / 1000) with the
+    VGG16 pair: the first call in a warm process (one frame of another size has been through the entry point), the same call again,
+    captures, eager images and the bytes the captured passes hold."""
+    import contextlib
+    import io
+    import json
+    from bench import MIXED_SIZES
+    from faster_rcnn_amd import entry, shapes, voc_dets
+    from faster_rcnn_amd.data.voc_data_helpers import VOC_CLASS_MAPPING
+    from faster_rcnn_amd.det_util import DetTrainingManager
+    det = vgg.vgg16_classifier(64, 21, weights=w, dtype=args.dtype)
+    mgr = DetTrainingManager(rpn_model=rpn, class_mapping=VOC_CLASS_MAPPING, preprocess_func=vgg.preprocess, anchor_dims=anchors)
+    rs = np.random.RandomState(seed)
+    sizes = []
+    for (wd, h), share in MIXED_SIZES:
+        sizes += [(wd, h)] * int(round(share * n_images))
+    while len(sizes) < n_images:
+        sizes.append((500, int(rs.randint(250, 500))))
+    sizes = sizes[:n_images]
+    rs.shuffle(sizes)
+    pool, raw = {}, []
+    for i, (wd, h) in enumerate(sizes):
+        if (wd, h) not in pool:
+            pool[(wd, h)] = rs.randint(0, 256, (h, wd, 3)).astype(np.uint8)
+        raw.append(shapes.Image(shapes.Metadata("mixed%03d" % i, wd, h, [], "none"), pool[(wd, h)]))
+    images, ratios = util.resize_imgs(raw, min_size=600, max_size=1000)
+    os.environ["FRCNN_ENTRY_CANVAS"] = "1" if args.canvas else "0"     # (VGG16 canvases are opt-in)
+    eng = entry.for_models(mgr, det, 64, 16, entry.default_in_flight(args.dtype))
+    eager = [0]
+    real = voc_dets._get_dets_eager
+    voc_dets._get_dets_eager = lambda *a, **k: (eager.__setitem__(0, eager[0] + 1), real(*a, **k))[1]
+
+    def run(imgs, rts):
+        with contextlib.redirect_stdout(io.StringIO()):
+            t0 = time.perf_counter()
+            voc_dets.get_dets_by_cls(mgr, det, rts, imgs)
+            return time.perf_counter() - t0
+    warm = shapes.Image(shapes.Metadata("warm", 480, 320, [], "none"), rs.randint(0, 256, (320, 480, 3)).astype(np.uint8))
+    run([warm], [1.0])                                           # the process is warm: library loaded, filters packed, allocator primed
+    eng.cache.clear()
+    eager[0] = 0
+    before = eng.stats()
+    t1 = run(images, ratios)
+    mid, e1 = eng.stats(), eager[0]
+    t2 = run(images, ratios)
+    after = eng.stats()
+    print(json.dumps({"leg": "VGG16 %s mixed sizes, %s" % (args.dtype, "canvas passes" if eng.canvas_capable else "exact-geometry passes"),
+                      "images": n_images, "geometries": len({(im.height, im.width) for im in images}),
+                      "first_call_img_s": round(n_images / t1, 1), "second_call_img_s": round(n_images / t2, 1),
+                      "captures_first": mid["captures"] - before["captures"], "captures_second": after["captures"] - mid["captures"],
+                      "eager_images_first": e1, "eager_images_second": eager[0] - e1, "bytes_held": after["bytes"], "graphs": after["graphs"],
+                      "canvas_classes": sorted({k[1:3] for k in eng.cache.keys() if k[:1] == ("canvas",)}),
+                      "images_per_pass": eng.batch, "in_flight": eng.in_flight, "f32_engine": eng.f32_engine,
+                      "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "4")}))
+    eng.cache.clear()
+
+
+if args.mixed:
+    mixed_leg()
+elif args.detector:
     from faster_rcnn_amd.pipeline import BatchedInferencePipeline, InferencePipeline
     det = vgg.vgg16_classifier(64, 21, weights=w, dtype=args.dtype)
     make = (lambda: BatchedInferencePipeline(rpn, det, anchors, B, max_proposals=300)) if B > 1 else (lambda: InferencePipeline(rpn, det, anchors, max_proposals=300))
