@@ -29,13 +29,14 @@ models, the same call runs here as ONE captured pass per image:
 """
 import collections
 import os
+import time
 
 import numpy as np
 import torch
 
 from . import models, ops
 from ._lib import FrcnnError
-from .pipeline import InferencePipeline
+from .pipeline import BatchedInferencePipeline, InferencePipeline, no_gc
 from .shapes import declares as _declares
 
 MEAN_BGR = (103.939, 116.779, 123.68)           # resnet.preprocess / vgg.preprocess (resnet.py:64-75, vgg.py:52-57)
@@ -212,10 +213,15 @@ def _capture_stream():
 
 
 class _Slot:
-    """One captured pass for one image size, with its staging on both sides of PCIe."""
-    __slots__ = ("key", "pipe", "graph", "out", "io_dev", "io_pin", "pix_host", "dyn_host", "out_pin", "event", "busy", "nbytes",
-                 "x_f32", "ws", "seq", "tabs", "u8_resized", "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw",
-                 "annotate", "frame_io")
+    """One captured pass for one image size (or canvas class), with its staging on both sides of PCIe.  Every field exists on every slot;
+    what a kind of pass does not use stays None (``tabs`` / ``frame_io``: exact passes; ``extents`` / ``_ext_raw``: canvas passes)."""
+    __slots__ = ("key", "pipe", "graph", "out", "io_dev", "io_pin", "dyn_host", "out_pin", "event", "busy", "nbytes", "x_f32", "ws", "tabs", "u8_resized",
+                 "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io")
+
+    def __init__(self):
+        for name in self.__slots__:
+            setattr(self, name, None)
+        self.busy = self.canvas = self.annotate = False
 
 
 def _close_slot(s):
@@ -223,19 +229,16 @@ def _close_slot(s):
     references to its tensors are dropped, so that nothing is left for a garbage-collector finalizer to do later from whatever thread
     happens to collect (a finalizer issuing HIP calls inside another capture crashed a launch).  Idle slots only."""
     assert not s.busy, "closing a captured pass with an image in flight"
-    if getattr(s, "ready", None) is not None:
+    if s.ready is not None:
         s.ready.synchronize()                            # (never replayed: its warm-up pass may still be writing the slot's buffers)
-    if getattr(s, "graph", None) is not None:
+    if s.graph is not None:
         s.event.synchronize()                            # its last replay (and the copies behind it) are done
         s.graph.reset()
-    if getattr(s, "pipe", None) is not None and hasattr(s.pipe, "close"):
+    if s.pipe is not None and hasattr(s.pipe, "close"):
         s.pipe.close()
-    for name in ("io_pin", "_out_raw", "_ext_raw"):
-        piece = getattr(s, name, None)
-        if piece is not None:
-            _PinnedArena.give_back(piece)
-    for name in ("graph", "out", "out_packed", "io_dev", "x_f32", "u8_resized", "tabs", "ws", "amax", "pipe", "io_pin", "_out_raw", "out_pin", "pix_hosts", "pix_host", "dyn_host", "extents", "_ext_raw", "frame_io"):
-        setattr(s, name, None)
+    for name in s.__slots__:
+        _PinnedArena.give_back(getattr(s, name))         # (the fields cut from the pinned arena: only those carry a block)
+    s.__init__()                                         # every field back to its default: the slot holds nothing
 
 
 class GraphCache:
@@ -376,27 +379,6 @@ class DetectionEntry:
         return 0 < n_rows <= 512                        # frcnn_detections: one workgroup, <= 512 scored rows
 
     # ------------------------------------------------------------------ capture
-    def _capture(self, H, W, src=None, flip=False, B=1, annotate=False):
-        """``src`` = (source height, source width): the pass starts from the decoded frame at the file's size and resizes
-        (and flips) it on the device; None: the uploaded pixels are already (H, W).  ``B`` > 1: one pass over B frames of that
-        geometry (pipeline.BatchedInferencePipeline), each with its own [resize_ratio, det_threshold] pair.  ``annotate``: the
-        pass then draws each frame's detections into its uploaded source frame (ops.annotate_u8, annotate_video.py)."""
-        import gc
-        import time
-        t0 = time.perf_counter()
-        # No cyclic-garbage collection inside the capture: a collection that starts while the stream is capturing may run the
-        # finalizers of unrelated dead objects -- another engine's captured passes, their private memory pools -- whose HIP calls
-        # are not legal in a capturing thread (seen as a crash inside a launch when a test's models died just before).
-        gc_was_on = gc.isenabled()
-        from .pipeline import collect_before_capture
-        collect_before_capture()                                    # (at most one full collection per second: it costs more than the capture)
-        gc.disable()
-        try:
-            return self._capture_locked(H, W, src, flip, B, t0, annotate)
-        finally:
-            if gc_was_on:
-                gc.enable()
-
     def _device_taps(self, dst, src):
         t = self._taps_dev.get((dst, src))
         if t is None:
@@ -405,172 +387,42 @@ class DetectionEntry:
             t = self._taps_dev[(dst, src)] = torch.from_numpy(ops.resize_cubic_taps(dst, src)).cuda()
         return t
 
-    def _capture_canvas_locked(self, Hc, Wc, B, t0):
-        """A pass over B canvases of (Hc, Wc): the frames' resize + preprocess stay OUTSIDE the graph (their sizes are per image: a few
-        eager launches in front of every replay), the graph holds trunk .. post-process with the images' true extents read from
-        ``s.extents`` (device words)."""
-        import time
-        m = self.manager
-        kw = dict(stride=self.stride, pre_nms_top_n=PRE_NMS_TOP_N, max_proposals=MAX_PROPOSALS, roi_batch=self.num_rois, pad_to_batch=PAD_TO_BATCH,
-                  bg_idx=m.class_mapping["bg"])
-        if B > 1:
-            from .pipeline import BatchedInferencePipeline
-            pipe = BatchedInferencePipeline(m.rpn_model, self.detector, m.anchor_dims, B, **kw)
-        else:
-            pipe = InferencePipeline(m.rpn_model, self.detector, m.anchor_dims, **kw)
-        reserved0 = torch.cuda.memory_reserved()
-        stamps = [("pipeline", time.perf_counter())]
-        seg = (Hc * Wc * 3 + 15) // 16 * 16                         # a frame's staging segment: any source of at most the canvas's pixel count
-        off = B * seg
-        s = _Slot()
-        s.key, s.pipe, s.busy, s.seq, s.batch, s.canvas, s.seg = ("canvas", Hc, Wc), pipe, False, 0, B, True, seg
+    def _stage(self, s, seg, fine):
+        """The slot's staging on both sides of PCIe: [B frame segments of ``seg`` bytes | B x (resize_ratio, det_threshold)].
+        -> (the pinned side as a numpy array, the device view the pass reads the pairs from: (B, 2) f64, one image's (2,) for B = 1)."""
+        B, off = s.batch, s.batch * seg
+        s.seg = seg
         s.io_dev = torch.zeros(off + 16 * B, dtype=torch.uint8, device="cuda")
-        stamps.append(("buffers: device staging", time.perf_counter()))
+        fine("buffers: device staging")
         s.io_pin = self._pinned.take(off + 16 * B, zero=True)
-        stamps.append(("buffers: pinned staging", time.perf_counter()))
+        fine("buffers: pinned staging")
         host = s.io_pin.numpy()
-        s.pix_hosts = [host[i * seg:(i + 1) * seg] for i in range(B)]
-        s.pix_host = s.pix_hosts[0]
         s.dyn_host = host[off:off + 16 * B].view(np.float64).reshape(B, 2)
         s.dyn_host[:] = (1.0, 0.0)
         dyn_dev = s.io_dev[off:off + 16 * B].view(torch.float64).view(B, 2)
-        s.tabs = None
-        s.u8_resized = torch.empty((B, seg), dtype=torch.uint8, device="cuda")
-        s.x_f32 = torch.zeros((B, Hc, Wc, 3), dtype=torch.float32, device="cuda")
-        stamps.append(("buffers: canvases", time.perf_counter()))
-        s._ext_raw = self._pinned.take(self._extents_class.LEVELS * B * 8)
-        s.extents = self._extents_class(B, pinned=s._ext_raw)
-        for i in range(B):
-            s.extents.set(i, Hc, Wc)
-        s.extents.upload()
-        run = lambda: pipe.forward_dev(s.x_f32, dyn=dyn_dev if B > 1 else dyn_dev[0], extents=s.extents)
-        shared = self.in_flight > 1
-        dtype = getattr(getattr(self.detector, "head", None), "dtype", "f32")
-        s.ws = ops.NO_SPLIT_K if ((shared and (dtype == "bf16" or os.environ.get("FRCNN_ENTRY_NO_SPLITK"))) or B > 1) else ops.ConvWorkspace()
-        stamps.append(("buffers: extents", time.perf_counter()))
-        s.io_dev.copy_(s.io_pin)
-        stamps.append(("buffers: first upload", time.perf_counter()))
-        s.amax = ops.AmaxArena() if self.f32_engine == "f16x3" else None
-        side = _capture_stream()
-        side.wait_stream(torch.cuda.current_stream())
-        stamps.append(("buffers", time.perf_counter()))
-        with torch.cuda.stream(side), ops.conv_workspace(s.ws), ops.tile_policy(shared), ops.f32_engine(self.f32_engine), ops.amax_arena(s.amax):
-            for _ in range(WARMUP_PASSES):
-                run()
-            stamps.append(("warm-up enqueue", time.perf_counter()))
-            s.ready = torch.cuda.Event()
-            s.ready.record(side)
-            s.graph = torch.cuda.CUDAGraph()
-            s.graph.capture_begin(pool=torch.cuda.graph_pool_handle(), capture_error_mode="thread_local")
-            try:
-                s.out = run()
-                stamps.append(("capture enqueue", time.perf_counter()))
-            finally:
-                s.graph.capture_end()
-        stamps.append(("instantiate", time.perf_counter()))
-        packed = s.out["det_packed"]
-        s.out_packed = packed if isinstance(packed, (list, tuple)) else [packed]
-        s._out_raw = self._pinned.take(4 * B * s.out_packed[0].numel())
-        s.out_pin = s._out_raw.view(torch.int32).view((B,) + tuple(s.out_packed[0].shape))
-        s.event = torch.cuda.Event()
-        s.nbytes = max(int(torch.cuda.memory_reserved() - reserved0), int(s.io_dev.numel() + s.x_f32.numel() * 4))
-        stamps.append(("read-back buffers", time.perf_counter()))
-        self.capture_seconds += time.perf_counter() - t0
-        self._book_capture(t0, stamps)
-        return s
+        return host, (dyn_dev if B > 1 else dyn_dev[0])
 
-    def _capture_canvas(self, Hc, Wc, B):
-        import gc
-        import time
-        t0 = time.perf_counter()
-        gc_was_on = gc.isenabled()
-        from .pipeline import collect_before_capture
-        collect_before_capture()
-        gc.disable()
-        try:
-            return self._capture_canvas_locked(Hc, Wc, B, t0)
-        finally:
-            if gc_was_on:
-                gc.enable()
-
-    def _submit_canvas(self, images, resize_ratios, det_threshold, pixels, B):
-        """``submit_batch`` in canvas mode: per image the frame goes up at ITS size, is resized (and flipped) to ITS (H, W) and
-        preprocessed into the corner of canvas i by eager launches on the pass's stream; the true sizes go up as extents."""
-        _, H0, W0, _, _ = pixels[0]
-        Hc, Wc = self.canvas_class(H0, W0)
-        s = self.cache.acquire(("canvas", Hc, Wc) + ((B,) if B > 1 else ()), lambda: self._capture_canvas(Hc, Wc, B))
-        metas = []
-        for i in range(B):
-            j = i if i < len(images) else 0
-            arr, H, W, src, flip = pixels[j]
-            arr = np.ascontiguousarray(arr)
-            oy, ox = s.extents.offset_of(H, W)                      # ResNet: (H & 1, W & 1); VGG16: (0, 0)
-            assert arr.dtype == np.uint8 and arr.nbytes <= s.seg and H + oy <= Hc and W + ox <= Wc, "one pass, one canvas class"
-            s.pix_hosts[i][:arr.nbytes] = arr.reshape(-1)
-            s.dyn_host[i, 0], s.dyn_host[i, 1] = float(resize_ratios[j]), float(det_threshold)
-            s.extents.set(i, H, W)
-            metas.append((arr.shape[0], arr.shape[1], H, W, src, flip, (oy, ox)))
-        st = self._streams[self._seq % self.in_flight]
-        self._seq += 1
-        with torch.cuda.stream(st):
-            if s.ready is not None:
-                st.wait_event(s.ready)
-                s.ready = None
-            s.io_dev.copy_(s.io_pin, non_blocking=True)
-            s.extents.upload()
-            for i, (in_h, in_w, H, W, src, flip, offset) in enumerate(metas):
-                frame = s.io_dev[i * s.seg:i * s.seg + in_h * in_w * 3].view(in_h, in_w, 3)
-                if src is not None:                                 # shapes.Image.data: INTER_CUBIC resize (+ flip) of the decoded frame
-                    frame = ops.resize_cubic_u8(frame, H, W, flip=flip, tabs=(self._device_taps(W, in_w), self._device_taps(H, in_h)),
-                                                out=s.u8_resized[i][:H * W * 3].view(H, W, 3))
-                ops.preprocess_u8_canvas(frame, MEAN_BGR, s.x_f32[i], offset=offset)
-            s.graph.replay()
-            for i in range(len(images)):
-                s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
-            s.event.record(st)
-        s.busy = True
-        return Ticket(s, list(images))
-
-    def _capture_locked(self, H, W, src, flip, B, t0, annotate=False):
-        import time
-        m = self.manager
-        kw = dict(stride=self.stride, pre_nms_top_n=PRE_NMS_TOP_N, max_proposals=MAX_PROPOSALS, roi_batch=self.num_rois, pad_to_batch=PAD_TO_BATCH,
-                  bg_idx=m.class_mapping["bg"])
-        if B > 1:
-            from .pipeline import BatchedInferencePipeline
-            pipe = BatchedInferencePipeline(m.rpn_model, self.detector, m.anchor_dims, B, **kw)
-        else:
-            pipe = InferencePipeline(m.rpn_model, self.detector, m.anchor_dims, **kw)
-        reserved0 = torch.cuda.memory_reserved()
-        stamps = [("pipeline", time.perf_counter())]
+    def _exact_pass(self, s, fine, H, W, src, flip):
+        """The buffers and the pass of an exact-geometry slot; resize and preprocess are INSIDE the pass.  ``src`` = (source height,
+        source width): the pass starts from the decoded frame at the file's size and resizes (and flips) it on the device; None: the
+        uploaded pixels are already (H, W).  An annotating pass then draws each frame's detections into its uploaded source frame
+        (ops.annotate_u8, annotate_video.py)."""
+        B, pipe, annotate = s.batch, s.pipe, s.annotate
         in_h, in_w = src if src is not None else (H, W)
         npix = in_h * in_w * 3
         pix_bytes = npix if self.device_preprocess else 4 * npix
-        seg = (pix_bytes + 15) // 16 * 16                           # one frame's segment of the staging buffer
-        off = B * seg                                               # ... then B x [resize_ratio, det_threshold]
-        s = _Slot()
-        s.key, s.pipe, s.busy, s.seq, s.batch, s.annotate = (H, W), pipe, False, 0, B, annotate
-        s.io_dev = torch.zeros(off + 16 * B, dtype=torch.uint8, device="cuda")
-        s.io_pin = self._pinned.take(off + 16 * B, zero=True)
-        host = s.io_pin.numpy()
+        host, dyn = self._stage(s, (pix_bytes + 15) // 16 * 16, fine)
+        seg = s.seg
         if self.device_preprocess:
             s.pix_hosts = [host[i * seg:i * seg + npix].reshape(in_h, in_w, 3) for i in range(B)]
-        else:
-            s.pix_hosts = [host[i * seg:i * seg + pix_bytes].view(np.float32).reshape(H, W, 3) for i in range(B)]
-        s.pix_host = s.pix_hosts[0]
-        s.dyn_host = host[off:off + 16 * B].view(np.float64).reshape(B, 2)
-        s.dyn_host[:] = (1.0, 0.0)
-        dyn_dev = s.io_dev[off:off + 16 * B].view(torch.float64).view(B, 2)
-        s.tabs = s.u8_resized = None
-        if self.device_preprocess:
             u8 = [s.io_dev[i * seg:i * seg + npix].view(in_h, in_w, 3) for i in range(B)]
             s.x_f32 = torch.empty((B, H, W, 3), dtype=torch.float32, device="cuda")
             if src is not None:
-                assert self.device_preprocess
                 s.tabs = (torch.from_numpy(ops.resize_cubic_taps(W, in_w)).cuda(), torch.from_numpy(ops.resize_cubic_taps(H, in_h)).cuda())
                 s.u8_resized = torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
         else:
-            assert B == 1 and not annotate
+            assert B == 1 and not annotate and src is None
+            s.pix_hosts = [host[:pix_bytes].view(np.float32).reshape(H, W, 3)]
             s.x_f32 = s.io_dev[:pix_bytes].view(torch.float32).view(1, H, W, 3)
         # annotating pass: frame i is read back from its staging segment into the slot's own pinned segment after the replay
         s.frame_io = [(s.io_dev[i * seg:i * seg + npix], s.io_pin[i * seg:i * seg + npix]) for i in range(B)] if annotate else None
@@ -583,52 +435,93 @@ class DetectionEntry:
                     if src is not None:                             # shapes.Image.data: INTER_CUBIC resize (+ flip) of the decoded frame
                         frame = ops.resize_cubic_u8(u8[i], H, W, flip=flip, tabs=s.tabs, out=s.u8_resized)
                     ops.preprocess_u8(frame, MEAN_BGR, out=s.x_f32[i:i + 1])     # resnet.preprocess + the f32 feed cast, bit for bit
-            res = pipe.forward_dev(s.x_f32, dyn=dyn_dev if B > 1 else dyn_dev[0])
+            res = pipe.forward_dev(s.x_f32, dyn=dyn)
             if annotate:                                            # the detections drawn into the source frame (its only reader is done)
                 packed = res["det_packed"]
                 for i in range(B):
                     ops.annotate_u8(u8[i], packed[i] if B > 1 else packed, tables)
             return res
+        return run
 
-        shared = self.in_flight > 1
-        # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
-        # (fp32 models keep split-K also beside other passes, as bench.py's headline does: the small grids of rpn_conv1 / stage 4 then run
-        # the split engine's split-K form; the bf16 engine loses with it when several passes share the chip)
-        dtype = getattr(getattr(self.detector, "head", None), "dtype", "f32")
-        s.ws = ops.NO_SPLIT_K if ((shared and (dtype == "bf16" or os.environ.get("FRCNN_ENTRY_NO_SPLITK"))) or B > 1) else ops.ConvWorkspace()
-        s.io_dev.copy_(s.io_pin)
-        s.amax = ops.AmaxArena() if self.f32_engine == "f16x3" else None      # the pass's magnitude records (fixed addresses across replays)
-        # Warm-up and capture on ONE side stream, with no device-wide synchronisation: the passes of other geometries that are in flight on
-        # the engine's streams keep running (round 6: torch.cuda.graph's enter -- synchronize, empty_cache -- and two more synchronize calls
-        # drained them at every capture, and a list of mixed image sizes captures per geometry).  The warm-up pass writes the slot's own
-        # buffers, as the replays will: ``s.ready`` orders the first replay behind it.
-        side = _capture_stream()
-        side.wait_stream(torch.cuda.current_stream())
-        stamps.append(("buffers", time.perf_counter()))
-        with torch.cuda.stream(side), ops.conv_workspace(s.ws), ops.tile_policy(shared), ops.f32_engine(self.f32_engine), ops.amax_arena(s.amax):
-            for _ in range(WARMUP_PASSES):
-                run()
-            stamps.append(("warm-up enqueue", time.perf_counter()))
-            s.ready = torch.cuda.Event()
-            s.ready.record(side)
-            s.graph = torch.cuda.CUDAGraph()
-            s.graph.capture_begin(pool=torch.cuda.graph_pool_handle(), capture_error_mode="thread_local")
-            try:
-                s.out = run()
-                stamps.append(("capture enqueue", time.perf_counter()))
-            finally:
-                s.graph.capture_end()
-        stamps.append(("instantiate", time.perf_counter()))
-        packed = s.out["det_packed"]
-        s.out_packed = packed if isinstance(packed, (list, tuple)) else [packed]
-        s._out_raw = self._pinned.take(4 * B * s.out_packed[0].numel())
-        s.out_pin = s._out_raw.view(torch.int32).view((B,) + tuple(s.out_packed[0].shape))
-        s.event = torch.cuda.Event()
-        s.nbytes = max(int(torch.cuda.memory_reserved() - reserved0), int(s.io_dev.numel() + s.x_f32.numel() * 4))
-        stamps.append(("read-back buffers", time.perf_counter()))
-        self.capture_seconds += time.perf_counter() - t0
-        self._book_capture(t0, stamps)
-        return s
+    def _canvas_pass(self, s, fine, Hc, Wc):
+        """The buffers and the pass of a slot over B canvases of (Hc, Wc): the frames' resize + preprocess stay OUTSIDE the graph (their
+        sizes are per image: a few eager launches in front of every replay, _canvas_preprocess), the graph holds trunk .. post-process
+        with the images' true extents read from ``s.extents`` (device words)."""
+        B = s.batch
+        host, dyn = self._stage(s, (Hc * Wc * 3 + 15) // 16 * 16, fine)      # a frame's segment: any source of at most the canvas's pixel count
+        s.pix_hosts = [host[i * s.seg:(i + 1) * s.seg] for i in range(B)]
+        s.u8_resized = torch.empty((B, s.seg), dtype=torch.uint8, device="cuda")
+        s.x_f32 = torch.zeros((B, Hc, Wc, 3), dtype=torch.float32, device="cuda")
+        fine("buffers: canvases")
+        s._ext_raw = self._pinned.take(self._extents_class.LEVELS * B * 8)
+        s.extents = self._extents_class(B, pinned=s._ext_raw)
+        for i in range(B):
+            s.extents.set(i, Hc, Wc)                                # (warm-up and capture run over the full canvas)
+        s.extents.upload()
+        return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
+
+    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False):
+        """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
+        pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
+        (H, W) (_canvas_pass)."""
+        t0 = time.perf_counter()
+        with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
+            m = self.manager
+            kw = dict(stride=self.stride, pre_nms_top_n=PRE_NMS_TOP_N, max_proposals=MAX_PROPOSALS, roi_batch=self.num_rois, pad_to_batch=PAD_TO_BATCH,
+                      bg_idx=m.class_mapping["bg"])
+            if B > 1:
+                pipe = BatchedInferencePipeline(m.rpn_model, self.detector, m.anchor_dims, B, **kw)
+            else:
+                pipe = InferencePipeline(m.rpn_model, self.detector, m.anchor_dims, **kw)
+            reserved0 = torch.cuda.memory_reserved()
+            stamps = []
+            stamp = lambda name: stamps.append((name, time.perf_counter()))
+            fine = stamp if canvas else (lambda name: None)         # (a canvas capture's "buffers" are booked piece by piece)
+            stamp("pipeline")
+            s = _Slot()
+            s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
+            run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
+            shared = self.in_flight > 1
+            # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
+            # (fp32 models keep split-K also beside other passes, as bench.py's headline does: the small grids of rpn_conv1 / stage 4 then run
+            # the split engine's split-K form; the bf16 engine loses with it when several passes share the chip)
+            dtype = getattr(getattr(self.detector, "head", None), "dtype", "f32")
+            s.ws = ops.NO_SPLIT_K if ((shared and (dtype == "bf16" or os.environ.get("FRCNN_ENTRY_NO_SPLITK"))) or B > 1) else ops.ConvWorkspace()
+            fine("buffers: extents")
+            s.io_dev.copy_(s.io_pin)
+            fine("buffers: first upload")
+            s.amax = ops.AmaxArena() if self.f32_engine == "f16x3" else None      # the pass's magnitude records (fixed addresses across replays)
+            # Warm-up and capture on ONE side stream, with no device-wide synchronisation: the passes of other geometries that are in flight on
+            # the engine's streams keep running (round 6: torch.cuda.graph's enter -- synchronize, empty_cache -- and two more synchronize calls
+            # drained them at every capture, and a list of mixed image sizes captures per geometry).  The warm-up pass writes the slot's own
+            # buffers, as the replays will: ``s.ready`` orders the first replay behind it.
+            side = _capture_stream()
+            side.wait_stream(torch.cuda.current_stream())
+            stamp("buffers")
+            with torch.cuda.stream(side), ops.conv_workspace(s.ws), ops.tile_policy(shared), ops.f32_engine(self.f32_engine), ops.amax_arena(s.amax):
+                for _ in range(WARMUP_PASSES):
+                    run()
+                stamp("warm-up enqueue")
+                s.ready = torch.cuda.Event()
+                s.ready.record(side)
+                s.graph = torch.cuda.CUDAGraph()
+                s.graph.capture_begin(pool=torch.cuda.graph_pool_handle(), capture_error_mode="thread_local")
+                try:
+                    s.out = run()
+                    stamp("capture enqueue")
+                finally:
+                    s.graph.capture_end()
+            stamp("instantiate")
+            packed = s.out["det_packed"]
+            s.out_packed = packed if isinstance(packed, (list, tuple)) else [packed]
+            s._out_raw = self._pinned.take(4 * B * s.out_packed[0].numel())
+            s.out_pin = s._out_raw.view(torch.int32).view((B,) + tuple(s.out_packed[0].shape))
+            s.event = torch.cuda.Event()
+            s.nbytes = max(int(torch.cuda.memory_reserved() - reserved0), int(s.io_dev.numel() + s.x_f32.numel() * 4))
+            stamp("read-back buffers")
+            self.capture_seconds += time.perf_counter() - t0
+            self._book_capture(t0, stamps)
+            return s
 
     def _book_capture(self, t0, stamps):
         """Where a capture's host time goes (stats()["capture_breakdown_ms"], summed over the engine's captures)."""
@@ -806,14 +699,19 @@ class DetectionEntry:
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
-            if key[0] == "canvas":
-                return self._submit_canvas(images, resize_ratios, det_threshold, pixels, B)
             key = key + ((B,) if B > 1 else ())
-        s = self.cache.acquire(key, lambda: self._capture(H, W, src, flip, B, annotate))
+        if key[0] == "canvas":
+            s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
+        else:
+            s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate))
+        metas = []
         for i in range(B):
             j = i if i < len(images) else 0
-            np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
             s.dyn_host[i, 0], s.dyn_host[i, 1] = float(resize_ratios[j]), float(det_threshold)
+            if s.canvas:
+                metas.append(self._canvas_frame(s, i, pixels[j]))
+            else:
+                np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
         st = self._streams[self._seq % self.in_flight]
         self._seq += 1
         with torch.cuda.stream(st):
@@ -821,6 +719,8 @@ class DetectionEntry:
                 st.wait_event(s.ready)                             # (the first replay of a fresh pass: behind its warm-up)
                 s.ready = None
             s.io_dev.copy_(s.io_pin, non_blocking=True)
+            if s.canvas:
+                self._canvas_preprocess(s, metas)
             s.graph.replay()
             for i in range(len(images)):
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
@@ -829,6 +729,29 @@ class DetectionEntry:
             s.event.record(st)
         s.busy = True
         return Ticket(s, list(images))
+
+    def _canvas_frame(self, s, i, pixels):
+        """Frame i of a canvas pass, host side: the frame goes into its staging segment at ITS size, its true size into the extents.
+        -> what _canvas_preprocess needs to know about it."""
+        arr, H, W, src, flip = pixels
+        arr = np.ascontiguousarray(arr)
+        oy, ox = s.extents.offset_of(H, W)                          # ResNet: (H & 1, W & 1); VGG16: (0, 0)
+        _, Hc, Wc = s.key
+        assert arr.dtype == np.uint8 and arr.nbytes <= s.seg and H + oy <= Hc and W + ox <= Wc, "one pass, one canvas class"
+        s.pix_hosts[i][:arr.nbytes] = arr.reshape(-1)
+        s.extents.set(i, H, W)
+        return arr.shape[0], arr.shape[1], H, W, src, flip, (oy, ox)
+
+    def _canvas_preprocess(self, s, metas):
+        """The eager launches in front of a canvas pass's replay, on its stream: the true sizes go up as extents, every frame is resized
+        (and flipped) to ITS (H, W) and preprocessed into the corner of its canvas."""
+        s.extents.upload()
+        for i, (in_h, in_w, H, W, src, flip, offset) in enumerate(metas):
+            frame = s.io_dev[i * s.seg:i * s.seg + in_h * in_w * 3].view(in_h, in_w, 3)
+            if src is not None:                                     # shapes.Image.data: INTER_CUBIC resize (+ flip) of the decoded frame
+                frame = ops.resize_cubic_u8(frame, H, W, flip=flip, tabs=(self._device_taps(W, in_w), self._device_taps(H, in_h)),
+                                            out=s.u8_resized[i][:H * W * 3].view(H, W, 3))
+            ops.preprocess_u8_canvas(frame, MEAN_BGR, s.x_f32[i], offset=offset)
 
     def collect_batch(self, ticket):
         """-> [(num_rois, dets)] for the images of a ``submit_batch`` ticket; [(num_rois, dets, frame)] for an annotating one, ``frame``
@@ -850,7 +773,7 @@ class DetectionEntry:
                 cls = packed[4 + 4 * rows:4 + 4 * rows + nd].copy()
                 prob = packed[4 + 5 * rows:4 + 5 * rows + nd].view(np.float32).copy()
                 dets = [{"bbox": bbox[k], "cls_name": rev[int(cls[k])], "prob": prob[k]} for k in range(nd)]
-                res.append((n_rois, dets, s.pix_hosts[i].copy()) if getattr(s, "annotate", False) else (n_rois, dets))
+                res.append((n_rois, dets, s.pix_hosts[i].copy()) if s.annotate else (n_rois, dets))
             return res
         finally:
             s.busy = False                               # whatever happened while decoding the records: the slot is free again

@@ -13,13 +13,23 @@ Stages (reference line -> entry point):
     detector.predict             voc_dets.py:49      frcnn_roi_crop_resize_fwd + conv engine
     argmax / decode / per-class nms  voc_dets.py:51-86   frcnn_detections
 """
+import contextlib as _contextlib
+import gc as _gc
+import os as _os
+import time as _time
+
 import numpy as np
 import torch
 
 from . import ops
 
+# dev knob: False keeps the per-image stages of a batched pass on the pass's own stream
+PARALLEL_BRANCHES = _os.environ.get("FRCNN_PAR_BRANCHES", "0") != "0"
+
 
 class InferencePipeline:
+    batch = 1                                               # images per pass (BatchedInferencePipeline: B)
+
     def __init__(self, rpn_model, det_model, anchor_dims, stride=16, pre_nms_top_n=8000, max_proposals=300,
                  roi_batch=64, pad_to_batch=False, bg_idx=None, det_threshold=0.0):
         self.rpn, self.det = rpn_model, det_model
@@ -85,11 +95,11 @@ class InferencePipeline:
         ``throughput``: this graph will replay beside others (several images in flight): conv launches then pick
         their tiles for a shared chip (ops.tile_policy: larger tiles, whose MFMA efficiency is better, even where
         they leave CUs idle for a launch running alone)."""
-        self._static_in = torch.zeros((1, height, width, 3), dtype=torch.float32, device="cuda")
+        self._static_in = torch.zeros((self.batch, height, width, 3), dtype=torch.float32, device="cuda")
         # the graph owns its split-K workspace: graphs of several pipelines replay concurrently.  The warm-up
         # passes size it, so the capture itself allocates (and re-zeroes) nothing.
         self._conv_ws = ops.ConvWorkspace() if split_k else ops.NO_SPLIT_K
-        self._amax = ops.AmaxArena() if f32_engine == "f16x3" else None
+        self._amax = self._amax_arena() if f32_engine == "f16x3" else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), ops.conv_workspace(self._conv_ws), ops.tile_policy(throughput), ops.f32_engine(f32_engine), \
@@ -104,6 +114,9 @@ class InferencePipeline:
                 ops.f32_engine(f32_engine), ops.amax_arena(self._amax):
             self._static_out = self.forward_dev(self._static_in, resize_ratio)
         return self
+
+    def _amax_arena(self):
+        return ops.AmaxArena()
 
     def close(self):
         """Destroy the captured graph and drop its tensors NOW, in the calling thread (after the last replay has finished): nothing
@@ -138,14 +151,10 @@ def _pass_status(res, packed):
         res["h3_status"] = arena.status(out=packed[2:3])
 
 
-import contextlib as _contextlib
-import gc as _gc
-
-
 @_contextlib.contextmanager
 def no_gc():
     """No cyclic-garbage collection while a stream is capturing: a collection may run the finalizers of unrelated dead objects
-    (other captured graphs, their memory pools) whose HIP calls are not legal in a capturing thread (entry.DetectionEntry._capture)."""
+    (other captured graphs, their memory pools) whose HIP calls are not legal in a capturing thread (entry.DetectionEntry._capture_slot)."""
     was_on = _gc.isenabled()
     collect_before_capture()
     _gc.disable()
@@ -164,16 +173,10 @@ def collect_before_capture(min_interval_s=1.0):
     OFF while it runs (no finalizer of a dead engine's captured passes can start inside it); collecting first merely keeps the backlog
     short, and a full collection of this process's heap is ~23 ms -- more than the rest of a DetectionEntry capture, which a list of
     mixed image sizes makes per geometry (scripts/dev/r6_capture_cost.py)."""
-    import time as _time
     now = _time.monotonic()
     if now - _LAST_COLLECT[0] >= min_interval_s:
         _gc.collect()
         _LAST_COLLECT[0] = _time.monotonic()
-
-
-import os as _os
-# dev knob: False keeps the per-image stages of a batched pass on the pass's own stream
-PARALLEL_BRANCHES = _os.environ.get("FRCNN_PAR_BRANCHES", "0") != "0"
 
 
 class BatchedInferencePipeline(InferencePipeline):
@@ -248,19 +251,7 @@ class BatchedInferencePipeline(InferencePipeline):
     def capture(self, height, width, resize_ratio=1.0, warmup=2, split_k=False, throughput=True, f32_engine=None):
         """``f32_engine``: None = the ambient ops.F32_ENGINE scope (bf16 models: their few f32 layers); an fp32 model names its engine
         like InferencePipeline.capture does ("f16x3": the pass owns an ops.AmaxArena sized for B images' records)."""
-        engine = ops.F32_ENGINE if f32_engine is None else f32_engine
-        self._static_in = torch.zeros((self.batch, height, width, 3), dtype=torch.float32, device="cuda")
-        self._conv_ws = ops.ConvWorkspace() if split_k else ops.NO_SPLIT_K
-        self._amax = ops.AmaxArena(192 + 16 * self.batch) if engine == "f16x3" else None
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), ops.conv_workspace(self._conv_ws), ops.tile_policy(throughput), ops.f32_engine(engine), ops.amax_arena(self._amax):
-            for _ in range(warmup):
-                self.forward_dev(self._static_in, resize_ratio)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._graph = torch.cuda.CUDAGraph()
-        with no_gc(), torch.cuda.graph(self._graph, capture_error_mode="thread_local"), ops.conv_workspace(self._conv_ws), ops.tile_policy(throughput), \
-                ops.f32_engine(engine), ops.amax_arena(self._amax):
-            self._static_out = self.forward_dev(self._static_in, resize_ratio)
-        return self
+        return super().capture(height, width, resize_ratio, warmup, split_k, throughput, ops.F32_ENGINE if f32_engine is None else f32_engine)
+
+    def _amax_arena(self):
+        return ops.AmaxArena(192 + 16 * self.batch)

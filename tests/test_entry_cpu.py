@@ -382,3 +382,64 @@ def test_full_collections_before_captures_are_throttled(monkeypatch):
     assert len(calls) == 1
     pipeline.collect_before_capture(min_interval_s=0.0)
     assert len(calls) == 2
+
+
+def test_a_slot_has_every_field_and_closing_it_gives_each_pinned_piece_back_once_and_leaves_it_empty(monkeypatch):
+    """entry._Slot: every field exists from the start, whichever kind of pass fills it; entry._close_slot derives from the class what it
+    clears and which fields were cut from the pinned arena (they carry ``_arena_block``), and gives each of those back exactly once."""
+    s = entry._Slot()
+    assert all(hasattr(s, name) for name in entry._Slot.__slots__)
+    assert (s.busy, s.canvas, s.annotate) == (False, False, False)
+    assert all(getattr(s, name) is None for name in entry._Slot.__slots__ if name not in ("busy", "canvas", "annotate"))
+    entry._close_slot(s)                                                     # nothing captured, nothing pinned: a no-op
+    assert all(getattr(s, name) is None for name in entry._Slot.__slots__ if name not in ("busy", "canvas", "annotate"))
+
+    block = ["memory", 3 * 4096, 3]                                          # _PinnedArena's [tensor, used bytes, live pieces]
+    pieces = [types.SimpleNamespace(_arena_block=block) for _ in range(3)]
+    given = []
+    real = entry._PinnedArena.give_back
+    monkeypatch.setattr(entry._PinnedArena, "give_back", staticmethod(lambda piece: (given.append(piece) if hasattr(piece, "_arena_block") else None, real(piece))[1]))
+    s.io_pin, s._out_raw, s._ext_raw = pieces
+    s.out_pin, s.pix_hosts, s.dyn_host = object(), [object()], object()      # views into the pieces: no block of their own
+    s.key, s.batch, s.nbytes, s.seg, s.canvas = ("canvas", 608, 800), 4, 100, 64, True
+    s.busy = True
+    with pytest.raises(AssertionError):
+        entry._close_slot(s)                                                 # an image in flight: not closed, nothing given back
+    assert not given and s.io_pin is pieces[0]
+    s.busy = False
+    entry._close_slot(s)
+    assert sorted(map(id, given)) == sorted(map(id, pieces))                 # each piece once
+    assert block[2] == 0 and block[1] == 0                                   # ... so the block starts over
+    assert all(getattr(s, name) is None for name in entry._Slot.__slots__ if name not in ("busy", "canvas", "annotate"))
+    assert (s.busy, s.canvas, s.annotate) == (False, False, False)
+    entry._close_slot(s)                                                     # closing again gives nothing back twice
+    assert len(given) == 3 and block[2] == 0
+
+
+def test_no_gc_restores_the_collectors_state_on_return_and_on_raise(monkeypatch):
+    """pipeline.no_gc: the collector is off inside, and afterwards as it was before -- on when it was on, whether the body returns or
+    raises, and still off when it was off."""
+    import gc
+    from faster_rcnn_amd import pipeline
+    monkeypatch.setattr(pipeline, "collect_before_capture", lambda *a, **k: None)
+    was = gc.isenabled()
+    try:
+        gc.enable()
+        with pipeline.no_gc():
+            assert not gc.isenabled()
+        assert gc.isenabled()
+        with pytest.raises(KeyError):
+            with pipeline.no_gc():
+                assert not gc.isenabled()
+                raise KeyError("inside")
+        assert gc.isenabled()
+        gc.disable()
+        with pipeline.no_gc():
+            assert not gc.isenabled()
+        assert not gc.isenabled()
+        with pytest.raises(KeyError):
+            with pipeline.no_gc():
+                raise KeyError("inside")
+        assert not gc.isenabled()
+    finally:
+        gc.enable() if was else gc.disable()

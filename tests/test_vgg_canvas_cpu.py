@@ -94,7 +94,7 @@ def test_planned_canvases_hold_every_member_at_offset_zero():
     assert set(plan) == set(counts) and 1 <= len(set(plan.values())) <= entry.CANVAS_MAX_CLASSES
     from faster_rcnn_amd import nets
     for (h, w), (hc, wc) in plan.items():
-        oy, ox = nets.VggExtents.offset_of(h, w)                          # where entry._submit_canvas puts a VGG16 frame: (0, 0)
+        oy, ox = nets.VggExtents.offset_of(h, w)                          # where entry._canvas_frame puts a VGG16 frame: (0, 0)
         assert (oy, ox) == (0, 0) and hc % 2 == 0 and wc % 2 == 0 and h + oy <= hc and w + ox <= wc
         assert nets.VggExtents.levels_of(h, w)[4] <= nets.VggExtents.levels_of(hc, wc)[4]      # ... and its map inside the canvas's
     assert entry.plan_canvas_classes(counts) == plan                      # deterministic
