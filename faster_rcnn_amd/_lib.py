@@ -158,6 +158,15 @@ EXT_SIGNATURES = {
     "frcnn_vgg_conv1_bf16_fwd_extents": (I, [P, I, I, I, P, P, P, P, P]),
 }
 
+PNG_VERSION = 1         # include/ext/frcnn_hip_png.h FRCNN_PNG_VERSION
+PNG_SIGNATURES = {
+    "frcnn_png_version": (I, []),
+    "frcnn_png_band_rows": (I, []),
+    "frcnn_png_bound": (c_size_t, [I, I]),
+    "frcnn_png_workspace_bytes": (c_size_t, [I, I]),
+    "frcnn_png_encode_u8": (I, [P, I, I, I, P, c_size_t, P, P, P]),
+}
+
 
 class ConvDesc(ctypes.Structure):
     """frcnn_conv_desc (include/frcnn_hip.h)."""
@@ -220,6 +229,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in PNG_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_png_version() != PNG_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_png_version()} of the PNG encoder extension, this binding "
+                         f"{PNG_VERSION} (include/ext/frcnn_hip_png.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_vgg_canvas_version() != VGG_CANVAS_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_vgg_canvas_version()} of the VGG16 canvas extension, this binding "
                          f"{VGG_CANVAS_VERSION} (include/ext/frcnn_hip_vgg_canvas.h): rebuild with `python -m faster_rcnn_amd.build`")

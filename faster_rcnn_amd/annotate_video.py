@@ -15,6 +15,11 @@ PNGs ahead on threads, uploads them in the decoder's RGB order (green is (0,255,
 geometry into ``entry.default_batch`` passes with ``entry.default_in_flight`` of them in flight, and writes PNGs on a few
 threads (PIL, compress_level=1) in list order.  PNGs that are not 8-bit RGB (grey, palette, 16-bit, alpha) are read through
 PIL's ``convert("RGB")``; cv2.imread's colour conversion may differ from it for 16-bit files.
+
+``png_encoder="device"`` (``--png_encoder device``, or FRCNN_ANNOTATE_PNG_ENCODER=device as the default) moves the encode into the pass
+as well: ops.png_encode_u8 turns the drawn frame into the bytes of a .png file on the device (csrc/png.hip), the file comes back instead
+of the raw frame and the writer threads only write it out.  The files decode to the same pixels as the host encoder's; their bytes
+differ (and are larger: fixed Huffman codes with run matches).  The default stays "host".
 """
 import os
 import pathlib
@@ -31,6 +36,15 @@ DECODE_THREADS = int(os.environ.get("FRCNN_ANNOTATE_DECODE_THREADS", "4"))
 # writers and 125 on eight (scripts/bench_annotate.py)
 WRITE_THREADS = int(os.environ.get("FRCNN_ANNOTATE_WRITE_THREADS", "8"))
 PNG_COMPRESS_LEVEL = 1
+PNG_ENCODERS = ("host", "device")
+
+
+def default_png_encoder():
+    """FRCNN_ANNOTATE_PNG_ENCODER, else "host" (PIL on the writer threads)."""
+    enc = os.environ.get("FRCNN_ANNOTATE_PNG_ENCODER", "host")
+    if enc not in PNG_ENCODERS:
+        raise ValueError("FRCNN_ANNOTATE_PNG_ENCODER=%r: one of %s" % (enc, ", ".join(PNG_ENCODERS)))
+    return enc
 
 
 def drawn(det, width, height):
@@ -119,6 +133,11 @@ def _write_png(path, rgb):
     PilImage.fromarray(rgb).save(path, compress_level=PNG_COMPRESS_LEVEL)
 
 
+def _write_bytes(path, data):
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 class _Frame:
     """A file-backed frame decoded ahead of time: the reference's InMemoryImage (width, height, resize) whose pixels are
     uploaded in the decoder's RGB order (entry.DetectionEntry.host_pixels: the device resize swaps channels to BGR)."""
@@ -139,9 +158,14 @@ class _Frame:
         return self.resize(ratio), ratio
 
 
-def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max):
-    """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop."""
+def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None):
+    """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
+    ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``."""
     from concurrent.futures import ThreadPoolExecutor
+    png_encoder = default_png_encoder() if png_encoder is None else png_encoder
+    if png_encoder not in PNG_ENCODERS:
+        raise ValueError("png_encoder=%r: one of %s" % (png_encoder, ", ".join(PNG_ENCODERS)))
+    on_device = png_encoder == "device"
     paths = [os.path.join(input_dir, f) for f in image_filenames]
     dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
     eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
@@ -151,7 +175,12 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             print("processing {}".format(path))
             frame = np.ascontiguousarray(_read_rgb(path)[:, :, ::-1])
             img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
-            _write_png(os.path.join(out_dir, name), get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max)[:, :, ::-1])
+            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max)
+            if on_device:
+                import torch
+                _write_bytes(os.path.join(out_dir, name), ops.png_bytes(torch.from_numpy(out).cuda(), bgr=True))
+            else:
+                _write_png(os.path.join(out_dir, name), out[:, :, ::-1])
         return
 
     def load(path):                                       # (decode thread) -> (frame, resized, ratio, pixels)
@@ -175,7 +204,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             print("processing {}".format(paths[pos]))
             print("num rois: {}".format(num_rois))
             _print_drawn(dets, frame.width, frame.height)
-            writes.append(write.submit(_write_png, os.path.join(out_dir, image_filenames[pos]), out))
+            writes.append(write.submit(_write_bytes if on_device else _write_png, os.path.join(out_dir, image_filenames[pos]), out))
         while len(writes) > 4 * WRITE_THREADS:            # (bounded: encoded frames must not pile up in memory)
             writes.pop(0).result()
 
@@ -185,7 +214,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
         for part, take in parts:
             ticket = eng.submit_batch([g[2] for g in part], [g[3] for g in part], DET_THRESHOLD, [g[4] for g in part],
-                                      batch=take, annotate=True)
+                                      batch=take, annotate=True, encode="png" if on_device else None)
             window.append(([(g[0], g[1]) for g in part], ticket))
             if len(window) >= eng.in_flight:
                 finish()
@@ -235,6 +264,9 @@ def build_parser():
     p.add_argument("--anchor_scales", dest="anchor_scales", default="128,256,512")
     p.add_argument("--dtype", dest="dtype", choices=("f32", "bf16"), default="f32",
                    help="precision the networks are served in: bf16 = the bf16 conv path on the matrix cores (the reference has no such flag: it runs fp32 only)")
+    p.add_argument("--png_encoder", dest="png_encoder", choices=PNG_ENCODERS, default=default_png_encoder(),
+                   help="who encodes the annotated frames: host = PIL on writer threads, device = inside the detection pass on the GPU "
+                        "(FRCNN_ANNOTATE_PNG_ENCODER sets the default)")
     return p
 
 
@@ -261,7 +293,8 @@ def main(argv=None):
     manager = DetTrainingManager(rpn_model=rpn, class_mapping=class_mapping, preprocess_func=preprocess, anchor_dims=anchors)
     resize_min, resize_max = resize_dims_from_str(args.resize_dims)
     annotate_images(training_manager=manager, detector=detector, input_dir=args.input_dir, out_dir=args.out_dir,
-                    image_filenames=png_filenames(args.input_dir), resize_min=resize_min, resize_max=resize_max)
+                    image_filenames=png_filenames(args.input_dir), resize_min=resize_min, resize_max=resize_max,
+                    png_encoder=args.png_encoder)
 
 
 if __name__ == "__main__":

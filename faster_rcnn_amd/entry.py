@@ -214,9 +214,11 @@ def _capture_stream():
 
 class _Slot:
     """One captured pass for one image size (or canvas class), with its staging on both sides of PCIe.  Every field exists on every slot;
-    what a kind of pass does not use stays None (``tabs`` / ``frame_io``: exact passes; ``extents`` / ``_ext_raw``: canvas passes)."""
+    what a kind of pass does not use stays None (``tabs`` / ``frame_io``: exact passes; ``extents`` / ``_ext_raw``: canvas passes; ``png_*``:
+    annotating passes that encode on the device)."""
     __slots__ = ("key", "pipe", "graph", "out", "io_dev", "io_pin", "dyn_host", "out_pin", "event", "busy", "nbytes", "x_f32", "ws", "tabs", "u8_resized",
-                 "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io")
+                 "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
+                 "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw")
 
     def __init__(self):
         for name in self.__slots__:
@@ -406,7 +408,8 @@ class DetectionEntry:
         """The buffers and the pass of an exact-geometry slot; resize and preprocess are INSIDE the pass.  ``src`` = (source height,
         source width): the pass starts from the decoded frame at the file's size and resizes (and flips) it on the device; None: the
         uploaded pixels are already (H, W).  An annotating pass then draws each frame's detections into its uploaded source frame
-        (ops.annotate_u8, annotate_video.py)."""
+        (ops.annotate_u8, annotate_video.py); with ``s.encode`` == "png" it then encodes the drawn frame as a PNG file on the device
+        (ops.png_encode_u8) into the slot's own buffer, which is what such a pass reads back instead of the raw frame."""
         B, pipe, annotate = s.batch, s.pipe, s.annotate
         in_h, in_w = src if src is not None else (H, W)
         npix = in_h * in_w * 3
@@ -425,8 +428,17 @@ class DetectionEntry:
             s.pix_hosts = [host[:pix_bytes].view(np.float32).reshape(H, W, 3)]
             s.x_f32 = s.io_dev[:pix_bytes].view(torch.float32).view(1, H, W, 3)
         # annotating pass: frame i is read back from its staging segment into the slot's own pinned segment after the replay
-        s.frame_io = [(s.io_dev[i * seg:i * seg + npix], s.io_pin[i * seg:i * seg + npix]) for i in range(B)] if annotate else None
+        s.frame_io = [(s.io_dev[i * seg:i * seg + npix], s.io_pin[i * seg:i * seg + npix]) for i in range(B)] if annotate and not s.encode else None
         tables = self.annotate_tables() if annotate else None
+        if s.encode:
+            # a frame's row: [the file, at most png_bound bytes | pad to 16 | its length, int32 | pad]: one fixed-size copy brings both back
+            # (the bound is 0.5 % over the raw frame).  File-backed frames were uploaded in the decoder's order (host_pixels: flip bit 1).
+            s.png_bound = ops.png_bound(in_h, in_w)
+            len_at = (s.png_bound + 15) // 16 * 16
+            s.png_dev = torch.zeros((B, len_at + 16), dtype=torch.uint8, device="cuda")
+            s.png_ws = torch.empty(ops.png_workspace_bytes(in_h, in_w), dtype=torch.uint8, device="cuda")     # (the frames of a pass encode one after another)
+            png_out = [(s.png_dev[i][:s.png_bound], s.png_dev[i][len_at:len_at + 4].view(torch.int32)) for i in range(B)]
+            uploaded_rgb = src is not None and bool(int(flip) & 2)
 
         def run():
             if self.device_preprocess:
@@ -440,6 +452,8 @@ class DetectionEntry:
                 packed = res["det_packed"]
                 for i in range(B):
                     ops.annotate_u8(u8[i], packed[i] if B > 1 else packed, tables)
+                    if s.encode:
+                        ops.png_encode_u8(u8[i], bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1], workspace=s.png_ws)
             return res
         return run
 
@@ -460,10 +474,10 @@ class DetectionEntry:
         s.extents.upload()
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
-    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False):
+    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
-        (H, W) (_canvas_pass)."""
+        (H, W) (_canvas_pass).  ``encode``: "png" for an annotating pass that ends in the device PNG encoder."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -480,6 +494,7 @@ class DetectionEntry:
             stamp("pipeline")
             s = _Slot()
             s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
+            s.encode = encode
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -516,6 +531,9 @@ class DetectionEntry:
             s.out_packed = packed if isinstance(packed, (list, tuple)) else [packed]
             s._out_raw = self._pinned.take(4 * B * s.out_packed[0].numel())
             s.out_pin = s._out_raw.view(torch.int32).view((B,) + tuple(s.out_packed[0].shape))
+            if s.encode:                                            # (taken behind the capture: a failed one never held it)
+                s._png_raw = self._pinned.take(s.png_dev.numel(), zero=True)
+                s.png_pin = s._png_raw.view(s.png_dev.shape)
             s.event = torch.cuda.Event()
             s.nbytes = max(int(torch.cuda.memory_reserved() - reserved0), int(s.io_dev.numel() + s.x_f32.numel() * 4))
             stamp("read-back buffers")
@@ -681,11 +699,17 @@ class DetectionEntry:
         """``pixels``: the result of ``host_pixels(image)`` when the caller fetched it ahead of time."""
         return self.submit_batch([image], [resize_ratio], det_threshold, [self.host_pixels(image) if pixels is None else pixels], batch=1)
 
-    def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False):
+    def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
-        uploaded frame and reads the frame back; ``collect_batch`` then returns (num_rois, dets, frame)."""
+        uploaded frame and reads the frame back; ``collect_batch`` then returns (num_rois, dets, frame).  ``encode`` = "png" (annotating
+        passes only; again a pass of its own, key tagged "annotate", "png"): the drawn frame is encoded as a PNG file inside the pass
+        and the FILE is read back; ``collect_batch`` then returns (num_rois, dets, png) with ``png`` the file's bytes."""
+        if encode not in (None, "png"):
+            raise FrcnnError("submit_batch: encode=%r (None or \"png\")" % (encode,))
+        if encode and not annotate:
+            raise FrcnnError("submit_batch: encode=\"png\" encodes the ANNOTATED frame: pass annotate=True")
         self._check_epoch()
         B = self.batch if batch is None else batch
         assert 1 <= len(images) <= B and len(images) == len(pixels) == len(resize_ratios)
@@ -695,7 +719,7 @@ class DetectionEntry:
                 raise FrcnnError("annotating passes need the device-side preprocess (a foreign preprocess_func uploads float pixels)")
             key = self.geometry_of(pixels[0])
             assert all(self.geometry_of(p) == key for p in pixels), "one pass, one geometry"
-            key = key + ((B,) if B > 1 else ()) + ("annotate",)
+            key = key + ((B,) if B > 1 else ()) + (("annotate", "png") if encode else ("annotate",))
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -703,7 +727,7 @@ class DetectionEntry:
         if key[0] == "canvas":
             s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
         else:
-            s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate))
+            s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode))
         metas = []
         for i in range(B):
             j = i if i < len(images) else 0
@@ -724,7 +748,9 @@ class DetectionEntry:
             s.graph.replay()
             for i in range(len(images)):
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
-                if s.annotate:
+                if s.encode:
+                    s.png_pin[i].copy_(s.png_dev[i], non_blocking=True)
+                elif s.annotate:
                     s.frame_io[i][1].copy_(s.frame_io[i][0], non_blocking=True)
             s.event.record(st)
         s.busy = True
@@ -755,7 +781,8 @@ class DetectionEntry:
 
     def collect_batch(self, ticket):
         """-> [(num_rois, dets)] for the images of a ``submit_batch`` ticket; [(num_rois, dets, frame)] for an annotating one, ``frame``
-        the annotated source frame (uint8 (h, w, 3), in the channel order it was uploaded in)."""
+        the annotated source frame (uint8 (h, w, 3), in the channel order it was uploaded in); [(num_rois, dets, png)] for one that
+        encodes, ``png`` the annotated frame as the bytes of a PNG file (RGB)."""
         s = ticket.slot
         try:
             s.event.synchronize()
@@ -773,7 +800,14 @@ class DetectionEntry:
                 cls = packed[4 + 4 * rows:4 + 4 * rows + nd].copy()
                 prob = packed[4 + 5 * rows:4 + 5 * rows + nd].view(np.float32).copy()
                 dets = [{"bbox": bbox[k], "cls_name": rev[int(cls[k])], "prob": prob[k]} for k in range(nd)]
-                res.append((n_rois, dets, s.pix_hosts[i].copy()) if s.annotate else (n_rois, dets))
+                if s.encode:
+                    row = s.png_pin[i].numpy()
+                    n = int(row[-16:-12].view(np.int32)[0])
+                    if not 0 < n <= s.png_bound:
+                        raise FrcnnError("device PNG encoder: length word %d outside (0, %d]" % (n, s.png_bound))
+                    res.append((n_rois, dets, row[:n].tobytes()))
+                else:
+                    res.append((n_rois, dets, s.pix_hosts[i].copy()) if s.annotate else (n_rois, dets))
             return res
         finally:
             s.busy = False                               # whatever happened while decoding the records: the slot is free again

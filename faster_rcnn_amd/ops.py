@@ -1059,6 +1059,63 @@ def annotate_u8(frame, det_packed, tables):
     return frame
 
 
+PNG_BAND_ROWS = 1        # scanlines per IDAT chunk of the device encoder (frcnn_png_band_rows(); tests/test_png_cpu.py holds the two together)
+
+
+def png_bound(h, w):
+    """The largest PNG file, in bytes, that ``png_encode_u8`` can make of an (h, w, 3) frame (frcnn_png_bound: the stored form of every
+    band plus the framing).  A pure host call: needs the built library, no GPU."""
+    h, w = int(h), int(w)
+    n = int(_lib.load().frcnn_png_bound(h, w)) if 1 <= h < 2 ** 31 and 1 <= w < 2 ** 31 else 0
+    if n == 0:
+        raise _lib.FrcnnError(f"png_bound: frame {h}x{w} unsupported (both sides >= 1, h * (1 + 3w) below 2 GiB)")
+    return n
+
+
+def png_workspace_bytes(h, w):
+    """Bytes of device workspace ``png_encode_u8`` needs for an (h, w, 3) frame (frcnn_png_workspace_bytes)."""
+    png_bound(h, w)
+    return int(_lib.load().frcnn_png_workspace_bytes(int(h), int(w)))
+
+
+def png_encode_u8(frame, bgr=False, out=None, out_len=None, workspace=None):
+    """Encode ``frame`` -- an (h, w, 3) uint8 device tensor, R,G,B per pixel or (``bgr``) B,G,R -- as an 8-bit RGB PNG file on the device
+    (frcnn_png_encode_u8).  -> (out, out_len): ``out`` uint8 [>= png_bound(h, w)] holds the file, ``out_len`` int32 [1] its length; what
+    is not passed (``workspace`` included) is allocated.  Never synchronises; reads nothing on the host per frame, so the call can
+    be captured in a graph with fixed ``out`` / ``out_len`` / ``workspace``.  Bad arguments raise FrcnnError before anything is launched."""
+    _require_gpu()
+    if not (isinstance(frame, torch.Tensor) and frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3
+            and frame.shape[2] == 3 and frame.is_contiguous()):
+        raise _lib.FrcnnError("png_encode_u8: frame must be a contiguous (h, w, 3) uint8 device tensor, got %s"
+                              % (tuple(frame.shape) if isinstance(frame, torch.Tensor) else type(frame).__name__,))
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    lib = _lib.load()
+    bound, need = int(lib.frcnn_png_bound(h, w)), int(lib.frcnn_png_workspace_bytes(h, w))
+    if out is None and bound:
+        out = torch.empty(bound, dtype=torch.uint8, device="cuda")
+    if out_len is None:
+        out_len = torch.zeros(1, dtype=torch.int32, device="cuda")
+    if workspace is None and need:
+        workspace = _ws(need)
+    for name, t, dt in (("out", out, torch.uint8), ("out_len", out_len, torch.int32), ("workspace", workspace, torch.uint8)):
+        if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise _lib.FrcnnError(f"png_encode_u8: {name} must be a contiguous {dt} device tensor")
+    if workspace is not None and workspace.numel() < need:
+        raise _lib.FrcnnError(f"png_encode_u8: workspace of {workspace.numel()} bytes, {need} needed")
+    _lib.call("frcnn_png_encode_u8", _p(frame) if frame.numel() else None, h, w, 1 if bgr else 0, _p(out), out.numel() if out is not None else 0,
+              _p(out_len), _p(workspace), _stream())
+    return out, out_len
+
+
+def png_bytes(frame, bgr=False):
+    """``png_encode_u8`` and the file as ``bytes``: the eager convenience (one synchronisation, one copy of the encoded length)."""
+    out, out_len = png_encode_u8(frame, bgr=bgr)
+    n = int(out_len.item())
+    if not 0 < n <= out.numel():
+        raise _lib.FrcnnError(f"png_bytes: encoded length {n} outside (0, {out.numel()}]")
+    return out[:n].cpu().numpy().tobytes()
+
+
 def split_detections(packed, rows=None):
     """Views (n_dets, det_bbox, det_cls, det_prob, det_roi) into a `det_packed` buffer (device tensor or its host copy)."""
     rows = (packed.numel() - 4) // 7 if rows is None else rows

@@ -1,0 +1,39 @@
+/* PNG files encoded on the device: an EXTENSION of the C ABI of libfrcnn_hip.so (include/frcnn_hip.h, whose revision and symbol table
+ * stay as they are: FRCNN_ABI_VERSION 110).  The entry points below live in the same library, follow the same conventions (int status,
+ * message via frcnn_last_error, `stream` = hipStream_t or NULL) and carry a revision of their own: a host that uses them checks
+ * frcnn_png_version() == FRCNN_PNG_VERSION besides frcnn_version().
+ *   1 = frcnn_png_band_rows, frcnn_png_bound, frcnn_png_workspace_bytes, frcnn_png_encode_u8. */
+#ifndef FRCNN_HIP_PNG_H
+#define FRCNN_HIP_PNG_H
+#include <stddef.h>
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define FRCNN_PNG_VERSION 1
+int frcnn_png_version(void);
+
+/* The encoder writes an 8-bit RGB, non-interlaced PNG: every scanline Sub-filtered, the filtered stream cut into bands of
+ * frcnn_png_band_rows() rows, each band one IDAT chunk (a fixed-Huffman deflate block with run matches closed by a sync flush, or stored
+ * blocks where that is shorter), a closing IDAT with the final empty block and the Adler-32, IEND.  Any PNG reader decodes it; the bytes
+ * are a function of the frame alone (no float arithmetic, no dependence on scheduling).
+ * frcnn_png_bound: the largest file an h x w frame can become = 66 + 2 + sum over bands of (12 + n + 5 * ceil(n / 65535)), n = the band's
+ * filtered bytes (rows * (1 + 3w)); 0 for a size frcnn_png_encode_u8 refuses.  frcnn_png_workspace_bytes: the device workspace it needs
+ * (16-byte aligned), 0 likewise. */
+int frcnn_png_band_rows(void);
+size_t frcnn_png_bound(int h, int w);
+size_t frcnn_png_workspace_bytes(int h, int w);
+
+/* frame [h][w][3] uint8 DEVICE, contiguous, R,G,B per pixel (bgr != 0: B,G,R; the file is RGB either way) -> out: the whole file, and
+ * *out_len (DEVICE int32, 4-byte aligned) its length in bytes (<= frcnn_png_bound(h, w)); bytes of out beyond it are left as they were.
+ * out needs no alignment; out_capacity >= frcnn_png_bound(h, w) (FRCNN_E_ARG otherwise, as for a null pointer).  Three launches on
+ * `stream`: no allocation, no synchronisation, nothing read on the host per frame -- the call can be captured in a hipGraph and replayed.
+ * FRCNN_E_UNSUPPORTED: h or w < 1, or h * (1 + 3w) > 2^31 - 1.  Nothing is launched on an error. */
+int frcnn_png_encode_u8(const uint8_t* frame, int h, int w, int bgr, uint8_t* out, size_t out_capacity, int32_t* out_len, void* workspace,
+                        void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* FRCNN_HIP_PNG_H */

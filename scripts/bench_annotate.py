@@ -6,9 +6,10 @@
 per pair (a) voc_dets.get_dets_by_cls over N in-memory frames, (b) the same frames through annotating passes (detections + the
 frame drawn and read back), (c) annotate_video.annotate_images from PNG files to PNG files, with the host's PNG decode and encode
 per frame timed on their own (one thread).  Synthetic weights, dense_class calibrated so that many classes fire.  Prints one
-JSON line.
+JSON line.  ``--png_encoder device`` (or ``both``) adds leg (c) with the frames encoded inside the pass (ops.png_encode_u8) and the
+writer threads only writing bytes, plus the bytes written per frame by either encoder.
 
-    python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32]
+    python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both]
 """
 import argparse
 import contextlib
@@ -69,7 +70,7 @@ def annotate_in_memory(eng, resized, ratios):
     return frames
 
 
-def run_pair(name, cfg, n_frames, reps):
+def run_pair(name, cfg, n_frames, reps, encoders=("host",)):
     import numpy as np
     from PIL import Image as PilImage
     from faster_rcnn_amd import annotate_video, entry, shapes, util, voc_dets
@@ -103,7 +104,12 @@ def run_pair(name, cfg, n_frames, reps):
         names = ["%06d.png" % i for i in range(n_frames)]
         for nm, s in zip(names, srcs):
             PilImage.fromarray(s[:, :, ::-1]).save(os.path.join(d_in, nm), compress_level=1)
-        tc, tcs = timed(lambda: annotate_video.annotate_images(mgr, det, d_in, d_out, names, cfg["resize"][0], cfg["resize"][1]))
+        legs = {}
+        for enc in encoders:
+            tc, tcs = timed(lambda: annotate_video.annotate_images(mgr, det, d_in, d_out, names, cfg["resize"][0], cfg["resize"][1], png_encoder=enc))
+            tag = "c_" if enc == "host" else "c_%s_" % enc
+            legs.update({tag + "annotate_images_fps": round(n_frames / tc, 1), tag + "runs_s": [round(t, 4) for t in tcs],
+                         tag + "bytes_per_frame": sum(os.path.getsize(os.path.join(d_out, nm)) for nm in names) // n_frames})
         k = min(32, n_frames)
         t0 = time.perf_counter()
         decoded = [annotate_video._read_rgb(os.path.join(d_in, nm)) for nm in names[:k]]
@@ -112,8 +118,8 @@ def run_pair(name, cfg, n_frames, reps):
         for nm, f in zip(names[:k], decoded):
             annotate_video._write_png(os.path.join(tmp, "enc_" + nm), f)
         t_enc = (time.perf_counter() - t0) / k
-    res.update({"c_annotate_images_fps": round(n_frames / tc, 1), "c_runs_s": [round(t, 4) for t in tcs],
-                "c_png_decode_ms_per_frame_1thread": round(t_dec * 1e3, 2), "c_png_encode_ms_per_frame_1thread": round(t_enc * 1e3, 2),
+    res.update(legs)
+    res.update({"raw_bytes_per_frame": h * w * 3, "c_png_decode_ms_per_frame_1thread": round(t_dec * 1e3, 2), "c_png_encode_ms_per_frame_1thread": round(t_enc * 1e3, 2),
                 "c_decode_threads": annotate_video.DECODE_THREADS, "c_write_threads": annotate_video.WRITE_THREADS})
     return res
 
@@ -123,13 +129,14 @@ def main():
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--pairs", default=",".join(PAIRS))
+    ap.add_argument("--png_encoder", choices=("host", "device", "both"), default="host", help="who encodes leg (c)'s output files")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_annotate.py needs a GPU")
     out = {"metric": "annotate_frames_per_s", "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
     for name in args.pairs.split(","):
-        out[name] = run_pair(name, PAIRS[name], args.frames, args.reps)
+        out[name] = run_pair(name, PAIRS[name], args.frames, args.reps, ("host", "device") if args.png_encoder == "both" else (args.png_encoder,))
     print(json.dumps(out))
 
 
