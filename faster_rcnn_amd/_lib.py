@@ -167,6 +167,15 @@ PNG_SIGNATURES = {
     "frcnn_png_encode_u8": (I, [P, I, I, I, P, c_size_t, P, P, P]),
 }
 
+PNG_HUFF_VERSION = 1    # include/ext/frcnn_hip_png_huff.h FRCNN_PNG_HUFF_VERSION
+PNG_HUFF_SIGNATURES = {
+    "frcnn_png_huff_version": (I, []),
+    "frcnn_png_huff_band_rows": (I, []),
+    "frcnn_png_huff_bound": (c_size_t, [I, I]),
+    "frcnn_png_huff_workspace_bytes": (c_size_t, [I, I]),
+    "frcnn_png_huff_encode_u8": (I, [P, I, I, I, P, c_size_t, P, P, P]),
+}
+
 
 class ConvDesc(ctypes.Structure):
     """frcnn_conv_desc (include/frcnn_hip.h)."""
@@ -233,6 +242,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in PNG_HUFF_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_png_huff_version() != PNG_HUFF_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_png_huff_version()} of the PNG encoder's huffman extension, this binding "
+                         f"{PNG_HUFF_VERSION} (include/ext/frcnn_hip_png_huff.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_png_version() != PNG_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_png_version()} of the PNG encoder extension, this binding "
                          f"{PNG_VERSION} (include/ext/frcnn_hip_png.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -20,6 +20,10 @@ PIL's ``convert("RGB")``; cv2.imread's colour conversion may differ from it for 
 as well: ops.png_encode_u8 turns the drawn frame into the bytes of a .png file on the device (csrc/png.hip), the file comes back instead
 of the raw frame and the writer threads only write it out.  The files decode to the same pixels as the host encoder's; their bytes
 differ (and are larger: fixed Huffman codes with run matches).  The default stays "host".
+
+``png_compress="huffman"`` (``--png_compress huffman``, or FRCNN_ANNOTATE_PNG_COMPRESS=huffman as the default) selects the device
+encoder's second mode: adaptive row filters and a dynamic Huffman code per band of eight rows, files about the size of the host
+encoder's.  It is a mode of the DEVICE encoder: with the host encoder it raises ValueError.  The default stays "runs".
 """
 import os
 import pathlib
@@ -37,6 +41,7 @@ DECODE_THREADS = int(os.environ.get("FRCNN_ANNOTATE_DECODE_THREADS", "4"))
 WRITE_THREADS = int(os.environ.get("FRCNN_ANNOTATE_WRITE_THREADS", "8"))
 PNG_COMPRESS_LEVEL = 1
 PNG_ENCODERS = ("host", "device")
+PNG_COMPRESS = ("runs", "huffman")                # modes of the device encoder (ops.PNG_COMPRESS)
 
 
 def default_png_encoder():
@@ -45,6 +50,28 @@ def default_png_encoder():
     if enc not in PNG_ENCODERS:
         raise ValueError("FRCNN_ANNOTATE_PNG_ENCODER=%r: one of %s" % (enc, ", ".join(PNG_ENCODERS)))
     return enc
+
+
+def default_png_compress():
+    """FRCNN_ANNOTATE_PNG_COMPRESS, else "runs"."""
+    mode = os.environ.get("FRCNN_ANNOTATE_PNG_COMPRESS", "runs")
+    if mode not in PNG_COMPRESS:
+        raise ValueError("FRCNN_ANNOTATE_PNG_COMPRESS=%r: one of %s" % (mode, ", ".join(PNG_COMPRESS)))
+    return mode
+
+
+def png_options(png_encoder=None, png_compress=None):
+    """-> (encoder, compress) with None replaced by the defaults; ValueError for an unknown name and for "huffman" with the host encoder."""
+    png_encoder = default_png_encoder() if png_encoder is None else png_encoder
+    png_compress = default_png_compress() if png_compress is None else png_compress
+    if png_encoder not in PNG_ENCODERS:
+        raise ValueError("png_encoder=%r: one of %s" % (png_encoder, ", ".join(PNG_ENCODERS)))
+    if png_compress not in PNG_COMPRESS:
+        raise ValueError("png_compress=%r: one of %s" % (png_compress, ", ".join(PNG_COMPRESS)))
+    if png_compress != "runs" and png_encoder != "device":
+        raise ValueError("png_compress=%r is a mode of the device encoder: it needs png_encoder=\"device\" (--png_encoder device)"
+                         % (png_compress,))
+    return png_encoder, png_compress
 
 
 def drawn(det, width, height):
@@ -158,14 +185,15 @@ class _Frame:
         return self.resize(ratio), ratio
 
 
-def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None):
+def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
+                    png_compress=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
-    ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``."""
+    ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
+    ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``."""
     from concurrent.futures import ThreadPoolExecutor
-    png_encoder = default_png_encoder() if png_encoder is None else png_encoder
-    if png_encoder not in PNG_ENCODERS:
-        raise ValueError("png_encoder=%r: one of %s" % (png_encoder, ", ".join(PNG_ENCODERS)))
+    png_encoder, png_compress = png_options(png_encoder, png_compress)
     on_device = png_encoder == "device"
+    encode = ("png" if png_compress == "runs" else "png-" + png_compress) if on_device else None
     paths = [os.path.join(input_dir, f) for f in image_filenames]
     dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
     eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
@@ -178,7 +206,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max)
             if on_device:
                 import torch
-                _write_bytes(os.path.join(out_dir, name), ops.png_bytes(torch.from_numpy(out).cuda(), bgr=True))
+                _write_bytes(os.path.join(out_dir, name), ops.png_bytes(torch.from_numpy(out).cuda(), bgr=True, compress=png_compress))
             else:
                 _write_png(os.path.join(out_dir, name), out[:, :, ::-1])
         return
@@ -214,7 +242,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
         for part, take in parts:
             ticket = eng.submit_batch([g[2] for g in part], [g[3] for g in part], DET_THRESHOLD, [g[4] for g in part],
-                                      batch=take, annotate=True, encode="png" if on_device else None)
+                                      batch=take, annotate=True, encode=encode)
             window.append(([(g[0], g[1]) for g in part], ticket))
             if len(window) >= eng.in_flight:
                 finish()
@@ -267,6 +295,9 @@ def build_parser():
     p.add_argument("--png_encoder", dest="png_encoder", choices=PNG_ENCODERS, default=default_png_encoder(),
                    help="who encodes the annotated frames: host = PIL on writer threads, device = inside the detection pass on the GPU "
                         "(FRCNN_ANNOTATE_PNG_ENCODER sets the default)")
+    p.add_argument("--png_compress", dest="png_compress", choices=PNG_COMPRESS, default=default_png_compress(),
+                   help="the device encoder's mode: runs = Sub filter, fixed Huffman codes; huffman = adaptive row filters and a dynamic "
+                        "Huffman code per band, smaller files (FRCNN_ANNOTATE_PNG_COMPRESS sets the default; needs --png_encoder device)")
     return p
 
 
@@ -278,6 +309,7 @@ def main(argv=None):
     from .det_util import DetTrainingManager
     from .util import get_anchors
     args = build_parser().parse_args(argv)
+    png_options(args.png_encoder, args.png_compress)                          # (before any model is loaded)
     os.environ.setdefault("GPU_MAX_HW_QUEUES", voc_dets.ENTRY_HW_QUEUES)      # (as voc_dets.main: passes in flight want > 4 queues)
     class_mapping = KITTI_CLASS_MAPPING if args.kitti else VOC_CLASS_MAPPING
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
@@ -294,7 +326,7 @@ def main(argv=None):
     resize_min, resize_max = resize_dims_from_str(args.resize_dims)
     annotate_images(training_manager=manager, detector=detector, input_dir=args.input_dir, out_dir=args.out_dir,
                     image_filenames=png_filenames(args.input_dir), resize_min=resize_min, resize_max=resize_max,
-                    png_encoder=args.png_encoder)
+                    png_encoder=args.png_encoder, png_compress=args.png_compress)
 
 
 if __name__ == "__main__":

@@ -40,6 +40,8 @@ from .pipeline import BatchedInferencePipeline, InferencePipeline, no_gc
 from .shapes import declares as _declares
 
 MEAN_BGR = (103.939, 116.779, 123.68)           # resnet.preprocess / vgg.preprocess (resnet.py:64-75, vgg.py:52-57)
+# submit_batch(encode=...) of an annotating pass -> the device PNG encoder's compress mode (ops.png_encode_u8)
+PNG_ENCODES = {"png": "runs", "png-huffman": "huffman"}
 PRE_NMS_TOP_N, MAX_PROPOSALS = 8000, 300        # det_util.py:151-156
 
 
@@ -408,8 +410,9 @@ class DetectionEntry:
         """The buffers and the pass of an exact-geometry slot; resize and preprocess are INSIDE the pass.  ``src`` = (source height,
         source width): the pass starts from the decoded frame at the file's size and resizes (and flips) it on the device; None: the
         uploaded pixels are already (H, W).  An annotating pass then draws each frame's detections into its uploaded source frame
-        (ops.annotate_u8, annotate_video.py); with ``s.encode`` == "png" it then encodes the drawn frame as a PNG file on the device
-        (ops.png_encode_u8) into the slot's own buffer, which is what such a pass reads back instead of the raw frame."""
+        (ops.annotate_u8, annotate_video.py); with ``s.encode`` == "png" or "png-huffman" it then encodes the drawn frame as a PNG file on
+        the device (ops.png_encode_u8, compress "runs" or "huffman") into the slot's own buffer, which is what such a pass reads back
+        instead of the raw frame."""
         B, pipe, annotate = s.batch, s.pipe, s.annotate
         in_h, in_w = src if src is not None else (H, W)
         npix = in_h * in_w * 3
@@ -433,10 +436,11 @@ class DetectionEntry:
         if s.encode:
             # a frame's row: [the file, at most png_bound bytes | pad to 16 | its length, int32 | pad]: one fixed-size copy brings both back
             # (the bound is 0.5 % over the raw frame).  File-backed frames were uploaded in the decoder's order (host_pixels: flip bit 1).
-            s.png_bound = ops.png_bound(in_h, in_w)
+            compress = PNG_ENCODES[s.encode]
+            s.png_bound = ops.png_bound(in_h, in_w, compress)
             len_at = (s.png_bound + 15) // 16 * 16
             s.png_dev = torch.zeros((B, len_at + 16), dtype=torch.uint8, device="cuda")
-            s.png_ws = torch.empty(ops.png_workspace_bytes(in_h, in_w), dtype=torch.uint8, device="cuda")     # (the frames of a pass encode one after another)
+            s.png_ws = torch.empty(ops.png_workspace_bytes(in_h, in_w, compress), dtype=torch.uint8, device="cuda")     # (the frames of a pass encode one after another)
             png_out = [(s.png_dev[i][:s.png_bound], s.png_dev[i][len_at:len_at + 4].view(torch.int32)) for i in range(B)]
             uploaded_rgb = src is not None and bool(int(flip) & 2)
 
@@ -453,7 +457,8 @@ class DetectionEntry:
                 for i in range(B):
                     ops.annotate_u8(u8[i], packed[i] if B > 1 else packed, tables)
                     if s.encode:
-                        ops.png_encode_u8(u8[i], bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1], workspace=s.png_ws)
+                        ops.png_encode_u8(u8[i], bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1], workspace=s.png_ws,
+                                              compress=compress)
             return res
         return run
 
@@ -477,7 +482,7 @@ class DetectionEntry:
     def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
-        (H, W) (_canvas_pass).  ``encode``: "png" for an annotating pass that ends in the device PNG encoder."""
+        (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -705,11 +710,13 @@ class DetectionEntry:
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
         uploaded frame and reads the frame back; ``collect_batch`` then returns (num_rois, dets, frame).  ``encode`` = "png" (annotating
         passes only; again a pass of its own, key tagged "annotate", "png"): the drawn frame is encoded as a PNG file inside the pass
-        and the FILE is read back; ``collect_batch`` then returns (num_rois, dets, png) with ``png`` the file's bytes."""
-        if encode not in (None, "png"):
-            raise FrcnnError("submit_batch: encode=%r (None or \"png\")" % (encode,))
+        and the FILE is read back; ``collect_batch`` then returns (num_rois, dets, png) with ``png`` the file's bytes.  "png-huffman":
+        the same through the encoder's huffman mode (key tagged "annotate", "png-huffman": one more pass of its own, buffers sized by
+        that mode's bound)."""
+        if encode is not None and encode not in PNG_ENCODES:
+            raise FrcnnError("submit_batch: encode=%r (None, %s)" % (encode, ", ".join('"%s"' % e for e in PNG_ENCODES)))
         if encode and not annotate:
-            raise FrcnnError("submit_batch: encode=\"png\" encodes the ANNOTATED frame: pass annotate=True")
+            raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
         self._check_epoch()
         B = self.batch if batch is None else batch
         assert 1 <= len(images) <= B and len(images) == len(pixels) == len(resize_ratios)
@@ -719,7 +726,7 @@ class DetectionEntry:
                 raise FrcnnError("annotating passes need the device-side preprocess (a foreign preprocess_func uploads float pixels)")
             key = self.geometry_of(pixels[0])
             assert all(self.geometry_of(p) == key for p in pixels), "one pass, one geometry"
-            key = key + ((B,) if B > 1 else ()) + (("annotate", "png") if encode else ("annotate",))
+            key = key + ((B,) if B > 1 else ()) + (("annotate", encode) if encode else ("annotate",))
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"

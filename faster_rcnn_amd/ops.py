@@ -1060,29 +1060,42 @@ def annotate_u8(frame, det_packed, tables):
 
 
 PNG_BAND_ROWS = 1        # scanlines per IDAT chunk of the device encoder (frcnn_png_band_rows(); tests/test_png_cpu.py holds the two together)
+PNG_HUFF_BAND_ROWS = 8   # ... of its huffman mode (frcnn_png_huff_band_rows(); tests/test_png_huff_cpu.py)
+# compress= of the png_* calls -> the prefix of their entry points: "runs" (include/ext/frcnn_hip_png.h: Sub filter, fixed Huffman codes,
+# run matches) or "huffman" (include/ext/frcnn_hip_png_huff.h: adaptive row filters, a dynamic Huffman code per band)
+PNG_COMPRESS = {"runs": "frcnn_png_", "huffman": "frcnn_png_huff_"}
 
 
-def png_bound(h, w):
-    """The largest PNG file, in bytes, that ``png_encode_u8`` can make of an (h, w, 3) frame (frcnn_png_bound: the stored form of every
-    band plus the framing).  A pure host call: needs the built library, no GPU."""
+def _png_entry(compress, what):
+    if compress not in PNG_COMPRESS:
+        raise _lib.FrcnnError("%s: compress=%r (one of %s)" % (what, compress, ", ".join(PNG_COMPRESS)))
+    return PNG_COMPRESS[compress]
+
+
+def png_bound(h, w, compress="runs"):
+    """The largest PNG file, in bytes, that ``png_encode_u8`` can make of an (h, w, 3) frame (frcnn_png_bound / frcnn_png_huff_bound: the
+    stored form of every band plus the framing).  A pure host call: needs the built library, no GPU."""
     h, w = int(h), int(w)
-    n = int(_lib.load().frcnn_png_bound(h, w)) if 1 <= h < 2 ** 31 and 1 <= w < 2 ** 31 else 0
+    bound = getattr(_lib.load(), _png_entry(compress, "png_bound") + "bound")
+    n = int(bound(h, w)) if 1 <= h < 2 ** 31 and 1 <= w < 2 ** 31 else 0
     if n == 0:
         raise _lib.FrcnnError(f"png_bound: frame {h}x{w} unsupported (both sides >= 1, h * (1 + 3w) below 2 GiB)")
     return n
 
 
-def png_workspace_bytes(h, w):
-    """Bytes of device workspace ``png_encode_u8`` needs for an (h, w, 3) frame (frcnn_png_workspace_bytes)."""
-    png_bound(h, w)
-    return int(_lib.load().frcnn_png_workspace_bytes(int(h), int(w)))
+def png_workspace_bytes(h, w, compress="runs"):
+    """Bytes of device workspace ``png_encode_u8`` needs for an (h, w, 3) frame (frcnn_png_workspace_bytes / frcnn_png_huff_...)."""
+    png_bound(h, w, compress)
+    return int(getattr(_lib.load(), _png_entry(compress, "png_workspace_bytes") + "workspace_bytes")(int(h), int(w)))
 
 
-def png_encode_u8(frame, bgr=False, out=None, out_len=None, workspace=None):
+def png_encode_u8(frame, bgr=False, out=None, out_len=None, workspace=None, compress="runs"):
     """Encode ``frame`` -- an (h, w, 3) uint8 device tensor, R,G,B per pixel or (``bgr``) B,G,R -- as an 8-bit RGB PNG file on the device
-    (frcnn_png_encode_u8).  -> (out, out_len): ``out`` uint8 [>= png_bound(h, w)] holds the file, ``out_len`` int32 [1] its length; what
-    is not passed (``workspace`` included) is allocated.  Never synchronises; reads nothing on the host per frame, so the call can
-    be captured in a graph with fixed ``out`` / ``out_len`` / ``workspace``.  Bad arguments raise FrcnnError before anything is launched."""
+    (frcnn_png_encode_u8; ``compress`` = "huffman": frcnn_png_huff_encode_u8, adaptive row filters and a dynamic Huffman code per band of
+    PNG_HUFF_BAND_ROWS rows).  -> (out, out_len): ``out`` uint8 [>= png_bound(h, w, compress)] holds the file, ``out_len`` int32 [1] its
+    length; what is not passed (``workspace`` included) is allocated.  Never synchronises; reads nothing on the host per frame, so the call
+    can be captured in a graph with fixed ``out`` / ``out_len`` / ``workspace``.  Bad arguments raise FrcnnError before anything is launched."""
+    prefix = _png_entry(compress, "png_encode_u8")
     _require_gpu()
     if not (isinstance(frame, torch.Tensor) and frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3
             and frame.shape[2] == 3 and frame.is_contiguous()):
@@ -1090,7 +1103,7 @@ def png_encode_u8(frame, bgr=False, out=None, out_len=None, workspace=None):
                               % (tuple(frame.shape) if isinstance(frame, torch.Tensor) else type(frame).__name__,))
     h, w = int(frame.shape[0]), int(frame.shape[1])
     lib = _lib.load()
-    bound, need = int(lib.frcnn_png_bound(h, w)), int(lib.frcnn_png_workspace_bytes(h, w))
+    bound, need = int(getattr(lib, prefix + "bound")(h, w)), int(getattr(lib, prefix + "workspace_bytes")(h, w))
     if out is None and bound:
         out = torch.empty(bound, dtype=torch.uint8, device="cuda")
     if out_len is None:
@@ -1102,14 +1115,14 @@ def png_encode_u8(frame, bgr=False, out=None, out_len=None, workspace=None):
             raise _lib.FrcnnError(f"png_encode_u8: {name} must be a contiguous {dt} device tensor")
     if workspace is not None and workspace.numel() < need:
         raise _lib.FrcnnError(f"png_encode_u8: workspace of {workspace.numel()} bytes, {need} needed")
-    _lib.call("frcnn_png_encode_u8", _p(frame) if frame.numel() else None, h, w, 1 if bgr else 0, _p(out), out.numel() if out is not None else 0,
+    _lib.call(prefix + "encode_u8", _p(frame) if frame.numel() else None, h, w, 1 if bgr else 0, _p(out), out.numel() if out is not None else 0,
               _p(out_len), _p(workspace), _stream())
     return out, out_len
 
 
-def png_bytes(frame, bgr=False):
+def png_bytes(frame, bgr=False, compress="runs"):
     """``png_encode_u8`` and the file as ``bytes``: the eager convenience (one synchronisation, one copy of the encoded length)."""
-    out, out_len = png_encode_u8(frame, bgr=bgr)
+    out, out_len = png_encode_u8(frame, bgr=bgr, compress=compress)
     n = int(out_len.item())
     if not 0 < n <= out.numel():
         raise _lib.FrcnnError(f"png_bytes: encoded length {n} outside (0, {out.numel()}]")

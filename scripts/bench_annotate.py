@@ -7,9 +7,13 @@ per pair (a) voc_dets.get_dets_by_cls over N in-memory frames, (b) the same fram
 frame drawn and read back), (c) annotate_video.annotate_images from PNG files to PNG files, with the host's PNG decode and encode
 per frame timed on their own (one thread).  Synthetic weights, dense_class calibrated so that many classes fire.  Prints one
 JSON line.  ``--png_encoder device`` (or ``both``) adds leg (c) with the frames encoded inside the pass (ops.png_encode_u8) and the
-writer threads only writing bytes, plus the bytes written per frame by either encoder.
+writer threads only writing bytes, plus the bytes written per frame by either encoder.  ``--png_encoder all`` runs three legs (c) --
+host, device with --png_compress runs, device with --png_compress huffman -- ALTERNATING inside every repetition, so that drift of the
+machine falls on all three alike.  ``--content photo`` fills the frames with the VOC fixture photograph (tiled to the frame size, shifted
+per frame) instead of uniform noise: noise does not compress, so bytes per frame mean something only on the photograph.
 
-    python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both]
+    python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
+                                     [--content noise|photo]
 """
 import argparse
 import contextlib
@@ -70,14 +74,26 @@ def annotate_in_memory(eng, resized, ratios):
     return frames
 
 
-def run_pair(name, cfg, n_frames, reps, encoders=("host",)):
+LEGS = {"host": ("host", "runs"), "device": ("device", "runs"), "device_huffman": ("device", "huffman")}      # leg -> (png_encoder, png_compress)
+
+
+def photo_frames(h, w, n):
+    """The VOC fixture photograph tiled to (h, w), shifted by a few pixels per frame (BGR, as cv2 would have read it)."""
+    import numpy as np
+    from PIL import Image as PilImage
+    rgb = np.asarray(PilImage.open(os.path.join(ROOT, "tests", "golden", "VOC_test", "JPEGImages", "000005.jpg")).convert("RGB"))
+    big = np.tile(rgb, (-(-h // rgb.shape[0]) + 1, -(-w // rgb.shape[1]) + 1, 1))
+    return [np.ascontiguousarray(big[i % 97:i % 97 + h, 3 * i % 211:3 * i % 211 + w, ::-1]) for i in range(n)]
+
+
+def run_pair(name, cfg, n_frames, reps, encoders=("host",), content="noise"):
     import numpy as np
     from PIL import Image as PilImage
     from faster_rcnn_amd import annotate_video, entry, shapes, util, voc_dets
     mgr, det = build(cfg)
     h, w = cfg["hw"]
     rs = np.random.RandomState(5)
-    srcs = [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
     imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
     resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
     eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
@@ -104,12 +120,26 @@ def run_pair(name, cfg, n_frames, reps, encoders=("host",)):
         names = ["%06d.png" % i for i in range(n_frames)]
         for nm, s in zip(names, srcs):
             PilImage.fromarray(s[:, :, ::-1]).save(os.path.join(d_in, nm), compress_level=1)
-        legs = {}
+        legs, times, sizes = {}, {enc: [] for enc in encoders}, {}
+
+        def leg(enc):
+            png_encoder, png_compress = LEGS[enc]
+            t0 = time.perf_counter()
+            with contextlib.redirect_stdout(io.StringIO()):
+                annotate_video.annotate_images(mgr, det, d_in, d_out, names, cfg["resize"][0], cfg["resize"][1], png_encoder=png_encoder,
+                                               png_compress=png_compress)
+            return time.perf_counter() - t0
+
+        for enc in encoders:                                        # warm-up: captures
+            leg(enc)
+        for _ in range(reps):                                       # the legs alternate inside every repetition
+            for enc in encoders:
+                times[enc].append(leg(enc))
+                sizes[enc] = sum(os.path.getsize(os.path.join(d_out, nm)) for nm in names) // n_frames
         for enc in encoders:
-            tc, tcs = timed(lambda: annotate_video.annotate_images(mgr, det, d_in, d_out, names, cfg["resize"][0], cfg["resize"][1], png_encoder=enc))
             tag = "c_" if enc == "host" else "c_%s_" % enc
-            legs.update({tag + "annotate_images_fps": round(n_frames / tc, 1), tag + "runs_s": [round(t, 4) for t in tcs],
-                         tag + "bytes_per_frame": sum(os.path.getsize(os.path.join(d_out, nm)) for nm in names) // n_frames})
+            legs.update({tag + "annotate_images_fps": round(n_frames / statistics.median(times[enc]), 1),
+                         tag + "runs_s": [round(t, 4) for t in times[enc]], tag + "bytes_per_frame": sizes[enc]})
         k = min(32, n_frames)
         t0 = time.perf_counter()
         decoded = [annotate_video._read_rgb(os.path.join(d_in, nm)) for nm in names[:k]]
@@ -119,7 +149,7 @@ def run_pair(name, cfg, n_frames, reps, encoders=("host",)):
             annotate_video._write_png(os.path.join(tmp, "enc_" + nm), f)
         t_enc = (time.perf_counter() - t0) / k
     res.update(legs)
-    res.update({"raw_bytes_per_frame": h * w * 3, "c_png_decode_ms_per_frame_1thread": round(t_dec * 1e3, 2), "c_png_encode_ms_per_frame_1thread": round(t_enc * 1e3, 2),
+    res.update({"raw_bytes_per_frame": h * w * 3, "content": content, "c_png_decode_ms_per_frame_1thread": round(t_dec * 1e3, 2), "c_png_encode_ms_per_frame_1thread": round(t_enc * 1e3, 2),
                 "c_decode_threads": annotate_video.DECODE_THREADS, "c_write_threads": annotate_video.WRITE_THREADS})
     return res
 
@@ -129,14 +159,17 @@ def main():
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--pairs", default=",".join(PAIRS))
-    ap.add_argument("--png_encoder", choices=("host", "device", "both"), default="host", help="who encodes leg (c)'s output files")
+    ap.add_argument("--png_encoder", choices=("host", "device", "both", "all"), default="host",
+                    help="who encodes leg (c)'s output files; all = host, device (runs) and device (huffman), alternating")
+    ap.add_argument("--content", choices=("noise", "photo"), default="noise", help="what the frames hold (see the module docstring)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_annotate.py needs a GPU")
     out = {"metric": "annotate_frames_per_s", "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
     for name in args.pairs.split(","):
-        out[name] = run_pair(name, PAIRS[name], args.frames, args.reps, ("host", "device") if args.png_encoder == "both" else (args.png_encoder,))
+        encoders = {"both": ("host", "device"), "all": tuple(LEGS)}.get(args.png_encoder, (args.png_encoder,))
+        out[name] = run_pair(name, PAIRS[name], args.frames, args.reps, encoders, args.content)
     print(json.dumps(out))
 
 
