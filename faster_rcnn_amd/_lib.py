@@ -176,6 +176,16 @@ PNG_HUFF_SIGNATURES = {
     "frcnn_png_huff_encode_u8": (I, [P, I, I, I, P, c_size_t, P, P, P]),
 }
 
+JPEG_VERSION = 1        # include/ext/frcnn_hip_jpeg.h FRCNN_JPEG_VERSION
+JPEG_SIGNATURES = {
+    "frcnn_jpeg_version": (I, []),
+    "frcnn_jpeg_restart_mcus": (I, []),
+    "frcnn_jpeg_header_bytes": (c_size_t, []),
+    "frcnn_jpeg_bound": (c_size_t, [I, I]),
+    "frcnn_jpeg_workspace_bytes": (c_size_t, [I, I]),
+    "frcnn_jpeg_encode_u8": (I, [P, I, I, I, I, P, c_size_t, P, P, P]),
+}
+
 
 class ConvDesc(ctypes.Structure):
     """frcnn_conv_desc (include/frcnn_hip.h)."""
@@ -246,6 +256,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in JPEG_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_jpeg_version() != JPEG_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_version()} of the JPEG encoder extension, this binding "
+                         f"{JPEG_VERSION} (include/ext/frcnn_hip_jpeg.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_png_huff_version() != PNG_HUFF_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_png_huff_version()} of the PNG encoder's huffman extension, this binding "
                          f"{PNG_HUFF_VERSION} (include/ext/frcnn_hip_png_huff.h): rebuild with `python -m faster_rcnn_amd.build`")

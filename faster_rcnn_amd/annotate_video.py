@@ -24,6 +24,13 @@ differ (and are larger: fixed Huffman codes with run matches).  The 
 ``png_compress="huffman"`` (``--png_compress huffman``, or FRCNN_ANNOTATE_PNG_COMPRESS=huffman as the default) selects the device
 encoder's second mode: adaptive row filters and a dynamic Huffman code per band of eight rows, files about the size of the host
 encoder's.  It is a mode of the DEVICE encoder: with the host encoder it raises ValueError.  The default stays "runs".
+
+``frame_format="jpg"`` (``--frame_format jpg``, or FRCNN_ANNOTATE_FRAME_FORMAT=jpg as the default) writes every annotated frame as
+``<stem>.jpg`` instead: a baseline JPEG at ``jpeg_quality`` (``--jpeg_quality``, 1..100, default 90) without chroma subsampling (the boxes
+are 3 pixels wide).  ``jpeg_encoder="host"`` (the default; FRCNN_ANNOTATE_JPEG_ENCODER) is PIL on the writer threads,
+``jpeg_encoder="device"`` encodes inside the pass (ops.jpeg_encode_u8, csrc/jpeg.hip): the file comes back instead of the raw frame.  Both
+use the Annex K tables at the same IJG quality; their bytes differ in the rounding of colour transform and DCT.  The JPEG
+options with ``png`` frames, and the device PNG options with ``jpg`` frames, raise ValueError.  The default stays "png".
 """
 import os
 import pathlib
@@ -42,6 +49,9 @@ WRITE_THREADS = int(os.environ.get("FRCNN_ANNOTATE_WRITE_THREADS", "8"))
 PNG_COMPRESS_LEVEL = 1
 PNG_ENCODERS = ("host", "device")
 PNG_COMPRESS = ("runs", "huffman")                # modes of the device encoder (ops.PNG_COMPRESS)
+FRAME_FORMATS = ("png", "jpg")
+JPEG_ENCODERS = ("host", "device")
+JPEG_QUALITY = 90
 
 
 def default_png_encoder():
@@ -72,6 +82,45 @@ def png_options(png_encoder=None, png_compress=None):
         raise ValueError("png_compress=%r is a mode of the device encoder: it needs png_encoder=\"device\" (--png_encoder device)"
                          % (png_compress,))
     return png_encoder, png_compress
+
+
+def default_frame_format():
+    """FRCNN_ANNOTATE_FRAME_FORMAT, else "png"."""
+    fmt = os.environ.get("FRCNN_ANNOTATE_FRAME_FORMAT", "png")
+    if fmt not in FRAME_FORMATS:
+        raise ValueError("FRCNN_ANNOTATE_FRAME_FORMAT=%r: one of %s" % (fmt, ", ".join(FRAME_FORMATS)))
+    return fmt
+
+
+def default_jpeg_encoder():
+    """FRCNN_ANNOTATE_JPEG_ENCODER, else "host" (PIL on the writer threads)."""
+    enc = os.environ.get("FRCNN_ANNOTATE_JPEG_ENCODER", "host")
+    if enc not in JPEG_ENCODERS:
+        raise ValueError("FRCNN_ANNOTATE_JPEG_ENCODER=%r: one of %s" % (enc, ", ".join(JPEG_ENCODERS)))
+    return enc
+
+
+def jpeg_options(frame_format=None, jpeg_encoder=None, jpeg_quality=None, png_encoder="host", png_compress="runs"):
+    """-> (frame_format, jpeg_encoder, jpeg_quality) with None replaced by the defaults (quality: JPEG_QUALITY).  ``png_encoder`` /
+    ``png_compress``: what ``png_options`` returned.  ValueError for an unknown name, a quality outside 1..100, the device JPEG encoder
+    or a quality with "png" frames, and the device PNG encoder or its huffman mode with "jpg" frames."""
+    frame_format = default_frame_format() if frame_format is None else frame_format
+    jpeg_encoder = default_jpeg_encoder() if jpeg_encoder is None else jpeg_encoder
+    if frame_format not in FRAME_FORMATS:
+        raise ValueError("frame_format=%r: one of %s" % (frame_format, ", ".join(FRAME_FORMATS)))
+    if jpeg_encoder not in JPEG_ENCODERS:
+        raise ValueError("jpeg_encoder=%r: one of %s" % (jpeg_encoder, ", ".join(JPEG_ENCODERS)))
+    if jpeg_quality is not None and (isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, (int, np.integer))
+                                     or not 1 <= int(jpeg_quality) <= 100):
+        raise ValueError("jpeg_quality=%r: an integer in 1..100" % (jpeg_quality,))
+    if frame_format == "png":
+        if jpeg_encoder != "host":
+            raise ValueError("jpeg_encoder=%r encodes JPEG frames: it needs frame_format=\"jpg\" (--frame_format jpg)" % (jpeg_encoder,))
+        if jpeg_quality is not None:
+            raise ValueError("jpeg_quality=%r is a setting of JPEG frames: it needs frame_format=\"jpg\" (--frame_format jpg)" % (jpeg_quality,))
+    elif png_encoder != "host" or png_compress != "runs":
+        raise ValueError("png_encoder=%r / png_compress=%r are settings of PNG frames: not with frame_format=\"jpg\"" % (png_encoder, png_compress))
+    return frame_format, jpeg_encoder, JPEG_QUALITY if jpeg_quality is None else int(jpeg_quality)
 
 
 def drawn(det, width, height):
@@ -160,6 +209,11 @@ def _write_png(path, rgb):
     PilImage.fromarray(rgb).save(path, compress_level=PNG_COMPRESS_LEVEL)
 
 
+def _write_jpg(path, rgb, quality):
+    from PIL import Image as PilImage
+    PilImage.fromarray(rgb).save(path, format="JPEG", quality=quality, subsampling=0)
+
+
 def _write_bytes(path, data):
     with open(path, "wb") as f:
         f.write(data)
@@ -186,29 +240,42 @@ class _Frame:
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
-                    png_compress=None):
+                    png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
-    ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``."""
+    ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
+    ``frame_format``: "png" or "jpg" (each output keeps its stem and gets the extension .jpg); None = ``default_frame_format()``.
+    ``jpeg_encoder``: "host" or "device", as ``png_encoder``; ``jpeg_quality``: 1..100, None = JPEG_QUALITY."""
     from concurrent.futures import ThreadPoolExecutor
     png_encoder, png_compress = png_options(png_encoder, png_compress)
-    on_device = png_encoder == "device"
-    encode = ("png" if png_compress == "runs" else "png-" + png_compress) if on_device else None
+    frame_format, jpeg_encoder, jpeg_quality = jpeg_options(frame_format, jpeg_encoder, jpeg_quality, png_encoder, png_compress)
+    jpg = frame_format == "jpg"
+    on_device = (jpeg_encoder if jpg else png_encoder) == "device"
+    if jpg:
+        encode, quality = ("jpeg", jpeg_quality) if on_device else (None, None)
+        out_names = [os.path.splitext(f)[0] + ".jpg" for f in image_filenames]
+        write_host = lambda path, rgb: _write_jpg(path, rgb, jpeg_quality)
+    else:
+        encode, quality = ("png" if png_compress == "runs" else "png-" + png_compress) if on_device else None, None
+        out_names = list(image_filenames)
+        write_host = _write_png
     paths = [os.path.join(input_dir, f) for f in image_filenames]
     dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
     eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
     pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
     if eng is None:                                       # eager path / foreign models: the reference's loop
-        for name, path in zip(image_filenames, paths):
+        for name, path in zip(out_names, paths):
             print("processing {}".format(path))
             frame = np.ascontiguousarray(_read_rgb(path)[:, :, ::-1])
             img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
             out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max)
             if on_device:
                 import torch
-                _write_bytes(os.path.join(out_dir, name), ops.png_bytes(torch.from_numpy(out).cuda(), bgr=True, compress=png_compress))
+                dev = torch.from_numpy(out).cuda()
+                _write_bytes(os.path.join(out_dir, name), ops.jpeg_bytes(dev, quality=jpeg_quality, bgr=True) if jpg else
+                             ops.png_bytes(dev, bgr=True, compress=png_compress))
             else:
-                _write_png(os.path.join(out_dir, name), out[:, :, ::-1])
+                write_host(os.path.join(out_dir, name), out[:, :, ::-1])
         return
 
     def load(path):                                       # (decode thread) -> (frame, resized, ratio, pixels)
@@ -232,7 +299,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             print("processing {}".format(paths[pos]))
             print("num rois: {}".format(num_rois))
             _print_drawn(dets, frame.width, frame.height)
-            writes.append(write.submit(_write_bytes if on_device else _write_png, os.path.join(out_dir, image_filenames[pos]), out))
+            writes.append(write.submit(_write_bytes if on_device else write_host, os.path.join(out_dir, out_names[pos]), out))
         while len(writes) > 4 * WRITE_THREADS:            # (bounded: encoded frames must not pile up in memory)
             writes.pop(0).result()
 
@@ -242,7 +309,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
         for part, take in parts:
             ticket = eng.submit_batch([g[2] for g in part], [g[3] for g in part], DET_THRESHOLD, [g[4] for g in part],
-                                      batch=take, annotate=True, encode=encode)
+                                      batch=take, annotate=True, encode=encode, quality=quality)
             window.append(([(g[0], g[1]) for g in part], ticket))
             if len(window) >= eng.in_flight:
                 finish()
@@ -298,6 +365,14 @@ def build_parser():
     p.add_argument("--png_compress", dest="png_compress", choices=PNG_COMPRESS, default=default_png_compress(),
                    help="the device encoder's mode: runs = Sub filter, fixed Huffman codes; huffman = adaptive row filters and a dynamic "
                         "Huffman code per band, smaller files (FRCNN_ANNOTATE_PNG_COMPRESS sets the default; needs --png_encoder device)")
+    p.add_argument("--frame_format", dest="frame_format", choices=FRAME_FORMATS, default=default_frame_format(),
+                   help="how the annotated frames are written: png (lossless), or jpg = <stem>.jpg, baseline JPEG without chroma "
+                        "subsampling (FRCNN_ANNOTATE_FRAME_FORMAT sets the default)")
+    p.add_argument("--jpeg_encoder", dest="jpeg_encoder", choices=JPEG_ENCODERS, default=default_jpeg_encoder(),
+                   help="who encodes JPEG frames: host = PIL on writer threads, device = inside the detection pass on the GPU "
+                        "(FRCNN_ANNOTATE_JPEG_ENCODER sets the default; needs --frame_format jpg)")
+    p.add_argument("--jpeg_quality", dest="jpeg_quality", type=int, default=None,
+                   help="IJG quality of JPEG frames, 1..100 (default %d; needs --frame_format jpg)" % JPEG_QUALITY)
     return p
 
 
@@ -309,7 +384,7 @@ def main(argv=None):
     from .det_util import DetTrainingManager
     from .util import get_anchors
     args = build_parser().parse_args(argv)
-    png_options(args.png_encoder, args.png_compress)                          # (before any model is loaded)
+    jpeg_options(args.frame_format, args.jpeg_encoder, args.jpeg_quality, *png_options(args.png_encoder, args.png_compress))     # (before any model is loaded)
     os.environ.setdefault("GPU_MAX_HW_QUEUES", voc_dets.ENTRY_HW_QUEUES)      # (as voc_dets.main: passes in flight want > 4 queues)
     class_mapping = KITTI_CLASS_MAPPING if args.kitti else VOC_CLASS_MAPPING
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
@@ -326,7 +401,8 @@ def main(argv=None):
     resize_min, resize_max = resize_dims_from_str(args.resize_dims)
     annotate_images(training_manager=manager, detector=detector, input_dir=args.input_dir, out_dir=args.out_dir,
                     image_filenames=png_filenames(args.input_dir), resize_min=resize_min, resize_max=resize_max,
-                    png_encoder=args.png_encoder, png_compress=args.png_compress)
+                    png_encoder=args.png_encoder, png_compress=args.png_compress, frame_format=args.frame_format,
+                    jpeg_encoder=args.jpeg_encoder, jpeg_quality=args.jpeg_quality)
 
 
 if __name__ == "__main__":

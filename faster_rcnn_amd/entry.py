@@ -42,6 +42,8 @@ from .shapes import declares as _declares
 MEAN_BGR = (103.939, 116.779, 123.68)           # resnet.preprocess / vgg.preprocess (resnet.py:64-75, vgg.py:52-57)
 # submit_batch(encode=...) of an annotating pass -> the device PNG encoder's compress mode (ops.png_encode_u8)
 PNG_ENCODES = {"png": "runs", "png-huffman": "huffman"}
+# submit_batch(encode="jpeg", quality=q): the device JPEG encoder (ops.jpeg_encode_u8) at the end of an annotating pass
+JPEG_ENCODE = "jpeg"
 PRE_NMS_TOP_N, MAX_PROPOSALS = 8000, 300        # det_util.py:151-156
 
 
@@ -217,10 +219,11 @@ def _capture_stream():
 class _Slot:
     """One captured pass for one image size (or canvas class), with its staging on both sides of PCIe.  Every field exists on every slot;
     what a kind of pass does not use stays None (``tabs`` / ``frame_io``: exact passes; ``extents`` / ``_ext_raw``: canvas passes; ``png_*``:
-    annotating passes that encode on the device)."""
+    annotating passes that encode on the device -- a PNG or, with ``quality``, a JPEG file; ``first_copy``: the bytes of a JPEG row that
+    are read back with every replay)."""
     __slots__ = ("key", "pipe", "graph", "out", "io_dev", "io_pin", "dyn_host", "out_pin", "event", "busy", "nbytes", "x_f32", "ws", "tabs", "u8_resized",
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
-                 "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw")
+                 "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy")
 
     def __init__(self):
         for name in self.__slots__:
@@ -412,7 +415,7 @@ class DetectionEntry:
         uploaded pixels are already (H, W).  An annotating pass then draws each frame's detections into its uploaded source frame
         (ops.annotate_u8, annotate_video.py); with ``s.encode`` == "png" or "png-huffman" it then encodes the drawn frame as a PNG file on
         the device (ops.png_encode_u8, compress "runs" or "huffman") into the slot's own buffer, which is what such a pass reads back
-        instead of the raw frame."""
+        instead of the raw frame; with ``s.encode`` == "jpeg" as a JPEG file at ``s.quality`` (ops.jpeg_encode_u8)."""
         B, pipe, annotate = s.batch, s.pipe, s.annotate
         in_h, in_w = src if src is not None else (H, W)
         npix = in_h * in_w * 3
@@ -433,7 +436,18 @@ class DetectionEntry:
         # annotating pass: frame i is read back from its staging segment into the slot's own pinned segment after the replay
         s.frame_io = [(s.io_dev[i * seg:i * seg + npix], s.io_pin[i * seg:i * seg + npix]) for i in range(B)] if annotate and not s.encode else None
         tables = self.annotate_tables() if annotate else None
-        if s.encode:
+        if s.encode == JPEG_ENCODE:
+            # a frame's row: [its length, int32 | pad to 16 | the file, at most jpeg_bound bytes].  The bound is 6.5 times the raw frame
+            # (every block at its longest), which is device memory only: a replay reads back the row's first ``first_copy`` bytes -- the
+            # length, the header and a quarter of the raw frame's size, more than a photograph takes at quality 90 -- and collect_batch
+            # fetches the rest of a longer file.
+            s.png_bound = ops.jpeg_bound(in_h, in_w)
+            s.png_dev = torch.zeros((B, 16 + (s.png_bound + 15) // 16 * 16), dtype=torch.uint8, device="cuda")
+            s.first_copy = min(16 + ops.jpeg_header_bytes() + npix // 4, 16 + s.png_bound)
+            s.png_ws = torch.empty(ops.jpeg_workspace_bytes(in_h, in_w), dtype=torch.uint8, device="cuda")
+            png_out = [(s.png_dev[i][16:16 + s.png_bound], s.png_dev[i][0:4].view(torch.int32)) for i in range(B)]
+            uploaded_rgb = src is not None and bool(int(flip) & 2)
+        elif s.encode:
             # a frame's row: [the file, at most png_bound bytes | pad to 16 | its length, int32 | pad]: one fixed-size copy brings both back
             # (the bound is 0.5 % over the raw frame).  File-backed frames were uploaded in the decoder's order (host_pixels: flip bit 1).
             compress = PNG_ENCODES[s.encode]
@@ -456,7 +470,10 @@ class DetectionEntry:
                 packed = res["det_packed"]
                 for i in range(B):
                     ops.annotate_u8(u8[i], packed[i] if B > 1 else packed, tables)
-                    if s.encode:
+                    if s.encode == JPEG_ENCODE:
+                        ops.jpeg_encode_u8(u8[i], quality=s.quality, bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1],
+                                           workspace=s.png_ws)
+                    elif s.encode:
                         ops.png_encode_u8(u8[i], bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1], workspace=s.png_ws,
                                               compress=compress)
             return res
@@ -479,10 +496,11 @@ class DetectionEntry:
         s.extents.upload()
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
-    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None):
+    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
-        (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder."""
+        (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
+        ends in the device JPEG encoder at ``quality``."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -499,7 +517,7 @@ class DetectionEntry:
             stamp("pipeline")
             s = _Slot()
             s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
-            s.encode = encode
+            s.encode, s.quality = encode, quality
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -537,8 +555,9 @@ class DetectionEntry:
             s._out_raw = self._pinned.take(4 * B * s.out_packed[0].numel())
             s.out_pin = s._out_raw.view(torch.int32).view((B,) + tuple(s.out_packed[0].shape))
             if s.encode:                                            # (taken behind the capture: a failed one never held it)
-                s._png_raw = self._pinned.take(s.png_dev.numel(), zero=True)
-                s.png_pin = s._png_raw.view(s.png_dev.shape)
+                shape = (B, s.first_copy) if s.encode == JPEG_ENCODE else tuple(s.png_dev.shape)
+                s._png_raw = self._pinned.take(shape[0] * shape[1], zero=True)
+                s.png_pin = s._png_raw[:shape[0] * shape[1]].view(shape)
             s.event = torch.cuda.Event()
             s.nbytes = max(int(torch.cuda.memory_reserved() - reserved0), int(s.io_dev.numel() + s.x_f32.numel() * 4))
             stamp("read-back buffers")
@@ -704,7 +723,7 @@ class DetectionEntry:
         """``pixels``: the result of ``host_pixels(image)`` when the caller fetched it ahead of time."""
         return self.submit_batch([image], [resize_ratio], det_threshold, [self.host_pixels(image) if pixels is None else pixels], batch=1)
 
-    def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None):
+    def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -712,8 +731,18 @@ class DetectionEntry:
         passes only; again a pass of its own, key tagged "annotate", "png"): the drawn frame is encoded as a PNG file inside the pass
         and the FILE is read back; ``collect_batch`` then returns (num_rois, dets, png) with ``png`` the file's bytes.  "png-huffman":
         the same through the encoder's huffman mode (key tagged "annotate", "png-huffman": one more pass of its own, buffers sized by
-        that mode's bound)."""
-        if encode is not None and encode not in PNG_ENCODES:
+        that mode's bound).  ``encode`` = "jpeg" with ``quality`` = 1..100 (stated by the caller: it is part of the pass): the drawn
+        frame is encoded as a baseline JPEG file at that IJG quality (ops.jpeg_encode_u8; key tagged "annotate", "jpeg", quality) and
+        ``collect_batch`` returns (num_rois, dets, jpg).  ``quality`` with any other ``encode`` is an error."""
+        if encode == JPEG_ENCODE:
+            if not annotate:
+                raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
+            if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+                raise FrcnnError("submit_batch: encode=\"%s\" takes quality= an integer in 1..100, got %r" % (encode, quality))
+            quality = int(quality)
+        elif quality is not None:
+            raise FrcnnError("submit_batch: quality=%r goes with encode=\"%s\" only" % (quality, JPEG_ENCODE))
+        elif encode is not None and encode not in PNG_ENCODES:
             raise FrcnnError("submit_batch: encode=%r (None, %s)" % (encode, ", ".join('"%s"' % e for e in PNG_ENCODES)))
         if encode and not annotate:
             raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
@@ -726,7 +755,7 @@ class DetectionEntry:
                 raise FrcnnError("annotating passes need the device-side preprocess (a foreign preprocess_func uploads float pixels)")
             key = self.geometry_of(pixels[0])
             assert all(self.geometry_of(p) == key for p in pixels), "one pass, one geometry"
-            key = key + ((B,) if B > 1 else ()) + (("annotate", encode) if encode else ("annotate",))
+            key = key + ((B,) if B > 1 else ()) + (("annotate", encode) if encode else ("annotate",)) + ((quality,) if quality else ())
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -734,7 +763,7 @@ class DetectionEntry:
         if key[0] == "canvas":
             s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
         else:
-            s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode))
+            s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality))
         metas = []
         for i in range(B):
             j = i if i < len(images) else 0
@@ -755,7 +784,9 @@ class DetectionEntry:
             s.graph.replay()
             for i in range(len(images)):
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
-                if s.encode:
+                if s.encode == JPEG_ENCODE:
+                    s.png_pin[i].copy_(s.png_dev[i][:s.first_copy], non_blocking=True)
+                elif s.encode:
                     s.png_pin[i].copy_(s.png_dev[i], non_blocking=True)
                 elif s.annotate:
                     s.frame_io[i][1].copy_(s.frame_io[i][0], non_blocking=True)
@@ -789,7 +820,7 @@ class DetectionEntry:
     def collect_batch(self, ticket):
         """-> [(num_rois, dets)] for the images of a ``submit_batch`` ticket; [(num_rois, dets, frame)] for an annotating one, ``frame``
         the annotated source frame (uint8 (h, w, 3), in the channel order it was uploaded in); [(num_rois, dets, png)] for one that
-        encodes, ``png`` the annotated frame as the bytes of a PNG file (RGB)."""
+        encodes, ``png`` the annotated frame as the bytes of a PNG file (RGB), or of a JPEG file for encode="jpeg"."""
         s = ticket.slot
         try:
             s.event.synchronize()
@@ -807,7 +838,16 @@ class DetectionEntry:
                 cls = packed[4 + 4 * rows:4 + 4 * rows + nd].copy()
                 prob = packed[4 + 5 * rows:4 + 5 * rows + nd].view(np.float32).copy()
                 dets = [{"bbox": bbox[k], "cls_name": rev[int(cls[k])], "prob": prob[k]} for k in range(nd)]
-                if s.encode:
+                if s.encode == JPEG_ENCODE:
+                    row = s.png_pin[i].numpy()
+                    n = int(row[0:4].view(np.int32)[0])
+                    if not 0 < n <= s.png_bound:
+                        raise FrcnnError("device JPEG encoder: length word %d outside (0, %d]" % (n, s.png_bound))
+                    data = row[16:min(16 + n, s.first_copy)].tobytes()
+                    if 16 + n > s.first_copy:               # a file longer than the first copy: its remainder now (synchronous)
+                        data += s.png_dev[i][s.first_copy:16 + n].cpu().numpy().tobytes()
+                    res.append((n_rois, dets, data))
+                elif s.encode:
                     row = s.png_pin[i].numpy()
                     n = int(row[-16:-12].view(np.int32)[0])
                     if not 0 < n <= s.png_bound:

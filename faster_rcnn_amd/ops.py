@@ -1128,6 +1128,70 @@ def png_bytes(frame, bgr=False, compress="runs"):
         raise _lib.FrcnnError(f"png_bytes: encoded length {n} outside (0, {out.numel()}]")
     return out[:n].cpu().numpy().tobytes()
 
+JPEG_RESTART_MCUS = 16   # MCUs per restart interval of the device JPEG encoder (frcnn_jpeg_restart_mcus(); tests/test_jpeg_cpu.py)
+
+
+def jpeg_bound(h, w):
+    """The largest JPEG file, in bytes, that ``jpeg_encode_u8`` can make of an (h, w, 3) frame (frcnn_jpeg_bound: every block at its
+    longest, every byte stuffed).  A pure host call: needs the built library, no GPU."""
+    h, w = int(h), int(w)
+    n = int(_lib.load().frcnn_jpeg_bound(h, w)) if 1 <= h < 2 ** 31 and 1 <= w < 2 ** 31 else 0
+    if n == 0:
+        raise _lib.FrcnnError(f"jpeg_bound: frame {h}x{w} unsupported (both sides in 1..65535, the bound below 2 GiB)")
+    return n
+
+
+def jpeg_header_bytes():
+    """Bytes in front of a file's entropy-coded data, SOI .. SOS: the same for every frame (frcnn_jpeg_header_bytes)."""
+    return int(_lib.load().frcnn_jpeg_header_bytes())
+
+
+def jpeg_workspace_bytes(h, w):
+    """Bytes of device workspace ``jpeg_encode_u8`` needs for an (h, w, 3) frame (frcnn_jpeg_workspace_bytes)."""
+    jpeg_bound(h, w)
+    return int(_lib.load().frcnn_jpeg_workspace_bytes(int(h), int(w)))
+
+
+def jpeg_encode_u8(frame, quality=90, bgr=False, out=None, out_len=None, workspace=None):
+    """Encode ``frame`` -- an (h, w, 3) uint8 device tensor, R,G,B per pixel or (``bgr``) B,G,R -- as a baseline JFIF file (4:4:4, the
+    Annex K tables at IJG ``quality`` 1..100, restart intervals of JPEG_RESTART_MCUS MCUs) on the device (frcnn_jpeg_encode_u8).
+    -> (out, out_len): ``out`` uint8 [>= jpeg_bound(h, w)] holds the file, ``out_len`` int32 [1] its length; what is not passed
+    (``workspace`` included) is allocated.  Never synchronises; reads nothing on the host per frame, so the call can be captured in a graph
+    with fixed ``out`` / ``out_len`` / ``workspace``.  Bad arguments raise FrcnnError before anything is launched."""
+    _require_gpu()
+    if not (isinstance(frame, torch.Tensor) and frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3
+            and frame.shape[2] == 3 and frame.is_contiguous()):
+        raise _lib.FrcnnError("jpeg_encode_u8: frame must be a contiguous (h, w, 3) uint8 device tensor, got %s"
+                              % (tuple(frame.shape) if isinstance(frame, torch.Tensor) else type(frame).__name__,))
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise _lib.FrcnnError("jpeg_encode_u8: quality=%r (an integer in 1..100)" % (quality,))
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    lib = _lib.load()
+    bound, need = int(lib.frcnn_jpeg_bound(h, w)), int(lib.frcnn_jpeg_workspace_bytes(h, w))
+    if out is None and bound:
+        out = torch.empty(bound, dtype=torch.uint8, device="cuda")
+    if out_len is None:
+        out_len = torch.zeros(1, dtype=torch.int32, device="cuda")
+    if workspace is None and need:
+        workspace = _ws(need)
+    for name, t, dt in (("out", out, torch.uint8), ("out_len", out_len, torch.int32), ("workspace", workspace, torch.uint8)):
+        if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise _lib.FrcnnError(f"jpeg_encode_u8: {name} must be a contiguous {dt} device tensor")
+    if workspace is not None and workspace.numel() < need:
+        raise _lib.FrcnnError(f"jpeg_encode_u8: workspace of {workspace.numel()} bytes, {need} needed")
+    _lib.call("frcnn_jpeg_encode_u8", _p(frame) if frame.numel() else None, h, w, 1 if bgr else 0, int(quality), _p(out),
+              out.numel() if out is not None else 0, _p(out_len), _p(workspace), _stream())
+    return out, out_len
+
+
+def jpeg_bytes(frame, quality=90, bgr=False):
+    """``jpeg_encode_u8`` and the file as ``bytes``: the eager convenience (one synchronisation, one copy of the encoded length)."""
+    out, out_len = jpeg_encode_u8(frame, quality=quality, bgr=bgr)
+    n = int(out_len.item())
+    if not 0 < n <= out.numel():
+        raise _lib.FrcnnError(f"jpeg_bytes: encoded length {n} outside (0, {out.numel()}]")
+    return out[:n].cpu().numpy().tobytes()
+
 
 def split_detections(packed, rows=None):
     """Views (n_dets, det_bbox, det_cls, det_prob, det_roi) into a `det_packed` buffer (device tensor or its host copy)."""

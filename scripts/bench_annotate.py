@@ -11,9 +11,11 @@ writer threads only writing bytes, plus the bytes written per frame by either en
 host, device with --png_compress runs, device with --png_compress huffman -- ALTERNATING inside every repetition, so that drift of the
 machine falls on all three alike.  ``--content photo`` fills the frames with the VOC fixture photograph (tiled to the frame size, shifted
 per frame) instead of uniform noise: noise does not compress, so bytes per frame mean something only on the photograph.
+``--legs`` names the legs (c) outright, alternating in the same way: besides the three PNG legs, ``jpeg_host`` and ``jpeg_device`` write
+``--frame_format jpg`` at quality 90 with PIL on the writer threads and with the device encoder (ops.jpeg_encode_u8) inside the pass.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
-                                     [--content noise|photo]
+                                     [--legs host,device_huffman,jpeg_host,jpeg_device] [--content noise|photo]
 """
 import argparse
 import contextlib
@@ -74,7 +76,11 @@ def annotate_in_memory(eng, resized, ratios):
     return frames
 
 
-LEGS = {"host": ("host", "runs"), "device": ("device", "runs"), "device_huffman": ("device", "huffman")}      # leg -> (png_encoder, png_compress)
+# leg -> annotate_images' options
+LEGS = {"host": dict(png_encoder="host", png_compress="runs"), "device": dict(png_encoder="device", png_compress="runs"),
+        "device_huffman": dict(png_encoder="device", png_compress="huffman"),
+        "jpeg_host": dict(png_encoder="host", png_compress="runs", frame_format="jpg", jpeg_encoder="host", jpeg_quality=90),
+        "jpeg_device": dict(png_encoder="host", png_compress="runs", frame_format="jpg", jpeg_encoder="device", jpeg_quality=90)}
 
 
 def photo_frames(h, w, n):
@@ -123,11 +129,9 @@ def run_pair(name, cfg, n_frames, reps, encoders=("host",), content="noise"):
         legs, times, sizes = {}, {enc: [] for enc in encoders}, {}
 
         def leg(enc):
-            png_encoder, png_compress = LEGS[enc]
             t0 = time.perf_counter()
             with contextlib.redirect_stdout(io.StringIO()):
-                annotate_video.annotate_images(mgr, det, d_in, d_out, names, cfg["resize"][0], cfg["resize"][1], png_encoder=png_encoder,
-                                               png_compress=png_compress)
+                annotate_video.annotate_images(mgr, det, d_in, d_out, names, cfg["resize"][0], cfg["resize"][1], **LEGS[enc])
             return time.perf_counter() - t0
 
         for enc in encoders:                                        # warm-up: captures
@@ -135,7 +139,8 @@ def run_pair(name, cfg, n_frames, reps, encoders=("host",), content="noise"):
         for _ in range(reps):                                       # the legs alternate inside every repetition
             for enc in encoders:
                 times[enc].append(leg(enc))
-                sizes[enc] = sum(os.path.getsize(os.path.join(d_out, nm)) for nm in names) // n_frames
+                ext = ".jpg" if LEGS[enc].get("frame_format") == "jpg" else ".png"
+                sizes[enc] = sum(os.path.getsize(os.path.join(d_out, nm[:-4] + ext)) for nm in names) // n_frames
         for enc in encoders:
             tag = "c_" if enc == "host" else "c_%s_" % enc
             legs.update({tag + "annotate_images_fps": round(n_frames / statistics.median(times[enc]), 1),
@@ -161,6 +166,7 @@ def main():
     ap.add_argument("--pairs", default=",".join(PAIRS))
     ap.add_argument("--png_encoder", choices=("host", "device", "both", "all"), default="host",
                     help="who encodes leg (c)'s output files; all = host, device (runs) and device (huffman), alternating")
+    ap.add_argument("--legs", default=None, help="the legs (c) by name, comma-separated (%s); overrides --png_encoder" % ", ".join(LEGS))
     ap.add_argument("--content", choices=("noise", "photo"), default="noise", help="what the frames hold (see the module docstring)")
     args = ap.parse_args()
     import torch
@@ -168,7 +174,11 @@ def main():
         raise SystemExit("bench_annotate.py needs a GPU")
     out = {"metric": "annotate_frames_per_s", "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
     for name in args.pairs.split(","):
-        encoders = {"both": ("host", "device"), "all": tuple(LEGS)}.get(args.png_encoder, (args.png_encoder,))
+        encoders = {"both": ("host", "device"), "all": ("host", "device", "device_huffman")}.get(args.png_encoder, (args.png_encoder,))
+        if args.legs:
+            encoders = tuple(args.legs.split(","))
+            if any(e not in LEGS for e in encoders):
+                raise SystemExit("--legs: one or more of %s" % ", ".join(LEGS))
         out[name] = run_pair(name, PAIRS[name], args.frames, args.reps, encoders, args.content)
     print(json.dumps(out))
 
