@@ -186,6 +186,25 @@ JPEG_SIGNATURES = {
     "frcnn_jpeg_encode_u8": (I, [P, I, I, I, I, P, c_size_t, P, P, P]),
 }
 
+JPEG_DEC_VERSION = 1    # include/ext/frcnn_hip_jpeg_dec.h FRCNN_JPEG_DEC_VERSION
+JPEG_DEC_SIGNATURES = {
+    "frcnn_jpeg_dec_version": (I, []),
+    "frcnn_jpeg_dec_plan": (I, [P, c_size_t, P]),
+    "frcnn_jpeg_dec_workspace_bytes": (c_size_t, [P]),
+    "frcnn_jpeg_decode_u8": (I, [P, P, I, P, c_size_t, P, P, P]),
+}
+E_UNSUPPORTED = -4     # include/frcnn_hip.h FRCNN_E_UNSUPPORTED
+JPEG_DEC_BLOCKS, JPEG_DEC_ZIGZAG, JPEG_DEC_CODE, JPEG_DEC_TABLE = 1, 2, 4, 8     # FRCNN_JPEG_DEC_* status bits
+
+
+class JpegDecPlan(ctypes.Structure):
+    """frcnn_jpeg_dec_plan_t (include/ext/frcnn_hip_jpeg_dec.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("h", "w", "components", "hs", "vs", "mcus_x", "mcus_y", "blocks_per_mcu")] + \
+               [(k, ctypes.c_uint32) for k in ("expected_blocks", "restart_interval", "file_len", "scan_off", "scan_len")] + \
+               [("dqt_off", ctypes.c_uint32 * 3), ("dht_off", ctypes.c_uint32 * 2 * 2), ("dht_count", ctypes.c_uint32 * 2 * 2),
+                ("comp_dc", ctypes.c_uint8 * 4), ("comp_ac", ctypes.c_uint8 * 4),
+                ("subsequence_bytes", ctypes.c_uint32), ("subsequences", ctypes.c_uint32)]
+
 
 class ConvDesc(ctypes.Structure):
     """frcnn_conv_desc (include/frcnn_hip.h)."""
@@ -260,6 +279,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in JPEG_DEC_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_jpeg_dec_version() != JPEG_DEC_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_dec_version()} of the JPEG decoder extension, this binding "
+                         f"{JPEG_DEC_VERSION} (include/ext/frcnn_hip_jpeg_dec.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_jpeg_version() != JPEG_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_version()} of the JPEG encoder extension, this binding "
                          f"{JPEG_VERSION} (include/ext/frcnn_hip_jpeg.h): rebuild with `python -m faster_rcnn_amd.build`")

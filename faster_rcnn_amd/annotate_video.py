@@ -219,6 +219,51 @@ def _write_bytes(path, data):
         f.write(data)
 
 
+JPEG_SUFFIXES = (".jpg", ".jpeg")
+JPEG_DECODERS = ("host", "device")
+
+
+def frame_filenames(input_dir, jpeg_decoder="host"):
+    """``png_filenames`` and, with ``jpeg_decoder`` = "device", the ``*.jpg`` / ``*.jpeg`` names too: the input frames, sorted."""
+    from .feed import jpeg_decoder_option
+    if jpeg_decoder_option(jpeg_decoder, "jpeg_decoder") != "device":
+        return png_filenames(input_dir)
+    return sorted(f for f in os.listdir(input_dir) if f.endswith(".png") or f.lower().endswith(JPEG_SUFFIXES))
+
+
+class _FileFrame:
+    """A .jpg input frame the device decodes: the file's bytes and the size its header states (entry.DetectionEntry.host_pixels asks
+    ``raw_file()``); ``raw_rgb`` decodes on the host for whoever still wants pixels."""
+
+    def __init__(self, data, path, file_size, width=None, height=None):
+        self.data, self._image_path, self.file_size = data, path, file_size
+        self.height = int(file_size[0]) if height is None else height
+        self.width = int(file_size[1]) if width is None else width
+        self._pixels = None
+
+    def raw_file(self):
+        return self.data
+
+    def raw_size(self):
+        return self.file_size
+
+    @property
+    def raw_rgb(self):
+        import io
+        from PIL import Image
+        with Image.open(io.BytesIO(self.data)) as im:
+            return np.asarray(im.convert("RGB"))
+
+    raw = property(lambda s: s.raw_rgb[:, :, ::-1])
+
+    def resize(self, scale_ratio):
+        return _FileFrame(self.data, self._image_path, self.file_size, int(round(scale_ratio * self.width)), int(round(scale_ratio * self.height)))
+
+    def resize_within_bounds(self, min_size, max_size):
+        ratio = shapes._bounds_ratio(self.width, self.height, min_size, max_size)
+        return self.resize(ratio), ratio
+
+
 class _Frame:
     """A file-backed frame decoded ahead of time: the reference's InMemoryImage (width, height, resize) whose pixels are
     uploaded in the decoder's RGB order (entry.DetectionEntry.host_pixels: the device resize swaps channels to BGR)."""
@@ -240,13 +285,18 @@ class _Frame:
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
-                    png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None):
+                    png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
     ``frame_format``: "png" or "jpg" (each output keeps its stem and gets the extension .jpg); None = ``default_frame_format()``.
-    ``jpeg_encoder``: "host" or "device", as ``png_encoder``; ``jpeg_quality``: 1..100, None = JPEG_QUALITY."""
+    ``jpeg_encoder``: "host" or "device", as ``png_encoder``; ``jpeg_quality``: 1..100, None = JPEG_QUALITY.
+    ``jpeg_decoder``: "host" or "device": who decodes ``.jpg`` INPUT frames the device decoder supports (captured path only); None =
+    what ``entry.jpeg_decoder()`` says (FRCNN_ENTRY_JPEG_DECODER, default "host")."""
     from concurrent.futures import ThreadPoolExecutor
+    if jpeg_decoder is not None:
+        entry.set_jpeg_decoder(jpeg_decoder)
+    device_decode = entry.jpeg_decoder() == "device"
     png_encoder, png_compress = png_options(png_encoder, png_compress)
     frame_format, jpeg_encoder, jpeg_quality = jpeg_options(frame_format, jpeg_encoder, jpeg_quality, png_encoder, png_compress)
     jpg = frame_format == "jpg"
@@ -279,7 +329,17 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         return
 
     def load(path):                                       # (decode thread) -> (frame, resized, ratio, pixels)
-        frame = _Frame(_read_rgb(path))
+        frame = None
+        if device_decode and path.lower().endswith(JPEG_SUFFIXES):
+            with open(path, "rb") as f:
+                data = f.read()
+            try:
+                plan = ops.jpeg_dec_plan(data)
+                frame = _FileFrame(data, path, (int(plan.h), int(plan.w)))
+            except ops.JpegUnsupported:
+                pass                                          # (progressive, CMYK, ...: PIL below)
+        if frame is None:
+            frame = _Frame(_read_rgb(path))
         resized, ratio = frame.resize_within_bounds(resize_min, resize_max)
         return frame, resized, ratio, eng.host_pixels(resized)
 
@@ -371,6 +431,9 @@ def build_parser():
     p.add_argument("--jpeg_encoder", dest="jpeg_encoder", choices=JPEG_ENCODERS, default=default_jpeg_encoder(),
                    help="who encodes JPEG frames: host = PIL on writer threads, device = inside the detection pass on the GPU "
                         "(FRCNN_ANNOTATE_JPEG_ENCODER sets the default; needs --frame_format jpg)")
+    p.add_argument("--jpeg_decoder", dest="jpeg_decoder", choices=JPEG_DECODERS, default=None,
+                   help="who decodes .jpg INPUT frames: host (PIL) or device (csrc/jpeg_dec.hip; input_dir's *.jpg / *.jpeg are then "
+                        "taken beside its *.png); default: FRCNN_ENTRY_JPEG_DECODER, else host")
     p.add_argument("--jpeg_quality", dest="jpeg_quality", type=int, default=None,
                    help="IJG quality of JPEG frames, 1..100 (default %d; needs --frame_format jpg)" % JPEG_QUALITY)
     return p
@@ -400,7 +463,8 @@ def main(argv=None):
     manager = DetTrainingManager(rpn_model=rpn, class_mapping=class_mapping, preprocess_func=preprocess, anchor_dims=anchors)
     resize_min, resize_max = resize_dims_from_str(args.resize_dims)
     annotate_images(training_manager=manager, detector=detector, input_dir=args.input_dir, out_dir=args.out_dir,
-                    image_filenames=png_filenames(args.input_dir), resize_min=resize_min, resize_max=resize_max,
+                    image_filenames=frame_filenames(args.input_dir, args.jpeg_decoder or entry.jpeg_decoder()), resize_min=resize_min,
+                    resize_max=resize_max, jpeg_decoder=args.jpeg_decoder,
                     png_encoder=args.png_encoder, png_compress=args.png_compress, frame_format=args.frame_format,
                     jpeg_encoder=args.jpeg_encoder, jpeg_quality=args.jpeg_quality)
 

@@ -112,6 +112,7 @@ class DetTrainingManager:
             if not have:
                 rois, feat = self._proposals_dev(image, 12000, 2000, x=x)
                 filtered_rois, y_class_num, y_transform = _rois_to_truth(rois, image, self.class_mapping, stride=self.stride)
+                feed.check_decodes()                          # (the proposals were just read on the host: a device decode's status is back too)
                 self._cache[key] = {"rois": filtered_rois, "y_class_num": y_class_num, "y_transform": y_transform}
             first = feat if self.conv_only else x
             if first is not None:

@@ -89,6 +89,30 @@ WARMUP_PASSES = max(1, int(os.environ.get("FRCNN_ENTRY_WARMUP", "1")))
 # PLANS the classes from the list's size histogram (DetectionEntry.plan_canvases): few classes, each worth its captures.
 # file-backed frames go up in the decoder's channel order and are swapped to BGR by the device resize (0: reverse on the host as before)
 RGB_UPLOAD = os.environ.get("FRCNN_ENTRY_RGB_UPLOAD", "1") != "0"
+# who decodes a file-backed frame: "host" (PIL, the default) or "device" (ops.jpeg_decode_u8 in front of the replay, for the files its
+# planner supports and for per-geometry passes; PIL for the rest and for canvas passes).  FRCNN_ENTRY_JPEG_DECODER, or
+# ``set_jpeg_decoder`` (voc_dets / annotate_video --jpeg_decoder), which wins.
+_JPEG_DECODER = None
+
+
+def set_jpeg_decoder(value):
+    """"host" / "device" for every DetectionEntry of the process from now on; None: back to FRCNN_ENTRY_JPEG_DECODER."""
+    global _JPEG_DECODER
+    from .feed import jpeg_decoder_option
+    _JPEG_DECODER = None if value is None else jpeg_decoder_option(value, "jpeg_decoder")
+
+
+def jpeg_decoder():
+    from .feed import jpeg_decoder_option
+    return _JPEG_DECODER or jpeg_decoder_option(os.environ.get("FRCNN_ENTRY_JPEG_DECODER"), "FRCNN_ENTRY_JPEG_DECODER")
+
+
+class JpegFile:
+    """What ``host_pixels`` hands ``submit_batch`` in place of the decoded array when the device decodes: the file and its plan."""
+    __slots__ = ("data", "plan", "name")
+
+    def __init__(self, data, plan, name):
+        self.data, self.plan, self.name = data, plan, name
 CANVAS_GRANULE = int(os.environ.get("FRCNN_ENTRY_CANVAS_GRANULE", "32"))
 CANVAS_MIN_GEOMETRIES = int(os.environ.get("FRCNN_ENTRY_CANVAS_MIN", "4"))
 # captured passes kept per canvas class: with several classes interleaving in a list, two of one class in flight at once is the common
@@ -223,7 +247,8 @@ class _Slot:
     are read back with every replay)."""
     __slots__ = ("key", "pipe", "graph", "out", "io_dev", "io_pin", "dyn_host", "out_pin", "event", "busy", "nbytes", "x_f32", "ws", "tabs", "u8_resized",
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
-                 "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy")
+                 "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy",
+                 "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names")
 
     def __init__(self):
         for name in self.__slots__:
@@ -590,6 +615,13 @@ class DetectionEntry:
         Returns (array, H, W, src or None, flip)."""
         if self.device_preprocess and _declares(image, "raw") and _declares(image, "height"):
             H, W, flip = int(image.height), int(image.width), bool(getattr(image, "flipped", False))
+            if RGB_UPLOAD and not self.canvas and jpeg_decoder() == "device":
+                from . import feed
+                planned = feed.plan_file(image)               # None: in-memory pixels, or a file the device decoder does not take
+                if planned is not None:
+                    data, plan = planned
+                    return JpegFile(data, plan, getattr(image, "_image_path", None) or str(getattr(image, "name", "?"))), H, W, \
+                        (int(plan.h), int(plan.w)), 2 | int(flip)
             rgb = getattr(image, "raw_rgb", None) if RGB_UPLOAD else None
             if rgb is not None:
                 # a file-backed frame goes up as the decoder delivers it (RGB); the device resize writes B, G, R (flip bit 1) -- a resize to
@@ -764,12 +796,14 @@ class DetectionEntry:
             s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
         else:
             s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality))
-        metas = []
+        metas, files = [], []
         for i in range(B):
             j = i if i < len(images) else 0
             s.dyn_host[i, 0], s.dyn_host[i, 1] = float(resize_ratios[j]), float(det_threshold)
             if s.canvas:
                 metas.append(self._canvas_frame(s, i, pixels[j]))
+            elif isinstance(pixels[j][0], JpegFile):
+                files.append((i, pixels[j][0]))
             else:
                 np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
         st = self._streams[self._seq % self.in_flight]
@@ -778,10 +812,18 @@ class DetectionEntry:
             if s.ready is not None:
                 st.wait_event(s.ready)                             # (the first replay of a fresh pass: behind its warm-up)
                 s.ready = None
+            if files:
+                self._stage_files(s, files)
+            else:
+                s.jpg_names = None
             s.io_dev.copy_(s.io_pin, non_blocking=True)
             if s.canvas:
                 self._canvas_preprocess(s, metas)
+            if files:
+                self._decode_files(s, files, src)                   # each file's frame into its source segment, behind the io copy
             s.graph.replay()
+            if files:
+                s.jpg_status_pin.copy_(s.jpg_status, non_blocking=True)
             for i in range(len(images)):
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
                 if s.encode == JPEG_ENCODE:
@@ -793,6 +835,36 @@ class DetectionEntry:
             s.event.record(st)
         s.busy = True
         return Ticket(s, list(images))
+
+    def _stage_files(self, s, files):
+        """Host side of a pass whose frames the device decodes: the files' bytes into the slot's pinned file area (grow-only; the slot is
+        idle, so nothing reads the old one), room for them and for the decoder's workspace on the device."""
+        B = s.batch
+        cap = (max(len(f.data) for _, f in files) + 255) // 256 * 256
+        if s.jpg_pin is None or s.jpg_pin.shape[1] < cap:
+            s.jpg_pin = torch.empty((B, cap + cap // 4), dtype=torch.uint8).pin_memory()
+            s.jpg_dev = torch.empty((B, cap + cap // 4), dtype=torch.uint8, device="cuda")
+        need = max(ops.jpeg_dec_workspace_bytes(f.plan) for _, f in files)
+        if s.jpg_ws is None or s.jpg_ws.numel() < need:
+            s.jpg_ws = torch.empty(need + need // 4, dtype=torch.uint8, device="cuda")
+        if s.jpg_status is None:
+            s.jpg_status = torch.zeros(B, dtype=torch.int32, device="cuda")
+            s.jpg_status_pin = torch.zeros(B, dtype=torch.int32).pin_memory()
+        s.jpg_names = [None] * B
+        for i, f in files:
+            s.jpg_pin[i, :len(f.data)].numpy()[:] = np.frombuffer(f.data, dtype=np.uint8)
+            s.jpg_names[i] = f.name
+
+    def _decode_files(self, s, files, src):
+        """Device side, on the pass's stream between the io copy and the replay: upload, clear the status words, decode every file into
+        its frame's source segment (R,G,B as PIL delivers it: the pass's resize swaps, flip bit 1)."""
+        in_h, in_w = src
+        s.jpg_status.zero_()
+        for i, f in files:
+            n = len(f.data)
+            s.jpg_dev[i, :n].copy_(s.jpg_pin[i, :n], non_blocking=True)
+            out = s.io_dev[i * s.seg:i * s.seg + in_h * in_w * 3].view(in_h, in_w, 3)
+            ops.jpeg_decode_u8(s.jpg_dev[i, :n], f.plan, out=out, status=s.jpg_status[i:i + 1], workspace=s.jpg_ws)
 
     def _canvas_frame(self, s, i, pixels):
         """Frame i of a canvas pass, host side: the frame goes into its staging segment at ITS size, its true size into the extents.
@@ -826,6 +898,12 @@ class DetectionEntry:
             s.event.synchronize()
             rev = self.rev_class_mapping
             res = []
+            if s.jpg_names:
+                words = s.jpg_status_pin.numpy()
+                for i, name in enumerate(s.jpg_names):
+                    if name is not None and int(words[i]):
+                        raise FrcnnError("device JPEG decoder: %s is damaged (status %d: FRCNN_JPEG_DEC_* in include/ext/frcnn_hip_jpeg_dec.h); "
+                                         "decode it on the host or repair the file" % (name, int(words[i])))
             if s.amax is not None:
                 bits = int(s.out_pin[0].numpy()[2])                 # the pass's f16x3 status word (pipeline._pass_status)
                 if bits:

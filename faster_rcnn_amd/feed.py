@@ -16,6 +16,35 @@ from .shapes import declares as _declares
 
 MEAN_BGR = (103.939, 116.779, 123.68)           # resnet.preprocess / vgg.preprocess (resnet.py:64-75, vgg.py:52-57)
 RGB_UPLOAD = os.environ.get("FRCNN_FEED_RGB_UPLOAD", "1") != "0"
+JPEG_DECODERS = ("host", "device")
+
+
+def jpeg_decoder_option(value, what):
+    """A decoder setting ("host": PIL, the default; "device": ops.jpeg_decode_u8 for the files its planner supports, PIL for the rest)
+    checked: -> the value, ValueError naming ``what`` (an environment variable, an option) for anything else."""
+    value = "host" if value is None or value == "" else value
+    if value not in JPEG_DECODERS:
+        raise ValueError("%s=%r: one of %s" % (what, value, ", ".join(JPEG_DECODERS)))
+    return value
+
+
+def default_jpeg_decoder():
+    """FRCNN_FEED_JPEG_DECODER: who decodes a file-backed frame for ``device_image`` (read at every call: a test may set it)."""
+    return jpeg_decoder_option(os.environ.get("FRCNN_FEED_JPEG_DECODER"), "FRCNN_FEED_JPEG_DECODER")
+
+
+def plan_file(image):
+    """(the file's bytes, its decode plan) of a file-backed image the device decoder supports, else None (in-memory pixels, no
+    ``raw_file``, a file outside the supported set: the caller takes the host path).  Pure host work: a thread may do it ahead."""
+    if not _declares(image, "raw_file") or getattr(image, "_pixels", None) is not None:
+        return None
+    data = image.raw_file()
+    if data is None:
+        return None
+    try:
+        return data, ops.jpeg_dec_plan(data)
+    except ops.JpegUnsupported:
+        return None
 
 
 class _PinRing:
@@ -88,8 +117,10 @@ _DECODED = {}                                    # id(image) -> (image, Future o
 
 
 def decode_ahead(image):
-    """Start decoding a file-backed image's pixels on the background thread (device_image picks the result up)."""
+    """Start decoding a file-backed image's pixels on the background thread (device_image picks the result up).  With the device decoder
+    the thread reads the file and plans it instead; an unsupported file is decoded there as before."""
     global _DECODER
+    device = default_jpeg_decoder() == "device"
     if not (DECODE_AHEAD and RGB_UPLOAD and hasattr(type(image), "raw_rgb")) or getattr(image, "_pixels", 0) is not None or id(image) in _DECODED:
         return
     if _DECODER is None:
@@ -97,14 +128,65 @@ def decode_ahead(image):
         _DECODER = ThreadPoolExecutor(max_workers=1, thread_name_prefix="frcnn-decode")
     if len(_DECODED) > 8:
         _DECODED.clear()                                      # (frames asked for and never taken: forget them)
-    _DECODED[id(image)] = (image, _DECODER.submit(lambda: image.raw_rgb))
+    def work():
+        planned = plan_file(image) if device else None
+        return planned if planned is not None else image.raw_rgb
+    _DECODED[id(image)] = (image, _DECODER.submit(work))
 
 
 def _raw_rgb(image):
+    """The decoded RGB frame, or with the device decoder (file bytes, plan) for a supported file."""
     ent = _DECODED.pop(id(image), None)
     if ent is not None and ent[0] is image:
-        return ent[1].result()
+        got = ent[1].result()
+        if not isinstance(got, tuple) or default_jpeg_decoder() == "device":
+            return got
+        return image.raw_rgb                                  # (planned ahead, and the setting changed since)
+    if default_jpeg_decoder() == "device":
+        planned = plan_file(image)
+        if planned is not None:
+            return planned
     return image.raw_rgb
+
+
+# Device decodes whose status word has not been looked at: (pinned int32 [1], event behind its copy, file name).  ``check_decodes`` is
+# called where a training manager has just synchronised for its own counts: it reads the words whose copy has FINISHED and waits for none.
+_DECODE_STATUS = []
+_STATUS_PIN, _STATUS_AT = None, 0
+
+
+def _decode_on_device(data, plan, name):
+    """The file decoded on the current stream -> (h, w, 3) uint8 R,G,B device tensor; its status word is queued for check_decodes."""
+    file_dev = upload(np.frombuffer(data, dtype=np.uint8))
+    rgb, status = ops.jpeg_decode_u8(file_dev, plan)
+    global _STATUS_PIN, _STATUS_AT
+    if _STATUS_PIN is None:
+        _STATUS_PIN = torch.zeros(64, dtype=torch.int32).pin_memory()
+    if len(_DECODE_STATUS) >= 32:                             # (nobody called check_decodes: the oldest word's place is needed again)
+        _DECODE_STATUS[0][1].synchronize()
+        check_decodes()
+    word, _STATUS_AT = _STATUS_PIN[_STATUS_AT:_STATUS_AT + 1], (_STATUS_AT + 1) % 64
+    word.copy_(status, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    _DECODE_STATUS.append((word, ev, name))
+    return rgb
+
+
+def check_decodes():
+    """Raise FrcnnError for a device decode that reported a damaged file.  Never waits: a word still in flight stays for the next call."""
+    if not _DECODE_STATUS:
+        return
+    waiting, bad = [], None
+    for word, ev, name in _DECODE_STATUS:
+        if not ev.query():
+            waiting.append((word, ev, name))
+        elif int(word[0]) and bad is None:
+            bad = (name, int(word[0]))
+    _DECODE_STATUS[:] = waiting
+    if bad is not None:
+        raise ops._lib.FrcnnError("device JPEG decoder: %s is damaged (status %d: FRCNN_JPEG_DEC_* in include/ext/frcnn_hip_jpeg_dec.h); "
+                                  "decode it on the host or repair the file" % bad)
 
 
 def device_image(image, preprocess_func):
@@ -114,6 +196,9 @@ def device_image(image, preprocess_func):
         # a file-backed frame goes up in the JPEG decoder's channel order; the device resize (to its own size when none is needed: a
         # copy) writes B, G, R -- the host's channel reversal cost as much as half the decode (round 6, as entry.DetectionEntry)
         rgb = _raw_rgb(image) if (RGB_UPLOAD and hasattr(type(image), "raw_rgb")) else None
+        if isinstance(rgb, tuple):                               # (file bytes, plan): decoded on the device into what the resize reads
+            dev = _decode_on_device(rgb[0], rgb[1], getattr(image, "_image_path", None) or getattr(image, "name", "?"))
+            return ops.preprocess_u8(ops.resize_cubic_u8(dev, H, W, flip=2 | int(flip)), MEAN_BGR)
         if rgb is not None:
             rgb = np.asarray(rgb)
             if rgb.dtype == np.uint8 and rgb.ndim == 3 and rgb.shape[2] == 3:

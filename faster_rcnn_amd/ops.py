@@ -1193,6 +1193,72 @@ def jpeg_bytes(frame, quality=90, bgr=False):
     return out[:n].cpu().numpy().tobytes()
 
 
+class JpegUnsupported(_lib.FrcnnError):
+    """``jpeg_dec_plan``: the file lies outside the device decoder's supported set; the message names the reason."""
+
+
+def jpeg_dec_plan(data):
+    """The host-side marker parse of a .jpg file's bytes (frcnn_jpeg_dec_plan) -> a ``_lib.JpegDecPlan``: size, components, sampling,
+    where the tables and the entropy-coded segment lie, into how many subsequences it is cut.  ``JpegUnsupported`` (a FrcnnError) with
+    the reason for a file outside the supported set (include/ext/frcnn_hip_jpeg_dec.h): the caller decodes it on the host.  A pure host
+    call: needs the built library, no GPU."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise _lib.FrcnnError("jpeg_dec_plan: the file's bytes, got %s" % type(data).__name__)
+    data = bytes(data)
+    plan = _lib.JpegDecPlan()
+    lib = _lib.load()
+    code = lib.frcnn_jpeg_dec_plan(data, len(data), ctypes.byref(plan))
+    if code == _lib.E_UNSUPPORTED:
+        raise JpegUnsupported((lib.frcnn_last_error() or b"").decode())
+    _lib.check(code, "frcnn_jpeg_dec_plan")
+    return plan
+
+
+def jpeg_dec_workspace_bytes(plan):
+    """Bytes of device workspace ``jpeg_decode_u8`` needs for ``plan`` (frcnn_jpeg_dec_workspace_bytes)."""
+    n = int(_lib.load().frcnn_jpeg_dec_workspace_bytes(ctypes.byref(plan)))
+    if n == 0:
+        raise _lib.FrcnnError("jpeg_dec_workspace_bytes: not a plan that jpeg_dec_plan made")
+    return n
+
+
+def jpeg_decode_u8(file, plan=None, bgr=False, out=None, status=None, workspace=None):
+    """Decode a baseline .jpg file on the device (frcnn_jpeg_decode_u8): ``file`` is its bytes, or a uint8 device tensor that holds them
+    (then ``plan`` = jpeg_dec_plan(bytes) is required) -> (out, status): ``out`` an (h, w, 3) uint8 device tensor, R,G,B per pixel or
+    (``bgr``) B,G,R, the pixels libjpeg's default decoder gives; ``status`` int32 [1], 0 for a sound file, _lib.JPEG_DEC_* bits ORed in
+    otherwise (sticky: a status tensor passed in is not cleared; ``out`` is undefined then).  What is not passed (``workspace`` included) is
+    allocated.  The device-tensor form never synchronises: the caller reads ``status`` where it synchronises anyway.  The bytes form is a
+    convenience: its upload is a pageable copy, which blocks the host.  ``JpegUnsupported`` for a file outside the supported set."""
+    _require_gpu()
+    if isinstance(file, (bytes, bytearray, memoryview)):
+        data = bytes(file)
+        if plan is None:
+            plan = jpeg_dec_plan(data)
+        file = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    if not (isinstance(file, torch.Tensor) and file.is_cuda and file.dtype == torch.uint8 and file.dim() == 1 and file.is_contiguous()):
+        raise _lib.FrcnnError("jpeg_decode_u8: file must be bytes or a contiguous 1-d uint8 device tensor")
+    if not isinstance(plan, _lib.JpegDecPlan):
+        raise _lib.FrcnnError("jpeg_decode_u8: a device tensor needs the plan of its bytes (jpeg_dec_plan)")
+    if file.numel() < plan.file_len:
+        raise _lib.FrcnnError(f"jpeg_decode_u8: file of {file.numel()} bytes, the plan was made of {plan.file_len}")
+    need = jpeg_dec_workspace_bytes(plan)
+    h, w = int(plan.h), int(plan.w)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    if workspace is None:
+        workspace = _ws(need)
+    for name, t, dt in (("out", out, torch.uint8), ("status", status, torch.int32), ("workspace", workspace, torch.uint8)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise _lib.FrcnnError(f"jpeg_decode_u8: {name} must be a contiguous {dt} device tensor")
+    if workspace.numel() < need:
+        raise _lib.FrcnnError(f"jpeg_decode_u8: workspace of {workspace.numel()} bytes, {need} needed")
+    _lib.call("frcnn_jpeg_decode_u8", _p(file), ctypes.byref(plan), 1 if bgr else 0, _p(out), out.numel(), _p(status), _p(workspace),
+              _stream())
+    return out, status
+
+
 def split_detections(packed, rows=None):
     """Views (n_dets, det_bbox, det_cls, det_prob, det_roi) into a `det_packed` buffer (device tensor or its host copy)."""
     rows = (packed.numel() - 4) // 7 if rows is None else rows

@@ -87,6 +87,7 @@ class RpnTrainingManager:
         self.prefetch(image)
         x, can_use, is_pos, bbreg, pos_locs, neg_locs, counts_host, ev, cells = self._dev.pop(image.cache_key)
         ev.synchronize()
+        feed.check_decodes()                                  # (a device JPEG decode's status word came back in front of the counts)
         num_pos, num_neg = (int(v) for v in counts_host.tolist())
         off_pos, off_neg = _sample_off(num_pos, num_neg)           # the reference's two draws, in its order (rpn_util.py:336-348)
         with torch.cuda.stream(self._own_stream()):

@@ -119,6 +119,14 @@ class Image:
         self.__dict__["_raw_size"] = (int(arr.shape[0]), int(arr.shape[1]))
         return arr
 
+    def raw_file(self):
+        """The bytes of the image's file, or None for in-memory pixels: what a device-side decoder (ops.jpeg_dec_plan, ops.jpeg_decode_u8)
+        takes in place of ``raw_rgb``.  (A method, not a property: see ``declares``.)"""
+        if self._pixels is not None:
+            return None
+        with open(self._image_path, "rb") as f:
+            return f.read()
+
     def raw_size(self):
         """(height, width) of ``raw`` without decoding the pixels (PIL reads the header only)."""
         if self._pixels is not None:

@@ -283,6 +283,9 @@ def build_parser():
     p.add_argument("--network", dest="network", choices=("vgg16", "resnet50", "resnet101"), default="vgg16")
     p.add_argument("--out_dir", dest="out_dir", default=".")
     p.add_argument("--det_threshold", dest="det_threshold", default=DEFAULT_DET_THRESHOLD)
+    p.add_argument("--jpeg_decoder", dest="jpeg_decoder", choices=("host", "device"), default=None,
+                   help="who decodes the images' JPEG files: host (PIL) or device (csrc/jpeg_dec.hip, for baseline files and per-geometry "
+                        "passes; PIL for the rest); default: FRCNN_ENTRY_JPEG_DECODER, else host")
     p.add_argument("--dtype", dest="dtype", choices=("f32", "bf16"), default="f32",
                    help="precision the networks are served in: bf16 = the bf16 conv path on the matrix cores (the reference has no such flag: it runs fp32 only)")
     return p
@@ -295,6 +298,9 @@ def main(argv=None):
     from .data.voc_data_helpers import KITTI_CLASS_MAPPING, VOC_CLASS_MAPPING
     from .util import get_anchors, resize_imgs
     args = build_parser().parse_args(argv)
+    if args.jpeg_decoder is not None:
+        from . import entry
+        entry.set_jpeg_decoder(args.jpeg_decoder)
     # four passes in flight -- staging copy, replay, read-back each -- want more hardware queues than the runtime's default four (497 ->
     # 542-547 img/s on eight, entry.default_in_flight); read when the HIP runtime starts, an explicit setting wins
     os.environ.setdefault("GPU_MAX_HW_QUEUES", ENTRY_HW_QUEUES)
