@@ -193,6 +193,13 @@ JPEG_DEC_SIGNATURES = {
     "frcnn_jpeg_dec_workspace_bytes": (c_size_t, [P]),
     "frcnn_jpeg_decode_u8": (I, [P, P, I, P, c_size_t, P, P, P]),
 }
+JPEG_DEC_BATCH_VERSION = 1      # include/ext/frcnn_hip_jpeg_dec_batch.h FRCNN_JPEG_DEC_BATCH_VERSION
+JPEG_DEC_BATCH_MAX = 64         # ... FRCNN_JPEG_DEC_BATCH_MAX
+JPEG_DEC_BATCH_SIGNATURES = {
+    "frcnn_jpeg_dec_batch_version": (I, []),
+    "frcnn_jpeg_dec_batch_layout": (c_size_t, [P, I, P]),
+    "frcnn_jpeg_decode_batch_u8": (I, [P, P, I, P, c_size_t, I, P, c_size_t, P, P, c_size_t, P]),
+}
 E_UNSUPPORTED = -4     # include/frcnn_hip.h FRCNN_E_UNSUPPORTED
 JPEG_DEC_BLOCKS, JPEG_DEC_ZIGZAG, JPEG_DEC_CODE, JPEG_DEC_TABLE = 1, 2, 4, 8     # FRCNN_JPEG_DEC_* status bits
 
@@ -204,6 +211,11 @@ class JpegDecPlan(ctypes.Structure):
                [("dqt_off", ctypes.c_uint32 * 3), ("dht_off", ctypes.c_uint32 * 2 * 2), ("dht_count", ctypes.c_uint32 * 2 * 2),
                 ("comp_dc", ctypes.c_uint8 * 4), ("comp_ac", ctypes.c_uint8 * 4),
                 ("subsequence_bytes", ctypes.c_uint32), ("subsequences", ctypes.c_uint32)]
+
+
+class JpegDecBatchItem(ctypes.Structure):
+    """frcnn_jpeg_dec_batch_item_t (include/ext/frcnn_hip_jpeg_dec_batch.h)."""
+    _fields_ = [("plan", JpegDecPlan), ("file_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("ws_off", ctypes.c_uint64)]
 
 
 class ConvDesc(ctypes.Structure):
@@ -283,6 +295,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in JPEG_DEC_BATCH_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_jpeg_dec_batch_version() != JPEG_DEC_BATCH_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_dec_batch_version()} of the JPEG decoder's batch extension, this binding "
+                         f"{JPEG_DEC_BATCH_VERSION} (include/ext/frcnn_hip_jpeg_dec_batch.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_jpeg_dec_version() != JPEG_DEC_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_dec_version()} of the JPEG decoder extension, this binding "
                          f"{JPEG_DEC_VERSION} (include/ext/frcnn_hip_jpeg_dec.h): rebuild with `python -m faster_rcnn_amd.build`")

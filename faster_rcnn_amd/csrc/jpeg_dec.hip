@@ -20,10 +20,15 @@
 //
 // Bounds.  Every byte of the segment is read through rd() (zero past its end); a block index is checked against the plan's total before
 // a coefficient is written; a zigzag index never passes 63; table indices are checked; the planes hold whole MCUs.  So a damaged scan
-// yields a status word, not a fault.  One workgroup per file leaves the entropy stage on ONE CU: it is the batch (other files' decodes on
-// other streams) and the other passes in flight that fill the chip.
+// yields a status word, not a fault.  One workgroup per file leaves the entropy stage on ONE CU: it is the batch that fills the chip.
+//
+// The batched form (include/ext/frcnn_hip_jpeg_dec_batch.h): k_jpeg_dec_*_batch run the SAME __device__ bodies for n files in one launch
+// each.  A table of items (plan + where the file, the frame and the workspace region lie) in device memory replaces the by-value plan;
+// a workgroup finds its item from its grid index and returns as a whole where the grid, sized by the batch's largest item, reaches past
+// its own.  Every bound above holds per item: its status word, its workspace region, its output range.
 #include "common.h"
 #include "../../include/ext/frcnn_hip_jpeg_dec.h"
+#include "../../include/ext/frcnn_hip_jpeg_dec_batch.h"
 
 namespace frcnn {
 namespace {
@@ -37,6 +42,7 @@ constexpr int DEC_COLOUR_THREADS = 256;
 constexpr int DEC_DC_THREADS = 1024;
 
 using Plan = frcnn_jpeg_dec_plan_t;
+using Item = frcnn_jpeg_dec_batch_item_t;
 
 struct DecZigzag { uint8_t at[64]; };
 // zigzag position -> natural index 8 * v + u
@@ -44,17 +50,23 @@ __constant__ DecZigzag DEC_ZIGZAG = {{0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 
                                       35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}};
 
 // ------------------------------------------------------------------------------------------------------------------- host sizes
+struct DecPlanes { uint8_t* p[3]; int pw[3]; };
 struct DecLayout { size_t coef, flags, plane[3], total; int pw[3], ph[3]; };
 
-inline DecLayout dec_layout(const Plan& p) {
+__host__ __device__ inline size_t dec_align16(size_t v) { return (v + 15) / 16 * 16; }
+
+// (also on the device: a batched kernel finds its item's arrays from the plan it reads)
+__host__ __device__ inline DecLayout dec_layout(const Plan& p) {
     DecLayout l = {};
     size_t at = 0;
-    l.coef = at; at += align_up((size_t)p.expected_blocks * 128, 16);
-    l.flags = at; at += align_up((size_t)p.expected_blocks, 16);
-    for (int c = 0; c < p.components; ++c) {
+    l.coef = at; at += dec_align16((size_t)p.expected_blocks * 128);
+    l.flags = at; at += dec_align16((size_t)p.expected_blocks);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {                               // (constant indices: the device keeps the struct in registers)
+        if (c >= p.components) continue;
         l.pw[c] = p.mcus_x * 8 * (c ? 1 : p.hs);
         l.ph[c] = p.mcus_y * 8 * (c ? 1 : p.vs);
-        l.plane[c] = at; at += align_up((size_t)l.pw[c] * (size_t)l.ph[c], 16);
+        l.plane[c] = at; at += dec_align16((size_t)l.pw[c] * (size_t)l.ph[c]);
     }
     l.total = at;
     return l;
@@ -227,7 +239,9 @@ __device__ __forceinline__ uint32_t dec_wave_scan(uint32_t v) {
     return v;
 }
 
-__global__ void __launch_bounds__(DEC_MAX_LANES) k_jpeg_dec_entropy(const uint8_t* file, Plan plan, int16_t* coef, uint8_t* flags, int32_t* status) {
+// The entropy stage of ONE file by the whole workgroup (blockDim.x a multiple of 64, >= plan.subsequences; lanes past the file's
+// subsequences idle through every barrier: ``active`` is false for them, so they never change the round loop's flag).
+__device__ __forceinline__ void dec_entropy_body(const uint8_t* file, const Plan& plan, int16_t* coef, uint8_t* flags, int32_t* status) {
     __shared__ HuffLds s_huff;
     __shared__ uint32_t s_xpos[DEC_MAX_LANES], s_xbz[DEC_MAX_LANES];
     __shared__ uint32_t s_part[DEC_MAX_LANES / 64];
@@ -345,12 +359,40 @@ __global__ void __launch_bounds__(DEC_MAX_LANES) k_jpeg_dec_entropy(const uint8_
     }
 }
 
+__global__ void __launch_bounds__(DEC_MAX_LANES) k_jpeg_dec_entropy(const uint8_t* file, Plan plan, int16_t* coef, uint8_t* flags, int32_t* status) {
+    dec_entropy_body(file, plan, coef, flags, status);
+}
+
+// The batched kernels: grid index -> item.  The item lies in device memory at an address that is uniform over the workgroup and that
+// nothing written here aliases (__restrict__): its fields are scalar loads, as the by-value plan's are from the kernel arguments.
+struct DecItemArrays { const uint8_t* file; int16_t* coef; uint8_t* flags; DecPlanes planes; };
+
+__device__ __forceinline__ DecItemArrays dec_item_arrays(const Item& it, const uint8_t* files, uint8_t* workspace) {
+    const DecLayout l = dec_layout(it.plan);
+    uint8_t* ws = workspace + it.ws_off;
+    DecItemArrays a = {};
+    a.file = files + it.file_off;
+    a.coef = reinterpret_cast<int16_t*>(ws + l.coef);
+    a.flags = ws + l.flags;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        if (c < it.plan.components) { a.planes.p[c] = ws + l.plane[c]; a.planes.pw[c] = l.pw[c]; }
+    return a;
+}
+
+// grid.x = item; the block is the batch's largest ``subsequences`` rounded up to 64
+__global__ void __launch_bounds__(DEC_MAX_LANES) k_jpeg_dec_entropy_batch(const uint8_t* files, const Item* __restrict__ items, uint8_t* workspace, int32_t* status) {
+    const Item& it = items[blockIdx.x];
+    const DecItemArrays a = dec_item_arrays(it, files, workspace);
+    dec_entropy_body(a.file, it.plan, a.coef, a.flags, status + blockIdx.x);
+}
+
 // One workgroup per component.  Its blocks in coding order, a stretch per lane: (cut seen, sum since the cut or the stretch's start)
 // folded per stretch, scanned across the lanes (Hillis-Steele in LDS), then each stretch written with the sum that flows into it.
-__global__ void __launch_bounds__(DEC_DC_THREADS) k_jpeg_dec_dc(Plan plan, int16_t* coef, const uint8_t* flags) {
+__device__ __forceinline__ void dec_dc_body(const Plan& plan, uint32_t comp, int16_t* coef, const uint8_t* flags) {
     __shared__ int s_sum[DEC_DC_THREADS];
     __shared__ uint32_t s_cut[DEC_DC_THREADS];
-    const uint32_t tid = threadIdx.x, comp = blockIdx.x;
+    const uint32_t tid = threadIdx.x;
     const uint32_t bpm = (uint32_t)plan.blocks_per_mcu, luma = plan.components == 3 ? (uint32_t)(plan.hs * plan.vs) : 1u;
     const uint32_t mcus = (uint32_t)plan.mcus_x * (uint32_t)plan.mcus_y;
     const uint32_t n = comp == 0 ? mcus * luma : mcus;          // blocks of this component
@@ -387,6 +429,18 @@ __global__ void __launch_bounds__(DEC_DC_THREADS) k_jpeg_dec_dc(Plan plan, int16
     }
 }
 
+__global__ void __launch_bounds__(DEC_DC_THREADS) k_jpeg_dec_dc(Plan plan, int16_t* coef, const uint8_t* flags) {
+    dec_dc_body(plan, blockIdx.x, coef, flags);
+}
+
+// grid = (3, items): a workgroup whose component the item does not have returns as a whole
+__global__ void __launch_bounds__(DEC_DC_THREADS) k_jpeg_dec_dc_batch(const Item* __restrict__ items, uint8_t* workspace) {
+    const Item& it = items[blockIdx.y];
+    if ((int)blockIdx.x >= it.plan.components) return;
+    const DecItemArrays a = dec_item_arrays(it, nullptr, workspace);
+    dec_dc_body(it.plan, blockIdx.x, a.coef, a.flags);
+}
+
 // jidctint's 8-point pass (CONST_BITS 13): x in, the eight outputs descaled by SHIFT.  The sums are formed in uint32_t: the same bits as
 // int for every sound file (|sum| < 2^31), and a defined wrap instead of a signed overflow for the coefficients of a damaged one.
 template <int SHIFT>
@@ -414,17 +468,15 @@ __device__ __forceinline__ void idct_1d(const int (&xi)[8], int (&y)[8]) {
     y[3] = (int)(tmp13 + t0 + HALF) >> SHIFT; y[4] = (int)(tmp13 - t0 + HALF) >> SHIFT;
 }
 
-struct DecPlanes { uint8_t* p[3]; int pw[3]; };
-
 // Eight lanes per block: lane = column in the first pass, row in the second; the 8x8 intermediate through LDS (row stride 9).
-__global__ void __launch_bounds__(DEC_IDCT_THREADS) k_jpeg_dec_idct(const uint8_t* file, Plan plan, const int16_t* coef, DecPlanes planes) {
+__device__ __forceinline__ void dec_idct_body(const uint8_t* file, const Plan& plan, const int16_t* coef, const DecPlanes planes, uint32_t group) {
     __shared__ int s_ws[DEC_IDCT_BLOCKS][72];
     __shared__ uint16_t s_q[3][64];                             // natural order
     const uint32_t tid = threadIdx.x, sub = tid >> 3, lane = tid & 7u;
     for (uint32_t x = tid; x < (uint32_t)plan.components * 64u; x += DEC_IDCT_THREADS)
         s_q[x >> 6][DEC_ZIGZAG.at[x & 63u]] = file[plan.dqt_off[x >> 6] + (x & 63u)];
     __syncthreads();
-    const unsigned long long blk = (unsigned long long)blockIdx.x * DEC_IDCT_BLOCKS + sub;
+    const unsigned long long blk = (unsigned long long)group * DEC_IDCT_BLOCKS + sub;
     const bool live = blk < plan.expected_blocks;
     const uint32_t bpm = (uint32_t)plan.blocks_per_mcu, luma = plan.components == 3 ? (uint32_t)(plan.hs * plan.vs) : 1u;
     const uint32_t m = live ? (uint32_t)(blk / bpm) : 0u, b = live ? (uint32_t)(blk % bpm) : 0u;
@@ -454,10 +506,24 @@ __global__ void __launch_bounds__(DEC_IDCT_THREADS) k_jpeg_dec_idct(const uint8_
         const uint32_t my = m / (uint32_t)plan.mcus_x, mx = m - my * (uint32_t)plan.mcus_x;
         const uint32_t by = comp == 0 ? my * (uint32_t)plan.vs + b / (uint32_t)plan.hs : my;
         const uint32_t bx = comp == 0 ? mx * (uint32_t)plan.hs + b % (uint32_t)plan.hs : mx;
-        uint32_t* dst = reinterpret_cast<uint32_t*>(planes.p[comp] + ((size_t)by * 8 + lane) * (size_t)planes.pw[comp] + (size_t)bx * 8);
+        uint8_t* plane = comp == 0 ? planes.p[0] : (comp == 1 ? planes.p[1] : planes.p[2]);
+        const int pw = comp == 0 ? planes.pw[0] : (comp == 1 ? planes.pw[1] : planes.pw[2]);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(plane + ((size_t)by * 8 + lane) * (size_t)pw + (size_t)bx * 8);
         dst[0] = lo;                                            // (planes are 16-byte aligned, their widths multiples of 8)
         dst[1] = hi;
     }
+}
+
+__global__ void __launch_bounds__(DEC_IDCT_THREADS) k_jpeg_dec_idct(const uint8_t* file, Plan plan, const int16_t* coef, DecPlanes planes) {
+    dec_idct_body(file, plan, coef, planes, blockIdx.x);
+}
+
+// grid = (ceil(the batch's most blocks / 32), items): workgroups past the item's blocks return
+__global__ void __launch_bounds__(DEC_IDCT_THREADS) k_jpeg_dec_idct_batch(const uint8_t* files, const Item* __restrict__ items, uint8_t* workspace) {
+    const Item& it = items[blockIdx.y];
+    if ((unsigned long long)blockIdx.x * DEC_IDCT_BLOCKS >= it.plan.expected_blocks) return;
+    const DecItemArrays a = dec_item_arrays(it, files, workspace);
+    dec_idct_body(a.file, it.plan, a.coef, a.planes, blockIdx.x);
 }
 
 // a chroma sample at full size: libjpeg's fancy upsampling; a plane of width <= 2 is replicated
@@ -480,8 +546,7 @@ __device__ __forceinline__ int dec_chroma(const uint8_t* plane, int pw, const Pl
     return (x & 1) ? (3 * cs + 3 * near[i + 1] + far[i + 1] + 7) >> 4 : (3 * cs + 3 * near[i - 1] + far[i - 1] + 8) >> 4;
 }
 
-__global__ void __launch_bounds__(DEC_COLOUR_THREADS) k_jpeg_dec_colour(Plan plan, DecPlanes planes, int bgr, uint8_t* out) {
-    const int x = (int)(blockIdx.x * DEC_COLOUR_THREADS + threadIdx.x), y = (int)blockIdx.y;
+__device__ __forceinline__ void dec_colour_body(const Plan& plan, const DecPlanes planes, int bgr, uint8_t* out, int x, int y) {
     if (x >= plan.w || y >= plan.h) return;
     const int lum = planes.p[0][(size_t)y * planes.pw[0] + x];
     int r = lum, g = lum, b = lum;
@@ -498,6 +563,18 @@ __global__ void __launch_bounds__(DEC_COLOUR_THREADS) k_jpeg_dec_colour(Plan pla
     p[0] = (uint8_t)(bgr ? b : r);
     p[1] = (uint8_t)g;
     p[2] = (uint8_t)(bgr ? r : b);
+}
+
+__global__ void __launch_bounds__(DEC_COLOUR_THREADS) k_jpeg_dec_colour(Plan plan, DecPlanes planes, int bgr, uint8_t* out) {
+    dec_colour_body(plan, planes, bgr, out, (int)(blockIdx.x * DEC_COLOUR_THREADS + threadIdx.x), (int)blockIdx.y);
+}
+
+// grid = (ceil(the batch's largest w / 256), its largest h, items): rows and columns past the item's own return
+__global__ void __launch_bounds__(DEC_COLOUR_THREADS) k_jpeg_dec_colour_batch(const Item* __restrict__ items, uint8_t* workspace, int bgr, uint8_t* out) {
+    const Item& it = items[blockIdx.z];
+    if ((int)(blockIdx.x * DEC_COLOUR_THREADS) >= it.plan.w || (int)blockIdx.y >= it.plan.h) return;
+    const DecItemArrays a = dec_item_arrays(it, nullptr, workspace);
+    dec_colour_body(it.plan, a.planes, bgr, out + it.out_off, (int)(blockIdx.x * DEC_COLOUR_THREADS + threadIdx.x), (int)blockIdx.y);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the planner
@@ -661,4 +738,73 @@ extern "C" int frcnn_jpeg_decode_u8(const uint8_t* file_dev, const frcnn_jpeg_de
     k_jpeg_dec_idct<<<(p.expected_blocks + DEC_IDCT_BLOCKS - 1) / DEC_IDCT_BLOCKS, DEC_IDCT_THREADS, 0, s>>>(file_dev, p, coef, planes);
     k_jpeg_dec_colour<<<dim3((p.w + DEC_COLOUR_THREADS - 1) / DEC_COLOUR_THREADS, p.h), DEC_COLOUR_THREADS, 0, s>>>(p, planes, bgr ? 1 : 0, out);
     return check_launch("jpeg_decode_u8");
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the batched form
+extern "C" int frcnn_jpeg_dec_batch_version(void) { return FRCNN_JPEG_DEC_BATCH_VERSION; }
+
+extern "C" size_t frcnn_jpeg_dec_batch_layout(const frcnn_jpeg_dec_plan_t* plans, int n, uint64_t* ws_off) {
+    if (!plans || !ws_off || n < 1 || n > FRCNN_JPEG_DEC_BATCH_MAX) return 0;
+    for (int i = 0; i < n; ++i)
+        if (dec_plan_fault(plans[i])) return 0;
+    size_t at = 0;
+    for (int i = 0; i < n; ++i) { ws_off[i] = at; at += dec_layout(plans[i]).total; }
+    return at;
+}
+
+namespace {
+struct DecRange { unsigned long long lo, hi; int item; };
+
+// -1, or the index of an item of (sorted by lo) ``r`` that reaches into its successor
+inline int dec_overlap(DecRange* r, int n) {
+    for (int i = 1; i < n; ++i)                                // (insertion sort: n <= 64)
+        for (int j = i; j > 0 && r[j].lo < r[j - 1].lo; --j) { const DecRange t = r[j]; r[j] = r[j - 1]; r[j - 1] = t; }
+    for (int i = 0; i + 1 < n; ++i)
+        if (r[i].hi > r[i + 1].lo) return i;
+    return -1;
+}
+}  // namespace
+
+extern "C" int frcnn_jpeg_decode_batch_u8(const frcnn_jpeg_dec_batch_item_t* items_host, const frcnn_jpeg_dec_batch_item_t* items_dev, int n,
+                                          const uint8_t* files_dev, size_t files_capacity, int bgr, uint8_t* out_dev, size_t out_capacity,
+                                          int32_t* status_dev, void* workspace, size_t workspace_capacity, void* stream) {
+    if (!items_host || !items_dev || !files_dev || !out_dev || !status_dev || !workspace) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: null pointer");
+    if (n < 1 || n > FRCNN_JPEG_DEC_BATCH_MAX) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: n=%d outside 1..%d", n, FRCNN_JPEG_DEC_BATCH_MAX);
+    if (reinterpret_cast<uintptr_t>(workspace) & 15u) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(status_dev) & 3u) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: status_dev must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(items_dev) & 7u) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: items_dev must be 8-byte aligned");
+    DecRange outs[FRCNN_JPEG_DEC_BATCH_MAX], regions[FRCNN_JPEG_DEC_BATCH_MAX];
+    uint32_t lanes = 64, blocks = 1;
+    int max_w = 1, max_h = 1;
+    for (int i = 0; i < n; ++i) {
+        const Item& it = items_host[i];
+        const Plan& p = it.plan;
+        if (const char* what = dec_plan_fault(p)) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: item %d: the plan contradicts itself (%s)", i, what);
+        const unsigned long long frame = (unsigned long long)p.h * p.w * 3, need = dec_layout(p).total;
+        if (it.file_off > files_capacity || p.file_len > files_capacity - it.file_off)
+            return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: item %d: file_off=%llu + file_len=%u beyond files_capacity=%zu", i, (unsigned long long)it.file_off, p.file_len, files_capacity);
+        if (it.out_off > out_capacity || frame > out_capacity - it.out_off)
+            return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: item %d: out_off=%llu + %d * %d * 3 beyond out_capacity=%zu", i, (unsigned long long)it.out_off, p.h, p.w, out_capacity);
+        if (it.ws_off & 15u) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: item %d: ws_off=%llu must be 16-byte aligned", i, (unsigned long long)it.ws_off);
+        if (it.ws_off > workspace_capacity || need > workspace_capacity - it.ws_off)
+            return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: item %d: ws_off=%llu + %llu beyond workspace_capacity=%zu", i, (unsigned long long)it.ws_off, need, workspace_capacity);
+        outs[i] = {it.out_off, it.out_off + frame, i};
+        regions[i] = {it.ws_off, it.ws_off + need, i};
+        const uint32_t l = (p.subsequences + 63u) / 64u * 64u;
+        lanes = l > lanes ? l : lanes;
+        blocks = p.expected_blocks > blocks ? p.expected_blocks : blocks;
+        max_w = p.w > max_w ? p.w : max_w;
+        max_h = p.h > max_h ? p.h : max_h;
+    }
+    int k = dec_overlap(outs, n);
+    if (k >= 0) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: the output ranges of items %d and %d overlap", outs[k].item, outs[k + 1].item);
+    k = dec_overlap(regions, n);
+    if (k >= 0) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: the workspace regions of items %d and %d overlap", regions[k].item, regions[k + 1].item);
+    hipStream_t s = as_stream(stream);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    k_jpeg_dec_entropy_batch<<<n, lanes, 0, s>>>(files_dev, items_dev, ws, status_dev);
+    k_jpeg_dec_dc_batch<<<dim3(3, n), DEC_DC_THREADS, 0, s>>>(items_dev, ws);
+    k_jpeg_dec_idct_batch<<<dim3((blocks + DEC_IDCT_BLOCKS - 1) / DEC_IDCT_BLOCKS, n), DEC_IDCT_THREADS, 0, s>>>(files_dev, items_dev, ws);
+    k_jpeg_dec_colour_batch<<<dim3((max_w + DEC_COLOUR_THREADS - 1) / DEC_COLOUR_THREADS, max_h, n), DEC_COLOUR_THREADS, 0, s>>>(items_dev, ws, bgr ? 1 : 0, out_dev);
+    return check_launch("jpeg_decode_batch_u8");
 }

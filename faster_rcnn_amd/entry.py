@@ -28,13 +28,14 @@ models, the same call runs here as ONE captured pass per image:
   holds pointers to packed filters, so the cache is dropped and re-captured on the next call.
 """
 import collections
+import ctypes
 import os
 import time
 
 import numpy as np
 import torch
 
-from . import models, ops
+from . import _lib, models, ops
 from ._lib import FrcnnError
 from .pipeline import BatchedInferencePipeline, InferencePipeline, no_gc
 from .shapes import declares as _declares
@@ -89,8 +90,8 @@ WARMUP_PASSES = max(1, int(os.environ.get("FRCNN_ENTRY_WARMUP", "1")))
 # PLANS the classes from the list's size histogram (DetectionEntry.plan_canvases): few classes, each worth its captures.
 # file-backed frames go up in the decoder's channel order and are swapped to BGR by the device resize (0: reverse on the host as before)
 RGB_UPLOAD = os.environ.get("FRCNN_ENTRY_RGB_UPLOAD", "1") != "0"
-# who decodes a file-backed frame: "host" (PIL, the default) or "device" (ops.jpeg_decode_u8 in front of the replay, for the files its
-# planner supports and for per-geometry passes; PIL for the rest and for canvas passes).  FRCNN_ENTRY_JPEG_DECODER, or
+# who decodes a file-backed frame: "host" (PIL, the default) or "device" (ops.jpeg_decode_batch_u8 in front of the replay, for the files
+# its planner supports, in per-geometry and canvas passes alike; PIL for the rest).  FRCNN_ENTRY_JPEG_DECODER, or
 # ``set_jpeg_decoder`` (voc_dets / annotate_video --jpeg_decoder), which wins.
 _JPEG_DECODER = None
 
@@ -100,6 +101,15 @@ def set_jpeg_decoder(value):
     global _JPEG_DECODER
     from .feed import jpeg_decoder_option
     _JPEG_DECODER = None if value is None else jpeg_decoder_option(value, "jpeg_decoder")
+
+
+def jpeg_batch():
+    """FRCNN_ENTRY_JPEG_BATCH (read at every call: a test or a benchmark may set it): "1", the default, decodes all files of a pass in
+    one ops.jpeg_decode_batch_u8; "0" keeps one ops.jpeg_decode_u8 (and one upload) per file, so that the two can be measured."""
+    value = os.environ.get("FRCNN_ENTRY_JPEG_BATCH") or "1"
+    if value not in ("0", "1"):
+        raise ValueError("FRCNN_ENTRY_JPEG_BATCH=%r: 0 or 1" % value)
+    return value == "1"
 
 
 def jpeg_decoder():
@@ -248,7 +258,7 @@ class _Slot:
     __slots__ = ("key", "pipe", "graph", "out", "io_dev", "io_pin", "dyn_host", "out_pin", "event", "busy", "nbytes", "x_f32", "ws", "tabs", "u8_resized",
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy",
-                 "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names")
+                 "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used")
 
     def __init__(self):
         for name in self.__slots__:
@@ -615,7 +625,7 @@ class DetectionEntry:
         Returns (array, H, W, src or None, flip)."""
         if self.device_preprocess and _declares(image, "raw") and _declares(image, "height"):
             H, W, flip = int(image.height), int(image.width), bool(getattr(image, "flipped", False))
-            if RGB_UPLOAD and not self.canvas and jpeg_decoder() == "device":
+            if RGB_UPLOAD and jpeg_decoder() == "device":
                 from . import feed
                 planned = feed.plan_file(image)               # None: in-memory pixels, or a file the device decoder does not take
                 if planned is not None:
@@ -688,10 +698,11 @@ class DetectionEntry:
     def canvas_ok(self, pixels):
         """Can this frame go through a canvas pass?  (device preprocess, a source no larger than its canvas)"""
         arr, H, W, src, flip = pixels
-        if not (self.canvas_capable and getattr(arr, "dtype", None) == np.uint8):
+        if not (self.canvas_capable and (isinstance(arr, JpegFile) or getattr(arr, "dtype", None) == np.uint8)):
             return False
         Hc, Wc = self.canvas_class(H, W)
-        return int(np.prod(arr.shape)) <= Hc * Wc * 3
+        size = arr.plan.h * arr.plan.w * 3 if isinstance(arr, JpegFile) else int(np.prod(arr.shape))
+        return size <= Hc * Wc * 3
 
     @staticmethod
     def geometry_of(pixels):
@@ -800,11 +811,11 @@ class DetectionEntry:
         for i in range(B):
             j = i if i < len(images) else 0
             s.dyn_host[i, 0], s.dyn_host[i, 1] = float(resize_ratios[j]), float(det_threshold)
+            if isinstance(pixels[j][0], JpegFile):
+                files.append((i, pixels[j][0]))
             if s.canvas:
                 metas.append(self._canvas_frame(s, i, pixels[j]))
-            elif isinstance(pixels[j][0], JpegFile):
-                files.append((i, pixels[j][0]))
-            else:
+            elif not isinstance(pixels[j][0], JpegFile):
                 np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
         st = self._streams[self._seq % self.in_flight]
         self._seq += 1
@@ -817,10 +828,10 @@ class DetectionEntry:
             else:
                 s.jpg_names = None
             s.io_dev.copy_(s.io_pin, non_blocking=True)
+            if files:
+                self._decode_files(s, files)                        # each file's frame into its source segment, behind the io copy
             if s.canvas:
                 self._canvas_preprocess(s, metas)
-            if files:
-                self._decode_files(s, files, src)                   # each file's frame into its source segment, behind the io copy
             s.graph.replay()
             if files:
                 s.jpg_status_pin.copy_(s.jpg_status, non_blocking=True)
@@ -837,46 +848,81 @@ class DetectionEntry:
         return Ticket(s, list(images))
 
     def _stage_files(self, s, files):
-        """Host side of a pass whose frames the device decodes: the files' bytes into the slot's pinned file area (grow-only; the slot is
-        idle, so nothing reads the old one), room for them and for the decoder's workspace on the device."""
+        """Host side of a pass whose frames the device decodes: [item table | the files' bytes back to back] into the slot's one pinned
+        area (grow-only; the slot is idle, so nothing reads the old one), room for them and for the decoder's workspace on the device.
+        ``files``: (frame index, JpegFile) of the pass's file-backed frames; item k is files[k], its output frame i's source segment.  A
+        file that fills several frames (the padding of a short group) is staged once."""
         B = s.batch
-        cap = (max(len(f.data) for _, f in files) + 255) // 256 * 256
-        if s.jpg_pin is None or s.jpg_pin.shape[1] < cap:
-            s.jpg_pin = torch.empty((B, cap + cap // 4), dtype=torch.uint8).pin_memory()
-            s.jpg_dev = torch.empty((B, cap + cap // 4), dtype=torch.uint8, device="cuda")
-        need = max(ops.jpeg_dec_workspace_bytes(f.plan) for _, f in files)
+        item = ctypes.sizeof(_lib.JpegDecBatchItem)
+        table = (B * item + 255) // 256 * 256
+        at, seen, file_off = 0, {}, []
+        for _, f in files:
+            if id(f) not in seen:
+                seen[id(f)] = at
+                at += len(f.data)
+            file_off.append(seen[id(f)])
+        if s.jpg_pin is None or s.jpg_pin.numel() < table + at:
+            size = table + (at + at // 4 + 255) // 256 * 256
+            s.jpg_pin = torch.empty(size, dtype=torch.uint8).pin_memory()
+            s.jpg_area = torch.empty(size, dtype=torch.uint8, device="cuda")
+            s.jpg_dev = s.jpg_area[table:]                           # the file area; the table lies in front of it
+        plans = [f.plan for _, f in files]
+        ws_off, need = [], 0
+        for k in range(0, len(plans), _lib.JPEG_DEC_BATCH_MAX):      # (a call takes JPEG_DEC_BATCH_MAX items: its regions behind the last call's)
+            offs, total = ops.jpeg_dec_batch_layout(plans[k:k + _lib.JPEG_DEC_BATCH_MAX])
+            ws_off += [need + o for o in offs]
+            need += total
         if s.jpg_ws is None or s.jpg_ws.numel() < need:
             s.jpg_ws = torch.empty(need + need // 4, dtype=torch.uint8, device="cuda")
         if s.jpg_status is None:
             s.jpg_status = torch.zeros(B, dtype=torch.int32, device="cuda")
             s.jpg_status_pin = torch.zeros(B, dtype=torch.int32).pin_memory()
-        s.jpg_names = [None] * B
-        for i, f in files:
-            s.jpg_pin[i, :len(f.data)].numpy()[:] = np.frombuffer(f.data, dtype=np.uint8)
-            s.jpg_names[i] = f.name
+        s.jpg_items = ops.jpeg_batch_items(plans, file_off, [i * s.seg for i, _ in files], ws_off)
+        s.jpg_used = table + at
+        s.jpg_names = [f.name for _, f in files]                    # (item k's status word is word k)
+        host = s.jpg_pin.numpy()
+        host[:len(files) * item] = np.frombuffer(s.jpg_items, dtype=np.uint8)
+        for f in {id(f): f for _, f in files}.values():
+            host[table + seen[id(f)]:table + seen[id(f)] + len(f.data)] = np.frombuffer(f.data, dtype=np.uint8)
 
-    def _decode_files(self, s, files, src):
-        """Device side, on the pass's stream between the io copy and the replay: upload, clear the status words, decode every file into
-        its frame's source segment (R,G,B as PIL delivers it: the pass's resize swaps, flip bit 1)."""
-        in_h, in_w = src
+    def _decode_files(self, s, files):
+        """Device side, on the pass's stream between the io copy and the canvas preprocess / the replay: one upload of the staged area,
+        the status words cleared, one batched decode of every file into its frame's source segment (R,G,B as PIL delivers it: the pass's
+        resize swaps, flip bit 1).  FRCNN_ENTRY_JPEG_BATCH=0: an upload and a single-file decode per file instead."""
+        item, table = ctypes.sizeof(_lib.JpegDecBatchItem), s.jpg_area.numel() - s.jpg_dev.numel()
+        if jpeg_batch():
+            s.jpg_area[:s.jpg_used].copy_(s.jpg_pin[:s.jpg_used], non_blocking=True)
+            s.jpg_status.zero_()
+            for k in range(0, len(files), _lib.JPEG_DEC_BATCH_MAX):
+                n = min(_lib.JPEG_DEC_BATCH_MAX, len(files) - k)
+                part = (_lib.JpegDecBatchItem * n).from_buffer(s.jpg_items, k * item)
+                ops.jpeg_decode_batch_u8(s.jpg_dev, part, s.io_dev, status=s.jpg_status[k:k + n], workspace=s.jpg_ws,
+                                         items_dev=s.jpg_area[k * item:(k + n) * item])
+            return
         s.jpg_status.zero_()
-        for i, f in files:
-            n = len(f.data)
-            s.jpg_dev[i, :n].copy_(s.jpg_pin[i, :n], non_blocking=True)
-            out = s.io_dev[i * s.seg:i * s.seg + in_h * in_w * 3].view(in_h, in_w, 3)
-            ops.jpeg_decode_u8(s.jpg_dev[i, :n], f.plan, out=out, status=s.jpg_status[i:i + 1], workspace=s.jpg_ws)
+        for k, (i, f) in enumerate(files):
+            it = s.jpg_items[k]
+            lo, n, frame = table + int(it.file_off), len(f.data), int(f.plan.h) * int(f.plan.w) * 3
+            s.jpg_area[lo:lo + n].copy_(s.jpg_pin[lo:lo + n], non_blocking=True)
+            out = s.io_dev[i * s.seg:i * s.seg + frame].view(int(f.plan.h), int(f.plan.w), 3)
+            ops.jpeg_decode_u8(s.jpg_area[lo:lo + n], f.plan, out=out, status=s.jpg_status[k:k + 1], workspace=s.jpg_ws)
 
     def _canvas_frame(self, s, i, pixels):
         """Frame i of a canvas pass, host side: the frame goes into its staging segment at ITS size, its true size into the extents.
         -> what _canvas_preprocess needs to know about it."""
         arr, H, W, src, flip = pixels
-        arr = np.ascontiguousarray(arr)
         oy, ox = s.extents.offset_of(H, W)                          # ResNet: (H & 1, W & 1); VGG16: (0, 0)
         _, Hc, Wc = s.key
-        assert arr.dtype == np.uint8 and arr.nbytes <= s.seg and H + oy <= Hc and W + ox <= Wc, "one pass, one canvas class"
-        s.pix_hosts[i][:arr.nbytes] = arr.reshape(-1)
+        if isinstance(arr, JpegFile):                               # the device decodes it into the segment (_decode_files): only its size here
+            in_h, in_w = int(arr.plan.h), int(arr.plan.w)
+            assert in_h * in_w * 3 <= s.seg and H + oy <= Hc and W + ox <= Wc, "one pass, one canvas class"
+        else:
+            arr = np.ascontiguousarray(arr)
+            in_h, in_w = arr.shape[0], arr.shape[1]
+            assert arr.dtype == np.uint8 and arr.nbytes <= s.seg and H + oy <= Hc and W + ox <= Wc, "one pass, one canvas class"
+            s.pix_hosts[i][:arr.nbytes] = arr.reshape(-1)
         s.extents.set(i, H, W)
-        return arr.shape[0], arr.shape[1], H, W, src, flip, (oy, ox)
+        return in_h, in_w, H, W, src, flip, (oy, ox)
 
     def _canvas_preprocess(self, s, metas):
         """The eager launches in front of a canvas pass's replay, on its stream: the true sizes go up as extents, every frame is resized

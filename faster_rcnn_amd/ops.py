@@ -1259,6 +1259,57 @@ def jpeg_decode_u8(file, plan=None, bgr=False, out=None, status=None, workspace=
     return out, status
 
 
+def jpeg_dec_batch_layout(plans):
+    """Workspace regions for a batch of plans laid back to back (frcnn_jpeg_dec_batch_layout) -> (ws_off, total): the byte offset of
+    every plan's region (16-byte aligned, each ``jpeg_dec_workspace_bytes(plan)`` long) and the bytes of workspace the batch needs.  A
+    pure host call."""
+    n = len(plans)
+    if not 1 <= n <= _lib.JPEG_DEC_BATCH_MAX:
+        raise _lib.FrcnnError(f"jpeg_dec_batch_layout: {n} plans, 1..{_lib.JPEG_DEC_BATCH_MAX} go into one batch")
+    arr = (_lib.JpegDecPlan * n)(*plans)
+    offs = (ctypes.c_uint64 * n)()
+    total = int(_lib.load().frcnn_jpeg_dec_batch_layout(arr, n, offs))
+    if total == 0:
+        raise _lib.FrcnnError("jpeg_dec_batch_layout: not plans that jpeg_dec_plan made")
+    return [int(o) for o in offs], total
+
+
+def jpeg_batch_items(plans, file_off, out_off, ws_off):
+    """The item table of a batch (``_lib.JpegDecBatchItem`` x n, a ctypes array: ``bytes(table)`` is what goes to the device)."""
+    items = (_lib.JpegDecBatchItem * len(plans))()
+    for it, p, f, o, w in zip(items, plans, file_off, out_off, ws_off):
+        it.plan, it.file_off, it.out_off, it.ws_off = p, int(f), int(o), int(w)
+    return items
+
+
+def jpeg_decode_batch_u8(files, items, out, bgr=False, status=None, workspace=None, items_dev=None):
+    """Decode the baseline .jpg files of a batch on the device in ONE set of four launches (frcnn_jpeg_decode_batch_u8): ``files`` a 1-d
+    uint8 device tensor that holds every file's bytes, ``items`` the table (``jpeg_batch_items``: per file its plan, where its bytes lie
+    in ``files``, where its (h, w, 3) frame goes in ``out`` and where its region lies in ``workspace``), ``out`` a 1-d uint8 device
+    tensor -> status: int32 [n], per file 0 or _lib.JPEG_DEC_* bits ORed in (sticky: a tensor passed in is not cleared).  ``items_dev``:
+    a device tensor that already holds ``bytes(items)`` (uploaded by the caller on the current stream); None: uploaded here, a pageable
+    copy, which blocks the host.  ``status`` and ``workspace`` are allocated when not passed.  Never synchronises otherwise."""
+    _require_gpu()
+    n = len(items)
+    if not isinstance(items, ctypes.Array) or items._type_ is not _lib.JpegDecBatchItem:
+        raise _lib.FrcnnError("jpeg_decode_batch_u8: items must be a table made by jpeg_batch_items")
+    if items_dev is None:
+        items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).cuda()
+    if status is None:
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
+    if workspace is None:
+        workspace = _ws(max((int(it.ws_off) + jpeg_dec_workspace_bytes(it.plan) for it in items), default=0))
+    for name, t, dt in (("files", files, torch.uint8), ("out", out, torch.uint8), ("status", status, torch.int32),
+                        ("workspace", workspace, torch.uint8), ("items_dev", items_dev, torch.uint8)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise _lib.FrcnnError(f"jpeg_decode_batch_u8: {name} must be a contiguous {dt} device tensor")
+    if items_dev.numel() < ctypes.sizeof(items) or status.numel() < n:
+        raise _lib.FrcnnError(f"jpeg_decode_batch_u8: items_dev of {items_dev.numel()} bytes / status of {status.numel()} words for {n} items")
+    _lib.call("frcnn_jpeg_decode_batch_u8", ctypes.addressof(items), _p(items_dev), n, _p(files), files.numel(), 1 if bgr else 0,
+              _p(out), out.numel(), _p(status), _p(workspace), workspace.numel(), _stream())
+    return status
+
+
 def split_detections(packed, rows=None):
     """Views (n_dets, det_bbox, det_cls, det_prob, det_roi) into a `det_packed` buffer (device tensor or its host copy)."""
     rows = (packed.numel() - 4) // 7 if rows is None else rows

@@ -284,8 +284,8 @@ def build_parser():
     p.add_argument("--out_dir", dest="out_dir", default=".")
     p.add_argument("--det_threshold", dest="det_threshold", default=DEFAULT_DET_THRESHOLD)
     p.add_argument("--jpeg_decoder", dest="jpeg_decoder", choices=("host", "device"), default=None,
-                   help="who decodes the images' JPEG files: host (PIL) or device (csrc/jpeg_dec.hip, for baseline files and per-geometry "
-                        "passes; PIL for the rest); default: FRCNN_ENTRY_JPEG_DECODER, else host")
+                   help="who decodes the images' JPEG files: host (PIL) or device (csrc/jpeg_dec.hip, for baseline files, in per-geometry "
+                        "and canvas passes; PIL for the rest); default: FRCNN_ENTRY_JPEG_DECODER, else host")
     p.add_argument("--dtype", dest="dtype", choices=("f32", "bf16"), default="f32",
                    help="precision the networks are served in: bf16 = the bf16 conv path on the matrix cores (the reference has no such flag: it runs fp32 only)")
     return p
