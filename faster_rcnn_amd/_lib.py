@@ -186,6 +186,24 @@ JPEG_SIGNATURES = {
     "frcnn_jpeg_encode_u8": (I, [P, I, I, I, I, P, c_size_t, P, P, P]),
 }
 
+JPEG_OPT_VERSION = 1    # include/ext/frcnn_hip_jpeg_opt.h FRCNN_JPEG_OPT_VERSION
+JPEG_OPT_SIGNATURES = {
+    "frcnn_jpeg_opt_version": (I, []),
+    "frcnn_jpeg_opt_restart_mcus": (I, [I]),
+    "frcnn_jpeg_opt_bound": (c_size_t, [I, I, I]),
+    "frcnn_jpeg_opt_workspace_bytes": (c_size_t, [I, I, I, I]),
+    "frcnn_jpeg_opt_encode_u8": (I, [P, I, I, I, I, I, I, P, c_size_t, P, P, P]),
+    "frcnn_jpeg_opt_build_tables": (I, [P, P, P]),
+}
+JPEG_OPT_SUBSAMPLINGS = (444, 420)                              # FRCNN_JPEG_OPT_444 / _420
+JPEG_OPT_HUFFMANS = {"standard": 0, "optimized": 1}             # FRCNN_JPEG_OPT_STANDARD / _OPTIMIZED
+
+
+class JpegOptTable(ctypes.Structure):
+    """frcnn_jpeg_opt_table_t (include/ext/frcnn_hip_jpeg_opt.h)."""
+    _fields_ = [("bits", ctypes.c_uint8 * 16), ("huffval", ctypes.c_uint8 * 256), ("count", ctypes.c_uint32)]
+
+
 JPEG_DEC_VERSION = 1    # include/ext/frcnn_hip_jpeg_dec.h FRCNN_JPEG_DEC_VERSION
 JPEG_DEC_SIGNATURES = {
     "frcnn_jpeg_dec_version": (I, []),
@@ -291,6 +309,10 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in JPEG_OPT_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
     for name, (res, args) in JPEG_DEC_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -305,6 +327,9 @@ def load():
     if lib.frcnn_jpeg_dec_version() != JPEG_DEC_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_dec_version()} of the JPEG decoder extension, this binding "
                          f"{JPEG_DEC_VERSION} (include/ext/frcnn_hip_jpeg_dec.h): rebuild with `python -m faster_rcnn_amd.build`")
+    if lib.frcnn_jpeg_opt_version() != JPEG_OPT_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_opt_version()} of the JPEG encoder's 4:2:0 / optimised-table extension, "
+                         f"this binding {JPEG_OPT_VERSION} (include/ext/frcnn_hip_jpeg_opt.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_jpeg_version() != JPEG_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_version()} of the JPEG encoder extension, this binding "
                          f"{JPEG_VERSION} (include/ext/frcnn_hip_jpeg.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -31,6 +31,11 @@ are 3 pixels wide).  ``jpeg_encoder="host"`` (the default; FRCNN_ANNOTATE_JPEG_E
 ``jpeg_encoder="device"`` encodes inside the pass (ops.jpeg_encode_u8, csrc/jpeg.hip): the file comes back instead of the raw frame.  Both
 use the Annex K tables at the same IJG quality; their bytes differ in the rounding of colour transform and DCT.  The JPEG
 options with ``png`` frames, and the device PNG options with ``jpg`` frames, raise ValueError.  The default stays "png".
+
+``jpeg_subsampling=420`` (``--jpeg_subsampling 420``, FRCNN_ANNOTATE_JPEG_SUBSAMPLING) halves the chroma planes both ways and
+``jpeg_huffman="optimized"`` (``--jpeg_huffman optimized``, FRCNN_ANNOTATE_JPEG_HUFFMAN) writes Huffman tables built from each frame's own
+symbol counts: the two options every JPEG writer has, honoured by both encoders (PIL: ``subsampling=2``, ``optimize=True``; device:
+csrc/jpeg_opt.hip).  Both need ``jpg`` frames; the defaults stay 444 / "standard" (sizes: DESIGN §8).
 """
 import os
 import pathlib
@@ -52,6 +57,8 @@ PNG_COMPRESS = ("runs", "huffman")                # modes of the device encoder 
 FRAME_FORMATS = ("png", "jpg")
 JPEG_ENCODERS = ("host", "device")
 JPEG_QUALITY = 90
+JPEG_SUBSAMPLINGS = (444, 420)
+JPEG_HUFFMANS = ("standard", "optimized")
 
 
 def default_png_encoder():
@@ -98,6 +105,39 @@ def default_jpeg_encoder():
     if enc not in JPEG_ENCODERS:
         raise ValueError("FRCNN_ANNOTATE_JPEG_ENCODER=%r: one of %s" % (enc, ", ".join(JPEG_ENCODERS)))
     return enc
+
+
+def default_jpeg_subsampling():
+    """FRCNN_ANNOTATE_JPEG_SUBSAMPLING (444 or 420), else 444."""
+    value = os.environ.get("FRCNN_ANNOTATE_JPEG_SUBSAMPLING", "444")
+    if value not in [str(s) for s in JPEG_SUBSAMPLINGS]:
+        raise ValueError("FRCNN_ANNOTATE_JPEG_SUBSAMPLING=%r: one of %s" % (value, ", ".join(str(s) for s in JPEG_SUBSAMPLINGS)))
+    return int(value)
+
+
+def default_jpeg_huffman():
+    """FRCNN_ANNOTATE_JPEG_HUFFMAN, else "standard" (the tables of Annex K.3)."""
+    value = os.environ.get("FRCNN_ANNOTATE_JPEG_HUFFMAN", "standard")
+    if value not in JPEG_HUFFMANS:
+        raise ValueError("FRCNN_ANNOTATE_JPEG_HUFFMAN=%r: one of %s" % (value, ", ".join(JPEG_HUFFMANS)))
+    return value
+
+
+def jpeg_size_options(frame_format, jpeg_subsampling=None, jpeg_huffman=None):
+    """-> (jpeg_subsampling, jpeg_huffman) with None replaced by the defaults.  ``frame_format``: what ``jpeg_options`` returned.
+    ValueError for an unknown value, and for 420 or "optimized" with "png" frames: both are settings of JPEG frames, of either encoder."""
+    jpeg_subsampling = default_jpeg_subsampling() if jpeg_subsampling is None else jpeg_subsampling
+    jpeg_huffman = default_jpeg_huffman() if jpeg_huffman is None else jpeg_huffman
+    if isinstance(jpeg_subsampling, bool) or jpeg_subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError("jpeg_subsampling=%r: one of %s" % (jpeg_subsampling, ", ".join(str(s) for s in JPEG_SUBSAMPLINGS)))
+    if not isinstance(jpeg_huffman, str) or jpeg_huffman not in JPEG_HUFFMANS:
+        raise ValueError("jpeg_huffman=%r: one of %s" % (jpeg_huffman, ", ".join(JPEG_HUFFMANS)))
+    if frame_format != "jpg":
+        if jpeg_subsampling != 444:
+            raise ValueError("jpeg_subsampling=%r is a setting of JPEG frames: it needs frame_format=\"jpg\" (--frame_format jpg)" % (jpeg_subsampling,))
+        if jpeg_huffman != "standard":
+            raise ValueError("jpeg_huffman=%r is a setting of JPEG frames: it needs frame_format=\"jpg\" (--frame_format jpg)" % (jpeg_huffman,))
+    return int(jpeg_subsampling), jpeg_huffman
 
 
 def jpeg_options(frame_format=None, jpeg_encoder=None, jpeg_quality=None, png_encoder="host", png_compress="runs"):
@@ -209,9 +249,10 @@ def _write_png(path, rgb):
     PilImage.fromarray(rgb).save(path, compress_level=PNG_COMPRESS_LEVEL)
 
 
-def _write_jpg(path, rgb, quality):
+def _write_jpg(path, rgb, quality, subsampling=444, huffman="standard"):
     from PIL import Image as PilImage
-    PilImage.fromarray(rgb).save(path, format="JPEG", quality=quality, subsampling=0)
+    PilImage.fromarray(rgb).save(path, format="JPEG", quality=quality, subsampling=2 if subsampling == 420 else 0,
+                                 optimize=huffman == "optimized")
 
 
 def _write_bytes(path, data):
@@ -285,12 +326,15 @@ class _Frame:
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
-                    png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None):
+                    png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
+                    jpeg_huffman=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
     ``frame_format``: "png" or "jpg" (each output keeps its stem and gets the extension .jpg); None = ``default_frame_format()``.
     ``jpeg_encoder``: "host" or "device", as ``png_encoder``; ``jpeg_quality``: 1..100, None = JPEG_QUALITY.
+    ``jpeg_subsampling``: 444 or 420, ``jpeg_huffman``: "standard" or "optimized" -- of JPEG frames, whichever encoder writes them;
+    None = ``default_jpeg_subsampling()`` / ``default_jpeg_huffman()``.
     ``jpeg_decoder``: "host" or "device": who decodes ``.jpg`` INPUT frames the device decoder supports (captured path only); None =
     what ``entry.jpeg_decoder()`` says (FRCNN_ENTRY_JPEG_DECODER, default "host")."""
     from concurrent.futures import ThreadPoolExecutor
@@ -299,14 +343,17 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     device_decode = entry.jpeg_decoder() == "device"
     png_encoder, png_compress = png_options(png_encoder, png_compress)
     frame_format, jpeg_encoder, jpeg_quality = jpeg_options(frame_format, jpeg_encoder, jpeg_quality, png_encoder, png_compress)
+    jpeg_subsampling, jpeg_huffman = jpeg_size_options(frame_format, jpeg_subsampling, jpeg_huffman)
     jpg = frame_format == "jpg"
     on_device = (jpeg_encoder if jpg else png_encoder) == "device"
     if jpg:
         encode, quality = ("jpeg", jpeg_quality) if on_device else (None, None)
+        jpeg_mode = dict(subsampling=jpeg_subsampling, huffman=jpeg_huffman) if on_device else {}
         out_names = [os.path.splitext(f)[0] + ".jpg" for f in image_filenames]
-        write_host = lambda path, rgb: _write_jpg(path, rgb, jpeg_quality)
+        write_host = lambda path, rgb: _write_jpg(path, rgb, jpeg_quality, jpeg_subsampling, jpeg_huffman)
     else:
         encode, quality = ("png" if png_compress == "runs" else "png-" + png_compress) if on_device else None, None
+        jpeg_mode = {}
         out_names = list(image_filenames)
         write_host = _write_png
     paths = [os.path.join(input_dir, f) for f in image_filenames]
@@ -322,7 +369,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             if on_device:
                 import torch
                 dev = torch.from_numpy(out).cuda()
-                _write_bytes(os.path.join(out_dir, name), ops.jpeg_bytes(dev, quality=jpeg_quality, bgr=True) if jpg else
+                _write_bytes(os.path.join(out_dir, name), ops.jpeg_bytes(dev, quality=jpeg_quality, bgr=True, subsampling=jpeg_subsampling,
+                                                                                huffman=jpeg_huffman) if jpg else
                              ops.png_bytes(dev, bgr=True, compress=png_compress))
             else:
                 write_host(os.path.join(out_dir, name), out[:, :, ::-1])
@@ -369,7 +417,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
         for part, take in parts:
             ticket = eng.submit_batch([g[2] for g in part], [g[3] for g in part], DET_THRESHOLD, [g[4] for g in part],
-                                      batch=take, annotate=True, encode=encode, quality=quality)
+                                      batch=take, annotate=True, encode=encode, quality=quality, **jpeg_mode)
             window.append(([(g[0], g[1]) for g in part], ticket))
             if len(window) >= eng.in_flight:
                 finish()
@@ -436,6 +484,12 @@ def build_parser():
                         "taken beside its *.png); default: FRCNN_ENTRY_JPEG_DECODER, else host")
     p.add_argument("--jpeg_quality", dest="jpeg_quality", type=int, default=None,
                    help="IJG quality of JPEG frames, 1..100 (default %d; needs --frame_format jpg)" % JPEG_QUALITY)
+    p.add_argument("--jpeg_subsampling", dest="jpeg_subsampling", type=int, choices=JPEG_SUBSAMPLINGS, default=default_jpeg_subsampling(),
+                   help="chroma of JPEG frames: 444 = full resolution, 420 = halved both ways, with either encoder "
+                        "(FRCNN_ANNOTATE_JPEG_SUBSAMPLING sets the default; needs --frame_format jpg)")
+    p.add_argument("--jpeg_huffman", dest="jpeg_huffman", choices=JPEG_HUFFMANS, default=default_jpeg_huffman(),
+                   help="Huffman tables of JPEG frames: standard = Annex K.3, optimized = built from each frame's symbol counts, smaller "
+                        "files, with either encoder (FRCNN_ANNOTATE_JPEG_HUFFMAN sets the default; needs --frame_format jpg)")
     return p
 
 
@@ -447,7 +501,9 @@ def main(argv=None):
     from .det_util import DetTrainingManager
     from .util import get_anchors
     args = build_parser().parse_args(argv)
-    jpeg_options(args.frame_format, args.jpeg_encoder, args.jpeg_quality, *png_options(args.png_encoder, args.png_compress))     # (before any model is loaded)
+    frame_format = jpeg_options(args.frame_format, args.jpeg_encoder, args.jpeg_quality,
+                                *png_options(args.png_encoder, args.png_compress))[0]                     # (before any model is loaded)
+    jpeg_size_options(frame_format, args.jpeg_subsampling, args.jpeg_huffman)
     os.environ.setdefault("GPU_MAX_HW_QUEUES", voc_dets.ENTRY_HW_QUEUES)      # (as voc_dets.main: passes in flight want > 4 queues)
     class_mapping = KITTI_CLASS_MAPPING if args.kitti else VOC_CLASS_MAPPING
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
@@ -466,7 +522,8 @@ def main(argv=None):
                     image_filenames=frame_filenames(args.input_dir, args.jpeg_decoder or entry.jpeg_decoder()), resize_min=resize_min,
                     resize_max=resize_max, jpeg_decoder=args.jpeg_decoder,
                     png_encoder=args.png_encoder, png_compress=args.png_compress, frame_format=args.frame_format,
-                    jpeg_encoder=args.jpeg_encoder, jpeg_quality=args.jpeg_quality)
+                    jpeg_encoder=args.jpeg_encoder, jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling,
+                    jpeg_huffman=args.jpeg_huffman)
 
 
 if __name__ == "__main__":

@@ -45,6 +45,7 @@ MEAN_BGR = (103.939, 116.779, 123.68)           # resnet.preprocess / vgg.prepro
 PNG_ENCODES = {"png": "runs", "png-huffman": "huffman"}
 # submit_batch(encode="jpeg", quality=q): the device JPEG encoder (ops.jpeg_encode_u8) at the end of an annotating pass
 JPEG_ENCODE = "jpeg"
+JPEG_MODE = (444, "standard")          # ... its default (subsampling, huffman): frcnn_jpeg_encode_u8; any other pair: frcnn_jpeg_opt_encode_u8
 PRE_NMS_TOP_N, MAX_PROPOSALS = 8000, 300        # det_util.py:151-156
 
 
@@ -257,7 +258,7 @@ class _Slot:
     are read back with every replay)."""
     __slots__ = ("key", "pipe", "graph", "out", "io_dev", "io_pin", "dyn_host", "out_pin", "event", "busy", "nbytes", "x_f32", "ws", "tabs", "u8_resized",
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
-                 "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy",
+                 "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used")
 
     def __init__(self):
@@ -450,7 +451,8 @@ class DetectionEntry:
         uploaded pixels are already (H, W).  An annotating pass then draws each frame's detections into its uploaded source frame
         (ops.annotate_u8, annotate_video.py); with ``s.encode`` == "png" or "png-huffman" it then encodes the drawn frame as a PNG file on
         the device (ops.png_encode_u8, compress "runs" or "huffman") into the slot's own buffer, which is what such a pass reads back
-        instead of the raw frame; with ``s.encode`` == "jpeg" as a JPEG file at ``s.quality`` (ops.jpeg_encode_u8)."""
+        instead of the raw frame; with ``s.encode`` == "jpeg" as a JPEG file at ``s.quality`` in ``s.jpeg_mode`` = (subsampling, huffman)
+        (ops.jpeg_encode_u8)."""
         B, pipe, annotate = s.batch, s.pipe, s.annotate
         in_h, in_w = src if src is not None else (H, W)
         npix = in_h * in_w * 3
@@ -476,10 +478,11 @@ class DetectionEntry:
             # (every block at its longest), which is device memory only: a replay reads back the row's first ``first_copy`` bytes -- the
             # length, the header and a quarter of the raw frame's size, more than a photograph takes at quality 90 -- and collect_batch
             # fetches the rest of a longer file.
-            s.png_bound = ops.jpeg_bound(in_h, in_w)
+            subsampling, huffman = s.jpeg_mode
+            s.png_bound = ops.jpeg_bound(in_h, in_w, subsampling, huffman)
             s.png_dev = torch.zeros((B, 16 + (s.png_bound + 15) // 16 * 16), dtype=torch.uint8, device="cuda")
             s.first_copy = min(16 + ops.jpeg_header_bytes() + npix // 4, 16 + s.png_bound)
-            s.png_ws = torch.empty(ops.jpeg_workspace_bytes(in_h, in_w), dtype=torch.uint8, device="cuda")
+            s.png_ws = torch.empty(ops.jpeg_workspace_bytes(in_h, in_w, subsampling, huffman), dtype=torch.uint8, device="cuda")
             png_out = [(s.png_dev[i][16:16 + s.png_bound], s.png_dev[i][0:4].view(torch.int32)) for i in range(B)]
             uploaded_rgb = src is not None and bool(int(flip) & 2)
         elif s.encode:
@@ -507,7 +510,7 @@ class DetectionEntry:
                     ops.annotate_u8(u8[i], packed[i] if B > 1 else packed, tables)
                     if s.encode == JPEG_ENCODE:
                         ops.jpeg_encode_u8(u8[i], quality=s.quality, bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1],
-                                           workspace=s.png_ws)
+                                           workspace=s.png_ws, subsampling=subsampling, huffman=huffman)
                     elif s.encode:
                         ops.png_encode_u8(u8[i], bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1], workspace=s.png_ws,
                                               compress=compress)
@@ -531,11 +534,11 @@ class DetectionEntry:
         s.extents.upload()
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
-    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None):
+    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None, jpeg_mode=JPEG_MODE):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
         (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
-        ends in the device JPEG encoder at ``quality``."""
+        ends in the device JPEG encoder at ``quality`` in ``jpeg_mode`` = (subsampling, huffman)."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -552,7 +555,7 @@ class DetectionEntry:
             stamp("pipeline")
             s = _Slot()
             s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
-            s.encode, s.quality = encode, quality
+            s.encode, s.quality, s.jpeg_mode = encode, quality, jpeg_mode
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -766,7 +769,8 @@ class DetectionEntry:
         """``pixels``: the result of ``host_pixels(image)`` when the caller fetched it ahead of time."""
         return self.submit_batch([image], [resize_ratio], det_threshold, [self.host_pixels(image) if pixels is None else pixels], batch=1)
 
-    def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None):
+    def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
+                     subsampling=None, huffman=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -776,13 +780,21 @@ class DetectionEntry:
         the same through the encoder's huffman mode (key tagged "annotate", "png-huffman": one more pass of its own, buffers sized by
         that mode's bound).  ``encode`` = "jpeg" with ``quality`` = 1..100 (stated by the caller: it is part of the pass): the drawn
         frame is encoded as a baseline JPEG file at that IJG quality (ops.jpeg_encode_u8; key tagged "annotate", "jpeg", quality) and
-        ``collect_batch`` returns (num_rois, dets, jpg).  ``quality`` with any other ``encode`` is an error."""
+        ``collect_batch`` returns (num_rois, dets, jpg).  ``quality`` with any other ``encode`` is an error.  ``subsampling`` = 444 / 420
+        and ``huffman`` = "standard" / "optimized" (encode="jpeg" only; None: 444, "standard") select the encoder's mode; any pair but the
+        default is a pass of its own, its key tagged with the pair behind the quality -- (444, "standard") IS the pass without them."""
         if encode == JPEG_ENCODE:
             if not annotate:
                 raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
             if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
                 raise FrcnnError("submit_batch: encode=\"%s\" takes quality= an integer in 1..100, got %r" % (encode, quality))
             quality = int(quality)
+            jpeg_mode = (JPEG_MODE[0] if subsampling is None else subsampling, JPEG_MODE[1] if huffman is None else huffman)
+            if isinstance(jpeg_mode[0], bool) or jpeg_mode[0] not in _lib.JPEG_OPT_SUBSAMPLINGS or not isinstance(jpeg_mode[1], str) \
+                    or jpeg_mode[1] not in _lib.JPEG_OPT_HUFFMANS:
+                raise FrcnnError("submit_batch: subsampling=%r (444, 420), huffman=%r (\"standard\", \"optimized\")" % (subsampling, huffman))
+        elif subsampling is not None or huffman is not None:
+            raise FrcnnError("submit_batch: subsampling=%r / huffman=%r go with encode=\"%s\" only" % (subsampling, huffman, JPEG_ENCODE))
         elif quality is not None:
             raise FrcnnError("submit_batch: quality=%r goes with encode=\"%s\" only" % (quality, JPEG_ENCODE))
         elif encode is not None and encode not in PNG_ENCODES:
@@ -799,6 +811,8 @@ class DetectionEntry:
             key = self.geometry_of(pixels[0])
             assert all(self.geometry_of(p) == key for p in pixels), "one pass, one geometry"
             key = key + ((B,) if B > 1 else ()) + (("annotate", encode) if encode else ("annotate",)) + ((quality,) if quality else ())
+            if encode == JPEG_ENCODE and jpeg_mode != JPEG_MODE:
+                key = key + jpeg_mode
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -806,7 +820,8 @@ class DetectionEntry:
         if key[0] == "canvas":
             s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
         else:
-            s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality))
+            s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality,
+                                                                     jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE))
         metas, files = [], []
         for i in range(B):
             j = i if i < len(images) else 0

@@ -1131,34 +1131,64 @@ def png_bytes(frame, bgr=False, compress="runs"):
 JPEG_RESTART_MCUS = 16   # MCUs per restart interval of the device JPEG encoder (frcnn_jpeg_restart_mcus(); tests/test_jpeg_cpu.py)
 
 
-def jpeg_bound(h, w):
-    """The largest JPEG file, in bytes, that ``jpeg_encode_u8`` can make of an (h, w, 3) frame (frcnn_jpeg_bound: every block at its
-    longest, every byte stuffed).  A pure host call: needs the built library, no GPU."""
+def _jpeg_mode(what, subsampling, huffman):
+    """-> (default mode?, the C ABI's huffman value): (444, "standard") takes frcnn_jpeg_* (revision 1 of the encoder), every other pair
+    frcnn_jpeg_opt_* (include/ext/frcnn_hip_jpeg_opt.h)."""
+    if isinstance(subsampling, bool) or subsampling not in _lib.JPEG_OPT_SUBSAMPLINGS:
+        raise _lib.FrcnnError("%s: subsampling=%r (444 or 420)" % (what, subsampling))
+    if not isinstance(huffman, str) or huffman not in _lib.JPEG_OPT_HUFFMANS:
+        raise _lib.FrcnnError("%s: huffman=%r (\"standard\" or \"optimized\")" % (what, huffman))
+    return (subsampling == 444 and huffman == "standard"), _lib.JPEG_OPT_HUFFMANS[huffman]
+
+
+def jpeg_restart_mcus(subsampling=444):
+    """MCUs per restart interval: 16 at 4:4:4, 8 at 4:2:0 (48 blocks either way)."""
+    _jpeg_mode("jpeg_restart_mcus", subsampling, "standard")
+    return int(_lib.load().frcnn_jpeg_opt_restart_mcus(int(subsampling)))
+
+
+def jpeg_bound(h, w, subsampling=444, huffman="standard"):
+    """The largest JPEG file, in bytes, that ``jpeg_encode_u8`` can make of an (h, w, 3) frame in this mode (frcnn_jpeg_bound /
+    frcnn_jpeg_opt_bound: every block at its longest, every byte stuffed; the same for both ``huffman`` modes).  A pure host call: needs
+    the built library, no GPU."""
+    default, _ = _jpeg_mode("jpeg_bound", subsampling, huffman)
     h, w = int(h), int(w)
-    n = int(_lib.load().frcnn_jpeg_bound(h, w)) if 1 <= h < 2 ** 31 and 1 <= w < 2 ** 31 else 0
+    lib = _lib.load()
+    n = 0
+    if 1 <= h < 2 ** 31 and 1 <= w < 2 ** 31:
+        n = int(lib.frcnn_jpeg_bound(h, w)) if default else int(lib.frcnn_jpeg_opt_bound(h, w, int(subsampling)))
     if n == 0:
         raise _lib.FrcnnError(f"jpeg_bound: frame {h}x{w} unsupported (both sides in 1..65535, the bound below 2 GiB)")
     return n
 
 
 def jpeg_header_bytes():
-    """Bytes in front of a file's entropy-coded data, SOI .. SOS: the same for every frame (frcnn_jpeg_header_bytes)."""
+    """Bytes in front of a file's entropy-coded data, SOI .. SOS: the same for every frame with the standard tables, the most with
+    optimised ones (frcnn_jpeg_header_bytes)."""
     return int(_lib.load().frcnn_jpeg_header_bytes())
 
 
-def jpeg_workspace_bytes(h, w):
-    """Bytes of device workspace ``jpeg_encode_u8`` needs for an (h, w, 3) frame (frcnn_jpeg_workspace_bytes)."""
-    jpeg_bound(h, w)
-    return int(_lib.load().frcnn_jpeg_workspace_bytes(int(h), int(w)))
+def jpeg_workspace_bytes(h, w, subsampling=444, huffman="standard"):
+    """Bytes of device workspace ``jpeg_encode_u8`` needs for an (h, w, 3) frame in this mode (frcnn_jpeg_workspace_bytes /
+    frcnn_jpeg_opt_workspace_bytes)."""
+    default, huff = _jpeg_mode("jpeg_workspace_bytes", subsampling, huffman)
+    jpeg_bound(h, w, subsampling, huffman)
+    if default:
+        return int(_lib.load().frcnn_jpeg_workspace_bytes(int(h), int(w)))
+    return int(_lib.load().frcnn_jpeg_opt_workspace_bytes(int(h), int(w), int(subsampling), huff))
 
 
-def jpeg_encode_u8(frame, quality=90, bgr=False, out=None, out_len=None, workspace=None):
-    """Encode ``frame`` -- an (h, w, 3) uint8 device tensor, R,G,B per pixel or (``bgr``) B,G,R -- as a baseline JFIF file (4:4:4, the
-    Annex K tables at IJG ``quality`` 1..100, restart intervals of JPEG_RESTART_MCUS MCUs) on the device (frcnn_jpeg_encode_u8).
-    -> (out, out_len): ``out`` uint8 [>= jpeg_bound(h, w)] holds the file, ``out_len`` int32 [1] its length; what is not passed
-    (``workspace`` included) is allocated.  Never synchronises; reads nothing on the host per frame, so the call can be captured in a graph
-    with fixed ``out`` / ``out_len`` / ``workspace``.  Bad arguments raise FrcnnError before anything is launched."""
+def jpeg_encode_u8(frame, quality=90, bgr=False, out=None, out_len=None, workspace=None, subsampling=444, huffman="standard"):
+    """Encode ``frame`` -- an (h, w, 3) uint8 device tensor, R,G,B per pixel or (``bgr``) B,G,R -- as a baseline JFIF file (the
+    Annex K quantisation tables at IJG ``quality`` 1..100, restart intervals of jpeg_restart_mcus(subsampling) MCUs) on the device.
+    ``subsampling`` 444 or 420 (chroma halved both ways), ``huffman`` "standard" (Annex K.3) or "optimized" (four tables built on the
+    device from the frame's own symbol counts, libjpeg's construction).  The defaults take frcnn_jpeg_encode_u8 as before, every other
+    pair frcnn_jpeg_opt_encode_u8.
+    -> (out, out_len): ``out`` uint8 [>= jpeg_bound(h, w, subsampling)] holds the file, ``out_len`` int32 [1] its length; what is not
+    passed (``workspace`` included) is allocated.  Never synchronises; reads nothing on the host per frame, so the call can be captured in
+    a graph with fixed ``out`` / ``out_len`` / ``workspace``.  Bad arguments raise FrcnnError before anything is launched."""
     _require_gpu()
+    default, huff = _jpeg_mode("jpeg_encode_u8", subsampling, huffman)
     if not (isinstance(frame, torch.Tensor) and frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3
             and frame.shape[2] == 3 and frame.is_contiguous()):
         raise _lib.FrcnnError("jpeg_encode_u8: frame must be a contiguous (h, w, 3) uint8 device tensor, got %s"
@@ -1167,7 +1197,11 @@ def jpeg_encode_u8(frame, quality=90, bgr=False, out=None, out_len=None, workspa
         raise _lib.FrcnnError("jpeg_encode_u8: quality=%r (an integer in 1..100)" % (quality,))
     h, w = int(frame.shape[0]), int(frame.shape[1])
     lib = _lib.load()
-    bound, need = int(lib.frcnn_jpeg_bound(h, w)), int(lib.frcnn_jpeg_workspace_bytes(h, w))
+    if default:
+        bound, need = int(lib.frcnn_jpeg_bound(h, w)), int(lib.frcnn_jpeg_workspace_bytes(h, w))
+    else:
+        bound = int(lib.frcnn_jpeg_opt_bound(h, w, int(subsampling)))
+        need = int(lib.frcnn_jpeg_opt_workspace_bytes(h, w, int(subsampling), huff))
     if out is None and bound:
         out = torch.empty(bound, dtype=torch.uint8, device="cuda")
     if out_len is None:
@@ -1179,18 +1213,55 @@ def jpeg_encode_u8(frame, quality=90, bgr=False, out=None, out_len=None, workspa
             raise _lib.FrcnnError(f"jpeg_encode_u8: {name} must be a contiguous {dt} device tensor")
     if workspace is not None and workspace.numel() < need:
         raise _lib.FrcnnError(f"jpeg_encode_u8: workspace of {workspace.numel()} bytes, {need} needed")
-    _lib.call("frcnn_jpeg_encode_u8", _p(frame) if frame.numel() else None, h, w, 1 if bgr else 0, int(quality), _p(out),
-              out.numel() if out is not None else 0, _p(out_len), _p(workspace), _stream())
+    if default:
+        _lib.call("frcnn_jpeg_encode_u8", _p(frame) if frame.numel() else None, h, w, 1 if bgr else 0, int(quality), _p(out),
+                  out.numel() if out is not None else 0, _p(out_len), _p(workspace), _stream())
+    else:
+        _lib.call("frcnn_jpeg_opt_encode_u8", _p(frame) if frame.numel() else None, h, w, 1 if bgr else 0, int(quality), int(subsampling),
+                  huff, _p(out), out.numel() if out is not None else 0, _p(out_len), _p(workspace), _stream())
     return out, out_len
 
 
-def jpeg_bytes(frame, quality=90, bgr=False):
+def jpeg_bytes(frame, quality=90, bgr=False, subsampling=444, huffman="standard"):
     """``jpeg_encode_u8`` and the file as ``bytes``: the eager convenience (one synchronisation, one copy of the encoded length)."""
-    out, out_len = jpeg_encode_u8(frame, quality=quality, bgr=bgr)
+    out, out_len = jpeg_encode_u8(frame, quality=quality, bgr=bgr, subsampling=subsampling, huffman=huffman)
     n = int(out_len.item())
     if not 0 < n <= out.numel():
         raise _lib.FrcnnError(f"jpeg_bytes: encoded length {n} outside (0, {out.numel()}]")
     return out[:n].cpu().numpy().tobytes()
+
+
+def jpeg_build_tables(hist, out=None):
+    """The optimised encoder's table kernel alone (frcnn_jpeg_opt_build_tables): ``hist`` four histograms of 256 counts (an int32
+    device tensor [4][256] whose bits are read as uint32, or anything numpy makes into [4][256] counts below 2^32) -> a uint8 device
+    tensor [4][276]: four ``_lib.JpegOptTable`` records (BITS[16], HUFFVAL[256], count), table k from histogram k by libjpeg's
+    jpeg_gen_optimal_table.  ``jpeg_tables_from_records`` unpacks them on the host."""
+    _require_gpu()
+    if not isinstance(hist, torch.Tensor):
+        a = np.asarray(hist)
+        if a.shape != (4, 256) or a.min() < 0 or a.max() >= 2 ** 32:
+            raise _lib.FrcnnError("jpeg_build_tables: hist must be [4][256] counts in 0..2^32-1")
+        hist = torch.from_numpy(a.astype(np.uint32).view(np.int32).copy()).cuda()
+    if not (hist.is_cuda and hist.dtype == torch.int32 and tuple(hist.shape) == (4, 256) and hist.is_contiguous()):
+        raise _lib.FrcnnError("jpeg_build_tables: hist must be a contiguous int32 device tensor [4][256]")
+    size = ctypes.sizeof(_lib.JpegOptTable)
+    if out is None:
+        out = torch.zeros((4, size), dtype=torch.uint8, device="cuda")
+    if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (4, size) and out.is_contiguous()):
+        raise _lib.FrcnnError(f"jpeg_build_tables: out must be a contiguous uint8 device tensor [4][{size}]")
+    _lib.call("frcnn_jpeg_opt_build_tables", _p(hist), _p(out), _stream())
+    return out
+
+
+def jpeg_tables_from_records(records):
+    """``jpeg_build_tables``'s result -> [(BITS: 16 ints, HUFFVAL: the table's symbols)] x 4 on the host (one synchronising copy)."""
+    raw = records.cpu().numpy().tobytes()
+    size = ctypes.sizeof(_lib.JpegOptTable)
+    out = []
+    for k in range(4):
+        rec = _lib.JpegOptTable.from_buffer_copy(raw[k * size:(k + 1) * size])
+        out.append((list(rec.bits), list(rec.huffval)[:rec.count]))
+    return out
 
 
 class JpegUnsupported(_lib.FrcnnError):

@@ -13,9 +13,11 @@ machine falls on all three alike.  ``--content photo`` fills the frames with the
 per frame) instead of uniform noise: noise does not compress, so bytes per frame mean something only on the photograph.
 ``--legs`` names the legs (c) outright, alternating in the same way: besides the three PNG legs, ``jpeg_host`` and ``jpeg_device`` write
 ``--frame_format jpg`` at quality 90 with PIL on the writer threads and with the device encoder (ops.jpeg_encode_u8) inside the pass.
+``jpeg_host_420_opt`` and ``jpeg_device_420_opt`` are the same two with ``jpeg_subsampling=420, jpeg_huffman="optimized"`` (PIL's
+``subsampling=2, optimize=True``; the device encoder's csrc/jpeg_opt.hip); every leg reports its bytes per frame.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
-                                     [--legs host,device_huffman,jpeg_host,jpeg_device] [--content noise|photo]
+                                     [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt] [--content noise|photo]
 """
 import argparse
 import contextlib
@@ -80,7 +82,11 @@ def annotate_in_memory(eng, resized, ratios):
 LEGS = {"host": dict(png_encoder="host", png_compress="runs"), "device": dict(png_encoder="device", png_compress="runs"),
         "device_huffman": dict(png_encoder="device", png_compress="huffman"),
         "jpeg_host": dict(png_encoder="host", png_compress="runs", frame_format="jpg", jpeg_encoder="host", jpeg_quality=90),
-        "jpeg_device": dict(png_encoder="host", png_compress="runs", frame_format="jpg", jpeg_encoder="device", jpeg_quality=90)}
+        "jpeg_device": dict(png_encoder="host", png_compress="runs", frame_format="jpg", jpeg_encoder="device", jpeg_quality=90),
+        "jpeg_host_420_opt": dict(png_encoder="host", png_compress="runs", frame_format="jpg", jpeg_encoder="host", jpeg_quality=90,
+                                  jpeg_subsampling=420, jpeg_huffman="optimized"),
+        "jpeg_device_420_opt": dict(png_encoder="host", png_compress="runs", frame_format="jpg", jpeg_encoder="device", jpeg_quality=90,
+                                    jpeg_subsampling=420, jpeg_huffman="optimized")}
 
 
 def photo_frames(h, w, n):
