@@ -222,6 +222,34 @@ E_UNSUPPORTED = -4     # include/frcnn_hip.h FRCNN_E_UNSUPPORTED
 JPEG_DEC_BLOCKS, JPEG_DEC_ZIGZAG, JPEG_DEC_CODE, JPEG_DEC_TABLE = 1, 2, 4, 8     # FRCNN_JPEG_DEC_* status bits
 
 
+PNG_DEC_VERSION = 1     # include/ext/frcnn_hip_png_dec.h FRCNN_PNG_DEC_VERSION
+PNG_DEC_BATCH_MAX = 64  # ... FRCNN_PNG_DEC_BATCH_MAX
+PNG_DEC_WINDOW_BYTES = 8192     # ... FRCNN_PNG_DEC_WINDOW_BYTES: compressed bytes per window of the inflate kernel
+PNG_DEC_MAX_STREAM = 1 << 24    # ... FRCNN_PNG_DEC_MAX_STREAM
+PNG_DEC_SIGNATURES = {
+    "frcnn_png_dec_version": (I, []),
+    "frcnn_png_dec_plan": (I, [P, c_size_t, P]),
+    "frcnn_png_dec_spans": (I, [P, c_size_t, P, P, c_size_t]),
+    "frcnn_png_dec_workspace_bytes": (c_size_t, [P]),
+    "frcnn_png_dec_batch_layout": (c_size_t, [P, I, P]),
+    "frcnn_png_decode_batch_u8": (I, [P, P, I, P, c_size_t, I, P, c_size_t, P, P, c_size_t, P]),
+}
+# FRCNN_PNG_DEC_* status bits
+PNG_DEC_CODE, PNG_DEC_BLOCK, PNG_DEC_OVERSUBSCRIBED, PNG_DEC_DISTANCE, PNG_DEC_OVERRUN, PNG_DEC_UNDERRUN, PNG_DEC_ADLER, PNG_DEC_FILTER = \
+    1, 2, 4, 8, 16, 32, 64, 128
+
+
+class PngDecPlan(ctypes.Structure):
+    """frcnn_png_dec_plan_t (include/ext/frcnn_hip_png_dec.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("h", "w", "channels")] + \
+               [(k, ctypes.c_uint32) for k in ("file_len", "idat_off", "idat_count", "stream_len", "inflated_len")]
+
+
+class PngDecBatchItem(ctypes.Structure):
+    """frcnn_png_dec_batch_item_t (include/ext/frcnn_hip_png_dec.h)."""
+    _fields_ = [("plan", PngDecPlan), ("file_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("ws_off", ctypes.c_uint64)]
+
+
 class JpegDecPlan(ctypes.Structure):
     """frcnn_jpeg_dec_plan_t (include/ext/frcnn_hip_jpeg_dec.h)."""
     _fields_ = [(k, ctypes.c_int32) for k in ("h", "w", "components", "hs", "vs", "mcus_x", "mcus_y", "blocks_per_mcu")] + \
@@ -321,6 +349,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in PNG_DEC_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_png_dec_version() != PNG_DEC_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_png_dec_version()} of the PNG decoder extension, this binding "
+                         f"{PNG_DEC_VERSION} (include/ext/frcnn_hip_png_dec.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_jpeg_dec_batch_version() != JPEG_DEC_BATCH_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_dec_batch_version()} of the JPEG decoder's batch extension, this binding "
                          f"{JPEG_DEC_BATCH_VERSION} (include/ext/frcnn_hip_jpeg_dec_batch.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -264,20 +264,26 @@ JPEG_SUFFIXES = (".jpg", ".jpeg")
 JPEG_DECODERS = ("host", "device")
 
 
-def frame_filenames(input_dir, jpeg_decoder="host"):
-    """``png_filenames`` and, with ``jpeg_decoder`` = "device", the ``*.jpg`` / ``*.jpeg`` names too: the input frames, sorted."""
-    from .feed import jpeg_decoder_option
+PNG_DECODERS = ("host", "device")
+
+
+def frame_filenames(input_dir, jpeg_decoder="host", png_decoder="host"):
+    """``png_filenames`` and, with ``jpeg_decoder`` = "device", the ``*.jpg`` / ``*.jpeg`` names too: the input frames, sorted.
+    ``png_decoder`` ("host" / "device": who decodes the ``*.png`` frames) is checked and changes no name."""
+    from .feed import jpeg_decoder_option, png_decoder_option
+    png_decoder_option(png_decoder, "png_decoder")
     if jpeg_decoder_option(jpeg_decoder, "jpeg_decoder") != "device":
         return png_filenames(input_dir)
     return sorted(f for f in os.listdir(input_dir) if f.endswith(".png") or f.lower().endswith(JPEG_SUFFIXES))
 
 
 class _FileFrame:
-    """A .jpg input frame the device decodes: the file's bytes and the size its header states (entry.DetectionEntry.host_pixels asks
-    ``raw_file()``); ``raw_rgb`` decodes on the host for whoever still wants pixels."""
+    """A .jpg or .png input frame the device decodes: the file's bytes and the size its header states (entry.DetectionEntry.host_pixels
+    asks ``raw_file()``); ``raw_rgb`` decodes on the host for whoever still wants pixels.  ``png_planned``: what feed.plan_png made of
+    a .png file on the decode thread (its zlib stream and plan), so that ``host_pixels`` does not parse it again."""
 
-    def __init__(self, data, path, file_size, width=None, height=None):
-        self.data, self._image_path, self.file_size = data, path, file_size
+    def __init__(self, data, path, file_size, width=None, height=None, png_planned=None):
+        self.data, self._image_path, self.file_size, self.png_planned = data, path, file_size, png_planned
         self.height = int(file_size[0]) if height is None else height
         self.width = int(file_size[1]) if width is None else width
         self._pixels = None
@@ -298,7 +304,8 @@ class _FileFrame:
     raw = property(lambda s: s.raw_rgb[:, :, ::-1])
 
     def resize(self, scale_ratio):
-        return _FileFrame(self.data, self._image_path, self.file_size, int(round(scale_ratio * self.width)), int(round(scale_ratio * self.height)))
+        return _FileFrame(self.data, self._image_path, self.file_size, int(round(scale_ratio * self.width)), int(round(scale_ratio * self.height)),
+                          self.png_planned)
 
     def resize_within_bounds(self, min_size, max_size):
         ratio = shapes._bounds_ratio(self.width, self.height, min_size, max_size)
@@ -327,7 +334,7 @@ class _Frame:
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
-                    jpeg_huffman=None):
+                    jpeg_huffman=None, png_decoder=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -336,11 +343,16 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     ``jpeg_subsampling``: 444 or 420, ``jpeg_huffman``: "standard" or "optimized" -- of JPEG frames, whichever encoder writes them;
     None = ``default_jpeg_subsampling()`` / ``default_jpeg_huffman()``.
     ``jpeg_decoder``: "host" or "device": who decodes ``.jpg`` INPUT frames the device decoder supports (captured path only); None =
-    what ``entry.jpeg_decoder()`` says (FRCNN_ENTRY_JPEG_DECODER, default "host")."""
+    what ``entry.jpeg_decoder()`` says (FRCNN_ENTRY_JPEG_DECODER, default "host").
+    ``png_decoder``: "host" or "device": who decodes ``.png`` INPUT frames the device decoder supports (captured path only; the decode
+    threads then only read the file and check its chunks); None = what ``entry.png_decoder()`` says (FRCNN_ENTRY_PNG_DECODER, default "host")."""
     from concurrent.futures import ThreadPoolExecutor
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
+    if png_decoder is not None:
+        entry.set_png_decoder(png_decoder)
     device_decode = entry.jpeg_decoder() == "device"
+    device_png = entry.png_decoder() == "device"
     png_encoder, png_compress = png_options(png_encoder, png_compress)
     frame_format, jpeg_encoder, jpeg_quality = jpeg_options(frame_format, jpeg_encoder, jpeg_quality, png_encoder, png_compress)
     jpeg_subsampling, jpeg_huffman = jpeg_size_options(frame_format, jpeg_subsampling, jpeg_huffman)
@@ -386,6 +398,13 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
                 frame = _FileFrame(data, path, (int(plan.h), int(plan.w)))
             except ops.JpegUnsupported:
                 pass                                          # (progressive, CMYK, ...: PIL below)
+        elif device_png and path.lower().endswith(".png"):
+            from .feed import plan_png
+            with open(path, "rb") as f:
+                data = f.read()
+            planned = plan_png(data)                          # None: palette, 16-bit, interlaced, ...: PIL below
+            if planned is not None:
+                frame = _FileFrame(data, path, (int(planned[1].h), int(planned[1].w)), png_planned=planned)
         if frame is None:
             frame = _Frame(_read_rgb(path))
         resized, ratio = frame.resize_within_bounds(resize_min, resize_max)
@@ -482,6 +501,9 @@ def build_parser():
     p.add_argument("--jpeg_decoder", dest="jpeg_decoder", choices=JPEG_DECODERS, default=None,
                    help="who decodes .jpg INPUT frames: host (PIL) or device (csrc/jpeg_dec.hip; input_dir's *.jpg / *.jpeg are then "
                         "taken beside its *.png); default: FRCNN_ENTRY_JPEG_DECODER, else host")
+    p.add_argument("--png_decoder", dest="png_decoder", choices=PNG_DECODERS, default=None,
+                   help="who decodes .png INPUT frames: host (PIL) or device (csrc/png_dec.hip, for the files its planner takes); "
+                        "default: FRCNN_ENTRY_PNG_DECODER, else host")
     p.add_argument("--jpeg_quality", dest="jpeg_quality", type=int, default=None,
                    help="IJG quality of JPEG frames, 1..100 (default %d; needs --frame_format jpg)" % JPEG_QUALITY)
     p.add_argument("--jpeg_subsampling", dest="jpeg_subsampling", type=int, choices=JPEG_SUBSAMPLINGS, default=default_jpeg_subsampling(),
@@ -520,7 +542,7 @@ def main(argv=None):
     resize_min, resize_max = resize_dims_from_str(args.resize_dims)
     annotate_images(training_manager=manager, detector=detector, input_dir=args.input_dir, out_dir=args.out_dir,
                     image_filenames=frame_filenames(args.input_dir, args.jpeg_decoder or entry.jpeg_decoder()), resize_min=resize_min,
-                    resize_max=resize_max, jpeg_decoder=args.jpeg_decoder,
+                    resize_max=resize_max, jpeg_decoder=args.jpeg_decoder, png_decoder=args.png_decoder,
                     png_encoder=args.png_encoder, png_compress=args.png_compress, frame_format=args.frame_format,
                     jpeg_encoder=args.jpeg_encoder, jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling,
                     jpeg_huffman=args.jpeg_huffman)

@@ -124,6 +124,30 @@ class JpegFile:
 
     def __init__(self, data, plan, name):
         self.data, self.plan, self.name = data, plan, name
+
+
+# who decodes a file-backed .png frame: "host" (PIL, the default) or "device" (ops.png_decode_batch_u8 in front of the replay, beside the
+# JPEG decoder's call when a pass mixes both; PIL for the files its planner refuses).  FRCNN_ENTRY_PNG_DECODER, or ``set_png_decoder``
+# (annotate_video --png_decoder), which wins.
+_PNG_DECODER = None
+
+
+def set_png_decoder(value):
+    """"host" / "device" for every DetectionEntry of the process from now on; None: back to FRCNN_ENTRY_PNG_DECODER."""
+    global _PNG_DECODER
+    from .feed import png_decoder_option
+    _PNG_DECODER = None if value is None else png_decoder_option(value, "png_decoder")
+
+
+def png_decoder():
+    from .feed import png_decoder_option
+    return _PNG_DECODER or png_decoder_option(os.environ.get("FRCNN_ENTRY_PNG_DECODER"), "FRCNN_ENTRY_PNG_DECODER")
+
+
+class PngFile(JpegFile):
+    """A .png frame the device decodes: ``data`` is its zlib stream (the IDAT payloads back to back), ``plan`` a ``_lib.PngDecPlan``.  A
+    JpegFile to everything that only asks for the frame's size (plan.h, plan.w) and stages ``data``."""
+    __slots__ = ()
 CANVAS_GRANULE = int(os.environ.get("FRCNN_ENTRY_CANVAS_GRANULE", "32"))
 CANVAS_MIN_GEOMETRIES = int(os.environ.get("FRCNN_ENTRY_CANVAS_MIN", "4"))
 # captured passes kept per canvas class: with several classes interleaving in a list, two of one class in flight at once is the common
@@ -259,7 +283,8 @@ class _Slot:
     __slots__ = ("key", "pipe", "graph", "out", "io_dev", "io_pin", "dyn_host", "out_pin", "event", "busy", "nbytes", "x_f32", "ws", "tabs", "u8_resized",
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
-                 "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used")
+                 "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
+                 "jpg_count", "png_items")
 
     def __init__(self):
         for name in self.__slots__:
@@ -628,12 +653,15 @@ class DetectionEntry:
         Returns (array, H, W, src or None, flip)."""
         if self.device_preprocess and _declares(image, "raw") and _declares(image, "height"):
             H, W, flip = int(image.height), int(image.width), bool(getattr(image, "flipped", False))
-            if RGB_UPLOAD and jpeg_decoder() == "device":
+            jpeg_dev, png_dev = jpeg_decoder() == "device", png_decoder() == "device"
+            if RGB_UPLOAD and (jpeg_dev or png_dev):
                 from . import feed
-                planned = feed.plan_file(image)               # None: in-memory pixels, or a file the device decoder does not take
+                # None: in-memory pixels, or a file the device decoders do not take
+                planned = feed.plan_entry_file(image, jpeg=jpeg_dev, png=True) if png_dev else feed.plan_file(image)
                 if planned is not None:
                     data, plan = planned
-                    return JpegFile(data, plan, getattr(image, "_image_path", None) or str(getattr(image, "name", "?"))), H, W, \
+                    kind = PngFile if isinstance(plan, _lib.PngDecPlan) else JpegFile
+                    return kind(data, plan, getattr(image, "_image_path", None) or str(getattr(image, "name", "?"))), H, W, \
                         (int(plan.h), int(plan.w)), 2 | int(flip)
             rgb = getattr(image, "raw_rgb", None) if RGB_UPLOAD else None
             if rgb is not None:
@@ -868,8 +896,10 @@ class DetectionEntry:
         ``files``: (frame index, JpegFile) of the pass's file-backed frames; item k is files[k], its output frame i's source segment.  A
         file that fills several frames (the padding of a short group) is staged once."""
         B = s.batch
-        item = ctypes.sizeof(_lib.JpegDecBatchItem)
-        table = (B * item + 255) // 256 * 256
+        files.sort(key=lambda t: isinstance(t[1], PngFile))         # (in place, stable: the .jpg items first, then the .png items)
+        nj = sum(1 for _, f in files if not isinstance(f, PngFile))
+        item, pitem = ctypes.sizeof(_lib.JpegDecBatchItem), ctypes.sizeof(_lib.PngDecBatchItem)
+        table = (B * (item + pitem) + 255) // 256 * 256             # [B JPEG items | B PNG items]
         at, seen, file_off = 0, {}, []
         for _, f in files:
             if id(f) not in seen:
@@ -883,8 +913,12 @@ class DetectionEntry:
             s.jpg_dev = s.jpg_area[table:]                           # the file area; the table lies in front of it
         plans = [f.plan for _, f in files]
         ws_off, need = [], 0
-        for k in range(0, len(plans), _lib.JPEG_DEC_BATCH_MAX):      # (a call takes JPEG_DEC_BATCH_MAX items: its regions behind the last call's)
-            offs, total = ops.jpeg_dec_batch_layout(plans[k:k + _lib.JPEG_DEC_BATCH_MAX])
+        for k in range(0, nj, _lib.JPEG_DEC_BATCH_MAX):              # (a call takes JPEG_DEC_BATCH_MAX items: its regions behind the last call's)
+            offs, total = ops.jpeg_dec_batch_layout(plans[k:min(nj, k + _lib.JPEG_DEC_BATCH_MAX)])
+            ws_off += [need + o for o in offs]
+            need += total
+        for k in range(nj, len(plans), _lib.PNG_DEC_BATCH_MAX):
+            offs, total = ops.png_dec_batch_layout(plans[k:k + _lib.PNG_DEC_BATCH_MAX])
             ws_off += [need + o for o in offs]
             need += total
         if s.jpg_ws is None or s.jpg_ws.numel() < need:
@@ -892,11 +926,17 @@ class DetectionEntry:
         if s.jpg_status is None:
             s.jpg_status = torch.zeros(B, dtype=torch.int32, device="cuda")
             s.jpg_status_pin = torch.zeros(B, dtype=torch.int32).pin_memory()
-        s.jpg_items = ops.jpeg_batch_items(plans, file_off, [i * s.seg for i, _ in files], ws_off)
+        out_off = [i * s.seg for i, _ in files]
+        s.jpg_items = ops.jpeg_batch_items(plans[:nj], file_off[:nj], out_off[:nj], ws_off[:nj])
+        s.png_items = ops.png_batch_items(plans[nj:], file_off[nj:], out_off[nj:], ws_off[nj:])
+        s.jpg_count = nj
         s.jpg_used = table + at
-        s.jpg_names = [f.name for _, f in files]                    # (item k's status word is word k)
+        s.jpg_names = [f.name for _, f in files]                    # (item k's status word is word k: the .jpg items, then the .png items)
         host = s.jpg_pin.numpy()
-        host[:len(files) * item] = np.frombuffer(s.jpg_items, dtype=np.uint8)
+        if nj:
+            host[:nj * item] = np.frombuffer(s.jpg_items, dtype=np.uint8)
+        if len(files) > nj:
+            host[B * item:B * item + (len(files) - nj) * pitem] = np.frombuffer(s.png_items, dtype=np.uint8)
         for f in {id(f): f for _, f in files}.values():
             host[table + seen[id(f)]:table + seen[id(f)] + len(f.data)] = np.frombuffer(f.data, dtype=np.uint8)
 
@@ -905,17 +945,24 @@ class DetectionEntry:
         the status words cleared, one batched decode of every file into its frame's source segment (R,G,B as PIL delivers it: the pass's
         resize swaps, flip bit 1).  FRCNN_ENTRY_JPEG_BATCH=0: an upload and a single-file decode per file instead."""
         item, table = ctypes.sizeof(_lib.JpegDecBatchItem), s.jpg_area.numel() - s.jpg_dev.numel()
-        if jpeg_batch():
+        nj, batched = s.jpg_count, jpeg_batch()
+        if batched or len(files) > nj:                              # (the .png items are always decoded as a batch)
             s.jpg_area[:s.jpg_used].copy_(s.jpg_pin[:s.jpg_used], non_blocking=True)
-            s.jpg_status.zero_()
-            for k in range(0, len(files), _lib.JPEG_DEC_BATCH_MAX):
-                n = min(_lib.JPEG_DEC_BATCH_MAX, len(files) - k)
+        s.jpg_status.zero_()
+        pitem, ptable = ctypes.sizeof(_lib.PngDecBatchItem), s.batch * item
+        for k in range(0, len(files) - nj, _lib.PNG_DEC_BATCH_MAX):
+            n = min(_lib.PNG_DEC_BATCH_MAX, len(files) - nj - k)
+            part = (_lib.PngDecBatchItem * n).from_buffer(s.png_items, k * pitem)
+            ops.png_decode_batch_u8(s.jpg_dev, part, s.io_dev, status=s.jpg_status[nj + k:nj + k + n], workspace=s.jpg_ws,
+                                    items_dev=s.jpg_area[ptable + k * pitem:ptable + (k + n) * pitem])
+        if batched:
+            for k in range(0, nj, _lib.JPEG_DEC_BATCH_MAX):
+                n = min(_lib.JPEG_DEC_BATCH_MAX, nj - k)
                 part = (_lib.JpegDecBatchItem * n).from_buffer(s.jpg_items, k * item)
                 ops.jpeg_decode_batch_u8(s.jpg_dev, part, s.io_dev, status=s.jpg_status[k:k + n], workspace=s.jpg_ws,
                                          items_dev=s.jpg_area[k * item:(k + n) * item])
             return
-        s.jpg_status.zero_()
-        for k, (i, f) in enumerate(files):
+        for k, (i, f) in enumerate(files[:nj]):
             it = s.jpg_items[k]
             lo, n, frame = table + int(it.file_off), len(f.data), int(f.plan.h) * int(f.plan.w) * 3
             s.jpg_area[lo:lo + n].copy_(s.jpg_pin[lo:lo + n], non_blocking=True)
@@ -962,6 +1009,9 @@ class DetectionEntry:
             if s.jpg_names:
                 words = s.jpg_status_pin.numpy()
                 for i, name in enumerate(s.jpg_names):
+                    if name is not None and int(words[i]) and i >= (s.jpg_count or 0):
+                        raise FrcnnError("device PNG decoder: %s is damaged (status %d: FRCNN_PNG_DEC_* in include/ext/frcnn_hip_png_dec.h); "
+                                         "decode it on the host or repair the file" % (name, int(words[i])))
                     if name is not None and int(words[i]):
                         raise FrcnnError("device JPEG decoder: %s is damaged (status %d: FRCNN_JPEG_DEC_* in include/ext/frcnn_hip_jpeg_dec.h); "
                                          "decode it on the host or repair the file" % (name, int(words[i])))

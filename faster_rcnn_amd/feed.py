@@ -47,6 +47,46 @@ def plan_file(image):
         return None
 
 
+PNG_DECODERS = ("host", "device")
+
+
+def png_decoder_option(value, what):
+    """A PNG decoder setting ("host": PIL, the default; "device": ops.png_decode_batch_u8 for the files its planner supports, PIL for the
+    rest) checked: -> the value, ValueError naming ``what`` (an environment variable, an option) for anything else."""
+    value = "host" if value is None or value == "" else value
+    if value not in PNG_DECODERS:
+        raise ValueError("%s=%r: one of %s" % (what, value, ", ".join(PNG_DECODERS)))
+    return value
+
+
+def plan_png(data):
+    """(the zlib stream of a .png file's bytes: its IDAT payloads back to back, what goes to the device; its decode plan), or None for a
+    file outside the device PNG decoder's supported set.  Pure host work."""
+    try:
+        plan = ops.png_dec_plan(data)
+    except ops.PngUnsupported:
+        return None
+    return ops.png_dec_stream(data, plan), plan
+
+
+def plan_entry_file(image, jpeg=True, png=False):
+    """``plan_file`` for the detection entry, which may decode either kind on the device: a file-backed image whose bytes start with
+    the PNG signature is planned by the PNG decoder's planner when ``png`` (-> (its zlib stream, its ``PngDecPlan``); what an
+    ``annotate_video._FileFrame`` planned ahead is taken as it is), any other file by ``plan_file`` when ``jpeg``.  None: the caller
+    takes the host path.  (``device_image``, the training feed, keeps to ``plan_file``: it decodes .png files on the host.)"""
+    if not _declares(image, "raw_file") or getattr(image, "_pixels", None) is not None:
+        return None
+    data = image.raw_file()
+    if data is None:
+        return None
+    if bytes(data[:8]) == ops.PNG_SIGNATURE:
+        if not png:
+            return None
+        planned = getattr(image, "png_planned", None)
+        return planned if planned is not None else plan_png(data)
+    return plan_file(image) if jpeg else None
+
+
 class _PinRing:
     """A few grow-only pinned staging areas used in turn: ``upload(array)`` copies the array into the next one and starts an
     ASYNCHRONOUS copy to the device on the current stream (a pageable source makes the runtime stage the bytes itself and block the

@@ -1381,6 +1381,120 @@ def jpeg_decode_batch_u8(files, items, out, bgr=False, status=None, workspace=No
     return status
 
 
+class PngUnsupported(_lib.FrcnnError):
+    """``png_dec_plan``: the file lies outside the device decoder's supported set; the message names the reason."""
+
+
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_DEC_WINDOW_BYTES = _lib.PNG_DEC_WINDOW_BYTES    # compressed bytes per window of the inflate kernel (a larger block carries its tables over)
+
+
+def png_dec_plan(data):
+    """The host-side chunk parse of a .png file's bytes (frcnn_png_dec_plan) -> a ``_lib.PngDecPlan``: size, channels, where the IDATs
+    lie, the bytes of the zlib stream and of what it inflates to; the CRC-32 of IHDR and of every IDAT is verified.  ``PngUnsupported``
+    (a FrcnnError) with the reason for a file outside the supported set (include/ext/frcnn_hip_png_dec.h): the caller decodes it on the
+    host.  A pure host call: needs the built library, no GPU."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise _lib.FrcnnError("png_dec_plan: the file's bytes, got %s" % type(data).__name__)
+    data = bytes(data)
+    plan = _lib.PngDecPlan()
+    lib = _lib.load()
+    code = lib.frcnn_png_dec_plan(data, len(data), ctypes.byref(plan))
+    if code == _lib.E_UNSUPPORTED:
+        raise PngUnsupported((lib.frcnn_last_error() or b"").decode())
+    _lib.check(code, "frcnn_png_dec_plan")
+    return plan
+
+
+def png_dec_spans(data, plan):
+    """[(offset, length)] of the IDAT payloads of the file ``plan`` was made of (frcnn_png_dec_spans), in file order."""
+    data = bytes(data)
+    n = int(plan.idat_count)
+    spans = (ctypes.c_uint32 * (2 * max(n, 1)))()
+    _lib.call("frcnn_png_dec_spans", data, len(data), ctypes.byref(plan), spans, n)
+    return [(int(spans[2 * k]), int(spans[2 * k + 1])) for k in range(n)]
+
+
+def png_dec_stream(data, plan):
+    """What goes to the device: the file's zlib stream, its IDAT payloads back to back (``plan.stream_len`` bytes)."""
+    data = bytes(data)
+    spans = png_dec_spans(data, plan)
+    return data[spans[0][0]:spans[0][0] + spans[0][1]] if len(spans) == 1 else b"".join(data[o:o + n] for o, n in spans)
+
+
+def png_dec_workspace_bytes(plan):
+    """Bytes of device workspace a file of ``plan`` needs (frcnn_png_dec_workspace_bytes): its inflated bytes."""
+    n = int(_lib.load().frcnn_png_dec_workspace_bytes(ctypes.byref(plan)))
+    if n == 0:
+        raise _lib.FrcnnError("png_dec_workspace_bytes: not a plan that png_dec_plan made")
+    return n
+
+
+def png_dec_batch_layout(plans):
+    """Workspace regions for a batch of plans laid back to back (frcnn_png_dec_batch_layout) -> (ws_off, total).  A pure host call."""
+    n = len(plans)
+    if not 1 <= n <= _lib.PNG_DEC_BATCH_MAX:
+        raise _lib.FrcnnError(f"png_dec_batch_layout: {n} plans, 1..{_lib.PNG_DEC_BATCH_MAX} go into one batch")
+    arr = (_lib.PngDecPlan * n)(*plans)
+    offs = (ctypes.c_uint64 * n)()
+    total = int(_lib.load().frcnn_png_dec_batch_layout(arr, n, offs))
+    if total == 0:
+        raise _lib.FrcnnError("png_dec_batch_layout: not plans that png_dec_plan made")
+    return [int(o) for o in offs], total
+
+
+def png_batch_items(plans, file_off, out_off, ws_off):
+    """The item table of a batch (``_lib.PngDecBatchItem`` x n, a ctypes array: ``bytes(table)`` is what goes to the device);
+    ``file_off``: where each file's staged zlib stream (``png_dec_stream``) lies."""
+    items = (_lib.PngDecBatchItem * len(plans))()
+    for it, p, f, o, w in zip(items, plans, file_off, out_off, ws_off):
+        it.plan, it.file_off, it.out_off, it.ws_off = p, int(f), int(o), int(w)
+    return items
+
+
+def png_decode_batch_u8(files, items, out, bgr=False, status=None, workspace=None, items_dev=None):
+    """Decode the .png files of a batch on the device in TWO launches (frcnn_png_decode_batch_u8): ``files`` a 1-d uint8 device tensor
+    that holds every file's zlib stream, ``items`` the table (``png_batch_items``), ``out`` a 1-d uint8 device tensor -> status: int32
+    [n], per file 0 or _lib.PNG_DEC_* bits ORed in (sticky: a tensor passed in is not cleared).  ``items_dev``: a device tensor that
+    already holds ``bytes(items)``; None: uploaded here, a pageable copy, which blocks the host.  ``status`` and ``workspace`` are
+    allocated when not passed.  Never synchronises otherwise."""
+    _require_gpu()
+    n = len(items)
+    if not isinstance(items, ctypes.Array) or items._type_ is not _lib.PngDecBatchItem:
+        raise _lib.FrcnnError("png_decode_batch_u8: items must be a table made by png_batch_items")
+    if items_dev is None:
+        items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).cuda()
+    if status is None:
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
+    if workspace is None:
+        workspace = _ws(max((int(it.ws_off) + png_dec_workspace_bytes(it.plan) for it in items), default=0))
+    for name, t, dt in (("files", files, torch.uint8), ("out", out, torch.uint8), ("status", status, torch.int32),
+                        ("workspace", workspace, torch.uint8), ("items_dev", items_dev, torch.uint8)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise _lib.FrcnnError(f"png_decode_batch_u8: {name} must be a contiguous {dt} device tensor")
+    if items_dev.numel() < ctypes.sizeof(items) or status.numel() < n:
+        raise _lib.FrcnnError(f"png_decode_batch_u8: items_dev of {items_dev.numel()} bytes / status of {status.numel()} words for {n} items")
+    _lib.call("frcnn_png_decode_batch_u8", ctypes.addressof(items), _p(items_dev), n, _p(files), files.numel(), 1 if bgr else 0,
+              _p(out), out.numel(), _p(status), _p(workspace), workspace.numel(), _stream())
+    return status
+
+
+def png_decode_u8(file_bytes, bgr=False):
+    """One .png file's bytes decoded on the device: the eager convenience (a batch of one; pageable uploads, one synchronisation) -> an
+    (h, w, 3) uint8 device tensor, numpy.asarray(PIL.Image.open(f).convert("RGB")) byte for byte, or its channel reverse with ``bgr``.
+    ``PngUnsupported`` for a file outside the supported set, ``FrcnnError`` with the status word for a damaged one."""
+    _require_gpu()
+    data = bytes(file_bytes)
+    plan = png_dec_plan(data)
+    files = torch.frombuffer(bytearray(png_dec_stream(data, plan)), dtype=torch.uint8).cuda()
+    out = torch.empty((int(plan.h), int(plan.w), 3), dtype=torch.uint8, device="cuda")
+    status = png_decode_batch_u8(files, png_batch_items([plan], [0], [0], [0]), out.view(-1), bgr=bgr)
+    word = int(status.cpu()[0])
+    if word:
+        raise _lib.FrcnnError("png_decode_u8: the file is damaged (status %d: FRCNN_PNG_DEC_* in include/ext/frcnn_hip_png_dec.h)" % word)
+    return out
+
+
 def split_detections(packed, rows=None):
     """Views (n_dets, det_bbox, det_cls, det_prob, det_roi) into a `det_packed` buffer (device tensor or its host copy)."""
     rows = (packed.numel() - 4) // 7 if rows is None else rows

@@ -17,7 +17,7 @@ per frame) instead of uniform noise: noise does not compress, so bytes per frame
 ``subsampling=2, optimize=True``; the device encoder's csrc/jpeg_opt.hip); every leg reports its bytes per frame.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
-                                     [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt] [--content noise|photo]
+                                     [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device] [--content noise|photo]
 """
 import argparse
 import contextlib
@@ -86,7 +86,10 @@ LEGS = {"host": dict(png_encoder="host", png_compress="runs"), "device": dict(pn
         "jpeg_host_420_opt": dict(png_encoder="host", png_compress="runs", frame_format="jpg", jpeg_encoder="host", jpeg_quality=90,
                                   jpeg_subsampling=420, jpeg_huffman="optimized"),
         "jpeg_device_420_opt": dict(png_encoder="host", png_compress="runs", frame_format="jpg", jpeg_encoder="device", jpeg_quality=90,
-                                    jpeg_subsampling=420, jpeg_huffman="optimized")}
+                                    jpeg_subsampling=420, jpeg_huffman="optimized"),
+        # who decodes the .png INPUT frames, under the device_huffman output leg: PIL on the decode threads, or csrc/png_dec.hip inside the pass
+        "pngdec_host": dict(png_encoder="device", png_compress="huffman", png_decoder="host"),
+        "pngdec_device": dict(png_encoder="device", png_compress="huffman", png_decoder="device")}
 
 
 def photo_frames(h, w, n):
@@ -137,7 +140,10 @@ def run_pair(name, cfg, n_frames, reps, encoders=("host",), content="noise"):
         def leg(enc):
             t0 = time.perf_counter()
             with contextlib.redirect_stdout(io.StringIO()):
-                annotate_video.annotate_images(mgr, det, d_in, d_out, names, cfg["resize"][0], cfg["resize"][1], **LEGS[enc])
+                try:
+                    annotate_video.annotate_images(mgr, det, d_in, d_out, names, cfg["resize"][0], cfg["resize"][1], **LEGS[enc])
+                finally:
+                    entry.set_png_decoder(None)                 # (the option is process-wide: the next leg starts from the default)
             return time.perf_counter() - t0
 
         for enc in encoders:                                        # warm-up: captures
