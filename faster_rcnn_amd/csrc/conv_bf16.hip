@@ -984,9 +984,14 @@ __global__ void k_avgpool_bf16_f32_v8(const __bf16* x, int n, int hw, int C, int
     }
 }
 
-// RoiResizeConv on a bf16 feature map (custom_layers.py:35-56): f32 lerp, bf16 output
+// RoiResizeConv on a bf16 feature map (custom_layers.py:35-56): f32 lerp, bf16 output.  Contraction is off in these two kernels (the
+// rest of this file keeps the default): the result is the round-to-nearest-even of what roi.hip's f32 kernel gives on the widened map,
+// bit for bit -- what the oracle and tests/vgg_bf16_ref.py model.  Contracted, fx - lx became fma(px, sx, -lx): a fraction taken from
+// the UNROUNDED product, up to an ulp of fx away from TF's, and some elements landed on the neighbouring bf16 value
+// (tests/test_roi_kernels_gpu.py, docs/ROI_KERNEL_PARITY.md).
 __global__ void __launch_bounds__(256) k_roi_fwd_bf16(const __bf16* feat, int rows, int cols, int C, const float4* rois, int pool,
                                                       const float* fill, int relu, int pos_major, __bf16* out) {
+#pragma clang fp contract(off)
     const int pix = blockIdx.x;
     const int px = pix % pool, py = (pix / pool) % pool, r = pix / (pool * pool);
     const size_t orow = pos_major ? (size_t)(py * pool + px) * (gridDim.x / (pool * pool)) + r : (size_t)pix;
@@ -1024,6 +1029,7 @@ typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
 __global__ void __launch_bounds__(256) k_roi_fwd_bf16_batch(const __bf16* feat, int rows, int cols, int C, const float4* rois, int n_per_img, int pool,
                                                             const float* fill, int relu, int pos_major, __bf16* out) {
+#pragma clang fp contract(off)
     const int pix = blockIdx.x;
     const int px = pix % pool, py = (pix / pool) % pool, r = pix / (pool * pool);
     const size_t orow = pos_major ? (size_t)(py * pool + px) * (gridDim.x / (pool * pool)) + r : (size_t)pix;
