@@ -250,6 +250,30 @@ class PngDecBatchItem(ctypes.Structure):
     _fields_ = [("plan", PngDecPlan), ("file_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("ws_off", ctypes.c_uint64)]
 
 
+PNG_DEC_FULL_VERSION = 1        # include/ext/frcnn_hip_png_dec_full.h FRCNN_PNG_DEC_FULL_VERSION
+PNG_DEC_FULL_PLTE_BYTES = 768   # ... FRCNN_PNG_DEC_FULL_PLTE_BYTES: the staged palette of a colour-type-3 file
+PNG_DEC_FULL_SIGNATURES = {
+    "frcnn_png_dec_full_version": (I, []),
+    "frcnn_png_dec_full_plan": (I, [P, c_size_t, P]),
+    "frcnn_png_dec_full_spans": (I, [P, c_size_t, P, P, c_size_t]),
+    "frcnn_png_dec_full_workspace_bytes": (c_size_t, [P]),
+    "frcnn_png_dec_full_batch_layout": (c_size_t, [P, I, P]),
+    "frcnn_png_decode_full_batch_u8": (I, [P, P, I, P, c_size_t, I, P, c_size_t, P, P, c_size_t, P]),
+}
+
+
+class PngDecFullPlan(ctypes.Structure):
+    """frcnn_png_dec_full_plan_t (include/ext/frcnn_hip_png_dec_full.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("h", "w", "colour_type", "bit_depth", "interlace")] + \
+               [(k, ctypes.c_uint32) for k in ("file_len", "idat_off", "idat_count", "stream_len", "inflated_len", "plte_off", "plte_entries")]
+
+
+class PngDecFullBatchItem(ctypes.Structure):
+    """frcnn_png_dec_full_batch_item_t (include/ext/frcnn_hip_png_dec_full.h)."""
+    _fields_ = [("plan", PngDecFullPlan), ("file_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("ws_off", ctypes.c_uint64),
+                ("plte_off", ctypes.c_uint64)]
+
+
 class JpegDecPlan(ctypes.Structure):
     """frcnn_jpeg_dec_plan_t (include/ext/frcnn_hip_jpeg_dec.h)."""
     _fields_ = [(k, ctypes.c_int32) for k in ("h", "w", "components", "hs", "vs", "mcus_x", "mcus_y", "blocks_per_mcu")] + \
@@ -353,6 +377,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in PNG_DEC_FULL_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_png_dec_full_version() != PNG_DEC_FULL_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_png_dec_full_version()} of the PNG decoder's full-format extension, this "
+                         f"binding {PNG_DEC_FULL_VERSION} (include/ext/frcnn_hip_png_dec_full.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_png_dec_version() != PNG_DEC_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_png_dec_version()} of the PNG decoder extension, this binding "
                          f"{PNG_DEC_VERSION} (include/ext/frcnn_hip_png_dec.h): rebuild with `python -m faster_rcnn_amd.build`")

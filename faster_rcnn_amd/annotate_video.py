@@ -264,12 +264,12 @@ JPEG_SUFFIXES = (".jpg", ".jpeg")
 JPEG_DECODERS = ("host", "device")
 
 
-PNG_DECODERS = ("host", "device")
+PNG_DECODERS = ("host", "device", "device_full")
 
 
 def frame_filenames(input_dir, jpeg_decoder="host", png_decoder="host"):
     """``png_filenames`` and, with ``jpeg_decoder`` = "device", the ``*.jpg`` / ``*.jpeg`` names too: the input frames, sorted.
-    ``png_decoder`` ("host" / "device": who decodes the ``*.png`` frames) is checked and changes no name."""
+    ``png_decoder`` ("host" / "device" / "device_full": who decodes the ``*.png`` frames) is checked and changes no name."""
     from .feed import jpeg_decoder_option, png_decoder_option
     png_decoder_option(png_decoder, "png_decoder")
     if jpeg_decoder_option(jpeg_decoder, "jpeg_decoder") != "device":
@@ -279,7 +279,7 @@ def frame_filenames(input_dir, jpeg_decoder="host", png_decoder="host"):
 
 class _FileFrame:
     """A .jpg or .png input frame the device decodes: the file's bytes and the size its header states (entry.DetectionEntry.host_pixels
-    asks ``raw_file()``); ``raw_rgb`` decodes on the host for whoever still wants pixels.  ``png_planned``: what feed.plan_png made of
+    asks ``raw_file()``); ``raw_rgb`` decodes on the host for whoever still wants pixels.  ``png_planned``: what feed.plan_png (or, under "device_full", feed.plan_png_full) made of
     a .png file on the decode thread (its zlib stream and plan), so that ``host_pixels`` does not parse it again."""
 
     def __init__(self, data, path, file_size, width=None, height=None, png_planned=None):
@@ -344,7 +344,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     None = ``default_jpeg_subsampling()`` / ``default_jpeg_huffman()``.
     ``jpeg_decoder``: "host" or "device": who decodes ``.jpg`` INPUT frames the device decoder supports (captured path only); None =
     what ``entry.jpeg_decoder()`` says (FRCNN_ENTRY_JPEG_DECODER, default "host").
-    ``png_decoder``: "host" or "device": who decodes ``.png`` INPUT frames the device decoder supports (captured path only; the decode
+    ``png_decoder``: "host", "device" or "device_full" (csrc/png_dec_full.hip: palette, 1/2/4/16-bit, grey + alpha and Adam7 files too):
+    who decodes ``.png`` INPUT frames the device decoder supports (captured path only; the decode
     threads then only read the file and check its chunks); None = what ``entry.png_decoder()`` says (FRCNN_ENTRY_PNG_DECODER, default "host")."""
     from concurrent.futures import ThreadPoolExecutor
     if jpeg_decoder is not None:
@@ -352,7 +353,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     if png_decoder is not None:
         entry.set_png_decoder(png_decoder)
     device_decode = entry.jpeg_decoder() == "device"
-    device_png = entry.png_decoder() == "device"
+    device_png = entry.png_decoder()                          # "host", "device" or "device_full"
     png_encoder, png_compress = png_options(png_encoder, png_compress)
     frame_format, jpeg_encoder, jpeg_quality = jpeg_options(frame_format, jpeg_encoder, jpeg_quality, png_encoder, png_compress)
     jpeg_subsampling, jpeg_huffman = jpeg_size_options(frame_format, jpeg_subsampling, jpeg_huffman)
@@ -398,11 +399,12 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
                 frame = _FileFrame(data, path, (int(plan.h), int(plan.w)))
             except ops.JpegUnsupported:
                 pass                                          # (progressive, CMYK, ...: PIL below)
-        elif device_png and path.lower().endswith(".png"):
-            from .feed import plan_png
+        elif device_png != "host" and path.lower().endswith(".png"):
+            from .feed import plan_png, plan_png_full
             with open(path, "rb") as f:
                 data = f.read()
-            planned = plan_png(data)                          # None: palette, 16-bit, interlaced, ...: PIL below
+            # None: a file the chosen planner refuses ("device": palette, 16-bit, interlaced, ...; "device_full": 16-bit grey, ...): PIL below
+            planned = plan_png_full(data) if device_png == "device_full" else plan_png(data)
             if planned is not None:
                 frame = _FileFrame(data, path, (int(planned[1].h), int(planned[1].w)), png_planned=planned)
         if frame is None:
@@ -502,7 +504,9 @@ def build_parser():
                    help="who decodes .jpg INPUT frames: host (PIL) or device (csrc/jpeg_dec.hip; input_dir's *.jpg / *.jpeg are then "
                         "taken beside its *.png); default: FRCNN_ENTRY_JPEG_DECODER, else host")
     p.add_argument("--png_decoder", dest="png_decoder", choices=PNG_DECODERS, default=None,
-                   help="who decodes .png INPUT frames: host (PIL) or device (csrc/png_dec.hip, for the files its planner takes); "
+                   help="who decodes .png INPUT frames: host (PIL), device (csrc/png_dec.hip: 8-bit grey / RGB / RGBA without interlace) or "
+                        "device_full (csrc/png_dec_full.hip: palette, 1/2/4/16-bit, grey + alpha and Adam7 files too); PIL for the files the "
+                        "chosen planner refuses; "
                         "default: FRCNN_ENTRY_PNG_DECODER, else host")
     p.add_argument("--jpeg_quality", dest="jpeg_quality", type=int, default=None,
                    help="IJG quality of JPEG frames, 1..100 (default %d; needs --frame_format jpg)" % JPEG_QUALITY)

@@ -126,14 +126,15 @@ class JpegFile:
         self.data, self.plan, self.name = data, plan, name
 
 
-# who decodes a file-backed .png frame: "host" (PIL, the default) or "device" (ops.png_decode_batch_u8 in front of the replay, beside the
-# JPEG decoder's call when a pass mixes both; PIL for the files its planner refuses).  FRCNN_ENTRY_PNG_DECODER, or ``set_png_decoder``
-# (annotate_video --png_decoder), which wins.
+# who decodes a file-backed .png frame: "host" (PIL, the default), "device" (ops.png_decode_batch_u8 in front of the replay, beside the
+# JPEG decoder's call when a pass mixes both; PIL for the files its planner refuses) or "device_full" (ops.png_decode_full_batch_u8 in its
+# place: palette, 1/2/4/16-bit, grey + alpha and Adam7 files too; PIL for what ITS planner refuses).  FRCNN_ENTRY_PNG_DECODER, or
+# ``set_png_decoder`` (annotate_video --png_decoder), which wins.
 _PNG_DECODER = None
 
 
 def set_png_decoder(value):
-    """"host" / "device" for every DetectionEntry of the process from now on; None: back to FRCNN_ENTRY_PNG_DECODER."""
+    """"host" / "device" / "device_full" for every DetectionEntry of the process from now on; None: back to FRCNN_ENTRY_PNG_DECODER."""
     global _PNG_DECODER
     from .feed import png_decoder_option
     _PNG_DECODER = None if value is None else png_decoder_option(value, "png_decoder")
@@ -145,8 +146,9 @@ def png_decoder():
 
 
 class PngFile(JpegFile):
-    """A .png frame the device decodes: ``data`` is its zlib stream (the IDAT payloads back to back), ``plan`` a ``_lib.PngDecPlan``.  A
-    JpegFile to everything that only asks for the frame's size (plan.h, plan.w) and stages ``data``."""
+    """A .png frame the device decodes: ``data`` is its zlib stream (the IDAT payloads back to back), ``plan`` a ``_lib.PngDecPlan``;
+    under "device_full" ``plan`` is a ``_lib.PngDecFullPlan`` and a palette file's 768 staged palette bytes follow the stream in ``data``.
+    A JpegFile to everything that only asks for the frame's size (plan.h, plan.w) and stages ``data``."""
     __slots__ = ()
 CANVAS_GRANULE = int(os.environ.get("FRCNN_ENTRY_CANVAS_GRANULE", "32"))
 CANVAS_MIN_GEOMETRIES = int(os.environ.get("FRCNN_ENTRY_CANVAS_MIN", "4"))
@@ -284,7 +286,7 @@ class _Slot:
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
-                 "jpg_count", "png_items")
+                 "jpg_count", "png_items", "png_full")
 
     def __init__(self):
         for name in self.__slots__:
@@ -653,14 +655,15 @@ class DetectionEntry:
         Returns (array, H, W, src or None, flip)."""
         if self.device_preprocess and _declares(image, "raw") and _declares(image, "height"):
             H, W, flip = int(image.height), int(image.width), bool(getattr(image, "flipped", False))
-            jpeg_dev, png_dev = jpeg_decoder() == "device", png_decoder() == "device"
+            jpeg_dev, png_dev = jpeg_decoder() == "device", png_decoder()
+            png_dev = "full" if png_dev == "device_full" else png_dev == "device"
             if RGB_UPLOAD and (jpeg_dev or png_dev):
                 from . import feed
                 # None: in-memory pixels, or a file the device decoders do not take
-                planned = feed.plan_entry_file(image, jpeg=jpeg_dev, png=True) if png_dev else feed.plan_file(image)
+                planned = feed.plan_entry_file(image, jpeg=jpeg_dev, png=png_dev) if png_dev else feed.plan_file(image)
                 if planned is not None:
                     data, plan = planned
-                    kind = PngFile if isinstance(plan, _lib.PngDecPlan) else JpegFile
+                    kind = PngFile if isinstance(plan, (_lib.PngDecPlan, _lib.PngDecFullPlan)) else JpegFile
                     return kind(data, plan, getattr(image, "_image_path", None) or str(getattr(image, "name", "?"))), H, W, \
                         (int(plan.h), int(plan.w)), 2 | int(flip)
             rgb = getattr(image, "raw_rgb", None) if RGB_UPLOAD else None
@@ -898,8 +901,8 @@ class DetectionEntry:
         B = s.batch
         files.sort(key=lambda t: isinstance(t[1], PngFile))         # (in place, stable: the .jpg items first, then the .png items)
         nj = sum(1 for _, f in files if not isinstance(f, PngFile))
-        item, pitem = ctypes.sizeof(_lib.JpegDecBatchItem), ctypes.sizeof(_lib.PngDecBatchItem)
-        table = (B * (item + pitem) + 255) // 256 * 256             # [B JPEG items | B PNG items]
+        item, pitem = ctypes.sizeof(_lib.JpegDecBatchItem), ctypes.sizeof(_lib.PngDecFullBatchItem)
+        table = (B * (item + pitem) + 255) // 256 * 256             # [B JPEG items | B PNG items], room for the larger kind of PNG item
         at, seen, file_off = 0, {}, []
         for _, f in files:
             if id(f) not in seen:
@@ -912,13 +915,19 @@ class DetectionEntry:
             s.jpg_area = torch.empty(size, dtype=torch.uint8, device="cuda")
             s.jpg_dev = s.jpg_area[table:]                           # the file area; the table lies in front of it
         plans = [f.plan for _, f in files]
+        # one kind of PNG item per pass: with a full-format plan among them (png_decoder "device_full") revision-1 plans, which a pass
+        # can only hold when the setting changed under way, are restated as full-format ones
+        s.png_full = any(isinstance(p, _lib.PngDecFullPlan) for p in plans[nj:])
+        if s.png_full:
+            plans[nj:] = [ops.png_dec_full_of(p) if isinstance(p, _lib.PngDecPlan) else p for p in plans[nj:]]
+        pitem = ctypes.sizeof(_lib.PngDecFullBatchItem if s.png_full else _lib.PngDecBatchItem)
         ws_off, need = [], 0
         for k in range(0, nj, _lib.JPEG_DEC_BATCH_MAX):              # (a call takes JPEG_DEC_BATCH_MAX items: its regions behind the last call's)
             offs, total = ops.jpeg_dec_batch_layout(plans[k:min(nj, k + _lib.JPEG_DEC_BATCH_MAX)])
             ws_off += [need + o for o in offs]
             need += total
         for k in range(nj, len(plans), _lib.PNG_DEC_BATCH_MAX):
-            offs, total = ops.png_dec_batch_layout(plans[k:k + _lib.PNG_DEC_BATCH_MAX])
+            offs, total = (ops.png_dec_full_batch_layout if s.png_full else ops.png_dec_batch_layout)(plans[k:k + _lib.PNG_DEC_BATCH_MAX])
             ws_off += [need + o for o in offs]
             need += total
         if s.jpg_ws is None or s.jpg_ws.numel() < need:
@@ -928,7 +937,11 @@ class DetectionEntry:
             s.jpg_status_pin = torch.zeros(B, dtype=torch.int32).pin_memory()
         out_off = [i * s.seg for i, _ in files]
         s.jpg_items = ops.jpeg_batch_items(plans[:nj], file_off[:nj], out_off[:nj], ws_off[:nj])
-        s.png_items = ops.png_batch_items(plans[nj:], file_off[nj:], out_off[nj:], ws_off[nj:])
+        if s.png_full:                                              # (a palette lies behind its stream in the file's staged bytes)
+            s.png_items = ops.png_full_batch_items(plans[nj:], file_off[nj:], out_off[nj:], ws_off[nj:],
+                                                   [o + int(p.stream_len) for o, p in zip(file_off[nj:], plans[nj:])])
+        else:
+            s.png_items = ops.png_batch_items(plans[nj:], file_off[nj:], out_off[nj:], ws_off[nj:])
         s.jpg_count = nj
         s.jpg_used = table + at
         s.jpg_names = [f.name for _, f in files]                    # (item k's status word is word k: the .jpg items, then the .png items)
@@ -949,11 +962,12 @@ class DetectionEntry:
         if batched or len(files) > nj:                              # (the .png items are always decoded as a batch)
             s.jpg_area[:s.jpg_used].copy_(s.jpg_pin[:s.jpg_used], non_blocking=True)
         s.jpg_status.zero_()
-        pitem, ptable = ctypes.sizeof(_lib.PngDecBatchItem), s.batch * item
+        kind, decode = (_lib.PngDecFullBatchItem, ops.png_decode_full_batch_u8) if s.png_full else (_lib.PngDecBatchItem, ops.png_decode_batch_u8)
+        pitem, ptable = ctypes.sizeof(kind), s.batch * item
         for k in range(0, len(files) - nj, _lib.PNG_DEC_BATCH_MAX):
             n = min(_lib.PNG_DEC_BATCH_MAX, len(files) - nj - k)
-            part = (_lib.PngDecBatchItem * n).from_buffer(s.png_items, k * pitem)
-            ops.png_decode_batch_u8(s.jpg_dev, part, s.io_dev, status=s.jpg_status[nj + k:nj + k + n], workspace=s.jpg_ws,
+            part = (kind * n).from_buffer(s.png_items, k * pitem)
+            decode(s.jpg_dev, part, s.io_dev, status=s.jpg_status[nj + k:nj + k + n], workspace=s.jpg_ws,
                                     items_dev=s.jpg_area[ptable + k * pitem:ptable + (k + n) * pitem])
         if batched:
             for k in range(0, nj, _lib.JPEG_DEC_BATCH_MAX):

@@ -47,12 +47,17 @@ def plan_file(image):
         return None
 
 
-PNG_DECODERS = ("host", "device")
+PNG_DECODERS = ("host", "device", "device_full")
+
+
+def default_png_decoder():
+    """FRCNN_FEED_PNG_DECODER: who decodes a file-backed .png frame for ``device_image`` (read at every call: a test may set it)."""
+    return png_decoder_option(os.environ.get("FRCNN_FEED_PNG_DECODER"), "FRCNN_FEED_PNG_DECODER")
 
 
 def png_decoder_option(value, what):
     """A PNG decoder setting ("host": PIL, the default; "device": ops.png_decode_batch_u8 for the files its planner supports, PIL for the
-    rest) checked: -> the value, ValueError naming ``what`` (an environment variable, an option) for anything else."""
+    rest; "device_full": ops.png_decode_full_batch_u8, whose planner also takes palette, 1/2/4/16-bit, grey + alpha and Adam7 files) checked: -> the value, ValueError naming ``what`` (an environment variable, an option) for anything else."""
     value = "host" if value is None or value == "" else value
     if value not in PNG_DECODERS:
         raise ValueError("%s=%r: one of %s" % (what, value, ", ".join(PNG_DECODERS)))
@@ -69,11 +74,24 @@ def plan_png(data):
     return ops.png_dec_stream(data, plan), plan
 
 
+def plan_png_full(data):
+    """``plan_png`` through the full-format planner (ops.png_dec_full_plan) -> (the zlib stream, followed for a palette file by its 768
+    staged palette bytes: item.plte_off = item.file_off + plan.stream_len; its ``PngDecFullPlan``), or None for a file that planner
+    refuses (16-bit grey, a damaged container, ...).  Pure host work."""
+    try:
+        plan = ops.png_dec_full_plan(data)
+    except ops.PngUnsupported:
+        return None
+    stream, palette = ops.png_dec_full_stream(data, plan)
+    return stream + palette, plan
+
+
 def plan_entry_file(image, jpeg=True, png=False):
     """``plan_file`` for the detection entry, which may decode either kind on the device: a file-backed image whose bytes start with
-    the PNG signature is planned by the PNG decoder's planner when ``png`` (-> (its zlib stream, its ``PngDecPlan``); what an
-    ``annotate_video._FileFrame`` planned ahead is taken as it is), any other file by ``plan_file`` when ``jpeg``.  None: the caller
-    takes the host path.  (``device_image``, the training feed, keeps to ``plan_file``: it decodes .png files on the host.)"""
+    the PNG signature is planned by the PNG decoder's planner when ``png`` (-> (its zlib stream, its ``PngDecPlan``); ``png="full"``: by
+    the full-format planner, -> ``plan_png_full``'s pair; what an ``annotate_video._FileFrame`` planned ahead is taken as it is), any
+    other file by ``plan_file`` when ``jpeg``.  None: the caller takes the host path.  (``device_image``, the training feed, plans through
+    ``plan_feed_file``.)"""
     if not _declares(image, "raw_file") or getattr(image, "_pixels", None) is not None:
         return None
     data = image.raw_file()
@@ -83,8 +101,42 @@ def plan_entry_file(image, jpeg=True, png=False):
         if not png:
             return None
         planned = getattr(image, "png_planned", None)
-        return planned if planned is not None else plan_png(data)
+        if planned is not None and isinstance(planned[1], ops._lib.PngDecFullPlan) == (png == "full"):
+            return planned
+        return plan_png_full(data) if png == "full" else plan_png(data)
     return plan_file(image) if jpeg else None
+
+
+def plan_feed_file(image):
+    """``plan_file`` for the training feed under its two settings: a file that starts with the PNG signature is planned by the PNG
+    planner FRCNN_FEED_PNG_DECODER names (-> ``plan_png`` / ``plan_png_full``'s pair), any other file by ``plan_file`` when
+    FRCNN_FEED_JPEG_DECODER is "device".  None: in-memory pixels, no ``raw_file``, a setting of "host" for that kind of file, or a file
+    the planner refuses: the caller takes the host path.  Pure host work: a thread may do it ahead."""
+    png, jpeg = default_png_decoder(), default_jpeg_decoder() == "device"
+    if png == "host":
+        return plan_file(image) if jpeg else None
+    if not _declares(image, "raw_file") or getattr(image, "_pixels", None) is not None:
+        return None
+    data = image.raw_file()
+    if data is None:
+        return None
+    if bytes(data[:8]) == ops.PNG_SIGNATURE:
+        return plan_png_full(data) if png == "device_full" else plan_png(data)
+    return plan_file(image) if jpeg else None
+
+
+def _planned_kind(plan):
+    """"png" / "jpeg": which decoder (and which setting) a planned file belongs to."""
+    return "png" if isinstance(plan, (ops._lib.PngDecPlan, ops._lib.PngDecFullPlan)) else "jpeg"
+
+
+def _still_wanted(plan):
+    """Does the setting that was in force when a file was planned ahead still hold?"""
+    if isinstance(plan, ops._lib.PngDecFullPlan):
+        return default_png_decoder() == "device_full"
+    if isinstance(plan, ops._lib.PngDecPlan):
+        return default_png_decoder() == "device"
+    return default_jpeg_decoder() == "device"
 
 
 class _PinRing:
@@ -160,7 +212,7 @@ def decode_ahead(image):
     """Start decoding a file-backed image's pixels on the background thread (device_image picks the result up).  With the device decoder
     the thread reads the file and plans it instead; an unsupported file is decoded there as before."""
     global _DECODER
-    device = default_jpeg_decoder() == "device"
+    device = default_jpeg_decoder() == "device" or default_png_decoder() != "host"
     if not (DECODE_AHEAD and RGB_UPLOAD and hasattr(type(image), "raw_rgb")) or getattr(image, "_pixels", 0) is not None or id(image) in _DECODED:
         return
     if _DECODER is None:
@@ -169,7 +221,7 @@ def decode_ahead(image):
     if len(_DECODED) > 8:
         _DECODED.clear()                                      # (frames asked for and never taken: forget them)
     def work():
-        planned = plan_file(image) if device else None
+        planned = plan_feed_file(image) if device else None
         return planned if planned is not None else image.raw_rgb
     _DECODED[id(image)] = (image, _DECODER.submit(work))
 
@@ -179,17 +231,16 @@ def _raw_rgb(image):
     ent = _DECODED.pop(id(image), None)
     if ent is not None and ent[0] is image:
         got = ent[1].result()
-        if not isinstance(got, tuple) or default_jpeg_decoder() == "device":
+        if not isinstance(got, tuple) or _still_wanted(got[1]):
             return got
         return image.raw_rgb                                  # (planned ahead, and the setting changed since)
-    if default_jpeg_decoder() == "device":
-        planned = plan_file(image)
-        if planned is not None:
-            return planned
+    planned = plan_feed_file(image)
+    if planned is not None:
+        return planned
     return image.raw_rgb
 
 
-# Device decodes whose status word has not been looked at: (pinned int32 [1], event behind its copy, file name).  ``check_decodes`` is
+# Device decodes whose status word has not been looked at: (pinned int32 [1], event behind its copy, file name, "jpeg" / "png").  ``check_decodes`` is
 # called where a training manager has just synchronised for its own counts: it reads the words whose copy has FINISHED and waits for none.
 _DECODE_STATUS = []
 _STATUS_PIN, _STATUS_AT = None, 0
@@ -197,8 +248,12 @@ _STATUS_PIN, _STATUS_AT = None, 0
 
 def _decode_on_device(data, plan, name):
     """The file decoded on the current stream -> (h, w, 3) uint8 R,G,B device tensor; its status word is queued for check_decodes."""
-    file_dev = upload(np.frombuffer(data, dtype=np.uint8))
-    rgb, status = ops.jpeg_decode_u8(file_dev, plan)
+    kind = _planned_kind(plan)
+    if kind == "png":
+        rgb, status = _decode_png_on_device(data, plan)
+    else:
+        file_dev = upload(np.frombuffer(data, dtype=np.uint8))
+        rgb, status = ops.jpeg_decode_u8(file_dev, plan)
     global _STATUS_PIN, _STATUS_AT
     if _STATUS_PIN is None:
         _STATUS_PIN = torch.zeros(64, dtype=torch.int32).pin_memory()
@@ -209,8 +264,29 @@ def _decode_on_device(data, plan, name):
     word.copy_(status, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record()
-    _DECODE_STATUS.append((word, ev, name))
+    _DECODE_STATUS.append((word, ev, name, kind))
     return rgb
+
+
+def _decode_png_on_device(data, plan):
+    """A planned .png file (``plan_png`` / ``plan_png_full``'s pair) as a batch of one: ONE upload through the pin ring of [the item |
+    the zlib stream | the palette], the decode on the current stream -> ((h, w, 3) uint8 R,G,B device tensor, its status word [1])."""
+    import ctypes
+    full = isinstance(plan, ops._lib.PngDecFullPlan)
+    head = (ctypes.sizeof(ops._lib.PngDecFullBatchItem if full else ops._lib.PngDecBatchItem) + 15) // 16 * 16
+    offs, _ = (ops.png_dec_full_batch_layout if full else ops.png_dec_batch_layout)([plan])
+    if full:
+        items = ops.png_full_batch_items([plan], [0], [0], offs, [int(plan.stream_len)])
+    else:
+        items = ops.png_batch_items([plan], [0], [0], offs)
+    staged = np.empty(head + len(data), np.uint8)
+    staged[:ctypes.sizeof(items)] = np.frombuffer(items, dtype=np.uint8)
+    staged[head:] = np.frombuffer(data, dtype=np.uint8)
+    dev = upload(staged)
+    rgb = torch.empty((int(plan.h), int(plan.w), 3), dtype=torch.uint8, device="cuda")
+    decode = ops.png_decode_full_batch_u8 if full else ops.png_decode_batch_u8
+    status = decode(dev[head:], items, rgb.view(-1), status=torch.zeros(1, dtype=torch.int32, device="cuda"), items_dev=dev[:head])
+    return rgb, status
 
 
 def check_decodes():
@@ -218,22 +294,25 @@ def check_decodes():
     if not _DECODE_STATUS:
         return
     waiting, bad = [], None
-    for word, ev, name in _DECODE_STATUS:
+    for word, ev, name, kind in _DECODE_STATUS:
         if not ev.query():
-            waiting.append((word, ev, name))
+            waiting.append((word, ev, name, kind))
         elif int(word[0]) and bad is None:
-            bad = (name, int(word[0]))
+            bad = (name, int(word[0]), kind)
     _DECODE_STATUS[:] = waiting
+    if bad is not None and bad[2] == "png":
+        raise ops._lib.FrcnnError("device PNG decoder: %s is damaged (status %d: FRCNN_PNG_DEC_* in include/ext/frcnn_hip_png_dec.h); "
+                                  "decode it on the host or repair the file" % bad[:2])
     if bad is not None:
         raise ops._lib.FrcnnError("device JPEG decoder: %s is damaged (status %d: FRCNN_JPEG_DEC_* in include/ext/frcnn_hip_jpeg_dec.h); "
-                                  "decode it on the host or repair the file" % bad)
+                                  "decode it on the host or repair the file" % bad[:2])
 
 
 def device_image(image, preprocess_func):
     """(1,H,W,3) float32 device tensor == float32(np.expand_dims(preprocess_func(image.data), 0)), on the current stream."""
     if device_preprocess(preprocess_func) and _declares(image, "raw") and _declares(image, "height"):
         H, W, flip = int(image.height), int(image.width), bool(getattr(image, "flipped", False))
-        # a file-backed frame goes up in the JPEG decoder's channel order; the device resize (to its own size when none is needed: a
+        # a file-backed frame goes up in the decoder's channel order (R,G,B: PIL's, the device JPEG decoder's and the device PNG decoders'); the device resize (to its own size when none is needed: a
         # copy) writes B, G, R -- the host's channel reversal cost as much as half the decode (round 6, as entry.DetectionEntry)
         rgb = _raw_rgb(image) if (RGB_UPLOAD and hasattr(type(image), "raw_rgb")) else None
         if isinstance(rgb, tuple):                               # (file bytes, plan): decoded on the device into what the resize reads

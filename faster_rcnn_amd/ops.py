@@ -1495,6 +1495,128 @@ def png_decode_u8(file_bytes, bgr=False):
     return out
 
 
+# ---- the full-format PNG decoder (include/ext/frcnn_hip_png_dec_full.h, csrc/png_dec_full.hip): palette, 1/2/4/16-bit, grey + alpha, Adam7
+PNG_DEC_FULL_PLTE_BYTES = _lib.PNG_DEC_FULL_PLTE_BYTES
+
+
+def png_dec_full_plan(data):
+    """``png_dec_plan`` for the full-format decoder (frcnn_png_dec_full_plan) -> a ``_lib.PngDecFullPlan``: size, colour type, bit depth,
+    interlace, where the IDATs and the PLTE lie, the bytes of the zlib stream and of what it inflates to.  ``PngUnsupported`` with the
+    reason for a file outside ITS supported set (16-bit grey, a palette file without a usable PLTE, a damaged container, ...).  A pure
+    host call."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise _lib.FrcnnError("png_dec_full_plan: the file's bytes, got %s" % type(data).__name__)
+    data = bytes(data)
+    plan = _lib.PngDecFullPlan()
+    lib = _lib.load()
+    code = lib.frcnn_png_dec_full_plan(data, len(data), ctypes.byref(plan))
+    if code == _lib.E_UNSUPPORTED:
+        raise PngUnsupported((lib.frcnn_last_error() or b"").decode())
+    _lib.check(code, "frcnn_png_dec_full_plan")
+    return plan
+
+
+def png_dec_full_spans(data, plan):
+    """[(offset, length)] of the IDAT payloads of the file ``plan`` was made of (frcnn_png_dec_full_spans), in file order."""
+    data = bytes(data)
+    n = int(plan.idat_count)
+    spans = (ctypes.c_uint32 * (2 * max(n, 1)))()
+    _lib.call("frcnn_png_dec_full_spans", data, len(data), ctypes.byref(plan), spans, n)
+    return [(int(spans[2 * k]), int(spans[2 * k + 1])) for k in range(n)]
+
+
+def png_dec_full_stream(data, plan):
+    """What goes to the device -> (the file's zlib stream: its IDAT payloads back to back, ``plan.stream_len`` bytes; its palette: the
+    PLTE entries zero-padded to PNG_DEC_FULL_PLTE_BYTES = 768 bytes for a colour-type-3 file, b"" for any other)."""
+    data = bytes(data)
+    spans = png_dec_full_spans(data, plan)
+    stream = data[spans[0][0]:spans[0][0] + spans[0][1]] if len(spans) == 1 else b"".join(data[o:o + n] for o, n in spans)
+    if int(plan.colour_type) != 3:
+        return stream, b""
+    palette = data[int(plan.plte_off):int(plan.plte_off) + 3 * int(plan.plte_entries)]
+    return stream, palette + bytes(PNG_DEC_FULL_PLTE_BYTES - len(palette))
+
+
+def png_dec_full_of(plan):
+    """The ``PngDecFullPlan`` that says what a revision-1 ``PngDecPlan`` says: depth 8, no interlace, no palette."""
+    full = _lib.PngDecFullPlan()
+    full.h, full.w, full.colour_type, full.bit_depth, full.interlace = plan.h, plan.w, {1: 0, 3: 2, 4: 6}[int(plan.channels)], 8, 0
+    full.file_len, full.idat_off, full.idat_count = plan.file_len, plan.idat_off, plan.idat_count
+    full.stream_len, full.inflated_len = plan.stream_len, plan.inflated_len
+    return full
+
+
+def png_dec_full_workspace_bytes(plan):
+    """Bytes of device workspace a file of ``plan`` needs (frcnn_png_dec_full_workspace_bytes): its inflated bytes."""
+    n = int(_lib.load().frcnn_png_dec_full_workspace_bytes(ctypes.byref(plan)))
+    if n == 0:
+        raise _lib.FrcnnError("png_dec_full_workspace_bytes: not a plan that png_dec_full_plan made")
+    return n
+
+
+def png_dec_full_batch_layout(plans):
+    """Workspace regions for a batch of plans laid back to back (frcnn_png_dec_full_batch_layout) -> (ws_off, total).  A pure host call."""
+    n = len(plans)
+    if not 1 <= n <= _lib.PNG_DEC_BATCH_MAX:
+        raise _lib.FrcnnError(f"png_dec_full_batch_layout: {n} plans, 1..{_lib.PNG_DEC_BATCH_MAX} go into one batch")
+    arr = (_lib.PngDecFullPlan * n)(*plans)
+    offs = (ctypes.c_uint64 * n)()
+    total = int(_lib.load().frcnn_png_dec_full_batch_layout(arr, n, offs))
+    if total == 0:
+        raise _lib.FrcnnError("png_dec_full_batch_layout: not plans that png_dec_full_plan made")
+    return [int(o) for o in offs], total
+
+
+def png_full_batch_items(plans, file_off, out_off, ws_off, plte_off):
+    """The item table of a batch (``_lib.PngDecFullBatchItem`` x n, a ctypes array: ``bytes(table)`` is what goes to the device);
+    ``file_off`` / ``plte_off``: where each file's staged zlib stream and its 768 palette bytes (``png_dec_full_stream``) lie; the
+    ``plte_off`` of a file that is not colour type 3 is not looked at."""
+    items = (_lib.PngDecFullBatchItem * len(plans))()
+    for it, p, f, o, w, q in zip(items, plans, file_off, out_off, ws_off, plte_off):
+        it.plan, it.file_off, it.out_off, it.ws_off, it.plte_off = p, int(f), int(o), int(w), int(q)
+    return items
+
+
+def png_decode_full_batch_u8(files, items, out, bgr=False, status=None, workspace=None, items_dev=None):
+    """``png_decode_batch_u8`` for the full-format decoder, THREE launches (frcnn_png_decode_full_batch_u8): ``files`` holds every file's
+    zlib stream and every palette file's 768 palette bytes, ``items`` the table (``png_full_batch_items``) -> status: int32 [n], per file
+    0 or _lib.PNG_DEC_* bits ORed in (sticky).  ``items_dev``, ``status`` and ``workspace`` as there."""
+    _require_gpu()
+    n = len(items)
+    if not isinstance(items, ctypes.Array) or items._type_ is not _lib.PngDecFullBatchItem:
+        raise _lib.FrcnnError("png_decode_full_batch_u8: items must be a table made by png_full_batch_items")
+    if items_dev is None:
+        items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).cuda()
+    if status is None:
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
+    if workspace is None:
+        workspace = _ws(max((int(it.ws_off) + png_dec_full_workspace_bytes(it.plan) for it in items), default=0))
+    for name, t, dt in (("files", files, torch.uint8), ("out", out, torch.uint8), ("status", status, torch.int32),
+                        ("workspace", workspace, torch.uint8), ("items_dev", items_dev, torch.uint8)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise _lib.FrcnnError(f"png_decode_full_batch_u8: {name} must be a contiguous {dt} device tensor")
+    if items_dev.numel() < ctypes.sizeof(items) or status.numel() < n:
+        raise _lib.FrcnnError(f"png_decode_full_batch_u8: items_dev of {items_dev.numel()} bytes / status of {status.numel()} words for {n} items")
+    _lib.call("frcnn_png_decode_full_batch_u8", ctypes.addressof(items), _p(items_dev), n, _p(files), files.numel(), 1 if bgr else 0,
+              _p(out), out.numel(), _p(status), _p(workspace), workspace.numel(), _stream())
+    return status
+
+
+def png_decode_full_u8(file_bytes, bgr=False):
+    """``png_decode_u8`` through the full-format decoder: palette, 1/2/4/16-bit, grey + alpha and Adam7 files too."""
+    _require_gpu()
+    data = bytes(file_bytes)
+    plan = png_dec_full_plan(data)
+    stream, palette = png_dec_full_stream(data, plan)
+    files = torch.frombuffer(bytearray(stream + palette), dtype=torch.uint8).cuda()
+    out = torch.empty((int(plan.h), int(plan.w), 3), dtype=torch.uint8, device="cuda")
+    status = png_decode_full_batch_u8(files, png_full_batch_items([plan], [0], [0], [0], [len(stream)]), out.view(-1), bgr=bgr)
+    word = int(status.cpu()[0])
+    if word:
+        raise _lib.FrcnnError("png_decode_full_u8: the file is damaged (status %d: FRCNN_PNG_DEC_* in include/ext/frcnn_hip_png_dec.h)" % word)
+    return out
+
+
 def split_detections(packed, rows=None):
     """Views (n_dets, det_bbox, det_cls, det_prob, det_roi) into a `det_packed` buffer (device tensor or its host copy)."""
     rows = (packed.numel() - 4) // 7 if rows is None else rows

@@ -17,7 +17,7 @@ per frame) instead of uniform noise: noise does not compress, so bytes per frame
 ``subsampling=2, optimize=True``; the device encoder's csrc/jpeg_opt.hip); every leg reports its bytes per frame.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
-                                     [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device] [--content noise|photo]
+                                     [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
 """
 import argparse
 import contextlib
@@ -89,7 +89,9 @@ LEGS = {"host": dict(png_encoder="host", png_compress="runs"), "device": dict(pn
                                     jpeg_subsampling=420, jpeg_huffman="optimized"),
         # who decodes the .png INPUT frames, under the device_huffman output leg: PIL on the decode threads, or csrc/png_dec.hip inside the pass
         "pngdec_host": dict(png_encoder="device", png_compress="huffman", png_decoder="host"),
-        "pngdec_device": dict(png_encoder="device", png_compress="huffman", png_decoder="device")}
+        "pngdec_device": dict(png_encoder="device", png_compress="huffman", png_decoder="device"),
+        # ... or csrc/png_dec_full.hip (the same files here: the leg measures what the third launch and the wider planner cost on them)
+        "pngdec_device_full": dict(png_encoder="device", png_compress="huffman", png_decoder="device_full")}
 
 
 def photo_frames(h, w, n):
