@@ -279,7 +279,7 @@ def frame_filenames(input_dir, jpeg_decoder="host", png_decoder="host"):
 
 class _FileFrame:
     """A .jpg or .png input frame the device decodes: the file's bytes and the size its header states (entry.DetectionEntry.host_pixels
-    asks ``raw_file()``); ``raw_rgb`` decodes on the host for whoever still wants pixels.  ``png_planned``: what feed.plan_png (or, under "device_full", feed.plan_png_full) made of
+    asks ``raw_file()``); ``raw_rgb`` decodes on the host for whoever still wants pixels.  ``png_planned``: what feed.plan_png made, under the PNG decoder setting in force, of
     a .png file on the decode thread (its zlib stream and plan), so that ``host_pixels`` does not parse it again."""
 
     def __init__(self, data, path, file_size, width=None, height=None, png_planned=None):
@@ -400,11 +400,11 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             except ops.JpegUnsupported:
                 pass                                          # (progressive, CMYK, ...: PIL below)
         elif device_png != "host" and path.lower().endswith(".png"):
-            from .feed import plan_png, plan_png_full
+            from .feed import plan_png
             with open(path, "rb") as f:
                 data = f.read()
             # None: a file the chosen planner refuses ("device": palette, 16-bit, interlaced, ...; "device_full": 16-bit grey, ...): PIL below
-            planned = plan_png_full(data) if device_png == "device_full" else plan_png(data)
+            planned = plan_png(data, device_png)
             if planned is not None:
                 frame = _FileFrame(data, path, (int(planned[1].h), int(planned[1].w)), png_planned=planned)
         if frame is None:

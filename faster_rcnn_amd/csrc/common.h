@@ -58,4 +58,19 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// (also on the device: the batched decoders' kernels find an item's arrays from the plan they read)
+__host__ __device__ inline size_t align16(size_t v) { return (v + 15) / 16 * 16; }
+
+// The batched decoders' argument checks (jpeg_dec.hip, png_dec_host.h): item ``item`` owns bytes [lo, hi) of a buffer.
+struct Range { unsigned long long lo, hi; int item; };
+
+// -1, or the index of an item of (sorted by lo) ``r`` that reaches into its successor
+inline int range_overlap(Range* r, int n) {
+    for (int i = 1; i < n; ++i)                                // (insertion sort: n <= 64)
+        for (int j = i; j > 0 && r[j].lo < r[j - 1].lo; --j) { const Range t = r[j]; r[j] = r[j - 1]; r[j - 1] = t; }
+    for (int i = 0; i + 1 < n; ++i)
+        if (r[i].hi > r[i + 1].lo) return i;
+    return -1;
+}
+
 }  // namespace frcnn

@@ -53,20 +53,18 @@ __constant__ DecZigzag DEC_ZIGZAG = {{0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 
 struct DecPlanes { uint8_t* p[3]; int pw[3]; };
 struct DecLayout { size_t coef, flags, plane[3], total; int pw[3], ph[3]; };
 
-__host__ __device__ inline size_t dec_align16(size_t v) { return (v + 15) / 16 * 16; }
-
 // (also on the device: a batched kernel finds its item's arrays from the plan it reads)
 __host__ __device__ inline DecLayout dec_layout(const Plan& p) {
     DecLayout l = {};
     size_t at = 0;
-    l.coef = at; at += dec_align16((size_t)p.expected_blocks * 128);
-    l.flags = at; at += dec_align16((size_t)p.expected_blocks);
+    l.coef = at; at += align16((size_t)p.expected_blocks * 128);
+    l.flags = at; at += align16((size_t)p.expected_blocks);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {                               // (constant indices: the device keeps the struct in registers)
         if (c >= p.components) continue;
         l.pw[c] = p.mcus_x * 8 * (c ? 1 : p.hs);
         l.ph[c] = p.mcus_y * 8 * (c ? 1 : p.vs);
-        l.plane[c] = at; at += dec_align16((size_t)l.pw[c] * (size_t)l.ph[c]);
+        l.plane[c] = at; at += align16((size_t)l.pw[c] * (size_t)l.ph[c]);
     }
     l.total = at;
     return l;
@@ -752,19 +750,6 @@ extern "C" size_t frcnn_jpeg_dec_batch_layout(const frcnn_jpeg_dec_plan_t* plans
     return at;
 }
 
-namespace {
-struct DecRange { unsigned long long lo, hi; int item; };
-
-// -1, or the index of an item of (sorted by lo) ``r`` that reaches into its successor
-inline int dec_overlap(DecRange* r, int n) {
-    for (int i = 1; i < n; ++i)                                // (insertion sort: n <= 64)
-        for (int j = i; j > 0 && r[j].lo < r[j - 1].lo; --j) { const DecRange t = r[j]; r[j] = r[j - 1]; r[j - 1] = t; }
-    for (int i = 0; i + 1 < n; ++i)
-        if (r[i].hi > r[i + 1].lo) return i;
-    return -1;
-}
-}  // namespace
-
 extern "C" int frcnn_jpeg_decode_batch_u8(const frcnn_jpeg_dec_batch_item_t* items_host, const frcnn_jpeg_dec_batch_item_t* items_dev, int n,
                                           const uint8_t* files_dev, size_t files_capacity, int bgr, uint8_t* out_dev, size_t out_capacity,
                                           int32_t* status_dev, void* workspace, size_t workspace_capacity, void* stream) {
@@ -773,7 +758,7 @@ extern "C" int frcnn_jpeg_decode_batch_u8(const frcnn_jpeg_dec_batch_item_t* ite
     if (reinterpret_cast<uintptr_t>(workspace) & 15u) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: workspace must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(status_dev) & 3u) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: status_dev must be 4-byte aligned");
     if (reinterpret_cast<uintptr_t>(items_dev) & 7u) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: items_dev must be 8-byte aligned");
-    DecRange outs[FRCNN_JPEG_DEC_BATCH_MAX], regions[FRCNN_JPEG_DEC_BATCH_MAX];
+    Range outs[FRCNN_JPEG_DEC_BATCH_MAX], regions[FRCNN_JPEG_DEC_BATCH_MAX];
     uint32_t lanes = 64, blocks = 1;
     int max_w = 1, max_h = 1;
     for (int i = 0; i < n; ++i) {
@@ -796,9 +781,9 @@ extern "C" int frcnn_jpeg_decode_batch_u8(const frcnn_jpeg_dec_batch_item_t* ite
         max_w = p.w > max_w ? p.w : max_w;
         max_h = p.h > max_h ? p.h : max_h;
     }
-    int k = dec_overlap(outs, n);
+    int k = range_overlap(outs, n);
     if (k >= 0) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: the output ranges of items %d and %d overlap", outs[k].item, outs[k + 1].item);
-    k = dec_overlap(regions, n);
+    k = range_overlap(regions, n);
     if (k >= 0) return fail(FRCNN_E_ARG, "jpeg_decode_batch_u8: the workspace regions of items %d and %d overlap", regions[k].item, regions[k + 1].item);
     hipStream_t s = as_stream(stream);
     uint8_t* ws = static_cast<uint8_t*>(workspace);

@@ -1,8 +1,9 @@
 // What the device PNG decoder's translation units share (png_dec.hip: revision 1 of include/ext/frcnn_hip_png_dec.h; png_dec_full.hip:
 // palette, sub-byte and 16-bit samples, grey + alpha and Adam7, include/ext/frcnn_hip_png_dec_full.h): the parallel inflate of one zlib
-// stream by one workgroup (its description and its bounds argument are at the top of png_dec.hip), the filter predictor, the CRC-32 and
-// the range check of the batch validation.  Everything sits in an unnamed namespace: each translation unit has its own copy, __constant__
-// data included.
+// stream by one workgroup (its description and its bounds argument are at the top of png_dec.hip) with the kernel that runs it for either
+// kind of item, the filter predictor and the CRC-32.  The host half of both decoders (planner, spans, sizes, argument checks) is
+// png_dec_host.h, which includes this file.  Everything sits in an unnamed namespace: each translation unit has its own copy,
+// __constant__ data included.
 #pragma once
 #include "common.h"
 #include "../../include/ext/frcnn_hip_png_dec.h"
@@ -24,8 +25,6 @@ static_assert(PD_WIN_BITS / 8 == FRCNN_PNG_DEC_WINDOW_BYTES, "the header states 
 constexpr uint32_t ST_CODE = FRCNN_PNG_DEC_CODE, ST_BLOCK = FRCNN_PNG_DEC_BLOCK, ST_OVERSUB = FRCNN_PNG_DEC_OVERSUBSCRIBED,
                    ST_DISTANCE = FRCNN_PNG_DEC_DISTANCE, ST_OVERRUN = FRCNN_PNG_DEC_OVERRUN, ST_UNDERRUN = FRCNN_PNG_DEC_UNDERRUN,
                    ST_ADLER = FRCNN_PNG_DEC_ADLER, ST_FILTER = FRCNN_PNG_DEC_FILTER;
-
-__host__ __device__ inline size_t pd_align16(size_t v) { return (v + 15) / 16 * 16; }
 
 // --------------------------------------------------------------------------------------------------------------------- the codes
 struct PdHuff {
@@ -429,6 +428,14 @@ __device__ __forceinline__ void pd_inflate_body(const uint8_t* stream, uint32_t 
     }
 }
 
+// grid.x = item, for either kind of item.  The item lies in device memory at an address that is uniform over the workgroup and that
+// nothing written here aliases.
+template <class I>
+__global__ void __launch_bounds__(PD_THREADS) k_png_dec_inflate(const uint8_t* files, const I* __restrict__ items, uint8_t* workspace, int32_t* status) {
+    const I& it = items[blockIdx.x];
+    pd_inflate_body(files + it.file_off, it.plan.stream_len, it.plan.inflated_len, workspace + it.ws_off, status + blockIdx.x);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- the predictor
 __device__ __forceinline__ uint32_t pd_predict(uint32_t ft, int a, int b, int c) {
     if (ft == 1u) return (uint32_t)a;
@@ -462,17 +469,6 @@ inline uint32_t pd_crc(const uint8_t* d, size_t n) {
 }
 
 inline uint32_t pd_be32(const uint8_t* d) { return (uint32_t)d[0] << 24 | (uint32_t)d[1] << 16 | (uint32_t)d[2] << 8 | d[3]; }
-
-struct PdRange { unsigned long long lo, hi; int item; };
-
-// -1, or the index of an item of (sorted by lo) ``r`` that reaches into its successor
-inline int pd_overlap(PdRange* r, int n) {
-    for (int i = 1; i < n; ++i)                                // (insertion sort: n <= 64)
-        for (int j = i; j > 0 && r[j].lo < r[j - 1].lo; --j) { const PdRange t = r[j]; r[j] = r[j - 1]; r[j - 1] = t; }
-    for (int i = 0; i + 1 < n; ++i)
-        if (r[i].hi > r[i + 1].lo) return i;
-    return -1;
-}
 
 }  // namespace
 }  // namespace frcnn

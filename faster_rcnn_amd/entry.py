@@ -286,7 +286,7 @@ class _Slot:
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
-                 "jpg_count", "png_items", "png_full")
+                 "jpg_count", "png_items", "png_dec")
 
     def __init__(self):
         for name in self.__slots__:
@@ -656,14 +656,13 @@ class DetectionEntry:
         if self.device_preprocess and _declares(image, "raw") and _declares(image, "height"):
             H, W, flip = int(image.height), int(image.width), bool(getattr(image, "flipped", False))
             jpeg_dev, png_dev = jpeg_decoder() == "device", png_decoder()
-            png_dev = "full" if png_dev == "device_full" else png_dev == "device"
-            if RGB_UPLOAD and (jpeg_dev or png_dev):
+            if RGB_UPLOAD and (jpeg_dev or png_dev != "host"):
                 from . import feed
                 # None: in-memory pixels, or a file the device decoders do not take
-                planned = feed.plan_entry_file(image, jpeg=jpeg_dev, png=png_dev) if png_dev else feed.plan_file(image)
+                planned = feed.plan_entry_file(image, jpeg=jpeg_dev, png=png_dev)
                 if planned is not None:
                     data, plan = planned
-                    kind = PngFile if isinstance(plan, (_lib.PngDecPlan, _lib.PngDecFullPlan)) else JpegFile
+                    kind = PngFile if ops.decoder_of(plan).label == "PNG" else JpegFile
                     return kind(data, plan, getattr(image, "_image_path", None) or str(getattr(image, "name", "?"))), H, W, \
                         (int(plan.h), int(plan.w)), 2 | int(flip)
             rgb = getattr(image, "raw_rgb", None) if RGB_UPLOAD else None
@@ -901,8 +900,8 @@ class DetectionEntry:
         B = s.batch
         files.sort(key=lambda t: isinstance(t[1], PngFile))         # (in place, stable: the .jpg items first, then the .png items)
         nj = sum(1 for _, f in files if not isinstance(f, PngFile))
-        item, pitem = ctypes.sizeof(_lib.JpegDecBatchItem), ctypes.sizeof(_lib.PngDecFullBatchItem)
-        table = (B * (item + pitem) + 255) // 256 * 256             # [B JPEG items | B PNG items], room for the larger kind of PNG item
+        item = ctypes.sizeof(_lib.JpegDecBatchItem)
+        table = (B * (item + ctypes.sizeof(_lib.PngDecFullBatchItem)) + 255) // 256 * 256      # [B JPEG items | B PNG items], room for the larger kind of PNG item
         at, seen, file_off = 0, {}, []
         for _, f in files:
             if id(f) not in seen:
@@ -917,39 +916,32 @@ class DetectionEntry:
         plans = [f.plan for _, f in files]
         # one kind of PNG item per pass: with a full-format plan among them (png_decoder "device_full") revision-1 plans, which a pass
         # can only hold when the setting changed under way, are restated as full-format ones
-        s.png_full = any(isinstance(p, _lib.PngDecFullPlan) for p in plans[nj:])
-        if s.png_full:
+        full = any(isinstance(p, _lib.PngDecFullPlan) for p in plans[nj:])
+        s.png_dec = ops.PNG_DECODERS["device_full" if full else "device"]
+        if full:
             plans[nj:] = [ops.png_dec_full_of(p) if isinstance(p, _lib.PngDecPlan) else p for p in plans[nj:]]
-        pitem = ctypes.sizeof(_lib.PngDecFullBatchItem if s.png_full else _lib.PngDecBatchItem)
+        kinds = ((ops.JPEG_DECODER, 0, nj), (s.png_dec, nj, len(plans)))    # per decoder: its items of the pass
         ws_off, need = [], 0
-        for k in range(0, nj, _lib.JPEG_DEC_BATCH_MAX):              # (a call takes JPEG_DEC_BATCH_MAX items: its regions behind the last call's)
-            offs, total = ops.jpeg_dec_batch_layout(plans[k:min(nj, k + _lib.JPEG_DEC_BATCH_MAX)])
-            ws_off += [need + o for o in offs]
-            need += total
-        for k in range(nj, len(plans), _lib.PNG_DEC_BATCH_MAX):
-            offs, total = (ops.png_dec_full_batch_layout if s.png_full else ops.png_dec_batch_layout)(plans[k:k + _lib.PNG_DEC_BATCH_MAX])
-            ws_off += [need + o for o in offs]
-            need += total
+        for dec, lo, hi in kinds:
+            for k in range(lo, hi, dec.batch_max):                  # (a call takes batch_max items: its regions behind the last call's)
+                offs, total = dec.layout(plans[k:min(hi, k + dec.batch_max)])
+                ws_off += [need + o for o in offs]
+                need += total
         if s.jpg_ws is None or s.jpg_ws.numel() < need:
             s.jpg_ws = torch.empty(need + need // 4, dtype=torch.uint8, device="cuda")
         if s.jpg_status is None:
             s.jpg_status = torch.zeros(B, dtype=torch.int32, device="cuda")
             s.jpg_status_pin = torch.zeros(B, dtype=torch.int32).pin_memory()
         out_off = [i * s.seg for i, _ in files]
-        s.jpg_items = ops.jpeg_batch_items(plans[:nj], file_off[:nj], out_off[:nj], ws_off[:nj])
-        if s.png_full:                                              # (a palette lies behind its stream in the file's staged bytes)
-            s.png_items = ops.png_full_batch_items(plans[nj:], file_off[nj:], out_off[nj:], ws_off[nj:],
-                                                   [o + int(p.stream_len) for o, p in zip(file_off[nj:], plans[nj:])])
-        else:
-            s.png_items = ops.png_batch_items(plans[nj:], file_off[nj:], out_off[nj:], ws_off[nj:])
+        # (a palette lies behind its stream in the file's staged bytes: DeviceDecoder.items)
+        s.jpg_items, s.png_items = (dec.items(plans[lo:hi], file_off[lo:hi], out_off[lo:hi], ws_off[lo:hi]) for dec, lo, hi in kinds)
         s.jpg_count = nj
         s.jpg_used = table + at
         s.jpg_names = [f.name for _, f in files]                    # (item k's status word is word k: the .jpg items, then the .png items)
         host = s.jpg_pin.numpy()
-        if nj:
-            host[:nj * item] = np.frombuffer(s.jpg_items, dtype=np.uint8)
-        if len(files) > nj:
-            host[B * item:B * item + (len(files) - nj) * pitem] = np.frombuffer(s.png_items, dtype=np.uint8)
+        for items, first in ((s.jpg_items, 0), (s.png_items, B * item)):
+            if len(items):
+                host[first:first + ctypes.sizeof(items)] = np.frombuffer(items, dtype=np.uint8)
         for f in {id(f): f for _, f in files}.values():
             host[table + seen[id(f)]:table + seen[id(f)] + len(f.data)] = np.frombuffer(f.data, dtype=np.uint8)
 
@@ -962,19 +954,17 @@ class DetectionEntry:
         if batched or len(files) > nj:                              # (the .png items are always decoded as a batch)
             s.jpg_area[:s.jpg_used].copy_(s.jpg_pin[:s.jpg_used], non_blocking=True)
         s.jpg_status.zero_()
-        kind, decode = (_lib.PngDecFullBatchItem, ops.png_decode_full_batch_u8) if s.png_full else (_lib.PngDecBatchItem, ops.png_decode_batch_u8)
-        pitem, ptable = ctypes.sizeof(kind), s.batch * item
-        for k in range(0, len(files) - nj, _lib.PNG_DEC_BATCH_MAX):
-            n = min(_lib.PNG_DEC_BATCH_MAX, len(files) - nj - k)
-            part = (kind * n).from_buffer(s.png_items, k * pitem)
-            decode(s.jpg_dev, part, s.io_dev, status=s.jpg_status[nj + k:nj + k + n], workspace=s.jpg_ws,
-                                    items_dev=s.jpg_area[ptable + k * pitem:ptable + (k + n) * pitem])
+        # per decoder: its items, its first status word, where its items lie in the staged area; the .png items' launches go first
+        for dec, items, word, first in ((s.png_dec, s.png_items, nj, s.batch * item), (ops.JPEG_DECODER, s.jpg_items, 0, 0)):
+            if dec is ops.JPEG_DECODER and not batched:
+                continue
+            size = ctypes.sizeof(dec.item_type)
+            for k in range(0, len(items), dec.batch_max):
+                n = min(dec.batch_max, len(items) - k)
+                part = (dec.item_type * n).from_buffer(items, k * size)
+                dec.decode(s.jpg_dev, part, s.io_dev, status=s.jpg_status[word + k:word + k + n], workspace=s.jpg_ws,
+                           items_dev=s.jpg_area[first + k * size:first + (k + n) * size])
         if batched:
-            for k in range(0, nj, _lib.JPEG_DEC_BATCH_MAX):
-                n = min(_lib.JPEG_DEC_BATCH_MAX, nj - k)
-                part = (_lib.JpegDecBatchItem * n).from_buffer(s.jpg_items, k * item)
-                ops.jpeg_decode_batch_u8(s.jpg_dev, part, s.io_dev, status=s.jpg_status[k:k + n], workspace=s.jpg_ws,
-                                         items_dev=s.jpg_area[k * item:(k + n) * item])
             return
         for k, (i, f) in enumerate(files[:nj]):
             it = s.jpg_items[k]
@@ -1023,12 +1013,8 @@ class DetectionEntry:
             if s.jpg_names:
                 words = s.jpg_status_pin.numpy()
                 for i, name in enumerate(s.jpg_names):
-                    if name is not None and int(words[i]) and i >= (s.jpg_count or 0):
-                        raise FrcnnError("device PNG decoder: %s is damaged (status %d: FRCNN_PNG_DEC_* in include/ext/frcnn_hip_png_dec.h); "
-                                         "decode it on the host or repair the file" % (name, int(words[i])))
-                    if name is not None and int(words[i]):
-                        raise FrcnnError("device JPEG decoder: %s is damaged (status %d: FRCNN_JPEG_DEC_* in include/ext/frcnn_hip_jpeg_dec.h); "
-                                         "decode it on the host or repair the file" % (name, int(words[i])))
+                    if name is not None and int(words[i]):          # (the .jpg items' words, then the .png items')
+                        ops.raise_damaged(ops.JPEG_DECODER if i < (s.jpg_count or 0) else s.png_dec, int(words[i]), name)
             if s.amax is not None:
                 bits = int(s.out_pin[0].numpy()[2])                 # the pass's f16x3 status word (pipeline._pass_status)
                 if bits:

@@ -64,55 +64,42 @@ def png_decoder_option(value, what):
     return value
 
 
-def plan_png(data):
-    """(the zlib stream of a .png file's bytes: its IDAT payloads back to back, what goes to the device; its decode plan), or None for a
-    file outside the device PNG decoder's supported set.  Pure host work."""
+def plan_png(data, mode="device"):
+    """(what goes to the device of a .png file's bytes: its zlib stream, the IDAT payloads back to back, followed under "device_full" for a
+    palette file by its 768 staged palette bytes: item.plte_off = item.file_off + plan.stream_len; its decode plan) under the PNG decoder
+    setting ``mode`` ("device": a ``PngDecPlan``; "device_full": a ``PngDecFullPlan``), or None for a file that decoder's planner
+    refuses.  Pure host work."""
+    dec = ops.PNG_DECODERS[mode]
     try:
-        plan = ops.png_dec_plan(data)
+        plan = dec.plan(data)
     except ops.PngUnsupported:
         return None
-    return ops.png_dec_stream(data, plan), plan
+    return dec.stage(data, plan), plan
 
 
 def plan_png_full(data):
-    """``plan_png`` through the full-format planner (ops.png_dec_full_plan) -> (the zlib stream, followed for a palette file by its 768
-    staged palette bytes: item.plte_off = item.file_off + plan.stream_len; its ``PngDecFullPlan``), or None for a file that planner
-    refuses (16-bit grey, a damaged container, ...).  Pure host work."""
-    try:
-        plan = ops.png_dec_full_plan(data)
-    except ops.PngUnsupported:
-        return None
-    stream, palette = ops.png_dec_full_stream(data, plan)
-    return stream + palette, plan
+    """``plan_png`` under "device_full"."""
+    return plan_png(data, "device_full")
 
 
 def plan_entry_file(image, jpeg=True, png=False):
     """``plan_file`` for the detection entry, which may decode either kind on the device: a file-backed image whose bytes start with
-    the PNG signature is planned by the PNG decoder's planner when ``png`` (-> (its zlib stream, its ``PngDecPlan``); ``png="full"``: by
-    the full-format planner, -> ``plan_png_full``'s pair; what an ``annotate_video._FileFrame`` planned ahead is taken as it is), any
-    other file by ``plan_file`` when ``jpeg``.  None: the caller takes the host path.  (``device_image``, the training feed, plans through
-    ``plan_feed_file``.)"""
-    if not _declares(image, "raw_file") or getattr(image, "_pixels", None) is not None:
-        return None
-    data = image.raw_file()
-    if data is None:
-        return None
-    if bytes(data[:8]) == ops.PNG_SIGNATURE:
-        if not png:
-            return None
-        planned = getattr(image, "png_planned", None)
-        if planned is not None and isinstance(planned[1], ops._lib.PngDecFullPlan) == (png == "full"):
-            return planned
-        return plan_png_full(data) if png == "full" else plan_png(data)
-    return plan_file(image) if jpeg else None
+    the PNG signature is planned by the PNG decoder ``png`` names (a PNG decoder setting; True stands for "device", "full" for
+    "device_full", False for "host") -> ``plan_png``'s pair; what an ``annotate_video._FileFrame`` planned ahead under the same setting
+    is taken as it is), any other file by ``plan_file`` when ``jpeg``.  None: the caller takes the host path.  (``device_image``, the
+    training feed, plans through ``plan_feed_file``.)"""
+    return _plan_by_settings(image, jpeg, {True: "device", "full": "device_full", False: "host"}.get(png, png))
 
 
 def plan_feed_file(image):
     """``plan_file`` for the training feed under its two settings: a file that starts with the PNG signature is planned by the PNG
-    planner FRCNN_FEED_PNG_DECODER names (-> ``plan_png`` / ``plan_png_full``'s pair), any other file by ``plan_file`` when
+    planner FRCNN_FEED_PNG_DECODER names (-> ``plan_png``'s pair), any other file by ``plan_file`` when
     FRCNN_FEED_JPEG_DECODER is "device".  None: in-memory pixels, no ``raw_file``, a setting of "host" for that kind of file, or a file
     the planner refuses: the caller takes the host path.  Pure host work: a thread may do it ahead."""
-    png, jpeg = default_png_decoder(), default_jpeg_decoder() == "device"
+    return _plan_by_settings(image, default_jpeg_decoder() == "device", default_png_decoder())
+
+
+def _plan_by_settings(image, jpeg, png):
     if png == "host":
         return plan_file(image) if jpeg else None
     if not _declares(image, "raw_file") or getattr(image, "_pixels", None) is not None:
@@ -121,22 +108,17 @@ def plan_feed_file(image):
     if data is None:
         return None
     if bytes(data[:8]) == ops.PNG_SIGNATURE:
-        return plan_png_full(data) if png == "device_full" else plan_png(data)
+        planned = getattr(image, "png_planned", None)
+        if planned is not None and ops.decoder_of(planned[1]).setting == png:
+            return planned
+        return plan_png(data, png)
     return plan_file(image) if jpeg else None
-
-
-def _planned_kind(plan):
-    """"png" / "jpeg": which decoder (and which setting) a planned file belongs to."""
-    return "png" if isinstance(plan, (ops._lib.PngDecPlan, ops._lib.PngDecFullPlan)) else "jpeg"
 
 
 def _still_wanted(plan):
     """Does the setting that was in force when a file was planned ahead still hold?"""
-    if isinstance(plan, ops._lib.PngDecFullPlan):
-        return default_png_decoder() == "device_full"
-    if isinstance(plan, ops._lib.PngDecPlan):
-        return default_png_decoder() == "device"
-    return default_jpeg_decoder() == "device"
+    dec = ops.decoder_of(plan)
+    return (default_png_decoder() if dec.label == "PNG" else default_jpeg_decoder()) == dec.setting
 
 
 class _PinRing:
@@ -240,7 +222,7 @@ def _raw_rgb(image):
     return image.raw_rgb
 
 
-# Device decodes whose status word has not been looked at: (pinned int32 [1], event behind its copy, file name, "jpeg" / "png").  ``check_decodes`` is
+# Device decodes whose status word has not been looked at: (pinned int32 [1], event behind its copy, file name, its ops.DeviceDecoder).  ``check_decodes`` is
 # called where a training manager has just synchronised for its own counts: it reads the words whose copy has FINISHED and waits for none.
 _DECODE_STATUS = []
 _STATUS_PIN, _STATUS_AT = None, 0
@@ -248,9 +230,9 @@ _STATUS_PIN, _STATUS_AT = None, 0
 
 def _decode_on_device(data, plan, name):
     """The file decoded on the current stream -> (h, w, 3) uint8 R,G,B device tensor; its status word is queued for check_decodes."""
-    kind = _planned_kind(plan)
-    if kind == "png":
-        rgb, status = _decode_png_on_device(data, plan)
+    dec = ops.decoder_of(plan)
+    if dec.label == "PNG":
+        rgb, status = _decode_png_on_device(dec, data, plan)
     else:
         file_dev = upload(np.frombuffer(data, dtype=np.uint8))
         rgb, status = ops.jpeg_decode_u8(file_dev, plan)
@@ -264,28 +246,22 @@ def _decode_on_device(data, plan, name):
     word.copy_(status, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record()
-    _DECODE_STATUS.append((word, ev, name, kind))
+    _DECODE_STATUS.append((word, ev, name, dec))
     return rgb
 
 
-def _decode_png_on_device(data, plan):
-    """A planned .png file (``plan_png`` / ``plan_png_full``'s pair) as a batch of one: ONE upload through the pin ring of [the item |
-    the zlib stream | the palette], the decode on the current stream -> ((h, w, 3) uint8 R,G,B device tensor, its status word [1])."""
+def _decode_png_on_device(dec, data, plan):
+    """A planned .png file (``plan_png``'s pair, made for the decoder ``dec``) as a batch of one: ONE upload through the pin ring of [the
+    item | the zlib stream | the palette], the decode on the current stream -> ((h, w, 3) uint8 R,G,B device tensor, its status word [1])."""
     import ctypes
-    full = isinstance(plan, ops._lib.PngDecFullPlan)
-    head = (ctypes.sizeof(ops._lib.PngDecFullBatchItem if full else ops._lib.PngDecBatchItem) + 15) // 16 * 16
-    offs, _ = (ops.png_dec_full_batch_layout if full else ops.png_dec_batch_layout)([plan])
-    if full:
-        items = ops.png_full_batch_items([plan], [0], [0], offs, [int(plan.stream_len)])
-    else:
-        items = ops.png_batch_items([plan], [0], [0], offs)
+    head = (ctypes.sizeof(dec.item_type) + 15) // 16 * 16
+    items = dec.items([plan], [0], [0], dec.layout([plan])[0])
     staged = np.empty(head + len(data), np.uint8)
     staged[:ctypes.sizeof(items)] = np.frombuffer(items, dtype=np.uint8)
     staged[head:] = np.frombuffer(data, dtype=np.uint8)
     dev = upload(staged)
     rgb = torch.empty((int(plan.h), int(plan.w), 3), dtype=torch.uint8, device="cuda")
-    decode = ops.png_decode_full_batch_u8 if full else ops.png_decode_batch_u8
-    status = decode(dev[head:], items, rgb.view(-1), status=torch.zeros(1, dtype=torch.int32, device="cuda"), items_dev=dev[:head])
+    status = dec.decode(dev[head:], items, rgb.view(-1), status=torch.zeros(1, dtype=torch.int32, device="cuda"), items_dev=dev[:head])
     return rgb, status
 
 
@@ -294,18 +270,14 @@ def check_decodes():
     if not _DECODE_STATUS:
         return
     waiting, bad = [], None
-    for word, ev, name, kind in _DECODE_STATUS:
+    for word, ev, name, dec in _DECODE_STATUS:
         if not ev.query():
-            waiting.append((word, ev, name, kind))
+            waiting.append((word, ev, name, dec))
         elif int(word[0]) and bad is None:
-            bad = (name, int(word[0]), kind)
+            bad = (dec, int(word[0]), name)
     _DECODE_STATUS[:] = waiting
-    if bad is not None and bad[2] == "png":
-        raise ops._lib.FrcnnError("device PNG decoder: %s is damaged (status %d: FRCNN_PNG_DEC_* in include/ext/frcnn_hip_png_dec.h); "
-                                  "decode it on the host or repair the file" % bad[:2])
     if bad is not None:
-        raise ops._lib.FrcnnError("device JPEG decoder: %s is damaged (status %d: FRCNN_JPEG_DEC_* in include/ext/frcnn_hip_jpeg_dec.h); "
-                                  "decode it on the host or repair the file" % bad[:2])
+        ops.raise_damaged(*bad)
 
 
 def device_image(image, preprocess_func):

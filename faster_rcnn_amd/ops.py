@@ -5,6 +5,7 @@ arithmetic happens inside libfrcnn_hip.so.  Every function takes/returns CUDA(=H
 and is asynchronous on ``torch.cuda.current_stream()``.
 """
 import ctypes
+import dataclasses
 import os
 
 import numpy as np
@@ -1268,29 +1269,171 @@ class JpegUnsupported(_lib.FrcnnError):
     """``jpeg_dec_plan``: the file lies outside the device decoder's supported set; the message names the reason."""
 
 
+class PngUnsupported(_lib.FrcnnError):
+    """``png_dec_plan``: the file lies outside the device decoder's supported set; the message names the reason."""
+
+
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_DEC_WINDOW_BYTES = _lib.PNG_DEC_WINDOW_BYTES    # compressed bytes per window of the inflate kernel (a larger block carries its tables over)
+PNG_DEC_FULL_PLTE_BYTES = _lib.PNG_DEC_FULL_PLTE_BYTES
+
+
+@dataclasses.dataclass(frozen=True)
+class DeviceDecoder:
+    """One device decoder of file-backed frames: what its C entry points are called and take, and every operation on them ONCE.  The
+    public functions below (``jpeg_dec_plan`` ... ``png_decode_full_u8``) are bindings of these methods to one of the three records.
+    ``stem`` / ``decode_stem`` / ``items_name``: the names "frcnn_" + name are the C symbols of and the messages speak of
+    (<stem>_plan, <stem>_spans, <stem>_workspace_bytes, <stem>_batch_layout; <decode_stem>_batch_u8, <decode_stem>_u8); ``setting``: the
+    value of a decoder setting (feed.py, entry.py) that selects it; ``palette``: its items carry ``plte_off``."""
+    label: str
+    setting: str
+    stem: str
+    decode_stem: str
+    items_name: str
+    plan_type: type
+    item_type: type
+    batch_max: int
+    unsupported: type
+    palette: bool = False
+
+    def plan(self, data):
+        who = self.stem + "_plan"
+        if not isinstance(data, (bytes, bytearray, memoryview)):
+            raise _lib.FrcnnError("%s: the file's bytes, got %s" % (who, type(data).__name__))
+        data = bytes(data)
+        plan = self.plan_type()
+        lib = _lib.load()
+        code = getattr(lib, "frcnn_" + who)(data, len(data), ctypes.byref(plan))
+        if code == _lib.E_UNSUPPORTED:
+            raise self.unsupported((lib.frcnn_last_error() or b"").decode())
+        _lib.check(code, "frcnn_" + who)
+        return plan
+
+    def workspace_bytes(self, plan):
+        who = self.stem + "_workspace_bytes"
+        n = int(getattr(_lib.load(), "frcnn_" + who)(ctypes.byref(plan)))
+        if n == 0:
+            raise _lib.FrcnnError("%s: not a plan that %s_plan made" % (who, self.stem))
+        return n
+
+    def layout(self, plans):
+        who, n = self.stem + "_batch_layout", len(plans)
+        if not 1 <= n <= self.batch_max:
+            raise _lib.FrcnnError(f"{who}: {n} plans, 1..{self.batch_max} go into one batch")
+        arr = (self.plan_type * n)(*plans)
+        offs = (ctypes.c_uint64 * n)()
+        total = int(getattr(_lib.load(), "frcnn_" + who)(arr, n, offs))
+        if total == 0:
+            raise _lib.FrcnnError("%s: not plans that %s_plan made" % (who, self.stem))
+        return [int(o) for o in offs], total
+
+    def items(self, plans, file_off, out_off, ws_off, plte_off=None):
+        """The item table of a batch; a palette lies behind its stream in the file's staged bytes (``stage``) unless ``plte_off`` says
+        where else."""
+        items = (self.item_type * len(plans))()
+        for it, p, f, o, w in zip(items, plans, file_off, out_off, ws_off):
+            it.plan, it.file_off, it.out_off, it.ws_off = p, int(f), int(o), int(w)
+        if self.palette:
+            for it, q in zip(items, plte_off if plte_off is not None else [int(f) + int(p.stream_len) for f, p in zip(file_off, plans)]):
+                it.plte_off = int(q)
+        return items
+
+    def decode(self, files, items, out, bgr=False, status=None, workspace=None, items_dev=None):
+        _require_gpu()
+        who, n = self.decode_stem + "_batch_u8", len(items)
+        if not isinstance(items, ctypes.Array) or items._type_ is not self.item_type:
+            raise _lib.FrcnnError("%s: items must be a table made by %s" % (who, self.items_name))
+        if items_dev is None:
+            items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).cuda()
+        if status is None:
+            status = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
+        if workspace is None:
+            workspace = _ws(max((int(it.ws_off) + self.workspace_bytes(it.plan) for it in items), default=0))
+        for name, t, dt in (("files", files, torch.uint8), ("out", out, torch.uint8), ("status", status, torch.int32),
+                            ("workspace", workspace, torch.uint8), ("items_dev", items_dev, torch.uint8)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+                raise _lib.FrcnnError(f"{who}: {name} must be a contiguous {dt} device tensor")
+        if items_dev.numel() < ctypes.sizeof(items) or status.numel() < n:
+            raise _lib.FrcnnError(f"{who}: items_dev of {items_dev.numel()} bytes / status of {status.numel()} words for {n} items")
+        _lib.call("frcnn_" + who, ctypes.addressof(items), _p(items_dev), n, _p(files), files.numel(), 1 if bgr else 0,
+                  _p(out), out.numel(), _p(status), _p(workspace), workspace.numel(), _stream())
+        return status
+
+    # ---- the PNG records only: a .png file's zlib stream is gathered on the host
+    def spans(self, data, plan):
+        data = bytes(data)
+        n = int(plan.idat_count)
+        spans = (ctypes.c_uint32 * (2 * max(n, 1)))()
+        _lib.call("frcnn_%s_spans" % self.stem, data, len(data), ctypes.byref(plan), spans, n)
+        return [(int(spans[2 * k]), int(spans[2 * k + 1])) for k in range(n)]
+
+    def stream(self, data, plan):
+        data = bytes(data)
+        spans = self.spans(data, plan)
+        return data[spans[0][0]:spans[0][0] + spans[0][1]] if len(spans) == 1 else b"".join(data[o:o + n] for o, n in spans)
+
+    def palette_of(self, data, plan):
+        """The PLTE entries zero-padded to PNG_DEC_FULL_PLTE_BYTES for a colour-type-3 file under a decoder with palettes, else b""."""
+        if not self.palette or int(plan.colour_type) != 3:
+            return b""
+        palette = bytes(data)[int(plan.plte_off):int(plan.plte_off) + 3 * int(plan.plte_entries)]
+        return palette + bytes(PNG_DEC_FULL_PLTE_BYTES - len(palette))
+
+    def stage(self, data, plan):
+        """What goes to the device for one file: its zlib stream, behind it its staged palette where it has one."""
+        return self.stream(data, plan) + self.palette_of(data, plan)
+
+    def decode_one(self, file_bytes, bgr=False):
+        _require_gpu()
+        data = bytes(file_bytes)
+        plan = self.plan(data)
+        files = torch.frombuffer(bytearray(self.stage(data, plan)), dtype=torch.uint8).cuda()
+        out = torch.empty((int(plan.h), int(plan.w), 3), dtype=torch.uint8, device="cuda")
+        status = self.decode(files, self.items([plan], [0], [0], [0]), out.view(-1), bgr=bgr)
+        word = int(status.cpu()[0])
+        if word:
+            raise_damaged(self, word, who=self.decode_stem + "_u8")
+        return out
+
+
+JPEG_DECODER = DeviceDecoder("JPEG", "device", "jpeg_dec", "jpeg_decode", "jpeg_batch_items", _lib.JpegDecPlan, _lib.JpegDecBatchItem,
+                             _lib.JPEG_DEC_BATCH_MAX, JpegUnsupported)
+# by the value of a PNG decoder setting (feed.PNG_DECODERS but "host")
+PNG_DECODERS = {
+    "device": DeviceDecoder("PNG", "device", "png_dec", "png_decode", "png_batch_items", _lib.PngDecPlan, _lib.PngDecBatchItem,
+                            _lib.PNG_DEC_BATCH_MAX, PngUnsupported),
+    "device_full": DeviceDecoder("PNG", "device_full", "png_dec_full", "png_decode_full", "png_full_batch_items", _lib.PngDecFullPlan,
+                                 _lib.PngDecFullBatchItem, _lib.PNG_DEC_BATCH_MAX, PngUnsupported, palette=True),
+}
+_PNG1, _PNGF = PNG_DECODERS["device"], PNG_DECODERS["device_full"]
+_DECODER_OF = {d.plan_type: d for d in (JPEG_DECODER, _PNG1, _PNGF)}
+
+
+def decoder_of(plan):
+    """The ``DeviceDecoder`` whose planner made ``plan``."""
+    return _DECODER_OF[type(plan)]
+
+
+def raise_damaged(dec, word, name=None, who=None):
+    """The FrcnnError for a file whose device decode (by ``dec``) left the status word ``word``: about the file ``name``, or in the words
+    of the eager function ``who``."""
+    what = "(status %d: FRCNN_%s_DEC_* in include/ext/frcnn_hip_%s_dec.h)" % (word, dec.label, dec.label.lower())
+    if name is None:
+        raise _lib.FrcnnError("%s: the file is damaged %s" % (who, what))
+    raise _lib.FrcnnError("device %s decoder: %s is damaged %s; decode it on the host or repair the file" % (dec.label, name, what))
+
+
 def jpeg_dec_plan(data):
     """The host-side marker parse of a .jpg file's bytes (frcnn_jpeg_dec_plan) -> a ``_lib.JpegDecPlan``: size, components, sampling,
     where the tables and the entropy-coded segment lie, into how many subsequences it is cut.  ``JpegUnsupported`` (a FrcnnError) with
     the reason for a file outside the supported set (include/ext/frcnn_hip_jpeg_dec.h): the caller decodes it on the host.  A pure host
     call: needs the built library, no GPU."""
-    if not isinstance(data, (bytes, bytearray, memoryview)):
-        raise _lib.FrcnnError("jpeg_dec_plan: the file's bytes, got %s" % type(data).__name__)
-    data = bytes(data)
-    plan = _lib.JpegDecPlan()
-    lib = _lib.load()
-    code = lib.frcnn_jpeg_dec_plan(data, len(data), ctypes.byref(plan))
-    if code == _lib.E_UNSUPPORTED:
-        raise JpegUnsupported((lib.frcnn_last_error() or b"").decode())
-    _lib.check(code, "frcnn_jpeg_dec_plan")
-    return plan
+    return JPEG_DECODER.plan(data)
 
 
 def jpeg_dec_workspace_bytes(plan):
     """Bytes of device workspace ``jpeg_decode_u8`` needs for ``plan`` (frcnn_jpeg_dec_workspace_bytes)."""
-    n = int(_lib.load().frcnn_jpeg_dec_workspace_bytes(ctypes.byref(plan)))
-    if n == 0:
-        raise _lib.FrcnnError("jpeg_dec_workspace_bytes: not a plan that jpeg_dec_plan made")
-    return n
+    return JPEG_DECODER.workspace_bytes(plan)
 
 
 def jpeg_decode_u8(file, plan=None, bgr=False, out=None, status=None, workspace=None):
@@ -1334,23 +1477,12 @@ def jpeg_dec_batch_layout(plans):
     """Workspace regions for a batch of plans laid back to back (frcnn_jpeg_dec_batch_layout) -> (ws_off, total): the byte offset of
     every plan's region (16-byte aligned, each ``jpeg_dec_workspace_bytes(plan)`` long) and the bytes of workspace the batch needs.  A
     pure host call."""
-    n = len(plans)
-    if not 1 <= n <= _lib.JPEG_DEC_BATCH_MAX:
-        raise _lib.FrcnnError(f"jpeg_dec_batch_layout: {n} plans, 1..{_lib.JPEG_DEC_BATCH_MAX} go into one batch")
-    arr = (_lib.JpegDecPlan * n)(*plans)
-    offs = (ctypes.c_uint64 * n)()
-    total = int(_lib.load().frcnn_jpeg_dec_batch_layout(arr, n, offs))
-    if total == 0:
-        raise _lib.FrcnnError("jpeg_dec_batch_layout: not plans that jpeg_dec_plan made")
-    return [int(o) for o in offs], total
+    return JPEG_DECODER.layout(plans)
 
 
 def jpeg_batch_items(plans, file_off, out_off, ws_off):
     """The item table of a batch (``_lib.JpegDecBatchItem`` x n, a ctypes array: ``bytes(table)`` is what goes to the device)."""
-    items = (_lib.JpegDecBatchItem * len(plans))()
-    for it, p, f, o, w in zip(items, plans, file_off, out_off, ws_off):
-        it.plan, it.file_off, it.out_off, it.ws_off = p, int(f), int(o), int(w)
-    return items
+    return JPEG_DECODER.items(plans, file_off, out_off, ws_off)
 
 
 def jpeg_decode_batch_u8(files, items, out, bgr=False, status=None, workspace=None, items_dev=None):
@@ -1360,33 +1492,7 @@ def jpeg_decode_batch_u8(files, items, out, bgr=False, status=None, workspace=No
     tensor -> status: int32 [n], per file 0 or _lib.JPEG_DEC_* bits ORed in (sticky: a tensor passed in is not cleared).  ``items_dev``:
     a device tensor that already holds ``bytes(items)`` (uploaded by the caller on the current stream); None: uploaded here, a pageable
     copy, which blocks the host.  ``status`` and ``workspace`` are allocated when not passed.  Never synchronises otherwise."""
-    _require_gpu()
-    n = len(items)
-    if not isinstance(items, ctypes.Array) or items._type_ is not _lib.JpegDecBatchItem:
-        raise _lib.FrcnnError("jpeg_decode_batch_u8: items must be a table made by jpeg_batch_items")
-    if items_dev is None:
-        items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).cuda()
-    if status is None:
-        status = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
-    if workspace is None:
-        workspace = _ws(max((int(it.ws_off) + jpeg_dec_workspace_bytes(it.plan) for it in items), default=0))
-    for name, t, dt in (("files", files, torch.uint8), ("out", out, torch.uint8), ("status", status, torch.int32),
-                        ("workspace", workspace, torch.uint8), ("items_dev", items_dev, torch.uint8)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-            raise _lib.FrcnnError(f"jpeg_decode_batch_u8: {name} must be a contiguous {dt} device tensor")
-    if items_dev.numel() < ctypes.sizeof(items) or status.numel() < n:
-        raise _lib.FrcnnError(f"jpeg_decode_batch_u8: items_dev of {items_dev.numel()} bytes / status of {status.numel()} words for {n} items")
-    _lib.call("frcnn_jpeg_decode_batch_u8", ctypes.addressof(items), _p(items_dev), n, _p(files), files.numel(), 1 if bgr else 0,
-              _p(out), out.numel(), _p(status), _p(workspace), workspace.numel(), _stream())
-    return status
-
-
-class PngUnsupported(_lib.FrcnnError):
-    """``png_dec_plan``: the file lies outside the device decoder's supported set; the message names the reason."""
-
-
-PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
-PNG_DEC_WINDOW_BYTES = _lib.PNG_DEC_WINDOW_BYTES    # compressed bytes per window of the inflate kernel (a larger block carries its tables over)
+    return JPEG_DECODER.decode(files, items, out, bgr, status, workspace, items_dev)
 
 
 def png_dec_plan(data):
@@ -1394,62 +1500,33 @@ def png_dec_plan(data):
     lie, the bytes of the zlib stream and of what it inflates to; the CRC-32 of IHDR and of every IDAT is verified.  ``PngUnsupported``
     (a FrcnnError) with the reason for a file outside the supported set (include/ext/frcnn_hip_png_dec.h): the caller decodes it on the
     host.  A pure host call: needs the built library, no GPU."""
-    if not isinstance(data, (bytes, bytearray, memoryview)):
-        raise _lib.FrcnnError("png_dec_plan: the file's bytes, got %s" % type(data).__name__)
-    data = bytes(data)
-    plan = _lib.PngDecPlan()
-    lib = _lib.load()
-    code = lib.frcnn_png_dec_plan(data, len(data), ctypes.byref(plan))
-    if code == _lib.E_UNSUPPORTED:
-        raise PngUnsupported((lib.frcnn_last_error() or b"").decode())
-    _lib.check(code, "frcnn_png_dec_plan")
-    return plan
+    return _PNG1.plan(data)
 
 
 def png_dec_spans(data, plan):
     """[(offset, length)] of the IDAT payloads of the file ``plan`` was made of (frcnn_png_dec_spans), in file order."""
-    data = bytes(data)
-    n = int(plan.idat_count)
-    spans = (ctypes.c_uint32 * (2 * max(n, 1)))()
-    _lib.call("frcnn_png_dec_spans", data, len(data), ctypes.byref(plan), spans, n)
-    return [(int(spans[2 * k]), int(spans[2 * k + 1])) for k in range(n)]
+    return _PNG1.spans(data, plan)
 
 
 def png_dec_stream(data, plan):
     """What goes to the device: the file's zlib stream, its IDAT payloads back to back (``plan.stream_len`` bytes)."""
-    data = bytes(data)
-    spans = png_dec_spans(data, plan)
-    return data[spans[0][0]:spans[0][0] + spans[0][1]] if len(spans) == 1 else b"".join(data[o:o + n] for o, n in spans)
+    return _PNG1.stream(data, plan)
 
 
 def png_dec_workspace_bytes(plan):
     """Bytes of device workspace a file of ``plan`` needs (frcnn_png_dec_workspace_bytes): its inflated bytes."""
-    n = int(_lib.load().frcnn_png_dec_workspace_bytes(ctypes.byref(plan)))
-    if n == 0:
-        raise _lib.FrcnnError("png_dec_workspace_bytes: not a plan that png_dec_plan made")
-    return n
+    return _PNG1.workspace_bytes(plan)
 
 
 def png_dec_batch_layout(plans):
     """Workspace regions for a batch of plans laid back to back (frcnn_png_dec_batch_layout) -> (ws_off, total).  A pure host call."""
-    n = len(plans)
-    if not 1 <= n <= _lib.PNG_DEC_BATCH_MAX:
-        raise _lib.FrcnnError(f"png_dec_batch_layout: {n} plans, 1..{_lib.PNG_DEC_BATCH_MAX} go into one batch")
-    arr = (_lib.PngDecPlan * n)(*plans)
-    offs = (ctypes.c_uint64 * n)()
-    total = int(_lib.load().frcnn_png_dec_batch_layout(arr, n, offs))
-    if total == 0:
-        raise _lib.FrcnnError("png_dec_batch_layout: not plans that png_dec_plan made")
-    return [int(o) for o in offs], total
+    return _PNG1.layout(plans)
 
 
 def png_batch_items(plans, file_off, out_off, ws_off):
     """The item table of a batch (``_lib.PngDecBatchItem`` x n, a ctypes array: ``bytes(table)`` is what goes to the device);
     ``file_off``: where each file's staged zlib stream (``png_dec_stream``) lies."""
-    items = (_lib.PngDecBatchItem * len(plans))()
-    for it, p, f, o, w in zip(items, plans, file_off, out_off, ws_off):
-        it.plan, it.file_off, it.out_off, it.ws_off = p, int(f), int(o), int(w)
-    return items
+    return _PNG1.items(plans, file_off, out_off, ws_off)
 
 
 def png_decode_batch_u8(files, items, out, bgr=False, status=None, workspace=None, items_dev=None):
@@ -1458,83 +1535,34 @@ def png_decode_batch_u8(files, items, out, bgr=False, status=None, workspace=Non
     [n], per file 0 or _lib.PNG_DEC_* bits ORed in (sticky: a tensor passed in is not cleared).  ``items_dev``: a device tensor that
     already holds ``bytes(items)``; None: uploaded here, a pageable copy, which blocks the host.  ``status`` and ``workspace`` are
     allocated when not passed.  Never synchronises otherwise."""
-    _require_gpu()
-    n = len(items)
-    if not isinstance(items, ctypes.Array) or items._type_ is not _lib.PngDecBatchItem:
-        raise _lib.FrcnnError("png_decode_batch_u8: items must be a table made by png_batch_items")
-    if items_dev is None:
-        items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).cuda()
-    if status is None:
-        status = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
-    if workspace is None:
-        workspace = _ws(max((int(it.ws_off) + png_dec_workspace_bytes(it.plan) for it in items), default=0))
-    for name, t, dt in (("files", files, torch.uint8), ("out", out, torch.uint8), ("status", status, torch.int32),
-                        ("workspace", workspace, torch.uint8), ("items_dev", items_dev, torch.uint8)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-            raise _lib.FrcnnError(f"png_decode_batch_u8: {name} must be a contiguous {dt} device tensor")
-    if items_dev.numel() < ctypes.sizeof(items) or status.numel() < n:
-        raise _lib.FrcnnError(f"png_decode_batch_u8: items_dev of {items_dev.numel()} bytes / status of {status.numel()} words for {n} items")
-    _lib.call("frcnn_png_decode_batch_u8", ctypes.addressof(items), _p(items_dev), n, _p(files), files.numel(), 1 if bgr else 0,
-              _p(out), out.numel(), _p(status), _p(workspace), workspace.numel(), _stream())
-    return status
+    return _PNG1.decode(files, items, out, bgr, status, workspace, items_dev)
 
 
 def png_decode_u8(file_bytes, bgr=False):
     """One .png file's bytes decoded on the device: the eager convenience (a batch of one; pageable uploads, one synchronisation) -> an
     (h, w, 3) uint8 device tensor, numpy.asarray(PIL.Image.open(f).convert("RGB")) byte for byte, or its channel reverse with ``bgr``.
     ``PngUnsupported`` for a file outside the supported set, ``FrcnnError`` with the status word for a damaged one."""
-    _require_gpu()
-    data = bytes(file_bytes)
-    plan = png_dec_plan(data)
-    files = torch.frombuffer(bytearray(png_dec_stream(data, plan)), dtype=torch.uint8).cuda()
-    out = torch.empty((int(plan.h), int(plan.w), 3), dtype=torch.uint8, device="cuda")
-    status = png_decode_batch_u8(files, png_batch_items([plan], [0], [0], [0]), out.view(-1), bgr=bgr)
-    word = int(status.cpu()[0])
-    if word:
-        raise _lib.FrcnnError("png_decode_u8: the file is damaged (status %d: FRCNN_PNG_DEC_* in include/ext/frcnn_hip_png_dec.h)" % word)
-    return out
+    return _PNG1.decode_one(file_bytes, bgr)
 
 
 # ---- the full-format PNG decoder (include/ext/frcnn_hip_png_dec_full.h, csrc/png_dec_full.hip): palette, 1/2/4/16-bit, grey + alpha, Adam7
-PNG_DEC_FULL_PLTE_BYTES = _lib.PNG_DEC_FULL_PLTE_BYTES
-
-
 def png_dec_full_plan(data):
     """``png_dec_plan`` for the full-format decoder (frcnn_png_dec_full_plan) -> a ``_lib.PngDecFullPlan``: size, colour type, bit depth,
     interlace, where the IDATs and the PLTE lie, the bytes of the zlib stream and of what it inflates to.  ``PngUnsupported`` with the
     reason for a file outside ITS supported set (16-bit grey, a palette file without a usable PLTE, a damaged container, ...).  A pure
     host call."""
-    if not isinstance(data, (bytes, bytearray, memoryview)):
-        raise _lib.FrcnnError("png_dec_full_plan: the file's bytes, got %s" % type(data).__name__)
-    data = bytes(data)
-    plan = _lib.PngDecFullPlan()
-    lib = _lib.load()
-    code = lib.frcnn_png_dec_full_plan(data, len(data), ctypes.byref(plan))
-    if code == _lib.E_UNSUPPORTED:
-        raise PngUnsupported((lib.frcnn_last_error() or b"").decode())
-    _lib.check(code, "frcnn_png_dec_full_plan")
-    return plan
+    return _PNGF.plan(data)
 
 
 def png_dec_full_spans(data, plan):
     """[(offset, length)] of the IDAT payloads of the file ``plan`` was made of (frcnn_png_dec_full_spans), in file order."""
-    data = bytes(data)
-    n = int(plan.idat_count)
-    spans = (ctypes.c_uint32 * (2 * max(n, 1)))()
-    _lib.call("frcnn_png_dec_full_spans", data, len(data), ctypes.byref(plan), spans, n)
-    return [(int(spans[2 * k]), int(spans[2 * k + 1])) for k in range(n)]
+    return _PNGF.spans(data, plan)
 
 
 def png_dec_full_stream(data, plan):
     """What goes to the device -> (the file's zlib stream: its IDAT payloads back to back, ``plan.stream_len`` bytes; its palette: the
     PLTE entries zero-padded to PNG_DEC_FULL_PLTE_BYTES = 768 bytes for a colour-type-3 file, b"" for any other)."""
-    data = bytes(data)
-    spans = png_dec_full_spans(data, plan)
-    stream = data[spans[0][0]:spans[0][0] + spans[0][1]] if len(spans) == 1 else b"".join(data[o:o + n] for o, n in spans)
-    if int(plan.colour_type) != 3:
-        return stream, b""
-    palette = data[int(plan.plte_off):int(plan.plte_off) + 3 * int(plan.plte_entries)]
-    return stream, palette + bytes(PNG_DEC_FULL_PLTE_BYTES - len(palette))
+    return _PNGF.stream(data, plan), _PNGF.palette_of(data, plan)
 
 
 def png_dec_full_of(plan):
@@ -1548,73 +1576,31 @@ def png_dec_full_of(plan):
 
 def png_dec_full_workspace_bytes(plan):
     """Bytes of device workspace a file of ``plan`` needs (frcnn_png_dec_full_workspace_bytes): its inflated bytes."""
-    n = int(_lib.load().frcnn_png_dec_full_workspace_bytes(ctypes.byref(plan)))
-    if n == 0:
-        raise _lib.FrcnnError("png_dec_full_workspace_bytes: not a plan that png_dec_full_plan made")
-    return n
+    return _PNGF.workspace_bytes(plan)
 
 
 def png_dec_full_batch_layout(plans):
     """Workspace regions for a batch of plans laid back to back (frcnn_png_dec_full_batch_layout) -> (ws_off, total).  A pure host call."""
-    n = len(plans)
-    if not 1 <= n <= _lib.PNG_DEC_BATCH_MAX:
-        raise _lib.FrcnnError(f"png_dec_full_batch_layout: {n} plans, 1..{_lib.PNG_DEC_BATCH_MAX} go into one batch")
-    arr = (_lib.PngDecFullPlan * n)(*plans)
-    offs = (ctypes.c_uint64 * n)()
-    total = int(_lib.load().frcnn_png_dec_full_batch_layout(arr, n, offs))
-    if total == 0:
-        raise _lib.FrcnnError("png_dec_full_batch_layout: not plans that png_dec_full_plan made")
-    return [int(o) for o in offs], total
+    return _PNGF.layout(plans)
 
 
 def png_full_batch_items(plans, file_off, out_off, ws_off, plte_off):
     """The item table of a batch (``_lib.PngDecFullBatchItem`` x n, a ctypes array: ``bytes(table)`` is what goes to the device);
     ``file_off`` / ``plte_off``: where each file's staged zlib stream and its 768 palette bytes (``png_dec_full_stream``) lie; the
     ``plte_off`` of a file that is not colour type 3 is not looked at."""
-    items = (_lib.PngDecFullBatchItem * len(plans))()
-    for it, p, f, o, w, q in zip(items, plans, file_off, out_off, ws_off, plte_off):
-        it.plan, it.file_off, it.out_off, it.ws_off, it.plte_off = p, int(f), int(o), int(w), int(q)
-    return items
+    return _PNGF.items(plans, file_off, out_off, ws_off, plte_off)
 
 
 def png_decode_full_batch_u8(files, items, out, bgr=False, status=None, workspace=None, items_dev=None):
     """``png_decode_batch_u8`` for the full-format decoder, THREE launches (frcnn_png_decode_full_batch_u8): ``files`` holds every file's
     zlib stream and every palette file's 768 palette bytes, ``items`` the table (``png_full_batch_items``) -> status: int32 [n], per file
     0 or _lib.PNG_DEC_* bits ORed in (sticky).  ``items_dev``, ``status`` and ``workspace`` as there."""
-    _require_gpu()
-    n = len(items)
-    if not isinstance(items, ctypes.Array) or items._type_ is not _lib.PngDecFullBatchItem:
-        raise _lib.FrcnnError("png_decode_full_batch_u8: items must be a table made by png_full_batch_items")
-    if items_dev is None:
-        items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).cuda()
-    if status is None:
-        status = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
-    if workspace is None:
-        workspace = _ws(max((int(it.ws_off) + png_dec_full_workspace_bytes(it.plan) for it in items), default=0))
-    for name, t, dt in (("files", files, torch.uint8), ("out", out, torch.uint8), ("status", status, torch.int32),
-                        ("workspace", workspace, torch.uint8), ("items_dev", items_dev, torch.uint8)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-            raise _lib.FrcnnError(f"png_decode_full_batch_u8: {name} must be a contiguous {dt} device tensor")
-    if items_dev.numel() < ctypes.sizeof(items) or status.numel() < n:
-        raise _lib.FrcnnError(f"png_decode_full_batch_u8: items_dev of {items_dev.numel()} bytes / status of {status.numel()} words for {n} items")
-    _lib.call("frcnn_png_decode_full_batch_u8", ctypes.addressof(items), _p(items_dev), n, _p(files), files.numel(), 1 if bgr else 0,
-              _p(out), out.numel(), _p(status), _p(workspace), workspace.numel(), _stream())
-    return status
+    return _PNGF.decode(files, items, out, bgr, status, workspace, items_dev)
 
 
 def png_decode_full_u8(file_bytes, bgr=False):
     """``png_decode_u8`` through the full-format decoder: palette, 1/2/4/16-bit, grey + alpha and Adam7 files too."""
-    _require_gpu()
-    data = bytes(file_bytes)
-    plan = png_dec_full_plan(data)
-    stream, palette = png_dec_full_stream(data, plan)
-    files = torch.frombuffer(bytearray(stream + palette), dtype=torch.uint8).cuda()
-    out = torch.empty((int(plan.h), int(plan.w), 3), dtype=torch.uint8, device="cuda")
-    status = png_decode_full_batch_u8(files, png_full_batch_items([plan], [0], [0], [0], [len(stream)]), out.view(-1), bgr=bgr)
-    word = int(status.cpu()[0])
-    if word:
-        raise _lib.FrcnnError("png_decode_full_u8: the file is damaged (status %d: FRCNN_PNG_DEC_* in include/ext/frcnn_hip_png_dec.h)" % word)
-    return out
+    return _PNGF.decode_one(file_bytes, bgr)
 
 
 def split_detections(packed, rows=None):

@@ -176,6 +176,9 @@ def sound_cases(window_bytes=8192):
     stream = idat_payload(data)[0]
     assert len(stream) > 2 * window_bytes and (stream[2] >> 1) & 3 == 2, "not a dynamic block beyond the window"
     cases.append(("block_beyond_window", data, expected(noisy)))
+    # ---- exactly one row past a strip of 64 rows
+    rows65 = pattern(65, 6, 3, 65)
+    cases.append(("filter_mix_rgb_65rows", written(rows65, [4 if y % 64 else 3 for y in range(65)]), expected(rows65)))
     return cases
 
 

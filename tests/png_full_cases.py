@@ -143,6 +143,9 @@ def sound_cases():
     cases.append(("crop_adaptive_pil", buf.getvalue()))
     add("crop_adaptive_i1", np.asarray(pimg).astype(np.int64)[:, :, None], 3, 8, 1, mixed, bytes(pimg.getpalette()[:768]))
     add("crop_rgb_i1", crop().astype(np.int64), 2, 8, 1, mixed)
+    # ---- Adam7 at 2x2: four of the seven passes absent (1x1, where the first pass alone exists, is among the sizes above)
+    add("size_2x2_rgb_i1", samples(2, 2, 2, 8, 202), 2, 8, 1, mixed)
+    add("size_2x2_p1_i1", samples(2, 2, 3, 1, 203), 3, 1, 1, mixed, palette_of(2, 4))
     assert len({n for n, _ in cases}) == len(cases)
     return cases
 

@@ -99,10 +99,24 @@ def test_planner_accepts_the_supported_set():
         stream, palette = ops.png_dec_full_stream(data, plan)
         assert stream == info["stream"] and palette == info["palette"] and len(palette) == (768 if info["colour"] == 3 else 0), name
         assert ops.png_dec_full_workspace_bytes(plan) == (plan.inflated_len + 15) // 16 * 16, name
-    # a revision-1 plan restated says what the full planner says
-    for name, data in F.r1_cases()[:8]:
-        a, b = ops.png_dec_full_of(ops.png_dec_plan(data)), ops.png_dec_full_plan(data)
-        assert bytes(a) == bytes(b), name
+    # One chunk walker serves both planners.  A revision-1 plan restated says, field for field, what the full planner says, for every
+    # file of both tables that both accept; what revision 1 refuses of the full set it refuses with ITS words, by ITS order of precedence
+    # (palette, grey + alpha, depth, interlace).
+    both = 0
+    for name, data in F.all_sound() + sorted(F.damaged().items()):
+        full = ops.png_dec_full_plan(data)
+        if (full.colour_type in (0, 2, 6), full.bit_depth, full.interlace) == (True, 8, 0):
+            restated = ops.png_dec_full_of(ops.png_dec_plan(data))
+            assert [getattr(restated, f) for f, _ in full._fields_] == [getattr(full, f) for f, _ in full._fields_], name
+            both += 1
+        else:
+            want = ("palette (colour type 3)" if full.colour_type == 3 else "grey + alpha (colour type 4)" if full.colour_type == 4 else
+                    "%d-bit samples" % full.bit_depth if full.bit_depth != 8 else "interlaced (Adam7)")
+            with pytest.raises(ops.PngUnsupported) as err:
+                ops.png_dec_plan(data)
+            assert str(err.value) == "png_dec_plan: " + want, name
+    # (every file of revision 1's table is in the first class; of the 2 x 14 pair files all but (0, 8), (2, 8), (6, 8) without interlace in the second)
+    assert both >= len(F.r1_cases()) + 3 and len(F.all_sound()) + len(F.damaged()) - both >= 2 * len(F.PAIRS) - 3
 
 
 def test_planner_refuses_with_the_reason():
@@ -243,6 +257,50 @@ def test_argument_errors_return_before_any_device_call():
         b = Batch()
         setattr(b.items[item].plan, field, value)
         assert "item %d" % item in refused(b, "contradicts itself (%s)" % what)
+
+
+def test_argument_errors_agree_between_the_two_entry_points():
+    """One argument check serves frcnn_png_decode_batch_u8 and frcnn_png_decode_full_batch_u8: on the same four files and the same wrong
+    argument, the same FRCNN_E_ARG text but for the entry point's name.  Neither call reaches a device."""
+    _lib = _built()
+    from faster_rcnn_amd import ops
+    lib = _lib.load()
+    datas = [F.case("r1_" + n) for n in ("pil_17x23_c3_l6", "pil_33x65_c4_l6", "pil_1x7_c1_l6", "fixed")]
+
+    def message(setting, wrong):
+        dec = ops.PNG_DECODERS[setting]
+        plans = [dec.plan(d) for d in datas]
+        ws_off, ws = dec.layout(plans)
+        file_off = [sum(p.stream_len for p in plans[:i]) for i in range(5)]
+        out_off = [sum(p.h * p.w * 3 for p in plans[:i]) for i in range(5)]
+        a = dict(items=dec.items(plans, file_off, out_off, ws_off), items_dev=0x10000, n=4, files=0x20000, cap_files=file_off[4], out=0x30000,
+                 cap_out=out_off[4], status=0x40000, workspace=0x50000, cap_ws=ws)
+        wrong(a)
+        who = dec.decode_stem + "_batch_u8"
+        code = getattr(lib, "frcnn_" + who)(a["items"], a["items_dev"], a["n"], a["files"], a["cap_files"], 0, a["out"], a["cap_out"], a["status"],
+                                            a["workspace"], a["cap_ws"], None)
+        msg = (lib.frcnn_last_error() or b"").decode()
+        assert code == E_ARG and msg.startswith(who + ": "), (setting, code, msg)
+        return msg[len(who):]
+
+    def item(i, field, value, **more):
+        def wrong(a):
+            setattr(a["items"][i], field, value(a))
+            a.update({k: v(a) for k, v in more.items()})
+        return wrong
+    cases = [("null", lambda a, k=k: a.update({k: None})) for k in ("items", "items_dev", "files", "out", "status", "workspace")]
+    cases += [("n=0 outside 1..64", lambda a: a.update(n=0)), ("n=65 outside 1..64", lambda a: a.update(n=65)),
+              ("workspace must be", lambda a: a.update(workspace=0x50008)), ("status_dev must be", lambda a: a.update(status=0x40002)),
+              ("items_dev must be", lambda a: a.update(items_dev=0x10004)),
+              ("item 1: ws_off=", item(1, "ws_off", lambda a: a["items"][1].ws_off + 8, cap_ws=lambda a: a["cap_ws"] + 16)),
+              ("item 3: file_off=", lambda a: a.update(cap_files=a["cap_files"] - 1)),
+              ("item 3: out_off=", lambda a: a.update(cap_out=a["cap_out"] - 1)),
+              ("item 3: ws_off=", lambda a: a.update(cap_ws=a["cap_ws"] - 1)),
+              ("the output ranges of items 1 and 2 overlap", item(2, "out_off", lambda a: a["items"][1].out_off + 3)),
+              ("the workspace regions of items 0 and 3 overlap", item(3, "ws_off", lambda a: a["items"][0].ws_off))]
+    for word, wrong in cases:
+        one, full = message("device", wrong), message("device_full", wrong)
+        assert one == full and word in one, (word, one, full)
 
 
 def test_decoder_options(monkeypatch, tmp_path):
