@@ -288,6 +288,42 @@ class JpegDecBatchItem(ctypes.Structure):
     _fields_ = [("plan", JpegDecPlan), ("file_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("ws_off", ctypes.c_uint64)]
 
 
+JPEG_DEC_FULL_VERSION = 1       # include/ext/frcnn_hip_jpeg_dec_full.h FRCNN_JPEG_DEC_FULL_VERSION
+JPEG_DEC_FULL_MAX_SCANS = 64    # ... FRCNN_JPEG_DEC_FULL_MAX_SCANS
+JPEG_DEC_FULL_SIGNATURES = {
+    "frcnn_jpeg_dec_full_version": (I, []),
+    "frcnn_jpeg_dec_full_plan": (I, [P, c_size_t, P]),
+    "frcnn_jpeg_dec_full_workspace_bytes": (c_size_t, [P]),
+    "frcnn_jpeg_dec_full_batch_layout": (c_size_t, [P, I, P]),
+    "frcnn_jpeg_decode_full_batch_u8": (I, [P, P, I, P, c_size_t, I, P, c_size_t, P, P, c_size_t, P]),
+    "frcnn_jpeg_decode_full_u8": (I, [P, P, P, I, P, c_size_t, P, P, c_size_t, P]),
+}
+# FRCNN_JPEG_DEC_FULL_* status bits
+JPEG_DEC_FULL_BLOCKS, JPEG_DEC_FULL_ZIGZAG, JPEG_DEC_FULL_CODE, JPEG_DEC_FULL_TABLE, JPEG_DEC_FULL_EOBRUN = 1, 2, 4, 8, 16
+
+
+class JpegDecFullScan(ctypes.Structure):
+    """frcnn_jpeg_dec_full_scan_t (include/ext/frcnn_hip_jpeg_dec_full.h)."""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("off", "len", "restart_interval", "subsequence_bytes", "subsequences")] + \
+               [(k, ctypes.c_uint32 * 3) for k in ("dc_off", "dc_count", "ac_off", "ac_count")] + \
+               [(k, ctypes.c_uint8) for k in ("comps", "ss", "se", "ah", "al")] + [("reserved", ctypes.c_uint8 * 3)]
+
+
+class JpegDecFullPlan(ctypes.Structure):
+    """frcnn_jpeg_dec_full_plan_t (include/ext/frcnn_hip_jpeg_dec_full.h).  ``h`` / ``w`` / ``file_len``: the frame's, under the names
+    every decoder's plan has them."""
+    _fields_ = [("frame", JpegDecPlan), ("scans", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("scan", JpegDecFullScan * JPEG_DEC_FULL_MAX_SCANS)]
+    h = property(lambda self: self.frame.h)
+    w = property(lambda self: self.frame.w)
+    file_len = property(lambda self: self.frame.file_len)
+
+
+class JpegDecFullBatchItem(ctypes.Structure):
+    """frcnn_jpeg_dec_full_batch_item_t (include/ext/frcnn_hip_jpeg_dec_full.h)."""
+    _fields_ = [("plan", JpegDecFullPlan), ("file_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("ws_off", ctypes.c_uint64)]
+
+
 class ConvDesc(ctypes.Structure):
     """frcnn_conv_desc (include/frcnn_hip.h)."""
     _fields_ = [(k, ctypes.c_int32) for k in (
@@ -381,6 +417,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in JPEG_DEC_FULL_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_jpeg_dec_full_version() != JPEG_DEC_FULL_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_dec_full_version()} of the JPEG decoder's progressive extension, this "
+                         f"binding {JPEG_DEC_FULL_VERSION} (include/ext/frcnn_hip_jpeg_dec_full.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_png_dec_full_version() != PNG_DEC_FULL_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_png_dec_full_version()} of the PNG decoder's full-format extension, this "
                          f"binding {PNG_DEC_FULL_VERSION} (include/ext/frcnn_hip_png_dec_full.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -261,18 +261,18 @@ def _write_bytes(path, data):
 
 
 JPEG_SUFFIXES = (".jpg", ".jpeg")
-JPEG_DECODERS = ("host", "device")
+JPEG_DECODERS = ("host", "device", "device_full")
 
 
 PNG_DECODERS = ("host", "device", "device_full")
 
 
 def frame_filenames(input_dir, jpeg_decoder="host", png_decoder="host"):
-    """``png_filenames`` and, with ``jpeg_decoder`` = "device", the ``*.jpg`` / ``*.jpeg`` names too: the input frames, sorted.
+    """``png_filenames`` and, with ``jpeg_decoder`` = "device" or "device_full", the ``*.jpg`` / ``*.jpeg`` names too: the input frames, sorted.
     ``png_decoder`` ("host" / "device" / "device_full": who decodes the ``*.png`` frames) is checked and changes no name."""
     from .feed import jpeg_decoder_option, png_decoder_option
     png_decoder_option(png_decoder, "png_decoder")
-    if jpeg_decoder_option(jpeg_decoder, "jpeg_decoder") != "device":
+    if jpeg_decoder_option(jpeg_decoder, "jpeg_decoder") == "host":
         return png_filenames(input_dir)
     return sorted(f for f in os.listdir(input_dir) if f.endswith(".png") or f.lower().endswith(JPEG_SUFFIXES))
 
@@ -342,7 +342,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     ``jpeg_encoder``: "host" or "device", as ``png_encoder``; ``jpeg_quality``: 1..100, None = JPEG_QUALITY.
     ``jpeg_subsampling``: 444 or 420, ``jpeg_huffman``: "standard" or "optimized" -- of JPEG frames, whichever encoder writes them;
     None = ``default_jpeg_subsampling()`` / ``default_jpeg_huffman()``.
-    ``jpeg_decoder``: "host" or "device": who decodes ``.jpg`` INPUT frames the device decoder supports (captured path only); None =
+    ``jpeg_decoder``: "host", "device" or "device_full" (csrc/jpeg_dec_full.hip: progressive files too): who decodes ``.jpg`` INPUT
+    frames the device decoder supports (captured path only); None =
     what ``entry.jpeg_decoder()`` says (FRCNN_ENTRY_JPEG_DECODER, default "host").
     ``png_decoder``: "host", "device" or "device_full" (csrc/png_dec_full.hip: palette, 1/2/4/16-bit, grey + alpha and Adam7 files too):
     who decodes ``.png`` INPUT frames the device decoder supports (captured path only; the decode
@@ -352,7 +353,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
         entry.set_png_decoder(png_decoder)
-    device_decode = entry.jpeg_decoder() == "device"
+    device_decode = entry.jpeg_decoder()                      # "host", "device" or "device_full"
     device_png = entry.png_decoder()                          # "host", "device" or "device_full"
     png_encoder, png_compress = png_options(png_encoder, png_compress)
     frame_format, jpeg_encoder, jpeg_quality = jpeg_options(frame_format, jpeg_encoder, jpeg_quality, png_encoder, png_compress)
@@ -391,14 +392,16 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
 
     def load(path):                                       # (decode thread) -> (frame, resized, ratio, pixels)
         frame = None
-        if device_decode and path.lower().endswith(JPEG_SUFFIXES):
+        if device_decode != "host" and path.lower().endswith(JPEG_SUFFIXES):
             with open(path, "rb") as f:
                 data = f.read()
-            try:
-                plan = ops.jpeg_dec_plan(data)
-                frame = _FileFrame(data, path, (int(plan.h), int(plan.w)))
-            except ops.JpegUnsupported:
-                pass                                          # (progressive, CMYK, ...: PIL below)
+            for planner in (ops.jpeg_dec_plan,) + ((ops.jpeg_dec_full_plan,) if device_decode == "device_full" else ()):
+                try:
+                    plan = planner(data)
+                    frame = _FileFrame(data, path, (int(plan.h), int(plan.w)))
+                    break
+                except ops.JpegUnsupported:
+                    pass                                      # (progressive under "device", CMYK, ...: PIL below)
         elif device_png != "host" and path.lower().endswith(".png"):
             from .feed import plan_png
             with open(path, "rb") as f:
@@ -501,8 +504,9 @@ def build_parser():
                    help="who encodes JPEG frames: host = PIL on writer threads, device = inside the detection pass on the GPU "
                         "(FRCNN_ANNOTATE_JPEG_ENCODER sets the default; needs --frame_format jpg)")
     p.add_argument("--jpeg_decoder", dest="jpeg_decoder", choices=JPEG_DECODERS, default=None,
-                   help="who decodes .jpg INPUT frames: host (PIL) or device (csrc/jpeg_dec.hip; input_dir's *.jpg / *.jpeg are then "
-                        "taken beside its *.png); default: FRCNN_ENTRY_JPEG_DECODER, else host")
+                   help="who decodes .jpg INPUT frames: host (PIL), device (csrc/jpeg_dec.hip; input_dir's *.jpg / *.jpeg are then "
+                        "taken beside its *.png) or device_full (progressive files too: csrc/jpeg_dec_full.hip); default: "
+                        "FRCNN_ENTRY_JPEG_DECODER, else host")
     p.add_argument("--png_decoder", dest="png_decoder", choices=PNG_DECODERS, default=None,
                    help="who decodes .png INPUT frames: host (PIL), device (csrc/png_dec.hip: 8-bit grey / RGB / RGBA without interlace) or "
                         "device_full (csrc/png_dec_full.hip: palette, 1/2/4/16-bit, grey + alpha and Adam7 files too); PIL for the files the "

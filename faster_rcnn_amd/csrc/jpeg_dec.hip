@@ -26,57 +26,16 @@
 // each.  A table of items (plan + where the file, the frame and the workspace region lie) in device memory replaces the by-value plan;
 // a workgroup finds its item from its grid index and returns as a whole where the grid, sized by the batch's largest item, reaches past
 // its own.  Every bound above holds per item: its status word, its workspace region, its output range.
-#include "common.h"
-#include "../../include/ext/frcnn_hip_jpeg_dec.h"
+//
+// The table build, the code lookup, the byte-stuffing / RSTm window and the __device__ bodies of the DC, IDCT and colour kernels live in
+// jpeg_dec_common.h: the decoder of progressive files (jpeg_dec_full.hip) runs the same ones.
+#include "jpeg_dec_common.h"
 #include "../../include/ext/frcnn_hip_jpeg_dec_batch.h"
 
 namespace frcnn {
 namespace {
 
-constexpr int DEC_MAX_LANES = 1024;
-constexpr uint32_t DEC_MIN_S = 32;
-constexpr uint32_t DEC_MAX_SCAN = FRCNN_JPEG_DEC_MAX_SCAN;    // (see the header: what bounds the entropy kernel's worst case)
-constexpr int DEC_LOOK = 9;
-constexpr int DEC_IDCT_THREADS = 256, DEC_IDCT_BLOCKS = DEC_IDCT_THREADS / 8;
-constexpr int DEC_COLOUR_THREADS = 256;
-constexpr int DEC_DC_THREADS = 1024;
-
-using Plan = frcnn_jpeg_dec_plan_t;
 using Item = frcnn_jpeg_dec_batch_item_t;
-
-struct DecZigzag { uint8_t at[64]; };
-// zigzag position -> natural index 8 * v + u
-__constant__ DecZigzag DEC_ZIGZAG = {{0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                                      35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}};
-
-// ------------------------------------------------------------------------------------------------------------------- host sizes
-struct DecPlanes { uint8_t* p[3]; int pw[3]; };
-struct DecLayout { size_t coef, flags, plane[3], total; int pw[3], ph[3]; };
-
-// (also on the device: a batched kernel finds its item's arrays from the plan it reads)
-__host__ __device__ inline DecLayout dec_layout(const Plan& p) {
-    DecLayout l = {};
-    size_t at = 0;
-    l.coef = at; at += align16((size_t)p.expected_blocks * 128);
-    l.flags = at; at += align16((size_t)p.expected_blocks);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {                               // (constant indices: the device keeps the struct in registers)
-        if (c >= p.components) continue;
-        l.pw[c] = p.mcus_x * 8 * (c ? 1 : p.hs);
-        l.ph[c] = p.mcus_y * 8 * (c ? 1 : p.vs);
-        l.plane[c] = at; at += align16((size_t)l.pw[c] * (size_t)l.ph[c]);
-    }
-    l.total = at;
-    return l;
-}
-
-inline void dec_subsequences(uint32_t scan_len, uint32_t* S, uint32_t* N) {
-    uint32_t s = ((scan_len + DEC_MAX_LANES - 1) / DEC_MAX_LANES + 3) / 4 * 4;
-    s = s < DEC_MIN_S ? DEC_MIN_S : s;
-    const uint32_t n = (scan_len + s - 1) / s;
-    *S = s;
-    *N = n < 1 ? 1 : n;
-}
 
 // nullptr when the plan's fields agree with each other (what the kernels' bounds rest on), else what is wrong
 inline const char* dec_plan_fault(const Plan& p) {
@@ -103,14 +62,6 @@ inline const char* dec_plan_fault(const Plan& p) {
 // ------------------------------------------------------------------------------------------------------------- entropy decoding
 constexpr uint32_t ST_BLOCKS = FRCNN_JPEG_DEC_BLOCKS, ST_ZIGZAG = FRCNN_JPEG_DEC_ZIGZAG, ST_CODE = FRCNN_JPEG_DEC_CODE, ST_TABLE = FRCNN_JPEG_DEC_TABLE;
 
-struct HuffLds {
-    uint16_t look[4][1 << DEC_LOOK];    // [class * 2 + id]
-    uint8_t vals[4][256];
-    uint8_t bits[4][16];
-    int maxcode[4][17], delta[4][17];   // per length 1..16: the largest code (-1: none), symbol index = code + delta
-    int count[4];
-};
-
 struct EntropyCtx {
     const uint8_t* scan;
     uint32_t len;                       // bytes of the segment
@@ -125,54 +76,22 @@ struct EntropyCtx {
 // state word: zigzag index | block within the MCU << 8 | restart pending << 16
 struct DecState { uint32_t pos, bz; };
 
-__device__ __forceinline__ uint32_t rd(const EntropyCtx& c, uint32_t r) { return r < c.len ? (uint32_t)c.scan[r] : 0u; }
-
 // F_i: whole symbols from ``st`` until the next would start at or past ``end`` (a bit position); -> blocks completed.  WRITE: the final
 // walk, ``blk`` the index of the block the entry state stands in.
 template <bool WRITE>
 __device__ uint32_t dec_run(const EntropyCtx& c, uint32_t end, DecState& st, uint32_t blk, uint32_t* status) {
     uint32_t pos = st.pos, z = st.bz & 255u, b = (st.bz >> 8) & 255u, rst = (st.bz >> 16) & 1u, done = 0, flagged = 0;
     while (pos < end) {
-        // ---- the window: five data bytes from byte pos >> 3 on, the raw index of each, the bit at which an RSTm marker stands
-        uint32_t r = pos >> 3, idx[5], mraw = 0;
-        int mbit = -1, ebit = -1;
-        unsigned long long w = 0;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            idx[j] = r;
-            if (r >= c.len && ebit < 0 && mbit < 0) ebit = 8 * j;
-            uint32_t v = rd(c, r);
-            if (mbit >= 0) {
-                v = 0;
-            } else if (v == 0xFFu) {
-                const uint32_t nxt = rd(c, r + 1u);
-                if (nxt == 0u) r += 1u;
-                else if ((nxt & 0xF8u) == 0xD0u) { mbit = 8 * j; mraw = r; v = 0; }
-            }
-            w = (w << 8) | v;
-            if (mbit < 0) r += 1u;
-        }
+        const DecWindow win = dec_window(c.scan, c.len, pos);           // (the window, its marker and its end: jpeg_dec_common.h)
+        const unsigned long long w = win.w;
+        const int mbit = win.mbit, ebit = win.ebit;
         const uint32_t o = pos & 7u;
         const int comp = (int)b < c.luma ? 0 : (int)b - c.luma + 1;
         const int slot = z == 0 ? (int)((c.tables >> comp) & 1u) : 2 + (int)((c.tables >> (4 + comp)) & 1u);
         // ---- the code
         const uint32_t top = (uint32_t)(w >> (24u - o)) & 0xFFFFu;
-        uint32_t length, sym = 0, flag = 0;
-        const uint32_t e = c.huff->look[slot][top >> (16 - DEC_LOOK)];
-        if (e) {
-            length = e >> 8; sym = e & 255u;
-        } else {
-            length = 16; flag = ST_CODE;
-            for (int l = 1; l <= 16; ++l) {
-                const int code = (int)(top >> (16 - l));
-                if (code <= c.huff->maxcode[slot][l]) {
-                    const int k = code + c.huff->delta[slot][l];
-                    length = (uint32_t)l;
-                    if (k >= 0 && k < c.huff->count[slot]) { sym = c.huff->vals[slot][k]; flag = 0; } else flag = ST_TABLE;
-                    break;
-                }
-            }
-        }
+        uint32_t sym, flag;
+        const uint32_t length = dec_huff_code(*c.huff, slot, top, ST_CODE, ST_TABLE, &sym, &flag);
         const uint32_t size = sym & 15u;
         if ((z == 0 && sym > 11u) || (z > 0 && size > 10u)) flag |= ST_TABLE;
         const uint32_t n = length + size;
@@ -182,7 +101,7 @@ __device__ uint32_t dec_run(const EntropyCtx& c, uint32_t end, DecState& st, uin
                     for (uint32_t k = z; k < 64u; ++k) c.coef[(size_t)blk * 64 + DEC_ZIGZAG.at[k]] = 0;
                 ++blk; ++done;
             }
-            pos = (mraw + 2u) * 8u; b = 0; z = 0; rst = 1;
+            pos = (win.mraw + 2u) * 8u; b = 0; z = 0; rst = 1;
             continue;
         }
         if (ebit >= 0 && o + n > (uint32_t)ebit) {              // ... past the end of the segment (the last padding): abandoned, the end
@@ -214,27 +133,12 @@ __device__ uint32_t dec_run(const EntropyCtx& c, uint32_t end, DecState& st, uin
             b = (int)b + 1 < c.bpm ? b + 1u : 0u;
             rst = b ? rst : 0u;
         }
-        const uint32_t q = o + n, at = q >> 3;                  // (q <= 7 + 31: at <= 4)
-        uint32_t ri = idx[0];
-#pragma unroll
-        for (int j = 1; j < 5; ++j) ri = at == (uint32_t)j ? idx[j] : ri;
-        pos = ri * 8u + (q & 7u);
+        pos = dec_window_pos(win, o + n);                       // (o + n <= 7 + 31)
     }
     st.pos = pos;
     st.bz = z | (b << 8) | (rst << 16);
     if (WRITE) *status |= flagged;
     return done;
-}
-
-// inclusive sum over the wave
-__device__ __forceinline__ uint32_t dec_wave_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
 }
 
 // The entropy stage of ONE file by the whole workgroup (blockDim.x a multiple of 64, >= plan.subsequences; lanes past the file's
@@ -246,52 +150,11 @@ __device__ __forceinline__ void dec_entropy_body(const uint8_t* file, const Plan
     __shared__ uint32_t s_changed, s_status;
     const uint32_t tid = threadIdx.x, threads = blockDim.x;
 
-    // ---- the Huffman tables: BITS and HUFFVAL from the file, maxcode / delta per length (one lane per table), then the lookahead
-    // table: one lane per symbol finds its code and fills the 2^(9 - length) entries that start with it
-    for (uint32_t x = tid; x < 4u << DEC_LOOK; x += threads) s_huff.look[x >> DEC_LOOK][x & ((1u << DEC_LOOK) - 1u)] = 0;
-    for (uint32_t x = tid; x < 4u * 256u; x += threads) {
-        const uint32_t t = x >> 8, j = x & 255u, off = plan.dht_off[t >> 1][t & 1], n = off ? plan.dht_count[t >> 1][t & 1] : 0u;
-        s_huff.vals[t][j] = j < n ? file[off + 16u + j] : (uint8_t)0;
-        if (j < 16u) s_huff.bits[t][j] = off ? file[off + j] : (uint8_t)0;
-    }
+    // ---- the Huffman tables (slot = class * 2 + id), from the DHT payloads in the file
     if (tid == 0) { s_changed = 0; s_status = 0; }
-    __syncthreads();
-    if (tid < 4u) {
-        int code = 0, k = 0;
-        s_huff.count[tid] = plan.dht_off[tid >> 1][tid & 1] ? (int)plan.dht_count[tid >> 1][tid & 1] : 0;
-        for (int l = 1; l <= 16; ++l) {
-            const int nb = s_huff.bits[tid][l - 1];
-            s_huff.maxcode[tid][l] = -1;
-            s_huff.delta[tid][l] = 0;
-            if (nb) {
-                s_huff.delta[tid][l] = k - code;
-                code += nb; k += nb;
-                s_huff.maxcode[tid][l] = code - 1;
-            }
-            code <<= 1;
-        }
-    }
-    __syncthreads();
-    for (uint32_t x = tid; x < 4u * 256u; x += threads) {
-        const uint32_t t = x >> 8;
-        const int j = (int)(x & 255u);
-        if (j >= s_huff.count[t]) continue;
-        int k = 0;
-        for (int l = 1; l <= DEC_LOOK; ++l) {
-            const int nb = s_huff.bits[t][l - 1];
-            if (j < k + nb) {
-                const int code = j - s_huff.delta[t][l];
-                if (code >= 0 && code < (1 << l)) {
-                    const uint16_t e = (uint16_t)((l << 8) | s_huff.vals[t][j]);
-                    const int first = code << (DEC_LOOK - l);
-                    for (int i = 0; i < (1 << (DEC_LOOK - l)); ++i) s_huff.look[t][first + i] = e;
-                }
-                break;
-            }
-            k += nb;
-        }
-    }
-    __syncthreads();
+    const uint32_t t_off[4] = {plan.dht_off[0][0], plan.dht_off[0][1], plan.dht_off[1][0], plan.dht_off[1][1]};
+    const uint32_t t_n[4] = {plan.dht_count[0][0], plan.dht_count[0][1], plan.dht_count[1][0], plan.dht_count[1][1]};
+    dec_huff_build(s_huff, file, t_off, t_n);
 
     EntropyCtx c;
     c.scan = file + plan.scan_off;
@@ -385,48 +248,6 @@ __global__ void __launch_bounds__(DEC_MAX_LANES) k_jpeg_dec_entropy_batch(const 
     dec_entropy_body(a.file, it.plan, a.coef, a.flags, status + blockIdx.x);
 }
 
-// One workgroup per component.  Its blocks in coding order, a stretch per lane: (cut seen, sum since the cut or the stretch's start)
-// folded per stretch, scanned across the lanes (Hillis-Steele in LDS), then each stretch written with the sum that flows into it.
-__device__ __forceinline__ void dec_dc_body(const Plan& plan, uint32_t comp, int16_t* coef, const uint8_t* flags) {
-    __shared__ int s_sum[DEC_DC_THREADS];
-    __shared__ uint32_t s_cut[DEC_DC_THREADS];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t bpm = (uint32_t)plan.blocks_per_mcu, luma = plan.components == 3 ? (uint32_t)(plan.hs * plan.vs) : 1u;
-    const uint32_t mcus = (uint32_t)plan.mcus_x * (uint32_t)plan.mcus_y;
-    const uint32_t n = comp == 0 ? mcus * luma : mcus;          // blocks of this component
-    const uint32_t per = (n + DEC_DC_THREADS - 1) / DEC_DC_THREADS;
-    const uint32_t t0 = tid * per < n ? tid * per : n, t1 = t0 + per < n ? t0 + per : n;
-    auto block_of = [&](uint32_t t) { return comp == 0 ? (t / luma) * bpm + t % luma : t * bpm + luma + comp - 1u; };
-    int sum = 0;
-    uint32_t cut = 0;
-    for (uint32_t t = t0; t < t1; ++t) {
-        const uint32_t k = block_of(t);
-        const int d = coef[(size_t)k * 64];
-        if (flags[k]) { sum = d; cut = 1; } else sum += d;
-    }
-    s_sum[tid] = sum;
-    s_cut[tid] = cut;
-    __syncthreads();
-    for (uint32_t d = 1; d < (uint32_t)DEC_DC_THREADS; d <<= 1) {
-        int ps = 0;
-        uint32_t pc = 0;
-        if (tid >= d) { ps = s_sum[tid - d]; pc = s_cut[tid - d]; }
-        __syncthreads();
-        if (tid >= d) {
-            if (!s_cut[tid]) s_sum[tid] += ps;
-            s_cut[tid] |= pc;
-        }
-        __syncthreads();
-    }
-    int running = tid ? s_sum[tid - 1u] : 0;
-    for (uint32_t t = t0; t < t1; ++t) {
-        const uint32_t k = block_of(t);
-        const int d = coef[(size_t)k * 64];
-        running = flags[k] ? d : running + d;
-        coef[(size_t)k * 64] = (int16_t)running;
-    }
-}
-
 __global__ void __launch_bounds__(DEC_DC_THREADS) k_jpeg_dec_dc(Plan plan, int16_t* coef, const uint8_t* flags) {
     dec_dc_body(plan, blockIdx.x, coef, flags);
 }
@@ -439,79 +260,6 @@ __global__ void __launch_bounds__(DEC_DC_THREADS) k_jpeg_dec_dc_batch(const Item
     dec_dc_body(it.plan, blockIdx.x, a.coef, a.flags);
 }
 
-// jidctint's 8-point pass (CONST_BITS 13): x in, the eight outputs descaled by SHIFT.  The sums are formed in uint32_t: the same bits as
-// int for every sound file (|sum| < 2^31), and a defined wrap instead of a signed overflow for the coefficients of a damaged one.
-template <int SHIFT>
-__device__ __forceinline__ void idct_1d(const int (&xi)[8], int (&y)[8]) {
-    using U = uint32_t;
-    U x[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) x[k] = (U)xi[k];
-    constexpr U N_0_899 = (U)-7373, N_2_562 = (U)-20995, N_1_961 = (U)-16069, N_0_390 = (U)-3196;
-    U z1 = (x[2] + x[6]) * 4433u;
-    const U tmp2 = z1 - x[6] * 15137u, tmp3 = z1 + x[2] * 6270u;
-    const U tmp0 = (x[0] + x[4]) * 8192u, tmp1 = (x[0] - x[4]) * 8192u;
-    const U tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-    U t0 = x[7], t1 = x[5], t2 = x[3], t3 = x[1];
-    z1 = t0 + t3;
-    U z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
-    const U z5 = (z3 + z4) * 9633u;
-    t0 *= 2446u; t1 *= 16819u; t2 *= 25172u; t3 *= 12299u;
-    z1 *= N_0_899; z2 *= N_2_562; z3 = z3 * N_1_961 + z5; z4 = z4 * N_0_390 + z5;
-    t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
-    constexpr U HALF = 1u << (SHIFT - 1);
-    y[0] = (int)(tmp10 + t3 + HALF) >> SHIFT; y[7] = (int)(tmp10 - t3 + HALF) >> SHIFT;
-    y[1] = (int)(tmp11 + t2 + HALF) >> SHIFT; y[6] = (int)(tmp11 - t2 + HALF) >> SHIFT;
-    y[2] = (int)(tmp12 + t1 + HALF) >> SHIFT; y[5] = (int)(tmp12 - t1 + HALF) >> SHIFT;
-    y[3] = (int)(tmp13 + t0 + HALF) >> SHIFT; y[4] = (int)(tmp13 - t0 + HALF) >> SHIFT;
-}
-
-// Eight lanes per block: lane = column in the first pass, row in the second; the 8x8 intermediate through LDS (row stride 9).
-__device__ __forceinline__ void dec_idct_body(const uint8_t* file, const Plan& plan, const int16_t* coef, const DecPlanes planes, uint32_t group) {
-    __shared__ int s_ws[DEC_IDCT_BLOCKS][72];
-    __shared__ uint16_t s_q[3][64];                             // natural order
-    const uint32_t tid = threadIdx.x, sub = tid >> 3, lane = tid & 7u;
-    for (uint32_t x = tid; x < (uint32_t)plan.components * 64u; x += DEC_IDCT_THREADS)
-        s_q[x >> 6][DEC_ZIGZAG.at[x & 63u]] = file[plan.dqt_off[x >> 6] + (x & 63u)];
-    __syncthreads();
-    const unsigned long long blk = (unsigned long long)group * DEC_IDCT_BLOCKS + sub;
-    const bool live = blk < plan.expected_blocks;
-    const uint32_t bpm = (uint32_t)plan.blocks_per_mcu, luma = plan.components == 3 ? (uint32_t)(plan.hs * plan.vs) : 1u;
-    const uint32_t m = live ? (uint32_t)(blk / bpm) : 0u, b = live ? (uint32_t)(blk % bpm) : 0u;
-    const uint32_t comp = b < luma ? 0u : b - luma + 1u;
-    if (live) {
-        const int16_t* src = coef + (size_t)blk * 64;
-        int x[8], y[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) x[r] = (int)src[8 * r + lane] * (int)s_q[comp][8 * r + lane];
-        idct_1d<11>(x, y);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) s_ws[sub][9 * r + lane] = y[r];
-    }
-    __syncthreads();
-    if (live) {
-        int x[8], y[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) x[k] = s_ws[sub][9 * lane + k];
-        idct_1d<18>(x, y);
-        uint32_t lo = 0, hi = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int v = y[k] + 128;
-            const uint32_t u = (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-            if (k < 4) lo |= u << (8 * k); else hi |= u << (8 * (k - 4));
-        }
-        const uint32_t my = m / (uint32_t)plan.mcus_x, mx = m - my * (uint32_t)plan.mcus_x;
-        const uint32_t by = comp == 0 ? my * (uint32_t)plan.vs + b / (uint32_t)plan.hs : my;
-        const uint32_t bx = comp == 0 ? mx * (uint32_t)plan.hs + b % (uint32_t)plan.hs : mx;
-        uint8_t* plane = comp == 0 ? planes.p[0] : (comp == 1 ? planes.p[1] : planes.p[2]);
-        const int pw = comp == 0 ? planes.pw[0] : (comp == 1 ? planes.pw[1] : planes.pw[2]);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(plane + ((size_t)by * 8 + lane) * (size_t)pw + (size_t)bx * 8);
-        dst[0] = lo;                                            // (planes are 16-byte aligned, their widths multiples of 8)
-        dst[1] = hi;
-    }
-}
-
 __global__ void __launch_bounds__(DEC_IDCT_THREADS) k_jpeg_dec_idct(const uint8_t* file, Plan plan, const int16_t* coef, DecPlanes planes) {
     dec_idct_body(file, plan, coef, planes, blockIdx.x);
 }
@@ -522,45 +270,6 @@ __global__ void __launch_bounds__(DEC_IDCT_THREADS) k_jpeg_dec_idct_batch(const 
     if ((unsigned long long)blockIdx.x * DEC_IDCT_BLOCKS >= it.plan.expected_blocks) return;
     const DecItemArrays a = dec_item_arrays(it, files, workspace);
     dec_idct_body(a.file, it.plan, a.coef, a.planes, blockIdx.x);
-}
-
-// a chroma sample at full size: libjpeg's fancy upsampling; a plane of width <= 2 is replicated
-__device__ __forceinline__ int dec_chroma(const uint8_t* plane, int pw, const Plan& plan, int x, int y) {
-    if (plan.hs == 1) return plane[(size_t)y * pw + x];
-    const int n = (plan.w + 1) >> 1, i = x >> 1;
-    if (plan.vs == 1) {
-        const uint8_t* s = plane + (size_t)y * pw;
-        if (n <= 2 || x == 0 || x == 2 * n - 1) return s[i];
-        return (x & 1) ? (3 * s[i] + s[i + 1] + 2) >> 2 : (3 * s[i] + s[i - 1] + 1) >> 2;
-    }
-    const int rows = (plan.h + 1) >> 1, yr = y >> 1;
-    const uint8_t* near = plane + (size_t)yr * pw;
-    if (n <= 2) return near[i];
-    const int yf = (y & 1) ? (yr + 1 < rows ? yr + 1 : rows - 1) : (yr > 0 ? yr - 1 : 0);
-    const uint8_t* far = plane + (size_t)yf * pw;
-    const int cs = 3 * near[i] + far[i];
-    if (x == 0) return (4 * cs + 8) >> 4;
-    if (x == 2 * n - 1) return (4 * cs + 7) >> 4;
-    return (x & 1) ? (3 * cs + 3 * near[i + 1] + far[i + 1] + 7) >> 4 : (3 * cs + 3 * near[i - 1] + far[i - 1] + 8) >> 4;
-}
-
-__device__ __forceinline__ void dec_colour_body(const Plan& plan, const DecPlanes planes, int bgr, uint8_t* out, int x, int y) {
-    if (x >= plan.w || y >= plan.h) return;
-    const int lum = planes.p[0][(size_t)y * planes.pw[0] + x];
-    int r = lum, g = lum, b = lum;
-    if (plan.components == 3) {
-        const int cb = dec_chroma(planes.p[1], planes.pw[1], plan, x, y) - 128, cr = dec_chroma(planes.p[2], planes.pw[2], plan, x, y) - 128;
-        r = lum + ((91881 * cr + 32768) >> 16);
-        b = lum + ((116130 * cb + 32768) >> 16);
-        g = lum + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-        r = r < 0 ? 0 : (r > 255 ? 255 : r);
-        g = g < 0 ? 0 : (g > 255 ? 255 : g);
-        b = b < 0 ? 0 : (b > 255 ? 255 : b);
-    }
-    uint8_t* p = out + ((size_t)y * (size_t)plan.w + (size_t)x) * 3;
-    p[0] = (uint8_t)(bgr ? b : r);
-    p[1] = (uint8_t)g;
-    p[2] = (uint8_t)(bgr ? r : b);
 }
 
 __global__ void __launch_bounds__(DEC_COLOUR_THREADS) k_jpeg_dec_colour(Plan plan, DecPlanes planes, int bgr, uint8_t* out) {

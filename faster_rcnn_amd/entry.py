@@ -92,13 +92,14 @@ WARMUP_PASSES = max(1, int(os.environ.get("FRCNN_ENTRY_WARMUP", "1")))
 # file-backed frames go up in the decoder's channel order and are swapped to BGR by the device resize (0: reverse on the host as before)
 RGB_UPLOAD = os.environ.get("FRCNN_ENTRY_RGB_UPLOAD", "1") != "0"
 # who decodes a file-backed frame: "host" (PIL, the default) or "device" (ops.jpeg_decode_batch_u8 in front of the replay, for the files
-# its planner supports, in per-geometry and canvas passes alike; PIL for the rest).  FRCNN_ENTRY_JPEG_DECODER, or
+# its planner supports, in per-geometry and canvas passes alike; PIL for the rest) or "device_full" (as "device", and
+# ops.jpeg_decode_full_batch_u8 beside it for the progressive files ITS planner supports).  FRCNN_ENTRY_JPEG_DECODER, or
 # ``set_jpeg_decoder`` (voc_dets / annotate_video --jpeg_decoder), which wins.
 _JPEG_DECODER = None
 
 
 def set_jpeg_decoder(value):
-    """"host" / "device" for every DetectionEntry of the process from now on; None: back to FRCNN_ENTRY_JPEG_DECODER."""
+    """"host" / "device" / "device_full" for every DetectionEntry of the process from now on; None: back to FRCNN_ENTRY_JPEG_DECODER."""
     global _JPEG_DECODER
     from .feed import jpeg_decoder_option
     _JPEG_DECODER = None if value is None else jpeg_decoder_option(value, "jpeg_decoder")
@@ -286,7 +287,7 @@ class _Slot:
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
-                 "jpg_count", "png_items", "png_dec")
+                 "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs")
 
     def __init__(self):
         for name in self.__slots__:
@@ -655,8 +656,8 @@ class DetectionEntry:
         Returns (array, H, W, src or None, flip)."""
         if self.device_preprocess and _declares(image, "raw") and _declares(image, "height"):
             H, W, flip = int(image.height), int(image.width), bool(getattr(image, "flipped", False))
-            jpeg_dev, png_dev = jpeg_decoder() == "device", png_decoder()
-            if RGB_UPLOAD and (jpeg_dev or png_dev != "host"):
+            jpeg_dev, png_dev = jpeg_decoder(), png_decoder()
+            if RGB_UPLOAD and (jpeg_dev != "host" or png_dev != "host"):
                 from . import feed
                 # None: in-memory pixels, or a file the device decoders do not take
                 planned = feed.plan_entry_file(image, jpeg=jpeg_dev, png=png_dev)
@@ -898,10 +899,13 @@ class DetectionEntry:
         ``files``: (frame index, JpegFile) of the pass's file-backed frames; item k is files[k], its output frame i's source segment.  A
         file that fills several frames (the padding of a short group) is staged once."""
         B = s.batch
-        files.sort(key=lambda t: isinstance(t[1], PngFile))         # (in place, stable: the .jpg items first, then the .png items)
-        nj = sum(1 for _, f in files if not isinstance(f, PngFile))
+        kind_of = lambda f: 2 if isinstance(f, PngFile) else int(isinstance(f.plan, _lib.JpegDecFullPlan))
+        files.sort(key=lambda t: kind_of(t[1]))                     # (in place, stable: the baseline .jpg items, the progressive ones, the .png items)
+        nj, nf = (sum(1 for _, f in files if kind_of(f) == k) for k in (0, 1))
         item = ctypes.sizeof(_lib.JpegDecBatchItem)
-        table = (B * (item + ctypes.sizeof(_lib.PngDecFullBatchItem)) + 255) // 256 * 256      # [B JPEG items | B PNG items], room for the larger kind of PNG item
+        first_full = B * (item + ctypes.sizeof(_lib.PngDecFullBatchItem))      # [B JPEG items | B PNG items], room for the larger kind of PNG item
+        # ... | B progressive items] only in a pass that holds such a file: their items are 5 KB each
+        table = (first_full + (B * ctypes.sizeof(_lib.JpegDecFullBatchItem) if nf else 0) + 255) // 256 * 256
         at, seen, file_off = 0, {}, []
         for _, f in files:
             if id(f) not in seen:
@@ -912,15 +916,16 @@ class DetectionEntry:
             size = table + (at + at // 4 + 255) // 256 * 256
             s.jpg_pin = torch.empty(size, dtype=torch.uint8).pin_memory()
             s.jpg_area = torch.empty(size, dtype=torch.uint8, device="cuda")
-            s.jpg_dev = s.jpg_area[table:]                           # the file area; the table lies in front of it
+        s.jpg_dev = s.jpg_area[table:]                               # the file area; the table lies in front of it
         plans = [f.plan for _, f in files]
         # one kind of PNG item per pass: with a full-format plan among them (png_decoder "device_full") revision-1 plans, which a pass
         # can only hold when the setting changed under way, are restated as full-format ones
-        full = any(isinstance(p, _lib.PngDecFullPlan) for p in plans[nj:])
+        np_ = nj + nf                                                # the first .png item
+        full = any(isinstance(p, _lib.PngDecFullPlan) for p in plans[np_:])
         s.png_dec = ops.PNG_DECODERS["device_full" if full else "device"]
         if full:
-            plans[nj:] = [ops.png_dec_full_of(p) if isinstance(p, _lib.PngDecPlan) else p for p in plans[nj:]]
-        kinds = ((ops.JPEG_DECODER, 0, nj), (s.png_dec, nj, len(plans)))    # per decoder: its items of the pass
+            plans[np_:] = [ops.png_dec_full_of(p) if isinstance(p, _lib.PngDecPlan) else p for p in plans[np_:]]
+        kinds = ((ops.JPEG_DECODER, 0, nj), (ops.JPEG_FULL_DECODER, nj, np_), (s.png_dec, np_, len(plans)))    # per decoder: its items of the pass
         ws_off, need = [], 0
         for dec, lo, hi in kinds:
             for k in range(lo, hi, dec.batch_max):                  # (a call takes batch_max items: its regions behind the last call's)
@@ -934,12 +939,13 @@ class DetectionEntry:
             s.jpg_status_pin = torch.zeros(B, dtype=torch.int32).pin_memory()
         out_off = [i * s.seg for i, _ in files]
         # (a palette lies behind its stream in the file's staged bytes: DeviceDecoder.items)
-        s.jpg_items, s.png_items = (dec.items(plans[lo:hi], file_off[lo:hi], out_off[lo:hi], ws_off[lo:hi]) for dec, lo, hi in kinds)
+        s.jpg_items, s.full_items, s.png_items = (dec.items(plans[lo:hi], file_off[lo:hi], out_off[lo:hi], ws_off[lo:hi]) for dec, lo, hi in kinds)
         s.jpg_count = nj
+        s.jpg_decs = [dec for dec, lo, hi in kinds for _ in range(lo, hi)]     # item k's decoder
         s.jpg_used = table + at
-        s.jpg_names = [f.name for _, f in files]                    # (item k's status word is word k: the .jpg items, then the .png items)
+        s.jpg_names = [f.name for _, f in files]                    # (item k's status word is word k, in the order of ``kinds``)
         host = s.jpg_pin.numpy()
-        for items, first in ((s.jpg_items, 0), (s.png_items, B * item)):
+        for items, first in ((s.jpg_items, 0), (s.png_items, B * item), (s.full_items, first_full)):
             if len(items):
                 host[first:first + ctypes.sizeof(items)] = np.frombuffer(items, dtype=np.uint8)
         for f in {id(f): f for _, f in files}.values():
@@ -951,11 +957,13 @@ class DetectionEntry:
         resize swaps, flip bit 1).  FRCNN_ENTRY_JPEG_BATCH=0: an upload and a single-file decode per file instead."""
         item, table = ctypes.sizeof(_lib.JpegDecBatchItem), s.jpg_area.numel() - s.jpg_dev.numel()
         nj, batched = s.jpg_count, jpeg_batch()
-        if batched or len(files) > nj:                              # (the .png items are always decoded as a batch)
+        if batched or len(files) > nj:                              # (the progressive and the .png items are always decoded as a batch)
             s.jpg_area[:s.jpg_used].copy_(s.jpg_pin[:s.jpg_used], non_blocking=True)
         s.jpg_status.zero_()
         # per decoder: its items, its first status word, where its items lie in the staged area; the .png items' launches go first
-        for dec, items, word, first in ((s.png_dec, s.png_items, nj, s.batch * item), (ops.JPEG_DECODER, s.jpg_items, 0, 0)):
+        first_full = s.batch * (item + ctypes.sizeof(_lib.PngDecFullBatchItem))
+        for dec, items, word, first in ((s.png_dec, s.png_items, nj + len(s.full_items), s.batch * item),
+                                        (ops.JPEG_FULL_DECODER, s.full_items, nj, first_full), (ops.JPEG_DECODER, s.jpg_items, 0, 0)):
             if dec is ops.JPEG_DECODER and not batched:
                 continue
             size = ctypes.sizeof(dec.item_type)
@@ -1014,7 +1022,7 @@ class DetectionEntry:
                 words = s.jpg_status_pin.numpy()
                 for i, name in enumerate(s.jpg_names):
                     if name is not None and int(words[i]):          # (the .jpg items' words, then the .png items')
-                        ops.raise_damaged(ops.JPEG_DECODER if i < (s.jpg_count or 0) else s.png_dec, int(words[i]), name)
+                        ops.raise_damaged(s.jpg_decs[i], int(words[i]), name)
             if s.amax is not None:
                 bits = int(s.out_pin[0].numpy()[2])                 # the pass's f16x3 status word (pipeline._pass_status)
                 if bits:

@@ -16,11 +16,12 @@ from .shapes import declares as _declares
 
 MEAN_BGR = (103.939, 116.779, 123.68)           # resnet.preprocess / vgg.preprocess (resnet.py:64-75, vgg.py:52-57)
 RGB_UPLOAD = os.environ.get("FRCNN_FEED_RGB_UPLOAD", "1") != "0"
-JPEG_DECODERS = ("host", "device")
+JPEG_DECODERS = ("host", "device", "device_full")
 
 
 def jpeg_decoder_option(value, what):
-    """A decoder setting ("host": PIL, the default; "device": ops.jpeg_decode_u8 for the files its planner supports, PIL for the rest)
+    """A decoder setting ("host": PIL, the default; "device": ops.jpeg_decode_u8 for the files its planner supports, PIL for the rest;
+    "device_full": as "device", and ops.jpeg_decode_full_batch_u8 for the progressive files ITS planner supports, PIL for the rest)
     checked: -> the value, ValueError naming ``what`` (an environment variable, an option) for anything else."""
     value = "host" if value is None or value == "" else value
     if value not in JPEG_DECODERS:
@@ -33,9 +34,11 @@ def default_jpeg_decoder():
     return jpeg_decoder_option(os.environ.get("FRCNN_FEED_JPEG_DECODER"), "FRCNN_FEED_JPEG_DECODER")
 
 
-def plan_file(image):
+def plan_file(image, full=None):
     """(the file's bytes, its decode plan) of a file-backed image the device decoder supports, else None (in-memory pixels, no
-    ``raw_file``, a file outside the supported set: the caller takes the host path).  Pure host work: a thread may do it ahead."""
+    ``raw_file``, a file outside the supported set: the caller takes the host path).  ``full`` (None: FRCNN_FEED_JPEG_DECODER is
+    "device_full"): a file the baseline planner refuses goes to the progressive planner (-> a ``_lib.JpegDecFullPlan``) before it is
+    given up.  Pure host work: a thread may do it ahead."""
     if not _declares(image, "raw_file") or getattr(image, "_pixels", None) is not None:
         return None
     data = image.raw_file()
@@ -44,7 +47,13 @@ def plan_file(image):
     try:
         return data, ops.jpeg_dec_plan(data)
     except ops.JpegUnsupported:
-        return None
+        pass
+    if default_jpeg_decoder() == "device_full" if full is None else full:
+        try:
+            return data, ops.jpeg_dec_full_plan(data)
+        except ops.JpegUnsupported:
+            pass
+    return None
 
 
 PNG_DECODERS = ("host", "device", "device_full")
@@ -86,22 +95,25 @@ def plan_entry_file(image, jpeg=True, png=False):
     """``plan_file`` for the detection entry, which may decode either kind on the device: a file-backed image whose bytes start with
     the PNG signature is planned by the PNG decoder ``png`` names (a PNG decoder setting; True stands for "device", "full" for
     "device_full", False for "host") -> ``plan_png``'s pair; what an ``annotate_video._FileFrame`` planned ahead under the same setting
-    is taken as it is), any other file by ``plan_file`` when ``jpeg``.  None: the caller takes the host path.  (``device_image``, the
+    is taken as it is), any other file by ``plan_file`` when ``jpeg`` (a JPEG decoder setting, or True for "device" and False for
+    "host").  None: the caller takes the host path.  (``device_image``, the
     training feed, plans through ``plan_feed_file``.)"""
-    return _plan_by_settings(image, jpeg, {True: "device", "full": "device_full", False: "host"}.get(png, png))
+    return _plan_by_settings(image, {True: "device", False: "host"}.get(jpeg, jpeg), {True: "device", "full": "device_full", False: "host"}.get(png, png))
 
 
 def plan_feed_file(image):
     """``plan_file`` for the training feed under its two settings: a file that starts with the PNG signature is planned by the PNG
     planner FRCNN_FEED_PNG_DECODER names (-> ``plan_png``'s pair), any other file by ``plan_file`` when
-    FRCNN_FEED_JPEG_DECODER is "device".  None: in-memory pixels, no ``raw_file``, a setting of "host" for that kind of file, or a file
+    FRCNN_FEED_JPEG_DECODER is "device" or "device_full".  None: in-memory pixels, no ``raw_file``, a setting of "host" for that kind of file, or a file
     the planner refuses: the caller takes the host path.  Pure host work: a thread may do it ahead."""
-    return _plan_by_settings(image, default_jpeg_decoder() == "device", default_png_decoder())
+    return _plan_by_settings(image, default_jpeg_decoder(), default_png_decoder())
 
 
 def _plan_by_settings(image, jpeg, png):
+    full = jpeg == "device_full"
+    jpeg = jpeg != "host"
     if png == "host":
-        return plan_file(image) if jpeg else None
+        return plan_file(image, full) if jpeg else None
     if not _declares(image, "raw_file") or getattr(image, "_pixels", None) is not None:
         return None
     data = image.raw_file()
@@ -112,13 +124,15 @@ def _plan_by_settings(image, jpeg, png):
         if planned is not None and ops.decoder_of(planned[1]).setting == png:
             return planned
         return plan_png(data, png)
-    return plan_file(image) if jpeg else None
+    return plan_file(image, full) if jpeg else None
 
 
 def _still_wanted(plan):
     """Does the setting that was in force when a file was planned ahead still hold?"""
     dec = ops.decoder_of(plan)
-    return (default_png_decoder() if dec.label == "PNG" else default_jpeg_decoder()) == dec.setting
+    if dec.label == "PNG":
+        return default_png_decoder() == dec.setting
+    return default_jpeg_decoder() in ("device_full",) + (("device",) if dec.setting == "device" else ())    # ("device_full" keeps the baseline decoder)
 
 
 class _PinRing:
@@ -194,7 +208,7 @@ def decode_ahead(image):
     """Start decoding a file-backed image's pixels on the background thread (device_image picks the result up).  With the device decoder
     the thread reads the file and plans it instead; an unsupported file is decoded there as before."""
     global _DECODER
-    device = default_jpeg_decoder() == "device" or default_png_decoder() != "host"
+    device = default_jpeg_decoder() != "host" or default_png_decoder() != "host"
     if not (DECODE_AHEAD and RGB_UPLOAD and hasattr(type(image), "raw_rgb")) or getattr(image, "_pixels", 0) is not None or id(image) in _DECODED:
         return
     if _DECODER is None:
@@ -231,7 +245,7 @@ _STATUS_PIN, _STATUS_AT = None, 0
 def _decode_on_device(data, plan, name):
     """The file decoded on the current stream -> (h, w, 3) uint8 R,G,B device tensor; its status word is queued for check_decodes."""
     dec = ops.decoder_of(plan)
-    if dec.label == "PNG":
+    if dec.label == "PNG" or dec is ops.JPEG_FULL_DECODER:      # (a batch of one: the plan is too large to travel by value)
         rgb, status = _decode_png_on_device(dec, data, plan)
     else:
         file_dev = upload(np.frombuffer(data, dtype=np.uint8))
@@ -251,7 +265,7 @@ def _decode_on_device(data, plan, name):
 
 
 def _decode_png_on_device(dec, data, plan):
-    """A planned .png file (``plan_png``'s pair, made for the decoder ``dec``) as a batch of one: ONE upload through the pin ring of [the
+    """A planned .png file (``plan_png``'s pair, made for the decoder ``dec``), or a progressive .jpg file, as a batch of one: ONE upload through the pin ring of [the
     item | the zlib stream | the palette], the decode on the current stream -> ((h, w, 3) uint8 R,G,B device tensor, its status word [1])."""
     import ctypes
     head = (ctypes.sizeof(dec.item_type) + 15) // 16 * 16

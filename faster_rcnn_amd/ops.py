@@ -1281,10 +1281,11 @@ PNG_DEC_FULL_PLTE_BYTES = _lib.PNG_DEC_FULL_PLTE_BYTES
 @dataclasses.dataclass(frozen=True)
 class DeviceDecoder:
     """One device decoder of file-backed frames: what its C entry points are called and take, and every operation on them ONCE.  The
-    public functions below (``jpeg_dec_plan`` ... ``png_decode_full_u8``) are bindings of these methods to one of the three records.
+    public functions below (``jpeg_dec_plan`` ... ``png_decode_full_u8``) are bindings of these methods to one of the four records.
     ``stem`` / ``decode_stem`` / ``items_name``: the names "frcnn_" + name are the C symbols of and the messages speak of
     (<stem>_plan, <stem>_spans, <stem>_workspace_bytes, <stem>_batch_layout; <decode_stem>_batch_u8, <decode_stem>_u8); ``setting``: the
-    value of a decoder setting (feed.py, entry.py) that selects it; ``palette``: its items carry ``plte_off``."""
+    value of a decoder setting (feed.py, entry.py) that selects it; ``palette``: its items carry ``plte_off``; ``whole_file``: what it
+    stages of a file is the whole file (the JPEG records), not a stream gathered from it."""
     label: str
     setting: str
     stem: str
@@ -1295,6 +1296,7 @@ class DeviceDecoder:
     batch_max: int
     unsupported: type
     palette: bool = False
+    whole_file: bool = False
 
     def plan(self, data):
         who = self.stem + "_plan"
@@ -1380,7 +1382,10 @@ class DeviceDecoder:
         return palette + bytes(PNG_DEC_FULL_PLTE_BYTES - len(palette))
 
     def stage(self, data, plan):
-        """What goes to the device for one file: its zlib stream, behind it its staged palette where it has one."""
+        """What goes to the device for one file: the file itself (``whole_file``), or its zlib stream, behind it its staged palette where
+        it has one."""
+        if self.whole_file:
+            return bytes(data)
         return self.stream(data, plan) + self.palette_of(data, plan)
 
     def decode_one(self, file_bytes, bgr=False):
@@ -1397,7 +1402,10 @@ class DeviceDecoder:
 
 
 JPEG_DECODER = DeviceDecoder("JPEG", "device", "jpeg_dec", "jpeg_decode", "jpeg_batch_items", _lib.JpegDecPlan, _lib.JpegDecBatchItem,
-                             _lib.JPEG_DEC_BATCH_MAX, JpegUnsupported)
+                             _lib.JPEG_DEC_BATCH_MAX, JpegUnsupported, whole_file=True)
+# progressive files (include/ext/frcnn_hip_jpeg_dec_full.h): the decoder the JPEG setting "device_full" adds BEHIND the baseline one
+JPEG_FULL_DECODER = DeviceDecoder("JPEG", "device_full", "jpeg_dec_full", "jpeg_decode_full", "jpeg_full_batch_items", _lib.JpegDecFullPlan,
+                                  _lib.JpegDecFullBatchItem, _lib.JPEG_DEC_BATCH_MAX, JpegUnsupported, whole_file=True)
 # by the value of a PNG decoder setting (feed.PNG_DECODERS but "host")
 PNG_DECODERS = {
     "device": DeviceDecoder("PNG", "device", "png_dec", "png_decode", "png_batch_items", _lib.PngDecPlan, _lib.PngDecBatchItem,
@@ -1406,7 +1414,7 @@ PNG_DECODERS = {
                                  _lib.PngDecFullBatchItem, _lib.PNG_DEC_BATCH_MAX, PngUnsupported, palette=True),
 }
 _PNG1, _PNGF = PNG_DECODERS["device"], PNG_DECODERS["device_full"]
-_DECODER_OF = {d.plan_type: d for d in (JPEG_DECODER, _PNG1, _PNGF)}
+_DECODER_OF = {d.plan_type: d for d in (JPEG_DECODER, JPEG_FULL_DECODER, _PNG1, _PNGF)}
 
 
 def decoder_of(plan):
@@ -1493,6 +1501,45 @@ def jpeg_decode_batch_u8(files, items, out, bgr=False, status=None, workspace=No
     a device tensor that already holds ``bytes(items)`` (uploaded by the caller on the current stream); None: uploaded here, a pageable
     copy, which blocks the host.  ``status`` and ``workspace`` are allocated when not passed.  Never synchronises otherwise."""
     return JPEG_DECODER.decode(files, items, out, bgr, status, workspace, items_dev)
+
+
+# ---- the progressive JPEG decoder (include/ext/frcnn_hip_jpeg_dec_full.h, csrc/jpeg_dec_full.hip)
+def jpeg_dec_full_plan(data):
+    """``jpeg_dec_plan`` for a PROGRESSIVE .jpg file (frcnn_jpeg_dec_full_plan) -> a ``_lib.JpegDecFullPlan``: the frame fields of the
+    baseline plan (``plan.frame``) and the scan table.  ``JpegUnsupported`` with the reason for a file outside ITS supported set: a
+    baseline file (``jpeg_dec_plan``'s), an illegal or incomplete scan script, arithmetic coding, a cut file, ...  A pure host call."""
+    return JPEG_FULL_DECODER.plan(data)
+
+
+def jpeg_dec_full_workspace_bytes(plan):
+    """Bytes of device workspace a file of ``plan`` needs (frcnn_jpeg_dec_full_workspace_bytes)."""
+    return JPEG_FULL_DECODER.workspace_bytes(plan)
+
+
+def jpeg_dec_full_batch_layout(plans):
+    """Workspace regions for a batch of plans laid back to back (frcnn_jpeg_dec_full_batch_layout) -> (ws_off, total).  A pure host call."""
+    return JPEG_FULL_DECODER.layout(plans)
+
+
+def jpeg_full_batch_items(plans, file_off, out_off, ws_off):
+    """The item table of a batch (``_lib.JpegDecFullBatchItem`` x n, a ctypes array: ``bytes(table)`` is what goes to the device);
+    ``file_off``: where each WHOLE file lies."""
+    return JPEG_FULL_DECODER.items(plans, file_off, out_off, ws_off)
+
+
+def jpeg_decode_full_batch_u8(files, items, out, bgr=False, status=None, workspace=None, items_dev=None):
+    """``jpeg_decode_batch_u8`` for progressive files, FOUR launches whatever the files' scan scripts are
+    (frcnn_jpeg_decode_full_batch_u8): ``items`` the table (``jpeg_full_batch_items``) -> status: int32 [n], per file 0 or
+    _lib.JPEG_DEC_FULL_* bits ORed in (sticky).  ``items_dev``, ``status`` and ``workspace`` as there."""
+    return JPEG_FULL_DECODER.decode(files, items, out, bgr, status, workspace, items_dev)
+
+
+def jpeg_decode_full_u8(file_bytes, bgr=False):
+    """One progressive .jpg file's bytes decoded on the device: the eager convenience (a batch of one; pageable uploads, one
+    synchronisation) -> an (h, w, 3) uint8 device tensor, numpy.asarray(PIL.Image.open(f).convert("RGB")) byte for byte, or its channel
+    reverse with ``bgr``.  ``JpegUnsupported`` for a file outside the supported set, ``FrcnnError`` with the status word for a damaged
+    one."""
+    return JPEG_FULL_DECODER.decode_one(file_bytes, bgr)
 
 
 def png_dec_plan(data):

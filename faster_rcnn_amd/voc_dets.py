@@ -283,9 +283,10 @@ def build_parser():
     p.add_argument("--network", dest="network", choices=("vgg16", "resnet50", "resnet101"), default="vgg16")
     p.add_argument("--out_dir", dest="out_dir", default=".")
     p.add_argument("--det_threshold", dest="det_threshold", default=DEFAULT_DET_THRESHOLD)
-    p.add_argument("--jpeg_decoder", dest="jpeg_decoder", choices=("host", "device"), default=None,
-                   help="who decodes the images' JPEG files: host (PIL) or device (csrc/jpeg_dec.hip, for baseline files, in per-geometry "
-                        "and canvas passes; PIL for the rest); default: FRCNN_ENTRY_JPEG_DECODER, else host")
+    p.add_argument("--jpeg_decoder", dest="jpeg_decoder", choices=("host", "device", "device_full"), default=None,
+                   help="who decodes the images' JPEG files: host (PIL), device (csrc/jpeg_dec.hip, for baseline files, in per-geometry "
+                        "and canvas passes; PIL for the rest) or device_full (progressive files too: csrc/jpeg_dec_full.hip); default: "
+                        "FRCNN_ENTRY_JPEG_DECODER, else host")
     p.add_argument("--dtype", dest="dtype", choices=("f32", "bf16"), default="f32",
                    help="precision the networks are served in: bf16 = the bf16 conv path on the matrix cores (the reference has no such flag: it runs fp32 only)")
     return p

@@ -10,7 +10,9 @@ what crosses the link (the file's bytes against the decoded frame) and in how ma
 the list cycles over several sizes cut from the photograph and saved as baseline JPEG at mixed subsampling, so that canvas passes form
 (the VOC case).  ``--op-only --batch N``: N copies of the file through ops.jpeg_decode_u8 one after another against one
 ops.jpeg_decode_batch_u8.  The models are the small synthetic ResNet-50 of the tests: the figures are ratios of legs on the same
-passes, not a headline rate.  Prints one JSON line."""
+passes, not a headline rate.  ``--progressive``: the same legs on a PROGRESSIVE re-save of the input (quality 90), decoded under the JPEG
+decoder setting "device_full" (csrc/jpeg_dec_full.hip); the per-file leg is the batched one there (progressive files are always
+decoded as a batch), and ``--op-only`` times one ops.jpeg_decode_full_batch_u8 of max(1, --batch) copies.  Prints one JSON line."""
 import argparse
 import contextlib
 import io
@@ -85,6 +87,32 @@ def op_batch(args, data, plan):
                       "status": int(status.abs().max().item())}))
 
 
+def op_progressive(args, data):
+    """--progressive --op-only: max(1, --batch) copies of the progressive file through one ops.jpeg_decode_full_batch_u8 per iteration."""
+    import numpy as np
+    import torch
+    from faster_rcnn_amd import ops
+    plan = ops.jpeg_dec_full_plan(data)
+    n, frame = max(1, args.batch), plan.h * plan.w * 3
+    files = torch.from_numpy(np.frombuffer(data * n, dtype=np.uint8).copy()).cuda()
+    ws_off, total = ops.jpeg_dec_full_batch_layout([plan] * n)
+    ws = torch.empty(total, dtype=torch.uint8, device="cuda")
+    out = torch.empty(n * frame, dtype=torch.uint8, device="cuda")
+    status = torch.zeros(n, dtype=torch.int32, device="cuda")
+    items = ops.jpeg_full_batch_items([plan] * n, [i * len(data) for i in range(n)], [i * frame for i in range(n)], ws_off)
+    items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).cuda()
+    for _ in range(5):
+        ops.jpeg_decode_full_batch_u8(files, items, out, status=status, workspace=ws, items_dev=items_dev)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.iters):
+        ops.jpeg_decode_full_batch_u8(files, items, out, status=status, workspace=ws, items_dev=items_dev)
+    torch.cuda.synchronize()
+    print(json.dumps({"op": "jpeg_decode_full_batch_u8", "batch": n, "file_bytes": len(data), "h": plan.h, "w": plan.w, "scans": int(plan.scans),
+                      "iters": args.iters, "ms_per_batch": round(1e3 * (time.perf_counter() - t0) / args.iters, 4),
+                      "status": int(status.abs().max().item())}))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--file", default=os.path.join(ROOT, "tests", "golden", "VOC_test", "JPEGImages", "000005.jpg"))
@@ -94,11 +122,20 @@ def main():
     p.add_argument("--iters", type=int, default=200)
     p.add_argument("--batch", type=int, default=0, help="--op-only: N copies of the file per iteration, per-file loop against one batched call")
     p.add_argument("--mixed", action="store_true", help="several sizes cut from the file, so that canvas passes form")
+    p.add_argument("--progressive", action="store_true", help="the legs on a progressive re-save of the file, the device legs under device_full")
     args = p.parse_args()
     import torch
     from faster_rcnn_amd import entry, ops, shapes, util, voc_dets
+    keep = tempfile.TemporaryDirectory()
+    if args.progressive:
+        from PIL import Image as PilImage
+        with PilImage.open(args.file) as im:
+            args.file = os.path.join(keep.name, "progressive.jpg")
+            im.convert("RGB").save(args.file, "JPEG", quality=90, progressive=True)
     data = open(args.file, "rb").read()
-    plan = ops.jpeg_dec_plan(data)
+    if args.progressive and args.op_only:
+        return op_progressive(args, data)
+    plan = ops.jpeg_dec_full_plan(data).frame if args.progressive else ops.jpeg_dec_plan(data)
     if args.op_only and args.batch > 0:
         return op_batch(args, data, plan)
     if args.op_only:
@@ -125,7 +162,7 @@ def main():
             im = im.convert("RGB")
             for k, (dh, dw) in enumerate(MIXED_CUTS):
                 path = os.path.join(tmp.name, "cut%d.jpg" % k)
-                im.crop((0, 0, plan.w - dw, plan.h - dh)).save(path, "JPEG", quality=90, subsampling=k % 3)
+                im.crop((0, 0, plan.w - dw, plan.h - dh)).save(path, "JPEG", quality=90, subsampling=k % 3, progressive=args.progressive)
                 paths.append((path, plan.h - dh, plan.w - dw))
         images = [shapes.Image(shapes.Metadata("i%d" % i, paths[i % len(paths)][2], paths[i % len(paths)][1], [], paths[i % len(paths)][0]))
                   for i in range(args.images)]
@@ -135,7 +172,7 @@ def main():
     legs = {"host": [], "device_per_file": [], "device_batched": []}
 
     def run(leg):
-        entry.set_jpeg_decoder("host" if leg == "host" else "device")
+        entry.set_jpeg_decoder("host" if leg == "host" else ("device_full" if args.progressive else "device"))
         os.environ["FRCNN_ENTRY_JPEG_BATCH"] = "0" if leg == "device_per_file" else "1"
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -154,7 +191,7 @@ def main():
     med = lambda v: sorted(v)[len(v) // 2]
     eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight("f32"))
     print(json.dumps({"workload": "get_dets_by_cls from files, small synthetic ResNet-50", "images": args.images, "reps": args.reps,
-                      "mixed": bool(args.mixed), "canvas_passes": sum(k[0] == "canvas" for k in eng.cache.keys()), "batch": eng.batch,
+                      "mixed": bool(args.mixed), "progressive": bool(args.progressive), "canvas_passes": sum(k[0] == "canvas" for k in eng.cache.keys()), "batch": eng.batch,
                       "img_per_s": legs, "median": {k: med(v) for k, v in legs.items()},
                       "spread": {k: round((max(v) - min(v)) / med(v), 3) for k, v in legs.items()},
                       "batched_over_per_file": round(med(legs["device_batched"]) / med(legs["device_per_file"]), 3),
