@@ -324,6 +324,34 @@ class JpegDecFullBatchItem(ctypes.Structure):
     _fields_ = [("plan", JpegDecFullPlan), ("file_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("ws_off", ctypes.c_uint64)]
 
 
+Y4M_VERSION = 1                 # include/ext/frcnn_hip_y4m.h FRCNN_Y4M_VERSION
+Y4M_BATCH_MAX = 64              # ... FRCNN_Y4M_BATCH_MAX
+Y4M_MAX_SIDE = 32768            # ... FRCNN_Y4M_MAX_SIDE
+Y4M_SIGNATURES = {
+    "frcnn_y4m_version": (I, []),
+    "frcnn_y4m_frame_bytes": (c_size_t, [I, I, I]),
+    "frcnn_y4m_decode_batch_u8": (I, [P, P, I, P, c_size_t, I, P, c_size_t, P, P, c_size_t, P]),
+    "frcnn_y4m_decode_u8": (I, [P, c_size_t, P, I, P, c_size_t, P]),
+    "frcnn_y4m_encode_u8": (I, [P, c_size_t, I, I, I, I, I, I, P, c_size_t, c_size_t, P]),
+}
+Y4M_CHROMAS = {"420jpeg": 0, "420mpeg2": 1, "422": 2, "444": 3, "mono": 4}      # FRCNN_Y4M_C*
+Y4M_OUT_CHROMAS = ("420jpeg", "444")
+Y4M_RANGES = {"limited": 0, "full": 1}                                          # FRCNN_Y4M_LIMITED / _FULL
+
+
+class Y4mPlan(ctypes.Structure):
+    """frcnn_y4m_plan_t (include/ext/frcnn_hip_y4m.h).  ``y4m.parse_header`` hangs the stream's tags on the instance (``tags``,
+    ``header_len``): Python attributes beside the C fields, which is all that travels to the device."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("h", "w", "chroma", "range")] + [(k, ctypes.c_uint32) for k in ("frame_bytes", "reserved")]
+    chroma_name = property(lambda self: next(k for k, v in Y4M_CHROMAS.items() if v == self.chroma))
+    range_name = property(lambda self: next(k for k, v in Y4M_RANGES.items() if v == self.range))
+
+
+class Y4mBatchItem(ctypes.Structure):
+    """frcnn_y4m_batch_item_t (include/ext/frcnn_hip_y4m.h)."""
+    _fields_ = [("plan", Y4mPlan), ("file_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("ws_off", ctypes.c_uint64)]
+
+
 class ConvDesc(ctypes.Structure):
     """frcnn_conv_desc (include/frcnn_hip.h)."""
     _fields_ = [(k, ctypes.c_int32) for k in (
@@ -421,6 +449,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in Y4M_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_y4m_version() != Y4M_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_y4m_version()} of the YUV4MPEG2 extension, this binding "
+                         f"{Y4M_VERSION} (include/ext/frcnn_hip_y4m.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_jpeg_dec_full_version() != JPEG_DEC_FULL_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_jpeg_dec_full_version()} of the JPEG decoder's progressive extension, this "
                          f"binding {JPEG_DEC_FULL_VERSION} (include/ext/frcnn_hip_jpeg_dec_full.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -36,13 +36,20 @@ options with ``png`` frames, and the device PNG options with ``jpg`` frames, rai
 ``jpeg_huffman="optimized"`` (``--jpeg_huffman optimized``, FRCNN_ANNOTATE_JPEG_HUFFMAN) writes Huffman tables built from each frame's own
 symbol counts: the two options every JPEG writer has, honoured by both encoders (PIL: ``subsampling=2``, ``optimize=True``; device:
 csrc/jpeg_opt.hip).  Both need ``jpg`` frames; the defaults stay 444 / "standard" (sizes: DESIGN §8).
+
+A video STREAM goes through ``annotate_stream``: the command line's ``input_dir`` may be a YUV4MPEG2 file (``.y4m``) or ``-`` (stdin), and
+``--out_video PATH|-`` writes one y4m stream (``--video_chroma`` 420jpeg or 444; range and the F / A tags are the input's, limited / F25:1
+for a frame directory, whose frames must then share one size) instead of frame files -- with ``-`` every printed line goes to stderr.  The
+frames' chroma upsampling and colour matrix, and the inverse on the way out, run inside the passes (csrc/y4m.hip, DESIGN §8); a frame's
+"path" in the printed lines is ``<name>#<frame index>``.
 """
+import collections
 import os
 import pathlib
 
 import numpy as np
 
-from . import entry, ops, shapes, voc_dets
+from . import entry, ops, shapes, voc_dets, y4m
 from .util import resize_imgs
 
 STRIDE = 16                                       # get_dets' default: annotate_video.py:29 passes none
@@ -332,6 +339,223 @@ class _Frame:
         return self.resize(ratio), ratio
 
 
+def _load_frame(path, device_decode, device_png):
+    """(decode thread) One input frame file: a ``_FileFrame`` when a device decoder in force (``device_decode``: the JPEG setting,
+    ``device_png``: the PNG one) takes the file, else a ``_Frame`` decoded by PIL."""
+    frame = None
+    if device_decode != "host" and path.lower().endswith(JPEG_SUFFIXES):
+        with open(path, "rb") as f:
+            data = f.read()
+        for planner in (ops.jpeg_dec_plan,) + ((ops.jpeg_dec_full_plan,) if device_decode == "device_full" else ()):
+            try:
+                plan = planner(data)
+                frame = _FileFrame(data, path, (int(plan.h), int(plan.w)))
+                break
+            except ops.JpegUnsupported:
+                pass                                      # (progressive under "device", CMYK, ...: PIL below)
+    elif device_png != "host" and path.lower().endswith(".png"):
+        from .feed import plan_png
+        with open(path, "rb") as f:
+            data = f.read()
+        # None: a file the chosen planner refuses ("device": palette, 16-bit, interlaced, ...; "device_full": 16-bit grey, ...): PIL below
+        planned = plan_png(data, device_png)
+        if planned is not None:
+            frame = _FileFrame(data, path, (int(planned[1].h), int(planned[1].w)), png_planned=planned)
+    if frame is None:
+        frame = _Frame(_read_rgb(path))
+    return frame
+
+
+class _Y4mFrame:
+    """A frame of a YUV4MPEG2 stream: its planes and the stream's plan (entry.DetectionEntry.host_pixels finds ``y4m_plan`` and
+    ``raw_file()`` and lets the device convert); ``raw_rgb`` converts on the host (y4m.decode_host) for whoever still wants pixels."""
+
+    def __init__(self, data, plan, path, width=None, height=None):
+        self.data, self.y4m_plan, self._image_path = data, plan, path
+        self.height = int(plan.h) if height is None else height
+        self.width = int(plan.w) if width is None else width
+        self._pixels = None
+
+    def raw_file(self):
+        return self.data
+
+    def raw_size(self):
+        return int(self.y4m_plan.h), int(self.y4m_plan.w)
+
+    @property
+    def raw_rgb(self):
+        return y4m.decode_host(self.data, self.y4m_plan)
+
+    raw = property(lambda s: s.raw_rgb[:, :, ::-1])
+
+    def resize(self, scale_ratio):
+        return _Y4mFrame(self.data, self.y4m_plan, self._image_path, int(round(scale_ratio * self.width)), int(round(scale_ratio * self.height)))
+
+    def resize_within_bounds(self, min_size, max_size):
+        ratio = shapes._bounds_ratio(self.width, self.height, min_size, max_size)
+        return self.resize(ratio), ratio
+
+
+def stream_frames(reader):
+    """(label, frame) per frame of a ``y4m.Y4mReader``: the label ``<name>#<frame index>`` stands where a frame file's path does."""
+    for i, data in enumerate(reader):
+        label = "%s#%d" % (reader.name, i)
+        yield label, _Y4mFrame(data, reader.plan, label)
+
+
+def directory_frames(input_dir, image_filenames, jpeg_decoder=None, png_decoder=None):
+    """(path, frame) per frame file of a directory, for ``annotate_stream``: what ``annotate_images`` reads, as a stream."""
+    if jpeg_decoder is not None:
+        entry.set_jpeg_decoder(jpeg_decoder)
+    if png_decoder is not None:
+        entry.set_png_decoder(png_decoder)
+    for f in image_filenames:
+        path = os.path.join(input_dir, f)
+        yield path, _load_frame(path, entry.jpeg_decoder(), entry.png_decoder())
+
+
+def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
+                    png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None):
+    """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
+    passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
+    annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
+    every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
+    other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place."""
+    from concurrent.futures import ThreadPoolExecutor
+    to_video = isinstance(writer_or_out_dir, y4m.Y4mWriter)
+    source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
+    dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
+    eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
+    if to_video:
+        writer = writer_or_out_dir
+        if video_chroma is not None and video_chroma != writer.chroma:
+            raise ValueError("video_chroma=%r, the writer's stream is C%s" % (video_chroma, writer.chroma))
+        kwargs = dict(encode="y4m", y4m=(writer.chroma, writer.range))
+        on_device, jpg = True, False
+
+        def check_size(label, frame):
+            if (frame.width, frame.height) != (writer.w, writer.h):
+                raise ValueError("%s is %dx%d, the output stream's frames are %dx%d: one video stream holds frames of one size"
+                                 % (label, frame.width, frame.height, writer.w, writer.h))
+    else:
+        out_dir = writer_or_out_dir
+        png_encoder, png_compress = png_options(png_encoder, png_compress)
+        frame_format, jpeg_encoder, jpeg_quality = jpeg_options(frame_format, jpeg_encoder, jpeg_quality, png_encoder, png_compress)
+        jpeg_subsampling, jpeg_huffman = jpeg_size_options(frame_format, jpeg_subsampling, jpeg_huffman)
+        jpg = frame_format == "jpg"
+        on_device = (jpeg_encoder if jpg else png_encoder) == "device"
+        if jpg:
+            kwargs = dict(encode="jpeg", quality=jpeg_quality, subsampling=jpeg_subsampling, huffman=jpeg_huffman) if on_device else {}
+            write_host = lambda path, rgb: _write_jpg(path, rgb, jpeg_quality, jpeg_subsampling, jpeg_huffman)
+        else:
+            kwargs = dict(encode="png" if png_compress == "runs" else "png-" + png_compress) if on_device else {}
+            write_host = _write_png
+        pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
+        out_name = lambda pos: os.path.join(out_dir, "frame_%06d.%s" % (pos, "jpg" if jpg else "png"))
+        check_size = lambda label, frame: None
+
+    if eng is None:                                       # eager path / foreign models: one frame at a time, converted on the device
+        import torch
+        for pos, (label, src) in enumerate(source):
+            check_size(label, src)
+            print("processing {}".format(label))
+            if isinstance(src, _Y4mFrame):
+                frame = ops.y4m_decode_u8(src.data, src.y4m_plan, bgr=True).cpu().numpy()
+            else:
+                frame = np.ascontiguousarray(src.raw)
+            img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
+            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max)
+            if to_video:
+                writer.write(ops.y4m_encode_u8(torch.from_numpy(out).cuda(), writer.chroma, writer.range, bgr=True).cpu().numpy().tobytes())
+            elif on_device:
+                dev = torch.from_numpy(out).cuda()
+                _write_bytes(out_name(pos), ops.jpeg_bytes(dev, quality=jpeg_quality, bgr=True, subsampling=jpeg_subsampling, huffman=jpeg_huffman)
+                             if jpg else ops.png_bytes(dev, bgr=True, compress=png_compress))
+            else:
+                write_host(out_name(pos), out[:, :, ::-1])
+        if to_video:
+            writer.flush()
+        return
+
+    B = eng.batch
+    ahead = 2 * eng.in_flight * B
+    read = ThreadPoolExecutor(max_workers=1)              # the stream is sequential: one reader, ``ahead`` frames in front of the passes
+    write = ThreadPoolExecutor(max_workers=1 if to_video else max(1, WRITE_THREADS))
+    pending, writes, window = collections.deque(), [], []
+
+    def load():                                           # (reader thread) -> (label, frame, resized, ratio, pixels) or None at the end
+        try:
+            label, frame = next(source)
+        except StopIteration:
+            return None
+        check_size(label, frame)
+        resized, ratio = frame.resize_within_bounds(resize_min, resize_max)
+        return label, frame, resized, ratio, eng.host_pixels(resized)
+
+    def finish():
+        part, ticket = window[0]
+        try:
+            results = eng.collect_batch(ticket)
+        finally:
+            window.pop(0)
+        for (pos, label, frame), (num_rois, dets, out) in zip(part, results):
+            print("processing {}".format(label))
+            print("num rois: {}".format(num_rois))
+            _print_drawn(dets, frame.width, frame.height)
+            if to_video:
+                writes.append(write.submit(writer.write, out))            # (one writer thread: stream order)
+            else:
+                writes.append(write.submit(_write_bytes if on_device else write_host, out_name(pos), out))
+        while len(writes) > 4 * WRITE_THREADS:            # (bounded: encoded frames must not pile up in memory)
+            writes.pop(0).result()
+
+    def submit(group):
+        parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
+        for part, take in parts:
+            ticket = eng.submit_batch([g[3] for g in part], [g[4] for g in part], DET_THRESHOLD, [g[5] for g in part],
+                                      batch=take, annotate=True, **kwargs)
+            window.append(([(g[0], g[1], g[2]) for g in part], ticket))
+            if len(window) >= eng.in_flight:
+                finish()
+
+    try:
+        group, key, pos, done = [], None, 0, False
+        while True:
+            while not done and len(pending) < ahead:
+                pending.append(read.submit(load))
+            if not pending:
+                break
+            got = pending.popleft().result()
+            if got is None:
+                done = True
+                for f in pending:                         # (reads behind the end: each finds the source exhausted)
+                    f.result()
+                pending.clear()
+                continue
+            label, frame, resized, ratio, pixels = got
+            k = eng.geometry_of(pixels)
+            if group and (k != key or len(group) == B):
+                submit(group)
+                group = []
+            group.append((pos, label, frame, resized, ratio, pixels))
+            key, pos = k, pos + 1
+        if group:
+            submit(group)
+        while window:
+            finish()
+        for f in writes:
+            f.result()
+        if to_video:
+            writer.flush()
+    finally:
+        read.shutdown(wait=True, cancel_futures=True)
+        for _, ticket in window:                          # an exception mid-stream: no slot stays marked busy
+            ticket.slot.event.synchronize()
+            ticket.slot.busy = False
+        write.shutdown(wait=True)
+
+
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
                     jpeg_huffman=None, png_decoder=None):
@@ -391,27 +615,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         return
 
     def load(path):                                       # (decode thread) -> (frame, resized, ratio, pixels)
-        frame = None
-        if device_decode != "host" and path.lower().endswith(JPEG_SUFFIXES):
-            with open(path, "rb") as f:
-                data = f.read()
-            for planner in (ops.jpeg_dec_plan,) + ((ops.jpeg_dec_full_plan,) if device_decode == "device_full" else ()):
-                try:
-                    plan = planner(data)
-                    frame = _FileFrame(data, path, (int(plan.h), int(plan.w)))
-                    break
-                except ops.JpegUnsupported:
-                    pass                                      # (progressive under "device", CMYK, ...: PIL below)
-        elif device_png != "host" and path.lower().endswith(".png"):
-            from .feed import plan_png
-            with open(path, "rb") as f:
-                data = f.read()
-            # None: a file the chosen planner refuses ("device": palette, 16-bit, interlaced, ...; "device_full": 16-bit grey, ...): PIL below
-            planned = plan_png(data, device_png)
-            if planned is not None:
-                frame = _FileFrame(data, path, (int(planned[1].h), int(planned[1].w)), png_planned=planned)
-        if frame is None:
-            frame = _Frame(_read_rgb(path))
+        frame = _load_frame(path, device_decode, device_png)
         resized, ratio = frame.resize_within_bounds(resize_min, resize_max)
         return frame, resized, ratio, eng.host_pixels(resized)
 
@@ -482,7 +686,7 @@ def build_parser():
                    help="weights of the RPN trained in step 3 (Keras .h5 or this package's .npz)")
     p.add_argument("step4_model_path", metavar="step4_model_path", type=str,
                    help="weights of the detector from step 4 (must be compatible with the RPN)")
-    p.add_argument("input_dir", type=str, help="directory of the video's frames as *.png")
+    p.add_argument("input_dir", type=str, help="directory of the video's frames as *.png; or a YUV4MPEG2 stream: a .y4m path, or - for stdin")
     p.add_argument("--kitti", dest="kitti", action="store_true", help="KITTI classes instead of Pascal VOC")
     p.add_argument("--resize_dims", dest="resize_dims", default="600,1000",
                    help="resize parameters, e.g. 600,1000 for a min size of 600 pixels and a max of 1000")
@@ -520,17 +724,64 @@ def build_parser():
     p.add_argument("--jpeg_huffman", dest="jpeg_huffman", choices=JPEG_HUFFMANS, default=default_jpeg_huffman(),
                    help="Huffman tables of JPEG frames: standard = Annex K.3, optimized = built from each frame's symbol counts, smaller "
                         "files, with either encoder (FRCNN_ANNOTATE_JPEG_HUFFMAN sets the default; needs --frame_format jpg)")
+    p.add_argument("--out_video", dest="out_video", default=None, metavar="PATH|-",
+                   help="write ONE YUV4MPEG2 stream (PATH, or - for stdout: every printed line then goes to stderr) instead of frame files; "
+                        "range and the F / A tags are the input stream's (a frame directory: limited range, F25:1, and one frame size)")
+    p.add_argument("--video_chroma", dest="video_chroma", choices=VIDEO_CHROMAS, default=None,
+                   help="chroma of the stream --out_video writes: 420jpeg (the default) or 444")
     return p
+
+
+VIDEO_CHROMAS = ("420jpeg", "444")
+
+
+def is_stream_input(input_dir):
+    """Does the command line's ``input_dir`` name a YUV4MPEG2 stream (``-``: stdin, or a ``.y4m`` path) rather than a frame directory?"""
+    return input_dir == "-" or input_dir.lower().endswith(".y4m")
+
+
+def video_options(args):
+    """The video arguments checked (before any model is loaded) -> (stream input?, out_video or None, video_chroma).  ValueError for
+    --video_chroma without --out_video and for --out_video with options that choose how frame FILES are encoded."""
+    out_video = args.out_video
+    if args.video_chroma is not None and out_video is None:
+        raise ValueError("--video_chroma=%s is a setting of the stream --out_video writes: it needs --out_video" % args.video_chroma)
+    if out_video is not None:
+        if args.frame_format != "png" or args.png_encoder != "host" or args.png_compress != "runs" or args.jpeg_encoder != "host" \
+                or args.jpeg_quality is not None or args.jpeg_subsampling != 444 or args.jpeg_huffman != "standard":
+            raise ValueError("--out_video writes one YUV4MPEG2 stream: --frame_format / --png_* / --jpeg_* encoder options choose how frame "
+                             "FILES are written and do not go with it")
+    return is_stream_input(args.input_dir), out_video, args.video_chroma or "420jpeg"
+
+
+def _frame_size(path):
+    from PIL import Image as PilImage
+    with PilImage.open(path) as im:
+        return im.size                                    # (width, height)
 
 
 def main(argv=None):
     """annotate_video.py:47-82: load the two models, annotate every PNG of input_dir into out_dir."""
+    import contextlib
+    import sys
+    args = build_parser().parse_args(argv)
+    stream_in, out_video, video_chroma = video_options(args)
+    with contextlib.ExitStack() as stack:
+        if out_video == "-":                              # the stream owns stdout: everything printed goes to stderr
+            video_out = sys.stdout.buffer
+            stack.enter_context(contextlib.redirect_stdout(sys.stderr))
+        else:
+            video_out = None
+        _main(args, stream_in, out_video, video_chroma, video_out, stack)
+
+
+def _main(args, stream_in, out_video, video_chroma, video_out, stack):
+    import sys
     from . import resnet, vgg
     from .args_util import anchor_scales_from_str, resize_dims_from_str
     from .data.voc_data_helpers import KITTI_CLASS_MAPPING, VOC_CLASS_MAPPING
     from .det_util import DetTrainingManager
     from .util import get_anchors
-    args = build_parser().parse_args(argv)
     frame_format = jpeg_options(args.frame_format, args.jpeg_encoder, args.jpeg_quality,
                                 *png_options(args.png_encoder, args.png_compress))[0]                     # (before any model is loaded)
     jpeg_size_options(frame_format, args.jpeg_subsampling, args.jpeg_huffman)
@@ -548,6 +799,26 @@ def main(argv=None):
         preprocess = resnet.preprocess
     manager = DetTrainingManager(rpn_model=rpn, class_mapping=class_mapping, preprocess_func=preprocess, anchor_dims=anchors)
     resize_min, resize_max = resize_dims_from_str(args.resize_dims)
+    if stream_in or out_video is not None:
+        if stream_in:
+            fin = sys.stdin.buffer if args.input_dir == "-" else stack.enter_context(open(args.input_dir, "rb"))
+            reader = y4m.Y4mReader(fin, name="<stdin>" if args.input_dir == "-" else args.input_dir)
+            w, h, yrange, tags = int(reader.plan.w), int(reader.plan.h), reader.plan.range_name, reader.plan.tags
+        else:
+            names = frame_filenames(args.input_dir, args.jpeg_decoder or entry.jpeg_decoder())
+            if not names:
+                raise ValueError("%s holds no frames" % args.input_dir)
+            reader = directory_frames(args.input_dir, names, args.jpeg_decoder, args.png_decoder)
+            (w, h), yrange, tags = _frame_size(os.path.join(args.input_dir, names[0])), "limited", {"F": "25:1"}
+        if out_video is not None:
+            fout = video_out if video_out is not None else stack.enter_context(open(out_video, "wb"))
+            sink = y4m.Y4mWriter(fout, w, h, video_chroma, yrange, {k: tags[k] for k in ("F", "A") if k in tags})
+            annotate_stream(manager, detector, reader, sink, resize_min, resize_max)
+        else:
+            annotate_stream(manager, detector, reader, args.out_dir, resize_min, resize_max, png_encoder=args.png_encoder,
+                            png_compress=args.png_compress, frame_format=args.frame_format, jpeg_encoder=args.jpeg_encoder,
+                            jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, jpeg_huffman=args.jpeg_huffman)
+        return
     annotate_images(training_manager=manager, detector=detector, input_dir=args.input_dir, out_dir=args.out_dir,
                     image_filenames=frame_filenames(args.input_dir, args.jpeg_decoder or entry.jpeg_decoder()), resize_min=resize_min,
                     resize_max=resize_max, jpeg_decoder=args.jpeg_decoder, png_decoder=args.png_decoder,

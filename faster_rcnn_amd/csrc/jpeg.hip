@@ -58,11 +58,9 @@ __global__ void __launch_bounds__(JPEG_THREADS) k_jpeg_interval(const uint8_t* f
     const int py = my * 8 + (lane >> 3) < h ? my * 8 + (lane >> 3) : h - 1, px = mx * 8 + (lane & 7) < w ? mx * 8 + (lane & 7) : w - 1;
     const uint8_t* p = frame + ((size_t)py * (size_t)w + (size_t)px) * 3;
     const int r = p[bgr ? 2 : 0], g = p[1], b = p[bgr ? 0 : 2];
-    const int chroma_round = (128 << 16) + 32767;
     int comp[3];
-    comp[0] = ((19595 * r + 38470 * g + 7471 * b + 32768) >> 16) - 128;
-    comp[1] = ((-11059 * r - 21709 * g + 32768 * b + chroma_round) >> 16) - 128;
-    comp[2] = ((32768 * r - 27439 * g - 5329 * b + chroma_round) >> 16) - 128;
+    jfif_rgb_to_ycc(r, g, b, &comp[0], &comp[1], &comp[2]);     // (ycc_common.h)
+    comp[0] -= 128; comp[1] -= 128; comp[2] -= 128;
 
     int crow[8], ccol[8];                                       // COS[lane & 7][.] for the row pass, COS[lane >> 3][.] for the column pass
 #pragma unroll

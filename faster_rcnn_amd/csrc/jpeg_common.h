@@ -3,6 +3,7 @@
 // scans and the bit writer.  Everything sits in an unnamed namespace: each translation unit has its own copy, __constant__ data included.
 #pragma once
 #include "common.h"
+#include "ycc_common.h"
 #include "../../include/ext/frcnn_hip_jpeg.h"
 
 namespace frcnn {

@@ -6,6 +6,7 @@
 // each translation unit has its own copy, __constant__ data included.
 #pragma once
 #include "common.h"
+#include "ycc_common.h"
 #include "../../include/ext/frcnn_hip_jpeg_dec.h"
 
 namespace frcnn {
@@ -319,24 +320,17 @@ __device__ __forceinline__ void dec_idct_body(const uint8_t* file, const Plan& p
 }
 
 // ------------------------------------------------------------------------------------------------------------ upsampling, colour
-// a chroma sample at full size: libjpeg's fancy upsampling; a plane of width <= 2 is replicated
+// a chroma sample at full size: libjpeg's fancy upsampling (ycc_common.h); a plane of width <= 2 is replicated
 __device__ __forceinline__ int dec_chroma(const uint8_t* plane, int pw, const Plan& plan, int x, int y) {
     if (plan.hs == 1) return plane[(size_t)y * pw + x];
     const int n = (plan.w + 1) >> 1, i = x >> 1;
     if (plan.vs == 1) {
         const uint8_t* s = plane + (size_t)y * pw;
-        if (n <= 2 || x == 0 || x == 2 * n - 1) return s[i];
-        return (x & 1) ? (3 * s[i] + s[i + 1] + 2) >> 2 : (3 * s[i] + s[i - 1] + 1) >> 2;
+        return n <= 2 ? s[i] : fancy_h2v1(s, n, x);
     }
-    const int rows = (plan.h + 1) >> 1, yr = y >> 1;
-    const uint8_t* near = plane + (size_t)yr * pw;
+    const uint8_t* near = plane + (size_t)(y >> 1) * pw;
     if (n <= 2) return near[i];
-    const int yf = (y & 1) ? (yr + 1 < rows ? yr + 1 : rows - 1) : (yr > 0 ? yr - 1 : 0);
-    const uint8_t* far = plane + (size_t)yf * pw;
-    const int cs = 3 * near[i] + far[i];
-    if (x == 0) return (4 * cs + 8) >> 4;
-    if (x == 2 * n - 1) return (4 * cs + 7) >> 4;
-    return (x & 1) ? (3 * cs + 3 * near[i + 1] + far[i + 1] + 7) >> 4 : (3 * cs + 3 * near[i - 1] + far[i - 1] + 8) >> 4;
+    return fancy_h2v2(near, plane + (size_t)fancy_far_row(y, (plan.h + 1) >> 1) * pw, n, x);
 }
 
 __device__ __forceinline__ void dec_colour_body(const Plan& plan, const DecPlanes planes, int bgr, uint8_t* out, int x, int y) {
@@ -345,12 +339,7 @@ __device__ __forceinline__ void dec_colour_body(const Plan& plan, const DecPlane
     int r = lum, g = lum, b = lum;
     if (plan.components == 3) {
         const int cb = dec_chroma(planes.p[1], planes.pw[1], plan, x, y) - 128, cr = dec_chroma(planes.p[2], planes.pw[2], plan, x, y) - 128;
-        r = lum + ((91881 * cr + 32768) >> 16);
-        b = lum + ((116130 * cb + 32768) >> 16);
-        g = lum + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-        r = r < 0 ? 0 : (r > 255 ? 255 : r);
-        g = g < 0 ? 0 : (g > 255 ? 255 : g);
-        b = b < 0 ? 0 : (b > 255 ? 255 : b);
+        jfif_ycc_to_rgb(lum, cb, cr, &r, &g, &b);
     }
     uint8_t* p = out + ((size_t)y * (size_t)plan.w + (size_t)x) * 3;
     p[0] = (uint8_t)(bgr ? b : r);

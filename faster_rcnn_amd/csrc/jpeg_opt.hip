@@ -87,10 +87,7 @@ __device__ __forceinline__ void load_ycc(const uint8_t* frame, int h, int w, int
     const int py = y < h ? y : h - 1, px = x < w ? x : w - 1;
     const uint8_t* p = frame + ((size_t)py * (size_t)w + (size_t)px) * 3;
     const int r = p[bgr ? 2 : 0], g = p[1], b = p[bgr ? 0 : 2];
-    const int chroma_round = (128 << 16) + 32767;
-    *Y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
-    *Cb = (-11059 * r - 21709 * g + 32768 * b + chroma_round) >> 16;
-    *Cr = (32768 * r - 27439 * g - 5329 * b + chroma_round) >> 16;
+    jfif_rgb_to_ycc(r, g, b, Y, Cb, Cr);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ kernels
@@ -153,9 +150,8 @@ __global__ void __launch_bounds__(S420 ? 512 : 1024) k_opt_interval(const uint8_
             load_ycc(frame, h, w, bgr, my * 16 + 2 * (lane >> 3) + (k >> 1), mx * 16 + 2 * (lane & 7) + (k & 1), &Y, &Cb, &Cr);
             sb += Cb; sr += Cr;
         }
-        const int bias = 1 + (lane & 1);                        // libjpeg's h2v2_downsample: 1 at even, 2 at odd output columns
-        comp[NB - 2] = ((sb + bias) >> 2) - 128;
-        comp[NB - 1] = ((sr + bias) >> 2) - 128;
+        comp[NB - 2] = box2x2(sb, lane) - 128;                  // (libjpeg's h2v2_downsample: ycc_common.h)
+        comp[NB - 1] = box2x2(sr, lane) - 128;
     }
 
     int crow[8], ccol[8];                                       // COS[lane & 7][.] for the row pass, COS[lane >> 3][.] for the column pass

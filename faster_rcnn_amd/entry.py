@@ -46,6 +46,9 @@ PNG_ENCODES = {"png": "runs", "png-huffman": "huffman"}
 # submit_batch(encode="jpeg", quality=q): the device JPEG encoder (ops.jpeg_encode_u8) at the end of an annotating pass
 JPEG_ENCODE = "jpeg"
 JPEG_MODE = (444, "standard")          # ... its default (subsampling, huffman): frcnn_jpeg_encode_u8; any other pair: frcnn_jpeg_opt_encode_u8
+# submit_batch(encode="y4m", y4m=(chroma, range)): the drawn frames as YUV4MPEG2 records (ops.y4m_encode_frames_u8), all B in one launch
+Y4M_ENCODE = "y4m"
+Y4M_MODE = ("420jpeg", "limited")
 PRE_NMS_TOP_N, MAX_PROPOSALS = 8000, 300        # det_util.py:151-156
 
 
@@ -151,6 +154,17 @@ class PngFile(JpegFile):
     under "device_full" ``plan`` is a ``_lib.PngDecFullPlan`` and a palette file's 768 staged palette bytes follow the stream in ``data``.
     A JpegFile to everything that only asks for the frame's size (plan.h, plan.w) and stages ``data``."""
     __slots__ = ()
+
+
+class Y4mFile(JpegFile):
+    """A frame of a YUV4MPEG2 stream (annotate_video.annotate_stream): ``data`` is the frame's planes, ``plan`` a ``_lib.Y4mPlan``.  The
+    device converts it to R,G,B in its source segment beside the other kinds' decodes (ops.Y4M_DECODER: one launch, no workspace, no
+    status)."""
+    __slots__ = ()
+
+
+# host_pixels: the item kind by the label of the decoder whose planner made the plan
+_FILE_KINDS = {"JPEG": JpegFile, "PNG": PngFile, "Y4M": Y4mFile}
 CANVAS_GRANULE = int(os.environ.get("FRCNN_ENTRY_CANVAS_GRANULE", "32"))
 CANVAS_MIN_GEOMETRIES = int(os.environ.get("FRCNN_ENTRY_CANVAS_MIN", "4"))
 # captured passes kept per canvas class: with several classes interleaving in a list, two of one class in flight at once is the common
@@ -287,7 +301,7 @@ class _Slot:
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
-                 "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs")
+                 "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode")
 
     def __init__(self):
         for name in self.__slots__:
@@ -513,6 +527,12 @@ class DetectionEntry:
             s.png_ws = torch.empty(ops.jpeg_workspace_bytes(in_h, in_w, subsampling, huffman), dtype=torch.uint8, device="cuda")
             png_out = [(s.png_dev[i][16:16 + s.png_bound], s.png_dev[i][0:4].view(torch.int32)) for i in range(B)]
             uploaded_rgb = src is not None and bool(int(flip) & 2)
+        elif s.encode == Y4M_ENCODE:
+            # a frame's row: its record [Y | Cb | Cr], ops.y4m_frame_bytes long: the slot's output area is B records back to back
+            chroma, yrange = s.y4m_mode
+            s.png_bound = ops.y4m_frame_bytes(in_h, in_w, chroma)
+            s.png_dev = torch.zeros((B, s.png_bound), dtype=torch.uint8, device="cuda")
+            uploaded_rgb = src is not None and bool(int(flip) & 2)
         elif s.encode:
             # a frame's row: [the file, at most png_bound bytes | pad to 16 | its length, int32 | pad]: one fixed-size copy brings both back
             # (the bound is 0.5 % over the raw frame).  File-backed frames were uploaded in the decoder's order (host_pixels: flip bit 1).
@@ -536,12 +556,16 @@ class DetectionEntry:
                 packed = res["det_packed"]
                 for i in range(B):
                     ops.annotate_u8(u8[i], packed[i] if B > 1 else packed, tables)
+                    if s.encode == Y4M_ENCODE:
+                        continue                                    # (all B frames in one launch behind the loop)
                     if s.encode == JPEG_ENCODE:
                         ops.jpeg_encode_u8(u8[i], quality=s.quality, bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1],
                                            workspace=s.png_ws, subsampling=subsampling, huffman=huffman)
                     elif s.encode:
                         ops.png_encode_u8(u8[i], bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1], workspace=s.png_ws,
                                               compress=compress)
+                if s.encode == Y4M_ENCODE:
+                    ops.y4m_encode_frames_u8(s.io_dev, seg, B, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
             return res
         return run
 
@@ -562,11 +586,13 @@ class DetectionEntry:
         s.extents.upload()
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
-    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None, jpeg_mode=JPEG_MODE):
+    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None, jpeg_mode=JPEG_MODE,
+                      y4m_mode=Y4M_MODE):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
         (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
-        ends in the device JPEG encoder at ``quality`` in ``jpeg_mode`` = (subsampling, huffman)."""
+        ends in the device JPEG encoder at ``quality`` in ``jpeg_mode`` = (subsampling, huffman), "y4m" for one that ends in the YUV4MPEG2
+        encoder in ``y4m_mode`` = (chroma, range)."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -583,7 +609,7 @@ class DetectionEntry:
             stamp("pipeline")
             s = _Slot()
             s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
-            s.encode, s.quality, s.jpeg_mode = encode, quality, jpeg_mode
+            s.encode, s.quality, s.jpeg_mode, s.y4m_mode = encode, quality, jpeg_mode, y4m_mode
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -657,13 +683,18 @@ class DetectionEntry:
         if self.device_preprocess and _declares(image, "raw") and _declares(image, "height"):
             H, W, flip = int(image.height), int(image.width), bool(getattr(image, "flipped", False))
             jpeg_dev, png_dev = jpeg_decoder(), png_decoder()
+            y4m_plan = getattr(image, "y4m_plan", None)
+            if RGB_UPLOAD and isinstance(y4m_plan, _lib.Y4mPlan) and _declares(image, "raw_file"):
+                # a frame of a YUV4MPEG2 stream: its planes go up, the device converts them (no setting: there is no host codec to prefer)
+                return Y4mFile(image.raw_file(), y4m_plan, getattr(image, "_image_path", None) or str(getattr(image, "name", "?"))), H, W, \
+                    (int(y4m_plan.h), int(y4m_plan.w)), 2 | int(flip)
             if RGB_UPLOAD and (jpeg_dev != "host" or png_dev != "host"):
                 from . import feed
                 # None: in-memory pixels, or a file the device decoders do not take
                 planned = feed.plan_entry_file(image, jpeg=jpeg_dev, png=png_dev)
                 if planned is not None:
                     data, plan = planned
-                    kind = PngFile if ops.decoder_of(plan).label == "PNG" else JpegFile
+                    kind = _FILE_KINDS[ops.decoder_of(plan).label]
                     return kind(data, plan, getattr(image, "_image_path", None) or str(getattr(image, "name", "?"))), H, W, \
                         (int(plan.h), int(plan.w)), 2 | int(flip)
             rgb = getattr(image, "raw_rgb", None) if RGB_UPLOAD else None
@@ -801,7 +832,7 @@ class DetectionEntry:
         return self.submit_batch([image], [resize_ratio], det_threshold, [self.host_pixels(image) if pixels is None else pixels], batch=1)
 
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
-                     subsampling=None, huffman=None):
+                     subsampling=None, huffman=None, y4m=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -813,8 +844,23 @@ class DetectionEntry:
         frame is encoded as a baseline JPEG file at that IJG quality (ops.jpeg_encode_u8; key tagged "annotate", "jpeg", quality) and
         ``collect_batch`` returns (num_rois, dets, jpg).  ``quality`` with any other ``encode`` is an error.  ``subsampling`` = 444 / 420
         and ``huffman`` = "standard" / "optimized" (encode="jpeg" only; None: 444, "standard") select the encoder's mode; any pair but the
-        default is a pass of its own, its key tagged with the pair behind the quality -- (444, "standard") IS the pass without them."""
-        if encode == JPEG_ENCODE:
+        default is a pass of its own, its key tagged with the pair behind the quality -- (444, "standard") IS the pass without them.
+        ``encode`` = "y4m" with ``y4m`` = (chroma, range) ("420jpeg" / "444", "limited" / "full"; None: Y4M_MODE): the B drawn frames are
+        converted to YUV4MPEG2 records [Y | Cb | Cr] in one launch (ops.y4m_encode_frames_u8; key tagged "annotate", "y4m", chroma, range)
+        and ``collect_batch`` returns (num_rois, dets, record).  ``y4m`` with any other ``encode`` is an error."""
+        y4m_mode = Y4M_MODE
+        if encode == Y4M_ENCODE:
+            y4m_mode = Y4M_MODE if y4m is None else tuple(y4m)
+            if len(y4m_mode) != 2 or y4m_mode[0] not in _lib.Y4M_OUT_CHROMAS or y4m_mode[1] not in _lib.Y4M_RANGES:
+                raise FrcnnError("submit_batch: y4m=%r: (chroma, range) with chroma one of %s and range one of %s"
+                                 % (y4m, ", ".join(_lib.Y4M_OUT_CHROMAS), ", ".join(_lib.Y4M_RANGES)))
+            if quality is not None or subsampling is not None or huffman is not None:
+                raise FrcnnError("submit_batch: quality / subsampling / huffman go with encode=\"%s\" only" % JPEG_ENCODE)
+        elif y4m is not None:
+            raise FrcnnError("submit_batch: y4m=%r goes with encode=\"%s\" only" % (y4m, Y4M_ENCODE))
+        if encode == Y4M_ENCODE:
+            pass
+        elif encode == JPEG_ENCODE:
             if not annotate:
                 raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
             if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
@@ -844,6 +890,8 @@ class DetectionEntry:
             key = key + ((B,) if B > 1 else ()) + (("annotate", encode) if encode else ("annotate",)) + ((quality,) if quality else ())
             if encode == JPEG_ENCODE and jpeg_mode != JPEG_MODE:
                 key = key + jpeg_mode
+            if encode == Y4M_ENCODE:
+                key = key + y4m_mode
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -852,7 +900,7 @@ class DetectionEntry:
             s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
         else:
             s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality,
-                                                                     jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE))
+                                                                     jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode))
         metas, files = [], []
         for i in range(B):
             j = i if i < len(images) else 0
@@ -899,13 +947,14 @@ class DetectionEntry:
         ``files``: (frame index, JpegFile) of the pass's file-backed frames; item k is files[k], its output frame i's source segment.  A
         file that fills several frames (the padding of a short group) is staged once."""
         B = s.batch
-        kind_of = lambda f: 2 if isinstance(f, PngFile) else int(isinstance(f.plan, _lib.JpegDecFullPlan))
-        files.sort(key=lambda t: kind_of(t[1]))                     # (in place, stable: the baseline .jpg items, the progressive ones, the .png items)
-        nj, nf = (sum(1 for _, f in files if kind_of(f) == k) for k in (0, 1))
+        kind_of = lambda f: 3 if isinstance(f, Y4mFile) else 2 if isinstance(f, PngFile) else int(isinstance(f.plan, _lib.JpegDecFullPlan))
+        files.sort(key=lambda t: kind_of(t[1]))                     # (in place, stable: the baseline .jpg items, the progressive ones, the .png items, the y4m frames)
+        nj, nf, npng = (sum(1 for _, f in files if kind_of(f) == k) for k in (0, 1, 2))
         item = ctypes.sizeof(_lib.JpegDecBatchItem)
         first_full = B * (item + ctypes.sizeof(_lib.PngDecFullBatchItem))      # [B JPEG items | B PNG items], room for the larger kind of PNG item
-        # ... | B progressive items] only in a pass that holds such a file: their items are 5 KB each
-        table = (first_full + (B * ctypes.sizeof(_lib.JpegDecFullBatchItem) if nf else 0) + 255) // 256 * 256
+        # ... | B progressive items] only in a pass that holds such a file: their items are 5 KB each; ... | B y4m items] behind them
+        first_y4m = self._first_y4m_item(B, nf)
+        table = (first_y4m + B * ctypes.sizeof(_lib.Y4mBatchItem) + 255) // 256 * 256
         at, seen, file_off = 0, {}, []
         for _, f in files:
             if id(f) not in seen:
@@ -921,11 +970,13 @@ class DetectionEntry:
         # one kind of PNG item per pass: with a full-format plan among them (png_decoder "device_full") revision-1 plans, which a pass
         # can only hold when the setting changed under way, are restated as full-format ones
         np_ = nj + nf                                                # the first .png item
-        full = any(isinstance(p, _lib.PngDecFullPlan) for p in plans[np_:])
+        ny = np_ + npng                                              # the first y4m item
+        full = any(isinstance(p, _lib.PngDecFullPlan) for p in plans[np_:ny])
         s.png_dec = ops.PNG_DECODERS["device_full" if full else "device"]
         if full:
-            plans[np_:] = [ops.png_dec_full_of(p) if isinstance(p, _lib.PngDecPlan) else p for p in plans[np_:]]
-        kinds = ((ops.JPEG_DECODER, 0, nj), (ops.JPEG_FULL_DECODER, nj, np_), (s.png_dec, np_, len(plans)))    # per decoder: its items of the pass
+            plans[np_:ny] = [ops.png_dec_full_of(p) if isinstance(p, _lib.PngDecPlan) else p for p in plans[np_:ny]]
+        # per decoder: its items of the pass
+        kinds = ((ops.JPEG_DECODER, 0, nj), (ops.JPEG_FULL_DECODER, nj, np_), (s.png_dec, np_, ny), (ops.Y4M_DECODER, ny, len(plans)))
         ws_off, need = [], 0
         for dec, lo, hi in kinds:
             for k in range(lo, hi, dec.batch_max):                  # (a call takes batch_max items: its regions behind the last call's)
@@ -939,17 +990,24 @@ class DetectionEntry:
             s.jpg_status_pin = torch.zeros(B, dtype=torch.int32).pin_memory()
         out_off = [i * s.seg for i, _ in files]
         # (a palette lies behind its stream in the file's staged bytes: DeviceDecoder.items)
-        s.jpg_items, s.full_items, s.png_items = (dec.items(plans[lo:hi], file_off[lo:hi], out_off[lo:hi], ws_off[lo:hi]) for dec, lo, hi in kinds)
+        s.jpg_items, s.full_items, s.png_items, s.y4m_items = (dec.items(plans[lo:hi], file_off[lo:hi], out_off[lo:hi], ws_off[lo:hi])
+                                                               for dec, lo, hi in kinds)
         s.jpg_count = nj
         s.jpg_decs = [dec for dec, lo, hi in kinds for _ in range(lo, hi)]     # item k's decoder
         s.jpg_used = table + at
         s.jpg_names = [f.name for _, f in files]                    # (item k's status word is word k, in the order of ``kinds``)
         host = s.jpg_pin.numpy()
-        for items, first in ((s.jpg_items, 0), (s.png_items, B * item), (s.full_items, first_full)):
+        for items, first in ((s.jpg_items, 0), (s.png_items, B * item), (s.full_items, first_full), (s.y4m_items, first_y4m)):
             if len(items):
                 host[first:first + ctypes.sizeof(items)] = np.frombuffer(items, dtype=np.uint8)
         for f in {id(f): f for _, f in files}.values():
             host[table + seen[id(f)]:table + seen[id(f)] + len(f.data)] = np.frombuffer(f.data, dtype=np.uint8)
+
+    @staticmethod
+    def _first_y4m_item(B, progressive):
+        """Where the y4m items lie in a slot's staged table: behind the JPEG, the PNG and (in a pass that holds one) the progressive items."""
+        return B * (ctypes.sizeof(_lib.JpegDecBatchItem) + ctypes.sizeof(_lib.PngDecFullBatchItem)
+                    + (ctypes.sizeof(_lib.JpegDecFullBatchItem) if progressive else 0))
 
     def _decode_files(self, s, files):
         """Device side, on the pass's stream between the io copy and the canvas preprocess / the replay: one upload of the staged area,
@@ -962,7 +1020,9 @@ class DetectionEntry:
         s.jpg_status.zero_()
         # per decoder: its items, its first status word, where its items lie in the staged area; the .png items' launches go first
         first_full = s.batch * (item + ctypes.sizeof(_lib.PngDecFullBatchItem))
-        for dec, items, word, first in ((s.png_dec, s.png_items, nj + len(s.full_items), s.batch * item),
+        for dec, items, word, first in ((ops.Y4M_DECODER, s.y4m_items, nj + len(s.full_items) + len(s.png_items),
+                                         self._first_y4m_item(s.batch, len(s.full_items))),
+                                        (s.png_dec, s.png_items, nj + len(s.full_items), s.batch * item),
                                         (ops.JPEG_FULL_DECODER, s.full_items, nj, first_full), (ops.JPEG_DECODER, s.jpg_items, 0, 0)):
             if dec is ops.JPEG_DECODER and not batched:
                 continue
@@ -1044,6 +1104,8 @@ class DetectionEntry:
                     if 16 + n > s.first_copy:               # a file longer than the first copy: its remainder now (synchronous)
                         data += s.png_dev[i][s.first_copy:16 + n].cpu().numpy().tobytes()
                     res.append((n_rois, dets, data))
+                elif s.encode == Y4M_ENCODE:
+                    res.append((n_rois, dets, s.png_pin[i].numpy().tobytes()))      # the frame's record: a fixed size, no length word
                 elif s.encode:
                     row = s.png_pin[i].numpy()
                     n = int(row[-16:-12].view(np.int32)[0])

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import y4m as _y4m
 
 NMS_MAX_BOXES = 12288
 
@@ -1297,8 +1298,12 @@ class DeviceDecoder:
     unsupported: type
     palette: bool = False
     whole_file: bool = False
+    stateless: bool = False         # its kernels need no workspace and report no status (no <stem>_workspace_bytes / _batch_layout)
+    planner: object = None          # a Python planner (the y4m header is text: y4m.parse_header) instead of frcnn_<stem>_plan
 
     def plan(self, data):
+        if self.planner is not None:
+            return self.planner(data)
         who = self.stem + "_plan"
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise _lib.FrcnnError("%s: the file's bytes, got %s" % (who, type(data).__name__))
@@ -1312,6 +1317,8 @@ class DeviceDecoder:
         return plan
 
     def workspace_bytes(self, plan):
+        if self.stateless:
+            return 0
         who = self.stem + "_workspace_bytes"
         n = int(getattr(_lib.load(), "frcnn_" + who)(ctypes.byref(plan)))
         if n == 0:
@@ -1322,6 +1329,8 @@ class DeviceDecoder:
         who, n = self.stem + "_batch_layout", len(plans)
         if not 1 <= n <= self.batch_max:
             raise _lib.FrcnnError(f"{who}: {n} plans, 1..{self.batch_max} go into one batch")
+        if self.stateless:
+            return [0] * n, 0
         arr = (self.plan_type * n)(*plans)
         offs = (ctypes.c_uint64 * n)()
         total = int(getattr(_lib.load(), "frcnn_" + who)(arr, n, offs))
@@ -1347,18 +1356,23 @@ class DeviceDecoder:
             raise _lib.FrcnnError("%s: items must be a table made by %s" % (who, self.items_name))
         if items_dev is None:
             items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).cuda()
-        if status is None:
+        if status is None and not self.stateless:
             status = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
-        if workspace is None:
+        if self.stateless:
+            workspace = None
+        elif workspace is None:
             workspace = _ws(max((int(it.ws_off) + self.workspace_bytes(it.plan) for it in items), default=0))
         for name, t, dt in (("files", files, torch.uint8), ("out", out, torch.uint8), ("status", status, torch.int32),
                             ("workspace", workspace, torch.uint8), ("items_dev", items_dev, torch.uint8)):
+            if t is None and self.stateless and name in ("workspace", "status"):
+                continue
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
                 raise _lib.FrcnnError(f"{who}: {name} must be a contiguous {dt} device tensor")
-        if items_dev.numel() < ctypes.sizeof(items) or status.numel() < n:
+        if items_dev.numel() < ctypes.sizeof(items) or (status is not None and status.numel() < n):
             raise _lib.FrcnnError(f"{who}: items_dev of {items_dev.numel()} bytes / status of {status.numel()} words for {n} items")
         _lib.call("frcnn_" + who, ctypes.addressof(items), _p(items_dev), n, _p(files), files.numel(), 1 if bgr else 0,
-                  _p(out), out.numel(), _p(status), _p(workspace), workspace.numel(), _stream())
+                  _p(out), out.numel(), _p(status) if status is not None else None, _p(workspace) if workspace is not None else None,
+                  workspace.numel() if workspace is not None else 0, _stream())
         return status
 
     # ---- the PNG records only: a .png file's zlib stream is gathered on the host
@@ -1414,7 +1428,25 @@ PNG_DECODERS = {
                                  _lib.PngDecFullBatchItem, _lib.PNG_DEC_BATCH_MAX, PngUnsupported, palette=True),
 }
 _PNG1, _PNGF = PNG_DECODERS["device"], PNG_DECODERS["device_full"]
-_DECODER_OF = {d.plan_type: d for d in (JPEG_DECODER, JPEG_FULL_DECODER, _PNG1, _PNGF)}
+
+
+# ``y4m_parse_header``: a stream outside the supported set (10/12/16-bit samples, interlaced frames, C420paldv, C411, C444alpha); a
+# FrcnnError whose message names the reason (the class y4m.Y4mReader raises too)
+Y4mUnsupported = _y4m.Y4mUnsupported
+
+
+def y4m_parse_header(data):
+    """The header of a YUV4MPEG2 stream (``data``: bytes that hold at least its first line) -> a ``_lib.Y4mPlan``: h, w, chroma, range,
+    frame_bytes (the C fields: what a batch item carries), ``chroma_name`` / ``range_name``, and as attributes ``tags`` -- the F / A / I
+    values verbatim -- and ``header_len``.  ``Y4mUnsupported`` (a FrcnnError) with the reason for a stream outside the supported set,
+    ``FrcnnError`` for a broken header.  Pure host work, no library needed."""
+    return _y4m.parse_header(data)
+
+
+# YUV4MPEG2 frames (include/ext/frcnn_hip_y4m.h): what it stages of a frame is the frame; stateless, a Python planner
+Y4M_DECODER = DeviceDecoder("Y4M", "device", "y4m", "y4m_decode", "y4m_batch_items", _lib.Y4mPlan, _lib.Y4mBatchItem, _lib.Y4M_BATCH_MAX,
+                            Y4mUnsupported, whole_file=True, stateless=True, planner=y4m_parse_header)
+_DECODER_OF = {d.plan_type: d for d in (JPEG_DECODER, JPEG_FULL_DECODER, _PNG1, _PNGF, Y4M_DECODER)}
 
 
 def decoder_of(plan):
@@ -1540,6 +1572,88 @@ def jpeg_decode_full_u8(file_bytes, bgr=False):
     reverse with ``bgr``.  ``JpegUnsupported`` for a file outside the supported set, ``FrcnnError`` with the status word for a damaged
     one."""
     return JPEG_FULL_DECODER.decode_one(file_bytes, bgr)
+
+
+# ---- YUV4MPEG2 frames (include/ext/frcnn_hip_y4m.h, csrc/y4m.hip)
+def y4m_frame_bytes(h, w, chroma="420jpeg"):
+    """Bytes of one frame's planes [Y | Cb | Cr] in chroma mode ``chroma`` ("420jpeg", "420mpeg2", "422", "444", "mono")."""
+    return _y4m.frame_bytes(h, w, chroma)
+
+
+def y4m_plan(h, w, chroma="420jpeg", range="limited", tags=None):       # noqa: A002 -- the format's own word
+    """A ``_lib.Y4mPlan`` without a header: frames of (h, w) in ``chroma`` and ``range`` ("limited" / "full")."""
+    return _y4m.make_plan(h, w, chroma, range, tags)
+
+
+def y4m_batch_items(plans, file_off, out_off):
+    """The item table of a batch (``_lib.Y4mBatchItem`` x n, a ctypes array: ``bytes(table)`` is what goes to the device)."""
+    return Y4M_DECODER.items(plans, file_off, out_off, [0] * len(plans))
+
+
+def y4m_decode_batch_u8(files, items, out, bgr=False, items_dev=None):
+    """Up to 64 y4m frames, of any mix of sizes, chroma modes and ranges, to interleaved RGB in ONE launch
+    (frcnn_y4m_decode_batch_u8): ``files`` a 1-d uint8 device tensor that holds the frames' planes, ``items`` the table
+    (``y4m_batch_items``: per frame its plan, where its bytes lie in ``files`` and where its (h, w, 3) frame goes in ``out``), ``out``
+    a 1-d uint8 device tensor.  ``items_dev``: a device tensor that already holds ``bytes(items)``; None: uploaded here (a pageable
+    copy, which blocks the host).  Never synchronises otherwise; there is no status: a frame cannot be damaged."""
+    Y4M_DECODER.decode(files, items, out, bgr, None, None, items_dev)
+    return out
+
+
+def y4m_decode_u8(frame_bytes_dev, plan, out=None, bgr=False):
+    """One y4m frame on the device (frcnn_y4m_decode_u8, the batch of one): ``frame_bytes_dev`` a 1-d uint8 device tensor that holds
+    the frame's planes (or ``bytes``: uploaded here), ``plan`` a ``_lib.Y4mPlan`` (``y4m_parse_header`` / ``y4m_plan``) -> ``out``, an
+    (h, w, 3) uint8 device tensor, R,G,B per pixel or (``bgr``) B,G,R.  Never synchronises."""
+    _require_gpu()
+    if isinstance(frame_bytes_dev, (bytes, bytearray, memoryview)):
+        frame_bytes_dev = torch.frombuffer(bytearray(frame_bytes_dev), dtype=torch.uint8).cuda()
+    t = frame_bytes_dev
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous()):
+        raise _lib.FrcnnError("y4m_decode_u8: the frame must be bytes or a contiguous 1-d uint8 device tensor")
+    if not isinstance(plan, _lib.Y4mPlan):
+        raise _lib.FrcnnError("y4m_decode_u8: plan must be a Y4mPlan (y4m_parse_header, y4m_plan)")
+    h, w = int(plan.h), int(plan.w)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
+        raise _lib.FrcnnError("y4m_decode_u8: out must be a contiguous uint8 device tensor")
+    _lib.call("frcnn_y4m_decode_u8", _p(t) if t.numel() else None, t.numel(), ctypes.byref(plan), 1 if bgr else 0, _p(out), out.numel(),
+              _stream())
+    return out
+
+
+def y4m_encode_frames_u8(frames, frame_stride, n, h, w, chroma="420jpeg", range="limited", bgr=False, out=None):     # noqa: A002
+    """``n`` interleaved (h, w, 3) frames that lie ``frame_stride`` bytes apart in the uint8 device tensor ``frames`` -> ``out``, a
+    uint8 device tensor [n][>= y4m_frame_bytes(h, w, chroma)]: per frame the record [Y | Cb | Cr], in ONE launch
+    (frcnn_y4m_encode_u8).  ``chroma`` "420jpeg" or "444".  Never synchronises: capturable with fixed buffers."""
+    _require_gpu()
+    if chroma not in _lib.Y4M_OUT_CHROMAS or range not in _lib.Y4M_RANGES:
+        raise _lib.FrcnnError("y4m_encode_u8: chroma=%r (%s), range=%r (%s)" % (chroma, ", ".join(_lib.Y4M_OUT_CHROMAS), range,
+                                                                               ", ".join(_lib.Y4M_RANGES)))
+    n, h, w = int(n), int(h), int(w)
+    record = _y4m.frame_bytes(h, w, chroma)
+    if out is None:
+        out = torch.empty((n, record), dtype=torch.uint8, device="cuda")
+    for name, t in (("frames", frames), ("out", out)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise _lib.FrcnnError(f"y4m_encode_u8: {name} must be a contiguous uint8 device tensor")
+    if out.dim() != 2 or out.shape[0] < n or n < 1 or frames.numel() < (n - 1) * int(frame_stride) + h * w * 3:
+        raise _lib.FrcnnError("y4m_encode_u8: %d frames of stride %d in %d bytes, out %s" % (n, frame_stride, frames.numel(), tuple(out.shape)))
+    _lib.call("frcnn_y4m_encode_u8", _p(frames), int(frame_stride), n, h, w, 1 if bgr else 0, _lib.Y4M_CHROMAS[chroma],
+              _lib.Y4M_RANGES[range], _p(out), int(out.shape[1]), out.numel(), _stream())
+    return out
+
+
+def y4m_encode_u8(frame_dev, chroma="420jpeg", range="limited", bgr=False, out=None):       # noqa: A002
+    """An (h, w, 3) uint8 device frame, R,G,B per pixel or (``bgr``) B,G,R -> its y4m record [Y | Cb | Cr] as a 1-d uint8 device tensor
+    of y4m_frame_bytes(h, w, chroma) bytes; an (n, h, w, 3) tensor -> [n][record], all frames in one launch."""
+    if not (isinstance(frame_dev, torch.Tensor) and frame_dev.dim() in (3, 4) and frame_dev.shape[-1] == 3):
+        raise _lib.FrcnnError("y4m_encode_u8: frame must be an (h, w, 3) or (n, h, w, 3) uint8 device tensor")
+    single = frame_dev.dim() == 3
+    n = 1 if single else int(frame_dev.shape[0])
+    h, w = int(frame_dev.shape[-3]), int(frame_dev.shape[-2])
+    res = y4m_encode_frames_u8(frame_dev, h * w * 3, n, h, w, chroma, range, bgr, out if out is None or out.dim() == 2 else out.view(1, -1))
+    return res[0] if single else res
 
 
 def png_dec_plan(data):

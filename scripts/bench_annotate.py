@@ -16,6 +16,9 @@ per frame) instead of uniform noise: noise does not compress, so bytes per frame
 ``jpeg_host_420_opt`` and ``jpeg_device_420_opt`` are the same two with ``jpeg_subsampling=420, jpeg_huffman="optimized"`` (PIL's
 ``subsampling=2, optimize=True``; the device encoder's csrc/jpeg_opt.hip); every leg reports its bytes per frame.
 
+``--y4m`` runs three file-to-file legs instead (``run_y4m``): a YUV4MPEG2 stream to a YUV4MPEG2 stream, the stream to PNG files (device
+encoder) and PNG files to PNG files (host codecs), alternating in one session.
+
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
 """
@@ -173,6 +176,60 @@ def run_pair(name, cfg, n_frames, reps, encoders=("host",), content="noise"):
     return res
 
 
+def run_y4m(name, cfg, n_frames, reps, content="noise"):
+    """``--y4m``: three file-to-file legs in ONE session, alternating inside every repetition: a YUV4MPEG2 stream to a YUV4MPEG2 stream
+    (annotate_stream: the frames converted on the device at both ends of their pass), the same stream to PNG files through the device PNG
+    encoder, and the PNG-file to PNG-file leg (c) with the host's codecs, as ``run_pair`` times it.  The input stream is the PNG
+    frames' content converted by ops.y4m_encode_u8 (4:2:0, limited range)."""
+    import numpy as np
+    import torch
+    from PIL import Image as PilImage
+    from faster_rcnn_amd import annotate_video, ops, y4m
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    with tempfile.TemporaryDirectory() as tmp:
+        d_in, d_out, clip, clip_out = (os.path.join(tmp, x) for x in ("in", "out", "in.y4m", "out.y4m"))
+        os.makedirs(d_in)
+        names = ["%06d.png" % i for i in range(n_frames)]
+        with open(clip, "wb") as f:
+            writer = y4m.Y4mWriter(f, w, h, "420jpeg", "limited", {"F": "25:1"})
+            for nm, s in zip(names, srcs):
+                PilImage.fromarray(s[:, :, ::-1]).save(os.path.join(d_in, nm), compress_level=1)
+                writer.write(ops.y4m_encode_u8(torch.from_numpy(s).cuda(), "420jpeg", "limited", bgr=True).cpu().numpy().tobytes())
+
+        def y4m_to_y4m():
+            with open(clip, "rb") as fin, open(clip_out, "wb") as fout:
+                reader = y4m.Y4mReader(fin, name=clip)
+                sink = y4m.Y4mWriter(fout, w, h, "420jpeg", reader.plan.range_name, reader.plan.tags)
+                annotate_video.annotate_stream(mgr, det, reader, sink, *cfg["resize"])
+
+        def y4m_to_png():
+            with open(clip, "rb") as fin:
+                annotate_video.annotate_stream(mgr, det, y4m.Y4mReader(fin, name=clip), d_out, *cfg["resize"], png_encoder="device")
+
+        def png_to_png():
+            annotate_video.annotate_images(mgr, det, d_in, d_out, names, *cfg["resize"], png_encoder="host", png_compress="runs")
+
+        legs = {"y4m_to_y4m": y4m_to_y4m, "y4m_to_png_device": y4m_to_png, "png_to_png_host": png_to_png}
+        times = {k: [] for k in legs}
+        with contextlib.redirect_stdout(io.StringIO()):
+            for fn in legs.values():                                # warm-up: captures
+                fn()
+            for _ in range(reps):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    fn()
+                    times[k].append(time.perf_counter() - t0)
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "y4m_bytes_per_frame": y4m.frame_bytes(h, w, "420jpeg")}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--frames", type=int, default=256)
@@ -182,12 +239,17 @@ def main():
                     help="who encodes leg (c)'s output files; all = host, device (runs) and device (huffman), alternating")
     ap.add_argument("--legs", default=None, help="the legs (c) by name, comma-separated (%s); overrides --png_encoder" % ", ".join(LEGS))
     ap.add_argument("--content", choices=("noise", "photo"), default="noise", help="what the frames hold (see the module docstring)")
+    ap.add_argument("--y4m", action="store_true", help="instead of the legs above: y4m to y4m, y4m to PNG files (device encoder) and PNG files "
+                                                       "to PNG files (host codecs), alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_annotate.py needs a GPU")
     out = {"metric": "annotate_frames_per_s", "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
     for name in args.pairs.split(","):
+        if args.y4m:
+            out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
         encoders = {"both": ("host", "device"), "all": ("host", "device", "device_huffman")}.get(args.png_encoder, (args.png_encoder,))
         if args.legs:
             encoders = tuple(args.legs.split(","))
