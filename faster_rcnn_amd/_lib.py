@@ -158,6 +158,21 @@ EXT_SIGNATURES = {
     "frcnn_vgg_conv1_bf16_fwd_extents": (I, [P, I, I, I, P, P, P, P, P]),
 }
 
+ROI_RES_VERSION = 1     # include/ext/frcnn_hip_roi_res.h FRCNN_ROI_RES_VERSION
+ROI_TAP_BYTES = 32      # ... FRCNN_ROI_TAP_BYTES
+ROI_RES_SIGNATURES = {
+    "frcnn_roi_res_version": (I, []),
+    "frcnn_roi_tap_table": (I, [I, I, I, P, I, I, I, I, I, P, P]),
+    "frcnn_conv2d_roi_res_available": (I, [P, I, I]),
+    "frcnn_conv2d_fwd_h3_roi_res": (I, [P, P, P, P, P, P, P, P, P, P, P, P, ctypes.c_float, ctypes.c_float, P]),
+}
+
+
+class RoiRes(ctypes.Structure):
+    """frcnn_roi_res (include/ext/frcnn_hip_roi_res.h)."""
+    _fields_ = [("map", c_void_p), ("taps", c_void_p), ("fill", c_void_p), ("map_rows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 PNG_VERSION = 1         # include/ext/frcnn_hip_png.h FRCNN_PNG_VERSION
 PNG_SIGNATURES = {
     "frcnn_png_version": (I, []),
@@ -413,6 +428,10 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in ROI_RES_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
     for name, (res, args) in PNG_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -483,6 +502,9 @@ def load():
     if lib.frcnn_png_version() != PNG_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_png_version()} of the PNG encoder extension, this binding "
                          f"{PNG_VERSION} (include/ext/frcnn_hip_png.h): rebuild with `python -m faster_rcnn_amd.build`")
+    if lib.frcnn_roi_res_version() != ROI_RES_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_roi_res_version()} of the gathered-residual extension, this binding "
+                         f"{ROI_RES_VERSION} (include/ext/frcnn_hip_roi_res.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_vgg_canvas_version() != VGG_CANVAS_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_vgg_canvas_version()} of the VGG16 canvas extension, this binding "
                          f"{VGG_CANVAS_VERSION} (include/ext/frcnn_hip_vgg_canvas.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -42,6 +42,10 @@ struct ConvArgs {
     // the residual as two fp16 planes [2][M][Cout] under the scale 2^*res_pexp (a block's output handed on as planes only: the next
     // block's shortcut reads them back, residual == NULL then); the vector epilogues of the f16x3 256x128 forms only
     const void* res_planes = nullptr; const int* res_pexp = nullptr;
+    // the residual GATHERED from a map by RoI taps (include/ext/frcnn_hip_roi_res.h; residual == NULL and res_planes == NULL then):
+    // res_map [res_map_rows][Cout] f32, res_taps one 32-byte record per output row (k_roi_tap_table), res_fill [Cout] or NULL: what a
+    // rejected RoI yields.  The 16-waves 256x128 forms of conv_h3.hip only, as instantiations of their own (x6_epilogue_vec<.., GRES>).
+    const float* res_map = nullptr; const void* res_taps = nullptr; const float* res_fill = nullptr; int res_map_rows = 0;
 };
 
 // ---- magnitude records.  A record is AMAX_SLOTS floats, one per 128-byte line: a launch has hundreds to thousands of waves and a
@@ -316,7 +320,25 @@ struct X6Tile {
 // of whole rows (scale / shift / residual / mask / y as b128, out-of-range pieces on the buffer descriptors).
 // PLANES (conv_h3.hip): the tile also leaves as two fp16 planes under the scale y_scale (a power of two): ah = f16(v * s), al = f16((v * s - ah) * 2^11),
 // 8-byte pieces at [plane][row][column]; the f32 store is skipped when the launch has no f32 output.
-template <int TM, int TN, int WM, int WN, bool PLANES = false, bool S16 = false>
+// GRES: one 16-byte piece of the RoI-resampled residual from its four source pieces -- k_roi_fwd's LERP2 (roi.hip, built with
+// -ffp-contract=off), operation by operation: the translation units that include this contract by default, hence the pragma.
+__device__ __forceinline__ f32x4 roi_res_piece(const f32x4 a, const f32x4 b, const f32x4 d, const f32x4 e, float tx, float ty) {
+#pragma clang fp contract(off)
+    f32x4 v;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float top = a[c] + (b[c] - a[c]) * tx;
+        const float bot = d[c] + (e[c] - d[c]) * tx;
+        v[c] = top + (bot - top) * ty;
+    }
+    return v;
+}
+
+// GRES (ConvArgs.res_map): the residual is not read but resampled here -- per row the tap record (offsets of the four source rows of
+// the map, tx, ty, ok), per piece four 16-byte loads of the map (L2 / Infinity Cache: the map is a few per cent of the tensor it
+// replaces) and roi_res_piece, or the piece of res_fill when the RoI was rejected.  The records of wave-row h + 1 are requested with
+// the pieces of wave-row h, so only the first wave-row waits for its records.  Everything behind the residual is the common code.
+template <int TM, int TN, int WM, int WN, bool PLANES = false, bool S16 = false, bool GRES = false>
 __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const ConvArgs& p, int m0, int n0, int tid, int wm, int wn, int li, int lh, float* smem,
                                                 float y_scale = 1.0f) {
     constexpr int NT = 64 * WM * WN, BN = 32 * TN * WN, HB = 32 * TM, LD = BN + 4, C4 = BN / 4, RPP = NT / C4, PASSES = HB / RPP;
@@ -345,12 +367,36 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
     f32x4 rres[PASSES], rmask[PASSES];
     float vmax = 0.0f;
     unsigned pseen = 0u;
+    // GRES: the map, the tap records (two 16-byte words per row) and the fill piece of this thread's columns
+    const __amdgpu_buffer_rsrc_t gmrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(GRES ? p.res_map : p.x), 0, GRES ? (int)((size_t)p.res_map_rows * p.Cout * 4) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t gtrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<void*>(GRES ? p.res_taps : (const void*)p.x), 0, GRES ? (int)((size_t)p.M * 32) : 0, 0x00020000);
+    f32x4 gfill = {0.0f, 0.0f, 0.0f, 0.0f}, graw[GRES ? PASSES : 1][4];
+    i32x4 goff[GRES ? PASSES : 1], gw[GRES ? PASSES : 1];
+    auto fetch_taps = [&](int h) {                           // (rows past M: an out-of-range request reads zeros -- ok = 0, offsets 0)
+#pragma unroll
+        for (int q = 0; q < (GRES ? PASSES : 0); ++q) {
+            const int m = m0 + h * HB + q * RPP + prow;
+            const unsigned toff = (h < WM && m < p.M) ? (unsigned)m * 32u : OOB_OFFSET;
+            goff[q] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(gtrsrc, toff, 0, 0));
+            gw[q] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(gtrsrc, toff == OOB_OFFSET ? OOB_OFFSET : toff + 16u, 0, 0));
+        }
+    };
+    if constexpr (GRES) {
+        if (p.res_fill && n < p.Cout) gfill = *reinterpret_cast<const f32x4*>(p.res_fill + n);
+        fetch_taps(0);
+    }
     auto fetch = [&](int h) {                                // the global reads of wave-row h: in flight while it goes through LDS
 #pragma unroll
         for (int q = 0; q < PASSES; ++q) {
             const int m = m0 + h * HB + q * RPP + prow;
             const bool in = m < p.M && n < p.Cout;
-            if (p.residual) rres[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, in ? (unsigned)(((size_t)m * p.ldres + n) * 4) : OOB_OFFSET, 0, 0));
+            if constexpr (GRES) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    graw[q][k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gmrsrc, in ? ((unsigned)goff[q][k] + (unsigned)n) * 4u : OOB_OFFSET, 0, 0));
+            } else if (p.residual) rres[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, in ? (unsigned)(((size_t)m * p.ldres + n) * 4) : OOB_OFFSET, 0, 0));
             else if (p.res_planes) {                         // (8 + 8 bytes: the same bytes per element as the f32 tensor)
                 typedef _Float16 f16x4r __attribute__((ext_vector_type(4)));
                 typedef int i32x2r __attribute__((ext_vector_type(2)));
@@ -366,6 +412,16 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
 #pragma unroll 1
     for (int h = 0; h < WM; ++h) {
         fetch(h);
+        float gtx[PASSES], gty[PASSES];
+        bool gok[PASSES];
+        if constexpr (GRES) {                                // this wave-row's fractions are kept, its records make way for the next wave-row's
+#pragma unroll
+            for (int q = 0; q < PASSES; ++q) {
+                const int wtx = gw[q][0], wty = gw[q][1];    // (copies: __builtin_bit_cast of a vector ELEMENT reads element 0 whatever the index)
+                gtx[q] = __builtin_bit_cast(float, wtx); gty[q] = __builtin_bit_cast(float, wty); gok[q] = gw[q][2] != 0;
+            }
+            fetch_taps(h + 1);
+        }
         if (h) __syncthreads();                              // the previous wave-row has been read out (the caller synchronised before pass 0)
         if (wm == h) {
 #pragma unroll
@@ -385,6 +441,13 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
                 }
         }
         __syncthreads();
+        if constexpr (GRES) {
+#pragma unroll
+            for (int q = 0; q < PASSES; ++q) {
+                const f32x4 v = roi_res_piece(graw[q][0], graw[q][1], graw[q][2], graw[q][3], gtx[q], gty[q]);
+                rres[q] = gok[q] ? v : gfill;
+            }
+        }
         const float* src = smem + prow * LD + pcol;
 #pragma unroll
         for (int q = 0; q < PASSES; ++q) {
@@ -393,7 +456,7 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 float t = a[c] * sc[c] + sh[c];
-                if (p.residual || p.res_planes) t += rres[q][c];
+                if (GRES || p.residual || p.res_planes) t += rres[q][c];
                 if (p.mask && !(rmask[q][c] > 0.0f)) t = 0.0f;
                 v[c] = activate(t, y_act);
             }
@@ -453,5 +516,6 @@ int x6_tile_width(int cfg);
 // conv_h3.hip: the same GEMM on the fp16 matrix cores (two-way split with a scaled low part); `a.w` = header + two filter planes
 int launch_conv_h3(const ConvArgs& a, int cfg, hipStream_t s);
 int h3_tile_width(int cfg);
+bool h3_takes_ring(int cfg, int kpad);
 
 }  // namespace frcnn

@@ -578,7 +578,9 @@ __device__ __forceinline__ void h3_ring_tile(const ConvArgs& p, char* lds) {
 // APLANES: the activations arrive ALREADY split -- two fp16 planes [2][rows][Cin] a producing launch's epilogue wrote under the scale
 // 2^*x_pexp (ConvArgs.x_planes): 16-byte pieces go from memory to LDS unchanged, no conversion and no arithmetic in the loader (lab:
 // the head's 3x3 / 512 -> 2048 / 2048 -> 512 GEMMs 195 / 103 / 89 us against 246 / 127 / 104 with the split in the loader).
-template <int TM, int TN, int WM, int WN, bool APLANES = false, int RING = 0>
+// GRES: the residual is gathered from a map by RoI taps in the epilogue (ConvArgs.res_map; x6_epilogue_vec<.., GRES>) -- instantiations
+// of their own, so that the launches without it keep their code (a run-time test in an epilogue has cost 14 % before, conv_bf16.hip).
+template <int TM, int TN, int WM, int WN, bool APLANES = false, int RING = 0, bool GRES = false>
 __global__ void __launch_bounds__(64 * WM * WN) k_conv_igemm_h3_db(const ConvArgs p) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, NT = 64 * WM * WN;
     constexpr int RPP = APLANES ? NT / 4 : NT / 8, PA = APLANES ? (2 * BM) / RPP : BM / RPP;      // A: rows staged per pass (planes: 4 pieces of 16 B per row per plane)
@@ -587,6 +589,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_conv_igemm_h3_db(const ConvArg
     constexpr int BUFB = 2 * (BM + BN) * X6_ROWB;
     static_assert(BM % RPP == 0 && PA >= 1, "tile rows must be a multiple of the staging pass");
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    static_assert(!(RING && GRES), "the ring has no gathered residual");
     if constexpr (RING) {                                 // (an instantiation of its own: as a run-time branch beside the other loop the ring keeps a
         static_assert(APLANES, "the ring reads planes");  //  quarter of its gain -- 729 -> 717-723 instead of 748 -> 703-713 us -- to the shared register file)
         h3_ring_tile<TM, TN, WM, WN>(p, lds);
@@ -753,6 +756,11 @@ __global__ void __launch_bounds__(64 * WM * WN) k_conv_igemm_h3_db(const ConvArg
     if constexpr (H3_S16) { h3_gather<TM, TN>(s0, acc0); h3_gather<TM, TN>(s1, acc1); }
     h3_combine<TM, TN>(acc0, acc1);
     h3_unscale<TM, TN>(acc0, h3_pow2(-eA), h3_pow2(-eB));
+    if constexpr (GRES) {                                 // (the host admits 16-byte addressable rows only)
+        if (p.y_planes) x6_epilogue_vec<TM, TN, WM, WN, true, H3_S16, true>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds), h3_pow2(eY));
+        else x6_epilogue_vec<TM, TN, WM, WN, false, H3_S16, true>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds));
+        return;
+    }
     if (p.y_planes) x6_epilogue_vec<TM, TN, WM, WN, true, H3_S16>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds), h3_pow2(eY));
     else if (p.vec_epi) x6_epilogue_vec<TM, TN, WM, WN, false, H3_S16>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds));
     else epilogue<TM, TN, H3_S16>(acc0, p, m0, n0, wm, wn, li, lh);
@@ -771,6 +779,22 @@ static int launch_h3_db(const ConvArgs& a, hipStream_t s, bool ring_ok = true) {
     constexpr size_t lds = (size_t)2 * 2 * (BM + BN) * X6_ROWB;
     static_assert(lds >= X6Tile<TM, TN, WM, WN, 2>::epi, "the epilogue's wave-row must fit in the operand buffers");
     static std::atomic<uint64_t> lds_seen{0}, lds_seen_planes{0};
+    if (p.res_map) {                                      // the residual gathered by RoI taps: sixteen waves of 64x32, never the ring
+        if constexpr (WM * WN == 16 && TN == 1) {
+            if (!p.vec_epi || p.residual || p.res_planes || p.mask || p.n_split) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_roi_res: a dense single-layer launch with 16-byte addressable rows");
+            static std::atomic<uint64_t> lds_seen_gres{0}, lds_seen_gres_planes{0};
+            if (p.x_planes) {
+                if (int e = raise_lds_once(lds_seen_gres_planes, (const void*)k_conv_igemm_h3_db<TM, TN, WM, WN, true, 0, true>, lds, "conv2d_h3")) return e;
+                k_conv_igemm_h3_db<TM, TN, WM, WN, true, 0, true><<<p.tiles_m * p.tiles_n, 64 * WM * WN, lds, s>>>(p);
+                return check_launch("conv2d_fwd_h3_roi_res (planes in)");
+            }
+            if (int e = raise_lds_once(lds_seen_gres, (const void*)k_conv_igemm_h3_db<TM, TN, WM, WN, false, 0, true>, lds, "conv2d_h3")) return e;
+            k_conv_igemm_h3_db<TM, TN, WM, WN, false, 0, true><<<p.tiles_m * p.tiles_n, 64 * WM * WN, lds, s>>>(p);
+            return check_launch("conv2d_fwd_h3_roi_res");
+        } else {
+            return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_roi_res: the 256x128 tile on sixteen waves only");
+        }
+    }
     if (p.x_planes) {
         if constexpr (WM * WN == 16) {
             // long reductions only (the head's 3x3: 144 chunks); FRCNN_H3_RING=0 / FRCNN_H3_RING_MIN_CHUNKS are dev knobs
@@ -820,6 +844,9 @@ int launch_conv_h3(const ConvArgs& a, int cfg, hipStream_t s) {
 }
 
 int h3_tile_width(int cfg) { return (cfg == 84 || cfg == 87) ? 64 : 128; }
+
+// would launch_conv_h3(cfg) walk a plane-input launch of this packed depth on the three-stage ring?
+bool h3_takes_ring(int cfg, int kpad) { return cfg == 86 && g_h3_ring && kpad / BK >= g_h3_ring_min_chunks; }
 
 // ---- packing: max|w| of the packed filter into the header word, then the two planes under that scale
 __global__ void __launch_bounds__(256) k_h3_wmax(const float* w, size_t n, unsigned* header) {

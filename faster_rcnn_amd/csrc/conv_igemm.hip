@@ -27,6 +27,7 @@
 // + residual[m][n], activation (none / relu / sigmoid), store NHWC.
 #include "conv_f32_common.h"
 #include "conv_policy.h"
+#include "../../include/ext/frcnn_hip_roi_res.h"
 
 namespace frcnn {
 
@@ -975,6 +976,11 @@ static int launch_conv_sk(const ConvArgs& a, int G, hipStream_t s) {
 using namespace frcnn;
 
 struct DualOut { int n1; int act1; float* y2; int act2; };      // frcnn_conv2d_fwd_dual: the launch's second layer
+static int roi_res_available(const frcnn_conv_desc* d, int engine, bool x_is_planes);
+static int conv_h3_planes_impl(const frcnn_conv_desc* d, const float* x, const frcnn_h3_planes* x_planes, const float* x_amax, const void* w_planes_f16,
+                               const float* scale, const float* shift, const float* residual, const frcnn_h3_planes* residual_planes,
+                               const frcnn_roi_res* gathered, const float* residual_amax, float* y, float* y_amax, const frcnn_h3_planes* y_planes,
+                               float bound_c, float bound_d, void* stream);
 
 // the magnitude records of a launch (ConvArgs.x_amax / y_amax / y2_amax), every other field zero
 static ConvArgs amax_args(const float* x_amax, float* y_amax, float* y2_amax = nullptr) {
@@ -1029,6 +1035,13 @@ static int conv_fwd_impl(const frcnn_conv_desc* d, const float* x, const float* 
         if ((size_t)r.planes * d->cout * a.Kpad * 2 >= 0x7fffffffull) return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_%s: filter planes over 2 GiB", r.name);
         if (h3 && (reinterpret_cast<uintptr_t>(w_packed) & 15)) return fail(FRCNN_E_ARG, "conv2d_fwd_h3: 16-byte aligned filter planes required");
         const int cfg = split_config(r, d, dual ? dual->n1 : 0), bn = r.tile_width(cfg);
+        if (a.res_map) {
+            // the residual gathered by RoI taps (include/ext/frcnn_hip_roi_res.h): what frcnn_conv2d_roi_res_available admits, nothing else
+            if (roi_res_available(d, engine, a.x_planes != nullptr) != 1 || dual || mask || residual || a.res_planes || workspace)
+                return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_roi_res: not available for this launch (frcnn_conv2d_roi_res_available)");
+            if (y && !a.vec_epi) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_roi_res: 16-byte addressable output rows required");
+            if ((long long)a.res_map_rows * d->cout * 4 >= 0x7fffffffLL || M * 32 >= 0x7fffffffLL) return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_roi_res: map or tap table over 2 GiB");
+        }
         if (planes_io) {
             // activations as fp16 planes (f16x3 only): the double-buffered 256x128 forms only, 16-byte epilogue, one layer, no mask
             if ((cfg != 86 && cfg != 85 && cfg != 82) || dual || mask || (!a.vec_epi && y) || d->ldy > 0)
@@ -1097,6 +1110,20 @@ static int conv_fwd_impl(const frcnn_conv_desc* d, const float* x, const float* 
         case 4: return launch_conv<4, 2, false>(a, s);
         default: return fail(FRCNN_E_ARG, "conv2d_fwd: unknown tile config %d", cfg);
     }
+}
+
+// frcnn_conv2d_roi_res_available (the launch asks the same question): 1 / 0
+static int roi_res_available(const frcnn_conv_desc* d, int engine, bool x_is_planes) {
+    if (engine != FRCNN_ENGINE_H3) return 0;
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->ho <= 0 || d->wo <= 0) return 0;
+    if ((d->cin % BK) != 0 || d->kh * d->kw > 32 || (d->cout & 3) || d->ldy > 0 || d->ldres > 0) return 0;
+    const SplitRule& r = split_rule(engine);
+    const int cfg = split_config(r, d, 0);
+    if (cfg != 86 && cfg != 85) return 0;                   // 256x128 on sixteen waves; an explicit split-K code (184 / 181) maps to 84 / 81 here
+    if (x_is_planes && h3_takes_ring(cfg, frcnn_conv_packed_k(d->kh, d->kw, d->cin))) return 0;
+    const long long M = (long long)d->n * d->ho * d->wo;
+    if (M * d->cout * 4 >= 0x7fffffffLL || (long long)d->n * d->h * d->w * d->cin * 4 >= 0x7fffffffLL) return 0;
+    return 1;
 }
 
 extern "C" {
@@ -1186,10 +1213,39 @@ int frcnn_conv2d_fwd_h3_planes(const frcnn_conv_desc* d, const float* x, const f
     return frcnn_conv2d_fwd_h3_planes_res(d, x, x_planes, x_amax, w_planes_f16, scale, shift, residual, nullptr, residual_amax, y, y_amax, y_planes, bound_c, bound_d, stream);
 }
 
+int frcnn_conv2d_roi_res_available(const frcnn_conv_desc* d, int engine, int x_is_planes) {
+    if (!d) return fail(FRCNN_E_ARG, "conv2d_roi_res_available: null descriptor");
+    if (engine != FRCNN_ENGINE_NATIVE && engine != FRCNN_ENGINE_X6 && engine != FRCNN_ENGINE_H3) return fail(FRCNN_E_ARG, "conv2d_roi_res_available: unknown engine %d", engine);
+    return roi_res_available(d, engine, x_is_planes != 0);
+}
+
+int frcnn_conv2d_fwd_h3_roi_res(const frcnn_conv_desc* d, const float* x, const frcnn_h3_planes* x_planes, const float* x_amax,
+                                const void* w_planes_f16, const float* scale, const float* shift, const frcnn_roi_res* res,
+                                const float* residual_amax, float* y, float* y_amax, const frcnn_h3_planes* y_planes,
+                                float bound_c, float bound_d, void* stream) {
+    return conv_h3_planes_impl(d, x, x_planes, x_amax, w_planes_f16, scale, shift, nullptr, nullptr, res, residual_amax, y, y_amax, y_planes, bound_c, bound_d, stream);
+}
+
 int frcnn_conv2d_fwd_h3_planes_res(const frcnn_conv_desc* d, const float* x, const frcnn_h3_planes* x_planes, const float* x_amax, const void* w_planes_f16,
                                    const float* scale, const float* shift, const float* residual, const frcnn_h3_planes* residual_planes,
                                    const float* residual_amax, float* y, float* y_amax, const frcnn_h3_planes* y_planes, float bound_c, float bound_d,
                                    void* stream) {
+    return conv_h3_planes_impl(d, x, x_planes, x_amax, w_planes_f16, scale, shift, residual, residual_planes, nullptr, residual_amax, y, y_amax, y_planes, bound_c, bound_d, stream);
+}
+
+}  // extern "C"
+
+// frcnn_conv2d_fwd_h3_planes_res / frcnn_conv2d_fwd_h3_roi_res: the residual as an f32 tensor, as planes or (`gathered`) resampled from a map
+static int conv_h3_planes_impl(const frcnn_conv_desc* d, const float* x, const frcnn_h3_planes* x_planes, const float* x_amax, const void* w_planes_f16,
+                               const float* scale, const float* shift, const float* residual, const frcnn_h3_planes* residual_planes,
+                               const frcnn_roi_res* gathered, const float* residual_amax, float* y, float* y_amax, const frcnn_h3_planes* y_planes,
+                               float bound_c, float bound_d, void* stream) {
+    if (gathered) {
+        auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+        if (!gathered->map || !gathered->taps || gathered->map_rows <= 0 || gathered->reserved != 0)
+            return fail(FRCNN_E_ARG, "conv2d_fwd_h3_roi_res: map, tap table and map_rows > 0 required (reserved = 0)");
+        if (!a16(gathered->map) || !a16(gathered->taps) || !a16(gathered->fill)) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_roi_res: 16-byte aligned map, tap table and fill required");
+    }
     if (!x_amax) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_planes: the input's magnitude record is required");
     if (residual && residual_planes) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_planes: the residual as an f32 tensor OR as planes");
     if (residual_planes && (!residual_planes->planes || !residual_planes->exponent || (reinterpret_cast<uintptr_t>(residual_planes->planes) & 15)))
@@ -1197,15 +1253,14 @@ int frcnn_conv2d_fwd_h3_planes_res(const frcnn_conv_desc* d, const float* x, con
     if ((x != nullptr) == (x_planes != nullptr)) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_planes: exactly one of x / x_planes");
     if (!y && !y_planes) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_planes: no output");
     if (x_planes && (!x_planes->planes || !x_planes->exponent)) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_planes: incomplete input planes");
-    if (y_planes && (!y_planes->planes || !y_planes->exponent || !(bound_c >= 0.0f) || !(bound_d >= 0.0f) || ((residual || residual_planes) && !residual_amax)))
+    if (y_planes && (!y_planes->planes || !y_planes->exponent || !(bound_c >= 0.0f) || !(bound_d >= 0.0f) || ((residual || residual_planes || gathered) && !residual_amax)))
         return fail(FRCNN_E_ARG, "conv2d_fwd_h3_planes: output planes need their buffers, the filter's bound constants and, with a residual, its magnitude record");
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     if ((x_planes && !al16(x_planes->planes)) || (y_planes && !al16(y_planes->planes))) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_planes: 16-byte aligned planes required");
     ConvArgs rg = amax_args(x_amax, y_amax);
     if (x_planes) { rg.x_planes = x_planes->planes; rg.x_pexp = x_planes->exponent; }
-    if (y_planes) { rg.y_planes = y_planes->planes; rg.y_pexp = y_planes->exponent; rg.res_amax = (residual || residual_planes) ? residual_amax : nullptr; rg.bound_c = bound_c; rg.bound_d = bound_d; }
+    if (y_planes) { rg.y_planes = y_planes->planes; rg.y_pexp = y_planes->exponent; rg.res_amax = (residual || residual_planes || gathered) ? residual_amax : nullptr; rg.bound_c = bound_c; rg.bound_d = bound_d; }
     if (residual_planes) { rg.res_planes = residual_planes->planes; rg.res_pexp = residual_planes->exponent; }
+    if (gathered) { rg.res_map = gathered->map; rg.res_taps = gathered->taps; rg.res_fill = gathered->fill; rg.res_map_rows = gathered->map_rows; }
     return conv_fwd_impl(d, x, reinterpret_cast<const float*>(w_planes_f16), scale, shift, residual, nullptr, y, nullptr, nullptr, 0, stream, FRCNN_ENGINE_H3, rg);
 }
-
-}  // extern "C"

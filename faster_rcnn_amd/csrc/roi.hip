@@ -12,6 +12,7 @@
 //   top = tl + (tr - tl)*tx; bot = bl + (br - bl)*tx; out = top + (bot - top)*ty
 // Compiled with -ffp-contract=off so the three lerps round where TF's scalar code rounds.
 #include "common.h"
+#include "../../include/ext/frcnn_hip_roi_res.h"
 
 namespace frcnn {
 
@@ -125,6 +126,30 @@ __global__ void __launch_bounds__(256) k_roi_fwd_planes(const float4* feat, int 
         const unsigned bits = seen > 0x7bffu ? 7u : seen == 0x7bffu ? 3u : seen >= 0x7800u ? 1u : 0u;
         if ((threadIdx.x & 63) == 0 && bits) atomicOr(status, bits);
     }
+}
+
+// The taps of every sample as a table (include/ext/frcnn_hip_roi_res.h): one thread per output row m of the CONSUMING convolution, in
+// its row order, writes the 32-byte record its epilogue gathers the residual with (conv_f32_common.h, roi_res_piece): the element
+// offsets of the four source rows, the two fractions and the predicate -- all from roi_taps(), the one home of that arithmetic.
+struct RoiTapRec { int4 off; float tx, ty; int ok, zero; };
+static_assert(sizeof(RoiTapRec) == FRCNN_ROI_TAP_BYTES, "tap record");
+
+__global__ void __launch_bounds__(256) k_roi_tap_table(const float4* rois, int rows, int cols, int C, int pool, int n, int n_per_img,
+                                                       int pos_major, RoiTapRec* out) {
+    const int m = blockIdx.x * 256 + threadIdx.x, pp = pool * pool;
+    if (m >= n * pp) return;
+    const int r = pos_major ? m % n : m / pp, pos = pos_major ? m / n : m % pp;
+    const int py = pos / pool, px = pos % pool;
+    const Taps t = roi_taps(rois[r], py, px, pool, rows, cols);
+    RoiTapRec rec;
+    rec.off = make_int4(0, 0, 0, 0);
+    rec.tx = t.ok ? t.tx : 0.0f; rec.ty = t.ok ? t.ty : 0.0f; rec.ok = t.ok ? 1 : 0; rec.zero = 0;
+    if (t.ok) {                                           // (a rejected RoI's indices mean nothing)
+        const int base = n_per_img > 0 ? (r / n_per_img) * rows * cols : 0;
+        rec.off = make_int4((base + t.y_lo * cols + t.x_lo) * C, (base + t.y_lo * cols + t.x_hi) * C,
+                            (base + t.y_hi * cols + t.x_lo) * C, (base + t.y_hi * cols + t.x_hi) * C);
+    }
+    out[m] = rec;
 }
 
 // Gradient w.r.t. the feature map as a GATHER: one workgroup per feature cell lists the RoIs whose box contains the
@@ -294,6 +319,25 @@ int frcnn_roi_crop_resize_bwd_bf16(const void* dout_bf16, int rows, int cols, in
     if (!dout_bf16 || !rois || !dfeat) return fail(FRCNN_E_ARG, "roi_crop_resize_bwd_bf16: null pointer");
     k_roi_bwd_gather<__bf16><<<rows * cols, 256, 0, as_stream(stream)>>>((const __bf16*)dout_bf16, rows, cols, C, (const float4*)rois, n, pool, dfeat);
     return check_launch("roi_crop_resize_bwd_bf16");
+}
+
+int frcnn_roi_res_version(void) { return FRCNN_ROI_RES_VERSION; }
+
+int frcnn_roi_tap_table(int rows, int cols, int c, const float* rois, int n, int n_per_img, int n_maps, int pool, int layout,
+                        void* taps, void* stream) {
+    if (n < 0 || n_per_img < 0 || rows <= 0 || cols <= 0 || c <= 0 || (c & 3) || pool <= 0 || (layout != 0 && layout != 1))
+        return fail(FRCNN_E_ARG, "roi_tap_table: bad shape (c must be a multiple of 4, layout 0 or 1)");
+    if (n_per_img > 0 && (n_maps <= 0 || (long long)n > (long long)n_maps * n_per_img)) return fail(FRCNN_E_ARG, "roi_tap_table: more RoIs than n_maps * n_per_img");
+    const long long maps = n_per_img > 0 ? n_maps : 1;
+    if (maps * rows * cols * c * 4 >= 0x7fffffffLL) return fail(FRCNN_E_UNSUPPORTED, "roi_tap_table: maps over 2 GiB");
+    if ((long long)n * pool * pool >= 0x7fffffffLL / FRCNN_ROI_TAP_BYTES) return fail(FRCNN_E_UNSUPPORTED, "roi_tap_table: table over 2 GiB");
+    if (n == 0) return FRCNN_OK;
+    if (!rois || !taps) return fail(FRCNN_E_ARG, "roi_tap_table: null pointer");
+    if (reinterpret_cast<uintptr_t>(taps) & 15) return fail(FRCNN_E_ARG, "roi_tap_table: 16-byte aligned table required");
+    const int total = n * pool * pool;
+    k_roi_tap_table<<<(total + 255) / 256, 256, 0, as_stream(stream)>>>((const float4*)rois, rows, cols, c, pool, n, n_per_img, layout,
+                                                                         (RoiTapRec*)taps);
+    return check_launch("roi_tap_table");
 }
 
 }  // extern "C"

@@ -140,6 +140,10 @@ HEAD_PLANES = True      # dev knob (tests): False keeps every tensor of the dete
 # loader and walk the ring -- 436-443 -> 393-407 us per four-image launch -- but the 512 -> 2048 layers that now write and read 8-byte plane
 # pieces instead of 16-byte f32 pieces take 548-557 instead of 534-539 us: 533.5 against 536.5 img/s (scripts/dev/r6_block_planes_ab.sh)
 HEAD_BLOCK_PLANES = _os.environ.get("FRCNN_HEAD_BLOCK_PLANES", "0") != "0"
+# res5a's RoI-resampled shortcut is not written and read back (482 MB each way per four-image pass) but gathered from branch1's map in
+# branch2c's epilogue (ops.RoiResidual; csrc/conv_f32_common.h x6_epilogue_vec<.., GRES>), where that launch can: bit-identical results.
+# FRCNN_HEAD_ROI_RES=0/1 (dev knob); DESIGN section 7 has the A/B that set the default.
+HEAD_ROI_RES = _os.environ.get("FRCNN_HEAD_ROI_RES", "1") != "0"
 VGG_PLANES = _os.environ.get("FRCNN_VGG_PLANES", "1") != "0"        # VggBase: plane tensors between the convolutions of a block (round 6)
 # the same hand-over inside the TRUNK's bottleneck blocks, wherever the consuming launch is one that reads planes (the 256x128 tile
 # forms) -- VERDICT r5 item 3.  Mid-round, with 64x64 tiles under 256 tiles of 128x128: nothing (540.1 / 538.7 against 540.5 / 538.6
@@ -509,7 +513,8 @@ class ResNetHead:
             yield from b.values()
         yield self.dense.unit
 
-    def _first_block_hoisted(self, feat, rois, resize, layout=None):
+    def _first_block_hoisted(self, feat, rois, resize, layout=None, n_per_img=0):
+        """``n_per_img`` > 0: ``feat`` is a batch of maps and ``resize`` crops RoI r from image r // n_per_img's (forward_batched)."""
         a = self.blocks[0]
         if feat.dim() == 4 and feat.shape[0] > 1:               # a batch of maps (forward_batched): `resize` knows which RoI crops which
             fmap = feat
@@ -530,11 +535,19 @@ class ResNetHead:
             t = resize(u, rois, self.pool, fill=a["2a"].pc.shift, relu=True, layout=L, planes_out=True)
         else:
             t = resize(u, rois, self.pool, fill=a["2a"].pc.shift, relu=True, layout=L)
-        s = resize(v, rois, self.pool, fill=a["1"].pc.shift, layout=L)
         out_shape = crop_shape[:-1] + (_cout(a["2c"]),)
         nxt = self.blocks[1] if len(self.blocks) > 1 else None
-        return a["2c"](a["2b"](t, layout=L, planes_out=planes and _reads_planes(a["2c"], crop_shape[:-1] + (_cout(a["2b"]),), L)), residual=s, layout=L,
-                       planes_out=planes and nxt is not None and block_takes_planes(nxt, out_shape, L))
+        t = a["2b"](t, layout=L, planes_out=planes and _reads_planes(a["2c"], crop_shape[:-1] + (_cout(a["2b"]),), L))
+        c = a["2c"]
+        if c.pc is None:
+            c.lower()
+        if HEAD_ROI_RES and self.dtype == "f32":
+            # where branch2c's launch can, the shortcut is resampled inside its epilogue and only the taps are made here
+            s = ops.roi_shortcut(v, rois, self.pool, t, c.pc, fill=a["1"].pc.shift, layout=L, n_per_img=n_per_img,
+                                 stride=c.stride, padding=c.padding, act=c.act, tile=c.tile)
+        else:
+            s = resize(v, rois, self.pool, fill=a["1"].pc.shift, layout=L)
+        return c(t, residual=s, layout=L, planes_out=planes and nxt is not None and block_takes_planes(nxt, out_shape, L))
 
     def _run_rest(self, x, rest, L):
         """The identity blocks behind the first: each hands its output to the next as planes where that block can take them."""
@@ -574,7 +587,7 @@ class ResNetHead:
             # (14 % more chunks), each launch alone is 0.5 % slower -- and four passes in flight 0.9 % faster (549-551 against 545-546
             # img/s, three alternating runs).  One-image passes tie (507 / 507) and the latency form loses 2 %: they keep position-major.
             L = BATCHED_F32_HEAD_LAYOUT if self.layout else 0
-            x = self._first_block_hoisted(feat, rois, functools.partial(ops.roi_crop_resize, n_per_img=n_per_img), layout=L)
+            x = self._first_block_hoisted(feat, rois, functools.partial(ops.roi_crop_resize, n_per_img=n_per_img), layout=L, n_per_img=n_per_img)
             x = self._run_rest(x, self.blocks[1:], L)
             if L:
                 return self.dense(ops.avgpool_pos_major(x))

@@ -355,6 +355,73 @@ def roi_crop_resize(feat, rois, pool, fill=None, relu=False, layout=0, planes_ou
     return out
 
 
+class RoiResidual:
+    """The RoI-resampled shortcut as the convolution behind it gathers it (include/ext/frcnn_hip_roi_res.h): the MAP ``fmap`` (B,R,C,Cf)
+    or (R,C,Cf) f32, the tap table of the RoIs in the consuming launch's row order and the fill vector -- what
+    ``roi_crop_resize(fmap, rois, pool, fill=fill, layout=layout, n_per_img=n_per_img)`` would have written, never materialised.
+    ``conv2d(..., residual=RoiResidual(...))`` reads it where ``conv_takes_roi_res`` says so; ``shape`` is that tensor's."""
+
+    def __init__(self, fmap, rois, pool, fill=None, layout=0, n_per_img=0):
+        _require_gpu()
+        assert fmap.dtype == torch.float32 and fmap.is_contiguous() and fmap.dim() in (3, 4)
+        rows, cols, C = (int(v) for v in fmap.shape[-3:])
+        n_maps = int(fmap.shape[0]) if fmap.dim() == 4 else 1
+        assert n_per_img > 0 or n_maps == 1, "a batch of maps needs n_per_img"
+        rois = rois.reshape(-1, 4).to(torch.float32).contiguous()
+        n = int(rois.shape[0])
+        self.map, self.fill, self.map_rows = fmap, fill, n_maps * rows * cols
+        self.shape = (pool, pool, n, C) if layout else (n, pool, pool, C)
+        self.taps = torch.empty((max(n * pool * pool, 1), _lib.ROI_TAP_BYTES // 4), dtype=torch.int32, device="cuda")
+        _lib.call("frcnn_roi_tap_table", rows, cols, C, _p(rois), n, int(n_per_img), n_maps, int(pool), int(layout), _p(self.taps), _stream())
+        self._amax = None
+        if _tracking() and getattr(fmap, "_amax", None) is not None:
+            amax_carry(self, fmap, self._floor())
+
+    def _floor(self):
+        """max|fill|: with the map's bound, the bound of the resampled tensor (roi_crop_resize: a convex combination of map values, or the fill vector)."""
+        if self.fill is None:
+            return 0.0
+        floor = getattr(self.fill, "_absmax", None)
+        return float(self.fill.abs().max().item()) if floor is None else floor
+
+    def amax(self):
+        """The magnitude record of the tensor this stands for: the map's record merged with max|fill|; a map without a valid record (none, or
+        one of an earlier pass of its arena) is measured, as ``amax_of`` does for a resampled tensor nobody left a record on."""
+        if self._amax is None:
+            merged = _amax_new()
+            _lib.call("frcnn_amax_merge", _p(merged), _p(amax_of(self.map)), float(self._floor()), None, _stream())
+            self._amax = merged
+        return self._amax
+
+    def desc(self):
+        return _lib.RoiRes(map=self.map.data_ptr(), taps=self.taps.data_ptr(), fill=self.fill.data_ptr() if self.fill is not None else None,
+                           map_rows=self.map_rows, reserved=0)
+
+
+def conv_takes_roi_res(x, pc, stride=1, padding="valid", act=None, layout=0, tile=0):
+    """Would ``conv2d(x, pc, ..., residual=RoiResidual(...))`` gather its residual (frcnn_conv2d_roi_res_available: the f16x3 engine's
+    256x128 form on sixteen waves, un-split, not the ring)?  ``x``: the tensor (f32 or PlaneTensor) the launch will read."""
+    if not isinstance(pc, PackedConv):
+        return False
+    d = _conv_desc(tuple(x.shape), pc.kh, pc.kw, pc.cout, stride, padding, ACT[act], layout, tile or AUTO_TILE)
+    eng = _split_engine(d, pc, tile or AUTO_TILE)
+    code = {None: 0, "x6": 1, "h3": 2}[eng]
+    got = _lib.load().frcnn_conv2d_roi_res_available(ctypes.byref(d), code, 1 if isinstance(x, PlaneTensor) else 0)
+    if got < 0:
+        _lib.check(got, "frcnn_conv2d_roi_res_available")
+    return got == 1 and _planes_ok(d, pc, eng)
+
+
+def roi_shortcut(fmap, rois, pool, x, pc, fill=None, layout=0, n_per_img=0, stride=1, padding="valid", act=None, tile=0):
+    """The residual of ``conv2d(x, pc, stride, padding, act, residual=., tile=tile, layout=layout)`` when it is the RoI resampling of
+    ``fmap``: a RoiResidual where that launch gathers its residual (``conv_takes_roi_res``), otherwise the resampled f32 tensor
+    (``roi_crop_resize``) -- every other engine, tile and form.  Either way the convolution's result is the same, bit for bit."""
+    n = rois.reshape(-1, 4).shape[0]
+    if n > 0 and fmap.dtype == torch.float32 and fmap.is_contiguous() and conv_takes_roi_res(x, pc, stride, padding, act, layout, tile):
+        return RoiResidual(fmap, rois, pool, fill=fill, layout=layout, n_per_img=n_per_img)
+    return roi_crop_resize(fmap, rois, pool, fill=fill, layout=layout, n_per_img=n_per_img)
+
+
 def avgpool_pos_major(x):
     """(h,w,n,c) f32 position-major -> (n,c): AveragePooling2D over the whole h x w window."""
     _require_gpu()
@@ -836,17 +903,23 @@ def _conv2d_h3_planes(d, x, pc, residual, oshape, planes_out, act):
     yp = _lib.H3Planes(planes=y.planes.data_ptr(), exponent=y.exponent.data_ptr(), status=ya.data_ptr() + 4) if planes_out else None
     bc, bd = pc.h3_bound() if planes_out else (0.0, 0.0)
     xa = amax_of(x)                                              # (a measured record is a temporary: it must outlive the launch and its re-launches)
-    ra = amax_of(residual) if (residual is not None and planes_out) else None
     r_in = isinstance(residual, PlaneTensor)                     # a block's output handed on as planes: the shortcut reads them back
+    r_roi = isinstance(residual, RoiResidual)                    # the RoI-resampled shortcut, gathered from its map in the epilogue
+    ra = (residual.amax() if r_roi else amax_of(residual)) if (residual is not None and planes_out) else None
     rp = _lib.H3Planes(planes=residual.planes.data_ptr(), exponent=residual.exponent.data_ptr(), status=None) if r_in else None
-    args = (ctypes.byref(d), None if x_in else _p(x), ctypes.byref(xp) if x_in else None, _p(xa), _p(pc.h3_planes()), _p(pc.scale), _p(pc.shift),
-            None if r_in else _p(residual), ctypes.byref(rp) if r_in else None, _p(ra), None if planes_out else _p(y), _p(ya),
-            ctypes.byref(yp) if planes_out else None, bc, bd)
-    _lib.call("frcnn_conv2d_fwd_h3_planes_res", *args, _stream())
+    head = (ctypes.byref(d), None if x_in else _p(x), ctypes.byref(xp) if x_in else None, _p(xa), _p(pc.h3_planes()), _p(pc.scale), _p(pc.shift))
+    tail = (_p(ra), None if planes_out else _p(y), _p(ya), ctypes.byref(yp) if planes_out else None, bc, bd)
+    if r_roi:
+        rp = residual.desc()
+        fn, args = "frcnn_conv2d_fwd_h3_roi_res", head + (ctypes.byref(rp),) + tail
+    else:
+        fn, args = "frcnn_conv2d_fwd_h3_planes_res", head + (None if r_in else _p(residual), ctypes.byref(rp) if r_in else None) + tail
+    _lib.call(fn, *args, _stream())
     y._amax = ya
-    # (the instantiation that reads planes is a kernel of its own; writing planes is a run-time branch of either's epilogue)
-    _record_launch(lambda: _h3_planes_in_name(d, pc) if x_in else _h3_name(d), _gemm_shape(d, pc, d.stride), "frcnn_conv2d_fwd_h3_planes_res",
-                   args, (d, x, pc, residual, y, ya, xp, yp, xa, ra, rp), planes_out=bool(planes_out))
+    # (the instantiation that reads planes is a kernel of its own; writing planes is a run-time branch of either's epilogue; the gathered
+    # residual is an instantiation too, listed under the name of the launch it replaces so that per-kernel figures cover the same launches)
+    _record_launch(lambda: _h3_planes_in_name(d, pc) if x_in else _h3_name(d), _gemm_shape(d, pc, d.stride), fn,
+                   args, (d, x, pc, residual, y, ya, xp, yp, xa, ra, rp), planes_out=bool(planes_out), roi_res=bool(r_roi))
     return y
 
 
@@ -876,13 +949,16 @@ def conv2d(x, pc, stride=1, padding="valid", act=None, residual=None, out=None, 
     n, ho, wo = d.n, d.ho, d.wo
     oshape = (ho, wo, n, pc.cout) if layout else (n, ho, wo, pc.cout)
     res_planes = isinstance(residual, PlaneTensor)
-    if x_planes or planes_out or res_planes:
+    roi_res = isinstance(residual, RoiResidual)
+    if x_planes or planes_out or res_planes or roi_res:
         ok = out is None and _planes_ok(d, pc, _split_engine(d, pc, tile or AUTO_TILE))
+        if roi_res and not (ok and conv_takes_roi_res(x, pc, stride, padding, act, layout, tile)):
+            raise _lib.FrcnnError("conv2d: this launch cannot gather a RoiResidual (ops.conv_takes_roi_res; frcnn_conv2d_roi_res_available)")
         if (x_planes or res_planes) and not ok:
             raise _lib.FrcnnError("conv2d: a PlaneTensor input / residual needs an f16x3 launch on the 256x128 tile (frcnn_conv2d_fwd_h3_planes)")
         if ok:
             if residual is not None:
-                assert tuple(residual.shape) == tuple(oshape) and (res_planes or residual.is_contiguous())
+                assert tuple(residual.shape) == tuple(oshape) and (res_planes or roi_res or residual.is_contiguous())
             return _conv2d_h3_planes(d, x, pc, residual, oshape, planes_out, act)
     if out is None:
         out = torch.empty(oshape, dtype=torch.float32, device="cuda")
