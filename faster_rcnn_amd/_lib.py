@@ -367,6 +367,18 @@ class Y4mBatchItem(ctypes.Structure):
     _fields_ = [("plan", Y4mPlan), ("file_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("ws_off", ctypes.c_uint64)]
 
 
+REDACT_VERSION = 1              # include/ext/frcnn_hip_redact.h FRCNN_REDACT_VERSION
+REDACT_MAX_ROWS = 512           # ... FRCNN_REDACT_MAX_ROWS
+REDACT_SIGNATURES = {
+    "frcnn_redact_version": (I, []),
+    "frcnn_redact_ws_bytes": (c_size_t, [I, I, I, I]),
+    "frcnn_redact_u8": (I, [P, I, I, P, P, P, I, P, I, I, I, I, P, c_size_t, P]),
+}
+REDACT_MODES = {"fill": 0, "pixelate": 1, "blur": 2}                               # FRCNN_REDACT_FILL / _PIXELATE / _BLUR
+# mode -> (smallest size, largest size, the default): FRCNN_REDACT_PIXELATE_MIN / _MAX, FRCNN_REDACT_BLUR_MIN / _MAX; fill takes none (0)
+REDACT_SIZES = {"fill": (0, 0, 0), "pixelate": (2, 64, 16), "blur": (1, 32, 12)}
+
+
 class ConvDesc(ctypes.Structure):
     """frcnn_conv_desc (include/frcnn_hip.h)."""
     _fields_ = [(k, ctypes.c_int32) for k in (
@@ -472,6 +484,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in REDACT_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_redact_version() != REDACT_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
+                         f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_y4m_version() != Y4M_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_y4m_version()} of the YUV4MPEG2 extension, this binding "
                          f"{Y4M_VERSION} (include/ext/frcnn_hip_y4m.h): rebuild with `python -m faster_rcnn_amd.build`")

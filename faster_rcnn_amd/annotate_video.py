@@ -42,6 +42,14 @@ A video STREAM goes through ``annotate_stream``: the command line's ``input_dir`
 for a frame directory, whose frames must then share one size) instead of frame files -- with ``-`` every printed line goes to stderr.  The
 frames' chroma upsampling and colour matrix, and the inverse on the way out, run inside the passes (csrc/y4m.hip, DESIGN §8); a frame's
 "path" in the printed lines is ``<name>#<frame index>``.
+
+``redact=(classes, mode, size, margin)`` (``--redact CLASSES [--redact_mode pixelate|blur|fill] [--redact_size N] [--redact_margin N]``)
+HIDES the detected objects of those classes -- names of the active class mapping, or "all" -- instead of, or as well as, outlining them:
+every pixel inside a box (grown by ``margin``, clipped to the frame) becomes the mean of its cell of an N x N grid ("pixelate", N = 2..64,
+default 16), a box blur of radius N ("blur", 1..32, default 12) or black ("fill"), computed from the untouched frame (ops.redact_u8,
+csrc/redact.hip; the rule is DESIGN §8's).  Unlike the drawing, a box that crosses the frame's border IS redacted, and 'DontCare' / 'Misc'
+are when named.  It runs inside the pass in front of the drawing step, so before every encoder and for every input format.
+``draw=False`` (``--no_draw``) leaves the boxes and labels out.  The printed lines do not change with either.
 """
 import collections
 import os
@@ -203,21 +211,61 @@ def _pack_dets(dets, class_mapping):
 
 
 _EAGER_TABLES = {}
+_EAGER_REDACT_TABLES = {}
 
 
-def draw_eager(frame, dets, class_mapping):
-    """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place."""
+def _names_by_index(class_mapping):
+    rev = {v: k for k, v in class_mapping.items()}
+    return [rev.get(i, "") for i in range(max(rev) + 1)]
+
+
+def draw_eager(frame, dets, class_mapping, redact=None, draw=True):
+    """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place.
+    ``redact`` = (classes, mode, size, margin): one ops.redact_u8 in front of it; ``draw`` False: no drawing."""
     import torch
     key = tuple(sorted(class_mapping.items()))
-    tables = _EAGER_TABLES.get(key)
-    if tables is None:
-        rev = {v: k for k, v in class_mapping.items()}
-        tables = _EAGER_TABLES[key] = ops.annotate_tables([rev.get(i, "") for i in range(max(rev) + 1)])
-    if dets:                                              # (nothing to draw: the frame stays as it is)
+    if dets and (draw or redact is not None):             # (nothing to draw or hide: the frame stays as it is)
         dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
-        ops.annotate_u8(dev, torch.from_numpy(_pack_dets(dets, class_mapping)).cuda(), tables)
+        packed = torch.from_numpy(_pack_dets(dets, class_mapping)).cuda()
+        if redact is not None:
+            classes, mode, size, margin = redact
+            classes = classes if classes == "all" else tuple(classes)
+            table = _EAGER_REDACT_TABLES.get((key, classes))
+            if table is None:
+                table = _EAGER_REDACT_TABLES[(key, classes)] = ops.redact_table(_names_by_index(class_mapping), classes)
+            ops.redact_u8(dev, packed, table, mode, size, margin)
+        if draw:
+            tables = _EAGER_TABLES.get(key)
+            if tables is None:
+                tables = _EAGER_TABLES[key] = ops.annotate_tables(_names_by_index(class_mapping))
+            ops.annotate_u8(dev, packed, tables)
         frame[...] = dev.cpu().numpy()
     return frame
+
+
+REDACT_MODES = ("pixelate", "blur", "fill")
+
+
+def redact_from_args(args, class_mapping):
+    """(host only) The redaction the command line asks for -> (classes, mode, size, margin) as ``submit_batch(redact=...)`` takes it, or
+    None without ``--redact``.  classes: "all", or the tuple of names (of ``class_mapping``, the active one) in the order given; size:
+    the mode's default when not stated.  ValueError, with the reason, for an unknown class name, for ``--redact_mode`` /
+    ``--redact_size`` / ``--redact_margin`` without ``--redact``, for a size out of the mode's range and for a negative margin."""
+    if args.redact is None:
+        for flag, value in (("--redact_mode", args.redact_mode), ("--redact_size", args.redact_size), ("--redact_margin", args.redact_margin)):
+            if value is not None:
+                raise ValueError("%s=%s is a setting of the redaction: it needs --redact CLASSES" % (flag, value))
+        return None
+    names = [n.strip() for n in args.redact.split(",") if n.strip()]
+    if not names:
+        raise ValueError("--redact takes comma-separated class names, or all")
+    classes = "all" if names == ["all"] else ops.redact_class_list(_names_by_index(class_mapping), names)
+    mode = "pixelate" if args.redact_mode is None else args.redact_mode
+    size = ops.redact_size(mode, args.redact_size)
+    margin = 0 if args.redact_margin is None else int(args.redact_margin)
+    if margin < 0:
+        raise ValueError("--redact_margin=%d: an integer >= 0" % margin)
+    return classes, mode, size, margin
 
 
 def _print_drawn(dets, width, height):
@@ -226,19 +274,20 @@ def _print_drawn(dets, width, height):
             print(det)
 
 
-def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max):
-    """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it."""
+def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True):
+    """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
+    ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn."""
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1)
     if eng is not None:
         pixels = eng.host_pixels(resized_imgs[0])
         num_rois, dets, out = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], DET_THRESHOLD, [pixels],
-                                                                 batch=1, annotate=True))[0]
+                                                                 batch=1, annotate=True, redact=redact, draw=draw))[0]
         print("num rois: {}".format(num_rois))
         frame[...] = out
     else:
         dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=DET_THRESHOLD)
-        draw_eager(frame, dets, training_manager.class_mapping)
+        draw_eager(frame, dets, training_manager.class_mapping, redact, draw)
     _print_drawn(dets, img.width, img.height)
     return frame
 
@@ -415,13 +464,14 @@ def directory_frames(input_dir, image_filenames, jpeg_decoder=None, png_decoder=
 
 
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
-                    png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None):
+                    png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
+                    redact=None, draw=True):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw``: as ``annotate_images``."""
     from concurrent.futures import ThreadPoolExecutor
     to_video = isinstance(writer_or_out_dir, y4m.Y4mWriter)
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
@@ -454,6 +504,8 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
         pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
         out_name = lambda pos: os.path.join(out_dir, "frame_%06d.%s" % (pos, "jpg" if jpg else "png"))
         check_size = lambda label, frame: None
+    if redact is not None or not draw:                    # (else the passes, and their keys, are the ones without the arguments)
+        kwargs = dict(kwargs, redact=redact, draw=draw)
 
     if eng is None:                                       # eager path / foreign models: one frame at a time, converted on the device
         import torch
@@ -465,7 +517,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
             else:
                 frame = np.ascontiguousarray(src.raw)
             img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
-            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max)
+            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=redact, draw=draw)
             if to_video:
                 writer.write(ops.y4m_encode_u8(torch.from_numpy(out).cuda(), writer.chroma, writer.range, bgr=True).cpu().numpy().tobytes())
             elif on_device:
@@ -558,7 +610,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
-                    jpeg_huffman=None, png_decoder=None):
+                    jpeg_huffman=None, png_decoder=None, redact=None, draw=True):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -571,7 +623,9 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     what ``entry.jpeg_decoder()`` says (FRCNN_ENTRY_JPEG_DECODER, default "host").
     ``png_decoder``: "host", "device" or "device_full" (csrc/png_dec_full.hip: palette, 1/2/4/16-bit, grey + alpha and Adam7 files too):
     who decodes ``.png`` INPUT frames the device decoder supports (captured path only; the decode
-    threads then only read the file and check its chunks); None = what ``entry.png_decoder()`` says (FRCNN_ENTRY_PNG_DECODER, default "host")."""
+    threads then only read the file and check its chunks); None = what ``entry.png_decoder()`` says (FRCNN_ENTRY_PNG_DECODER, default "host").
+    ``redact``: (classes, mode, size, margin) as ``redact_from_args`` returns it -- those classes' boxes are hidden in every frame inside
+    its pass, in front of the drawing step and of whichever encoder writes the frame; None: nothing is.  ``draw`` False: no boxes, no labels."""
     from concurrent.futures import ThreadPoolExecutor
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
@@ -603,7 +657,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             print("processing {}".format(path))
             frame = np.ascontiguousarray(_read_rgb(path)[:, :, ::-1])
             img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
-            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max)
+            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=redact, draw=draw)
             if on_device:
                 import torch
                 dev = torch.from_numpy(out).cuda()
@@ -620,6 +674,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         return frame, resized, ratio, eng.host_pixels(resized)
 
     n, B = len(paths), eng.batch
+    edit = dict(redact=redact, draw=draw) if redact is not None or not draw else {}      # (else the passes without the arguments)
     decode = ThreadPoolExecutor(max_workers=max(1, DECODE_THREADS))
     write = ThreadPoolExecutor(max_workers=max(1, WRITE_THREADS))
     ahead = 2 * eng.in_flight * B
@@ -645,7 +700,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
         for part, take in parts:
             ticket = eng.submit_batch([g[2] for g in part], [g[3] for g in part], DET_THRESHOLD, [g[4] for g in part],
-                                      batch=take, annotate=True, encode=encode, quality=quality, **jpeg_mode)
+                                      batch=take, annotate=True, encode=encode, quality=quality, **jpeg_mode, **edit)
             window.append(([(g[0], g[1]) for g in part], ticket))
             if len(window) >= eng.in_flight:
                 finish()
@@ -729,6 +784,17 @@ def build_parser():
                         "range and the F / A tags are the input stream's (a frame directory: limited range, F25:1, and one frame size)")
     p.add_argument("--video_chroma", dest="video_chroma", choices=VIDEO_CHROMAS, default=None,
                    help="chroma of the stream --out_video writes: 420jpeg (the default) or 444")
+    p.add_argument("--redact", dest="redact", default=None, metavar="CLASSES",
+                   help="hide the detected objects of these classes: comma-separated names of the active class mapping, or all; a box that "
+                        "crosses the frame's border is hidden too")
+    p.add_argument("--redact_mode", dest="redact_mode", choices=REDACT_MODES, default=None,
+                   help="how they are hidden: pixelate (the default) = the means of an N x N pixel grid, blur = a box blur of radius N, "
+                        "fill = black (needs --redact)")
+    p.add_argument("--redact_size", dest="redact_size", type=int, default=None, metavar="N",
+                   help="pixelate: the cell's side, 2..64 (default 16); blur: the radius, 1..32 (default 12); none with fill (needs --redact)")
+    p.add_argument("--redact_margin", dest="redact_margin", type=int, default=None, metavar="N",
+                   help="pixels added around every redacted box (default 0; needs --redact)")
+    p.add_argument("--no_draw", dest="no_draw", action="store_true", help="draw no boxes and no labels (with --redact: only hide)")
     return p
 
 
@@ -787,6 +853,7 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     jpeg_size_options(frame_format, args.jpeg_subsampling, args.jpeg_huffman)
     os.environ.setdefault("GPU_MAX_HW_QUEUES", voc_dets.ENTRY_HW_QUEUES)      # (as voc_dets.main: passes in flight want > 4 queues)
     class_mapping = KITTI_CLASS_MAPPING if args.kitti else VOC_CLASS_MAPPING
+    redact, draw = redact_from_args(args, class_mapping), not args.no_draw                                  # (before any model is loaded)
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)
@@ -813,18 +880,19 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
         if out_video is not None:
             fout = video_out if video_out is not None else stack.enter_context(open(out_video, "wb"))
             sink = y4m.Y4mWriter(fout, w, h, video_chroma, yrange, {k: tags[k] for k in ("F", "A") if k in tags})
-            annotate_stream(manager, detector, reader, sink, resize_min, resize_max)
+            annotate_stream(manager, detector, reader, sink, resize_min, resize_max, redact=redact, draw=draw)
         else:
             annotate_stream(manager, detector, reader, args.out_dir, resize_min, resize_max, png_encoder=args.png_encoder,
                             png_compress=args.png_compress, frame_format=args.frame_format, jpeg_encoder=args.jpeg_encoder,
-                            jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, jpeg_huffman=args.jpeg_huffman)
+                            jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, jpeg_huffman=args.jpeg_huffman,
+                            redact=redact, draw=draw)
         return
     annotate_images(training_manager=manager, detector=detector, input_dir=args.input_dir, out_dir=args.out_dir,
                     image_filenames=frame_filenames(args.input_dir, args.jpeg_decoder or entry.jpeg_decoder()), resize_min=resize_min,
                     resize_max=resize_max, jpeg_decoder=args.jpeg_decoder, png_decoder=args.png_decoder,
                     png_encoder=args.png_encoder, png_compress=args.png_compress, frame_format=args.frame_format,
                     jpeg_encoder=args.jpeg_encoder, jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling,
-                    jpeg_huffman=args.jpeg_huffman)
+                    jpeg_huffman=args.jpeg_huffman, redact=redact, draw=draw)
 
 
 if __name__ == "__main__":

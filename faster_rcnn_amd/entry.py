@@ -301,7 +301,7 @@ class _Slot:
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
-                 "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode")
+                 "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws")
 
     def __init__(self):
         for name in self.__slots__:
@@ -444,13 +444,48 @@ class DetectionEntry:
         self._pinned = _PinnedArena()                    # (per engine: the blocks go when the engine goes)
         self.capture_breakdown = {}
         self._annotate_tables = None
+        self._nodraw_tables = None
+        self._redact_tables = {}
 
-    def annotate_tables(self):
-        """The drawing tables of ops.annotate_u8 for this engine's classes (uploaded once)."""
+    def class_names(self):
+        """This engine's class names by class index ("" for an index no class has)."""
+        rev = self.rev_class_mapping
+        return [rev.get(i, "") for i in range(max(rev) + 1)]
+
+    def annotate_tables(self, draw=True):
+        """The drawing tables of ops.annotate_u8 for this engine's classes (uploaded once).  ``draw`` False: the same tables with no
+        drawable class -- the drawing step of a pass that only redacts paints nothing, with no branch in the pass."""
+        if not draw:
+            if self._nodraw_tables is None:
+                names = self.class_names()
+                self._nodraw_tables = ops.annotate_tables(names, skip=tuple(names))
+            return self._nodraw_tables
         if self._annotate_tables is None:
-            rev = self.rev_class_mapping
-            self._annotate_tables = ops.annotate_tables([rev.get(i, "") for i in range(max(rev) + 1)])
+            self._annotate_tables = ops.annotate_tables(self.class_names())
         return self._annotate_tables
+
+    def redact_table(self, classes):
+        """The class table of ops.redact_u8 for ``classes`` ("all" or a tuple of names) of this engine's classes (uploaded once each)."""
+        t = self._redact_tables.get(classes)
+        if t is None:
+            t = self._redact_tables[classes] = ops.redact_table(self.class_names(), classes)
+        return t
+
+    def redact_option(self, redact):
+        """``submit_batch``'s ``redact`` checked and normalised -> (classes, mode, size, margin): classes "all" or a tuple of this
+        engine's class names, size the mode's default for None.  FrcnnError, with the reason, for anything else."""
+        try:
+            classes, mode, size, margin = redact
+        except (TypeError, ValueError):
+            raise FrcnnError("submit_batch: redact=%r: (classes, mode, size, margin)" % (redact,)) from None
+        try:
+            classes = "all" if classes == "all" or tuple(classes) == ("all",) else ops.redact_class_list(self.class_names(), classes)
+            size = ops.redact_size(mode, size)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: %s" % e) from None
+        if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or margin < 0:
+            raise FrcnnError("submit_batch: redact margin=%r: an integer >= 0" % (margin,))
+        return classes, mode, size, int(margin)
 
     # ------------------------------------------------------------------ eligibility
     @staticmethod
@@ -514,7 +549,13 @@ class DetectionEntry:
             s.x_f32 = s.io_dev[:pix_bytes].view(torch.float32).view(1, H, W, 3)
         # annotating pass: frame i is read back from its staging segment into the slot's own pinned segment after the replay
         s.frame_io = [(s.io_dev[i * seg:i * seg + npix], s.io_pin[i * seg:i * seg + npix]) for i in range(B)] if annotate and not s.encode else None
-        tables = self.annotate_tables() if annotate else None
+        tables = self.annotate_tables(not s.nodraw) if annotate else None
+        if s.redact:
+            # the redacted classes' boxes are hidden in each source frame IN FRONT of the drawing step, and so in front of every encoder;
+            # one workspace serves the frames of a pass, which are redacted one after another
+            r_classes, r_mode, r_size, r_margin = s.redact
+            r_table = self.redact_table(r_classes)
+            s.redact_ws = torch.empty(max(ops.redact_ws_bytes(in_h, in_w, r_mode, r_size), 16), dtype=torch.uint8, device="cuda")
         if s.encode == JPEG_ENCODE:
             # a frame's row: [its length, int32 | pad to 16 | the file, at most jpeg_bound bytes].  The bound is 6.5 times the raw frame
             # (every block at its longest), which is device memory only: a replay reads back the row's first ``first_copy`` bytes -- the
@@ -555,6 +596,8 @@ class DetectionEntry:
             if annotate:                                            # the detections drawn into the source frame (its only reader is done)
                 packed = res["det_packed"]
                 for i in range(B):
+                    if s.redact:
+                        ops.redact_u8(u8[i], packed[i] if B > 1 else packed, r_table, r_mode, r_size, r_margin, workspace=s.redact_ws)
                     ops.annotate_u8(u8[i], packed[i] if B > 1 else packed, tables)
                     if s.encode == Y4M_ENCODE:
                         continue                                    # (all B frames in one launch behind the loop)
@@ -587,12 +630,13 @@ class DetectionEntry:
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
     def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None, jpeg_mode=JPEG_MODE,
-                      y4m_mode=Y4M_MODE):
+                      y4m_mode=Y4M_MODE, redact=None, draw=True):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
         (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
         ends in the device JPEG encoder at ``quality`` in ``jpeg_mode`` = (subsampling, huffman), "y4m" for one that ends in the YUV4MPEG2
-        encoder in ``y4m_mode`` = (chroma, range)."""
+        encoder in ``y4m_mode`` = (chroma, range).  ``redact`` = (classes, mode, size, margin) (``redact_option``): an annotating pass that
+        hides those classes' boxes in each frame (ops.redact_u8) in front of the drawing step; ``draw`` False: one that draws nothing."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -610,6 +654,7 @@ class DetectionEntry:
             s = _Slot()
             s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
             s.encode, s.quality, s.jpeg_mode, s.y4m_mode = encode, quality, jpeg_mode, y4m_mode
+            s.redact, s.nodraw = redact, (None if draw else True)
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -832,7 +877,7 @@ class DetectionEntry:
         return self.submit_batch([image], [resize_ratio], det_threshold, [self.host_pixels(image) if pixels is None else pixels], batch=1)
 
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
-                     subsampling=None, huffman=None, y4m=None):
+                     subsampling=None, huffman=None, y4m=None, redact=None, draw=True):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -847,7 +892,16 @@ class DetectionEntry:
         default is a pass of its own, its key tagged with the pair behind the quality -- (444, "standard") IS the pass without them.
         ``encode`` = "y4m" with ``y4m`` = (chroma, range) ("420jpeg" / "444", "limited" / "full"; None: Y4M_MODE): the B drawn frames are
         converted to YUV4MPEG2 records [Y | Cb | Cr] in one launch (ops.y4m_encode_frames_u8; key tagged "annotate", "y4m", chroma, range)
-        and ``collect_batch`` returns (num_rois, dets, record).  ``y4m`` with any other ``encode`` is an error."""
+        and ``collect_batch`` returns (num_rois, dets, record).  ``y4m`` with any other ``encode`` is an error.
+        ``redact`` = (classes, mode, size, margin) (annotating passes only; a pass of its own, the annotating key with ("redact", classes,
+        mode, size, margin) appended): classes a tuple of class names or "all", mode "pixelate" / "blur" / "fill", size the cell side /
+        blur radius (None: the mode's default; 0 for "fill"), margin >= 0 pixels around each box.  Every box of those classes is hidden in
+        the frame (ops.redact_u8, DESIGN §8 "Redaction rule") before the drawing step, so in front of every ``encode``.  ``draw`` = False
+        (annotating passes only; key tagged ("nodraw",)): nothing is drawn.  Without the two, every key is what it was."""
+        if (redact is not None or not draw) and not annotate:
+            raise FrcnnError("submit_batch: redact= and draw=False change the frame an ANNOTATING pass returns: pass annotate=True")
+        if redact is not None:
+            redact = self.redact_option(redact)
         y4m_mode = Y4M_MODE
         if encode == Y4M_ENCODE:
             y4m_mode = Y4M_MODE if y4m is None else tuple(y4m)
@@ -892,6 +946,10 @@ class DetectionEntry:
                 key = key + jpeg_mode
             if encode == Y4M_ENCODE:
                 key = key + y4m_mode
+            if redact is not None:
+                key = key + ("redact",) + redact
+            if not draw:
+                key = key + ("nodraw",)
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -900,7 +958,7 @@ class DetectionEntry:
             s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
         else:
             s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality,
-                                                                     jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode))
+                                                                     jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode, redact, draw))
         metas, files = [], []
         for i in range(B):
             j = i if i < len(images) else 0

@@ -1137,7 +1137,79 @@ def annotate_u8(frame, det_packed, tables):
     return frame
 
 
-PNG_BAND_ROWS = 1        # scanlines per IDAT chunk of the device encoder (frcnn_png_band_rows(); tests/test_png_cpu.py holds the two together)
+# ----------------------------------------------------------------------------- redaction
+REDACT_MODES = tuple(_lib.REDACT_MODES)         # "fill", "pixelate", "blur"
+REDACT_SIZES = _lib.REDACT_SIZES                # mode -> (smallest, largest, default) ``size``
+
+
+def redact_class_list(class_names, redact_classes):
+    """(host only) The names ``redact_classes`` selects out of ``class_names`` (index = class index): "all" (or ("all",)) = every
+    class but the background "bg" and the unnamed indices; else an iterable of names, each of which must be one of those --
+    ValueError, listing them, for any other."""
+    names = [str(n) for n in class_names]
+    valid = [n for n in names if n and n != "bg"]
+    if redact_classes == "all" or tuple(redact_classes) == ("all",):
+        return tuple(valid)
+    if isinstance(redact_classes, str):
+        redact_classes = (redact_classes,)
+    unknown = [c for c in redact_classes if c not in valid]
+    if unknown:
+        raise ValueError("redact: unknown class name%s %s; the classes are: %s (or \"all\")"
+                         % ("s" if len(unknown) > 1 else "", ", ".join(repr(c) for c in unknown), ", ".join(valid)))
+    return tuple(redact_classes)
+
+
+def redact_size(mode, size=None):
+    """(host only) ``size`` of ``mode`` checked, None replaced by the mode's default: the side P of a pixelate cell (2..64, default
+    16), the radius r of the blur (1..32, default 12), 0 for fill.  ValueError for an unknown mode or a size out of its range."""
+    if mode not in REDACT_SIZES:
+        raise ValueError("redact mode %r: one of %s" % (mode, ", ".join(REDACT_MODES)))
+    lo, hi, default = REDACT_SIZES[mode]
+    if size is None:
+        return default
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or not lo <= int(size) <= hi:
+        raise ValueError("redact size %r out of range for mode \"%s\": %s" % (size, mode, "it takes none" if hi == 0 else "%d..%d" % (lo, hi)))
+    return int(size)
+
+
+def redact_table(class_names, redact_classes):
+    """The per-class byte table ``redact_u8`` reads: device u8 [C], 1 where ``class_names[i]`` is redacted.  ``redact_classes``: names,
+    or "all" for every class but the background (``redact_class_list``)."""
+    _require_gpu()
+    chosen = set(redact_class_list(class_names, redact_classes))
+    return torch.from_numpy(np.array([str(n) in chosen for n in class_names], dtype=np.uint8)).cuda()
+
+
+def redact_ws_bytes(h, w, mode="pixelate", size=None):
+    """Bytes of workspace ``redact_u8`` needs for an (h, w) frame (frcnn_redact_ws_bytes): 0 for "fill"."""
+    return int(_lib.load().frcnn_redact_ws_bytes(int(h), int(w), _lib.REDACT_MODES[mode], redact_size(mode, size)))
+
+
+def redact_u8(frame, det_packed, table, mode="pixelate", size=None, margin=0, workspace=None):
+    """Hide the detections of ``det_packed`` (the post-process's packed buffer, device) whose class is set in ``table``
+    (``redact_table``) in ``frame`` -- an (h, w, 3) uint8 device tensor, edited in place and returned: every pixel inside a box grown by
+    ``margin`` and clipped to the frame becomes 0 ("fill"), the mean of its cell of a ``size`` x ``size`` grid ("pixelate") or a box blur
+    of radius ``size`` ("blur") of the SOURCE frame (frcnn_redact_u8; the rule is DESIGN §8's).  ``size`` None: the mode's default.
+    ``workspace``: a u8 device tensor of at least ``redact_ws_bytes`` bytes; None allocates one.  Reads n_dets from device memory: the
+    call can be captured in a graph."""
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.is_contiguous()
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    if mode not in _lib.REDACT_MODES:
+        raise ValueError("redact mode %r: one of %s" % (mode, ", ".join(REDACT_MODES)))
+    size = REDACT_SIZES[mode][2] if size is None else int(size)            # (the range is the library's to check)
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    if workspace is None:
+        workspace = _ws(_lib.load().frcnn_redact_ws_bytes(h, w, _lib.REDACT_MODES[mode], size))
+    assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    n_dets, det_bbox, det_cls, _, _ = split_detections(det_packed)
+    _lib.call("frcnn_redact_u8", _p(frame), h, w, _p(det_bbox), _p(det_cls), _p(n_dets), int(det_cls.numel()), _p(table),
+              int(table.numel()), _lib.REDACT_MODES[mode], size, int(margin), _p(workspace), int(workspace.numel()), _stream())
+    return frame
+
+
+PNG_BAND_ROWS = 1       # scanlines per IDAT chunk of the device encoder (frcnn_png_band_rows(); tests/test_png_cpu.py holds the two together)
 PNG_HUFF_BAND_ROWS = 8   # ... of its huffman mode (frcnn_png_huff_band_rows(); tests/test_png_huff_cpu.py)
 # compress= of the png_* calls -> the prefix of their entry points: "runs" (include/ext/frcnn_hip_png.h: Sub filter, fixed Huffman codes,
 # run matches) or "huffman" (include/ext/frcnn_hip_png_huff.h: adaptive row filters, a dynamic Huffman code per band)

@@ -19,6 +19,10 @@ per frame) instead of uniform noise: noise does not compress, so bytes per frame
 ``--y4m`` runs three file-to-file legs instead (``run_y4m``): a YUV4MPEG2 stream to a YUV4MPEG2 stream, the stream to PNG files (device
 encoder) and PNG files to PNG files (host codecs), alternating in one session.
 
+``--redact`` runs the redaction's cost instead (``run_redact``): the same frames with and without ``--redact all --redact_mode blur``
+(radius 12, the default), alternating in one session -- through in-memory annotating passes and through annotate_images from PNG files
+to PNG files with the device encoder -- and reports the frames/s of both and their ratio.
+
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
 """
@@ -67,13 +71,13 @@ def build(cfg):
     return mgr, det
 
 
-def annotate_in_memory(eng, resized, ratios):
+def annotate_in_memory(eng, resized, ratios, **kwargs):
     """(b): the frames through annotating passes, eng.batch per pass, eng.in_flight passes in flight (annotate_images' loop
-    without the files)."""
+    without the files).  ``kwargs``: further arguments of submit_batch (``redact``)."""
     B, window, frames = eng.batch, [], []
     for i in range(0, len(resized), B):
         part = resized[i:i + B]
-        window.append(eng.submit_batch(part, ratios[i:i + B], 0.0, [eng.host_pixels(r) for r in part], batch=B, annotate=True))
+        window.append(eng.submit_batch(part, ratios[i:i + B], 0.0, [eng.host_pixels(r) for r in part], batch=B, annotate=True, **kwargs))
         if len(window) >= eng.in_flight:
             frames += [r[2] for r in eng.collect_batch(window.pop(0))]
     while window:
@@ -230,6 +234,54 @@ def run_y4m(name, cfg, n_frames, reps, content="noise"):
     return res
 
 
+REDACT_LEG = ("all", "blur", None, 0)                    # --redact all --redact_mode blur
+
+
+def run_redact(name, cfg, n_frames, reps, content="noise"):
+    """``--redact``: what hiding every detected object costs.  Two pairs of legs in ONE session, each pair alternating inside every
+    repetition: the frames through in-memory annotating passes (leg (b) of ``run_pair``) without and with ``redact=REDACT_LEG``, and
+    annotate_images from PNG files to PNG files (device encoder) without and with it.  Reports frames/s of each and with / without."""
+    import numpy as np
+    from PIL import Image as PilImage
+    from faster_rcnn_amd import annotate_video, entry, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+    with tempfile.TemporaryDirectory() as tmp:
+        d_in, d_out = os.path.join(tmp, "in"), os.path.join(tmp, "out")
+        os.makedirs(d_in)
+        names = ["%06d.png" % i for i in range(n_frames)]
+        for nm, s in zip(names, srcs):
+            PilImage.fromarray(s[:, :, ::-1]).save(os.path.join(d_in, nm), compress_level=1)
+        files = lambda **kw: annotate_video.annotate_images(mgr, det, d_in, d_out, names, *cfg["resize"], png_encoder="device", **kw)
+        legs = {"passes": lambda: annotate_in_memory(eng, resized, ratios),
+                "passes_redact": lambda: annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG),
+                "files": files, "files_redact": lambda: files(redact=REDACT_LEG)}
+        times = {k: [] for k in legs}
+        with contextlib.redirect_stdout(io.StringIO()):
+            for fn in legs.values():                                # warm-up: captures
+                fn()
+            for _ in range(reps):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    fn()
+                    times[k].append(time.perf_counter() - t0)
+        hidden = annotate_in_memory(eng, resized[:eng.batch], ratios[:eng.batch], redact=REDACT_LEG)
+        share = float(np.mean([(a != b).any(axis=2).mean() for a, b in zip(hidden, annotate_in_memory(eng, resized[:eng.batch], ratios[:eng.batch]))]))
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact": ["all", "blur", 12, 0], "images_per_pass": eng.batch, "in_flight": eng.in_flight, "pixels_changed_share": round(share, 3)}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    for k in ("passes", "files"):
+        res[k + "_redact_over_plain"] = round(statistics.median(times[k]) / statistics.median(times[k + "_redact"]), 3)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--frames", type=int, default=256)
@@ -241,6 +293,8 @@ def main():
     ap.add_argument("--content", choices=("noise", "photo"), default="noise", help="what the frames hold (see the module docstring)")
     ap.add_argument("--y4m", action="store_true", help="instead of the legs above: y4m to y4m, y4m to PNG files (device encoder) and PNG files "
                                                        "to PNG files (host codecs), alternating in one session")
+    ap.add_argument("--redact", action="store_true", help="instead of the legs above: the same frames with and without --redact all "
+                                                          "--redact_mode blur, alternating in one session (passes in memory, and files to files)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -249,6 +303,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.redact:
+            out[name] = run_redact(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         encoders = {"both": ("host", "device"), "all": ("host", "device", "device_huffman")}.get(args.png_encoder, (args.png_encoder,))
         if args.legs:
