@@ -378,6 +378,19 @@ REDACT_MODES = {"fill": 0, "pixelate": 1, "blur": 2}                            
 # mode -> (smallest size, largest size, the default): FRCNN_REDACT_PIXELATE_MIN / _MAX, FRCNN_REDACT_BLUR_MIN / _MAX; fill takes none (0)
 REDACT_SIZES = {"fill": (0, 0, 0), "pixelate": (2, 64, 16), "blur": (1, 32, 12)}
 
+TRACK_VERSION = 1               # include/ext/frcnn_hip_track.h FRCNN_TRACK_VERSION
+TRACK_MAX = 128                 # ... FRCNN_TRACK_MAX: slots of a state
+TRACK_MAX_FRAMES = 64           # ... FRCNN_TRACK_MAX_FRAMES: frames of one call
+TRACK_SIGNATURES = {
+    "frcnn_track_version": (I, []),
+    "frcnn_track_state_bytes": (c_size_t, [I]),
+    "frcnn_track_update": (I, [P, I, P, ctypes.c_longlong, I, P, I, P, I, I, I, I, I, I, P, ctypes.c_longlong, P]),
+    "frcnn_annotate_ids_u8": (I, [P, I, I, P, P, P, P, P, I, P, P, I, I, P, P]),
+}
+# (thr, hold, grow): the defaults, and the range of each (FRCNN_TRACK_MAX_HOLD, FRCNN_TRACK_MAX_GROW)
+TRACK_DEFAULTS = (30, 8, 0)
+TRACK_RANGES = ((1, 100), (0, 255), (0, 64))
+
 
 class ConvDesc(ctypes.Structure):
     """frcnn_conv_desc (include/frcnn_hip.h)."""
@@ -488,6 +501,13 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in TRACK_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_track_version() != TRACK_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_version()} of the tracking extension, this binding "
+                         f"{TRACK_VERSION} (include/ext/frcnn_hip_track.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

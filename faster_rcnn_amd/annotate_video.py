@@ -50,6 +50,14 @@ default 16), a box blur of radius N ("blur", 1..32, default 12) or black ("fill"
 csrc/redact.hip; the rule is DESIGN §8's).  Unlike the drawing, a box that crosses the frame's border IS redacted, and 'DontCare' / 'Misc'
 are when named.  It runs inside the pass in front of the drawing step, so before every encoder and for every input format.
 ``draw=False`` (``--no_draw``) leaves the boxes and labels out.  The printed lines do not change with either.
+
+``track=(thr, hold, grow)`` (``--track [--track_iou PCT] [--track_hold N] [--track_grow N]``) joins the detections of consecutive frames
+into tracks on the device (ops.track_update, csrc/track.hip; DESIGN §8 "Tracking rule"): a detection whose box overlaps a track's last
+box of the same class by at least PCT percent IoU (default 30) continues it and is labelled ``cls#id``; a track the detector loses is HELD
+for N frames (default 8), its box growing by ``grow`` pixels per frame (default 0) -- held boxes are redacted with ``--redact`` (so the
+redaction does not flicker off when the detector misses a frame) and never drawn.  Frames are tracked in input order; the tracked classes
+are the drawable ones and the redacted ones.  ``--tracks_out PATH`` writes one MOTChallenge line per live tracked row
+(``frame,id,left,top,width,height,prob,cls,-1,-1``, frames counted from 1).  The printed dets then carry "track_id".
 """
 import collections
 import os
@@ -212,6 +220,7 @@ def _pack_dets(dets, class_mapping):
 
 _EAGER_TABLES = {}
 _EAGER_REDACT_TABLES = {}
+_EAGER_TRACKERS = {}                                      # class mapping -> [state, {redact classes: table}, the one-frame count word]
 
 
 def _names_by_index(class_mapping):
@@ -219,26 +228,63 @@ def _names_by_index(class_mapping):
     return [rev.get(i, "") for i in range(max(rev) + 1)]
 
 
-def draw_eager(frame, dets, class_mapping, redact=None, draw=True):
-    """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place.
-    ``redact`` = (classes, mode, size, margin): one ops.redact_u8 in front of it; ``draw`` False: no drawing."""
+def _eager_tracker(class_mapping):
     import torch
     key = tuple(sorted(class_mapping.items()))
-    if dets and (draw or redact is not None):             # (nothing to draw or hide: the frame stays as it is)
+    t = _EAGER_TRACKERS.get(key)
+    if t is None:
+        t = _EAGER_TRACKERS[key] = [ops.track_state(entry.TRACK_CAPACITY), {}, torch.ones(1, dtype=torch.int32, device="cuda")]
+    return t
+
+
+def _eager_track_table(tracker, class_mapping, redact_classes):
+    table = tracker[1].get(redact_classes)
+    if table is None:
+        names = _names_by_index(class_mapping)
+        chosen = [n for n in names if n and n != "bg" and n not in ops.ANNOTATE_SKIP]
+        if redact_classes is not None:
+            chosen += [n for n in ops.redact_class_list(names, redact_classes) if n not in chosen]
+        table = tracker[1][redact_classes] = ops.track_table(names, chosen)
+    return table
+
+
+def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None):
+    """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place.
+    ``redact`` = (classes, mode, size, margin): one ops.redact_u8 in front of it; ``draw`` False: no drawing.
+    ``track`` = (thr, hold, grow): one ops.track_update (one frame) in front of both, on this class mapping's eager tracker state
+    (``reset_tracks`` empties it); ``dets`` is edited in place as ``collect_batch`` returns it: "track_id" on every det, the held rows
+    appended with "held"."""
+    import torch
+    key = tuple(sorted(class_mapping.items()))
+    if track is not None or (dets and (draw or redact is not None)):      # (nothing to draw or hide: the frame stays as it is)
         dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
         packed = torch.from_numpy(_pack_dets(dets, class_mapping)).cuda()
+        classes = None
         if redact is not None:
             classes, mode, size, margin = redact
             classes = classes if classes == "all" else tuple(classes)
+        if track is not None:
+            tracker = _eager_tracker(class_mapping)
+            rows = ops.track_update(tracker[0], packed, tracker[2], _eager_track_table(tracker, class_mapping, classes),
+                                    frame.shape[0], frame.shape[1], *track)[0]
+            n_rows, _, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(rows.cpu().numpy())
+            rev = {v: k for k, v in class_mapping.items()}
+            for k, d in enumerate(dets):
+                d["track_id"] = int(t_id[k])
+            dets += [{"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(), "track_id": int(t_id[k]),
+                      "held": int(t_age[k])} for k in range(len(dets), int(n_rows[0]))]
+        else:
+            rows = packed
+        if redact is not None:
             table = _EAGER_REDACT_TABLES.get((key, classes))
             if table is None:
                 table = _EAGER_REDACT_TABLES[(key, classes)] = ops.redact_table(_names_by_index(class_mapping), classes)
-            ops.redact_u8(dev, packed, table, mode, size, margin)
+            ops.redact_u8(dev, rows, table, mode, size, margin, tracked=track is not None)
         if draw:
             tables = _EAGER_TABLES.get(key)
             if tables is None:
                 tables = _EAGER_TABLES[key] = ops.annotate_tables(_names_by_index(class_mapping))
-            ops.annotate_u8(dev, packed, tables)
+            ops.annotate_u8(dev, rows, tables, tracked=track is not None)
         frame[...] = dev.cpu().numpy()
     return frame
 
@@ -268,26 +314,75 @@ def redact_from_args(args, class_mapping):
     return classes, mode, size, margin
 
 
+def track_from_args(args):
+    """(host only) The tracking the command line asks for -> (thr, hold, grow) as ``submit_batch(track=...)`` takes it, or None without
+    ``--track``.  ValueError, with the reason, for ``--track_iou`` / ``--track_hold`` / ``--track_grow`` / ``--tracks_out`` without
+    ``--track`` and for a value out of range (1..100, 0..255, 0..64)."""
+    if not args.track:
+        for flag, value in (("--track_iou", args.track_iou), ("--track_hold", args.track_hold), ("--track_grow", args.track_grow),
+                            ("--tracks_out", args.tracks_out)):
+            if value is not None:
+                raise ValueError("%s=%s is a setting of the tracker: it needs --track" % (flag, value))
+        return None
+    try:
+        return ops.track_option(args.track_iou, args.track_hold, args.track_grow)
+    except ValueError as e:
+        raise ValueError("--track_iou / --track_hold / --track_grow: %s" % e) from None
+
+
+def mot_lines(frame_no, dets, class_mapping):
+    """The MOTChallenge lines of one frame: ``frame,id,left,top,width,height,prob,cls,-1,-1`` per LIVE tracked det ("track_id" > 0, no
+    "held"), in row order; left / top the smaller corner, width / height the corners' distance, prob with six decimals, cls the index."""
+    out = []
+    for d in dets:
+        if d.get("held") or d.get("track_id", 0) <= 0:
+            continue
+        x1, y1, x2, y2 = [int(v) for v in d["bbox"]]
+        out.append("%d,%d,%d,%d,%d,%d,%.6f,%d,-1,-1" % (frame_no, d["track_id"], min(x1, x2), min(y1, y2), abs(x2 - x1), abs(y2 - y1),
+                                                       float(d["prob"]), class_mapping[d["cls_name"]]))
+    return out
+
+
+def _write_tracks(tracks_out, frame_no, dets, class_mapping):
+    if tracks_out is not None:
+        tracks_out.writelines(line + "\n" for line in mot_lines(frame_no, dets, class_mapping))
+
+
+def reset_tracks(training_manager, detector, in_flight=1):
+    """Forget every track before a new sequence: the state of the engine ``in_flight`` names, or the eager path's."""
+    eng = _engine(training_manager, detector, in_flight)
+    if eng is not None:
+        eng.track_reset()
+    else:
+        ops.track_reset(_eager_tracker(training_manager.class_mapping)[0])
+
+
 def _print_drawn(dets, width, height):
     for det in dets:
-        if drawn(det, width, height):
+        if not det.get("held") and drawn(det, width, height):       # (held rows, of tracking passes only, are never drawn)
             print(det)
 
 
-def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True):
+def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
+                        frame_no=1):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
-    ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn."""
+    ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
+    ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
+    ``tracks_out``: a text file that receives the frame's MOT lines under the number ``frame_no``."""
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1)
     if eng is not None:
         pixels = eng.host_pixels(resized_imgs[0])
         num_rois, dets, out = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], DET_THRESHOLD, [pixels],
-                                                                 batch=1, annotate=True, redact=redact, draw=draw))[0]
+                                                                 batch=1, annotate=True, redact=redact, draw=draw,
+                                                                 **({} if track is None else {"track": track})))[0]
         print("num rois: {}".format(num_rois))
         frame[...] = out
     else:
         dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=DET_THRESHOLD)
-        draw_eager(frame, dets, training_manager.class_mapping, redact, draw)
+        draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track)
+    if track is not None:
+        _write_tracks(tracks_out, frame_no, dets, training_manager.class_mapping)
     _print_drawn(dets, img.width, img.height)
     return frame
 
@@ -465,13 +560,13 @@ def directory_frames(input_dir, image_filenames, jpeg_decoder=None, png_decoder=
 
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
-                    redact=None, draw=True):
+                    redact=None, draw=True, track=None, tracks_out=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out``: as ``annotate_images``."""
     from concurrent.futures import ThreadPoolExecutor
     to_video = isinstance(writer_or_out_dir, y4m.Y4mWriter)
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
@@ -506,6 +601,10 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
         check_size = lambda label, frame: None
     if redact is not None or not draw:                    # (else the passes, and their keys, are the ones without the arguments)
         kwargs = dict(kwargs, redact=redact, draw=draw)
+    mapping = training_manager.class_mapping
+    if track is not None:                                 # a new sequence; its frames are submitted in stream order, as every stream's are
+        kwargs = dict(kwargs, track=track)
+        reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
 
     if eng is None:                                       # eager path / foreign models: one frame at a time, converted on the device
         import torch
@@ -517,7 +616,8 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
             else:
                 frame = np.ascontiguousarray(src.raw)
             img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
-            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=redact, draw=draw)
+            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=redact, draw=draw, track=track,
+                                      tracks_out=tracks_out, frame_no=pos + 1)
             if to_video:
                 writer.write(ops.y4m_encode_u8(torch.from_numpy(out).cuda(), writer.chroma, writer.range, bgr=True).cpu().numpy().tobytes())
             elif on_device:
@@ -554,6 +654,8 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
         for (pos, label, frame), (num_rois, dets, out) in zip(part, results):
             print("processing {}".format(label))
             print("num rois: {}".format(num_rois))
+            if track is not None:
+                _write_tracks(tracks_out, pos + 1, dets, mapping)
             _print_drawn(dets, frame.width, frame.height)
             if to_video:
                 writes.append(write.submit(writer.write, out))            # (one writer thread: stream order)
@@ -610,7 +712,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
-                    jpeg_huffman=None, png_decoder=None, redact=None, draw=True):
+                    jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -625,7 +727,10 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     who decodes ``.png`` INPUT frames the device decoder supports (captured path only; the decode
     threads then only read the file and check its chunks); None = what ``entry.png_decoder()`` says (FRCNN_ENTRY_PNG_DECODER, default "host").
     ``redact``: (classes, mode, size, margin) as ``redact_from_args`` returns it -- those classes' boxes are hidden in every frame inside
-    its pass, in front of the drawing step and of whichever encoder writes the frame; None: nothing is.  ``draw`` False: no boxes, no labels."""
+    its pass, in front of the drawing step and of whichever encoder writes the frame; None: nothing is.  ``draw`` False: no boxes, no labels.
+    ``track``: (thr, hold, grow) as ``track_from_args`` returns it -- the list is ONE sequence in list order: the tracker's state is reset
+    at the start, every tracked detection is labelled ``cls#id`` and lost tracks are held (and redacted) for ``hold`` frames; None: no
+    tracking.  ``tracks_out``: a text file that receives the MOT lines, frame i of the list under the number i + 1."""
     from concurrent.futures import ThreadPoolExecutor
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
@@ -652,12 +757,16 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
     eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
     pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
+    mapping = training_manager.class_mapping
+    if track is not None:
+        reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
     if eng is None:                                       # eager path / foreign models: the reference's loop
-        for name, path in zip(out_names, paths):
+        for frame_no, (name, path) in enumerate(zip(out_names, paths), 1):
             print("processing {}".format(path))
             frame = np.ascontiguousarray(_read_rgb(path)[:, :, ::-1])
             img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
-            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=redact, draw=draw)
+            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=redact, draw=draw, track=track,
+                                      tracks_out=tracks_out, frame_no=frame_no)
             if on_device:
                 import torch
                 dev = torch.from_numpy(out).cuda()
@@ -675,6 +784,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
 
     n, B = len(paths), eng.batch
     edit = dict(redact=redact, draw=draw) if redact is not None or not draw else {}      # (else the passes without the arguments)
+    if track is not None:                                 # (the groups below are submitted in list order, as tracking needs them)
+        edit = dict(edit, track=track)
     decode = ThreadPoolExecutor(max_workers=max(1, DECODE_THREADS))
     write = ThreadPoolExecutor(max_workers=max(1, WRITE_THREADS))
     ahead = 2 * eng.in_flight * B
@@ -689,6 +800,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         for (pos, frame), (num_rois, dets, out) in zip(part, results):
             print("processing {}".format(paths[pos]))
             print("num rois: {}".format(num_rois))
+            if track is not None:
+                _write_tracks(tracks_out, pos + 1, dets, mapping)
             _print_drawn(dets, frame.width, frame.height)
             writes.append(write.submit(_write_bytes if on_device else write_host, os.path.join(out_dir, out_names[pos]), out))
         while len(writes) > 4 * WRITE_THREADS:            # (bounded: encoded frames must not pile up in memory)
@@ -795,6 +908,18 @@ def build_parser():
     p.add_argument("--redact_margin", dest="redact_margin", type=int, default=None, metavar="N",
                    help="pixels added around every redacted box (default 0; needs --redact)")
     p.add_argument("--no_draw", dest="no_draw", action="store_true", help="draw no boxes and no labels (with --redact: only hide)")
+    p.add_argument("--track", dest="track", action="store_true",
+                   help="join the detections of consecutive frames into tracks: labels read cls#id, and a track the detector loses is held "
+                        "(and, with --redact, stays hidden) for --track_hold frames")
+    p.add_argument("--track_iou", dest="track_iou", type=int, default=None, metavar="PCT",
+                   help="a detection continues a track of its class when their boxes overlap by at least PCT percent IoU, 1..100 "
+                        "(default 30; needs --track)")
+    p.add_argument("--track_hold", dest="track_hold", type=int, default=None, metavar="N",
+                   help="frames a lost track is held, 0..255 (default 8; 0: ids only; needs --track)")
+    p.add_argument("--track_grow", dest="track_grow", type=int, default=None, metavar="N",
+                   help="pixels a held box grows by on every side per frame held, 0..64 (default 0; needs --track)")
+    p.add_argument("--tracks_out", dest="tracks_out", default=None, metavar="PATH",
+                   help="write the tracks as MOTChallenge lines frame,id,left,top,width,height,prob,cls,-1,-1 (needs --track)")
     return p
 
 
@@ -854,6 +979,8 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     os.environ.setdefault("GPU_MAX_HW_QUEUES", voc_dets.ENTRY_HW_QUEUES)      # (as voc_dets.main: passes in flight want > 4 queues)
     class_mapping = KITTI_CLASS_MAPPING if args.kitti else VOC_CLASS_MAPPING
     redact, draw = redact_from_args(args, class_mapping), not args.no_draw                                  # (before any model is loaded)
+    track = track_from_args(args)
+    tracking = {} if track is None else {"track": track, "tracks_out": stack.enter_context(open(args.tracks_out, "w")) if args.tracks_out else None}
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)
@@ -880,19 +1007,19 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
         if out_video is not None:
             fout = video_out if video_out is not None else stack.enter_context(open(out_video, "wb"))
             sink = y4m.Y4mWriter(fout, w, h, video_chroma, yrange, {k: tags[k] for k in ("F", "A") if k in tags})
-            annotate_stream(manager, detector, reader, sink, resize_min, resize_max, redact=redact, draw=draw)
+            annotate_stream(manager, detector, reader, sink, resize_min, resize_max, redact=redact, draw=draw, **tracking)
         else:
             annotate_stream(manager, detector, reader, args.out_dir, resize_min, resize_max, png_encoder=args.png_encoder,
                             png_compress=args.png_compress, frame_format=args.frame_format, jpeg_encoder=args.jpeg_encoder,
                             jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, jpeg_huffman=args.jpeg_huffman,
-                            redact=redact, draw=draw)
+                            redact=redact, draw=draw, **tracking)
         return
     annotate_images(training_manager=manager, detector=detector, input_dir=args.input_dir, out_dir=args.out_dir,
                     image_filenames=frame_filenames(args.input_dir, args.jpeg_decoder or entry.jpeg_decoder()), resize_min=resize_min,
                     resize_max=resize_max, jpeg_decoder=args.jpeg_decoder, png_decoder=args.png_decoder,
                     png_encoder=args.png_encoder, png_compress=args.png_compress, frame_format=args.frame_format,
                     jpeg_encoder=args.jpeg_encoder, jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling,
-                    jpeg_huffman=args.jpeg_huffman, redact=redact, draw=draw)
+                    jpeg_huffman=args.jpeg_huffman, redact=redact, draw=draw, **tracking)
 
 
 if __name__ == "__main__":

@@ -4,6 +4,7 @@
 // overlapping writes store the same bytes.  The drawing rule (square corners, a 5x7 bitmap font at scale 2) is this
 // project's and is stated in DESIGN §8; faster_rcnn_amd/annotate_video.py documents the same rule for callers.
 #include "common.h"
+#include "../../include/ext/frcnn_hip_track.h"
 #include <math.h>
 
 namespace frcnn {
@@ -13,6 +14,8 @@ constexpr int ANN_MAX_ROWS = 512;
 constexpr int ANN_MAX_LABEL_STRIDE = 64;
 // name (<= 63) + ' ' + the number: sign, up to 39 integer digits of a float32, '.', 2 decimals
 constexpr int ANN_LABEL_MAX = 128;
+constexpr int ANN_ID_MAX = 11;                                              // '#' + the ten digits of an int32 track id
+static_assert(ANN_MAX_LABEL_STRIDE - 1 + ANN_ID_MAX + 1 + 44 <= ANN_LABEL_MAX, "the label buffer holds the longest label with an id");
 
 __device__ __forceinline__ void paint(uint8_t* frame, int width, int x, int y) {
     uint8_t* p = frame + ((size_t)y * (size_t)width + (size_t)x) * 3;
@@ -81,7 +84,9 @@ __device__ int format_prob(float p, char* out, char* digits, uint32_t* limb) {
 __global__ void __launch_bounds__(ANN_THREADS) k_annotate_u8(uint8_t* frame, int height, int width, const int32_t* det_bbox,
                                                               const int32_t* det_cls, const float* det_prob, const int32_t* n_dets,
                                                               const uint8_t* drawable, const char* labels,
-                                                              int label_stride, int num_classes, const uint8_t* glyphs) {
+                                                              int label_stride, int num_classes, const uint8_t* glyphs,
+                                                              const int32_t* det_id) {
+    // det_id: the rows' track ids (frcnn_annotate_ids_u8), or null: no row has one
     // glyphs: printable ASCII 0x20..0x7E, 7 row bytes each, bit 4 = the leftmost column
     __shared__ char s_label[ANN_LABEL_MAX];
     __shared__ char s_digits[48];
@@ -103,11 +108,18 @@ __global__ void __launch_bounds__(ANN_THREADS) k_annotate_u8(uint8_t* frame, int
     paint_rect(frame, height, width, xa - 1, xa + 1, ya - 1, yb + 1);
     paint_rect(frame, height, width, xb - 1, xb + 1, ya - 1, yb + 1);
 
-    // ---- the label "{} {:6.2f}".format(cls_name, prob) at (x1, y2 + 16), formatted once per workgroup
+    // ---- the label "{} {:6.2f}".format(cls_name, prob) at (x1, y2 + 16), formatted once per workgroup; "{}#{} {:6.2f}" with a track id
     if (threadIdx.x == 0) {
         const char* name = labels + (size_t)cls * label_stride;
         int n = 0;
         while (n < label_stride - 1 && name[n] != 0) { s_label[n] = name[n]; ++n; }
+        const int id = det_id ? det_id[row] : 0;
+        if (id > 0) {
+            s_label[n++] = '#';
+            int nd = 0;
+            for (int v = id; v > 0; v /= 10) s_digits[nd++] = (char)('0' + v % 10);
+            while (nd > 0) s_label[n++] = s_digits[--nd];
+        }
         s_label[n++] = ' ';
         n += format_prob(det_prob[row], s_label + n, s_digits, s_limb);
         s_len = n;
@@ -142,6 +154,25 @@ extern "C" int frcnn_annotate_u8(uint8_t* frame, int height, int width, const in
         return fail(FRCNN_E_ARG, "annotate_u8: label_stride=%d not in [1, %d]", label_stride, ANN_MAX_LABEL_STRIDE);
     if (num_classes <= 0 || num_classes > 256) return fail(FRCNN_E_ARG, "annotate_u8: num_classes=%d not in [1, 256]", num_classes);
     k_annotate_u8<<<max_rows, ANN_THREADS, 0, as_stream(stream)>>>(frame, height, width, det_bbox, det_cls, det_prob, n_dets,
-                                                                     drawable, labels, label_stride, num_classes, glyphs);
+                                                                     drawable, labels, label_stride, num_classes, glyphs, nullptr);
     return check_launch("annotate_u8");
+}
+
+extern "C" int frcnn_annotate_ids_u8(uint8_t* frame, int height, int width, const int32_t* det_bbox, const int32_t* det_cls,
+                                     const float* det_prob, const int32_t* det_id, const int32_t* n_dets, int max_rows,
+                                     const uint8_t* drawable, const char* labels, int label_stride, int num_classes, const uint8_t* glyphs,
+                                     void* stream) {
+    if (!det_id) return frcnn_annotate_u8(frame, height, width, det_bbox, det_cls, det_prob, n_dets, max_rows, drawable, labels, label_stride,
+                                          num_classes, glyphs, stream);
+    if (!frame || !det_bbox || !det_cls || !det_prob || !n_dets || !drawable || !labels || !glyphs)
+        return fail(FRCNN_E_ARG, "annotate_ids_u8: null pointer");
+    if (height <= 0 || width <= 0)
+        return fail(FRCNN_E_ARG, "annotate_ids_u8: frame %dx%d out of range", height, width);
+    if (max_rows <= 0 || max_rows > ANN_MAX_ROWS) return fail(FRCNN_E_ARG, "annotate_ids_u8: max_rows=%d not in [1, %d]", max_rows, ANN_MAX_ROWS);
+    if (label_stride < 1 || label_stride > ANN_MAX_LABEL_STRIDE)
+        return fail(FRCNN_E_ARG, "annotate_ids_u8: label_stride=%d not in [1, %d]", label_stride, ANN_MAX_LABEL_STRIDE);
+    if (num_classes <= 0 || num_classes > 256) return fail(FRCNN_E_ARG, "annotate_ids_u8: num_classes=%d not in [1, 256]", num_classes);
+    k_annotate_u8<<<max_rows, ANN_THREADS, 0, as_stream(stream)>>>(frame, height, width, det_bbox, det_cls, det_prob, n_dets,
+                                                                     drawable, labels, label_stride, num_classes, glyphs, det_id);
+    return check_launch("annotate_ids_u8");
 }

@@ -50,6 +50,7 @@ JPEG_MODE = (444, "standard")          # ... its default (subsampling, huffman):
 Y4M_ENCODE = "y4m"
 Y4M_MODE = ("420jpeg", "limited")
 PRE_NMS_TOP_N, MAX_PROPOSALS = 8000, 300        # det_util.py:151-156
+TRACK_CAPACITY = 64                             # slots of an engine's tracker state (submit_batch(track=...))
 
 
 def _default_budget():
@@ -301,7 +302,8 @@ class _Slot:
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
-                 "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws")
+                 "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
+                 "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev")
 
     def __init__(self):
         for name in self.__slots__:
@@ -446,6 +448,8 @@ class DetectionEntry:
         self._annotate_tables = None
         self._nodraw_tables = None
         self._redact_tables = {}
+        self._track_state = None                         # the engine's ONE tracker state (ops.track_state): its pointer is in the graphs
+        self._track_tables = {}
 
     def class_names(self):
         """This engine's class names by class index ("" for an index no class has)."""
@@ -487,6 +491,49 @@ class DetectionEntry:
             raise FrcnnError("submit_batch: redact margin=%r: an integer >= 0" % (margin,))
         return classes, mode, size, int(margin)
 
+    # ------------------------------------------------------------------ tracking
+    @property
+    def track_stream(self):
+        """The ONE stream every pass submitted with ``track=`` replays on, in submit order: frame i + 1 needs frame i's state."""
+        return self._streams[0]
+
+    def track_state(self):
+        """The engine's tracker state (device int32, ops.track_state), made on first use: TRACK_CAPACITY slots, fewer when the
+        post-process's rows leave less room under the drawing and redaction kernels' 512 rows."""
+        if self._track_state is None:
+            rows = -(-MAX_PROPOSALS // self.num_rois) * self.num_rois
+            cap = min(TRACK_CAPACITY, _lib.REDACT_MAX_ROWS - rows)
+            if cap < 1:
+                raise FrcnnError("track=: the post-process's %d rows leave no room for held rows (at most %d rows in all)" % (rows, _lib.REDACT_MAX_ROWS))
+            self._track_state = ops.track_state(cap)
+        return self._track_state
+
+    def track_reset(self):
+        """Forget every track: the state is zeroed on the tracking stream, behind the tracked passes submitted so far."""
+        state = self.track_state()
+        with torch.cuda.stream(self.track_stream):
+            ops.track_reset(state)
+
+    def track_table(self, redact_classes=None):
+        """The class table of ops.track_update: the classes the drawing rule draws united with ``redact_classes`` (uploaded once each)."""
+        t = self._track_tables.get(redact_classes)
+        if t is None:
+            names = self.class_names()
+            chosen = [n for n in names if n and n != "bg" and n not in ops.ANNOTATE_SKIP]
+            if redact_classes is not None:
+                chosen += [n for n in ops.redact_class_list(names, redact_classes) if n not in chosen]
+            t = self._track_tables[redact_classes] = ops.track_table(names, chosen)
+        return t
+
+    @staticmethod
+    def track_option(track):
+        """``submit_batch``'s ``track`` checked -> (thr, hold, grow) (None in a place: its default).  FrcnnError with the reason."""
+        try:
+            thr, hold, grow = track
+            return ops.track_option(thr, hold, grow)
+        except (TypeError, ValueError) as e:
+            raise FrcnnError("submit_batch: track=%r: (thr, hold, grow): %s" % (track, e)) from None
+
     # ------------------------------------------------------------------ eligibility
     @staticmethod
     def usable(manager, detector, num_rois):
@@ -512,11 +559,15 @@ class DetectionEntry:
         -> (the pinned side as a numpy array, the device view the pass reads the pairs from: (B, 2) f64, one image's (2,) for B = 1)."""
         B, off = s.batch, s.batch * seg
         s.seg = seg
-        s.io_dev = torch.zeros(off + 16 * B, dtype=torch.uint8, device="cuda")
+        tail = 16 if s.track else 0                      # a tracking pass: | the count of real frames, int32 (ops.track_update's n_frames)]
+        s.io_dev = torch.zeros(off + 16 * B + tail, dtype=torch.uint8, device="cuda")
         fine("buffers: device staging")
-        s.io_pin = self._pinned.take(off + 16 * B, zero=True)
+        s.io_pin = self._pinned.take(off + 16 * B + tail, zero=True)
         fine("buffers: pinned staging")
         host = s.io_pin.numpy()
+        if s.track:                                      # (0 until a submit says otherwise: warm-up and capture leave the state alone)
+            s.n_frames_host = host[off + 16 * B:off + 16 * B + 4].view(np.int32)
+            s.n_frames_dev = s.io_dev[off + 16 * B:off + 16 * B + 4].view(torch.int32)
         s.dyn_host = host[off:off + 16 * B].view(np.float64).reshape(B, 2)
         s.dyn_host[:] = (1.0, 0.0)
         dyn_dev = s.io_dev[off:off + 16 * B].view(torch.float64).view(B, 2)
@@ -556,6 +607,11 @@ class DetectionEntry:
             r_classes, r_mode, r_size, r_margin = s.redact
             r_table = self.redact_table(r_classes)
             s.redact_ws = torch.empty(max(ops.redact_ws_bytes(in_h, in_w, r_mode, r_size), 16), dtype=torch.uint8, device="cuda")
+        if s.track:
+            # ONE tracker update over the pass's B frames behind the post-process: the redaction then reads every tracked row (the held
+            # boxes are hidden), the drawing step the live rows with their ids
+            t_thr, t_hold, t_grow = s.track
+            t_state, t_table = self.track_state(), self.track_table(s.redact[0] if s.redact else None)
         if s.encode == JPEG_ENCODE:
             # a frame's row: [its length, int32 | pad to 16 | the file, at most jpeg_bound bytes].  The bound is 6.5 times the raw frame
             # (every block at its longest), which is device memory only: a replay reads back the row's first ``first_copy`` bytes -- the
@@ -595,10 +651,16 @@ class DetectionEntry:
             res = pipe.forward_dev(s.x_f32, dyn=dyn)
             if annotate:                                            # the detections drawn into the source frame (its only reader is done)
                 packed = res["det_packed"]
+                if s.track:
+                    if s.track_out is None:                         # (the first warm-up pass: the rows of a packed buffer are known now)
+                        R = ops.track_rows(packed) + ops.track_capacity(t_state)
+                        s.track_out = torch.zeros((B, 4 + 8 * R), dtype=torch.int32, device="cuda")
+                    ops.track_update(t_state, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold, t_grow, out=s.track_out)
                 for i in range(B):
+                    rows = s.track_out[i] if s.track else packed[i] if B > 1 else packed
                     if s.redact:
-                        ops.redact_u8(u8[i], packed[i] if B > 1 else packed, r_table, r_mode, r_size, r_margin, workspace=s.redact_ws)
-                    ops.annotate_u8(u8[i], packed[i] if B > 1 else packed, tables)
+                        ops.redact_u8(u8[i], rows, r_table, r_mode, r_size, r_margin, workspace=s.redact_ws, tracked=bool(s.track))
+                    ops.annotate_u8(u8[i], rows, tables, tracked=bool(s.track))
                     if s.encode == Y4M_ENCODE:
                         continue                                    # (all B frames in one launch behind the loop)
                     if s.encode == JPEG_ENCODE:
@@ -630,13 +692,14 @@ class DetectionEntry:
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
     def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None, jpeg_mode=JPEG_MODE,
-                      y4m_mode=Y4M_MODE, redact=None, draw=True):
+                      y4m_mode=Y4M_MODE, redact=None, draw=True, track=None):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
         (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
         ends in the device JPEG encoder at ``quality`` in ``jpeg_mode`` = (subsampling, huffman), "y4m" for one that ends in the YUV4MPEG2
         encoder in ``y4m_mode`` = (chroma, range).  ``redact`` = (classes, mode, size, margin) (``redact_option``): an annotating pass that
-        hides those classes' boxes in each frame (ops.redact_u8) in front of the drawing step; ``draw`` False: one that draws nothing."""
+        hides those classes' boxes in each frame (ops.redact_u8) in front of the drawing step; ``draw`` False: one that draws nothing.
+        ``track`` = (thr, hold, grow): an annotating pass that runs the engine's tracker over its frames (ops.track_update)."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -654,7 +717,7 @@ class DetectionEntry:
             s = _Slot()
             s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
             s.encode, s.quality, s.jpeg_mode, s.y4m_mode = encode, quality, jpeg_mode, y4m_mode
-            s.redact, s.nodraw = redact, (None if draw else True)
+            s.redact, s.nodraw, s.track = redact, (None if draw else True), track
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -695,6 +758,9 @@ class DetectionEntry:
                 shape = (B, s.first_copy) if s.encode == JPEG_ENCODE else tuple(s.png_dev.shape)
                 s._png_raw = self._pinned.take(shape[0] * shape[1], zero=True)
                 s.png_pin = s._png_raw[:shape[0] * shape[1]].view(shape)
+            if s.track:
+                s._track_raw = self._pinned.take(4 * s.track_out.numel())
+                s.track_pin = s._track_raw.view(torch.int32)[:s.track_out.numel()].view(tuple(s.track_out.shape))
             s.event = torch.cuda.Event()
             s.nbytes = max(int(torch.cuda.memory_reserved() - reserved0), int(s.io_dev.numel() + s.x_f32.numel() * 4))
             stamp("read-back buffers")
@@ -877,7 +943,7 @@ class DetectionEntry:
         return self.submit_batch([image], [resize_ratio], det_threshold, [self.host_pixels(image) if pixels is None else pixels], batch=1)
 
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
-                     subsampling=None, huffman=None, y4m=None, redact=None, draw=True):
+                     subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -897,9 +963,21 @@ class DetectionEntry:
         mode, size, margin) appended): classes a tuple of class names or "all", mode "pixelate" / "blur" / "fill", size the cell side /
         blur radius (None: the mode's default; 0 for "fill"), margin >= 0 pixels around each box.  Every box of those classes is hidden in
         the frame (ops.redact_u8, DESIGN §8 "Redaction rule") before the drawing step, so in front of every ``encode``.  ``draw`` = False
-        (annotating passes only; key tagged ("nodraw",)): nothing is drawn.  Without the two, every key is what it was."""
+        (annotating passes only; key tagged ("nodraw",)): nothing is drawn.  Without the two, every key is what it was.
+        ``track`` = (thr, hold, grow) (annotating passes only; a pass of its own, the annotating key with ("track", thr, hold, grow)
+        appended; None in a place: 30, 8, 0): the engine's tracker (DESIGN §8 "Tracking rule", ops.track_update) runs over the pass's
+        frames in order, behind the post-process: every live row of a tracked class gets a stable id, which the label shows as
+        ``cls#id``, and a track the detector has lost is HELD for ``hold`` frames, its box grown by ``grow`` pixels per frame -- held
+        boxes are redacted (with ``redact``) and never drawn.  ``collect_batch``'s dets then carry "track_id" (0: untracked), and the
+        held rows follow the live ones as dets with "held" = their age.  Passes with ``track`` replay on ONE stream of the engine
+        (``track_stream``) in submit order, whatever ``in_flight`` is: submit the frames in the order they were shot, and call
+        ``track_reset()`` between two sequences.  A short group's padding frames do not count."""
         if (redact is not None or not draw) and not annotate:
             raise FrcnnError("submit_batch: redact= and draw=False change the frame an ANNOTATING pass returns: pass annotate=True")
+        if track is not None:
+            if not annotate:
+                raise FrcnnError("submit_batch: track= tracks the detections of an ANNOTATING pass: pass annotate=True")
+            track = self.track_option(track)
         if redact is not None:
             redact = self.redact_option(redact)
         y4m_mode = Y4M_MODE
@@ -950,6 +1028,8 @@ class DetectionEntry:
                 key = key + ("redact",) + redact
             if not draw:
                 key = key + ("nodraw",)
+            if track is not None:
+                key = key + ("track",) + track
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -958,7 +1038,7 @@ class DetectionEntry:
             s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
         else:
             s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality,
-                                                                     jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode, redact, draw))
+                                                                     jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode, redact, draw, track))
         metas, files = [], []
         for i in range(B):
             j = i if i < len(images) else 0
@@ -969,8 +1049,12 @@ class DetectionEntry:
                 metas.append(self._canvas_frame(s, i, pixels[j]))
             elif not isinstance(pixels[j][0], JpegFile):
                 np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
-        st = self._streams[self._seq % self.in_flight]
-        self._seq += 1
+        if s.track:
+            s.n_frames_host[0] = len(images)                        # goes up with the frames: the padding does not advance the tracker
+            st = self.track_stream
+        else:
+            st = self._streams[self._seq % self.in_flight]
+            self._seq += 1
         with torch.cuda.stream(st):
             if s.ready is not None:
                 st.wait_event(s.ready)                             # (the first replay of a fresh pass: behind its warm-up)
@@ -995,6 +1079,8 @@ class DetectionEntry:
                     s.png_pin[i].copy_(s.png_dev[i], non_blocking=True)
                 elif s.annotate:
                     s.frame_io[i][1].copy_(s.frame_io[i][0], non_blocking=True)
+                if s.track:
+                    s.track_pin[i].copy_(s.track_out[i], non_blocking=True)
             s.event.record(st)
         s.busy = True
         return Ticket(s, list(images))
@@ -1153,6 +1239,14 @@ class DetectionEntry:
                 cls = packed[4 + 4 * rows:4 + 4 * rows + nd].copy()
                 prob = packed[4 + 5 * rows:4 + 5 * rows + nd].view(np.float32).copy()
                 dets = [{"bbox": bbox[k], "cls_name": rev[int(cls[k])], "prob": prob[k]} for k in range(nd)]
+                if s.track:                                         # the live rows' ids, then the held rows
+                    n_rows, n_live, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(s.track_pin[i].numpy())
+                    if int(n_live[0]) != nd:
+                        raise FrcnnError("tracker: %d live rows for %d detections" % (int(n_live[0]), nd))
+                    for k in range(nd):
+                        dets[k]["track_id"] = int(t_id[k])
+                    dets += [{"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(),
+                              "track_id": int(t_id[k]), "held": int(t_age[k])} for k in range(nd, int(n_rows[0]))]
                 if s.encode == JPEG_ENCODE:
                     row = s.png_pin[i].numpy()
                     n = int(row[0:4].view(np.int32)[0])

@@ -1121,17 +1121,30 @@ def annotate_tables(class_names, skip=ANNOTATE_SKIP):
             "glyphs": torch.from_numpy(np.ascontiguousarray(GLYPHS)).cuda()}
 
 
-def annotate_u8(frame, det_packed, tables):
+def annotate_u8(frame, det_packed, tables, ids=None, tracked=False):
     """Draw the detections of ``det_packed`` (the post-process's packed buffer, device) into ``frame`` -- an (h, w, 3) uint8 device
     tensor, edited in place -- as the reference's annotate_video.py:32-41 does: a 3-pixel (0,255,0) box and the label
     "{} {:6.2f}" under it (frcnn_annotate_u8; the drawing rule is DESIGN §8's).  ``tables``: ``annotate_tables``.  Reads
-    n_dets from device memory: the call can be captured in a graph."""
+    n_dets from device memory: the call can be captured in a graph.
+    ``ids``: an int32 device tensor, one track id per row of ``det_packed`` -- a row whose id is > 0 is labelled "{}#{} {:6.2f}" with the
+    id behind the class name (frcnn_annotate_ids_u8); None: the call and its output are what they were.
+    ``tracked`` True: ``det_packed`` is one tracked buffer of ``track_update`` instead; its LIVE rows are drawn, with their ids."""
     _require_gpu()
     assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
     assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.is_contiguous()
-    n_dets, det_bbox, det_cls, det_prob, _ = split_detections(det_packed)
     labels = tables["labels"]
-    _lib.call("frcnn_annotate_u8", _p(frame), int(frame.shape[0]), int(frame.shape[1]), _p(det_bbox), _p(det_cls), _p(det_prob),
+    if tracked:
+        assert ids is None and det_packed.dim() == 1
+        _, n_dets, _, _, det_bbox, det_cls, det_prob, ids, _ = split_tracked(det_packed)
+    else:
+        n_dets, det_bbox, det_cls, det_prob, _ = split_detections(det_packed)
+    if ids is None:
+        _lib.call("frcnn_annotate_u8", _p(frame), int(frame.shape[0]), int(frame.shape[1]), _p(det_bbox), _p(det_cls), _p(det_prob),
+                  _p(n_dets), int(det_cls.numel()), _p(tables["drawable"]), _p(labels), int(labels.shape[1]), int(labels.shape[0]),
+                  _p(tables["glyphs"]), _stream())
+        return frame
+    assert ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous() and ids.numel() == det_cls.numel()
+    _lib.call("frcnn_annotate_ids_u8", _p(frame), int(frame.shape[0]), int(frame.shape[1]), _p(det_bbox), _p(det_cls), _p(det_prob), _p(ids),
               _p(n_dets), int(det_cls.numel()), _p(tables["drawable"]), _p(labels), int(labels.shape[1]), int(labels.shape[0]),
               _p(tables["glyphs"]), _stream())
     return frame
@@ -1185,13 +1198,14 @@ def redact_ws_bytes(h, w, mode="pixelate", size=None):
     return int(_lib.load().frcnn_redact_ws_bytes(int(h), int(w), _lib.REDACT_MODES[mode], redact_size(mode, size)))
 
 
-def redact_u8(frame, det_packed, table, mode="pixelate", size=None, margin=0, workspace=None):
+def redact_u8(frame, det_packed, table, mode="pixelate", size=None, margin=0, workspace=None, tracked=False):
     """Hide the detections of ``det_packed`` (the post-process's packed buffer, device) whose class is set in ``table``
     (``redact_table``) in ``frame`` -- an (h, w, 3) uint8 device tensor, edited in place and returned: every pixel inside a box grown by
     ``margin`` and clipped to the frame becomes 0 ("fill"), the mean of its cell of a ``size`` x ``size`` grid ("pixelate") or a box blur
     of radius ``size`` ("blur") of the SOURCE frame (frcnn_redact_u8; the rule is DESIGN §8's).  ``size`` None: the mode's default.
     ``workspace``: a u8 device tensor of at least ``redact_ws_bytes`` bytes; None allocates one.  Reads n_dets from device memory: the
-    call can be captured in a graph."""
+    call can be captured in a graph.  ``tracked`` True: ``det_packed`` is one tracked buffer of ``track_update`` instead, and the boxes
+    are all its rows, the held ones included."""
     _require_gpu()
     assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
     assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.is_contiguous()
@@ -1203,10 +1217,113 @@ def redact_u8(frame, det_packed, table, mode="pixelate", size=None, margin=0, wo
     if workspace is None:
         workspace = _ws(_lib.load().frcnn_redact_ws_bytes(h, w, _lib.REDACT_MODES[mode], size))
     assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
-    n_dets, det_bbox, det_cls, _, _ = split_detections(det_packed)
+    if tracked:                                         # (every row up to n_rows: the held ones too)
+        assert det_packed.dim() == 1
+        n_dets, _, _, _, det_bbox, det_cls, _, _, _ = split_tracked(det_packed)
+    else:
+        n_dets, det_bbox, det_cls, _, _ = split_detections(det_packed)
     _lib.call("frcnn_redact_u8", _p(frame), h, w, _p(det_bbox), _p(det_cls), _p(n_dets), int(det_cls.numel()), _p(table),
               int(table.numel()), _lib.REDACT_MODES[mode], size, int(margin), _p(workspace), int(workspace.numel()), _stream())
     return frame
+
+
+# ----------------------------------------------------------------------------- tracking
+TRACK_MAX = _lib.TRACK_MAX                      # slots of a state, at most
+TRACK_DEFAULTS = _lib.TRACK_DEFAULTS            # (thr, hold, grow)
+
+
+def track_option(thr=None, hold=None, grow=None):
+    """(host only) (thr, hold, grow) checked, None replaced by the default (30, 8, 0): thr the IoU threshold in percent, 1..100; hold the
+    frames a lost track is kept, 0..255; grow the pixels a held box grows by per frame of age, 0..64.  ValueError with the reason."""
+    out = []
+    for name, v, default, (lo, hi) in zip(("thr", "hold", "grow"), (thr, hold, grow), TRACK_DEFAULTS, _lib.TRACK_RANGES):
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError("track %s=%r: an integer in %d..%d" % (name, v, lo, hi))
+        out.append(int(v))
+    return tuple(out)
+
+
+def track_state(capacity=64):
+    """An empty tracker state of ``capacity`` slots (1..TRACK_MAX): a zeroed int32 device tensor of frcnn_track_state_bytes / 4 words,
+    [n_slots, ids issued, overflow, frames | id | cls | bbox | prob | age] (include/ext/frcnn_hip_track.h)."""
+    _require_gpu()
+    n = int(_lib.load().frcnn_track_state_bytes(int(capacity)))
+    if n == 0:
+        raise _lib.FrcnnError("track_state: capacity=%r not in [1, %d]" % (capacity, TRACK_MAX))
+    return torch.zeros(n // 4, dtype=torch.int32, device="cuda")
+
+
+def track_capacity(state):
+    return (int(state.numel()) - 4) // 8
+
+
+def track_reset(state):
+    """Empty the state (on the current stream): no tracks, the next id is 1, overflow and the frame count 0."""
+    state.zero_()
+    return state
+
+
+def track_table(class_names, classes):
+    """The per-class byte table ``track_update`` reads: device u8 [C], 1 where ``class_names[i]`` is tracked.  ``classes``: names, or
+    "all" for every class but the background (``redact_class_list``'s reading)."""
+    _require_gpu()
+    chosen = set(redact_class_list(class_names, classes))
+    return torch.from_numpy(np.array([str(n) in chosen for n in class_names], dtype=np.uint8)).cuda()
+
+
+def track_rows(det_packed):
+    """Rows of a ``det_packed`` buffer (or of each of a batch of them)."""
+    one = det_packed[0] if isinstance(det_packed, (list, tuple)) or det_packed.dim() == 2 else det_packed
+    return (int(one.numel()) - 4) // 7
+
+
+def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, out=None):
+    """The tracking rule (DESIGN §8 "Tracking rule", frcnn_track_update) over the frames of ``det_packed`` IN ORDER, in one launch:
+    ``state`` (``track_state``) is read and advanced, and frame f's tracked buffer lands in ``out[f]`` -- -> ``out``, a (B, 4 + 8R) int32
+    tensor, R = the packed buffers' rows + the state's capacity (``split_tracked`` cuts it up; ``redact_u8`` and ``annotate_u8`` take
+    ``out[f]`` in a ``det_packed``'s place with ``tracked=True``).  ``det_packed``: one packed buffer of the post-process (B = 1), a
+    (B, words) tensor, or a list of B buffers of one size -- used where they lie when they are evenly spaced in memory (the stride is an
+    argument of the call), else gathered with one copy.  ``n_frames``: an int32 device tensor whose first word says how many of the B
+    frames are real; the rest is a short pass's padding and leaves the state alone.  ``table``: ``track_table``.  (h, w): the frame's size.
+    Reads *n_dets and *n_frames on the device: the call can be captured in a graph."""
+    _require_gpu()
+    if isinstance(det_packed, (list, tuple)):
+        bufs = list(det_packed)
+        assert bufs and all(b.is_cuda and b.dtype == torch.int32 and b.dim() == 1 and b.is_contiguous() and b.numel() == bufs[0].numel() for b in bufs)
+        B, words = len(bufs), int(bufs[0].numel())
+        step = (bufs[1].data_ptr() - bufs[0].data_ptr()) if B > 1 else 4 * words
+        if B == 1 or (step % 4 == 0 and step >= 4 * words and all(bufs[i].data_ptr() - bufs[0].data_ptr() == i * step for i in range(B))):
+            base, stride = bufs[0], step // 4
+        else:
+            base, stride = torch.stack(bufs), words
+    else:
+        assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.is_contiguous() and det_packed.dim() in (1, 2)
+        base = det_packed
+        B, words = (1, int(base.numel())) if base.dim() == 1 else (int(base.shape[0]), int(base.shape[1]))
+        stride = words
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    cap, rows = track_capacity(state), (words - 4) // 7
+    R = rows + cap
+    if out is None:
+        out = torch.empty((B, 4 + 8 * R), dtype=torch.int32, device="cuda")
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (B, 4 + 8 * R)
+    _lib.call("frcnn_track_update", _p(state), cap, _p(base), int(stride), B, _p(n_frames), rows, _p(table), int(table.numel()),
+              int(thr), int(hold), int(grow), int(h), int(w), _p(out), 4 + 8 * R, _stream())
+    return out
+
+
+def split_tracked(buf):
+    """Views (n_rows, n_live, next_id, overflow, bbox, cls, prob, id, age) into ONE tracked buffer (device tensor or its host copy,
+    torch or numpy), as ``split_detections`` cuts up a ``det_packed``: the four counts are one-word views, bbox is (R, 4), prob float32."""
+    R = (int(buf.shape[0]) - 4) // 8
+    prob = buf[4 + 5 * R:4 + 6 * R]
+    prob = prob.view(torch.float32) if isinstance(prob, torch.Tensor) else prob.view(np.float32)
+    bbox = buf[4:4 + 4 * R]
+    bbox = bbox.view(R, 4) if isinstance(bbox, torch.Tensor) else bbox.reshape(R, 4)
+    return (buf[0:1], buf[1:2], buf[2:3], buf[3:4], bbox, buf[4 + 4 * R:4 + 5 * R], prob, buf[4 + 6 * R:4 + 7 * R], buf[4 + 7 * R:4 + 8 * R])
 
 
 PNG_BAND_ROWS = 1       # scanlines per IDAT chunk of the device encoder (frcnn_png_band_rows(); tests/test_png_cpu.py holds the two together)

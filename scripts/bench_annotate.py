@@ -23,6 +23,10 @@ encoder) and PNG files to PNG files (host codecs), alternating in one session.
 (radius 12, the default), alternating in one session -- through in-memory annotating passes and through annotate_images from PNG files
 to PNG files with the device encoder -- and reports the frames/s of both and their ratio.
 
+``--track`` runs the tracker's cost instead (``run_track``): the ``--redact`` leg's frames and redaction without and with ``--track``
+(IoU 30 %, hold 8, grow 0, the defaults), alternating in one session through in-memory annotating passes; tracking passes replay on one
+stream of the engine, so the figure includes what that ordering costs.
+
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
 """
@@ -282,6 +286,49 @@ def run_redact(name, cfg, n_frames, reps, content="noise"):
     return res
 
 
+TRACK_LEG = (30, 8, 0)                                   # --track with its defaults
+
+
+def run_track(name, cfg, n_frames, reps, content="noise"):
+    """``--track``: what tracking costs on top of the redaction.  One pair of legs in ONE session, alternating inside every repetition:
+    the ``--redact`` leg's frames through in-memory annotating passes with ``redact=REDACT_LEG``, without and with ``track=TRACK_LEG``
+    (the tracker is reset in front of every tracked run).  Reports frames/s of both, with / without, and what the tracker saw."""
+    import numpy as np
+    from faster_rcnn_amd import entry, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+
+    def tracked():
+        eng.track_reset()
+        return annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, track=TRACK_LEG)
+
+    legs = {"redact": lambda: annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG), "redact_track": tracked}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    import torch
+    torch.cuda.synchronize()
+    state = eng.track_state().cpu().numpy()
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact": ["all", "blur", 12, 0], "track": list(TRACK_LEG), "images_per_pass": eng.batch, "in_flight": eng.in_flight,
+           "tracker": {"live_slots": int(state[0]), "ids_issued": int(state[1]), "overflow": int(state[2]), "frames": int(state[3])}}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["track_over_plain"] = round(statistics.median(times["redact"]) / statistics.median(times["redact_track"]), 3)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--frames", type=int, default=256)
@@ -295,6 +342,8 @@ def main():
                                                        "to PNG files (host codecs), alternating in one session")
     ap.add_argument("--redact", action="store_true", help="instead of the legs above: the same frames with and without --redact all "
                                                           "--redact_mode blur, alternating in one session (passes in memory, and files to files)")
+    ap.add_argument("--track", action="store_true", help="instead of the legs above: the --redact leg's frames and redaction without and with "
+                                                         "--track (IoU 30, hold 8), alternating in one session (passes in memory)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -303,6 +352,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.track:
+            out[name] = run_track(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.redact:
             out[name] = run_redact(name, PAIRS[name], args.frames, args.reps, args.content)
