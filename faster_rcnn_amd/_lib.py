@@ -369,6 +369,7 @@ class Y4mBatchItem(ctypes.Structure):
 
 REDACT_VERSION = 1              # include/ext/frcnn_hip_redact.h FRCNN_REDACT_VERSION
 REDACT_MAX_ROWS = 512           # ... FRCNN_REDACT_MAX_ROWS
+REDACT_MAX_SIDE = 32768         # ... FRCNN_REDACT_MAX_SIDE
 REDACT_SIGNATURES = {
     "frcnn_redact_version": (I, []),
     "frcnn_redact_ws_bytes": (c_size_t, [I, I, I, I]),
@@ -390,6 +391,16 @@ TRACK_SIGNATURES = {
 # (thr, hold, grow): the defaults, and the range of each (FRCNN_TRACK_MAX_HOLD, FRCNN_TRACK_MAX_GROW)
 TRACK_DEFAULTS = (30, 8, 0)
 TRACK_RANGES = ((1, 100), (0, 255), (0, 64))
+
+TRACK_MOTION_VERSION = 1        # include/ext/frcnn_hip_track_motion.h FRCNN_TRACK_MOTION_VERSION
+TRACK_MOTION_SIGNATURES = {
+    "frcnn_track_motion_version": (I, []),
+    "frcnn_track_motion_state_bytes": (c_size_t, [I, I]),
+    "frcnn_track_update_motion": (I, [P, I, P, P, ctypes.c_longlong, P, ctypes.c_longlong, I, P, I, P, I, I, I, I, I, I, I, P,
+                                      ctypes.c_longlong, P]),
+}
+# the block match's search radius: (smallest, largest, the default) (FRCNN_TRACK_MOTION_MIN_RADIUS / _MAX_RADIUS)
+TRACK_MOTION_RADIUS = (1, 16, 8)
 
 
 class ConvDesc(ctypes.Structure):
@@ -508,6 +519,13 @@ def load():
     if lib.frcnn_track_version() != TRACK_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_version()} of the tracking extension, this binding "
                          f"{TRACK_VERSION} (include/ext/frcnn_hip_track.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in TRACK_MOTION_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_track_motion_version() != TRACK_MOTION_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_motion_version()} of the tracker's motion extension, this binding "
+                         f"{TRACK_MOTION_VERSION} (include/ext/frcnn_hip_track_motion.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

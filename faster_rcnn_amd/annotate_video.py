@@ -58,6 +58,11 @@ for N frames (default 8), its box growing by ``grow`` pixels per frame (default 
 redaction does not flicker off when the detector misses a frame) and never drawn.  Frames are tracked in input order; the tracked classes
 are the drawable ones and the redacted ones.  ``--tracks_out PATH`` writes one MOTChallenge line per live tracked row
 (``frame,id,left,top,width,height,prob,cls,-1,-1``, frames counted from 1).  The printed dets then carry "track_id".
+``track_motion=R`` (``--track_motion [R]``, with ``--track``; 1..16, 8 when bare) moves every track's box with the pixels under it between
+consecutive frames (ops.track_update_motion, csrc/track_motion.hip; DESIGN §8 "Motion rule": an integer block match of at most R pixels
+either way on a 32 x 32 sample grid of the box, taken only when it gains a grey level per sample): a held box follows its object instead
+of standing still, and a fast object is matched where it now is.  The printed lines and ``--tracks_out`` keep their form: held rows are
+still not written.
 """
 import collections
 import os
@@ -221,6 +226,7 @@ def _pack_dets(dets, class_mapping):
 _EAGER_TABLES = {}
 _EAGER_REDACT_TABLES = {}
 _EAGER_TRACKERS = {}                                      # class mapping -> [state, {redact classes: table}, the one-frame count word]
+_EAGER_MOTION = {}                                        # (class mapping, h, w) -> that tracker's motion state for frames of the size
 
 
 def _names_by_index(class_mapping):
@@ -237,6 +243,15 @@ def _eager_tracker(class_mapping):
     return t
 
 
+def _eager_motion_state(class_mapping, h, w):
+    """The eager path's motion state (ops.track_motion_state) of this class mapping's tracker for (h, w) frames, made on first use."""
+    key = (tuple(sorted(class_mapping.items())), int(h), int(w))
+    m = _EAGER_MOTION.get(key)
+    if m is None:
+        m = _EAGER_MOTION[key] = ops.track_motion_state(h, w)
+    return m
+
+
 def _eager_track_table(tracker, class_mapping, redact_classes):
     table = tracker[1].get(redact_classes)
     if table is None:
@@ -248,13 +263,16 @@ def _eager_track_table(tracker, class_mapping, redact_classes):
     return table
 
 
-def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None):
+def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None):
     """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place.
     ``redact`` = (classes, mode, size, margin): one ops.redact_u8 in front of it; ``draw`` False: no drawing.
     ``track`` = (thr, hold, grow): one ops.track_update (one frame) in front of both, on this class mapping's eager tracker state
     (``reset_tracks`` empties it); ``dets`` is edited in place as ``collect_batch`` returns it: "track_id" on every det, the held rows
-    appended with "held"."""
+    appended with "held".  ``track_motion`` = R: ops.track_update_motion in its place, with the frame as it came and this class mapping's
+    motion state for the frame's size."""
     import torch
+    if track_motion is not None and track is None:
+        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     key = tuple(sorted(class_mapping.items()))
     if track is not None or (dets and (draw or redact is not None)):      # (nothing to draw or hide: the frame stays as it is)
         dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
@@ -265,8 +283,13 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None):
             classes = classes if classes == "all" else tuple(classes)
         if track is not None:
             tracker = _eager_tracker(class_mapping)
-            rows = ops.track_update(tracker[0], packed, tracker[2], _eager_track_table(tracker, class_mapping, classes),
-                                    frame.shape[0], frame.shape[1], *track)[0]
+            t_table = _eager_track_table(tracker, class_mapping, classes)
+            if track_motion is not None:                            # (in front of the redaction: ``dev`` is still the frame as it came)
+                rows = ops.track_update_motion(tracker[0], _eager_motion_state(class_mapping, frame.shape[0], frame.shape[1]), dev.view(-1), 0,
+                                               packed, tracker[2], t_table, frame.shape[0], frame.shape[1], *track,
+                                               ops.track_motion_radius(track_motion))[0]
+            else:
+                rows = ops.track_update(tracker[0], packed, tracker[2], t_table, frame.shape[0], frame.shape[1], *track)[0]
             n_rows, _, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(rows.cpu().numpy())
             rev = {v: k for k, v in class_mapping.items()}
             for k, d in enumerate(dets):
@@ -330,6 +353,20 @@ def track_from_args(args):
         raise ValueError("--track_iou / --track_hold / --track_grow: %s" % e) from None
 
 
+def track_motion_from_args(args):
+    """(host only) The motion step the command line asks for -> the search radius as ``submit_batch(track_motion=...)`` takes it (8 for
+    a bare ``--track_motion``), or None without the flag.  ValueError, with the reason, for ``--track_motion`` without ``--track`` and for
+    a radius outside 1..16."""
+    if args.track_motion is None:
+        return None
+    if not args.track:
+        raise ValueError("--track_motion=%s is a setting of the tracker: it needs --track" % args.track_motion)
+    try:
+        return ops.track_motion_radius(args.track_motion)
+    except ValueError as e:
+        raise ValueError("--track_motion: %s" % e) from None
+
+
 def mot_lines(frame_no, dets, class_mapping):
     """The MOTChallenge lines of one frame: ``frame,id,left,top,width,height,prob,cls,-1,-1`` per LIVE tracked det ("track_id" > 0, no
     "held"), in row order; left / top the smaller corner, width / height the corners' distance, prob with six decimals, cls the index."""
@@ -355,6 +392,10 @@ def reset_tracks(training_manager, detector, in_flight=1):
         eng.track_reset()
     else:
         ops.track_reset(_eager_tracker(training_manager.class_mapping)[0])
+        key = tuple(sorted(training_manager.class_mapping.items()))
+        for k, mstate in _EAGER_MOTION.items():
+            if k[0] == key:
+                ops.track_motion_reset(mstate)
 
 
 def _print_drawn(dets, width, height):
@@ -364,23 +405,27 @@ def _print_drawn(dets, width, height):
 
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
-                        frame_no=1):
+                        frame_no=1, track_motion=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
-    ``tracks_out``: a text file that receives the frame's MOT lines under the number ``frame_no``."""
+    ``tracks_out``: a text file that receives the frame's MOT lines under the number ``frame_no``.  ``track_motion`` = R (with
+    ``track``): the tracks' boxes are first moved with the pixels under them, at most R pixels either way (DESIGN §8 "Motion rule")."""
+    if track_motion is not None and track is None:
+        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
+    motion = {} if track_motion is None else {"track_motion": track_motion}
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1)
     if eng is not None:
         pixels = eng.host_pixels(resized_imgs[0])
         num_rois, dets, out = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], DET_THRESHOLD, [pixels],
                                                                  batch=1, annotate=True, redact=redact, draw=draw,
-                                                                 **({} if track is None else {"track": track})))[0]
+                                                                 **({} if track is None else {"track": track}), **motion))[0]
         print("num rois: {}".format(num_rois))
         frame[...] = out
     else:
         dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=DET_THRESHOLD)
-        draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track)
+        draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, **motion)
     if track is not None:
         _write_tracks(tracks_out, frame_no, dets, training_manager.class_mapping)
     _print_drawn(dets, img.width, img.height)
@@ -560,14 +605,17 @@ def directory_frames(input_dir, image_filenames, jpeg_decoder=None, png_decoder=
 
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
-                    redact=None, draw=True, track=None, tracks_out=None):
+                    redact=None, draw=True, track=None, tracks_out=None, track_motion=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion``: as ``annotate_images``."""
     from concurrent.futures import ThreadPoolExecutor
+    if track_motion is not None and track is None:
+        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
+    motion = {} if track_motion is None else {"track_motion": track_motion}
     to_video = isinstance(writer_or_out_dir, y4m.Y4mWriter)
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
     dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
@@ -603,7 +651,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
         kwargs = dict(kwargs, redact=redact, draw=draw)
     mapping = training_manager.class_mapping
     if track is not None:                                 # a new sequence; its frames are submitted in stream order, as every stream's are
-        kwargs = dict(kwargs, track=track)
+        kwargs = dict(kwargs, track=track, **motion)
         reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
 
     if eng is None:                                       # eager path / foreign models: one frame at a time, converted on the device
@@ -617,7 +665,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                 frame = np.ascontiguousarray(src.raw)
             img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
             out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=redact, draw=draw, track=track,
-                                      tracks_out=tracks_out, frame_no=pos + 1)
+                                      tracks_out=tracks_out, frame_no=pos + 1, **motion)
             if to_video:
                 writer.write(ops.y4m_encode_u8(torch.from_numpy(out).cuda(), writer.chroma, writer.range, bgr=True).cpu().numpy().tobytes())
             elif on_device:
@@ -712,7 +760,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
-                    jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None):
+                    jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -730,7 +778,12 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     its pass, in front of the drawing step and of whichever encoder writes the frame; None: nothing is.  ``draw`` False: no boxes, no labels.
     ``track``: (thr, hold, grow) as ``track_from_args`` returns it -- the list is ONE sequence in list order: the tracker's state is reset
     at the start, every tracked detection is labelled ``cls#id`` and lost tracks are held (and redacted) for ``hold`` frames; None: no
-    tracking.  ``tracks_out``: a text file that receives the MOT lines, frame i of the list under the number i + 1."""
+    tracking.  ``tracks_out``: a text file that receives the MOT lines, frame i of the list under the number i + 1.
+    ``track_motion``: the search radius as ``track_motion_from_args`` returns it (with ``track``) -- every track's box is moved with the
+    pixels under it from frame to frame, so a held box follows its object; None: held boxes stand still."""
+    if track_motion is not None and track is None:
+        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
+    motion = {} if track_motion is None else {"track_motion": track_motion}
     from concurrent.futures import ThreadPoolExecutor
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
@@ -766,7 +819,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             frame = np.ascontiguousarray(_read_rgb(path)[:, :, ::-1])
             img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
             out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=redact, draw=draw, track=track,
-                                      tracks_out=tracks_out, frame_no=frame_no)
+                                      tracks_out=tracks_out, frame_no=frame_no, **motion)
             if on_device:
                 import torch
                 dev = torch.from_numpy(out).cuda()
@@ -785,7 +838,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     n, B = len(paths), eng.batch
     edit = dict(redact=redact, draw=draw) if redact is not None or not draw else {}      # (else the passes without the arguments)
     if track is not None:                                 # (the groups below are submitted in list order, as tracking needs them)
-        edit = dict(edit, track=track)
+        edit = dict(edit, track=track, **motion)
     decode = ThreadPoolExecutor(max_workers=max(1, DECODE_THREADS))
     write = ThreadPoolExecutor(max_workers=max(1, WRITE_THREADS))
     ahead = 2 * eng.in_flight * B
@@ -918,6 +971,9 @@ def build_parser():
                    help="frames a lost track is held, 0..255 (default 8; 0: ids only; needs --track)")
     p.add_argument("--track_grow", dest="track_grow", type=int, default=None, metavar="N",
                    help="pixels a held box grows by on every side per frame held, 0..64 (default 0; needs --track)")
+    p.add_argument("--track_motion", dest="track_motion", type=int, nargs="?", const=ops.TRACK_MOTION_RADIUS[2], default=None, metavar="R",
+                   help="move every track's box with the pixels under it from frame to frame (a block match of at most R pixels either "
+                        "way, 1..16, default 8), so a held box follows its object (needs --track)")
     p.add_argument("--tracks_out", dest="tracks_out", default=None, metavar="PATH",
                    help="write the tracks as MOTChallenge lines frame,id,left,top,width,height,prob,cls,-1,-1 (needs --track)")
     return p
@@ -980,7 +1036,10 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     class_mapping = KITTI_CLASS_MAPPING if args.kitti else VOC_CLASS_MAPPING
     redact, draw = redact_from_args(args, class_mapping), not args.no_draw                                  # (before any model is loaded)
     track = track_from_args(args)
+    track_motion = track_motion_from_args(args)
     tracking = {} if track is None else {"track": track, "tracks_out": stack.enter_context(open(args.tracks_out, "w")) if args.tracks_out else None}
+    if track_motion is not None:
+        tracking["track_motion"] = track_motion
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "../../include/ext/frcnn_hip_redact.h"
 #include "../../include/ext/frcnn_hip_track.h"
+#include "track.h"
 
 namespace frcnn {
 
@@ -54,17 +55,20 @@ __device__ int block_scan(int v, int* s_w, int* total) {
     return base + inc - v;
 }
 
-__global__ void __launch_bounds__(TR_THREADS) k_track_update(int32_t* state, int cap, const int32_t* det, long long det_stride, int frames,
-                                                               const int32_t* n_frames, int max_rows, const uint8_t* tracked,
-                                                               int num_classes, int thr, int hold, int grow, int h, int w, int32_t* out,
-                                                               long long out_stride) {
+// ``det`` and ``out`` are those of frame ``first`` of a call of ``total`` frames, and the launch walks ``frames`` of them: a frame whose index
+// in the CALL is at or behind *n_frames is padding (frcnn_track_update walks a whole call, first = 0 and frames = total; the motion
+// extension one frame per launch, with the block match in between).
+__global__ void __launch_bounds__(TR_THREADS) k_track_update(int32_t* state, int cap, const int32_t* det, long long det_stride, int first,
+                                                               int frames, int total, const int32_t* n_frames, int max_rows,
+                                                               const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h,
+                                                               int w, int32_t* out, long long out_stride) {
     __shared__ int s_id[FRCNN_TRACK_MAX], s_cls[FRCNN_TRACK_MAX], s_prob[FRCNN_TRACK_MAX], s_age[FRCNN_TRACK_MAX], s_hit[FRCNN_TRACK_MAX];
     __shared__ int s_box[FRCNN_TRACK_MAX][4];
     __shared__ long long s_ri[2][TR_WAVES], s_ru[2][TR_WAVES];
     __shared__ int s_rr[2][TR_WAVES];
     __shared__ int s_w[TR_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nf = min(max(*n_frames, 0), frames);
+    const int nf = min(max(*n_frames, 0), total) - first;                   // real frames from this launch's first one on
     const int R = max_rows + cap;
     int n_slots = min(max(state[0], 0), cap), issued = state[1], overflow = state[2], seen = state[3];
     if (tid < cap) {
@@ -223,6 +227,36 @@ __global__ void __launch_bounds__(TR_THREADS) k_track_update(int32_t* state, int
     }
 }
 
+int track_check(const char* who, const int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int frames,
+                const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
+                const int32_t* out, long long out_stride) {
+    if (!state || !det_packed || !n_frames || !tracked || !out) return fail(FRCNN_E_ARG, "%s: null pointer", who);
+    if (capacity < 1 || capacity > FRCNN_TRACK_MAX) return fail(FRCNN_E_ARG, "%s: capacity=%d not in [1, %d]", who, capacity, FRCNN_TRACK_MAX);
+    if (frames < 1 || frames > FRCNN_TRACK_MAX_FRAMES) return fail(FRCNN_E_ARG, "%s: frames=%d not in [1, %d]", who, frames, FRCNN_TRACK_MAX_FRAMES);
+    if (max_rows <= 0 || max_rows > FRCNN_REDACT_MAX_ROWS - capacity)
+        return fail(FRCNN_E_ARG, "%s: max_rows=%d: max_rows + capacity (%d) not in [2, %d]", who, max_rows, capacity, FRCNN_REDACT_MAX_ROWS);
+    const long long det_words = 4 + 7LL * max_rows, out_words = 4 + 8LL * (max_rows + capacity);
+    if (frames > 1 && det_stride < det_words)
+        return fail(FRCNN_E_ARG, "%s: det_stride=%lld words, a packed buffer of %d rows has %lld", who, det_stride, max_rows, det_words);
+    if (frames > 1 && out_stride < out_words)
+        return fail(FRCNN_E_ARG, "%s: out_stride=%lld words, a tracked buffer has %lld", who, out_stride, out_words);
+    if (num_classes <= 0 || num_classes > 256) return fail(FRCNN_E_ARG, "%s: num_classes=%d not in [1, 256]", who, num_classes);
+    if (thr < 1 || thr > 100) return fail(FRCNN_E_ARG, "%s: thr=%d not in [1, 100] (percent)", who, thr);
+    if (hold < 0 || hold > FRCNN_TRACK_MAX_HOLD) return fail(FRCNN_E_ARG, "%s: hold=%d not in [0, %d]", who, hold, FRCNN_TRACK_MAX_HOLD);
+    if (grow < 0 || grow > FRCNN_TRACK_MAX_GROW) return fail(FRCNN_E_ARG, "%s: grow=%d not in [0, %d]", who, grow, FRCNN_TRACK_MAX_GROW);
+    if (h < 1 || h > FRCNN_REDACT_MAX_SIDE || w < 1 || w > FRCNN_REDACT_MAX_SIDE)
+        return fail(FRCNN_E_ARG, "%s: frame %dx%d out of range (sides 1..%d)", who, h, w, FRCNN_REDACT_MAX_SIDE);
+    return FRCNN_OK;
+}
+
+void track_launch(int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int first, int frames, int total,
+                  const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
+                  int32_t* out, long long out_stride, hipStream_t stream) {
+    k_track_update<<<1, TR_THREADS, 0, stream>>>(state, capacity, det_packed + (long long)first * det_stride, det_stride, first, frames, total,
+                                                 n_frames, max_rows, tracked, num_classes, thr, hold, grow, h, w,
+                                                 out + (long long)first * out_stride, out_stride);
+}
+
 }  // namespace frcnn
 
 using namespace frcnn;
@@ -237,24 +271,10 @@ extern "C" size_t frcnn_track_state_bytes(int capacity) {
 extern "C" int frcnn_track_update(int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int frames,
                                   const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow,
                                   int h, int w, int32_t* out, long long out_stride, void* stream) {
-    if (!state || !det_packed || !n_frames || !tracked || !out) return fail(FRCNN_E_ARG, "track_update: null pointer");
-    if (capacity < 1 || capacity > FRCNN_TRACK_MAX) return fail(FRCNN_E_ARG, "track_update: capacity=%d not in [1, %d]", capacity, FRCNN_TRACK_MAX);
-    if (frames < 1 || frames > FRCNN_TRACK_MAX_FRAMES)
-        return fail(FRCNN_E_ARG, "track_update: frames=%d not in [1, %d]", frames, FRCNN_TRACK_MAX_FRAMES);
-    if (max_rows <= 0 || max_rows > FRCNN_REDACT_MAX_ROWS - capacity)
-        return fail(FRCNN_E_ARG, "track_update: max_rows=%d: max_rows + capacity (%d) not in [2, %d]", max_rows, capacity, FRCNN_REDACT_MAX_ROWS);
-    const long long det_words = 4 + 7LL * max_rows, out_words = 4 + 8LL * (max_rows + capacity);
-    if (frames > 1 && det_stride < det_words)
-        return fail(FRCNN_E_ARG, "track_update: det_stride=%lld words, a packed buffer of %d rows has %lld", det_stride, max_rows, det_words);
-    if (frames > 1 && out_stride < out_words)
-        return fail(FRCNN_E_ARG, "track_update: out_stride=%lld words, a tracked buffer has %lld", out_stride, out_words);
-    if (num_classes <= 0 || num_classes > 256) return fail(FRCNN_E_ARG, "track_update: num_classes=%d not in [1, 256]", num_classes);
-    if (thr < 1 || thr > 100) return fail(FRCNN_E_ARG, "track_update: thr=%d not in [1, 100] (percent)", thr);
-    if (hold < 0 || hold > FRCNN_TRACK_MAX_HOLD) return fail(FRCNN_E_ARG, "track_update: hold=%d not in [0, %d]", hold, FRCNN_TRACK_MAX_HOLD);
-    if (grow < 0 || grow > FRCNN_TRACK_MAX_GROW) return fail(FRCNN_E_ARG, "track_update: grow=%d not in [0, %d]", grow, FRCNN_TRACK_MAX_GROW);
-    if (h < 1 || h > FRCNN_REDACT_MAX_SIDE || w < 1 || w > FRCNN_REDACT_MAX_SIDE)
-        return fail(FRCNN_E_ARG, "track_update: frame %dx%d out of range (sides 1..%d)", h, w, FRCNN_REDACT_MAX_SIDE);
-    k_track_update<<<1, TR_THREADS, 0, as_stream(stream)>>>(state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked,
-                                                             num_classes, thr, hold, grow, h, w, out, out_stride);
+    const int bad = track_check("track_update", state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr,
+                                hold, grow, h, w, out, out_stride);
+    if (bad) return bad;
+    track_launch(state, capacity, det_packed, det_stride, 0, frames, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow, h, w, out,
+                 out_stride, as_stream(stream));
     return check_launch("track_update");
 }

@@ -303,7 +303,7 @@ class _Slot:
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
-                 "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev")
+                 "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion")
 
     def __init__(self):
         for name in self.__slots__:
@@ -450,6 +450,7 @@ class DetectionEntry:
         self._redact_tables = {}
         self._track_state = None                         # the engine's ONE tracker state (ops.track_state): its pointer is in the graphs
         self._track_tables = {}
+        self._track_motion_states = {}                   # (h, w) of the source frames -> ops.track_motion_state: their pointers are in the graphs
 
     def class_names(self):
         """This engine's class names by class index ("" for an index no class has)."""
@@ -513,6 +514,17 @@ class DetectionEntry:
         state = self.track_state()
         with torch.cuda.stream(self.track_stream):
             ops.track_reset(state)
+            for mstate in self._track_motion_states.values():       # ... and no frame is the one in front of the next
+                ops.track_motion_reset(mstate)
+
+    def track_motion_state(self, h, w):
+        """The engine's motion state for source frames of (h, w) (ops.track_motion_state), made on first use: the passes submitted with
+        ``track_motion=`` keep their last frame in it.  A sequence that changes its frame size has no reference on the first frame of
+        the new size: the header of the new size's state does not carry the tracker's frame count."""
+        m = self._track_motion_states.get((h, w))
+        if m is None:
+            m = self._track_motion_states[(h, w)] = ops.track_motion_state(h, w)
+        return m
 
     def track_table(self, redact_classes=None):
         """The class table of ops.track_update: the classes the drawing rule draws united with ``redact_classes`` (uploaded once each)."""
@@ -533,6 +545,14 @@ class DetectionEntry:
             return ops.track_option(thr, hold, grow)
         except (TypeError, ValueError) as e:
             raise FrcnnError("submit_batch: track=%r: (thr, hold, grow): %s" % (track, e)) from None
+
+    @staticmethod
+    def track_motion_option(radius):
+        """``submit_batch``'s ``track_motion`` checked -> the search radius, 1..16.  FrcnnError with the reason."""
+        try:
+            return ops.track_motion_radius(radius)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: track_motion=%r: %s" % (radius, e)) from None
 
     # ------------------------------------------------------------------ eligibility
     @staticmethod
@@ -612,6 +632,9 @@ class DetectionEntry:
             # boxes are hidden), the drawing step the live rows with their ids
             t_thr, t_hold, t_grow = s.track
             t_state, t_table = self.track_state(), self.track_table(s.redact[0] if s.redact else None)
+            # with ``track_motion``: the block match moves the slots between the frames, which lie ``seg`` bytes apart in the staging
+            # area and are still as they were uploaded -- the call stays in front of every redaction and drawing step of the pass
+            t_motion = self.track_motion_state(in_h, in_w) if s.track_motion else None
         if s.encode == JPEG_ENCODE:
             # a frame's row: [its length, int32 | pad to 16 | the file, at most jpeg_bound bytes].  The bound is 6.5 times the raw frame
             # (every block at its longest), which is device memory only: a replay reads back the row's first ``first_copy`` bytes -- the
@@ -655,7 +678,11 @@ class DetectionEntry:
                     if s.track_out is None:                         # (the first warm-up pass: the rows of a packed buffer are known now)
                         R = ops.track_rows(packed) + ops.track_capacity(t_state)
                         s.track_out = torch.zeros((B, 4 + 8 * R), dtype=torch.int32, device="cuda")
-                    ops.track_update(t_state, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold, t_grow, out=s.track_out)
+                    if s.track_motion:
+                        ops.track_update_motion(t_state, t_motion, s.io_dev, seg, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold,
+                                                t_grow, s.track_motion, out=s.track_out)
+                    else:
+                        ops.track_update(t_state, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold, t_grow, out=s.track_out)
                 for i in range(B):
                     rows = s.track_out[i] if s.track else packed[i] if B > 1 else packed
                     if s.redact:
@@ -692,14 +719,15 @@ class DetectionEntry:
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
     def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None, jpeg_mode=JPEG_MODE,
-                      y4m_mode=Y4M_MODE, redact=None, draw=True, track=None):
+                      y4m_mode=Y4M_MODE, redact=None, draw=True, track=None, track_motion=None):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
         (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
         ends in the device JPEG encoder at ``quality`` in ``jpeg_mode`` = (subsampling, huffman), "y4m" for one that ends in the YUV4MPEG2
         encoder in ``y4m_mode`` = (chroma, range).  ``redact`` = (classes, mode, size, margin) (``redact_option``): an annotating pass that
         hides those classes' boxes in each frame (ops.redact_u8) in front of the drawing step; ``draw`` False: one that draws nothing.
-        ``track`` = (thr, hold, grow): an annotating pass that runs the engine's tracker over its frames (ops.track_update)."""
+        ``track`` = (thr, hold, grow): an annotating pass that runs the engine's tracker over its frames (ops.track_update);
+        ``track_motion`` = R: with the motion step of radius R in front of every frame's match (ops.track_update_motion)."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -717,7 +745,7 @@ class DetectionEntry:
             s = _Slot()
             s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
             s.encode, s.quality, s.jpeg_mode, s.y4m_mode = encode, quality, jpeg_mode, y4m_mode
-            s.redact, s.nodraw, s.track = redact, (None if draw else True), track
+            s.redact, s.nodraw, s.track, s.track_motion = redact, (None if draw else True), track, track_motion
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -943,7 +971,7 @@ class DetectionEntry:
         return self.submit_batch([image], [resize_ratio], det_threshold, [self.host_pixels(image) if pixels is None else pixels], batch=1)
 
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
-                     subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None):
+                     subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -971,13 +999,22 @@ class DetectionEntry:
         boxes are redacted (with ``redact``) and never drawn.  ``collect_batch``'s dets then carry "track_id" (0: untracked), and the
         held rows follow the live ones as dets with "held" = their age.  Passes with ``track`` replay on ONE stream of the engine
         (``track_stream``) in submit order, whatever ``in_flight`` is: submit the frames in the order they were shot, and call
-        ``track_reset()`` between two sequences.  A short group's padding frames do not count."""
+        ``track_reset()`` between two sequences.  A short group's padding frames do not count.
+        ``track_motion`` = R (tracking passes only; ("motion", R) appended behind the track tail of the key; 1..16): the motion step
+        (DESIGN §8 "Motion rule", ops.track_update_motion) runs in front of every frame's match: each track's box is moved by the best
+        integer shift, at most R pixels either way, of the pixels under it between the frame before and this one, so a held box follows
+        its object and a fast object is matched where it now is.  The engine keeps the last frame of each source size; ``track_reset()``
+        forgets them too.  Without it every key and byte of a tracking pass is what it was."""
         if (redact is not None or not draw) and not annotate:
             raise FrcnnError("submit_batch: redact= and draw=False change the frame an ANNOTATING pass returns: pass annotate=True")
         if track is not None:
             if not annotate:
                 raise FrcnnError("submit_batch: track= tracks the detections of an ANNOTATING pass: pass annotate=True")
             track = self.track_option(track)
+        if track_motion is not None:
+            if track is None:
+                raise FrcnnError("submit_batch: track_motion= moves the boxes of the tracker: pass track=(thr, hold, grow) too")
+            track_motion = self.track_motion_option(track_motion)
         if redact is not None:
             redact = self.redact_option(redact)
         y4m_mode = Y4M_MODE
@@ -1030,6 +1067,8 @@ class DetectionEntry:
                 key = key + ("nodraw",)
             if track is not None:
                 key = key + ("track",) + track
+            if track_motion is not None:
+                key = key + ("motion", track_motion)
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -1038,7 +1077,8 @@ class DetectionEntry:
             s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
         else:
             s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality,
-                                                                     jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode, redact, draw, track))
+                                                                     jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode, redact, draw, track,
+                                                                     track_motion))
         metas, files = [], []
         for i in range(B):
             j = i if i < len(images) else 0

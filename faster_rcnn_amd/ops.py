@@ -1278,16 +1278,8 @@ def track_rows(det_packed):
     return (int(one.numel()) - 4) // 7
 
 
-def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, out=None):
-    """The tracking rule (DESIGN §8 "Tracking rule", frcnn_track_update) over the frames of ``det_packed`` IN ORDER, in one launch:
-    ``state`` (``track_state``) is read and advanced, and frame f's tracked buffer lands in ``out[f]`` -- -> ``out``, a (B, 4 + 8R) int32
-    tensor, R = the packed buffers' rows + the state's capacity (``split_tracked`` cuts it up; ``redact_u8`` and ``annotate_u8`` take
-    ``out[f]`` in a ``det_packed``'s place with ``tracked=True``).  ``det_packed``: one packed buffer of the post-process (B = 1), a
-    (B, words) tensor, or a list of B buffers of one size -- used where they lie when they are evenly spaced in memory (the stride is an
-    argument of the call), else gathered with one copy.  ``n_frames``: an int32 device tensor whose first word says how many of the B
-    frames are real; the rest is a short pass's padding and leaves the state alone.  ``table``: ``track_table``.  (h, w): the frame's size.
-    Reads *n_dets and *n_frames on the device: the call can be captured in a graph."""
-    _require_gpu()
+def _track_packed(det_packed):
+    """``track_update``'s ``det_packed`` -> (the tensor frame 0 starts at, the frames' distance in words, B, a buffer's words)."""
     if isinstance(det_packed, (list, tuple)):
         bufs = list(det_packed)
         assert bufs and all(b.is_cuda and b.dtype == torch.int32 and b.dim() == 1 and b.is_contiguous() and b.numel() == bufs[0].numel() for b in bufs)
@@ -1302,6 +1294,20 @@ def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=
         base = det_packed
         B, words = (1, int(base.numel())) if base.dim() == 1 else (int(base.shape[0]), int(base.shape[1]))
         stride = words
+    return base, stride, B, words
+
+
+def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, out=None):
+    """The tracking rule (DESIGN §8 "Tracking rule", frcnn_track_update) over the frames of ``det_packed`` IN ORDER, in one launch:
+    ``state`` (``track_state``) is read and advanced, and frame f's tracked buffer lands in ``out[f]`` -- -> ``out``, a (B, 4 + 8R) int32
+    tensor, R = the packed buffers' rows + the state's capacity (``split_tracked`` cuts it up; ``redact_u8`` and ``annotate_u8`` take
+    ``out[f]`` in a ``det_packed``'s place with ``tracked=True``).  ``det_packed``: one packed buffer of the post-process (B = 1), a
+    (B, words) tensor, or a list of B buffers of one size -- used where they lie when they are evenly spaced in memory (the stride is an
+    argument of the call), else gathered with one copy.  ``n_frames``: an int32 device tensor whose first word says how many of the B
+    frames are real; the rest is a short pass's padding and leaves the state alone.  ``table``: ``track_table``.  (h, w): the frame's size.
+    Reads *n_dets and *n_frames on the device: the call can be captured in a graph."""
+    _require_gpu()
+    base, stride, B, words = _track_packed(det_packed)
     assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
     assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
     assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
@@ -1312,6 +1318,60 @@ def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=
     assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (B, 4 + 8 * R)
     _lib.call("frcnn_track_update", _p(state), cap, _p(base), int(stride), B, _p(n_frames), rows, _p(table), int(table.numel()),
               int(thr), int(hold), int(grow), int(h), int(w), _p(out), 4 + 8 * R, _stream())
+    return out
+
+
+TRACK_MOTION_RADIUS = _lib.TRACK_MOTION_RADIUS  # (smallest, largest, the default) search radius of ``track_update_motion``
+
+
+def track_motion_radius(r=None):
+    """(host only) The block match's search radius checked, None replaced by the default 8: an integer in 1..16.  ValueError with the
+    reason."""
+    lo, hi, default = TRACK_MOTION_RADIUS
+    r = default if r is None else r
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not lo <= int(r) <= hi:
+        raise ValueError("track motion radius=%r: an integer in %d..%d" % (r, lo, hi))
+    return int(r)
+
+
+def track_motion_state(h, w):
+    """A motion state for h x w frames with no reference: a zeroed uint8 device tensor of frcnn_track_motion_state_bytes = 16 + 3hw bytes,
+    [kept, h, w, 0 (int32) | the kept frame (h, w, 3)] (include/ext/frcnn_hip_track_motion.h)."""
+    _require_gpu()
+    n = int(_lib.load().frcnn_track_motion_state_bytes(int(h), int(w)))
+    if n == 0:
+        raise _lib.FrcnnError("track_motion_state: frame %rx%r out of range (sides 1..%d)" % (h, w, _lib.REDACT_MAX_SIDE))
+    return torch.zeros(n, dtype=torch.uint8, device="cuda")
+
+
+def track_motion_reset(mstate):
+    """Forget the kept frame (on the current stream): the header is zeroed, so the next frame has no reference."""
+    mstate[:16].zero_()
+    return mstate
+
+
+def track_update_motion(state, mstate, frames_u8, frame_stride, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, radius=8, out=None):
+    """``track_update`` with the motion step in front of every frame's match (DESIGN §8 "Motion rule", frcnn_track_update_motion): every
+    live slot's box is first moved by the best integer shift of the pixels under it, found by a block match of radius ``radius`` between
+    the frame before and this one, so that a held box follows its object.  ``mstate`` (``track_motion_state(h, w)``) carries the last frame
+    of one call to the next.  ``frames_u8``: a uint8 device tensor that holds frame f of the call, (h, w, 3) in any channel order, at
+    byte ``f * frame_stride``; read only.  Everything else, ``out`` and the return value: as ``track_update``.  At most two launches per
+    frame and one more per call; reads *n_dets, *n_frames and the slot count on the device: the call can be captured in a graph."""
+    _require_gpu()
+    base, stride, B, words = _track_packed(det_packed)
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert mstate.is_cuda and mstate.dtype == torch.uint8 and mstate.dim() == 1 and mstate.is_contiguous() and mstate.numel() == 16 + 3 * int(h) * int(w)
+    assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
+    assert int(frames_u8.numel()) >= (B - 1) * int(frame_stride) + 3 * int(h) * int(w) and int(frame_stride) >= 0
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    cap, rows = track_capacity(state), (words - 4) // 7
+    R = rows + cap
+    if out is None:
+        out = torch.empty((B, 4 + 8 * R), dtype=torch.int32, device="cuda")
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (B, 4 + 8 * R)
+    _lib.call("frcnn_track_update_motion", _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), B, _p(n_frames),
+              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), int(h), int(w), _p(out), 4 + 8 * R, _stream())
     return out
 
 

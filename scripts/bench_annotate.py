@@ -24,7 +24,8 @@ encoder) and PNG files to PNG files (host codecs), alternating in one session.
 to PNG files with the device encoder -- and reports the frames/s of both and their ratio.
 
 ``--track`` runs the tracker's cost instead (``run_track``): the ``--redact`` leg's frames and redaction without and with ``--track``
-(IoU 30 %, hold 8, grow 0, the defaults), alternating in one session through in-memory annotating passes; tracking passes replay on one
+(IoU 30 %, hold 8, grow 0, the defaults), alternating in one session through in-memory annotating passes; ``--track_motion`` likewise
+(``run_track_motion``) the ``--track`` leg without and with ``--track_motion 8``, and the tracker part of one pass alone; tracking passes replay on one
 stream of the engine, so the figure includes what that ordering costs.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
@@ -329,6 +330,96 @@ def run_track(name, cfg, n_frames, reps, content="noise"):
     return res
 
 
+MOTION_LEG = 8                                           # --track_motion with its default radius
+
+
+def tracker_part_us(eng, h, w, radius, iters=20):
+    """HIP-event time of the tracker part of ONE pass of eng.batch frames, outside a graph: a copy of the engine's tracker state as the
+    run left it, every live slot detected again where it is (so the slots stay), noise frames; ``radius`` None: ops.track_update (one
+    launch), else ops.track_update_motion (2 B + 1 launches, the kept frame primed by a first call).  -> the median in microseconds."""
+    import numpy as np
+    import torch
+    from faster_rcnn_amd import ops
+    B, rows = eng.batch, 300
+    words = eng.track_state().cpu().numpy()
+    cap, n = (words.size - 4) // 8, int(words[0])
+    packed = np.zeros(4 + 7 * rows, dtype=np.int32)
+    packed[0] = n
+    packed[4:4 + 4 * n] = words[4 + 2 * cap:4 + 2 * cap + 4 * n]
+    packed[4 + 4 * rows:4 + 4 * rows + n] = words[4 + cap:4 + cap + n]
+    packed[4 + 5 * rows:4 + 5 * rows + n] = words[4 + 6 * cap:4 + 6 * cap + n]
+    dets = torch.from_numpy(np.stack([packed] * B)).cuda()
+    frames = torch.from_numpy(np.random.RandomState(9).randint(0, 256, (B, h * w * 3)).astype(np.uint8)).cuda()
+    nf = torch.tensor([B], dtype=torch.int32, device="cuda")
+    table, mstate = eng.track_table("all"), ops.track_motion_state(h, w)
+    out = torch.zeros((B, 4 + 8 * (rows + cap)), dtype=torch.int32, device="cuda")
+    start = torch.from_numpy(words).cuda()
+
+    def once(state):
+        if radius is None:
+            ops.track_update(state, dets, nf, table, h, w, *TRACK_LEG, out=out)
+        else:
+            ops.track_update_motion(state, mstate, frames, h * w * 3, dets, nf, table, h, w, *TRACK_LEG, radius, out=out)
+
+    state = start.clone()
+    once(state)                                                     # (primes the kept frame; the state's frame count and the header agree)
+    times = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        once(state)
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1000.0)
+    return round(statistics.median(times), 1), n
+
+
+def run_track_motion(name, cfg, n_frames, reps, content="noise"):
+    """``--track_motion``: what the motion step costs on top of tracking.  One pair of legs in ONE session, alternating inside every
+    repetition: ``run_track``'s frames through in-memory annotating passes with ``redact=REDACT_LEG, track=TRACK_LEG``, without and with
+    ``track_motion=MOTION_LEG`` (the tracker is reset in front of every run).  Reports frames/s of both and their ratio, the tracker's
+    state at the end, and the HIP-event time of the tracker part of one pass both ways (``tracker_part_us``)."""
+    import numpy as np
+    from faster_rcnn_amd import entry, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+
+    def leg(**kw):
+        def run():
+            eng.track_reset()
+            return annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, track=TRACK_LEG, **kw)
+        return run
+
+    legs = {"track": leg(), "track_motion": leg(track_motion=MOTION_LEG)}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    import torch
+    torch.cuda.synchronize()
+    state = eng.track_state().cpu().numpy()
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact": ["all", "blur", 12, 0], "track": list(TRACK_LEG), "track_motion": MOTION_LEG, "images_per_pass": eng.batch,
+           "in_flight": eng.in_flight,
+           "tracker": {"live_slots": int(state[0]), "ids_issued": int(state[1]), "overflow": int(state[2]), "frames": int(state[3])}}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["motion_over_track"] = round(statistics.median(times["track"]) / statistics.median(times["track_motion"]), 3)
+    res["tracker_part_us"] = {"track_update": tracker_part_us(eng, h, w, None)[0]}
+    res["tracker_part_us"]["track_update_motion"], res["tracker_part_us"]["live_slots"] = tracker_part_us(eng, h, w, MOTION_LEG)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--frames", type=int, default=256)
@@ -344,6 +435,8 @@ def main():
                                                           "--redact_mode blur, alternating in one session (passes in memory, and files to files)")
     ap.add_argument("--track", action="store_true", help="instead of the legs above: the --redact leg's frames and redaction without and with "
                                                          "--track (IoU 30, hold 8), alternating in one session (passes in memory)")
+    ap.add_argument("--track_motion", action="store_true", help="instead of the legs above: the --track leg's frames, redaction and tracking "
+                                                                "without and with --track_motion 8, alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -352,6 +445,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.track_motion:
+            out[name] = run_track_motion(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.track:
             out[name] = run_track(name, PAIRS[name], args.frames, args.reps, args.content)
