@@ -402,6 +402,18 @@ TRACK_MOTION_SIGNATURES = {
 # the block match's search radius: (smallest, largest, the default) (FRCNN_TRACK_MOTION_MIN_RADIUS / _MAX_RADIUS)
 TRACK_MOTION_RADIUS = (1, 16, 8)
 
+TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
+TRACK_LOOKBACK_SIGNATURES = {
+    "frcnn_track_lookback_version": (I, []),
+    "frcnn_track_lookback_state_bytes": (c_size_t, [I, I, I, I, I, I]),
+    "frcnn_track_lookback": (I, [P, P, ctypes.c_longlong, P, ctypes.c_longlong, I, P, I, I, I, I, I, I, I, I, P, ctypes.c_longlong, P,
+                                 ctypes.c_longlong, P, P]),
+}
+# the frames a new track is chained back over: (smallest, largest, the default) (FRCNN_TRACK_LOOKBACK_MAX)
+TRACK_LOOKBACK = (1, 16, 8)
+TRACK_LOOKBACK_MAX_BACK = 128   # ... FRCNN_TRACK_LOOKBACK_MAX_BACK: back-filled rows a full frame can still take, at most
+TRACK_LOOKBACK_HEADER = 32      # ... FRCNN_TRACK_LOOKBACK_HEADER: bytes in front of a window's cells
+
 
 class ConvDesc(ctypes.Structure):
     """frcnn_conv_desc (include/frcnn_hip.h)."""
@@ -526,6 +538,13 @@ def load():
     if lib.frcnn_track_motion_version() != TRACK_MOTION_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_motion_version()} of the tracker's motion extension, this binding "
                          f"{TRACK_MOTION_VERSION} (include/ext/frcnn_hip_track_motion.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in TRACK_LOOKBACK_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_track_lookback_version() != TRACK_LOOKBACK_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_lookback_version()} of the tracker's look-back extension, this binding "
+                         f"{TRACK_LOOKBACK_VERSION} (include/ext/frcnn_hip_track_lookback.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -367,12 +367,48 @@ def track_motion_from_args(args):
         raise ValueError("--track_motion: %s" % e) from None
 
 
+TRACK_LOOKBACK_AUTO = 0        # a bare --track_lookback: as far back as one pass holds, at most ops.TRACK_LOOKBACK[2] = 8 frames
+
+
+def track_lookback_from_args(args):
+    """(host only) The look-back the command line asks for -> the frames as ``annotate_images(track_lookback=...)`` takes them
+    (TRACK_LOOKBACK_AUTO for a bare ``--track_lookback``), or None without the flag.  ValueError, with the reason, for
+    ``--track_lookback`` without ``--track`` and for a value outside 1..16."""
+    if args.track_lookback is None:
+        return None
+    if not args.track:
+        raise ValueError("--track_lookback=%s is a setting of the tracker: it needs --track" % args.track_lookback)
+    if args.track_lookback == TRACK_LOOKBACK_AUTO and not isinstance(args.track_lookback, bool):
+        return TRACK_LOOKBACK_AUTO
+    try:
+        return ops.track_lookback_option(args.track_lookback)
+    except ValueError as e:
+        raise ValueError("--track_lookback: %s" % e) from None
+
+
+def _lookback_frames(track_lookback, track, eng, B):
+    """``annotate_images`` / ``annotate_stream``'s ``track_lookback`` checked -> the look-back of their passes, or None."""
+    if track_lookback is None:
+        return None
+    if track is None:
+        raise ValueError("track_lookback=%r hides the tracker's new tracks in earlier frames: it needs track=(thr, hold, grow)" % (track_lookback,))
+    if eng is None:
+        raise ValueError("track_lookback=%r delays the output by one pass: the eager path (a foreign model) returns every frame at once and "
+                         "cannot" % (track_lookback,))
+    if track_lookback == TRACK_LOOKBACK_AUTO and not isinstance(track_lookback, bool):
+        return min(ops.TRACK_LOOKBACK[2], B)
+    n = ops.track_lookback_option(track_lookback)
+    if n > B:                                             # (what submit_batch would refuse at the first pass)
+        raise ValueError("track_lookback=%d reaches further back than a pass of %d frames holds: at most %d here" % (n, B, B))
+    return n
+
+
 def mot_lines(frame_no, dets, class_mapping):
     """The MOTChallenge lines of one frame: ``frame,id,left,top,width,height,prob,cls,-1,-1`` per LIVE tracked det ("track_id" > 0, no
     "held"), in row order; left / top the smaller corner, width / height the corners' distance, prob with six decimals, cls the index."""
     out = []
     for d in dets:
-        if d.get("held") or d.get("track_id", 0) <= 0:
+        if d.get("held") or d.get("backfilled") or d.get("track_id", 0) <= 0:
             continue
         x1, y1, x2, y2 = [int(v) for v in d["bbox"]]
         out.append("%d,%d,%d,%d,%d,%d,%.6f,%d,-1,-1" % (frame_no, d["track_id"], min(x1, x2), min(y1, y2), abs(x2 - x1), abs(y2 - y1),
@@ -400,17 +436,20 @@ def reset_tracks(training_manager, detector, in_flight=1):
 
 def _print_drawn(dets, width, height):
     for det in dets:
-        if not det.get("held") and drawn(det, width, height):       # (held rows, of tracking passes only, are never drawn)
+        if not det.get("held") and not det.get("backfilled") and drawn(det, width, height):       # (held and back-filled rows are never drawn)
             print(det)
 
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
-                        frame_no=1, track_motion=None):
+                        frame_no=1, track_motion=None, track_lookback=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
     ``tracks_out``: a text file that receives the frame's MOT lines under the number ``frame_no``.  ``track_motion`` = R (with
     ``track``): the tracks' boxes are first moved with the pixels under them, at most R pixels either way (DESIGN §8 "Motion rule")."""
+    if track_lookback is not None:
+        raise ValueError("track_lookback=%r delays the output: get_annotated_frame returns its frame at once and cannot; use annotate_images "
+                         "or annotate_stream" % (track_lookback,))
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     motion = {} if track_motion is None else {"track_motion": track_motion}
@@ -605,13 +644,13 @@ def directory_frames(input_dir, image_filenames, jpeg_decoder=None, png_decoder=
 
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
-                    redact=None, draw=True, track=None, tracks_out=None, track_motion=None):
+                    redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback``: as ``annotate_images``."""
     from concurrent.futures import ThreadPoolExecutor
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
@@ -650,8 +689,11 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
     if redact is not None or not draw:                    # (else the passes, and their keys, are the ones without the arguments)
         kwargs = dict(kwargs, redact=redact, draw=draw)
     mapping = training_manager.class_mapping
+    lookback = _lookback_frames(track_lookback, track, eng, None if eng is None else eng.batch)
     if track is not None:                                 # a new sequence; its frames are submitted in stream order, as every stream's are
         kwargs = dict(kwargs, track=track, **motion)
+        if lookback is not None:
+            kwargs["track_lookback"] = lookback
         reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
 
     if eng is None:                                       # eager path / foreign models: one frame at a time, converted on the device
@@ -683,6 +725,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
     read = ThreadPoolExecutor(max_workers=1)              # the stream is sequential: one reader, ``ahead`` frames in front of the passes
     write = ThreadPoolExecutor(max_workers=1 if to_video else max(1, WRITE_THREADS))
     pending, writes, window = collections.deque(), [], []
+    waiting, last_key = collections.deque(), [None]      # look-back: the groups whose frames a later pass emits; the geometry of the last pass
 
     def load():                                           # (reader thread) -> (label, frame, resized, ratio, pixels) or None at the end
         try:
@@ -699,6 +742,8 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
             results = eng.collect_batch(ticket)
         finally:
             window.pop(0)
+        if lookback is not None:                          # (the pass returned the group before its own, or nothing)
+            part = waiting.popleft() if results else ()
         for (pos, label, frame), (num_rois, dets, out) in zip(part, results):
             print("processing {}".format(label))
             print("num rois: {}".format(num_rois))
@@ -712,12 +757,26 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
         while len(writes) > 4 * WRITE_THREADS:            # (bounded: encoded frames must not pile up in memory)
             writes.pop(0).result()
 
+    def flush():                                          # the frames the look-back window still holds
+        if last_key[0] is not None:
+            window.append(((), eng.submit_batch([], [], DET_THRESHOLD, [], batch=B, annotate=True, **kwargs)))
+            last_key[0] = None
+            if len(window) >= eng.in_flight:
+                finish()
+
     def submit(group):
         parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
+        if lookback is not None:                          # full passes only: a window belongs to one size of pass; a new geometry: a new window
+            parts = [(group, B)]
+            if last_key[0] not in (None, eng.geometry_of(group[0][5])):
+                flush()
+            last_key[0] = eng.geometry_of(group[0][5])
         for part, take in parts:
             ticket = eng.submit_batch([g[3] for g in part], [g[4] for g in part], DET_THRESHOLD, [g[5] for g in part],
                                       batch=take, annotate=True, **kwargs)
             window.append(([(g[0], g[1], g[2]) for g in part], ticket))
+            if lookback is not None:
+                waiting.append(window[-1][0])
             if len(window) >= eng.in_flight:
                 finish()
 
@@ -744,6 +803,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
             key, pos = k, pos + 1
         if group:
             submit(group)
+        flush()
         while window:
             finish()
         for f in writes:
@@ -760,7 +820,8 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
-                    jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None):
+                    jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
+                    track_lookback=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -780,7 +841,11 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     at the start, every tracked detection is labelled ``cls#id`` and lost tracks are held (and redacted) for ``hold`` frames; None: no
     tracking.  ``tracks_out``: a text file that receives the MOT lines, frame i of the list under the number i + 1.
     ``track_motion``: the search radius as ``track_motion_from_args`` returns it (with ``track``) -- every track's box is moved with the
-    pixels under it from frame to frame, so a held box follows its object; None: held boxes stand still."""
+    pixels under it from frame to frame, so a held box follows its object; None: held boxes stand still.
+    ``track_lookback``: the frames as ``track_lookback_from_args`` returns them (with ``track``; TRACK_LOOKBACK_AUTO: as many as a pass
+    holds, at most 8) -- every new track is followed BACK over that many frames and hidden there too (DESIGN §8 "Look-back rule").  Every
+    group then goes through a full pass of B frames, a pass returns the frames of the pass before it and a flush ends the list: each
+    frame is written and printed when it is emitted, the same lines in the same order.  The eager path refuses it."""
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     motion = {} if track_motion is None else {"track_motion": track_motion}
@@ -811,6 +876,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
     pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
     mapping = training_manager.class_mapping
+    lookback = _lookback_frames(track_lookback, track, eng, None if eng is None else eng.batch)
     if track is not None:
         reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
     if eng is None:                                       # eager path / foreign models: the reference's loop
@@ -839,10 +905,13 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     edit = dict(redact=redact, draw=draw) if redact is not None or not draw else {}      # (else the passes without the arguments)
     if track is not None:                                 # (the groups below are submitted in list order, as tracking needs them)
         edit = dict(edit, track=track, **motion)
+    if lookback is not None:
+        edit["track_lookback"] = lookback
     decode = ThreadPoolExecutor(max_workers=max(1, DECODE_THREADS))
     write = ThreadPoolExecutor(max_workers=max(1, WRITE_THREADS))
     ahead = 2 * eng.in_flight * B
     pending, writes, window = {}, [], []
+    waiting, last_key = collections.deque(), [None]      # look-back: the groups whose frames a later pass emits; the geometry of the last pass
 
     def finish():
         part, ticket = window[0]
@@ -850,6 +919,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             results = eng.collect_batch(ticket)
         finally:
             window.pop(0)
+        if lookback is not None:                          # (the pass returned the group before its own, or nothing)
+            part = waiting.popleft() if results else ()
         for (pos, frame), (num_rois, dets, out) in zip(part, results):
             print("processing {}".format(paths[pos]))
             print("num rois: {}".format(num_rois))
@@ -864,10 +935,25 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         """<= B frames of one geometry: one pass of B (padded) when they fill at least half of it (as get_dets_by_cls), else
         one-frame passes."""
         parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
+        if lookback is not None:                          # full passes only: a window belongs to one size of pass; a new geometry: a new window
+            parts = [(group, B)]
+            if last_key[0] not in (None, eng.geometry_of(group[0][4])):
+                flush()
+            last_key[0] = eng.geometry_of(group[0][4])
         for part, take in parts:
             ticket = eng.submit_batch([g[2] for g in part], [g[3] for g in part], DET_THRESHOLD, [g[4] for g in part],
                                       batch=take, annotate=True, encode=encode, quality=quality, **jpeg_mode, **edit)
             window.append(([(g[0], g[1]) for g in part], ticket))
+            if lookback is not None:
+                waiting.append(window[-1][0])
+            if len(window) >= eng.in_flight:
+                finish()
+
+    def flush():                                          # the frames the look-back window still holds
+        if last_key[0] is not None:
+            window.append(((), eng.submit_batch([], [], DET_THRESHOLD, [], batch=B, annotate=True, encode=encode, quality=quality, **jpeg_mode,
+                                                **edit)))
+            last_key[0] = None
             if len(window) >= eng.in_flight:
                 finish()
 
@@ -886,6 +972,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             key = k
         if group:
             submit(group)
+        flush()
         while window:
             finish()
         for f in writes:
@@ -974,6 +1061,9 @@ def build_parser():
     p.add_argument("--track_motion", dest="track_motion", type=int, nargs="?", const=ops.TRACK_MOTION_RADIUS[2], default=None, metavar="R",
                    help="move every track's box with the pixels under it from frame to frame (a block match of at most R pixels either "
                         "way, 1..16, default 8), so a held box follows its object (needs --track)")
+    p.add_argument("--track_lookback", dest="track_lookback", type=int, nargs="?", const=TRACK_LOOKBACK_AUTO, default=None, metavar="N",
+                   help="hide every new track in the N frames BEFORE its first detection too (1..16 and at most the frames of one pass; "
+                        "bare: as many as a pass holds, at most 8); the output runs one pass behind the input (needs --track)")
     p.add_argument("--tracks_out", dest="tracks_out", default=None, metavar="PATH",
                    help="write the tracks as MOTChallenge lines frame,id,left,top,width,height,prob,cls,-1,-1 (needs --track)")
     return p
@@ -1040,6 +1130,9 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     tracking = {} if track is None else {"track": track, "tracks_out": stack.enter_context(open(args.tracks_out, "w")) if args.tracks_out else None}
     if track_motion is not None:
         tracking["track_motion"] = track_motion
+    track_lookback = track_lookback_from_args(args)
+    if track_lookback is not None:
+        tracking["track_lookback"] = track_lookback
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

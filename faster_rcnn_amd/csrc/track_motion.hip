@@ -2,42 +2,25 @@
 // integer block match per live slot between two frames, in front of csrc/track.hip's steps 1-4.  gfx950 (CDNA4) only.
 // A call walks its frames one by one -- the search of frame f + 1 needs the boxes after frame f --: k_motion_search (one workgroup per
 // slot of the state; one past n_slots, read on the device, returns at once) and then track.hip's kernel on that frame; k_motion_keep
-// closes the call.  A search workgroup stages the slot's <= 1024 template lumas once; a wave takes a candidate at a time, its lanes the
-// samples (16 each, in registers), and reads the current frame where it lies: the window of a strided grid does not tile into LDS, and a
-// whole search is <= 1.1 M pixel reads that L2 serves.  A candidate's cost is a shuffle sum; a wave keeps the minimum of ONE packed key
-// per candidate, cost << 22 | norm << 12 | dy + 16 << 6 | dx + 16 (18 + 10 + 6 + 6 bits): a uint64 minimum IS the lexicographic rule.  The
-// waves' keys meet in LDS and wave 0 shuffles them down.  One writer per slot word; no atomics.
+// closes the call.  The search itself is csrc/track_motion_search.h's (shared with csrc/track_lookback.hip).  One writer per slot word;
+// no atomics.
 #include "common.h"
 #include "../../include/ext/frcnn_hip_redact.h"
 #include "../../include/ext/frcnn_hip_track.h"
 #include "../../include/ext/frcnn_hip_track_motion.h"
 #include "track.h"
+#include "track_motion_search.h"
 
 namespace frcnn {
 
-constexpr int TM_THREADS = 1024;
-constexpr int TM_WAVES = TM_THREADS / 64;
-constexpr int TM_GRID = FRCNN_TRACK_MOTION_GRID;
-constexpr int TM_PER_LANE = TM_GRID * TM_GRID / 64;                         // samples of a lane
 constexpr int TM_HEADER = 16;                                               // bytes in front of the kept frame
-static_assert(TM_GRID * TM_GRID <= TM_THREADS, "a thread stages one template luma");
-static_assert(TM_WAVES <= 64, "wave 0 reduces the waves' keys");
-
-__device__ __forceinline__ int luma(const uint8_t* p) { return ((int)p[0] + 2 * (int)p[1] + (int)p[2] + 2) >> 2; }
-
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int off) {
-    const unsigned lo = __shfl_xor((unsigned)v, off), hi = __shfl_xor((unsigned)(v >> 32), off);
-    return ((unsigned long long)hi << 32) | lo;
-}
 
 // Step 0 for frame ``f`` of the call, slot blockIdx.x.
 __global__ void __launch_bounds__(TM_THREADS) k_motion_search(int32_t* state, int cap, const uint8_t* motion_state, const uint8_t* frames_u8,
                                                                 long long frame_stride, int f, int frames, const int32_t* n_frames,
                                                                 int radius, int h, int w) {
-    __shared__ uint8_t s_t[TM_GRID * TM_GRID];
-    __shared__ unsigned long long s_key[TM_WAVES];
-    __shared__ int s_zero;
-    const int slot = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ TmShared sh;
+    const int slot = blockIdx.x, lane = threadIdx.x & 63;
     if (f >= min(max(*n_frames, 0), frames)) return;                        // padding
     if (slot >= min(max(state[0], 0), cap)) return;
     const uint8_t* ref;
@@ -51,54 +34,8 @@ __global__ void __launch_bounds__(TM_THREADS) k_motion_search(int32_t* state, in
     const uint8_t* cur = frames_u8 + (long long)f * frame_stride;
     int32_t* raw = state + 4 + 2 * cap + 4 * slot;
     const int x1 = raw[0], y1 = raw[1], x2 = raw[2], y2 = raw[3];
-    const int xa = max(min(x1, x2), 0), xb = min(max(x1, x2), w - 1), ya = max(min(y1, y2), 0), yb = min(max(y1, y2), h - 1);
-    if (xa > xb || ya > yb) return;
-    const int sx = (xb - xa + 1 + TM_GRID - 1) / TM_GRID, sy = (yb - ya + 1 + TM_GRID - 1) / TM_GRID;
-    const int x0 = xa + sx / 2, y0 = ya + sy / 2;                           // (sx / 2 < the box's width: the first sample is inside)
-    const int cols = (xb - x0) / sx + 1, rows = (yb - y0) / sy + 1, n = cols * rows;
-    if (n < FRCNN_TRACK_MOTION_MIN_SAMPLES) return;                         // (the whole workgroup, as every return above)
-    if (tid < n) {
-        const int x = x0 + (tid % cols) * sx, y = y0 + (tid / cols) * sy;
-        s_t[tid] = (uint8_t)luma(ref + ((size_t)y * w + x) * 3);
-    }
-    __syncthreads();
-    // ---- this lane's samples lane, lane + 64, ...: place and template luma
-    int px[TM_PER_LANE], py[TM_PER_LANE], pt[TM_PER_LANE];
-#pragma unroll
-    for (int k = 0; k < TM_PER_LANE; ++k) {
-        const int i = lane + 64 * k;
-        const bool some = i < n;
-        px[k] = some ? x0 + (i % cols) * sx : -1;
-        py[k] = some ? y0 + (i / cols) * sy : 0;
-        pt[k] = some ? s_t[i] : 0;
-    }
-    const int side = 2 * radius + 1, cands = side * side;
-    unsigned long long best = ~0ull;
-    for (int c = wave; c < cands; c += TM_WAVES) {                          // (wave-uniform: the shuffles below see all 64 lanes)
-        const int dy = c / side - radius, dx = c % side - radius;
-        int cost = 0;
-#pragma unroll
-        for (int k = 0; k < TM_PER_LANE; ++k) {
-            if (px[k] < 0) continue;
-            const int xx = min(max(px[k] + dx, 0), w - 1), yy = min(max(py[k] + dy, 0), h - 1);
-            cost += abs(luma(cur + ((size_t)yy * w + xx) * 3) - pt[k]);
-        }
-        for (int off = 32; off > 0; off >>= 1) cost += __shfl_xor(cost, off);
-        const unsigned long long key = ((unsigned long long)cost << 22) | ((unsigned long long)(dx * dx + dy * dy) << 12) |
-                                       ((unsigned long long)(dy + 16) << 6) | (unsigned long long)(dx + 16);
-        best = key < best ? key : best;
-        if (dx == 0 && dy == 0 && lane == 0) s_zero = cost;
-    }
-    if (lane == 0) s_key[wave] = best;
-    __syncthreads();
-    if (wave != 0) return;
-    best = lane < TM_WAVES ? s_key[lane] : ~0ull;
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = shfl_xor_u64(best, off);
-        best = o < best ? o : best;
-    }
-    const int cost = (int)(best >> 22), dy = (int)((best >> 6) & 63) - 16, dx = (int)(best & 63) - 16;
-    if (cost + n > s_zero) return;                                          // the gate: a flat or unchanged region does not move
+    int dx = 0, dy = 0;
+    if (!tm_search(ref, cur, x1, y1, x2, y2, radius, h, w, sh, dx, dy)) return;      // (true in wave 0 alone)
     if (lane < 4) raw[lane] = (lane == 0 ? x1 : lane == 1 ? y1 : lane == 2 ? x2 : y2) + ((lane & 1) ? dy : dx);
 }
 

@@ -303,7 +303,8 @@ class _Slot:
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
-                 "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion")
+                 "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
+                 "track_lookback", "lb_out", "lb_pin", "_lb_raw")
 
     def __init__(self):
         for name in self.__slots__:
@@ -395,10 +396,11 @@ class GraphCache:
 
 
 class Ticket:
-    __slots__ = ("slot", "image")
+    __slots__ = ("slot", "image", "own", "emitted")
 
-    def __init__(self, slot, image):
-        self.slot, self.image = slot, image
+    def __init__(self, slot, image, own=None, emitted=None):
+        # ``own`` / ``emitted`` (look-back passes): the record of this submit's group and of the group whose frames this pass emits
+        self.slot, self.image, self.own, self.emitted = slot, image, own, emitted
 
 
 class DetectionEntry:
@@ -451,6 +453,9 @@ class DetectionEntry:
         self._track_state = None                         # the engine's ONE tracker state (ops.track_state): its pointer is in the graphs
         self._track_tables = {}
         self._track_motion_states = {}                   # (h, w) of the source frames -> ops.track_motion_state: their pointers are in the graphs
+        self._track_lookback_windows = {}                # (h, w, B) -> ops.track_lookback_state: the frames tracked but not yet emitted
+        self._lookback_waiting = {}                      # (h, w, B) -> the record of the group its window holds ({"images", "n_rois"})
+        self._lookback_last = None                       # (key, capture) of the last look-back submit: what a flush submit replays
 
     def class_names(self):
         """This engine's class names by class index ("" for an index no class has)."""
@@ -516,6 +521,36 @@ class DetectionEntry:
             ops.track_reset(state)
             for mstate in self._track_motion_states.values():       # ... and no frame is the one in front of the next
                 ops.track_motion_reset(mstate)
+            for window, _ in self._track_lookback_windows.values():  # ... and no frame waits to be emitted
+                ops.track_lookback_reset(window)
+        self._lookback_waiting.clear()
+        self._lookback_last = None
+
+    def track_lookback_window(self, h, w, B, rows=None):
+        """-> (the engine's look-back window for passes of B source frames of (h, w) (ops.track_lookback_state), its ``back``: the
+        tracker's capacity where the rows leave room), made on first use, by a pass that knows the ``rows`` of its packed buffers.
+        ``track_reset()`` empties it."""
+        win = self._track_lookback_windows.get((h, w, B))
+        if win is None:
+            cap = ops.track_capacity(self.track_state())
+            back = min(cap, _lib.REDACT_MAX_ROWS - rows - cap)
+            if back < 1:
+                raise FrcnnError("track_lookback=: %d rows and %d tracks leave no room for back-filled rows (at most %d rows in all)"
+                                 % (rows, cap, _lib.REDACT_MAX_ROWS))
+            win = self._track_lookback_windows[(h, w, B)] = (ops.track_lookback_state(B, h, w, rows, cap, back), back)
+        return win
+
+    @staticmethod
+    def track_lookback_option(n, B):
+        """``submit_batch``'s ``track_lookback`` checked against the pass's B frames -> the look-back.  FrcnnError with the reason."""
+        try:
+            n = ops.track_lookback_option(n)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: track_lookback=%r: %s" % (n, e)) from None
+        if n > B:
+            raise FrcnnError("submit_batch: track_lookback=%d reaches further back than a pass of %d frames holds: a frame would be emitted "
+                             "before a later pass could fill it (use passes of at least %d frames)" % (n, B, n))
+        return n
 
     def track_motion_state(self, h, w):
         """The engine's motion state for source frames of (h, w) (ops.track_motion_state), made on first use: the passes submitted with
@@ -635,6 +670,16 @@ class DetectionEntry:
             # with ``track_motion``: the block match moves the slots between the frames, which lie ``seg`` bytes apart in the staging
             # area and are still as they were uploaded -- the call stays in front of every redaction and drawing step of the pass
             t_motion = self.track_motion_state(in_h, in_w) if s.track_motion else None
+        if s.track_lookback:
+            # the frames, as uploaded, and their tracked buffers then join the engine's window, the new tracks are followed back through
+            # it, and the frames of the pass BEFORE come out: everything behind this point edits and encodes those (``out``), with their
+            # widened tracked buffers (``rows_of``)
+            lb_frames = torch.zeros((B, in_h, in_w, 3), dtype=torch.uint8, device="cuda")
+            out = [lb_frames[i] for i in range(B)]
+            if s.frame_io is not None:                              # (raw read-back: the emitted frame, into the slot's pinned segment)
+                s.frame_io = [(lb_frames[i].view(-1), s.io_pin[i * seg:i * seg + npix]) for i in range(B)]
+        else:
+            out = u8 if annotate and self.device_preprocess else None
         if s.encode == JPEG_ENCODE:
             # a frame's row: [its length, int32 | pad to 16 | the file, at most jpeg_bound bytes].  The bound is 6.5 times the raw frame
             # (every block at its longest), which is device memory only: a replay reads back the row's first ``first_copy`` bytes -- the
@@ -683,21 +728,32 @@ class DetectionEntry:
                                                 t_grow, s.track_motion, out=s.track_out)
                     else:
                         ops.track_update(t_state, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold, t_grow, out=s.track_out)
+                    if s.track_lookback:
+                        lb_window, lb_back = self.track_lookback_window(in_h, in_w, B, ops.track_rows(packed))
+                        if s.lb_out is None:
+                            R2 = ops.track_rows(packed) + ops.track_capacity(t_state) + lb_back
+                            s.lb_out = (lb_frames, torch.zeros((B, 4 + 8 * R2), dtype=torch.int32, device="cuda"),
+                                        torch.zeros(4, dtype=torch.int32, device="cuda"))
+                        ops.track_lookback(lb_window, s.io_dev, seg, s.track_out, s.n_frames_dev, ops.track_capacity(t_state), lb_back, in_h, in_w,
+                                           s.track_lookback, s.track_motion or 0, t_grow, out=s.lb_out)
                 for i in range(B):
-                    rows = s.track_out[i] if s.track else packed[i] if B > 1 else packed
+                    rows = s.lb_out[1][i] if s.track_lookback else s.track_out[i] if s.track else packed[i] if B > 1 else packed
                     if s.redact:
-                        ops.redact_u8(u8[i], rows, r_table, r_mode, r_size, r_margin, workspace=s.redact_ws, tracked=bool(s.track))
-                    ops.annotate_u8(u8[i], rows, tables, tracked=bool(s.track))
+                        ops.redact_u8(out[i], rows, r_table, r_mode, r_size, r_margin, workspace=s.redact_ws, tracked=bool(s.track))
+                    ops.annotate_u8(out[i], rows, tables, tracked=bool(s.track))
                     if s.encode == Y4M_ENCODE:
                         continue                                    # (all B frames in one launch behind the loop)
                     if s.encode == JPEG_ENCODE:
-                        ops.jpeg_encode_u8(u8[i], quality=s.quality, bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1],
+                        ops.jpeg_encode_u8(out[i], quality=s.quality, bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1],
                                            workspace=s.png_ws, subsampling=subsampling, huffman=huffman)
                     elif s.encode:
-                        ops.png_encode_u8(u8[i], bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1], workspace=s.png_ws,
+                        ops.png_encode_u8(out[i], bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1], workspace=s.png_ws,
                                               compress=compress)
                 if s.encode == Y4M_ENCODE:
-                    ops.y4m_encode_frames_u8(s.io_dev, seg, B, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
+                    if s.track_lookback:
+                        ops.y4m_encode_frames_u8(lb_frames.view(-1), npix, B, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
+                    else:
+                        ops.y4m_encode_frames_u8(s.io_dev, seg, B, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
             return res
         return run
 
@@ -719,7 +775,7 @@ class DetectionEntry:
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
     def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None, jpeg_mode=JPEG_MODE,
-                      y4m_mode=Y4M_MODE, redact=None, draw=True, track=None, track_motion=None):
+                      y4m_mode=Y4M_MODE, redact=None, draw=True, track=None, track_motion=None, track_lookback=None):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
         (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
@@ -727,7 +783,9 @@ class DetectionEntry:
         encoder in ``y4m_mode`` = (chroma, range).  ``redact`` = (classes, mode, size, margin) (``redact_option``): an annotating pass that
         hides those classes' boxes in each frame (ops.redact_u8) in front of the drawing step; ``draw`` False: one that draws nothing.
         ``track`` = (thr, hold, grow): an annotating pass that runs the engine's tracker over its frames (ops.track_update);
-        ``track_motion`` = R: with the motion step of radius R in front of every frame's match (ops.track_update_motion)."""
+        ``track_motion`` = R: with the motion step of radius R in front of every frame's match (ops.track_update_motion);
+        ``track_lookback`` = L: with the look-back call behind the tracker (ops.track_lookback): the pass edits, encodes and returns the
+        frames of the pass before it."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -746,6 +804,7 @@ class DetectionEntry:
             s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
             s.encode, s.quality, s.jpeg_mode, s.y4m_mode = encode, quality, jpeg_mode, y4m_mode
             s.redact, s.nodraw, s.track, s.track_motion = redact, (None if draw else True), track, track_motion
+            s.track_lookback = track_lookback
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -789,6 +848,10 @@ class DetectionEntry:
             if s.track:
                 s._track_raw = self._pinned.take(4 * s.track_out.numel())
                 s.track_pin = s._track_raw.view(torch.int32)[:s.track_out.numel()].view(tuple(s.track_out.shape))
+            if s.track_lookback:                                    # [the B emitted buffers | the count word]
+                words = s.lb_out[1].numel() + 4
+                s._lb_raw = self._pinned.take(4 * words)
+                s.lb_pin = s._lb_raw.view(torch.int32)[:words]
             s.event = torch.cuda.Event()
             s.nbytes = max(int(torch.cuda.memory_reserved() - reserved0), int(s.io_dev.numel() + s.x_f32.numel() * 4))
             stamp("read-back buffers")
@@ -971,7 +1034,8 @@ class DetectionEntry:
         return self.submit_batch([image], [resize_ratio], det_threshold, [self.host_pixels(image) if pixels is None else pixels], batch=1)
 
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
-                     subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None):
+                     subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
+                     track_lookback=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1004,7 +1068,16 @@ class DetectionEntry:
         (DESIGN §8 "Motion rule", ops.track_update_motion) runs in front of every frame's match: each track's box is moved by the best
         integer shift, at most R pixels either way, of the pixels under it between the frame before and this one, so a held box follows
         its object and a fast object is matched where it now is.  The engine keeps the last frame of each source size; ``track_reset()``
-        forgets them too.  Without it every key and byte of a tracking pass is what it was."""
+        forgets them too.  Without it every key and byte of a tracking pass is what it was.
+        ``track_lookback`` = L (tracking passes only; ("lookback", L) appended behind the track / motion tail of the key; 1..16 and at most
+        the pass's B): the look-back rule (DESIGN §8 "Look-back rule", ops.track_lookback) runs behind the tracker: every track born in the
+        pass is followed back over L frames and hidden there, and the pass edits, encodes and returns the frames of the look-back pass
+        submitted BEFORE it: ``collect_batch`` of submit k returns the results of submit k - 1 (none for the first; ``ticket.emitted``
+        holds their images), with the back-filled rows as dets with "backfilled" = k behind the held ones.  A submit with NO images is the
+        flush: it replays the LAST look-back pass submitted, whatever its other arguments say (they are not read, ``track_lookback`` only marks
+        it), with no frame, and returns the last group.  Collect look-back tickets in submit order.  An engine follows ONE look-back
+        sequence at a time: flush before the geometry, the pass size or any option changes (``annotate_images`` / ``annotate_stream``
+        do), and do not interleave two sequences."""
         if (redact is not None or not draw) and not annotate:
             raise FrcnnError("submit_batch: redact= and draw=False change the frame an ANNOTATING pass returns: pass annotate=True")
         if track is not None:
@@ -1015,6 +1088,8 @@ class DetectionEntry:
             if track is None:
                 raise FrcnnError("submit_batch: track_motion= moves the boxes of the tracker: pass track=(thr, hold, grow) too")
             track_motion = self.track_motion_option(track_motion)
+        if track_lookback is not None and track is None:
+            raise FrcnnError("submit_batch: track_lookback= hides the tracker's new tracks in earlier frames: pass track=(thr, hold, grow) too")
         if redact is not None:
             redact = self.redact_option(redact)
         y4m_mode = Y4M_MODE
@@ -1049,8 +1124,16 @@ class DetectionEntry:
             raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
         self._check_epoch()
         B = self.batch if batch is None else batch
+        flush = track_lookback is not None and len(images) == 0
+        if flush:
+            if self._lookback_last is None:
+                raise FrcnnError("submit_batch: a flush (no images) follows a look-back submit; none is waiting")
+            s = self.cache.acquire(*self._lookback_last)
+            return self._replay(s, [], [], [], det_threshold)
         assert 1 <= len(images) <= B and len(images) == len(pixels) == len(resize_ratios)
         _, H, W, src, flip = pixels[0]
+        if track_lookback is not None:
+            track_lookback = self.track_lookback_option(track_lookback, B)
         if annotate:
             if not self.device_preprocess:
                 raise FrcnnError("annotating passes need the device-side preprocess (a foreign preprocess_func uploads float pixels)")
@@ -1069,6 +1152,8 @@ class DetectionEntry:
                 key = key + ("track",) + track
             if track_motion is not None:
                 key = key + ("motion", track_motion)
+            if track_lookback is not None:
+                key = key + ("lookback", track_lookback)
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -1076,11 +1161,19 @@ class DetectionEntry:
         if key[0] == "canvas":
             s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
         else:
-            s = self.cache.acquire(key, lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality,
-                                                                     jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode, redact, draw, track,
-                                                                     track_motion))
+            capture = lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality,
+                                                 jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode, redact, draw, track, track_motion,
+                                                 track_lookback)
+            s = self.cache.acquire(key, capture)
+            if track_lookback is not None:
+                self._lookback_last = (key, capture)
+        return self._replay(s, images, pixels, resize_ratios, det_threshold)
+
+    def _replay(self, s, images, pixels, resize_ratios, det_threshold):
+        """The upload, the replay and the read-back copies of one submit on slot ``s`` -> its ticket.  No images: a look-back pass's flush."""
+        B = s.batch
         metas, files = [], []
-        for i in range(B):
+        for i in range(B if images else 0):
             j = i if i < len(images) else 0
             s.dyn_host[i, 0], s.dyn_host[i, 1] = float(resize_ratios[j]), float(det_threshold)
             if isinstance(pixels[j][0], JpegFile):
@@ -1090,7 +1183,7 @@ class DetectionEntry:
             elif not isinstance(pixels[j][0], JpegFile):
                 np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
         if s.track:
-            s.n_frames_host[0] = len(images)                        # goes up with the frames: the padding does not advance the tracker
+            s.n_frames_host[0] = len(images) if images else -1      # goes up with the frames: the padding does not advance the tracker; -1: a flush
             st = self.track_stream
         else:
             st = self._streams[self._seq % self.in_flight]
@@ -1111,19 +1204,30 @@ class DetectionEntry:
             s.graph.replay()
             if files:
                 s.jpg_status_pin.copy_(s.jpg_status, non_blocking=True)
+            own = emitted = None
+            if s.track_lookback:                                    # this pass returns the group its window held; its own group waits
+                in_h, in_w = int(s.lb_out[0].shape[1]), int(s.lb_out[0].shape[2])
+                own = {"images": list(images), "n_rois": None} if images else None
+                emitted = self._lookback_waiting.pop((in_h, in_w, B), None)
+                if own is not None:
+                    self._lookback_waiting[(in_h, in_w, B)] = own
+                words = s.lb_out[1].numel()
+                s.lb_pin[:words].copy_(s.lb_out[1].view(-1), non_blocking=True)
+                s.lb_pin[words:].copy_(s.lb_out[2], non_blocking=True)
             for i in range(len(images)):
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
+                if s.track:
+                    s.track_pin[i].copy_(s.track_out[i], non_blocking=True)
+            for i in range(len(emitted["images"]) if emitted else 0 if s.track_lookback else len(images)):
                 if s.encode == JPEG_ENCODE:
                     s.png_pin[i].copy_(s.png_dev[i][:s.first_copy], non_blocking=True)
                 elif s.encode:
                     s.png_pin[i].copy_(s.png_dev[i], non_blocking=True)
                 elif s.annotate:
                     s.frame_io[i][1].copy_(s.frame_io[i][0], non_blocking=True)
-                if s.track:
-                    s.track_pin[i].copy_(s.track_out[i], non_blocking=True)
             s.event.record(st)
         s.busy = True
-        return Ticket(s, list(images))
+        return Ticket(s, list(images), own, emitted)
 
     def _stage_files(self, s, files):
         """Host side of a pass whose frames the device decodes: [item table | the files' bytes back to back] into the slot's one pinned
@@ -1267,10 +1371,12 @@ class DetectionEntry:
                 for i, name in enumerate(s.jpg_names):
                     if name is not None and int(words[i]):          # (the .jpg items' words, then the .png items')
                         ops.raise_damaged(s.jpg_decs[i], int(words[i]), name)
-            if s.amax is not None:
+            if s.amax is not None and ticket.image:          # (a look-back flush brings no image: its pass's detections are not read, nor copied back)
                 bits = int(s.out_pin[0].numpy()[2])                 # the pass's f16x3 status word (pipeline._pass_status)
                 if bits:
                     raise FrcnnError("f16x3 pass not trustworthy (%s): status %d; run the image on the native or bf16x6 engine" % (ops.h3_status_text(bits), bits))
+            if s.track_lookback:
+                return self._collect_lookback(ticket)
             for i in range(len(ticket.image)):
                 packed = s.out_pin[i].numpy()
                 nd, n_rois = int(packed[0]), int(packed[1])
@@ -1287,28 +1393,59 @@ class DetectionEntry:
                         dets[k]["track_id"] = int(t_id[k])
                     dets += [{"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(),
                               "track_id": int(t_id[k]), "held": int(t_age[k])} for k in range(nd, int(n_rows[0]))]
-                if s.encode == JPEG_ENCODE:
-                    row = s.png_pin[i].numpy()
-                    n = int(row[0:4].view(np.int32)[0])
-                    if not 0 < n <= s.png_bound:
-                        raise FrcnnError("device JPEG encoder: length word %d outside (0, %d]" % (n, s.png_bound))
-                    data = row[16:min(16 + n, s.first_copy)].tobytes()
-                    if 16 + n > s.first_copy:               # a file longer than the first copy: its remainder now (synchronous)
-                        data += s.png_dev[i][s.first_copy:16 + n].cpu().numpy().tobytes()
-                    res.append((n_rois, dets, data))
-                elif s.encode == Y4M_ENCODE:
-                    res.append((n_rois, dets, s.png_pin[i].numpy().tobytes()))      # the frame's record: a fixed size, no length word
-                elif s.encode:
-                    row = s.png_pin[i].numpy()
-                    n = int(row[-16:-12].view(np.int32)[0])
-                    if not 0 < n <= s.png_bound:
-                        raise FrcnnError("device PNG encoder: length word %d outside (0, %d]" % (n, s.png_bound))
-                    res.append((n_rois, dets, row[:n].tobytes()))
-                else:
-                    res.append((n_rois, dets, s.pix_hosts[i].copy()) if s.annotate else (n_rois, dets))
+                res.append((n_rois, dets) + self._payload(s, i))
             return res
         finally:
             s.busy = False                               # whatever happened while decoding the records: the slot is free again
+
+    def _payload(self, s, i):
+        """What frame i of a collected pass returns behind (num_rois, dets): () , (the frame,) or (the encoded file's bytes,)."""
+        if s.encode == JPEG_ENCODE:
+            row = s.png_pin[i].numpy()
+            n = int(row[0:4].view(np.int32)[0])
+            if not 0 < n <= s.png_bound:
+                raise FrcnnError("device JPEG encoder: length word %d outside (0, %d]" % (n, s.png_bound))
+            data = row[16:min(16 + n, s.first_copy)].tobytes()
+            if 16 + n > s.first_copy:               # a file longer than the first copy: its remainder now (synchronous)
+                data += s.png_dev[i][s.first_copy:16 + n].cpu().numpy().tobytes()
+            return (data,)
+        elif s.encode == Y4M_ENCODE:
+            return (s.png_pin[i].numpy().tobytes(),)      # the frame's record: a fixed size, no length word
+        elif s.encode:
+            row = s.png_pin[i].numpy()
+            n = int(row[-16:-12].view(np.int32)[0])
+            if not 0 < n <= s.png_bound:
+                raise FrcnnError("device PNG encoder: length word %d outside (0, %d]" % (n, s.png_bound))
+            return (row[:n].tobytes(),)
+        else:
+            return (s.pix_hosts[i].copy(),) if s.annotate else ()
+
+    def _collect_lookback(self, ticket):
+        """``collect_batch`` of a look-back pass: this submit's num_rois are kept for the pass that will emit its frames, and the results
+        are those of the group this pass emitted, read from the emitted tracked buffers."""
+        s, rev = ticket.slot, self.rev_class_mapping
+        if ticket.own is not None:
+            ticket.own["n_rois"] = [int(s.out_pin[i].numpy()[1]) for i in range(len(ticket.image))]
+        group = ticket.emitted
+        if group is None:
+            return []
+        if group["n_rois"] is None:
+            raise FrcnnError("collect_batch: look-back tickets are collected in submit order")
+        lb = s.lb_pin.numpy()
+        words = (lb.size - 4) // s.batch
+        if int(lb[-4]) != len(group["images"]):
+            raise FrcnnError("look-back window: %d frames emitted for a group of %d" % (int(lb[-4]), len(group["images"])))
+        res = []
+        for i in range(len(group["images"])):
+            n_rows, n_live, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(lb[i * words:(i + 1) * words])
+            dets = []
+            for k in range(int(n_rows[0])):
+                d = {"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(), "track_id": int(t_id[k])}
+                if k >= int(n_live[0]):
+                    d["held" if int(t_age[k]) > 0 else "backfilled"] = abs(int(t_age[k]))
+                dets.append(d)
+            res.append((group["n_rois"][i], dets) + self._payload(s, i))
+        return res
 
     def collect(self, ticket):
         return self.collect_batch(ticket)[0]

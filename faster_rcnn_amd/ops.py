@@ -1375,6 +1375,74 @@ def track_update_motion(state, mstate, frames_u8, frame_stride, det_packed, n_fr
     return out
 
 
+TRACK_LOOKBACK = _lib.TRACK_LOOKBACK            # (smallest, largest, the default) look-back of ``track_lookback``, in frames
+
+
+def track_lookback_option(n=None):
+    """(host only) The look-back in frames checked, None replaced by the default 8: an integer in 1..16.  ValueError with the reason."""
+    lo, hi, default = TRACK_LOOKBACK
+    n = default if n is None else n
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not lo <= int(n) <= hi:
+        raise ValueError("track lookback=%r: an integer in %d..%d" % (n, lo, hi))
+    return int(n)
+
+
+def track_lookback_state(frames, h, w, max_rows, capacity, back):
+    """An empty look-back window for calls of ``frames`` frames of (h, w) whose tracked buffers have ``max_rows`` + ``capacity`` rows: a
+    zeroed uint8 device tensor of frcnn_track_lookback_state_bytes bytes, [count, half, back_overflow, 0 x 5 (int32) | two halves of
+    ``frames`` cells, each a widened tracked buffer of R2 = max_rows + capacity + back rows and a frame]
+    (include/ext/frcnn_hip_track_lookback.h)."""
+    _require_gpu()
+    n = int(_lib.load().frcnn_track_lookback_state_bytes(int(frames), int(h), int(w), int(max_rows), int(capacity), int(back)))
+    if n == 0:
+        raise _lib.FrcnnError("track_lookback_state: frames=%r, %rx%r, max_rows=%r, capacity=%r, back=%r out of range (at most %d rows in all)"
+                              % (frames, h, w, max_rows, capacity, back, _lib.REDACT_MAX_ROWS))
+    return torch.zeros(n, dtype=torch.uint8, device="cuda")
+
+
+def track_lookback_reset(window):
+    """Empty the window (on the current stream): the header is zeroed, so no frame waits and back_overflow is 0."""
+    window[:_lib.TRACK_LOOKBACK_HEADER].zero_()
+    return window
+
+
+def track_lookback(window, frames_u8, frame_stride, tracked, n_frames, capacity, back, h, w, lookback=TRACK_LOOKBACK[2], radius=0, grow=0, out=None):
+    """One call of the look-back rule (DESIGN §8 "Look-back rule", frcnn_track_lookback): the B frames of the call -- ``frames_u8`` holds
+    frame f, (h, w, 3) uint8 as uploaded, at byte ``f * frame_stride``; ``tracked`` is ``track_update``'s (B, 4 + 8R) result for them --
+    join ``window`` (``track_lookback_state``), every track born in them is followed BACKWARDS over at most ``lookback`` frames by the
+    block match of radius ``radius`` (0: its box stands still) and leaves one back-filled row, age -k, in each of those frames, and the
+    frames the window held before the call are emitted: -> ``out`` = (frames (B, h, w, 3) uint8, tracked (B, 4 + 8 R2) int32, count
+    int32 [1]), R2 = R + ``back``; the first ``count`` entries are the emitted frames, oldest first, untouched, with their widened
+    buffers (``redact_u8`` and ``annotate_u8`` take one with ``tracked=True``).  ``n_frames``: an int32 device tensor; its first word
+    says how many of the B frames are real, 0 emits again and changes nothing, < 0 emits and empties the window.  Five launches; every
+    count is read on the device: the call can be captured in a graph."""
+    _require_gpu()
+    h, w, cap, back = int(h), int(w), int(capacity), int(back)
+    assert window.is_cuda and window.dtype == torch.uint8 and window.dim() == 1 and window.is_contiguous()
+    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.is_contiguous() and tracked.dim() == 2
+    B, words = int(tracked.shape[0]), int(tracked.shape[1])
+    R = (words - 4) // 8
+    rows, R2 = R - cap, R + back
+    assert words == 4 + 8 * R and rows >= 1, "track_lookback: tracked buffers of %d words for capacity=%d" % (words, cap)
+    need = int(_lib.load().frcnn_track_lookback_state_bytes(B, h, w, rows, cap, back))
+    if need and int(window.numel()) != need:
+        raise _lib.FrcnnError("track_lookback: the window has %d bytes; one for calls of %d frames of %dx%d with %d + %d + %d rows has %d "
+                              "(track_lookback_state with the call's frames, rows, capacity and back)" % (window.numel(), B, h, w, rows, cap, back, need))
+    assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
+    assert int(frame_stride) >= 0 and int(frames_u8.numel()) >= (B - 1) * int(frame_stride) + 3 * h * w
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    if out is None:
+        out = (torch.zeros((B, h, w, 3), dtype=torch.uint8, device="cuda"), torch.zeros((B, 4 + 8 * R2), dtype=torch.int32, device="cuda"),
+               torch.zeros(1, dtype=torch.int32, device="cuda"))
+    o_frames, o_tracked, o_count = out
+    assert o_frames.is_cuda and o_frames.dtype == torch.uint8 and o_frames.is_contiguous() and tuple(o_frames.shape) == (B, h, w, 3)
+    assert o_tracked.is_cuda and o_tracked.dtype == torch.int32 and o_tracked.is_contiguous() and tuple(o_tracked.shape) == (B, 4 + 8 * R2)
+    assert o_count.is_cuda and o_count.dtype == torch.int32 and o_count.numel() >= 1
+    _lib.call("frcnn_track_lookback", _p(window), _p(frames_u8), int(frame_stride), _p(tracked), words, B, _p(n_frames), rows, cap, back,
+              int(lookback), int(radius), int(grow), h, w, _p(o_frames), 3 * h * w, _p(o_tracked), 4 + 8 * R2, _p(o_count), _stream())
+    return out
+
+
 def split_tracked(buf):
     """Views (n_rows, n_live, next_id, overflow, bbox, cls, prob, id, age) into ONE tracked buffer (device tensor or its host copy,
     torch or numpy), as ``split_detections`` cuts up a ``det_packed``: the four counts are one-word views, bbox is (R, 4), prob float32."""

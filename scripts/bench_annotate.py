@@ -26,7 +26,9 @@ to PNG files with the device encoder -- and reports the frames/s of both and the
 ``--track`` runs the tracker's cost instead (``run_track``): the ``--redact`` leg's frames and redaction without and with ``--track``
 (IoU 30 %, hold 8, grow 0, the defaults), alternating in one session through in-memory annotating passes; ``--track_motion`` likewise
 (``run_track_motion``) the ``--track`` leg without and with ``--track_motion 8``, and the tracker part of one pass alone; tracking passes replay on one
-stream of the engine, so the figure includes what that ordering costs.
+stream of the engine, so the figure includes what that ordering costs.  ``--track_lookback`` (``run_track_lookback``) runs the
+``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
+look-back call of one pass alone.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
@@ -78,15 +80,19 @@ def build(cfg):
 
 def annotate_in_memory(eng, resized, ratios, **kwargs):
     """(b): the frames through annotating passes, eng.batch per pass, eng.in_flight passes in flight (annotate_images' loop
-    without the files).  ``kwargs``: further arguments of submit_batch (``redact``)."""
+    without the files).  ``kwargs``: further arguments of submit_batch (``redact``).  With ``track_lookback`` a flush submit ends the
+    list: the passes return the frames of the pass before."""
     B, window, frames = eng.batch, [], []
     for i in range(0, len(resized), B):
         part = resized[i:i + B]
         window.append(eng.submit_batch(part, ratios[i:i + B], 0.0, [eng.host_pixels(r) for r in part], batch=B, annotate=True, **kwargs))
         if len(window) >= eng.in_flight:
             frames += [r[2] for r in eng.collect_batch(window.pop(0))]
+    if kwargs.get("track_lookback") is not None:
+        window.append(eng.submit_batch([], [], 0.0, [], batch=B, annotate=True, **kwargs))
     while window:
         frames += [r[2] for r in eng.collect_batch(window.pop(0))]
+    assert len(frames) == len(resized)
     return frames
 
 
@@ -420,6 +426,100 @@ def run_track_motion(name, cfg, n_frames, reps, content="noise"):
     return res
 
 
+LOOKBACK_BIRTHS = 8                                      # births per frame of ``lookback_part_us``'s synthetic pass
+
+
+def lookback_part_us(eng, h, w, lookback, radius, iters=20):
+    """HIP-event time of ops.track_lookback for ONE pass of eng.batch noise frames, outside a graph, on a window of its own: every frame
+    of the pass brings LOOKBACK_BIRTHS new tracks (random boxes of 40..120 pixels a side), so every call chains B x LOOKBACK_BIRTHS births
+    back over ``lookback`` frames, into the frames of the call before too.  -> the median in microseconds."""
+    import numpy as np
+    import torch
+    from faster_rcnn_amd import ops
+    B, rows, cap = eng.batch, 300, ops.track_capacity(eng.track_state())
+    R, back = rows + cap, min(cap, 512 - rows - cap)
+    rs = np.random.RandomState(11)
+    frames = torch.from_numpy(rs.randint(0, 256, (B, h, w, 3)).astype(np.uint8)).cuda()
+    tracked = np.zeros((B, 4 + 8 * R), dtype=np.int32)
+    tracked[:, 4:4 + 5 * R] = -1
+    n = LOOKBACK_BIRTHS
+    window = ops.track_lookback_state(B, h, w, rows, cap, back)
+    nf = torch.tensor([B], dtype=torch.int32, device="cuda")
+    out, times, next_id = None, [], 1
+    for it in range(iters + 1):
+        for f in range(B):                                          # ids go on rising from call to call: every row is a birth
+            x, y = rs.randint(0, w - 120, n), rs.randint(0, h - 120, n)
+            side = rs.randint(40, 121, n)
+            tracked[f, 4:4 + 4 * n] = np.stack([x, y, x + side, y + side], axis=1).reshape(-1)
+            tracked[f, 4 + 4 * R:4 + 4 * R + n] = 1
+            tracked[f, 4 + 6 * R:4 + 6 * R + n] = np.arange(next_id, next_id + n)
+            next_id += n
+            tracked[f, :4] = (n, n, next_id, 0)
+        dev = torch.from_numpy(tracked).cuda()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = ops.track_lookback(window, frames, h * w * 3, dev, nf, cap, back, h, w, lookback, radius, TRACK_LEG[2], out=out)
+        b.record()
+        b.synchronize()
+        if it:                                                      # (the first call has no window in front of it)
+            times.append(a.elapsed_time(b) * 1000.0)
+    return round(statistics.median(times), 1)
+
+
+def run_track_lookback(name, cfg, n_frames, reps, content="noise"):
+    """``--track_lookback``: what the look-back costs on top of tracking with the motion step.  One pair of legs in ONE session,
+    alternating inside every repetition: ``run_track``'s frames through in-memory annotating passes with ``redact=REDACT_LEG,
+    track=TRACK_LEG, track_motion=MOTION_LEG``, without and with ``track_lookback`` = min(8, frames per pass), the command line's
+    default (the tracker is reset in front of every run; the look-back run ends with its flush submit).  Reports frames/s of both and
+    their ratio, the tracker's state and the windows' back_overflow at the end, and the HIP-event time of the look-back call of one pass
+    alone (``lookback_part_us``)."""
+    import numpy as np
+    from faster_rcnn_amd import entry, ops, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+    lookback = min(ops.TRACK_LOOKBACK[2], eng.batch)
+    overflow = []
+
+    def leg(**kw):
+        def run():
+            eng.track_reset()
+            out = annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, track=TRACK_LEG, track_motion=MOTION_LEG, **kw)
+            if kw:                                                  # (read in front of the next reset)
+                overflow.append([int(win[:12].view(torch.int32)[2]) for win, _ in eng._track_lookback_windows.values()])
+            return out
+        return run
+
+    import torch
+    legs = {"track_motion": leg(), "track_lookback": leg(track_lookback=lookback)}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    torch.cuda.synchronize()
+    state = eng.track_state().cpu().numpy()
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact": ["all", "blur", 12, 0], "track": list(TRACK_LEG), "track_motion": MOTION_LEG, "track_lookback": lookback,
+           "images_per_pass": eng.batch, "in_flight": eng.in_flight,
+           "tracker": {"live_slots": int(state[0]), "ids_issued": int(state[1]), "overflow": int(state[2]), "frames": int(state[3])},
+           "back_overflow": overflow[-1]}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["lookback_over_motion"] = round(statistics.median(times["track_motion"]) / statistics.median(times["track_lookback"]), 3)
+    res["lookback_part_us"] = {"births_per_frame": LOOKBACK_BIRTHS, "track_lookback": lookback_part_us(eng, h, w, lookback, MOTION_LEG),
+                               "track_lookback_radius_0": lookback_part_us(eng, h, w, lookback, 0)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--frames", type=int, default=256)
@@ -437,6 +537,8 @@ def main():
                                                          "--track (IoU 30, hold 8), alternating in one session (passes in memory)")
     ap.add_argument("--track_motion", action="store_true", help="instead of the legs above: the --track leg's frames, redaction and tracking "
                                                                 "without and with --track_motion 8, alternating in one session")
+    ap.add_argument("--track_lookback", action="store_true", help="instead of the legs above: the --track --track_motion 8 leg without and "
+                                                                  "with --track_lookback at its default, alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -445,6 +547,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.track_lookback:
+            out[name] = run_track_lookback(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.track_motion:
             out[name] = run_track_motion(name, PAIRS[name], args.frames, args.reps, args.content)
