@@ -402,6 +402,15 @@ TRACK_MOTION_SIGNATURES = {
 # the block match's search radius: (smallest, largest, the default) (FRCNN_TRACK_MOTION_MIN_RADIUS / _MAX_RADIUS)
 TRACK_MOTION_RADIUS = (1, 16, 8)
 
+TRACK_INTERVAL_VERSION = 1      # include/ext/frcnn_hip_track_interval.h FRCNN_TRACK_INTERVAL_VERSION
+TRACK_INTERVAL_SIGNATURES = {
+    "frcnn_track_interval_version": (I, []),
+    "frcnn_track_update_interval": (I, [P, I, P, P, ctypes.c_longlong, P, ctypes.c_longlong, I, P, I, P, I, I, I, I, I, I, I, I, P,
+                                        ctypes.c_longlong, P]),
+}
+# frames from one key frame to the next: (smallest at the ABI, largest) (FRCNN_TRACK_INTERVAL_MIN / _MAX); the public option starts at 2
+TRACK_INTERVAL = (1, 16)
+
 TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
 TRACK_LOOKBACK_SIGNATURES = {
     "frcnn_track_lookback_version": (I, []),
@@ -545,6 +554,13 @@ def load():
     if lib.frcnn_track_lookback_version() != TRACK_LOOKBACK_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_lookback_version()} of the tracker's look-back extension, this binding "
                          f"{TRACK_LOOKBACK_VERSION} (include/ext/frcnn_hip_track_lookback.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in TRACK_INTERVAL_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_track_interval_version() != TRACK_INTERVAL_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_interval_version()} of the tracker's interval extension, this binding "
+                         f"{TRACK_INTERVAL_VERSION} (include/ext/frcnn_hip_track_interval.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

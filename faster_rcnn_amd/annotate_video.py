@@ -63,6 +63,13 @@ consecutive frames (ops.track_update_motion, csrc/track_motion.hip; DESIGN §8 "
 either way on a 32 x 32 sample grid of the box, taken only when it gains a grey level per sample): a held box follows its object instead
 of standing still, and a fast object is matched where it now is.  The printed lines and ``--tracks_out`` keep their form: held rows are
 still not written.
+``detect_every=K`` (``--detect_every K``, with ``--track --track_motion``; 2..16) runs the detector on every K-th frame only
+(ops.track_update_interval, csrc/track_interval.hip; DESIGN §8 "Interval rule"): a pass takes B * K frames, and on the frames between
+two detected ones every track's box follows the pixels under it by the block match alone -- drawn, redacted and written to
+``--tracks_out`` with the prob of its last match, printed with "propagated": True.  Nothing is matched, aged or born there: ``hold``
+counts detected frames.  The K-th frames are counted within each group of at most B * K consecutive frames of one geometry: in a video
+that is every K-th frame, in a list of mixed sizes a detected frame follows every change of size.  Not together with
+``--track_lookback``, and not on the one-frame-at-a-time paths.
 """
 import collections
 import os
@@ -70,7 +77,7 @@ import pathlib
 
 import numpy as np
 
-from . import entry, ops, shapes, voc_dets, y4m
+from . import _lib, entry, ops, shapes, voc_dets, y4m
 from .util import resize_imgs
 
 STRIDE = 16                                       # get_dets' default: annotate_video.py:29 passes none
@@ -386,6 +393,52 @@ def track_lookback_from_args(args):
         raise ValueError("--track_lookback: %s" % e) from None
 
 
+def detect_every_from_args(args):
+    """(host only) The detection interval the command line asks for -> K as ``annotate_images(detect_every=...)`` takes it, or None without
+    the flag.  ValueError, with the reason, for ``--detect_every`` without ``--track --track_motion``, together with ``--track_lookback``
+    and for a value outside 2..16."""
+    if args.detect_every is None:
+        return None
+    if not args.track or args.track_motion is None:
+        raise ValueError("--detect_every=%s follows the tracks by block matching between two detected frames: it needs --track --track_motion"
+                         % args.detect_every)
+    if args.track_lookback is not None:
+        raise ValueError("--detect_every together with --track_lookback is not supported: the look-back window keeps one tracked buffer per "
+                         "detected frame")
+    try:
+        return ops.track_interval_option(args.detect_every)
+    except ValueError as e:
+        raise ValueError("--detect_every: %s" % e) from None
+
+
+def _detect_every(detect_every, track, track_motion, track_lookback, eng, B):
+    """``annotate_images`` / ``annotate_stream``'s ``detect_every`` checked -> the K of their passes, or None."""
+    if detect_every is None:
+        return None
+    if track is None or track_motion is None:
+        raise ValueError("detect_every=%r follows the tracks by block matching between two detected frames: it needs track=(thr, hold, grow) "
+                         "and track_motion=R" % (detect_every,))
+    if track_lookback is not None:
+        raise ValueError("detect_every=%r together with track_lookback=%r is not supported: the look-back window keeps one tracked buffer per "
+                         "detected frame" % (detect_every, track_lookback))
+    if eng is None:
+        raise ValueError("detect_every=%r runs the detector once per pass of several frames: the eager path (a foreign model) detects one "
+                         "frame at a time and cannot" % (detect_every,))
+    k = ops.track_interval_option(detect_every)
+    if B * k > _lib.TRACK_MAX_FRAMES:                     # (what submit_batch would refuse at the first pass)
+        raise ValueError("detect_every=%d with passes of %d images is %d frames per pass: at most %d here" % (k, B, B * k, _lib.TRACK_MAX_FRAMES // B))
+    return k
+
+
+def _every_parts(group, B, every):
+    """The passes of a ``detect_every`` group of <= B * K frames of one geometry -> [(frames, images of the pass)]: one pass of B (padded)
+    when its key frames fill at least half of it, else one-image passes of K frames."""
+    keys = -(-len(group) // every)
+    if B > 1 and keys >= max(2, B // 2):
+        return [(group, B)]
+    return [(group[i:i + every], 1) for i in range(0, len(group), every)]
+
+
 def _lookback_frames(track_lookback, track, eng, B):
     """``annotate_images`` / ``annotate_stream``'s ``track_lookback`` checked -> the look-back of their passes, or None."""
     if track_lookback is None:
@@ -441,12 +494,15 @@ def _print_drawn(dets, width, height):
 
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
-                        frame_no=1, track_motion=None, track_lookback=None):
+                        frame_no=1, track_motion=None, track_lookback=None, detect_every=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
     ``tracks_out``: a text file that receives the frame's MOT lines under the number ``frame_no``.  ``track_motion`` = R (with
     ``track``): the tracks' boxes are first moved with the pixels under them, at most R pixels either way (DESIGN §8 "Motion rule")."""
+    if detect_every is not None:
+        raise ValueError("detect_every=%r runs the detector once per pass of several frames: get_annotated_frame detects its one frame and "
+                         "cannot; use annotate_images or annotate_stream" % (detect_every,))
     if track_lookback is not None:
         raise ValueError("track_lookback=%r delays the output: get_annotated_frame returns its frame at once and cannot; use annotate_images "
                          "or annotate_stream" % (track_lookback,))
@@ -644,13 +700,13 @@ def directory_frames(input_dir, image_filenames, jpeg_decoder=None, png_decoder=
 
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
-                    redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None):
+                    redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every``: as ``annotate_images``."""
     from concurrent.futures import ThreadPoolExecutor
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
@@ -689,11 +745,14 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
     if redact is not None or not draw:                    # (else the passes, and their keys, are the ones without the arguments)
         kwargs = dict(kwargs, redact=redact, draw=draw)
     mapping = training_manager.class_mapping
+    every = _detect_every(detect_every, track, track_motion, track_lookback, eng, None if eng is None else eng.batch)
     lookback = _lookback_frames(track_lookback, track, eng, None if eng is None else eng.batch)
     if track is not None:                                 # a new sequence; its frames are submitted in stream order, as every stream's are
         kwargs = dict(kwargs, track=track, **motion)
         if lookback is not None:
             kwargs["track_lookback"] = lookback
+        if every is not None:
+            kwargs["detect_every"] = every
         reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
 
     if eng is None:                                       # eager path / foreign models: one frame at a time, converted on the device
@@ -721,7 +780,8 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
         return
 
     B = eng.batch
-    ahead = 2 * eng.in_flight * B
+    F = B * (every or 1)                                  # frames of a full pass
+    ahead = 2 * eng.in_flight * F
     read = ThreadPoolExecutor(max_workers=1)              # the stream is sequential: one reader, ``ahead`` frames in front of the passes
     write = ThreadPoolExecutor(max_workers=1 if to_video else max(1, WRITE_THREADS))
     pending, writes, window = collections.deque(), [], []
@@ -771,8 +831,11 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
             if last_key[0] not in (None, eng.geometry_of(group[0][5])):
                 flush()
             last_key[0] = eng.geometry_of(group[0][5])
+        if every is not None:                             # the key frames 0, K, ... of a pass go to the network, every frame goes up
+            parts = _every_parts(group, B, every)
         for part, take in parts:
-            ticket = eng.submit_batch([g[3] for g in part], [g[4] for g in part], DET_THRESHOLD, [g[5] for g in part],
+            keys = part[::every or 1]
+            ticket = eng.submit_batch([g[3] for g in keys], [g[4] for g in keys], DET_THRESHOLD, [g[5] for g in part],
                                       batch=take, annotate=True, **kwargs)
             window.append(([(g[0], g[1], g[2]) for g in part], ticket))
             if lookback is not None:
@@ -796,7 +859,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                 continue
             label, frame, resized, ratio, pixels = got
             k = eng.geometry_of(pixels)
-            if group and (k != key or len(group) == B):
+            if group and (k != key or len(group) == F):
                 submit(group)
                 group = []
             group.append((pos, label, frame, resized, ratio, pixels))
@@ -821,7 +884,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
-                    track_lookback=None):
+                    track_lookback=None, detect_every=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -845,7 +908,15 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     ``track_lookback``: the frames as ``track_lookback_from_args`` returns them (with ``track``; TRACK_LOOKBACK_AUTO: as many as a pass
     holds, at most 8) -- every new track is followed BACK over that many frames and hidden there too (DESIGN §8 "Look-back rule").  Every
     group then goes through a full pass of B frames, a pass returns the frames of the pass before it and a flush ends the list: each
-    frame is written and printed when it is emitted, the same lines in the same order.  The eager path refuses it."""
+    frame is written and printed when it is emitted, the same lines in the same order.  The eager path refuses it.
+    ``detect_every``: K as ``detect_every_from_args`` returns it (with ``track`` and ``track_motion``, not with ``track_lookback``) -- the
+    detector runs on every K-th frame only and a pass takes B * K frames; on the frames between, every track's box follows the pixels under
+    it (DESIGN §8 "Interval rule"), is drawn, redacted and written to ``tracks_out`` with the prob of its last match.  Nothing is matched,
+    aged or born between two detected frames: ``hold`` counts detected frames.  The K-th frames are counted per GROUP, not over the list:
+    a group is a run of at most B * K consecutive frames of one geometry, it is cut where the geometry changes, and its frames 0, K,
+    2K, ... are the detected ones (a group whose key frames fill under half a pass goes through one-image passes of K frames, the same
+    key frames).  With frames of one size, a video, every group but the last is full and that is every K-th frame of the list; in a list
+    of mixed sizes a detected frame follows every change of geometry.  The eager path refuses it."""
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     motion = {} if track_motion is None else {"track_motion": track_motion}
@@ -876,6 +947,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
     pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
     mapping = training_manager.class_mapping
+    every = _detect_every(detect_every, track, track_motion, track_lookback, eng, None if eng is None else eng.batch)
     lookback = _lookback_frames(track_lookback, track, eng, None if eng is None else eng.batch)
     if track is not None:
         reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
@@ -907,9 +979,12 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         edit = dict(edit, track=track, **motion)
     if lookback is not None:
         edit["track_lookback"] = lookback
+    if every is not None:
+        edit["detect_every"] = every
+    F = B * (every or 1)                                  # frames of a full pass
     decode = ThreadPoolExecutor(max_workers=max(1, DECODE_THREADS))
     write = ThreadPoolExecutor(max_workers=max(1, WRITE_THREADS))
-    ahead = 2 * eng.in_flight * B
+    ahead = 2 * eng.in_flight * F
     pending, writes, window = {}, [], []
     waiting, last_key = collections.deque(), [None]      # look-back: the groups whose frames a later pass emits; the geometry of the last pass
 
@@ -940,8 +1015,11 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             if last_key[0] not in (None, eng.geometry_of(group[0][4])):
                 flush()
             last_key[0] = eng.geometry_of(group[0][4])
+        if every is not None:                             # the key frames 0, K, ... of a pass go to the network, every frame goes up
+            parts = _every_parts(group, B, every)
         for part, take in parts:
-            ticket = eng.submit_batch([g[2] for g in part], [g[3] for g in part], DET_THRESHOLD, [g[4] for g in part],
+            keys = part[::every or 1]
+            ticket = eng.submit_batch([g[2] for g in keys], [g[3] for g in keys], DET_THRESHOLD, [g[4] for g in part],
                                       batch=take, annotate=True, encode=encode, quality=quality, **jpeg_mode, **edit)
             window.append(([(g[0], g[1]) for g in part], ticket))
             if lookback is not None:
@@ -965,7 +1043,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
                     pending[j] = decode.submit(load, paths[j])
             frame, resized, ratio, pixels = pending.pop(i).result()
             k = eng.geometry_of(pixels)
-            if group and (k != key or len(group) == B):
+            if group and (k != key or len(group) == F):
                 submit(group)
                 group = []
             group.append((i, frame, resized, ratio, pixels))
@@ -1064,6 +1142,11 @@ def build_parser():
     p.add_argument("--track_lookback", dest="track_lookback", type=int, nargs="?", const=TRACK_LOOKBACK_AUTO, default=None, metavar="N",
                    help="hide every new track in the N frames BEFORE its first detection too (1..16 and at most the frames of one pass; "
                         "bare: as many as a pass holds, at most 8); the output runs one pass behind the input (needs --track)")
+    p.add_argument("--detect_every", dest="detect_every", type=int, default=None, metavar="K",
+                   help="run the detector on every K-th frame only, 2..16; on the frames between, every track's box follows the pixels "
+                        "under it by block matching and is drawn, redacted and written to --tracks_out with the prob of its last match. "
+                        "Nothing is matched, aged or born there: --track_hold counts DETECTED frames and a held box does not grow in "
+                        "between (needs --track --track_motion; not with --track_lookback)")
     p.add_argument("--tracks_out", dest="tracks_out", default=None, metavar="PATH",
                    help="write the tracks as MOTChallenge lines frame,id,left,top,width,height,prob,cls,-1,-1 (needs --track)")
     return p
@@ -1133,6 +1216,9 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     track_lookback = track_lookback_from_args(args)
     if track_lookback is not None:
         tracking["track_lookback"] = track_lookback
+    detect_every = detect_every_from_args(args)
+    if detect_every is not None:
+        tracking["detect_every"] = detect_every
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

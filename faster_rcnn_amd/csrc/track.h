@@ -1,4 +1,4 @@
-// What csrc/track_motion.hip shares with csrc/track.hip: frcnn_track_update's argument checks and the launch of its kernel on a part of
+// What csrc/track_motion.hip and csrc/track_interval.hip share with csrc/track.hip: frcnn_track_update's argument checks and the launch of its kernel on a part of
 // a call's frames (a kernel is launched from the translation unit that defines it).
 #pragma once
 #include "common.h"
@@ -14,5 +14,11 @@ int track_check(const char* who, const int32_t* state, int capacity, const int32
 void track_launch(int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int first, int frames, int total,
                   const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
                   int32_t* out, long long out_stride, hipStream_t stream);
+
+// The same with the buffers of frame ``first`` given as they lie: ``det`` and ``out`` are THAT frame's (the interval extension, whose
+// detections are not one buffer per frame)
+void track_launch_at(int32_t* state, int capacity, const int32_t* det, long long det_stride, int first, int frames, int total,
+                     const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
+                     int32_t* out, long long out_stride, hipStream_t stream);
 
 }  // namespace frcnn

@@ -249,12 +249,18 @@ int track_check(const char* who, const int32_t* state, int capacity, const int32
     return FRCNN_OK;
 }
 
+void track_launch_at(int32_t* state, int capacity, const int32_t* det, long long det_stride, int first, int frames, int total,
+                     const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
+                     int32_t* out, long long out_stride, hipStream_t stream) {
+    k_track_update<<<1, TR_THREADS, 0, stream>>>(state, capacity, det, det_stride, first, frames, total, n_frames, max_rows, tracked, num_classes,
+                                                 thr, hold, grow, h, w, out, out_stride);
+}
+
 void track_launch(int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int first, int frames, int total,
                   const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
                   int32_t* out, long long out_stride, hipStream_t stream) {
-    k_track_update<<<1, TR_THREADS, 0, stream>>>(state, capacity, det_packed + (long long)first * det_stride, det_stride, first, frames, total,
-                                                 n_frames, max_rows, tracked, num_classes, thr, hold, grow, h, w,
-                                                 out + (long long)first * out_stride, out_stride);
+    track_launch_at(state, capacity, det_packed + (long long)first * det_stride, det_stride, first, frames, total, n_frames, max_rows, tracked,
+                    num_classes, thr, hold, grow, h, w, out + (long long)first * out_stride, out_stride, stream);
 }
 
 }  // namespace frcnn

@@ -9,6 +9,7 @@
 #include "../../include/ext/frcnn_hip_track.h"
 #include "../../include/ext/frcnn_hip_track_motion.h"
 #include "track.h"
+#include "track_motion.h"
 #include "track_motion_search.h"
 
 namespace frcnn {
@@ -62,6 +63,34 @@ __global__ void __launch_bounds__(256) k_motion_keep(const int32_t* state, uint8
 
 }  // namespace frcnn
 
+namespace frcnn {
+
+int motion_check(const char* who, const uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride, int frames, int radius, int h,
+                 int w) {
+    if (!motion_state || !frames_u8) return fail(FRCNN_E_ARG, "%s: null pointer", who);
+    if (reinterpret_cast<uintptr_t>(motion_state) & 3) return fail(FRCNN_E_ARG, "%s: motion_state is not 4-byte aligned", who);
+    if (radius < FRCNN_TRACK_MOTION_MIN_RADIUS || radius > FRCNN_TRACK_MOTION_MAX_RADIUS)
+        return fail(FRCNN_E_ARG, "%s: radius=%d not in [%d, %d]", who, radius, FRCNN_TRACK_MOTION_MIN_RADIUS, FRCNN_TRACK_MOTION_MAX_RADIUS);
+    const long long frame_bytes = 3LL * h * w;
+    if (frames > 1 && frame_stride < frame_bytes)
+        return fail(FRCNN_E_ARG, "%s: frame_stride=%lld bytes, a %dx%d frame has %lld", who, frame_stride, h, w, frame_bytes);
+    return FRCNN_OK;
+}
+
+void motion_search_launch(int32_t* state, int capacity, const uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride, int f,
+                          int frames, const int32_t* n_frames, int radius, int h, int w, hipStream_t stream) {
+    k_motion_search<<<capacity, TM_THREADS, 0, stream>>>(state, capacity, motion_state, frames_u8, frame_stride, f, frames, n_frames, radius, h, w);
+}
+
+void motion_keep_launch(const int32_t* state, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride, int frames,
+                        const int32_t* n_frames, int h, int w, hipStream_t stream) {
+    const long long frame_bytes = 3LL * h * w;
+    const int blocks = (int)((frame_bytes / 16 + 255) / 256 < 1024 ? (frame_bytes / 16 + 255) / 256 : 1024);
+    k_motion_keep<<<blocks < 1 ? 1 : blocks, 256, 0, stream>>>(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w);
+}
+
+}  // namespace frcnn
+
 using namespace frcnn;
 
 extern "C" int frcnn_track_motion_version(void) { return FRCNN_TRACK_MOTION_VERSION; }
@@ -76,23 +105,16 @@ extern "C" int frcnn_track_update_motion(int32_t* state, int capacity, uint8_t* 
                                          const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int h, int w,
                                          int32_t* out, long long out_stride, void* stream) {
     const char* who = "track_update_motion";
-    const int bad = track_check(who, state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow,
-                                h, w, out, out_stride);
+    int bad = track_check(who, state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow,
+                          h, w, out, out_stride);
+    if (!bad) bad = motion_check(who, motion_state, frames_u8, frame_stride, frames, radius, h, w);
     if (bad) return bad;
-    if (!motion_state || !frames_u8) return fail(FRCNN_E_ARG, "%s: null pointer", who);
-    if (reinterpret_cast<uintptr_t>(motion_state) & 3) return fail(FRCNN_E_ARG, "%s: motion_state is not 4-byte aligned", who);
-    if (radius < FRCNN_TRACK_MOTION_MIN_RADIUS || radius > FRCNN_TRACK_MOTION_MAX_RADIUS)
-        return fail(FRCNN_E_ARG, "%s: radius=%d not in [%d, %d]", who, radius, FRCNN_TRACK_MOTION_MIN_RADIUS, FRCNN_TRACK_MOTION_MAX_RADIUS);
-    const long long frame_bytes = 3LL * h * w;
-    if (frames > 1 && frame_stride < frame_bytes)
-        return fail(FRCNN_E_ARG, "%s: frame_stride=%lld bytes, a %dx%d frame has %lld", who, frame_stride, h, w, frame_bytes);
     hipStream_t st = as_stream(stream);
     for (int f = 0; f < frames; ++f) {
-        k_motion_search<<<capacity, TM_THREADS, 0, st>>>(state, capacity, motion_state, frames_u8, frame_stride, f, frames, n_frames, radius, h, w);
+        motion_search_launch(state, capacity, motion_state, frames_u8, frame_stride, f, frames, n_frames, radius, h, w, st);
         track_launch(state, capacity, det_packed, det_stride, f, 1, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow, h, w, out,
                      out_stride, st);
     }
-    const int blocks = (int)((frame_bytes / 16 + 255) / 256 < 1024 ? (frame_bytes / 16 + 255) / 256 : 1024);
-    k_motion_keep<<<blocks < 1 ? 1 : blocks, 256, 0, st>>>(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w);
+    motion_keep_launch(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w, st);
     return check_launch(who);
 }

@@ -304,7 +304,7 @@ class _Slot:
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
                  "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
-                 "track_lookback", "lb_out", "lb_pin", "_lb_raw")
+                 "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames")
 
     def __init__(self):
         for name in self.__slots__:
@@ -396,11 +396,13 @@ class GraphCache:
 
 
 class Ticket:
-    __slots__ = ("slot", "image", "own", "emitted")
+    __slots__ = ("slot", "image", "own", "emitted", "frames")
 
-    def __init__(self, slot, image, own=None, emitted=None):
-        # ``own`` / ``emitted`` (look-back passes): the record of this submit's group and of the group whose frames this pass emits
+    def __init__(self, slot, image, own=None, emitted=None, frames=None):
+        # ``own`` / ``emitted`` (look-back passes): the record of this submit's group and of the group whose frames this pass emits;
+        # ``frames``: the source frames of the submit (more than its images in a ``detect_every`` pass)
         self.slot, self.image, self.own, self.emitted = slot, image, own, emitted
+        self.frames = len(image) if frames is None else frames
 
 
 class DetectionEntry:
@@ -582,6 +584,19 @@ class DetectionEntry:
             raise FrcnnError("submit_batch: track=%r: (thr, hold, grow): %s" % (track, e)) from None
 
     @staticmethod
+    def detect_every_option(k, B):
+        """``submit_batch``'s ``detect_every`` checked against the pass's B network images -> K, 2..16 with B * K frames in one tracker
+        call.  FrcnnError with the reason."""
+        try:
+            k = ops.track_interval_option(k)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: detect_every=%r: %s" % (k, e)) from None
+        if B * k > _lib.TRACK_MAX_FRAMES:
+            raise FrcnnError("submit_batch: detect_every=%d with batch=%d is a pass of %d frames: one tracker call takes at most %d "
+                             "(FRCNN_TRACK_MAX_FRAMES)" % (k, B, B * k, _lib.TRACK_MAX_FRAMES))
+        return k
+
+    @staticmethod
     def track_motion_option(radius):
         """``submit_batch``'s ``track_motion`` checked -> the search radius, 1..16.  FrcnnError with the reason."""
         try:
@@ -610,9 +625,10 @@ class DetectionEntry:
         return t
 
     def _stage(self, s, seg, fine):
-        """The slot's staging on both sides of PCIe: [B frame segments of ``seg`` bytes | B x (resize_ratio, det_threshold)].
+        """The slot's staging on both sides of PCIe: [B frame segments of ``seg`` bytes | B x (resize_ratio, det_threshold)]; a
+        ``detect_every`` pass has ``s.frames`` = B * K segments in front of its B pairs.
         -> (the pinned side as a numpy array, the device view the pass reads the pairs from: (B, 2) f64, one image's (2,) for B = 1)."""
-        B, off = s.batch, s.batch * seg
+        B, off = s.batch, s.frames * seg
         s.seg = seg
         tail = 16 if s.track else 0                      # a tracking pass: | the count of real frames, int32 (ops.track_update's n_frames)]
         s.io_dev = torch.zeros(off + 16 * B + tail, dtype=torch.uint8, device="cuda")
@@ -637,14 +653,15 @@ class DetectionEntry:
         instead of the raw frame; with ``s.encode`` == "jpeg" as a JPEG file at ``s.quality`` in ``s.jpeg_mode`` = (subsampling, huffman)
         (ops.jpeg_encode_u8)."""
         B, pipe, annotate = s.batch, s.pipe, s.annotate
+        F, K = s.frames, s.every or 1                               # source frames of the pass; the network sees every K-th (F = B unless ``detect_every``)
         in_h, in_w = src if src is not None else (H, W)
         npix = in_h * in_w * 3
         pix_bytes = npix if self.device_preprocess else 4 * npix
         host, dyn = self._stage(s, (pix_bytes + 15) // 16 * 16, fine)
         seg = s.seg
         if self.device_preprocess:
-            s.pix_hosts = [host[i * seg:i * seg + npix].reshape(in_h, in_w, 3) for i in range(B)]
-            u8 = [s.io_dev[i * seg:i * seg + npix].view(in_h, in_w, 3) for i in range(B)]
+            s.pix_hosts = [host[i * seg:i * seg + npix].reshape(in_h, in_w, 3) for i in range(F)]
+            u8 = [s.io_dev[i * seg:i * seg + npix].view(in_h, in_w, 3) for i in range(F)]
             s.x_f32 = torch.empty((B, H, W, 3), dtype=torch.float32, device="cuda")
             if src is not None:
                 s.tabs = (torch.from_numpy(ops.resize_cubic_taps(W, in_w)).cuda(), torch.from_numpy(ops.resize_cubic_taps(H, in_h)).cuda())
@@ -654,7 +671,7 @@ class DetectionEntry:
             s.pix_hosts = [host[:pix_bytes].view(np.float32).reshape(H, W, 3)]
             s.x_f32 = s.io_dev[:pix_bytes].view(torch.float32).view(1, H, W, 3)
         # annotating pass: frame i is read back from its staging segment into the slot's own pinned segment after the replay
-        s.frame_io = [(s.io_dev[i * seg:i * seg + npix], s.io_pin[i * seg:i * seg + npix]) for i in range(B)] if annotate and not s.encode else None
+        s.frame_io = [(s.io_dev[i * seg:i * seg + npix], s.io_pin[i * seg:i * seg + npix]) for i in range(F)] if annotate and not s.encode else None
         tables = self.annotate_tables(not s.nodraw) if annotate else None
         if s.redact:
             # the redacted classes' boxes are hidden in each source frame IN FRONT of the drawing step, and so in front of every encoder;
@@ -687,16 +704,16 @@ class DetectionEntry:
             # fetches the rest of a longer file.
             subsampling, huffman = s.jpeg_mode
             s.png_bound = ops.jpeg_bound(in_h, in_w, subsampling, huffman)
-            s.png_dev = torch.zeros((B, 16 + (s.png_bound + 15) // 16 * 16), dtype=torch.uint8, device="cuda")
+            s.png_dev = torch.zeros((F, 16 + (s.png_bound + 15) // 16 * 16), dtype=torch.uint8, device="cuda")
             s.first_copy = min(16 + ops.jpeg_header_bytes() + npix // 4, 16 + s.png_bound)
             s.png_ws = torch.empty(ops.jpeg_workspace_bytes(in_h, in_w, subsampling, huffman), dtype=torch.uint8, device="cuda")
-            png_out = [(s.png_dev[i][16:16 + s.png_bound], s.png_dev[i][0:4].view(torch.int32)) for i in range(B)]
+            png_out = [(s.png_dev[i][16:16 + s.png_bound], s.png_dev[i][0:4].view(torch.int32)) for i in range(F)]
             uploaded_rgb = src is not None and bool(int(flip) & 2)
         elif s.encode == Y4M_ENCODE:
             # a frame's row: its record [Y | Cb | Cr], ops.y4m_frame_bytes long: the slot's output area is B records back to back
             chroma, yrange = s.y4m_mode
             s.png_bound = ops.y4m_frame_bytes(in_h, in_w, chroma)
-            s.png_dev = torch.zeros((B, s.png_bound), dtype=torch.uint8, device="cuda")
+            s.png_dev = torch.zeros((F, s.png_bound), dtype=torch.uint8, device="cuda")
             uploaded_rgb = src is not None and bool(int(flip) & 2)
         elif s.encode:
             # a frame's row: [the file, at most png_bound bytes | pad to 16 | its length, int32 | pad]: one fixed-size copy brings both back
@@ -704,17 +721,17 @@ class DetectionEntry:
             compress = PNG_ENCODES[s.encode]
             s.png_bound = ops.png_bound(in_h, in_w, compress)
             len_at = (s.png_bound + 15) // 16 * 16
-            s.png_dev = torch.zeros((B, len_at + 16), dtype=torch.uint8, device="cuda")
+            s.png_dev = torch.zeros((F, len_at + 16), dtype=torch.uint8, device="cuda")
             s.png_ws = torch.empty(ops.png_workspace_bytes(in_h, in_w, compress), dtype=torch.uint8, device="cuda")     # (the frames of a pass encode one after another)
-            png_out = [(s.png_dev[i][:s.png_bound], s.png_dev[i][len_at:len_at + 4].view(torch.int32)) for i in range(B)]
+            png_out = [(s.png_dev[i][:s.png_bound], s.png_dev[i][len_at:len_at + 4].view(torch.int32)) for i in range(F)]
             uploaded_rgb = src is not None and bool(int(flip) & 2)
 
         def run():
             if self.device_preprocess:
-                for i in range(B):
-                    frame = u8[i]
+                for i in range(B):                                  # (a ``detect_every`` pass: segments 0, K, 2K, ... feed the network)
+                    frame = u8[i * K]
                     if src is not None:                             # shapes.Image.data: INTER_CUBIC resize (+ flip) of the decoded frame
-                        frame = ops.resize_cubic_u8(u8[i], H, W, flip=flip, tabs=s.tabs, out=s.u8_resized)
+                        frame = ops.resize_cubic_u8(u8[i * K], H, W, flip=flip, tabs=s.tabs, out=s.u8_resized)
                     ops.preprocess_u8(frame, MEAN_BGR, out=s.x_f32[i:i + 1])     # resnet.preprocess + the f32 feed cast, bit for bit
             res = pipe.forward_dev(s.x_f32, dyn=dyn)
             if annotate:                                            # the detections drawn into the source frame (its only reader is done)
@@ -722,8 +739,12 @@ class DetectionEntry:
                 if s.track:
                     if s.track_out is None:                         # (the first warm-up pass: the rows of a packed buffer are known now)
                         R = ops.track_rows(packed) + ops.track_capacity(t_state)
-                        s.track_out = torch.zeros((B, 4 + 8 * R), dtype=torch.int32, device="cuda")
-                    if s.track_motion:
+                        s.track_out = torch.zeros((F, 4 + 8 * R), dtype=torch.int32, device="cuda")
+                    if s.every:
+                        # the B key frames' detections, all F frames: between two key frames the block match alone moves the tracks
+                        ops.track_update_interval(t_state, t_motion, s.io_dev, seg, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold,
+                                                  t_grow, s.track_motion, K, out=s.track_out)
+                    elif s.track_motion:
                         ops.track_update_motion(t_state, t_motion, s.io_dev, seg, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold,
                                                 t_grow, s.track_motion, out=s.track_out)
                     else:
@@ -736,7 +757,7 @@ class DetectionEntry:
                                         torch.zeros(4, dtype=torch.int32, device="cuda"))
                         ops.track_lookback(lb_window, s.io_dev, seg, s.track_out, s.n_frames_dev, ops.track_capacity(t_state), lb_back, in_h, in_w,
                                            s.track_lookback, s.track_motion or 0, t_grow, out=s.lb_out)
-                for i in range(B):
+                for i in range(F):
                     rows = s.lb_out[1][i] if s.track_lookback else s.track_out[i] if s.track else packed[i] if B > 1 else packed
                     if s.redact:
                         ops.redact_u8(out[i], rows, r_table, r_mode, r_size, r_margin, workspace=s.redact_ws, tracked=bool(s.track))
@@ -753,7 +774,7 @@ class DetectionEntry:
                     if s.track_lookback:
                         ops.y4m_encode_frames_u8(lb_frames.view(-1), npix, B, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
                     else:
-                        ops.y4m_encode_frames_u8(s.io_dev, seg, B, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
+                        ops.y4m_encode_frames_u8(s.io_dev, seg, F, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
             return res
         return run
 
@@ -775,7 +796,7 @@ class DetectionEntry:
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
     def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None, jpeg_mode=JPEG_MODE,
-                      y4m_mode=Y4M_MODE, redact=None, draw=True, track=None, track_motion=None, track_lookback=None):
+                      y4m_mode=Y4M_MODE, redact=None, draw=True, track=None, track_motion=None, track_lookback=None, detect_every=None):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
         (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
@@ -785,7 +806,8 @@ class DetectionEntry:
         ``track`` = (thr, hold, grow): an annotating pass that runs the engine's tracker over its frames (ops.track_update);
         ``track_motion`` = R: with the motion step of radius R in front of every frame's match (ops.track_update_motion);
         ``track_lookback`` = L: with the look-back call behind the tracker (ops.track_lookback): the pass edits, encodes and returns the
-        frames of the pass before it."""
+        frames of the pass before it.  ``detect_every`` = K: a pass over B * K source frames whose network sees every K-th
+        (ops.track_update_interval)."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -805,6 +827,7 @@ class DetectionEntry:
             s.encode, s.quality, s.jpeg_mode, s.y4m_mode = encode, quality, jpeg_mode, y4m_mode
             s.redact, s.nodraw, s.track, s.track_motion = redact, (None if draw else True), track, track_motion
             s.track_lookback = track_lookback
+            s.every, s.frames = detect_every, B * (detect_every or 1)
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -842,7 +865,7 @@ class DetectionEntry:
             s._out_raw = self._pinned.take(4 * B * s.out_packed[0].numel())
             s.out_pin = s._out_raw.view(torch.int32).view((B,) + tuple(s.out_packed[0].shape))
             if s.encode:                                            # (taken behind the capture: a failed one never held it)
-                shape = (B, s.first_copy) if s.encode == JPEG_ENCODE else tuple(s.png_dev.shape)
+                shape = (s.frames, s.first_copy) if s.encode == JPEG_ENCODE else tuple(s.png_dev.shape)
                 s._png_raw = self._pinned.take(shape[0] * shape[1], zero=True)
                 s.png_pin = s._png_raw[:shape[0] * shape[1]].view(shape)
             if s.track:
@@ -1035,7 +1058,7 @@ class DetectionEntry:
 
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
-                     track_lookback=None):
+                     track_lookback=None, detect_every=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1077,7 +1100,17 @@ class DetectionEntry:
         flush: it replays the LAST look-back pass submitted, whatever its other arguments say (they are not read, ``track_lookback`` only marks
         it), with no frame, and returns the last group.  Collect look-back tickets in submit order.  An engine follows ONE look-back
         sequence at a time: flush before the geometry, the pass size or any option changes (``annotate_images`` / ``annotate_stream``
-        do), and do not interleave two sequences."""
+        do), and do not interleave two sequences.
+        ``detect_every`` = K (tracking passes with ``track_motion`` only; ("every", K) appended behind the track / motion tail of the key;
+        2..16 with batch * K at most 64): the network sees every K-th frame only (DESIGN §8 "Interval rule", ops.track_update_interval).
+        ``pixels`` then holds up to batch * K source frames of one geometry IN ORDER, ``images`` / ``resize_ratios`` the KEY frames
+        0, K, 2K, ... among them only: len(images) == ceil(len(pixels) / K).  Between two key frames the block match alone moves every
+        track's box; nothing is matched, aged or born there, so ``hold`` counts key frames and a held box does not grow in between.  The
+        redaction, the drawing step and the encoder run over every source frame, and ``collect_batch`` returns one result per source frame,
+        in order: a key frame's as a tracking pass returns it, a between frame's with num_rois 0 and dets made of the tracks -- the live
+        ones with "track_id" and "propagated": True (the prob is that of the track's last match), then the held ones.  Not together with
+        ``track_lookback`` (the look-back window holds one tracked buffer per network image); as every annotating pass, never a canvas
+        pass (its key is the exact geometry), and refused by name on an engine whose foreign preprocess uploads float pixels."""
         if (redact is not None or not draw) and not annotate:
             raise FrcnnError("submit_batch: redact= and draw=False change the frame an ANNOTATING pass returns: pass annotate=True")
         if track is not None:
@@ -1090,6 +1123,17 @@ class DetectionEntry:
             track_motion = self.track_motion_option(track_motion)
         if track_lookback is not None and track is None:
             raise FrcnnError("submit_batch: track_lookback= hides the tracker's new tracks in earlier frames: pass track=(thr, hold, grow) too")
+        if detect_every is not None:
+            if track_motion is None:
+                raise FrcnnError("submit_batch: detect_every= follows the tracks by block matching between two detected frames: pass "
+                                 "track=(thr, hold, grow) and track_motion=R too")
+            if track_lookback is not None:
+                raise FrcnnError("submit_batch: detect_every= together with track_lookback= is not supported: the look-back window keeps one "
+                                 "tracked buffer per detected frame")
+            if not self.device_preprocess:
+                raise FrcnnError("submit_batch: detect_every= needs the device-side preprocess: a foreign preprocess_func uploads float "
+                                 "pixels of the key frames only, and the block match reads the uint8 pixels of every source frame")
+            detect_every = self.detect_every_option(detect_every, self.batch if batch is None else batch)
         if redact is not None:
             redact = self.redact_option(redact)
         y4m_mode = Y4M_MODE
@@ -1130,7 +1174,13 @@ class DetectionEntry:
                 raise FrcnnError("submit_batch: a flush (no images) follows a look-back submit; none is waiting")
             s = self.cache.acquire(*self._lookback_last)
             return self._replay(s, [], [], [], det_threshold)
-        assert 1 <= len(images) <= B and len(images) == len(pixels) == len(resize_ratios)
+        if detect_every is not None:
+            if not 1 <= len(pixels) <= B * detect_every or len(images) != -(-len(pixels) // detect_every) or len(images) != len(resize_ratios):
+                raise FrcnnError("submit_batch: detect_every=%d with batch=%d takes 1..%d source frames in pixels and their key frames 0, %d, ... "
+                                 "in images / resize_ratios: got %d frames, %d images, %d ratios"
+                                 % (detect_every, B, B * detect_every, detect_every, len(pixels), len(images), len(resize_ratios)))
+        else:
+            assert 1 <= len(images) <= B and len(images) == len(pixels) == len(resize_ratios)
         _, H, W, src, flip = pixels[0]
         if track_lookback is not None:
             track_lookback = self.track_lookback_option(track_lookback, B)
@@ -1154,6 +1204,8 @@ class DetectionEntry:
                 key = key + ("motion", track_motion)
             if track_lookback is not None:
                 key = key + ("lookback", track_lookback)
+            if detect_every is not None:
+                key = key + ("every", detect_every)
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -1163,7 +1215,7 @@ class DetectionEntry:
         else:
             capture = lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality,
                                                  jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode, redact, draw, track, track_motion,
-                                                 track_lookback)
+                                                 track_lookback, detect_every)
             s = self.cache.acquire(key, capture)
             if track_lookback is not None:
                 self._lookback_last = (key, capture)
@@ -1176,6 +1228,8 @@ class DetectionEntry:
         for i in range(B if images else 0):
             j = i if i < len(images) else 0
             s.dyn_host[i, 0], s.dyn_host[i, 1] = float(resize_ratios[j]), float(det_threshold)
+        for i in range(s.frames if images else 0):                  # (B of them, but in a ``detect_every`` pass: every source frame goes up)
+            j = i if i < len(pixels) else 0
             if isinstance(pixels[j][0], JpegFile):
                 files.append((i, pixels[j][0]))
             if s.canvas:
@@ -1183,7 +1237,7 @@ class DetectionEntry:
             elif not isinstance(pixels[j][0], JpegFile):
                 np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
         if s.track:
-            s.n_frames_host[0] = len(images) if images else -1      # goes up with the frames: the padding does not advance the tracker; -1: a flush
+            s.n_frames_host[0] = len(pixels) if images else -1      # goes up with the frames: the padding does not advance the tracker; -1: a flush
             st = self.track_stream
         else:
             st = self._streams[self._seq % self.in_flight]
@@ -1216,9 +1270,9 @@ class DetectionEntry:
                 s.lb_pin[words:].copy_(s.lb_out[2], non_blocking=True)
             for i in range(len(images)):
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
-                if s.track:
-                    s.track_pin[i].copy_(s.track_out[i], non_blocking=True)
-            for i in range(len(emitted["images"]) if emitted else 0 if s.track_lookback else len(images)):
+            for i in range(len(pixels) if s.track else 0):
+                s.track_pin[i].copy_(s.track_out[i], non_blocking=True)
+            for i in range(len(emitted["images"]) if emitted else 0 if s.track_lookback else len(pixels)):
                 if s.encode == JPEG_ENCODE:
                     s.png_pin[i].copy_(s.png_dev[i][:s.first_copy], non_blocking=True)
                 elif s.encode:
@@ -1227,14 +1281,14 @@ class DetectionEntry:
                     s.frame_io[i][1].copy_(s.frame_io[i][0], non_blocking=True)
             s.event.record(st)
         s.busy = True
-        return Ticket(s, list(images), own, emitted)
+        return Ticket(s, list(images), own, emitted, len(pixels))
 
     def _stage_files(self, s, files):
         """Host side of a pass whose frames the device decodes: [item table | the files' bytes back to back] into the slot's one pinned
         area (grow-only; the slot is idle, so nothing reads the old one), room for them and for the decoder's workspace on the device.
         ``files``: (frame index, JpegFile) of the pass's file-backed frames; item k is files[k], its output frame i's source segment.  A
         file that fills several frames (the padding of a short group) is staged once."""
-        B = s.batch
+        B = s.frames
         kind_of = lambda f: 3 if isinstance(f, Y4mFile) else 2 if isinstance(f, PngFile) else int(isinstance(f.plan, _lib.JpegDecFullPlan))
         files.sort(key=lambda t: kind_of(t[1]))                     # (in place, stable: the baseline .jpg items, the progressive ones, the .png items, the y4m frames)
         nj, nf, npng = (sum(1 for _, f in files if kind_of(f) == k) for k in (0, 1, 2))
@@ -1307,10 +1361,10 @@ class DetectionEntry:
             s.jpg_area[:s.jpg_used].copy_(s.jpg_pin[:s.jpg_used], non_blocking=True)
         s.jpg_status.zero_()
         # per decoder: its items, its first status word, where its items lie in the staged area; the .png items' launches go first
-        first_full = s.batch * (item + ctypes.sizeof(_lib.PngDecFullBatchItem))
+        first_full = s.frames * (item + ctypes.sizeof(_lib.PngDecFullBatchItem))
         for dec, items, word, first in ((ops.Y4M_DECODER, s.y4m_items, nj + len(s.full_items) + len(s.png_items),
-                                         self._first_y4m_item(s.batch, len(s.full_items))),
-                                        (s.png_dec, s.png_items, nj + len(s.full_items), s.batch * item),
+                                         self._first_y4m_item(s.frames, len(s.full_items))),
+                                        (s.png_dec, s.png_items, nj + len(s.full_items), s.frames * item),
                                         (ops.JPEG_FULL_DECODER, s.full_items, nj, first_full), (ops.JPEG_DECODER, s.jpg_items, 0, 0)):
             if dec is ops.JPEG_DECODER and not batched:
                 continue
@@ -1377,7 +1431,20 @@ class DetectionEntry:
                     raise FrcnnError("f16x3 pass not trustworthy (%s): status %d; run the image on the native or bf16x6 engine" % (ops.h3_status_text(bits), bits))
             if s.track_lookback:
                 return self._collect_lookback(ticket)
-            for i in range(len(ticket.image)):
+            K = s.every or 1
+            for f in range(ticket.frames):
+                if f % K:                                           # a between frame of a ``detect_every`` pass: its dets are the tracks
+                    n_rows, n_live, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(s.track_pin[f].numpy())
+                    dets = [{"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(), "track_id": int(t_id[k])}
+                            for k in range(int(n_rows[0]))]
+                    for k, d in enumerate(dets):
+                        if k < int(n_live[0]):
+                            d["propagated"] = True
+                        else:
+                            d["held"] = int(t_age[k])
+                    res.append((0, dets) + self._payload(s, f))
+                    continue
+                i = f // K
                 packed = s.out_pin[i].numpy()
                 nd, n_rois = int(packed[0]), int(packed[1])
                 rows = (packed.size - 4) // 7
@@ -1386,14 +1453,14 @@ class DetectionEntry:
                 prob = packed[4 + 5 * rows:4 + 5 * rows + nd].view(np.float32).copy()
                 dets = [{"bbox": bbox[k], "cls_name": rev[int(cls[k])], "prob": prob[k]} for k in range(nd)]
                 if s.track:                                         # the live rows' ids, then the held rows
-                    n_rows, n_live, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(s.track_pin[i].numpy())
+                    n_rows, n_live, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(s.track_pin[f].numpy())
                     if int(n_live[0]) != nd:
                         raise FrcnnError("tracker: %d live rows for %d detections" % (int(n_live[0]), nd))
                     for k in range(nd):
                         dets[k]["track_id"] = int(t_id[k])
                     dets += [{"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(),
                               "track_id": int(t_id[k]), "held": int(t_age[k])} for k in range(nd, int(n_rows[0]))]
-                res.append((n_rois, dets) + self._payload(s, i))
+                res.append((n_rois, dets) + self._payload(s, f))
             return res
         finally:
             s.busy = False                               # whatever happened while decoding the records: the slot is free again

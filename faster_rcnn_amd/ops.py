@@ -1375,6 +1375,50 @@ def track_update_motion(state, mstate, frames_u8, frame_stride, det_packed, n_fr
     return out
 
 
+TRACK_INTERVAL = _lib.TRACK_INTERVAL            # (smallest, largest) interval of ``track_update_interval``; the public option starts at 2
+
+
+def track_interval_option(k):
+    """(host only) ``detect_every`` checked: an integer in 2..16, the frames from one detected frame to the next (1 is plain tracking and
+    exists at the ABI only).  ValueError with the reason."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= int(k) <= TRACK_INTERVAL[1]:
+        raise ValueError("detect every=%r: an integer in 2..%d (the frames from one detected frame to the next)" % (k, TRACK_INTERVAL[1]))
+    return int(k)
+
+
+def track_update_interval(state, mstate, frames_u8, frame_stride, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, radius=8, interval=1,
+                          out=None):
+    """``track_update_motion`` with the detector on every ``interval``-th frame only (DESIGN §8 "Interval rule", frcnn_track_update_interval):
+    ``det_packed`` holds the packed buffers of the KEY frames 0, interval, 2 interval, ... of the call -- B of them, as ``track_update``
+    takes them --, ``frames_u8`` the F source frames, key and between, ``frame_stride`` bytes apart, with (F + interval - 1) // interval ==
+    B; F is the rows of ``out`` (F, 4 + 8R) when given, else of a ``frames_u8`` of two or more dimensions, else B * interval.  A key frame is ``track_update_motion``'s frame; a between
+    frame moves every slot by the block match and writes the slots of age 0 as live rows (their moved boxes) and the held ones behind them:
+    no match, no ageing, no births, so ``hold`` counts key frames.  ``n_frames``: how many of the F frames are real.  -> ``out``.  At most
+    two launches per frame and one more per call; the call can be captured in a graph."""
+    _require_gpu()
+    base, stride, B, words = _track_packed(det_packed)
+    interval = int(interval)
+    F = int(out.shape[0]) if out is not None else int(frames_u8.shape[0]) if frames_u8.dim() > 1 else B * interval
+    if not _lib.TRACK_INTERVAL[0] <= interval <= _lib.TRACK_INTERVAL[1] or (F + interval - 1) // interval != B:
+        raise _lib.FrcnnError("track_update_interval: interval=%d (1..%d) and %d frames do not go with %d key frames' detections"
+                              % (interval, _lib.TRACK_INTERVAL[1], F, B))
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert mstate.is_cuda and mstate.dtype == torch.uint8 and mstate.dim() == 1 and mstate.is_contiguous() and mstate.numel() == 16 + 3 * int(h) * int(w)
+    assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
+    assert int(frames_u8.numel()) >= (F - 1) * int(frame_stride) + 3 * int(h) * int(w) and int(frame_stride) >= 0
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    cap, rows = track_capacity(state), (words - 4) // 7
+    R = rows + cap
+    if out is None:
+        out = torch.empty((F, 4 + 8 * R), dtype=torch.int32, device="cuda")
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (F, 4 + 8 * R)
+    _lib.call("frcnn_track_update_interval", _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), F, _p(n_frames),
+              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), interval, int(h), int(w), _p(out), 4 + 8 * R,
+              _stream())
+    return out
+
+
 TRACK_LOOKBACK = _lib.TRACK_LOOKBACK            # (smallest, largest, the default) look-back of ``track_lookback``, in frames
 
 

@@ -26,7 +26,8 @@ to PNG files with the device encoder -- and reports the frames/s of both and the
 ``--track`` runs the tracker's cost instead (``run_track``): the ``--redact`` leg's frames and redaction without and with ``--track``
 (IoU 30 %, hold 8, grow 0, the defaults), alternating in one session through in-memory annotating passes; ``--track_motion`` likewise
 (``run_track_motion``) the ``--track`` leg without and with ``--track_motion 8``, and the tracker part of one pass alone; tracking passes replay on one
-stream of the engine, so the figure includes what that ordering costs.  ``--track_lookback`` (``run_track_lookback``) runs the
+stream of the engine, so the figure includes what that ordering costs.  ``--detect_every`` (``run_detect_every``) runs the ``--track --track_motion 8`` leg
+without and with ``--detect_every 4``.  ``--track_lookback`` (``run_track_lookback``) runs the
 ``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
 look-back call of one pass alone.
 
@@ -81,11 +82,13 @@ def build(cfg):
 def annotate_in_memory(eng, resized, ratios, **kwargs):
     """(b): the frames through annotating passes, eng.batch per pass, eng.in_flight passes in flight (annotate_images' loop
     without the files).  ``kwargs``: further arguments of submit_batch (``redact``).  With ``track_lookback`` a flush submit ends the
-    list: the passes return the frames of the pass before."""
+    list: the passes return the frames of the pass before.  With ``detect_every`` = K a pass takes eng.batch * K frames and every K-th
+    of them is one of its images."""
     B, window, frames = eng.batch, [], []
-    for i in range(0, len(resized), B):
-        part = resized[i:i + B]
-        window.append(eng.submit_batch(part, ratios[i:i + B], 0.0, [eng.host_pixels(r) for r in part], batch=B, annotate=True, **kwargs))
+    K = kwargs.get("detect_every") or 1
+    for i in range(0, len(resized), B * K):
+        part = resized[i:i + B * K]
+        window.append(eng.submit_batch(part[::K], ratios[i:i + B * K:K], 0.0, [eng.host_pixels(r) for r in part], batch=B, annotate=True, **kwargs))
         if len(window) >= eng.in_flight:
             frames += [r[2] for r in eng.collect_batch(window.pop(0))]
     if kwargs.get("track_lookback") is not None:
@@ -520,6 +523,53 @@ def run_track_lookback(name, cfg, n_frames, reps, content="noise"):
     return res
 
 
+EVERY_LEG = 4                                            # --detect_every 4
+
+
+def run_detect_every(name, cfg, n_frames, reps, content="noise"):
+    """``--detect_every``: what the frame rate gains when the detector runs on every fourth frame only.  One pair of legs in ONE session,
+    alternating inside every repetition: ``run_track``'s frames through in-memory annotating passes with ``redact=REDACT_LEG,
+    track=TRACK_LEG, track_motion=MOTION_LEG``, without and with ``detect_every=EVERY_LEG`` (the tracker is reset in front of every
+    run).  Reports frames/s of both, their ratio and the tracker's state at the end of the last run."""
+    import numpy as np
+    import torch
+    from faster_rcnn_amd import entry, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+
+    def leg(**kw):
+        def run():
+            eng.track_reset()
+            return annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, track=TRACK_LEG, track_motion=MOTION_LEG, **kw)
+        return run
+
+    legs = {"track_motion": leg(), "detect_every": leg(detect_every=EVERY_LEG)}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    torch.cuda.synchronize()
+    state = eng.track_state().cpu().numpy()
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact": ["all", "blur", 12, 0], "track": list(TRACK_LEG), "track_motion": MOTION_LEG, "detect_every": EVERY_LEG,
+           "images_per_pass": eng.batch, "frames_per_pass": eng.batch * EVERY_LEG, "in_flight": eng.in_flight,
+           "tracker": {"live_slots": int(state[0]), "ids_issued": int(state[1]), "overflow": int(state[2]), "frames": int(state[3])}}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["every_over_motion"] = round(statistics.median(times["track_motion"]) / statistics.median(times["detect_every"]), 3)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--frames", type=int, default=256)
@@ -539,6 +589,8 @@ def main():
                                                                 "without and with --track_motion 8, alternating in one session")
     ap.add_argument("--track_lookback", action="store_true", help="instead of the legs above: the --track --track_motion 8 leg without and "
                                                                   "with --track_lookback at its default, alternating in one session")
+    ap.add_argument("--detect_every", action="store_true", help="instead of the legs above: the --track --track_motion 8 leg without and "
+                                                                "with --detect_every 4, alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -547,6 +599,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.detect_every:
+            out[name] = run_detect_every(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.track_lookback:
             out[name] = run_track_lookback(name, PAIRS[name], args.frames, args.reps, args.content)
