@@ -423,6 +423,13 @@ TRACK_LOOKBACK = (1, 16, 8)
 TRACK_LOOKBACK_MAX_BACK = 128   # ... FRCNN_TRACK_LOOKBACK_MAX_BACK: back-filled rows a full frame can still take, at most
 TRACK_LOOKBACK_HEADER = 32      # ... FRCNN_TRACK_LOOKBACK_HEADER: bytes in front of a window's cells
 
+TRACK_BACKTRACK_VERSION = 1     # include/ext/frcnn_hip_track_backtrack.h FRCNN_TRACK_BACKTRACK_VERSION
+TRACK_BACKTRACK_SIGNATURES = {
+    "frcnn_track_backtrack_version": (I, []),
+    "frcnn_track_backtrack": (I, [P, P, ctypes.c_longlong, P, ctypes.c_longlong, I, P, I, I, I, I, I, I, I, I, I, P, ctypes.c_longlong, P,
+                                  ctypes.c_longlong, P, P]),
+}
+
 
 class ConvDesc(ctypes.Structure):
     """frcnn_conv_desc (include/frcnn_hip.h)."""
@@ -554,6 +561,15 @@ def load():
     if lib.frcnn_track_lookback_version() != TRACK_LOOKBACK_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_lookback_version()} of the tracker's look-back extension, this binding "
                          f"{TRACK_LOOKBACK_VERSION} (include/ext/frcnn_hip_track_lookback.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in TRACK_BACKTRACK_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_track_backtrack.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_track_backtrack_version() != TRACK_BACKTRACK_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_backtrack_version()} of the tracker's back-track extension, this binding "
+                         f"{TRACK_BACKTRACK_VERSION} (include/ext/frcnn_hip_track_backtrack.h): rebuild with `python -m faster_rcnn_amd.build`")
     for name, (res, args) in TRACK_INTERVAL_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -70,6 +70,12 @@ two detected ones every track's box follows the pixels under it by the block mat
 counts detected frames.  The K-th frames are counted within each group of at most B * K consecutive frames of one geometry: in a video
 that is every K-th frame, in a list of mixed sizes a detected frame follows every change of size.  Not together with
 ``--track_lookback``, and not on the one-frame-at-a-time paths.
+``track_backtrack=N`` (``--track_backtrack [N]``, with ``--detect_every K``; 1..16, at least K - 1, at most B * K; bare: as many as a
+pass holds, at most 16) follows every track of a detected frame BACK through the frames in front of it (ops.track_backtrack,
+csrc/track_backtrack.hip; DESIGN §8 "Back-track rule") -- a continued track as far as the detected frame before, a new one over N frames
+-- and hides the boxes found there too: a frame between two detections is covered from both sides.  The output then runs one pass
+behind the input, as with ``--track_lookback``; the back-filled rows are printed with "backfilled": k, never drawn and not written to
+``--tracks_out``.
 """
 import collections
 import os
@@ -430,6 +436,49 @@ def _detect_every(detect_every, track, track_motion, track_lookback, eng, B):
     return k
 
 
+TRACK_BACKTRACK_AUTO = 0       # a bare --track_backtrack: as far back as one pass of B * K frames holds, at most 16 frames
+
+
+def track_backtrack_from_args(args):
+    """(host only) The back-track look-back the command line asks for -> the frames as ``annotate_images(track_backtrack=...)`` takes them
+    (TRACK_BACKTRACK_AUTO for a bare ``--track_backtrack``), or None without the flag.  ValueError, with the reason, for
+    ``--track_backtrack`` without ``--track --track_motion --detect_every K``, together with ``--track_lookback``, for a value outside
+    1..16 and for one under K - 1."""
+    if args.track_backtrack is None:
+        return None
+    if not args.track or args.track_motion is None or args.detect_every is None:
+        raise ValueError("--track_backtrack=%s follows the tracks of a detected frame back over the frames between two detections: it needs "
+                         "--track --track_motion --detect_every K" % args.track_backtrack)
+    if args.track_lookback is not None:
+        raise ValueError("--track_backtrack together with --track_lookback is not supported: the back-track rule hides a new track in the "
+                         "earlier frames itself")
+    if args.track_backtrack == TRACK_BACKTRACK_AUTO and not isinstance(args.track_backtrack, bool):
+        return TRACK_BACKTRACK_AUTO
+    try:
+        k = ops.track_interval_option(args.detect_every)
+        return ops.track_backtrack_option(args.track_backtrack, k, max(ops.TRACK_LOOKBACK[1], k))      # (the pass's frames: known with the engine)
+    except ValueError as e:
+        raise ValueError("--track_backtrack: %s" % e) from None
+
+
+def _backtrack_frames(track_backtrack, every, track_lookback, eng, B):
+    """``annotate_images`` / ``annotate_stream``'s ``track_backtrack`` checked against the K of their passes (``_detect_every``'s result)
+    -> the look-back of their passes, or None."""
+    if track_backtrack is None:
+        return None
+    if track_lookback is not None:
+        raise ValueError("track_backtrack=%r together with track_lookback=%r is not supported: the back-track rule hides a new track in the "
+                         "earlier frames itself" % (track_backtrack, track_lookback))
+    if every is None:
+        raise ValueError("track_backtrack=%r follows the tracks of a detected frame back over the frames between two detections: it needs "
+                         "track=(thr, hold, grow), track_motion=R and detect_every=K" % (track_backtrack,))
+    if eng is None:
+        raise ValueError("track_backtrack=%r delays the output by one pass: the eager path (a foreign model) returns every frame at once and "
+                         "cannot" % (track_backtrack,))
+    auto = track_backtrack == TRACK_BACKTRACK_AUTO and not isinstance(track_backtrack, bool)
+    return ops.track_backtrack_option(None if auto else track_backtrack, every, B * every)
+
+
 def _every_parts(group, B, every):
     """The passes of a ``detect_every`` group of <= B * K frames of one geometry -> [(frames, images of the pass)]: one pass of B (padded)
     when its key frames fill at least half of it, else one-image passes of K frames."""
@@ -494,7 +543,7 @@ def _print_drawn(dets, width, height):
 
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
-                        frame_no=1, track_motion=None, track_lookback=None, detect_every=None):
+                        frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
@@ -503,6 +552,9 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     if detect_every is not None:
         raise ValueError("detect_every=%r runs the detector once per pass of several frames: get_annotated_frame detects its one frame and "
                          "cannot; use annotate_images or annotate_stream" % (detect_every,))
+    if track_backtrack is not None:
+        raise ValueError("track_backtrack=%r delays the output: get_annotated_frame returns its frame at once and cannot; use annotate_images "
+                         "or annotate_stream" % (track_backtrack,))
     if track_lookback is not None:
         raise ValueError("track_lookback=%r delays the output: get_annotated_frame returns its frame at once and cannot; use annotate_images "
                          "or annotate_stream" % (track_lookback,))
@@ -700,13 +752,14 @@ def directory_frames(input_dir, image_filenames, jpeg_decoder=None, png_decoder=
 
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
-                    redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None):
+                    redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
+                    track_backtrack=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack``: as ``annotate_images``."""
     from concurrent.futures import ThreadPoolExecutor
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
@@ -747,12 +800,16 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
     mapping = training_manager.class_mapping
     every = _detect_every(detect_every, track, track_motion, track_lookback, eng, None if eng is None else eng.batch)
     lookback = _lookback_frames(track_lookback, track, eng, None if eng is None else eng.batch)
+    backtrack = _backtrack_frames(track_backtrack, every, track_lookback, eng, None if eng is None else eng.batch)
+    delayed = lookback is not None or backtrack is not None      # the passes return the frames of the pass before them
     if track is not None:                                 # a new sequence; its frames are submitted in stream order, as every stream's are
         kwargs = dict(kwargs, track=track, **motion)
         if lookback is not None:
             kwargs["track_lookback"] = lookback
         if every is not None:
             kwargs["detect_every"] = every
+        if backtrack is not None:
+            kwargs["track_backtrack"] = backtrack
         reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
 
     if eng is None:                                       # eager path / foreign models: one frame at a time, converted on the device
@@ -802,7 +859,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
             results = eng.collect_batch(ticket)
         finally:
             window.pop(0)
-        if lookback is not None:                          # (the pass returned the group before its own, or nothing)
+        if delayed:                                       # (the pass returned the group before its own, or nothing)
             part = waiting.popleft() if results else ()
         for (pos, label, frame), (num_rois, dets, out) in zip(part, results):
             print("processing {}".format(label))
@@ -826,19 +883,19 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
 
     def submit(group):
         parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
-        if lookback is not None:                          # full passes only: a window belongs to one size of pass; a new geometry: a new window
+        if delayed:                                       # full passes only: a window belongs to one size of pass; a new geometry: a new window
             parts = [(group, B)]
             if last_key[0] not in (None, eng.geometry_of(group[0][5])):
                 flush()
             last_key[0] = eng.geometry_of(group[0][5])
-        if every is not None:                             # the key frames 0, K, ... of a pass go to the network, every frame goes up
+        if every is not None and backtrack is None:       # the key frames 0, K, ... of a pass go to the network, every frame goes up
             parts = _every_parts(group, B, every)
         for part, take in parts:
             keys = part[::every or 1]
             ticket = eng.submit_batch([g[3] for g in keys], [g[4] for g in keys], DET_THRESHOLD, [g[5] for g in part],
                                       batch=take, annotate=True, **kwargs)
             window.append(([(g[0], g[1], g[2]) for g in part], ticket))
-            if lookback is not None:
+            if delayed:
                 waiting.append(window[-1][0])
             if len(window) >= eng.in_flight:
                 finish()
@@ -884,7 +941,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
-                    track_lookback=None, detect_every=None):
+                    track_lookback=None, detect_every=None, track_backtrack=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -916,7 +973,13 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     a group is a run of at most B * K consecutive frames of one geometry, it is cut where the geometry changes, and its frames 0, K,
     2K, ... are the detected ones (a group whose key frames fill under half a pass goes through one-image passes of K frames, the same
     key frames).  With frames of one size, a video, every group but the last is full and that is every K-th frame of the list; in a list
-    of mixed sizes a detected frame follows every change of geometry.  The eager path refuses it."""
+    of mixed sizes a detected frame follows every change of geometry.  The eager path refuses it.
+    ``track_backtrack``: the frames as ``track_backtrack_from_args`` returns them (with ``detect_every``, not with ``track_lookback``;
+    TRACK_BACKTRACK_AUTO: as many as a pass of B * K frames holds, at most 16; at least K - 1) -- at every detected frame every track is
+    followed BACK through the frames in front of it (DESIGN §8 "Back-track rule"): a continued track as far as the detected frame before,
+    a new one over that many frames, and the boxes found are hidden there too, so a frame between two detections is covered from both
+    sides.  Every group of at most B * K frames then goes through one full (padded) pass, a pass returns the frames of the pass before it
+    and a flush follows a change of geometry and the end of the list, as with ``track_lookback``.  The eager path refuses it."""
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     motion = {} if track_motion is None else {"track_motion": track_motion}
@@ -949,6 +1012,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     mapping = training_manager.class_mapping
     every = _detect_every(detect_every, track, track_motion, track_lookback, eng, None if eng is None else eng.batch)
     lookback = _lookback_frames(track_lookback, track, eng, None if eng is None else eng.batch)
+    backtrack = _backtrack_frames(track_backtrack, every, track_lookback, eng, None if eng is None else eng.batch)
+    delayed = lookback is not None or backtrack is not None      # the passes return the frames of the pass before them
     if track is not None:
         reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
     if eng is None:                                       # eager path / foreign models: the reference's loop
@@ -981,6 +1046,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         edit["track_lookback"] = lookback
     if every is not None:
         edit["detect_every"] = every
+    if backtrack is not None:
+        edit["track_backtrack"] = backtrack
     F = B * (every or 1)                                  # frames of a full pass
     decode = ThreadPoolExecutor(max_workers=max(1, DECODE_THREADS))
     write = ThreadPoolExecutor(max_workers=max(1, WRITE_THREADS))
@@ -994,7 +1061,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
             results = eng.collect_batch(ticket)
         finally:
             window.pop(0)
-        if lookback is not None:                          # (the pass returned the group before its own, or nothing)
+        if delayed:                                       # (the pass returned the group before its own, or nothing)
             part = waiting.popleft() if results else ()
         for (pos, frame), (num_rois, dets, out) in zip(part, results):
             print("processing {}".format(paths[pos]))
@@ -1010,19 +1077,19 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
         """<= B frames of one geometry: one pass of B (padded) when they fill at least half of it (as get_dets_by_cls), else
         one-frame passes."""
         parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
-        if lookback is not None:                          # full passes only: a window belongs to one size of pass; a new geometry: a new window
+        if delayed:                                       # full passes only: a window belongs to one size of pass; a new geometry: a new window
             parts = [(group, B)]
             if last_key[0] not in (None, eng.geometry_of(group[0][4])):
                 flush()
             last_key[0] = eng.geometry_of(group[0][4])
-        if every is not None:                             # the key frames 0, K, ... of a pass go to the network, every frame goes up
+        if every is not None and backtrack is None:       # the key frames 0, K, ... of a pass go to the network, every frame goes up
             parts = _every_parts(group, B, every)
         for part, take in parts:
             keys = part[::every or 1]
             ticket = eng.submit_batch([g[2] for g in keys], [g[3] for g in keys], DET_THRESHOLD, [g[4] for g in part],
                                       batch=take, annotate=True, encode=encode, quality=quality, **jpeg_mode, **edit)
             window.append(([(g[0], g[1]) for g in part], ticket))
-            if lookback is not None:
+            if delayed:
                 waiting.append(window[-1][0])
             if len(window) >= eng.in_flight:
                 finish()
@@ -1147,6 +1214,12 @@ def build_parser():
                         "under it by block matching and is drawn, redacted and written to --tracks_out with the prob of its last match. "
                         "Nothing is matched, aged or born there: --track_hold counts DETECTED frames and a held box does not grow in "
                         "between (needs --track --track_motion; not with --track_lookback)")
+    p.add_argument("--track_backtrack", dest="track_backtrack", type=int, nargs="?", const=TRACK_BACKTRACK_AUTO, default=None, metavar="N",
+                   help="with --detect_every K: at every detected frame follow every track BACK through the frames in front of it and hide "
+                        "it there too -- a continued track as far as the detected frame before, a new one over N frames (1..16, at least "
+                        "K - 1 and at most the B * K frames of one pass; bare: as many as a pass holds, at most 16) -- so a frame between two "
+                        "detections is covered from both sides; the output runs one pass behind the input (needs --track --track_motion "
+                        "--detect_every; not with --track_lookback)")
     p.add_argument("--tracks_out", dest="tracks_out", default=None, metavar="PATH",
                    help="write the tracks as MOTChallenge lines frame,id,left,top,width,height,prob,cls,-1,-1 (needs --track)")
     return p
@@ -1219,6 +1292,9 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     detect_every = detect_every_from_args(args)
     if detect_every is not None:
         tracking["detect_every"] = detect_every
+    track_backtrack = track_backtrack_from_args(args)
+    if track_backtrack is not None:
+        tracking["track_backtrack"] = track_backtrack
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

@@ -10,31 +10,15 @@
 //   k_lb_emit    the window's older frames copied out;
 //   k_lb_close   the header: the halves change places (no overlapping shift), or the window empties on a flush.
 // One writer per word; no atomics.  The chain writes rows at and behind a frame's n_rows only and reads rows in front of n_live only.
-#include "common.h"
-#include "../../include/ext/frcnn_hip_redact.h"
-#include "../../include/ext/frcnn_hip_track.h"
-#include "../../include/ext/frcnn_hip_track_lookback.h"
+// The geometry, the cells, the argument checks and the launches of join, emit and close are shared with csrc/track_backtrack.hip through
+// csrc/track_lookback.h.
+#include "track_lookback.h"
 #include "track_motion_search.h"
 
 namespace frcnn {
 
-constexpr int LB_HEADER = FRCNN_TRACK_LOOKBACK_HEADER;
-constexpr int LB_MAX_ROWS = FRCNN_REDACT_MAX_ROWS;
 static_assert(LB_MAX_ROWS <= TM_THREADS, "a thread of the chain's workgroup looks at one live row");
 static_assert(2 * FRCNN_TRACK_MAX_FRAMES <= TM_THREADS, "a thread of k_lb_counts takes one frame of the sequence");
-
-struct LbGeom {
-    int frames, R, R2, cap, h, w;
-    long long tracked_bytes, cell;                      // a widened buffer; a cell (buffer + padded frame)
-};
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// cell ``s`` of the call's sequence: the c window frames in half ``half``, then the call's frames in the other half
-__device__ __forceinline__ uint8_t* lb_cell(uint8_t* window, const LbGeom& g, int c, int half, int s) {
-    const int at = s < c ? half * g.frames + s : (half ^ 1) * g.frames + (s - c);
-    return window + LB_HEADER + (long long)at * g.cell;
-}
 
 __device__ __forceinline__ void lb_copy(uint8_t* dst, const uint8_t* src, size_t bytes, size_t at, size_t step) {
     if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
@@ -203,7 +187,7 @@ __global__ void k_lb_close(uint8_t* window, int frames, const int32_t* n_frames)
 }
 
 // the geometry of a window, or false for an argument out of range (``why`` says which)
-static bool lb_geom(int frames, int h, int w, int max_rows, int capacity, int back, LbGeom& g, const char*& why) {
+bool lb_geom(int frames, int h, int w, int max_rows, int capacity, int back, LbGeom& g, const char*& why) {
     why = nullptr;
     if (frames < 1 || frames > FRCNN_TRACK_MAX_FRAMES) why = "frames";
     else if (h < 1 || h > FRCNN_REDACT_MAX_SIDE || w < 1 || w > FRCNN_REDACT_MAX_SIDE) why = "frame side";
@@ -216,6 +200,51 @@ static bool lb_geom(int frames, int h, int w, int max_rows, int capacity, int ba
     g.tracked_bytes = 4LL * (4 + 8 * g.R2);
     g.cell = g.tracked_bytes + (3LL * h * w + 15) / 16 * 16;
     return true;
+}
+
+int lookback_check(const char* who, const uint8_t* window, const uint8_t* frames_u8, long long frame_stride, const int32_t* tracked,
+                   long long tracked_stride, int frames, const int32_t* n_frames, int max_rows, int capacity, int back, int lookback, int radius,
+                   int grow, int h, int w, const uint8_t* out_frames, long long out_frame_stride, const int32_t* out_tracked,
+                   long long out_tracked_stride, const int32_t* out_count, LbGeom& g) {
+    if (!window || !frames_u8 || !tracked || !n_frames || !out_frames || !out_tracked || !out_count) return fail(FRCNN_E_ARG, "%s: null pointer", who);
+    if (reinterpret_cast<uintptr_t>(window) & 15) return fail(FRCNN_E_ARG, "%s: window is not 16-byte aligned", who);
+    const char* why;
+    if (!lb_geom(frames, h, w, max_rows, capacity, back, g, why))
+        return fail(FRCNN_E_ARG, "%s: %s out of range (frames=%d, %dx%d, max_rows=%d, capacity=%d, back=%d; at most %d rows in all)", who, why, frames,
+                    h, w, max_rows, capacity, back, FRCNN_REDACT_MAX_ROWS);
+    if (lookback < 1 || lookback > FRCNN_TRACK_LOOKBACK_MAX)
+        return fail(FRCNN_E_ARG, "%s: lookback=%d not in [1, %d]", who, lookback, FRCNN_TRACK_LOOKBACK_MAX);
+    if (radius < 0 || radius > FRCNN_TRACK_MOTION_MAX_RADIUS)
+        return fail(FRCNN_E_ARG, "%s: radius=%d not in [0, %d]", who, radius, FRCNN_TRACK_MOTION_MAX_RADIUS);
+    if (grow < 0 || grow > FRCNN_TRACK_MAX_GROW) return fail(FRCNN_E_ARG, "%s: grow=%d not in [0, %d]", who, grow, FRCNN_TRACK_MAX_GROW);
+    const long long frame_bytes = 3LL * h * w;
+    if (frames > 1 && (frame_stride < frame_bytes || out_frame_stride < frame_bytes))
+        return fail(FRCNN_E_ARG, "%s: frame_stride=%lld, out_frame_stride=%lld bytes, a %dx%d frame has %lld", who, frame_stride, out_frame_stride, h,
+                    w, frame_bytes);
+    if (frames > 1 && (tracked_stride < 4 + 8 * g.R || out_tracked_stride < 4 + 8 * g.R2))
+        return fail(FRCNN_E_ARG, "%s: tracked_stride=%lld (a buffer has %d words), out_tracked_stride=%lld (%d)", who, tracked_stride, 4 + 8 * g.R,
+                    out_tracked_stride, 4 + 8 * g.R2);
+    return FRCNN_OK;
+}
+
+// the blocks a frame's bytes are copied by
+static unsigned lb_blocks(const LbGeom& g) {
+    const long long quads = 3LL * g.h * g.w / 16 + 1;
+    return (unsigned)((quads + 255) / 256 < 256 ? (quads + 255) / 256 : 256);
+}
+
+void lookback_join_launch(uint8_t* window, const LbGeom& g, const uint8_t* frames_u8, long long frame_stride, const int32_t* tracked,
+                          long long tracked_stride, const int32_t* n_frames, hipStream_t stream) {
+    k_lb_join<<<dim3(lb_blocks(g), g.frames), 256, 0, stream>>>(window, g, frames_u8, frame_stride, tracked, tracked_stride, n_frames);
+}
+
+void lookback_emit_launch(uint8_t* window, const LbGeom& g, uint8_t* out_frames, long long out_frame_stride, int32_t* out_tracked,
+                          long long out_tracked_stride, int32_t* out_count, hipStream_t stream) {
+    k_lb_emit<<<dim3(lb_blocks(g), g.frames), 256, 0, stream>>>(window, g, out_frames, out_frame_stride, out_tracked, out_tracked_stride, out_count);
+}
+
+void lookback_close_launch(uint8_t* window, const LbGeom& g, const int32_t* n_frames, hipStream_t stream) {
+    k_lb_close<<<1, 64, 0, stream>>>(window, g.frames, n_frames);
 }
 
 }  // namespace frcnn
@@ -236,32 +265,15 @@ extern "C" int frcnn_track_lookback(uint8_t* window, const uint8_t* frames_u8, l
                                     int lookback, int radius, int grow, int h, int w, uint8_t* out_frames, long long out_frame_stride,
                                     int32_t* out_tracked, long long out_tracked_stride, int32_t* out_count, void* stream) {
     const char* who = "track_lookback";
-    if (!window || !frames_u8 || !tracked || !n_frames || !out_frames || !out_tracked || !out_count) return fail(FRCNN_E_ARG, "%s: null pointer", who);
-    if (reinterpret_cast<uintptr_t>(window) & 15) return fail(FRCNN_E_ARG, "%s: window is not 16-byte aligned", who);
     LbGeom g;
-    const char* why;
-    if (!lb_geom(frames, h, w, max_rows, capacity, back, g, why))
-        return fail(FRCNN_E_ARG, "%s: %s out of range (frames=%d, %dx%d, max_rows=%d, capacity=%d, back=%d; at most %d rows in all)", who, why, frames,
-                    h, w, max_rows, capacity, back, FRCNN_REDACT_MAX_ROWS);
-    if (lookback < 1 || lookback > FRCNN_TRACK_LOOKBACK_MAX)
-        return fail(FRCNN_E_ARG, "%s: lookback=%d not in [1, %d]", who, lookback, FRCNN_TRACK_LOOKBACK_MAX);
-    if (radius < 0 || radius > FRCNN_TRACK_MOTION_MAX_RADIUS)
-        return fail(FRCNN_E_ARG, "%s: radius=%d not in [0, %d]", who, radius, FRCNN_TRACK_MOTION_MAX_RADIUS);
-    if (grow < 0 || grow > FRCNN_TRACK_MAX_GROW) return fail(FRCNN_E_ARG, "%s: grow=%d not in [0, %d]", who, grow, FRCNN_TRACK_MAX_GROW);
-    const long long frame_bytes = 3LL * h * w;
-    if (frames > 1 && (frame_stride < frame_bytes || out_frame_stride < frame_bytes))
-        return fail(FRCNN_E_ARG, "%s: frame_stride=%lld, out_frame_stride=%lld bytes, a %dx%d frame has %lld", who, frame_stride, out_frame_stride, h,
-                    w, frame_bytes);
-    if (frames > 1 && (tracked_stride < 4 + 8 * g.R || out_tracked_stride < 4 + 8 * g.R2))
-        return fail(FRCNN_E_ARG, "%s: tracked_stride=%lld (a buffer has %d words), out_tracked_stride=%lld (%d)", who, tracked_stride, 4 + 8 * g.R,
-                    out_tracked_stride, 4 + 8 * g.R2);
+    const int bad = lookback_check(who, window, frames_u8, frame_stride, tracked, tracked_stride, frames, n_frames, max_rows, capacity, back, lookback,
+                                   radius, grow, h, w, out_frames, out_frame_stride, out_tracked, out_tracked_stride, out_count, g);
+    if (bad != FRCNN_OK) return bad;
     hipStream_t st = as_stream(stream);
-    const long long quads = frame_bytes / 16 + 1;
-    const unsigned blocks = (unsigned)((quads + 255) / 256 < 256 ? (quads + 255) / 256 : 256);
-    k_lb_join<<<dim3(blocks, frames), 256, 0, st>>>(window, g, frames_u8, frame_stride, tracked, tracked_stride, n_frames);
+    lookback_join_launch(window, g, frames_u8, frame_stride, tracked, tracked_stride, n_frames, st);
     k_lb_chain<<<dim3(capacity, frames), TM_THREADS, 0, st>>>(window, g, n_frames, lookback, radius, grow);
     k_lb_counts<<<1, TM_THREADS, 0, st>>>(window, g, n_frames, lookback);
-    k_lb_emit<<<dim3(blocks, frames), 256, 0, st>>>(window, g, out_frames, out_frame_stride, out_tracked, out_tracked_stride, out_count);
-    k_lb_close<<<1, 64, 0, st>>>(window, frames, n_frames);
+    lookback_emit_launch(window, g, out_frames, out_frame_stride, out_tracked, out_tracked_stride, out_count, st);
+    lookback_close_launch(window, g, n_frames, st);
     return check_launch(who);
 }

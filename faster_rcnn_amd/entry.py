@@ -304,7 +304,7 @@ class _Slot:
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
                  "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
-                 "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames")
+                 "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack")
 
     def __init__(self):
         for name in self.__slots__:
@@ -554,6 +554,15 @@ class DetectionEntry:
                              "before a later pass could fill it (use passes of at least %d frames)" % (n, B, n))
         return n
 
+    @staticmethod
+    def track_backtrack_option(n, K, F):
+        """``submit_batch``'s ``track_backtrack`` checked against the pass's interval and its F source frames -> the look-back.
+        FrcnnError with the reason."""
+        try:
+            return ops.track_backtrack_option(n, K, F)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: track_backtrack=%r: %s" % (n, e)) from None
+
     def track_motion_state(self, h, w):
         """The engine's motion state for source frames of (h, w) (ops.track_motion_state), made on first use: the passes submitted with
         ``track_motion=`` keep their last frame in it.  A sequence that changes its frame size has no reference on the first frame of
@@ -691,10 +700,11 @@ class DetectionEntry:
             # the frames, as uploaded, and their tracked buffers then join the engine's window, the new tracks are followed back through
             # it, and the frames of the pass BEFORE come out: everything behind this point edits and encodes those (``out``), with their
             # widened tracked buffers (``rows_of``)
-            lb_frames = torch.zeros((B, in_h, in_w, 3), dtype=torch.uint8, device="cuda")
-            out = [lb_frames[i] for i in range(B)]
+            # (a ``track_backtrack`` pass is such a pass over its F = B * K source frames: F is B everywhere else)
+            lb_frames = torch.zeros((F, in_h, in_w, 3), dtype=torch.uint8, device="cuda")
+            out = [lb_frames[i] for i in range(F)]
             if s.frame_io is not None:                              # (raw read-back: the emitted frame, into the slot's pinned segment)
-                s.frame_io = [(lb_frames[i].view(-1), s.io_pin[i * seg:i * seg + npix]) for i in range(B)]
+                s.frame_io = [(lb_frames[i].view(-1), s.io_pin[i * seg:i * seg + npix]) for i in range(F)]
         else:
             out = u8 if annotate and self.device_preprocess else None
         if s.encode == JPEG_ENCODE:
@@ -750,13 +760,18 @@ class DetectionEntry:
                     else:
                         ops.track_update(t_state, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold, t_grow, out=s.track_out)
                     if s.track_lookback:
-                        lb_window, lb_back = self.track_lookback_window(in_h, in_w, B, ops.track_rows(packed))
+                        lb_window, lb_back = self.track_lookback_window(in_h, in_w, F, ops.track_rows(packed))
                         if s.lb_out is None:
                             R2 = ops.track_rows(packed) + ops.track_capacity(t_state) + lb_back
-                            s.lb_out = (lb_frames, torch.zeros((B, 4 + 8 * R2), dtype=torch.int32, device="cuda"),
+                            s.lb_out = (lb_frames, torch.zeros((F, 4 + 8 * R2), dtype=torch.int32, device="cuda"),
                                         torch.zeros(4, dtype=torch.int32, device="cuda"))
-                        ops.track_lookback(lb_window, s.io_dev, seg, s.track_out, s.n_frames_dev, ops.track_capacity(t_state), lb_back, in_h, in_w,
-                                           s.track_lookback, s.track_motion or 0, t_grow, out=s.lb_out)
+                        if s.track_backtrack:
+                            # behind the interval call: every tracked live row of the pass's key frames is followed back through the window
+                            ops.track_backtrack(lb_window, s.io_dev, seg, s.track_out, s.n_frames_dev, ops.track_capacity(t_state), lb_back, in_h,
+                                                in_w, s.track_backtrack, s.track_motion, t_grow, K, out=s.lb_out)
+                        else:
+                            ops.track_lookback(lb_window, s.io_dev, seg, s.track_out, s.n_frames_dev, ops.track_capacity(t_state), lb_back, in_h,
+                                               in_w, s.track_lookback, s.track_motion or 0, t_grow, out=s.lb_out)
                 for i in range(F):
                     rows = s.lb_out[1][i] if s.track_lookback else s.track_out[i] if s.track else packed[i] if B > 1 else packed
                     if s.redact:
@@ -772,7 +787,7 @@ class DetectionEntry:
                                               compress=compress)
                 if s.encode == Y4M_ENCODE:
                     if s.track_lookback:
-                        ops.y4m_encode_frames_u8(lb_frames.view(-1), npix, B, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
+                        ops.y4m_encode_frames_u8(lb_frames.view(-1), npix, F, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
                     else:
                         ops.y4m_encode_frames_u8(s.io_dev, seg, F, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
             return res
@@ -796,7 +811,8 @@ class DetectionEntry:
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
     def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None, jpeg_mode=JPEG_MODE,
-                      y4m_mode=Y4M_MODE, redact=None, draw=True, track=None, track_motion=None, track_lookback=None, detect_every=None):
+                      y4m_mode=Y4M_MODE, redact=None, draw=True, track=None, track_motion=None, track_lookback=None, detect_every=None,
+                      track_backtrack=None):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
         (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
@@ -807,7 +823,8 @@ class DetectionEntry:
         ``track_motion`` = R: with the motion step of radius R in front of every frame's match (ops.track_update_motion);
         ``track_lookback`` = L: with the look-back call behind the tracker (ops.track_lookback): the pass edits, encodes and returns the
         frames of the pass before it.  ``detect_every`` = K: a pass over B * K source frames whose network sees every K-th
-        (ops.track_update_interval)."""
+        (ops.track_update_interval); with ``track_backtrack`` = L: the back-track call behind it (ops.track_backtrack), a delayed pass as
+        a look-back pass is, over its B * K source frames."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -826,7 +843,7 @@ class DetectionEntry:
             s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
             s.encode, s.quality, s.jpeg_mode, s.y4m_mode = encode, quality, jpeg_mode, y4m_mode
             s.redact, s.nodraw, s.track, s.track_motion = redact, (None if draw else True), track, track_motion
-            s.track_lookback = track_lookback
+            s.track_lookback, s.track_backtrack = track_lookback or track_backtrack, track_backtrack      # (both: the delayed path is one)
             s.every, s.frames = detect_every, B * (detect_every or 1)
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
@@ -1058,7 +1075,7 @@ class DetectionEntry:
 
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
-                     track_lookback=None, detect_every=None):
+                     track_lookback=None, detect_every=None, track_backtrack=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1110,7 +1127,15 @@ class DetectionEntry:
         in order: a key frame's as a tracking pass returns it, a between frame's with num_rois 0 and dets made of the tracks -- the live
         ones with "track_id" and "propagated": True (the prob is that of the track's last match), then the held ones.  Not together with
         ``track_lookback`` (the look-back window holds one tracked buffer per network image); as every annotating pass, never a canvas
-        pass (its key is the exact geometry), and refused by name on an engine whose foreign preprocess uploads float pixels."""
+        pass (its key is the exact geometry), and refused by name on an engine whose foreign preprocess uploads float pixels.
+        ``track_backtrack`` = L (``detect_every`` passes only; ("backtrack", L) appended behind ("every", K); None in L's place: min(16,
+        batch * K); 1..16, at least K - 1 and at most batch * K): the back-track rule (DESIGN §8 "Back-track rule", ops.track_backtrack)
+        runs behind the interval call: every tracked live row of a key frame is followed BACKWARDS -- a track the key frame continues
+        through the between frames in front of it, a new one over L frames -- so a between frame is hidden from both sides: by the box
+        propagated forwards and by the one tracked back from the next detection.  The pass is a delayed pass exactly as a
+        ``track_lookback`` pass is -- ``collect_batch`` of submit k returns the results of submit k - 1, one per SOURCE frame, a submit
+        with no images is the flush, one sequence at a time --; its between frames keep "propagated": True on their live dets, and the
+        back-filled rows are dets with "backfilled" = k.  Not together with ``track_lookback``."""
         if (redact is not None or not draw) and not annotate:
             raise FrcnnError("submit_batch: redact= and draw=False change the frame an ANNOTATING pass returns: pass annotate=True")
         if track is not None:
@@ -1123,6 +1148,13 @@ class DetectionEntry:
             track_motion = self.track_motion_option(track_motion)
         if track_lookback is not None and track is None:
             raise FrcnnError("submit_batch: track_lookback= hides the tracker's new tracks in earlier frames: pass track=(thr, hold, grow) too")
+        if track_backtrack is not None:
+            if track_lookback is not None:
+                raise FrcnnError("submit_batch: track_backtrack= together with track_lookback= is not supported: the back-track rule hides a new "
+                                 "track in the earlier frames itself, and a pass has one window")
+            if detect_every is None:
+                raise FrcnnError("submit_batch: track_backtrack= follows the tracks of a detected frame back over the frames between two "
+                                 "detections: pass detect_every=K (with track= and track_motion=) too")
         if detect_every is not None:
             if track_motion is None:
                 raise FrcnnError("submit_batch: detect_every= follows the tracks by block matching between two detected frames: pass "
@@ -1168,7 +1200,7 @@ class DetectionEntry:
             raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
         self._check_epoch()
         B = self.batch if batch is None else batch
-        flush = track_lookback is not None and len(images) == 0
+        flush = (track_lookback is not None or track_backtrack is not None) and len(images) == 0
         if flush:
             if self._lookback_last is None:
                 raise FrcnnError("submit_batch: a flush (no images) follows a look-back submit; none is waiting")
@@ -1184,6 +1216,8 @@ class DetectionEntry:
         _, H, W, src, flip = pixels[0]
         if track_lookback is not None:
             track_lookback = self.track_lookback_option(track_lookback, B)
+        if track_backtrack is not None:
+            track_backtrack = self.track_backtrack_option(track_backtrack, detect_every, B * detect_every)
         if annotate:
             if not self.device_preprocess:
                 raise FrcnnError("annotating passes need the device-side preprocess (a foreign preprocess_func uploads float pixels)")
@@ -1206,6 +1240,8 @@ class DetectionEntry:
                 key = key + ("lookback", track_lookback)
             if detect_every is not None:
                 key = key + ("every", detect_every)
+            if track_backtrack is not None:
+                key = key + ("backtrack", track_backtrack)
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -1215,9 +1251,9 @@ class DetectionEntry:
         else:
             capture = lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality,
                                                  jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode, redact, draw, track, track_motion,
-                                                 track_lookback, detect_every)
+                                                 track_lookback, detect_every, track_backtrack)
             s = self.cache.acquire(key, capture)
-            if track_lookback is not None:
+            if track_lookback is not None or track_backtrack is not None:
                 self._lookback_last = (key, capture)
         return self._replay(s, images, pixels, resize_ratios, det_threshold)
 
@@ -1261,10 +1297,10 @@ class DetectionEntry:
             own = emitted = None
             if s.track_lookback:                                    # this pass returns the group its window held; its own group waits
                 in_h, in_w = int(s.lb_out[0].shape[1]), int(s.lb_out[0].shape[2])
-                own = {"images": list(images), "n_rois": None} if images else None
-                emitted = self._lookback_waiting.pop((in_h, in_w, B), None)
+                own = {"images": list(images), "n_rois": None, "frames": len(pixels)} if images else None
+                emitted = self._lookback_waiting.pop((in_h, in_w, s.frames), None)
                 if own is not None:
-                    self._lookback_waiting[(in_h, in_w, B)] = own
+                    self._lookback_waiting[(in_h, in_w, s.frames)] = own
                 words = s.lb_out[1].numel()
                 s.lb_pin[:words].copy_(s.lb_out[1].view(-1), non_blocking=True)
                 s.lb_pin[words:].copy_(s.lb_out[2], non_blocking=True)
@@ -1272,7 +1308,7 @@ class DetectionEntry:
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
             for i in range(len(pixels) if s.track else 0):
                 s.track_pin[i].copy_(s.track_out[i], non_blocking=True)
-            for i in range(len(emitted["images"]) if emitted else 0 if s.track_lookback else len(pixels)):
+            for i in range(emitted["frames"] if emitted else 0 if s.track_lookback else len(pixels)):
                 if s.encode == JPEG_ENCODE:
                     s.png_pin[i].copy_(s.png_dev[i][:s.first_copy], non_blocking=True)
                 elif s.encode:
@@ -1499,19 +1535,22 @@ class DetectionEntry:
         if group["n_rois"] is None:
             raise FrcnnError("collect_batch: look-back tickets are collected in submit order")
         lb = s.lb_pin.numpy()
-        words = (lb.size - 4) // s.batch
-        if int(lb[-4]) != len(group["images"]):
-            raise FrcnnError("look-back window: %d frames emitted for a group of %d" % (int(lb[-4]), len(group["images"])))
+        words = (lb.size - 4) // s.frames
+        if int(lb[-4]) != group["frames"]:
+            raise FrcnnError("look-back window: %d frames emitted for a group of %d" % (int(lb[-4]), group["frames"]))
+        K = s.every or 1                                            # (a ``track_backtrack`` pass: one result per source frame)
         res = []
-        for i in range(len(group["images"])):
+        for i in range(group["frames"]):
             n_rows, n_live, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(lb[i * words:(i + 1) * words])
             dets = []
             for k in range(int(n_rows[0])):
                 d = {"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(), "track_id": int(t_id[k])}
                 if k >= int(n_live[0]):
                     d["held" if int(t_age[k]) > 0 else "backfilled"] = abs(int(t_age[k]))
+                elif i % K:                                         # a between frame: its live dets are the tracks
+                    d["propagated"] = True
                 dets.append(d)
-            res.append((group["n_rois"][i], dets) + self._payload(s, i))
+            res.append((0 if i % K else group["n_rois"][i // K], dets) + self._payload(s, i))
         return res
 
     def collect(self, ticket):

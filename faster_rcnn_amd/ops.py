@@ -1487,6 +1487,59 @@ def track_lookback(window, frames_u8, frame_stride, tracked, n_frames, capacity,
     return out
 
 
+def track_backtrack_option(n, k, frames):
+    """(host only) The look-back of a back-tracking pass checked against its interval ``k`` and its ``frames`` source frames, None (or a
+    bare option, True) replaced by min(16, frames): an integer in 1..16, at least k - 1 and at most ``frames``.  ValueError with the
+    reason."""
+    lo, hi, _ = TRACK_LOOKBACK
+    k, frames = int(k), int(frames)
+    if n is None or n is True:
+        n = min(hi, frames)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not lo <= int(n) <= hi:
+        raise ValueError("track backtrack=%r: an integer in %d..%d" % (n, lo, hi))
+    n = int(n)
+    if n < k - 1:
+        raise ValueError("track backtrack=%d does not reach over the %d frames between two detections: frames no detection reaches would stay "
+                         "uncovered; at least %d with a detection every %d frames" % (n, k - 1, k - 1, k))
+    if n > frames:
+        raise ValueError("track backtrack=%d reaches further back than a pass of %d frames holds: a frame would be emitted before its rows are "
+                         "in place; at most %d here" % (n, frames, frames))
+    return n
+
+
+def track_backtrack(window, frames_u8, frame_stride, tracked, n_frames, capacity, back, h, w, lookback, radius, grow, interval, out=None):
+    """One call of the back-track rule (DESIGN §8 "Back-track rule", frcnn_track_backtrack): ``track_lookback`` over the F frames of an
+    interval call -- ``tracked`` is ``track_update_interval``'s (F, 4 + 8R) result with the same ``interval`` --, where every tracked live
+    row of a KEY frame is followed backwards: a new track over at most ``lookback`` frames, a continued one through the between frames in
+    front of its key frame.  ``window`` is a ``track_lookback_state`` for F frames; everything else, ``out`` and the return value: as
+    ``track_lookback``.  With ``interval`` 1 every byte is ``track_lookback``'s.  Five launches; the call can be captured in a graph."""
+    _require_gpu()
+    h, w, cap, back = int(h), int(w), int(capacity), int(back)
+    assert window.is_cuda and window.dtype == torch.uint8 and window.dim() == 1 and window.is_contiguous()
+    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.is_contiguous() and tracked.dim() == 2
+    F, words = int(tracked.shape[0]), int(tracked.shape[1])
+    R = (words - 4) // 8
+    rows, R2 = R - cap, R + back
+    assert words == 4 + 8 * R and rows >= 1, "track_backtrack: tracked buffers of %d words for capacity=%d" % (words, cap)
+    need = int(_lib.load().frcnn_track_lookback_state_bytes(F, h, w, rows, cap, back))
+    if need and int(window.numel()) != need:
+        raise _lib.FrcnnError("track_backtrack: the window has %d bytes; one for calls of %d frames of %dx%d with %d + %d + %d rows has %d "
+                              "(track_lookback_state with the call's frames, rows, capacity and back)" % (window.numel(), F, h, w, rows, cap, back, need))
+    assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
+    assert int(frame_stride) >= 0 and int(frames_u8.numel()) >= (F - 1) * int(frame_stride) + 3 * h * w
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    if out is None:
+        out = (torch.zeros((F, h, w, 3), dtype=torch.uint8, device="cuda"), torch.zeros((F, 4 + 8 * R2), dtype=torch.int32, device="cuda"),
+               torch.zeros(1, dtype=torch.int32, device="cuda"))
+    o_frames, o_tracked, o_count = out
+    assert o_frames.is_cuda and o_frames.dtype == torch.uint8 and o_frames.is_contiguous() and tuple(o_frames.shape) == (F, h, w, 3)
+    assert o_tracked.is_cuda and o_tracked.dtype == torch.int32 and o_tracked.is_contiguous() and tuple(o_tracked.shape) == (F, 4 + 8 * R2)
+    assert o_count.is_cuda and o_count.dtype == torch.int32 and o_count.numel() >= 1
+    _lib.call("frcnn_track_backtrack", _p(window), _p(frames_u8), int(frame_stride), _p(tracked), words, F, _p(n_frames), rows, cap, back,
+              int(lookback), int(radius), int(grow), int(interval), h, w, _p(o_frames), 3 * h * w, _p(o_tracked), 4 + 8 * R2, _p(o_count), _stream())
+    return out
+
+
 def split_tracked(buf):
     """Views (n_rows, n_live, next_id, overflow, bbox, cls, prob, id, age) into ONE tracked buffer (device tensor or its host copy,
     torch or numpy), as ``split_detections`` cuts up a ``det_packed``: the four counts are one-word views, bbox is (R, 4), prob float32."""

@@ -27,7 +27,8 @@ to PNG files with the device encoder -- and reports the frames/s of both and the
 (IoU 30 %, hold 8, grow 0, the defaults), alternating in one session through in-memory annotating passes; ``--track_motion`` likewise
 (``run_track_motion``) the ``--track`` leg without and with ``--track_motion 8``, and the tracker part of one pass alone; tracking passes replay on one
 stream of the engine, so the figure includes what that ordering costs.  ``--detect_every`` (``run_detect_every``) runs the ``--track --track_motion 8`` leg
-without and with ``--detect_every 4``.  ``--track_lookback`` (``run_track_lookback``) runs the
+without and with ``--detect_every 4``.  ``--track_backtrack`` (``run_track_backtrack``) runs the ``--detect_every 4`` leg without and with
+``--track_backtrack`` at its default, and times the back-track call of one pass alone.  ``--track_lookback`` (``run_track_lookback``) runs the
 ``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
 look-back call of one pass alone.
 
@@ -91,7 +92,7 @@ def annotate_in_memory(eng, resized, ratios, **kwargs):
         window.append(eng.submit_batch(part[::K], ratios[i:i + B * K:K], 0.0, [eng.host_pixels(r) for r in part], batch=B, annotate=True, **kwargs))
         if len(window) >= eng.in_flight:
             frames += [r[2] for r in eng.collect_batch(window.pop(0))]
-    if kwargs.get("track_lookback") is not None:
+    if kwargs.get("track_lookback") is not None or kwargs.get("track_backtrack") is not None:
         window.append(eng.submit_batch([], [], 0.0, [], batch=B, annotate=True, **kwargs))
     while window:
         frames += [r[2] for r in eng.collect_batch(window.pop(0))]
@@ -570,6 +571,104 @@ def run_detect_every(name, cfg, n_frames, reps, content="noise"):
     return res
 
 
+def backtrack_part_us(eng, h, w, lookback, radius, interval, iters=20):
+    """``lookback_part_us`` for ops.track_backtrack: ONE pass of eng.batch * ``interval`` noise frames on a window of its own.  Every KEY
+    frame of the pass sees LOOKBACK_BIRTHS tracks it continues (corrections: they walk the ``interval`` - 1 frames in front of it) and
+    LOOKBACK_BIRTHS new ones (births: they walk ``lookback`` frames); a between frame shows the continued tracks.  -> the median in
+    microseconds."""
+    import numpy as np
+    import torch
+    from faster_rcnn_amd import ops
+    F, rows, cap = eng.batch * interval, 300, ops.track_capacity(eng.track_state())
+    R, back = rows + cap, min(cap, 512 - rows - cap)
+    rs = np.random.RandomState(11)
+    frames = torch.from_numpy(rs.randint(0, 256, (F, h, w, 3)).astype(np.uint8)).cuda()
+    tracked = np.zeros((F, 4 + 8 * R), dtype=np.int32)
+    tracked[:, 4:4 + 5 * R] = -1
+    n = LOOKBACK_BIRTHS
+    window = ops.track_lookback_state(F, h, w, rows, cap, back)
+    nf = torch.tensor([F], dtype=torch.int32, device="cuda")
+    out, times, next_id = None, [], n + 1                            # ids 1..n: the continued tracks
+    for it in range(iters + 1):
+        for f in range(F):
+            key = f % interval == 0
+            m = 2 * n if key else n
+            x, y = rs.randint(0, w - 120, m), rs.randint(0, h - 120, m)
+            side = rs.randint(40, 121, m)
+            tracked[f, 4:4 + 5 * R] = -1
+            tracked[f, 4 + 6 * R:4 + 7 * R] = 0
+            tracked[f, 4:4 + 4 * m] = np.stack([x, y, x + side, y + side], axis=1).reshape(-1)
+            tracked[f, 4 + 4 * R:4 + 4 * R + m] = 1
+            tracked[f, 4 + 6 * R:4 + 6 * R + n] = np.arange(1, n + 1)
+            if key:
+                tracked[f, 4 + 6 * R + n:4 + 6 * R + m] = np.arange(next_id, next_id + n)
+                next_id += n
+            tracked[f, :4] = (m, m, next_id, 0)
+        dev = torch.from_numpy(tracked).cuda()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = ops.track_backtrack(window, frames, h * w * 3, dev, nf, cap, back, h, w, lookback, radius, TRACK_LEG[2], interval, out=out)
+        b.record()
+        b.synchronize()
+        if it:                                                      # (the first call has no window in front of it)
+            times.append(a.elapsed_time(b) * 1000.0)
+    return round(statistics.median(times), 1)
+
+
+def run_track_backtrack(name, cfg, n_frames, reps, content="noise"):
+    """``--track_backtrack``: what the back-track rule costs on top of ``--detect_every 4``.  One pair of legs in ONE session, alternating
+    inside every repetition: ``run_detect_every``'s ``detect_every`` leg without and with ``track_backtrack`` at the command line's default,
+    min(16, frames per pass) (the tracker is reset in front of every run; the back-track run ends with its flush submit).  Reports
+    frames/s of both and their ratio, the tracker's state and the windows' back_overflow at the end, and the HIP-event time of the
+    back-track call of one pass alone (``backtrack_part_us``) at radius 8 and at radius 0."""
+    import numpy as np
+    import torch
+    from faster_rcnn_amd import entry, ops, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+    lookback = ops.track_backtrack_option(None, EVERY_LEG, eng.batch * EVERY_LEG)
+    overflow = []
+
+    def leg(**kw):
+        def run():
+            eng.track_reset()
+            out = annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, track=TRACK_LEG, track_motion=MOTION_LEG, detect_every=EVERY_LEG, **kw)
+            if kw:                                                  # (read in front of the next reset)
+                overflow.append([int(win[:12].view(torch.int32)[2]) for win, _ in eng._track_lookback_windows.values()])
+            return out
+        return run
+
+    legs = {"detect_every": leg(), "track_backtrack": leg(track_backtrack=lookback)}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    torch.cuda.synchronize()
+    state = eng.track_state().cpu().numpy()
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact": ["all", "blur", 12, 0], "track": list(TRACK_LEG), "track_motion": MOTION_LEG, "detect_every": EVERY_LEG,
+           "track_backtrack": lookback, "images_per_pass": eng.batch, "frames_per_pass": eng.batch * EVERY_LEG, "in_flight": eng.in_flight,
+           "tracker": {"live_slots": int(state[0]), "ids_issued": int(state[1]), "overflow": int(state[2]), "frames": int(state[3])},
+           "back_overflow": overflow[-1]}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["backtrack_over_every"] = round(statistics.median(times["detect_every"]) / statistics.median(times["track_backtrack"]), 3)
+    res["backtrack_part_us"] = {"corrections_and_births_per_key_frame": [LOOKBACK_BIRTHS, LOOKBACK_BIRTHS],
+                                "track_backtrack": backtrack_part_us(eng, h, w, lookback, MOTION_LEG, EVERY_LEG),
+                                "track_backtrack_radius_0": backtrack_part_us(eng, h, w, lookback, 0, EVERY_LEG)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--frames", type=int, default=256)
@@ -591,6 +690,8 @@ def main():
                                                                   "with --track_lookback at its default, alternating in one session")
     ap.add_argument("--detect_every", action="store_true", help="instead of the legs above: the --track --track_motion 8 leg without and "
                                                                 "with --detect_every 4, alternating in one session")
+    ap.add_argument("--track_backtrack", action="store_true", help="instead of the legs above: the --detect_every 4 leg without and with "
+                                                                   "--track_backtrack at its default, alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -599,6 +700,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.track_backtrack:
+            out[name] = run_track_backtrack(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.detect_every:
             out[name] = run_detect_every(name, PAIRS[name], args.frames, args.reps, args.content)
