@@ -315,6 +315,10 @@ struct X6Tile {
     static constexpr size_t lds = planes > epi ? planes : epi;
 };
 
+// LDS bytes of x6_epilogue_vec<.., GRES>: the staging tile of one wave-row and the tap records of the row tile behind it
+template <int TM, int TN, int WM, int WN>
+constexpr size_t x6_gres_lds = X6Tile<TM, TN, WM, WN>::epi + (size_t)X6Tile<TM, TN, WM, WN>::BM * 32;
+
 // The 16-byte epilogue of conv_f32_common.h (epilogue_vec: same arithmetic per element, same order) with the tile turned through
 // LDS one WAVE-ROW at a time: pass h stages the 32 TM rows owned by the waves with wm == h, every thread then owns 16-byte pieces
 // of whole rows (scale / shift / residual / mask / y as b128, out-of-range pieces on the buffer descriptors).
@@ -336,8 +340,11 @@ __device__ __forceinline__ f32x4 roi_res_piece(const f32x4 a, const f32x4 b, con
 
 // GRES (ConvArgs.res_map): the residual is not read but resampled here -- per row the tap record (offsets of the four source rows of
 // the map, tx, ty, ok), per piece four 16-byte loads of the map (L2 / Infinity Cache: the map is a few per cent of the tensor it
-// replaces) and roi_res_piece, or the piece of res_fill when the RoI was rejected.  The records of wave-row h + 1 are requested with
-// the pieces of wave-row h, so only the first wave-row waits for its records.  Everything behind the residual is the common code.
+// replaces) and roi_res_piece, or the piece of res_fill when the RoI was rejected.  The records of the whole row tile (32 bytes per
+// row) are loaded ONCE at entry, one 16-byte word per thread, into LDS behind the staging tile (x6_gres_lds bytes in all) and one
+// barrier later are read-only: a wave-row reads its four offsets (ds_read_b128) right before its map loads and tx / ty / ok again at
+// the interpolation, so no part of a record is held in registers across the LDS turn and the 32 threads of a row share one broadcast
+// read instead of 32 dependent loads.  Everything behind the residual is the common code.
 template <int TM, int TN, int WM, int WN, bool PLANES = false, bool S16 = false, bool GRES = false>
 __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const ConvArgs& p, int m0, int n0, int tid, int wm, int wn, int li, int lh, float* smem,
                                                 float y_scale = 1.0f) {
@@ -367,25 +374,22 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
     f32x4 rres[PASSES], rmask[PASSES];
     float vmax = 0.0f;
     unsigned pseen = 0u;
-    // GRES: the map, the tap records (two 16-byte words per row) and the fill piece of this thread's columns
+    // GRES: the map, the fill piece of this thread's columns and the tile's tap records -- BM records of 32 bytes, staged once in LDS
+    // behind the wave-row's staging tile (the operand buffers are dead; the caller synchronised behind their last read)
     const __amdgpu_buffer_rsrc_t gmrsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(GRES ? p.res_map : p.x), 0, GRES ? (int)((size_t)p.res_map_rows * p.Cout * 4) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t gtrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void*>(GRES ? p.res_taps : (const void*)p.x), 0, GRES ? (int)((size_t)p.M * 32) : 0, 0x00020000);
     f32x4 gfill = {0.0f, 0.0f, 0.0f, 0.0f}, graw[GRES ? PASSES : 1][4];
-    i32x4 goff[GRES ? PASSES : 1], gw[GRES ? PASSES : 1];
-    auto fetch_taps = [&](int h) {                           // (rows past M: an out-of-range request reads zeros -- ok = 0, offsets 0)
-#pragma unroll
-        for (int q = 0; q < (GRES ? PASSES : 0); ++q) {
-            const int m = m0 + h * HB + q * RPP + prow;
-            const unsigned toff = (h < WM && m < p.M) ? (unsigned)m * 32u : OOB_OFFSET;
-            goff[q] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(gtrsrc, toff, 0, 0));
-            gw[q] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(gtrsrc, toff == OOB_OFFSET ? OOB_OFFSET : toff + 16u, 0, 0));
-        }
-    };
+    const char* const grec = reinterpret_cast<const char*>(smem + HB * LD) + prow * 32;      // + (h * HB + q * RPP) * 32: the record of this thread's row
     if constexpr (GRES) {
+        static_assert(2 * HB * WM <= NT && (HB * LD * 4) % 16 == 0, "one 16-byte word of the tile's records per thread");
+        if (tid < 2 * HB * WM) {                             // (rows past M: an out-of-range request reads zeros -- ok = 0, offsets 0)
+            const __amdgpu_buffer_rsrc_t gtrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res_taps), 0, (int)((size_t)p.M * 32), 0x00020000);
+            const int m = m0 + (tid >> 1);
+            const i32x4 w = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(gtrsrc, m < p.M ? (unsigned)m * 32u + (unsigned)(tid & 1) * 16u : OOB_OFFSET, 0, 0));
+            *reinterpret_cast<i32x4*>(reinterpret_cast<char*>(smem + HB * LD) + tid * 16) = w;
+        }
         if (p.res_fill && n < p.Cout) gfill = *reinterpret_cast<const f32x4*>(p.res_fill + n);
-        fetch_taps(0);
+        __syncthreads();                                     // the records are read-only from here on
     }
     auto fetch = [&](int h) {                                // the global reads of wave-row h: in flight while it goes through LDS
 #pragma unroll
@@ -393,9 +397,10 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
             const int m = m0 + h * HB + q * RPP + prow;
             const bool in = m < p.M && n < p.Cout;
             if constexpr (GRES) {
+                const i32x4 goff = *reinterpret_cast<const i32x4*>(grec + (h * HB + q * RPP) * 32);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    graw[q][k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gmrsrc, in ? ((unsigned)goff[q][k] + (unsigned)n) * 4u : OOB_OFFSET, 0, 0));
+                    graw[q][k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gmrsrc, in ? ((unsigned)goff[k] + (unsigned)n) * 4u : OOB_OFFSET, 0, 0));
             } else if (p.residual) rres[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, in ? (unsigned)(((size_t)m * p.ldres + n) * 4) : OOB_OFFSET, 0, 0));
             else if (p.res_planes) {                         // (8 + 8 bytes: the same bytes per element as the f32 tensor)
                 typedef _Float16 f16x4r __attribute__((ext_vector_type(4)));
@@ -412,16 +417,6 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
 #pragma unroll 1
     for (int h = 0; h < WM; ++h) {
         fetch(h);
-        float gtx[PASSES], gty[PASSES];
-        bool gok[PASSES];
-        if constexpr (GRES) {                                // this wave-row's fractions are kept, its records make way for the next wave-row's
-#pragma unroll
-            for (int q = 0; q < PASSES; ++q) {
-                const int wtx = gw[q][0], wty = gw[q][1];    // (copies: __builtin_bit_cast of a vector ELEMENT reads element 0 whatever the index)
-                gtx[q] = __builtin_bit_cast(float, wtx); gty[q] = __builtin_bit_cast(float, wty); gok[q] = gw[q][2] != 0;
-            }
-            fetch_taps(h + 1);
-        }
         if (h) __syncthreads();                              // the previous wave-row has been read out (the caller synchronised before pass 0)
         if (wm == h) {
 #pragma unroll
@@ -441,16 +436,16 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
                 }
         }
         __syncthreads();
-        if constexpr (GRES) {
-#pragma unroll
-            for (int q = 0; q < PASSES; ++q) {
-                const f32x4 v = roi_res_piece(graw[q][0], graw[q][1], graw[q][2], graw[q][3], gtx[q], gty[q]);
-                rres[q] = gok[q] ? v : gfill;
-            }
-        }
         const float* src = smem + prow * LD + pcol;
 #pragma unroll
         for (int q = 0; q < PASSES; ++q) {
+            if constexpr (GRES) {                            // tx, ty, ok: read back here, nothing of the record stays in registers across the turn
+                typedef int i32x3 __attribute__((ext_vector_type(3)));
+                const i32x3 gw = *reinterpret_cast<const i32x3*>(grec + (h * HB + q * RPP) * 32 + 16);
+                const int wtx = gw[0], wty = gw[1];          // (copies: __builtin_bit_cast of a vector ELEMENT reads element 0 whatever the index)
+                const f32x4 v = roi_res_piece(graw[q][0], graw[q][1], graw[q][2], graw[q][3], __builtin_bit_cast(float, wtx), __builtin_bit_cast(float, wty));
+                rres[q] = gw[2] != 0 ? v : gfill;
+            }
             const f32x4 a = *reinterpret_cast<const f32x4*>(src + q * RPP * LD);
             f32x4 v;
 #pragma unroll

@@ -673,15 +673,18 @@ __global__ void __launch_bounds__(64 * WM * WN) k_conv_igemm_h3_db(const ConvArg
     load_next();                                          // chunk 0: in flight while the two scales are fetched
     h3_fp16_saturate();
     const float x_max = amax_read(p.x_amax);
-    const int eA = APLANES ? *p.x_pexp : h3_exponent(x_max);
-    const int eB = h3_exponent(*reinterpret_cast<const float*>(wbase));
+    // (GRES: the exponents, uniform but vector registers to the compiler, are held in scalar registers over the loop -- the f32-input form
+    // otherwise spills one VGPR around it, as the form without the gather does)
+    const auto uni = [](int v) { return GRES ? __builtin_amdgcn_readfirstlane(v) : v; };
+    const int eA = uni(APLANES ? *p.x_pexp : h3_exponent(x_max));
+    const int eB = uni(h3_exponent(*reinterpret_cast<const float*>(wbase)));
     const float sA = h3_pow2(eA);
     if constexpr (!APLANES) h3_check_record(p.x_amax, x_max);
     unsigned seen = 0u;
     // the output's planes: |y| <= bound_c * max|x| + bound_d (+ max|residual|) whatever the data, so that bound's exponent cannot overflow
     int eY = 0;
     if (p.y_planes) {
-        eY = h3_exponent(p.bound_c * x_max + p.bound_d + (p.res_amax ? amax_read(p.res_amax) : 0.0f));
+        eY = uni(h3_exponent(p.bound_c * x_max + p.bound_d + (p.res_amax ? amax_read(p.res_amax) : 0.0f)));
         if (blockIdx.x == 0 && tid == 0) *p.y_pexp = eY;
     }
     auto store_from = [&](int buf, f32x4 (&ra)[PA], f32x4 (&rb)[PBT]) {
@@ -781,6 +784,7 @@ static int launch_h3_db(const ConvArgs& a, hipStream_t s, bool ring_ok = true) {
     static std::atomic<uint64_t> lds_seen{0}, lds_seen_planes{0};
     if (p.res_map) {                                      // the residual gathered by RoI taps: sixteen waves of 64x32, never the ring
         if constexpr (WM * WN == 16 && TN == 1) {
+            static_assert(lds >= x6_gres_lds<TM, TN, WM, WN>, "the epilogue's wave-row and the tile's tap records must fit in the operand buffers");
             if (!p.vec_epi || p.residual || p.res_planes || p.mask || p.n_split) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_roi_res: a dense single-layer launch with 16-byte addressable rows");
             static std::atomic<uint64_t> lds_seen_gres{0}, lds_seen_gres_planes{0};
             if (p.x_planes) {
