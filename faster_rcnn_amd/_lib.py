@@ -168,6 +168,14 @@ ROI_RES_SIGNATURES = {
 }
 
 
+POOL_EPILOGUE_VERSION = 1     # include/ext/frcnn_hip_pool_epilogue.h FRCNN_POOL_EPILOGUE_VERSION
+POOL_EPILOGUE_SIGNATURES = {
+    "frcnn_pool_epilogue_version": (I, []),
+    "frcnn_conv2d_pool_available": (I, [P, I, I, I]),
+    "frcnn_conv2d_fwd_h3_pool": (I, [P, P, P, P, P, P, P, P, P, P, I, P, P, P, P]),
+}
+
+
 class RoiRes(ctypes.Structure):
     """frcnn_roi_res (include/ext/frcnn_hip_roi_res.h)."""
     _fields_ = [("map", c_void_p), ("taps", c_void_p), ("fill", c_void_p), ("map_rows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
@@ -496,6 +504,10 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in POOL_EPILOGUE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
     for name, (res, args) in PNG_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -613,6 +625,9 @@ def load():
     if lib.frcnn_roi_res_version() != ROI_RES_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_roi_res_version()} of the gathered-residual extension, this binding "
                          f"{ROI_RES_VERSION} (include/ext/frcnn_hip_roi_res.h): rebuild with `python -m faster_rcnn_amd.build`")
+    if lib.frcnn_pool_epilogue_version() != POOL_EPILOGUE_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_pool_epilogue_version()} of the pooled-epilogue extension, this binding "
+                         f"{POOL_EPILOGUE_VERSION} (include/ext/frcnn_hip_pool_epilogue.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_vgg_canvas_version() != VGG_CANVAS_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_vgg_canvas_version()} of the VGG16 canvas extension, this binding "
                          f"{VGG_CANVAS_VERSION} (include/ext/frcnn_hip_vgg_canvas.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -46,6 +46,10 @@ struct ConvArgs {
     // res_map [res_map_rows][Cout] f32, res_taps one 32-byte record per output row (k_roi_tap_table), res_fill [Cout] or NULL: what a
     // rejected RoI yields.  The 16-waves 256x128 forms of conv_h3.hip only, as instantiations of their own (x6_epilogue_vec<.., GRES>).
     const float* res_map = nullptr; const void* res_taps = nullptr; const float* res_fill = nullptr; int res_map_rows = 0;
+    // the output AVERAGED over groups of pool_rows consecutive rows inside the epilogue (include/ext/frcnn_hip_pool_epilogue.h; 0 = off):
+    // a row tile starts at row t * pool_groups * pool_rows and holds pool_groups whole groups, y is [M / pool_rows][ldy] -- the 16-waves
+    // 256x128 plane-reading form of conv_h3.hip only, as an instantiation of its own (x6_epilogue_vec<.., POOL>).
+    int pool_rows = 0, pool_groups = 0;
 };
 
 // ---- magnitude records.  A record is AMAX_SLOTS floats, one per 128-byte line: a launch has hundreds to thousands of waves and a
@@ -345,16 +349,26 @@ __device__ __forceinline__ f32x4 roi_res_piece(const f32x4 a, const f32x4 b, con
 // barrier later are read-only: a wave-row reads its four offsets (ds_read_b128) right before its map loads and tx / ty / ok again at
 // the interpolation, so no part of a record is held in registers across the LDS turn and the 32 threads of a row share one broadcast
 // read instead of 32 dependent loads.  Everything behind the residual is the common code.
-template <int TM, int TN, int WM, int WN, bool PLANES = false, bool S16 = false, bool GRES = false>
+// POOL (ConvArgs.pool_rows): the tile is not stored but AVERAGED over its groups of pool_rows rows (k_pool<false> of pool.hip behind the
+// launch, bit for bit: acc = 0.0f, the group's rows added one by one in ascending order, one division).  The caller's row tile starts
+// at m0 = tile * pool_groups * pool_rows and holds pool_groups whole groups; the rows of the 32 TM WM computed behind them belong to the
+// next tile or lie past M: no residual is requested for them and no sum reads them.  A thread of the common code owns rows prow + RPP q
+// of a wave-row, not a run of them, so each writes its finished piece back to its place in the staging tile; one barrier later thread
+// (j, c) = (tid / BN, tid % BN), group j and column c, adds the rows of ITS group that lie in this wave-row to a register it keeps over
+// the WM wave-rows (they are walked in row order; a wave reads 64 consecutive columns of one row: no bank conflict), and stores
+// acc / pool_rows to y[(tile * pool_groups + j) * ldy + n0 + c] behind the last.  The `if (h) __syncthreads()` of the next wave-row
+// keeps its staging behind these reads.  y_amax receives max |pooled value|.
+template <int TM, int TN, int WM, int WN, bool PLANES = false, bool S16 = false, bool GRES = false, bool POOL = false>
 __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const ConvArgs& p, int m0, int n0, int tid, int wm, int wn, int li, int lh, float* smem,
                                                 float y_scale = 1.0f) {
     constexpr int NT = 64 * WM * WN, BN = 32 * TN * WN, HB = 32 * TM, LD = BN + 4, C4 = BN / 4, RPP = NT / C4, PASSES = HB / RPP;
     static_assert(HB % RPP == 0 && NT % C4 == 0 && PASSES >= 1 && PASSES <= 8, "epilogue passes");
+    static_assert(!POOL || (!PLANES && !GRES), "the pooled form: f32 output, residual read or none");
     const bool second = p.n_split && n0 >= p.n_split;       // two layers in one launch: the tile belongs to ONE of them (host guarantees it)
     float* const yb = second ? p.y2 : p.y;
     const int y_ld = second ? p.ldy2 : p.ldy, y_act = second ? p.act2 : p.act, y_n0 = second ? p.n_split : 0;
     const int y_cols = p.n_split ? (second ? p.Cout - p.n_split : p.n_split) : p.Cout;
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(yb, 0, (int)((size_t)p.M * y_ld * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(yb, 0, POOL ? 0 : (int)((size_t)p.M * y_ld * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t prsrc = __builtin_amdgcn_make_buffer_rsrc(PLANES ? p.y_planes : (void*)yb, 0, PLANES ? (int)((size_t)2 * p.M * p.Cout * 2) : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(p.residual ? p.residual : p.x), 0, p.residual ? (int)((size_t)p.M * p.ldres * 4) : 0, 0x00020000);
@@ -391,11 +405,17 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
         if (p.res_fill && n < p.Cout) gfill = *reinterpret_cast<const f32x4*>(p.res_fill + n);
         __syncthreads();                                     // the records are read-only from here on
     }
+    // POOL: the rows of the tile that belong to it, this thread's group and column, its running sum
+    const int pool_tile_rows = POOL ? p.pool_rows * p.pool_groups : 0;
+    const int pool_j = tid / BN, pool_c = tid % BN;
+    const int pool_lo = pool_j * p.pool_rows, pool_hi = pool_lo + p.pool_rows, pool_out = (m0 / (POOL ? p.pool_rows : 1)) + pool_j;
+    const bool pool_on = POOL && pool_j < p.pool_groups && pool_out * p.pool_rows < p.M && n0 + pool_c < p.Cout;
+    float pool_acc = 0.0f;
     auto fetch = [&](int h) {                                // the global reads of wave-row h: in flight while it goes through LDS
 #pragma unroll
         for (int q = 0; q < PASSES; ++q) {
             const int m = m0 + h * HB + q * RPP + prow;
-            const bool in = m < p.M && n < p.Cout;
+            const bool in = m < p.M && n < p.Cout && (!POOL || h * HB + q * RPP + prow < pool_tile_rows);
             if constexpr (GRES) {
                 const i32x4 goff = *reinterpret_cast<const i32x4*>(grec + (h * HB + q * RPP) * 32);
 #pragma unroll
@@ -455,6 +475,10 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
                 if (p.mask && !(rmask[q][c] > 0.0f)) t = 0.0f;
                 v[c] = activate(t, y_act);
             }
+            if constexpr (POOL) {                            // back to its place in the staging tile: the sums below walk the rows in order
+                *reinterpret_cast<f32x4*>(smem + (q * RPP + prow) * LD + pcol) = v;
+                continue;
+            }
             const int ym = m0 + h * HB + q * RPP + prow, yn = n0 - y_n0 + pcol;
             const bool in = ym < p.M && yn < y_cols;
             const unsigned yoff = in ? (unsigned)(((size_t)ym * y_ld + yn) * 4) : OOB_OFFSET;
@@ -475,6 +499,22 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, h), prsrc, poff, 0, 0);
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, l), prsrc, poff == OOB_OFFSET ? OOB_OFFSET : poff + (unsigned)((size_t)p.M * p.Cout * 2), 0, 0);
             }
+        }
+        if constexpr (POOL) {
+            __syncthreads();                                 // the wave-row's finished values are all in the staging tile
+            if (pool_on) {
+                const int lo = pool_lo > h * HB ? pool_lo : h * HB, hi = pool_hi < (h + 1) * HB ? pool_hi : (h + 1) * HB;
+                const float* row = smem + (lo - h * HB) * LD + pool_c;
+#pragma unroll 4
+                for (int r = lo; r < hi; ++r, row += LD) pool_acc += *row;
+            }
+        }
+    }
+    if constexpr (POOL) {
+        if (pool_on) {
+            const float pooled = pool_acc / (float)p.pool_rows;
+            yb[(size_t)pool_out * y_ld + n0 + pool_c] = pooled;
+            vmax = fabsf(pooled);
         }
     }
     if (float* rec = second ? p.y2_amax : p.y_amax) {

@@ -580,7 +580,10 @@ __device__ __forceinline__ void h3_ring_tile(const ConvArgs& p, char* lds) {
 // the head's 3x3 / 512 -> 2048 / 2048 -> 512 GEMMs 195 / 103 / 89 us against 246 / 127 / 104 with the split in the loader).
 // GRES: the residual is gathered from a map by RoI taps in the epilogue (ConvArgs.res_map; x6_epilogue_vec<.., GRES>) -- instantiations
 // of their own, so that the launches without it keep their code (a run-time test in an epilogue has cost 14 % before, conv_bf16.hip).
-template <int TM, int TN, int WM, int WN, bool APLANES = false, int RING = 0, bool GRES = false>
+// POOL: the output averaged over groups of pool_rows rows in the epilogue (ConvArgs.pool_rows; x6_epilogue_vec<.., POOL>): row tile t starts
+// at row t * pool_groups * pool_rows, so that no group straddles two workgroups; the main loop still multiplies BM rows from there (the
+// rows behind the tile's groups are the next tile's or lie past M: computed, then ignored).  An instantiation of its own, as GRES is.
+template <int TM, int TN, int WM, int WN, bool APLANES = false, int RING = 0, bool GRES = false, bool POOL = false>
 __global__ void __launch_bounds__(64 * WM * WN) k_conv_igemm_h3_db(const ConvArgs p) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, NT = 64 * WM * WN;
     constexpr int RPP = APLANES ? NT / 4 : NT / 8, PA = APLANES ? (2 * BM) / RPP : BM / RPP;      // A: rows staged per pass (planes: 4 pieces of 16 B per row per plane)
@@ -590,6 +593,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_conv_igemm_h3_db(const ConvArg
     static_assert(BM % RPP == 0 && PA >= 1, "tile rows must be a multiple of the staging pass");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     static_assert(!(RING && GRES), "the ring has no gathered residual");
+    static_assert(!POOL || (APLANES && !RING && !GRES), "the pooled form: planes in, the two register-staged buffers, residual read or none");
     if constexpr (RING) {                                 // (an instantiation of its own: as a run-time branch beside the other loop the ring keeps a
         static_assert(APLANES, "the ring reads planes");  //  quarter of its gain -- 729 -> 717-723 instead of 748 -> 703-713 us -- to the shared register file)
         h3_ring_tile<TM, TN, WM, WN>(p, lds);
@@ -602,7 +606,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_conv_igemm_h3_db(const ConvArg
     const int nwg = p.tiles_m * p.tiles_n;
     int tile_m, tile_n;
     h3_tile_of(p, xcd_remap(blockIdx.x, nwg), tile_m, tile_n);
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    const int m0 = tile_m * (POOL ? p.pool_rows * p.pool_groups : BM), n0 = tile_n * BN;
     const size_t plane_bytes = (size_t)p.Cout * p.Kpad * 2;
     const char* wbase = reinterpret_cast<const char*>(p.w);
     const size_t x_elems = (size_t)p.n_img * p.H * p.W * p.Cin;
@@ -764,6 +768,10 @@ __global__ void __launch_bounds__(64 * WM * WN) k_conv_igemm_h3_db(const ConvArg
         else x6_epilogue_vec<TM, TN, WM, WN, false, H3_S16, true>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds));
         return;
     }
+    if constexpr (POOL) {                                 // (f32 output only, 16-byte addressable residual rows: the host admits nothing else)
+        x6_epilogue_vec<TM, TN, WM, WN, false, H3_S16, false, true>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds));
+        return;
+    }
     if (p.y_planes) x6_epilogue_vec<TM, TN, WM, WN, true, H3_S16>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds), h3_pow2(eY));
     else if (p.vec_epi) x6_epilogue_vec<TM, TN, WM, WN, false, H3_S16>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds));
     else epilogue<TM, TN, H3_S16>(acc0, p, m0, n0, wm, wn, li, lh);
@@ -782,7 +790,21 @@ static int launch_h3_db(const ConvArgs& a, hipStream_t s, bool ring_ok = true) {
     constexpr size_t lds = (size_t)2 * 2 * (BM + BN) * X6_ROWB;
     static_assert(lds >= X6Tile<TM, TN, WM, WN, 2>::epi, "the epilogue's wave-row must fit in the operand buffers");
     static std::atomic<uint64_t> lds_seen{0}, lds_seen_planes{0};
-    if (p.res_map) {                                      // the residual gathered by RoI taps: sixteen waves of 64x32, never the ring
+    if (p.pool_rows) {                                    // the output averaged over groups of rows: sixteen waves of 64x32 reading planes, never the ring
+        if constexpr (WM * WN == 16 && TN == 1) {
+            if (!p.x_planes || !p.vec_epi || !p.y || p.y_planes || p.res_planes || p.res_map || p.mask || p.n_split || p.layout || p.splits != 1 ||
+                p.pool_rows < 0 || p.pool_groups < 1 || p.pool_rows * p.pool_groups > BM || p.pool_groups * BN > 64 * WM * WN || p.M % p.pool_rows)
+                return fail(FRCNN_E_ARG, "conv2d_fwd_h3_pool: a dense single-layer plane-input launch whose row tile holds whole groups of rows");
+            p.tiles_m = (p.M / p.pool_rows + p.pool_groups - 1) / p.pool_groups;
+            static std::atomic<uint64_t> lds_seen_pool{0};
+            if (int e = raise_lds_once(lds_seen_pool, (const void*)k_conv_igemm_h3_db<TM, TN, WM, WN, true, 0, false, true>, lds, "conv2d_h3")) return e;
+            k_conv_igemm_h3_db<TM, TN, WM, WN, true, 0, false, true><<<p.tiles_m * p.tiles_n, 64 * WM * WN, lds, s>>>(p);
+            return check_launch("conv2d_fwd_h3_pool");
+        } else {
+            return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_pool: the 256x128 tile on sixteen waves only");
+        }
+    }
+    if (p.res_map) {                                   // the residual gathered by RoI taps: sixteen waves of 64x32, never the ring
         if constexpr (WM * WN == 16 && TN == 1) {
             static_assert(lds >= x6_gres_lds<TM, TN, WM, WN>, "the epilogue's wave-row and the tile's tap records must fit in the operand buffers");
             if (!p.vec_epi || p.residual || p.res_planes || p.mask || p.n_split) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_roi_res: a dense single-layer launch with 16-byte addressable rows");

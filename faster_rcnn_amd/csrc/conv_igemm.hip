@@ -28,6 +28,7 @@
 #include "conv_f32_common.h"
 #include "conv_policy.h"
 #include "../../include/ext/frcnn_hip_roi_res.h"
+#include "../../include/ext/frcnn_hip_pool_epilogue.h"
 
 namespace frcnn {
 
@@ -977,6 +978,7 @@ using namespace frcnn;
 
 struct DualOut { int n1; int act1; float* y2; int act2; };      // frcnn_conv2d_fwd_dual: the launch's second layer
 static int roi_res_available(const frcnn_conv_desc* d, int engine, bool x_is_planes);
+static int pool_available(const frcnn_conv_desc* d, int engine, bool x_is_planes, int window);
 static int conv_h3_planes_impl(const frcnn_conv_desc* d, const float* x, const frcnn_h3_planes* x_planes, const float* x_amax, const void* w_planes_f16,
                                const float* scale, const float* shift, const float* residual, const frcnn_h3_planes* residual_planes,
                                const frcnn_roi_res* gathered, const float* residual_amax, float* y, float* y_amax, const frcnn_h3_planes* y_planes,
@@ -1041,6 +1043,13 @@ static int conv_fwd_impl(const frcnn_conv_desc* d, const float* x, const float* 
                 return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_roi_res: not available for this launch (frcnn_conv2d_roi_res_available)");
             if (y && !a.vec_epi) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_roi_res: 16-byte addressable output rows required");
             if ((long long)a.res_map_rows * d->cout * 4 >= 0x7fffffffLL || M * 32 >= 0x7fffffffLL) return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_roi_res: map or tap table over 2 GiB");
+        }
+        if (a.pool_rows) {
+            // the output averaged over groups of rows (include/ext/frcnn_hip_pool_epilogue.h): what frcnn_conv2d_pool_available admits, nothing else
+            if (pool_available(d, engine, a.x_planes != nullptr, a.pool_rows) != 1 || dual || mask || a.res_planes || a.res_map || a.y_planes || workspace || !y)
+                return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_pool: not available for this launch (frcnn_conv2d_pool_available)");
+            if (!a.vec_epi) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_pool: 16-byte addressable output and residual rows required");
+            a.pool_groups = 256 / a.pool_rows < 1024 / 128 ? 256 / a.pool_rows : 1024 / 128;      // whole groups in a 256-row tile, one thread per group and column
         }
         if (planes_io) {
             // activations as fp16 planes (f16x3 only): the double-buffered 256x128 forms only, 16-byte epilogue, one layer, no mask
@@ -1126,7 +1135,49 @@ static int roi_res_available(const frcnn_conv_desc* d, int engine, bool x_is_pla
     return 1;
 }
 
+// frcnn_conv2d_pool_available (the launch asks the same question): 1 / 0
+static int pool_available(const frcnn_conv_desc* d, int engine, bool x_is_planes, int window) {
+    if (engine != FRCNN_ENGINE_H3 || !x_is_planes) return 0;
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->ho <= 0 || d->wo <= 0) return 0;
+    if (d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad_top || d->pad_left || d->ho != d->h || d->wo != d->w || d->layout) return 0;
+    if ((d->cin % BK) != 0 || (d->cout & 3) || d->ldy > 0 || d->ldres > 0) return 0;
+    const SplitRule& r = split_rule(engine);
+    const int cfg = split_config(r, d, 0);
+    if (cfg != 86 && cfg != 85) return 0;                   // 256x128 on sixteen waves; an explicit split-K code (184 / 181) maps to 84 / 81 here
+    if (h3_takes_ring(cfg, frcnn_conv_packed_k(d->kh, d->kw, d->cin))) return 0;
+    const long long M = (long long)d->n * d->ho * d->wo;
+    if (window < 1 || window > 256 || M % window) return 0;
+    if (M * d->cout * 4 >= 0x7fffffffLL || (long long)d->n * d->h * d->w * d->cin * 4 >= 0x7fffffffLL) return 0;
+    return 1;
+}
+
 extern "C" {
+
+int frcnn_pool_epilogue_version(void) { return FRCNN_POOL_EPILOGUE_VERSION; }
+
+int frcnn_conv2d_pool_available(const frcnn_conv_desc* d, int engine, int x_is_planes, int window) {
+    if (!d) return fail(FRCNN_E_ARG, "conv2d_pool_available: null descriptor");
+    if (engine != FRCNN_ENGINE_NATIVE && engine != FRCNN_ENGINE_X6 && engine != FRCNN_ENGINE_H3) return fail(FRCNN_E_ARG, "conv2d_pool_available: unknown engine %d", engine);
+    return pool_available(d, engine, x_is_planes != 0, window);
+}
+
+int frcnn_conv2d_fwd_h3_pool(const frcnn_conv_desc* d, const float* x, const frcnn_h3_planes* x_planes, const float* x_amax,
+                             const void* w_planes_f16, const float* scale, const float* shift, const float* residual,
+                             const frcnn_h3_planes* residual_planes, const float* mask, int window, float* y, float* y_amax,
+                             const frcnn_h3_planes* y_planes, void* stream) {
+    if (!d || !w_planes_f16 || !y) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_pool: null pointer");
+    if (!x_amax) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_pool: the input's magnitude record is required");
+    if (x || residual_planes || mask || y_planes)
+        return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_pool: plane input, an f32 residual or none, no mask and no plane output (frcnn_conv2d_pool_available)");
+    if (pool_available(d, FRCNN_ENGINE_H3, x_planes != nullptr, window) != 1)
+        return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_pool: not available for this launch (frcnn_conv2d_pool_available)");
+    if (!x_planes->planes || !x_planes->exponent || (reinterpret_cast<uintptr_t>(x_planes->planes) & 15))
+        return fail(FRCNN_E_ARG, "conv2d_fwd_h3_pool: incomplete or misaligned input planes");
+    ConvArgs rg = amax_args(x_amax, y_amax);
+    rg.x_planes = x_planes->planes; rg.x_pexp = x_planes->exponent;
+    rg.pool_rows = window;
+    return conv_fwd_impl(d, nullptr, reinterpret_cast<const float*>(w_planes_f16), scale, shift, residual, nullptr, y, nullptr, nullptr, 0, stream, FRCNN_ENGINE_H3, rg);
+}
 
 int frcnn_conv_packed_k(int kh, int kw, int cin) { return packed_k(kh * kw, cin); }
 

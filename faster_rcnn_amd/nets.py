@@ -66,6 +66,15 @@ class ConvUnit:
             return ops.conv2d_bf16(x, self.pc, self.stride, self.padding, act, residual, self.out_f32, self.tile, layout)
         return ops.conv2d(x, self.pc, self.stride, self.padding, act, residual, out, self.tile, layout, planes_out)
 
+    def avgpool(self, x, residual=None, layout=0):
+        """This layer followed by the average over each image's whole window -> (n, cout) f32 (ops.conv2d_avgpool: inside the launch's
+        epilogue where it can, two launches otherwise; f32 path only)."""
+        assert self.dtype == "f32"
+        if self.pc is None:
+            self.lower()
+        h, w = (x.shape[0], x.shape[1]) if layout else (x.shape[1], x.shape[2])
+        return ops.conv2d_avgpool(x, self.pc, self.stride, self.padding, self.act, residual, h * w, self.tile, layout)
+
 
 class DualUnit:
     """Two ConvUnits that read the SAME input with the same kernel size, stride and padding, as ONE launch
@@ -144,6 +153,10 @@ HEAD_BLOCK_PLANES = _os.environ.get("FRCNN_HEAD_BLOCK_PLANES", "0") != "0"
 # branch2c's epilogue (ops.RoiResidual; csrc/conv_f32_common.h x6_epilogue_vec<.., GRES>), where that launch can: bit-identical results.
 # FRCNN_HEAD_ROI_RES=0/1 (dev knob); DESIGN section 7 has the A/B that set the default.
 HEAD_ROI_RES = _os.environ.get("FRCNN_HEAD_ROI_RES", "1") != "0"
+# res5c's output is not written and read back by the 7x7 average pool (482 MB each way per four-image pass) but averaged inside
+# res5c_branch2c's epilogue on row tiles of five whole RoIs (ops.conv2d_avgpool; csrc/conv_f32_common.h x6_epilogue_vec<.., POOL>), where
+# that launch can ([roi][7][7][c] crops, planes in): bit-identical results.  FRCNN_HEAD_POOL_EPI=0/1 (dev knob); DESIGN section 7 has the A/B.
+HEAD_POOL_EPI = _os.environ.get("FRCNN_HEAD_POOL_EPI", "1") != "0"
 VGG_PLANES = _os.environ.get("FRCNN_VGG_PLANES", "1") != "0"        # VggBase: plane tensors between the convolutions of a block (round 6)
 # the same hand-over inside the TRUNK's bottleneck blocks, wherever the consuming launch is one that reads planes (the 256x128 tile
 # forms) -- VERDICT r5 item 3.  Mid-round, with 64x64 tiles under 256 tiles of 128x128: nothing (540.1 / 538.7 against 540.5 / 538.6
@@ -228,12 +241,13 @@ class VggExtents(Extents):
         return out
 
 
-def run_block(u, x, layout=0, planes=False, mask=None, out_planes=False):
+def run_block(u, x, layout=0, planes=False, mask=None, out_planes=False, pool=False):
     """identity_block / conv_block (resnet.py:114-247) and their TimeDistributed twins (:250-392).  ``planes``: branch2a's and
     branch2b's outputs have ONE reader each, the next convolution of the block: on the f16x3 engine they are handed on as the fp16
     planes that convolution multiplies (ops.PlaneTensor), so its loader splits nothing.  ``out_planes`` (round 6): the block's OUTPUT
     as planes only -- its two readers are the next block's branch2a, which stages them unchanged, and that block's closing 1x1, which
-    reads the shortcut back from them (block_takes_planes says whether the next block can); ``x`` may be such a tensor."""
+    reads the shortcut back from them (block_takes_planes says whether the next block can); ``x`` may be such a tensor.
+    ``pool``: the block's output averaged over each image's whole window, (n, cout) f32 (ConvUnit.avgpool: the head's last block)."""
     planes = planes and HEAD_PLANES
     pair = _pair(u["2a"], u["1"]) if "1" in u else None
     if pair is not None:                                    # branch2a and the shortcut conv read x: one launch
@@ -244,6 +258,8 @@ def run_block(u, x, layout=0, planes=False, mask=None, out_planes=False):
     if mask is not None:                                    # a canvas pass: branch2b's 3x3 must read zeros beyond each image's true extent
         t = ops.zero_outside(t, mask)
     t = u["2b"](t, layout=layout, planes_out=planes and _reads_planes(u["2c"], t.shape, layout))
+    if pool:
+        return u["2c"].avgpool(t, residual=shortcut, layout=layout)
     return u["2c"](t, residual=shortcut, layout=layout, planes_out=out_planes)
 
 
@@ -549,11 +565,12 @@ class ResNetHead:
             s = resize(v, rois, self.pool, fill=a["1"].pc.shift, layout=L)
         return c(t, residual=s, layout=L, planes_out=planes and nxt is not None and block_takes_planes(nxt, out_shape, L))
 
-    def _run_rest(self, x, rest, L):
-        """The identity blocks behind the first: each hands its output to the next as planes where that block can take them."""
+    def _run_rest(self, x, rest, L, pool=False):
+        """The identity blocks behind the first: each hands its output to the next as planes where that block can take them.
+        ``pool``: the last block ends in the head's average pool (run_block) -> (n, cout) f32."""
         for i, b in enumerate(rest):
             nxt = rest[i + 1] if i + 1 < len(rest) else None
-            x = run_block(b, x, L, planes=self.dtype == "f32",
+            x = run_block(b, x, L, planes=self.dtype == "f32", pool=pool and nxt is None,
                           out_planes=self.dtype == "f32" and nxt is not None and block_takes_planes(nxt, tuple(x.shape[:-1]) + (_cout(b["2c"]),), L))
         return x
 
@@ -566,6 +583,8 @@ class ResNetHead:
         else:
             x = resize(feat, rois, self.pool, layout=L)     # (n,7,7,1024), or (7,7,n,1024) position-major
             rest = self.blocks
+        if self.dtype == "f32" and L == 0 and HEAD_POOL_EPI and rest:
+            return self.dense(self._run_rest(x, rest, L, pool=True))     # the average pool inside res5c_branch2c's launch where it can
         x = self._run_rest(x, rest, L)
         if self.dtype == "bf16":
             return self.dense(ops.avgpool_bf16(x, 7, L))   # pooled features and the dense layers stay f32
@@ -588,6 +607,9 @@ class ResNetHead:
             # img/s, three alternating runs).  One-image passes tie (507 / 507) and the latency form loses 2 %: they keep position-major.
             L = BATCHED_F32_HEAD_LAYOUT if self.layout else 0
             x = self._first_block_hoisted(feat, rois, functools.partial(ops.roi_crop_resize, n_per_img=n_per_img), layout=L, n_per_img=n_per_img)
+            if L == 0 and HEAD_POOL_EPI and len(self.blocks) > 1:
+                # res5c_branch2c averages its output over each RoI's 49 rows itself where it can (ops.conv2d_avgpool)
+                return self.dense(self._run_rest(x, self.blocks[1:], L, pool=True))
             x = self._run_rest(x, self.blocks[1:], L)
             if L:
                 return self.dense(ops.avgpool_pos_major(x))

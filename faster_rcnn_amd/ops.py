@@ -1034,6 +1034,56 @@ def pool2d(x, k, stride, is_max=True, planes_out=False):
     return amax_carry(out, x)                                    # max / mean of a window never exceeds the largest |input|
 
 
+def conv_takes_pool(x, pc, stride=1, padding="valid", act=None, layout=0, tile=0, window=49):
+    """Would ``conv2d_avgpool(x, pc, ...)`` average inside the convolution's epilogue (frcnn_conv2d_pool_available: a 1x1 / stride-1 launch
+    of the f16x3 engine's 256x128 form on sixteen waves that reads planes, [roi][7][7][c] rows, un-split, not the ring, rows a multiple of
+    ``window``)?  ``x``: the tensor (f32 or PlaneTensor) the launch will read."""
+    if not isinstance(pc, PackedConv) or len(x.shape) != 4:
+        return False
+    d = _conv_desc(tuple(x.shape), pc.kh, pc.kw, pc.cout, stride, padding, ACT[act], layout, tile or AUTO_TILE)
+    eng = _split_engine(d, pc, tile or AUTO_TILE)
+    code = {None: 0, "x6": 1, "h3": 2}[eng]
+    got = _lib.load().frcnn_conv2d_pool_available(ctypes.byref(d), code, 1 if isinstance(x, PlaneTensor) else 0, int(window))
+    if got < 0:
+        _lib.check(got, "frcnn_conv2d_pool_available")
+    return got == 1 and _planes_ok(d, pc, eng) and window == d.h * d.w
+
+
+def conv2d_avgpool(x, pc, stride=1, padding="valid", act=None, residual=None, window=49, tile=0, layout=0):
+    """``conv2d(x, pc, stride, padding, act, residual, tile=tile, layout=layout)`` followed by the average over each image's WHOLE h x w
+    window (``window`` = h * w samples; the detector head: the 7 x 7 samples of a RoI) -> (n, cout) f32.  Where ``conv_takes_pool`` says so
+    the average is taken inside the convolution's epilogue (frcnn_conv2d_fwd_h3_pool: the (n,h,w,cout) tensor is never written);
+    everywhere else the convolution and ``pool2d`` / ``avgpool_pos_major`` run as two launches.  Either way the result is the same, bit
+    for bit."""
+    _require_gpu()
+    if (layout == 0 and (residual is None or (isinstance(residual, torch.Tensor) and residual.dtype == torch.float32 and residual.is_contiguous()))
+            and conv_takes_pool(x, pc, stride, padding, act, layout, tile, window)):
+        d = _conv_desc(tuple(x.shape), pc.kh, pc.kw, pc.cout, stride, padding, ACT[act], layout, tile or AUTO_TILE)
+        if residual is not None:
+            assert tuple(residual.shape) == (d.n, d.ho, d.wo, pc.cout)
+        xp = _lib.H3Planes(planes=x.planes.data_ptr(), exponent=x.exponent.data_ptr(), status=None)
+        y = torch.empty((d.n, pc.cout), dtype=torch.float32, device="cuda")
+        ya, xa = _amax_new(), amax_of(x)                         # ya: max |pooled value|, for an f16x3 reader of y
+        fn = "frcnn_conv2d_fwd_h3_pool"
+        args = (ctypes.byref(d), None, ctypes.byref(xp), _p(xa), _p(pc.h3_planes()), _p(pc.scale), _p(pc.shift), _p(residual), None, None,
+                int(window), _p(y), _p(ya), None)
+        _lib.call(fn, *args, _stream())
+        y._amax = ya
+        # (an instantiation of the plane-reading kernel, listed under that kernel's name with the convolution's FLOP, so that per-kernel
+        # figures cover the same launches as before; the fifth word of the shape keeps it apart from the plain launches of the same GEMM
+        # where launches are grouped by (kernel, shape) and timed once per group)
+        _record_launch(lambda: _h3_planes_in_name(d, pc), _gemm_shape(d, pc, d.stride) + ("pool",), fn, args, (d, x, pc, residual, y, ya, xp, xa), pool=int(window))
+        return y
+    y = conv2d(x, pc, stride, padding, act, residual, None, tile, layout)
+    if layout:
+        assert window == y.shape[0] * y.shape[1]
+        return avgpool_pos_major(y)
+    n, h, w, c = y.shape
+    assert h == w and window == h * w
+    y = pool2d(y, h, h, False)
+    return amax_carry(y.reshape(n, c), y)
+
+
 def pool2d_extents(x, true_hw):
     """MaxPooling2D((2,2), strides=(2,2)) on the f32 tensors of a canvas pass (frcnn_pool2d_fwd_extents): x (n,hc,wc,C) need NOT be masked;
     true_hw = device int32 (n,2), image i's true (rows, cols) at x's level.  Inside floor(rows/2) x floor(cols/2) the result is
