@@ -80,6 +80,7 @@ behind the input, as with ``--track_lookback``; the back-filled rows are printed
 import collections
 import os
 import pathlib
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -750,108 +751,155 @@ def directory_frames(input_dir, image_filenames, jpeg_decoder=None, png_decoder=
         yield path, _load_frame(path, entry.jpeg_decoder(), entry.png_decoder())
 
 
-def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
-                    png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
-                    redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
-                    track_backtrack=None):
-    """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
-    passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
-    annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
-    every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
-    other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack``: as ``annotate_images``."""
-    from concurrent.futures import ThreadPoolExecutor
-    if track_motion is not None and track is None:
-        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
-    motion = {} if track_motion is None else {"track_motion": track_motion}
-    to_video = isinstance(writer_or_out_dir, y4m.Y4mWriter)
-    source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
-    dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
-    eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
-    if to_video:
-        writer = writer_or_out_dir
-        if video_chroma is not None and video_chroma != writer.chroma:
-            raise ValueError("video_chroma=%r, the writer's stream is C%s" % (video_chroma, writer.chroma))
-        kwargs = dict(encode="y4m", y4m=(writer.chroma, writer.range))
-        on_device, jpg = True, False
-
-        def check_size(label, frame):
-            if (frame.width, frame.height) != (writer.w, writer.h):
-                raise ValueError("%s is %dx%d, the output stream's frames are %dx%d: one video stream holds frames of one size"
-                                 % (label, frame.width, frame.height, writer.w, writer.h))
+def _encoder_options(png_encoder, png_compress, frame_format, jpeg_encoder, jpeg_quality, jpeg_subsampling, jpeg_huffman):
+    """The frame-file encoder arguments of ``annotate_images`` checked (``png_options``, ``jpeg_options``, ``jpeg_size_options``) -> (the
+    encoder's keywords of submit_batch -- none with a host encoder: the pass, and its key, without the arguments --, does the pass encode?,
+    .jpg files?, ``write_host(path, rgb)`` of the host encoder, ``encode(bgr device frame)`` -> the file's bytes: the device encoder outside
+    a pass, for the eager path)."""
+    png_encoder, png_compress = png_options(png_encoder, png_compress)
+    frame_format, jpeg_encoder, jpeg_quality = jpeg_options(frame_format, jpeg_encoder, jpeg_quality, png_encoder, png_compress)
+    jpeg_subsampling, jpeg_huffman = jpeg_size_options(frame_format, jpeg_subsampling, jpeg_huffman)
+    jpg = frame_format == "jpg"
+    on_device = (jpeg_encoder if jpg else png_encoder) == "device"
+    if jpg:
+        kwargs = dict(encode="jpeg", quality=jpeg_quality, subsampling=jpeg_subsampling, huffman=jpeg_huffman) if on_device else {}
+        write_host = lambda path, rgb: _write_jpg(path, rgb, jpeg_quality, jpeg_subsampling, jpeg_huffman)
+        encode = lambda dev: ops.jpeg_bytes(dev, quality=jpeg_quality, bgr=True, subsampling=jpeg_subsampling, huffman=jpeg_huffman)
     else:
-        out_dir = writer_or_out_dir
-        png_encoder, png_compress = png_options(png_encoder, png_compress)
-        frame_format, jpeg_encoder, jpeg_quality = jpeg_options(frame_format, jpeg_encoder, jpeg_quality, png_encoder, png_compress)
-        jpeg_subsampling, jpeg_huffman = jpeg_size_options(frame_format, jpeg_subsampling, jpeg_huffman)
-        jpg = frame_format == "jpg"
-        on_device = (jpeg_encoder if jpg else png_encoder) == "device"
-        if jpg:
-            kwargs = dict(encode="jpeg", quality=jpeg_quality, subsampling=jpeg_subsampling, huffman=jpeg_huffman) if on_device else {}
-            write_host = lambda path, rgb: _write_jpg(path, rgb, jpeg_quality, jpeg_subsampling, jpeg_huffman)
-        else:
-            kwargs = dict(encode="png" if png_compress == "runs" else "png-" + png_compress) if on_device else {}
-            write_host = _write_png
-        pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
-        out_name = lambda pos: os.path.join(out_dir, "frame_%06d.%s" % (pos, "jpg" if jpg else "png"))
-        check_size = lambda label, frame: None
-    if redact is not None or not draw:                    # (else the passes, and their keys, are the ones without the arguments)
-        kwargs = dict(kwargs, redact=redact, draw=draw)
-    mapping = training_manager.class_mapping
-    every = _detect_every(detect_every, track, track_motion, track_lookback, eng, None if eng is None else eng.batch)
-    lookback = _lookback_frames(track_lookback, track, eng, None if eng is None else eng.batch)
-    backtrack = _backtrack_frames(track_backtrack, every, track_lookback, eng, None if eng is None else eng.batch)
-    delayed = lookback is not None or backtrack is not None      # the passes return the frames of the pass before them
-    if track is not None:                                 # a new sequence; its frames are submitted in stream order, as every stream's are
-        kwargs = dict(kwargs, track=track, **motion)
-        if lookback is not None:
-            kwargs["track_lookback"] = lookback
-        if every is not None:
-            kwargs["detect_every"] = every
-        if backtrack is not None:
-            kwargs["track_backtrack"] = backtrack
-        reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
+        kwargs = dict(encode="png" if png_compress == "runs" else "png-" + png_compress) if on_device else {}
+        write_host = _write_png
+        encode = lambda dev: ops.png_bytes(dev, bgr=True, compress=png_compress)
+    return kwargs, on_device, jpg, write_host, encode
 
-    if eng is None:                                       # eager path / foreign models: one frame at a time, converted on the device
-        import torch
-        for pos, (label, src) in enumerate(source):
-            check_size(label, src)
-            print("processing {}".format(label))
-            if isinstance(src, _Y4mFrame):
-                frame = ops.y4m_decode_u8(src.data, src.y4m_plan, bgr=True).cpu().numpy()
-            else:
-                frame = np.ascontiguousarray(src.raw)
-            img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
-            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=redact, draw=draw, track=track,
-                                      tracks_out=tracks_out, frame_no=pos + 1, **motion)
-            if to_video:
-                writer.write(ops.y4m_encode_u8(torch.from_numpy(out).cuda(), writer.chroma, writer.range, bgr=True).cpu().numpy().tobytes())
-            elif on_device:
-                dev = torch.from_numpy(out).cuda()
-                _write_bytes(out_name(pos), ops.jpeg_bytes(dev, quality=jpeg_quality, bgr=True, subsampling=jpeg_subsampling, huffman=jpeg_huffman)
-                             if jpg else ops.png_bytes(dev, bgr=True, compress=png_compress))
-            else:
-                write_host(out_name(pos), out[:, :, ::-1])
-        if to_video:
-            writer.flush()
-        return
 
-    B = eng.batch
-    F = B * (every or 1)                                  # frames of a full pass
-    ahead = 2 * eng.in_flight * F
-    read = ThreadPoolExecutor(max_workers=1)              # the stream is sequential: one reader, ``ahead`` frames in front of the passes
-    write = ThreadPoolExecutor(max_workers=1 if to_video else max(1, WRITE_THREADS))
-    pending, writes, window = collections.deque(), [], []
-    waiting, last_key = collections.deque(), [None]      # look-back: the groups whose frames a later pass emits; the geometry of the last pass
+def _tracking_options(eng, track, track_motion, track_lookback, detect_every, track_backtrack):
+    """The tracking arguments of ``annotate_images`` checked against the engine (None: the eager path) -> (their keywords of submit_batch,
+    the K of a ``detect_every`` pass or None, do the passes return the frames of the pass before them?, the look-back of a
+    ``track_backtrack`` pass or None)."""
+    B = None if eng is None else eng.batch
+    every = _detect_every(detect_every, track, track_motion, track_lookback, eng, B)
+    lookback = _lookback_frames(track_lookback, track, eng, B)
+    backtrack = _backtrack_frames(track_backtrack, every, track_lookback, eng, B)
+    kwargs = {} if track is None else {"track": track}
+    for name, value in (("track_motion", track_motion), ("track_lookback", lookback), ("detect_every", every), ("track_backtrack", backtrack)):
+        if value is not None:
+            kwargs[name] = value
+    return kwargs, every, lookback is not None or backtrack is not None, backtrack
 
-    def load():                                           # (reader thread) -> (label, frame, resized, ratio, pixels) or None at the end
+
+class _Sink:
+    """Where the annotated frames go.  ``kwargs``: the encoder's keywords of submit_batch; ``check(label, frame)`` refuses an input frame
+    the sink cannot take; ``emit(pos, out)`` hands frame ``pos`` as its pass returned it to ``write(pos, out)`` on the ``threads`` writer
+    threads -- at most 4 * WRITE_THREADS wait there: encoded frames must not pile up in memory --; ``emit_eager(pos, bgr)`` writes the eager
+    path's frame at once; ``finish()`` waits for every write, then calls ``flush``; ``close()`` ends the threads."""
+
+    def __init__(self, threads, kwargs, write, emit_eager, check=lambda label, frame: None, flush=lambda: None):
+        self.kwargs, self._write, self.emit_eager, self.check, self._flush = kwargs, write, emit_eager, check, flush
+        self._pool, self._writes = ThreadPoolExecutor(max_workers=threads), []
+
+    def emit(self, pos, out):
+        self._writes.append(self._pool.submit(self._write, pos, out))
+        while len(self._writes) > 4 * WRITE_THREADS:
+            self._writes.pop(0).result()
+
+    def finish(self):
+        for f in self._writes:
+            f.result()
+        del self._writes[:]
+        self._flush()
+
+    def close(self):
+        self._pool.shutdown(wait=True)
+
+
+def _y4m_sink(writer, video_chroma=None):
+    """One YUV4MPEG2 stream through a ``y4m.Y4mWriter``: every frame is converted to the writer's chroma mode and range inside its pass
+    and written by ONE thread, so in stream order; every input frame must have the writer's size."""
+    import torch
+    if video_chroma is not None and video_chroma != writer.chroma:
+        raise ValueError("video_chroma=%r, the writer's stream is C%s" % (video_chroma, writer.chroma))
+
+    def check(label, frame):
+        if (frame.width, frame.height) != (writer.w, writer.h):
+            raise ValueError("%s is %dx%d, the output stream's frames are %dx%d: one video stream holds frames of one size"
+                             % (label, frame.width, frame.height, writer.w, writer.h))
+
+    record = lambda bgr: ops.y4m_encode_u8(torch.from_numpy(bgr).cuda(), writer.chroma, writer.range, bgr=True).cpu().numpy().tobytes()
+    return _Sink(1, dict(encode="y4m", y4m=(writer.chroma, writer.range)), lambda pos, out: writer.write(out),
+                 lambda pos, bgr: writer.write(record(bgr)), check, writer.flush)
+
+
+def _file_sink(out_dir, names, *encoders):
+    """Frame files in ``out_dir``, written on WRITE_THREADS threads through the encoders that ``encoders`` (``_encoder_options``'
+    arguments) choose.  ``names``: the input frames' file names -- frame ``pos`` keeps its own, with the extension .jpg for JPEG frames --,
+    or None: ``frame_%06d.png`` / ``.jpg``."""
+    import torch
+    kwargs, on_device, jpg, write_host, encode = _encoder_options(*encoders)
+    pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
+    if names is None:
+        name = lambda pos: "frame_%06d.%s" % (pos, "jpg" if jpg else "png")
+    else:
+        name = lambda pos: os.path.splitext(names[pos])[0] + ".jpg" if jpg else names[pos]
+    if on_device:
+        write = lambda pos, data: _write_bytes(os.path.join(out_dir, name(pos)), data)
+        write_eager = lambda pos, bgr: write(pos, encode(torch.from_numpy(bgr).cuda()))
+    else:
+        write = lambda pos, rgb: write_host(os.path.join(out_dir, name(pos)), rgb)
+        write_eager = lambda pos, bgr: write(pos, bgr[:, :, ::-1])
+    return _Sink(max(1, WRITE_THREADS), kwargs, write, write_eager)
+
+
+def _loaded_stream(source, prepare, ahead):
+    """``prepare(label, frame)`` of every (label, frame) of the iterator ``source``, in order, read by ONE thread (a stream is sequential)
+    that stays ``ahead`` frames in front of the consumer."""
+    read, pending = ThreadPoolExecutor(max_workers=1), collections.deque()
+
+    def load():                                           # (reader thread) -> the prepared frame, or None at the end
         try:
             label, frame = next(source)
         except StopIteration:
             return None
-        check_size(label, frame)
-        resized, ratio = frame.resize_within_bounds(resize_min, resize_max)
-        return label, frame, resized, ratio, eng.host_pixels(resized)
+        return prepare(label, frame)
+
+    try:
+        while True:
+            while len(pending) < ahead:
+                pending.append(read.submit(load))
+            got = pending.popleft().result()
+            if got is None:
+                for f in pending:                         # (reads behind the end: each finds the source exhausted)
+                    f.result()
+                return
+            yield got
+    finally:
+        read.shutdown(wait=True, cancel_futures=True)
+
+
+def _loaded_files(paths, prepare, ahead):
+    """``prepare(path)`` of every frame file of the list ``paths``, in order, decoded on DECODE_THREADS threads that stay ``ahead`` files in
+    front of the consumer."""
+    decode, pending, n = ThreadPoolExecutor(max_workers=max(1, DECODE_THREADS)), {}, len(paths)
+    try:
+        for i in range(n):
+            for j in range(i, min(n, i + ahead)):
+                if j not in pending:
+                    pending[j] = decode.submit(prepare, paths[j])
+            yield pending.pop(i).result()
+    finally:
+        decode.shutdown(wait=True, cancel_futures=True)
+
+
+def _run_passes(eng, loaded, emit, pass_kwargs, every, delayed, backtrack):
+    """The pipelined loop: the frames of ``loaded`` -- an in-order generator of (label, frame, resized, ratio, pixels) that reads ahead --
+    are grouped into runs of at most B * K of one geometry, a group goes through one pass of B (padded) when it fills at least half of it
+    (as get_dets_by_cls) and through one-frame passes else, ``eng.in_flight`` passes are in flight, and ``emit(pos, label, frame, result)``
+    gets every frame's result in order.  ``pass_kwargs``: what every submit_batch takes behind ``batch``; ``every`` / ``delayed`` /
+    ``backtrack``: ``_tracking_options``' -- a delayed pass is always a full one, returns the group before its own, and a flush submit
+    follows a change of geometry and the last group."""
+    B = eng.batch
+    F = B * (every or 1)                                  # frames of a full pass
+    window = []
+    waiting, last_key = collections.deque(), [None]      # delayed passes: the groups whose frames a later pass emits; the geometry of the last pass
 
     def finish():
         part, ticket = window[0]
@@ -861,22 +909,12 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
             window.pop(0)
         if delayed:                                       # (the pass returned the group before its own, or nothing)
             part = waiting.popleft() if results else ()
-        for (pos, label, frame), (num_rois, dets, out) in zip(part, results):
-            print("processing {}".format(label))
-            print("num rois: {}".format(num_rois))
-            if track is not None:
-                _write_tracks(tracks_out, pos + 1, dets, mapping)
-            _print_drawn(dets, frame.width, frame.height)
-            if to_video:
-                writes.append(write.submit(writer.write, out))            # (one writer thread: stream order)
-            else:
-                writes.append(write.submit(_write_bytes if on_device else write_host, out_name(pos), out))
-        while len(writes) > 4 * WRITE_THREADS:            # (bounded: encoded frames must not pile up in memory)
-            writes.pop(0).result()
+        for (pos, label, frame), result in zip(part, results):
+            emit(pos, label, frame, result)
 
     def flush():                                          # the frames the look-back window still holds
         if last_key[0] is not None:
-            window.append(((), eng.submit_batch([], [], DET_THRESHOLD, [], batch=B, annotate=True, **kwargs)))
+            window.append(((), eng.submit_batch([], [], DET_THRESHOLD, [], batch=B, **pass_kwargs)))
             last_key[0] = None
             if len(window) >= eng.in_flight:
                 finish()
@@ -892,8 +930,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
             parts = _every_parts(group, B, every)
         for part, take in parts:
             keys = part[::every or 1]
-            ticket = eng.submit_batch([g[3] for g in keys], [g[4] for g in keys], DET_THRESHOLD, [g[5] for g in part],
-                                      batch=take, annotate=True, **kwargs)
+            ticket = eng.submit_batch([g[3] for g in keys], [g[4] for g in keys], DET_THRESHOLD, [g[5] for g in part], batch=take, **pass_kwargs)
             window.append(([(g[0], g[1], g[2]) for g in part], ticket))
             if delayed:
                 waiting.append(window[-1][0])
@@ -901,41 +938,103 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                 finish()
 
     try:
-        group, key, pos, done = [], None, 0, False
-        while True:
-            while not done and len(pending) < ahead:
-                pending.append(read.submit(load))
-            if not pending:
-                break
-            got = pending.popleft().result()
-            if got is None:
-                done = True
-                for f in pending:                         # (reads behind the end: each finds the source exhausted)
-                    f.result()
-                pending.clear()
-                continue
-            label, frame, resized, ratio, pixels = got
+        group, key = [], None
+        for pos, (label, frame, resized, ratio, pixels) in enumerate(loaded):
             k = eng.geometry_of(pixels)
             if group and (k != key or len(group) == F):
                 submit(group)
                 group = []
             group.append((pos, label, frame, resized, ratio, pixels))
-            key, pos = k, pos + 1
+            key = k
         if group:
             submit(group)
         flush()
         while window:
             finish()
-        for f in writes:
-            f.result()
-        if to_video:
-            writer.flush()
     finally:
-        read.shutdown(wait=True, cancel_futures=True)
+        loaded.close()                                    # (ends the read-ahead threads)
         for _, ticket in window:                          # an exception mid-stream: no slot stays marked busy
             ticket.slot.event.synchronize()
             ticket.slot.busy = False
-        write.shutdown(wait=True)
+
+
+def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max, **kwargs):
+    """The eager path (foreign models): the reference's loop, one (label, frame) of ``frames`` at a time through ``get_annotated_frame``
+    (``kwargs``: its arguments behind the sizes); a stream's frame is converted on the device."""
+    for pos, (label, src) in enumerate(frames):
+        sink.check(label, src)
+        print("processing {}".format(label))
+        if isinstance(src, _Y4mFrame):
+            frame = ops.y4m_decode_u8(src.data, src.y4m_plan, bgr=True).cpu().numpy()
+        else:
+            frame = np.ascontiguousarray(src.raw)
+        img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
+        sink.emit_eager(pos, get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, frame_no=pos + 1, **kwargs))
+
+
+def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
+              tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None):
+    """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
+    ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
+    ``make_sink()``: the ``_Sink``."""
+    if track_motion is not None and track is None:
+        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
+    motion = {} if track_motion is None else {"track_motion": track_motion}
+    sink = make_sink()
+    try:
+        dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
+        eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
+        tracking, every, delayed, backtrack = _tracking_options(eng, track, track_motion, track_lookback, detect_every, track_backtrack)
+        if track is not None:                             # a new sequence; its frames are submitted in input order, as every list's are
+            reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
+        if eng is None:
+            _run_eager(training_manager, detector, frames, sink, resize_min, resize_max, redact=redact, draw=draw, track=track,
+                       tracks_out=tracks_out, **motion)
+        else:
+            kwargs = dict(sink.kwargs, annotate=True, **tracking)
+            if redact is not None or not draw:            # (else the passes, and their keys, are the ones without the arguments)
+                kwargs.update(redact=redact, draw=draw)
+            mapping = training_manager.class_mapping
+
+            def prepare(label, frame):                    # (read-ahead thread) -> (label, frame, resized, ratio, pixels)
+                sink.check(label, frame)
+                resized, ratio = frame.resize_within_bounds(resize_min, resize_max)
+                return label, frame, resized, ratio, eng.host_pixels(resized)
+
+            def emit(pos, label, frame, result):
+                num_rois, dets, out = result
+                print("processing {}".format(label))
+                print("num rois: {}".format(num_rois))
+                if track is not None:
+                    _write_tracks(tracks_out, pos + 1, dets, mapping)
+                _print_drawn(dets, frame.width, frame.height)
+                sink.emit(pos, out)
+
+            _run_passes(eng, loaded_from(prepare, 2 * eng.in_flight * eng.batch * (every or 1)), emit, kwargs, every, delayed, backtrack)
+        sink.finish()
+    finally:
+        sink.close()
+
+
+def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
+                    png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
+                    redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
+                    track_backtrack=None):
+    """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
+    passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
+    annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
+    every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
+    other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack``: as ``annotate_images``."""
+    source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
+    if isinstance(writer_or_out_dir, y4m.Y4mWriter):
+        make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma)
+    else:
+        make_sink = lambda: _file_sink(writer_or_out_dir, None, png_encoder, png_compress, frame_format, jpeg_encoder, jpeg_quality, jpeg_subsampling,
+                                      jpeg_huffman)
+    _annotate(training_manager, detector, source, lambda prepare, ahead: _loaded_stream(source, prepare, ahead), make_sink, resize_min, resize_max,
+              redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
+              detect_every=detect_every, track_backtrack=track_backtrack)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
@@ -980,154 +1079,18 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     a new one over that many frames, and the boxes found are hidden there too, so a frame between two detections is covered from both
     sides.  Every group of at most B * K frames then goes through one full (padded) pass, a pass returns the frames of the pass before it
     and a flush follows a change of geometry and the end of the list, as with ``track_lookback``.  The eager path refuses it."""
-    if track_motion is not None and track is None:
-        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
-    motion = {} if track_motion is None else {"track_motion": track_motion}
-    from concurrent.futures import ThreadPoolExecutor
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
         entry.set_png_decoder(png_decoder)
-    device_decode = entry.jpeg_decoder()                      # "host", "device" or "device_full"
-    device_png = entry.png_decoder()                          # "host", "device" or "device_full"
-    png_encoder, png_compress = png_options(png_encoder, png_compress)
-    frame_format, jpeg_encoder, jpeg_quality = jpeg_options(frame_format, jpeg_encoder, jpeg_quality, png_encoder, png_compress)
-    jpeg_subsampling, jpeg_huffman = jpeg_size_options(frame_format, jpeg_subsampling, jpeg_huffman)
-    jpg = frame_format == "jpg"
-    on_device = (jpeg_encoder if jpg else png_encoder) == "device"
-    if jpg:
-        encode, quality = ("jpeg", jpeg_quality) if on_device else (None, None)
-        jpeg_mode = dict(subsampling=jpeg_subsampling, huffman=jpeg_huffman) if on_device else {}
-        out_names = [os.path.splitext(f)[0] + ".jpg" for f in image_filenames]
-        write_host = lambda path, rgb: _write_jpg(path, rgb, jpeg_quality, jpeg_subsampling, jpeg_huffman)
-    else:
-        encode, quality = ("png" if png_compress == "runs" else "png-" + png_compress) if on_device else None, None
-        jpeg_mode = {}
-        out_names = list(image_filenames)
-        write_host = _write_png
+    device_decode, device_png = entry.jpeg_decoder(), entry.png_decoder()      # "host", "device" or "device_full" each
     paths = [os.path.join(input_dir, f) for f in image_filenames]
-    dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
-    eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
-    pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
-    mapping = training_manager.class_mapping
-    every = _detect_every(detect_every, track, track_motion, track_lookback, eng, None if eng is None else eng.batch)
-    lookback = _lookback_frames(track_lookback, track, eng, None if eng is None else eng.batch)
-    backtrack = _backtrack_frames(track_backtrack, every, track_lookback, eng, None if eng is None else eng.batch)
-    delayed = lookback is not None or backtrack is not None      # the passes return the frames of the pass before them
-    if track is not None:
-        reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
-    if eng is None:                                       # eager path / foreign models: the reference's loop
-        for frame_no, (name, path) in enumerate(zip(out_names, paths), 1):
-            print("processing {}".format(path))
-            frame = np.ascontiguousarray(_read_rgb(path)[:, :, ::-1])
-            img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
-            out = get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=redact, draw=draw, track=track,
-                                      tracks_out=tracks_out, frame_no=frame_no, **motion)
-            if on_device:
-                import torch
-                dev = torch.from_numpy(out).cuda()
-                _write_bytes(os.path.join(out_dir, name), ops.jpeg_bytes(dev, quality=jpeg_quality, bgr=True, subsampling=jpeg_subsampling,
-                                                                                huffman=jpeg_huffman) if jpg else
-                             ops.png_bytes(dev, bgr=True, compress=png_compress))
-            else:
-                write_host(os.path.join(out_dir, name), out[:, :, ::-1])
-        return
-
-    def load(path):                                       # (decode thread) -> (frame, resized, ratio, pixels)
-        frame = _load_frame(path, device_decode, device_png)
-        resized, ratio = frame.resize_within_bounds(resize_min, resize_max)
-        return frame, resized, ratio, eng.host_pixels(resized)
-
-    n, B = len(paths), eng.batch
-    edit = dict(redact=redact, draw=draw) if redact is not None or not draw else {}      # (else the passes without the arguments)
-    if track is not None:                                 # (the groups below are submitted in list order, as tracking needs them)
-        edit = dict(edit, track=track, **motion)
-    if lookback is not None:
-        edit["track_lookback"] = lookback
-    if every is not None:
-        edit["detect_every"] = every
-    if backtrack is not None:
-        edit["track_backtrack"] = backtrack
-    F = B * (every or 1)                                  # frames of a full pass
-    decode = ThreadPoolExecutor(max_workers=max(1, DECODE_THREADS))
-    write = ThreadPoolExecutor(max_workers=max(1, WRITE_THREADS))
-    ahead = 2 * eng.in_flight * F
-    pending, writes, window = {}, [], []
-    waiting, last_key = collections.deque(), [None]      # look-back: the groups whose frames a later pass emits; the geometry of the last pass
-
-    def finish():
-        part, ticket = window[0]
-        try:
-            results = eng.collect_batch(ticket)
-        finally:
-            window.pop(0)
-        if delayed:                                       # (the pass returned the group before its own, or nothing)
-            part = waiting.popleft() if results else ()
-        for (pos, frame), (num_rois, dets, out) in zip(part, results):
-            print("processing {}".format(paths[pos]))
-            print("num rois: {}".format(num_rois))
-            if track is not None:
-                _write_tracks(tracks_out, pos + 1, dets, mapping)
-            _print_drawn(dets, frame.width, frame.height)
-            writes.append(write.submit(_write_bytes if on_device else write_host, os.path.join(out_dir, out_names[pos]), out))
-        while len(writes) > 4 * WRITE_THREADS:            # (bounded: encoded frames must not pile up in memory)
-            writes.pop(0).result()
-
-    def submit(group):
-        """<= B frames of one geometry: one pass of B (padded) when they fill at least half of it (as get_dets_by_cls), else
-        one-frame passes."""
-        parts = [(group, B)] if B > 1 and len(group) >= max(2, B // 2) else [([g], 1) for g in group]
-        if delayed:                                       # full passes only: a window belongs to one size of pass; a new geometry: a new window
-            parts = [(group, B)]
-            if last_key[0] not in (None, eng.geometry_of(group[0][4])):
-                flush()
-            last_key[0] = eng.geometry_of(group[0][4])
-        if every is not None and backtrack is None:       # the key frames 0, K, ... of a pass go to the network, every frame goes up
-            parts = _every_parts(group, B, every)
-        for part, take in parts:
-            keys = part[::every or 1]
-            ticket = eng.submit_batch([g[2] for g in keys], [g[3] for g in keys], DET_THRESHOLD, [g[4] for g in part],
-                                      batch=take, annotate=True, encode=encode, quality=quality, **jpeg_mode, **edit)
-            window.append(([(g[0], g[1]) for g in part], ticket))
-            if delayed:
-                waiting.append(window[-1][0])
-            if len(window) >= eng.in_flight:
-                finish()
-
-    def flush():                                          # the frames the look-back window still holds
-        if last_key[0] is not None:
-            window.append(((), eng.submit_batch([], [], DET_THRESHOLD, [], batch=B, annotate=True, encode=encode, quality=quality, **jpeg_mode,
-                                                **edit)))
-            last_key[0] = None
-            if len(window) >= eng.in_flight:
-                finish()
-
-    try:
-        group, key = [], None
-        for i in range(n):
-            for j in range(i, min(n, i + ahead)):
-                if j not in pending:
-                    pending[j] = decode.submit(load, paths[j])
-            frame, resized, ratio, pixels = pending.pop(i).result()
-            k = eng.geometry_of(pixels)
-            if group and (k != key or len(group) == F):
-                submit(group)
-                group = []
-            group.append((i, frame, resized, ratio, pixels))
-            key = k
-        if group:
-            submit(group)
-        flush()
-        while window:
-            finish()
-        for f in writes:
-            f.result()
-    finally:
-        decode.shutdown(wait=True, cancel_futures=True)
-        for _, ticket in window:                          # an exception mid-list: no slot stays marked busy
-            ticket.slot.event.synchronize()
-            ticket.slot.busy = False
-        write.shutdown(wait=True)
+    make_sink = lambda: _file_sink(out_dir, image_filenames, png_encoder, png_compress, frame_format, jpeg_encoder, jpeg_quality, jpeg_subsampling,
+                                  jpeg_huffman)
+    _annotate(training_manager, detector, ((path, _Frame(_read_rgb(path))) for path in paths),
+              lambda prepare, ahead: _loaded_files(paths, lambda path: prepare(path, _load_frame(path, device_decode, device_png)), ahead),
+              make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
+              track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack)
 
 
 def build_parser():

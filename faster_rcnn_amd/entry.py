@@ -29,6 +29,7 @@ models, the same call runs here as ONE captured pass per image:
 """
 import collections
 import ctypes
+import dataclasses
 import os
 import time
 
@@ -293,6 +294,130 @@ def _capture_stream():
     return _CAPTURE_STREAM
 
 
+@dataclasses.dataclass(frozen=True)
+class PassSpec:
+    """The options of one captured pass, checked and normalised: what ``submit_batch``'s keywords say (``checked``), what the cache key
+    says of them (``key_tail``) and what ``_capture_slot`` builds the pass from.  The default is the plain detection pass, and every
+    canvas pass.  A new option is a field here, its check in ``checked`` and its tag in ``key_tail``."""
+    annotate: bool = False
+    encode: object = None
+    quality: object = None
+    jpeg_mode: tuple = JPEG_MODE
+    y4m_mode: tuple = Y4M_MODE
+    redact: object = None
+    draw: bool = True
+    track: object = None
+    track_motion: object = None
+    track_lookback: object = None
+    detect_every: object = None
+    track_backtrack: object = None
+
+    @classmethod
+    def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
+                track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None):
+        """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
+        ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
+        them, behind ``submit_batch``'s flush, which reads neither."""
+        if (redact is not None or not draw) and not annotate:
+            raise FrcnnError("submit_batch: redact= and draw=False change the frame an ANNOTATING pass returns: pass annotate=True")
+        if track is not None:
+            if not annotate:
+                raise FrcnnError("submit_batch: track= tracks the detections of an ANNOTATING pass: pass annotate=True")
+            track = engine.track_option(track)
+        if track_motion is not None:
+            if track is None:
+                raise FrcnnError("submit_batch: track_motion= moves the boxes of the tracker: pass track=(thr, hold, grow) too")
+            track_motion = engine.track_motion_option(track_motion)
+        if track_lookback is not None and track is None:
+            raise FrcnnError("submit_batch: track_lookback= hides the tracker's new tracks in earlier frames: pass track=(thr, hold, grow) too")
+        if track_backtrack is not None:
+            if track_lookback is not None:
+                raise FrcnnError("submit_batch: track_backtrack= together with track_lookback= is not supported: the back-track rule hides a new "
+                                 "track in the earlier frames itself, and a pass has one window")
+            if detect_every is None:
+                raise FrcnnError("submit_batch: track_backtrack= follows the tracks of a detected frame back over the frames between two "
+                                 "detections: pass detect_every=K (with track= and track_motion=) too")
+        if detect_every is not None:
+            if track_motion is None:
+                raise FrcnnError("submit_batch: detect_every= follows the tracks by block matching between two detected frames: pass "
+                                 "track=(thr, hold, grow) and track_motion=R too")
+            if track_lookback is not None:
+                raise FrcnnError("submit_batch: detect_every= together with track_lookback= is not supported: the look-back window keeps one "
+                                 "tracked buffer per detected frame")
+            if not engine.device_preprocess:
+                raise FrcnnError("submit_batch: detect_every= needs the device-side preprocess: a foreign preprocess_func uploads float "
+                                 "pixels of the key frames only, and the block match reads the uint8 pixels of every source frame")
+            detect_every = engine.detect_every_option(detect_every, engine.batch if batch is None else batch)
+        if redact is not None:
+            redact = engine.redact_option(redact)
+        jpeg_mode, y4m_mode = JPEG_MODE, Y4M_MODE
+        if encode == Y4M_ENCODE:
+            y4m_mode = Y4M_MODE if y4m is None else tuple(y4m)
+            if len(y4m_mode) != 2 or y4m_mode[0] not in _lib.Y4M_OUT_CHROMAS or y4m_mode[1] not in _lib.Y4M_RANGES:
+                raise FrcnnError("submit_batch: y4m=%r: (chroma, range) with chroma one of %s and range one of %s"
+                                 % (y4m, ", ".join(_lib.Y4M_OUT_CHROMAS), ", ".join(_lib.Y4M_RANGES)))
+            if quality is not None or subsampling is not None or huffman is not None:
+                raise FrcnnError("submit_batch: quality / subsampling / huffman go with encode=\"%s\" only" % JPEG_ENCODE)
+        elif y4m is not None:
+            raise FrcnnError("submit_batch: y4m=%r goes with encode=\"%s\" only" % (y4m, Y4M_ENCODE))
+        if encode == Y4M_ENCODE:
+            pass
+        elif encode == JPEG_ENCODE:
+            if not annotate:
+                raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
+            if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+                raise FrcnnError("submit_batch: encode=\"%s\" takes quality= an integer in 1..100, got %r" % (encode, quality))
+            quality = int(quality)
+            jpeg_mode = (JPEG_MODE[0] if subsampling is None else subsampling, JPEG_MODE[1] if huffman is None else huffman)
+            if isinstance(jpeg_mode[0], bool) or jpeg_mode[0] not in _lib.JPEG_OPT_SUBSAMPLINGS or not isinstance(jpeg_mode[1], str) \
+                    or jpeg_mode[1] not in _lib.JPEG_OPT_HUFFMANS:
+                raise FrcnnError("submit_batch: subsampling=%r (444, 420), huffman=%r (\"standard\", \"optimized\")" % (subsampling, huffman))
+        elif subsampling is not None or huffman is not None:
+            raise FrcnnError("submit_batch: subsampling=%r / huffman=%r go with encode=\"%s\" only" % (subsampling, huffman, JPEG_ENCODE))
+        elif quality is not None:
+            raise FrcnnError("submit_batch: quality=%r goes with encode=\"%s\" only" % (quality, JPEG_ENCODE))
+        elif encode is not None and encode not in PNG_ENCODES:
+            raise FrcnnError("submit_batch: encode=%r (None, %s)" % (encode, ", ".join('"%s"' % e for e in PNG_ENCODES)))
+        if encode and not annotate:
+            raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
+        return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
+                   track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack)
+
+    @property
+    def delayed(self):
+        """Does the pass return the frames of the pass before it (a look-back or back-track pass)?"""
+        return self.track_lookback is not None or self.track_backtrack is not None
+
+    def sized(self, engine, B):
+        """The look-back of a delayed pass checked against the B images of the pass -> the spec with it normalised."""
+        if self.track_lookback is not None:
+            return dataclasses.replace(self, track_lookback=engine.track_lookback_option(self.track_lookback, B))
+        if self.track_backtrack is not None:
+            K = self.detect_every
+            return dataclasses.replace(self, track_backtrack=engine.track_backtrack_option(self.track_backtrack, K, B * K))
+        return self
+
+    def key_tail(self, B):
+        """What an ANNOTATING pass of B images appends to its geometry in the cache key: (444, "standard") is the pass without the pair,
+        and every option that is not stated leaves the key what it was."""
+        key = ((B,) if B > 1 else ()) + (("annotate", self.encode) if self.encode else ("annotate",)) + ((self.quality,) if self.quality else ())
+        if self.encode == JPEG_ENCODE and self.jpeg_mode != JPEG_MODE:
+            key = key + self.jpeg_mode
+        if self.encode == Y4M_ENCODE:
+            key = key + self.y4m_mode
+        if self.redact is not None:
+            key = key + ("redact",) + self.redact
+        if not self.draw:
+            key = key + ("nodraw",)
+        if self.track is not None:
+            key = key + ("track",) + self.track
+        for tag, value in (("motion", self.track_motion), ("lookback", self.track_lookback), ("every", self.detect_every),
+                           ("backtrack", self.track_backtrack)):
+            if value is not None:
+                key = key + (tag, value)
+        return key
+
+
 class _Slot:
     """One captured pass for one image size (or canvas class), with its staging on both sides of PCIe.  Every field exists on every slot;
     what a kind of pass does not use stays None (``tabs`` / ``frame_io``: exact passes; ``extents`` / ``_ext_raw``: canvas passes; ``png_*``:
@@ -304,7 +429,7 @@ class _Slot:
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
                  "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
-                 "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack")
+                 "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec")
 
     def __init__(self):
         for name in self.__slots__:
@@ -810,12 +935,11 @@ class DetectionEntry:
         s.extents.upload()
         return lambda: s.pipe.forward_dev(s.x_f32, dyn=dyn, extents=s.extents)
 
-    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, annotate=False, encode=None, quality=None, jpeg_mode=JPEG_MODE,
-                      y4m_mode=Y4M_MODE, redact=None, draw=True, track=None, track_motion=None, track_lookback=None, detect_every=None,
-                      track_backtrack=None):
+    def _capture_slot(self, B, canvas, H, W, src=None, flip=False, spec=PassSpec()):
         """One captured pass over B frames, each with its own [resize_ratio, det_threshold] pair (B > 1:
         pipeline.BatchedInferencePipeline): of the exact geometry (H, W, src, flip) (_exact_pass), or with ``canvas`` of the canvas class
-        (H, W) (_canvas_pass).  ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
+        (H, W) (_canvas_pass).  ``spec`` (``PassSpec``) says what the pass does and fills the slot's fields of the same names.
+        ``encode``: "png" / "png-huffman" for an annotating pass that ends in the device PNG encoder, "jpeg" for one that
         ends in the device JPEG encoder at ``quality`` in ``jpeg_mode`` = (subsampling, huffman), "y4m" for one that ends in the YUV4MPEG2
         encoder in ``y4m_mode`` = (chroma, range).  ``redact`` = (classes, mode, size, margin) (``redact_option``): an annotating pass that
         hides those classes' boxes in each frame (ops.redact_u8) in front of the drawing step; ``draw`` False: one that draws nothing.
@@ -840,11 +964,11 @@ class DetectionEntry:
             fine = stamp if canvas else (lambda name: None)         # (a canvas capture's "buffers" are booked piece by piece)
             stamp("pipeline")
             s = _Slot()
-            s.key, s.pipe, s.batch, s.canvas, s.annotate = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, annotate
-            s.encode, s.quality, s.jpeg_mode, s.y4m_mode = encode, quality, jpeg_mode, y4m_mode
-            s.redact, s.nodraw, s.track, s.track_motion = redact, (None if draw else True), track, track_motion
-            s.track_lookback, s.track_backtrack = track_lookback or track_backtrack, track_backtrack      # (both: the delayed path is one)
-            s.every, s.frames = detect_every, B * (detect_every or 1)
+            s.key, s.pipe, s.batch, s.canvas, s.spec = (("canvas", H, W) if canvas else (H, W)), pipe, B, canvas, spec
+            s.annotate, s.encode, s.quality, s.jpeg_mode, s.y4m_mode = spec.annotate, spec.encode, spec.quality, spec.jpeg_mode, spec.y4m_mode
+            s.redact, s.nodraw, s.track, s.track_motion = spec.redact, (None if spec.draw else True), spec.track, spec.track_motion
+            s.track_lookback, s.track_backtrack = spec.track_lookback or spec.track_backtrack, spec.track_backtrack      # (both: the delayed path is one)
+            s.every, s.frames = spec.detect_every, B * (spec.detect_every or 1)
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -1136,77 +1260,18 @@ class DetectionEntry:
         ``track_lookback`` pass is -- ``collect_batch`` of submit k returns the results of submit k - 1, one per SOURCE frame, a submit
         with no images is the flush, one sequence at a time --; its between frames keep "propagated": True on their live dets, and the
         back-filled rows are dets with "backfilled" = k.  Not together with ``track_lookback``."""
-        if (redact is not None or not draw) and not annotate:
-            raise FrcnnError("submit_batch: redact= and draw=False change the frame an ANNOTATING pass returns: pass annotate=True")
-        if track is not None:
-            if not annotate:
-                raise FrcnnError("submit_batch: track= tracks the detections of an ANNOTATING pass: pass annotate=True")
-            track = self.track_option(track)
-        if track_motion is not None:
-            if track is None:
-                raise FrcnnError("submit_batch: track_motion= moves the boxes of the tracker: pass track=(thr, hold, grow) too")
-            track_motion = self.track_motion_option(track_motion)
-        if track_lookback is not None and track is None:
-            raise FrcnnError("submit_batch: track_lookback= hides the tracker's new tracks in earlier frames: pass track=(thr, hold, grow) too")
-        if track_backtrack is not None:
-            if track_lookback is not None:
-                raise FrcnnError("submit_batch: track_backtrack= together with track_lookback= is not supported: the back-track rule hides a new "
-                                 "track in the earlier frames itself, and a pass has one window")
-            if detect_every is None:
-                raise FrcnnError("submit_batch: track_backtrack= follows the tracks of a detected frame back over the frames between two "
-                                 "detections: pass detect_every=K (with track= and track_motion=) too")
-        if detect_every is not None:
-            if track_motion is None:
-                raise FrcnnError("submit_batch: detect_every= follows the tracks by block matching between two detected frames: pass "
-                                 "track=(thr, hold, grow) and track_motion=R too")
-            if track_lookback is not None:
-                raise FrcnnError("submit_batch: detect_every= together with track_lookback= is not supported: the look-back window keeps one "
-                                 "tracked buffer per detected frame")
-            if not self.device_preprocess:
-                raise FrcnnError("submit_batch: detect_every= needs the device-side preprocess: a foreign preprocess_func uploads float "
-                                 "pixels of the key frames only, and the block match reads the uint8 pixels of every source frame")
-            detect_every = self.detect_every_option(detect_every, self.batch if batch is None else batch)
-        if redact is not None:
-            redact = self.redact_option(redact)
-        y4m_mode = Y4M_MODE
-        if encode == Y4M_ENCODE:
-            y4m_mode = Y4M_MODE if y4m is None else tuple(y4m)
-            if len(y4m_mode) != 2 or y4m_mode[0] not in _lib.Y4M_OUT_CHROMAS or y4m_mode[1] not in _lib.Y4M_RANGES:
-                raise FrcnnError("submit_batch: y4m=%r: (chroma, range) with chroma one of %s and range one of %s"
-                                 % (y4m, ", ".join(_lib.Y4M_OUT_CHROMAS), ", ".join(_lib.Y4M_RANGES)))
-            if quality is not None or subsampling is not None or huffman is not None:
-                raise FrcnnError("submit_batch: quality / subsampling / huffman go with encode=\"%s\" only" % JPEG_ENCODE)
-        elif y4m is not None:
-            raise FrcnnError("submit_batch: y4m=%r goes with encode=\"%s\" only" % (y4m, Y4M_ENCODE))
-        if encode == Y4M_ENCODE:
-            pass
-        elif encode == JPEG_ENCODE:
-            if not annotate:
-                raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
-            if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
-                raise FrcnnError("submit_batch: encode=\"%s\" takes quality= an integer in 1..100, got %r" % (encode, quality))
-            quality = int(quality)
-            jpeg_mode = (JPEG_MODE[0] if subsampling is None else subsampling, JPEG_MODE[1] if huffman is None else huffman)
-            if isinstance(jpeg_mode[0], bool) or jpeg_mode[0] not in _lib.JPEG_OPT_SUBSAMPLINGS or not isinstance(jpeg_mode[1], str) \
-                    or jpeg_mode[1] not in _lib.JPEG_OPT_HUFFMANS:
-                raise FrcnnError("submit_batch: subsampling=%r (444, 420), huffman=%r (\"standard\", \"optimized\")" % (subsampling, huffman))
-        elif subsampling is not None or huffman is not None:
-            raise FrcnnError("submit_batch: subsampling=%r / huffman=%r go with encode=\"%s\" only" % (subsampling, huffman, JPEG_ENCODE))
-        elif quality is not None:
-            raise FrcnnError("submit_batch: quality=%r goes with encode=\"%s\" only" % (quality, JPEG_ENCODE))
-        elif encode is not None and encode not in PNG_ENCODES:
-            raise FrcnnError("submit_batch: encode=%r (None, %s)" % (encode, ", ".join('"%s"' % e for e in PNG_ENCODES)))
-        if encode and not annotate:
-            raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
+        spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
+                                redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
+                                detect_every=detect_every, track_backtrack=track_backtrack)
         self._check_epoch()
         B = self.batch if batch is None else batch
-        flush = (track_lookback is not None or track_backtrack is not None) and len(images) == 0
-        if flush:
+        if spec.delayed and len(images) == 0:                       # the flush
             if self._lookback_last is None:
                 raise FrcnnError("submit_batch: a flush (no images) follows a look-back submit; none is waiting")
             s = self.cache.acquire(*self._lookback_last)
             return self._replay(s, [], [], [], det_threshold)
-        if detect_every is not None:
+        if spec.detect_every is not None:
+            detect_every = spec.detect_every
             if not 1 <= len(pixels) <= B * detect_every or len(images) != -(-len(pixels) // detect_every) or len(images) != len(resize_ratios):
                 raise FrcnnError("submit_batch: detect_every=%d with batch=%d takes 1..%d source frames in pixels and their key frames 0, %d, ... "
                                  "in images / resize_ratios: got %d frames, %d images, %d ratios"
@@ -1214,34 +1279,13 @@ class DetectionEntry:
         else:
             assert 1 <= len(images) <= B and len(images) == len(pixels) == len(resize_ratios)
         _, H, W, src, flip = pixels[0]
-        if track_lookback is not None:
-            track_lookback = self.track_lookback_option(track_lookback, B)
-        if track_backtrack is not None:
-            track_backtrack = self.track_backtrack_option(track_backtrack, detect_every, B * detect_every)
+        spec = spec.sized(self, B)
         if annotate:
             if not self.device_preprocess:
                 raise FrcnnError("annotating passes need the device-side preprocess (a foreign preprocess_func uploads float pixels)")
             key = self.geometry_of(pixels[0])
             assert all(self.geometry_of(p) == key for p in pixels), "one pass, one geometry"
-            key = key + ((B,) if B > 1 else ()) + (("annotate", encode) if encode else ("annotate",)) + ((quality,) if quality else ())
-            if encode == JPEG_ENCODE and jpeg_mode != JPEG_MODE:
-                key = key + jpeg_mode
-            if encode == Y4M_ENCODE:
-                key = key + y4m_mode
-            if redact is not None:
-                key = key + ("redact",) + redact
-            if not draw:
-                key = key + ("nodraw",)
-            if track is not None:
-                key = key + ("track",) + track
-            if track_motion is not None:
-                key = key + ("motion", track_motion)
-            if track_lookback is not None:
-                key = key + ("lookback", track_lookback)
-            if detect_every is not None:
-                key = key + ("every", detect_every)
-            if track_backtrack is not None:
-                key = key + ("backtrack", track_backtrack)
+            key = key + spec.key_tail(B)
         else:
             key = self.geometry(pixels[0])
             assert all(self.geometry(p) == key for p in pixels), "one pass, one geometry"
@@ -1249,11 +1293,9 @@ class DetectionEntry:
         if key[0] == "canvas":
             s = self.cache.acquire(key, lambda: self._capture_slot(B, True, key[1], key[2]))
         else:
-            capture = lambda: self._capture_slot(B, False, H, W, src, flip, annotate, encode, quality,
-                                                 jpeg_mode if encode == JPEG_ENCODE else JPEG_MODE, y4m_mode, redact, draw, track, track_motion,
-                                                 track_lookback, detect_every, track_backtrack)
+            capture = lambda: self._capture_slot(B, False, H, W, src, flip, spec)
             s = self.cache.acquire(key, capture)
-            if track_lookback is not None or track_backtrack is not None:
+            if spec.delayed:
                 self._lookback_last = (key, capture)
         return self._replay(s, images, pixels, resize_ratios, det_threshold)
 

@@ -1347,6 +1347,27 @@ def _track_packed(det_packed):
     return base, stride, B, words
 
 
+def _track_update_args(state, n_frames, table, words, frames, out):
+    """What the ``track_update*`` calls check alike: ``state``, ``n_frames``, ``table`` and ``out`` -- allocated here when None,
+    (``frames``, 4 + 8R) int32 -- for packed buffers of ``words`` words -> (the state's capacity, the buffers' rows, R, ``out``)."""
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    cap, rows = track_capacity(state), (words - 4) // 7
+    R = rows + cap
+    if out is None:
+        out = torch.empty((frames, 4 + 8 * R), dtype=torch.int32, device="cuda")
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (frames, 4 + 8 * R)
+    return cap, rows, R, out
+
+
+def _track_motion_args(mstate, frames_u8, frame_stride, frames, h, w):
+    """What the two motion forms check of ``mstate`` and of the ``frames`` source frames in ``frames_u8``."""
+    assert mstate.is_cuda and mstate.dtype == torch.uint8 and mstate.dim() == 1 and mstate.is_contiguous() and mstate.numel() == 16 + 3 * int(h) * int(w)
+    assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
+    assert int(frames_u8.numel()) >= (frames - 1) * int(frame_stride) + 3 * int(h) * int(w) and int(frame_stride) >= 0
+
+
 def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, out=None):
     """The tracking rule (DESIGN §8 "Tracking rule", frcnn_track_update) over the frames of ``det_packed`` IN ORDER, in one launch:
     ``state`` (``track_state``) is read and advanced, and frame f's tracked buffer lands in ``out[f]`` -- -> ``out``, a (B, 4 + 8R) int32
@@ -1358,14 +1379,7 @@ def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=
     Reads *n_dets and *n_frames on the device: the call can be captured in a graph."""
     _require_gpu()
     base, stride, B, words = _track_packed(det_packed)
-    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
-    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
-    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
-    cap, rows = track_capacity(state), (words - 4) // 7
-    R = rows + cap
-    if out is None:
-        out = torch.empty((B, 4 + 8 * R), dtype=torch.int32, device="cuda")
-    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (B, 4 + 8 * R)
+    cap, rows, R, out = _track_update_args(state, n_frames, table, words, B, out)
     _lib.call("frcnn_track_update", _p(state), cap, _p(base), int(stride), B, _p(n_frames), rows, _p(table), int(table.numel()),
               int(thr), int(hold), int(grow), int(h), int(w), _p(out), 4 + 8 * R, _stream())
     return out
@@ -1409,17 +1423,8 @@ def track_update_motion(state, mstate, frames_u8, frame_stride, det_packed, n_fr
     frame and one more per call; reads *n_dets, *n_frames and the slot count on the device: the call can be captured in a graph."""
     _require_gpu()
     base, stride, B, words = _track_packed(det_packed)
-    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
-    assert mstate.is_cuda and mstate.dtype == torch.uint8 and mstate.dim() == 1 and mstate.is_contiguous() and mstate.numel() == 16 + 3 * int(h) * int(w)
-    assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
-    assert int(frames_u8.numel()) >= (B - 1) * int(frame_stride) + 3 * int(h) * int(w) and int(frame_stride) >= 0
-    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
-    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
-    cap, rows = track_capacity(state), (words - 4) // 7
-    R = rows + cap
-    if out is None:
-        out = torch.empty((B, 4 + 8 * R), dtype=torch.int32, device="cuda")
-    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (B, 4 + 8 * R)
+    _track_motion_args(mstate, frames_u8, frame_stride, B, h, w)
+    cap, rows, R, out = _track_update_args(state, n_frames, table, words, B, out)
     _lib.call("frcnn_track_update_motion", _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), B, _p(n_frames),
               rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), int(h), int(w), _p(out), 4 + 8 * R, _stream())
     return out
@@ -1452,17 +1457,8 @@ def track_update_interval(state, mstate, frames_u8, frame_stride, det_packed, n_
     if not _lib.TRACK_INTERVAL[0] <= interval <= _lib.TRACK_INTERVAL[1] or (F + interval - 1) // interval != B:
         raise _lib.FrcnnError("track_update_interval: interval=%d (1..%d) and %d frames do not go with %d key frames' detections"
                               % (interval, _lib.TRACK_INTERVAL[1], F, B))
-    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
-    assert mstate.is_cuda and mstate.dtype == torch.uint8 and mstate.dim() == 1 and mstate.is_contiguous() and mstate.numel() == 16 + 3 * int(h) * int(w)
-    assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
-    assert int(frames_u8.numel()) >= (F - 1) * int(frame_stride) + 3 * int(h) * int(w) and int(frame_stride) >= 0
-    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
-    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
-    cap, rows = track_capacity(state), (words - 4) // 7
-    R = rows + cap
-    if out is None:
-        out = torch.empty((F, 4 + 8 * R), dtype=torch.int32, device="cuda")
-    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (F, 4 + 8 * R)
+    _track_motion_args(mstate, frames_u8, frame_stride, F, h, w)
+    cap, rows, R, out = _track_update_args(state, n_frames, table, words, F, out)
     _lib.call("frcnn_track_update_interval", _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), F, _p(n_frames),
               rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), interval, int(h), int(w), _p(out), 4 + 8 * R,
               _stream())
@@ -1500,16 +1496,9 @@ def track_lookback_reset(window):
     return window
 
 
-def track_lookback(window, frames_u8, frame_stride, tracked, n_frames, capacity, back, h, w, lookback=TRACK_LOOKBACK[2], radius=0, grow=0, out=None):
-    """One call of the look-back rule (DESIGN §8 "Look-back rule", frcnn_track_lookback): the B frames of the call -- ``frames_u8`` holds
-    frame f, (h, w, 3) uint8 as uploaded, at byte ``f * frame_stride``; ``tracked`` is ``track_update``'s (B, 4 + 8R) result for them --
-    join ``window`` (``track_lookback_state``), every track born in them is followed BACKWARDS over at most ``lookback`` frames by the
-    block match of radius ``radius`` (0: its box stands still) and leaves one back-filled row, age -k, in each of those frames, and the
-    frames the window held before the call are emitted: -> ``out`` = (frames (B, h, w, 3) uint8, tracked (B, 4 + 8 R2) int32, count
-    int32 [1]), R2 = R + ``back``; the first ``count`` entries are the emitted frames, oldest first, untouched, with their widened
-    buffers (``redact_u8`` and ``annotate_u8`` take one with ``tracked=True``).  ``n_frames``: an int32 device tensor; its first word
-    says how many of the B frames are real, 0 emits again and changes nothing, < 0 emits and empties the window.  Five launches; every
-    count is read on the device: the call can be captured in a graph."""
+def _track_window_call(who, window, frames_u8, frame_stride, tracked, n_frames, capacity, back, h, w, lookback, radius, grow, interval, out):
+    """The body ``track_lookback`` and ``track_backtrack`` share: the checks (``who`` names the caller in their messages), ``out`` and the
+    call of frcnn_<who>; ``interval``: the arguments the entry point takes between ``grow`` and the frame's size -- (interval,) or none."""
     _require_gpu()
     h, w, cap, back = int(h), int(w), int(capacity), int(back)
     assert window.is_cuda and window.dtype == torch.uint8 and window.dim() == 1 and window.is_contiguous()
@@ -1517,11 +1506,11 @@ def track_lookback(window, frames_u8, frame_stride, tracked, n_frames, capacity,
     B, words = int(tracked.shape[0]), int(tracked.shape[1])
     R = (words - 4) // 8
     rows, R2 = R - cap, R + back
-    assert words == 4 + 8 * R and rows >= 1, "track_lookback: tracked buffers of %d words for capacity=%d" % (words, cap)
+    assert words == 4 + 8 * R and rows >= 1, "%s: tracked buffers of %d words for capacity=%d" % (who, words, cap)
     need = int(_lib.load().frcnn_track_lookback_state_bytes(B, h, w, rows, cap, back))
     if need and int(window.numel()) != need:
-        raise _lib.FrcnnError("track_lookback: the window has %d bytes; one for calls of %d frames of %dx%d with %d + %d + %d rows has %d "
-                              "(track_lookback_state with the call's frames, rows, capacity and back)" % (window.numel(), B, h, w, rows, cap, back, need))
+        raise _lib.FrcnnError("%s: the window has %d bytes; one for calls of %d frames of %dx%d with %d + %d + %d rows has %d "
+                              "(track_lookback_state with the call's frames, rows, capacity and back)" % (who, window.numel(), B, h, w, rows, cap, back, need))
     assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
     assert int(frame_stride) >= 0 and int(frames_u8.numel()) >= (B - 1) * int(frame_stride) + 3 * h * w
     assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
@@ -1532,9 +1521,23 @@ def track_lookback(window, frames_u8, frame_stride, tracked, n_frames, capacity,
     assert o_frames.is_cuda and o_frames.dtype == torch.uint8 and o_frames.is_contiguous() and tuple(o_frames.shape) == (B, h, w, 3)
     assert o_tracked.is_cuda and o_tracked.dtype == torch.int32 and o_tracked.is_contiguous() and tuple(o_tracked.shape) == (B, 4 + 8 * R2)
     assert o_count.is_cuda and o_count.dtype == torch.int32 and o_count.numel() >= 1
-    _lib.call("frcnn_track_lookback", _p(window), _p(frames_u8), int(frame_stride), _p(tracked), words, B, _p(n_frames), rows, cap, back,
-              int(lookback), int(radius), int(grow), h, w, _p(o_frames), 3 * h * w, _p(o_tracked), 4 + 8 * R2, _p(o_count), _stream())
+    _lib.call("frcnn_" + who, _p(window), _p(frames_u8), int(frame_stride), _p(tracked), words, B, _p(n_frames), rows, cap, back,
+              int(lookback), int(radius), int(grow), *interval, h, w, _p(o_frames), 3 * h * w, _p(o_tracked), 4 + 8 * R2, _p(o_count), _stream())
     return out
+
+
+def track_lookback(window, frames_u8, frame_stride, tracked, n_frames, capacity, back, h, w, lookback=TRACK_LOOKBACK[2], radius=0, grow=0, out=None):
+    """One call of the look-back rule (DESIGN §8 "Look-back rule", frcnn_track_lookback): the B frames of the call -- ``frames_u8`` holds
+    frame f, (h, w, 3) uint8 as uploaded, at byte ``f * frame_stride``; ``tracked`` is ``track_update``'s (B, 4 + 8R) result for them --
+    join ``window`` (``track_lookback_state``), every track born in them is followed BACKWARDS over at most ``lookback`` frames by the
+    block match of radius ``radius`` (0: its box stands still) and leaves one back-filled row, age -k, in each of those frames, and the
+    frames the window held before the call are emitted: -> ``out`` = (frames (B, h, w, 3) uint8, tracked (B, 4 + 8 R2) int32, count
+    int32 [1]), R2 = R + ``back``; the first ``count`` entries are the emitted frames, oldest first, untouched, with their widened
+    buffers (``redact_u8`` and ``annotate_u8`` take one with ``tracked=True``).  ``n_frames``: an int32 device tensor; its first word
+    says how many of the B frames are real, 0 emits again and changes nothing, < 0 emits and empties the window.  Five launches; every
+    count is read on the device: the call can be captured in a graph."""
+    return _track_window_call("track_lookback", window, frames_u8, frame_stride, tracked, n_frames, capacity, back, h, w, lookback, radius, grow,
+                              (), out)
 
 
 def track_backtrack_option(n, k, frames):
@@ -1563,31 +1566,8 @@ def track_backtrack(window, frames_u8, frame_stride, tracked, n_frames, capacity
     row of a KEY frame is followed backwards: a new track over at most ``lookback`` frames, a continued one through the between frames in
     front of its key frame.  ``window`` is a ``track_lookback_state`` for F frames; everything else, ``out`` and the return value: as
     ``track_lookback``.  With ``interval`` 1 every byte is ``track_lookback``'s.  Five launches; the call can be captured in a graph."""
-    _require_gpu()
-    h, w, cap, back = int(h), int(w), int(capacity), int(back)
-    assert window.is_cuda and window.dtype == torch.uint8 and window.dim() == 1 and window.is_contiguous()
-    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.is_contiguous() and tracked.dim() == 2
-    F, words = int(tracked.shape[0]), int(tracked.shape[1])
-    R = (words - 4) // 8
-    rows, R2 = R - cap, R + back
-    assert words == 4 + 8 * R and rows >= 1, "track_backtrack: tracked buffers of %d words for capacity=%d" % (words, cap)
-    need = int(_lib.load().frcnn_track_lookback_state_bytes(F, h, w, rows, cap, back))
-    if need and int(window.numel()) != need:
-        raise _lib.FrcnnError("track_backtrack: the window has %d bytes; one for calls of %d frames of %dx%d with %d + %d + %d rows has %d "
-                              "(track_lookback_state with the call's frames, rows, capacity and back)" % (window.numel(), F, h, w, rows, cap, back, need))
-    assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
-    assert int(frame_stride) >= 0 and int(frames_u8.numel()) >= (F - 1) * int(frame_stride) + 3 * h * w
-    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
-    if out is None:
-        out = (torch.zeros((F, h, w, 3), dtype=torch.uint8, device="cuda"), torch.zeros((F, 4 + 8 * R2), dtype=torch.int32, device="cuda"),
-               torch.zeros(1, dtype=torch.int32, device="cuda"))
-    o_frames, o_tracked, o_count = out
-    assert o_frames.is_cuda and o_frames.dtype == torch.uint8 and o_frames.is_contiguous() and tuple(o_frames.shape) == (F, h, w, 3)
-    assert o_tracked.is_cuda and o_tracked.dtype == torch.int32 and o_tracked.is_contiguous() and tuple(o_tracked.shape) == (F, 4 + 8 * R2)
-    assert o_count.is_cuda and o_count.dtype == torch.int32 and o_count.numel() >= 1
-    _lib.call("frcnn_track_backtrack", _p(window), _p(frames_u8), int(frame_stride), _p(tracked), words, F, _p(n_frames), rows, cap, back,
-              int(lookback), int(radius), int(grow), int(interval), h, w, _p(o_frames), 3 * h * w, _p(o_tracked), 4 + 8 * R2, _p(o_count), _stream())
-    return out
+    return _track_window_call("track_backtrack", window, frames_u8, frame_stride, tracked, n_frames, capacity, back, h, w, lookback, radius, grow,
+                              (int(interval),), out)
 
 
 def split_tracked(buf):
