@@ -419,6 +419,17 @@ TRACK_INTERVAL_SIGNATURES = {
 # frames from one key frame to the next: (smallest at the ABI, largest) (FRCNN_TRACK_INTERVAL_MIN / _MAX); the public option starts at 2
 TRACK_INTERVAL = (1, 16)
 
+TRACK_CUT_VERSION = 1           # include/ext/frcnn_hip_track_cut.h FRCNN_TRACK_CUT_VERSION
+TRACK_CUT_SIGNATURES = {
+    "frcnn_track_cut_version": (I, []),
+    "frcnn_track_cut_workspace_bytes": (c_size_t, [I]),
+    "frcnn_track_update_cut": (I, [P, I, P, P, ctypes.c_longlong, P, ctypes.c_longlong, I, P, I, P, I, I, I, I, I, I, I, I, P,
+                                   ctypes.c_longlong, I, P, P, P]),
+}
+# the share of the largest signature distance at which a frame is a cut, in percent: (smallest, largest, the default)
+# (FRCNN_TRACK_CUT_MIN_PCT / _MAX_PCT; the default is provisional: no threshold has been measured on real footage)
+TRACK_CUT_PCT = (1, 100, 40)
+
 TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
 TRACK_LOOKBACK_SIGNATURES = {
     "frcnn_track_lookback_version": (I, []),
@@ -589,6 +600,15 @@ def load():
     if lib.frcnn_track_interval_version() != TRACK_INTERVAL_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_interval_version()} of the tracker's interval extension, this binding "
                          f"{TRACK_INTERVAL_VERSION} (include/ext/frcnn_hip_track_interval.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in TRACK_CUT_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_track_cut.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_track_cut_version() != TRACK_CUT_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_cut_version()} of the tracker's scene-cut extension, this binding "
+                         f"{TRACK_CUT_VERSION} (include/ext/frcnn_hip_track_cut.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -76,6 +76,13 @@ csrc/track_backtrack.hip; DESIGN §8 "Back-track rule") -- a continued track as 
 -- and hides the boxes found there too: a frame between two detections is covered from both sides.  The output then runs one pass
 behind the input, as with ``--track_lookback``; the back-filled rows are printed with "backfilled": k, never drawn and not written to
 ``--tracks_out``.
+``track_scene_cut=PCT`` (``--track_scene_cut [PCT]``, with ``--track --track_motion``, with or without ``--detect_every K``; 1..100; bare:
+40, a provisional default that no real footage has been measured for) ends every track at a hard cut (ops.track_update_cut,
+csrc/track_cut.hip; DESIGN §8 "Cut rule"): a frame whose 4 x 4-region luma histogram differs from that of the frame before by PCT percent
+of the largest distance there is starts a new scene -- no id is carried into it, no held box of the old scene is redacted in it, and
+between two detected frames nothing is shown behind a cut until the next detected frame.  A line ``scene cut: <path>`` is printed in front
+of that frame's lines; ``--tracks_out`` keeps its format.  Fades and dissolves are not detected.  Not together with ``--track_lookback``
+or ``--track_backtrack``: their backward chains would have to stop at a cut.
 """
 import collections
 import os
@@ -277,16 +284,18 @@ def _eager_track_table(tracker, class_mapping, redact_classes):
     return table
 
 
-def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None):
+def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None):
     """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place.
     ``redact`` = (classes, mode, size, margin): one ops.redact_u8 in front of it; ``draw`` False: no drawing.
     ``track`` = (thr, hold, grow): one ops.track_update (one frame) in front of both, on this class mapping's eager tracker state
     (``reset_tracks`` empties it); ``dets`` is edited in place as ``collect_batch`` returns it: "track_id" on every det, the held rows
     appended with "held".  ``track_motion`` = R: ops.track_update_motion in its place, with the frame as it came and this class mapping's
-    motion state for the frame's size."""
+    motion state for the frame's size.  ``track_scene_cut`` = PCT (with ``track_motion``): ops.track_update_cut with interval 1 in its
+    place -- the kept frame is the reference --, and ``info``, a dict, receives "scene_cut": True when the frame is a cut."""
     import torch
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
+    _track_scene_cut(track_scene_cut, track, track_motion, None, None)
     key = tuple(sorted(class_mapping.items()))
     if track is not None or (dets and (draw or redact is not None)):      # (nothing to draw or hide: the frame stays as it is)
         dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
@@ -298,7 +307,14 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
         if track is not None:
             tracker = _eager_tracker(class_mapping)
             t_table = _eager_track_table(tracker, class_mapping, classes)
-            if track_motion is not None:                            # (in front of the redaction: ``dev`` is still the frame as it came)
+            if track_scene_cut is not None:                         # (one frame: its reference is the kept frame)
+                rows, cuts = ops.track_update_cut(tracker[0], _eager_motion_state(class_mapping, frame.shape[0], frame.shape[1]), dev.view(-1), 0,
+                                                  packed, tracker[2], t_table, frame.shape[0], frame.shape[1], *track,
+                                                  ops.track_motion_radius(track_motion), 1, ops.track_cut_option(track_scene_cut))
+                rows = rows[0]
+                if info is not None and int(cuts[0]):
+                    info["scene_cut"] = True
+            elif track_motion is not None:                          # (in front of the redaction: ``dev`` is still the frame as it came)
                 rows = ops.track_update_motion(tracker[0], _eager_motion_state(class_mapping, frame.shape[0], frame.shape[1]), dev.view(-1), 0,
                                                packed, tracker[2], t_table, frame.shape[0], frame.shape[1], *track,
                                                ops.track_motion_radius(track_motion))[0]
@@ -489,6 +505,39 @@ def _every_parts(group, B, every):
     return [(group[i:i + every], 1) for i in range(0, len(group), every)]
 
 
+def track_scene_cut_from_args(args):
+    """(host only) The scene-cut threshold the command line asks for -> the percentage as ``submit_batch(track_scene_cut=...)`` takes it
+    (ops.TRACK_CUT_PCT[2] = 40 for a bare ``--track_scene_cut``), or None without the flag.  ValueError, with the reason, for
+    ``--track_scene_cut`` without ``--track --track_motion``, together with ``--track_lookback`` or ``--track_backtrack`` and for a value
+    outside 1..100."""
+    if args.track_scene_cut is None:
+        return None
+    if not args.track or args.track_motion is None:
+        raise ValueError("--track_scene_cut=%s compares every frame with the frame the block match keeps: it needs --track --track_motion"
+                         % args.track_scene_cut)
+    for flag, value in (("--track_lookback", args.track_lookback), ("--track_backtrack", args.track_backtrack)):
+        if value is not None:
+            raise ValueError("--track_scene_cut together with %s is not supported: a backward chain would have to stop at a cut" % flag)
+    try:
+        return ops.track_cut_option(args.track_scene_cut)
+    except ValueError as e:
+        raise ValueError("--track_scene_cut: %s" % e) from None
+
+
+def _track_scene_cut(track_scene_cut, track, track_motion, track_lookback, track_backtrack):
+    """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame``'s ``track_scene_cut`` checked -> the percentage, or None."""
+    if track_scene_cut is None:
+        return None
+    if track is None or track_motion is None:
+        raise ValueError("track_scene_cut=%r compares every frame with the frame the block match keeps: it needs track=(thr, hold, grow) and "
+                         "track_motion=R" % (track_scene_cut,))
+    for name, value in (("track_lookback", track_lookback), ("track_backtrack", track_backtrack)):
+        if value is not None:
+            raise ValueError("track_scene_cut=%r together with %s=%r is not supported: a backward chain would have to stop at a cut"
+                             % (track_scene_cut, name, value))
+    return ops.track_cut_option(track_scene_cut)
+
+
 def _lookback_frames(track_lookback, track, eng, B):
     """``annotate_images`` / ``annotate_stream``'s ``track_lookback`` checked -> the look-back of their passes, or None."""
     if track_lookback is None:
@@ -544,12 +593,14 @@ def _print_drawn(dets, width, height):
 
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
-                        frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None):
+                        frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
     ``tracks_out``: a text file that receives the frame's MOT lines under the number ``frame_no``.  ``track_motion`` = R (with
-    ``track``): the tracks' boxes are first moved with the pixels under them, at most R pixels either way (DESIGN §8 "Motion rule")."""
+    ``track``): the tracks' boxes are first moved with the pixels under them, at most R pixels either way (DESIGN §8 "Motion rule").
+    ``track_scene_cut`` = PCT (with ``track_motion``): every track ends when the frame is a hard cut against the frame before it (DESIGN
+    §8 "Cut rule"); a line ``scene cut: <frame_no>`` is then printed in front of the frame's lines."""
     if detect_every is not None:
         raise ValueError("detect_every=%r runs the detector once per pass of several frames: get_annotated_frame detects its one frame and "
                          "cannot; use annotate_images or annotate_stream" % (detect_every,))
@@ -562,18 +613,26 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     motion = {} if track_motion is None else {"track_motion": track_motion}
+    if _track_scene_cut(track_scene_cut, track, track_motion, None, None) is not None:
+        motion["track_scene_cut"] = track_scene_cut
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1)
+    info = {}
     if eng is not None:
         pixels = eng.host_pixels(resized_imgs[0])
-        num_rois, dets, out = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], DET_THRESHOLD, [pixels],
-                                                                 batch=1, annotate=True, redact=redact, draw=draw,
-                                                                 **({} if track is None else {"track": track}), **motion))[0]
+        num_rois, dets, out, *more = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], DET_THRESHOLD, [pixels],
+                                                                        batch=1, annotate=True, redact=redact, draw=draw,
+                                                                        **({} if track is None else {"track": track}), **motion))[0]
+        info = more[0] if more else info                          # (a ``track_scene_cut`` pass: the frame's marks behind its payload)
+        if info.get("scene_cut"):
+            print("scene cut: {}".format(frame_no))
         print("num rois: {}".format(num_rois))
         frame[...] = out
     else:
         dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=DET_THRESHOLD)
-        draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, **motion)
+        draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, info=info, **motion)
+        if info.get("scene_cut"):
+            print("scene cut: {}".format(frame_no))
     if track is not None:
         _write_tracks(tracks_out, frame_no, dets, training_manager.class_mapping)
     _print_drawn(dets, img.width, img.height)
@@ -772,7 +831,7 @@ def _encoder_options(png_encoder, png_compress, frame_format, jpeg_encoder, jpeg
     return kwargs, on_device, jpg, write_host, encode
 
 
-def _tracking_options(eng, track, track_motion, track_lookback, detect_every, track_backtrack):
+def _tracking_options(eng, track, track_motion, track_lookback, detect_every, track_backtrack, track_scene_cut=None):
     """The tracking arguments of ``annotate_images`` checked against the engine (None: the eager path) -> (their keywords of submit_batch,
     the K of a ``detect_every`` pass or None, do the passes return the frames of the pass before them?, the look-back of a
     ``track_backtrack`` pass or None)."""
@@ -780,8 +839,10 @@ def _tracking_options(eng, track, track_motion, track_lookback, detect_every, tr
     every = _detect_every(detect_every, track, track_motion, track_lookback, eng, B)
     lookback = _lookback_frames(track_lookback, track, eng, B)
     backtrack = _backtrack_frames(track_backtrack, every, track_lookback, eng, B)
+    cut = _track_scene_cut(track_scene_cut, track, track_motion, track_lookback, track_backtrack)
     kwargs = {} if track is None else {"track": track}
-    for name, value in (("track_motion", track_motion), ("track_lookback", lookback), ("detect_every", every), ("track_backtrack", backtrack)):
+    for name, value in (("track_motion", track_motion), ("track_lookback", lookback), ("detect_every", every), ("track_backtrack", backtrack),
+                        ("track_scene_cut", cut)):
         if value is not None:
             kwargs[name] = value
     return kwargs, every, lookback is not None or backtrack is not None, backtrack
@@ -973,7 +1034,7 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 
 
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
-              tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None):
+              tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
@@ -984,7 +1045,10 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     try:
         dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
         eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
-        tracking, every, delayed, backtrack = _tracking_options(eng, track, track_motion, track_lookback, detect_every, track_backtrack)
+        tracking, every, delayed, backtrack = _tracking_options(eng, track, track_motion, track_lookback, detect_every, track_backtrack,
+                                                                track_scene_cut)
+        if track_scene_cut is not None:                   # (the eager path: one frame at a time against the kept frame)
+            motion["track_scene_cut"] = track_scene_cut
         if track is not None:                             # a new sequence; its frames are submitted in input order, as every list's are
             reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
         if eng is None:
@@ -1002,7 +1066,9 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
                 return label, frame, resized, ratio, eng.host_pixels(resized)
 
             def emit(pos, label, frame, result):
-                num_rois, dets, out = result
+                num_rois, dets, out, *marks = result      # (a ``track_scene_cut`` pass: the frame's marks behind its payload)
+                if marks and marks[0].get("scene_cut"):
+                    print("scene cut: {}".format(label))
                 print("processing {}".format(label))
                 print("num rois: {}".format(num_rois))
                 if track is not None:
@@ -1019,13 +1085,13 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
-                    track_backtrack=None):
+                    track_backtrack=None, track_scene_cut=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut``: as ``annotate_images``."""
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
     if isinstance(writer_or_out_dir, y4m.Y4mWriter):
         make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma)
@@ -1034,13 +1100,13 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                                       jpeg_huffman)
     _annotate(training_manager, detector, source, lambda prepare, ahead: _loaded_stream(source, prepare, ahead), make_sink, resize_min, resize_max,
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
-              detect_every=detect_every, track_backtrack=track_backtrack)
+              detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
-                    track_lookback=None, detect_every=None, track_backtrack=None):
+                    track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1078,7 +1144,13 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     followed BACK through the frames in front of it (DESIGN §8 "Back-track rule"): a continued track as far as the detected frame before,
     a new one over that many frames, and the boxes found are hidden there too, so a frame between two detections is covered from both
     sides.  Every group of at most B * K frames then goes through one full (padded) pass, a pass returns the frames of the pass before it
-    and a flush follows a change of geometry and the end of the list, as with ``track_lookback``.  The eager path refuses it."""
+    and a flush follows a change of geometry and the end of the list, as with ``track_lookback``.  The eager path refuses it.
+    ``track_scene_cut``: the percentage as ``track_scene_cut_from_args`` returns it (with ``track`` and ``track_motion``, with or without
+    ``detect_every``; not with ``track_lookback`` or ``track_backtrack``, whose backward chains would have to stop at a cut) -- a frame
+    whose 4 x 4-region luma histogram differs from the frame before by that share of the largest distance there is, is a hard cut (DESIGN
+    §8 "Cut rule"): every track ends in front of it, so no id is inherited by the new scene and no held box of the old scene is redacted
+    in it; between two detected frames nothing is shown behind a cut until the next detected frame.  A line ``scene cut: <path>`` is
+    printed in front of that frame's lines.  A fade or a dissolve is not detected.  None: every byte and line is what it was."""
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
@@ -1090,7 +1162,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     _annotate(training_manager, detector, ((path, _Frame(_read_rgb(path))) for path in paths),
               lambda prepare, ahead: _loaded_files(paths, lambda path: prepare(path, _load_frame(path, device_decode, device_png)), ahead),
               make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
-              track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack)
+              track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut)
 
 
 def build_parser():
@@ -1183,6 +1255,12 @@ def build_parser():
                         "K - 1 and at most the B * K frames of one pass; bare: as many as a pass holds, at most 16) -- so a frame between two "
                         "detections is covered from both sides; the output runs one pass behind the input (needs --track --track_motion "
                         "--detect_every; not with --track_lookback)")
+    p.add_argument("--track_scene_cut", dest="track_scene_cut", type=int, nargs="?", const=ops.TRACK_CUT_PCT[2], default=None, metavar="PCT",
+                   help="end every track at a hard cut: a frame whose 4x4-region luma histogram differs from the frame before by PCT percent "
+                        "of the largest distance there is (1..100; bare: 40, a provisional default that no real footage has been measured "
+                        "for) starts a new scene -- no id is carried into it and no held box of the old scene is redacted in it; a line "
+                        "'scene cut: <path>' is printed in front of that frame's lines; fades and dissolves are not detected (needs --track "
+                        "--track_motion; with or without --detect_every; not with --track_lookback or --track_backtrack)")
     p.add_argument("--tracks_out", dest="tracks_out", default=None, metavar="PATH",
                    help="write the tracks as MOTChallenge lines frame,id,left,top,width,height,prob,cls,-1,-1 (needs --track)")
     return p
@@ -1258,6 +1336,9 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     track_backtrack = track_backtrack_from_args(args)
     if track_backtrack is not None:
         tracking["track_backtrack"] = track_backtrack
+    track_scene_cut = track_scene_cut_from_args(args)
+    if track_scene_cut is not None:
+        tracking["track_scene_cut"] = track_scene_cut
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

@@ -9,6 +9,7 @@
 #include "../../include/ext/frcnn_hip_track.h"
 #include "../../include/ext/frcnn_hip_track_interval.h"
 #include "track.h"
+#include "track_interval.h"
 #include "track_motion.h"
 
 namespace frcnn {
@@ -66,6 +67,26 @@ __global__ void __launch_bounds__(TI_THREADS) k_interval_between(int32_t* state,
     }
 }
 
+int interval_check(const char* who, const int32_t* state, int capacity, const uint8_t* motion_state, const uint8_t* frames_u8,
+                   long long frame_stride, const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
+                   const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h, int w,
+                   const int32_t* out, long long out_stride) {
+    if (interval < FRCNN_TRACK_INTERVAL_MIN || interval > FRCNN_TRACK_INTERVAL_MAX)
+        return fail(FRCNN_E_ARG, "%s: interval=%d not in [%d, %d]", who, interval, FRCNN_TRACK_INTERVAL_MIN, FRCNN_TRACK_INTERVAL_MAX);
+    // the packed buffers are one per KEY frame: their distance is read only when the call has more than one of them
+    const long long det_words = 4 + 7LL * max_rows;
+    const bool keys = frames >= 1 && (frames + interval - 1) / interval > 1;
+    int bad = track_check(who, state, capacity, det_packed, keys ? det_stride : det_words, frames, n_frames, max_rows, tracked, num_classes, thr,
+                          hold, grow, h, w, out, out_stride);
+    if (!bad) bad = motion_check(who, motion_state, frames_u8, frame_stride, frames, radius, h, w);
+    return bad;
+}
+
+void interval_between_launch(int32_t* state, int capacity, int f, int total, const int32_t* n_frames, int max_rows, int grow, int h, int w,
+                             int32_t* o, hipStream_t stream) {
+    k_interval_between<<<1, TI_THREADS, 0, stream>>>(state, capacity, f, total, n_frames, max_rows, grow, h, w, o);
+}
+
 }  // namespace frcnn
 
 using namespace frcnn;
@@ -77,14 +98,8 @@ extern "C" int frcnn_track_update_interval(int32_t* state, int capacity, uint8_t
                                            const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h,
                                            int w, int32_t* out, long long out_stride, void* stream) {
     const char* who = "track_update_interval";
-    if (interval < FRCNN_TRACK_INTERVAL_MIN || interval > FRCNN_TRACK_INTERVAL_MAX)
-        return fail(FRCNN_E_ARG, "%s: interval=%d not in [%d, %d]", who, interval, FRCNN_TRACK_INTERVAL_MIN, FRCNN_TRACK_INTERVAL_MAX);
-    // the packed buffers are one per KEY frame: their distance is read only when the call has more than one of them
-    const long long det_words = 4 + 7LL * max_rows;
-    const bool keys = frames >= 1 && (frames + interval - 1) / interval > 1;
-    int bad = track_check(who, state, capacity, det_packed, keys ? det_stride : det_words, frames, n_frames, max_rows, tracked, num_classes, thr,
-                          hold, grow, h, w, out, out_stride);
-    if (!bad) bad = motion_check(who, motion_state, frames_u8, frame_stride, frames, radius, h, w);
+    const int bad = interval_check(who, state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames, max_rows,
+                                   tracked, num_classes, thr, hold, grow, radius, interval, h, w, out, out_stride);
     if (bad) return bad;
     hipStream_t st = as_stream(stream);
     for (int f = 0; f < frames; ++f) {
@@ -94,7 +109,7 @@ extern "C" int frcnn_track_update_interval(int32_t* state, int capacity, uint8_t
             track_launch_at(state, capacity, det_packed + (long long)(f / interval) * det_stride, det_stride, f, 1, frames, n_frames, max_rows,
                             tracked, num_classes, thr, hold, grow, h, w, o, out_stride, st);
         else
-            k_interval_between<<<1, TI_THREADS, 0, st>>>(state, capacity, f, frames, n_frames, max_rows, grow, h, w, o);
+            interval_between_launch(state, capacity, f, frames, n_frames, max_rows, grow, h, w, o, st);
     }
     motion_keep_launch(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w, st);
     return check_launch(who);

@@ -311,10 +311,11 @@ class PassSpec:
     track_lookback: object = None
     detect_every: object = None
     track_backtrack: object = None
+    track_scene_cut: object = None
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
-                track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None):
+                track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -348,6 +349,18 @@ class PassSpec:
                 raise FrcnnError("submit_batch: detect_every= needs the device-side preprocess: a foreign preprocess_func uploads float "
                                  "pixels of the key frames only, and the block match reads the uint8 pixels of every source frame")
             detect_every = engine.detect_every_option(detect_every, engine.batch if batch is None else batch)
+        if track_scene_cut is not None:
+            if track_motion is None:
+                raise FrcnnError("submit_batch: track_scene_cut= compares every frame with the frame the block match keeps: pass "
+                                 "track=(thr, hold, grow) and track_motion=R too")
+            for name, value in (("track_lookback", track_lookback), ("track_backtrack", track_backtrack)):
+                if value is not None:
+                    raise FrcnnError("submit_batch: track_scene_cut= together with %s= is not supported: a backward chain would have to "
+                                     "stop at a cut" % name)
+            if not engine.device_preprocess:
+                raise FrcnnError("submit_batch: track_scene_cut= needs the device-side preprocess: a foreign preprocess_func uploads float "
+                                 "pixels, and the cut rule reads the uint8 pixels of every source frame")
+            track_scene_cut = engine.track_scene_cut_option(track_scene_cut)
         if redact is not None:
             redact = engine.redact_option(redact)
         jpeg_mode, y4m_mode = JPEG_MODE, Y4M_MODE
@@ -381,7 +394,8 @@ class PassSpec:
         if encode and not annotate:
             raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
-                   track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack)
+                   track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
+                   track_scene_cut=track_scene_cut)
 
     @property
     def delayed(self):
@@ -412,7 +426,7 @@ class PassSpec:
         if self.track is not None:
             key = key + ("track",) + self.track
         for tag, value in (("motion", self.track_motion), ("lookback", self.track_lookback), ("every", self.detect_every),
-                           ("backtrack", self.track_backtrack)):
+                           ("backtrack", self.track_backtrack), ("cut", self.track_scene_cut)):
             if value is not None:
                 key = key + (tag, value)
         return key
@@ -429,7 +443,8 @@ class _Slot:
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
                  "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
-                 "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec")
+                 "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
+                 "track_scene_cut", "cut_ws", "cuts", "cuts_pin", "_cuts_raw")
 
     def __init__(self):
         for name in self.__slots__:
@@ -731,6 +746,14 @@ class DetectionEntry:
         return k
 
     @staticmethod
+    def track_scene_cut_option(pct):
+        """``submit_batch``'s ``track_scene_cut`` checked -> the threshold in percent, 1..100.  FrcnnError with the reason."""
+        try:
+            return ops.track_cut_option(pct)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: track_scene_cut=%r: %s" % (pct, e)) from None
+
+    @staticmethod
     def track_motion_option(radius):
         """``submit_batch``'s ``track_motion`` checked -> the search radius, 1..16.  FrcnnError with the reason."""
         try:
@@ -821,6 +844,8 @@ class DetectionEntry:
             # with ``track_motion``: the block match moves the slots between the frames, which lie ``seg`` bytes apart in the staging
             # area and are still as they were uploaded -- the call stays in front of every redaction and drawing step of the pass
             t_motion = self.track_motion_state(in_h, in_w) if s.track_motion else None
+            if s.track_scene_cut:
+                s.cut_ws, s.cuts = ops.track_cut_workspace(F), torch.zeros(F, dtype=torch.int32, device="cuda")
         if s.track_lookback:
             # the frames, as uploaded, and their tracked buffers then join the engine's window, the new tracks are followed back through
             # it, and the frames of the pass BEFORE come out: everything behind this point edits and encodes those (``out``), with their
@@ -875,7 +900,11 @@ class DetectionEntry:
                     if s.track_out is None:                         # (the first warm-up pass: the rows of a packed buffer are known now)
                         R = ops.track_rows(packed) + ops.track_capacity(t_state)
                         s.track_out = torch.zeros((F, 4 + 8 * R), dtype=torch.int32, device="cuda")
-                    if s.every:
+                    if s.track_scene_cut:
+                        # in the place of the motion or interval call: the cut step in front of every frame, the frames' marks in ``s.cuts``
+                        ops.track_update_cut(t_state, t_motion, s.io_dev, seg, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold,
+                                             t_grow, s.track_motion, K, s.track_scene_cut, out=s.track_out, cuts=s.cuts, workspace=s.cut_ws)
+                    elif s.every:
                         # the B key frames' detections, all F frames: between two key frames the block match alone moves the tracks
                         ops.track_update_interval(t_state, t_motion, s.io_dev, seg, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold,
                                                   t_grow, s.track_motion, K, out=s.track_out)
@@ -969,6 +998,7 @@ class DetectionEntry:
             s.redact, s.nodraw, s.track, s.track_motion = spec.redact, (None if spec.draw else True), spec.track, spec.track_motion
             s.track_lookback, s.track_backtrack = spec.track_lookback or spec.track_backtrack, spec.track_backtrack      # (both: the delayed path is one)
             s.every, s.frames = spec.detect_every, B * (spec.detect_every or 1)
+            s.track_scene_cut = spec.track_scene_cut
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -1012,6 +1042,9 @@ class DetectionEntry:
             if s.track:
                 s._track_raw = self._pinned.take(4 * s.track_out.numel())
                 s.track_pin = s._track_raw.view(torch.int32)[:s.track_out.numel()].view(tuple(s.track_out.shape))
+            if s.track_scene_cut:
+                s._cuts_raw = self._pinned.take(4 * s.frames)
+                s.cuts_pin = s._cuts_raw.view(torch.int32)[:s.frames]
             if s.track_lookback:                                    # [the B emitted buffers | the count word]
                 words = s.lb_out[1].numel() + 4
                 s._lb_raw = self._pinned.take(4 * words)
@@ -1199,7 +1232,7 @@ class DetectionEntry:
 
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
-                     track_lookback=None, detect_every=None, track_backtrack=None):
+                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1259,10 +1292,19 @@ class DetectionEntry:
         propagated forwards and by the one tracked back from the next detection.  The pass is a delayed pass exactly as a
         ``track_lookback`` pass is -- ``collect_batch`` of submit k returns the results of submit k - 1, one per SOURCE frame, a submit
         with no images is the flush, one sequence at a time --; its between frames keep "propagated": True on their live dets, and the
-        back-filled rows are dets with "backfilled" = k.  Not together with ``track_lookback``."""
+        back-filled rows are dets with "backfilled" = k.  Not together with ``track_lookback``.
+        ``track_scene_cut`` = PCT (tracking passes with ``track_motion`` only, with or without ``detect_every``; ("cut", PCT) appended
+        behind the tags above; 1..100, None in PCT's place is not the default here: ops.track_cut_option() is, 40, provisional): the cut
+        rule (DESIGN §8 "Cut rule", ops.track_update_cut) takes the place of the motion or interval call: a frame whose 4 x 4-region luma
+        histogram differs from that of the frame before by PCT percent of the largest distance there is, is a hard cut, and every track
+        ends in front of it -- no id continues across it, no held row crosses it, and a between frame behind it has no dets until the
+        next key frame.  Every result of such a pass carries one more element behind its payload, a dict: {"scene_cut": True} for a frame
+        that is a cut, {} else.  Refused by name without ``track_motion``, together with ``track_lookback`` or ``track_backtrack`` (their
+        backward chains would have to stop at a cut) and on an engine whose foreign preprocess uploads float pixels.  Without it every
+        key and byte is what it was."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
-                                detect_every=detect_every, track_backtrack=track_backtrack)
+                                detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1350,6 +1392,8 @@ class DetectionEntry:
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
             for i in range(len(pixels) if s.track else 0):
                 s.track_pin[i].copy_(s.track_out[i], non_blocking=True)
+            if s.track_scene_cut:
+                s.cuts_pin.copy_(s.cuts, non_blocking=True)
             for i in range(emitted["frames"] if emitted else 0 if s.track_lookback else len(pixels)):
                 if s.encode == JPEG_ENCODE:
                     s.png_pin[i].copy_(s.png_dev[i][:s.first_copy], non_blocking=True)
@@ -1520,7 +1564,7 @@ class DetectionEntry:
                             d["propagated"] = True
                         else:
                             d["held"] = int(t_age[k])
-                    res.append((0, dets) + self._payload(s, f))
+                    res.append((0, dets) + self._payload(s, f) + self._marks(s, f))
                     continue
                 i = f // K
                 packed = s.out_pin[i].numpy()
@@ -1538,10 +1582,18 @@ class DetectionEntry:
                         dets[k]["track_id"] = int(t_id[k])
                     dets += [{"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(),
                               "track_id": int(t_id[k]), "held": int(t_age[k])} for k in range(nd, int(n_rows[0]))]
-                res.append((n_rois, dets) + self._payload(s, f))
+                res.append((n_rois, dets) + self._payload(s, f) + self._marks(s, f))
             return res
         finally:
             s.busy = False                               # whatever happened while decoding the records: the slot is free again
+
+    @staticmethod
+    def _marks(s, i):
+        """What frame i of a collected ``track_scene_cut`` pass returns behind its payload: one dict, {"scene_cut": True} for a frame that
+        is a cut and an empty one else; () for every other pass."""
+        if not s.track_scene_cut:
+            return ()
+        return ({"scene_cut": True},) if int(s.cuts_pin[i]) else ({},)
 
     def _payload(self, s, i):
         """What frame i of a collected pass returns behind (num_rois, dets): () , (the frame,) or (the encoded file's bytes,)."""

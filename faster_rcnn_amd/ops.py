@@ -1465,6 +1465,61 @@ def track_update_interval(state, mstate, frames_u8, frame_stride, det_packed, n_
     return out
 
 
+TRACK_CUT_PCT = _lib.TRACK_CUT_PCT              # (smallest, largest, the default) threshold of ``track_update_cut``, in percent
+
+
+def track_cut_option(pct=None):
+    """(host only) The scene-cut threshold checked, None replaced by the default 40: an integer in 1..100, the share of the largest
+    distance two frames' signatures can have at which the later frame is a cut.  The default is PROVISIONAL: no threshold has been
+    measured on real footage.  ValueError with the reason."""
+    lo, hi, default = TRACK_CUT_PCT
+    pct = default if pct is None else pct
+    if isinstance(pct, bool) or not isinstance(pct, (int, np.integer)) or not lo <= int(pct) <= hi:
+        raise ValueError("track scene cut=%r: an integer in %d..%d (percent)" % (pct, lo, hi))
+    return int(pct)
+
+
+def track_cut_workspace(frames):
+    """The workspace of ``track_update_cut`` calls of up to ``frames`` frames: an int32 device tensor of
+    frcnn_track_cut_workspace_bytes(frames) bytes, (frames + 1) signatures of 512 counters.  Nothing is carried in it between calls."""
+    _require_gpu()
+    n = int(_lib.load().frcnn_track_cut_workspace_bytes(int(frames)))
+    if n == 0:
+        raise _lib.FrcnnError("track_cut_workspace: frames=%r out of range (1..%d)" % (frames, _lib.TRACK_MAX_FRAMES))
+    return torch.empty(n // 4, dtype=torch.int32, device="cuda")
+
+
+def track_update_cut(state, mstate, frames_u8, frame_stride, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, radius=8, interval=1,
+                     pct=None, out=None, cuts=None, workspace=None):
+    """``track_update_interval`` (``interval`` 1: ``track_update_motion``) with the cut step in front of every frame (DESIGN §8 "Cut rule",
+    frcnn_track_update_cut): a frame whose 4 x 4-region luma histogram differs from that of the frame before -- for the call's first
+    frame: the kept frame of ``mstate``, when it is the frame before -- by ``pct`` percent (``track_cut_option``) of the largest distance
+    there is, is a hard cut, and every track ends in front of it: no id continues across it and no held row crosses it.  ``cuts``: an
+    int32 device tensor of F words, 1 where frame f is a cut; ``workspace``: ``track_cut_workspace(F)`` (both allocated here when None;
+    a captured call passes them).  Everything else as ``track_update_interval``.  -> (``out``, ``cuts``).  With no cut every byte of
+    ``state``, ``mstate`` and ``out`` is ``track_update_interval``'s.  Four launches per call and one per frame on top of those; the
+    call can be captured in a graph."""
+    _require_gpu()
+    base, stride, B, words = _track_packed(det_packed)
+    interval, pct = int(interval), track_cut_option(pct) if pct is None else int(pct)
+    F = int(out.shape[0]) if out is not None else int(frames_u8.shape[0]) if frames_u8.dim() > 1 else B * interval
+    if not _lib.TRACK_INTERVAL[0] <= interval <= _lib.TRACK_INTERVAL[1] or (F + interval - 1) // interval != B:
+        raise _lib.FrcnnError("track_update_cut: interval=%d (1..%d) and %d frames do not go with %d key frames' detections"
+                              % (interval, _lib.TRACK_INTERVAL[1], F, B))
+    _track_motion_args(mstate, frames_u8, frame_stride, F, h, w)
+    cap, rows, R, out = _track_update_args(state, n_frames, table, words, F, out)
+    if cuts is None:
+        cuts = torch.empty(F, dtype=torch.int32, device="cuda")
+    if workspace is None:
+        workspace = track_cut_workspace(F)
+    assert cuts.is_cuda and cuts.dtype == torch.int32 and cuts.is_contiguous() and cuts.numel() == F
+    assert workspace.is_cuda and workspace.dtype == torch.int32 and workspace.is_contiguous() and workspace.numel() >= 512 * (F + 1)
+    _lib.call("frcnn_track_update_cut", _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), F, _p(n_frames),
+              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), interval, int(h), int(w), _p(out), 4 + 8 * R,
+              pct, _p(workspace), _p(cuts), _stream())
+    return out, cuts
+
+
 TRACK_LOOKBACK = _lib.TRACK_LOOKBACK            # (smallest, largest, the default) look-back of ``track_lookback``, in frames
 
 

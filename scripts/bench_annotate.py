@@ -30,7 +30,8 @@ stream of the engine, so the figure includes what that ordering costs.  ``--dete
 without and with ``--detect_every 4``.  ``--track_backtrack`` (``run_track_backtrack``) runs the ``--detect_every 4`` leg without and with
 ``--track_backtrack`` at its default, and times the back-track call of one pass alone.  ``--track_lookback`` (``run_track_lookback``) runs the
 ``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
-look-back call of one pass alone.
+look-back call of one pass alone.  ``--track_scene_cut`` (``run_track_scene_cut``) runs the ``--track --track_motion 8`` leg without and with
+``--track_scene_cut`` at its default.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
@@ -430,6 +431,61 @@ def run_track_motion(name, cfg, n_frames, reps, content="noise"):
     return res
 
 
+def run_track_scene_cut(name, cfg, n_frames, reps, content="noise"):
+    """``--track_scene_cut``: what the cut rule costs on top of ``--track --track_motion 8``.  One pair of legs in ONE session, alternating
+    inside every repetition: ``run_track_motion``'s ``track_motion`` leg without and with ``track_scene_cut`` at its default (the tracker
+    is reset in front of every run).  Reports frames/s of both, their ratio, the tracker's state at the end and the cuts the last run
+    with the option saw (independent noise frames of this size differ by a small share of the largest distance: none is expected)."""
+    import numpy as np
+    from faster_rcnn_amd import entry, ops, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+    pct = ops.track_cut_option()
+    cuts = [0]
+    collect = eng.collect_batch
+
+    def counting(ticket):                                           # (the marks ride behind every frame's payload)
+        res = collect(ticket)
+        cuts[0] += sum(1 for r in res if len(r) > 3 and r[3].get("scene_cut"))
+        return res
+
+    eng.collect_batch = counting
+
+    def leg(**kw):
+        def run():
+            eng.track_reset()
+            cuts[0] = 0
+            return annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, track=TRACK_LEG, track_motion=MOTION_LEG, **kw)
+        return run
+
+    legs = {"track_motion": leg(), "track_scene_cut": leg(track_scene_cut=pct)}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    import torch
+    torch.cuda.synchronize()
+    state = eng.track_state().cpu().numpy()
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact": ["all", "blur", 12, 0], "track": list(TRACK_LEG), "track_motion": MOTION_LEG, "track_scene_cut": pct,
+           "images_per_pass": eng.batch, "in_flight": eng.in_flight, "cuts_seen": cuts[0],
+           "tracker": {"live_slots": int(state[0]), "ids_issued": int(state[1]), "overflow": int(state[2]), "frames": int(state[3])}}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["cut_over_motion"] = round(statistics.median(times["track_motion"]) / statistics.median(times["track_scene_cut"]), 3)
+    return res
+
+
 LOOKBACK_BIRTHS = 8                                      # births per frame of ``lookback_part_us``'s synthetic pass
 
 
@@ -692,6 +748,8 @@ def main():
                                                                 "with --detect_every 4, alternating in one session")
     ap.add_argument("--track_backtrack", action="store_true", help="instead of the legs above: the --detect_every 4 leg without and with "
                                                                    "--track_backtrack at its default, alternating in one session")
+    ap.add_argument("--track_scene_cut", action="store_true", help="instead of the legs above: the --track --track_motion 8 leg without and "
+                                                                   "with --track_scene_cut at its default, alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -700,6 +758,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.track_scene_cut:
+            out[name] = run_track_scene_cut(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.track_backtrack:
             out[name] = run_track_backtrack(name, PAIRS[name], args.frames, args.reps, args.content)
