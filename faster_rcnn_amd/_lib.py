@@ -430,6 +430,18 @@ TRACK_CUT_SIGNATURES = {
 # (FRCNN_TRACK_CUT_MIN_PCT / _MAX_PCT; the default is provisional: no threshold has been measured on real footage)
 TRACK_CUT_PCT = (1, 100, 40)
 
+TRACK_TRAILS_VERSION = 1        # include/ext/frcnn_hip_track_trails.h FRCNN_TRACK_TRAILS_VERSION
+TRACK_TRAILS_SIGNATURES = {
+    "frcnn_track_trails_version": (I, []),
+    "frcnn_track_trails_state_bytes": (c_size_t, [I, I]),
+    "frcnn_track_trails_list_words": (c_size_t, [I, I]),
+    "frcnn_track_trails_update": (I, [P, I, P, ctypes.c_longlong, I, I, P, P, I, I, I, I, P, P]),
+    "frcnn_track_trails_draw_u8": (I, [P, I, I, P, I, I, I, P]),
+}
+# the points a trail keeps and the width it is drawn with, each (smallest, largest, the default), and the largest expiry in frames
+# (FRCNN_TRACK_TRAILS_MIN_LENGTH / _MAX_LENGTH, 1 / _MAX_WIDTH, _MAX_EXPIRE)
+TRACK_TRAILS = ((2, 64, 16), (1, 9, 3), 4095)
+
 TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
 TRACK_LOOKBACK_SIGNATURES = {
     "frcnn_track_lookback_version": (I, []),
@@ -609,6 +621,15 @@ def load():
     if lib.frcnn_track_cut_version() != TRACK_CUT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_cut_version()} of the tracker's scene-cut extension, this binding "
                          f"{TRACK_CUT_VERSION} (include/ext/frcnn_hip_track_cut.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in TRACK_TRAILS_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_track_trails.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_track_trails_version() != TRACK_TRAILS_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_trails_version()} of the tracker's trail extension, this binding "
+                         f"{TRACK_TRAILS_VERSION} (include/ext/frcnn_hip_track_trails.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

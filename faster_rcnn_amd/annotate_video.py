@@ -83,6 +83,11 @@ of the largest distance there is starts a new scene -- no id is carried into it,
 between two detected frames nothing is shown behind a cut until the next detected frame.  A line ``scene cut: <path>`` is printed in front
 of that frame's lines; ``--tracks_out`` keeps its format.  Fades and dissolves are not detected.  Not together with ``--track_lookback``
 or ``--track_backtrack``: their backward chains would have to stop at a cut.
+``track_trails=(N, W)`` (``--track_trails [N]``, with ``--track`` in any of the forms above; 2..64 points, 16 when bare; ``--trail_width W``,
+1..9 pixels, default 3) draws the path every track took (ops.track_trails_update / ops.track_trails_draw_u8, csrc/track_trails.hip; DESIGN
+§8 "Trail rule"): the centre of every live tracked box joins the trail of its id, and each frame shows the last N points of the ids live
+in it as a line W pixels wide in the colour of the id, over the redaction and under the boxes and labels.  A trail ends where its id
+ends -- at a scene cut, or when the tracker gives the id up.  The printed lines and ``--tracks_out`` are unchanged.  Not with ``--no_draw``.
 """
 import collections
 import os
@@ -248,6 +253,7 @@ _EAGER_TABLES = {}
 _EAGER_REDACT_TABLES = {}
 _EAGER_TRACKERS = {}                                      # class mapping -> [state, {redact classes: table}, the one-frame count word]
 _EAGER_MOTION = {}                                        # (class mapping, h, w) -> that tracker's motion state for frames of the size
+_EAGER_TRAILS = {}                                        # (class mapping, N) -> that tracker's trail state for trails of N points
 
 
 def _names_by_index(class_mapping):
@@ -273,6 +279,15 @@ def _eager_motion_state(class_mapping, h, w):
     return m
 
 
+def _eager_trails_state(class_mapping, length):
+    """The eager path's trail state (ops.track_trails_state) of this class mapping's tracker for trails of ``length`` points."""
+    key = (tuple(sorted(class_mapping.items())), int(length))
+    t = _EAGER_TRAILS.get(key)
+    if t is None:
+        t = _EAGER_TRAILS[key] = ops.track_trails_state(min(2 * entry.TRACK_CAPACITY, ops.TRACK_MAX), length)
+    return t
+
+
 def _eager_track_table(tracker, class_mapping, redact_classes):
     table = tracker[1].get(redact_classes)
     if table is None:
@@ -284,15 +299,20 @@ def _eager_track_table(tracker, class_mapping, redact_classes):
     return table
 
 
-def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None):
+def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
+               track_trails=None, rgb=False):
     """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place.
     ``redact`` = (classes, mode, size, margin): one ops.redact_u8 in front of it; ``draw`` False: no drawing.
     ``track`` = (thr, hold, grow): one ops.track_update (one frame) in front of both, on this class mapping's eager tracker state
     (``reset_tracks`` empties it); ``dets`` is edited in place as ``collect_batch`` returns it: "track_id" on every det, the held rows
     appended with "held".  ``track_motion`` = R: ops.track_update_motion in its place, with the frame as it came and this class mapping's
     motion state for the frame's size.  ``track_scene_cut`` = PCT (with ``track_motion``): ops.track_update_cut with interval 1 in its
-    place -- the kept frame is the reference --, and ``info``, a dict, receives "scene_cut": True when the frame is a cut."""
+    place -- the kept frame is the reference --, and ``info``, a dict, receives "scene_cut": True when the frame is a cut.
+    ``track_trails`` = (N, W) (with ``track``, not with ``draw`` False): a one-frame ops.track_trails_update behind the tracker call, on
+    this class mapping's eager trail state, and one ops.track_trails_draw_u8 between the redaction and the drawing step; ``rgb``: the
+    frame's channel order (False: B, G, R)."""
     import torch
+    track_trails = _track_trails(track_trails, track, draw)
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     _track_scene_cut(track_scene_cut, track, track_motion, None, None)
@@ -333,6 +353,11 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
             if table is None:
                 table = _EAGER_REDACT_TABLES[(key, classes)] = ops.redact_table(_names_by_index(class_mapping), classes)
             ops.redact_u8(dev, rows, table, mode, size, margin, tracked=track is not None)
+        if track_trails is not None:
+            length, width = track_trails
+            lists = ops.track_trails_update(_eager_trails_state(class_mapping, length), rows.view(1, -1), tracker[2], length,
+                                            entry.DetectionEntry.track_trails_expire(track, None), frame.shape[0], frame.shape[1])
+            ops.track_trails_draw_u8(dev, lists[0], length, width, rgb=rgb)
         if draw:
             tables = _EAGER_TABLES.get(key)
             if tables is None:
@@ -538,6 +563,36 @@ def _track_scene_cut(track_scene_cut, track, track_motion, track_lookback, track
     return ops.track_cut_option(track_scene_cut)
 
 
+def track_trails_from_args(args):
+    """(host only) The trails the command line asks for -> (N, W) as ``submit_batch(track_trails=...)`` takes it (N = ops.TRACK_TRAILS[0][2]
+    = 16 for a bare ``--track_trails``, W = ``--trail_width`` or 3), or None without the flag.  ValueError, with the reason, for
+    ``--trail_width`` without ``--track_trails``, ``--track_trails`` without ``--track`` or with ``--no_draw``, and for an N outside 2..64
+    or a W outside 1..9."""
+    if args.track_trails is None:
+        if args.trail_width is not None:
+            raise ValueError("--trail_width=%s is the width the trails are drawn with: it needs --track_trails" % args.trail_width)
+        return None
+    if not args.track:
+        raise ValueError("--track_trails=%s draws the paths of the tracker's ids: it needs --track" % args.track_trails)
+    if args.no_draw:
+        raise ValueError("--track_trails together with --no_draw is not supported: a run that draws nothing draws no trails")
+    try:
+        return ops.track_trails_option((args.track_trails, args.trail_width))
+    except ValueError as e:
+        raise ValueError("--track_trails / --trail_width: %s" % e) from None
+
+
+def _track_trails(track_trails, track, draw):
+    """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame``'s ``track_trails`` checked -> (N, W), or None."""
+    if track_trails is None:
+        return None
+    if track is None:
+        raise ValueError("track_trails=%r draws the paths of the tracker's ids: it needs track=(thr, hold, grow)" % (track_trails,))
+    if not draw:
+        raise ValueError("track_trails=%r together with draw=False is not supported: a run that draws nothing draws no trails" % (track_trails,))
+    return ops.track_trails_option(track_trails)
+
+
 def _lookback_frames(track_lookback, track, eng, B):
     """``annotate_images`` / ``annotate_stream``'s ``track_lookback`` checked -> the look-back of their passes, or None."""
     if track_lookback is None:
@@ -584,6 +639,9 @@ def reset_tracks(training_manager, detector, in_flight=1):
         for k, mstate in _EAGER_MOTION.items():
             if k[0] == key:
                 ops.track_motion_reset(mstate)
+        for k, trails in _EAGER_TRAILS.items():
+            if k[0] == key:
+                ops.track_reset(trails)
 
 
 def _print_drawn(dets, width, height):
@@ -593,14 +651,17 @@ def _print_drawn(dets, width, height):
 
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
-                        frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None):
+                        frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
+                        track_trails=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
     ``tracks_out``: a text file that receives the frame's MOT lines under the number ``frame_no``.  ``track_motion`` = R (with
     ``track``): the tracks' boxes are first moved with the pixels under them, at most R pixels either way (DESIGN §8 "Motion rule").
     ``track_scene_cut`` = PCT (with ``track_motion``): every track ends when the frame is a hard cut against the frame before it (DESIGN
-    §8 "Cut rule"); a line ``scene cut: <frame_no>`` is then printed in front of the frame's lines."""
+    §8 "Cut rule"); a line ``scene cut: <frame_no>`` is then printed in front of the frame's lines.
+    ``track_trails`` = (N, W) (with ``track``): the path of every id live in the frame is drawn, its last N points, W pixels wide (DESIGN
+    §8 "Trail rule"); the frames before this one are the calls before this one."""
     if detect_every is not None:
         raise ValueError("detect_every=%r runs the detector once per pass of several frames: get_annotated_frame detects its one frame and "
                          "cannot; use annotate_images or annotate_stream" % (detect_every,))
@@ -615,6 +676,9 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     motion = {} if track_motion is None else {"track_motion": track_motion}
     if _track_scene_cut(track_scene_cut, track, track_motion, None, None) is not None:
         motion["track_scene_cut"] = track_scene_cut
+    trails = _track_trails(track_trails, track, draw)
+    if trails is not None:
+        motion["track_trails"] = trails
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1)
     info = {}
@@ -1034,7 +1098,8 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 
 
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
-              tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None):
+              tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
+              track_trails=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
@@ -1049,6 +1114,9 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
                                                                 track_scene_cut)
         if track_scene_cut is not None:                   # (the eager path: one frame at a time against the kept frame)
             motion["track_scene_cut"] = track_scene_cut
+        trails = _track_trails(track_trails, track, draw)
+        if trails is not None:
+            motion["track_trails"] = tracking["track_trails"] = trails
         if track is not None:                             # a new sequence; its frames are submitted in input order, as every list's are
             reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
         if eng is None:
@@ -1085,13 +1153,13 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
-                    track_backtrack=None, track_scene_cut=None):
+                    track_backtrack=None, track_scene_cut=None, track_trails=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails``: as ``annotate_images``."""
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
     if isinstance(writer_or_out_dir, y4m.Y4mWriter):
         make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma)
@@ -1100,13 +1168,13 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                                       jpeg_huffman)
     _annotate(training_manager, detector, source, lambda prepare, ahead: _loaded_stream(source, prepare, ahead), make_sink, resize_min, resize_max,
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
-              detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut)
+              detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
-                    track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None):
+                    track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1150,7 +1218,11 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     whose 4 x 4-region luma histogram differs from the frame before by that share of the largest distance there is, is a hard cut (DESIGN
     §8 "Cut rule"): every track ends in front of it, so no id is inherited by the new scene and no held box of the old scene is redacted
     in it; between two detected frames nothing is shown behind a cut until the next detected frame.  A line ``scene cut: <path>`` is
-    printed in front of that frame's lines.  A fade or a dissolve is not detected.  None: every byte and line is what it was."""
+    printed in front of that frame's lines.  A fade or a dissolve is not detected.  None: every byte and line is what it was.
+    ``track_trails``: (N, W) as ``track_trails_from_args`` returns it (with ``track``, in every form above; not with ``draw`` False) -- the
+    path of every id is kept on the device and each frame shows the last N points of the ids live in it as a line W pixels wide in the
+    colour of the id (DESIGN §8 "Trail rule"), over the redaction and under the boxes; a delayed pass draws them in the order its frames
+    are emitted.  The printed lines and ``tracks_out`` are unchanged.  None: every byte and line is what it was."""
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
@@ -1162,7 +1234,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     _annotate(training_manager, detector, ((path, _Frame(_read_rgb(path))) for path in paths),
               lambda prepare, ahead: _loaded_files(paths, lambda path: prepare(path, _load_frame(path, device_decode, device_png)), ahead),
               make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
-              track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut)
+              track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
+              track_trails=track_trails)
 
 
 def build_parser():
@@ -1261,6 +1334,12 @@ def build_parser():
                         "for) starts a new scene -- no id is carried into it and no held box of the old scene is redacted in it; a line "
                         "'scene cut: <path>' is printed in front of that frame's lines; fades and dissolves are not detected (needs --track "
                         "--track_motion; with or without --detect_every; not with --track_lookback or --track_backtrack)")
+    p.add_argument("--track_trails", dest="track_trails", type=int, nargs="?", const=ops.TRACK_TRAILS[0][2], default=None, metavar="N",
+                   help="draw the path of every track: the last N centres of its box (2..64; bare: 16) as a line in the colour of its id, "
+                        "over the redaction and under the boxes; a trail ends where its id ends (needs --track; with every tracking option; "
+                        "not with --no_draw)")
+    p.add_argument("--trail_width", dest="trail_width", type=int, default=None, metavar="W",
+                   help="the width of the trails in pixels, 1..9 (default 3; needs --track_trails)")
     p.add_argument("--tracks_out", dest="tracks_out", default=None, metavar="PATH",
                    help="write the tracks as MOTChallenge lines frame,id,left,top,width,height,prob,cls,-1,-1 (needs --track)")
     return p
@@ -1339,6 +1418,9 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     track_scene_cut = track_scene_cut_from_args(args)
     if track_scene_cut is not None:
         tracking["track_scene_cut"] = track_scene_cut
+    track_trails = track_trails_from_args(args)
+    if track_trails is not None:
+        tracking["track_trails"] = track_trails
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

@@ -312,10 +312,12 @@ class PassSpec:
     detect_every: object = None
     track_backtrack: object = None
     track_scene_cut: object = None
+    track_trails: object = None
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
-                track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None):
+                track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
+                track_trails=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -361,6 +363,13 @@ class PassSpec:
                 raise FrcnnError("submit_batch: track_scene_cut= needs the device-side preprocess: a foreign preprocess_func uploads float "
                                  "pixels, and the cut rule reads the uint8 pixels of every source frame")
             track_scene_cut = engine.track_scene_cut_option(track_scene_cut)
+        if track_trails is not None:
+            if track is None:
+                raise FrcnnError("submit_batch: track_trails= draws the paths of the tracker's ids: pass track=(thr, hold, grow) too")
+            if not draw:
+                raise FrcnnError("submit_batch: track_trails= together with draw=False is not supported: a pass that draws nothing draws "
+                                 "no trails")
+            track_trails = engine.track_trails_option(track_trails)
         if redact is not None:
             redact = engine.redact_option(redact)
         jpeg_mode, y4m_mode = JPEG_MODE, Y4M_MODE
@@ -395,7 +404,7 @@ class PassSpec:
             raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
-                   track_scene_cut=track_scene_cut)
+                   track_scene_cut=track_scene_cut, track_trails=track_trails)
 
     @property
     def delayed(self):
@@ -429,6 +438,8 @@ class PassSpec:
                            ("backtrack", self.track_backtrack), ("cut", self.track_scene_cut)):
             if value is not None:
                 key = key + (tag, value)
+        if self.track_trails is not None:
+            key = key + ("trails",) + self.track_trails
         return key
 
 
@@ -444,7 +455,7 @@ class _Slot:
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
                  "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
                  "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
-                 "track_scene_cut", "cut_ws", "cuts", "cuts_pin", "_cuts_raw")
+                 "track_scene_cut", "cut_ws", "cuts", "cuts_pin", "_cuts_raw", "track_trails", "trail_lists")
 
     def __init__(self):
         for name in self.__slots__:
@@ -593,6 +604,7 @@ class DetectionEntry:
         self._nodraw_tables = None
         self._redact_tables = {}
         self._track_state = None                         # the engine's ONE tracker state (ops.track_state): its pointer is in the graphs
+        self._track_trails_states = {}                   # length N -> the engine's trail state (ops.track_trails_state) beside the tracker state
         self._track_tables = {}
         self._track_motion_states = {}                   # (h, w) of the source frames -> ops.track_motion_state: their pointers are in the graphs
         self._track_lookback_windows = {}                # (h, w, B) -> ops.track_lookback_state: the frames tracked but not yet emitted
@@ -656,6 +668,33 @@ class DetectionEntry:
             self._track_state = ops.track_state(cap)
         return self._track_state
 
+    def track_trails_state(self, length):
+        """The engine's trail state for trails of ``length`` points (device int32, ops.track_trails_state), made on first use, of
+        ``track_trails_capacity()`` trails.  ``track_reset()`` empties it."""
+        state = self._track_trails_states.get(length)
+        if state is None:
+            state = self._track_trails_states[length] = ops.track_trails_state(self.track_trails_capacity(), length)
+        return state
+
+    def track_trails_capacity(self):
+        """The trails of the engine's trail state: twice the tracker's slots, at most ops.TRACK_MAX.  A trail outlives its track by a
+        frame, and behind a scene cut the old scene's trails wait for their expiry while every slot already has a new id."""
+        return min(2 * ops.track_capacity(self.track_state()), ops.TRACK_MAX)
+
+    @staticmethod
+    def track_trails_option(value):
+        """``submit_batch``'s ``track_trails`` checked -> (N, W).  FrcnnError with the reason."""
+        try:
+            return ops.track_trails_option(value)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: track_trails=%r: %s" % (value, e)) from None
+
+    @staticmethod
+    def track_trails_expire(track, detect_every):
+        """The frames a trail outlives its last point in a pass with ``track`` = (thr, hold, grow): (hold + 1) * K, K = ``detect_every``
+        or 1 -- as long as the tracker can still re-match the id -- and at most the rule's 4095."""
+        return min((track[1] + 1) * (detect_every or 1), ops.TRACK_TRAILS[2])
+
     def track_reset(self):
         """Forget every track: the state is zeroed on the tracking stream, behind the tracked passes submitted so far."""
         state = self.track_state()
@@ -665,6 +704,8 @@ class DetectionEntry:
                 ops.track_motion_reset(mstate)
             for window, _ in self._track_lookback_windows.values():  # ... and no frame waits to be emitted
                 ops.track_lookback_reset(window)
+            for trails in self._track_trails_states.values():       # ... and no path has begun
+                ops.track_reset(trails)
         self._lookback_waiting.clear()
         self._lookback_last = None
 
@@ -846,6 +887,13 @@ class DetectionEntry:
             t_motion = self.track_motion_state(in_h, in_w) if s.track_motion else None
             if s.track_scene_cut:
                 s.cut_ws, s.cuts = ops.track_cut_workspace(F), torch.zeros(F, dtype=torch.int32, device="cuda")
+            if s.track_trails:
+                # ONE trail update behind the tracker call (behind the look-back / back-track call of a delayed pass) over the tracked
+                # buffers the drawing step reads, then each frame's trails drawn over its redaction and under its boxes
+                tr_length, tr_width = s.track_trails
+                tr_state, tr_expire = self.track_trails_state(tr_length), self.track_trails_expire(s.track, s.every)
+                s.trail_lists = ops.track_trails_workspace(F, self.track_trails_capacity(), tr_length)
+                trails_rgb = src is not None and bool(int(flip) & 2)        # (the channel order the frames were uploaded in: ``uploaded_rgb``)
         if s.track_lookback:
             # the frames, as uploaded, and their tracked buffers then join the engine's window, the new tracks are followed back through
             # it, and the frames of the pass BEFORE come out: everything behind this point edits and encodes those (``out``), with their
@@ -926,10 +974,20 @@ class DetectionEntry:
                         else:
                             ops.track_lookback(lb_window, s.io_dev, seg, s.track_out, s.n_frames_dev, ops.track_capacity(t_state), lb_back, in_h,
                                                in_w, s.track_lookback, s.track_motion or 0, t_grow, out=s.lb_out)
+                    if s.track_trails:
+                        if s.track_lookback:
+                            # the emitted buffers, and the emitted count for their ``n_frames`` word; the pass's own count is the gate: a
+                            # warm-up run (0 frames) emits what the window holds once more, and those are no new frames
+                            ops.track_trails_update(tr_state, s.lb_out[1], s.lb_out[2], tr_length, tr_expire, in_h, in_w, lists=s.trail_lists,
+                                                    gate=s.n_frames_dev)
+                        else:
+                            ops.track_trails_update(tr_state, s.track_out, s.n_frames_dev, tr_length, tr_expire, in_h, in_w, lists=s.trail_lists)
                 for i in range(F):
                     rows = s.lb_out[1][i] if s.track_lookback else s.track_out[i] if s.track else packed[i] if B > 1 else packed
                     if s.redact:
                         ops.redact_u8(out[i], rows, r_table, r_mode, r_size, r_margin, workspace=s.redact_ws, tracked=bool(s.track))
+                    if s.track_trails:
+                        ops.track_trails_draw_u8(out[i], s.trail_lists[i], tr_length, tr_width, rgb=trails_rgb)
                     ops.annotate_u8(out[i], rows, tables, tracked=bool(s.track))
                     if s.encode == Y4M_ENCODE:
                         continue                                    # (all B frames in one launch behind the loop)
@@ -998,7 +1056,7 @@ class DetectionEntry:
             s.redact, s.nodraw, s.track, s.track_motion = spec.redact, (None if spec.draw else True), spec.track, spec.track_motion
             s.track_lookback, s.track_backtrack = spec.track_lookback or spec.track_backtrack, spec.track_backtrack      # (both: the delayed path is one)
             s.every, s.frames = spec.detect_every, B * (spec.detect_every or 1)
-            s.track_scene_cut = spec.track_scene_cut
+            s.track_scene_cut, s.track_trails = spec.track_scene_cut, spec.track_trails
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -1232,7 +1290,7 @@ class DetectionEntry:
 
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
-                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None):
+                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1301,10 +1359,20 @@ class DetectionEntry:
         next key frame.  Every result of such a pass carries one more element behind its payload, a dict: {"scene_cut": True} for a frame
         that is a cut, {} else.  Refused by name without ``track_motion``, together with ``track_lookback`` or ``track_backtrack`` (their
         backward chains would have to stop at a cut) and on an engine whose foreign preprocess uploads float pixels.  Without it every
-        key and byte is what it was."""
+        key and byte is what it was.
+        ``track_trails`` = (N, W) (tracking passes only, every form of them; ("trails", N, W) appended behind all the tags above; N 2..64
+        points, W 1..9 pixels, an integer N or None in either place: ops.track_trails_option's defaults 16 and 3): the trail rule (DESIGN §8
+        "Trail rule") draws the path of every id: one ops.track_trails_update behind the tracker call -- in a delayed pass behind the
+        look-back / back-track call, over the EMITTED buffers and their count -- appends the centre of every live tracked row to the trail
+        of its id in the engine's trail state (``track_trails_state``, emptied by ``track_reset()``), and each frame's trails are drawn
+        (ops.track_trails_draw_u8) over its redaction and under its boxes and labels, in the colour of the id, the highest id on top.  A
+        trail leaves (hold + 1) * K frames behind its last point (``track_trails_expire``), K = ``detect_every`` or 1.  The results are
+        what they are without it: only the frames' bytes change.  Refused by name without ``track`` and with ``draw`` False; as every
+        annotating pass, on an engine with a foreign preprocess.  Without it every key and byte is what it was."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
-                                detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut)
+                                detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
+                                track_trails=track_trails)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush

@@ -1520,6 +1520,95 @@ def track_update_cut(state, mstate, frames_u8, frame_stride, det_packed, n_frame
     return out, cuts
 
 
+TRACK_TRAILS = _lib.TRACK_TRAILS                # ((smallest, largest, default) length N, the same of the width W, the largest expire)
+
+
+def track_trails_option(value=None):
+    """(host only) The trail option checked -> (N, W): N the points a trail keeps, 2..64, W the width it is drawn with, 1..9.  ``value``:
+    None (the defaults, 16 and 3), an integer N, or a pair (N, W) either of which may be None.  ValueError with the reason."""
+    (n_lo, n_hi, n_def), (w_lo, w_hi, w_def), _ = TRACK_TRAILS
+    if value is None or isinstance(value, (int, np.integer)):
+        value = (value, None)
+    try:
+        n, wd = value
+    except (TypeError, ValueError):
+        raise ValueError("track trails=%r: N, or (N, W)" % (value,)) from None
+    n, wd = n_def if n is None else n, w_def if wd is None else wd
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not n_lo <= int(n) <= n_hi:
+        raise ValueError("track trails length=%r: an integer in %d..%d (points)" % (n, n_lo, n_hi))
+    if isinstance(wd, bool) or not isinstance(wd, (int, np.integer)) or not w_lo <= int(wd) <= w_hi:
+        raise ValueError("track trails width=%r: an integer in %d..%d (pixels)" % (wd, w_lo, w_hi))
+    return int(n), int(wd)
+
+
+def _track_trails_words(capacity, length):
+    n = int(_lib.load().frcnn_track_trails_list_words(int(capacity), int(length)))
+    if n == 0:
+        raise _lib.FrcnnError("track trails: capacity=%r not in [1, %d] or length=%r not in [%d, %d]"
+                              % (capacity, TRACK_MAX, length, TRACK_TRAILS[0][0], TRACK_TRAILS[0][1]))
+    return n
+
+
+def track_trails_state(capacity, length):
+    """An empty trail state of ``capacity`` trails of ``length`` points: a zeroed int32 device tensor of frcnn_track_trails_state_bytes / 4
+    words, [n_entries, frames, dropped, 0 | per entry: id, cls, last_seen, n, pts[length][2]] (include/ext/frcnn_hip_track_trails.h).
+    Zeroing it (``track_reset``) empties it."""
+    _require_gpu()
+    return torch.zeros(_track_trails_words(capacity, length), dtype=torch.int32, device="cuda")
+
+
+def track_trails_workspace(frames, capacity, length):
+    """The point lists of a ``track_trails_update`` call of ``frames`` frames: an int32 device tensor (frames, list words), a list
+    [n_trails, 0, 0, 0 | per trail: id, cls, n, 0, pts[length][2]].  Every word is written by every call."""
+    _require_gpu()
+    if not 1 <= int(frames) <= _lib.TRACK_MAX_FRAMES:
+        raise _lib.FrcnnError("track_trails_workspace: frames=%r out of range (1..%d)" % (frames, _lib.TRACK_MAX_FRAMES))
+    return torch.empty((int(frames), _track_trails_words(capacity, length)), dtype=torch.int32, device="cuda")
+
+
+def track_trails_update(state, tracked, n_frames, length, expire, h, w, capacity=None, lists=None, gate=None):
+    """Steps 1-4 of the trail rule (DESIGN §8 "Trail rule", frcnn_track_trails_update) over the frames of ``tracked`` IN ORDER, in one
+    launch: ``tracked`` is a (frames, 4 + 8 rows) int32 tensor of tracked buffers -- ``track_update``'s ``out``, or the widened buffers a
+    look-back emits --, ``n_frames`` the device word that says how many of them are real.  The centre of every live tracked row joins
+    the trail of its id in ``state`` (``track_trails_state``; ``capacity``: its trails, read from its size when None), trails not seen
+    for more than ``expire`` frames leave, and frame f's point list lands in ``lists[f]`` (``track_trails_workspace``; allocated here
+    when None; a captured call passes it) -> ``lists``.  ``gate``: None, or a device word that is 0 when no frame of the call is real,
+    whatever ``n_frames`` says (a pass whose ``n_frames`` is the count a look-back emitted passes its own frame count: a warm-up
+    replay emits the same frames again).  The call can be captured in a graph."""
+    _require_gpu()
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.dim() == 2 and tracked.is_contiguous()
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert gate is None or (gate.is_cuda and gate.dtype == torch.int32 and gate.numel() >= 1)
+    length = int(length)
+    if capacity is None:
+        capacity = (int(state.numel()) - 4) // (4 + 2 * max(length, 1))
+    frames, words = int(tracked.shape[0]), int(tracked.shape[1])
+    assert (words - 4) % 8 == 0
+    if lists is None:
+        lists = track_trails_workspace(frames, capacity, length)
+    assert int(state.numel()) == _track_trails_words(capacity, length)
+    assert lists.is_cuda and lists.dtype == torch.int32 and lists.is_contiguous() and tuple(lists.shape) == (frames, int(state.numel()))
+    _lib.call("frcnn_track_trails_update", _p(state), int(capacity), _p(tracked), words, (words - 4) // 8, frames, _p(n_frames), _p(gate), length,
+              int(expire), int(h), int(w), _p(lists), _stream())
+    return lists
+
+
+def track_trails_draw_u8(frame, plist, length, width=None, rgb=False):
+    """DRAW of the trail rule (frcnn_track_trails_draw_u8): the trails of ``plist`` -- one point list of ``track_trails_update`` -- drawn
+    into ``frame``, an (h, w, 3) uint8 device tensor, edited in place and returned: a capsule of ``width`` pixels (None: 3) around every
+    segment, in the colour of the trail's id, the highest id on top.  ``rgb``: the frame's bytes are R, G, B (False: B, G, R, as the
+    encoders' ``bgr=True``).  One launch; reads the list's count from device memory, so the call can be captured in a graph."""
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert plist.is_cuda and plist.dtype == torch.int32 and plist.dim() == 1 and plist.is_contiguous()
+    length, width = int(length), TRACK_TRAILS[1][2] if width is None else int(width)
+    assert int(plist.numel()) >= 4 and (int(plist.numel()) - 4) % (4 + 2 * max(length, 1)) == 0
+    _lib.call("frcnn_track_trails_draw_u8", _p(frame), int(frame.shape[0]), int(frame.shape[1]), _p(plist), length, width, int(bool(rgb)),
+              _stream())
+    return frame
+
+
 TRACK_LOOKBACK = _lib.TRACK_LOOKBACK            # (smallest, largest, the default) look-back of ``track_lookback``, in frames
 
 
