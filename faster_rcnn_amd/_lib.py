@@ -442,6 +442,21 @@ TRACK_TRAILS_SIGNATURES = {
 # (FRCNN_TRACK_TRAILS_MIN_LENGTH / _MAX_LENGTH, 1 / _MAX_WIDTH, _MAX_EXPIRE)
 TRACK_TRAILS = ((2, 64, 16), (1, 9, 3), 4095)
 
+HEAT_VERSION = 1                # include/ext/frcnn_hip_heat.h FRCNN_HEAT_VERSION
+HEAT_SIGNATURES = {
+    "frcnn_heat_version": (I, []),
+    "frcnn_heat_state_bytes": (c_size_t, [I, I]),
+    "frcnn_heat_update": (I, [P, I, I, P, I, I, P, I, I, I, P, P, P]),
+    "frcnn_heat_draw_u8": (I, [P, I, I, P, I, I, P]),
+}
+# (smallest, largest, the default) alpha and decay (1 / 255 / FRCNN_HEAT_DEFAULT_ALPHA, 0 / FRCNN_HEAT_MAX_DECAY / 0), the value a pixel stops
+# at (FRCNN_HEAT_MAX), the frame indices of a call (FRCNN_HEAT_MAX_FRAMES) and the update kernel's tile (FRCNN_HEAT_TILE_W, _TILE_H)
+HEAT_ALPHA = (1, 255, 160)
+HEAT_DECAY = (0, 15, 0)
+HEAT_MAX = 1 << 30
+HEAT_MAX_FRAMES = 65536
+HEAT_TILE = (64, 16)
+
 TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
 TRACK_LOOKBACK_SIGNATURES = {
     "frcnn_track_lookback_version": (I, []),
@@ -630,6 +645,15 @@ def load():
     if lib.frcnn_track_trails_version() != TRACK_TRAILS_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_trails_version()} of the tracker's trail extension, this binding "
                          f"{TRACK_TRAILS_VERSION} (include/ext/frcnn_hip_track_trails.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in HEAT_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_heat.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_heat_version() != HEAT_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_heat_version()} of the heat-map extension, this binding "
+                         f"{HEAT_VERSION} (include/ext/frcnn_hip_heat.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

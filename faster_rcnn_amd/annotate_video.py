@@ -88,6 +88,14 @@ or ``--track_backtrack``: their backward chains would have to stop at a cut.
 §8 "Trail rule"): the centre of every live tracked box joins the trail of its id, and each frame shows the last N points of the ids live
 in it as a line W pixels wide in the colour of the id, over the redaction and under the boxes and labels.  A trail ends where its id
 ends -- at a scene cut, or when the tracker gives the id up.  The printed lines and ``--tracks_out`` are unchanged.  Not with ``--no_draw``.
+``heatmap=(classes, A, S)`` (``--heatmap CLASSES``, class names of the active mapping or ``all``; ``--heatmap_alpha A``, 1..255, default 160;
+``--heatmap_decay S``, 0..15, default 0 = none) shows where the objects of those classes have been over the whole list (ops.heat_update /
+ops.heat_draw_u8, csrc/heat.hip; DESIGN §8 "Heat rule"): every pixel of a map on the device gains 256 per box that covers it in every frame
+-- every detection, or with ``--track`` the live tracked rows; held and back-filled boxes are guesses and do not count -- loses
+ceil(v / 2^S) per frame, and is blended into each frame over the redaction and under the trails, boxes and labels, black through red and
+yellow to white at the hottest pixel.  ``annotate_images`` / ``annotate_stream`` start with a cold map, ``get_annotated_frame`` continues
+the map of the calls before it (``reset_heat`` starts anew).  ``heatmap_out=PATH.png`` (``--heatmap_out``) writes the map at the end of
+the list as an 8-bit grey PNG, one per frame size met (``PATH_<w>x<h>.png`` when there are several).  With every other option.
 """
 import collections
 import os
@@ -254,6 +262,7 @@ _EAGER_REDACT_TABLES = {}
 _EAGER_TRACKERS = {}                                      # class mapping -> [state, {redact classes: table}, the one-frame count word]
 _EAGER_MOTION = {}                                        # (class mapping, h, w) -> that tracker's motion state for frames of the size
 _EAGER_TRAILS = {}                                        # (class mapping, N) -> that tracker's trail state for trails of N points
+_EAGER_HEAT = {}                                          # (class mapping, h, w) -> the eager path's heat state for frames of the size
 
 
 def _names_by_index(class_mapping):
@@ -288,6 +297,15 @@ def _eager_trails_state(class_mapping, length):
     return t
 
 
+def _eager_heat_state(class_mapping, h, w):
+    """The eager path's heat state (ops.heat_state) of this class mapping for (h, w) frames, made on first use."""
+    key = (tuple(sorted(class_mapping.items())), int(h), int(w))
+    m = _EAGER_HEAT.get(key)
+    if m is None:
+        m = _EAGER_HEAT[key] = ops.heat_state(h, w)
+    return m
+
+
 def _eager_track_table(tracker, class_mapping, redact_classes):
     table = tracker[1].get(redact_classes)
     if table is None:
@@ -300,7 +318,7 @@ def _eager_track_table(tracker, class_mapping, redact_classes):
 
 
 def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
-               track_trails=None, rgb=False):
+               track_trails=None, rgb=False, heatmap=None):
     """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place.
     ``redact`` = (classes, mode, size, margin): one ops.redact_u8 in front of it; ``draw`` False: no drawing.
     ``track`` = (thr, hold, grow): one ops.track_update (one frame) in front of both, on this class mapping's eager tracker state
@@ -310,14 +328,18 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     place -- the kept frame is the reference --, and ``info``, a dict, receives "scene_cut": True when the frame is a cut.
     ``track_trails`` = (N, W) (with ``track``, not with ``draw`` False): a one-frame ops.track_trails_update behind the tracker call, on
     this class mapping's eager trail state, and one ops.track_trails_draw_u8 between the redaction and the drawing step; ``rgb``: the
-    frame's channel order (False: B, G, R)."""
+    frame's channel order (False: B, G, R).
+    ``heatmap`` = (classes, A, S): a one-frame ops.heat_update on this class mapping's eager heat state for the frame's size (``reset_heat``
+    empties it) -- the detections, or with ``track`` the live tracked rows -- and one ops.heat_draw_u8 between the redaction and the
+    trails; a frame without detections is blended too."""
     import torch
     track_trails = _track_trails(track_trails, track, draw)
+    heatmap = _heatmap(heatmap)
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     _track_scene_cut(track_scene_cut, track, track_motion, None, None)
     key = tuple(sorted(class_mapping.items()))
-    if track is not None or (dets and (draw or redact is not None)):      # (nothing to draw or hide: the frame stays as it is)
+    if track is not None or heatmap is not None or (dets and (draw or redact is not None)):      # (nothing to draw or hide: the frame stays as it is)
         dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
         packed = torch.from_numpy(_pack_dets(dets, class_mapping)).cuda()
         classes = None
@@ -353,6 +375,14 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
             if table is None:
                 table = _EAGER_REDACT_TABLES[(key, classes)] = ops.redact_table(_names_by_index(class_mapping), classes)
             ops.redact_u8(dev, rows, table, mode, size, margin, tracked=track is not None)
+        if heatmap is not None:
+            h_classes, h_alpha, h_decay = heatmap
+            h_table = _EAGER_REDACT_TABLES.get((key, h_classes))
+            if h_table is None:
+                h_table = _EAGER_REDACT_TABLES[(key, h_classes)] = ops.redact_table(_names_by_index(class_mapping), h_classes)
+            h_state = _eager_heat_state(class_mapping, frame.shape[0], frame.shape[1])
+            ops.heat_update(h_state, frame.shape[0], frame.shape[1], rows, h_table, h_decay, tracked=track is not None)
+            ops.heat_draw_u8(dev, h_state, h_alpha, rgb=rgb)
         if track_trails is not None:
             length, width = track_trails
             lists = ops.track_trails_update(_eager_trails_state(class_mapping, length), rows.view(1, -1), tracker[2], length,
@@ -593,6 +623,91 @@ def _track_trails(track_trails, track, draw):
     return ops.track_trails_option(track_trails)
 
 
+def heatmap_from_args(args, class_mapping):
+    """(host only) The heat map the command line asks for -> ((classes, A, S) as ``submit_batch(heat=...)`` takes it, the path of
+    ``--heatmap_out`` or None), or (None, None) without ``--heatmap``.  classes: "all", or the tuple of names (of ``class_mapping``, the
+    active one) in the order given.  ValueError, with the reason, for ``--heatmap_alpha`` / ``--heatmap_decay`` / ``--heatmap_out`` without
+    ``--heatmap``, an unknown class name, an A outside 1..255, an S outside 0..15 and a ``--heatmap_out`` that does not end in .png."""
+    if args.heatmap is None:
+        for flag, value in (("--heatmap_alpha", args.heatmap_alpha), ("--heatmap_decay", args.heatmap_decay), ("--heatmap_out", args.heatmap_out)):
+            if value is not None:
+                raise ValueError("%s=%s is a setting of the heat map: it needs --heatmap CLASSES" % (flag, value))
+        return None, None
+    names = [n.strip() for n in args.heatmap.split(",") if n.strip()]
+    if not names:
+        raise ValueError("--heatmap takes comma-separated class names, or all")
+    try:
+        classes = "all" if names == ["all"] else ops.redact_class_list(_names_by_index(class_mapping), names)
+        heat = ops.heat_option(classes, args.heatmap_alpha, args.heatmap_decay)
+    except ValueError as e:
+        raise ValueError("--heatmap / --heatmap_alpha / --heatmap_decay: %s" % e) from None
+    return heat, _heatmap_out(args.heatmap_out, heat)
+
+
+def _heatmap(heatmap):
+    """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame``'s ``heatmap`` checked -> (classes, A, S), or None."""
+    if heatmap is None:
+        return None
+    try:
+        classes, alpha, decay = () if isinstance(heatmap, str) else heatmap
+    except (TypeError, ValueError):
+        raise ValueError("heatmap=%r: (classes, alpha, decay)" % (heatmap,)) from None
+    return ops.heat_option(classes, alpha, decay)
+
+
+def _heatmap_out(heatmap_out, heatmap):
+    """``heatmap_out`` checked against ``heatmap`` -> the path, or None."""
+    if heatmap_out is None:
+        return None
+    if heatmap is None:
+        raise ValueError("heatmap_out=%r is where the heat map is written: it needs heatmap=(classes, alpha, decay)" % (heatmap_out,))
+    if not str(heatmap_out).lower().endswith(".png"):
+        raise ValueError("heatmap_out=%r: the map is written as an 8-bit grey PNG, a path that ends in .png" % (heatmap_out,))
+    return str(heatmap_out)
+
+
+def heatmap_paths(path, sizes):
+    """(host only) ``--heatmap_out``'s files for the frame sizes ``sizes`` ((h, w) each) -> {(h, w): path}: ``path`` itself for one size,
+    ``<stem>_<w>x<h>.png`` for each of several."""
+    sizes = sorted(sizes)
+    if len(sizes) <= 1:
+        return {hw: path for hw in sizes}
+    return {(h, w): "%s_%dx%d%s" % (path[:-4], w, h, path[-4:]) for h, w in sizes}
+
+
+def write_heatmaps(path, states):
+    """``states``: {(h, w): a heat state's host copy (numpy)}.  Every size that saw a frame is written as an 8-bit grey PNG of the draw
+    step's t values (ops.heat_levels) with PIL -> the paths written."""
+    from PIL import Image as PilImage
+    met = {hw: st for hw, st in states.items() if int(st[0]) > 0}
+    paths = heatmap_paths(path, met)
+    for (h, w), out in paths.items():
+        PilImage.fromarray(ops.heat_levels(met[(h, w)], h, w), mode="L").save(out)
+    return [paths[hw] for hw in sorted(paths)]
+
+
+def _heat_states(training_manager, eng):
+    """The host copies of the heat states of ``eng``, or of the eager path with None: {(h, w): numpy int32}."""
+    import torch
+    torch.cuda.synchronize()
+    if eng is not None:
+        return {hw: st.cpu().numpy() for hw, st in eng._heat_states.items()}
+    key = tuple(sorted(training_manager.class_mapping.items()))
+    return {(k[1], k[2]): st.cpu().numpy() for k, st in _EAGER_HEAT.items() if k[0] == key}
+
+
+def reset_heat(training_manager, detector, in_flight=1):
+    """A cold heat map before a new sequence: the states of the engine ``in_flight`` names, or the eager path's."""
+    eng = _engine(training_manager, detector, in_flight)
+    if eng is not None:
+        eng.heat_reset()
+    else:
+        key = tuple(sorted(training_manager.class_mapping.items()))
+        for k, state in _EAGER_HEAT.items():
+            if k[0] == key:
+                ops.heat_reset(state)
+
+
 def _lookback_frames(track_lookback, track, eng, B):
     """``annotate_images`` / ``annotate_stream``'s ``track_lookback`` checked -> the look-back of their passes, or None."""
     if track_lookback is None:
@@ -652,7 +767,7 @@ def _print_drawn(dets, width, height):
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                        track_trails=None):
+                        track_trails=None, heatmap=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
@@ -661,7 +776,9 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     ``track_scene_cut`` = PCT (with ``track_motion``): every track ends when the frame is a hard cut against the frame before it (DESIGN
     §8 "Cut rule"); a line ``scene cut: <frame_no>`` is then printed in front of the frame's lines.
     ``track_trails`` = (N, W) (with ``track``): the path of every id live in the frame is drawn, its last N points, W pixels wide (DESIGN
-    §8 "Trail rule"); the frames before this one are the calls before this one."""
+    §8 "Trail rule"); the frames before this one are the calls before this one.
+    ``heatmap`` = (classes, A, S): the frame's boxes of those classes heat the map of the calls before this one (``reset_heat`` starts a
+    cold one), which is blended into the frame (DESIGN §8 "Heat rule")."""
     if detect_every is not None:
         raise ValueError("detect_every=%r runs the detector once per pass of several frames: get_annotated_frame detects its one frame and "
                          "cannot; use annotate_images or annotate_stream" % (detect_every,))
@@ -679,6 +796,7 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     trails = _track_trails(track_trails, track, draw)
     if trails is not None:
         motion["track_trails"] = trails
+    heatmap = _heatmap(heatmap)
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1)
     info = {}
@@ -686,7 +804,8 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         pixels = eng.host_pixels(resized_imgs[0])
         num_rois, dets, out, *more = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], DET_THRESHOLD, [pixels],
                                                                         batch=1, annotate=True, redact=redact, draw=draw,
-                                                                        **({} if track is None else {"track": track}), **motion))[0]
+                                                                        **({} if track is None else {"track": track}), **motion,
+                                                                        **({} if heatmap is None else {"heat": heatmap})))[0]
         info = more[0] if more else info                          # (a ``track_scene_cut`` pass: the frame's marks behind its payload)
         if info.get("scene_cut"):
             print("scene cut: {}".format(frame_no))
@@ -694,7 +813,7 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         frame[...] = out
     else:
         dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=DET_THRESHOLD)
-        draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, info=info, **motion)
+        draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, info=info, heatmap=heatmap, **motion)
         if info.get("scene_cut"):
             print("scene cut: {}".format(frame_no))
     if track is not None:
@@ -1099,13 +1218,15 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-              track_trails=None):
+              track_trails=None, heatmap=None, heatmap_out=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     motion = {} if track_motion is None else {"track_motion": track_motion}
+    heatmap = _heatmap(heatmap)
+    heatmap_out = _heatmap_out(heatmap_out, heatmap)
     sink = make_sink()
     try:
         dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
@@ -1117,6 +1238,9 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
         trails = _track_trails(track_trails, track, draw)
         if trails is not None:
             motion["track_trails"] = tracking["track_trails"] = trails
+        if heatmap is not None:                           # a cold map for the list
+            motion["heatmap"] = tracking["heat"] = heatmap
+            reset_heat(training_manager, detector, 1 if eng is None else eng.in_flight)
         if track is not None:                             # a new sequence; its frames are submitted in input order, as every list's are
             reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
         if eng is None:
@@ -1146,6 +1270,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
 
             _run_passes(eng, loaded_from(prepare, 2 * eng.in_flight * eng.batch * (every or 1)), emit, kwargs, every, delayed, backtrack)
         sink.finish()
+        if heatmap_out is not None:                       # (host only: the states read back, their t values as grey PNG files)
+            write_heatmaps(heatmap_out, _heat_states(training_manager, eng))
     finally:
         sink.close()
 
@@ -1153,13 +1279,13 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
-                    track_backtrack=None, track_scene_cut=None, track_trails=None):
+                    track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out``: as ``annotate_images``."""
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
     if isinstance(writer_or_out_dir, y4m.Y4mWriter):
         make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma)
@@ -1168,13 +1294,15 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                                       jpeg_huffman)
     _annotate(training_manager, detector, source, lambda prepare, ahead: _loaded_stream(source, prepare, ahead), make_sink, resize_min, resize_max,
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
-              detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails)
+              detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
+              heatmap=heatmap, heatmap_out=heatmap_out)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
-                    track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None):
+                    track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
+                    heatmap_out=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1222,7 +1350,13 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     ``track_trails``: (N, W) as ``track_trails_from_args`` returns it (with ``track``, in every form above; not with ``draw`` False) -- the
     path of every id is kept on the device and each frame shows the last N points of the ids live in it as a line W pixels wide in the
     colour of the id (DESIGN §8 "Trail rule"), over the redaction and under the boxes; a delayed pass draws them in the order its frames
-    are emitted.  The printed lines and ``tracks_out`` are unchanged.  None: every byte and line is what it was."""
+    are emitted.  The printed lines and ``tracks_out`` are unchanged.  None: every byte and line is what it was.
+    ``heatmap``: (classes, A, S) as ``heatmap_from_args`` returns it (with every option above, ``draw`` False included) -- a map on the
+    device that starts cold with the list gains 256 per box of those classes in every frame (every detection; with ``track`` the live
+    tracked rows, in a delayed pass the emitted frames'), loses ceil(v / 2^S) per frame, and is blended into each frame at weight A for
+    the hottest pixel, over the redaction and under the trails, boxes and labels (DESIGN §8 "Heat rule").  ``heatmap_out``: a path ending
+    in .png that receives the map at the end of the list, 8-bit grey, one file per frame size met (``<stem>_<w>x<h>.png`` for several).
+    The printed lines and ``tracks_out`` are unchanged.  None: every byte and line is what it was."""
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
@@ -1235,7 +1369,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               lambda prepare, ahead: _loaded_files(paths, lambda path: prepare(path, _load_frame(path, device_decode, device_png)), ahead),
               make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-              track_trails=track_trails)
+              track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out)
 
 
 def build_parser():
@@ -1340,6 +1474,16 @@ def build_parser():
                         "not with --no_draw)")
     p.add_argument("--trail_width", dest="trail_width", type=int, default=None, metavar="W",
                    help="the width of the trails in pixels, 1..9 (default 3; needs --track_trails)")
+    p.add_argument("--heatmap", dest="heatmap", default=None, metavar="CLASSES",
+                   help="blend an occupancy heat map into every frame: where the boxes of these classes (comma-separated names of the active "
+                        "mapping, or all) have been since the first frame, black through red and yellow to white at the hottest pixel, over the "
+                        "redaction and under the trails, boxes and labels; with --track the live tracked boxes count, held ones do not")
+    p.add_argument("--heatmap_alpha", dest="heatmap_alpha", type=int, default=None, metavar="A",
+                   help="the weight of the hottest pixel's colour, 1..255 (default 160; needs --heatmap)")
+    p.add_argument("--heatmap_decay", dest="heatmap_decay", type=int, default=None, metavar="S",
+                   help="every frame takes ceil(v / 2^S) off every pixel of the map, 1..15; 0 (the default): the map never cools (needs --heatmap)")
+    p.add_argument("--heatmap_out", dest="heatmap_out", default=None, metavar="PATH.png",
+                   help="write the map at the end of the list as an 8-bit grey PNG, one per frame size met (needs --heatmap)")
     p.add_argument("--tracks_out", dest="tracks_out", default=None, metavar="PATH",
                    help="write the tracks as MOTChallenge lines frame,id,left,top,width,height,prob,cls,-1,-1 (needs --track)")
     return p
@@ -1421,6 +1565,11 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     track_trails = track_trails_from_args(args)
     if track_trails is not None:
         tracking["track_trails"] = track_trails
+    heatmap, heatmap_out = heatmap_from_args(args, class_mapping)
+    if heatmap is not None:
+        tracking["heatmap"] = heatmap
+    if heatmap_out is not None:
+        tracking["heatmap_out"] = heatmap_out
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

@@ -313,11 +313,12 @@ class PassSpec:
     track_backtrack: object = None
     track_scene_cut: object = None
     track_trails: object = None
+    heat: object = None
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
                 track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                track_trails=None):
+                track_trails=None, heat=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -370,6 +371,13 @@ class PassSpec:
                 raise FrcnnError("submit_batch: track_trails= together with draw=False is not supported: a pass that draws nothing draws "
                                  "no trails")
             track_trails = engine.track_trails_option(track_trails)
+        if heat is not None:
+            if not annotate:
+                raise FrcnnError("submit_batch: heat= blends the heat map into the frame an ANNOTATING pass returns: pass annotate=True")
+            if not engine.device_preprocess:
+                raise FrcnnError("submit_batch: heat= needs the device-side preprocess: a foreign preprocess_func uploads float pixels, and "
+                                 "the heat map is blended into the uint8 source frame")
+            heat = engine.heat_option(heat)
         if redact is not None:
             redact = engine.redact_option(redact)
         jpeg_mode, y4m_mode = JPEG_MODE, Y4M_MODE
@@ -404,7 +412,7 @@ class PassSpec:
             raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
-                   track_scene_cut=track_scene_cut, track_trails=track_trails)
+                   track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat)
 
     @property
     def delayed(self):
@@ -440,6 +448,8 @@ class PassSpec:
                 key = key + (tag, value)
         if self.track_trails is not None:
             key = key + ("trails",) + self.track_trails
+        if self.heat is not None:
+            key = key + ("heat",) + self.heat
         return key
 
 
@@ -455,7 +465,7 @@ class _Slot:
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
                  "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
                  "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
-                 "track_scene_cut", "cut_ws", "cuts", "cuts_pin", "_cuts_raw", "track_trails", "trail_lists")
+                 "track_scene_cut", "cut_ws", "cuts", "cuts_pin", "_cuts_raw", "track_trails", "trail_lists", "heat")
 
     def __init__(self):
         for name in self.__slots__:
@@ -605,6 +615,7 @@ class DetectionEntry:
         self._redact_tables = {}
         self._track_state = None                         # the engine's ONE tracker state (ops.track_state): its pointer is in the graphs
         self._track_trails_states = {}                   # length N -> the engine's trail state (ops.track_trails_state) beside the tracker state
+        self._heat_states = {}                           # (h, w) of the source frames -> ops.heat_state: their pointers are in the graphs
         self._track_tables = {}
         self._track_motion_states = {}                   # (h, w) of the source frames -> ops.track_motion_state: their pointers are in the graphs
         self._track_lookback_windows = {}                # (h, w, B) -> ops.track_lookback_state: the frames tracked but not yet emitted
@@ -650,6 +661,36 @@ class DetectionEntry:
         if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or margin < 0:
             raise FrcnnError("submit_batch: redact margin=%r: an integer >= 0" % (margin,))
         return classes, mode, size, int(margin)
+
+    # ------------------------------------------------------------------ heat map
+    def heat_state(self, h, w):
+        """The engine's heat state for source frames of (h, w) (device int32, ops.heat_state), made on first use: one per size, shared by
+        every pass submitted with ``heat=`` whatever its other options.  ``heat_reset()`` empties it; ``track_reset()`` does not."""
+        state = self._heat_states.get((h, w))
+        if state is None:
+            state = self._heat_states[(h, w)] = ops.heat_state(h, w)
+        return state
+
+    def heat_reset(self):
+        """A cold map for every size: the states are zeroed on the ordered stream, behind the heat passes submitted so far."""
+        with torch.cuda.stream(self.track_stream):
+            for state in self._heat_states.values():
+                ops.heat_reset(state)
+
+    def heat_option(self, heat):
+        """``submit_batch``'s ``heat`` checked and normalised -> (classes, A, S): classes "all" or a tuple of this engine's class names,
+        None for A or S replaced by the defaults (160, 0).  FrcnnError, with the reason, for anything else."""
+        try:
+            classes, alpha, decay = () if isinstance(heat, str) else heat
+        except (TypeError, ValueError):
+            raise FrcnnError("submit_batch: heat=%r: (classes, alpha, decay)" % (heat,)) from None
+        try:
+            classes, alpha, decay = ops.heat_option(classes, alpha, decay)
+            if classes != "all":
+                classes = ops.redact_class_list(self.class_names(), classes)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: heat=%r: %s" % (heat, e)) from None
+        return classes, alpha, decay
 
     # ------------------------------------------------------------------ tracking
     @property
@@ -828,13 +869,13 @@ class DetectionEntry:
         -> (the pinned side as a numpy array, the device view the pass reads the pairs from: (B, 2) f64, one image's (2,) for B = 1)."""
         B, off = s.batch, s.frames * seg
         s.seg = seg
-        tail = 16 if s.track else 0                      # a tracking pass: | the count of real frames, int32 (ops.track_update's n_frames)]
+        tail = 16 if s.track or s.heat else 0            # a tracking or heat pass: | the count of real frames, int32 (ops.track_update's n_frames)]
         s.io_dev = torch.zeros(off + 16 * B + tail, dtype=torch.uint8, device="cuda")
         fine("buffers: device staging")
         s.io_pin = self._pinned.take(off + 16 * B + tail, zero=True)
         fine("buffers: pinned staging")
         host = s.io_pin.numpy()
-        if s.track:                                      # (0 until a submit says otherwise: warm-up and capture leave the state alone)
+        if tail:                                         # (0 until a submit says otherwise: warm-up and capture leave the state alone)
             s.n_frames_host = host[off + 16 * B:off + 16 * B + 4].view(np.int32)
             s.n_frames_dev = s.io_dev[off + 16 * B:off + 16 * B + 4].view(torch.int32)
         s.dyn_host = host[off:off + 16 * B].view(np.float64).reshape(B, 2)
@@ -894,6 +935,12 @@ class DetectionEntry:
                 tr_state, tr_expire = self.track_trails_state(tr_length), self.track_trails_expire(s.track, s.every)
                 s.trail_lists = ops.track_trails_workspace(F, self.track_trails_capacity(), tr_length)
                 trails_rgb = src is not None and bool(int(flip) & 2)        # (the channel order the frames were uploaded in: ``uploaded_rgb``)
+        if s.heat:
+            # each frame: one heat update from the rows the redaction reads (the live ones of a tracked buffer), then the map blended in,
+            # over the redaction and under the trails, the boxes and the labels.  The engine's state of this frame size lives across passes.
+            h_classes, h_alpha, h_decay = s.heat
+            h_state, h_table = self.heat_state(in_h, in_w), self.redact_table(h_classes)
+            heat_rgb = src is not None and bool(int(flip) & 2)              # (the channel order the frames were uploaded in: ``uploaded_rgb``)
         if s.track_lookback:
             # the frames, as uploaded, and their tracked buffers then join the engine's window, the new tracks are followed back through
             # it, and the frames of the pass BEFORE come out: everything behind this point edits and encodes those (``out``), with their
@@ -986,6 +1033,14 @@ class DetectionEntry:
                     rows = s.lb_out[1][i] if s.track_lookback else s.track_out[i] if s.track else packed[i] if B > 1 else packed
                     if s.redact:
                         ops.redact_u8(out[i], rows, r_table, r_mode, r_size, r_margin, workspace=s.redact_ws, tracked=bool(s.track))
+                    if s.heat:
+                        # a delayed pass heats the EMITTED frames: their count is the ``n_frames`` word, the pass's own count the gate
+                        # (a warm-up run emits what the window holds once more, and those are no new frames)
+                        if s.track_lookback:
+                            ops.heat_update(h_state, in_h, in_w, rows, h_table, h_decay, i, s.lb_out[2], gate=s.n_frames_dev, tracked=True)
+                        else:
+                            ops.heat_update(h_state, in_h, in_w, rows, h_table, h_decay, i, s.n_frames_dev, tracked=bool(s.track))
+                        ops.heat_draw_u8(out[i], h_state, h_alpha, rgb=heat_rgb)
                     if s.track_trails:
                         ops.track_trails_draw_u8(out[i], s.trail_lists[i], tr_length, tr_width, rgb=trails_rgb)
                     ops.annotate_u8(out[i], rows, tables, tracked=bool(s.track))
@@ -1056,7 +1111,7 @@ class DetectionEntry:
             s.redact, s.nodraw, s.track, s.track_motion = spec.redact, (None if spec.draw else True), spec.track, spec.track_motion
             s.track_lookback, s.track_backtrack = spec.track_lookback or spec.track_backtrack, spec.track_backtrack      # (both: the delayed path is one)
             s.every, s.frames = spec.detect_every, B * (spec.detect_every or 1)
-            s.track_scene_cut, s.track_trails = spec.track_scene_cut, spec.track_trails
+            s.track_scene_cut, s.track_trails, s.heat = spec.track_scene_cut, spec.track_trails, spec.heat
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -1290,7 +1345,8 @@ class DetectionEntry:
 
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
-                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None):
+                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
+                     heat=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1368,11 +1424,21 @@ class DetectionEntry:
         (ops.track_trails_draw_u8) over its redaction and under its boxes and labels, in the colour of the id, the highest id on top.  A
         trail leaves (hold + 1) * K frames behind its last point (``track_trails_expire``), K = ``detect_every`` or 1.  The results are
         what they are without it: only the frames' bytes change.  Refused by name without ``track`` and with ``draw`` False; as every
-        annotating pass, on an engine with a foreign preprocess.  Without it every key and byte is what it was."""
+        annotating pass, on an engine with a foreign preprocess.  Without it every key and byte is what it was.
+        ``heat`` = (classes, A, S) (annotating passes, with every other option, ``draw`` False included; ("heat", classes, A, S) appended
+        behind all the tags above; classes "all" or names, A the blend weight 1..255, S the decay 0..15, None for the defaults 160 and 0):
+        the heat rule (DESIGN §8 "Heat rule") keeps where the objects of those classes have been: for each frame one ops.heat_update --
+        every detection of a plain pass, the LIVE rows of a tracking pass (a ``detect_every`` between frame's propagated rows among them),
+        in a delayed pass the EMITTED frames' -- into the engine's heat state of the frame size (``heat_state``; it lives across passes
+        and submits until ``heat_reset()``; ``track_reset()`` leaves it), and one ops.heat_draw_u8 that blends the map into the frame over
+        its redaction and under its trails, boxes and labels.  The map depends on the order of the frames: such passes replay in submit
+        order on one stream, as tracking passes do, whatever ``in_flight`` is.  The results are what they are without it: only the
+        frames' bytes change.  Refused by name without ``annotate``, on an engine with a foreign preprocess and for options out of
+        range.  Without it every key and byte is what it was."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-                                track_trails=track_trails)
+                                track_trails=track_trails, heat=heat)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1424,7 +1490,7 @@ class DetectionEntry:
                 metas.append(self._canvas_frame(s, i, pixels[j]))
             elif not isinstance(pixels[j][0], JpegFile):
                 np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
-        if s.track:
+        if s.track or s.heat:                                       # (a heat pass too: the map depends on the order of the frames)
             s.n_frames_host[0] = len(pixels) if images else -1      # goes up with the frames: the padding does not advance the tracker; -1: a flush
             st = self.track_stream
         else:

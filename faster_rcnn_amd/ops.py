@@ -1609,6 +1609,108 @@ def track_trails_draw_u8(frame, plist, length, width=None, rgb=False):
     return frame
 
 
+# ----------------------------------------------------------------------------- heat map
+HEAT_ALPHA, HEAT_DECAY = _lib.HEAT_ALPHA, _lib.HEAT_DECAY    # (smallest, largest, the default) of the blend weight A and of the decay S
+HEAT_MAX = _lib.HEAT_MAX                        # the value a pixel of the map stops at
+
+
+def heat_option(classes, alpha=None, decay=None):
+    """(host only) The heat-map option checked -> (classes, A, S): classes "all" or a tuple of class names (which names there are is the
+    caller's to check: ``redact_class_list``), A the blend weight of the hottest pixel, 1..255 (None: 160), S the decay, 0..15 (None: 0,
+    none): every frame takes ceil(v / 2^S) off every pixel.  ValueError with the reason."""
+    if isinstance(classes, str):
+        classes = (classes,)
+    try:
+        classes = tuple(classes)
+    except TypeError:
+        raise ValueError("heat classes=%r: \"all\", a class name or a list of class names" % (classes,)) from None
+    if not classes or not all(isinstance(c, str) and c for c in classes):
+        raise ValueError("heat classes=%r: \"all\", a class name or a list of class names" % (classes,))
+    classes = "all" if classes == ("all",) else classes
+    out = []
+    for name, v, (lo, hi, default) in (("alpha", alpha, HEAT_ALPHA), ("decay", decay, HEAT_DECAY)):
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError("heat %s=%r: an integer in %d..%d" % (name, v, lo, hi))
+        out.append(int(v))
+    return (classes,) + tuple(out)
+
+
+def heat_state_words(h, w):
+    """(host only) 4-byte words of a heat state BUFFER for frames of (h, w) (frcnn_heat_state_bytes / 4): the state, 4 + h w words
+    [frames, peak, saturated, 0 | map[h][w]], and the update kernel's scratch words behind it."""
+    n = int(_lib.load().frcnn_heat_state_bytes(int(h), int(w)))
+    if n == 0:
+        raise _lib.FrcnnError("heat state: frame %rx%r out of range (sides 1..%d)" % (h, w, _lib.REDACT_MAX_SIDE))
+    return n // 4
+
+
+def heat_state(h, w):
+    """An empty heat state for frames of (h, w): a zeroed int32 device tensor of ``heat_state_words`` words, [frames, peak, saturated, 0 |
+    map[h][w] | scratch] (include/ext/frcnn_hip_heat.h).  Zeroing it (``heat_reset``) empties it; ``heat_map`` cuts the map out of it."""
+    _require_gpu()
+    return torch.zeros(heat_state_words(h, w), dtype=torch.int32, device="cuda")
+
+
+def heat_reset(state):
+    """Empty the state (on the current stream): no frames, a cold map."""
+    state.zero_()
+    return state
+
+
+def heat_map(state, h, w):
+    """(frames, peak, saturated, the (h, w) map) of a heat state, device tensor or its host copy (torch or numpy): views."""
+    m = state[4:4 + int(h) * int(w)]
+    return int(state[0]), int(state[1]), int(state[2]), (m.view(int(h), int(w)) if isinstance(m, torch.Tensor) else m.reshape(int(h), int(w)))
+
+
+def heat_levels(state, h, w):
+    """(host only) The map of a heat state's HOST copy (numpy) as the draw step sees it: uint8 (h, w), t = (v * 255) // peak, all 0 for a
+    cold map -- the grey picture ``annotate_video --heatmap_out`` writes."""
+    _, peak, _, m = heat_map(np.asarray(state), h, w)
+    if peak <= 0:
+        return np.zeros((int(h), int(w)), dtype=np.uint8)
+    return (np.clip(m.astype(np.int64), 0, peak) * 255 // peak).astype(np.uint8)
+
+
+def heat_update(state, h, w, det_packed, table, decay=0, frame_index=0, n_frames=None, gate=None, tracked=False):
+    """UPDATE of the heat rule (DESIGN §8 "Heat rule", frcnn_heat_update) for one frame of (h, w): the map of ``state`` (``heat_state``)
+    decays by ``decay`` and every pixel gains 256 per box of ``det_packed`` that covers it -- the post-process's packed buffer, every row
+    of a class set in ``table`` (``redact_table``'s form), or with ``tracked`` True one tracked buffer of ``track_update`` (plain or
+    widened), its LIVE rows only.  The frame counts when ``frame_index`` < *``n_frames`` (a device int32 word; None: a word that says 1,
+    allocated here -- a captured call passes its own) and, with ``gate`` (a device word), *gate != 0; else nothing is written.  Two
+    launches, everything guarded on the device: the call can be captured in a graph -> ``state``."""
+    _require_gpu()
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.dim() == 1 and det_packed.is_contiguous()
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    h, w = int(h), int(w)
+    assert int(state.numel()) == heat_state_words(h, w)
+    if n_frames is None:
+        n_frames = torch.ones(1, dtype=torch.int32, device="cuda")
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert gate is None or (gate.is_cuda and gate.dtype == torch.int32 and gate.numel() >= 1)
+    per = 8 if tracked else 7
+    assert (int(det_packed.numel()) - 4) % per == 0
+    _lib.call("frcnn_heat_update", _p(state), h, w, _p(det_packed), (int(det_packed.numel()) - 4) // per, int(bool(tracked)), _p(table),
+              int(table.numel()), int(decay), int(frame_index), _p(n_frames), _p(gate), _stream())
+    return state
+
+
+def heat_draw_u8(frame, state, alpha=None, rgb=False):
+    """DRAW of the heat rule (frcnn_heat_draw_u8): the map of ``state`` blended into ``frame``, an (h, w, 3) uint8 device tensor, edited
+    in place and returned: a pixel at t = (v * 255) // peak takes the ramp's colour (black, red, yellow, white) at weight
+    (``alpha`` * t) // 255 (None: 160); a cold map writes nothing.  ``rgb``: the frame's bytes are R, G, B (False: B, G, R, as the
+    encoders' ``bgr=True``).  One launch; reads ``peak`` from device memory, so the call can be captured in a graph."""
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    assert int(state.numel()) == heat_state_words(h, w)
+    _lib.call("frcnn_heat_draw_u8", _p(frame), h, w, _p(state), HEAT_ALPHA[2] if alpha is None else int(alpha), int(bool(rgb)), _stream())
+    return frame
+
+
 TRACK_LOOKBACK = _lib.TRACK_LOOKBACK            # (smallest, largest, the default) look-back of ``track_lookback``, in frames
 
 
