@@ -3,7 +3,7 @@ vectors captured from the reference.  Integer / mask / index results must be bit
 import numpy as np
 import pytest
 
-from tests import synth
+from tests import detections_ref, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -385,6 +385,9 @@ def test_detections_device(ops):
             assert np.array_equal(out["det_cls"].cpu().numpy()[:nd], g[tag + "_cls"])
             assert np.array_equal(out["det_prob"].cpu().numpy()[:nd], g[tag + "_prob"])
             assert np.array_equal(out["det_bbox"].cpu().numpy()[:nd], g[tag + "_bbox"])
+            # the scored row behind every detection: a padded duplicate ties with the live row it copies, and the lower row wins
+            want = detections_ref.detections(r, g["out_cls"][:rows], g["out_reg"][:rows], rows, 20, float(ratio), float(thr), 16.0)
+            assert len(want[3]) == nd and np.array_equal(out["det_roi"].cpu().numpy()[:nd], want[3])
             # the captured-pass form: the two scalars from device memory; roi_batch 64 scores the padded list out of the live count
             dyn = dev(np.array([ratio, thr], np.float64))
             for n_live, batch in ((rows, 0), (n, 64)):

@@ -12,6 +12,7 @@ import torch
 
 from faster_rcnn_amd import ops
 from oracle import np_ref as ref
+from tests import detections_ref
 
 
 def dev(a):
@@ -100,7 +101,7 @@ def main():
             check(np.array_equal(cand_h[want_pick][e], w_rois), "roi_targets eligibility " + tag)
         # detections on random detector outputs
         C = int(rs.choice([2, 10, 21]))
-        m = int(rs.randint(1, 300))
+        m = int(rs.randint(1, 513))
         rois_f = np.sort(rs.randint(0, 60, (m, 4)), axis=1).astype(np.float32)[:, [0, 1, 2, 3]]
         rois_f[:, 2:] = np.maximum(rois_f[:, 2:], rois_f[:, :2] + 1)
         logits = rs.randn(m, C).astype(np.float32) * 3
@@ -110,12 +111,18 @@ def main():
         thr = float(rs.choice([0.0, 0.3, 0.7]))
         ratio = float(rs.choice([1.0, 1.6, 0.625]))
         out = ops.detections(dev(rois_f), dev(np.array([m], np.int32)), dev(probs), dev(oreg), 64, C - 1, thr, 16.0, ratio)
-        want = ref.detections(rois_f, probs, oreg, C - 1, ratio, det_threshold=thr)
-        nd = int(out["n_dets"].item())
-        got = [(int(out["det_cls"][i]), float(out["det_prob"][i]), tuple(int(v) for v in out["det_bbox"][i])) for i in range(nd)]
-        exp = [(int(w[0]), float(w[1]), tuple(int(v) for v in w[2])) for w in want]
-        runs = lambda seq: [sorted(b for c, p, b in seq if (c, p) == key) for key in dict.fromkeys((c, p) for c, p, _ in seq)]
-        check(nd == len(want) and [g[:2] for g in got] == [e_[:2] for e_ in exp] and runs(got) == runs(exp), "detections " + tag + " m=%d C=%d" % (m, C))
+        # the suite's contract (tests/detections_ref.py, docs/DETECTIONS_PARITY.md): exact, ties by row index, det_roi included
+        dcase = {"rois": rois_f, "cls": probs, "reg": oreg, "n_live": m, "roi_batch": 0, "bg": C - 1, "thr": thr, "ratio": ratio,
+                 "stride": 16.0, "nms": 0.5}
+        if detections_ref.unstable(dcase):
+            print("detections " + tag + " m=%d C=%d: a decision within one ulp of exp, draw skipped" % (m, C))
+        else:
+            w_cls, w_prob, w_bbox, w_roi, _ = detections_ref.run(dcase)
+            nd = int(out["n_dets"].item())
+            same = nd == len(w_cls) and all(np.array_equal(out[k].cpu().numpy()[:nd], w) for k, w in
+                                            (("det_cls", w_cls), ("det_prob", w_prob), ("det_bbox", w_bbox), ("det_roi", w_roi)))
+            check(same and (out["det_cls"].cpu().numpy()[nd:] == -1).all() and (out["det_roi"].cpu().numpy()[nd:] == -1).all(),
+                  "detections " + tag + " m=%d C=%d" % (m, C))
         # RoI crop + bilinear resize (bit-exact), with the fill / ReLU / position-major variants of the hoisted head
         if it % 2 == 0:
             from oracle import keras_ref
