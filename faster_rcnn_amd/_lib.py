@@ -457,6 +457,24 @@ HEAT_MAX = 1 << 30
 HEAT_MAX_FRAMES = 65536
 HEAT_TILE = (64, 16)
 
+COUNT_VERSION = 1               # include/ext/frcnn_hip_count.h FRCNN_COUNT_VERSION
+COUNT_SIGNATURES = {
+    "frcnn_count_version": (I, []),
+    "frcnn_count_state_bytes": (c_size_t, [I]),
+    "frcnn_count_list_words": (c_size_t, []),
+    "frcnn_count_update": (I, [P, I, P, ctypes.c_longlong, I, I, P, P, P, I, P, I, I, I, I, P, P]),
+    "frcnn_count_draw_u8": (I, [P, I, I, P, P, I, I, I, P]),
+}
+# the counting lines of a call at most, the events a frame's list holds (FRCNN_COUNT_MAX_LINES, _MAX_EVENTS), the range of a line's
+# coordinates (_MIN_COORD, _MAX_COORD), (smallest, largest, the default) width (1 / _MAX_WIDTH / _DEFAULT_WIDTH), the largest expiry in
+# frames (_MAX_EXPIRE) and the words of a count list (_LIST_WORDS)
+COUNT_MAX_LINES = 8
+COUNT_MAX_EVENTS = 64
+COUNT_COORD = (-32768, 65535)
+COUNT_WIDTH = (1, 9, 3)
+COUNT_MAX_EXPIRE = 4095
+COUNT_LIST_WORDS = 4 + 2 * COUNT_MAX_LINES + 4 * COUNT_MAX_EVENTS
+
 TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
 TRACK_LOOKBACK_SIGNATURES = {
     "frcnn_track_lookback_version": (I, []),
@@ -654,6 +672,15 @@ def load():
     if lib.frcnn_heat_version() != HEAT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_heat_version()} of the heat-map extension, this binding "
                          f"{HEAT_VERSION} (include/ext/frcnn_hip_heat.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in COUNT_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_count.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_count_version() != COUNT_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_count_version()} of the line-count extension, this binding "
+                         f"{COUNT_VERSION} (include/ext/frcnn_hip_count.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

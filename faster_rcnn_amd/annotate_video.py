@@ -96,6 +96,14 @@ ceil(v / 2^S) per frame, and is blended into each frame over the redaction and u
 yellow to white at the hottest pixel.  ``annotate_images`` / ``annotate_stream`` start with a cold map, ``get_annotated_frame`` continues
 the map of the calls before it (``reset_heat`` starts anew).  ``heatmap_out=PATH.png`` (``--heatmap_out``) writes the map at the end of
 the list as an 8-bit grey PNG, one per frame size met (``PATH_<w>x<h>.png`` when there are several).  With every other option.
+``count=(lines, classes, W)`` (``--count_line X1,Y1,X2,Y2``, repeatable up to 8 times, with ``--track`` in any of the forms above;
+``--count_classes``, ``--count_width``) counts the tracks whose box centre crosses a line, once per id, line and direction
+(ops.count_update / ops.count_draw_u8, csrc/count.hip; DESIGN §8 "Count rule"): each frame shows the lines and a label ``L{l} +{pos}
+-{neg}`` per line over the redaction, heat map and trails and under the boxes, ``counts_out=PATH`` (``--counts_out``) receives a CSV row
+``frame,line,direction,id,cls`` per crossing, and at the end one line per counting line and the totals per class are printed.  A list
+starts from zero totals; ``get_annotated_frame(count=, counts_out=)`` and the eager path take the option as one-frame calls that continue
+the state (``reset_counts`` zeroes it).  On the command line a value that begins with a minus sign needs the ``=`` form:
+``--count_line=-5,0,-5,100``.
 """
 import collections
 import os
@@ -288,6 +296,18 @@ def _eager_motion_state(class_mapping, h, w):
     return m
 
 
+_EAGER_COUNT = {}                                         # class mapping -> that tracker's count state
+
+
+def _eager_count_state(class_mapping):
+    """The eager path's count state (ops.count_state) of this class mapping's tracker."""
+    key = tuple(sorted(class_mapping.items()))
+    c = _EAGER_COUNT.get(key)
+    if c is None:
+        c = _EAGER_COUNT[key] = ops.count_state(min(2 * entry.TRACK_CAPACITY, ops.TRACK_MAX))
+    return c
+
+
 def _eager_trails_state(class_mapping, length):
     """The eager path's trail state (ops.track_trails_state) of this class mapping's tracker for trails of ``length`` points."""
     key = (tuple(sorted(class_mapping.items())), int(length))
@@ -318,7 +338,7 @@ def _eager_track_table(tracker, class_mapping, redact_classes):
 
 
 def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
-               track_trails=None, rgb=False, heatmap=None):
+               track_trails=None, rgb=False, heatmap=None, count=None):
     """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place.
     ``redact`` = (classes, mode, size, margin): one ops.redact_u8 in front of it; ``draw`` False: no drawing.
     ``track`` = (thr, hold, grow): one ops.track_update (one frame) in front of both, on this class mapping's eager tracker state
@@ -331,10 +351,14 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     frame's channel order (False: B, G, R).
     ``heatmap`` = (classes, A, S): a one-frame ops.heat_update on this class mapping's eager heat state for the frame's size (``reset_heat``
     empties it) -- the detections, or with ``track`` the live tracked rows -- and one ops.heat_draw_u8 between the redaction and the
-    trails; a frame without detections is blended too."""
+    trails; a frame without detections is blended too.
+    ``count`` = (lines, classes, W) (with ``track``): a one-frame ops.count_update behind the tracker call, on this class mapping's eager
+    count state (``reset_counts`` zeroes it), one ops.count_draw_u8 behind the trails and in front of the drawing step unless ``draw`` is
+    False, and ``info`` receives "crossings": [(line, dir, id, cls)]."""
     import torch
     track_trails = _track_trails(track_trails, track, draw)
     heatmap = _heatmap(heatmap)
+    count = _count(count, track)
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     _track_scene_cut(track_scene_cut, track, track_motion, None, None)
@@ -388,6 +412,17 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
             lists = ops.track_trails_update(_eager_trails_state(class_mapping, length), rows.view(1, -1), tracker[2], length,
                                             entry.DetectionEntry.track_trails_expire(track, None), frame.shape[0], frame.shape[1])
             ops.track_trails_draw_u8(dev, lists[0], length, width, rgb=rgb)
+        if count is not None:
+            c_lines, c_classes, c_width = count
+            c_table = _EAGER_REDACT_TABLES.get((key, c_classes))
+            if c_table is None:
+                c_table = _EAGER_REDACT_TABLES[(key, c_classes)] = ops.redact_table(_names_by_index(class_mapping), c_classes)
+            clists = ops.count_update(_eager_count_state(class_mapping), rows.view(1, -1), tracker[2], c_lines, c_table,
+                                      entry.DetectionEntry.track_trails_expire(track, None), frame.shape[0], frame.shape[1])
+            if draw:
+                ops.count_draw_u8(dev, clists[0], c_lines, c_width, rgb=rgb)
+            if info is not None:
+                info["crossings"] = ops.count_events(clists[0].cpu().numpy())
         if draw:
             tables = _EAGER_TABLES.get(key)
             if tables is None:
@@ -623,6 +658,116 @@ def _track_trails(track_trails, track, draw):
     return ops.track_trails_option(track_trails)
 
 
+def count_from_args(args, class_mapping):
+    """(host only) The line count the command line asks for -> ((lines, classes, W) as ``submit_batch(count=...)`` takes it, the path of
+    ``--counts_out`` or None), or (None, None) without ``--count_line``.  ValueError, with the reason, for ``--count_classes`` /
+    ``--count_width`` / ``--counts_out`` without ``--count_line``, ``--count_line`` without ``--track``, more than 8 lines, a tuple that is
+    not four integers X1,Y1,X2,Y2, A = B, an unknown class name and a W outside 1..9."""
+    if not args.count_line:
+        for flag, value in (("--count_classes", args.count_classes), ("--count_width", args.count_width), ("--counts_out", args.counts_out)):
+            if value is not None:
+                raise ValueError("%s=%s is a setting of the line count: it needs --count_line X1,Y1,X2,Y2" % (flag, value))
+        return None, None
+    if not args.track:
+        raise ValueError("--count_line counts the tracker's ids as they cross the line: it needs --track")
+    lines = []
+    for text in args.count_line:
+        try:
+            line = tuple(int(v) for v in text.split(","))
+        except ValueError:
+            line = ()
+        if len(line) != 4:
+            raise ValueError("--count_line %s: four integers X1,Y1,X2,Y2" % text)
+        lines.append(line)
+    names = [n.strip() for n in (args.count_classes or "all").split(",") if n.strip()]
+    if not names:
+        raise ValueError("--count_classes takes comma-separated class names, or all")
+    try:
+        classes = "all" if names == ["all"] else ops.redact_class_list(_names_by_index(class_mapping), names)
+        return ops.count_option(lines, classes, args.count_width), args.counts_out
+    except ValueError as e:
+        raise ValueError("--count_line / --count_classes / --count_width: %s" % e) from None
+
+
+def _count(count, track):
+    """``annotate_images`` / ``annotate_stream``'s ``count`` checked -> (lines, classes, W), or None."""
+    if count is None:
+        return None
+    if track is None:
+        raise ValueError("count=%r counts the tracker's ids as they cross a line: it needs track=(thr, hold, grow)" % (count,))
+    try:
+        lines, classes, width = count
+    except (TypeError, ValueError):
+        raise ValueError("count=%r: (lines, classes, width)" % (count,)) from None
+    return ops.count_option(lines, classes, width)
+
+
+COUNTS_HEADER = "frame,line,direction,id,cls"
+
+
+def counts_rows(frame_no, crossings, names):
+    """(host only) The ``--counts_out`` rows of one frame: ``frame,line,direction,id,cls`` per crossing (line, dir, id, cls), frames from
+    1, direction + or -, the class by its name in ``names`` (names by index)."""
+    return ["%d,%d,%s,%d,%s" % (frame_no, line, "+" if d else "-", tid, names[cls] if 0 <= cls < len(names) else cls)
+            for line, d, tid, cls in crossings]
+
+
+def print_counts(n_lines, totals, per_class, events_dropped):
+    """(host only) The lines printed at the end of a counted list: one per counting line with its two totals, the totals per class (from
+    the crossings listed), and a warning when crossings were left out of the lists."""
+    for l in range(n_lines):
+        print("line {}: +{} -{}".format(l, totals[l][1], totals[l][0]))
+    for name in sorted(per_class):
+        print("crossings of {}: +{} -{}".format(name, per_class[name][1], per_class[name][0]))
+    if events_dropped:
+        print("warning: {} crossings did not fit their frames' lists: the counts file is short by that many rows; the totals are exact"
+              .format(events_dropped))
+
+
+class CountsLog:
+    """Where the crossings of a counted sequence go: the ``--counts_out`` file (``path`` None: none) and the totals per class name."""
+
+    def __init__(self, path, names):
+        self.names, self.per_class = list(names), {}
+        self.file = open(path, "w") if path is not None else None
+        if self.file is not None:
+            self.file.write(COUNTS_HEADER + "\n")
+
+    def add(self, frame_no, crossings):
+        for _, d, _, cls in crossings:
+            self.per_class.setdefault(self.names[cls] if 0 <= cls < len(self.names) else str(cls), [0, 0])[d] += 1
+        if self.file is not None:
+            self.file.writelines(row + "\n" for row in counts_rows(frame_no, crossings, self.names))
+
+    def close(self):
+        if self.file is not None:
+            self.file.close()
+            self.file = None
+
+
+def _write_counts(counts_out, frame_no, crossings, class_mapping):
+    """``counts_out``: None, a ``CountsLog``, or a text file that receives the frame's CSV rows (no header)."""
+    if isinstance(counts_out, CountsLog):
+        counts_out.add(frame_no, crossings)
+    elif counts_out is not None:
+        counts_out.writelines(row + "\n" for row in counts_rows(frame_no, crossings, _names_by_index(class_mapping)))
+
+
+def _count_state(training_manager, eng):
+    """The count state of ``eng``, or of the eager path with None."""
+    return eng.count_state() if eng is not None else _eager_count_state(training_manager.class_mapping)
+
+
+def reset_counts(training_manager, detector, in_flight=1):
+    """Zero totals and no entries before a new sequence: the count state of the engine ``in_flight`` names, or the eager path's.
+    (``reset_tracks`` ends the ids and keeps the totals.)"""
+    eng = _engine(training_manager, detector, in_flight)
+    if eng is not None:
+        eng.count_reset()
+    else:
+        ops.count_reset(_eager_count_state(training_manager.class_mapping))
+
+
 def heatmap_from_args(args, class_mapping):
     """(host only) The heat map the command line asks for -> ((classes, A, S) as ``submit_batch(heat=...)`` takes it, the path of
     ``--heatmap_out`` or None), or (None, None) without ``--heatmap``.  classes: "all", or the tuple of names (of ``class_mapping``, the
@@ -757,6 +902,8 @@ def reset_tracks(training_manager, detector, in_flight=1):
         for k, trails in _EAGER_TRAILS.items():
             if k[0] == key:
                 ops.track_reset(trails)
+        if key in _EAGER_COUNT:                                     # the ids end; what was counted stays counted
+            ops.count_reset(_EAGER_COUNT[key], keep_totals=True)
 
 
 def _print_drawn(dets, width, height):
@@ -767,7 +914,7 @@ def _print_drawn(dets, width, height):
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                        track_trails=None, heatmap=None):
+                        track_trails=None, heatmap=None, count=None, counts_out=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
@@ -778,7 +925,14 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     ``track_trails`` = (N, W) (with ``track``): the path of every id live in the frame is drawn, its last N points, W pixels wide (DESIGN
     §8 "Trail rule"); the frames before this one are the calls before this one.
     ``heatmap`` = (classes, A, S): the frame's boxes of those classes heat the map of the calls before this one (``reset_heat`` starts a
-    cold one), which is blended into the frame (DESIGN §8 "Heat rule")."""
+    cold one), which is blended into the frame (DESIGN §8 "Heat rule").
+    ``count`` = (lines, classes, W) (with ``track``): the frame is one more step of the count state the calls before it left (DESIGN §8
+    "Count rule"; ``reset_counts`` starts from zero totals, ``reset_tracks`` ends the ids and keeps them): the lines and their totals are
+    drawn unless ``draw`` is False, and ``counts_out``, a text file, receives the frame's rows ``frame,line,direction,id,cls`` under the
+    number ``frame_no``."""
+    count = _count(count, track)
+    if counts_out is not None and count is None:
+        raise ValueError("counts_out is where the crossings are written: it needs count=(lines, classes, width)")
     if detect_every is not None:
         raise ValueError("detect_every=%r runs the detector once per pass of several frames: get_annotated_frame detects its one frame and "
                          "cannot; use annotate_images or annotate_stream" % (detect_every,))
@@ -796,6 +950,8 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     trails = _track_trails(track_trails, track, draw)
     if trails is not None:
         motion["track_trails"] = trails
+    if count is not None:
+        motion["count"] = count
     heatmap = _heatmap(heatmap)
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1)
@@ -818,6 +974,8 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
             print("scene cut: {}".format(frame_no))
     if track is not None:
         _write_tracks(tracks_out, frame_no, dets, training_manager.class_mapping)
+    if count is not None:
+        _write_counts(counts_out, frame_no, info["crossings"], training_manager.class_mapping)
     _print_drawn(dets, img.width, img.height)
     return frame
 
@@ -1218,7 +1376,7 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-              track_trails=None, heatmap=None, heatmap_out=None):
+              track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
@@ -1227,6 +1385,10 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     motion = {} if track_motion is None else {"track_motion": track_motion}
     heatmap = _heatmap(heatmap)
     heatmap_out = _heatmap_out(heatmap_out, heatmap)
+    count = _count(count, track)
+    if counts_out is not None and count is None:
+        raise ValueError("counts_out=%r is where the crossings are written: it needs count=(lines, classes, width)" % (counts_out,))
+    counts_log = None
     sink = make_sink()
     try:
         dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
@@ -1243,6 +1405,11 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             reset_heat(training_manager, detector, 1 if eng is None else eng.in_flight)
         if track is not None:                             # a new sequence; its frames are submitted in input order, as every list's are
             reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
+        if count is not None:                             # zero totals for the list
+            motion["count"] = tracking["count"] = count
+            reset_counts(training_manager, detector, 1 if eng is None else eng.in_flight)
+            counts_log = CountsLog(counts_out, _names_by_index(training_manager.class_mapping))
+            motion["counts_out"] = counts_log
         if eng is None:
             _run_eager(training_manager, detector, frames, sink, resize_min, resize_max, redact=redact, draw=draw, track=track,
                        tracks_out=tracks_out, **motion)
@@ -1261,6 +1428,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
                 num_rois, dets, out, *marks = result      # (a ``track_scene_cut`` pass: the frame's marks behind its payload)
                 if marks and marks[0].get("scene_cut"):
                     print("scene cut: {}".format(label))
+                if count is not None:
+                    counts_log.add(pos + 1, marks[0]["crossings"])
                 print("processing {}".format(label))
                 print("num rois: {}".format(num_rois))
                 if track is not None:
@@ -1270,22 +1439,29 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
 
             _run_passes(eng, loaded_from(prepare, 2 * eng.in_flight * eng.batch * (every or 1)), emit, kwargs, every, delayed, backtrack)
         sink.finish()
+        if count is not None:                             # (host only: the state read back)
+            counts_log.close()
+            state = ops.count_totals(_count_state(training_manager, eng))
+            print_counts(len(count[0]), state["totals"], counts_log.per_class, state["events_dropped"])
         if heatmap_out is not None:                       # (host only: the states read back, their t values as grey PNG files)
             write_heatmaps(heatmap_out, _heat_states(training_manager, eng))
     finally:
+        if counts_log is not None:
+            counts_log.close()
         sink.close()
 
 
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
-                    track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None):
+                    track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
+                    counts_out=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out``: as ``annotate_images``."""
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
     if isinstance(writer_or_out_dir, y4m.Y4mWriter):
         make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma)
@@ -1295,14 +1471,14 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
     _annotate(training_manager, detector, source, lambda prepare, ahead: _loaded_stream(source, prepare, ahead), make_sink, resize_min, resize_max,
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
               detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
-              heatmap=heatmap, heatmap_out=heatmap_out)
+              heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
-                    heatmap_out=None):
+                    heatmap_out=None, count=None, counts_out=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1369,7 +1545,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               lambda prepare, ahead: _loaded_files(paths, lambda path: prepare(path, _load_frame(path, device_decode, device_png)), ahead),
               make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-              track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out)
+              track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out)
 
 
 def build_parser():
@@ -1484,6 +1660,18 @@ def build_parser():
                    help="every frame takes ceil(v / 2^S) off every pixel of the map, 1..15; 0 (the default): the map never cools (needs --heatmap)")
     p.add_argument("--heatmap_out", dest="heatmap_out", default=None, metavar="PATH.png",
                    help="write the map at the end of the list as an 8-bit grey PNG, one per frame size met (needs --heatmap)")
+    p.add_argument("--count_line", dest="count_line", action="append", default=None, metavar="X1,Y1,X2,Y2",
+                   help="count the tracks whose box centre crosses the line from (X1,Y1) to (X2,Y2), in source-frame pixels (-32768..65535), "
+                        "once per id and direction; a value that begins with a minus sign is written --count_line=-5,0,-5,100; repeatable up to 8 "
+                        "times; each line is drawn with its totals 'L{l} +{pos} -{neg}' over "
+                        "the redaction, heat map and trails and under the boxes, and the totals are printed at the end (needs --track)")
+    p.add_argument("--count_classes", dest="count_classes", default=None, metavar="CLASSES",
+                   help="the classes that count: comma-separated names of the active mapping, or all (the default; needs --count_line)")
+    p.add_argument("--count_width", dest="count_width", type=int, default=None, metavar="W",
+                   help="the width the counting lines are drawn with in pixels, 1..9 (default 3; needs --count_line)")
+    p.add_argument("--counts_out", dest="counts_out", default=None, metavar="PATH",
+                   help="write every crossing as a CSV row frame,line,direction,id,cls: frames from 1, direction + or -, the class by name "
+                        "(needs --count_line)")
     p.add_argument("--tracks_out", dest="tracks_out", default=None, metavar="PATH",
                    help="write the tracks as MOTChallenge lines frame,id,left,top,width,height,prob,cls,-1,-1 (needs --track)")
     return p
@@ -1570,6 +1758,11 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
         tracking["heatmap"] = heatmap
     if heatmap_out is not None:
         tracking["heatmap_out"] = heatmap_out
+    count, counts_out = count_from_args(args, class_mapping)
+    if count is not None:
+        tracking["count"] = count
+    if counts_out is not None:
+        tracking["counts_out"] = counts_out
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

@@ -314,11 +314,12 @@ class PassSpec:
     track_scene_cut: object = None
     track_trails: object = None
     heat: object = None
+    count: object = None
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
                 track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                track_trails=None, heat=None):
+                track_trails=None, heat=None, count=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -378,6 +379,10 @@ class PassSpec:
                 raise FrcnnError("submit_batch: heat= needs the device-side preprocess: a foreign preprocess_func uploads float pixels, and "
                                  "the heat map is blended into the uint8 source frame")
             heat = engine.heat_option(heat)
+        if count is not None:
+            if track is None:
+                raise FrcnnError("submit_batch: count= counts the tracker's ids as they cross a line: pass track=(thr, hold, grow) too")
+            count = engine.count_option(count)
         if redact is not None:
             redact = engine.redact_option(redact)
         jpeg_mode, y4m_mode = JPEG_MODE, Y4M_MODE
@@ -412,7 +417,7 @@ class PassSpec:
             raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
-                   track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat)
+                   track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count)
 
     @property
     def delayed(self):
@@ -450,6 +455,8 @@ class PassSpec:
             key = key + ("trails",) + self.track_trails
         if self.heat is not None:
             key = key + ("heat",) + self.heat
+        if self.count is not None:
+            key = key + ("count",) + self.count
         return key
 
 
@@ -465,7 +472,8 @@ class _Slot:
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
                  "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
                  "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
-                 "track_scene_cut", "cut_ws", "cuts", "cuts_pin", "_cuts_raw", "track_trails", "trail_lists", "heat")
+                 "track_scene_cut", "cut_ws", "cuts", "cuts_pin", "_cuts_raw", "track_trails", "trail_lists", "heat",
+                 "count", "count_lists", "count_pin", "_count_raw")
 
     def __init__(self):
         for name in self.__slots__:
@@ -615,6 +623,7 @@ class DetectionEntry:
         self._redact_tables = {}
         self._track_state = None                         # the engine's ONE tracker state (ops.track_state): its pointer is in the graphs
         self._track_trails_states = {}                   # length N -> the engine's trail state (ops.track_trails_state) beside the tracker state
+        self._count_state = None                         # the engine's ONE count state (ops.count_state): its pointer is in the graphs
         self._heat_states = {}                           # (h, w) of the source frames -> ops.heat_state: their pointers are in the graphs
         self._track_tables = {}
         self._track_motion_states = {}                   # (h, w) of the source frames -> ops.track_motion_state: their pointers are in the graphs
@@ -736,6 +745,36 @@ class DetectionEntry:
         or 1 -- as long as the tracker can still re-match the id -- and at most the rule's 4095."""
         return min((track[1] + 1) * (detect_every or 1), ops.TRACK_TRAILS[2])
 
+    # ------------------------------------------------------------------ line counts
+    def count_state(self):
+        """The engine's count state (device int32, ops.count_state), made on first use, of ``track_trails_capacity()`` entries: one,
+        shared by every pass submitted with ``count=``.  ``count_reset()`` empties it, totals included; ``track_reset()`` drops its
+        entries -- the ids end -- and leaves the totals.  ``ops.count_totals`` reads it."""
+        if self._count_state is None:
+            self._count_state = ops.count_state(self.track_trails_capacity())
+        return self._count_state
+
+    def count_reset(self):
+        """Zero totals and no entries: the state is zeroed on the ordered stream, behind the counting passes submitted so far."""
+        if self._count_state is not None:
+            with torch.cuda.stream(self.track_stream):
+                ops.count_reset(self._count_state)
+
+    def count_option(self, count):
+        """``submit_batch``'s ``count`` checked and normalised -> (lines, classes, W): lines a tuple of 1..8 (ax, ay, bx, by), classes
+        "all" or a tuple of this engine's class names, W 1..9 (None: 3).  FrcnnError, with the reason, for anything else."""
+        try:
+            lines, classes, width = count
+        except (TypeError, ValueError):
+            raise FrcnnError("submit_batch: count=%r: (lines, classes, width)" % (count,)) from None
+        try:
+            lines, classes, width = ops.count_option(lines, classes, width)
+            if classes != "all":
+                classes = ops.redact_class_list(self.class_names(), classes)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: count=%r: %s" % (count, e)) from None
+        return lines, classes, width
+
     def track_reset(self):
         """Forget every track: the state is zeroed on the tracking stream, behind the tracked passes submitted so far."""
         state = self.track_state()
@@ -747,6 +786,8 @@ class DetectionEntry:
                 ops.track_lookback_reset(window)
             for trails in self._track_trails_states.values():       # ... and no path has begun
                 ops.track_reset(trails)
+            if self._count_state is not None:                       # ... and no id waits for its next step; what was counted stays
+                ops.count_reset(self._count_state, keep_totals=True)
         self._lookback_waiting.clear()
         self._lookback_last = None
 
@@ -935,6 +976,14 @@ class DetectionEntry:
                 tr_state, tr_expire = self.track_trails_state(tr_length), self.track_trails_expire(s.track, s.every)
                 s.trail_lists = ops.track_trails_workspace(F, self.track_trails_capacity(), tr_length)
                 trails_rgb = src is not None and bool(int(flip) & 2)        # (the channel order the frames were uploaded in: ``uploaded_rgb``)
+            if s.count:
+                # ONE count update behind the tracker call (behind the look-back / back-track call of a delayed pass), where the trail
+                # update sits, then each frame's lines and totals drawn over its redaction, heat and trails and under its boxes
+                c_lines, c_classes, c_width = s.count
+                c_state, c_table, c_expire = self.count_state(), self.redact_table(c_classes), self.track_trails_expire(s.track, s.every)
+                s.count_lists = ops.count_workspace(F)
+                s.count_lists.zero_()
+                count_rgb = src is not None and bool(int(flip) & 2)
         if s.heat:
             # each frame: one heat update from the rows the redaction reads (the live ones of a tracked buffer), then the map blended in,
             # over the redaction and under the trails, the boxes and the labels.  The engine's state of this frame size lives across passes.
@@ -1029,6 +1078,12 @@ class DetectionEntry:
                                                     gate=s.n_frames_dev)
                         else:
                             ops.track_trails_update(tr_state, s.track_out, s.n_frames_dev, tr_length, tr_expire, in_h, in_w, lists=s.trail_lists)
+                    if s.count:
+                        if s.track_lookback:                        # (the emitted buffers and their count, gated by the pass's own: as the trails)
+                            ops.count_update(c_state, s.lb_out[1], s.lb_out[2], c_lines, c_table, c_expire, in_h, in_w, lists=s.count_lists,
+                                             gate=s.n_frames_dev)
+                        else:
+                            ops.count_update(c_state, s.track_out, s.n_frames_dev, c_lines, c_table, c_expire, in_h, in_w, lists=s.count_lists)
                 for i in range(F):
                     rows = s.lb_out[1][i] if s.track_lookback else s.track_out[i] if s.track else packed[i] if B > 1 else packed
                     if s.redact:
@@ -1043,6 +1098,8 @@ class DetectionEntry:
                         ops.heat_draw_u8(out[i], h_state, h_alpha, rgb=heat_rgb)
                     if s.track_trails:
                         ops.track_trails_draw_u8(out[i], s.trail_lists[i], tr_length, tr_width, rgb=trails_rgb)
+                    if s.count and not s.nodraw:
+                        ops.count_draw_u8(out[i], s.count_lists[i], c_lines, c_width, rgb=count_rgb)
                     ops.annotate_u8(out[i], rows, tables, tracked=bool(s.track))
                     if s.encode == Y4M_ENCODE:
                         continue                                    # (all B frames in one launch behind the loop)
@@ -1111,7 +1168,7 @@ class DetectionEntry:
             s.redact, s.nodraw, s.track, s.track_motion = spec.redact, (None if spec.draw else True), spec.track, spec.track_motion
             s.track_lookback, s.track_backtrack = spec.track_lookback or spec.track_backtrack, spec.track_backtrack      # (both: the delayed path is one)
             s.every, s.frames = spec.detect_every, B * (spec.detect_every or 1)
-            s.track_scene_cut, s.track_trails, s.heat = spec.track_scene_cut, spec.track_trails, spec.heat
+            s.track_scene_cut, s.track_trails, s.heat, s.count = spec.track_scene_cut, spec.track_trails, spec.heat, spec.count
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -1158,6 +1215,9 @@ class DetectionEntry:
             if s.track_scene_cut:
                 s._cuts_raw = self._pinned.take(4 * s.frames)
                 s.cuts_pin = s._cuts_raw.view(torch.int32)[:s.frames]
+            if s.count:
+                s._count_raw = self._pinned.take(4 * s.count_lists.numel())
+                s.count_pin = s._count_raw.view(torch.int32)[:s.count_lists.numel()].view(tuple(s.count_lists.shape))
             if s.track_lookback:                                    # [the B emitted buffers | the count word]
                 words = s.lb_out[1].numel() + 4
                 s._lb_raw = self._pinned.take(4 * words)
@@ -1346,7 +1406,7 @@ class DetectionEntry:
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
                      track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
-                     heat=None):
+                     heat=None, count=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1434,11 +1494,22 @@ class DetectionEntry:
         its redaction and under its trails, boxes and labels.  The map depends on the order of the frames: such passes replay in submit
         order on one stream, as tracking passes do, whatever ``in_flight`` is.  The results are what they are without it: only the
         frames' bytes change.  Refused by name without ``annotate``, on an engine with a foreign preprocess and for options out of
-        range.  Without it every key and byte is what it was."""
+        range.  Without it every key and byte is what it was.
+        ``count`` = (lines, classes, W) (tracking passes only, every form of them; ("count", lines, classes, W) appended behind all the
+        tags above; lines 1..8 tuples (ax, ay, bx, by) in source-frame pixels, -32768..65535, A != B; classes "all" or names; W the width
+        the lines are drawn with, 1..9, None: 3): the count rule (DESIGN §8 "Count rule") counts every id once per line and direction as
+        the centre of its box crosses: one ops.count_update behind the tracker call -- in a delayed pass behind the look-back /
+        back-track call, over the EMITTED buffers and their count, gated by the pass's own count, exactly where the trail update sits --
+        steps the engine's count state (``count_state``; ``count_reset()`` zeroes it, ``track_reset()`` drops its entries and keeps the
+        totals), and each frame's lines and labels "L{l} +{pos} -{neg}" are drawn (ops.count_draw_u8) over its redaction, heat and trails
+        and under its boxes and labels; ``draw`` False still counts and draws no line.  The count lists come back with the dets: every
+        result of such a pass carries, in ONE trailing dict (the one that carries "scene_cut"), "crossings": [(line, dir, id, cls), ...]
+        -- dir 1 for +, cls the class index.  An entry leaves (hold + 1) * K frames behind its last step.  Refused by name without
+        ``track`` and for options out of range.  Without it every key and byte is what it was."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-                                track_trails=track_trails, heat=heat)
+                                track_trails=track_trails, heat=heat, count=count)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1528,6 +1599,8 @@ class DetectionEntry:
                 s.track_pin[i].copy_(s.track_out[i], non_blocking=True)
             if s.track_scene_cut:
                 s.cuts_pin.copy_(s.cuts, non_blocking=True)
+            if s.count:                                             # the count lists come back with the dets
+                s.count_pin.copy_(s.count_lists, non_blocking=True)
             for i in range(emitted["frames"] if emitted else 0 if s.track_lookback else len(pixels)):
                 if s.encode == JPEG_ENCODE:
                     s.png_pin[i].copy_(s.png_dev[i][:s.first_copy], non_blocking=True)
@@ -1723,11 +1796,15 @@ class DetectionEntry:
 
     @staticmethod
     def _marks(s, i):
-        """What frame i of a collected ``track_scene_cut`` pass returns behind its payload: one dict, {"scene_cut": True} for a frame that
-        is a cut and an empty one else; () for every other pass."""
-        if not s.track_scene_cut:
+        """What frame i of a collected ``track_scene_cut`` or ``count`` pass returns behind its payload: ONE dict -- "scene_cut": True for a
+        frame that is a cut, "crossings": [(line, dir, id, cls)] in a counting pass (the events of the frame's count list, dir 1 for +) --
+        ; () for every other pass."""
+        if not s.track_scene_cut and not s.count:
             return ()
-        return ({"scene_cut": True},) if int(s.cuts_pin[i]) else ({},)
+        marks = {"scene_cut": True} if s.track_scene_cut and int(s.cuts_pin[i]) else {}
+        if s.count:
+            marks["crossings"] = ops.count_events(s.count_pin[i].numpy())
+        return (marks,)
 
     def _payload(self, s, i):
         """What frame i of a collected pass returns behind (num_rois, dets): () , (the frame,) or (the encoded file's bytes,)."""
@@ -1778,7 +1855,7 @@ class DetectionEntry:
                 elif i % K:                                         # a between frame: its live dets are the tracks
                     d["propagated"] = True
                 dets.append(d)
-            res.append((0 if i % K else group["n_rois"][i // K], dets) + self._payload(s, i))
+            res.append((0 if i % K else group["n_rois"][i // K], dets) + self._payload(s, i) + self._marks(s, i))
         return res
 
     def collect(self, ticket):

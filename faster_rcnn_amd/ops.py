@@ -1711,6 +1711,152 @@ def heat_draw_u8(frame, state, alpha=None, rgb=False):
     return frame
 
 
+# ----------------------------------------------------------------------------- line counts
+COUNT_MAX_LINES, COUNT_MAX_EVENTS = _lib.COUNT_MAX_LINES, _lib.COUNT_MAX_EVENTS      # the lines of a call, the events of a frame's list
+COUNT_WIDTH = _lib.COUNT_WIDTH                  # (smallest, largest, the default) width W the lines are drawn with
+COUNT_LIST_WORDS = _lib.COUNT_LIST_WORDS        # words of a count list: [n_events, frames, 0, 0 | totals[8][2] | events[64][4]]
+COUNT_HEAD, COUNT_ENTRY = 4 + 2 * _lib.COUNT_MAX_LINES, 6                            # a state's words in front of its entries; an entry's
+
+
+def count_option(lines, classes="all", width=None):
+    """(host only) The count option checked -> (lines, classes, W): lines a tuple of 1..8 tuples (ax, ay, bx, by) of integers in
+    -32768..65535 with A != B (one such tuple alone is one line), classes "all" or a tuple of class names (which names there are is the
+    caller's to check: ``redact_class_list``), W the width the lines are drawn with, 1..9 (None: 3).  ValueError with the reason."""
+    lo, hi = _lib.COUNT_COORD
+    try:
+        lines = tuple(lines)
+        if len(lines) == 4 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in lines):
+            lines = (lines,)
+        lines = tuple(tuple(ln) for ln in lines)
+    except TypeError:
+        raise ValueError("count lines=%r: a list of (ax, ay, bx, by)" % (lines,)) from None
+    if not 1 <= len(lines) <= COUNT_MAX_LINES:
+        raise ValueError("count lines: %d of them, 1..%d are possible" % (len(lines), COUNT_MAX_LINES))
+    for ln in lines:
+        if len(ln) != 4 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and lo <= int(v) <= hi for v in ln):
+            raise ValueError("count line %r: four integers ax, ay, bx, by in %d..%d" % (ln, lo, hi))
+        if (int(ln[0]), int(ln[1])) == (int(ln[2]), int(ln[3])):
+            raise ValueError("count line %r: A = B is a point, not a line" % (ln,))
+    lines = tuple(tuple(int(v) for v in ln) for ln in lines)
+    if classes is None:
+        classes = "all"
+    if isinstance(classes, str):
+        classes = (classes,)
+    try:
+        classes = tuple(classes)
+    except TypeError:
+        raise ValueError("count classes=%r: \"all\", a class name or a list of class names" % (classes,)) from None
+    if not classes or not all(isinstance(c, str) and c for c in classes):
+        raise ValueError("count classes=%r: \"all\", a class name or a list of class names" % (classes,))
+    classes = "all" if classes == ("all",) else classes
+    w_lo, w_hi, w_def = COUNT_WIDTH
+    width = w_def if width is None else width
+    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or not w_lo <= int(width) <= w_hi:
+        raise ValueError("count width=%r: an integer in %d..%d (pixels)" % (width, w_lo, w_hi))
+    return lines, classes, int(width)
+
+
+def _count_lines_arg(lines):
+    """``lines`` (n, 4) as the host int32 array the entry points read (keep the array alive over the call), its pointer and n."""
+    a = np.ascontiguousarray(np.asarray(lines, dtype=np.int64).reshape(-1, 4).clip(-2 ** 31, 2 ** 31 - 1), dtype=np.int32)
+    return a, a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0])
+
+
+def count_state_words(capacity):
+    """(host only) 4-byte words of a count state of ``capacity`` entries (frcnn_count_state_bytes / 4): 20 + 6 capacity."""
+    n = int(_lib.load().frcnn_count_state_bytes(int(capacity)))
+    if n == 0:
+        raise _lib.FrcnnError("count state: capacity=%r not in [1, %d]" % (capacity, TRACK_MAX))
+    return n // 4
+
+
+def count_state(capacity):
+    """An empty count state of ``capacity`` entries: a zeroed int32 device tensor, [n_entries, frames, dropped, events_dropped |
+    totals[8][2] | per entry: id, cls, last_seen, counted, px, py] (include/ext/frcnn_hip_count.h).  Zeroing it (``count_reset``) empties
+    it, totals included."""
+    _require_gpu()
+    return torch.zeros(count_state_words(capacity), dtype=torch.int32, device="cuda")
+
+
+def count_reset(state, keep_totals=False):
+    """Empty the state (on the current stream): no entries, no frames, totals 0.  ``keep_totals``: only the entries leave -- the ids end,
+    what was counted stays counted (``frames``, the sticky sums and the totals are kept)."""
+    if keep_totals:
+        state[0:1].zero_()
+        state[COUNT_HEAD:].zero_()
+    else:
+        state.zero_()
+    return state
+
+
+def count_workspace(frames):
+    """The count lists of a ``count_update`` call of ``frames`` frames: an int32 device tensor (frames, COUNT_LIST_WORDS).  Every word is
+    written by every call."""
+    _require_gpu()
+    if not 1 <= int(frames) <= _lib.TRACK_MAX_FRAMES:
+        raise _lib.FrcnnError("count_workspace: frames=%r out of range (1..%d)" % (frames, _lib.TRACK_MAX_FRAMES))
+    assert int(_lib.load().frcnn_count_list_words()) == COUNT_LIST_WORDS
+    return torch.empty((int(frames), COUNT_LIST_WORDS), dtype=torch.int32, device="cuda")
+
+
+def count_update(state, tracked, n_frames, lines, table, expire, h, w, capacity=None, lists=None, gate=None):
+    """Steps 1-4 of the count rule (DESIGN §8 "Count rule", frcnn_count_update) over the frames of ``tracked`` IN ORDER, in one launch:
+    ``tracked`` is a (frames, 4 + 8 rows) int32 tensor of tracked buffers -- ``track_update``'s ``out``, or the widened buffers a
+    look-back emits --, ``n_frames`` the device word that says how many of them are real.  The centre of every live tracked row of a
+    class set in ``table`` (device uint8 [C], ``redact_table``'s form) steps the entry of its id in ``state`` (``count_state``;
+    ``capacity``: its entries, read from its size when None) and is tested against ``lines`` ((n, 4) host integers, ax, ay, bx, by); a
+    crossing counts once per id, line and direction.  Entries not seen for more than ``expire`` frames leave, and frame f's count list
+    lands in ``lists[f]`` (``count_workspace``; allocated here when None; a captured call passes it) -> ``lists``.  ``gate``: None, or a
+    device word that is 0 when no frame of the call is real, whatever ``n_frames`` says.  The call can be captured in a graph."""
+    _require_gpu()
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.dim() == 2 and tracked.is_contiguous()
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert gate is None or (gate.is_cuda and gate.dtype == torch.int32 and gate.numel() >= 1)
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    if capacity is None:
+        capacity = (int(state.numel()) - COUNT_HEAD) // COUNT_ENTRY
+    frames, words = int(tracked.shape[0]), int(tracked.shape[1])
+    assert (words - 4) % 8 == 0
+    if lists is None:
+        lists = count_workspace(frames)
+    assert int(state.numel()) == count_state_words(capacity)
+    assert lists.is_cuda and lists.dtype == torch.int32 and lists.is_contiguous() and tuple(lists.shape) == (frames, COUNT_LIST_WORDS)
+    keep, lines_p, n_lines = _count_lines_arg(lines)
+    _lib.call("frcnn_count_update", _p(state), int(capacity), _p(tracked), words, (words - 4) // 8, frames, _p(n_frames), _p(gate), lines_p,
+              n_lines, _p(table), int(table.numel()), int(expire), int(h), int(w), _p(lists), _stream())
+    return lists
+
+
+def count_draw_u8(frame, clist, lines, width=None, rgb=False):
+    """DRAW of the count rule (frcnn_count_draw_u8): ``lines`` drawn into ``frame``, an (h, w, 3) uint8 device tensor, edited in place and
+    returned: each line a capsule of ``width`` pixels (None: 3) in PALETTE[l & 7], and above them a label "L{l} +{pos} -{neg}" per line
+    with the totals of ``clist`` -- one count list of ``count_update`` --, formatted on the device.  A list of a frame that is not real
+    draws nothing.  ``rgb``: the frame's bytes are R, G, B (False: B, G, R).  One launch; the list is read on the device, so the call can
+    be captured in a graph."""
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert clist.is_cuda and clist.dtype == torch.int32 and clist.dim() == 1 and clist.is_contiguous() and int(clist.numel()) == COUNT_LIST_WORDS
+    keep, lines_p, n_lines = _count_lines_arg(lines)
+    _lib.call("frcnn_count_draw_u8", _p(frame), int(frame.shape[0]), int(frame.shape[1]), _p(clist), lines_p, n_lines,
+              COUNT_WIDTH[2] if width is None else int(width), int(bool(rgb)), _stream())
+    return frame
+
+
+def count_totals(state):
+    """(host only; reads the state back) The totals of a count state, device tensor or host copy -> {"frames", "dropped",
+    "events_dropped", "entries", "totals": [(neg, pos)] * 8} -- totals[l] = (crossings of line l in direction -, in direction +)."""
+    s = state.cpu().numpy() if isinstance(state, torch.Tensor) else np.asarray(state)
+    return {"entries": int(s[0]), "frames": int(s[1]), "dropped": int(s[2]), "events_dropped": int(s[3]),
+            "totals": [(int(s[4 + 2 * l]), int(s[5 + 2 * l])) for l in range(COUNT_MAX_LINES)]}
+
+
+def count_events(clist):
+    """(host only) The events of one count list's HOST copy -> [(line, dir, id, cls)], in (row, line) order."""
+    c = np.asarray(clist)
+    return [tuple(int(v) for v in c[COUNT_HEAD + 4 * k:COUNT_HEAD + 4 * k + 4]) for k in range(min(max(int(c[0]), 0), COUNT_MAX_EVENTS))]
+
+
 TRACK_LOOKBACK = _lib.TRACK_LOOKBACK            # (smallest, largest, the default) look-back of ``track_lookback``, in frames
 
 
