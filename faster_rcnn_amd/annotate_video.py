@@ -113,6 +113,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _lib, entry, ops, shapes, voc_dets, y4m
+from .frame_edit import EditChain, EditStates
 from .util import resize_imgs
 
 STRIDE = 16                                       # get_dets' default: annotate_video.py:29 passes none
@@ -265,12 +266,7 @@ def _pack_dets(dets, class_mapping):
     return packed
 
 
-_EAGER_TABLES = {}
-_EAGER_REDACT_TABLES = {}
-_EAGER_TRACKERS = {}                                      # class mapping -> [state, {redact classes: table}, the one-frame count word]
-_EAGER_MOTION = {}                                        # (class mapping, h, w) -> that tracker's motion state for frames of the size
-_EAGER_TRAILS = {}                                        # (class mapping, N) -> that tracker's trail state for trails of N points
-_EAGER_HEAT = {}                                          # (class mapping, h, w) -> the eager path's heat state for frames of the size
+_EAGER_STATES = {}                                        # class mapping -> the eager path's EditStates
 
 
 def _names_by_index(class_mapping):
@@ -278,156 +274,69 @@ def _names_by_index(class_mapping):
     return [rev.get(i, "") for i in range(max(rev) + 1)]
 
 
-def _eager_tracker(class_mapping):
-    import torch
+def _eager_states(class_mapping):
+    """The eager path's editing states (frame_edit.EditStates) of this class mapping, made on first use: a tracker of
+    entry.TRACK_CAPACITY slots, trail and count states of twice as many entries."""
     key = tuple(sorted(class_mapping.items()))
-    t = _EAGER_TRACKERS.get(key)
-    if t is None:
-        t = _EAGER_TRACKERS[key] = [ops.track_state(entry.TRACK_CAPACITY), {}, torch.ones(1, dtype=torch.int32, device="cuda")]
-    return t
-
-
-def _eager_motion_state(class_mapping, h, w):
-    """The eager path's motion state (ops.track_motion_state) of this class mapping's tracker for (h, w) frames, made on first use."""
-    key = (tuple(sorted(class_mapping.items())), int(h), int(w))
-    m = _EAGER_MOTION.get(key)
-    if m is None:
-        m = _EAGER_MOTION[key] = ops.track_motion_state(h, w)
-    return m
-
-
-_EAGER_COUNT = {}                                         # class mapping -> that tracker's count state
+    states = _EAGER_STATES.get(key)
+    if states is None:
+        states = _EAGER_STATES[key] = EditStates(_names_by_index(class_mapping), entry.TRACK_CAPACITY,
+                                                 min(2 * entry.TRACK_CAPACITY, ops.TRACK_MAX))
+    return states
 
 
 def _eager_count_state(class_mapping):
-    """The eager path's count state (ops.count_state) of this class mapping's tracker."""
-    key = tuple(sorted(class_mapping.items()))
-    c = _EAGER_COUNT.get(key)
-    if c is None:
-        c = _EAGER_COUNT[key] = ops.count_state(min(2 * entry.TRACK_CAPACITY, ops.TRACK_MAX))
-    return c
+    return _eager_states(class_mapping).count_state()
 
 
 def _eager_trails_state(class_mapping, length):
-    """The eager path's trail state (ops.track_trails_state) of this class mapping's tracker for trails of ``length`` points."""
-    key = (tuple(sorted(class_mapping.items())), int(length))
-    t = _EAGER_TRAILS.get(key)
-    if t is None:
-        t = _EAGER_TRAILS[key] = ops.track_trails_state(min(2 * entry.TRACK_CAPACITY, ops.TRACK_MAX), length)
-    return t
+    return _eager_states(class_mapping).trails_state(length)
 
 
 def _eager_heat_state(class_mapping, h, w):
-    """The eager path's heat state (ops.heat_state) of this class mapping for (h, w) frames, made on first use."""
-    key = (tuple(sorted(class_mapping.items())), int(h), int(w))
-    m = _EAGER_HEAT.get(key)
-    if m is None:
-        m = _EAGER_HEAT[key] = ops.heat_state(h, w)
-    return m
-
-
-def _eager_track_table(tracker, class_mapping, redact_classes):
-    table = tracker[1].get(redact_classes)
-    if table is None:
-        names = _names_by_index(class_mapping)
-        chosen = [n for n in names if n and n != "bg" and n not in ops.ANNOTATE_SKIP]
-        if redact_classes is not None:
-            chosen += [n for n in ops.redact_class_list(names, redact_classes) if n not in chosen]
-        table = tracker[1][redact_classes] = ops.track_table(names, chosen)
-    return table
+    return _eager_states(class_mapping).heat_state(h, w)
 
 
 def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
                track_trails=None, rgb=False, heatmap=None, count=None):
-    """One ops.annotate_u8 over host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is drawn into in place.
-    ``redact`` = (classes, mode, size, margin): one ops.redact_u8 in front of it; ``draw`` False: no drawing.
-    ``track`` = (thr, hold, grow): one ops.track_update (one frame) in front of both, on this class mapping's eager tracker state
-    (``reset_tracks`` empties it); ``dets`` is edited in place as ``collect_batch`` returns it: "track_id" on every det, the held rows
-    appended with "held".  ``track_motion`` = R: ops.track_update_motion in its place, with the frame as it came and this class mapping's
-    motion state for the frame's size.  ``track_scene_cut`` = PCT (with ``track_motion``): ops.track_update_cut with interval 1 in its
-    place -- the kept frame is the reference --, and ``info``, a dict, receives "scene_cut": True when the frame is a cut.
-    ``track_trails`` = (N, W) (with ``track``, not with ``draw`` False): a one-frame ops.track_trails_update behind the tracker call, on
-    this class mapping's eager trail state, and one ops.track_trails_draw_u8 between the redaction and the drawing step; ``rgb``: the
-    frame's channel order (False: B, G, R).
-    ``heatmap`` = (classes, A, S): a one-frame ops.heat_update on this class mapping's eager heat state for the frame's size (``reset_heat``
-    empties it) -- the detections, or with ``track`` the live tracked rows -- and one ops.heat_draw_u8 between the redaction and the
-    trails; a frame without detections is blended too.
-    ``count`` = (lines, classes, W) (with ``track``): a one-frame ops.count_update behind the tracker call, on this class mapping's eager
-    count state (``reset_counts`` zeroes it), one ops.count_draw_u8 behind the trails and in front of the drawing step unless ``draw`` is
-    False, and ``info`` receives "crossings": [(line, dir, id, cls)]."""
+    """The editing chain over ONE frame and its host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is edited in
+    place, by a one-frame ``frame_edit.EditChain`` -- its docstring states the calls and their order -- on this class mapping's eager
+    states (``reset_tracks``, ``reset_heat`` and ``reset_counts`` empty them); ``rgb``: the frame's channel order (False: B, G, R).
+    ``redact`` = (classes, mode, size, margin); ``draw`` False: nothing is drawn.
+    ``track`` = (thr, hold, grow): ``dets`` is edited in place as ``collect_batch`` returns it: "track_id" on every det, the held rows
+    appended with "held".  ``track_motion`` = R: the motion step, with the frame as it came and this class mapping's motion state for the
+    frame's size.  ``track_scene_cut`` = PCT (with ``track_motion``): the cut step -- the kept frame is the reference --, and ``info``, a
+    dict, receives "scene_cut": True when the frame is a cut.
+    ``track_trails`` = (N, W) (with ``track``, not with ``draw`` False).
+    ``heatmap`` = (classes, A, S): the detections, or with ``track`` the live tracked rows, heat this class mapping's state for the
+    frame's size; a frame without detections is blended too.
+    ``count`` = (lines, classes, W) (with ``track``): ``info`` receives "crossings": [(line, dir, id, cls)]."""
     import torch
     track_trails = _track_trails(track_trails, track, draw)
     heatmap = _heatmap(heatmap)
     count = _count(count, track)
-    if track_motion is not None and track is None:
-        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
-    _track_scene_cut(track_scene_cut, track, track_motion, None, None)
-    key = tuple(sorted(class_mapping.items()))
+    radius = _track_motion(track_motion, track)
+    track_scene_cut = _track_scene_cut(track_scene_cut, track, track_motion, None, None)
     if track is not None or heatmap is not None or (dets and (draw or redact is not None)):      # (nothing to draw or hide: the frame stays as it is)
         dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
         packed = torch.from_numpy(_pack_dets(dets, class_mapping)).cuda()
-        classes = None
         if redact is not None:
-            classes, mode, size, margin = redact
-            classes = classes if classes == "all" else tuple(classes)
+            redact = (redact[0] if redact[0] == "all" else tuple(redact[0]),) + tuple(redact[1:])
+        states = _eager_states(class_mapping)
+        spec = entry.PassSpec(annotate=True, redact=redact, draw=draw, track=track, track_scene_cut=track_scene_cut, track_trails=track_trails,
+                              track_motion=radius, heat=heatmap, count=count)
+        chain = EditChain(states, spec, 1, 1, frame.shape[:2], rgb)
+        chain.update(dev.view(-1), 0, packed, states.one_frame())         # (in front of the edits: ``dev`` is still the frame as it came)
+        chain.edit(0, dev)
         if track is not None:
-            tracker = _eager_tracker(class_mapping)
-            t_table = _eager_track_table(tracker, class_mapping, classes)
-            if track_scene_cut is not None:                         # (one frame: its reference is the kept frame)
-                rows, cuts = ops.track_update_cut(tracker[0], _eager_motion_state(class_mapping, frame.shape[0], frame.shape[1]), dev.view(-1), 0,
-                                                  packed, tracker[2], t_table, frame.shape[0], frame.shape[1], *track,
-                                                  ops.track_motion_radius(track_motion), 1, ops.track_cut_option(track_scene_cut))
-                rows = rows[0]
-                if info is not None and int(cuts[0]):
-                    info["scene_cut"] = True
-            elif track_motion is not None:                          # (in front of the redaction: ``dev`` is still the frame as it came)
-                rows = ops.track_update_motion(tracker[0], _eager_motion_state(class_mapping, frame.shape[0], frame.shape[1]), dev.view(-1), 0,
-                                               packed, tracker[2], t_table, frame.shape[0], frame.shape[1], *track,
-                                               ops.track_motion_radius(track_motion))[0]
-            else:
-                rows = ops.track_update(tracker[0], packed, tracker[2], t_table, frame.shape[0], frame.shape[1], *track)[0]
-            n_rows, _, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(rows.cpu().numpy())
-            rev = {v: k for k, v in class_mapping.items()}
+            _, ids, held = ops.tracked_dets(chain.track_out[0].cpu().numpy(), _names_by_index(class_mapping), start=len(dets))
             for k, d in enumerate(dets):
-                d["track_id"] = int(t_id[k])
-            dets += [{"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(), "track_id": int(t_id[k]),
-                      "held": int(t_age[k])} for k in range(len(dets), int(n_rows[0]))]
-        else:
-            rows = packed
-        if redact is not None:
-            table = _EAGER_REDACT_TABLES.get((key, classes))
-            if table is None:
-                table = _EAGER_REDACT_TABLES[(key, classes)] = ops.redact_table(_names_by_index(class_mapping), classes)
-            ops.redact_u8(dev, rows, table, mode, size, margin, tracked=track is not None)
-        if heatmap is not None:
-            h_classes, h_alpha, h_decay = heatmap
-            h_table = _EAGER_REDACT_TABLES.get((key, h_classes))
-            if h_table is None:
-                h_table = _EAGER_REDACT_TABLES[(key, h_classes)] = ops.redact_table(_names_by_index(class_mapping), h_classes)
-            h_state = _eager_heat_state(class_mapping, frame.shape[0], frame.shape[1])
-            ops.heat_update(h_state, frame.shape[0], frame.shape[1], rows, h_table, h_decay, tracked=track is not None)
-            ops.heat_draw_u8(dev, h_state, h_alpha, rgb=rgb)
-        if track_trails is not None:
-            length, width = track_trails
-            lists = ops.track_trails_update(_eager_trails_state(class_mapping, length), rows.view(1, -1), tracker[2], length,
-                                            entry.DetectionEntry.track_trails_expire(track, None), frame.shape[0], frame.shape[1])
-            ops.track_trails_draw_u8(dev, lists[0], length, width, rgb=rgb)
-        if count is not None:
-            c_lines, c_classes, c_width = count
-            c_table = _EAGER_REDACT_TABLES.get((key, c_classes))
-            if c_table is None:
-                c_table = _EAGER_REDACT_TABLES[(key, c_classes)] = ops.redact_table(_names_by_index(class_mapping), c_classes)
-            clists = ops.count_update(_eager_count_state(class_mapping), rows.view(1, -1), tracker[2], c_lines, c_table,
-                                      entry.DetectionEntry.track_trails_expire(track, None), frame.shape[0], frame.shape[1])
-            if draw:
-                ops.count_draw_u8(dev, clists[0], c_lines, c_width, rgb=rgb)
-            if info is not None:
-                info["crossings"] = ops.count_events(clists[0].cpu().numpy())
-        if draw:
-            tables = _EAGER_TABLES.get(key)
-            if tables is None:
-                tables = _EAGER_TABLES[key] = ops.annotate_tables(_names_by_index(class_mapping))
-            ops.annotate_u8(dev, rows, tables, tracked=track is not None)
+                d["track_id"] = int(ids[k])
+            dets += held
+        if info is not None and track_scene_cut is not None and int(chain.cuts[0]):
+            info["scene_cut"] = True
+        if info is not None and count is not None:
+            info["crossings"] = ops.count_events(chain.count_lists[0].cpu().numpy())
         frame[...] = dev.cpu().numpy()
     return frame
 
@@ -614,6 +523,15 @@ def track_scene_cut_from_args(args):
         raise ValueError("--track_scene_cut: %s" % e) from None
 
 
+def _track_motion(track_motion, track):
+    """``draw_eager``'s ``track_motion`` checked -> the search radius, or None."""
+    if track_motion is None:
+        return None
+    if track is None:
+        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
+    return ops.track_motion_radius(track_motion)
+
+
 def _track_scene_cut(track_scene_cut, track, track_motion, track_lookback, track_backtrack):
     """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame``'s ``track_scene_cut`` checked -> the percentage, or None."""
     if track_scene_cut is None:
@@ -755,7 +673,7 @@ def _write_counts(counts_out, frame_no, crossings, class_mapping):
 
 def _count_state(training_manager, eng):
     """The count state of ``eng``, or of the eager path with None."""
-    return eng.count_state() if eng is not None else _eager_count_state(training_manager.class_mapping)
+    return eng.count_state() if eng is not None else _eager_states(training_manager.class_mapping).count_state()
 
 
 def reset_counts(training_manager, detector, in_flight=1):
@@ -765,7 +683,7 @@ def reset_counts(training_manager, detector, in_flight=1):
     if eng is not None:
         eng.count_reset()
     else:
-        ops.count_reset(_eager_count_state(training_manager.class_mapping))
+        _eager_states(training_manager.class_mapping).reset_counts()
 
 
 def heatmap_from_args(args, class_mapping):
@@ -835,10 +753,8 @@ def _heat_states(training_manager, eng):
     """The host copies of the heat states of ``eng``, or of the eager path with None: {(h, w): numpy int32}."""
     import torch
     torch.cuda.synchronize()
-    if eng is not None:
-        return {hw: st.cpu().numpy() for hw, st in eng._heat_states.items()}
-    key = tuple(sorted(training_manager.class_mapping.items()))
-    return {(k[1], k[2]): st.cpu().numpy() for k, st in _EAGER_HEAT.items() if k[0] == key}
+    states = eng.edit_states if eng is not None else _eager_states(training_manager.class_mapping)
+    return {hw: st.cpu().numpy() for hw, st in states.heat.items()}
 
 
 def reset_heat(training_manager, detector, in_flight=1):
@@ -847,10 +763,7 @@ def reset_heat(training_manager, detector, in_flight=1):
     if eng is not None:
         eng.heat_reset()
     else:
-        key = tuple(sorted(training_manager.class_mapping.items()))
-        for k, state in _EAGER_HEAT.items():
-            if k[0] == key:
-                ops.heat_reset(state)
+        _eager_states(training_manager.class_mapping).reset_heat()
 
 
 def _lookback_frames(track_lookback, track, eng, B):
@@ -894,16 +807,7 @@ def reset_tracks(training_manager, detector, in_flight=1):
     if eng is not None:
         eng.track_reset()
     else:
-        ops.track_reset(_eager_tracker(training_manager.class_mapping)[0])
-        key = tuple(sorted(training_manager.class_mapping.items()))
-        for k, mstate in _EAGER_MOTION.items():
-            if k[0] == key:
-                ops.track_motion_reset(mstate)
-        for k, trails in _EAGER_TRAILS.items():
-            if k[0] == key:
-                ops.track_reset(trails)
-        if key in _EAGER_COUNT:                                     # the ids end; what was counted stays counted
-            ops.count_reset(_EAGER_COUNT[key], keep_totals=True)
+        _eager_states(training_manager.class_mapping).reset_tracks()
 
 
 def _print_drawn(dets, width, height):

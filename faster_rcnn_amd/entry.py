@@ -38,6 +38,7 @@ import torch
 
 from . import _lib, models, ops
 from ._lib import FrcnnError
+from .frame_edit import EditChain, EditStates
 from .pipeline import BatchedInferencePipeline, InferencePipeline, no_gc
 from .shapes import declares as _declares
 
@@ -462,18 +463,18 @@ class PassSpec:
 
 class _Slot:
     """One captured pass for one image size (or canvas class), with its staging on both sides of PCIe.  Every field exists on every slot;
-    what a kind of pass does not use stays None (``tabs`` / ``frame_io``: exact passes; ``extents`` / ``_ext_raw``: canvas passes; ``png_*``:
+    what a kind of pass does not use stays None (``tabs`` / ``frame_io``: exact passes; ``chain``: annotating passes, the
+    ``EditChain`` that holds their tracked buffers and lists; ``extents`` / ``_ext_raw``: canvas passes; ``png_*``:
     annotating passes that encode on the device -- a PNG or, with ``quality``, a JPEG file; ``first_copy``: the bytes of a JPEG row that
     are read back with every replay)."""
     __slots__ = ("key", "pipe", "graph", "out", "io_dev", "io_pin", "dyn_host", "out_pin", "event", "busy", "nbytes", "x_f32", "ws", "tabs", "u8_resized",
                  "batch", "pix_hosts", "out_packed", "amax", "_out_raw", "ready", "extents", "seg", "canvas", "_ext_raw", "annotate", "frame_io",
                  "encode", "png_dev", "png_ws", "png_bound", "png_pin", "_png_raw", "quality", "first_copy", "jpeg_mode",
                  "jpg_pin", "jpg_dev", "jpg_ws", "jpg_status", "jpg_status_pin", "jpg_names", "jpg_area", "jpg_items", "jpg_used",
-                 "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "redact_ws",
-                 "track", "track_out", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
-                 "track_lookback", "lb_out", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
-                 "track_scene_cut", "cut_ws", "cuts", "cuts_pin", "_cuts_raw", "track_trails", "trail_lists", "heat",
-                 "count", "count_lists", "count_pin", "_count_raw")
+                 "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "chain",
+                 "track", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
+                 "track_lookback", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
+                 "track_scene_cut", "cuts_pin", "_cuts_raw", "track_trails", "heat", "count", "count_pin", "_count_raw")
 
     def __init__(self):
         for name in self.__slots__:
@@ -618,16 +619,11 @@ class DetectionEntry:
         self._taps_dev = {}
         self._pinned = _PinnedArena()                    # (per engine: the blocks go when the engine goes)
         self.capture_breakdown = {}
-        self._annotate_tables = None
-        self._nodraw_tables = None
-        self._redact_tables = {}
-        self._track_state = None                         # the engine's ONE tracker state (ops.track_state): its pointer is in the graphs
-        self._track_trails_states = {}                   # length N -> the engine's trail state (ops.track_trails_state) beside the tracker state
-        self._count_state = None                         # the engine's ONE count state (ops.count_state): its pointer is in the graphs
-        self._heat_states = {}                           # (h, w) of the source frames -> ops.heat_state: their pointers are in the graphs
-        self._track_tables = {}
-        self._track_motion_states = {}                   # (h, w) of the source frames -> ops.track_motion_state: their pointers are in the graphs
-        self._track_lookback_windows = {}                # (h, w, B) -> ops.track_lookback_state: the frames tracked but not yet emitted
+        # the engine's ONE set of editing states (their pointers are in the graphs): a tracker of TRACK_CAPACITY slots, fewer when the
+        # post-process's rows leave less room under the drawing and redaction kernels' 512 rows; a trail outlives its track by a frame,
+        # and behind a scene cut the old scene's trails wait for their expiry while every slot already has a new id: twice the slots
+        cap = min(TRACK_CAPACITY, _lib.REDACT_MAX_ROWS - -(-MAX_PROPOSALS // self.num_rois) * self.num_rois)
+        self.edit_states = EditStates(self.class_names(), cap, min(2 * cap, ops.TRACK_MAX))
         self._lookback_waiting = {}                      # (h, w, B) -> the record of the group its window holds ({"images", "n_rois"})
         self._lookback_last = None                       # (key, capture) of the last look-back submit: what a flush submit replays
 
@@ -637,23 +633,12 @@ class DetectionEntry:
         return [rev.get(i, "") for i in range(max(rev) + 1)]
 
     def annotate_tables(self, draw=True):
-        """The drawing tables of ops.annotate_u8 for this engine's classes (uploaded once).  ``draw`` False: the same tables with no
-        drawable class -- the drawing step of a pass that only redacts paints nothing, with no branch in the pass."""
-        if not draw:
-            if self._nodraw_tables is None:
-                names = self.class_names()
-                self._nodraw_tables = ops.annotate_tables(names, skip=tuple(names))
-            return self._nodraw_tables
-        if self._annotate_tables is None:
-            self._annotate_tables = ops.annotate_tables(self.class_names())
-        return self._annotate_tables
+        """The drawing tables of ops.annotate_u8 for this engine's classes (``EditStates.annotate_tables``)."""
+        return self.edit_states.annotate_tables(draw)
 
     def redact_table(self, classes):
         """The class table of ops.redact_u8 for ``classes`` ("all" or a tuple of names) of this engine's classes (uploaded once each)."""
-        t = self._redact_tables.get(classes)
-        if t is None:
-            t = self._redact_tables[classes] = ops.redact_table(self.class_names(), classes)
-        return t
+        return self.edit_states.redact_table(classes)
 
     def redact_option(self, redact):
         """``submit_batch``'s ``redact`` checked and normalised -> (classes, mode, size, margin): classes "all" or a tuple of this
@@ -675,16 +660,12 @@ class DetectionEntry:
     def heat_state(self, h, w):
         """The engine's heat state for source frames of (h, w) (device int32, ops.heat_state), made on first use: one per size, shared by
         every pass submitted with ``heat=`` whatever its other options.  ``heat_reset()`` empties it; ``track_reset()`` does not."""
-        state = self._heat_states.get((h, w))
-        if state is None:
-            state = self._heat_states[(h, w)] = ops.heat_state(h, w)
-        return state
+        return self.edit_states.heat_state(h, w)
 
     def heat_reset(self):
         """A cold map for every size: the states are zeroed on the ordered stream, behind the heat passes submitted so far."""
         with torch.cuda.stream(self.track_stream):
-            for state in self._heat_states.values():
-                ops.heat_reset(state)
+            self.edit_states.reset_heat()
 
     def heat_option(self, heat):
         """``submit_batch``'s ``heat`` checked and normalised -> (classes, A, S): classes "all" or a tuple of this engine's class names,
@@ -708,28 +689,20 @@ class DetectionEntry:
         return self._streams[0]
 
     def track_state(self):
-        """The engine's tracker state (device int32, ops.track_state), made on first use: TRACK_CAPACITY slots, fewer when the
-        post-process's rows leave less room under the drawing and redaction kernels' 512 rows."""
-        if self._track_state is None:
+        """The engine's tracker state (device int32, ops.track_state), made on first use: ``edit_states.track_capacity`` slots."""
+        if self.edit_states.track_capacity < 1:
             rows = -(-MAX_PROPOSALS // self.num_rois) * self.num_rois
-            cap = min(TRACK_CAPACITY, _lib.REDACT_MAX_ROWS - rows)
-            if cap < 1:
-                raise FrcnnError("track=: the post-process's %d rows leave no room for held rows (at most %d rows in all)" % (rows, _lib.REDACT_MAX_ROWS))
-            self._track_state = ops.track_state(cap)
-        return self._track_state
+            raise FrcnnError("track=: the post-process's %d rows leave no room for held rows (at most %d rows in all)" % (rows, _lib.REDACT_MAX_ROWS))
+        return self.edit_states.tracker()
 
     def track_trails_state(self, length):
         """The engine's trail state for trails of ``length`` points (device int32, ops.track_trails_state), made on first use, of
         ``track_trails_capacity()`` trails.  ``track_reset()`` empties it."""
-        state = self._track_trails_states.get(length)
-        if state is None:
-            state = self._track_trails_states[length] = ops.track_trails_state(self.track_trails_capacity(), length)
-        return state
+        return self.edit_states.trails_state(length)
 
     def track_trails_capacity(self):
-        """The trails of the engine's trail state: twice the tracker's slots, at most ops.TRACK_MAX.  A trail outlives its track by a
-        frame, and behind a scene cut the old scene's trails wait for their expiry while every slot already has a new id."""
-        return min(2 * ops.track_capacity(self.track_state()), ops.TRACK_MAX)
+        """The trails of the engine's trail state: twice the tracker's slots, at most ops.TRACK_MAX."""
+        return self.edit_states.trail_capacity
 
     @staticmethod
     def track_trails_option(value):
@@ -739,26 +712,19 @@ class DetectionEntry:
         except ValueError as e:
             raise FrcnnError("submit_batch: track_trails=%r: %s" % (value, e)) from None
 
-    @staticmethod
-    def track_trails_expire(track, detect_every):
-        """The frames a trail outlives its last point in a pass with ``track`` = (thr, hold, grow): (hold + 1) * K, K = ``detect_every``
-        or 1 -- as long as the tracker can still re-match the id -- and at most the rule's 4095."""
-        return min((track[1] + 1) * (detect_every or 1), ops.TRACK_TRAILS[2])
+    track_trails_expire = staticmethod(EditChain.trails_expire)
 
     # ------------------------------------------------------------------ line counts
     def count_state(self):
         """The engine's count state (device int32, ops.count_state), made on first use, of ``track_trails_capacity()`` entries: one,
         shared by every pass submitted with ``count=``.  ``count_reset()`` empties it, totals included; ``track_reset()`` drops its
         entries -- the ids end -- and leaves the totals.  ``ops.count_totals`` reads it."""
-        if self._count_state is None:
-            self._count_state = ops.count_state(self.track_trails_capacity())
-        return self._count_state
+        return self.edit_states.count_state()
 
     def count_reset(self):
         """Zero totals and no entries: the state is zeroed on the ordered stream, behind the counting passes submitted so far."""
-        if self._count_state is not None:
-            with torch.cuda.stream(self.track_stream):
-                ops.count_reset(self._count_state)
+        with torch.cuda.stream(self.track_stream):
+            self.edit_states.reset_counts()
 
     def count_option(self, count):
         """``submit_batch``'s ``count`` checked and normalised -> (lines, classes, W): lines a tuple of 1..8 (ax, ay, bx, by), classes
@@ -776,34 +742,18 @@ class DetectionEntry:
         return lines, classes, width
 
     def track_reset(self):
-        """Forget every track: the state is zeroed on the tracking stream, behind the tracked passes submitted so far."""
-        state = self.track_state()
+        """Forget every track: the states are zeroed on the tracking stream, behind the tracked passes submitted so far
+        (``EditStates.reset_tracks``: the motion headers, the look-back windows, the trails and the count entries with them)."""
+        self.track_state()
         with torch.cuda.stream(self.track_stream):
-            ops.track_reset(state)
-            for mstate in self._track_motion_states.values():       # ... and no frame is the one in front of the next
-                ops.track_motion_reset(mstate)
-            for window, _ in self._track_lookback_windows.values():  # ... and no frame waits to be emitted
-                ops.track_lookback_reset(window)
-            for trails in self._track_trails_states.values():       # ... and no path has begun
-                ops.track_reset(trails)
-            if self._count_state is not None:                       # ... and no id waits for its next step; what was counted stays
-                ops.count_reset(self._count_state, keep_totals=True)
+            self.edit_states.reset_tracks()
         self._lookback_waiting.clear()
         self._lookback_last = None
 
     def track_lookback_window(self, h, w, B, rows=None):
-        """-> (the engine's look-back window for passes of B source frames of (h, w) (ops.track_lookback_state), its ``back``: the
-        tracker's capacity where the rows leave room), made on first use, by a pass that knows the ``rows`` of its packed buffers.
-        ``track_reset()`` empties it."""
-        win = self._track_lookback_windows.get((h, w, B))
-        if win is None:
-            cap = ops.track_capacity(self.track_state())
-            back = min(cap, _lib.REDACT_MAX_ROWS - rows - cap)
-            if back < 1:
-                raise FrcnnError("track_lookback=: %d rows and %d tracks leave no room for back-filled rows (at most %d rows in all)"
-                                 % (rows, cap, _lib.REDACT_MAX_ROWS))
-            win = self._track_lookback_windows[(h, w, B)] = (ops.track_lookback_state(B, h, w, rows, cap, back), back)
-        return win
+        """-> (the engine's look-back window for passes of B source frames of (h, w) (ops.track_lookback_state), its ``back``), made on
+        first use, by a pass that knows the ``rows`` of its packed buffers.  ``track_reset()`` empties it."""
+        return self.edit_states.lookback_window(h, w, B, rows)
 
     @staticmethod
     def track_lookback_option(n, B):
@@ -828,23 +778,12 @@ class DetectionEntry:
 
     def track_motion_state(self, h, w):
         """The engine's motion state for source frames of (h, w) (ops.track_motion_state), made on first use: the passes submitted with
-        ``track_motion=`` keep their last frame in it.  A sequence that changes its frame size has no reference on the first frame of
-        the new size: the header of the new size's state does not carry the tracker's frame count."""
-        m = self._track_motion_states.get((h, w))
-        if m is None:
-            m = self._track_motion_states[(h, w)] = ops.track_motion_state(h, w)
-        return m
+        ``track_motion=`` keep their last frame in it."""
+        return self.edit_states.motion_state(h, w)
 
     def track_table(self, redact_classes=None):
         """The class table of ops.track_update: the classes the drawing rule draws united with ``redact_classes`` (uploaded once each)."""
-        t = self._track_tables.get(redact_classes)
-        if t is None:
-            names = self.class_names()
-            chosen = [n for n in names if n and n != "bg" and n not in ops.ANNOTATE_SKIP]
-            if redact_classes is not None:
-                chosen += [n for n in ops.redact_class_list(names, redact_classes) if n not in chosen]
-            t = self._track_tables[redact_classes] = ops.track_table(names, chosen)
-        return t
+        return self.edit_states.track_table(redact_classes)
 
     @staticmethod
     def track_option(track):
@@ -927,8 +866,8 @@ class DetectionEntry:
     def _exact_pass(self, s, fine, H, W, src, flip):
         """The buffers and the pass of an exact-geometry slot; resize and preprocess are INSIDE the pass.  ``src`` = (source height,
         source width): the pass starts from the decoded frame at the file's size and resizes (and flips) it on the device; None: the
-        uploaded pixels are already (H, W).  An annotating pass then draws each frame's detections into its uploaded source frame
-        (ops.annotate_u8, annotate_video.py); with ``s.encode`` == "png" or "png-huffman" it then encodes the drawn frame as a PNG file on
+        uploaded pixels are already (H, W).  An annotating pass then edits each uploaded source frame where it lies (``s.chain``, an
+        ``EditChain``: redaction, heat map, trails, count lines, boxes and labels, in the order its docstring states); with ``s.encode`` == "png" or "png-huffman" it then encodes the drawn frame as a PNG file on
         the device (ops.png_encode_u8, compress "runs" or "huffman") into the slot's own buffer, which is what such a pass reads back
         instead of the raw frame; with ``s.encode`` == "jpeg" as a JPEG file at ``s.quality`` in ``s.jpeg_mode`` = (subsampling, huffman)
         (ops.jpeg_encode_u8)."""
@@ -952,55 +891,17 @@ class DetectionEntry:
             s.x_f32 = s.io_dev[:pix_bytes].view(torch.float32).view(1, H, W, 3)
         # annotating pass: frame i is read back from its staging segment into the slot's own pinned segment after the replay
         s.frame_io = [(s.io_dev[i * seg:i * seg + npix], s.io_pin[i * seg:i * seg + npix]) for i in range(F)] if annotate and not s.encode else None
-        tables = self.annotate_tables(not s.nodraw) if annotate else None
-        if s.redact:
-            # the redacted classes' boxes are hidden in each source frame IN FRONT of the drawing step, and so in front of every encoder;
-            # one workspace serves the frames of a pass, which are redacted one after another
-            r_classes, r_mode, r_size, r_margin = s.redact
-            r_table = self.redact_table(r_classes)
-            s.redact_ws = torch.empty(max(ops.redact_ws_bytes(in_h, in_w, r_mode, r_size), 16), dtype=torch.uint8, device="cuda")
-        if s.track:
-            # ONE tracker update over the pass's B frames behind the post-process: the redaction then reads every tracked row (the held
-            # boxes are hidden), the drawing step the live rows with their ids
-            t_thr, t_hold, t_grow = s.track
-            t_state, t_table = self.track_state(), self.track_table(s.redact[0] if s.redact else None)
-            # with ``track_motion``: the block match moves the slots between the frames, which lie ``seg`` bytes apart in the staging
-            # area and are still as they were uploaded -- the call stays in front of every redaction and drawing step of the pass
-            t_motion = self.track_motion_state(in_h, in_w) if s.track_motion else None
-            if s.track_scene_cut:
-                s.cut_ws, s.cuts = ops.track_cut_workspace(F), torch.zeros(F, dtype=torch.int32, device="cuda")
-            if s.track_trails:
-                # ONE trail update behind the tracker call (behind the look-back / back-track call of a delayed pass) over the tracked
-                # buffers the drawing step reads, then each frame's trails drawn over its redaction and under its boxes
-                tr_length, tr_width = s.track_trails
-                tr_state, tr_expire = self.track_trails_state(tr_length), self.track_trails_expire(s.track, s.every)
-                s.trail_lists = ops.track_trails_workspace(F, self.track_trails_capacity(), tr_length)
-                trails_rgb = src is not None and bool(int(flip) & 2)        # (the channel order the frames were uploaded in: ``uploaded_rgb``)
-            if s.count:
-                # ONE count update behind the tracker call (behind the look-back / back-track call of a delayed pass), where the trail
-                # update sits, then each frame's lines and totals drawn over its redaction, heat and trails and under its boxes
-                c_lines, c_classes, c_width = s.count
-                c_state, c_table, c_expire = self.count_state(), self.redact_table(c_classes), self.track_trails_expire(s.track, s.every)
-                s.count_lists = ops.count_workspace(F)
-                s.count_lists.zero_()
-                count_rgb = src is not None and bool(int(flip) & 2)
-        if s.heat:
-            # each frame: one heat update from the rows the redaction reads (the live ones of a tracked buffer), then the map blended in,
-            # over the redaction and under the trails, the boxes and the labels.  The engine's state of this frame size lives across passes.
-            h_classes, h_alpha, h_decay = s.heat
-            h_state, h_table = self.heat_state(in_h, in_w), self.redact_table(h_classes)
-            heat_rgb = src is not None and bool(int(flip) & 2)              # (the channel order the frames were uploaded in: ``uploaded_rgb``)
-        if s.track_lookback:
-            # the frames, as uploaded, and their tracked buffers then join the engine's window, the new tracks are followed back through
-            # it, and the frames of the pass BEFORE come out: everything behind this point edits and encodes those (``out``), with their
-            # widened tracked buffers (``rows_of``)
+        uploaded_rgb = src is not None and bool(int(flip) & 2)      # the channel order the frames were uploaded in (host_pixels: flip bit 1)
+        if annotate:
+            # the editing chain (``EditChain``: its docstring states the order) over the frames as uploaded, ``seg`` bytes apart in the
+            # staging area.  A delayed pass edits, encodes and returns the frames of the pass BEFORE it, which the chain's window emits
             # (a ``track_backtrack`` pass is such a pass over its F = B * K source frames: F is B everywhere else)
-            lb_frames = torch.zeros((F, in_h, in_w, 3), dtype=torch.uint8, device="cuda")
-            out = [lb_frames[i] for i in range(F)]
-            if s.frame_io is not None:                              # (raw read-back: the emitted frame, into the slot's pinned segment)
-                s.frame_io = [(lb_frames[i].view(-1), s.io_pin[i * seg:i * seg + npix]) for i in range(F)]
-        else:
-            out = u8 if annotate and self.device_preprocess else None
+            if s.track:
+                self.track_state()                                  # (refuses an engine whose rows leave no room for a tracker)
+            chain = s.chain = EditChain(self.edit_states, s.spec, F, K, (in_h, in_w), uploaded_rgb)
+            out = [chain.lb_frames[i] for i in range(F)] if s.track_lookback else u8
+            if s.track_lookback and s.frame_io is not None:         # (raw read-back: the emitted frame, into the slot's pinned segment)
+                s.frame_io = [(out[i].view(-1), s.io_pin[i * seg:i * seg + npix]) for i in range(F)]
         if s.encode == JPEG_ENCODE:
             # a frame's row: [its length, int32 | pad to 16 | the file, at most jpeg_bound bytes].  The bound is 6.5 times the raw frame
             # (every block at its longest), which is device memory only: a replay reads back the row's first ``first_copy`` bytes -- the
@@ -1012,13 +913,11 @@ class DetectionEntry:
             s.first_copy = min(16 + ops.jpeg_header_bytes() + npix // 4, 16 + s.png_bound)
             s.png_ws = torch.empty(ops.jpeg_workspace_bytes(in_h, in_w, subsampling, huffman), dtype=torch.uint8, device="cuda")
             png_out = [(s.png_dev[i][16:16 + s.png_bound], s.png_dev[i][0:4].view(torch.int32)) for i in range(F)]
-            uploaded_rgb = src is not None and bool(int(flip) & 2)
         elif s.encode == Y4M_ENCODE:
             # a frame's row: its record [Y | Cb | Cr], ops.y4m_frame_bytes long: the slot's output area is B records back to back
             chroma, yrange = s.y4m_mode
             s.png_bound = ops.y4m_frame_bytes(in_h, in_w, chroma)
             s.png_dev = torch.zeros((F, s.png_bound), dtype=torch.uint8, device="cuda")
-            uploaded_rgb = src is not None and bool(int(flip) & 2)
         elif s.encode:
             # a frame's row: [the file, at most png_bound bytes | pad to 16 | its length, int32 | pad]: one fixed-size copy brings both back
             # (the bound is 0.5 % over the raw frame).  File-backed frames were uploaded in the decoder's order (host_pixels: flip bit 1).
@@ -1028,7 +927,6 @@ class DetectionEntry:
             s.png_dev = torch.zeros((F, len_at + 16), dtype=torch.uint8, device="cuda")
             s.png_ws = torch.empty(ops.png_workspace_bytes(in_h, in_w, compress), dtype=torch.uint8, device="cuda")     # (the frames of a pass encode one after another)
             png_out = [(s.png_dev[i][:s.png_bound], s.png_dev[i][len_at:len_at + 4].view(torch.int32)) for i in range(F)]
-            uploaded_rgb = src is not None and bool(int(flip) & 2)
 
         def run():
             if self.device_preprocess:
@@ -1038,69 +936,10 @@ class DetectionEntry:
                         frame = ops.resize_cubic_u8(u8[i * K], H, W, flip=flip, tabs=s.tabs, out=s.u8_resized)
                     ops.preprocess_u8(frame, MEAN_BGR, out=s.x_f32[i:i + 1])     # resnet.preprocess + the f32 feed cast, bit for bit
             res = pipe.forward_dev(s.x_f32, dyn=dyn)
-            if annotate:                                            # the detections drawn into the source frame (its only reader is done)
-                packed = res["det_packed"]
-                if s.track:
-                    if s.track_out is None:                         # (the first warm-up pass: the rows of a packed buffer are known now)
-                        R = ops.track_rows(packed) + ops.track_capacity(t_state)
-                        s.track_out = torch.zeros((F, 4 + 8 * R), dtype=torch.int32, device="cuda")
-                    if s.track_scene_cut:
-                        # in the place of the motion or interval call: the cut step in front of every frame, the frames' marks in ``s.cuts``
-                        ops.track_update_cut(t_state, t_motion, s.io_dev, seg, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold,
-                                             t_grow, s.track_motion, K, s.track_scene_cut, out=s.track_out, cuts=s.cuts, workspace=s.cut_ws)
-                    elif s.every:
-                        # the B key frames' detections, all F frames: between two key frames the block match alone moves the tracks
-                        ops.track_update_interval(t_state, t_motion, s.io_dev, seg, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold,
-                                                  t_grow, s.track_motion, K, out=s.track_out)
-                    elif s.track_motion:
-                        ops.track_update_motion(t_state, t_motion, s.io_dev, seg, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold,
-                                                t_grow, s.track_motion, out=s.track_out)
-                    else:
-                        ops.track_update(t_state, packed, s.n_frames_dev, t_table, in_h, in_w, t_thr, t_hold, t_grow, out=s.track_out)
-                    if s.track_lookback:
-                        lb_window, lb_back = self.track_lookback_window(in_h, in_w, F, ops.track_rows(packed))
-                        if s.lb_out is None:
-                            R2 = ops.track_rows(packed) + ops.track_capacity(t_state) + lb_back
-                            s.lb_out = (lb_frames, torch.zeros((F, 4 + 8 * R2), dtype=torch.int32, device="cuda"),
-                                        torch.zeros(4, dtype=torch.int32, device="cuda"))
-                        if s.track_backtrack:
-                            # behind the interval call: every tracked live row of the pass's key frames is followed back through the window
-                            ops.track_backtrack(lb_window, s.io_dev, seg, s.track_out, s.n_frames_dev, ops.track_capacity(t_state), lb_back, in_h,
-                                                in_w, s.track_backtrack, s.track_motion, t_grow, K, out=s.lb_out)
-                        else:
-                            ops.track_lookback(lb_window, s.io_dev, seg, s.track_out, s.n_frames_dev, ops.track_capacity(t_state), lb_back, in_h,
-                                               in_w, s.track_lookback, s.track_motion or 0, t_grow, out=s.lb_out)
-                    if s.track_trails:
-                        if s.track_lookback:
-                            # the emitted buffers, and the emitted count for their ``n_frames`` word; the pass's own count is the gate: a
-                            # warm-up run (0 frames) emits what the window holds once more, and those are no new frames
-                            ops.track_trails_update(tr_state, s.lb_out[1], s.lb_out[2], tr_length, tr_expire, in_h, in_w, lists=s.trail_lists,
-                                                    gate=s.n_frames_dev)
-                        else:
-                            ops.track_trails_update(tr_state, s.track_out, s.n_frames_dev, tr_length, tr_expire, in_h, in_w, lists=s.trail_lists)
-                    if s.count:
-                        if s.track_lookback:                        # (the emitted buffers and their count, gated by the pass's own: as the trails)
-                            ops.count_update(c_state, s.lb_out[1], s.lb_out[2], c_lines, c_table, c_expire, in_h, in_w, lists=s.count_lists,
-                                             gate=s.n_frames_dev)
-                        else:
-                            ops.count_update(c_state, s.track_out, s.n_frames_dev, c_lines, c_table, c_expire, in_h, in_w, lists=s.count_lists)
+            if annotate:                                            # the frames edited where they lie (their only reader is done)
+                chain.update(s.io_dev, seg, res["det_packed"], s.n_frames_dev)
                 for i in range(F):
-                    rows = s.lb_out[1][i] if s.track_lookback else s.track_out[i] if s.track else packed[i] if B > 1 else packed
-                    if s.redact:
-                        ops.redact_u8(out[i], rows, r_table, r_mode, r_size, r_margin, workspace=s.redact_ws, tracked=bool(s.track))
-                    if s.heat:
-                        # a delayed pass heats the EMITTED frames: their count is the ``n_frames`` word, the pass's own count the gate
-                        # (a warm-up run emits what the window holds once more, and those are no new frames)
-                        if s.track_lookback:
-                            ops.heat_update(h_state, in_h, in_w, rows, h_table, h_decay, i, s.lb_out[2], gate=s.n_frames_dev, tracked=True)
-                        else:
-                            ops.heat_update(h_state, in_h, in_w, rows, h_table, h_decay, i, s.n_frames_dev, tracked=bool(s.track))
-                        ops.heat_draw_u8(out[i], h_state, h_alpha, rgb=heat_rgb)
-                    if s.track_trails:
-                        ops.track_trails_draw_u8(out[i], s.trail_lists[i], tr_length, tr_width, rgb=trails_rgb)
-                    if s.count and not s.nodraw:
-                        ops.count_draw_u8(out[i], s.count_lists[i], c_lines, c_width, rgb=count_rgb)
-                    ops.annotate_u8(out[i], rows, tables, tracked=bool(s.track))
+                    chain.edit(i, out[i])
                     if s.encode == Y4M_ENCODE:
                         continue                                    # (all B frames in one launch behind the loop)
                     if s.encode == JPEG_ENCODE:
@@ -1111,7 +950,7 @@ class DetectionEntry:
                                               compress=compress)
                 if s.encode == Y4M_ENCODE:
                     if s.track_lookback:
-                        ops.y4m_encode_frames_u8(lb_frames.view(-1), npix, F, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
+                        ops.y4m_encode_frames_u8(chain.lb_frames.view(-1), npix, F, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
                     else:
                         ops.y4m_encode_frames_u8(s.io_dev, seg, F, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
             return res
@@ -1147,7 +986,8 @@ class DetectionEntry:
         ``track_lookback`` = L: with the look-back call behind the tracker (ops.track_lookback): the pass edits, encodes and returns the
         frames of the pass before it.  ``detect_every`` = K: a pass over B * K source frames whose network sees every K-th
         (ops.track_update_interval); with ``track_backtrack`` = L: the back-track call behind it (ops.track_backtrack), a delayed pass as
-        a look-back pass is, over its B * K source frames."""
+        a look-back pass is, over its B * K source frames.  Which of these calls an annotating pass makes, and in which order, is the
+        chain's to say (``frame_edit.EditChain``, built by _exact_pass from ``spec``)."""
         t0 = time.perf_counter()
         with no_gc():                                               # (collects first, at most once per second: a collection costs more than the capture)
             m = self.manager
@@ -1210,16 +1050,18 @@ class DetectionEntry:
                 s._png_raw = self._pinned.take(shape[0] * shape[1], zero=True)
                 s.png_pin = s._png_raw[:shape[0] * shape[1]].view(shape)
             if s.track:
-                s._track_raw = self._pinned.take(4 * s.track_out.numel())
-                s.track_pin = s._track_raw.view(torch.int32)[:s.track_out.numel()].view(tuple(s.track_out.shape))
+                track_out = s.chain.track_out
+                s._track_raw = self._pinned.take(4 * track_out.numel())
+                s.track_pin = s._track_raw.view(torch.int32)[:track_out.numel()].view(tuple(track_out.shape))
             if s.track_scene_cut:
                 s._cuts_raw = self._pinned.take(4 * s.frames)
                 s.cuts_pin = s._cuts_raw.view(torch.int32)[:s.frames]
             if s.count:
-                s._count_raw = self._pinned.take(4 * s.count_lists.numel())
-                s.count_pin = s._count_raw.view(torch.int32)[:s.count_lists.numel()].view(tuple(s.count_lists.shape))
+                count_lists = s.chain.count_lists
+                s._count_raw = self._pinned.take(4 * count_lists.numel())
+                s.count_pin = s._count_raw.view(torch.int32)[:count_lists.numel()].view(tuple(count_lists.shape))
             if s.track_lookback:                                    # [the B emitted buffers | the count word]
-                words = s.lb_out[1].numel() + 4
+                words = s.chain.lb_out[1].numel() + 4
                 s._lb_raw = self._pinned.take(4 * words)
                 s.lb_pin = s._lb_raw.view(torch.int32)[:words]
             s.event = torch.cuda.Event()
@@ -1505,7 +1347,8 @@ class DetectionEntry:
         and under its boxes and labels; ``draw`` False still counts and draws no line.  The count lists come back with the dets: every
         result of such a pass carries, in ONE trailing dict (the one that carries "scene_cut"), "crossings": [(line, dir, id, cls), ...]
         -- dir 1 for +, cls the class index.  An entry leaves (hold + 1) * K frames behind its last step.  Refused by name without
-        ``track`` and for options out of range.  Without it every key and byte is what it was."""
+        ``track`` and for options out of range.  Without it every key and byte is what it was.
+        The order of all these steps in a pass is stated once, in ``frame_edit.EditChain``'s docstring."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
@@ -1585,22 +1428,22 @@ class DetectionEntry:
                 s.jpg_status_pin.copy_(s.jpg_status, non_blocking=True)
             own = emitted = None
             if s.track_lookback:                                    # this pass returns the group its window held; its own group waits
-                in_h, in_w = int(s.lb_out[0].shape[1]), int(s.lb_out[0].shape[2])
+                (in_h, in_w), lb_out = s.chain.hw, s.chain.lb_out
                 own = {"images": list(images), "n_rois": None, "frames": len(pixels)} if images else None
                 emitted = self._lookback_waiting.pop((in_h, in_w, s.frames), None)
                 if own is not None:
                     self._lookback_waiting[(in_h, in_w, s.frames)] = own
-                words = s.lb_out[1].numel()
-                s.lb_pin[:words].copy_(s.lb_out[1].view(-1), non_blocking=True)
-                s.lb_pin[words:].copy_(s.lb_out[2], non_blocking=True)
+                words = lb_out[1].numel()
+                s.lb_pin[:words].copy_(lb_out[1].view(-1), non_blocking=True)
+                s.lb_pin[words:].copy_(lb_out[2], non_blocking=True)
             for i in range(len(images)):
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
             for i in range(len(pixels) if s.track else 0):
-                s.track_pin[i].copy_(s.track_out[i], non_blocking=True)
+                s.track_pin[i].copy_(s.chain.track_out[i], non_blocking=True)
             if s.track_scene_cut:
-                s.cuts_pin.copy_(s.cuts, non_blocking=True)
+                s.cuts_pin.copy_(s.chain.cuts, non_blocking=True)
             if s.count:                                             # the count lists come back with the dets
-                s.count_pin.copy_(s.count_lists, non_blocking=True)
+                s.count_pin.copy_(s.chain.count_lists, non_blocking=True)
             for i in range(emitted["frames"] if emitted else 0 if s.track_lookback else len(pixels)):
                 if s.encode == JPEG_ENCODE:
                     s.png_pin[i].copy_(s.png_dev[i][:s.first_copy], non_blocking=True)
@@ -1763,14 +1606,7 @@ class DetectionEntry:
             K = s.every or 1
             for f in range(ticket.frames):
                 if f % K:                                           # a between frame of a ``detect_every`` pass: its dets are the tracks
-                    n_rows, n_live, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(s.track_pin[f].numpy())
-                    dets = [{"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(), "track_id": int(t_id[k])}
-                            for k in range(int(n_rows[0]))]
-                    for k, d in enumerate(dets):
-                        if k < int(n_live[0]):
-                            d["propagated"] = True
-                        else:
-                            d["held"] = int(t_age[k])
+                    _, _, dets = ops.tracked_dets(s.track_pin[f].numpy(), rev, propagated=True)
                     res.append((0, dets) + self._payload(s, f) + self._marks(s, f))
                     continue
                 i = f // K
@@ -1782,13 +1618,12 @@ class DetectionEntry:
                 prob = packed[4 + 5 * rows:4 + 5 * rows + nd].view(np.float32).copy()
                 dets = [{"bbox": bbox[k], "cls_name": rev[int(cls[k])], "prob": prob[k]} for k in range(nd)]
                 if s.track:                                         # the live rows' ids, then the held rows
-                    n_rows, n_live, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(s.track_pin[f].numpy())
-                    if int(n_live[0]) != nd:
-                        raise FrcnnError("tracker: %d live rows for %d detections" % (int(n_live[0]), nd))
+                    n_live, ids, held = ops.tracked_dets(s.track_pin[f].numpy(), rev, start=nd)
+                    if n_live != nd:
+                        raise FrcnnError("tracker: %d live rows for %d detections" % (n_live, nd))
                     for k in range(nd):
-                        dets[k]["track_id"] = int(t_id[k])
-                    dets += [{"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(),
-                              "track_id": int(t_id[k]), "held": int(t_age[k])} for k in range(nd, int(n_rows[0]))]
+                        dets[k]["track_id"] = int(ids[k])
+                    dets += held
                 res.append((n_rois, dets) + self._payload(s, f) + self._marks(s, f))
             return res
         finally:
@@ -1846,15 +1681,7 @@ class DetectionEntry:
         K = s.every or 1                                            # (a ``track_backtrack`` pass: one result per source frame)
         res = []
         for i in range(group["frames"]):
-            n_rows, n_live, _, _, t_bbox, t_cls, t_prob, t_id, t_age = ops.split_tracked(lb[i * words:(i + 1) * words])
-            dets = []
-            for k in range(int(n_rows[0])):
-                d = {"bbox": t_bbox[k].astype(np.int64), "cls_name": rev[int(t_cls[k])], "prob": t_prob[k].copy(), "track_id": int(t_id[k])}
-                if k >= int(n_live[0]):
-                    d["held" if int(t_age[k]) > 0 else "backfilled"] = abs(int(t_age[k]))
-                elif i % K:                                         # a between frame: its live dets are the tracks
-                    d["propagated"] = True
-                dets.append(d)
+            _, _, dets = ops.tracked_dets(lb[i * words:(i + 1) * words], rev, propagated=bool(i % K))
             res.append((0 if i % K else group["n_rois"][i // K], dets) + self._payload(s, i) + self._marks(s, i))
         return res
 

@@ -1973,6 +1973,24 @@ def split_tracked(buf):
     return (buf[0:1], buf[1:2], buf[2:3], buf[3:4], bbox, buf[4 + 4 * R:4 + 5 * R], prob, buf[4 + 6 * R:4 + 7 * R], buf[4 + 7 * R:4 + 8 * R])
 
 
+def tracked_dets(buf, names, start=0, propagated=False):
+    """(host only) ONE tracked buffer's host copy (numpy) as dets -> (n_live, the rows' ids, [{"bbox", "cls_name", "prob", "track_id"} for
+    the rows from ``start`` on]): the live rows first -- with "propagated": True when ``propagated``: the rows of a between frame, which
+    are the tracks themselves --, then the rows behind them with "held" = their age, or for a look-back's back-filled rows (age -k)
+    "backfilled" = k.  ``names``: class index -> name.  A caller that has the live rows as dets already passes their number as ``start``
+    and takes their ids from the second value."""
+    n_rows, n_live, _, _, bbox, cls, prob, tid, age = split_tracked(buf)
+    n_live, dets = int(n_live[0]), []
+    for k in range(start, int(n_rows[0])):
+        d = {"bbox": bbox[k].astype(np.int64), "cls_name": names[int(cls[k])], "prob": prob[k].copy(), "track_id": int(tid[k])}
+        if k >= n_live:
+            d["held" if int(age[k]) > 0 else "backfilled"] = abs(int(age[k]))
+        elif propagated:
+            d["propagated"] = True
+        dets.append(d)
+    return n_live, tid, dets
+
+
 PNG_BAND_ROWS = 1       # scanlines per IDAT chunk of the device encoder (frcnn_png_band_rows(); tests/test_png_cpu.py holds the two together)
 PNG_HUFF_BAND_ROWS = 8   # ... of its huffman mode (frcnn_png_huff_band_rows(); tests/test_png_huff_cpu.py)
 # compress= of the png_* calls -> the prefix of their entry points: "runs" (include/ext/frcnn_hip_png.h: Sub filter, fixed Huffman codes,

@@ -691,7 +691,7 @@ def run_track_lookback(name, cfg, n_frames, reps, content="noise"):
             eng.track_reset()
             out = annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, track=TRACK_LEG, track_motion=MOTION_LEG, **kw)
             if kw:                                                  # (read in front of the next reset)
-                overflow.append([int(win[:12].view(torch.int32)[2]) for win, _ in eng._track_lookback_windows.values()])
+                overflow.append([int(win[:12].view(torch.int32)[2]) for win, _ in eng.edit_states.lookback.values()])
             return out
         return run
 
@@ -836,7 +836,7 @@ def run_track_backtrack(name, cfg, n_frames, reps, content="noise"):
             eng.track_reset()
             out = annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, track=TRACK_LEG, track_motion=MOTION_LEG, detect_every=EVERY_LEG, **kw)
             if kw:                                                  # (read in front of the next reset)
-                overflow.append([int(win[:12].view(torch.int32)[2]) for win, _ in eng._track_lookback_windows.values()])
+                overflow.append([int(win[:12].view(torch.int32)[2]) for win, _ in eng.edit_states.lookback.values()])
             return out
         return run
 
