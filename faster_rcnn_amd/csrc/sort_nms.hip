@@ -10,6 +10,9 @@
 //        resolves each 64-candidate chunk with scalar bit tricks + v_readlane, ORs the kept
 //        rows' words in with independent (pipelined) loads and stops at max_boxes exactly
 //        like the reference loop does.
+//        The two run in BANDS of row blocks (mask band 0, scan band 0, mask band 1, ...): the scan hands its
+//        state on in the workspace, and once it is done the later launches return at once, so the rows
+//        no scan will read are never computed.
 // Compiled with -ffp-contract=off (the f64 overlap ratio must round like numpy's).
 #include "common.h"
 #include <stdlib.h>
@@ -33,7 +36,8 @@ __device__ __forceinline__ unsigned mono_f32(float f) {      // order-preserving
 constexpr int TOPK_BINS = 65536;
 constexpr int TOPK_BLOCK = 256;
 struct TopkCtrl { int32_t n_cand; int32_t thr_bin; int32_t n_valid; int32_t pad[61]; };
-constexpr int TOPK_DIRECT_N = 32768;        // at or below this many scores the plain all-pairs sweep is faster than the four passes
+constexpr int TOPK_DIRECT_N = 16384;       // at or below this many scores the plain all-pairs sweep is faster than the four passes
+constexpr int TOPK_RANK_SLACK = 1024;       // k_topk_rank's grid has rows for min(N, K + this) candidates and loops over any beyond
 
 __device__ __forceinline__ u64 topk_key(float score, int i) { return (((u64)mono_f32(score)) << 32) | (unsigned)(~(unsigned)i); }
 
@@ -118,26 +122,30 @@ __global__ void k_topk_compact(const float* scores, const uint8_t* valid, int N,
 }
 
 // 2-D decomposition: block (bi, bj) counts, for its 256 candidates i, how many candidates of j-slice bj are
-// larger, and adds the partial rank with one atomic per key.  The grid is sized for N (static under hipGraph
-// capture); blocks beyond the device-side candidate count exit at once.
+// larger, and adds the partial rank with one atomic per key.  The grid is static under hipGraph capture and has
+// rows for the candidates the histogram normally leaves (about K), not for N: a block row walks the candidate
+// list with the grid's stride, so a degenerate distribution (C up to N) costs more rounds, never a wrong rank;
+// rows and j-slices beyond the device-side candidate count exit at once.
 __global__ void __launch_bounds__(TOPK_BLOCK) k_topk_rank(const u64* keys, const TopkCtrl* ctrl, int32_t* rank) {
     __shared__ u64 tile[TOPK_BLOCK];
     const int n = ctrl->n_cand;
-    if ((int)blockIdx.x * TOPK_BLOCK >= n) return;
     const int slice = ((n + (int)gridDim.y - 1) / (int)gridDim.y + TOPK_BLOCK - 1) / TOPK_BLOCK * TOPK_BLOCK;
-    const int i = blockIdx.x * TOPK_BLOCK + threadIdx.x;
-    const u64 mine = i < n ? keys[i] : ~0ull;
     const int j_begin = blockIdx.y * slice, j_end = min(n, j_begin + slice);
-    int cnt = 0;
-    for (int t0 = j_begin; t0 < j_end; t0 += TOPK_BLOCK) {
-        const int j = t0 + threadIdx.x;
-        tile[threadIdx.x] = j < j_end ? keys[j] : 0ull;
-        __syncthreads();
+    if (j_begin >= n) return;
+    for (int i0 = blockIdx.x * TOPK_BLOCK; i0 < n; i0 += (int)gridDim.x * TOPK_BLOCK) {     // (workgroup-uniform bounds)
+        const int i = i0 + threadIdx.x;
+        const u64 mine = i < n ? keys[i] : ~0ull;
+        int cnt = 0;
+        for (int t0 = j_begin; t0 < j_end; t0 += TOPK_BLOCK) {
+            const int j = t0 + threadIdx.x;
+            tile[threadIdx.x] = j < j_end ? keys[j] : 0ull;
+            __syncthreads();
 #pragma unroll 16
-        for (int jj = 0; jj < TOPK_BLOCK; ++jj) cnt += tile[jj] > mine;       // LDS broadcast reads
-        __syncthreads();
+            for (int jj = 0; jj < TOPK_BLOCK; ++jj) cnt += tile[jj] > mine;       // LDS broadcast reads
+            __syncthreads();
+        }
+        if (i < n && cnt) atomicAdd(&rank[i], cnt);
     }
-    if (i < n && cnt) atomicAdd(&rank[i], cnt);
 }
 
 __global__ void k_zero_u32(unsigned* p, int n) {
@@ -190,15 +198,31 @@ __device__ __forceinline__ bool suppresses(const double4 a, double area_a, const
 }
 __device__ __forceinline__ double box_area1(const double4 b) { return (b.z - b.x + 1.0) * (b.w - b.y + 1.0); }
 
+// What the scan hands from one band of row blocks to the next (behind the mask words in the workspace).  Band 0's
+// scan starts from nothing and writes all of it, so no launch and no memset has to clear it between calls.
+struct NmsState {
+    int32_t done;               // total == max_boxes or the chunks ran out: keep and n_keep are final, later launches return
+    int32_t total;              // boxes kept so far (keep[0 .. total) is written)
+    int32_t pad[2];
+    u64 removed[FRCNN_NMS_MAX_BOXES / 64];      // the suppression bitmap, word w = candidates 64w .. 64w+63
+};
+// Row blocks per band, the last band takes the rest: short bands first, because the scan usually fills max_boxes
+// within the first few hundred candidates (a band costs two launches, so there are few of them).
+constexpr int NMS_BANDS = 4;
+__host__ __device__ constexpr int nms_band_begin(int b) { return b == 0 ? 0 : b == 1 ? 16 : b == 2 ? 32 : 64; }
+
 // One wave64 per 64x64 tile (row block rb <= column block cb).  Lane = row; its 64 tests
 // against the column block form one u64.  Bit j of mask[i][cb] <=> box i suppresses box
-// cb*64+j; only bits with column index > i are ever consumed.
+// cb*64+j; only bits with column index > i are ever consumed.  A launch fills the row blocks
+// from rb0 on that its grid covers; `state` is null for band 0.
 template <typename Box4>
-__global__ void __launch_bounds__(64) k_nms_mask(const Box4* boxes, const int32_t* n_ptr, int K, int W, double thresh, u64* mask) {
+__global__ void __launch_bounds__(64) k_nms_mask(const Box4* boxes, const int32_t* n_ptr, int K, int W, double thresh, u64* mask,
+                                                 int rb0, const NmsState* state) {
+    if (state && state->done) return;
     const int n = min(*n_ptr, K);
-    // linear tile id -> (rb, cb) of the upper triangle, row-major
+    // linear tile id -> (rb, cb) of the band's part of the upper triangle, row-major
     int tid = blockIdx.x;
-    int rb = 0;
+    int rb = rb0;
     while (tid >= W - rb) { tid -= W - rb; ++rb; }
     const int cb = rb + tid;
     if (rb * 64 >= n || cb * 64 >= n) return;
@@ -233,21 +257,26 @@ __device__ __forceinline__ u64 readlane_u64(u64 v, int lane /*uniform*/) {
     return ((u64)hi << 32) | lo;
 }
 
+// One band of the scan: chunks [c0, c1) (c1 is clipped to the live chunks).  Band 0 (c0 == 0) starts from an empty
+// bitmap; a later band returns if the scan is done and otherwise picks up `state`.  The launch that finishes the
+// scan writes keep's -1 tail and n_keep and sets state->done; any other leaves its bitmap and count in `state`.
 __global__ void __launch_bounds__(64) k_nms_scan(const u64* mask, const int32_t* n_ptr, int K, int W, int max_boxes,
-                                                 int32_t* keep, int32_t* n_keep) {
+                                                 int32_t* keep, int32_t* n_keep, int c0, int c1, NmsState* state) {
     const int lane = threadIdx.x;
+    if (c0 > 0 && state->done) return;
     const int n = min(*n_ptr, K);
     u64 removed[NMS_SLOTS];                 // lane l, slot s holds bitmap word s*64 + l
 #pragma unroll
-    for (int s = 0; s < NMS_SLOTS; ++s) removed[s] = 0;
-    int total = 0;
+    for (int s = 0; s < NMS_SLOTS; ++s) removed[s] = (c0 > 0 && s * 64 + lane < W) ? state->removed[s * 64 + lane] : 0ull;
+    int total = c0 > 0 ? state->total : 0;
     const int chunks = (n + 63) / 64;
-    u64 diag_next = lane < n ? mask[(size_t)lane * W] : 0ull;          // chunk 0's diagonal word of row `lane`
-    for (int c = 0; c < chunks && total < max_boxes; ++c) {
+    const int cend = min(c1, chunks);
+    u64 diag_next = c0 * 64 + lane < n ? mask[(size_t)(c0 * 64 + lane) * W + c0] : 0ull;    // chunk c0's diagonal word of its row `lane`
+    for (int c = c0; c < cend && total < max_boxes; ++c) {
         const int base = c * 64;
         const int i = base + lane;
         const u64 diag = diag_next;
-        if (c + 1 < chunks) {                 // the next chunk's diagonal words do not depend on this chunk's outcome:
+        if (c + 1 < cend) {                   // the next chunk's diagonal words do not depend on this chunk's outcome:
             const int in = i + 64;            // fetch them now, their latency hides behind the resolve below
             diag_next = in < n ? mask[(size_t)in * W + c + 1] : 0ull;
         }
@@ -294,8 +323,15 @@ __global__ void __launch_bounds__(64) k_nms_scan(const u64* mask, const int32_t*
                 for (int s = 0; s < NMS_SLOTS; ++s) removed[s] |= v[u][s];
         }
     }
+    if (total < max_boxes && cend < chunks) {           // the next band goes on from here
+#pragma unroll
+        for (int s = 0; s < NMS_SLOTS; ++s)
+            if (s * 64 + lane < W) state->removed[s * 64 + lane] = removed[s];
+        if (lane == 0) { state->total = total; state->done = 0; }
+        return;
+    }
     for (int i = total + lane; i < max_boxes; i += 64) keep[i] = -1;
-    if (lane == 0) *n_keep = total;
+    if (lane == 0) { *n_keep = total; state->done = 1; }
 }
 
 __global__ void k_gather_rois(const short4* cand, const int32_t* keep, const int32_t* n_keep, int batch, int out_rows, float4* out) {
@@ -310,6 +346,11 @@ __global__ void k_gather_rois(const short4* cand, const int32_t* keep, const int
         o = make_float4((float)b.x, (float)b.y, (float)b.z, (float)b.w);
     }
     out[k] = o;
+}
+
+static size_t nms_mask_bytes(int K) {
+    const size_t W = (size_t)(K + 63) / 64;
+    return align_up((size_t)(K > 0 ? K : 1) * W * 8, 256);
 }
 
 template <typename Box4>
@@ -328,11 +369,18 @@ static int nms_launch(const Box4* boxes, const int32_t* n, int K, double thresh,
         return fail(FRCNN_E_WORKSPACE, "%s: workspace needs %zu bytes", what, frcnn_nms_workspace_bytes(K));
     const int W = (K + 63) / 64;
     u64* mask = (u64*)workspace;
-    const int tiles = W * (W + 1) / 2;
-    k_nms_mask<Box4><<<tiles, 64, 0, s>>>(boxes, n, K, W, thresh, mask);
-    if (int e = check_launch(what)) return e;
-    k_nms_scan<<<1, 64, 0, s>>>(mask, n, K, W, max_boxes, keep, n_keep);
-    return check_launch(what);
+    NmsState* state = (NmsState*)((char*)workspace + nms_mask_bytes(K));
+    // every launch is captured; whether a band still has work is decided on the device (state->done)
+    for (int b = 0; b < NMS_BANDS && nms_band_begin(b) < W; ++b) {
+        const int r0 = nms_band_begin(b);
+        const int r1 = (b + 1 < NMS_BANDS && nms_band_begin(b + 1) < W) ? nms_band_begin(b + 1) : W;
+        const int tiles = (r1 - r0) * W - (r1 * (r1 - 1) - r0 * (r0 - 1)) / 2;      // sum of W - rb over the band's row blocks
+        k_nms_mask<Box4><<<tiles, 64, 0, s>>>(boxes, n, K, W, thresh, mask, r0, b ? state : nullptr);
+        if (int e = check_launch(what)) return e;
+        k_nms_scan<<<1, 64, 0, s>>>(mask, n, K, W, max_boxes, keep, n_keep, r0, r1, state);
+        if (int e = check_launch(what)) return e;
+    }
+    return FRCNN_OK;
 }
 
 }  // namespace frcnn
@@ -363,7 +411,7 @@ int frcnn_topk_order(const float* scores, const uint8_t* valid, int N, int K, in
     u64* cand = (u64*)((char*)ctrl + sizeof(TopkCtrl));
     int32_t* rank = (int32_t*)((char*)cand + align_up((size_t)N * 8, 256));
     const int bi = (N + TOPK_BLOCK - 1) / TOPK_BLOCK;
-    const int direct = N <= TOPK_DIRECT_N;
+    const int direct = N <= TOPK_DIRECT_N || K >= N;      // K >= N: every valid score is a candidate whatever the histogram says
     // The counters are cleared by a kernel, not hipMemsetAsync: captured into a hipGraph, a lone memset node between
     // two kernel nodes was observed (ROCm 7.2, gfx950) not to be ordered against its neighbours -- k_topk_compact
     // then appended behind the previous replay's count and ran off the end of the candidate list.
@@ -381,9 +429,10 @@ int frcnn_topk_order(const float* scores, const uint8_t* valid, int N, int K, in
     }
     k_topk_compact<<<bi, TOPK_BLOCK, 0, s>>>(scores, valid, N, ctrl, cand, rank, direct);
     if (int e = check_launch("topk_order compact")) return e;
-    int split = 2048 / bi;
+    const int rows = direct || N - TOPK_RANK_SLACK <= K ? bi : (K + TOPK_RANK_SLACK + TOPK_BLOCK - 1) / TOPK_BLOCK;
+    int split = 2048 / rows;
     split = split < 8 ? 8 : (split > 64 ? 64 : split);
-    k_topk_rank<<<dim3(bi, split), TOPK_BLOCK, 0, s>>>(cand, ctrl, rank);
+    k_topk_rank<<<dim3(rows, split), TOPK_BLOCK, 0, s>>>(cand, ctrl, rank);
     if (int e = check_launch("topk_order rank")) return e;
     const int bs = ((N > K ? N : K) + TOPK_BLOCK - 1) / TOPK_BLOCK;     // covers every candidate and every output slot
     k_topk_scatter<<<bs, TOPK_BLOCK, 0, s>>>(cand, rank, ctrl, K, order, n_out);
@@ -398,8 +447,7 @@ int frcnn_gather_candidates(const float* rois, const float* scores, const int32_
 }
 
 size_t frcnn_nms_workspace_bytes(int K) {
-    const size_t W = (size_t)(K + 63) / 64;
-    return align_up((size_t)(K > 0 ? K : 1) * W * 8, 256);
+    return nms_mask_bytes(K) + align_up(sizeof(NmsState), 256);     // the mask words, then the scan's hand-over state
 }
 
 int frcnn_nms_i16(const int16_t* boxes, const int32_t* n, int K, double thresh, int max_boxes,

@@ -164,7 +164,10 @@ int frcnn_gather_candidates(const float* rois, const float* scores, const int32_
  * n (device i32) = number of live rows (<= K <= FRCNN_NMS_MAX_BOXES).
  * keep[max_boxes] i32 receives positions into the candidate list in pick order (entries >= *n_keep are set
  * to -1: the call defines every slot, the caller need not clear the buffers), n_keep (device i32) their count.
- * _i16: int16 boxes (proposal NMS).  _f64: float64 boxes (voc_dets.py:76). */
+ * _i16: int16 boxes (proposal NMS).  _f64: float64 boxes (voc_dets.py:76).
+ * The workspace holds the suppression mask and, behind it, the state the scan hands from one band of rows to the next: size it
+ * with frcnn_nms_workspace_bytes(K), never by a formula of the host's own.  Its contents need no clearing between calls; two
+ * calls in flight at the same time need a workspace each. */
 size_t frcnn_nms_workspace_bytes(int K);
 int frcnn_nms_i16(const int16_t* boxes, const int32_t* n, int K, double thresh, int max_boxes,
                   int32_t* keep, int32_t* n_keep, void* workspace, size_t workspace_bytes, void* stream);
