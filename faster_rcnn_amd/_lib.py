@@ -475,6 +475,29 @@ COUNT_WIDTH = (1, 9, 3)
 COUNT_MAX_EXPIRE = 4095
 COUNT_LIST_WORDS = 4 + 2 * COUNT_MAX_LINES + 4 * COUNT_MAX_EVENTS
 
+ZONE_VERSION = 1                # include/ext/frcnn_hip_zone.h FRCNN_ZONE_VERSION
+ZONE_SIGNATURES = {
+    "frcnn_zone_version": (I, []),
+    "frcnn_zone_state_bytes": (c_size_t, [I]),
+    "frcnn_zone_list_words": (c_size_t, []),
+    "frcnn_zone_update": (I, [P, I, P, ctypes.c_longlong, I, I, P, P, P, P, I, P, I, I, I, I, I, P, P]),
+    "frcnn_zone_draw_u8": (I, [P, I, I, P, P, P, I, I, I, P]),
+}
+# the zones of a call at most, (fewest, most) vertices of one, the events a frame's list holds (FRCNN_ZONE_MAX_ZONES, _MIN_VERTS /
+# _MAX_VERTS, _MAX_EVENTS), the range of a coordinate (_MIN_COORD, _MAX_COORD), (smallest, largest, the default) width (1 / _MAX_WIDTH /
+# _DEFAULT_WIDTH), the largest expiry in frames (_MAX_EXPIRE), where a zone's dwell stops (_MAX_DWELL), and the words of a state's
+# header, of an entry and of a zone list (_HEAD_WORDS, _ENTRY_WORDS, _LIST_WORDS)
+ZONE_MAX_ZONES = 8
+ZONE_VERTS = (3, 16)
+ZONE_MAX_EVENTS = 64
+ZONE_COORD = (-32768, 65535)
+ZONE_WIDTH = (1, 9, 3)
+ZONE_MAX_EXPIRE = 4095
+ZONE_MAX_DWELL = 1 << 30
+ZONE_HEAD_WORDS = 4 + 4 * ZONE_MAX_ZONES
+ZONE_ENTRY_WORDS = 5 + ZONE_MAX_ZONES
+ZONE_LIST_WORDS = 4 + 5 * ZONE_MAX_ZONES + 5 * ZONE_MAX_EVENTS
+
 TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
 TRACK_LOOKBACK_SIGNATURES = {
     "frcnn_track_lookback_version": (I, []),
@@ -681,6 +704,15 @@ def load():
     if lib.frcnn_count_version() != COUNT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_count_version()} of the line-count extension, this binding "
                          f"{COUNT_VERSION} (include/ext/frcnn_hip_count.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in ZONE_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_zone.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_zone_version() != ZONE_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_zone_version()} of the zone extension, this binding "
+                         f"{ZONE_VERSION} (include/ext/frcnn_hip_zone.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

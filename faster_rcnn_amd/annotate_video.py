@@ -104,6 +104,14 @@ the list as an 8-bit grey PNG, one per frame size met (``PATH_<w>x<h>.png`` when
 starts from zero totals; ``get_annotated_frame(count=, counts_out=)`` and the eager path take the option as one-frame calls that continue
 the state (``reset_counts`` zeroes it).  On the command line a value that begins with a minus sign needs the ``=`` form:
 ``--count_line=-5,0,-5,100``.
+``zone=(zones, classes, W, anchor)`` (``--zone X1,Y1,X2,Y2,X3,Y3[,...]``, repeatable up to 8 times, with ``--track`` in any of the forms
+above; ``--zone_classes``, ``--zone_width``, ``--zone_anchor centre|bottom``) tests every track's box centre, or the middle of its bottom
+edge, against polygon zones with an exact even-odd rule (ops.zone_update / ops.zone_draw_u8, csrc/zone.hip; DESIGN §8 "Zone rule"): each
+frame shows the occupied zones tinted, every zone's outline and a label ``Z{z} {occupancy}/{visitors}`` behind the heat map and under
+every line, ``zones_out=PATH`` (``--zones_out``) receives a CSV row ``frame,zone,kind,id,cls,dwell`` per event, kind enter, exit or lost,
+and at the end one line per zone is printed: visitors, peak, stays and the mean dwell of the completed stays.  A list starts from an
+empty state; ``get_annotated_frame(zone=, zones_out=)`` and the eager path take the option as one-frame calls that continue the state
+(``reset_zones`` starts over).  ``--no_draw`` still counts.  A value that begins with a minus sign needs the ``=`` form: ``--zone=-5,0,9,0,9,9``.
 """
 import collections
 import os
@@ -298,7 +306,7 @@ def _eager_heat_state(class_mapping, h, w):
 
 
 def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
-               track_trails=None, rgb=False, heatmap=None, count=None):
+               track_trails=None, rgb=False, heatmap=None, count=None, zone=None):
     """The editing chain over ONE frame and its host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is edited in
     place, by a one-frame ``frame_edit.EditChain`` -- its docstring states the calls and their order -- on this class mapping's eager
     states (``reset_tracks``, ``reset_heat`` and ``reset_counts`` empty them); ``rgb``: the frame's channel order (False: B, G, R).
@@ -310,11 +318,13 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     ``track_trails`` = (N, W) (with ``track``, not with ``draw`` False).
     ``heatmap`` = (classes, A, S): the detections, or with ``track`` the live tracked rows, heat this class mapping's state for the
     frame's size; a frame without detections is blended too.
-    ``count`` = (lines, classes, W) (with ``track``): ``info`` receives "crossings": [(line, dir, id, cls)]."""
+    ``count`` = (lines, classes, W) (with ``track``): ``info`` receives "crossings": [(line, dir, id, cls)].
+    ``zone`` = (zones, classes, W, anchor) (with ``track``): ``info`` receives "zones": {"occupancy", "events"} as a pass's result does."""
     import torch
     track_trails = _track_trails(track_trails, track, draw)
     heatmap = _heatmap(heatmap)
     count = _count(count, track)
+    zone = _zone(zone, track)
     radius = _track_motion(track_motion, track)
     track_scene_cut = _track_scene_cut(track_scene_cut, track, track_motion, None, None)
     if track is not None or heatmap is not None or (dets and (draw or redact is not None)):      # (nothing to draw or hide: the frame stays as it is)
@@ -324,7 +334,7 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
             redact = (redact[0] if redact[0] == "all" else tuple(redact[0]),) + tuple(redact[1:])
         states = _eager_states(class_mapping)
         spec = entry.PassSpec(annotate=True, redact=redact, draw=draw, track=track, track_scene_cut=track_scene_cut, track_trails=track_trails,
-                              track_motion=radius, heat=heatmap, count=count)
+                              track_motion=radius, heat=heatmap, count=count, zone=zone)
         chain = EditChain(states, spec, 1, 1, frame.shape[:2], rgb)
         chain.update(dev.view(-1), 0, packed, states.one_frame())         # (in front of the edits: ``dev`` is still the frame as it came)
         chain.edit(0, dev)
@@ -337,6 +347,9 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
             info["scene_cut"] = True
         if info is not None and count is not None:
             info["crossings"] = ops.count_events(chain.count_lists[0].cpu().numpy())
+        if info is not None and zone is not None:
+            zlist = chain.zone_lists[0].cpu().numpy()
+            info["zones"] = {"occupancy": ops.zone_occupancy(zlist, len(zone[0])), "events": ops.zone_events(zlist)}
         frame[...] = dev.cpu().numpy()
     return frame
 
@@ -686,6 +699,115 @@ def reset_counts(training_manager, detector, in_flight=1):
         _eager_states(training_manager.class_mapping).reset_counts()
 
 
+def zone_from_args(args, class_mapping):
+    """(host only) The zones the command line asks for -> ((zones, classes, W, anchor) as ``submit_batch(zone=...)`` takes it, the path of
+    ``--zones_out`` or None), or (None, None) without ``--zone``.  ValueError, with the reason, for ``--zone_classes`` / ``--zone_width`` /
+    ``--zone_anchor`` / ``--zones_out`` without ``--zone``, ``--zone`` without ``--track``, more than 8 zones, a value that is not an even
+    number of at least six integers, equal consecutive vertices, an unknown class name, a W outside 1..9 and an unknown anchor."""
+    if not args.zone:
+        for flag, value in (("--zone_classes", args.zone_classes), ("--zone_width", args.zone_width), ("--zone_anchor", args.zone_anchor),
+                            ("--zones_out", args.zones_out)):
+            if value is not None:
+                raise ValueError("%s=%s is a setting of the zones: it needs --zone X1,Y1,X2,Y2,X3,Y3[,...]" % (flag, value))
+        return None, None
+    if not args.track:
+        raise ValueError("--zone tests the tracker's ids against the zone: it needs --track")
+    zones = []
+    for text in args.zone:
+        try:
+            flat = tuple(int(v) for v in text.split(","))
+        except ValueError:
+            flat = ()
+        if len(flat) < 6 or len(flat) % 2:
+            raise ValueError("--zone %s: an even number of integers X1,Y1,X2,Y2,X3,Y3[,...], three vertices at least" % text)
+        zones.append(tuple(zip(flat[0::2], flat[1::2])))
+    names = [n.strip() for n in (args.zone_classes or "all").split(",") if n.strip()]
+    if not names:
+        raise ValueError("--zone_classes takes comma-separated class names, or all")
+    try:
+        classes = "all" if names == ["all"] else ops.redact_class_list(_names_by_index(class_mapping), names)
+        return ops.zone_option(zones, classes, args.zone_width, args.zone_anchor), args.zones_out
+    except ValueError as e:
+        raise ValueError("--zone / --zone_classes / --zone_width / --zone_anchor: %s" % e) from None
+
+
+def _zone(zone, track):
+    """``annotate_images`` / ``annotate_stream``'s ``zone`` checked -> (zones, classes, W, anchor), or None."""
+    if zone is None:
+        return None
+    if track is None:
+        raise ValueError("zone=%r tests the tracker's ids against the zones: it needs track=(thr, hold, grow)" % (zone,))
+    try:
+        zones, classes, width, anchor = zone
+    except (TypeError, ValueError):
+        raise ValueError("zone=%r: (zones, classes, width, anchor)" % (zone,)) from None
+    return ops.zone_option(zones, classes, width, anchor)
+
+
+ZONES_HEADER = "frame,zone,kind,id,cls,dwell"
+
+
+def zones_rows(frame_no, events, names):
+    """(host only) The ``--zones_out`` rows of one frame: ``frame,zone,kind,id,cls,dwell`` per event (zone, kind, id, cls, dwell), frames
+    from 1, kind enter, exit or lost, the class by its name in ``names`` (names by index), the dwell in frames (0 for enter)."""
+    return ["%d,%d,%s,%d,%s,%d" % (frame_no, z, ops.ZONE_KINDS[kind], tid, names[cls] if 0 <= cls < len(names) else cls, dwell)
+            for z, kind, tid, cls, dwell in events]
+
+
+def print_zones(n_zones, totals):
+    """(host only) The lines printed at the end of a list with zones, from ``ops.zone_totals``' form: one per zone -- visitors, peak, stays
+    and the mean dwell in frames over the completed stays --, and a warning when events were left out of the lists."""
+    for z in range(n_zones):
+        stays, dwell = totals["stays"][z], totals["dwell"][z]
+        mean = "{:.1f} frames".format(dwell / stays) if stays else "-"
+        print("zone {}: visitors {} peak {} stays {} mean dwell {}".format(z, totals["visitors"][z], totals["peak"][z], stays, mean))
+    if totals["events_dropped"]:
+        print("warning: {} zone events did not fit their frames' lists: the zones file is short by that many rows; the totals are exact"
+              .format(totals["events_dropped"]))
+
+
+class ZonesLog:
+    """Where the zone events of a sequence go: the ``--zones_out`` file (``path`` None: none)."""
+
+    def __init__(self, path, names):
+        self.names = list(names)
+        self.file = open(path, "w") if path is not None else None
+        if self.file is not None:
+            self.file.write(ZONES_HEADER + "\n")
+
+    def add(self, frame_no, events):
+        if self.file is not None:
+            self.file.writelines(row + "\n" for row in zones_rows(frame_no, events, self.names))
+
+    def close(self):
+        if self.file is not None:
+            self.file.close()
+            self.file = None
+
+
+def _write_zones(zones_out, frame_no, events, class_mapping):
+    """``zones_out``: None, a ``ZonesLog``, or a text file that receives the frame's CSV rows (no header)."""
+    if isinstance(zones_out, ZonesLog):
+        zones_out.add(frame_no, events)
+    elif zones_out is not None:
+        zones_out.writelines(row + "\n" for row in zones_rows(frame_no, events, _names_by_index(class_mapping)))
+
+
+def _zone_state(training_manager, eng):
+    """The zone state of ``eng``, or of the eager path with None."""
+    return eng.zone_state() if eng is not None else _eager_states(training_manager.class_mapping).zone_state()
+
+
+def reset_zones(training_manager, detector, in_flight=1):
+    """An empty zone state, totals included, before a new sequence: the state of the engine ``in_flight`` names, or the eager path's.
+    (``reset_tracks`` ends the ids and keeps the totals.)"""
+    eng = _engine(training_manager, detector, in_flight)
+    if eng is not None:
+        eng.zone_reset()
+    else:
+        _eager_states(training_manager.class_mapping).reset_zones()
+
+
 def heatmap_from_args(args, class_mapping):
     """(host only) The heat map the command line asks for -> ((classes, A, S) as ``submit_batch(heat=...)`` takes it, the path of
     ``--heatmap_out`` or None), or (None, None) without ``--heatmap``.  classes: "all", or the tuple of names (of ``class_mapping``, the
@@ -818,7 +940,7 @@ def _print_drawn(dets, width, height):
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                        track_trails=None, heatmap=None, count=None, counts_out=None):
+                        track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
@@ -833,10 +955,16 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     ``count`` = (lines, classes, W) (with ``track``): the frame is one more step of the count state the calls before it left (DESIGN §8
     "Count rule"; ``reset_counts`` starts from zero totals, ``reset_tracks`` ends the ids and keeps them): the lines and their totals are
     drawn unless ``draw`` is False, and ``counts_out``, a text file, receives the frame's rows ``frame,line,direction,id,cls`` under the
-    number ``frame_no``."""
+    number ``frame_no``.
+    ``zone`` = (zones, classes, W, anchor) (with ``track``): the frame is one more step of the zone state the calls before it left (DESIGN
+    §8 "Zone rule"; ``reset_zones`` starts over, ``reset_tracks`` ends the ids and keeps the totals): the zones are drawn unless ``draw``
+    is False, and ``zones_out``, a text file, receives the frame's rows ``frame,zone,kind,id,cls,dwell``."""
     count = _count(count, track)
     if counts_out is not None and count is None:
         raise ValueError("counts_out is where the crossings are written: it needs count=(lines, classes, width)")
+    zone = _zone(zone, track)
+    if zones_out is not None and zone is None:
+        raise ValueError("zones_out is where the zone events are written: it needs zone=(zones, classes, width, anchor)")
     if detect_every is not None:
         raise ValueError("detect_every=%r runs the detector once per pass of several frames: get_annotated_frame detects its one frame and "
                          "cannot; use annotate_images or annotate_stream" % (detect_every,))
@@ -856,6 +984,8 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         motion["track_trails"] = trails
     if count is not None:
         motion["count"] = count
+    if zone is not None:
+        motion["zone"] = zone
     heatmap = _heatmap(heatmap)
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1)
@@ -880,6 +1010,8 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         _write_tracks(tracks_out, frame_no, dets, training_manager.class_mapping)
     if count is not None:
         _write_counts(counts_out, frame_no, info["crossings"], training_manager.class_mapping)
+    if zone is not None:
+        _write_zones(zones_out, frame_no, info["zones"]["events"], training_manager.class_mapping)
     _print_drawn(dets, img.width, img.height)
     return frame
 
@@ -1280,7 +1412,7 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-              track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None):
+              track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
@@ -1292,7 +1424,10 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     count = _count(count, track)
     if counts_out is not None and count is None:
         raise ValueError("counts_out=%r is where the crossings are written: it needs count=(lines, classes, width)" % (counts_out,))
-    counts_log = None
+    zone = _zone(zone, track)
+    if zones_out is not None and zone is None:
+        raise ValueError("zones_out=%r is where the zone events are written: it needs zone=(zones, classes, width, anchor)" % (zones_out,))
+    counts_log = zones_log = None
     sink = make_sink()
     try:
         dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
@@ -1314,6 +1449,11 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             reset_counts(training_manager, detector, 1 if eng is None else eng.in_flight)
             counts_log = CountsLog(counts_out, _names_by_index(training_manager.class_mapping))
             motion["counts_out"] = counts_log
+        if zone is not None:                              # an empty state for the list
+            motion["zone"] = tracking["zone"] = zone
+            reset_zones(training_manager, detector, 1 if eng is None else eng.in_flight)
+            zones_log = ZonesLog(zones_out, _names_by_index(training_manager.class_mapping))
+            motion["zones_out"] = zones_log
         if eng is None:
             _run_eager(training_manager, detector, frames, sink, resize_min, resize_max, redact=redact, draw=draw, track=track,
                        tracks_out=tracks_out, **motion)
@@ -1334,6 +1474,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
                     print("scene cut: {}".format(label))
                 if count is not None:
                     counts_log.add(pos + 1, marks[0]["crossings"])
+                if zone is not None:
+                    zones_log.add(pos + 1, marks[0]["zones"]["events"])
                 print("processing {}".format(label))
                 print("num rois: {}".format(num_rois))
                 if track is not None:
@@ -1347,11 +1489,16 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             counts_log.close()
             state = ops.count_totals(_count_state(training_manager, eng))
             print_counts(len(count[0]), state["totals"], counts_log.per_class, state["events_dropped"])
+        if zone is not None:                              # (host only: the state read back)
+            zones_log.close()
+            print_zones(len(zone[0]), ops.zone_totals(_zone_state(training_manager, eng)))
         if heatmap_out is not None:                       # (host only: the states read back, their t values as grey PNG files)
             write_heatmaps(heatmap_out, _heat_states(training_manager, eng))
     finally:
         if counts_log is not None:
             counts_log.close()
+        if zones_log is not None:
+            zones_log.close()
         sink.close()
 
 
@@ -1359,7 +1506,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
                     track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
-                    counts_out=None):
+                    counts_out=None, zone=None, zones_out=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
@@ -1375,14 +1522,14 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
     _annotate(training_manager, detector, source, lambda prepare, ahead: _loaded_stream(source, prepare, ahead), make_sink, resize_min, resize_max,
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
               detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
-              heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out)
+              heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
-                    heatmap_out=None, count=None, counts_out=None):
+                    heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1449,7 +1596,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               lambda prepare, ahead: _loaded_files(paths, lambda path: prepare(path, _load_frame(path, device_decode, device_png)), ahead),
               make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-              track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out)
+              track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out)
 
 
 def build_parser():
@@ -1569,6 +1716,18 @@ def build_parser():
                         "once per id and direction; a value that begins with a minus sign is written --count_line=-5,0,-5,100; repeatable up to 8 "
                         "times; each line is drawn with its totals 'L{l} +{pos} -{neg}' over "
                         "the redaction, heat map and trails and under the boxes, and the totals are printed at the end (needs --track)")
+    p.add_argument("--zone", dest="zone", action="append", default=None, metavar="X1,Y1,X2,Y2,X3,Y3[,...]",
+                   help="a polygon zone of 3..16 vertices in source-frame pixels (-32768..65535): who is inside (the centre of the box, or "
+                        "with --zone_anchor bottom the middle of its bottom edge), how many ids have visited and how long they stayed; a value "
+                        "that begins with a minus sign is written --zone=-5,0,9,0,9,9; repeatable up to 8 times (needs --track)")
+    p.add_argument("--zone_classes", dest="zone_classes", default=None, metavar="CLASSES",
+                   help="the classes the zones see: comma-separated names of the active mapping, or all (the default; needs --zone)")
+    p.add_argument("--zone_width", dest="zone_width", type=int, default=None, metavar="W",
+                   help="the width the zones' outlines are drawn with in pixels, 1..9 (default 3; needs --zone)")
+    p.add_argument("--zone_anchor", dest="zone_anchor", choices=("centre", "bottom"), default=None,
+                   help="the point of a box that is tested: its centre (the default) or the middle of its bottom edge (needs --zone)")
+    p.add_argument("--zones_out", dest="zones_out", default=None, metavar="PATH",
+                   help="write a CSV row frame,zone,kind,id,cls,dwell per zone event, kind enter, exit or lost (needs --zone)")
     p.add_argument("--count_classes", dest="count_classes", default=None, metavar="CLASSES",
                    help="the classes that count: comma-separated names of the active mapping, or all (the default; needs --count_line)")
     p.add_argument("--count_width", dest="count_width", type=int, default=None, metavar="W",
@@ -1667,6 +1826,11 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
         tracking["count"] = count
     if counts_out is not None:
         tracking["counts_out"] = counts_out
+    zone, zones_out = zone_from_args(args, class_mapping)
+    if zone is not None:
+        tracking["zone"] = zone
+    if zones_out is not None:
+        tracking["zones_out"] = zones_out
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

@@ -316,11 +316,12 @@ class PassSpec:
     track_trails: object = None
     heat: object = None
     count: object = None
+    zone: object = None                                  # (zones, classes, W, anchor), ops.zone_option's form: frame_edit.EditChain reads it
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
                 track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                track_trails=None, heat=None, count=None):
+                track_trails=None, heat=None, count=None, zone=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -384,6 +385,10 @@ class PassSpec:
             if track is None:
                 raise FrcnnError("submit_batch: count= counts the tracker's ids as they cross a line: pass track=(thr, hold, grow) too")
             count = engine.count_option(count)
+        if zone is not None:
+            if track is None:
+                raise FrcnnError("submit_batch: zone= tests the tracker's ids against the zones: pass track=(thr, hold, grow) too")
+            zone = engine.zone_option(zone)
         if redact is not None:
             redact = engine.redact_option(redact)
         jpeg_mode, y4m_mode = JPEG_MODE, Y4M_MODE
@@ -418,7 +423,7 @@ class PassSpec:
             raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
-                   track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count)
+                   track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count, zone=zone)
 
     @property
     def delayed(self):
@@ -458,6 +463,8 @@ class PassSpec:
             key = key + ("heat",) + self.heat
         if self.count is not None:
             key = key + ("count",) + self.count
+        if self.zone is not None:
+            key = key + ("zone",) + self.zone
         return key
 
 
@@ -474,7 +481,7 @@ class _Slot:
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "chain",
                  "track", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
                  "track_lookback", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
-                 "track_scene_cut", "cuts_pin", "_cuts_raw", "track_trails", "heat", "count", "count_pin", "_count_raw")
+                 "track_scene_cut", "cuts_pin", "_cuts_raw", "track_trails", "heat", "count", "count_pin", "_count_raw", "zone", "zone_pin", "_zone_raw")
 
     def __init__(self):
         for name in self.__slots__:
@@ -740,6 +747,34 @@ class DetectionEntry:
         except ValueError as e:
             raise FrcnnError("submit_batch: count=%r: %s" % (count, e)) from None
         return lines, classes, width
+
+    # ------------------------------------------------------------------ zones
+    def zone_state(self):
+        """The engine's zone state (device int32, ops.zone_state), made on first use, of ``track_trails_capacity()`` entries: one,
+        shared by every pass submitted with ``zone=``.  ``zone_reset()`` empties it, totals included; ``track_reset()`` drops its
+        entries -- the ids end, without events, open stays are not counted -- and leaves the totals.  ``ops.zone_totals`` reads it."""
+        return self.edit_states.zone_state()
+
+    def zone_reset(self):
+        """Zero totals and no entries: the state is zeroed on the ordered stream, behind the zone passes submitted so far."""
+        with torch.cuda.stream(self.track_stream):
+            self.edit_states.reset_zones()
+
+    def zone_option(self, zone):
+        """``submit_batch``'s ``zone`` checked and normalised -> (zones, classes, W, anchor): zones a tuple of 1..8 polygons of 3..16
+        (x, y), classes "all" or a tuple of this engine's class names, W 1..9 (None: 3), anchor 0 / 1 ("centre" / "bottom", None:
+        centre).  FrcnnError, with the reason, for anything else."""
+        try:
+            zones, classes, width, anchor = zone
+        except (TypeError, ValueError):
+            raise FrcnnError("submit_batch: zone=%r: (zones, classes, width, anchor)" % (zone,)) from None
+        try:
+            zones, classes, width, anchor = ops.zone_option(zones, classes, width, anchor)
+            if classes != "all":
+                classes = ops.redact_class_list(self.class_names(), classes)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: zone=%r: %s" % (zone, e)) from None
+        return zones, classes, width, anchor
 
     def track_reset(self):
         """Forget every track: the states are zeroed on the tracking stream, behind the tracked passes submitted so far
@@ -1009,6 +1044,7 @@ class DetectionEntry:
             s.track_lookback, s.track_backtrack = spec.track_lookback or spec.track_backtrack, spec.track_backtrack      # (both: the delayed path is one)
             s.every, s.frames = spec.detect_every, B * (spec.detect_every or 1)
             s.track_scene_cut, s.track_trails, s.heat, s.count = spec.track_scene_cut, spec.track_trails, spec.heat, spec.count
+            s.zone = spec.zone
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -1060,6 +1096,10 @@ class DetectionEntry:
                 count_lists = s.chain.count_lists
                 s._count_raw = self._pinned.take(4 * count_lists.numel())
                 s.count_pin = s._count_raw.view(torch.int32)[:count_lists.numel()].view(tuple(count_lists.shape))
+            if s.zone:
+                zone_lists = s.chain.zone_lists
+                s._zone_raw = self._pinned.take(4 * zone_lists.numel())
+                s.zone_pin = s._zone_raw.view(torch.int32)[:zone_lists.numel()].view(tuple(zone_lists.shape))
             if s.track_lookback:                                    # [the B emitted buffers | the count word]
                 words = s.chain.lb_out[1].numel() + 4
                 s._lb_raw = self._pinned.take(4 * words)
@@ -1248,7 +1288,7 @@ class DetectionEntry:
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
                      track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
-                     heat=None, count=None):
+                     heat=None, count=None, zone=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1348,11 +1388,20 @@ class DetectionEntry:
         result of such a pass carries, in ONE trailing dict (the one that carries "scene_cut"), "crossings": [(line, dir, id, cls), ...]
         -- dir 1 for +, cls the class index.  An entry leaves (hold + 1) * K frames behind its last step.  Refused by name without
         ``track`` and for options out of range.  Without it every key and byte is what it was.
+        ``zone`` = (zones, classes, W, anchor) (tracking passes only, every form of them; ("zone", zones, classes, W, anchor) appended
+        behind ("count", ...); zones 1..8 polygons of 3..16 (x, y) in source-frame pixels, -32768..65535; classes "all" or names; W the
+        width of the outlines, 1..9, None: 3; anchor "centre" or "bottom"): the zone rule (DESIGN §8 "Zone rule"): one ops.zone_update
+        behind the count update, over the same buffers, count and gate, steps the engine's zone state (``zone_state``; ``zone_reset()``
+        zeroes it, ``track_reset()`` drops its entries and keeps the totals), and each frame's occupied zones are tinted and all
+        outlines and labels "Z{z} {occupancy}/{visitors}" drawn (ops.zone_draw_u8) behind its heat map and under every line; ``draw``
+        False still counts.  Every result of such a pass carries in its ONE trailing dict "zones": {"occupancy": [per zone],
+        "events": [(zone, kind, id, cls, dwell)]}, kind 1 enter, 0 exit, 2 lost.  Refused by name without ``track`` and for options out
+        of range.  Without it every key and byte is what it was.
         The order of all these steps in a pass is stated once, in ``frame_edit.EditChain``'s docstring."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-                                track_trails=track_trails, heat=heat, count=count)
+                                track_trails=track_trails, heat=heat, count=count, zone=zone)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1444,6 +1493,8 @@ class DetectionEntry:
                 s.cuts_pin.copy_(s.chain.cuts, non_blocking=True)
             if s.count:                                             # the count lists come back with the dets
                 s.count_pin.copy_(s.chain.count_lists, non_blocking=True)
+            if s.zone:
+                s.zone_pin.copy_(s.chain.zone_lists, non_blocking=True)
             for i in range(emitted["frames"] if emitted else 0 if s.track_lookback else len(pixels)):
                 if s.encode == JPEG_ENCODE:
                     s.png_pin[i].copy_(s.png_dev[i][:s.first_copy], non_blocking=True)
@@ -1631,14 +1682,18 @@ class DetectionEntry:
 
     @staticmethod
     def _marks(s, i):
-        """What frame i of a collected ``track_scene_cut`` or ``count`` pass returns behind its payload: ONE dict -- "scene_cut": True for a
-        frame that is a cut, "crossings": [(line, dir, id, cls)] in a counting pass (the events of the frame's count list, dir 1 for +) --
-        ; () for every other pass."""
-        if not s.track_scene_cut and not s.count:
+        """What frame i of a collected ``track_scene_cut``, ``count`` or ``zone`` pass returns behind its payload: ONE dict -- "scene_cut":
+        True for a frame that is a cut, "crossings": [(line, dir, id, cls)] in a counting pass (the events of the frame's count list, dir 1
+        for +), "zones": {"occupancy": [per zone], "events": [(zone, kind, id, cls, dwell)]} in a zone pass (the frame's zone list) --;
+        () for every other pass."""
+        if not s.track_scene_cut and not s.count and not s.zone:
             return ()
         marks = {"scene_cut": True} if s.track_scene_cut and int(s.cuts_pin[i]) else {}
         if s.count:
             marks["crossings"] = ops.count_events(s.count_pin[i].numpy())
+        if s.zone:                                       # "zones": the frame's occupancy per zone and its events (zone, kind, id, cls, dwell)
+            zlist = s.zone_pin[i].numpy()
+            marks["zones"] = {"occupancy": ops.zone_occupancy(zlist, len(s.zone[0])), "events": ops.zone_events(zlist)}
         return (marks,)
 
     def _payload(self, s, i):

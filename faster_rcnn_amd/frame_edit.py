@@ -16,12 +16,12 @@ def _made(table, key, make):
 
 class EditStates:
     """The device state of the editing rules for the classes ``class_names`` (index = class index), each piece made on first use: a
-    tracker of ``track_capacity`` slots, trail and count states of ``trail_capacity`` entries.  The pointers of all of them are in the
+    tracker of ``track_capacity`` slots, trail, count and zone states of ``trail_capacity`` entries.  The pointers of all of them are in the
     captured graphs that use them: nothing here is ever replaced, only zeroed by the three resets (on the current stream)."""
 
     def __init__(self, class_names, track_capacity, trail_capacity):
         self.class_names, self.track_capacity, self.trail_capacity = list(class_names), int(track_capacity), int(trail_capacity)
-        self._tracker = self._count = self._one = None
+        self._tracker = self._count = self._zone = self._one = None
         self.motion = {}                                 # (h, w) of the source frames -> ops.track_motion_state
         self.lookback = {}                               # (h, w, F) -> (ops.track_lookback_state: the frames tracked but not yet emitted, its back)
         self.trails = {}                                 # length N -> ops.track_trails_state
@@ -68,6 +68,12 @@ class EditStates:
             self._count = ops.count_state(self.trail_capacity)
         return self._count
 
+    def zone_state(self):
+        """The ONE zone state (device int32, ops.zone_state; ``ops.zone_totals`` reads it), sized like the count state."""
+        if self._zone is None:
+            self._zone = ops.zone_state(self.trail_capacity)
+        return self._zone
+
     def heat_state(self, h, w):
         """The heat state for source frames of (h, w): one per size, whatever the other options of the calls that heat it."""
         return _made(self.heat, (int(h), int(w)), lambda: ops.heat_state(h, w))
@@ -103,6 +109,8 @@ class EditStates:
             ops.track_reset(trails)
         if self._count is not None:                      # ... and no id waits for its next step; what was counted stays
             ops.count_reset(self._count, keep_totals=True)
+        if self._zone is not None:                       # ... and nobody is inside: no event is made, an open stay is not counted
+            ops.zone_reset(self._zone, keep_totals=True)
 
     def reset_heat(self):
         """A cold map for every size."""
@@ -113,6 +121,11 @@ class EditStates:
         """Zero totals and no entries."""
         if self._count is not None:
             ops.count_reset(self._count)
+
+    def reset_zones(self):
+        """Zero totals and no entries."""
+        if self._zone is not None:
+            ops.zone_reset(self._zone)
 
 
 class EditChain:
@@ -127,13 +140,15 @@ class EditChain:
          point reads the EMITTED buffers and the emitted count as its ``n_frames`` word, gated by the pass's own count (a warm-up run, 0
          frames, emits what the window holds once more, and those are no new frames): ``tracked``, ``n_frames``, ``gate``;
       3. ops.track_trails_update -> ``trail_lists``;
-      4. ops.count_update -> ``count_lists``.
+      4. ops.count_update -> ``count_lists``;
+      5. ops.zone_update -> ``zone_lists``: the same ``tracked`` / ``n_frames`` / ``gate``, so a delayed pass counts in emitted order.
     ``edit``, once per frame, on ``rows(i)`` -- the frame's emitted buffer, else its tracked buffer, else its packed detections:
-      5. ops.redact_u8: every tracked row, the held ones too;
-      6. ops.heat_update (the live rows) and ops.heat_draw_u8;
-      7. ops.track_trails_draw_u8;
-      8. ops.count_draw_u8, unless nothing is drawn;
-      9. ops.annotate_u8: the live rows with their ids; with the no-draw tables when nothing is drawn.
+      6. ops.redact_u8: every tracked row, the held ones too;
+      7. ops.heat_update (the live rows) and ops.heat_draw_u8;
+      8. ops.zone_draw_u8, unless nothing is drawn: a tinted area lies under every line;
+      9. ops.track_trails_draw_u8;
+     10. ops.count_draw_u8, unless nothing is drawn;
+     11. ops.annotate_u8: the live rows with their ids; with the no-draw tables when nothing is drawn.
     The encoders follow, at the caller's.
 
     ``states``: an ``EditStates``; ``spec``: the normalised options, read by ``entry.PassSpec``'s field names; F source frames of ``hw``
@@ -150,7 +165,9 @@ class EditChain:
         h, w = hw
         self.lookback = spec.track_lookback or spec.track_backtrack             # (both: the delayed path is one)
         self.tables = states.annotate_tables(spec.draw)
-        self.track_out = self.lb_out = self.lb_frames = self.cuts = self.trail_lists = self.count_lists = None
+        self.track_out = self.lb_out = self.lb_frames = self.cuts = self.trail_lists = self.count_lists = self.zone_lists = None
+        if spec.zone and not spec.track:
+            raise FrcnnError("zone= tests the tracker's ids against the zones: the chain needs track=(thr, hold, grow) too")
         if spec.redact:
             # one workspace serves the frames of a pass, which are redacted one after another
             classes, mode, size, _ = spec.redact
@@ -169,13 +186,17 @@ class EditChain:
                 self.count, self.count_table = states.count_state(), states.redact_table(spec.count[1])
                 self.count_lists = ops.count_workspace(F)
                 self.count_lists.zero_()
+            if spec.zone:
+                self.zone, self.zone_table = states.zone_state(), states.redact_table(spec.zone[1])
+                self.zone_lists = ops.zone_workspace(F)
+                self.zone_lists.zero_()
         if spec.heat:
             self.heat, self.heat_table = states.heat_state(h, w), states.redact_table(spec.heat[0])
         if self.lookback:
             self.lb_frames = torch.zeros((F, h, w, 3), dtype=torch.uint8, device="cuda")
 
     def update(self, frames_u8, frame_stride, packed, n_frames):
-        """Steps 1-4.  ``frames_u8`` holds source frame f at byte ``f * frame_stride``; ``packed``: the post-process's packed buffers of
+        """Steps 1-5.  ``frames_u8`` holds source frame f at byte ``f * frame_stride``; ``packed``: the post-process's packed buffers of
         the key frames (one buffer for one); ``n_frames``: the device word that says how many of the F frames are real."""
         sp, (h, w), K = self.spec, self.hw, self.K
         self.packed = packed
@@ -216,6 +237,9 @@ class EditChain:
         if sp.count:
             ops.count_update(self.count, self.tracked, self.n_frames, sp.count[0], self.count_table, self.expire, h, w,
                              lists=self.count_lists, gate=self.gate)
+        if sp.zone:
+            ops.zone_update(self.zone, self.tracked, self.n_frames, sp.zone[0], self.zone_table, self.expire, h, w, anchor=sp.zone[3],
+                            lists=self.zone_lists, gate=self.gate)
 
     def rows(self, i):
         """What the edits of frame i read."""
@@ -224,7 +248,7 @@ class EditChain:
         return self.packed[i] if self.F > 1 else self.packed
 
     def edit(self, i, frame):
-        """Steps 5-9 on ``frame``, an (h, w, 3) uint8 device tensor: frame i of the pass, or of the pass before it in a delayed pass."""
+        """Steps 6-11 on ``frame``, an (h, w, 3) uint8 device tensor: frame i of the pass, or of the pass before it in a delayed pass."""
         sp, (h, w), rows, tracked = self.spec, self.hw, self.rows(i), bool(self.spec.track)
         if sp.redact:
             _, mode, size, margin = sp.redact
@@ -233,6 +257,8 @@ class EditChain:
             _, alpha, decay = sp.heat
             ops.heat_update(self.heat, h, w, rows, self.heat_table, decay, i, self.n_frames, gate=self.gate, tracked=tracked)
             ops.heat_draw_u8(frame, self.heat, alpha, rgb=self.rgb)
+        if sp.zone and sp.draw:
+            ops.zone_draw_u8(frame, self.zone_lists[i], sp.zone[0], sp.zone[2], rgb=self.rgb)
         if sp.track_trails:
             ops.track_trails_draw_u8(frame, self.trail_lists[i], *sp.track_trails, rgb=self.rgb)
         if sp.count and sp.draw:

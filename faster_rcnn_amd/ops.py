@@ -1857,6 +1857,191 @@ def count_events(clist):
     return [tuple(int(v) for v in c[COUNT_HEAD + 4 * k:COUNT_HEAD + 4 * k + 4]) for k in range(min(max(int(c[0]), 0), COUNT_MAX_EVENTS))]
 
 
+# ----------------------------------------------------------------------------- zones
+ZONE_MAX_ZONES, ZONE_VERTS, ZONE_MAX_EVENTS = _lib.ZONE_MAX_ZONES, _lib.ZONE_VERTS, _lib.ZONE_MAX_EVENTS
+ZONE_WIDTH = _lib.ZONE_WIDTH                    # (smallest, largest, the default) width W the outlines are drawn with
+ZONE_ANCHORS = ("centre", "bottom")             # the POINT of a row: index = the entry points' ``anchor``
+ZONE_KINDS = ("exit", "enter", "lost")          # index = an event's kind
+# words of a zone list: [n_events, frames, 0, 0 | occupancy[8] | visitors[8] | stays[8] | dwell[8] | peak[8] | events[64][5]]; of a
+# state in front of its entries; of an entry; of a list in front of its events
+ZONE_LIST_WORDS, ZONE_HEAD, ZONE_ENTRY, ZONE_LIST_HEAD = _lib.ZONE_LIST_WORDS, _lib.ZONE_HEAD_WORDS, _lib.ZONE_ENTRY_WORDS, 4 + 5 * _lib.ZONE_MAX_ZONES
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def zone_option(zones, classes="all", width=None, anchor=None):
+    """(host only) The zone option checked -> (zones, classes, W, anchor): zones a tuple of 1..8 polygons, each a tuple of 3..16 vertices
+    (x, y) of integers in -32768..65535, no two consecutive ones equal (the last and the first are consecutive); a polygon may be given
+    as its vertices or as the flat x1, y1, x2, y2, ..., and one polygon alone is one zone.  classes "all" or a tuple of class names
+    (which names there are is the caller's to check: ``redact_class_list``), W the width of the outlines, 1..9 (None: 3), anchor 0 / 1
+    from "centre" / "bottom" (None: centre).  ValueError with the reason."""
+    lo, hi = _lib.ZONE_COORD
+    v_lo, v_hi = ZONE_VERTS
+    try:
+        zones = tuple(zones)
+        if zones and (all(_is_int(v) for v in zones) or all(not _is_int(p) and len(tuple(p)) == 2 and all(_is_int(v) for v in p) for p in zones)):
+            zones = (zones,)                             # one polygon alone
+        polys = []
+        for zn in zones:
+            zn = tuple(zn)
+            if zn and all(_is_int(v) for v in zn):
+                if len(zn) % 2:
+                    raise ValueError("zone %r: an odd number of coordinates" % (zn,))
+                zn = tuple(zip(zn[0::2], zn[1::2]))
+            polys.append(tuple(tuple(p) for p in zn))
+    except TypeError:
+        raise ValueError("zones=%r: a list of polygons, each a list of (x, y)" % (zones,)) from None
+    if not 1 <= len(polys) <= ZONE_MAX_ZONES:
+        raise ValueError("zones: %d of them, 1..%d are possible" % (len(polys), ZONE_MAX_ZONES))
+    for zn in polys:
+        if not v_lo <= len(zn) <= v_hi:
+            raise ValueError("zone %r: %d vertices, %d..%d are possible" % (zn, len(zn), v_lo, v_hi))
+        if not all(len(p) == 2 and all(_is_int(v) and lo <= int(v) <= hi for v in p) for p in zn):
+            raise ValueError("zone %r: vertices are two integers x, y in %d..%d" % (zn, lo, hi))
+        for i, p in enumerate(zn):
+            q = zn[(i + 1) % len(zn)]
+            if (int(p[0]), int(p[1])) == (int(q[0]), int(q[1])):
+                raise ValueError("zone %r: two consecutive vertices at (%d, %d)" % (zn, p[0], p[1]))
+    polys = tuple(tuple((int(x), int(y)) for x, y in zn) for zn in polys)
+    if classes is None:
+        classes = "all"
+    if isinstance(classes, str):
+        classes = (classes,)
+    try:
+        classes = tuple(classes)
+    except TypeError:
+        raise ValueError("zone classes=%r: \"all\", a class name or a list of class names" % (classes,)) from None
+    if not classes or not all(isinstance(c, str) and c for c in classes):
+        raise ValueError("zone classes=%r: \"all\", a class name or a list of class names" % (classes,))
+    classes = "all" if classes == ("all",) else classes
+    w_lo, w_hi, w_def = ZONE_WIDTH
+    width = w_def if width is None else width
+    if not _is_int(width) or not w_lo <= int(width) <= w_hi:
+        raise ValueError("zone width=%r: an integer in %d..%d (pixels)" % (width, w_lo, w_hi))
+    anchor = 0 if anchor is None else anchor
+    if isinstance(anchor, str):
+        anchor = {"centre": 0, "center": 0, "bottom": 1}.get(anchor, anchor)
+    if not _is_int(anchor) or int(anchor) not in (0, 1):
+        raise ValueError("zone anchor=%r: \"centre\" or \"bottom\"" % (anchor,))
+    return polys, classes, int(width), int(anchor)
+
+
+def _zone_verts_arg(zones):
+    """``zones`` (polygons of (x, y)) as the two host int32 arrays the entry points read (keep them alive over the call), their pointers
+    and the number of zones."""
+    nv = np.ascontiguousarray([len(zn) for zn in zones], dtype=np.int32)
+    flat = [v for zn in zones for p in zn for v in p]
+    verts = np.ascontiguousarray(np.asarray(flat, dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1), dtype=np.int32)
+    return (verts, nv), verts.ctypes.data_as(ctypes.c_void_p), nv.ctypes.data_as(ctypes.c_void_p), int(nv.size)
+
+
+def zone_state_words(capacity):
+    """(host only) 4-byte words of a zone state of ``capacity`` entries (frcnn_zone_state_bytes / 4): 36 + 13 capacity."""
+    n = int(_lib.load().frcnn_zone_state_bytes(int(capacity)))
+    if n == 0:
+        raise _lib.FrcnnError("zone state: capacity=%r not in [1, %d]" % (capacity, TRACK_MAX))
+    return n // 4
+
+
+def zone_state(capacity):
+    """An empty zone state of ``capacity`` entries: a zeroed int32 device tensor, [n_entries, frames, dropped, events_dropped |
+    visitors[8] | stays[8] | dwell[8] | peak[8] | per entry: id, cls, last_seen, inside, visited, since[8]]
+    (include/ext/frcnn_hip_zone.h).  Zeroing it (``zone_reset``) empties it, totals included."""
+    _require_gpu()
+    return torch.zeros(zone_state_words(capacity), dtype=torch.int32, device="cuda")
+
+
+def zone_reset(state, keep_totals=False):
+    """Empty the state (on the current stream): no entries, no frames, totals 0.  ``keep_totals``: only the entries leave -- the ids end
+    without an event, their open stays are not counted, and ``frames``, the sticky sums, visitors, stays, dwell and peak are kept."""
+    if keep_totals:
+        state[0:1].zero_()
+        state[ZONE_HEAD:].zero_()
+    else:
+        state.zero_()
+    return state
+
+
+def zone_workspace(frames):
+    """The zone lists of a ``zone_update`` call of ``frames`` frames: an int32 device tensor (frames, ZONE_LIST_WORDS).  Every word is
+    written by every call."""
+    _require_gpu()
+    if not 1 <= int(frames) <= _lib.TRACK_MAX_FRAMES:
+        raise _lib.FrcnnError("zone_workspace: frames=%r out of range (1..%d)" % (frames, _lib.TRACK_MAX_FRAMES))
+    assert int(_lib.load().frcnn_zone_list_words()) == ZONE_LIST_WORDS
+    return torch.empty((int(frames), ZONE_LIST_WORDS), dtype=torch.int32, device="cuda")
+
+
+def zone_update(state, tracked, n_frames, zones, table, expire, h, w, anchor=0, capacity=None, lists=None, gate=None):
+    """Steps 1-5 of the zone rule (DESIGN §8 "Zone rule", frcnn_zone_update) over the frames of ``tracked`` IN ORDER, in one launch:
+    ``tracked`` and ``n_frames`` as ``count_update`` takes them.  The point (``anchor`` 0: the centre, 1: the bottom centre) of every
+    live tracked row of a class set in ``table`` (device uint8 [C], ``redact_table``'s form) is tested against ``zones`` (host polygons
+    of (x, y), ``zone_option``'s form) and steps the entry of its id in ``state`` (``zone_state``; ``capacity``: its entries, read from
+    its size when None): enter and exit events with the dwell, an id a visitor of a zone once.  Entries not seen for more than ``expire``
+    frames leave, with a lost event per zone they were in, and frame f's zone list lands in ``lists[f]`` (``zone_workspace``; allocated
+    here when None; a captured call passes it) -> ``lists``.  ``gate``: None, or a device word that is 0 when no frame of the call is
+    real, whatever ``n_frames`` says.  The call can be captured in a graph."""
+    _require_gpu()
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.dim() == 2 and tracked.is_contiguous()
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert gate is None or (gate.is_cuda and gate.dtype == torch.int32 and gate.numel() >= 1)
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    if capacity is None:
+        capacity = (int(state.numel()) - ZONE_HEAD) // ZONE_ENTRY
+    frames, words = int(tracked.shape[0]), int(tracked.shape[1])
+    assert (words - 4) % 8 == 0
+    if lists is None:
+        lists = zone_workspace(frames)
+    assert int(state.numel()) == zone_state_words(capacity)
+    assert lists.is_cuda and lists.dtype == torch.int32 and lists.is_contiguous() and tuple(lists.shape) == (frames, ZONE_LIST_WORDS)
+    keep, verts_p, nv_p, n_zones = _zone_verts_arg(zones)           # (``keep`` owns the host arrays the two pointers point into: alive over the call)
+    _lib.call("frcnn_zone_update", _p(state), int(capacity), _p(tracked), words, (words - 4) // 8, frames, _p(n_frames), _p(gate), verts_p, nv_p,
+              n_zones, _p(table), int(table.numel()), int(anchor), int(expire), int(h), int(w), _p(lists), _stream())
+    return lists
+
+
+def zone_draw_u8(frame, zlist, zones, width=None, rgb=False):
+    """DRAW of the zone rule (frcnn_zone_draw_u8) into ``frame``, an (h, w, 3) uint8 device tensor, edited in place and returned: the
+    zones that ``zlist`` -- one zone list of ``zone_update`` -- says are occupied tinted with PALETTE[z & 7] at a quarter, every zone's
+    outline as capsules of ``width`` pixels (None: 3), and a label "Z{z} {occupancy}/{visitors}" per zone, formatted on the device.  A
+    list of a frame that is not real draws nothing.  ``rgb``: the frame's bytes are R, G, B (False: B, G, R).  One launch; the list is
+    read on the device, so the call can be captured in a graph."""
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert zlist.is_cuda and zlist.dtype == torch.int32 and zlist.dim() == 1 and zlist.is_contiguous() and int(zlist.numel()) == ZONE_LIST_WORDS
+    keep, verts_p, nv_p, n_zones = _zone_verts_arg(zones)           # (``keep`` owns the host arrays the two pointers point into: alive over the call)
+    _lib.call("frcnn_zone_draw_u8", _p(frame), int(frame.shape[0]), int(frame.shape[1]), _p(zlist), verts_p, nv_p, n_zones,
+              ZONE_WIDTH[2] if width is None else int(width), int(bool(rgb)), _stream())
+    return frame
+
+
+def zone_totals(state):
+    """(host only; reads the state back) The totals of a zone state, device tensor or host copy -> {"entries", "frames", "dropped",
+    "events_dropped", "visitors", "stays", "dwell", "peak": a list of 8 each} -- dwell[z] the frames of the completed stays in zone z."""
+    s = state.cpu().numpy() if isinstance(state, torch.Tensor) else np.asarray(state)
+    Z = ZONE_MAX_ZONES
+    out = {"entries": int(s[0]), "frames": int(s[1]), "dropped": int(s[2]), "events_dropped": int(s[3])}
+    for k, name in enumerate(("visitors", "stays", "dwell", "peak")):
+        out[name] = [int(v) for v in s[4 + Z * k:4 + Z * (k + 1)]]
+    return out
+
+
+def zone_occupancy(zlist, n_zones=ZONE_MAX_ZONES):
+    """(host only) occupancy[z] of one zone list's HOST copy, for the first ``n_zones`` zones."""
+    c = np.asarray(zlist)
+    return [int(v) for v in c[4:4 + int(n_zones)]]
+
+
+def zone_events(zlist):
+    """(host only) The events of one zone list's HOST copy -> [(zone, kind, id, cls, dwell)], kind an index of ``ZONE_KINDS``: the rows'
+    enter and exit events in (row, zone) order, then the lost events in (id, zone) order."""
+    c = np.asarray(zlist)
+    return [tuple(int(v) for v in c[ZONE_LIST_HEAD + 5 * k:ZONE_LIST_HEAD + 5 * k + 5]) for k in range(min(max(int(c[0]), 0), ZONE_MAX_EVENTS))]
+
+
 TRACK_LOOKBACK = _lib.TRACK_LOOKBACK            # (smallest, largest, the default) look-back of ``track_lookback``, in frames
 
 
