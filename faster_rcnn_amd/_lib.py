@@ -498,6 +498,22 @@ ZONE_HEAD_WORDS = 4 + 4 * ZONE_MAX_ZONES
 ZONE_ENTRY_WORDS = 5 + ZONE_MAX_ZONES
 ZONE_LIST_WORDS = 4 + 5 * ZONE_MAX_ZONES + 5 * ZONE_MAX_EVENTS
 
+PLATE_VERSION = 1               # include/ext/frcnn_hip_plate.h FRCNN_PLATE_VERSION
+PLATE_SIGNATURES = {
+    "frcnn_plate_version": (I, []),
+    "frcnn_plate_state_bytes": (c_size_t, [I, I]),
+    "frcnn_plate_update": (I, [P, I, I, P, P, I, I, I, I, I, I, P, P, P, P]),
+    "frcnn_plate_fill_u8": (I, [P, I, I, P, P, I, I, P, I, I, I, P]),
+}
+# (smallest, largest, the default) settle, tolerance and margin (1 / FRCNN_PLATE_MAX_SETTLE / _DEFAULT_SETTLE, 0 / 255 / _DEFAULT_TOL,
+# 0 / _MAX_MARGIN / _DEFAULT_MARGIN: the defaults are PROVISIONAL, not measured on real footage), the frame indices of a call
+# (FRCNN_PLATE_MAX_FRAMES) and the update kernel's tile (FRCNN_PLATE_TILE_W, _TILE_H)
+PLATE_SETTLE = (1, 255, 8)
+PLATE_TOL = (0, 255, 10)
+PLATE_MARGIN = (0, 64, 8)
+PLATE_MAX_FRAMES = 65536
+PLATE_TILE = (128, 8)
+
 TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
 TRACK_LOOKBACK_SIGNATURES = {
     "frcnn_track_lookback_version": (I, []),
@@ -713,6 +729,15 @@ def load():
     if lib.frcnn_zone_version() != ZONE_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_zone_version()} of the zone extension, this binding "
                          f"{ZONE_VERSION} (include/ext/frcnn_hip_zone.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in PLATE_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_plate.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_plate_version() != PLATE_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_plate_version()} of the background-plate extension, this binding "
+                         f"{PLATE_VERSION} (include/ext/frcnn_hip_plate.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

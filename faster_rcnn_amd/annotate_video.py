@@ -112,6 +112,17 @@ every line, ``zones_out=PATH`` (``--zones_out``) receives a CSV row ``frame,zone
 and at the end one line per zone is printed: visitors, peak, stays and the mean dwell of the completed stays.  A list starts from an
 empty state; ``get_annotated_frame(zone=, zones_out=)`` and the eager path take the option as one-frame calls that continue the state
 (``reset_zones`` starts over).  ``--no_draw`` still counts.  A value that begins with a minus sign needs the ``=`` form: ``--zone=-5,0,9,0,9,9``.
+``remove=(classes, S, T, M)`` (``--remove CLASSES``, class names of the active mapping or ``all``; ``--remove_settle S``, 1..255;
+``--remove_tol T``, 0..255; ``--remove_margin M``, 0..64; the defaults 8, 10 and 8 are PROVISIONAL: nobody has measured them on real
+footage) paints the objects of those classes out of fixed-camera footage (ops.plate_update / ops.plate_fill_u8, csrc/plate.hip; DESIGN §8
+"Plate rule"): a background plate on the device learns every pixel that no box of ANY class touches -- held and back-filled tracked rows
+too -- and that stays within T of the value its run began with for S frames, and the boxes of the classes, grown by M, are filled with
+it.  Where the plate is not known yet the redaction shows, if ``--redact`` covers the classes, else black.  An object that stands still
+and is never detected becomes background after S frames: that is the rule's limit.  A ``--track_scene_cut`` cut empties the plate.  A
+list starts from an empty plate; ``get_annotated_frame(remove=)`` and the eager path continue it as one-frame calls (``reset_plate``
+empties it).  ``plate_out=PATH.png`` (``--plate_out``) writes the plate at the end as an RGB PNG with unknown pixels black, one per
+frame size met, named as ``--heatmap_out`` names its files, and one line per size is printed: ``plate 1242x375: 128 frames, 97.3 %
+known`` (a size met in both channel orders has two plates: a line and a file for each).  With every other option, ``--no_draw`` included, with and without ``--track``.
 """
 import collections
 import os
@@ -306,7 +317,7 @@ def _eager_heat_state(class_mapping, h, w):
 
 
 def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
-               track_trails=None, rgb=False, heatmap=None, count=None, zone=None):
+               track_trails=None, rgb=False, heatmap=None, count=None, zone=None, remove=None):
     """The editing chain over ONE frame and its host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is edited in
     place, by a one-frame ``frame_edit.EditChain`` -- its docstring states the calls and their order -- on this class mapping's eager
     states (``reset_tracks``, ``reset_heat`` and ``reset_counts`` empty them); ``rgb``: the frame's channel order (False: B, G, R).
@@ -319,22 +330,25 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     ``heatmap`` = (classes, A, S): the detections, or with ``track`` the live tracked rows, heat this class mapping's state for the
     frame's size; a frame without detections is blended too.
     ``count`` = (lines, classes, W) (with ``track``): ``info`` receives "crossings": [(line, dir, id, cls)].
-    ``zone`` = (zones, classes, W, anchor) (with ``track``): ``info`` receives "zones": {"occupancy", "events"} as a pass's result does."""
+    ``zone`` = (zones, classes, W, anchor) (with ``track``): ``info`` receives "zones": {"occupancy", "events"} as a pass's result does.
+    ``remove`` = (classes, S, T, M): the frame teaches this class mapping's plate state for its size and channel order, and the boxes of
+    those classes are painted out with it (``reset_plate`` empties it); a frame without detections teaches it too."""
     import torch
     track_trails = _track_trails(track_trails, track, draw)
     heatmap = _heatmap(heatmap)
+    remove = _remove(remove)
     count = _count(count, track)
     zone = _zone(zone, track)
     radius = _track_motion(track_motion, track)
     track_scene_cut = _track_scene_cut(track_scene_cut, track, track_motion, None, None)
-    if track is not None or heatmap is not None or (dets and (draw or redact is not None)):      # (nothing to draw or hide: the frame stays as it is)
+    if track is not None or heatmap is not None or remove is not None or (dets and (draw or redact is not None)):      # (else the frame stays as it is)
         dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
         packed = torch.from_numpy(_pack_dets(dets, class_mapping)).cuda()
         if redact is not None:
             redact = (redact[0] if redact[0] == "all" else tuple(redact[0]),) + tuple(redact[1:])
         states = _eager_states(class_mapping)
         spec = entry.PassSpec(annotate=True, redact=redact, draw=draw, track=track, track_scene_cut=track_scene_cut, track_trails=track_trails,
-                              track_motion=radius, heat=heatmap, count=count, zone=zone)
+                              track_motion=radius, heat=heatmap, count=count, zone=zone, remove=remove)
         chain = EditChain(states, spec, 1, 1, frame.shape[:2], rgb)
         chain.update(dev.view(-1), 0, packed, states.one_frame())         # (in front of the edits: ``dev`` is still the frame as it came)
         chain.edit(0, dev)
@@ -888,6 +902,111 @@ def reset_heat(training_manager, detector, in_flight=1):
         _eager_states(training_manager.class_mapping).reset_heat()
 
 
+def remove_from_args(args, class_mapping):
+    """(host only) The removal the command line asks for -> ((classes, S, T, M) as ``submit_batch(remove=...)`` takes it, the path of
+    ``--plate_out`` or None), or (None, None) without ``--remove``.  classes: "all", or the tuple of names (of ``class_mapping``, the
+    active one) in the order given.  ValueError, with the reason, for ``--remove_settle`` / ``--remove_tol`` / ``--remove_margin`` /
+    ``--plate_out`` without ``--remove``, an unknown class name, an S outside 1..255, a T outside 0..255, an M outside 0..64 and a
+    ``--plate_out`` that does not end in .png."""
+    if args.remove is None:
+        for flag, value in (("--remove_settle", args.remove_settle), ("--remove_tol", args.remove_tol), ("--remove_margin", args.remove_margin),
+                            ("--plate_out", args.plate_out)):
+            if value is not None:
+                raise ValueError("%s=%s is a setting of the removal: it needs --remove CLASSES" % (flag, value))
+        return None, None
+    names = [n.strip() for n in args.remove.split(",") if n.strip()]
+    if not names:
+        raise ValueError("--remove takes comma-separated class names, or all")
+    try:
+        classes = "all" if names == ["all"] else ops.plate_class_list(_names_by_index(class_mapping), names)
+        remove = ops.plate_option(classes, args.remove_settle, args.remove_tol, args.remove_margin)
+    except ValueError as e:
+        raise ValueError("--remove / --remove_settle / --remove_tol / --remove_margin: %s" % e) from None
+    return remove, _plate_out(args.plate_out, remove)
+
+
+def _remove(remove):
+    """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame``'s ``remove`` checked -> (classes, S, T, M), or None."""
+    if remove is None:
+        return None
+    try:
+        classes, settle, tol, margin = () if isinstance(remove, str) else remove
+    except (TypeError, ValueError):
+        raise ValueError("remove=%r: (classes, settle, tol, margin)" % (remove,)) from None
+    return ops.plate_option(classes, settle, tol, margin)
+
+
+def _plate_out(plate_out, remove):
+    """``plate_out`` checked against ``remove`` -> the path, or None."""
+    if plate_out is None:
+        return None
+    if remove is None:
+        raise ValueError("plate_out=%r is where the background plate is written: it needs remove=(classes, settle, tol, margin)" % (plate_out,))
+    if not str(plate_out).lower().endswith(".png"):
+        raise ValueError("plate_out=%r: the plate is written as an RGB PNG, a path that ends in .png" % (plate_out,))
+    return str(plate_out)
+
+
+def plate_summaries(states):
+    """``states``: {(h, w, rgb): a plate state's host copy (numpy)} -> {(h, w, rgb): (frames, known, the (h, w, 3) plate as R, G, B with
+    unknown pixels black)} for every state that saw a frame.  A size whose frames came in both channel orders (frames decoded by
+    different decoders) has learned two plates, and both are reported."""
+    met = {}
+    for (h, w, rgb), st in sorted(states.items()):
+        frames, known, plate, _ = ops.plate_image(st, h, w)
+        if frames > 0:
+            met[(h, w, rgb)] = (frames, known, plate if rgb else plate[:, :, ::-1])
+    return met
+
+
+def _plate_order_tag(key, summaries):
+    """"" for a size met in one channel order; else which of its two plates this is."""
+    h, w, rgb = key
+    if (h, w, not rgb) not in summaries:
+        return ""
+    return "rgb" if rgb else "bgr"
+
+
+def print_plates(summaries):
+    """One line per frame size met: ``plate 1242x375: 128 frames, 97.3 % known``; a size met in both channel orders has a line per order,
+    ``plate 1242x375 (bgr frames): ...`` and ``plate 1242x375 (rgb frames): ...``."""
+    for key, (frames, known, _) in sorted(summaries.items()):
+        h, w, _ = key
+        tag = _plate_order_tag(key, summaries)
+        print("plate {}x{}{}: {} frames, {:.1f} % known".format(w, h, " (%s frames)" % tag if tag else "", frames, 100.0 * known / (h * w)))
+
+
+def write_plates(path, summaries):
+    """Every plate of ``plate_summaries``'s result written as an RGB PNG with PIL, named as ``heatmap_paths`` names its files -- ``path``
+    itself for one size, ``<stem>_<w>x<h>.png`` for several --, with ``_bgr`` / ``_rgb`` behind the size where one size has two plates
+    -> the paths written."""
+    from PIL import Image as PilImage
+    by_size = heatmap_paths(path, {key[:2] for key in summaries})
+    paths = {}
+    for key in sorted(summaries):
+        out, tag = by_size[key[:2]], _plate_order_tag(key, summaries)
+        paths[key] = "%s_%s%s" % (out[:-4], tag, out[-4:]) if tag else out
+        PilImage.fromarray(np.ascontiguousarray(summaries[key][2]), mode="RGB").save(paths[key])
+    return [paths[key] for key in sorted(paths)]
+
+
+def _plate_states(training_manager, eng):
+    """The host copies of the plate states of ``eng``, or of the eager path with None: {(h, w, rgb): numpy int32}."""
+    import torch
+    torch.cuda.synchronize()
+    states = eng.edit_states if eng is not None else _eager_states(training_manager.class_mapping)
+    return {key: st.cpu().numpy() for key, st in states.plate.items()}
+
+
+def reset_plate(training_manager, detector, in_flight=1):
+    """An empty plate before a new sequence: the states of the engine ``in_flight`` names, or the eager path's."""
+    eng = _engine(training_manager, detector, in_flight)
+    if eng is not None:
+        eng.plate_reset()
+    else:
+        _eager_states(training_manager.class_mapping).reset_plate()
+
+
 def _lookback_frames(track_lookback, track, eng, B):
     """``annotate_images`` / ``annotate_stream``'s ``track_lookback`` checked -> the look-back of their passes, or None."""
     if track_lookback is None:
@@ -940,7 +1059,7 @@ def _print_drawn(dets, width, height):
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                        track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None):
+                        track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
@@ -958,7 +1077,9 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     number ``frame_no``.
     ``zone`` = (zones, classes, W, anchor) (with ``track``): the frame is one more step of the zone state the calls before it left (DESIGN
     §8 "Zone rule"; ``reset_zones`` starts over, ``reset_tracks`` ends the ids and keeps the totals): the zones are drawn unless ``draw``
-    is False, and ``zones_out``, a text file, receives the frame's rows ``frame,zone,kind,id,cls,dwell``."""
+    is False, and ``zones_out``, a text file, receives the frame's rows ``frame,zone,kind,id,cls,dwell``.
+    ``remove`` = (classes, S, T, M): the frame teaches the background plate of the calls before this one (``reset_plate`` starts an empty
+    one), and the boxes of those classes are painted out with it (DESIGN §8 "Plate rule")."""
     count = _count(count, track)
     if counts_out is not None and count is None:
         raise ValueError("counts_out is where the crossings are written: it needs count=(lines, classes, width)")
@@ -987,6 +1108,9 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     if zone is not None:
         motion["zone"] = zone
     heatmap = _heatmap(heatmap)
+    remove = _remove(remove)
+    if remove is not None:
+        motion["remove"] = remove
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1)
     info = {}
@@ -1412,7 +1536,8 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-              track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None):
+              track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None,
+              plate_out=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
@@ -1421,6 +1546,10 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     motion = {} if track_motion is None else {"track_motion": track_motion}
     heatmap = _heatmap(heatmap)
     heatmap_out = _heatmap_out(heatmap_out, heatmap)
+    remove = _remove(remove)
+    plate_out = _plate_out(plate_out, remove)
+    if remove is not None and remove[0] != "all":         # (unknown names are refused here, in front of any capture)
+        ops.plate_class_list(_names_by_index(training_manager.class_mapping), remove[0])
     count = _count(count, track)
     if counts_out is not None and count is None:
         raise ValueError("counts_out=%r is where the crossings are written: it needs count=(lines, classes, width)" % (counts_out,))
@@ -1442,6 +1571,9 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
         if heatmap is not None:                           # a cold map for the list
             motion["heatmap"] = tracking["heat"] = heatmap
             reset_heat(training_manager, detector, 1 if eng is None else eng.in_flight)
+        if remove is not None:                            # an empty plate for the list
+            motion["remove"] = tracking["remove"] = remove
+            reset_plate(training_manager, detector, 1 if eng is None else eng.in_flight)
         if track is not None:                             # a new sequence; its frames are submitted in input order, as every list's are
             reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
         if count is not None:                             # zero totals for the list
@@ -1494,6 +1626,11 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             print_zones(len(zone[0]), ops.zone_totals(_zone_state(training_manager, eng)))
         if heatmap_out is not None:                       # (host only: the states read back, their t values as grey PNG files)
             write_heatmaps(heatmap_out, _heat_states(training_manager, eng))
+        if remove is not None:                            # (host only: the states read back; the plate as an RGB PNG, unknown pixels black)
+            plates = plate_summaries(_plate_states(training_manager, eng))
+            print_plates(plates)
+            if plate_out is not None:
+                write_plates(plate_out, plates)
     finally:
         if counts_log is not None:
             counts_log.close()
@@ -1506,13 +1643,13 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
                     track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
-                    counts_out=None, zone=None, zones_out=None):
+                    counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out`` / ``remove`` / ``plate_out``: as ``annotate_images``."""
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
     if isinstance(writer_or_out_dir, y4m.Y4mWriter):
         make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma)
@@ -1522,14 +1659,15 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
     _annotate(training_manager, detector, source, lambda prepare, ahead: _loaded_stream(source, prepare, ahead), make_sink, resize_min, resize_max,
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
               detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
-              heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out)
+              heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out, remove=remove,
+              plate_out=plate_out)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
-                    heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None):
+                    heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1596,7 +1734,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               lambda prepare, ahead: _loaded_files(paths, lambda path: prepare(path, _load_frame(path, device_decode, device_png)), ahead),
               make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-              track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out)
+              track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out,
+              remove=remove, plate_out=plate_out)
 
 
 def build_parser():
@@ -1711,6 +1850,21 @@ def build_parser():
                    help="every frame takes ceil(v / 2^S) off every pixel of the map, 1..15; 0 (the default): the map never cools (needs --heatmap)")
     p.add_argument("--heatmap_out", dest="heatmap_out", default=None, metavar="PATH.png",
                    help="write the map at the end of the list as an 8-bit grey PNG, one per frame size met (needs --heatmap)")
+    p.add_argument("--remove", dest="remove", default=None, metavar="CLASSES",
+                   help="paint the objects of these classes (comma-separated names of the active mapping, or all) out of every frame with a "
+                        "background plate learned from the frames themselves, for fixed-camera footage: a pixel that no box of any class "
+                        "touches and that holds still for S frames becomes background; until the background under a box is known the "
+                        "redaction shows there (with --redact of the same classes), else black.  An object that stands still and is never "
+                        "detected becomes background")
+    p.add_argument("--remove_settle", dest="remove_settle", type=int, default=None, metavar="S",
+                   help="the frames a pixel must hold still to become background, 1..255 (default 8, provisional: not measured on real "
+                        "footage; needs --remove)")
+    p.add_argument("--remove_tol", dest="remove_tol", type=int, default=None, metavar="T",
+                   help="how far a channel may lie from the value its run began with, 0..255 (default 10, provisional; needs --remove)")
+    p.add_argument("--remove_margin", dest="remove_margin", type=int, default=None, metavar="M",
+                   help="the pixels every box grows by, 0..64 (default 8, provisional; needs --remove)")
+    p.add_argument("--plate_out", dest="plate_out", default=None, metavar="PATH.png",
+                   help="write the plate at the end of the list as an RGB PNG with unknown pixels black, one per frame size met (needs --remove)")
     p.add_argument("--count_line", dest="count_line", action="append", default=None, metavar="X1,Y1,X2,Y2",
                    help="count the tracks whose box centre crosses the line from (X1,Y1) to (X2,Y2), in source-frame pixels (-32768..65535), "
                         "once per id and direction; a value that begins with a minus sign is written --count_line=-5,0,-5,100; repeatable up to 8 "
@@ -1821,6 +1975,11 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
         tracking["heatmap"] = heatmap
     if heatmap_out is not None:
         tracking["heatmap_out"] = heatmap_out
+    remove, plate_out = remove_from_args(args, class_mapping)
+    if remove is not None:
+        tracking["remove"] = remove
+    if plate_out is not None:
+        tracking["plate_out"] = plate_out
     count, counts_out = count_from_args(args, class_mapping)
     if count is not None:
         tracking["count"] = count

@@ -317,11 +317,12 @@ class PassSpec:
     heat: object = None
     count: object = None
     zone: object = None                                  # (zones, classes, W, anchor), ops.zone_option's form: frame_edit.EditChain reads it
+    remove: object = None                                # (classes, S, T, M), ops.plate_option's form
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
                 track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                track_trails=None, heat=None, count=None, zone=None):
+                track_trails=None, heat=None, count=None, zone=None, remove=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -389,6 +390,13 @@ class PassSpec:
             if track is None:
                 raise FrcnnError("submit_batch: zone= tests the tracker's ids against the zones: pass track=(thr, hold, grow) too")
             zone = engine.zone_option(zone)
+        if remove is not None:
+            if not annotate:
+                raise FrcnnError("submit_batch: remove= paints the objects out of the frame an ANNOTATING pass returns: pass annotate=True")
+            if not engine.device_preprocess:
+                raise FrcnnError("submit_batch: remove= needs the device-side preprocess: a foreign preprocess_func uploads float pixels, "
+                                 "and the plate is learned from the uint8 source frame")
+            remove = engine.remove_option(remove)
         if redact is not None:
             redact = engine.redact_option(redact)
         jpeg_mode, y4m_mode = JPEG_MODE, Y4M_MODE
@@ -423,7 +431,7 @@ class PassSpec:
             raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
-                   track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count, zone=zone)
+                   track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove)
 
     @property
     def delayed(self):
@@ -465,6 +473,8 @@ class PassSpec:
             key = key + ("count",) + self.count
         if self.zone is not None:
             key = key + ("zone",) + self.zone
+        if self.remove is not None:
+            key = key + ("remove",) + self.remove
         return key
 
 
@@ -481,7 +491,8 @@ class _Slot:
                  "jpg_count", "png_items", "png_dec", "full_items", "jpg_decs", "y4m_items", "y4m_mode", "redact", "nodraw", "chain",
                  "track", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
                  "track_lookback", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
-                 "track_scene_cut", "cuts_pin", "_cuts_raw", "track_trails", "heat", "count", "count_pin", "_count_raw", "zone", "zone_pin", "_zone_raw")
+                 "track_scene_cut", "cuts_pin", "_cuts_raw", "track_trails", "heat", "count", "count_pin", "_count_raw", "zone", "zone_pin", "_zone_raw",
+                 "remove")
 
     def __init__(self):
         for name in self.__slots__:
@@ -748,6 +759,39 @@ class DetectionEntry:
             raise FrcnnError("submit_batch: count=%r: %s" % (count, e)) from None
         return lines, classes, width
 
+    # ------------------------------------------------------------------ background plate
+    def plate_state(self, h, w, rgb=None):
+        """The engine's plate state for source frames of (h, w) (device int32, ops.plate_state; ``ops.plate_image`` reads it): one per
+        size and channel order, shared by every pass submitted with ``remove=`` whatever its other options.  ``rgb`` None: the one
+        there is of that size (made for B, G, R frames if there is none), else the one of that channel order.  ``plate_reset()`` empties
+        it; ``track_reset()`` does not."""
+        if rgb is None:
+            made = [k[2] for k in self.edit_states.plate if k[:2] == (int(h), int(w))]
+            if len(made) > 1:
+                raise FrcnnError("plate_state: frames of %dx%d were met in both channel orders: say rgb=True or rgb=False" % (w, h))
+            rgb = made[0] if made else False
+        return self.edit_states.plate_state(h, w, rgb)
+
+    def plate_reset(self):
+        """An empty plate for every size: the states are zeroed on the ordered stream, behind the remove passes submitted so far."""
+        with torch.cuda.stream(self.track_stream):
+            self.edit_states.reset_plate()
+
+    def remove_option(self, remove):
+        """``submit_batch``'s ``remove`` checked and normalised -> (classes, S, T, M): classes "all" or a tuple of this engine's class
+        names, None for S, T or M replaced by the (provisional) defaults (8, 10, 8).  FrcnnError, with the reason, for anything else."""
+        try:
+            classes, settle, tol, margin = () if isinstance(remove, str) else remove
+        except (TypeError, ValueError):
+            raise FrcnnError("submit_batch: remove=%r: (classes, settle, tol, margin)" % (remove,)) from None
+        try:
+            classes, settle, tol, margin = ops.plate_option(classes, settle, tol, margin)
+            if classes != "all":
+                classes = ops.plate_class_list(self.class_names(), classes)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: remove=%r: %s" % (remove, e)) from None
+        return classes, settle, tol, margin
+
     # ------------------------------------------------------------------ zones
     def zone_state(self):
         """The engine's zone state (device int32, ops.zone_state), made on first use, of ``track_trails_capacity()`` entries: one,
@@ -884,7 +928,7 @@ class DetectionEntry:
         -> (the pinned side as a numpy array, the device view the pass reads the pairs from: (B, 2) f64, one image's (2,) for B = 1)."""
         B, off = s.batch, s.frames * seg
         s.seg = seg
-        tail = 16 if s.track or s.heat else 0            # a tracking or heat pass: | the count of real frames, int32 (ops.track_update's n_frames)]
+        tail = 16 if s.track or s.heat or s.remove else 0     # a tracking, heat or remove pass: | the count of real frames, int32 (ops.track_update's n_frames)]
         s.io_dev = torch.zeros(off + 16 * B + tail, dtype=torch.uint8, device="cuda")
         fine("buffers: device staging")
         s.io_pin = self._pinned.take(off + 16 * B + tail, zero=True)
@@ -1044,7 +1088,7 @@ class DetectionEntry:
             s.track_lookback, s.track_backtrack = spec.track_lookback or spec.track_backtrack, spec.track_backtrack      # (both: the delayed path is one)
             s.every, s.frames = spec.detect_every, B * (spec.detect_every or 1)
             s.track_scene_cut, s.track_trails, s.heat, s.count = spec.track_scene_cut, spec.track_trails, spec.heat, spec.count
-            s.zone = spec.zone
+            s.zone, s.remove = spec.zone, spec.remove
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -1288,7 +1332,7 @@ class DetectionEntry:
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
                      track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
-                     heat=None, count=None, zone=None):
+                     heat=None, count=None, zone=None, remove=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1397,11 +1441,24 @@ class DetectionEntry:
         False still counts.  Every result of such a pass carries in its ONE trailing dict "zones": {"occupancy": [per zone],
         "events": [(zone, kind, id, cls, dwell)]}, kind 1 enter, 0 exit, 2 lost.  Refused by name without ``track`` and for options out
         of range.  Without it every key and byte is what it was.
+        ``remove`` = (classes, S, T, M) (annotating passes, with every other option, without ``track`` too; ("remove", classes, S, T, M)
+        appended behind ("zone", ...); classes "all" or names, S the settle 1..255, T the tolerance 0..255, M the margin 0..64, None for
+        the PROVISIONAL defaults 8, 10 and 8, which nobody has measured on real footage): the plate rule (DESIGN §8 "Plate rule") paints
+        the objects of those classes out.  For each frame one ops.plate_update learns the background from the untouched frame outside
+        EVERY row of the buffer the edits read -- the packed detections of a plain pass, every tracked row of a tracking pass, held ones
+        too, the emitted rows of a delayed pass, back-filled ones too -- into the engine's plate state of the frame size and channel
+        order (``plate_state``; it lives across passes and submits until ``plate_reset()``; ``track_reset()`` leaves it; a
+        ``track_scene_cut`` frame's cut word empties it), and one ops.plate_fill_u8 behind the redaction copies the plate into the boxes
+        of the classes: where it is not known yet the redaction shows, if ``redact`` covers the classes, else black.  The plate depends
+        on the order of the frames: such passes replay in submit order on one stream, as heat passes do.  An object that stands still
+        and is never detected becomes background after S frames.  The results are what they are without it: only the frames' bytes
+        change.  Refused by name without ``annotate``, on an engine with a foreign preprocess and for options out of range.  Without it
+        every key and byte is what it was.
         The order of all these steps in a pass is stated once, in ``frame_edit.EditChain``'s docstring."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-                                track_trails=track_trails, heat=heat, count=count, zone=zone)
+                                track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1453,7 +1510,7 @@ class DetectionEntry:
                 metas.append(self._canvas_frame(s, i, pixels[j]))
             elif not isinstance(pixels[j][0], JpegFile):
                 np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
-        if s.track or s.heat:                                       # (a heat pass too: the map depends on the order of the frames)
+        if s.track or s.heat or s.remove:                           # (a heat or remove pass too: their states depend on the order of the frames)
             s.n_frames_host[0] = len(pixels) if images else -1      # goes up with the frames: the padding does not advance the tracker; -1: a flush
             st = self.track_stream
         else:

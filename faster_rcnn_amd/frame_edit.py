@@ -26,7 +26,8 @@ class EditStates:
         self.lookback = {}                               # (h, w, F) -> (ops.track_lookback_state: the frames tracked but not yet emitted, its back)
         self.trails = {}                                 # length N -> ops.track_trails_state
         self.heat = {}                                   # (h, w) of the source frames -> ops.heat_state
-        self._annotate, self._redact, self._track = {}, {}, {}
+        self.plate = {}                                  # (h, w, rgb) of the source frames -> ops.plate_state
+        self._annotate, self._redact, self._track, self._track_remove = {}, {}, {}, {}
 
     def tracker(self):
         """The ONE tracker state (device int32, ops.track_state)."""
@@ -78,6 +79,11 @@ class EditStates:
         """The heat state for source frames of (h, w): one per size, whatever the other options of the calls that heat it."""
         return _made(self.heat, (int(h), int(w)), lambda: ops.heat_state(h, w))
 
+    def plate_state(self, h, w, rgb):
+        """The plate state for source frames of (h, w) whose bytes are R, G, B (``rgb``) or B, G, R: one per size and channel order --
+        the plate is kept in the frames' own byte order --, whatever the other options of the calls that learn it."""
+        return _made(self.plate, (int(h), int(w), bool(rgb)), lambda: ops.plate_state(h, w))
+
     def annotate_tables(self, draw=True):
         """The drawing tables of ops.annotate_u8 (uploaded once).  ``draw`` False: the same tables with no drawable class -- the drawing
         step of a chain that only redacts paints nothing, with no branch in the chain."""
@@ -88,15 +94,19 @@ class EditStates:
         """The class table of ops.redact_u8 (and of the heat and count updates) for ``classes``, "all" or a tuple of names."""
         return _made(self._redact, classes, lambda: ops.redact_table(self.class_names, classes))
 
-    def track_table(self, redact_classes=None):
-        """The class table of ops.track_update: the classes the drawing rule draws united with ``redact_classes``."""
+    def track_table(self, redact_classes=None, remove_classes=None):
+        """The class table of ops.track_update: the classes the drawing rule draws united with ``redact_classes`` and with
+        ``remove_classes``.  (The tables of a chain that removes are kept apart: a key without ``remove_classes`` is what it was.)"""
         def make():
             names = self.class_names
             chosen = [n for n in names if n and n != "bg" and n not in ops.ANNOTATE_SKIP]
-            if redact_classes is not None:
-                chosen += [n for n in ops.redact_class_list(names, redact_classes) if n not in chosen]
+            for classes in (redact_classes, remove_classes):
+                if classes is not None:
+                    chosen += [n for n in ops.redact_class_list(names, classes) if n not in chosen]
             return ops.track_table(names, chosen)
-        return _made(self._track, redact_classes, make)
+        if remove_classes is None:
+            return _made(self._track, redact_classes, make)
+        return _made(self._track_remove, (redact_classes, remove_classes), make)
 
     def reset_tracks(self):
         """Forget every track: the ids end, and what was counted stays counted."""
@@ -116,6 +126,11 @@ class EditStates:
         """A cold map for every size."""
         for state in self.heat.values():
             ops.heat_reset(state)
+
+    def reset_plate(self):
+        """An empty plate for every size and channel order."""
+        for state in self.plate.values():
+            ops.plate_reset(state)
 
     def reset_counts(self):
         """Zero totals and no entries."""
@@ -143,7 +158,11 @@ class EditChain:
       4. ops.count_update -> ``count_lists``;
       5. ops.zone_update -> ``zone_lists``: the same ``tracked`` / ``n_frames`` / ``gate``, so a delayed pass counts in emitted order.
     ``edit``, once per frame, on ``rows(i)`` -- the frame's emitted buffer, else its tracked buffer, else its packed detections:
+     5b. ops.plate_update, on the frame NO edit has touched: every row blocks, the held and back-filled ones too, whatever its class;
+         with ``track_scene_cut`` the frame's cut word empties the plate first;
       6. ops.redact_u8: every tracked row, the held ones too;
+     6b. ops.plate_fill_u8, over the redaction: the rows of the remove classes become the plate.  Where the plate is not known yet
+         the redaction shows, if the chain redacts all the remove classes (``keep_unknown``); else black;
       7. ops.heat_update (the live rows) and ops.heat_draw_u8;
       8. ops.zone_draw_u8, unless nothing is drawn: a tinted area lies under every line;
       9. ops.track_trails_draw_u8;
@@ -174,7 +193,8 @@ class EditChain:
             self.redact_table = states.redact_table(classes)
             self.redact_ws = torch.empty(max(ops.redact_ws_bytes(h, w, mode, size), 16), dtype=torch.uint8, device="cuda")
         if spec.track:
-            self.state, self.track_table = states.tracker(), states.track_table(spec.redact[0] if spec.redact else None)
+            self.state = states.tracker()
+            self.track_table = states.track_table(spec.redact[0] if spec.redact else None, spec.remove[0] if spec.remove else None)
             self.motion = states.motion_state(h, w) if spec.track_motion else None
             self.expire = self.trails_expire(spec.track, spec.detect_every)
             if spec.track_scene_cut:
@@ -192,6 +212,13 @@ class EditChain:
                 self.zone_lists.zero_()
         if spec.heat:
             self.heat, self.heat_table = states.heat_state(h, w), states.redact_table(spec.heat[0])
+        if spec.remove:
+            classes = spec.remove[0]
+            self.plate, self.remove_table = states.plate_state(h, w, self.rgb), states.redact_table(classes)
+            names = states.class_names
+            # the redaction shows until the background is known where it covers the remove classes ("all" stands for its names); else black
+            covered = spec.redact and set(ops.redact_class_list(names, classes)) <= set(ops.redact_class_list(names, spec.redact[0]))
+            self.keep_unknown = bool(covered)
         if self.lookback:
             self.lb_frames = torch.zeros((F, h, w, 3), dtype=torch.uint8, device="cuda")
 
@@ -248,11 +275,17 @@ class EditChain:
         return self.packed[i] if self.F > 1 else self.packed
 
     def edit(self, i, frame):
-        """Steps 6-11 on ``frame``, an (h, w, 3) uint8 device tensor: frame i of the pass, or of the pass before it in a delayed pass."""
+        """Steps 5b-11 on ``frame``, an (h, w, 3) uint8 device tensor: frame i of the pass, or of the pass before it in a delayed pass."""
         sp, (h, w), rows, tracked = self.spec, self.hw, self.rows(i), bool(self.spec.track)
+        if sp.remove:
+            _, settle, tol, p_margin = sp.remove
+            ops.plate_update(self.plate, frame, rows, settle, tol, p_margin, i, self.n_frames, gate=self.gate,
+                             cut=None if self.cuts is None else self.cuts[i], tracked=tracked)
         if sp.redact:
             _, mode, size, margin = sp.redact
             ops.redact_u8(frame, rows, self.redact_table, mode, size, margin, workspace=self.redact_ws, tracked=tracked)
+        if sp.remove:
+            ops.plate_fill_u8(frame, self.plate, rows, self.remove_table, p_margin, keep_unknown=self.keep_unknown, tracked=tracked)
         if sp.heat:
             _, alpha, decay = sp.heat
             ops.heat_update(self.heat, h, w, rows, self.heat_table, decay, i, self.n_frames, gate=self.gate, tracked=tracked)

@@ -2042,6 +2042,128 @@ def zone_events(zlist):
     return [tuple(int(v) for v in c[ZONE_LIST_HEAD + 5 * k:ZONE_LIST_HEAD + 5 * k + 5]) for k in range(min(max(int(c[0]), 0), ZONE_MAX_EVENTS))]
 
 
+# ----------------------------------------------------------------------------- background plate
+# (smallest, largest, the default) of the settle S, the tolerance T and the margin M.  The defaults are PROVISIONAL: nobody has measured
+# them on real footage.
+PLATE_SETTLE, PLATE_TOL, PLATE_MARGIN = _lib.PLATE_SETTLE, _lib.PLATE_TOL, _lib.PLATE_MARGIN
+
+
+def plate_option(classes, settle=None, tol=None, margin=None):
+    """(host only) The remove option checked -> (classes, S, T, M): classes "all" or a tuple of class names (which names there are is the
+    caller's to check: ``redact_class_list``), S the frames a pixel must hold still to become background, 1..255 (None: 8), T how far
+    a channel may lie from the run's anchor, 0..255 (None: 10), M the pixels a box grows by, 0..64 (None: 8).  The defaults are
+    provisional.  ValueError with the reason."""
+    if isinstance(classes, str):
+        classes = (classes,)
+    try:
+        classes = tuple(classes)
+    except TypeError:
+        raise ValueError("remove classes=%r: \"all\", a class name or a list of class names" % (classes,)) from None
+    if not classes or not all(isinstance(c, str) and c for c in classes):
+        raise ValueError("remove classes=%r: \"all\", a class name or a list of class names" % (classes,))
+    classes = "all" if classes == ("all",) else classes
+    out = []
+    for name, v, (lo, hi, default) in (("settle", settle, PLATE_SETTLE), ("tol", tol, PLATE_TOL), ("margin", margin, PLATE_MARGIN)):
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError("remove %s=%r: an integer in %d..%d" % (name, v, lo, hi))
+        out.append(int(v))
+    return (classes,) + tuple(out)
+
+
+def plate_class_list(class_names, classes):
+    """(host only) ``redact_class_list`` for the remove classes: the same reading of "all" and of names, and the refusal of an unknown
+    name says whose it is."""
+    try:
+        return redact_class_list(class_names, classes)
+    except ValueError as e:
+        text = str(e)
+        raise ValueError("remove: " + (text[len("redact: "):] if text.startswith("redact: ") else text)) from None
+
+
+def plate_state_words(h, w):
+    """(host only) 4-byte words of a plate state BUFFER for frames of (h, w) (frcnn_plate_state_bytes / 4): the state, 4 + 2 h w words
+    [frames, known, 0, 0 | px[h][w][2]], and the update kernel's scratch words behind it."""
+    n = int(_lib.load().frcnn_plate_state_bytes(int(h), int(w)))
+    if n == 0:
+        raise _lib.FrcnnError("plate state: frame %rx%r out of range (sides 1..%d)" % (h, w, _lib.REDACT_MAX_SIDE))
+    return n // 4
+
+
+def plate_state(h, w):
+    """An empty plate state for frames of (h, w): a zeroed int32 device tensor of ``plate_state_words`` words, [frames, known, 0, 0 |
+    px[h][w][2] | scratch] (include/ext/frcnn_hip_plate.h).  Zeroing it (``plate_reset``) empties it; ``plate_image`` reads it."""
+    _require_gpu()
+    return torch.zeros(plate_state_words(h, w), dtype=torch.int32, device="cuda")
+
+
+def plate_reset(state):
+    """Empty the state (on the current stream): no frames, no pixel known."""
+    state.zero_()
+    return state
+
+
+def plate_image(state, h, w):
+    """(frames, known, the (h, w, 3) uint8 plate in the frames' byte order with unknown pixels black, the (h, w) bool mask of the known
+    pixels) of a plate state, device tensor or its host copy (torch or numpy): host arrays."""
+    h, w = int(h), int(w)
+    host = state.detach().cpu().numpy() if isinstance(state, torch.Tensor) else np.asarray(state)
+    w0 = np.ascontiguousarray(host[4:4 + 2 * h * w].reshape(h, w, 2)[:, :, 0]).view(np.uint8).reshape(h, w, 4)
+    known = w0[:, :, 3] != 0
+    return int(host[0]), int(host[1]), np.where(known[:, :, None], w0[:, :, :3], 0).astype(np.uint8), known
+
+
+def _plate_rows(det_packed, tracked):
+    per = 8 if tracked else 7
+    assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.dim() == 1 and det_packed.is_contiguous()
+    assert (int(det_packed.numel()) - 4) % per == 0
+    return (int(det_packed.numel()) - 4) // per
+
+
+def plate_update(state, frame, det_packed, settle=None, tol=None, margin=None, frame_index=0, n_frames=None, gate=None, cut=None,
+                 tracked=False):
+    """UPDATE of the plate rule (DESIGN §8 "Plate rule", frcnn_plate_update) from ``frame``, an (h, w, 3) uint8 device tensor that no
+    edit has touched yet: every pixel outside the boxes of ``det_packed`` grown by ``margin`` -- EVERY row of the post-process's packed
+    buffer whatever its class, or with ``tracked`` True of one tracked buffer of ``track_update`` (plain or widened), the held and
+    back-filled rows too -- that has stayed within ``tol`` of its run's anchor for ``settle`` frames becomes the plate of ``state``
+    (``plate_state``); a pixel under a box starts over and keeps its plate.  The frame counts when ``frame_index`` < *``n_frames`` (a
+    device int32 word; None: a word that says 1, allocated here -- a captured call passes its own) and, with ``gate`` (a device word),
+    *gate != 0; else nothing is written.  ``cut``: a device int32 word; non-zero empties the plate in front of the update.  Two
+    launches, everything guarded on the device: the call can be captured in a graph -> ``state``."""
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    assert int(state.numel()) == plate_state_words(h, w)
+    rows = _plate_rows(det_packed, tracked)
+    if n_frames is None:
+        n_frames = torch.ones(1, dtype=torch.int32, device="cuda")
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert gate is None or (gate.is_cuda and gate.dtype == torch.int32 and gate.numel() >= 1)
+    assert cut is None or (cut.is_cuda and cut.dtype == torch.int32 and cut.numel() >= 1)
+    _lib.call("frcnn_plate_update", _p(state), h, w, _p(frame), _p(det_packed), rows, int(bool(tracked)),
+              PLATE_MARGIN[2] if margin is None else int(margin), PLATE_SETTLE[2] if settle is None else int(settle),
+              PLATE_TOL[2] if tol is None else int(tol), int(frame_index), _p(n_frames), _p(gate), _p(cut), _stream())
+    return state
+
+
+def plate_fill_u8(frame, state, det_packed, table, margin=None, keep_unknown=False, tracked=False):
+    """FILL of the plate rule (frcnn_plate_fill_u8): every pixel of ``frame``, an (h, w, 3) uint8 device tensor, edited in place and
+    returned, that lies in a box of ``det_packed`` (as ``plate_update`` reads it) of a class set in ``table`` (``redact_table``'s form),
+    grown by ``margin``, becomes the plate's where ``state`` knows it; where it does not, black, or with ``keep_unknown`` what it is.
+    One launch; reads the counts from device memory, so the call can be captured in a graph."""
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    assert int(state.numel()) == plate_state_words(h, w)
+    rows = _plate_rows(det_packed, tracked)
+    _lib.call("frcnn_plate_fill_u8", _p(frame), h, w, _p(state), _p(det_packed), rows, int(bool(tracked)), _p(table), int(table.numel()),
+              PLATE_MARGIN[2] if margin is None else int(margin), int(bool(keep_unknown)), _stream())
+    return frame
+
+
 TRACK_LOOKBACK = _lib.TRACK_LOOKBACK            # (smallest, largest, the default) look-back of ``track_lookback``, in frames
 
 
