@@ -514,6 +514,26 @@ PLATE_MARGIN = (0, 64, 8)
 PLATE_MAX_FRAMES = 65536
 PLATE_TILE = (128, 8)
 
+TRACK_REID_VERSION = 1          # include/ext/frcnn_hip_track_reid.h FRCNN_TRACK_REID_VERSION
+TRACK_REID_SIGNATURES = {
+    "frcnn_track_reid_version": (I, []),
+    "frcnn_track_reid_state_bytes": (c_size_t, [I]),
+    "frcnn_track_reid_workspace_bytes": (c_size_t, [I, I]),
+    "frcnn_track_reid_update": (I, [P, I, P, ctypes.c_longlong, I, I, I, P, ctypes.c_longlong, I, I, P, P, P, I, I, I, P, P, ctypes.c_longlong,
+                                    P, P]),
+}
+# (smallest, largest, the default) pct and keep (1 / 100 / FRCNN_TRACK_REID_DEFAULT_PCT, 1 / _MAX_KEEP / _DEFAULT_KEEP: the defaults are
+# PROVISIONAL, not measured on real footage), the entries of a state at most (_MAX), the words of a signature, of an entry and of a
+# frame's list (_SIG_WORDS, _ENTRY_WORDS, _LIST_WORDS), the events a list holds (_MAX_EVENTS) and the largest distance (_MAX_DISTANCE)
+TRACK_REID_PCT = (1, 100, 25)
+TRACK_REID_KEEP = (1, 4095, 250)
+TRACK_REID_MAX = 256
+TRACK_REID_SIG_WORDS = 192
+TRACK_REID_ENTRY_WORDS = 5 + TRACK_REID_SIG_WORDS
+TRACK_REID_MAX_EVENTS = 32
+TRACK_REID_LIST_WORDS = 4 + 5 * TRACK_REID_MAX_EVENTS
+TRACK_REID_MAX_DISTANCE = 8192
+
 TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
 TRACK_LOOKBACK_SIGNATURES = {
     "frcnn_track_lookback_version": (I, []),
@@ -738,6 +758,15 @@ def load():
     if lib.frcnn_plate_version() != PLATE_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_plate_version()} of the background-plate extension, this binding "
                          f"{PLATE_VERSION} (include/ext/frcnn_hip_plate.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in TRACK_REID_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_track_reid.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_track_reid_version() != TRACK_REID_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_reid_version()} of the re-identify extension, this binding "
+                         f"{TRACK_REID_VERSION} (include/ext/frcnn_hip_track_reid.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

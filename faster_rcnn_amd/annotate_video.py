@@ -123,6 +123,15 @@ list starts from an empty plate; ``get_annotated_frame(remove=)`` and the eager 
 empties it).  ``plate_out=PATH.png`` (``--plate_out``) writes the plate at the end as an RGB PNG with unknown pixels black, one per
 frame size met, named as ``--heatmap_out`` names its files, and one line per size is printed: ``plate 1242x375: 128 frames, 97.3 %
 known`` (a size met in both channel orders has two plates: a line and a file for each).  With every other option, ``--no_draw`` included, with and without ``--track``.
+``track_reid=(pct, keep)`` (``--track_reid [PCT]``, 1..100, bare: 25; ``--reid_keep N``, 1..4095 frames, default 250; both defaults are
+PROVISIONAL: nobody has measured them on real footage; with ``--track`` in every form but ``--track_lookback`` / ``--track_backtrack``)
+gives an object that was hidden for longer than ``--track_hold`` frames its old id back (ops.track_reid_update, csrc/track_reid.hip;
+DESIGN §8 "Re-identify rule"): every live tracked row gets a colour signature, and a new track whose signature lies within PCT percent
+of that of an id the tracker gave up at most N frames ago carries that id -- in the labels, ``--tracks_out``, the printed ``track_id``,
+the trails, the count lines (which then count it once) and the zones.  A line ``re-identified: <path> id <pid>`` is printed in front
+of that frame's lines and ``re-identified: N`` at the end; ``reid_out=PATH`` (``--reid_out``) receives a CSV row
+``frame,id,tracker_id,cls,distance,gap`` per event.  A list starts from an empty memory; ``get_annotated_frame(track_reid=)`` and the
+eager path continue it as one-frame calls (``reset_tracks`` empties it).  A ``--track_scene_cut`` cut empties it too.
 """
 import collections
 import os
@@ -317,7 +326,7 @@ def _eager_heat_state(class_mapping, h, w):
 
 
 def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
-               track_trails=None, rgb=False, heatmap=None, count=None, zone=None, remove=None):
+               track_trails=None, rgb=False, heatmap=None, count=None, zone=None, remove=None, track_reid=None):
     """The editing chain over ONE frame and its host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is edited in
     place, by a one-frame ``frame_edit.EditChain`` -- its docstring states the calls and their order -- on this class mapping's eager
     states (``reset_tracks``, ``reset_heat`` and ``reset_counts`` empty them); ``rgb``: the frame's channel order (False: B, G, R).
@@ -332,8 +341,11 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     ``count`` = (lines, classes, W) (with ``track``): ``info`` receives "crossings": [(line, dir, id, cls)].
     ``zone`` = (zones, classes, W, anchor) (with ``track``): ``info`` receives "zones": {"occupancy", "events"} as a pass's result does.
     ``remove`` = (classes, S, T, M): the frame teaches this class mapping's plate state for its size and channel order, and the boxes of
-    those classes are painted out with it (``reset_plate`` empties it); a frame without detections teaches it too."""
+    those classes are painted out with it (``reset_plate`` empties it); a frame without detections teaches it too.
+    ``track_reid`` = (pct, keep) (with ``track``): the ids are those of the re-identify rule, and ``info`` receives "reid": [(pid, tid,
+    cls, distance, gap)]."""
     import torch
+    track_reid = _track_reid(track_reid, track)
     track_trails = _track_trails(track_trails, track, draw)
     heatmap = _heatmap(heatmap)
     remove = _remove(remove)
@@ -348,12 +360,12 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
             redact = (redact[0] if redact[0] == "all" else tuple(redact[0]),) + tuple(redact[1:])
         states = _eager_states(class_mapping)
         spec = entry.PassSpec(annotate=True, redact=redact, draw=draw, track=track, track_scene_cut=track_scene_cut, track_trails=track_trails,
-                              track_motion=radius, heat=heatmap, count=count, zone=zone, remove=remove)
+                              track_motion=radius, heat=heatmap, count=count, zone=zone, remove=remove, track_reid=track_reid)
         chain = EditChain(states, spec, 1, 1, frame.shape[:2], rgb)
         chain.update(dev.view(-1), 0, packed, states.one_frame())         # (in front of the edits: ``dev`` is still the frame as it came)
         chain.edit(0, dev)
         if track is not None:
-            _, ids, held = ops.tracked_dets(chain.track_out[0].cpu().numpy(), _names_by_index(class_mapping), start=len(dets))
+            _, ids, held = ops.tracked_dets(chain.host_tracked[0].cpu().numpy(), _names_by_index(class_mapping), start=len(dets))
             for k, d in enumerate(dets):
                 d["track_id"] = int(ids[k])
             dets += held
@@ -364,6 +376,8 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
         if info is not None and zone is not None:
             zlist = chain.zone_lists[0].cpu().numpy()
             info["zones"] = {"occupancy": ops.zone_occupancy(zlist, len(zone[0])), "events": ops.zone_events(zlist)}
+        if info is not None and track_reid is not None:
+            info["reid"] = ops.track_reid_events(chain.reid_lists[0].cpu().numpy())
         frame[...] = dev.cpu().numpy()
     return frame
 
@@ -807,6 +821,83 @@ def _write_zones(zones_out, frame_no, events, class_mapping):
         zones_out.writelines(row + "\n" for row in zones_rows(frame_no, events, _names_by_index(class_mapping)))
 
 
+REID_HEADER = "frame,id,tracker_id,cls,distance,gap"
+
+
+def reid_rows(frame_no, events, names):
+    """(host only) The ``--reid_out`` rows of one frame: ``frame,id,tracker_id,cls,distance,gap`` per event (pid, tid, cls, distance, gap),
+    frames from 1, the class by its name in ``names`` (names by index), the distance 0..8192, the gap in frames."""
+    return ["%d,%d,%d,%s,%d,%d" % (frame_no, pid, tid, names[cls] if 0 <= cls < len(names) else cls, dist, gap)
+            for pid, tid, cls, dist, gap in events]
+
+
+class ReidLog:
+    """Where the re-identifications of a sequence go: the ``--reid_out`` file (``path`` None: none), and how many there were."""
+
+    def __init__(self, path, names):
+        self.names, self.total = list(names), 0
+        self.file = open(path, "w") if path is not None else None
+        if self.file is not None:
+            self.file.write(REID_HEADER + "\n")
+
+    def add(self, frame_no, events):
+        self.total += len(events)
+        if self.file is not None:
+            self.file.writelines(row + "\n" for row in reid_rows(frame_no, events, self.names))
+
+    def close(self):
+        if self.file is not None:
+            self.file.close()
+            self.file = None
+
+
+def _write_reid(reid_out, frame_no, events, class_mapping):
+    """``reid_out``: None, a ``ReidLog``, or a text file that receives the frame's CSV rows (no header)."""
+    if isinstance(reid_out, ReidLog):
+        reid_out.add(frame_no, events)
+    elif reid_out is not None:
+        reid_out.writelines(row + "\n" for row in reid_rows(frame_no, events, _names_by_index(class_mapping)))
+
+
+def _print_reid(label, events):
+    for ev in events:
+        print("re-identified: {} id {}".format(label, ev[0]))
+
+
+def _track_reid(track_reid, track):
+    """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame``'s ``track_reid`` checked -> (pct, keep), or None."""
+    if track_reid is None:
+        return None
+    if track is None:
+        raise ValueError("track_reid=%r gives the tracker's ids back: it needs track=(thr, hold, grow)" % (track_reid,))
+    try:
+        pct, keep = track_reid
+    except (TypeError, ValueError):
+        raise ValueError("track_reid=%r: (pct, keep)" % (track_reid,)) from None
+    return ops.track_reid_option(pct, keep)
+
+
+def track_reid_from_args(args):
+    """(host only) The re-identification the command line asks for -> ((pct, keep) as ``submit_batch(track_reid=...)`` takes it, the path
+    of ``--reid_out`` or None), or (None, None) without ``--track_reid``.  ValueError, with the reason, for ``--reid_keep`` / ``--reid_out``
+    without ``--track_reid``, ``--track_reid`` without ``--track`` or together with ``--track_lookback`` / ``--track_backtrack``, and for
+    values out of range."""
+    if args.track_reid is None:
+        for flag, value in (("--reid_keep", args.reid_keep), ("--reid_out", args.reid_out)):
+            if value is not None:
+                raise ValueError("%s=%s is a setting of the re-identification: it needs --track_reid" % (flag, value))
+        return None, None
+    if not args.track:
+        raise ValueError("--track_reid gives the tracker's ids back: it needs --track")
+    for flag, value in (("--track_lookback", args.track_lookback), ("--track_backtrack", args.track_backtrack)):
+        if value is not None:
+            raise ValueError("--track_reid together with %s is not supported: the window of a delayed pass holds the tracker's own ids" % flag)
+    try:
+        return ops.track_reid_option(args.track_reid, args.reid_keep), args.reid_out
+    except ValueError as e:
+        raise ValueError("--track_reid / --reid_keep: %s" % e) from None
+
+
 def _zone_state(training_manager, eng):
     """The zone state of ``eng``, or of the eager path with None."""
     return eng.zone_state() if eng is not None else _eager_states(training_manager.class_mapping).zone_state()
@@ -1059,7 +1150,8 @@ def _print_drawn(dets, width, height):
 
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                        track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None):
+                        track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, track_reid=None,
+                        reid_out=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
@@ -1079,7 +1171,16 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     §8 "Zone rule"; ``reset_zones`` starts over, ``reset_tracks`` ends the ids and keeps the totals): the zones are drawn unless ``draw``
     is False, and ``zones_out``, a text file, receives the frame's rows ``frame,zone,kind,id,cls,dwell``.
     ``remove`` = (classes, S, T, M): the frame teaches the background plate of the calls before this one (``reset_plate`` starts an empty
-    one), and the boxes of those classes are painted out with it (DESIGN §8 "Plate rule")."""
+    one), and the boxes of those classes are painted out with it (DESIGN §8 "Plate rule").
+    ``track_reid`` = (pct, keep) (with ``track``): the frame continues the appearance memory of the calls before it (DESIGN §8
+    "Re-identify rule"; ``reset_tracks`` empties it): a track that returns carries its old id everywhere, a line ``re-identified:
+    <frame_no> id <pid>`` is printed in front of the frame's lines, and ``reid_out``, a text file, receives the frame's rows
+    ``frame,id,tracker_id,cls,distance,gap``."""
+    track_reid = _track_reid(track_reid, track)
+    if reid_out is not None and track_reid is None:
+        raise ValueError("reid_out is where the re-identifications are written: it needs track_reid=(pct, keep)")
+    if track_reid is not None and track_lookback is not None:
+        raise ValueError("track_reid=%r together with track_lookback= is not supported" % (track_reid,))
     count = _count(count, track)
     if counts_out is not None and count is None:
         raise ValueError("counts_out is where the crossings are written: it needs count=(lines, classes, width)")
@@ -1111,6 +1212,8 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     remove = _remove(remove)
     if remove is not None:
         motion["remove"] = remove
+    if track_reid is not None:
+        motion["track_reid"] = track_reid
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1)
     info = {}
@@ -1123,6 +1226,7 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         info = more[0] if more else info                          # (a ``track_scene_cut`` pass: the frame's marks behind its payload)
         if info.get("scene_cut"):
             print("scene cut: {}".format(frame_no))
+        _print_reid(frame_no, info.get("reid", ()))
         print("num rois: {}".format(num_rois))
         frame[...] = out
     else:
@@ -1130,8 +1234,11 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, info=info, heatmap=heatmap, **motion)
         if info.get("scene_cut"):
             print("scene cut: {}".format(frame_no))
+        _print_reid(frame_no, info.get("reid", ()))
     if track is not None:
         _write_tracks(tracks_out, frame_no, dets, training_manager.class_mapping)
+    if track_reid is not None:
+        _write_reid(reid_out, frame_no, info["reid"], training_manager.class_mapping)
     if count is not None:
         _write_counts(counts_out, frame_no, info["crossings"], training_manager.class_mapping)
     if zone is not None:
@@ -1537,7 +1644,7 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
               track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None,
-              plate_out=None):
+              plate_out=None, track_reid=None, reid_out=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
@@ -1556,7 +1663,13 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     zone = _zone(zone, track)
     if zones_out is not None and zone is None:
         raise ValueError("zones_out=%r is where the zone events are written: it needs zone=(zones, classes, width, anchor)" % (zones_out,))
-    counts_log = zones_log = None
+    track_reid = _track_reid(track_reid, track)
+    if reid_out is not None and track_reid is None:
+        raise ValueError("reid_out=%r is where the re-identifications are written: it needs track_reid=(pct, keep)" % (reid_out,))
+    if track_reid is not None and (track_lookback is not None or track_backtrack is not None):
+        raise ValueError("track_reid=%r together with track_lookback= / track_backtrack= is not supported: the window of a delayed pass "
+                         "holds the tracker's own ids" % (track_reid,))
+    counts_log = zones_log = reid_log = None
     sink = make_sink()
     try:
         dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
@@ -1586,6 +1699,10 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             reset_zones(training_manager, detector, 1 if eng is None else eng.in_flight)
             zones_log = ZonesLog(zones_out, _names_by_index(training_manager.class_mapping))
             motion["zones_out"] = zones_log
+        if track_reid is not None:                        # (an empty memory for the list: reset_tracks above emptied it)
+            motion["track_reid"] = tracking["track_reid"] = track_reid
+            reid_log = ReidLog(reid_out, _names_by_index(training_manager.class_mapping))
+            motion["reid_out"] = reid_log
         if eng is None:
             _run_eager(training_manager, detector, frames, sink, resize_min, resize_max, redact=redact, draw=draw, track=track,
                        tracks_out=tracks_out, **motion)
@@ -1608,6 +1725,9 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
                     counts_log.add(pos + 1, marks[0]["crossings"])
                 if zone is not None:
                     zones_log.add(pos + 1, marks[0]["zones"]["events"])
+                if track_reid is not None:
+                    reid_log.add(pos + 1, marks[0]["reid"])
+                    _print_reid(label, marks[0]["reid"])
                 print("processing {}".format(label))
                 print("num rois: {}".format(num_rois))
                 if track is not None:
@@ -1624,6 +1744,9 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
         if zone is not None:                              # (host only: the state read back)
             zones_log.close()
             print_zones(len(zone[0]), ops.zone_totals(_zone_state(training_manager, eng)))
+        if track_reid is not None:
+            reid_log.close()
+            print("re-identified: {}".format(reid_log.total))
         if heatmap_out is not None:                       # (host only: the states read back, their t values as grey PNG files)
             write_heatmaps(heatmap_out, _heat_states(training_manager, eng))
         if remove is not None:                            # (host only: the states read back; the plate as an RGB PNG, unknown pixels black)
@@ -1636,6 +1759,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             counts_log.close()
         if zones_log is not None:
             zones_log.close()
+        if reid_log is not None:
+            reid_log.close()
         sink.close()
 
 
@@ -1643,13 +1768,13 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
                     track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
-                    counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None):
+                    counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None, reid_out=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out`` / ``remove`` / ``plate_out``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out`` / ``remove`` / ``plate_out`` / ``track_reid`` / ``reid_out``: as ``annotate_images``."""
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
     if isinstance(writer_or_out_dir, y4m.Y4mWriter):
         make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma)
@@ -1660,14 +1785,15 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
               detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
               heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out, remove=remove,
-              plate_out=plate_out)
+              plate_out=plate_out, track_reid=track_reid, reid_out=reid_out)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
-                    heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None):
+                    heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None,
+                    reid_out=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1735,7 +1861,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
               track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out,
-              remove=remove, plate_out=plate_out)
+              remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out)
 
 
 def build_parser():
@@ -1834,6 +1960,16 @@ def build_parser():
                         "for) starts a new scene -- no id is carried into it and no held box of the old scene is redacted in it; a line "
                         "'scene cut: <path>' is printed in front of that frame's lines; fades and dissolves are not detected (needs --track "
                         "--track_motion; with or without --detect_every; not with --track_lookback or --track_backtrack)")
+    p.add_argument("--track_reid", dest="track_reid", type=int, nargs="?", const=ops.TRACK_REID_PCT[2], default=None, metavar="PCT",
+                   help="give an object that returns after more than --track_hold frames its old id back: a new track whose colour signature "
+                        "lies within PCT percent of the largest distance there is (1..100; bare: 25, a provisional default that no real "
+                        "footage has been measured for) of that of an id the tracker gave up carries that id in labels, files, trails, "
+                        "counts and zones; a line 're-identified: <path> id <id>' is printed in front of that frame's lines and "
+                        "'re-identified: N' at the end (needs --track; not with --track_lookback or --track_backtrack)")
+    p.add_argument("--reid_keep", dest="reid_keep", type=int, default=None, metavar="N",
+                   help="the frames an id that is gone is remembered, 1..4095 (default 250, provisional; needs --track_reid)")
+    p.add_argument("--reid_out", dest="reid_out", default=None, metavar="PATH",
+                   help="write a CSV row frame,id,tracker_id,cls,distance,gap per re-identification (needs --track_reid)")
     p.add_argument("--track_trails", dest="track_trails", type=int, nargs="?", const=ops.TRACK_TRAILS[0][2], default=None, metavar="N",
                    help="draw the path of every track: the last N centres of its box (2..64; bare: 16) as a line in the colour of its id, "
                         "over the redaction and under the boxes; a trail ends where its id ends (needs --track; with every tracking option; "
@@ -1985,6 +2121,11 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
         tracking["count"] = count
     if counts_out is not None:
         tracking["counts_out"] = counts_out
+    track_reid, reid_out = track_reid_from_args(args)
+    if track_reid is not None:
+        tracking["track_reid"] = track_reid
+    if reid_out is not None:
+        tracking["reid_out"] = reid_out
     zone, zones_out = zone_from_args(args, class_mapping)
     if zone is not None:
         tracking["zone"] = zone

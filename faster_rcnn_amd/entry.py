@@ -318,11 +318,12 @@ class PassSpec:
     count: object = None
     zone: object = None                                  # (zones, classes, W, anchor), ops.zone_option's form: frame_edit.EditChain reads it
     remove: object = None                                # (classes, S, T, M), ops.plate_option's form
+    track_reid: object = None                            # (pct, keep), ops.track_reid_option's form
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
                 track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                track_trails=None, heat=None, count=None, zone=None, remove=None):
+                track_trails=None, heat=None, count=None, zone=None, remove=None, track_reid=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -397,6 +398,17 @@ class PassSpec:
                 raise FrcnnError("submit_batch: remove= needs the device-side preprocess: a foreign preprocess_func uploads float pixels, "
                                  "and the plate is learned from the uint8 source frame")
             remove = engine.remove_option(remove)
+        if track_reid is not None:
+            if track is None:
+                raise FrcnnError("submit_batch: track_reid= gives the tracker's ids back: pass track=(thr, hold, grow) too")
+            for name, value in (("track_lookback", track_lookback), ("track_backtrack", track_backtrack)):
+                if value is not None:
+                    raise FrcnnError("submit_batch: track_reid= together with %s= is not supported: the window of a delayed pass holds "
+                                     "the tracked buffers of earlier passes, whose ids are the tracker's" % name)
+            if not engine.device_preprocess:
+                raise FrcnnError("submit_batch: track_reid= needs the device-side preprocess: a foreign preprocess_func uploads float "
+                                 "pixels, and the signatures are read from the uint8 source frame")
+            track_reid = engine.track_reid_option(track_reid)
         if redact is not None:
             redact = engine.redact_option(redact)
         jpeg_mode, y4m_mode = JPEG_MODE, Y4M_MODE
@@ -431,7 +443,8 @@ class PassSpec:
             raise FrcnnError("submit_batch: encode=\"%s\" encodes the ANNOTATED frame: pass annotate=True" % encode)
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
-                   track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove)
+                   track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove,
+                   track_reid=track_reid)
 
     @property
     def delayed(self):
@@ -475,6 +488,8 @@ class PassSpec:
             key = key + ("zone",) + self.zone
         if self.remove is not None:
             key = key + ("remove",) + self.remove
+        if self.track_reid is not None:
+            key = key + ("track_reid",) + self.track_reid
         return key
 
 
@@ -492,7 +507,7 @@ class _Slot:
                  "track", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
                  "track_lookback", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
                  "track_scene_cut", "cuts_pin", "_cuts_raw", "track_trails", "heat", "count", "count_pin", "_count_raw", "zone", "zone_pin", "_zone_raw",
-                 "remove")
+                 "remove", "track_reid", "reid_pin", "_reid_raw")
 
     def __init__(self):
         for name in self.__slots__:
@@ -792,6 +807,31 @@ class DetectionEntry:
             raise FrcnnError("submit_batch: remove=%r: %s" % (remove, e)) from None
         return classes, settle, tol, margin
 
+    # ------------------------------------------------------------------ re-identification
+    def reid_state(self):
+        """The engine's re-identify state (device int32, ops.track_reid_state), made on first use, of twice the tracker's slots (256 at
+        most): one, shared by every pass submitted with ``track_reid=``.  ``reid_reset()`` empties it, and so does ``track_reset()``
+        (the tracker's ids start over).  ``ops.track_reid_totals`` reads it."""
+        return self.edit_states.reid_state()
+
+    def reid_reset(self):
+        """Forget every look: the state is zeroed on the ordered stream, behind the passes submitted so far.  An object that returns
+        from now on is a new id; the tracker's own ids go on."""
+        with torch.cuda.stream(self.track_stream):
+            self.edit_states.reset_reid()
+
+    def track_reid_option(self, track_reid):
+        """``submit_batch``'s ``track_reid`` checked and normalised -> (pct, keep): None for either replaced by the PROVISIONAL defaults
+        25 and 250, which nobody has measured on real footage.  FrcnnError, with the reason, for anything else."""
+        try:
+            pct, keep = track_reid
+        except (TypeError, ValueError):
+            raise FrcnnError("submit_batch: track_reid=%r: (pct, keep)" % (track_reid,)) from None
+        try:
+            return ops.track_reid_option(pct, keep)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: track_reid=%r: %s" % (track_reid, e)) from None
+
     # ------------------------------------------------------------------ zones
     def zone_state(self):
         """The engine's zone state (device int32, ops.zone_state), made on first use, of ``track_trails_capacity()`` entries: one,
@@ -1088,7 +1128,7 @@ class DetectionEntry:
             s.track_lookback, s.track_backtrack = spec.track_lookback or spec.track_backtrack, spec.track_backtrack      # (both: the delayed path is one)
             s.every, s.frames = spec.detect_every, B * (spec.detect_every or 1)
             s.track_scene_cut, s.track_trails, s.heat, s.count = spec.track_scene_cut, spec.track_trails, spec.heat, spec.count
-            s.zone, s.remove = spec.zone, spec.remove
+            s.zone, s.remove, s.track_reid = spec.zone, spec.remove, spec.track_reid
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -1130,7 +1170,7 @@ class DetectionEntry:
                 s._png_raw = self._pinned.take(shape[0] * shape[1], zero=True)
                 s.png_pin = s._png_raw[:shape[0] * shape[1]].view(shape)
             if s.track:
-                track_out = s.chain.track_out
+                track_out = s.chain.host_tracked
                 s._track_raw = self._pinned.take(4 * track_out.numel())
                 s.track_pin = s._track_raw.view(torch.int32)[:track_out.numel()].view(tuple(track_out.shape))
             if s.track_scene_cut:
@@ -1144,6 +1184,10 @@ class DetectionEntry:
                 zone_lists = s.chain.zone_lists
                 s._zone_raw = self._pinned.take(4 * zone_lists.numel())
                 s.zone_pin = s._zone_raw.view(torch.int32)[:zone_lists.numel()].view(tuple(zone_lists.shape))
+            if s.track_reid:
+                reid_lists = s.chain.reid_lists
+                s._reid_raw = self._pinned.take(4 * reid_lists.numel())
+                s.reid_pin = s._reid_raw.view(torch.int32)[:reid_lists.numel()].view(tuple(reid_lists.shape))
             if s.track_lookback:                                    # [the B emitted buffers | the count word]
                 words = s.chain.lb_out[1].numel() + 4
                 s._lb_raw = self._pinned.take(4 * words)
@@ -1332,7 +1376,7 @@ class DetectionEntry:
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
                      track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
-                     heat=None, count=None, zone=None, remove=None):
+                     heat=None, count=None, zone=None, remove=None, track_reid=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1454,11 +1498,21 @@ class DetectionEntry:
         and is never detected becomes background after S frames.  The results are what they are without it: only the frames' bytes
         change.  Refused by name without ``annotate``, on an engine with a foreign preprocess and for options out of range.  Without it
         every key and byte is what it was.
+        ``track_reid`` = (pct, keep) (tracking passes, every form but the delayed ones; ("track_reid", pct, keep) appended last, behind
+        ("remove", ...); pct 1..100, keep 1..4095 frames, None for the PROVISIONAL defaults 25 and 250, which nobody has measured on
+        real footage): the re-identify rule (DESIGN §8 "Re-identify rule"): one ops.track_reid_update behind the tracker call gives a
+        track whose colour signature lies within pct percent of that of an id the tracker gave up at most keep frames ago that id
+        back, in the engine's re-identify state (``reid_state``; ``reid_reset()`` and ``track_reset()`` empty it; a
+        ``track_scene_cut`` frame's cut word too).  Everything behind it -- trails, counts (whose entries then live max(expire, keep)
+        frames), zones, labels, the "track_id" of the returned dets -- sees those ids.  Every result of such a pass carries in its ONE
+        trailing dict "reid": [(pid, tid, cls, distance, gap)].  Refused by name without ``track``, with ``track_lookback`` /
+        ``track_backtrack``, on an engine with a foreign preprocess and for options out of range.  Without it every key and byte is
+        what it was.
         The order of all these steps in a pass is stated once, in ``frame_edit.EditChain``'s docstring."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-                                track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove)
+                                track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove, track_reid=track_reid)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1545,13 +1599,15 @@ class DetectionEntry:
             for i in range(len(images)):
                 s.out_pin[i].copy_(s.out_packed[i], non_blocking=True)
             for i in range(len(pixels) if s.track else 0):
-                s.track_pin[i].copy_(s.chain.track_out[i], non_blocking=True)
+                s.track_pin[i].copy_(s.chain.host_tracked[i], non_blocking=True)      # (with track_reid: the buffers with pids)
             if s.track_scene_cut:
                 s.cuts_pin.copy_(s.chain.cuts, non_blocking=True)
             if s.count:                                             # the count lists come back with the dets
                 s.count_pin.copy_(s.chain.count_lists, non_blocking=True)
             if s.zone:
                 s.zone_pin.copy_(s.chain.zone_lists, non_blocking=True)
+            if s.track_reid:
+                s.reid_pin.copy_(s.chain.reid_lists, non_blocking=True)
             for i in range(emitted["frames"] if emitted else 0 if s.track_lookback else len(pixels)):
                 if s.encode == JPEG_ENCODE:
                     s.png_pin[i].copy_(s.png_dev[i][:s.first_copy], non_blocking=True)
@@ -1741,9 +1797,10 @@ class DetectionEntry:
     def _marks(s, i):
         """What frame i of a collected ``track_scene_cut``, ``count`` or ``zone`` pass returns behind its payload: ONE dict -- "scene_cut":
         True for a frame that is a cut, "crossings": [(line, dir, id, cls)] in a counting pass (the events of the frame's count list, dir 1
-        for +), "zones": {"occupancy": [per zone], "events": [(zone, kind, id, cls, dwell)]} in a zone pass (the frame's zone list) --;
+        for +), "zones": {"occupancy": [per zone], "events": [(zone, kind, id, cls, dwell)]} in a zone pass (the frame's zone list), "reid":
+        [(pid, tid, cls, distance, gap)] in a ``track_reid`` pass (the frame's reid list) --;
         () for every other pass."""
-        if not s.track_scene_cut and not s.count and not s.zone:
+        if not s.track_scene_cut and not s.count and not s.zone and not s.track_reid:
             return ()
         marks = {"scene_cut": True} if s.track_scene_cut and int(s.cuts_pin[i]) else {}
         if s.count:
@@ -1751,6 +1808,8 @@ class DetectionEntry:
         if s.zone:                                       # "zones": the frame's occupancy per zone and its events (zone, kind, id, cls, dwell)
             zlist = s.zone_pin[i].numpy()
             marks["zones"] = {"occupancy": ops.zone_occupancy(zlist, len(s.zone[0])), "events": ops.zone_events(zlist)}
+        if s.track_reid:                                 # "reid": the frame's re-identifications (pid, tid, cls, distance, gap)
+            marks["reid"] = ops.track_reid_events(s.reid_pin[i].numpy())
         return (marks,)
 
     def _payload(self, s, i):

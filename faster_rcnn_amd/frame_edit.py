@@ -16,12 +16,13 @@ def _made(table, key, make):
 
 class EditStates:
     """The device state of the editing rules for the classes ``class_names`` (index = class index), each piece made on first use: a
-    tracker of ``track_capacity`` slots, trail, count and zone states of ``trail_capacity`` entries.  The pointers of all of them are in the
-    captured graphs that use them: nothing here is ever replaced, only zeroed by the three resets (on the current stream)."""
+    tracker of ``track_capacity`` slots, trail, count and zone states of ``trail_capacity`` entries, a re-identify state of twice the
+    tracker's slots (256 at most).  The pointers of all of them are in the captured graphs that use them: nothing here is ever replaced,
+    only zeroed by the resets (on the current stream)."""
 
     def __init__(self, class_names, track_capacity, trail_capacity):
         self.class_names, self.track_capacity, self.trail_capacity = list(class_names), int(track_capacity), int(trail_capacity)
-        self._tracker = self._count = self._zone = self._one = None
+        self._tracker = self._count = self._zone = self._one = self._reid = None
         self.motion = {}                                 # (h, w) of the source frames -> ops.track_motion_state
         self.lookback = {}                               # (h, w, F) -> (ops.track_lookback_state: the frames tracked but not yet emitted, its back)
         self.trails = {}                                 # length N -> ops.track_trails_state
@@ -75,6 +76,13 @@ class EditStates:
             self._zone = ops.zone_state(self.trail_capacity)
         return self._zone
 
+    def reid_state(self):
+        """The ONE re-identify state (device int32, ops.track_reid_state; ``ops.track_reid_totals`` reads it): 2 * ``track_capacity``
+        entries, 256 at most -- the tracks there are and as many that are gone."""
+        if self._reid is None:
+            self._reid = ops.track_reid_state(min(2 * self.track_capacity, ops.TRACK_REID_MAX))
+        return self._reid
+
     def heat_state(self, h, w):
         """The heat state for source frames of (h, w): one per size, whatever the other options of the calls that heat it."""
         return _made(self.heat, (int(h), int(w)), lambda: ops.heat_state(h, w))
@@ -121,6 +129,12 @@ class EditStates:
             ops.count_reset(self._count, keep_totals=True)
         if self._zone is not None:                       # ... and nobody is inside: no event is made, an open stay is not counted
             ops.zone_reset(self._zone, keep_totals=True)
+        self.reset_reid()                                # ... and no look is remembered: the tracker's ids start over
+
+    def reset_reid(self):
+        """Forget every look: an object that returns is a new id.  (The tracker's own ids go on.)"""
+        if self._reid is not None:
+            ops.track_reid_reset(self._reid)
 
     def reset_heat(self):
         """A cold map for every size."""
@@ -150,12 +164,16 @@ class EditChain:
     ``update``, once per pass, behind the post-process and in front of every edit (the frames are still as they were uploaded):
       1. ONE tracker call over the pass's frames -- ops.track_update_cut with ``track_scene_cut``, else ops.track_update_interval with
          ``detect_every``, else ops.track_update_motion with ``track_motion``, else ops.track_update -> ``track_out``;
+     1b. with ``track_reid``: ops.track_reid_update on ``track_out`` and the pass's frames (with ``track_scene_cut`` the frames' cut words
+         empty its table) -> ``reid_out``, ``reid_lists``: copies of the tracked buffers in which a track that returns has its old id.
+         ``tracked`` is ``reid_out`` from here on: every step below, and the host's copy, sees those ids and no other;
       2. a delayed pass: ops.track_backtrack, or ops.track_lookback: the frames and their tracked buffers join the window, and the
          frames of the pass BEFORE come out in ``lb_out`` = (frames, widened tracked buffers, their count).  Everything behind this
          point reads the EMITTED buffers and the emitted count as its ``n_frames`` word, gated by the pass's own count (a warm-up run, 0
          frames, emits what the window holds once more, and those are no new frames): ``tracked``, ``n_frames``, ``gate``;
       3. ops.track_trails_update -> ``trail_lists``;
-      4. ops.count_update -> ``count_lists``;
+      4. ops.count_update -> ``count_lists``; with ``track_reid`` its expire is min(max(expire, keep), 4095), so that "once per id, line
+         and direction" outlives the gap an id returns over (trails and zones keep theirs: a zone entry that lingers still occupies);
       5. ops.zone_update -> ``zone_lists``: the same ``tracked`` / ``n_frames`` / ``gate``, so a delayed pass counts in emitted order.
     ``edit``, once per frame, on ``rows(i)`` -- the frame's emitted buffer, else its tracked buffer, else its packed detections:
      5b. ops.plate_update, on the frame NO edit has touched: every row blocks, the held and back-filled ones too, whatever its class;
@@ -185,8 +203,15 @@ class EditChain:
         self.lookback = spec.track_lookback or spec.track_backtrack             # (both: the delayed path is one)
         self.tables = states.annotate_tables(spec.draw)
         self.track_out = self.lb_out = self.lb_frames = self.cuts = self.trail_lists = self.count_lists = self.zone_lists = None
+        self.reid_ws = self.reid_out = self.reid_lists = None
         if spec.zone and not spec.track:
             raise FrcnnError("zone= tests the tracker's ids against the zones: the chain needs track=(thr, hold, grow) too")
+        if spec.track_reid:
+            if not spec.track:
+                raise FrcnnError("track_reid= gives the tracker's ids back: the chain needs track=(thr, hold, grow) too")
+            if self.lookback:
+                raise FrcnnError("track_reid= does not go with track_lookback= / track_backtrack=: their windows hold the tracked buffers of "
+                                 "earlier passes, whose ids are the tracker's")
         if spec.redact:
             # one workspace serves the frames of a pass, which are redacted one after another
             classes, mode, size, _ = spec.redact
@@ -196,7 +221,10 @@ class EditChain:
             self.state = states.tracker()
             self.track_table = states.track_table(spec.redact[0] if spec.redact else None, spec.remove[0] if spec.remove else None)
             self.motion = states.motion_state(h, w) if spec.track_motion else None
-            self.expire = self.trails_expire(spec.track, spec.detect_every)
+            self.expire = self.count_expire = self.trails_expire(spec.track, spec.detect_every)
+            if spec.track_reid:
+                self.reid = states.reid_state()
+                self.count_expire = min(max(self.expire, spec.track_reid[1]), ops.TRACK_TRAILS[2])
             if spec.track_scene_cut:
                 self.cut_ws, self.cuts = ops.track_cut_workspace(F), torch.zeros(F, dtype=torch.int32, device="cuda")
             if spec.track_trails:
@@ -223,7 +251,7 @@ class EditChain:
             self.lb_frames = torch.zeros((F, h, w, 3), dtype=torch.uint8, device="cuda")
 
     def update(self, frames_u8, frame_stride, packed, n_frames):
-        """Steps 1-5.  ``frames_u8`` holds source frame f at byte ``f * frame_stride``; ``packed``: the post-process's packed buffers of
+        """Steps 1-5 (1b too).  ``frames_u8`` holds source frame f at byte ``f * frame_stride``; ``packed``: the post-process's packed buffers of
         the key frames (one buffer for one); ``n_frames``: the device word that says how many of the F frames are real."""
         sp, (h, w), K = self.spec, self.hw, self.K
         self.packed = packed
@@ -245,6 +273,12 @@ class EditChain:
         else:
             ops.track_update(self.state, *common, out=self.track_out)
         self.tracked = self.track_out
+        if sp.track_reid:
+            if self.reid_ws is None:
+                self.reid_ws = ops.track_reid_workspace(self.F, ops.track_rows(packed) + cap)
+            self.reid_out, self.reid_lists = ops.track_reid_update(self.reid, frames_u8, frame_stride, self.track_out, n_frames, self.track_table,
+                                                                   h, w, *sp.track_reid, rgb=self.rgb, cuts=self.cuts, workspace=self.reid_ws)
+            self.tracked = self.reid_out
         if self.lookback:
             window, back = self.states.lookback_window(h, w, self.F, ops.track_rows(packed))      # (made by the first call: the rows are known now)
             if self.lb_out is None:
@@ -262,11 +296,16 @@ class EditChain:
             ops.track_trails_update(self.trails, self.tracked, self.n_frames, sp.track_trails[0], self.expire, h, w, lists=self.trail_lists,
                                     gate=self.gate)
         if sp.count:
-            ops.count_update(self.count, self.tracked, self.n_frames, sp.count[0], self.count_table, self.expire, h, w,
+            ops.count_update(self.count, self.tracked, self.n_frames, sp.count[0], self.count_table, self.count_expire, h, w,
                              lists=self.count_lists, gate=self.gate)
         if sp.zone:
             ops.zone_update(self.zone, self.tracked, self.n_frames, sp.zone[0], self.zone_table, self.expire, h, w, anchor=sp.zone[3],
                             lists=self.zone_lists, gate=self.gate)
+
+    @property
+    def host_tracked(self):
+        """The tracked buffers of the pass itself that the host copies: ``reid_out`` with ``track_reid``, else ``track_out``."""
+        return self.track_out if self.reid_out is None else self.reid_out
 
     def rows(self, i):
         """What the edits of frame i read."""

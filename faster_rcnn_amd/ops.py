@@ -2164,6 +2164,116 @@ def plate_fill_u8(frame, state, det_packed, table, margin=None, keep_unknown=Fal
     return frame
 
 
+# ----------------------------------------------------------------------------- re-identification
+# (smallest, largest, the default) of pct and keep.  The defaults are PROVISIONAL: nobody has measured them on real footage.
+TRACK_REID_PCT, TRACK_REID_KEEP, TRACK_REID_MAX = _lib.TRACK_REID_PCT, _lib.TRACK_REID_KEEP, _lib.TRACK_REID_MAX
+TRACK_REID_ENTRY_WORDS, TRACK_REID_SIG_WORDS = _lib.TRACK_REID_ENTRY_WORDS, _lib.TRACK_REID_SIG_WORDS
+TRACK_REID_LIST_WORDS, TRACK_REID_MAX_EVENTS = _lib.TRACK_REID_LIST_WORDS, _lib.TRACK_REID_MAX_EVENTS
+
+
+def track_reid_option(pct=None, keep=None):
+    """(host only) The re-identify option checked -> (pct, keep): pct the share of the largest distance two signatures can have up to
+    which a new track takes an old id, 1..100 (None: 25); keep the frames an id that is gone is remembered, 1..4095 (None: 250).  Both
+    defaults are PROVISIONAL: nobody has measured them on real footage.  ValueError with the reason."""
+    out = []
+    for name, v, (lo, hi, default) in (("pct", pct, TRACK_REID_PCT), ("keep", keep, TRACK_REID_KEEP)):
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError("track reid %s=%r: an integer in %d..%d" % (name, v, lo, hi))
+        out.append(int(v))
+    return tuple(out)
+
+
+def track_reid_state_words(capacity):
+    """(host only) 4-byte words of a re-identify state of ``capacity`` entries (frcnn_track_reid_state_bytes / 4): 4 + 197 capacity."""
+    n = int(_lib.load().frcnn_track_reid_state_bytes(int(capacity)))
+    if n == 0:
+        raise _lib.FrcnnError("track reid state: capacity=%r not in [1, %d]" % (capacity, TRACK_REID_MAX))
+    return n // 4
+
+
+def track_reid_state(capacity):
+    """An empty re-identify state of ``capacity`` entries (1..256): a zeroed int32 device tensor, [n_entries, frames, dropped,
+    reidentified | per entry: pid, tid, cls, last_seen, has_sig, sig[192]] (include/ext/frcnn_hip_track_reid.h).  Zeroing it
+    (``track_reid_reset``) empties it."""
+    _require_gpu()
+    return torch.zeros(track_reid_state_words(capacity), dtype=torch.int32, device="cuda")
+
+
+def track_reid_reset(state):
+    """Empty the state (on the current stream): no entries, no frames, the sums 0."""
+    state.zero_()
+    return state
+
+
+def track_reid_workspace(frames, rows):
+    """What a ``track_reid_update`` call over ``frames`` tracked buffers of ``rows`` rows writes besides the state -> (``workspace``: int32
+    (frames, rows, 193), a has-signature word and the signature of every row; ``out``: int32 (frames, 4 + 8 rows), the tracked buffers
+    with pids; ``lists``: int32 (frames, TRACK_REID_LIST_WORDS)).  Nothing is carried in them between calls; a captured call passes them."""
+    _require_gpu()
+    n = int(_lib.load().frcnn_track_reid_workspace_bytes(int(frames), int(rows)))
+    if n == 0:
+        raise _lib.FrcnnError("track_reid_workspace: frames=%r (1..%d) or rows=%r (1..%d) out of range"
+                              % (frames, _lib.TRACK_MAX_FRAMES, rows, _lib.REDACT_MAX_ROWS))
+    frames, rows = int(frames), int(rows)
+    return (torch.zeros((frames, rows, 1 + TRACK_REID_SIG_WORDS), dtype=torch.int32, device="cuda"),
+            torch.zeros((frames, 4 + 8 * rows), dtype=torch.int32, device="cuda"),
+            torch.zeros((frames, TRACK_REID_LIST_WORDS), dtype=torch.int32, device="cuda"))
+
+
+def track_reid_update(state, frames_u8, frame_stride, tracked, n_frames, table, h, w, pct=None, keep=None, rgb=False, cuts=None,
+                      capacity=None, workspace=None):
+    """The re-identify rule (DESIGN §8 "Re-identify rule", frcnn_track_reid_update) over the frames of ``tracked`` IN ORDER: ``tracked``
+    is a (frames, 4 + 8 rows) int32 tensor of PLAIN tracked buffers -- a ``track_update*`` call's ``out`` --, source frame f, as it was
+    uploaded, lies at byte ``f * frame_stride`` of ``frames_u8`` ((h, w, 3) uint8 each; ``rgb``: the bytes are R, G, B, False: B, G, R),
+    ``n_frames`` is the device word that says how many of them are real, ``table`` the tracker's class table.  Every live row gets a
+    colour signature; a new tracker id whose signature lies within ``pct`` percent of the largest distance of that of an id the tracker
+    gave up at most ``keep`` frames ago takes that id's place in ``state`` (``track_reid_state``; ``capacity``: its entries, read from its
+    size when None).  ``cuts``: None, or the int32 device tensor of frames words a ``track_update_cut`` call wrote: a set word empties
+    the table in front of its frame.  ``workspace``: ``track_reid_workspace(frames, rows)`` (allocated here when None; a captured call
+    passes it) -> (out, lists): the tracked buffers with the rewritten ids, and frame f's re-identifications in ``lists[f]``
+    (``track_reid_events``).  Two launches; everything is guarded on the device, so the call can be captured in a graph."""
+    _require_gpu()
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.dim() == 2 and tracked.is_contiguous()
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    frames, words = int(tracked.shape[0]), int(tracked.shape[1])
+    assert (words - 4) % 8 == 0
+    rows = (words - 4) // 8
+    assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
+    assert int(frames_u8.numel()) >= (frames - 1) * int(frame_stride) + 3 * int(h) * int(w) and int(frame_stride) >= 0
+    assert cuts is None or (cuts.is_cuda and cuts.dtype == torch.int32 and cuts.is_contiguous() and cuts.numel() == frames)
+    if capacity is None:
+        capacity = (int(state.numel()) - 4) // TRACK_REID_ENTRY_WORDS
+    assert int(state.numel()) == track_reid_state_words(capacity)
+    if workspace is None:
+        workspace = track_reid_workspace(frames, rows)
+    ws, out, lists = workspace
+    assert ws.is_cuda and ws.dtype == torch.int32 and ws.is_contiguous() and tuple(ws.shape) == (frames, rows, 1 + TRACK_REID_SIG_WORDS)
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (frames, words)
+    assert lists.is_cuda and lists.dtype == torch.int32 and lists.is_contiguous() and tuple(lists.shape) == (frames, TRACK_REID_LIST_WORDS)
+    _lib.call("frcnn_track_reid_update", _p(state), int(capacity), _p(frames_u8), int(frame_stride), int(h), int(w), int(bool(rgb)),
+              _p(tracked), words, rows, frames, _p(n_frames), _p(cuts), _p(table), int(table.numel()),
+              TRACK_REID_PCT[2] if pct is None else int(pct), TRACK_REID_KEEP[2] if keep is None else int(keep), _p(ws), _p(out), words,
+              _p(lists), _stream())
+    return out, lists
+
+
+def track_reid_events(rlist):
+    """(host only) The events of one reid list's HOST copy -> [(pid, tid, cls, distance, gap)], in row order: the row the tracker calls
+    tid is the object it called pid until ``gap`` frames ago; distance 0..8192."""
+    c = np.asarray(rlist)
+    return [tuple(int(v) for v in c[4 + 5 * k:9 + 5 * k]) for k in range(min(max(int(c[0]), 0), TRACK_REID_MAX_EVENTS))]
+
+
+def track_reid_totals(state):
+    """(host only; reads the state back) The sums of a re-identify state, device tensor or host copy -> {"entries", "frames", "dropped",
+    "reidentified"}."""
+    s = state.cpu().numpy() if isinstance(state, torch.Tensor) else np.asarray(state)
+    return {"entries": int(s[0]), "frames": int(s[1]), "dropped": int(s[2]), "reidentified": int(s[3])}
+
+
 TRACK_LOOKBACK = _lib.TRACK_LOOKBACK            # (smallest, largest, the default) look-back of ``track_lookback``, in frames
 
 

@@ -32,7 +32,7 @@ without and with ``--detect_every 4``.  ``--track_backtrack`` (``run_track_backt
 ``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
 look-back call of one pass alone.  ``--track_scene_cut`` (``run_track_scene_cut``) runs the ``--track --track_motion 8`` leg without and with
 ``--track_scene_cut`` at its default.  ``--track_trails`` (``run_track_trails``) runs the same leg without and with ``--track_trails`` at its
-defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.
+defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
@@ -626,6 +626,50 @@ def run_remove(name, cfg, n_frames, reps, content="noise"):
     return res
 
 
+def run_track_reid(name, cfg, n_frames, reps, content="noise"):
+    """``--track_reid``: what the re-identify stage costs on top of ``--track --track_motion 8``.  One pair of legs in ONE session,
+    alternating inside every repetition: ``run_track_motion``'s ``track_motion`` leg without and with ``track_reid=(25, 250)`` (the
+    tracker, and with it the re-identify state, is reset in front of every run).  Reports frames/s of both, their ratio and the state's
+    sums at the end.  Noise frames are the dear case for the step kernel: tracks are born in every frame, and each birth takes a turn of
+    its one workgroup; what real footage costs is not measured."""
+    import numpy as np
+    from faster_rcnn_amd import entry, ops, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+    reid = ops.track_reid_option()
+
+    def leg(**kw):
+        def run():
+            eng.track_reset()
+            return annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, track=TRACK_LEG, track_motion=MOTION_LEG, **kw)
+        return run
+
+    legs = {"track_motion": leg(), "track_reid": leg(track_reid=reid)}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    import torch
+    torch.cuda.synchronize()
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact": ["all", "blur", 12, 0], "track": list(TRACK_LEG), "track_motion": MOTION_LEG, "track_reid": list(reid),
+           "images_per_pass": eng.batch, "in_flight": eng.in_flight, "reid": ops.track_reid_totals(eng.reid_state())}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["track_reid_over_motion"] = round(statistics.median(times["track_motion"]) / statistics.median(times["track_reid"]), 3)
+    return res
+
+
 def run_count_line(name, cfg, n_frames, reps, content="noise"):
     """``--count_line``: what counting costs on top of ``--track --track_motion 8``.  One pair of legs in ONE session, alternating inside
     every repetition: ``run_track_motion``'s ``track_motion`` leg without and with ``count`` = two lines (a horizontal and a vertical one
@@ -994,6 +1038,9 @@ def main():
                                                               "with two --count_line lines, alternating in one session")
     ap.add_argument("--zone", action="store_true", help="instead of the legs above: the --track --track_motion 8 leg without and with two "
                                                         "--zone rectangles of a quarter of the frame each, alternating in one session")
+    ap.add_argument("--track_reid", action="store_true", help="instead of the legs above: the --track --track_motion 8 leg without and "
+                                                              "with --track_reid at its defaults, alternating in one session (also as "
+                                                              "--track --track_reid)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -1002,6 +1049,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.track_reid:
+            out[name] = run_track_reid(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.heatmap:
             out[name] = run_heatmap(name, PAIRS[name], args.frames, args.reps, args.content)
