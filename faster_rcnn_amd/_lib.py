@@ -176,6 +176,21 @@ POOL_EPILOGUE_SIGNATURES = {
 }
 
 
+ROWMAP_VERSION = 1            # include/ext/frcnn_hip_rowmap.h FRCNN_ROWMAP_VERSION
+ROWMAP_TILE_ROWS = 256        # the row tile of the one launch form that reads a map (frcnn_conv2d_rowmap_available)
+ROWMAP_SIGNATURES = {
+    "frcnn_rowmap_version": (I, []),
+    "frcnn_conv_rowmap_build": (I, [P, I, I, P, c_size_t, P, c_size_t, P, P]),
+    "frcnn_conv2d_rowmap_available": (I, [P, I, I]),
+    "frcnn_conv2d_fwd_h3_rowmap": (I, [P, P, P, P, P, P, P, P, P, ctypes.c_float, ctypes.c_float, P, P]),
+}
+
+
+class RowMap(ctypes.Structure):
+    """frcnn_rowmap (include/ext/frcnn_hip_rowmap.h)."""
+    _fields_ = [("row_map", c_void_p), ("tile_taps", c_void_p), ("rows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class RoiRes(ctypes.Structure):
     """frcnn_roi_res (include/ext/frcnn_hip_roi_res.h)."""
     _fields_ = [("map", c_void_p), ("taps", c_void_p), ("fill", c_void_p), ("map_rows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
@@ -623,6 +638,10 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in ROWMAP_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
     for name, (res, args) in PNG_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -806,6 +825,9 @@ def load():
     if lib.frcnn_pool_epilogue_version() != POOL_EPILOGUE_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_pool_epilogue_version()} of the pooled-epilogue extension, this binding "
                          f"{POOL_EPILOGUE_VERSION} (include/ext/frcnn_hip_pool_epilogue.h): rebuild with `python -m faster_rcnn_amd.build`")
+    if lib.frcnn_rowmap_version() != ROWMAP_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_rowmap_version()} of the row-map extension, this binding "
+                         f"{ROWMAP_VERSION} (include/ext/frcnn_hip_rowmap.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_vgg_canvas_version() != VGG_CANVAS_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_vgg_canvas_version()} of the VGG16 canvas extension, this binding "
                          f"{VGG_CANVAS_VERSION} (include/ext/frcnn_hip_vgg_canvas.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -50,6 +50,10 @@ struct ConvArgs {
     // a row tile starts at row t * pool_groups * pool_rows and holds pool_groups whole groups, y is [M / pool_rows][ldy] -- the 16-waves
     // 256x128 plane-reading form of conv_h3.hip only, as an instantiation of its own (x6_epilogue_vec<.., POOL>).
     int pool_rows = 0, pool_groups = 0;
+    // rows assigned to tiles by a map (include/ext/frcnn_hip_rowmap.h; NULL = off): tile row j of the launch computes output row
+    // row_map[j] (-1: none), row tile t walks the filter taps of tile_taps[t]; tiles_m = map_rows / 256 -- the 16-waves 256x128 plane-reading
+    // ring of conv_h3.hip only, as an instantiation of its own (h3_ring_tile<.., ROWMAP>, x6_epilogue_vec<.., ROWMAP>).
+    const int* row_map = nullptr; const unsigned* tile_taps = nullptr; int map_rows = 0;
 };
 
 // ---- magnitude records.  A record is AMAX_SLOTS floats, one per 128-byte line: a launch has hundreds to thousands of waves and a
@@ -358,12 +362,16 @@ __device__ __forceinline__ f32x4 roi_res_piece(const f32x4 a, const f32x4 b, con
 // the WM wave-rows (they are walked in row order; a wave reads 64 consecutive columns of one row: no bank conflict), and stores
 // acc / pool_rows to y[(tile * pool_groups + j) * ldy + n0 + c] behind the last.  The `if (h) __syncthreads()` of the next wave-row
 // keeps its staging behind these reads.  y_amax receives max |pooled value|.
-template <int TM, int TN, int WM, int WN, bool PLANES = false, bool S16 = false, bool GRES = false, bool POOL = false>
+// ROWMAP (ConvArgs.row_map): tile row j holds output row row_map[m0 + j] instead of m0 + j (-1: none, nothing is read or stored for it); the
+// thread's rows of a wave-row are looked up with that wave-row's other global reads.  Everything per element is the common code.
+template <int TM, int TN, int WM, int WN, bool PLANES = false, bool S16 = false, bool GRES = false, bool POOL = false, bool ROWMAP = false>
 __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const ConvArgs& p, int m0, int n0, int tid, int wm, int wn, int li, int lh, float* smem,
                                                 float y_scale = 1.0f) {
     constexpr int NT = 64 * WM * WN, BN = 32 * TN * WN, HB = 32 * TM, LD = BN + 4, C4 = BN / 4, RPP = NT / C4, PASSES = HB / RPP;
     static_assert(HB % RPP == 0 && NT % C4 == 0 && PASSES >= 1 && PASSES <= 8, "epilogue passes");
     static_assert(!POOL || (!PLANES && !GRES), "the pooled form: f32 output, residual read or none");
+    static_assert(!ROWMAP || (!GRES && !POOL), "mapped rows: the plain and the plane-writing forms");
+    int rmap[ROWMAP ? PASSES : 1];                          // ROWMAP: the output rows of this thread's pieces in the current wave-row
     const bool second = p.n_split && n0 >= p.n_split;       // two layers in one launch: the tile belongs to ONE of them (host guarantees it)
     float* const yb = second ? p.y2 : p.y;
     const int y_ld = second ? p.ldy2 : p.ldy, y_act = second ? p.act2 : p.act, y_n0 = second ? p.n_split : 0;
@@ -414,8 +422,9 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
     auto fetch = [&](int h) {                                // the global reads of wave-row h: in flight while it goes through LDS
 #pragma unroll
         for (int q = 0; q < PASSES; ++q) {
-            const int m = m0 + h * HB + q * RPP + prow;
-            const bool in = m < p.M && n < p.Cout && (!POOL || h * HB + q * RPP + prow < pool_tile_rows);
+            int m = m0 + h * HB + q * RPP + prow;
+            if constexpr (ROWMAP) { m = p.row_map[m]; rmap[q] = m; }      // (m0 + BM <= map_rows: the launch has map_rows / BM row tiles)
+            const bool in = (ROWMAP ? m >= 0 : m < p.M) && n < p.Cout && (!POOL || h * HB + q * RPP + prow < pool_tile_rows);
             if constexpr (GRES) {
                 const i32x4 goff = *reinterpret_cast<const i32x4*>(grec + (h * HB + q * RPP) * 32);
 #pragma unroll
@@ -479,8 +488,8 @@ __device__ __forceinline__ void x6_epilogue_vec(f32x16 (&acc)[TM][TN], const Con
                 *reinterpret_cast<f32x4*>(smem + (q * RPP + prow) * LD + pcol) = v;
                 continue;
             }
-            const int ym = m0 + h * HB + q * RPP + prow, yn = n0 - y_n0 + pcol;
-            const bool in = ym < p.M && yn < y_cols;
+            const int ym = ROWMAP ? rmap[q] : m0 + h * HB + q * RPP + prow, yn = n0 - y_n0 + pcol;
+            const bool in = (ROWMAP ? ym >= 0 : ym < p.M) && yn < y_cols;
             const unsigned yoff = in ? (unsigned)(((size_t)ym * y_ld + yn) * 4) : OOB_OFFSET;
             if (!PLANES || yb) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), yrsrc, yoff, 0, 0);
             if (in) vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));

@@ -434,7 +434,13 @@ k_conv_igemm_h3(const ConvArgs p) {
 // (the head's 3x3: 144 chunks, 748 -> 712 us per four-image launch), the sixteen chunks of 512 -> 2048 run 3-5 % slower on it -- a fixed
 // ~2.7 us per tile that neither the LDS request nor the place of the scale reads explains (scripts/dev/r6_ring_shortk.sh) -- and keep
 // the double buffer.
-template <int TM, int TN, int WM, int WN>
+// ROWMAP (ConvArgs.row_map; include/ext/frcnn_hip_rowmap.h): tile row j computes output row row_map[m0 + j] instead of m0 + j (-1: none -- it
+// stages zeros and stores nothing) and the tile walks the taps of tile_taps[tile_m], one word the host built beside the map, instead of
+// h3_tap_mask's.  A lane looks its rows up where it derives (img, ho, wo) from them, before the loop, and the epilogue where it derives
+// its output rows: the loop itself is the same code.  With [roi][7][7][c] crops sorted by padding class (interior / edge / corner
+// positions of 256 RoIs per group of tiles) a tile walks 9, 6 or 4 taps of a 3x3 filter where every unmapped tile walks 9.  Per output
+// row the kept taps run in their old order and the dropped ones added exact zeros: bit-identical results (h3_tap_mask's argument).
+template <int TM, int TN, int WM, int WN, bool ROWMAP = false>
 __device__ __forceinline__ void h3_ring_tile(const ConvArgs& p, char* lds) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, NW = WM * WN;
     constexpr int GA = 2 * BM / 16, GB = 2 * BN / 16;     // 16-row groups (one wave instruction each) of the two planes of A / of B
@@ -465,9 +471,9 @@ __device__ __forceinline__ void h3_ring_tile(const ConvArgs& p, char* lds) {
 #pragma unroll
     for (int i = 0; i < PA; ++i) {
         const int g = wave + NW * i, pl = g / (BM / 16), r0 = 16 * (g % (BM / 16));
-        const int row = r0 + grow, m = m0 + row, piece = slot ^ h3_swz(row);
+        const int row = r0 + grow, m = ROWMAP ? p.row_map[m0 + row] : m0 + row, piece = slot ^ h3_swz(row);      // (ROWMAP: m0 + BM <= map_rows)
         a_dst[i] = pl * BM * X6_ROWB + r0 * X6_ROWB;
-        if (m < p.M) {
+        if (ROWMAP ? m >= 0 : m < p.M) {
             int wo, ho, img;
             if (p.layout) { img = m % p.n_img; const int pos = m / p.n_img; ho = pos / p.Wo; wo = pos - ho * p.Wo; }
             else { wo = m % p.Wo; const int t = m / p.Wo; ho = t % p.Ho; img = t / p.Ho; }
@@ -489,7 +495,8 @@ __device__ __forceinline__ void h3_ring_tile(const ConvArgs& p, char* lds) {
     }
 
     const int RS = p.R * p.S;
-    const unsigned tap_mask = h3_tap_mask(p, m0, BM);
+    unsigned tap_mask = ROWMAP ? p.tile_taps[tile_m] & (RS >= 32 ? 0xffffffffu : (1u << RS) - 1u) : h3_tap_mask(p, m0, BM);      // (one scalar load per workgroup)
+    if (ROWMAP && tap_mask == 0u) tap_mask = 1u;          // (the host's builder writes no empty word; the walk below needs one tap)
     const int nk = (p.Kpad / (BK * RS)) * __popc(tap_mask);
     unsigned rem = tap_mask;
     int c0 = 0, w_grp = 0;
@@ -565,6 +572,11 @@ __device__ __forceinline__ void h3_ring_tile(const ConvArgs& p, char* lds) {
     h3_gather<TM, TN>(s0, acc0); h3_gather<TM, TN>(s1, acc1);
     h3_combine<TM, TN>(acc0, acc1);
     h3_unscale<TM, TN>(acc0, h3_pow2(-eA), h3_pow2(-eB));
+    if constexpr (ROWMAP) {                               // (16-byte addressable rows: the host admits nothing else)
+        if (p.y_planes) x6_epilogue_vec<TM, TN, WM, WN, true, H3_S16, false, false, true>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds), h3_pow2(eY));
+        else x6_epilogue_vec<TM, TN, WM, WN, false, H3_S16, false, false, true>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds));
+        return;
+    }
     if (p.y_planes) x6_epilogue_vec<TM, TN, WM, WN, true, H3_S16>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds), h3_pow2(eY));
     else if (p.vec_epi) x6_epilogue_vec<TM, TN, WM, WN, false, H3_S16>(acc0, p, m0, n0, tid, wm, wn, li, lh, reinterpret_cast<float*>(lds));
     else epilogue<TM, TN, H3_S16>(acc0, p, m0, n0, wm, wn, li, lh);
@@ -583,7 +595,8 @@ __device__ __forceinline__ void h3_ring_tile(const ConvArgs& p, char* lds) {
 // POOL: the output averaged over groups of pool_rows rows in the epilogue (ConvArgs.pool_rows; x6_epilogue_vec<.., POOL>): row tile t starts
 // at row t * pool_groups * pool_rows, so that no group straddles two workgroups; the main loop still multiplies BM rows from there (the
 // rows behind the tile's groups are the next tile's or lie past M: computed, then ignored).  An instantiation of its own, as GRES is.
-template <int TM, int TN, int WM, int WN, bool APLANES = false, int RING = 0, bool GRES = false, bool POOL = false>
+// ROWMAP: the ring with its rows assigned to tiles by a map (ConvArgs.row_map; h3_ring_tile<.., ROWMAP>).  An instantiation of its own too.
+template <int TM, int TN, int WM, int WN, bool APLANES = false, int RING = 0, bool GRES = false, bool POOL = false, bool ROWMAP = false>
 __global__ void __launch_bounds__(64 * WM * WN) k_conv_igemm_h3_db(const ConvArgs p) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, NT = 64 * WM * WN;
     constexpr int RPP = APLANES ? NT / 4 : NT / 8, PA = APLANES ? (2 * BM) / RPP : BM / RPP;      // A: rows staged per pass (planes: 4 pieces of 16 B per row per plane)
@@ -594,9 +607,10 @@ __global__ void __launch_bounds__(64 * WM * WN) k_conv_igemm_h3_db(const ConvArg
     extern __shared__ __attribute__((aligned(16))) char lds[];
     static_assert(!(RING && GRES), "the ring has no gathered residual");
     static_assert(!POOL || (APLANES && !RING && !GRES), "the pooled form: planes in, the two register-staged buffers, residual read or none");
+    static_assert(!ROWMAP || RING, "mapped rows: the ring only");
     if constexpr (RING) {                                 // (an instantiation of its own: as a run-time branch beside the other loop the ring keeps a
         static_assert(APLANES, "the ring reads planes");  //  quarter of its gain -- 729 -> 717-723 instead of 748 -> 703-713 us -- to the shared register file)
-        h3_ring_tile<TM, TN, WM, WN>(p, lds);
+        h3_ring_tile<TM, TN, WM, WN, ROWMAP>(p, lds);
         return;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -802,6 +816,21 @@ static int launch_h3_db(const ConvArgs& a, hipStream_t s, bool ring_ok = true) {
             return check_launch("conv2d_fwd_h3_pool");
         } else {
             return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_pool: the 256x128 tile on sixteen waves only");
+        }
+    }
+    if (p.row_map) {                                      // rows assigned to tiles by a map: sixteen waves of 64x32 reading planes, always on the ring (the mode's one loop)
+        if constexpr (WM * WN == 16 && TN == 1) {
+            if (!ring_ok || !p.x_planes || !p.vec_epi || !p.tile_taps || p.map_rows < BM || p.map_rows % BM || p.layout || p.splits != 1 ||
+                p.residual || p.res_planes || p.res_map || p.pool_rows || p.mask || p.n_split)
+                return fail(FRCNN_E_ARG, "conv2d_fwd_h3_rowmap: a dense single-layer plane-input launch on the ring, a map of whole row tiles");
+            p.tiles_m = p.map_rows / BM;
+            constexpr size_t ring_lds = (size_t)3 * 2 * (BM + BN) * X6_ROWB;
+            static std::atomic<uint64_t> lds_seen_rowmap{0};
+            if (int e = raise_lds_once(lds_seen_rowmap, (const void*)k_conv_igemm_h3_db<TM, TN, WM, WN, true, 1, false, false, true>, ring_lds, "conv2d_h3")) return e;
+            k_conv_igemm_h3_db<TM, TN, WM, WN, true, 1, false, false, true><<<p.tiles_m * p.tiles_n, 64 * WM * WN, ring_lds, s>>>(p);
+            return check_launch("conv2d_fwd_h3_rowmap");
+        } else {
+            return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_rowmap: the 256x128 tile on sixteen waves only");
         }
     }
     if (p.res_map) {                                   // the residual gathered by RoI taps: sixteen waves of 64x32, never the ring

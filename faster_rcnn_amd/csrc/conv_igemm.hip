@@ -29,6 +29,7 @@
 #include "conv_policy.h"
 #include "../../include/ext/frcnn_hip_roi_res.h"
 #include "../../include/ext/frcnn_hip_pool_epilogue.h"
+#include "../../include/ext/frcnn_hip_rowmap.h"
 
 namespace frcnn {
 
@@ -979,10 +980,11 @@ using namespace frcnn;
 struct DualOut { int n1; int act1; float* y2; int act2; };      // frcnn_conv2d_fwd_dual: the launch's second layer
 static int roi_res_available(const frcnn_conv_desc* d, int engine, bool x_is_planes);
 static int pool_available(const frcnn_conv_desc* d, int engine, bool x_is_planes, int window);
+static int rowmap_available(const frcnn_conv_desc* d, int engine, bool x_is_planes);
 static int conv_h3_planes_impl(const frcnn_conv_desc* d, const float* x, const frcnn_h3_planes* x_planes, const float* x_amax, const void* w_planes_f16,
                                const float* scale, const float* shift, const float* residual, const frcnn_h3_planes* residual_planes,
                                const frcnn_roi_res* gathered, const float* residual_amax, float* y, float* y_amax, const frcnn_h3_planes* y_planes,
-                               float bound_c, float bound_d, void* stream);
+                               float bound_c, float bound_d, void* stream, const frcnn_rowmap* rowmap = nullptr);
 
 // the magnitude records of a launch (ConvArgs.x_amax / y_amax / y2_amax), every other field zero
 static ConvArgs amax_args(const float* x_amax, float* y_amax, float* y2_amax = nullptr) {
@@ -1050,6 +1052,13 @@ static int conv_fwd_impl(const frcnn_conv_desc* d, const float* x, const float* 
                 return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_pool: not available for this launch (frcnn_conv2d_pool_available)");
             if (!a.vec_epi) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_pool: 16-byte addressable output and residual rows required");
             a.pool_groups = 256 / a.pool_rows < 1024 / 128 ? 256 / a.pool_rows : 1024 / 128;      // whole groups in a 256-row tile, one thread per group and column
+        }
+        if (a.row_map) {
+            // rows assigned to tiles by a map (include/ext/frcnn_hip_rowmap.h): what frcnn_conv2d_rowmap_available admits, nothing else
+            if (rowmap_available(d, engine, a.x_planes != nullptr) != 1 || dual || mask || residual || a.res_planes || a.res_map || a.pool_rows || workspace)
+                return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_rowmap: not available for this launch (frcnn_conv2d_rowmap_available)");
+            if (y && !a.vec_epi) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_rowmap: 16-byte addressable output rows required");
+            if (a.map_rows < 256 || a.map_rows % 256 || a.map_rows < M) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_rowmap: the map holds whole 256-row tiles and at least every output row");
         }
         if (planes_io) {
             // activations as fp16 planes (f16x3 only): the double-buffered 256x128 forms only, 16-byte epilogue, one layer, no mask
@@ -1151,7 +1160,36 @@ static int pool_available(const frcnn_conv_desc* d, int engine, bool x_is_planes
     return 1;
 }
 
+// frcnn_conv2d_rowmap_available (the launch asks the same question): 1 / 0
+static int rowmap_available(const frcnn_conv_desc* d, int engine, bool x_is_planes) {
+    if (engine != FRCNN_ENGINE_H3 || !x_is_planes) return 0;
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->ho <= 0 || d->wo <= 0) return 0;
+    if (d->layout || (d->cin % BK) != 0 || d->kh * d->kw > 32 || (d->cout & 3) || d->ldy > 0 || d->ldres > 0) return 0;
+    const SplitRule& r = split_rule(engine);
+    if (split_config(r, d, 0) != 86) return 0;              // 256x128 on sixteen waves, the ring allowed (85 keeps the two buffers); a split-K code maps to 84 / 81 here
+    const long long M = (long long)d->n * d->ho * d->wo;
+    if (M * d->cout * 4 >= 0x7fffffffLL || (long long)d->n * d->h * d->w * d->cin * 4 >= 0x7fffffffLL) return 0;
+    return 1;
+}
+
 extern "C" {
+
+int frcnn_conv2d_rowmap_available(const frcnn_conv_desc* d, int engine, int x_is_planes) {
+    if (!d) return fail(FRCNN_E_ARG, "conv2d_rowmap_available: null descriptor");
+    if (engine != FRCNN_ENGINE_NATIVE && engine != FRCNN_ENGINE_X6 && engine != FRCNN_ENGINE_H3) return fail(FRCNN_E_ARG, "conv2d_rowmap_available: unknown engine %d", engine);
+    return rowmap_available(d, engine, x_is_planes != 0);
+}
+
+int frcnn_conv2d_fwd_h3_rowmap(const frcnn_conv_desc* d, const frcnn_h3_planes* x_planes, const float* x_amax, const void* w_planes_f16,
+                               const float* scale, const float* shift, float* y, float* y_amax, const frcnn_h3_planes* y_planes,
+                               float bound_c, float bound_d, const frcnn_rowmap* map, void* stream) {
+    if (!d || !w_planes_f16 || !map) return fail(FRCNN_E_ARG, "conv2d_fwd_h3_rowmap: null pointer");
+    if (!map->row_map || !map->tile_taps || map->rows <= 0 || map->reserved != 0 || (reinterpret_cast<uintptr_t>(map->row_map) & 3) || (reinterpret_cast<uintptr_t>(map->tile_taps) & 3))
+        return fail(FRCNN_E_ARG, "conv2d_fwd_h3_rowmap: row map, tap words and rows > 0 required (reserved = 0)");
+    if (rowmap_available(d, FRCNN_ENGINE_H3, x_planes != nullptr) != 1)
+        return fail(FRCNN_E_UNSUPPORTED, "conv2d_fwd_h3_rowmap: not available for this launch (frcnn_conv2d_rowmap_available)");
+    return conv_h3_planes_impl(d, nullptr, x_planes, x_amax, w_planes_f16, scale, shift, nullptr, nullptr, nullptr, nullptr, y, y_amax, y_planes, bound_c, bound_d, stream, map);
+}
 
 int frcnn_pool_epilogue_version(void) { return FRCNN_POOL_EPILOGUE_VERSION; }
 
@@ -1290,7 +1328,7 @@ int frcnn_conv2d_fwd_h3_planes_res(const frcnn_conv_desc* d, const float* x, con
 static int conv_h3_planes_impl(const frcnn_conv_desc* d, const float* x, const frcnn_h3_planes* x_planes, const float* x_amax, const void* w_planes_f16,
                                const float* scale, const float* shift, const float* residual, const frcnn_h3_planes* residual_planes,
                                const frcnn_roi_res* gathered, const float* residual_amax, float* y, float* y_amax, const frcnn_h3_planes* y_planes,
-                               float bound_c, float bound_d, void* stream) {
+                               float bound_c, float bound_d, void* stream, const frcnn_rowmap* rowmap) {
     if (gathered) {
         auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
         if (!gathered->map || !gathered->taps || gathered->map_rows <= 0 || gathered->reserved != 0)
@@ -1313,5 +1351,6 @@ static int conv_h3_planes_impl(const frcnn_conv_desc* d, const float* x, const f
     if (y_planes) { rg.y_planes = y_planes->planes; rg.y_pexp = y_planes->exponent; rg.res_amax = (residual || residual_planes || gathered) ? residual_amax : nullptr; rg.bound_c = bound_c; rg.bound_d = bound_d; }
     if (residual_planes) { rg.res_planes = residual_planes->planes; rg.res_pexp = residual_planes->exponent; }
     if (gathered) { rg.res_map = gathered->map; rg.res_taps = gathered->taps; rg.res_fill = gathered->fill; rg.res_map_rows = gathered->map_rows; }
+    if (rowmap) { rg.row_map = rowmap->row_map; rg.tile_taps = rowmap->tile_taps; rg.map_rows = rowmap->rows; }
     return conv_fwd_impl(d, x, reinterpret_cast<const float*>(w_planes_f16), scale, shift, residual, nullptr, y, nullptr, nullptr, 0, stream, FRCNN_ENGINE_H3, rg);
 }

@@ -55,16 +55,16 @@ class ConvUnit:
         self.pc = packer(*self.folded())
         return self
 
-    def __call__(self, x, residual=None, out=None, act="unit", layout=0, planes_out=False):
+    def __call__(self, x, residual=None, out=None, act="unit", layout=0, planes_out=False, rowmap=False):
         """``act`` overrides the unit's activation for this call ("unit" = keep it); ``layout`` 1 = position-major
         tensors (h,w,n,c), see frcnn_conv_desc.layout; ``planes_out``: ops.conv2d (f32 path: the result may come back as an
-        ops.PlaneTensor for the next convolution)."""
+        ops.PlaneTensor for the next convolution); ``rowmap``: ops.conv2d (f32 path: class-sorted row tiles where the launch can)."""
         if self.pc is None:
             self.lower()
         act = self.act if act == "unit" else act
         if self.dtype == "bf16":
             return ops.conv2d_bf16(x, self.pc, self.stride, self.padding, act, residual, self.out_f32, self.tile, layout)
-        return ops.conv2d(x, self.pc, self.stride, self.padding, act, residual, out, self.tile, layout, planes_out)
+        return ops.conv2d(x, self.pc, self.stride, self.padding, act, residual, out, self.tile, layout, planes_out, rowmap)
 
     def avgpool(self, x, residual=None, layout=0):
         """This layer followed by the average over each image's whole window -> (n, cout) f32 (ops.conv2d_avgpool: inside the launch's
@@ -157,6 +157,11 @@ HEAD_ROI_RES = _os.environ.get("FRCNN_HEAD_ROI_RES", "1") != "0"
 # res5c_branch2c's epilogue on row tiles of five whole RoIs (ops.conv2d_avgpool; csrc/conv_f32_common.h x6_epilogue_vec<.., POOL>), where
 # that launch can ([roi][7][7][c] crops, planes in): bit-identical results.  FRCNN_HEAD_POOL_EPI=0/1 (dev knob); DESIGN section 7 has the A/B.
 HEAD_POOL_EPI = _os.environ.get("FRCNN_HEAD_POOL_EPI", "1") != "0"
+# the batched pass's 3x3 layers (res5a/b/c_branch2b on [roi][7][7][c] crops) assign their rows to tiles by padding class -- interior, edge
+# and corner positions of 256 RoIs per group of tiles -- so that a tile walks 9, 6 or 4 filter taps instead of every tile all nine
+# (ops.conv2d rowmap=; csrc/conv_h3.hip h3_ring_tile<.., ROWMAP>), where that launch can and the map saves tap-tiles: tensors in the same
+# layout, bit-identical results.  FRCNN_HEAD_ROWMAP=0/1 (dev knob); DESIGN section 7 has the A/B.
+HEAD_ROWMAP = _os.environ.get("FRCNN_HEAD_ROWMAP", "1") != "0"
 VGG_PLANES = _os.environ.get("FRCNN_VGG_PLANES", "1") != "0"        # VggBase: plane tensors between the convolutions of a block (round 6)
 # the same hand-over inside the TRUNK's bottleneck blocks, wherever the consuming launch is one that reads planes (the 256x128 tile
 # forms) -- VERDICT r5 item 3.  Mid-round, with 64x64 tiles under 256 tiles of 128x128: nothing (540.1 / 538.7 against 540.5 / 538.6
@@ -241,13 +246,14 @@ class VggExtents(Extents):
         return out
 
 
-def run_block(u, x, layout=0, planes=False, mask=None, out_planes=False, pool=False):
+def run_block(u, x, layout=0, planes=False, mask=None, out_planes=False, pool=False, rowmap=False):
     """identity_block / conv_block (resnet.py:114-247) and their TimeDistributed twins (:250-392).  ``planes``: branch2a's and
     branch2b's outputs have ONE reader each, the next convolution of the block: on the f16x3 engine they are handed on as the fp16
     planes that convolution multiplies (ops.PlaneTensor), so its loader splits nothing.  ``out_planes`` (round 6): the block's OUTPUT
     as planes only -- its two readers are the next block's branch2a, which stages them unchanged, and that block's closing 1x1, which
     reads the shortcut back from them (block_takes_planes says whether the next block can); ``x`` may be such a tensor.
-    ``pool``: the block's output averaged over each image's whole window, (n, cout) f32 (ConvUnit.avgpool: the head's last block)."""
+    ``pool``: the block's output averaged over each image's whole window, (n, cout) f32 (ConvUnit.avgpool: the head's last block).
+    ``rowmap``: branch2b's rows assigned to tiles by padding class where its launch can (ConvUnit.__call__; the batched head)."""
     planes = planes and HEAD_PLANES
     pair = _pair(u["2a"], u["1"]) if "1" in u else None
     if pair is not None:                                    # branch2a and the shortcut conv read x: one launch
@@ -257,7 +263,7 @@ def run_block(u, x, layout=0, planes=False, mask=None, out_planes=False, pool=Fa
         t = u["2a"](x, layout=layout, planes_out=planes and _reads_planes(u["2b"], tuple(x.shape[:-1]) + (_cout(u["2a"]),), layout))
     if mask is not None:                                    # a canvas pass: branch2b's 3x3 must read zeros beyond each image's true extent
         t = ops.zero_outside(t, mask)
-    t = u["2b"](t, layout=layout, planes_out=planes and _reads_planes(u["2c"], t.shape, layout))
+    t = u["2b"](t, layout=layout, planes_out=planes and _reads_planes(u["2c"], t.shape, layout), rowmap=rowmap)
     if pool:
         return u["2c"].avgpool(t, residual=shortcut, layout=layout)
     return u["2c"](t, residual=shortcut, layout=layout, planes_out=out_planes)
@@ -529,8 +535,9 @@ class ResNetHead:
             yield from b.values()
         yield self.dense.unit
 
-    def _first_block_hoisted(self, feat, rois, resize, layout=None, n_per_img=0):
-        """``n_per_img`` > 0: ``feat`` is a batch of maps and ``resize`` crops RoI r from image r // n_per_img's (forward_batched)."""
+    def _first_block_hoisted(self, feat, rois, resize, layout=None, n_per_img=0, rowmap=False):
+        """``n_per_img`` > 0: ``feat`` is a batch of maps and ``resize`` crops RoI r from image r // n_per_img's (forward_batched).
+        ``rowmap``: run_block's, for branch2b."""
         a = self.blocks[0]
         if feat.dim() == 4 and feat.shape[0] > 1:               # a batch of maps (forward_batched): `resize` knows which RoI crops which
             fmap = feat
@@ -553,7 +560,7 @@ class ResNetHead:
             t = resize(u, rois, self.pool, fill=a["2a"].pc.shift, relu=True, layout=L)
         out_shape = crop_shape[:-1] + (_cout(a["2c"]),)
         nxt = self.blocks[1] if len(self.blocks) > 1 else None
-        t = a["2b"](t, layout=L, planes_out=planes and _reads_planes(a["2c"], crop_shape[:-1] + (_cout(a["2b"]),), L))
+        t = a["2b"](t, layout=L, planes_out=planes and _reads_planes(a["2c"], crop_shape[:-1] + (_cout(a["2b"]),), L), rowmap=rowmap)
         c = a["2c"]
         if c.pc is None:
             c.lower()
@@ -565,12 +572,12 @@ class ResNetHead:
             s = resize(v, rois, self.pool, fill=a["1"].pc.shift, layout=L)
         return c(t, residual=s, layout=L, planes_out=planes and nxt is not None and block_takes_planes(nxt, out_shape, L))
 
-    def _run_rest(self, x, rest, L, pool=False):
+    def _run_rest(self, x, rest, L, pool=False, rowmap=False):
         """The identity blocks behind the first: each hands its output to the next as planes where that block can take them.
         ``pool``: the last block ends in the head's average pool (run_block) -> (n, cout) f32."""
         for i, b in enumerate(rest):
             nxt = rest[i + 1] if i + 1 < len(rest) else None
-            x = run_block(b, x, L, planes=self.dtype == "f32", pool=pool and nxt is None,
+            x = run_block(b, x, L, planes=self.dtype == "f32", pool=pool and nxt is None, rowmap=rowmap,
                           out_planes=self.dtype == "f32" and nxt is not None and block_takes_planes(nxt, tuple(x.shape[:-1]) + (_cout(b["2c"]),), L))
         return x
 
@@ -606,11 +613,13 @@ class ResNetHead:
             # (14 % more chunks), each launch alone is 0.5 % slower -- and four passes in flight 0.9 % faster (549-551 against 545-546
             # img/s, three alternating runs).  One-image passes tie (507 / 507) and the latency form loses 2 %: they keep position-major.
             L = BATCHED_F32_HEAD_LAYOUT if self.layout else 0
-            x = self._first_block_hoisted(feat, rois, functools.partial(ops.roi_crop_resize, n_per_img=n_per_img), layout=L, n_per_img=n_per_img)
+            rm = HEAD_ROWMAP and L == 0                     # the 3x3 layers skip padding taps per class-sorted row tile where they can (ops.conv2d)
+            x = self._first_block_hoisted(feat, rois, functools.partial(ops.roi_crop_resize, n_per_img=n_per_img), layout=L, n_per_img=n_per_img,
+                                          rowmap=rm)
             if L == 0 and HEAD_POOL_EPI and len(self.blocks) > 1:
                 # res5c_branch2c averages its output over each RoI's 49 rows itself where it can (ops.conv2d_avgpool)
-                return self.dense(self._run_rest(x, self.blocks[1:], L, pool=True))
-            x = self._run_rest(x, self.blocks[1:], L)
+                return self.dense(self._run_rest(x, self.blocks[1:], L, pool=True, rowmap=rm))
+            x = self._run_rest(x, self.blocks[1:], L, rowmap=rm)
             if L:
                 return self.dense(ops.avgpool_pos_major(x))
             x = ops.pool2d(x, 7, 7, False)

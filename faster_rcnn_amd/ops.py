@@ -894,8 +894,9 @@ def _conv_launch(d, x, w, scale, shift, residual, mask, out, y_amax=None):
     return (fn, args), ws
 
 
-def _conv2d_h3_planes(d, x, pc, residual, oshape, planes_out, act):
-    """frcnn_conv2d_fwd_h3_planes: x a PlaneTensor or an f32 tensor, the result a PlaneTensor (planes_out) or an f32 tensor."""
+def _conv2d_h3_planes(d, x, pc, residual, oshape, planes_out, act, rowmap=None):
+    """frcnn_conv2d_fwd_h3_planes: x a PlaneTensor or an f32 tensor, the result a PlaneTensor (planes_out) or an f32 tensor.
+    ``rowmap``: the launch's rows assigned to tiles by this map (``_conv_rowmap``; plane input, no residual: frcnn_conv2d_fwd_h3_rowmap)."""
     x_in = isinstance(x, PlaneTensor)
     xp = _lib.H3Planes(planes=x.planes.data_ptr(), exponent=x.exponent.data_ptr(), status=None) if x_in else None
     y = PlaneTensor(oshape) if planes_out else torch.empty(oshape, dtype=torch.float32, device="cuda")
@@ -909,7 +910,12 @@ def _conv2d_h3_planes(d, x, pc, residual, oshape, planes_out, act):
     rp = _lib.H3Planes(planes=residual.planes.data_ptr(), exponent=residual.exponent.data_ptr(), status=None) if r_in else None
     head = (ctypes.byref(d), None if x_in else _p(x), ctypes.byref(xp) if x_in else None, _p(xa), _p(pc.h3_planes()), _p(pc.scale), _p(pc.shift))
     tail = (_p(ra), None if planes_out else _p(y), _p(ya), ctypes.byref(yp) if planes_out else None, bc, bd)
-    if r_roi:
+    rm = None
+    if rowmap is not None:
+        assert x_in and residual is None
+        rm = _lib.RowMap(row_map=rowmap[0].data_ptr(), tile_taps=rowmap[1].data_ptr(), rows=rowmap[0].numel(), reserved=0)
+        fn, args = "frcnn_conv2d_fwd_h3_rowmap", (head[0],) + head[2:] + tail[1:] + (ctypes.byref(rm),)
+    elif r_roi:
         rp = residual.desc()
         fn, args = "frcnn_conv2d_fwd_h3_roi_res", head + (ctypes.byref(rp),) + tail
     else:
@@ -918,9 +924,62 @@ def _conv2d_h3_planes(d, x, pc, residual, oshape, planes_out, act):
     y._amax = ya
     # (the instantiation that reads planes is a kernel of its own; writing planes is a run-time branch of either's epilogue; the gathered
     # residual is an instantiation too, listed under the name of the launch it replaces so that per-kernel figures cover the same launches)
-    _record_launch(lambda: _h3_planes_in_name(d, pc) if x_in else _h3_name(d), _gemm_shape(d, pc, d.stride), fn,
-                   args, (d, x, pc, residual, y, ya, xp, yp, xa, ra, rp), planes_out=bool(planes_out), roi_res=bool(r_roi))
+    # (the mapped ring likewise: the plane-reading kernel's name, a fifth word in the shape as the pooled launch has)
+    _record_launch(lambda: _h3_planes_in_name(d, pc) if x_in else _h3_name(d), _gemm_shape(d, pc, d.stride) + (("rowmap",) if rm is not None else ()), fn,
+                   args, (d, x, pc, residual, y, ya, xp, yp, xa, ra, rp, rm, rowmap), planes_out=bool(planes_out), roi_res=bool(r_roi),
+                   **({"rowmap": True} if rm is not None else {}))
     return y
+
+
+# Class-sorted row tiles (include/ext/frcnn_hip_rowmap.h): the map of a launch depends on its geometry only, so it is built once per
+# geometry on the host and kept on the device for every later launch and every captured pass (fixed addresses across replays).
+ROWMAP_ORDER = int(os.environ.get("FRCNN_ROWMAP_ORDER", "0"))       # dev knob: class order inside a super-group (0 raster, 1 long tiles first)
+_ROWMAP_CACHE = {}
+
+
+def conv_rowmap_host(d, order=None, tile_rows=_lib.ROWMAP_TILE_ROWS):
+    """frcnn_conv_rowmap_build on the host, no GPU: -> (pays, row_map int32 [rows], tile_taps uint32 [rows / tile_rows], tap_tiles).
+    ``pays`` False: the map saves no tap-tile against the plain launch ("not available"); it is a valid map all the same."""
+    lib = _lib.load()
+    order = ROWMAP_ORDER if order is None else order
+    rows, tap_tiles = ctypes.c_int64(0), ctypes.c_int64(0)
+    got = lib.frcnn_conv_rowmap_build(ctypes.byref(d), tile_rows, order, None, 0, None, 0, ctypes.byref(rows), ctypes.byref(tap_tiles))
+    if got < 0:
+        _lib.check(got, "frcnn_conv_rowmap_build")
+    row_map = np.empty(rows.value, np.int32)
+    taps = np.empty(rows.value // tile_rows, np.uint32)
+    got = lib.frcnn_conv_rowmap_build(ctypes.byref(d), tile_rows, order, row_map.ctypes.data_as(ctypes.c_void_p), row_map.size,
+                                      taps.ctypes.data_as(ctypes.c_void_p), taps.size, None, None)
+    if got < 0:
+        _lib.check(got, "frcnn_conv_rowmap_build")
+    return got == 1, row_map, taps, tap_tiles.value
+
+
+def _conv_rowmap(d, force=False):
+    """The device copy of descriptor ``d``'s map, (row_map, tile_taps) int32 tensors, or None where the map does not pay (``force``: then
+    too).  Built and uploaded on first use, which must lie outside a capture (a warm-up pass does it)."""
+    key = (torch.cuda.current_device(), ROWMAP_ORDER, d.n, d.h, d.w, d.ho, d.wo, d.kh, d.kw, d.stride, d.pad_top, d.pad_left)
+    got = _ROWMAP_CACHE.get(key)
+    if got is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.FrcnnError("conv2d(rowmap=...): the row map of this shape is uploaded on first use, which cannot happen inside a capture "
+                                  "(run the pass once before capturing it)")
+        pays, row_map, taps, _ = conv_rowmap_host(d)
+        got = _ROWMAP_CACHE[key] = (pays, torch.from_numpy(row_map).cuda(), torch.from_numpy(taps.view(np.int32)).cuda())
+    return (got[1], got[2]) if (got[0] or force) else None
+
+
+def conv_takes_rowmap(x, pc, stride=1, padding="valid", act=None, layout=0, tile=0):
+    """Can ``conv2d(x, pc, ..., rowmap=True)`` assign its rows to tiles by a map (frcnn_conv2d_rowmap_available: the f16x3 engine's 256x128
+    ring reading planes, [roi][h][w][c] rows, un-split)?  Whether the map PAYS is a second question (``_conv_rowmap``)."""
+    if not isinstance(pc, PackedConv) or not isinstance(x, PlaneTensor) or layout:
+        return False
+    d = _conv_desc(tuple(x.shape), pc.kh, pc.kw, pc.cout, stride, padding, ACT[act], layout, tile or AUTO_TILE)
+    eng = _split_engine(d, pc, tile or AUTO_TILE)
+    got = _lib.load().frcnn_conv2d_rowmap_available(ctypes.byref(d), {None: 0, "x6": 1, "h3": 2}[eng], 1)
+    if got < 0:
+        _lib.check(got, "frcnn_conv2d_rowmap_available")
+    return got == 1 and _planes_ok(d, pc, eng)
 
 
 def _h3_planes_in_name(d, pc):
@@ -936,12 +995,15 @@ def _planes_ok(d, pc, eng):
             and (_CONV_WS is NO_SPLIT_K or _ws_need(d, "frcnn_conv2d_h3_workspace_bytes") == 0))
 
 
-def conv2d(x, pc, stride=1, padding="valid", act=None, residual=None, out=None, tile=0, layout=0, planes_out=False):
+def conv2d(x, pc, stride=1, padding="valid", act=None, residual=None, out=None, tile=0, layout=0, planes_out=False, rowmap=False):
     """x: (n,h,w,cin) f32 NHWC device tensor; pc: PackedConv -> (n,ho,wo,cout).
     layout=1: position-major tensors, x (h,w,n,cin) -> (ho,wo,n,cout) (frcnn_conv_desc.layout).
     ``planes_out``: a REQUEST to hand the result on as a PlaneTensor (the caller knows its only readers are f16x3 convolutions of the
     detector head's size); honoured when this launch runs on the engine's 256x128 tile, otherwise the f32 tensor comes back as usual.
-    x may be a PlaneTensor (then the launch must be such a one: anything else raises)."""
+    x may be a PlaneTensor (then the launch must be such a one: anything else raises).
+    ``rowmap``: a REQUEST to assign the launch's rows to tiles by padding class, so that a tile skips the filter taps that meet only zero
+    padding (include/ext/frcnn_hip_rowmap.h): honoured where ``conv_takes_rowmap`` says the launch can and the map saves tap-tiles
+    ("force": wherever the launch can); the same result bit for bit either way, tensors in the same layout."""
     _require_gpu()
     x_planes = isinstance(x, PlaneTensor)
     assert (x_planes or (x.dtype == torch.float32 and x.is_contiguous())) and x.shape[-1] == pc.cin, (x.shape, pc.cin)
@@ -959,7 +1021,10 @@ def conv2d(x, pc, stride=1, padding="valid", act=None, residual=None, out=None, 
         if ok:
             if residual is not None:
                 assert tuple(residual.shape) == tuple(oshape) and (res_planes or roi_res or residual.is_contiguous())
-            return _conv2d_h3_planes(d, x, pc, residual, oshape, planes_out, act)
+            rm = None
+            if rowmap and residual is None and conv_takes_rowmap(x, pc, stride, padding, act, layout, tile):
+                rm = _conv_rowmap(d, force=rowmap == "force")
+            return _conv2d_h3_planes(d, x, pc, residual, oshape, planes_out, act, rm)
     if out is None:
         out = torch.empty(oshape, dtype=torch.float32, device="cuda")
     else:
