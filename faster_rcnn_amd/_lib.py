@@ -549,6 +549,17 @@ TRACK_REID_MAX_EVENTS = 32
 TRACK_REID_LIST_WORDS = 4 + 5 * TRACK_REID_MAX_EVENTS
 TRACK_REID_MAX_DISTANCE = 8192
 
+DETECT_POST_VERSION = 1         # include/ext/frcnn_hip_detect_post.h FRCNN_DETECT_POST_VERSION
+DETECT_POST_SIGNATURES = {
+    "frcnn_detect_post_version": (I, []),
+    "frcnn_detections_post": (I, [P, P, I, P, P, I, I, c_double, c_double, c_double, c_double, P, P, P, P, P, I, c_double, c_double, c_double, P]),
+    "frcnn_detections_post_dyn": (I, [P, P, I, I, P, P, I, I, c_double, c_double, P, P, P, P, P, P, I, c_double, c_double, c_double, P]),
+}
+# FRCNN_NMS_HARD / _SOFT_LINEAR / _SOFT_GAUSSIAN, and the defaults of nms_thresh, sigma and the voting IoU (sigma and the voting IoU, like
+# min_score = the image's threshold, are PROVISIONAL: their effect on mAP has not been measured on a dataset)
+DETECT_POST_MODES = ("hard", "soft_linear", "soft_gaussian")
+DETECT_POST_DEFAULTS = (0.5, 0.5, 0.5)
+
 TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
 TRACK_LOOKBACK_SIGNATURES = {
     "frcnn_track_lookback_version": (I, []),
@@ -786,6 +797,15 @@ def load():
     if lib.frcnn_track_reid_version() != TRACK_REID_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_reid_version()} of the re-identify extension, this binding "
                          f"{TRACK_REID_VERSION} (include/ext/frcnn_hip_track_reid.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in DETECT_POST_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_detect_post.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_detect_post_version() != DETECT_POST_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_detect_post_version()} of the post-process extension, this binding "
+                         f"{DETECT_POST_VERSION} (include/ext/frcnn_hip_detect_post.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

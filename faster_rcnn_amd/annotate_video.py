@@ -275,10 +275,11 @@ def png_filenames(input_dir):
     return sorted(f for f in os.listdir(input_dir) if f.endswith(".png"))
 
 
-def _engine(training_manager, detector, in_flight):
+def _engine(training_manager, detector, in_flight, post=None):
+    """``post``: the post-process option (ops.det_post_option); an engine with it is one of its own, with its own editing states."""
     if not voc_dets.FAST_ENTRY:
         return None
-    eng = entry.for_models(training_manager, detector, 64, STRIDE, in_flight=in_flight)
+    eng = entry.for_models(training_manager, detector, 64, STRIDE, in_flight=in_flight, post=post)
     return eng if eng is not None and eng.device_preprocess else None
 
 
@@ -717,10 +718,10 @@ def _count_state(training_manager, eng):
     return eng.count_state() if eng is not None else _eager_states(training_manager.class_mapping).count_state()
 
 
-def reset_counts(training_manager, detector, in_flight=1):
+def reset_counts(training_manager, detector, in_flight=1, post=None):
     """Zero totals and no entries before a new sequence: the count state of the engine ``in_flight`` names, or the eager path's.
     (``reset_tracks`` ends the ids and keeps the totals.)"""
-    eng = _engine(training_manager, detector, in_flight)
+    eng = _engine(training_manager, detector, in_flight, post)
     if eng is not None:
         eng.count_reset()
     else:
@@ -903,10 +904,10 @@ def _zone_state(training_manager, eng):
     return eng.zone_state() if eng is not None else _eager_states(training_manager.class_mapping).zone_state()
 
 
-def reset_zones(training_manager, detector, in_flight=1):
+def reset_zones(training_manager, detector, in_flight=1, post=None):
     """An empty zone state, totals included, before a new sequence: the state of the engine ``in_flight`` names, or the eager path's.
     (``reset_tracks`` ends the ids and keeps the totals.)"""
-    eng = _engine(training_manager, detector, in_flight)
+    eng = _engine(training_manager, detector, in_flight, post)
     if eng is not None:
         eng.zone_reset()
     else:
@@ -984,9 +985,9 @@ def _heat_states(training_manager, eng):
     return {hw: st.cpu().numpy() for hw, st in states.heat.items()}
 
 
-def reset_heat(training_manager, detector, in_flight=1):
+def reset_heat(training_manager, detector, in_flight=1, post=None):
     """A cold heat map before a new sequence: the states of the engine ``in_flight`` names, or the eager path's."""
-    eng = _engine(training_manager, detector, in_flight)
+    eng = _engine(training_manager, detector, in_flight, post)
     if eng is not None:
         eng.heat_reset()
     else:
@@ -1089,9 +1090,9 @@ def _plate_states(training_manager, eng):
     return {key: st.cpu().numpy() for key, st in states.plate.items()}
 
 
-def reset_plate(training_manager, detector, in_flight=1):
+def reset_plate(training_manager, detector, in_flight=1, post=None):
     """An empty plate before a new sequence: the states of the engine ``in_flight`` names, or the eager path's."""
-    eng = _engine(training_manager, detector, in_flight)
+    eng = _engine(training_manager, detector, in_flight, post)
     if eng is not None:
         eng.plate_reset()
     else:
@@ -1133,9 +1134,9 @@ def _write_tracks(tracks_out, frame_no, dets, class_mapping):
         tracks_out.writelines(line + "\n" for line in mot_lines(frame_no, dets, class_mapping))
 
 
-def reset_tracks(training_manager, detector, in_flight=1):
+def reset_tracks(training_manager, detector, in_flight=1, post=None):
     """Forget every track before a new sequence: the state of the engine ``in_flight`` names, or the eager path's."""
-    eng = _engine(training_manager, detector, in_flight)
+    eng = _engine(training_manager, detector, in_flight, post)
     if eng is not None:
         eng.track_reset()
     else:
@@ -1151,7 +1152,7 @@ def _print_drawn(dets, width, height):
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
                         track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, track_reid=None,
-                        reid_out=None):
+                        reid_out=None, post=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
@@ -1175,7 +1176,11 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     ``track_reid`` = (pct, keep) (with ``track``): the frame continues the appearance memory of the calls before it (DESIGN §8
     "Re-identify rule"; ``reset_tracks`` empties it): a track that returns carries its old id everywhere, a line ``re-identified:
     <frame_no> id <pid>`` is printed in front of the frame's lines, and ``reid_out``, a text file, receives the frame's rows
-    ``frame,id,tracker_id,cls,distance,gap``."""
+    ``frame,id,tracker_id,cls,distance,gap``.
+    ``post``: the post-process option (``ops.det_post_option``: soft-NMS / box voting, DESIGN §8 "Post-process rule") -- which boxes the
+    detector reports, in front of everything above; the engine with the option keeps editing states of its own (``reset_tracks(...,
+    post=)``).  None: every byte and line is what it was."""
+    post = None if post is None else ops.det_post_option(post)
     track_reid = _track_reid(track_reid, track)
     if reid_out is not None and track_reid is None:
         raise ValueError("reid_out is where the re-identifications are written: it needs track_reid=(pct, keep)")
@@ -1215,7 +1220,7 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     if track_reid is not None:
         motion["track_reid"] = track_reid
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
-    eng = _engine(training_manager, detector, 1)
+    eng = _engine(training_manager, detector, 1, post)
     info = {}
     if eng is not None:
         pixels = eng.host_pixels(resized_imgs[0])
@@ -1230,7 +1235,7 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         print("num rois: {}".format(num_rois))
         frame[...] = out
     else:
-        dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=DET_THRESHOLD)
+        dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=DET_THRESHOLD, post=post)
         draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, info=info, heatmap=heatmap, **motion)
         if info.get("scene_cut"):
             print("scene cut: {}".format(frame_no))
@@ -1644,13 +1649,16 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
               track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None,
-              plate_out=None, track_reid=None, reid_out=None):
+              plate_out=None, track_reid=None, reid_out=None, post=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     motion = {} if track_motion is None else {"track_motion": track_motion}
+    post = None if post is None else ops.det_post_option(post)        # (refused here, in front of any capture)
+    if post is not None:
+        motion["post"] = post
     heatmap = _heatmap(heatmap)
     heatmap_out = _heatmap_out(heatmap_out, heatmap)
     remove = _remove(remove)
@@ -1673,7 +1681,7 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     sink = make_sink()
     try:
         dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
-        eng = _engine(training_manager, detector, entry.default_in_flight(dtype))
+        eng = _engine(training_manager, detector, entry.default_in_flight(dtype), post)
         tracking, every, delayed, backtrack = _tracking_options(eng, track, track_motion, track_lookback, detect_every, track_backtrack,
                                                                 track_scene_cut)
         if track_scene_cut is not None:                   # (the eager path: one frame at a time against the kept frame)
@@ -1683,20 +1691,20 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             motion["track_trails"] = tracking["track_trails"] = trails
         if heatmap is not None:                           # a cold map for the list
             motion["heatmap"] = tracking["heat"] = heatmap
-            reset_heat(training_manager, detector, 1 if eng is None else eng.in_flight)
+            reset_heat(training_manager, detector, 1 if eng is None else eng.in_flight, post)
         if remove is not None:                            # an empty plate for the list
             motion["remove"] = tracking["remove"] = remove
-            reset_plate(training_manager, detector, 1 if eng is None else eng.in_flight)
+            reset_plate(training_manager, detector, 1 if eng is None else eng.in_flight, post)
         if track is not None:                             # a new sequence; its frames are submitted in input order, as every list's are
-            reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight)
+            reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight, post)
         if count is not None:                             # zero totals for the list
             motion["count"] = tracking["count"] = count
-            reset_counts(training_manager, detector, 1 if eng is None else eng.in_flight)
+            reset_counts(training_manager, detector, 1 if eng is None else eng.in_flight, post)
             counts_log = CountsLog(counts_out, _names_by_index(training_manager.class_mapping))
             motion["counts_out"] = counts_log
         if zone is not None:                              # an empty state for the list
             motion["zone"] = tracking["zone"] = zone
-            reset_zones(training_manager, detector, 1 if eng is None else eng.in_flight)
+            reset_zones(training_manager, detector, 1 if eng is None else eng.in_flight, post)
             zones_log = ZonesLog(zones_out, _names_by_index(training_manager.class_mapping))
             motion["zones_out"] = zones_log
         if track_reid is not None:                        # (an empty memory for the list: reset_tracks above emptied it)
@@ -1768,13 +1776,13 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
                     track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
-                    counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None, reid_out=None):
+                    counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None, reid_out=None, post=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out`` / ``remove`` / ``plate_out`` / ``track_reid`` / ``reid_out``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out`` / ``remove`` / ``plate_out`` / ``track_reid`` / ``reid_out`` / ``post``: as ``annotate_images``."""
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
     if isinstance(writer_or_out_dir, y4m.Y4mWriter):
         make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma)
@@ -1785,7 +1793,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
               detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
               heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out, remove=remove,
-              plate_out=plate_out, track_reid=track_reid, reid_out=reid_out)
+              plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
@@ -1793,7 +1801,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
                     heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None,
-                    reid_out=None):
+                    reid_out=None, post=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1847,7 +1855,11 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     tracked rows, in a delayed pass the emitted frames'), loses ceil(v / 2^S) per frame, and is blended into each frame at weight A for
     the hottest pixel, over the redaction and under the trails, boxes and labels (DESIGN §8 "Heat rule").  ``heatmap_out``: a path ending
     in .png that receives the map at the end of the list, 8-bit grey, one file per frame size met (``<stem>_<w>x<h>.png`` for several).
-    The printed lines and ``tracks_out`` are unchanged.  None: every byte and line is what it was."""
+    The printed lines and ``tracks_out`` are unchanged.  None: every byte and line is what it was.
+    ``post``: the post-process option as ``args_util.post_from_args`` returns it (``ops.det_post_option``: mode, nms_thresh, sigma,
+    min_score, vote_iou) -- soft-NMS and box voting inside the captured passes (DESIGN §8 "Post-process rule"), on the eager path through
+    ``ops.detections_post``: which boxes every frame reports, with decayed scores in the soft modes; everything above then works on those
+    boxes.  The passes belong to an engine of their own.  None: no pass, engine key, printed line or output byte changes."""
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
@@ -1861,7 +1873,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
               track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out,
-              remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out)
+              remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post)
 
 
 def build_parser():
@@ -2027,6 +2039,8 @@ def build_parser():
                         "(needs --count_line)")
     p.add_argument("--tracks_out", dest="tracks_out", default=None, metavar="PATH",
                    help="write the tracks as MOTChallenge lines frame,id,left,top,width,height,prob,cls,-1,-1 (needs --track)")
+    from .args_util import add_post_arguments
+    add_post_arguments(p)                                 # --nms, --nms_thresh, --nms_sigma, --nms_min_score, --box_vote
     return p
 
 
@@ -2076,7 +2090,7 @@ def main(argv=None):
 def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     import sys
     from . import resnet, vgg
-    from .args_util import anchor_scales_from_str, resize_dims_from_str
+    from .args_util import anchor_scales_from_str, post_from_args, resize_dims_from_str
     from .data.voc_data_helpers import KITTI_CLASS_MAPPING, VOC_CLASS_MAPPING
     from .det_util import DetTrainingManager
     from .util import get_anchors
@@ -2131,6 +2145,9 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
         tracking["zone"] = zone
     if zones_out is not None:
         tracking["zones_out"] = zones_out
+    post = post_from_args(args)                           # (before any model is loaded: dependent options are refused by name)
+    if post is not None:
+        tracking["post"] = post
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

@@ -24,3 +24,37 @@ def resize_dims_from_str(resize_dims_str):
 
 def anchor_scales_from_str(anchor_scales_str):
     return [int(d) for d in anchor_scales_str.split(",")]
+
+
+from ._lib import DETECT_POST_MODES as NMS_MODES          # (one list: the C ABI's mode numbers are its indices)
+
+
+def add_post_arguments(p):
+    """The five post-process arguments voc_dets and annotate_video share (DESIGN §8 "Post-process rule")."""
+    p.add_argument("--nms", dest="nms", choices=NMS_MODES, default=None,
+                   help="the detection post-process's NMS: hard (the reference's, the default), soft_linear or soft_gaussian (Soft-NMS: an "
+                        "overlapped box loses score instead of being deleted; the written prob is the decayed score)")
+    p.add_argument("--nms_thresh", dest="nms_thresh", type=float, default=None, help="IoU above which hard deletes and soft_linear decays (0.5)")
+    p.add_argument("--nms_sigma", dest="nms_sigma", type=float, default=None,
+                   help="soft_gaussian's sigma (0.5, provisional: not tuned on a dataset); only with --nms soft_gaussian")
+    p.add_argument("--nms_min_score", dest="nms_min_score", type=float, default=None,
+                   help="a soft mode stops a class when its best decayed score falls under this (default: the detection threshold; "
+                        "provisional); not with --nms hard")
+    p.add_argument("--box_vote", dest="box_vote", type=float, nargs="?", const=0.5, default=None, metavar="IOU",
+                   help="box voting: a detection's box becomes the score-weighted mean of its class's boxes that overlap it by at least "
+                        "IOU (bare: 0.5, provisional)")
+
+
+def post_from_args(args):
+    """The post-process option of a parsed command line -> None when none of the five arguments was given (nothing changes then), else
+    ops.det_post_option's tuple.  Arguments that depend on another are refused by name: ValueError with the reason."""
+    given = [getattr(args, k, None) for k in ("nms", "nms_thresh", "nms_sigma", "nms_min_score", "box_vote")]
+    if all(v is None for v in given):
+        return None
+    mode = args.nms or "hard"
+    if args.nms_sigma is not None and mode != "soft_gaussian":
+        raise ValueError("--nms_sigma needs --nms soft_gaussian (it is the gaussian weight's sigma; the mode here is %s)" % mode)
+    if args.nms_min_score is not None and mode == "hard":
+        raise ValueError("--nms_min_score needs --nms soft_linear or soft_gaussian (hard NMS decays no score)")
+    from . import ops
+    return ops.det_post_option((mode, args.nms_thresh, args.nms_sigma, args.nms_min_score, args.box_vote))

@@ -23,6 +23,7 @@ SOURCES = {
     "sort_nms.hip": ["-ffp-contract=off"],
     "roi.hip": ["-ffp-contract=off"],
     "detect.hip": ["-ffp-contract=off"],
+    "detect_post.hip": ["-ffp-contract=off"],
 }
 
 

@@ -613,8 +613,11 @@ class DetectionEntry:
     ``collect(ticket)`` returns ``(num_rois, dets)`` with ``dets`` the reference's list of
     ``{'bbox': int array [x1,y1,x2,y2], 'cls_name', 'prob'}`` in its order (voc_dets.py:73-86)."""
 
-    def __init__(self, manager, detector, num_rois=64, stride=16, in_flight=1, byte_budget=None, f32_engine=None):
+    def __init__(self, manager, detector, num_rois=64, stride=16, in_flight=1, byte_budget=None, f32_engine=None, post=None):
         self.manager, self.detector = manager, detector
+        # the post-process option (ops.det_post_option: soft-NMS / box voting), fixed per engine: every pass it captures -- exact, canvas,
+        # annotating -- runs it; None = the reference's rule, the kernels and bytes of an engine built before the option existed
+        self.post = None if post is None else ops.det_post_option(post)
         # the matrix path of the fp32 convolutions inside the captured passes (ops.f32_engine): by default the large launches run
         # on the fp16 matrix cores by a two-way operand split with a scaled low part -- fp32-grade results (csrc/conv_h3.hip:
         # error against fp64 under the native kernel's), three matrix instructions per block of products; FRCNN_F32_ENGINE=bf16x6
@@ -1112,6 +1115,8 @@ class DetectionEntry:
             m = self.manager
             kw = dict(stride=self.stride, pre_nms_top_n=PRE_NMS_TOP_N, max_proposals=MAX_PROPOSALS, roi_batch=self.num_rois, pad_to_batch=PAD_TO_BATCH,
                       bg_idx=m.class_mapping["bg"])
+            if self.post is not None:
+                kw["post"] = self.post
             if B > 1:
                 pipe = BatchedInferencePipeline(m.rpn_model, self.detector, m.anchor_dims, B, **kw)
             else:
@@ -1861,20 +1866,25 @@ class DetectionEntry:
 
     def stats(self):
         c = self.cache
-        return {"graphs": len(c), "sizes": len(c.keys()), "bytes": c.nbytes, "byte_budget": c.byte_budget, "captures": c.captures,
+        post = {} if self.post is None else {"post": dict(zip(ops.DET_POST_FIELDS, self.post))}      # (only an engine that has the option says so)
+        return {**post, "graphs": len(c), "sizes": len(c.keys()), "bytes": c.nbytes, "byte_budget": c.byte_budget, "captures": c.captures,
                 "hits": c.hits, "evictions": c.evictions, "capture_seconds": round(self.capture_seconds, 3), "in_flight": self.in_flight,
                 "device_preprocess": self.device_preprocess, "f32_engine": self.f32_engine, "images_per_pass": self.batch,
                 "canvas_slots": {"%dx%d" % k[1:3]: v for k, v in self._canvas_slots.items()},      # canvas class "HcxWc" -> captured passes its plan allows
                 "capture_breakdown_ms": {k: round(v, 1) for k, v in self.capture_breakdown.items()}}
 
 
-def for_models(manager, detector, num_rois=64, stride=16, in_flight=1):
-    """The DetectionEntry of this (manager, detector, num_rois, stride, in_flight), built on first use and kept on the
-    manager; None when the pair cannot take the captured path (voc_dets then runs the eager one)."""
+def for_models(manager, detector, num_rois=64, stride=16, in_flight=1, post=None):
+    """The DetectionEntry of this (manager, detector, num_rois, stride, in_flight[, post]), built on first use and kept on the
+    manager; None when the pair cannot take the captured path (voc_dets then runs the eager one).  ``post``: the post-process option
+    (ops.det_post_option); an engine with it is a table entry of its own beside the one without."""
     if not torch.cuda.is_available() or not DetectionEntry.usable(manager, detector, num_rois):
         return None
     table = manager.__dict__.setdefault("_entries", {})
     key = (id(detector), int(num_rois), stride, int(in_flight))
+    if post is not None:
+        post = ops.det_post_option(post)
+        key += (post,)
     eng = table.get(key)
     if eng is None or eng.detector is not detector:
         global _QUEUES_SAID
@@ -1884,7 +1894,7 @@ def for_models(manager, detector, num_rois=64, stride=16, in_flight=1):
             warnings.warn("faster_rcnn_amd.entry: this process runs on %s hardware queues (GPU_MAX_HW_QUEUES; ROCm's default is 4): get_dets_by_cls measures "
                           "~9 %% slower there than on 8 (497 against 542-547 img/s).  The setting is read when the HIP runtime starts: export "
                           "GPU_MAX_HW_QUEUES=8 before the first device call, as voc_dets.main does." % os.environ.get("GPU_MAX_HW_QUEUES", "4"))
-        eng = table[key] = DetectionEntry(manager, detector, num_rois, stride, in_flight)
+        eng = table[key] = DetectionEntry(manager, detector, num_rois, stride, in_flight, post=post)
     return eng
 
 

@@ -1214,6 +1214,87 @@ def detections_dyn(rois, n_rois, out_cls, out_reg, roi_batch, bg_idx, stride, dy
     return {"det_cls": det_cls, "det_prob": det_prob, "det_bbox": det_bbox, "det_roi": det_roi, "n_dets": n_dets, "det_packed": packed}
 
 
+DET_POST_MODES = _lib.DETECT_POST_MODES
+DET_POST_FIELDS = ("mode", "nms_thresh", "sigma", "min_score", "vote_iou")
+
+
+def det_post_option(post=None):
+    """(host only) The post-process option checked -> (mode, nms_thresh, sigma, min_score, vote_iou) (DESIGN §8 "Post-process rule",
+    include/ext/frcnn_hip_detect_post.h).  ``post``: None, a mode name, a tuple in that order (missing tail = defaults) or a dict of those
+    names.  mode ``hard`` | ``soft_linear`` | ``soft_gaussian`` (None: hard); nms_thresh in [0, 1] (None: 0.5); sigma > 0 (None: 0.5);
+    min_score None (the image's det_threshold) or in [0, 1]; vote_iou None (no voting) or in (0, 1].  sigma 0.5, voting at 0.5 and
+    min_score = det_threshold are PROVISIONAL: their effect on mAP has not been measured on a dataset.  ValueError with the reason."""
+    if post is None:
+        post = ()
+    if isinstance(post, str):
+        post = (post,)
+    if isinstance(post, dict):
+        unknown = sorted(set(post) - set(DET_POST_FIELDS))
+        if unknown:
+            raise ValueError("post-process option: unknown field(s) %s (%s)" % (", ".join(map(repr, unknown)), ", ".join(DET_POST_FIELDS)))
+        post = tuple(post.get(k) for k in DET_POST_FIELDS)
+    if not isinstance(post, (tuple, list)) or len(post) > len(DET_POST_FIELDS):
+        raise ValueError("post-process option %r: None, a mode name, a dict or a tuple of at most (%s)" % (post, ", ".join(DET_POST_FIELDS)))
+    mode, nt, sigma, min_score, vote = tuple(post) + (None,) * (len(DET_POST_FIELDS) - len(post))
+    mode = "hard" if mode is None else mode
+    if mode not in DET_POST_MODES:
+        raise ValueError("post-process mode %r: one of %s" % (mode, ", ".join(DET_POST_MODES)))
+
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != v:
+            raise ValueError("post-process %s=%r: a number" % (name, v))
+        return float(v)
+    d_nt, d_sigma, _ = _lib.DETECT_POST_DEFAULTS
+    nt = d_nt if nt is None else number("nms_thresh", nt)
+    if not 0.0 <= nt <= 1.0:
+        raise ValueError("post-process nms_thresh=%r: in [0, 1]" % nt)
+    sigma = d_sigma if sigma is None else number("sigma", sigma)
+    if not (sigma > 0.0 and sigma != float("inf")):
+        raise ValueError("post-process sigma=%r: finite and > 0" % sigma)
+    if min_score is not None:
+        min_score = number("min_score", min_score)
+        if not 0.0 <= min_score <= 1.0:
+            raise ValueError("post-process min_score=%r: None (the image's det_threshold) or in [0, 1]" % min_score)
+    if vote is not None:
+        vote = number("vote_iou", vote)
+        if not 0.0 < vote <= 1.0:
+            raise ValueError("post-process vote_iou=%r: None (no voting) or in (0, 1]" % vote)
+    return (mode, nt, sigma, min_score, vote)
+
+
+def _det_post_args(post):
+    mode, nt, sigma, min_score, vote = det_post_option(post)
+    return nt, (DET_POST_MODES.index(mode), sigma, -1.0 if min_score is None else min_score, 0.0 if vote is None else vote)
+
+
+def detections_post(rois, n_rois, out_cls, out_reg, roi_batch, bg_idx, det_threshold, stride, resize_ratio, post=None):
+    """``detections`` under the post-process option ``post`` (``det_post_option``; its nms_thresh is the NMS threshold): soft-NMS and box
+    voting on the device, the same outputs (frcnn_detections_post).  ``det_prob`` is the decayed score in the soft modes."""
+    _require_gpu()
+    nt, extra = _det_post_args(post)
+    rows, C = out_cls.shape
+    packed = torch.empty(4 + 7 * rows, dtype=torch.int32, device="cuda")
+    n_dets, det_bbox, det_cls, det_prob, det_roi = split_detections(packed, rows)
+    _lib.call("frcnn_detections_post", _p(rois), _p(n_rois), rows, _p(out_cls.contiguous()), _p(out_reg.contiguous()), C, int(bg_idx),
+              float(det_threshold), float(stride), float(resize_ratio), nt,
+              _p(det_cls), _p(det_prob), _p(det_bbox), _p(det_roi), _p(n_dets), *extra, _stream())
+    return {"det_cls": det_cls, "det_prob": det_prob, "det_bbox": det_bbox, "det_roi": det_roi, "n_dets": n_dets, "det_packed": packed}
+
+
+def detections_post_dyn(rois, n_rois, out_cls, out_reg, roi_batch, bg_idx, stride, dyn, post=None):
+    """``detections_dyn`` under the post-process option ``post`` (frcnn_detections_post_dyn): a min_score of None is ``dyn[1]``."""
+    _require_gpu()
+    nt, extra = _det_post_args(post)
+    rows, C = out_cls.shape
+    assert dyn.dtype == torch.float64 and dyn.numel() >= 2 and dyn.is_cuda
+    packed = torch.empty(4 + 7 * rows, dtype=torch.int32, device="cuda")
+    n_dets, det_bbox, det_cls, det_prob, det_roi = split_detections(packed, rows)
+    _lib.call("frcnn_detections_post_dyn", _p(rois), _p(n_rois), int(roi_batch), rows, _p(out_cls.contiguous()), _p(out_reg.contiguous()),
+              C, int(bg_idx), float(stride), nt, dyn.data_ptr(),
+              _p(det_cls), _p(det_prob), _p(det_bbox), _p(det_roi), _p(packed), *extra, _stream())
+    return {"det_cls": det_cls, "det_prob": det_prob, "det_bbox": det_bbox, "det_roi": det_roi, "n_dets": n_dets, "det_packed": packed}
+
+
 # ----------------------------------------------------------------------------- annotation
 ANNOTATE_SKIP = ("DontCare", "Misc")            # classes the reference's annotate_video.py:33-34 never draws
 ANNOTATE_LABEL_STRIDE = 32                      # bytes per class name in the label table (NUL included)

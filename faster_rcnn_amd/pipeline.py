@@ -31,11 +31,14 @@ class InferencePipeline:
     batch = 1                                               # images per pass (BatchedInferencePipeline: B)
 
     def __init__(self, rpn_model, det_model, anchor_dims, stride=16, pre_nms_top_n=8000, max_proposals=300,
-                 roi_batch=64, pad_to_batch=False, bg_idx=None, det_threshold=0.0):
+                 roi_batch=64, pad_to_batch=False, bg_idx=None, det_threshold=0.0, post=None):
         self.rpn, self.det = rpn_model, det_model
         self.anchor_dims = np.asarray(anchor_dims)
         self.anchor_conv = self.anchor_dims // stride
-        self.stride, self.pre, self.post = stride, pre_nms_top_n, max_proposals
+        self.stride, self.pre, self.max_proposals = stride, pre_nms_top_n, max_proposals
+        # the post-process option (ops.det_post_option: soft-NMS / box voting, DESIGN §8 "Post-process rule"); None = the reference's
+        # rule through frcnn_detections(_dyn), exactly as before the option existed
+        self.post = None if post is None else ops.det_post_option(post)
         self.roi_batch = roi_batch
         # strict mode scores the reference's padded duplicates too (voc_dets.py:42-46)
         self.pad_to_batch = bool(pad_to_batch)
@@ -55,7 +58,7 @@ class InferencePipeline:
         scores = cls.reshape(-1)
         order, n = ops.topk_order(scores, valid, self.pre)
         cand, cand_scores = ops.gather_candidates(rois_all, scores, order, n, self.pre)
-        keep, n_keep = ops.nms_sorted(cand, n, 0.7, self.post)
+        keep, n_keep = ops.nms_sorted(cand, n, 0.7, self.max_proposals)
         rois = ops.gather_rois(cand, keep, n_keep, self.roi_batch, self.n_rois, out=rois_out)
         return rois, n_keep, cand, keep
 
@@ -71,14 +74,22 @@ class InferencePipeline:
         out_cls, out_reg = self.det.forward_dev(feat, rois)
         res = {"rpn_cls": cls, "rpn_reg": reg, "feat": feat, "rois": rois, "n_rois": n_keep,
                "cls": out_cls, "reg": out_reg}
-        if dyn is not None:
-            res.update(ops.detections_dyn(rois, n_keep, out_cls, out_reg, self.roi_batch if self.pad_to_batch else 0, self.bg_idx,
-                                          float(self.stride), dyn))
-        else:
-            res.update(ops.detections(rois, n_keep, out_cls, out_reg, self.roi_batch, self.bg_idx, self.det_threshold,
-                                      float(self.stride), float(resize_ratio)))
+        res.update(self._detections(rois, n_keep, out_cls, out_reg, resize_ratio, dyn))
         _pass_status(res, res["det_packed"])
         return res
+
+    def _detections(self, rois, n_keep, out_cls, out_reg, resize_ratio, dyn):
+        """One image's post-process: the reference's rule, or with ``self.post`` set the post-process extension's."""
+        batch = self.roi_batch if self.pad_to_batch else 0
+        if self.post is not None:
+            if dyn is not None:
+                return ops.detections_post_dyn(rois, n_keep, out_cls, out_reg, batch, self.bg_idx, float(self.stride), dyn, self.post)
+            return ops.detections_post(rois, n_keep, out_cls, out_reg, self.roi_batch, self.bg_idx, self.det_threshold,
+                                       float(self.stride), float(resize_ratio), self.post)
+        if dyn is not None:
+            return ops.detections_dyn(rois, n_keep, out_cls, out_reg, batch, self.bg_idx, float(self.stride), dyn)
+        return ops.detections(rois, n_keep, out_cls, out_reg, self.roi_batch, self.bg_idx, self.det_threshold,
+                              float(self.stride), float(resize_ratio))
 
     # ------------------------------------------------------------------ hipGraph
     def capture(self, height, width, resize_ratio=1.0, warmup=2, split_k=True, throughput=False, f32_engine="native"):
@@ -237,12 +248,8 @@ class BatchedInferencePipeline(InferencePipeline):
         out_cls, out_reg = self.det.head.forward_batched(feat, rois, self.n_rois)
         res = {"rpn_cls": cls, "rpn_reg": reg, "feat": feat, "rois": rois.view(B, self.n_rois, 4), "n_rois": n_keep,
                "cls": out_cls.view(B, self.n_rois, -1), "reg": out_reg.view(B, self.n_rois, -1)}
-        if dyn is not None:
-            dets = self._fan_out(lambda i: ops.detections_dyn(rois[i * self.n_rois:(i + 1) * self.n_rois], n_keep[i], res["cls"][i], res["reg"][i],
-                                                              self.roi_batch if self.pad_to_batch else 0, self.bg_idx, float(self.stride), dyn[i]))
-        else:
-            dets = self._fan_out(lambda i: ops.detections(rois[i * self.n_rois:(i + 1) * self.n_rois], n_keep[i], res["cls"][i], res["reg"][i], self.roi_batch,
-                                                          self.bg_idx, self.det_threshold, float(self.stride), float(resize_ratio)))
+        dets = self._fan_out(lambda i: self._detections(rois[i * self.n_rois:(i + 1) * self.n_rois], n_keep[i], res["cls"][i], res["reg"][i],
+                                                        resize_ratio, None if dyn is None else dyn[i]))
         for k in dets[0]:
             res[k] = [d[k] for d in dets]
         _pass_status(res, res["det_packed"][0])

@@ -45,16 +45,17 @@ def _pad_rois(rois, num_rois):
 
 
 def get_dets(training_manager, detector, image, resize_ratio, num_rois=64, stride=16,
-             det_threshold=DEFAULT_DET_THRESHOLD):
-    eng = entry.for_models(training_manager, detector, num_rois, stride, in_flight=1) if FAST_ENTRY else None
+             det_threshold=DEFAULT_DET_THRESHOLD, post=None):
+    """``post``: the post-process option (ops.det_post_option: soft-NMS / box voting); None = the reference's rule."""
+    eng = entry.for_models(training_manager, detector, num_rois, stride, in_flight=1, post=post) if FAST_ENTRY else None
     if eng is not None:
         num_boxes, dets = eng.collect(eng.submit(image, resize_ratio, det_threshold))
         print("num rois: {}".format(num_boxes))
         return dets
-    return _get_dets_eager(training_manager, detector, image, resize_ratio, num_rois, stride, det_threshold)
+    return _get_dets_eager(training_manager, detector, image, resize_ratio, num_rois, stride, det_threshold, post)
 
 
-def _get_dets_eager(training_manager, detector, image, resize_ratio, num_rois, stride, det_threshold):
+def _get_dets_eager(training_manager, detector, image, resize_ratio, num_rois, stride, det_threshold, post=None):
     conv_out, rois = training_manager.get_det_inputs(image)
     class_mapping = training_manager.class_mapping
     rev_class_mapping = dict((v, k) for k, v in class_mapping.items())
@@ -75,7 +76,10 @@ def _get_dets_eager(training_manager, detector, image, resize_ratio, num_rois, s
         out_cls = torch.from_numpy(np.concatenate(cls_parts).astype(np.float32)).cuda()
         out_reg = torch.from_numpy(np.concatenate(reg_parts).astype(np.float32)).cuda()
     n_rows = torch.tensor([len(padded)], dtype=torch.int32, device="cuda")
-    res = ops.detections(rois_d, n_rows, out_cls, out_reg, num_rois, class_mapping["bg"], det_threshold, stride, resize_ratio)
+    if post is not None:
+        res = ops.detections_post(rois_d, n_rows, out_cls, out_reg, num_rois, class_mapping["bg"], det_threshold, stride, resize_ratio, post)
+    else:
+        res = ops.detections(rois_d, n_rows, out_cls, out_reg, num_rois, class_mapping["bg"], det_threshold, stride, resize_ratio)
     n_dets, bbox, cls, prob, _ = ops.split_detections(res["det_packed"].cpu())      # one copy for all five outputs
     nd = int(n_dets.item())
     det_cls, det_prob, det_bbox = cls.numpy()[:nd], prob.numpy()[:nd], bbox.numpy()[:nd]
@@ -83,7 +87,7 @@ def _get_dets_eager(training_manager, detector, image, resize_ratio, num_rois, s
             for i in range(nd)]
 
 
-def get_dets_by_cls(training_manager, detector, resized_ratios, images, stride=16, det_threshold=DEFAULT_DET_THRESHOLD):
+def get_dets_by_cls(training_manager, detector, resized_ratios, images, stride=16, det_threshold=DEFAULT_DET_THRESHOLD, post=None):
     """voc_dets.py:91-111.  On the captured path the images are pipelined: up to ``entry.default_in_flight()`` are enqueued
     (own HIP stream each) before the oldest one's detections are read, and results are folded into the dict in list order,
     so the dict -- keys, per-image lists, their order -- is the one the reference's one-by-one loop builds."""
@@ -97,11 +101,11 @@ def get_dets_by_cls(training_manager, detector, resized_ratios, images, stride=1
     eng = None
     if FAST_ENTRY:
         dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
-        eng = entry.for_models(training_manager, detector, 64, stride, in_flight=entry.default_in_flight(dtype))
+        eng = entry.for_models(training_manager, detector, 64, stride, in_flight=entry.default_in_flight(dtype), post=post)
     if eng is None:
         for image, resized_ratio in zip(images, resized_ratios):
             start_time = timeit.default_timer()
-            dets = get_dets(training_manager, detector, image, resized_ratio, stride=stride, det_threshold=det_threshold)
+            dets = get_dets(training_manager, detector, image, resized_ratio, stride=stride, det_threshold=det_threshold, post=post)
             fold(image, dets, start_time)
         return dets_by_cls
     return _get_dets_by_cls_captured(eng, training_manager, detector, resized_ratios, images, stride, det_threshold, fold, dets_by_cls)
@@ -177,7 +181,9 @@ def _get_dets_by_cls_captured(eng, training_manager, detector, resized_ratios, i
             for pos, pixels, start_time in group:            # a rare geometry: the eager sequence (the host waits for it; passes in flight keep running)
                 said = io.StringIO()
                 with contextlib.redirect_stdout(said):       # its "num rois" line is printed when the image's turn in the LIST comes
-                    dets = _get_dets_eager(training_manager, detector, images[pos], resized_ratios[pos], eng.num_rois, stride, det_threshold)
+                    # (the option only when the engine has one: callers and tests that replace _get_dets_eager keep its seven arguments)
+                    dets = _get_dets_eager(training_manager, detector, images[pos], resized_ratios[pos], eng.num_rois, stride, det_threshold,
+                                           *(() if getattr(eng, "post", None) is None else (eng.post,)))
                 line = said.getvalue().strip().splitlines()
                 done[pos] = (line[0][len("num rois: "):] if line and line[0].startswith("num rois: ") else None, dets, start_time)
             fold_ready()
@@ -289,16 +295,19 @@ def build_parser():
                         "FRCNN_ENTRY_JPEG_DECODER, else host")
     p.add_argument("--dtype", dest="dtype", choices=("f32", "bf16"), default="f32",
                    help="precision the networks are served in: bf16 = the bf16 conv path on the matrix cores (the reference has no such flag: it runs fp32 only)")
+    from .args_util import add_post_arguments
+    add_post_arguments(p)
     return p
 
 
 def main(argv=None):
     """voc_dets.py:161-192: load the two models, resize the image set, detect, write the per-class files."""
     from . import resnet, vgg
-    from .args_util import anchor_scales_from_str, base_paths_to_imgs, resize_dims_from_str
+    from .args_util import anchor_scales_from_str, base_paths_to_imgs, post_from_args, resize_dims_from_str
     from .data.voc_data_helpers import KITTI_CLASS_MAPPING, VOC_CLASS_MAPPING
     from .util import get_anchors, resize_imgs
     args = build_parser().parse_args(argv)
+    post = post_from_args(args)                           # (ValueError with the reason, as annotate_video: before any model is loaded)
     if args.jpeg_decoder is not None:
         from . import entry
         entry.set_jpeg_decoder(args.jpeg_decoder)
@@ -321,7 +330,7 @@ def main(argv=None):
     manager = DetTrainingManager(rpn_model=model_rpn, class_mapping=class_mapping, preprocess_func=preprocess, anchor_dims=anchors)
     resize_min, resize_max = resize_dims_from_str(args.resize_dims)
     processed_imgs, resized_ratios = resize_imgs(test_imgs, min_size=resize_min, max_size=resize_max)
-    dets = get_dets_by_cls(manager, model_det, resized_ratios, processed_imgs, stride=stride, det_threshold=float(args.det_threshold))
+    dets = get_dets_by_cls(manager, model_det, resized_ratios, processed_imgs, stride=stride, det_threshold=float(args.det_threshold), post=post)
     write_dets(dets, args.out_dir)
     return dets
 

@@ -32,7 +32,7 @@ without and with ``--detect_every 4``.  ``--track_backtrack`` (``run_track_backt
 ``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
 look-back call of one pass alone.  ``--track_scene_cut`` (``run_track_scene_cut``) runs the ``--track --track_motion 8`` leg without and with
 ``--track_scene_cut`` at its default.  ``--track_trails`` (``run_track_trails``) runs the same leg without and with ``--track_trails`` at its
-defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.
+defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
@@ -670,6 +670,49 @@ def run_track_reid(name, cfg, n_frames, reps, content="noise"):
     return res
 
 
+POST_LEG = ("soft_gaussian", None, None, None, 0.5)        # --nms soft_gaussian --box_vote, everything else at its (provisional) default
+
+
+def run_post(name, cfg, n_frames, reps, content="noise"):
+    """``--post``: what soft-NMS and box voting cost inside the passes.  One pair of legs in ONE session, alternating inside every
+    repetition: the frames through in-memory annotating passes (leg (b) of ``run_pair``) on the engine without the option and on the
+    engine with ``post=POST_LEG`` (an engine of its own: DESIGN §8 "Post-process rule").  Noise frames give about 300 detections a frame,
+    the worst case for the pick loop.  Reports frames/s of each (medians), without / with, and the detections a frame of each leg has."""
+    import numpy as np
+    from faster_rcnn_amd import entry, ops, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    in_flight = entry.default_in_flight(cfg["dtype"])
+    engs = {"plain": entry.for_models(mgr, det, 64, 16, in_flight=in_flight), "post": entry.for_models(mgr, det, 64, 16, in_flight=in_flight, post=POST_LEG)}
+    assert engs["plain"] is not engs["post"] and engs["plain"].post is None
+    legs = {k: (lambda e=e: annotate_in_memory(e, resized, ratios)) for k, e in engs.items()}
+    times = {k: [] for k in legs}
+    with contextlib.redirect_stdout(io.StringIO()):
+        for fn in legs.values():                                    # warm-up: captures
+            fn()
+        for _ in range(reps):
+            for k, fn in legs.items():
+                t0 = time.perf_counter()
+                fn()
+                times[k].append(time.perf_counter() - t0)
+    B = engs["plain"].batch
+    dets = {k: [len(r[1]) for r in e.collect_batch(e.submit_batch(resized[:B], ratios[:B], 0.0, [e.host_pixels(r) for r in resized[:B]], batch=B,
+                                                                  annotate=True))] for k, e in engs.items()}
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "post": dict(zip(ops.DET_POST_FIELDS, engs["post"].post)), "images_per_pass": B, "in_flight": in_flight,
+           "detections_per_frame": {k: round(float(np.mean(v)), 1) for k, v in dets.items()}}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["post_over_plain"] = round(statistics.median(times["plain"]) / statistics.median(times["post"]), 3)
+    res["ms_per_frame_added"] = round(1e3 * (statistics.median(times["post"]) - statistics.median(times["plain"])) / n_frames, 4)
+    return res
+
+
 def run_count_line(name, cfg, n_frames, reps, content="noise"):
     """``--count_line``: what counting costs on top of ``--track --track_motion 8``.  One pair of legs in ONE session, alternating inside
     every repetition: ``run_track_motion``'s ``track_motion`` leg without and with ``count`` = two lines (a horizontal and a vertical one
@@ -1041,6 +1084,8 @@ def main():
     ap.add_argument("--track_reid", action="store_true", help="instead of the legs above: the --track --track_motion 8 leg without and "
                                                               "with --track_reid at its defaults, alternating in one session (also as "
                                                               "--track --track_reid)")
+    ap.add_argument("--post", action="store_true", help="instead of the legs above: in-memory annotating passes without and with --nms "
+                                                        "soft_gaussian --box_vote (the post-process option), alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -1049,6 +1094,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.post:
+            out[name] = run_post(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.track_reid:
             out[name] = run_track_reid(name, PAIRS[name], args.frames, args.reps, args.content)
