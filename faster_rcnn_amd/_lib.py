@@ -560,6 +560,13 @@ DETECT_POST_SIGNATURES = {
 DETECT_POST_MODES = ("hard", "soft_linear", "soft_gaussian")
 DETECT_POST_DEFAULTS = (0.5, 0.5, 0.5)
 
+SCALE_VERSION = 1               # include/ext/frcnn_hip_scale.h FRCNN_SCALE_VERSION
+SCALE_SIGNATURES = {
+    "frcnn_scale_version": (I, []),
+    "frcnn_downscale_u8": (I, [P, ctypes.c_longlong, I, P, I, I, P, ctypes.c_longlong, I, I, P]),
+}
+SCALE_MAX_RATIO = 16            # ... FRCNN_SCALE_MAX_RATIO: a source side is at most this many times the output's
+
 TRACK_LOOKBACK_VERSION = 1      # include/ext/frcnn_hip_track_lookback.h FRCNN_TRACK_LOOKBACK_VERSION
 TRACK_LOOKBACK_SIGNATURES = {
     "frcnn_track_lookback_version": (I, []),
@@ -806,6 +813,15 @@ def load():
     if lib.frcnn_detect_post_version() != DETECT_POST_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_detect_post_version()} of the post-process extension, this binding "
                          f"{DETECT_POST_VERSION} (include/ext/frcnn_hip_detect_post.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in SCALE_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_scale.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_scale_version() != SCALE_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_scale_version()} of the scale extension, this binding "
+                         f"{SCALE_VERSION} (include/ext/frcnn_hip_scale.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -136,6 +136,7 @@ eager path continue it as one-frame calls (``reset_tracks`` empties it).  A ``--
 import collections
 import os
 import pathlib
+import re
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -327,7 +328,7 @@ def _eager_heat_state(class_mapping, h, w):
 
 
 def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
-               track_trails=None, rgb=False, heatmap=None, count=None, zone=None, remove=None, track_reid=None):
+               track_trails=None, rgb=False, heatmap=None, count=None, zone=None, remove=None, track_reid=None, out_size=None):
     """The editing chain over ONE frame and its host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is edited in
     place, by a one-frame ``frame_edit.EditChain`` -- its docstring states the calls and their order -- on this class mapping's eager
     states (``reset_tracks``, ``reset_heat`` and ``reset_counts`` empty them); ``rgb``: the frame's channel order (False: B, G, R).
@@ -344,8 +345,11 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     ``remove`` = (classes, S, T, M): the frame teaches this class mapping's plate state for its size and channel order, and the boxes of
     those classes are painted out with it (``reset_plate`` empties it); a frame without detections teaches it too.
     ``track_reid`` = (pct, keep) (with ``track``): the ids are those of the re-identify rule, and ``info`` receives "reid": [(pid, tid,
-    cls, distance, gap)]."""
+    cls, distance, gap)].
+    ``out_size`` = ("size", W, H) or ("scale", N): the LAST step (DESIGN §8 "Scale rule", ops.downscale_u8): the edited frame scaled down
+    on the device is what is returned, a new (H, W, 3) array; ``frame`` is edited in place as without it."""
     import torch
+    scaled_hw = None if out_size is None else ops.scale_option(out_size, frame.shape[:2])
     track_reid = _track_reid(track_reid, track)
     track_trails = _track_trails(track_trails, track, draw)
     heatmap = _heatmap(heatmap)
@@ -380,6 +384,8 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
         if info is not None and track_reid is not None:
             info["reid"] = ops.track_reid_events(chain.reid_lists[0].cpu().numpy())
         frame[...] = dev.cpu().numpy()
+    if scaled_hw is not None:
+        return ops.downscale_u8(torch.from_numpy(np.ascontiguousarray(frame)).cuda(), *scaled_hw).cpu().numpy()
     return frame
 
 
@@ -1152,7 +1158,7 @@ def _print_drawn(dets, width, height):
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
                         track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, track_reid=None,
-                        reid_out=None, post=None):
+                        reid_out=None, post=None, out_size=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
@@ -1179,8 +1185,13 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     ``frame,id,tracker_id,cls,distance,gap``.
     ``post``: the post-process option (``ops.det_post_option``: soft-NMS / box voting, DESIGN §8 "Post-process rule") -- which boxes the
     detector reports, in front of everything above; the engine with the option keeps editing states of its own (``reset_tracks(...,
-    post=)``).  None: every byte and line is what it was."""
+    post=)``).  None: every byte and line is what it was.
+    ``out_size`` = ("size", W, H) or ("scale", N): the annotated frame is scaled down on the device behind every edit (DESIGN §8 "Scale
+    rule") and the scaled frame, a new (H, W, 3) array, is returned in ``frame``'s place; the dets, the printed lines and every file
+    written stay in the coordinates of ``frame``.  ValueError for a target the rule refuses for this frame."""
     post = None if post is None else ops.det_post_option(post)
+    if out_size is not None:
+        scaled_size(out_size, frame_no, frame.shape[1], frame.shape[0])
     track_reid = _track_reid(track_reid, track)
     if reid_out is not None and track_reid is None:
         raise ValueError("reid_out is where the re-identifications are written: it needs track_reid=(pct, keep)")
@@ -1227,16 +1238,21 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         num_rois, dets, out, *more = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], DET_THRESHOLD, [pixels],
                                                                         batch=1, annotate=True, redact=redact, draw=draw,
                                                                         **({} if track is None else {"track": track}), **motion,
-                                                                        **({} if heatmap is None else {"heat": heatmap})))[0]
+                                                                        **({} if heatmap is None else {"heat": heatmap}),
+                                                                        **({} if out_size is None else {"out_size": out_size})))[0]
         info = more[0] if more else info                          # (a ``track_scene_cut`` pass: the frame's marks behind its payload)
         if info.get("scene_cut"):
             print("scene cut: {}".format(frame_no))
         _print_reid(frame_no, info.get("reid", ()))
         print("num rois: {}".format(num_rois))
-        frame[...] = out
+        if out_size is None:
+            frame[...] = out
+        else:
+            frame = out
     else:
         dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=DET_THRESHOLD, post=post)
-        draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, info=info, heatmap=heatmap, **motion)
+        frame = draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, info=info, heatmap=heatmap, out_size=out_size,
+                           **motion)
         if info.get("scene_cut"):
             print("scene cut: {}".format(frame_no))
         _print_reid(frame_no, info.get("reid", ()))
@@ -1486,17 +1502,19 @@ class _Sink:
         self._pool.shutdown(wait=True)
 
 
-def _y4m_sink(writer, video_chroma=None):
+def _y4m_sink(writer, video_chroma=None, out_size=None):
     """One YUV4MPEG2 stream through a ``y4m.Y4mWriter``: every frame is converted to the writer's chroma mode and range inside its pass
-    and written by ONE thread, so in stream order; every input frame must have the writer's size."""
+    and written by ONE thread, so in stream order; every input frame must have the writer's size -- with ``out_size`` its SCALED size
+    must be the writer's."""
     import torch
     if video_chroma is not None and video_chroma != writer.chroma:
         raise ValueError("video_chroma=%r, the writer's stream is C%s" % (video_chroma, writer.chroma))
 
     def check(label, frame):
-        if (frame.width, frame.height) != (writer.w, writer.h):
-            raise ValueError("%s is %dx%d, the output stream's frames are %dx%d: one video stream holds frames of one size"
-                             % (label, frame.width, frame.height, writer.w, writer.h))
+        size = (frame.width, frame.height) if out_size is None else scaled_size(out_size, label, frame.width, frame.height)
+        if size != (writer.w, writer.h):
+            raise ValueError("%s is %dx%d%s, the output stream's frames are %dx%d: one video stream holds frames of one size"
+                             % (label, frame.width, frame.height, "" if out_size is None else " (scaled: %dx%d)" % size, writer.w, writer.h))
 
     record = lambda bgr: ops.y4m_encode_u8(torch.from_numpy(bgr).cuda(), writer.chroma, writer.range, bgr=True).cpu().numpy().tobytes()
     return _Sink(1, dict(encode="y4m", y4m=(writer.chroma, writer.range)), lambda pos, out: writer.write(out),
@@ -1649,7 +1667,7 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
               track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None,
-              plate_out=None, track_reid=None, reid_out=None, post=None):
+              plate_out=None, track_reid=None, reid_out=None, post=None, out_size=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
@@ -1677,8 +1695,18 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     if track_reid is not None and (track_lookback is not None or track_backtrack is not None):
         raise ValueError("track_reid=%r together with track_lookback= / track_backtrack= is not supported: the window of a delayed pass "
                          "holds the tracker's own ids" % (track_reid,))
+    out_size = None if out_size is None else ops.scale_form(out_size)      # (refused here, in front of any capture)
+    if out_size is not None:
+        motion["out_size"] = out_size
     counts_log = zones_log = reid_log = None
     sink = make_sink()
+    if out_size is not None:                              # a frame the target does not fit is refused by name, on both paths
+        sink_check = sink.check
+
+        def check(label, frame):
+            scaled_size(out_size, label, frame.width, frame.height)
+            sink_check(label, frame)
+        sink.check = check
     try:
         dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
         eng = _engine(training_manager, detector, entry.default_in_flight(dtype), post)
@@ -1718,6 +1746,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             kwargs = dict(sink.kwargs, annotate=True, **tracking)
             if redact is not None or not draw:            # (else the passes, and their keys, are the ones without the arguments)
                 kwargs.update(redact=redact, draw=draw)
+            if out_size is not None:
+                kwargs.update(out_size=out_size)
             mapping = training_manager.class_mapping
 
             def prepare(label, frame):                    # (read-ahead thread) -> (label, frame, resized, ratio, pixels)
@@ -1776,16 +1806,17 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
                     track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
-                    counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None, reid_out=None, post=None):
+                    counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None, reid_out=None, post=None,
+                    out_size=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out`` / ``remove`` / ``plate_out`` / ``track_reid`` / ``reid_out`` / ``post``: as ``annotate_images``."""
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out`` / ``remove`` / ``plate_out`` / ``track_reid`` / ``reid_out`` / ``post`` / ``out_size``: as ``annotate_images`` (a ``Y4mWriter``'s size is then the SCALED size).  """
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
     if isinstance(writer_or_out_dir, y4m.Y4mWriter):
-        make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma)
+        make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma, out_size)
     else:
         make_sink = lambda: _file_sink(writer_or_out_dir, None, png_encoder, png_compress, frame_format, jpeg_encoder, jpeg_quality, jpeg_subsampling,
                                       jpeg_huffman)
@@ -1793,7 +1824,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
               detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
               heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out, remove=remove,
-              plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post)
+              plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
@@ -1801,7 +1832,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
                     heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None,
-                    reid_out=None, post=None):
+                    reid_out=None, post=None, out_size=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1859,7 +1890,13 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     ``post``: the post-process option as ``args_util.post_from_args`` returns it (``ops.det_post_option``: mode, nms_thresh, sigma,
     min_score, vote_iou) -- soft-NMS and box voting inside the captured passes (DESIGN §8 "Post-process rule"), on the eager path through
     ``ops.detections_post``: which boxes every frame reports, with decayed scores in the soft modes; everything above then works on those
-    boxes.  The passes belong to an engine of their own.  None: no pass, engine key, printed line or output byte changes."""
+    boxes.  The passes belong to an engine of their own.  None: no pass, engine key, printed line or output byte changes.
+    ``out_size``: ("size", W, H) or ("scale", N) as ``out_size_from_args`` returns it -- every frame is scaled DOWN on the device as the
+    last step of its pass, behind every edit and in front of whichever encoder writes it (DESIGN §8 "Scale rule": the exact area mean, in
+    integers; labels shrink with the picture): the device encoders encode, and the read-back copies, the smaller frame; the host encoders
+    simply receive it.  ("scale", N) applies per frame size in a list of mixed sizes; ("size", W, H) is refused with the name of the
+    first frame that is smaller than it (or more than 16 times its size along a side).  The printed lines, ``tracks_out``, ``counts_out``
+    and ``zones_out`` stay in SOURCE coordinates.  None: no pass, key, printed line or output byte changes."""
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
@@ -1873,7 +1910,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
               track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out,
-              remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post)
+              remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size)
 
 
 def build_parser():
@@ -1928,6 +1965,12 @@ def build_parser():
                         "range and the F / A tags are the input stream's (a frame directory: limited range, F25:1, and one frame size)")
     p.add_argument("--video_chroma", dest="video_chroma", choices=VIDEO_CHROMAS, default=None,
                    help="chroma of the stream --out_video writes: 420jpeg (the default) or 444")
+    p.add_argument("--out_size", dest="out_size", default=None, metavar="WxH",
+                   help="scale every annotated frame DOWN to W x H on the device, behind every edit and in front of the encoder (an exact "
+                        "area mean; labels shrink with the picture); at most the frame's size and at least 1/16 of it along each side; "
+                        "boxes printed and written to --tracks_out / --counts_out / --zones_out stay in source coordinates")
+    p.add_argument("--out_scale", dest="out_scale", type=int, default=None, metavar="N",
+                   help="as --out_size with both sides divided by N (2..16) and rounded up, per frame size; not together with --out_size")
     p.add_argument("--redact", dest="redact", default=None, metavar="CLASSES",
                    help="hide the detected objects of these classes: comma-separated names of the active class mapping, or all; a box that "
                         "crosses the frame's border is hidden too")
@@ -2066,6 +2109,32 @@ def video_options(args):
     return is_stream_input(args.input_dir), out_video, args.video_chroma or "420jpeg"
 
 
+def out_size_from_args(args):
+    """(host only) The output scale the command line asks for -> ("size", W, H) for --out_size WxH, ("scale", N) for --out_scale N, as
+    ``submit_batch(out_size=...)`` takes it, or None.  ValueError for both flags together, a size that is not WxH, a side of 0 and a
+    divisor outside 2..16."""
+    if args.out_size is not None and args.out_scale is not None:
+        raise ValueError("--out_size=%s and --out_scale=%s both state the output size: give one" % (args.out_size, args.out_scale))
+    if args.out_scale is not None:
+        return ops.scale_form(("scale", args.out_scale))
+    if args.out_size is None:
+        return None
+    m = re.fullmatch(r"\s*(\d+)\s*[xX]\s*(\d+)\s*", args.out_size)
+    if not m:
+        raise ValueError("--out_size=%s: WxH, two positive integers" % args.out_size)
+    return ops.scale_form(("size", int(m.group(1)), int(m.group(2))))
+
+
+def scaled_size(out_size, label, width, height):
+    """(host only) The (width, height) frame ``label`` of (width, height) has behind the scale step; ValueError that names the frame
+    when the rule refuses the target for it."""
+    try:
+        H, W = ops.scale_option(out_size, (height, width))
+    except ValueError as e:
+        raise ValueError("%s (%dx%d): %s" % (label, width, height, e)) from None
+    return W, H
+
+
 def _frame_size(path):
     from PIL import Image as PilImage
     with PilImage.open(path) as im:
@@ -2148,6 +2217,9 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     post = post_from_args(args)                           # (before any model is loaded: dependent options are refused by name)
     if post is not None:
         tracking["post"] = post
+    out_size = out_size_from_args(args)                   # (before any model is loaded)
+    if out_size is not None:
+        tracking["out_size"] = out_size
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)
@@ -2173,6 +2245,8 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
             (w, h), yrange, tags = _frame_size(os.path.join(args.input_dir, names[0])), "limited", {"F": "25:1"}
         if out_video is not None:
             fout = video_out if video_out is not None else stack.enter_context(open(out_video, "wb"))
+            if out_size is not None:                      # the header carries the scaled size
+                w, h = scaled_size(out_size, "<stdin>" if args.input_dir == "-" else args.input_dir, w, h)
             sink = y4m.Y4mWriter(fout, w, h, video_chroma, yrange, {k: tags[k] for k in ("F", "A") if k in tags})
             annotate_stream(manager, detector, reader, sink, resize_min, resize_max, redact=redact, draw=draw, **tracking)
         else:

@@ -319,11 +319,12 @@ class PassSpec:
     zone: object = None                                  # (zones, classes, W, anchor), ops.zone_option's form: frame_edit.EditChain reads it
     remove: object = None                                # (classes, S, T, M), ops.plate_option's form
     track_reid: object = None                            # (pct, keep), ops.track_reid_option's form
+    out_size: object = None                              # ("size", W, H) or ("scale", N), ops.scale_form's form: the scale step's target
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
                 track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                track_trails=None, heat=None, count=None, zone=None, remove=None, track_reid=None):
+                track_trails=None, heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -411,6 +412,13 @@ class PassSpec:
             track_reid = engine.track_reid_option(track_reid)
         if redact is not None:
             redact = engine.redact_option(redact)
+        if out_size is not None:
+            if not annotate:
+                raise FrcnnError("submit_batch: out_size= scales the frame an ANNOTATING pass returns: pass annotate=True")
+            try:
+                out_size = ops.scale_form(out_size)
+            except ValueError as e:
+                raise FrcnnError("submit_batch: %s" % e) from None
         jpeg_mode, y4m_mode = JPEG_MODE, Y4M_MODE
         if encode == Y4M_ENCODE:
             y4m_mode = Y4M_MODE if y4m is None else tuple(y4m)
@@ -444,7 +452,28 @@ class PassSpec:
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
                    track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove,
-                   track_reid=track_reid)
+                   track_reid=track_reid, out_size=out_size)
+
+    def out_hw(self, hw):
+        """The size (H, W) of the frames a pass over source frames of ``hw`` = (h, w) encodes and returns: the scale step's target, or
+        ``hw`` itself without ``out_size``.  FrcnnError, with the reason, for a target the scale rule refuses for this frame size and for
+        one the pass's encoder refuses."""
+        if self.out_size is None:
+            return int(hw[0]), int(hw[1])
+        try:
+            H, W = ops.scale_option(self.out_size, hw)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: %s" % e) from None
+        try:                                             # (the encoder's own word on the size it would be handed)
+            if self.encode == JPEG_ENCODE:
+                ops.jpeg_bound(H, W, *self.jpeg_mode)
+            elif self.encode == Y4M_ENCODE:
+                ops.y4m_frame_bytes(H, W, self.y4m_mode[0])
+            elif self.encode:
+                ops.png_bound(H, W, PNG_ENCODES[self.encode])
+        except FrcnnError as e:
+            raise FrcnnError("submit_batch: out_size %dx%d with encode=\"%s\": %s" % (W, H, self.encode, e)) from None
+        return H, W
 
     @property
     def delayed(self):
@@ -490,6 +519,8 @@ class PassSpec:
             key = key + ("remove",) + self.remove
         if self.track_reid is not None:
             key = key + ("track_reid",) + self.track_reid
+        if self.out_size is not None:
+            key = key + ("scale",) + self.out_size
         return key
 
 
@@ -507,7 +538,7 @@ class _Slot:
                  "track", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
                  "track_lookback", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
                  "track_scene_cut", "cuts_pin", "_cuts_raw", "track_trails", "heat", "count", "count_pin", "_count_raw", "zone", "zone_pin", "_zone_raw",
-                 "remove", "track_reid", "reid_pin", "_reid_raw")
+                 "remove", "track_reid", "reid_pin", "_reid_raw", "out_size", "scale_dev", "pix_out")
 
     def __init__(self):
         for name in self.__slots__:
@@ -1024,30 +1055,41 @@ class DetectionEntry:
             out = [chain.lb_frames[i] for i in range(F)] if s.track_lookback else u8
             if s.track_lookback and s.frame_io is not None:         # (raw read-back: the emitted frame, into the slot's pinned segment)
                 s.frame_io = [(out[i].view(-1), s.io_pin[i * seg:i * seg + npix]) for i in range(F)]
+        # the scale step (DESIGN §8 "Scale rule"): the last edit, in front of every encoder.  Each edited frame is scaled into the slot's
+        # scaled area, ``sc_seg`` bytes a frame, and THAT is what the encoders read and a pass without one copies back
+        enc_h, enc_w = s.spec.out_hw((in_h, in_w))
+        enc_pix = enc_h * enc_w * 3
+        if s.out_size:
+            sc_seg = (enc_pix + 15) // 16 * 16
+            s.scale_dev = torch.zeros(F * sc_seg, dtype=torch.uint8, device="cuda")
+            scaled = [s.scale_dev[i * sc_seg:i * sc_seg + enc_pix].view(enc_h, enc_w, 3) for i in range(F)]
+            if s.frame_io is not None:
+                s.frame_io = [(scaled[i].view(-1), s.io_pin[i * seg:i * seg + enc_pix]) for i in range(F)]
+                s.pix_out = [host[i * seg:i * seg + enc_pix].reshape(enc_h, enc_w, 3) for i in range(F)]
         if s.encode == JPEG_ENCODE:
             # a frame's row: [its length, int32 | pad to 16 | the file, at most jpeg_bound bytes].  The bound is 6.5 times the raw frame
             # (every block at its longest), which is device memory only: a replay reads back the row's first ``first_copy`` bytes -- the
             # length, the header and a quarter of the raw frame's size, more than a photograph takes at quality 90 -- and collect_batch
             # fetches the rest of a longer file.
             subsampling, huffman = s.jpeg_mode
-            s.png_bound = ops.jpeg_bound(in_h, in_w, subsampling, huffman)
+            s.png_bound = ops.jpeg_bound(enc_h, enc_w, subsampling, huffman)
             s.png_dev = torch.zeros((F, 16 + (s.png_bound + 15) // 16 * 16), dtype=torch.uint8, device="cuda")
-            s.first_copy = min(16 + ops.jpeg_header_bytes() + npix // 4, 16 + s.png_bound)
-            s.png_ws = torch.empty(ops.jpeg_workspace_bytes(in_h, in_w, subsampling, huffman), dtype=torch.uint8, device="cuda")
+            s.first_copy = min(16 + ops.jpeg_header_bytes() + enc_pix // 4, 16 + s.png_bound)
+            s.png_ws = torch.empty(ops.jpeg_workspace_bytes(enc_h, enc_w, subsampling, huffman), dtype=torch.uint8, device="cuda")
             png_out = [(s.png_dev[i][16:16 + s.png_bound], s.png_dev[i][0:4].view(torch.int32)) for i in range(F)]
         elif s.encode == Y4M_ENCODE:
             # a frame's row: its record [Y | Cb | Cr], ops.y4m_frame_bytes long: the slot's output area is B records back to back
             chroma, yrange = s.y4m_mode
-            s.png_bound = ops.y4m_frame_bytes(in_h, in_w, chroma)
+            s.png_bound = ops.y4m_frame_bytes(enc_h, enc_w, chroma)
             s.png_dev = torch.zeros((F, s.png_bound), dtype=torch.uint8, device="cuda")
         elif s.encode:
             # a frame's row: [the file, at most png_bound bytes | pad to 16 | its length, int32 | pad]: one fixed-size copy brings both back
             # (the bound is 0.5 % over the raw frame).  File-backed frames were uploaded in the decoder's order (host_pixels: flip bit 1).
             compress = PNG_ENCODES[s.encode]
-            s.png_bound = ops.png_bound(in_h, in_w, compress)
+            s.png_bound = ops.png_bound(enc_h, enc_w, compress)
             len_at = (s.png_bound + 15) // 16 * 16
             s.png_dev = torch.zeros((F, len_at + 16), dtype=torch.uint8, device="cuda")
-            s.png_ws = torch.empty(ops.png_workspace_bytes(in_h, in_w, compress), dtype=torch.uint8, device="cuda")     # (the frames of a pass encode one after another)
+            s.png_ws = torch.empty(ops.png_workspace_bytes(enc_h, enc_w, compress), dtype=torch.uint8, device="cuda")     # (the frames of a pass encode one after another)
             png_out = [(s.png_dev[i][:s.png_bound], s.png_dev[i][len_at:len_at + 4].view(torch.int32)) for i in range(F)]
 
         def run():
@@ -1064,17 +1106,22 @@ class DetectionEntry:
                     chain.edit(i, out[i])
                     if s.encode == Y4M_ENCODE:
                         continue                                    # (all B frames in one launch behind the loop)
+                    final = out[i]
+                    if s.out_size:
+                        final = ops.downscale_u8(out[i], enc_h, enc_w, out=scaled[i])
                     if s.encode == JPEG_ENCODE:
-                        ops.jpeg_encode_u8(out[i], quality=s.quality, bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1],
+                        ops.jpeg_encode_u8(final, quality=s.quality, bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1],
                                            workspace=s.png_ws, subsampling=subsampling, huffman=huffman)
                     elif s.encode:
-                        ops.png_encode_u8(out[i], bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1], workspace=s.png_ws,
+                        ops.png_encode_u8(final, bgr=not uploaded_rgb, out=png_out[i][0], out_len=png_out[i][1], workspace=s.png_ws,
                                               compress=compress)
                 if s.encode == Y4M_ENCODE:
-                    if s.track_lookback:
-                        ops.y4m_encode_frames_u8(chain.lb_frames.view(-1), npix, F, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
-                    else:
-                        ops.y4m_encode_frames_u8(s.io_dev, seg, F, in_h, in_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
+                    frames, stride = (chain.lb_frames.view(-1), npix) if s.track_lookback else (s.io_dev, seg)
+                    if s.out_size:                                  # (all F frames scaled in one launch, then encoded in one)
+                        ops.downscale_u8(frames.as_strided((F, in_h, in_w, 3), (stride, 3 * in_w, 3, 1)), enc_h, enc_w,
+                                         out=s.scale_dev.as_strided((F, enc_h, enc_w, 3), (sc_seg, 3 * enc_w, 3, 1)))
+                        frames, stride = s.scale_dev, sc_seg
+                    ops.y4m_encode_frames_u8(frames, stride, F, enc_h, enc_w, chroma, yrange, bgr=not uploaded_rgb, out=s.png_dev)
             return res
         return run
 
@@ -1133,7 +1180,7 @@ class DetectionEntry:
             s.track_lookback, s.track_backtrack = spec.track_lookback or spec.track_backtrack, spec.track_backtrack      # (both: the delayed path is one)
             s.every, s.frames = spec.detect_every, B * (spec.detect_every or 1)
             s.track_scene_cut, s.track_trails, s.heat, s.count = spec.track_scene_cut, spec.track_trails, spec.heat, spec.count
-            s.zone, s.remove, s.track_reid = spec.zone, spec.remove, spec.track_reid
+            s.zone, s.remove, s.track_reid, s.out_size = spec.zone, spec.remove, spec.track_reid, spec.out_size
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -1381,7 +1428,7 @@ class DetectionEntry:
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
                      track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
-                     heat=None, count=None, zone=None, remove=None, track_reid=None):
+                     heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1513,11 +1560,21 @@ class DetectionEntry:
         trailing dict "reid": [(pid, tid, cls, distance, gap)].  Refused by name without ``track``, with ``track_lookback`` /
         ``track_backtrack``, on an engine with a foreign preprocess and for options out of range.  Without it every key and byte is
         what it was.
+        ``out_size`` = ("size", W, H) or ("scale", N) (annotating passes, with every other option; ("scale",) + the option appended LAST,
+        behind ("track_reid", ...); N a divisor 2..16: H = ceil(h / N), W = ceil(w / N)): the scale rule (DESIGN §8 "Scale rule"): each
+        frame, behind ALL its edits -- labels shrink with the picture --, is scaled down to (H, W) by the exact area mean (one
+        ops.downscale_u8 into the slot's scaled area; with encode="y4m" one call over all frames behind the loop), and the scaled frame
+        is what every encoder reads -- its bound and workspace are those of (H, W) -- and what a pass without an encoder copies back:
+        ``collect_batch`` returns the (H, W, 3) frame.  A delayed pass scales the frames it emits.  The dets, the tracked rows and every
+        list stay in SOURCE coordinates.  Refused by name, in front of any capture: without ``annotate``; a target the rule refuses for
+        the pass's frame size (larger than it, less than 1/16 of it along a side, a side of 0); a size the pass's encoder refuses, with
+        the encoder's own reason.  Without it every key and byte is what it was.
         The order of all these steps in a pass is stated once, in ``frame_edit.EditChain``'s docstring."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-                                track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove, track_reid=track_reid)
+                                track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove, track_reid=track_reid,
+                                out_size=out_size)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1535,6 +1592,7 @@ class DetectionEntry:
             assert 1 <= len(images) <= B and len(images) == len(pixels) == len(resize_ratios)
         _, H, W, src, flip = pixels[0]
         spec = spec.sized(self, B)
+        spec.out_hw(src if src is not None else (H, W))            # (refuses a target this frame size or the encoder cannot take)
         if annotate:
             if not self.device_preprocess:
                 raise FrcnnError("annotating passes need the device-side preprocess (a foreign preprocess_func uploads float pixels)")
@@ -1837,7 +1895,7 @@ class DetectionEntry:
                 raise FrcnnError("device PNG encoder: length word %d outside (0, %d]" % (n, s.png_bound))
             return (row[:n].tobytes(),)
         else:
-            return (s.pix_hosts[i].copy(),) if s.annotate else ()
+            return ((s.pix_out or s.pix_hosts)[i].copy(),) if s.annotate else ()
 
     def _collect_lookback(self, ticket):
         """``collect_batch`` of a look-back pass: this submit's num_rois are kept for the pass that will emit its frames, and the results

@@ -186,7 +186,8 @@ class EditChain:
       9. ops.track_trails_draw_u8;
      10. ops.count_draw_u8, unless nothing is drawn;
      11. ops.annotate_u8: the live rows with their ids; with the no-draw tables when nothing is drawn.
-    The encoders follow, at the caller's.
+    With ``out_size`` the scale step follows (12. ops.downscale_u8, DESIGN §8 "Scale rule": the LAST edit, so labels shrink with the
+    picture), then the encoders, both at the caller's: the chain itself works in source coordinates throughout.
 
     ``states``: an ``EditStates``; ``spec``: the normalised options, read by ``entry.PassSpec``'s field names; F source frames of ``hw``
     = (h, w), of which the detector saw every K-th; ``rgb``: the frames' bytes are R, G, B (False: B, G, R)."""

@@ -2310,6 +2310,77 @@ def plate_fill_u8(frame, state, det_packed, table, margin=None, keep_unknown=Fal
     return frame
 
 
+# ----------------------------------------------------------------------------- output scale
+SCALE_MAX_RATIO = _lib.SCALE_MAX_RATIO
+
+
+def scale_form(option):
+    """(host only) The output-scale option as it is stated, whatever the frames' size -> ("size", W, H) or ("scale", N) with plain ints.
+    ValueError with the reason: another form, a divisor outside 2..16, a side of 0."""
+    integer = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    try:
+        kind, args = option[0], tuple(option[1:])
+    except (TypeError, IndexError, KeyError):
+        raise ValueError("out_size=%r: (\"size\", W, H) or (\"scale\", N)" % (option,)) from None
+    if kind == "scale" and len(args) == 1 and integer(args[0]):
+        if not 2 <= int(args[0]) <= SCALE_MAX_RATIO:
+            raise ValueError("out_scale=%d: a divisor in 2..%d" % (int(args[0]), SCALE_MAX_RATIO))
+        return ("scale", int(args[0]))
+    if kind == "size" and len(args) == 2 and all(integer(v) for v in args):
+        W, H = int(args[0]), int(args[1])
+        if H < 1 or W < 1:
+            raise ValueError("out_size %dx%d: both sides must be at least 1" % (W, H))
+        return ("size", W, H)
+    raise ValueError("out_size=%r: (\"size\", W, H) or (\"scale\", N)" % (option,))
+
+
+def scale_option(option, hw):
+    """(host only) The output-scale option for source frames of ``hw`` = (h, w) -> the output size (H, W): ``option`` is ("size", W, H) --
+    the size itself, width first as a command line states it -- or ("scale", N), a divisor 2..16: H = ceil(h / N), W = ceil(w / N).
+    ValueError with the reason for anything the scale rule (DESIGN §8 "Scale rule") refuses: a side of 0, a target larger than the source,
+    a source side more than 16 times the target's."""
+    h, w = int(hw[0]), int(hw[1])
+    option = scale_form(option)
+    if option[0] == "scale":
+        N = option[1]
+        H, W = (h + N - 1) // N, (w + N - 1) // N
+    else:
+        W, H = option[1:]
+    if H > h or W > w:
+        raise ValueError("out_size %dx%d is larger than the %dx%d frame: the scale step only scales down" % (W, H, w, h))
+    if h > SCALE_MAX_RATIO * H or w > SCALE_MAX_RATIO * W:
+        raise ValueError("out_size %dx%d is less than 1/%d of the %dx%d frame along a side" % (W, H, SCALE_MAX_RATIO, w, h))
+    return H, W
+
+
+def downscale_u8(frame_or_frames, H, W, out=None, n_frames=None):
+    """The scale rule (DESIGN §8 "Scale rule", frcnn_downscale_u8): an (h, w, 3) uint8 device frame, or (n, h, w, 3) frames whose first
+    stride may be larger than a frame, scaled down to (H, W) by the exact area mean, in integers -> ``out``, an (H, W, 3) or (n, H, W, 3)
+    uint8 device tensor (allocated when None; its first stride too may be larger than a frame).  ``n_frames``: a device int32 word; the
+    frames behind min(max(*n_frames, 0), n) are not written (None: all are).  One launch whatever n is; reads nothing on the host, so the
+    call can be captured in a graph.  Bad arguments raise FrcnnError before anything is launched."""
+    _require_gpu()
+    t = frame_or_frames
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() in (3, 4) and t.shape[-1] == 3):
+        raise _lib.FrcnnError("downscale_u8: frame must be an (h, w, 3) or (n, h, w, 3) uint8 device tensor")
+    single = t.dim() == 3
+    n, h, w = (1 if single else int(t.shape[0])), int(t.shape[-3]), int(t.shape[-2])
+    H, W = int(H), int(W)
+    if out is None:
+        out = torch.empty(((H, W, 3) if single else (n, H, W, 3)), dtype=torch.uint8, device="cuda")
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == ((H, W, 3) if single else (n, H, W, 3))):
+        raise _lib.FrcnnError("downscale_u8: out must be a uint8 device tensor of shape %s" % (((H, W, 3) if single else (n, H, W, 3)),))
+    for name, x in (("frame", t), ("out", out)):                            # (a frame is contiguous; the frames may lie apart)
+        if x.numel() and x.stride()[-3:] != (3 * int(x.shape[-2]), 3, 1):
+            raise _lib.FrcnnError("downscale_u8: every frame of %s must be contiguous" % name)
+    assert n_frames is None or (n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1)
+    src_stride = 3 * h * w if single or n == 1 else int(t.stride(0))
+    dst_stride = 3 * H * W if single or n == 1 else int(out.stride(0))
+    _lib.call("frcnn_downscale_u8", t.data_ptr() if t.numel() else None, src_stride, n, _p(n_frames), h, w,
+              out.data_ptr() if out.numel() else None, dst_stride, H, W, _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- re-identification
 # (smallest, largest, the default) of pct and keep.  The defaults are PROVISIONAL: nobody has measured them on real footage.
 TRACK_REID_PCT, TRACK_REID_KEEP, TRACK_REID_MAX = _lib.TRACK_REID_PCT, _lib.TRACK_REID_KEEP, _lib.TRACK_REID_MAX

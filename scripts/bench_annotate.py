@@ -32,7 +32,7 @@ without and with ``--detect_every 4``.  ``--track_backtrack`` (``run_track_backt
 ``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
 look-back call of one pass alone.  ``--track_scene_cut`` (``run_track_scene_cut``) runs the ``--track --track_motion 8`` leg without and with
 ``--track_scene_cut`` at its default.  ``--track_trails`` (``run_track_trails``) runs the same leg without and with ``--track_trails`` at its
-defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).
+defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--out_scale`` (``run_out_scale``) runs in-memory annotating passes, the PNG-file to PNG-file leg (device encoder, huffman) and y4m to y4m, each without and with ``--out_scale 2``.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
@@ -248,6 +248,73 @@ def run_y4m(name, cfg, n_frames, reps, content="noise"):
     for k, ts in times.items():
         res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
         res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    return res
+
+
+OUT_SCALE_LEG = ("scale", 2)                             # --out_scale 2
+
+
+def run_out_scale(name, cfg, n_frames, reps, content="noise"):
+    """``--out_scale``: what the scale step (DESIGN §8 "Scale rule") costs and saves.  Three pairs of legs in ONE session, each leg without
+    and with ``out_size=("scale", 2)``, all six alternating inside every repetition: (a) annotating passes in memory (``run_pair``'s leg
+    (b): with the option the kernel is added and a quarter of the bytes is copied back), (b) PNG files to PNG files through the device
+    encoder's huffman mode, (c) a YUV4MPEG2 stream to a YUV4MPEG2 stream.  The kernel alone is not separated from the smaller read-back."""
+    import numpy as np
+    import torch
+    from PIL import Image as PilImage
+    from faster_rcnn_amd import annotate_video, entry, ops, shapes, util, y4m
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    h2, w2 = ops.scale_option(OUT_SCALE_LEG, (h, w))
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+    with tempfile.TemporaryDirectory() as tmp:
+        d_in, d_out, clip, clip_out = (os.path.join(tmp, x) for x in ("in", "out", "in.y4m", "out.y4m"))
+        os.makedirs(d_in)
+        names = ["%06d.png" % i for i in range(n_frames)]
+        with open(clip, "wb") as f:
+            writer = y4m.Y4mWriter(f, w, h, "420jpeg", "limited", {"F": "25:1"})
+            for nm, s in zip(names, srcs):
+                PilImage.fromarray(s[:, :, ::-1]).save(os.path.join(d_in, nm), compress_level=1)
+                writer.write(ops.y4m_encode_u8(torch.from_numpy(s).cuda(), "420jpeg", "limited", bgr=True).cpu().numpy().tobytes())
+
+        def y4m_to_y4m(size, **kw):
+            def run():
+                with open(clip, "rb") as fin, open(clip_out, "wb") as fout:
+                    reader = y4m.Y4mReader(fin, name=clip)
+                    sink = y4m.Y4mWriter(fout, size[1], size[0], "420jpeg", reader.plan.range_name, reader.plan.tags)
+                    annotate_video.annotate_stream(mgr, det, reader, sink, *cfg["resize"], **kw)
+            return run
+
+        png = lambda **kw: lambda: annotate_video.annotate_images(mgr, det, d_in, d_out, names, *cfg["resize"], png_encoder="device",
+                                                                  png_compress="huffman", **kw)
+        legs = {"a_in_memory": lambda: annotate_in_memory(eng, resized, ratios),
+                "a_in_memory_scaled": lambda: annotate_in_memory(eng, resized, ratios, out_size=OUT_SCALE_LEG),
+                "b_png_to_png_device_huffman": png(), "b_png_to_png_device_huffman_scaled": png(out_size=OUT_SCALE_LEG),
+                "c_y4m_to_y4m": y4m_to_y4m((h, w)), "c_y4m_to_y4m_scaled": y4m_to_y4m((h2, w2), out_size=OUT_SCALE_LEG)}
+        times, sizes = {k: [] for k in legs}, {}
+        with contextlib.redirect_stdout(io.StringIO()):
+            for fn in legs.values():                                # warm-up: captures
+                fn()
+            for _ in range(reps):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    fn()
+                    times[k].append(time.perf_counter() - t0)
+                    if k.startswith("b_"):
+                        sizes[k] = sum(os.path.getsize(os.path.join(d_out, nm)) for nm in names) // n_frames
+    res = {"frames": n_frames, "frame_hw": [h, w], "scaled_hw": [h2, w2], "out_size": list(OUT_SCALE_LEG), "resize_dims": list(cfg["resize"]),
+           "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content, "images_per_pass": eng.batch, "in_flight": eng.in_flight}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    for k, v in sizes.items():
+        res[k + "_bytes_per_frame"] = v
+    for pair in ("a_in_memory", "b_png_to_png_device_huffman", "c_y4m_to_y4m"):
+        res[pair + "_scaled_over_plain"] = round(statistics.median(times[pair]) / statistics.median(times[pair + "_scaled"]), 3)
     return res
 
 
@@ -1086,6 +1153,9 @@ def main():
                                                               "--track --track_reid)")
     ap.add_argument("--post", action="store_true", help="instead of the legs above: in-memory annotating passes without and with --nms "
                                                         "soft_gaussian --box_vote (the post-process option), alternating in one session")
+    ap.add_argument("--out_scale", action="store_true", help="instead of the legs above: in-memory annotating passes, PNG files to PNG files "
+                                                             "(device encoder, huffman) and y4m to y4m, each without and with --out_scale 2, "
+                                                             "alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -1094,6 +1164,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.out_scale:
+            out[name] = run_out_scale(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.post:
             out[name] = run_post(name, PAIRS[name], args.frames, args.reps, args.content)
