@@ -402,6 +402,14 @@ REDACT_MODES = {"fill": 0, "pixelate": 1, "blur": 2}                            
 # mode -> (smallest size, largest size, the default): FRCNN_REDACT_PIXELATE_MIN / _MAX, FRCNN_REDACT_BLUR_MIN / _MAX; fill takes none (0)
 REDACT_SIZES = {"fill": (0, 0, 0), "pixelate": (2, 64, 16), "blur": (1, 32, 12)}
 
+REDACT_SHAPE_VERSION = 1        # include/ext/frcnn_hip_redact_shape.h FRCNN_REDACT_SHAPE_VERSION
+REDACT_SHAPE_SIGNATURES = {
+    "frcnn_redact_shape_version": (I, []),
+    "frcnn_redact_shaped_u8": (I, [P, I, I, P, P, P, I, P, I, I, I, I, I, I, P, c_size_t, P]),
+}
+REDACT_SHAPES = {"box": 0, "ellipse": 1}                                           # FRCNN_REDACT_SHAPE_BOX / _ELLIPSE
+REDACT_FEATHER = (0, 32)                                                           # 0..FRCNN_REDACT_FEATHER_MAX
+
 TRACK_VERSION = 1               # include/ext/frcnn_hip_track.h FRCNN_TRACK_VERSION
 TRACK_MAX = 128                 # ... FRCNN_TRACK_MAX: slots of a state
 TRACK_MAX_FRAMES = 64           # ... FRCNN_TRACK_MAX_FRAMES: frames of one call
@@ -822,6 +830,15 @@ def load():
     if lib.frcnn_scale_version() != SCALE_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_scale_version()} of the scale extension, this binding "
                          f"{SCALE_VERSION} (include/ext/frcnn_hip_scale.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in REDACT_SHAPE_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_redact_shape.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_redact_shape_version() != REDACT_SHAPE_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_shape_version()} of the shaped-redaction extension, this binding "
+                         f"{REDACT_SHAPE_VERSION} (include/ext/frcnn_hip_redact_shape.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -51,6 +51,14 @@ csrc/redact.hip; the rule is DESIGN §8's).  Unlike the drawing, a box that cros
 are when named.  It runs inside the pass in front of the drawing step, so before every encoder and for every input format.
 ``draw=False`` (``--no_draw``) leaves the boxes and labels out.  The printed lines do not change with either.
 
+``redact_shape=(shape, feather)`` (``--redact_shape {box,ellipse} --redact_feather N``, with ``--redact`` only) shapes what the redaction
+puts on the picture (ops.redact_shaped_u8, csrc/redact_shape.hip; DESIGN §8 "Shape rule"): "ellipse" hides the ellipse inscribed in each
+box grown by the margin -- the box is NOT clipped, so an ellipse across the border stays that of the whole box --, and a feather of N
+pixels (0..32) lets the replacement fade into the scene OUTSIDE the shape: what the hard shape hides stays fully hidden.  Held and
+back-filled boxes are shaped like live ones; the plate of ``--remove``, the tracker, the heat map and the drawn boxes keep their
+rectangles.  It works for file, y4m and stdin input and with every encoder, as the redaction does.  "box" with feather 0 is the default
+and IS the plain redaction: no pass, key, printed line or output byte changes.
+
 ``track=(thr, hold, grow)`` (``--track [--track_iou PCT] [--track_hold N] [--track_grow N]``) joins the detections of consecutive frames
 into tracks on the device (ops.track_update, csrc/track.hip; DESIGN §8 "Tracking rule"): a detection whose box overlaps a track's last
 box of the same class by at least PCT percent IoU (default 30) continues it and is labelled ``cls#id``; a track the detector loses is HELD
@@ -328,7 +336,8 @@ def _eager_heat_state(class_mapping, h, w):
 
 
 def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
-               track_trails=None, rgb=False, heatmap=None, count=None, zone=None, remove=None, track_reid=None, out_size=None):
+               track_trails=None, rgb=False, heatmap=None, count=None, zone=None, remove=None, track_reid=None, out_size=None,
+               redact_shape=None):
     """The editing chain over ONE frame and its host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is edited in
     place, by a one-frame ``frame_edit.EditChain`` -- its docstring states the calls and their order -- on this class mapping's eager
     states (``reset_tracks``, ``reset_heat`` and ``reset_counts`` empty them); ``rgb``: the frame's channel order (False: B, G, R).
@@ -347,8 +356,11 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     ``track_reid`` = (pct, keep) (with ``track``): the ids are those of the re-identify rule, and ``info`` receives "reid": [(pid, tid,
     cls, distance, gap)].
     ``out_size`` = ("size", W, H) or ("scale", N): the LAST step (DESIGN §8 "Scale rule", ops.downscale_u8): the edited frame scaled down
-    on the device is what is returned, a new (H, W, 3) array; ``frame`` is edited in place as without it."""
+    on the device is what is returned, a new (H, W, 3) array; ``frame`` is edited in place as without it.
+    ``redact_shape`` = (shape, feather) (with ``redact``): the redaction hides ellipses and fades out over ``feather`` pixels (DESIGN §8
+    "Shape rule", ops.redact_shaped_u8); ("box", 0) is the call without it."""
     import torch
+    redact_shape = _redact_shape(redact_shape, redact)
     scaled_hw = None if out_size is None else ops.scale_option(out_size, frame.shape[:2])
     track_reid = _track_reid(track_reid, track)
     track_trails = _track_trails(track_trails, track, draw)
@@ -365,7 +377,8 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
             redact = (redact[0] if redact[0] == "all" else tuple(redact[0]),) + tuple(redact[1:])
         states = _eager_states(class_mapping)
         spec = entry.PassSpec(annotate=True, redact=redact, draw=draw, track=track, track_scene_cut=track_scene_cut, track_trails=track_trails,
-                              track_motion=radius, heat=heatmap, count=count, zone=zone, remove=remove, track_reid=track_reid)
+                              track_motion=radius, heat=heatmap, count=count, zone=zone, remove=remove, track_reid=track_reid,
+                              redact_shape=redact_shape)
         chain = EditChain(states, spec, 1, 1, frame.shape[:2], rgb)
         chain.update(dev.view(-1), 0, packed, states.one_frame())         # (in front of the edits: ``dev`` is still the frame as it came)
         chain.edit(0, dev)
@@ -412,6 +425,38 @@ def redact_from_args(args, class_mapping):
     if margin < 0:
         raise ValueError("--redact_margin=%d: an integer >= 0" % margin)
     return classes, mode, size, margin
+
+
+def _redact_shape(redact_shape, redact):
+    """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame`` / ``draw_eager``'s ``redact_shape`` checked against ``redact``
+    -> (shape, feather), or None: without it and for ("box", 0), which is the plain redaction."""
+    if redact_shape is None:
+        return None
+    if redact is None:
+        raise ValueError("redact_shape=%r shapes the redaction: it needs redact=(classes, mode, size, margin)" % (redact_shape,))
+    try:
+        shape, feather = redact_shape
+    except (TypeError, ValueError):
+        raise ValueError("redact_shape=%r: (shape, feather)" % (redact_shape,)) from None
+    option = ops.redact_shape_option(shape, feather)
+    return None if option == ("box", 0) else option
+
+
+def redact_shape_from_args(args):
+    """(host only) The shape of the redaction the command line asks for -> (shape, feather) as ``submit_batch(redact_shape=...)`` takes
+    it, or None without ``--redact_shape`` / ``--redact_feather`` and for "box" with feather 0, which is the plain redaction.  ValueError,
+    with the reason, for either flag without ``--redact`` and for a feather outside 0..32."""
+    if args.redact_shape is None and args.redact_feather is None:
+        return None
+    if args.redact is None:
+        for flag, value in (("--redact_shape", args.redact_shape), ("--redact_feather", args.redact_feather)):
+            if value is not None:
+                raise ValueError("%s=%s is a setting of the redaction: it needs --redact CLASSES" % (flag, value))
+    try:
+        option = ops.redact_shape_option(args.redact_shape, args.redact_feather)
+    except ValueError as e:
+        raise ValueError("--redact_shape / --redact_feather: %s" % e) from None
+    return None if option == ("box", 0) else option
 
 
 def track_from_args(args):
@@ -1158,7 +1203,7 @@ def _print_drawn(dets, width, height):
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
                         track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, track_reid=None,
-                        reid_out=None, post=None, out_size=None):
+                        reid_out=None, post=None, out_size=None, redact_shape=None):
     """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
@@ -1188,8 +1233,11 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     post=)``).  None: every byte and line is what it was.
     ``out_size`` = ("size", W, H) or ("scale", N): the annotated frame is scaled down on the device behind every edit (DESIGN §8 "Scale
     rule") and the scaled frame, a new (H, W, 3) array, is returned in ``frame``'s place; the dets, the printed lines and every file
-    written stay in the coordinates of ``frame``.  ValueError for a target the rule refuses for this frame."""
+    written stay in the coordinates of ``frame``.  ValueError for a target the rule refuses for this frame.
+    ``redact_shape`` = (shape, feather) (with ``redact``): the boxes hide the ellipses inscribed in them and the replacement fades out
+    over ``feather`` pixels outside the shape (DESIGN §8 "Shape rule"); ("box", 0) and None: every byte is what it was."""
     post = None if post is None else ops.det_post_option(post)
+    redact_shape = _redact_shape(redact_shape, redact)
     if out_size is not None:
         scaled_size(out_size, frame_no, frame.shape[1], frame.shape[0])
     track_reid = _track_reid(track_reid, track)
@@ -1230,6 +1278,8 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         motion["remove"] = remove
     if track_reid is not None:
         motion["track_reid"] = track_reid
+    if redact_shape is not None:
+        motion["redact_shape"] = redact_shape
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     eng = _engine(training_manager, detector, 1, post)
     info = {}
@@ -1667,7 +1717,7 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
               track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None,
-              plate_out=None, track_reid=None, reid_out=None, post=None, out_size=None):
+              plate_out=None, track_reid=None, reid_out=None, post=None, out_size=None, redact_shape=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
@@ -1698,6 +1748,9 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     out_size = None if out_size is None else ops.scale_form(out_size)      # (refused here, in front of any capture)
     if out_size is not None:
         motion["out_size"] = out_size
+    redact_shape = _redact_shape(redact_shape, redact)    # (refused here, in front of any capture)
+    if redact_shape is not None:
+        motion["redact_shape"] = redact_shape
     counts_log = zones_log = reid_log = None
     sink = make_sink()
     if out_size is not None:                              # a frame the target does not fit is refused by name, on both paths
@@ -1748,6 +1801,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
                 kwargs.update(redact=redact, draw=draw)
             if out_size is not None:
                 kwargs.update(out_size=out_size)
+            if redact_shape is not None:
+                kwargs.update(redact_shape=redact_shape)
             mapping = training_manager.class_mapping
 
             def prepare(label, frame):                    # (read-ahead thread) -> (label, frame, resized, ratio, pixels)
@@ -1807,13 +1862,13 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
                     track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
                     counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None, reid_out=None, post=None,
-                    out_size=None):
+                    out_size=None, redact_shape=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
     other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out`` / ``remove`` / ``plate_out`` / ``track_reid`` / ``reid_out`` / ``post`` / ``out_size``: as ``annotate_images`` (a ``Y4mWriter``'s size is then the SCALED size).  """
+    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out`` / ``remove`` / ``plate_out`` / ``track_reid`` / ``reid_out`` / ``post`` / ``out_size`` / ``redact_shape``: as ``annotate_images`` (a ``Y4mWriter``'s size is then the SCALED size).  """
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
     if isinstance(writer_or_out_dir, y4m.Y4mWriter):
         make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma, out_size)
@@ -1824,7 +1879,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
               detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
               heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out, remove=remove,
-              plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size)
+              plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size, redact_shape=redact_shape)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
@@ -1832,7 +1887,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
                     heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None,
-                    reid_out=None, post=None, out_size=None):
+                    reid_out=None, post=None, out_size=None, redact_shape=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1896,7 +1951,12 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     integers; labels shrink with the picture): the device encoders encode, and the read-back copies, the smaller frame; the host encoders
     simply receive it.  ("scale", N) applies per frame size in a list of mixed sizes; ("size", W, H) is refused with the name of the
     first frame that is smaller than it (or more than 16 times its size along a side).  The printed lines, ``tracks_out``, ``counts_out``
-    and ``zones_out`` stay in SOURCE coordinates.  None: no pass, key, printed line or output byte changes."""
+    and ``zones_out`` stay in SOURCE coordinates.  None: no pass, key, printed line or output byte changes.
+    ``redact_shape``: (shape, feather) as ``redact_shape_from_args`` returns it (with ``redact``, and with every option above) -- every
+    box the redaction hides, held and back-filled ones too, hides the ellipse inscribed in the box grown by the margin ("ellipse"), and
+    the replacement fades into the scene over ``feather`` pixels OUTSIDE the shape, so nothing the hard shape hides shows (DESIGN §8
+    "Shape rule", ops.redact_shaped_u8).  The plate of ``remove``, the tracker, the heat map and the drawn boxes keep their rectangles.
+    None and ("box", 0): no pass, key, printed line or output byte changes."""
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
@@ -1910,7 +1970,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
               track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out,
-              remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size)
+              remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size,
+              redact_shape=redact_shape)
 
 
 def build_parser():
@@ -1981,6 +2042,11 @@ def build_parser():
                    help="pixelate: the cell's side, 2..64 (default 16); blur: the radius, 1..32 (default 12); none with fill (needs --redact)")
     p.add_argument("--redact_margin", dest="redact_margin", type=int, default=None, metavar="N",
                    help="pixels added around every redacted box (default 0; needs --redact)")
+    p.add_argument("--redact_shape", dest="redact_shape", choices=ops.REDACT_SHAPES, default=None,
+                   help="what of every redacted box is hidden: box (default) = all of it; ellipse = the ellipse inscribed in the box "
+                        "grown by --redact_margin, not clipped to the frame (needs --redact)")
+    p.add_argument("--redact_feather", dest="redact_feather", type=int, default=None, metavar="N",
+                   help="the redaction fades into the scene over N pixels OUTSIDE the shape, 0..32 (default 0: a hard edge; needs --redact)")
     p.add_argument("--no_draw", dest="no_draw", action="store_true", help="draw no boxes and no labels (with --redact: only hide)")
     p.add_argument("--track", dest="track", action="store_true",
                    help="join the detections of consecutive frames into tracks: labels read cls#id, and a track the detector loses is held "
@@ -2220,6 +2286,9 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     out_size = out_size_from_args(args)                   # (before any model is loaded)
     if out_size is not None:
         tracking["out_size"] = out_size
+    redact_shape = redact_shape_from_args(args)           # (before any model is loaded)
+    if redact_shape is not None:
+        tracking["redact_shape"] = redact_shape
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

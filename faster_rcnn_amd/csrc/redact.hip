@@ -6,13 +6,10 @@
 // workgroup first collects the rows whose box meets its tile (from the device's *n_dets; usually none, and the workgroup is done), then
 // each thread walks its byte column down the tile.  Threads are bytes, not pixels: a row is 3w bytes with no alignment to speak of, and
 // 64 lanes on 64 consecutive bytes are one coalesced access wherever the row starts.  Every output byte has one writer.
-#include "common.h"
-#include "../../include/ext/frcnn_hip_redact.h"
+#include "redact.h"
 
 namespace frcnn {
 
-constexpr int RD_THREADS = 256;
-constexpr int RD_TILE_ROWS = 16;
 constexpr int RD_HALO = 3 * FRCNN_REDACT_BLUR_MAX;                          // bytes of a row on either side of a blur window's centre
 
 // phase one, PIXELATE: a wave per cell; cells[(i * cw + j) * 3 + c] = the rounded mean of channel c over cell (i, j)
@@ -124,6 +121,46 @@ static bool size_ok(int mode, int size) {
     return false;
 }
 
+int redact_check(const char* who, const uint8_t* frame, int h, int w, const int32_t* det_bbox, const int32_t* det_cls, const int32_t* n_dets,
+                 int max_rows, const uint8_t* redact, int num_classes, int mode, int size, int margin, const void* workspace,
+                 size_t ws_bytes) {
+    if (!frame || !det_bbox || !det_cls || !n_dets || !redact) return fail(FRCNN_E_ARG, "%s: null pointer", who);
+    if (h < 1 || h > FRCNN_REDACT_MAX_SIDE || w < 1 || w > FRCNN_REDACT_MAX_SIDE)
+        return fail(FRCNN_E_ARG, "%s: frame %dx%d out of range (sides 1..%d)", who, h, w, FRCNN_REDACT_MAX_SIDE);
+    if (max_rows <= 0 || max_rows > FRCNN_REDACT_MAX_ROWS)
+        return fail(FRCNN_E_ARG, "%s: max_rows=%d not in [1, %d]", who, max_rows, FRCNN_REDACT_MAX_ROWS);
+    if (num_classes <= 0 || num_classes > 256) return fail(FRCNN_E_ARG, "%s: num_classes=%d not in [1, 256]", who, num_classes);
+    if (mode != FRCNN_REDACT_FILL && mode != FRCNN_REDACT_PIXELATE && mode != FRCNN_REDACT_BLUR)
+        return fail(FRCNN_E_ARG, "%s: mode=%d (0 fill, 1 pixelate, 2 blur)", who, mode);
+    if (!size_ok(mode, size))
+        return fail(FRCNN_E_ARG, "%s: size=%d out of range for mode %d (fill: 0, pixelate: %d..%d, blur: %d..%d)", who, size, mode,
+                    FRCNN_REDACT_PIXELATE_MIN, FRCNN_REDACT_PIXELATE_MAX, FRCNN_REDACT_BLUR_MIN, FRCNN_REDACT_BLUR_MAX);
+    if (margin < 0) return fail(FRCNN_E_ARG, "%s: margin=%d is negative", who, margin);
+    const size_t need = frcnn_redact_ws_bytes(h, w, mode, size);
+    if (need && !workspace) return fail(FRCNN_E_ARG, "%s: null workspace", who);
+    if (ws_bytes < need) return fail(FRCNN_E_ARG, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
+    return FRCNN_OK;
+}
+
+int redact_phase_one(const char* who, const uint8_t* frame, int h, int w, const int32_t* n_dets, int mode, int size, void* workspace,
+                     hipStream_t st) {
+    char what[64];
+    if (mode == FRCNN_REDACT_PIXELATE) {
+        const int ch = (h + size - 1) / size, cw = (w + size - 1) / size;
+        const long long cells = (long long)ch * cw;
+        const unsigned blocks = (unsigned)((cells + RD_THREADS / 64 - 1) / (RD_THREADS / 64));
+        k_redact_cells<<<blocks, RD_THREADS, 0, st>>>(frame, h, w, n_dets, size, ch, cw, (uint8_t*)workspace);
+        snprintf(what, sizeof what, "%s (cells)", who);
+        return check_launch(what);
+    }
+    if (mode == FRCNN_REDACT_BLUR) {
+        k_redact_hblur<<<dim3((3 * w + RD_THREADS - 1) / RD_THREADS, h), RD_THREADS, 0, st>>>(frame, h, w, n_dets, size, (uint8_t*)workspace);
+        snprintf(what, sizeof what, "%s (rows)", who);
+        return check_launch(what);
+    }
+    return FRCNN_OK;
+}
+
 }  // namespace frcnn
 
 using namespace frcnn;
@@ -140,33 +177,12 @@ extern "C" size_t frcnn_redact_ws_bytes(int h, int w, int mode, int size) {
 extern "C" int frcnn_redact_u8(uint8_t* frame, int h, int w, const int32_t* det_bbox, const int32_t* det_cls, const int32_t* n_dets,
                                int max_rows, const uint8_t* redact, int num_classes, int mode, int size, int margin, void* workspace,
                                size_t ws_bytes, void* stream) {
-    if (!frame || !det_bbox || !det_cls || !n_dets || !redact) return fail(FRCNN_E_ARG, "redact_u8: null pointer");
-    if (h < 1 || h > FRCNN_REDACT_MAX_SIDE || w < 1 || w > FRCNN_REDACT_MAX_SIDE)
-        return fail(FRCNN_E_ARG, "redact_u8: frame %dx%d out of range (sides 1..%d)", h, w, FRCNN_REDACT_MAX_SIDE);
-    if (max_rows <= 0 || max_rows > FRCNN_REDACT_MAX_ROWS)
-        return fail(FRCNN_E_ARG, "redact_u8: max_rows=%d not in [1, %d]", max_rows, FRCNN_REDACT_MAX_ROWS);
-    if (num_classes <= 0 || num_classes > 256) return fail(FRCNN_E_ARG, "redact_u8: num_classes=%d not in [1, 256]", num_classes);
-    if (mode != FRCNN_REDACT_FILL && mode != FRCNN_REDACT_PIXELATE && mode != FRCNN_REDACT_BLUR)
-        return fail(FRCNN_E_ARG, "redact_u8: mode=%d (0 fill, 1 pixelate, 2 blur)", mode);
-    if (!size_ok(mode, size))
-        return fail(FRCNN_E_ARG, "redact_u8: size=%d out of range for mode %d (fill: 0, pixelate: %d..%d, blur: %d..%d)", size, mode,
-                    FRCNN_REDACT_PIXELATE_MIN, FRCNN_REDACT_PIXELATE_MAX, FRCNN_REDACT_BLUR_MIN, FRCNN_REDACT_BLUR_MAX);
-    if (margin < 0) return fail(FRCNN_E_ARG, "redact_u8: margin=%d is negative", margin);
-    const size_t need = frcnn_redact_ws_bytes(h, w, mode, size);
-    if (need && !workspace) return fail(FRCNN_E_ARG, "redact_u8: null workspace");
-    if (ws_bytes < need) return fail(FRCNN_E_ARG, "redact_u8: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    if (int rc = redact_check("redact_u8", frame, h, w, det_bbox, det_cls, n_dets, max_rows, redact, num_classes, mode, size, margin, workspace,
+                              ws_bytes))
+        return rc;
     hipStream_t st = as_stream(stream);
+    if (int rc = redact_phase_one("redact_u8", frame, h, w, n_dets, mode, size, workspace, st)) return rc;
     const int col_blocks = (3 * w + RD_THREADS - 1) / RD_THREADS;
-    if (mode == FRCNN_REDACT_PIXELATE) {
-        const int ch = (h + size - 1) / size, cw = (w + size - 1) / size;
-        const long long cells = (long long)ch * cw;
-        const unsigned blocks = (unsigned)((cells + RD_THREADS / 64 - 1) / (RD_THREADS / 64));
-        k_redact_cells<<<blocks, RD_THREADS, 0, st>>>(frame, h, w, n_dets, size, ch, cw, (uint8_t*)workspace);
-        if (int rc = check_launch("redact_u8 (cells)")) return rc;
-    } else if (mode == FRCNN_REDACT_BLUR) {
-        k_redact_hblur<<<dim3(col_blocks, h), RD_THREADS, 0, st>>>(frame, h, w, n_dets, size, (uint8_t*)workspace);
-        if (int rc = check_launch("redact_u8 (rows)")) return rc;
-    }
     k_redact_apply<<<dim3(col_blocks, (h + RD_TILE_ROWS - 1) / RD_TILE_ROWS), RD_THREADS, 0, st>>>(
         frame, h, w, det_bbox, det_cls, n_dets, max_rows, redact, num_classes, mode, size, margin, (const uint8_t*)workspace);
     return check_launch("redact_u8");

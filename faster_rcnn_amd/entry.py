@@ -306,6 +306,7 @@ class PassSpec:
     jpeg_mode: tuple = JPEG_MODE
     y4m_mode: tuple = Y4M_MODE
     redact: object = None
+    redact_shape: object = None                          # (shape, feather), ops.redact_shape_option's form; None: ("box", 0), the plain redaction
     draw: bool = True
     track: object = None
     track_motion: object = None
@@ -324,7 +325,7 @@ class PassSpec:
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
                 track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                track_trails=None, heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None):
+                track_trails=None, heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -412,6 +413,10 @@ class PassSpec:
             track_reid = engine.track_reid_option(track_reid)
         if redact is not None:
             redact = engine.redact_option(redact)
+        if redact_shape is not None:
+            if redact is None:
+                raise FrcnnError("submit_batch: redact_shape= shapes the redaction: pass redact=(classes, mode, size, margin) too")
+            redact_shape = engine.redact_shape_option(redact_shape)
         if out_size is not None:
             if not annotate:
                 raise FrcnnError("submit_batch: out_size= scales the frame an ANNOTATING pass returns: pass annotate=True")
@@ -452,7 +457,7 @@ class PassSpec:
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
                    track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove,
-                   track_reid=track_reid, out_size=out_size)
+                   track_reid=track_reid, out_size=out_size, redact_shape=redact_shape)
 
     def out_hw(self, hw):
         """The size (H, W) of the frames a pass over source frames of ``hw`` = (h, w) encodes and returns: the scale step's target, or
@@ -499,6 +504,8 @@ class PassSpec:
             key = key + self.y4m_mode
         if self.redact is not None:
             key = key + ("redact",) + self.redact
+        if self.redact_shape is not None:                # (never ("box", 0): that is the pass without it)
+            key = key + ("shape",) + self.redact_shape
         if not self.draw:
             key = key + ("nodraw",)
         if self.track is not None:
@@ -722,6 +729,19 @@ class DetectionEntry:
         if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or margin < 0:
             raise FrcnnError("submit_batch: redact margin=%r: an integer >= 0" % (margin,))
         return classes, mode, size, int(margin)
+
+    def redact_shape_option(self, redact_shape):
+        """``submit_batch``'s ``redact_shape`` checked and normalised -> (shape, feather), or None for ("box", 0), which IS the plain
+        redaction: one spec, one key.  FrcnnError, with the reason, for anything else."""
+        try:
+            shape, feather = redact_shape
+        except (TypeError, ValueError):
+            raise FrcnnError("submit_batch: redact_shape=%r: (shape, feather)" % (redact_shape,)) from None
+        try:
+            option = ops.redact_shape_option(shape, feather)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: %s" % e) from None
+        return None if option == ("box", 0) else option
 
     # ------------------------------------------------------------------ heat map
     def heat_state(self, h, w):
@@ -1428,7 +1448,7 @@ class DetectionEntry:
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
                      track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
-                     heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None):
+                     heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1569,12 +1589,19 @@ class DetectionEntry:
         list stay in SOURCE coordinates.  Refused by name, in front of any capture: without ``annotate``; a target the rule refuses for
         the pass's frame size (larger than it, less than 1/16 of it along a side, a side of 0); a size the pass's encoder refuses, with
         the encoder's own reason.  Without it every key and byte is what it was.
+        ``redact_shape`` = (shape, feather) (passes with ``redact`` only; ("shape", shape, feather) appended directly behind ("redact",
+        ...); shape "box" / "ellipse", feather 0..32 pixels, None in a place: "box", 0): the shape rule (DESIGN §8 "Shape rule"): the
+        redaction step is ops.redact_shaped_u8 instead of ops.redact_u8 -- every box, held and back-filled ones too, hides the ellipse
+        inscribed in it, NOT clipped to the frame, and the replacement fades out over ``feather`` pixels OUTSIDE the shape.  Nothing else
+        of the pass knows: the plate steps, the tracker, the heat map and the drawn boxes keep their rectangles.  ("box", 0) and None ARE
+        the pass without it: one spec, one key.  Refused by name, in front of any capture: without ``redact``, for an unknown shape and
+        for a feather out of range.  Without it every key and byte is what it was.
         The order of all these steps in a pass is stated once, in ``frame_edit.EditChain``'s docstring."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
                                 track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove, track_reid=track_reid,
-                                out_size=out_size)
+                                out_size=out_size, redact_shape=redact_shape)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush

@@ -178,7 +178,8 @@ class EditChain:
     ``edit``, once per frame, on ``rows(i)`` -- the frame's emitted buffer, else its tracked buffer, else its packed detections:
      5b. ops.plate_update, on the frame NO edit has touched: every row blocks, the held and back-filled ones too, whatever its class;
          with ``track_scene_cut`` the frame's cut word empties the plate first;
-      6. ops.redact_u8: every tracked row, the held ones too;
+      6. ops.redact_u8: every tracked row, the held ones too; with ``redact_shape`` ops.redact_shaped_u8 in its place (DESIGN §8 "Shape
+         rule"), and nowhere else: the plate steps on either side of it keep their rectangles;
      6b. ops.plate_fill_u8, over the redaction: the rows of the remove classes become the plate.  Where the plate is not known yet
          the redaction shows, if the chain redacts all the remove classes (``keep_unknown``); else black;
       7. ops.heat_update (the live rows) and ops.heat_draw_u8;
@@ -213,6 +214,8 @@ class EditChain:
             if self.lookback:
                 raise FrcnnError("track_reid= does not go with track_lookback= / track_backtrack=: their windows hold the tracked buffers of "
                                  "earlier passes, whose ids are the tracker's")
+        if spec.redact_shape and not spec.redact:
+            raise FrcnnError("redact_shape= shapes the redaction: the chain needs redact=(classes, mode, size, margin) too")
         if spec.redact:
             # one workspace serves the frames of a pass, which are redacted one after another
             classes, mode, size, _ = spec.redact
@@ -323,7 +326,11 @@ class EditChain:
                              cut=None if self.cuts is None else self.cuts[i], tracked=tracked)
         if sp.redact:
             _, mode, size, margin = sp.redact
-            ops.redact_u8(frame, rows, self.redact_table, mode, size, margin, workspace=self.redact_ws, tracked=tracked)
+            if sp.redact_shape:
+                ops.redact_shaped_u8(frame, rows, self.redact_table, mode, size, margin, *sp.redact_shape, workspace=self.redact_ws,
+                                     tracked=tracked)
+            else:
+                ops.redact_u8(frame, rows, self.redact_table, mode, size, margin, workspace=self.redact_ws, tracked=tracked)
         if sp.remove:
             ops.plate_fill_u8(frame, self.plate, rows, self.remove_table, p_margin, keep_unknown=self.keep_unknown, tracked=tracked)
         if sp.heat:

@@ -1423,8 +1423,55 @@ def redact_u8(frame, det_packed, table, mode="pixelate", size=None, margin=0, wo
     return frame
 
 
+REDACT_SHAPES = tuple(_lib.REDACT_SHAPES)       # "box", "ellipse"
+REDACT_FEATHER = _lib.REDACT_FEATHER            # (smallest, largest) feather in pixels
+
+
+def redact_shape_option(shape=None, feather=None):
+    """(host only) (shape, feather) checked, None replaced by the default ("box", 0): shape "box" or "ellipse", feather the pixels the
+    edge ramps outwards over, 0..32 (DESIGN §8 "Shape rule").  ValueError with the reason."""
+    shape = "box" if shape is None else shape
+    feather = 0 if feather is None else feather
+    if not isinstance(shape, str) or shape not in _lib.REDACT_SHAPES:
+        raise ValueError("redact shape %r: one of %s" % (shape, ", ".join(REDACT_SHAPES)))
+    lo, hi = REDACT_FEATHER
+    if isinstance(feather, bool) or not isinstance(feather, (int, np.integer)) or not lo <= int(feather) <= hi:
+        raise ValueError("redact feather %r: an integer in %d..%d" % (feather, lo, hi))
+    return shape, int(feather)
+
+
+def redact_shaped_u8(frame, det_packed, table, mode="pixelate", size=None, margin=0, shape="box", feather=0, workspace=None, tracked=False):
+    """``redact_u8`` with a shaped, soft-edged mask (frcnn_redact_shaped_u8, csrc/redact_shape.hip; DESIGN §8 "Shape rule"): every box
+    is grown by ``margin`` and NOT clipped; ``shape`` "ellipse" hides the ellipse inscribed in it; the replacement is blended in with a
+    weight that is full inside the shape and ramps to nothing over ``feather`` pixels OUTSIDE it, the largest weight of any row
+    winning.  ("box", 0) gives ``redact_u8``'s bytes.  Every other argument, the workspace (``redact_ws_bytes``) and the return are
+    ``redact_u8``'s; the shape and the feather range are the library's to check."""
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.is_contiguous()
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    if mode not in _lib.REDACT_MODES:
+        raise ValueError("redact mode %r: one of %s" % (mode, ", ".join(REDACT_MODES)))
+    if shape not in _lib.REDACT_SHAPES:
+        raise ValueError("redact shape %r: one of %s" % (shape, ", ".join(REDACT_SHAPES)))
+    size = REDACT_SIZES[mode][2] if size is None else int(size)            # (the range is the library's to check)
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    if workspace is None:
+        workspace = _ws(_lib.load().frcnn_redact_ws_bytes(h, w, _lib.REDACT_MODES[mode], size))
+    assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    if tracked:                                         # (every row up to n_rows: the held ones too)
+        assert det_packed.dim() == 1
+        n_dets, _, _, _, det_bbox, det_cls, _, _, _ = split_tracked(det_packed)
+    else:
+        n_dets, det_bbox, det_cls, _, _ = split_detections(det_packed)
+    _lib.call("frcnn_redact_shaped_u8", _p(frame), h, w, _p(det_bbox), _p(det_cls), _p(n_dets), int(det_cls.numel()), _p(table),
+              int(table.numel()), _lib.REDACT_MODES[mode], size, int(margin), _lib.REDACT_SHAPES[shape], int(feather), _p(workspace),
+              int(workspace.numel()), _stream())
+    return frame
+
+
 # ----------------------------------------------------------------------------- tracking
-TRACK_MAX = _lib.TRACK_MAX                      # slots of a state, at most
+TRACK_MAX = _lib.TRACK_MAX                     # slots of a state, at most
 TRACK_DEFAULTS = _lib.TRACK_DEFAULTS            # (thr, hold, grow)
 
 

@@ -32,7 +32,7 @@ without and with ``--detect_every 4``.  ``--track_backtrack`` (``run_track_backt
 ``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
 look-back call of one pass alone.  ``--track_scene_cut`` (``run_track_scene_cut``) runs the ``--track --track_motion 8`` leg without and with
 ``--track_scene_cut`` at its default.  ``--track_trails`` (``run_track_trails``) runs the same leg without and with ``--track_trails`` at its
-defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--out_scale`` (``run_out_scale``) runs in-memory annotating passes, the PNG-file to PNG-file leg (device encoder, huffman) and y4m to y4m, each without and with ``--out_scale 2``.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).
+defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--out_scale`` (``run_out_scale``) runs in-memory annotating passes, the PNG-file to PNG-file leg (device encoder, huffman) and y4m to y4m, each without and with ``--out_scale 2``.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).  ``--redact_shape`` (``run_redact_shape``) runs the ``--redact all --redact_mode blur`` passes without and with ``--redact_shape ellipse --redact_feather 8``.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
@@ -363,6 +363,48 @@ def run_redact(name, cfg, n_frames, reps, content="noise"):
         res[k + "_runs_s"] = [round(t, 4) for t in ts]
     for k in ("passes", "files"):
         res[k + "_redact_over_plain"] = round(statistics.median(times[k]) / statistics.median(times[k + "_redact"]), 3)
+    return res
+
+
+REDACT_SHAPE_LEG = ("ellipse", 8)                        # --redact_shape ellipse --redact_feather 8
+
+
+def run_redact_shape(name, cfg, n_frames, reps, content="noise"):
+    """``--redact_shape``: what the shaped, soft-edged redaction (DESIGN §8 "Shape rule") costs against the plain one.  One pair of legs in
+    ONE session, alternating inside every repetition: the ``--redact`` leg's frames through in-memory annotating passes with
+    ``redact=REDACT_LEG``, without and with ``redact_shape=REDACT_SHAPE_LEG``.  Reports frames/s of both, their ratio and the share of
+    the pixels each changes.  Not separated: the phase-two kernel alone, and photo content (on noise frames the detector fires all over
+    the frame, so most tiles meet a box or a ring)."""
+    import numpy as np
+    from faster_rcnn_amd import entry, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+    legs = {"redact": lambda: annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG),
+            "redact_shape": lambda: annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, redact_shape=REDACT_SHAPE_LEG)}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    few = slice(0, eng.batch)
+    plain = annotate_in_memory(eng, resized[few], ratios[few])
+    share = {k: float(np.mean([(a != b).any(axis=2).mean() for a, b in zip(annotate_in_memory(eng, resized[few], ratios[few], redact=REDACT_LEG, **kw), plain)]))
+             for k, kw in (("redact", {}), ("redact_shape", {"redact_shape": REDACT_SHAPE_LEG}))}
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact": ["all", "blur", 12, 0], "redact_shape": list(REDACT_SHAPE_LEG), "images_per_pass": eng.batch, "in_flight": eng.in_flight,
+           "pixels_changed_share": {k: round(v, 3) for k, v in share.items()}}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["shape_over_redact"] = round(statistics.median(times["redact"]) / statistics.median(times["redact_shape"]), 3)
     return res
 
 
@@ -1156,6 +1198,8 @@ def main():
     ap.add_argument("--out_scale", action="store_true", help="instead of the legs above: in-memory annotating passes, PNG files to PNG files "
                                                              "(device encoder, huffman) and y4m to y4m, each without and with --out_scale 2, "
                                                              "alternating in one session")
+    ap.add_argument("--redact_shape", action="store_true", help="instead of the legs above: the --redact all --redact_mode blur leg without and "
+                                                                "with --redact_shape ellipse --redact_feather 8, alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -1164,6 +1208,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.redact_shape:
+            out[name] = run_redact_shape(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.out_scale:
             out[name] = run_out_scale(name, PAIRS[name], args.frames, args.reps, args.content)
