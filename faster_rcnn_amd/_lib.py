@@ -20,6 +20,7 @@ class FrcnnError(RuntimeError):
 ABI_VERSION = 110       # include/frcnn_hip.h FRCNN_ABI_VERSION (tests/test_abi.py holds the two together)
 P = c_void_p
 I = c_int
+F32 = ctypes.c_float
 # name -> (restype, argtypes).  Must list every symbol include/frcnn_hip.h declares
 # (tests/test_abi.py parses the header and checks this table and the .so against it).
 SIGNATURES = {
@@ -453,6 +454,19 @@ TRACK_CUT_SIGNATURES = {
 # (FRCNN_TRACK_CUT_MIN_PCT / _MAX_PCT; the default is provisional: no threshold has been measured on real footage)
 TRACK_CUT_PCT = (1, 100, 40)
 
+TRACK_WEAK_VERSION = 1          # include/ext/frcnn_hip_track_weak.h FRCNN_TRACK_WEAK_VERSION
+# each parent's signature with ``float strong`` in front of ``out``
+TRACK_WEAK_SIGNATURES = {
+    "frcnn_track_weak_version": (I, []),
+    "frcnn_track_update_weak": (I, [P, I, P, ctypes.c_longlong, I, P, I, P, I, I, I, I, I, I, F32, P, ctypes.c_longlong, P]),
+    "frcnn_track_update_motion_weak": (I, [P, I, P, P, ctypes.c_longlong, P, ctypes.c_longlong, I, P, I, P, I, I, I, I, I, I, I, F32, P,
+                                           ctypes.c_longlong, P]),
+    "frcnn_track_update_interval_weak": (I, [P, I, P, P, ctypes.c_longlong, P, ctypes.c_longlong, I, P, I, P, I, I, I, I, I, I, I, I, F32, P,
+                                             ctypes.c_longlong, P]),
+    "frcnn_track_update_cut_weak": (I, [P, I, P, P, ctypes.c_longlong, P, ctypes.c_longlong, I, P, I, P, I, I, I, I, I, I, I, I, F32, P,
+                                        ctypes.c_longlong, I, P, P, P]),
+}
+
 TRACK_TRAILS_VERSION = 1        # include/ext/frcnn_hip_track_trails.h FRCNN_TRACK_TRAILS_VERSION
 TRACK_TRAILS_SIGNATURES = {
     "frcnn_track_trails_version": (I, []),
@@ -758,6 +772,15 @@ def load():
     if lib.frcnn_track_cut_version() != TRACK_CUT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_cut_version()} of the tracker's scene-cut extension, this binding "
                          f"{TRACK_CUT_VERSION} (include/ext/frcnn_hip_track_cut.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in TRACK_WEAK_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_track_weak.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_track_weak_version() != TRACK_WEAK_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_track_weak_version()} of the tracker's weak-row extension, this binding "
+                         f"{TRACK_WEAK_VERSION} (include/ext/frcnn_hip_track_weak.h): rebuild with `python -m faster_rcnn_amd.build`")
     for name, (res, args) in TRACK_TRAILS_SIGNATURES.items():
         fn = getattr(lib, name, None)
         if fn is None:

@@ -140,6 +140,12 @@ the trails, the count lines (which then count it once) and the zones.  A line ``
 of that frame's lines and ``re-identified: N`` at the end; ``reid_out=PATH`` (``--reid_out``) receives a CSV row
 ``frame,id,tracker_id,cls,distance,gap`` per event.  A list starts from an empty memory; ``get_annotated_frame(track_reid=)`` and the
 eager path continue it as one-frame calls (``reset_tracks`` empties it).  A ``--track_scene_cut`` cut empties it too.
+``det_threshold=T`` (``--det_threshold T``, 0..1; default DET_THRESHOLD = 0.0, the reference script's) reports detections of score T or
+more only, with or without ``track``.  ``track_low=L`` (``--track_low L``, with ``--track``, L < T; no bare form: no default has been
+measured) is the weak rule (DESIGN §8 "Weak rule", the ``strong=`` form of the tracker calls, csrc/track.hip): the passes are submitted
+with det_threshold=L and track_strong=T, a detection with a score in [L, T) may only continue a track no stronger one continued and is
+dropped otherwise, and every printed line and ``tracks_out`` show the kept rows.  The eager path (a foreign model) takes
+``det_threshold`` and refuses ``track_low`` by name.  Without the two, no pass, key, printed line or output byte changes.
 """
 import collections
 import os
@@ -916,6 +922,32 @@ def _print_reid(label, events):
         print("re-identified: {} id {}".format(label, ev[0]))
 
 
+def _det_thresholds(det_threshold, track_low, track, eager=False):
+    """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame``'s ``det_threshold`` and ``track_low`` checked -> (T, L): T the
+    score threshold of the output (None: DET_THRESHOLD), L the low threshold of the weak rule (DESIGN §8 "Weak rule") or None.  ``eager``:
+    the caller runs the eager path (a foreign model), which has no captured pass to run the rule in.  ValueError with the reason
+    (ops.track_weak_option's; the eager path's refusal of an L)."""
+    T, L = ops.track_weak_option(DET_THRESHOLD if det_threshold is None else det_threshold, track_low, track is not None)
+    if L is not None and eager:
+        raise ValueError("track_low=%r runs the tracker's weak rule inside the captured passes: the eager path (a foreign model) cannot"
+                         % (track_low,))
+    return T, L
+
+
+def det_thresholds_from_args(args):
+    """(host only) The thresholds the command line asks for -> {} without the two flags, else the ``det_threshold=`` / ``track_low=`` that
+    ``annotate_images`` takes.  ValueError, with the reason, for ``--track_low`` without ``--track``, for a ``--track_low`` that is not
+    under ``--det_threshold`` and for values outside 0..1."""
+    try:
+        ops.track_weak_option(DET_THRESHOLD if args.det_threshold is None else args.det_threshold, args.track_low, bool(args.track))
+    except ValueError as e:
+        raise ValueError("--det_threshold / --track_low: %s" % e) from None
+    out = {} if args.det_threshold is None else {"det_threshold": args.det_threshold}
+    if args.track_low is not None:
+        out["track_low"] = args.track_low
+    return out
+
+
 def _track_reid(track_reid, track):
     """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame``'s ``track_reid`` checked -> (pct, keep), or None."""
     if track_reid is None:
@@ -1203,8 +1235,9 @@ def _print_drawn(dets, width, height):
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
                         track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, track_reid=None,
-                        reid_out=None, post=None, out_size=None, redact_shape=None):
-    """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
+                        reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None):
+    """(``det_threshold`` / ``track_low``: as ``annotate_images``.)
+    annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
     ``tracks_out``: a text file that receives the frame's MOT lines under the number ``frame_no``.  ``track_motion`` = R (with
@@ -1280,12 +1313,17 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         motion["track_reid"] = track_reid
     if redact_shape is not None:
         motion["redact_shape"] = redact_shape
-    resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
+    strong, low = _det_thresholds(det_threshold, track_low, track)    # (the pair itself, in front of the engine)
     eng = _engine(training_manager, detector, 1, post)
+    _det_thresholds(det_threshold, track_low, track, eager=eng is None)      # (a foreign model refuses an L, in front of any work)
+    resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     info = {}
+    if low is not None:
+        motion["track_strong"] = strong
     if eng is not None:
         pixels = eng.host_pixels(resized_imgs[0])
-        num_rois, dets, out, *more = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], DET_THRESHOLD, [pixels],
+        num_rois, dets, out, *more = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], strong if low is None else low,
+                                                                        [pixels],
                                                                         batch=1, annotate=True, redact=redact, draw=draw,
                                                                         **({} if track is None else {"track": track}), **motion,
                                                                         **({} if heatmap is None else {"heat": heatmap}),
@@ -1300,7 +1338,7 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         else:
             frame = out
     else:
-        dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=DET_THRESHOLD, post=post)
+        dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=strong, post=post)
         frame = draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, info=info, heatmap=heatmap, out_size=out_size,
                            **motion)
         if info.get("scene_cut"):
@@ -1631,13 +1669,13 @@ def _loaded_files(paths, prepare, ahead):
         decode.shutdown(wait=True, cancel_futures=True)
 
 
-def _run_passes(eng, loaded, emit, pass_kwargs, every, delayed, backtrack):
+def _run_passes(eng, loaded, emit, pass_kwargs, every, delayed, backtrack, det_threshold=DET_THRESHOLD):
     """The pipelined loop: the frames of ``loaded`` -- an in-order generator of (label, frame, resized, ratio, pixels) that reads ahead --
     are grouped into runs of at most B * K of one geometry, a group goes through one pass of B (padded) when it fills at least half of it
     (as get_dets_by_cls) and through one-frame passes else, ``eng.in_flight`` passes are in flight, and ``emit(pos, label, frame, result)``
     gets every frame's result in order.  ``pass_kwargs``: what every submit_batch takes behind ``batch``; ``every`` / ``delayed`` /
     ``backtrack``: ``_tracking_options``' -- a delayed pass is always a full one, returns the group before its own, and a flush submit
-    follows a change of geometry and the last group."""
+    follows a change of geometry and the last group.  ``det_threshold``: the score threshold every pass uploads."""
     B = eng.batch
     F = B * (every or 1)                                  # frames of a full pass
     window = []
@@ -1656,7 +1694,7 @@ def _run_passes(eng, loaded, emit, pass_kwargs, every, delayed, backtrack):
 
     def flush():                                          # the frames the look-back window still holds
         if last_key[0] is not None:
-            window.append(((), eng.submit_batch([], [], DET_THRESHOLD, [], batch=B, **pass_kwargs)))
+            window.append(((), eng.submit_batch([], [], det_threshold, [], batch=B, **pass_kwargs)))
             last_key[0] = None
             if len(window) >= eng.in_flight:
                 finish()
@@ -1672,7 +1710,7 @@ def _run_passes(eng, loaded, emit, pass_kwargs, every, delayed, backtrack):
             parts = _every_parts(group, B, every)
         for part, take in parts:
             keys = part[::every or 1]
-            ticket = eng.submit_batch([g[3] for g in keys], [g[4] for g in keys], DET_THRESHOLD, [g[5] for g in part], batch=take, **pass_kwargs)
+            ticket = eng.submit_batch([g[3] for g in keys], [g[4] for g in keys], det_threshold, [g[5] for g in part], batch=take, **pass_kwargs)
             window.append(([(g[0], g[1], g[2]) for g in part], ticket))
             if delayed:
                 waiting.append(window[-1][0])
@@ -1717,13 +1755,15 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
 def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
               track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None,
-              plate_out=None, track_reid=None, reid_out=None, post=None, out_size=None, redact_shape=None):
+              plate_out=None, track_reid=None, reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None,
+              track_low=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
     if track_motion is not None and track is None:
         raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
     motion = {} if track_motion is None else {"track_motion": track_motion}
+    strong, low = _det_thresholds(det_threshold, track_low, track)    # (refused here, in front of any capture)
     post = None if post is None else ops.det_post_option(post)        # (refused here, in front of any capture)
     if post is not None:
         motion["post"] = post
@@ -1763,6 +1803,7 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     try:
         dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
         eng = _engine(training_manager, detector, entry.default_in_flight(dtype), post)
+        _det_thresholds(det_threshold, track_low, track, eager=eng is None)      # (a foreign model refuses an L)
         tracking, every, delayed, backtrack = _tracking_options(eng, track, track_motion, track_lookback, detect_every, track_backtrack,
                                                                 track_scene_cut)
         if track_scene_cut is not None:                   # (the eager path: one frame at a time against the kept frame)
@@ -1792,7 +1833,11 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             motion["track_reid"] = tracking["track_reid"] = track_reid
             reid_log = ReidLog(reid_out, _names_by_index(training_manager.class_mapping))
             motion["reid_out"] = reid_log
+        if low is not None:                               # the weak rule: the passes emit rows down to ``low``, the tracker is told ``strong``
+            tracking["track_strong"] = strong
         if eng is None:
+            if strong != DET_THRESHOLD:
+                motion["det_threshold"] = strong
             _run_eager(training_manager, detector, frames, sink, resize_min, resize_max, redact=redact, draw=draw, track=track,
                        tracks_out=tracks_out, **motion)
         else:
@@ -1828,7 +1873,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
                 _print_drawn(dets, frame.width, frame.height)
                 sink.emit(pos, out)
 
-            _run_passes(eng, loaded_from(prepare, 2 * eng.in_flight * eng.batch * (every or 1)), emit, kwargs, every, delayed, backtrack)
+            _run_passes(eng, loaded_from(prepare, 2 * eng.in_flight * eng.batch * (every or 1)), emit, kwargs, every, delayed, backtrack,
+                        det_threshold=strong if low is None else low)
         sink.finish()
         if count is not None:                             # (host only: the state read back)
             counts_log.close()
@@ -1862,7 +1908,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
                     track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
                     counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None, reid_out=None, post=None,
-                    out_size=None, redact_shape=None):
+                    out_size=None, redact_shape=None, det_threshold=None, track_low=None):
     """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
@@ -1879,7 +1925,8 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
               redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
               detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
               heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out, remove=remove,
-              plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size, redact_shape=redact_shape)
+              plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size, redact_shape=redact_shape,
+              det_threshold=det_threshold, track_low=track_low)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
@@ -1887,7 +1934,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
                     heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None,
-                    reid_out=None, post=None, out_size=None, redact_shape=None):
+                    reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -1956,7 +2003,14 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     box the redaction hides, held and back-filled ones too, hides the ellipse inscribed in the box grown by the margin ("ellipse"), and
     the replacement fades into the scene over ``feather`` pixels OUTSIDE the shape, so nothing the hard shape hides shows (DESIGN §8
     "Shape rule", ops.redact_shaped_u8).  The plate of ``remove``, the tracker, the heat map and the drawn boxes keep their rectangles.
-    None and ("box", 0): no pass, key, printed line or output byte changes."""
+    None and ("box", 0): no pass, key, printed line or output byte changes.
+    ``det_threshold``: T, a float in 0..1 (``--det_threshold``; None: DET_THRESHOLD = 0.0, the reference script's): the score under which
+    a detection is not reported; with or without ``track``.  ``track_low``: L < T (``--track_low``, with ``track``): the weak rule
+    (DESIGN §8 "Weak rule", the ``strong=`` form of the tracker call): the passes emit rows down to L (submit_batch's det_threshold = L,
+    track_strong = T), a row with a score in [L, T) may only continue a track that no row of T or more continued, and every other such
+    row is dropped -- so an object whose score dips stays covered by the detector's own box, under its id, and nothing new is reported
+    under T.  "num dets", the printed lines and ``tracks_out`` show the kept rows.  Refused by name without ``track``, for L >= T and
+    outside 0..1, and on the eager path (a foreign model).  None and None: no pass, key, printed line or output byte changes."""
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
@@ -1971,7 +2025,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
               track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out,
               remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size,
-              redact_shape=redact_shape)
+              redact_shape=redact_shape, det_threshold=det_threshold, track_low=track_low)
 
 
 def build_parser():
@@ -2064,6 +2118,12 @@ def build_parser():
     p.add_argument("--track_lookback", dest="track_lookback", type=int, nargs="?", const=TRACK_LOOKBACK_AUTO, default=None, metavar="N",
                    help="hide every new track in the N frames BEFORE its first detection too (1..16 and at most the frames of one pass; "
                         "bare: as many as a pass holds, at most 8); the output runs one pass behind the input (needs --track)")
+    p.add_argument("--det_threshold", dest="det_threshold", type=float, default=None, metavar="T",
+                   help="report detections with a score of T or more only, 0..1 (default 0.0: every detection, as the reference script)")
+    p.add_argument("--track_low", dest="track_low", type=float, default=None, metavar="L",
+                   help="with --track and --det_threshold T: a detection with a score in [L, T) may continue a track that no stronger "
+                        "detection continued, and is dropped otherwise; it never starts a track (needs L < T; no default: none has been "
+                        "measured on real footage)")
     p.add_argument("--detect_every", dest="detect_every", type=int, default=None, metavar="K",
                    help="run the detector on every K-th frame only, 2..16; on the frames between, every track's box follows the pixels "
                         "under it by block matching and is drawn, redacted and written to --tracks_out with the prob of its last match. "
@@ -2289,6 +2349,7 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     redact_shape = redact_shape_from_args(args)           # (before any model is loaded)
     if redact_shape is not None:
         tracking["redact_shape"] = redact_shape
+    tracking.update(det_thresholds_from_args(args))       # (before any model is loaded)
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "../../include/ext/frcnn_hip_redact.h"
 #include "../../include/ext/frcnn_hip_track.h"
+#include "../../include/ext/frcnn_hip_track_weak.h"
 #include "track.h"
 
 namespace frcnn {
@@ -55,19 +56,56 @@ __device__ int block_scan(int v, int* s_w, int* total) {
     return base + inc - v;
 }
 
+// The workgroup's best open row of class ``scls`` for the slot box ``sb`` (inter 0: none), the same value in every thread: each thread
+// scores its two rows, a shuffle reduction finds the wave's best and the waves' records in LDS set ``buf`` (0 / 1, alternating from one
+// call to the next: one barrier per call) the workgroup's.  The match stages of both rules go through here.
+__device__ __forceinline__ Cand slot_best(const Box& sb, int scls, int thr, const bool (&open)[2], const int (&rcls)[2], const Box (&rb)[2],
+                                          const long long (&rarea)[2], int buf, long long (*s_ri)[TR_WAVES], long long (*s_ru)[TR_WAVES],
+                                          int (*s_rr)[TR_WAVES]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long sarea = (long long)(sb.xb - sb.xa + 1) * (sb.yb - sb.ya + 1);
+    Cand best{0, 0, 0x7fffffff};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (!open[k] || rcls[k] != scls) continue;
+        const int iw = min(sb.xb, rb[k].xb) - max(sb.xa, rb[k].xa) + 1, ih = min(sb.yb, rb[k].yb) - max(sb.ya, rb[k].ya) + 1;
+        if (iw <= 0 || ih <= 0) continue;                                   // (an empty slot box never gets here)
+        const long long inter = (long long)iw * ih, uni = rarea[k] + sarea - inter;
+        if (inter * 100 < (long long)thr * uni) continue;
+        const Cand c{inter, uni, 2 * tid + k};
+        if (better(c, best)) best = c;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const Cand c{__shfl_xor(best.inter, off), __shfl_xor(best.uni, off), __shfl_xor(best.row, off)};
+        if (better(c, best)) best = c;
+    }
+    if (lane == 0) { s_ri[buf][wave] = best.inter; s_ru[buf][wave] = best.uni; s_rr[buf][wave] = best.row; }
+    __syncthreads();
+    best = Cand{s_ri[buf][0], s_ru[buf][0], s_rr[buf][0]};
+    for (int k = 1; k < TR_WAVES; ++k) {
+        const Cand c{s_ri[buf][k], s_ru[buf][k], s_rr[buf][k]};
+        if (better(c, best)) best = c;
+    }
+    return best;
+}
+
 // ``det`` and ``out`` are those of frame ``first`` of a call of ``total`` frames, and the launch walks ``frames`` of them: a frame whose index
 // in the CALL is at or behind *n_frames is padding (frcnn_track_update walks a whole call, first = 0 and frames = total; the motion
 // extension one frame per launch, with the block match in between).
+// WEAK (include/ext/frcnn_hip_track_weak.h, DESIGN §8 "Weak rule"): a row whose score is not >= ``strong`` is weak; the match has a stage B
+// in which the slots stage A left alone take weak rows, births are the strong rows' alone, and the live part of the output is the strong
+// rows and the matched weak ones, moved up in row order by one more prefix sum.  Without WEAK ``strong`` is not read.
+template <bool WEAK>
 __global__ void __launch_bounds__(TR_THREADS) k_track_update(int32_t* state, int cap, const int32_t* det, long long det_stride, int first,
                                                                int frames, int total, const int32_t* n_frames, int max_rows,
                                                                const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h,
-                                                               int w, int32_t* out, long long out_stride) {
+                                                               int w, float strong, int32_t* out, long long out_stride) {
     __shared__ int s_id[FRCNN_TRACK_MAX], s_cls[FRCNN_TRACK_MAX], s_prob[FRCNN_TRACK_MAX], s_age[FRCNN_TRACK_MAX], s_hit[FRCNN_TRACK_MAX];
     __shared__ int s_box[FRCNN_TRACK_MAX][4];
     __shared__ long long s_ri[2][TR_WAVES], s_ru[2][TR_WAVES];
     __shared__ int s_rr[2][TR_WAVES];
     __shared__ int s_w[TR_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int nf = min(max(*n_frames, 0), total) - first;                   // real frames from this launch's first one on
     const int R = max_rows + cap;
     int n_slots = min(max(state[0], 0), cap), issued = state[1], overflow = state[2], seen = state[3];
@@ -97,7 +135,8 @@ __global__ void __launch_bounds__(TR_THREADS) k_track_update(int32_t* state, int
         int raw[2][4], rcls[2], rprob[2], rid[2];
         Box rb[2];
         long long rarea[2];
-        bool open[2];                                                       // eligible and not yet matched
+        bool open[2];                                                       // eligible and not yet matched (WEAK: and strong)
+        bool wopen[2] = {false, false}, kept_row[2] = {false, false};       // WEAK: the same of the weak rows; a row of the live part
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int r = 2 * tid + k;
@@ -112,6 +151,11 @@ __global__ void __launch_bounds__(TR_THREADS) k_track_update(int32_t* state, int
                 const bool some = rb[k].xa <= rb[k].xb && rb[k].ya <= rb[k].yb;
                 open[k] = some && rcls[k] >= 0 && rcls[k] < num_classes && tracked[rcls[k]] != 0;
                 rarea[k] = some ? (long long)(rb[k].xb - rb[k].xa + 1) * (rb[k].yb - rb[k].ya + 1) : 0;
+                if constexpr (WEAK) {
+                    kept_row[k] = __int_as_float(rprob[k]) >= strong;       // (false for a NaN score)
+                    wopen[k] = open[k] && !kept_row[k];
+                    open[k] = open[k] && kept_row[k];
+                }
             }
         }
         if (tid < cap) s_hit[tid] = 0;
@@ -120,31 +164,7 @@ __global__ void __launch_bounds__(TR_THREADS) k_track_update(int32_t* state, int
         if (n > 0) {
             for (int s = 0; s < n_slots; ++s) {
                 const Box sb = clipped(s_box[s][0], s_box[s][1], s_box[s][2], s_box[s][3], h, w);
-                const int scls = s_cls[s];
-                const long long sarea = (long long)(sb.xb - sb.xa + 1) * (sb.yb - sb.ya + 1);
-                Cand best{0, 0, 0x7fffffff};
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    if (!open[k] || rcls[k] != scls) continue;
-                    const int iw = min(sb.xb, rb[k].xb) - max(sb.xa, rb[k].xa) + 1, ih = min(sb.yb, rb[k].yb) - max(sb.ya, rb[k].ya) + 1;
-                    if (iw <= 0 || ih <= 0) continue;                       // (an empty slot box never gets here)
-                    const long long inter = (long long)iw * ih, uni = rarea[k] + sarea - inter;
-                    if (inter * 100 < (long long)thr * uni) continue;
-                    const Cand c{inter, uni, 2 * tid + k};
-                    if (better(c, best)) best = c;
-                }
-                for (int off = 32; off > 0; off >>= 1) {
-                    const Cand c{__shfl_xor(best.inter, off), __shfl_xor(best.uni, off), __shfl_xor(best.row, off)};
-                    if (better(c, best)) best = c;
-                }
-                const int buf = s & 1;                                      // (two sets of records: one barrier per slot)
-                if (lane == 0) { s_ri[buf][wave] = best.inter; s_ru[buf][wave] = best.uni; s_rr[buf][wave] = best.row; }
-                __syncthreads();
-                best = Cand{s_ri[buf][0], s_ru[buf][0], s_rr[buf][0]};
-                for (int k = 1; k < TR_WAVES; ++k) {
-                    const Cand c{s_ri[buf][k], s_ru[buf][k], s_rr[buf][k]};
-                    if (better(c, best)) best = c;
-                }
+                const Cand best = slot_best(sb, s_cls[s], thr, open, rcls, rb, rarea, s & 1, s_ri, s_ru, s_rr);   // (two sets of records)
                 if (best.inter <= 0) continue;                              // (the whole workgroup)
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
@@ -154,6 +174,28 @@ __global__ void __launch_bounds__(TR_THREADS) k_track_update(int32_t* state, int
                     for (int c = 0; c < 4; ++c) s_box[s][c] = raw[k][c];
                     s_prob[s] = rprob[k];
                     s_hit[s] = 1;
+                }
+            }
+            if constexpr (WEAK) {
+                // ---- 1B: the slots stage A left alone, in id order, each against the weak rows still open; a round is a slot that goes
+                // again, and the records' sets alternate by rounds (behind the barrier, so stage A's last reads are done)
+                if (__syncthreads_or(wopen[0] || wopen[1])) {
+                    int round = 0;
+                    for (int s = 0; s < n_slots; ++s) {
+                        if (s_hit[s]) continue;                             // (the whole workgroup: written behind slot s's barrier alone)
+                        const Box sb = clipped(s_box[s][0], s_box[s][1], s_box[s][2], s_box[s][3], h, w);
+                        const Cand best = slot_best(sb, s_cls[s], thr, wopen, rcls, rb, rarea, round++ & 1, s_ri, s_ru, s_rr);
+                        if (best.inter <= 0) continue;
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) {
+                            if (2 * tid + k != best.row) continue;
+                            wopen[k] = false; kept_row[k] = true;
+                            rid[k] = s_id[s];
+                            for (int c = 0; c < 4; ++c) s_box[s][c] = raw[k][c];
+                            s_prob[s] = rprob[k];
+                            s_hit[s] = 1;
+                        }
+                    }
                 }
             }
         }
@@ -192,27 +234,39 @@ __global__ void __launch_bounds__(TR_THREADS) k_track_update(int32_t* state, int
         issued += born; overflow += wanted - born; n_slots += born; seen += 1;
         __syncthreads();
         // ---- 4 output: the frame's rows with their ids, the held slots behind them, dead rows behind those
+        int live = n;                                                       // rows of the live part
+        if constexpr (WEAK) {                                               // the strong rows and the matched weak ones move up, order kept
+            int at = block_scan((int)kept_row[0] + (int)kept_row[1], s_w, &live);
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int r = 2 * tid + k;
-            if (r >= n) continue;
-            for (int c = 0; c < 4; ++c) o_box[4 * r + c] = raw[k][c];
-            o_cls[r] = rcls[k]; o_prob[r] = rprob[k]; o_id[r] = rid[k]; o_age[r] = 0;
+            for (int k = 0; k < 2; ++k) {
+                if (!kept_row[k]) continue;                                 // (never set for a row at or behind n)
+                for (int c = 0; c < 4; ++c) o_box[4 * at + c] = raw[k][c];
+                o_cls[at] = rcls[k]; o_prob[at] = rprob[k]; o_id[at] = rid[k]; o_age[at] = 0;
+                ++at;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int r = 2 * tid + k;
+                if (r >= n) continue;
+                for (int c = 0; c < 4; ++c) o_box[4 * r + c] = raw[k][c];
+                o_cls[r] = rcls[k]; o_prob[r] = rprob[k]; o_id[r] = rid[k]; o_age[r] = 0;
+            }
         }
         const int age = tid < n_slots ? s_age[tid] : 0;
         int held = 0;
         const int hp = block_scan(age >= 1, s_w, &held);
         if (age >= 1) {
-            const int r = n + hp, g = grow * age;
+            const int r = live + hp, g = grow * age;
             const Box sb = clipped(s_box[tid][0], s_box[tid][1], s_box[tid][2], s_box[tid][3], h, w);
             o_box[4 * r] = sb.xa - g; o_box[4 * r + 1] = sb.ya - g; o_box[4 * r + 2] = sb.xb + g; o_box[4 * r + 3] = sb.yb + g;
             o_cls[r] = s_cls[tid]; o_prob[r] = s_prob[tid]; o_id[r] = s_id[tid]; o_age[r] = age;
         }
-        for (int r = n + held + tid; r < R; r += TR_THREADS) {
+        for (int r = live + held + tid; r < R; r += TR_THREADS) {
             for (int c = 0; c < 4; ++c) o_box[4 * r + c] = -1;
             o_cls[r] = -1; o_prob[r] = 0; o_id[r] = 0; o_age[r] = 0;
         }
-        if (tid == 0) { o[0] = n + held; o[1] = n; o[2] = issued + 1; o[3] = overflow; }
+        if (tid == 0) { o[0] = live + held; o[1] = live; o[2] = issued + 1; o[3] = overflow; }
     }
     if (nf <= 0) return;                                                    // no frame: the state keeps every word
     __syncthreads();
@@ -251,16 +305,25 @@ int track_check(const char* who, const int32_t* state, int capacity, const int32
 
 void track_launch_at(int32_t* state, int capacity, const int32_t* det, long long det_stride, int first, int frames, int total,
                      const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
-                     int32_t* out, long long out_stride, hipStream_t stream) {
-    k_track_update<<<1, TR_THREADS, 0, stream>>>(state, capacity, det, det_stride, first, frames, total, n_frames, max_rows, tracked, num_classes,
-                                                 thr, hold, grow, h, w, out, out_stride);
+                     int32_t* out, long long out_stride, hipStream_t stream, const float* strong) {
+    if (strong)
+        k_track_update<true><<<1, TR_THREADS, 0, stream>>>(state, capacity, det, det_stride, first, frames, total, n_frames, max_rows, tracked,
+                                                           num_classes, thr, hold, grow, h, w, *strong, out, out_stride);
+    else
+        k_track_update<false><<<1, TR_THREADS, 0, stream>>>(state, capacity, det, det_stride, first, frames, total, n_frames, max_rows, tracked,
+                                                            num_classes, thr, hold, grow, h, w, 0.0f, out, out_stride);
+}
+
+int weak_check(const char* who, float strong) {
+    if (strong != strong) return fail(FRCNN_E_ARG, "%s: strong is NaN", who);
+    return FRCNN_OK;
 }
 
 void track_launch(int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int first, int frames, int total,
                   const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
-                  int32_t* out, long long out_stride, hipStream_t stream) {
+                  int32_t* out, long long out_stride, hipStream_t stream, const float* strong) {
     track_launch_at(state, capacity, det_packed + (long long)first * det_stride, det_stride, first, frames, total, n_frames, max_rows, tracked,
-                    num_classes, thr, hold, grow, h, w, out + (long long)first * out_stride, out_stride, stream);
+                    num_classes, thr, hold, grow, h, w, out + (long long)first * out_stride, out_stride, stream, strong);
 }
 
 }  // namespace frcnn
@@ -274,13 +337,31 @@ extern "C" size_t frcnn_track_state_bytes(int capacity) {
     return 4 * (4 + 8 * (size_t)capacity);
 }
 
+// frcnn_track_update (strong null) and frcnn_track_update_weak
+static int track_update_call(const char* who, int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int frames,
+                             const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h,
+                             int w, const float* strong, int32_t* out, long long out_stride, void* stream) {
+    int bad = track_check(who, state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr,
+                                hold, grow, h, w, out, out_stride);
+    if (!bad && strong) bad = weak_check(who, *strong);
+    if (bad) return bad;
+    track_launch(state, capacity, det_packed, det_stride, 0, frames, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow, h, w, out,
+                 out_stride, as_stream(stream), strong);
+    return check_launch(who);
+}
+
 extern "C" int frcnn_track_update(int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int frames,
                                   const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow,
                                   int h, int w, int32_t* out, long long out_stride, void* stream) {
-    const int bad = track_check("track_update", state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr,
-                                hold, grow, h, w, out, out_stride);
-    if (bad) return bad;
-    track_launch(state, capacity, det_packed, det_stride, 0, frames, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow, h, w, out,
-                 out_stride, as_stream(stream));
-    return check_launch("track_update");
+    return track_update_call("track_update", state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr, hold,
+                             grow, h, w, nullptr, out, out_stride, stream);
+}
+
+extern "C" int frcnn_track_weak_version(void) { return FRCNN_TRACK_WEAK_VERSION; }
+
+extern "C" int frcnn_track_update_weak(int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int frames,
+                                       const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold,
+                                       int grow, int h, int w, float strong, int32_t* out, long long out_stride, void* stream) {
+    return track_update_call("track_update_weak", state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr,
+                             hold, grow, h, w, &strong, out, out_stride, stream);
 }

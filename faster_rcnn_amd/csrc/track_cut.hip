@@ -11,6 +11,7 @@
 #include "../../include/ext/frcnn_hip_track.h"
 #include "../../include/ext/frcnn_hip_track_cut.h"
 #include "../../include/ext/frcnn_hip_track_interval.h"
+#include "../../include/ext/frcnn_hip_track_weak.h"
 #include "track.h"
 #include "track_interval.h"
 #include "track_motion.h"
@@ -114,11 +115,11 @@ extern "C" size_t frcnn_track_cut_workspace_bytes(int frames) {
     return (size_t)(frames + 1) * TC_WORDS * sizeof(int32_t);
 }
 
-extern "C" int frcnn_track_update_cut(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
-                                      const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
-                                      const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h, int w,
-                                      int32_t* out, long long out_stride, int pct, int32_t* workspace, int32_t* cuts, void* stream) {
-    const char* who = "track_update_cut";
+// frcnn_track_update_cut (strong null) and frcnn_track_update_cut_weak
+static int cut_call(const char* who, int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
+                    const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows, const uint8_t* tracked,
+                    int num_classes, int thr, int hold, int grow, int radius, int interval, int h, int w, const float* strong, int32_t* out,
+                    long long out_stride, int pct, int32_t* workspace, int32_t* cuts, void* stream) {
     const int bad = interval_check(who, state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames, max_rows,
                                    tracked, num_classes, thr, hold, grow, radius, interval, h, w, out, out_stride);
     if (bad) return bad;
@@ -126,6 +127,7 @@ extern "C" int frcnn_track_update_cut(int32_t* state, int capacity, uint8_t* mot
         return fail(FRCNN_E_ARG, "%s: pct=%d not in [%d, %d]", who, pct, FRCNN_TRACK_CUT_MIN_PCT, FRCNN_TRACK_CUT_MAX_PCT);
     if (!workspace || !cuts) return fail(FRCNN_E_ARG, "%s: null pointer", who);
     if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(FRCNN_E_ARG, "%s: workspace is not 4-byte aligned", who);
+    if (strong && weak_check(who, *strong)) return FRCNN_E_ARG;
     hipStream_t st = as_stream(stream);
     const int words = (frames + 1) * TC_WORDS;
     k_cut_clear<<<(words + TC_THREADS - 1) / TC_THREADS, TC_THREADS, 0, st>>>(workspace, words);
@@ -139,10 +141,27 @@ extern "C" int frcnn_track_update_cut(int32_t* state, int capacity, uint8_t* mot
         int32_t* o = out + (long long)f * out_stride;
         if (f % interval == 0)
             track_launch_at(state, capacity, det_packed + (long long)(f / interval) * det_stride, det_stride, f, 1, frames, n_frames, max_rows,
-                            tracked, num_classes, thr, hold, grow, h, w, o, out_stride, st);
+                            tracked, num_classes, thr, hold, grow, h, w, o, out_stride, st, strong);
         else
             interval_between_launch(state, capacity, f, frames, n_frames, max_rows, grow, h, w, o, st);
     }
     motion_keep_launch(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w, st);
     return check_launch(who);
+}
+
+extern "C" int frcnn_track_update_cut(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
+                                      const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
+                                      const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h, int w,
+                                      int32_t* out, long long out_stride, int pct, int32_t* workspace, int32_t* cuts, void* stream) {
+    return cut_call("track_update_cut", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames, max_rows,
+                    tracked, num_classes, thr, hold, grow, radius, interval, h, w, nullptr, out, out_stride, pct, workspace, cuts, stream);
+}
+
+extern "C" int frcnn_track_update_cut_weak(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
+                                           const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
+                                           const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h,
+                                           int w, float strong, int32_t* out, long long out_stride, int pct, int32_t* workspace, int32_t* cuts,
+                                           void* stream) {
+    return cut_call("track_update_cut_weak", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames,
+                    max_rows, tracked, num_classes, thr, hold, grow, radius, interval, h, w, &strong, out, out_stride, pct, workspace, cuts, stream);
 }

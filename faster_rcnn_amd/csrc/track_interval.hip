@@ -8,6 +8,7 @@
 #include "../../include/ext/frcnn_hip_redact.h"
 #include "../../include/ext/frcnn_hip_track.h"
 #include "../../include/ext/frcnn_hip_track_interval.h"
+#include "../../include/ext/frcnn_hip_track_weak.h"
 #include "track.h"
 #include "track_interval.h"
 #include "track_motion.h"
@@ -93,13 +94,14 @@ using namespace frcnn;
 
 extern "C" int frcnn_track_interval_version(void) { return FRCNN_TRACK_INTERVAL_VERSION; }
 
-extern "C" int frcnn_track_update_interval(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
-                                           const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
-                                           const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h,
-                                           int w, int32_t* out, long long out_stride, void* stream) {
-    const char* who = "track_update_interval";
-    const int bad = interval_check(who, state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames, max_rows,
+// frcnn_track_update_interval (strong null) and frcnn_track_update_interval_weak
+static int interval_call(const char* who, int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
+                         const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
+                         const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h, int w,
+                         const float* strong, int32_t* out, long long out_stride, void* stream) {
+    int bad = interval_check(who, state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames, max_rows,
                                    tracked, num_classes, thr, hold, grow, radius, interval, h, w, out, out_stride);
+    if (!bad && strong) bad = weak_check(who, *strong);
     if (bad) return bad;
     hipStream_t st = as_stream(stream);
     for (int f = 0; f < frames; ++f) {
@@ -107,10 +109,27 @@ extern "C" int frcnn_track_update_interval(int32_t* state, int capacity, uint8_t
         int32_t* o = out + (long long)f * out_stride;
         if (f % interval == 0)
             track_launch_at(state, capacity, det_packed + (long long)(f / interval) * det_stride, det_stride, f, 1, frames, n_frames, max_rows,
-                            tracked, num_classes, thr, hold, grow, h, w, o, out_stride, st);
+                            tracked, num_classes, thr, hold, grow, h, w, o, out_stride, st, strong);
         else
             interval_between_launch(state, capacity, f, frames, n_frames, max_rows, grow, h, w, o, st);
     }
     motion_keep_launch(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w, st);
     return check_launch(who);
+}
+
+extern "C" int frcnn_track_update_interval(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
+                                           const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
+                                           const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h,
+                                           int w, int32_t* out, long long out_stride, void* stream) {
+    return interval_call("track_update_interval", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames,
+                         max_rows, tracked, num_classes, thr, hold, grow, radius, interval, h, w, nullptr, out, out_stride, stream);
+}
+
+extern "C" int frcnn_track_update_interval_weak(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8,
+                                                long long frame_stride, const int32_t* det_packed, long long det_stride, int frames,
+                                                const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr,
+                                                int hold, int grow, int radius, int interval, int h, int w, float strong, int32_t* out,
+                                                long long out_stride, void* stream) {
+    return interval_call("track_update_interval_weak", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames,
+                         n_frames, max_rows, tracked, num_classes, thr, hold, grow, radius, interval, h, w, &strong, out, out_stride, stream);
 }

@@ -8,6 +8,7 @@
 #include "../../include/ext/frcnn_hip_redact.h"
 #include "../../include/ext/frcnn_hip_track.h"
 #include "../../include/ext/frcnn_hip_track_motion.h"
+#include "../../include/ext/frcnn_hip_track_weak.h"
 #include "track.h"
 #include "track_motion.h"
 #include "track_motion_search.h"
@@ -100,21 +101,39 @@ extern "C" size_t frcnn_track_motion_state_bytes(int h, int w) {
     return TM_HEADER + (size_t)3 * h * w;
 }
 
-extern "C" int frcnn_track_update_motion(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
-                                         const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
-                                         const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int h, int w,
-                                         int32_t* out, long long out_stride, void* stream) {
-    const char* who = "track_update_motion";
+// frcnn_track_update_motion (strong null) and frcnn_track_update_motion_weak
+static int motion_call(const char* who, int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
+                       const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows, const uint8_t* tracked,
+                       int num_classes, int thr, int hold, int grow, int radius, int h, int w, const float* strong, int32_t* out,
+                       long long out_stride, void* stream) {
     int bad = track_check(who, state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow,
                           h, w, out, out_stride);
     if (!bad) bad = motion_check(who, motion_state, frames_u8, frame_stride, frames, radius, h, w);
+    if (!bad && strong) bad = weak_check(who, *strong);
     if (bad) return bad;
     hipStream_t st = as_stream(stream);
     for (int f = 0; f < frames; ++f) {
         motion_search_launch(state, capacity, motion_state, frames_u8, frame_stride, f, frames, n_frames, radius, h, w, st);
         track_launch(state, capacity, det_packed, det_stride, f, 1, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow, h, w, out,
-                     out_stride, st);
+                     out_stride, st, strong);
     }
     motion_keep_launch(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w, st);
     return check_launch(who);
+}
+
+extern "C" int frcnn_track_update_motion(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
+                                         const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
+                                         const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int h, int w,
+                                         int32_t* out, long long out_stride, void* stream) {
+    return motion_call("track_update_motion", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames,
+                       max_rows, tracked, num_classes, thr, hold, grow, radius, h, w, nullptr, out, out_stride, stream);
+}
+
+extern "C" int frcnn_track_update_motion_weak(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8,
+                                              long long frame_stride, const int32_t* det_packed, long long det_stride, int frames,
+                                              const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold,
+                                              int grow, int radius, int h, int w, float strong, int32_t* out, long long out_stride,
+                                              void* stream) {
+    return motion_call("track_update_motion_weak", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames,
+                       n_frames, max_rows, tracked, num_classes, thr, hold, grow, radius, h, w, &strong, out, out_stride, stream);
 }

@@ -321,11 +321,13 @@ class PassSpec:
     remove: object = None                                # (classes, S, T, M), ops.plate_option's form
     track_reid: object = None                            # (pct, keep), ops.track_reid_option's form
     out_size: object = None                              # ("size", W, H) or ("scale", N), ops.scale_form's form: the scale step's target
+    track_strong: object = None                          # T, a float: the Weak rule's ``strong`` (the uploaded det_threshold is then the LOW one)
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
                 track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                track_trails=None, heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None):
+                track_trails=None, heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None,
+                track_strong=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -411,6 +413,13 @@ class PassSpec:
                 raise FrcnnError("submit_batch: track_reid= needs the device-side preprocess: a foreign preprocess_func uploads float "
                                  "pixels, and the signatures are read from the uint8 source frame")
             track_reid = engine.track_reid_option(track_reid)
+        if track_strong is not None:
+            if track is None:
+                raise FrcnnError("submit_batch: track_strong= tells the tracker which rows are strong: pass track=(thr, hold, grow) too")
+            try:
+                track_strong = ops.track_weak_option(track_strong, None)[0]
+            except ValueError as e:
+                raise FrcnnError("submit_batch: track_strong: %s" % e) from None
         if redact is not None:
             redact = engine.redact_option(redact)
         if redact_shape is not None:
@@ -457,7 +466,7 @@ class PassSpec:
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
                    track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove,
-                   track_reid=track_reid, out_size=out_size, redact_shape=redact_shape)
+                   track_reid=track_reid, out_size=out_size, redact_shape=redact_shape, track_strong=track_strong)
 
     def out_hw(self, hw):
         """The size (H, W) of the frames a pass over source frames of ``hw`` = (h, w) encodes and returns: the scale step's target, or
@@ -528,6 +537,8 @@ class PassSpec:
             key = key + ("track_reid",) + self.track_reid
         if self.out_size is not None:
             key = key + ("scale",) + self.out_size
+        if self.track_strong is not None:
+            key = key + ("weak", self.track_strong)
         return key
 
 
@@ -1448,7 +1459,7 @@ class DetectionEntry:
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
                      track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
-                     heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None):
+                     heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None, track_strong=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1596,12 +1607,21 @@ class DetectionEntry:
         of the pass knows: the plate steps, the tracker, the heat map and the drawn boxes keep their rectangles.  ("box", 0) and None ARE
         the pass without it: one spec, one key.  Refused by name, in front of any capture: without ``redact``, for an unknown shape and
         for a feather out of range.  Without it every key and byte is what it was.
+        ``track_strong`` = T (tracking passes only, every form of them; ("weak", T) appended LAST, behind ("scale", ...); a float in
+        0..1): the weak rule (DESIGN §8 "Weak rule"): the tracker call of the pass is its ``strong=T`` form.  ``det_threshold`` stays the
+        value that is uploaded -- what the post-process emits down to, the LOW threshold --, and a row whose score is under T may only
+        continue a track that no strong row continued; every other such row is dropped from the tracked buffer's live part.  The dets
+        ``collect_batch`` returns for a frame are then the KEPT rows -- built from the tracked buffer's live rows, which carry bbox, cls
+        and prob of the packed rows they came from, with their "track_id" --, so "num dets" and everything written from them show kept
+        rows only; every consumer of the tracked buffer (redaction, plate, heat, trails, count, zone, reid, look-back, back-track,
+        drawing) reads it as it is.  Refused by name without ``track`` and for a T outside 0..1.  Without it every key and byte is what
+        it was.
         The order of all these steps in a pass is stated once, in ``frame_edit.EditChain``'s docstring."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
                                 track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove, track_reid=track_reid,
-                                out_size=out_size, redact_shape=redact_shape)
+                                out_size=out_size, redact_shape=redact_shape, track_strong=track_strong)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1866,6 +1886,12 @@ class DetectionEntry:
                 i = f // K
                 packed = s.out_pin[i].numpy()
                 nd, n_rois = int(packed[0]), int(packed[1])
+                if s.track and s.spec.track_strong is not None:    # the weak rule: the dets are the rows of the tracked buffer, the kept ones
+                    n_live, _, dets = ops.tracked_dets(s.track_pin[f].numpy(), rev)      # first, then the held (as a delayed pass reads its own)
+                    if n_live > nd:
+                        raise FrcnnError("tracker: %d live rows for %d detections" % (n_live, nd))
+                    res.append((n_rois, dets) + self._payload(s, f) + self._marks(s, f))
+                    continue
                 rows = (packed.size - 4) // 7
                 bbox = packed[4:4 + 4 * nd].reshape(nd, 4).astype(np.int64)
                 cls = packed[4 + 4 * rows:4 + 4 * rows + nd].copy()

@@ -267,15 +267,17 @@ class EditChain:
         if self.track_out is None:                       # (the first call: the rows of a packed buffer are known now)
             self.track_out = torch.zeros((self.F, 4 + 8 * (ops.track_rows(packed) + cap)), dtype=torch.int32, device="cuda")
         common = (packed, n_frames, self.track_table, h, w, thr, hold, grow)
+        strong = sp.track_strong                         # (None: the Tracking rule; else the Weak rule, whichever form the call has)
         if sp.track_scene_cut:
             ops.track_update_cut(self.state, self.motion, frames_u8, frame_stride, *common, sp.track_motion, K, sp.track_scene_cut,
-                                 out=self.track_out, cuts=self.cuts, workspace=self.cut_ws)
+                                 out=self.track_out, cuts=self.cuts, workspace=self.cut_ws, strong=strong)
         elif sp.detect_every:
-            ops.track_update_interval(self.state, self.motion, frames_u8, frame_stride, *common, sp.track_motion, K, out=self.track_out)
+            ops.track_update_interval(self.state, self.motion, frames_u8, frame_stride, *common, sp.track_motion, K, out=self.track_out,
+                                      strong=strong)
         elif sp.track_motion:
-            ops.track_update_motion(self.state, self.motion, frames_u8, frame_stride, *common, sp.track_motion, out=self.track_out)
+            ops.track_update_motion(self.state, self.motion, frames_u8, frame_stride, *common, sp.track_motion, out=self.track_out, strong=strong)
         else:
-            ops.track_update(self.state, *common, out=self.track_out)
+            ops.track_update(self.state, *common, out=self.track_out, strong=strong)
         self.tracked = self.track_out
         if sp.track_reid:
             if self.reid_ws is None:

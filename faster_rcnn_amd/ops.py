@@ -1561,7 +1561,31 @@ def _track_motion_args(mstate, frames_u8, frame_stride, frames, h, w):
     assert int(frames_u8.numel()) >= (frames - 1) * int(frame_stride) + 3 * int(h) * int(w) and int(frame_stride) >= 0
 
 
-def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, out=None):
+def track_weak_option(det_threshold=None, low=None, track=True):
+    """(host only) The pair (``det_threshold``, ``low``) of the Weak rule (DESIGN §8 "Weak rule") checked -> (T, L): T a float in 0..1, None
+    read as 0.0; L None (no weak rows: the Tracking rule) or a float in 0..1 with L < T, which needs ``track``.  With an L the detector
+    emits rows down to L and the tracker is told ``strong`` = T.  ValueError with the reason, by name."""
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError("%s=%r: a number in 0..1" % (name, v))
+        return float(v)
+    T = 0.0 if det_threshold is None else number("det threshold", det_threshold)
+    if low is None:
+        return T, None
+    L = number("track low", low)
+    if not track:
+        raise ValueError("track low=%r needs tracking (track): a weak row can only continue a track" % (low,))
+    if not L < T:
+        raise ValueError("track low=%r must be below det threshold=%r: the rows between the two are the weak ones" % (low, T))
+    return T, L
+
+
+def _weak(name, strong):
+    """The entry point and the arguments in front of ``out`` for ``strong``: None is the parent call."""
+    return (name, ()) if strong is None else (name + "_weak", (float(strong),))
+
+
+def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, out=None, strong=None):
     """The tracking rule (DESIGN §8 "Tracking rule", frcnn_track_update) over the frames of ``det_packed`` IN ORDER, in one launch:
     ``state`` (``track_state``) is read and advanced, and frame f's tracked buffer lands in ``out[f]`` -- -> ``out``, a (B, 4 + 8R) int32
     tensor, R = the packed buffers' rows + the state's capacity (``split_tracked`` cuts it up; ``redact_u8`` and ``annotate_u8`` take
@@ -1569,12 +1593,15 @@ def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=
     (B, words) tensor, or a list of B buffers of one size -- used where they lie when they are evenly spaced in memory (the stride is an
     argument of the call), else gathered with one copy.  ``n_frames``: an int32 device tensor whose first word says how many of the B
     frames are real; the rest is a short pass's padding and leaves the state alone.  ``table``: ``track_table``.  (h, w): the frame's size.
-    Reads *n_dets and *n_frames on the device: the call can be captured in a graph."""
+    ``strong``: None, or a float for the Weak rule (DESIGN §8 "Weak rule", frcnn_track_update_weak; the same argument of the three forms
+    below): a row with a score under it may only continue a track that no other row continued, and is dropped from the live part otherwise,
+    so n_live <= *n_dets.  Reads *n_dets and *n_frames on the device: the call can be captured in a graph."""
     _require_gpu()
     base, stride, B, words = _track_packed(det_packed)
     cap, rows, R, out = _track_update_args(state, n_frames, table, words, B, out)
-    _lib.call("frcnn_track_update", _p(state), cap, _p(base), int(stride), B, _p(n_frames), rows, _p(table), int(table.numel()),
-              int(thr), int(hold), int(grow), int(h), int(w), _p(out), 4 + 8 * R, _stream())
+    name, weak = _weak("frcnn_track_update", strong)
+    _lib.call(name, _p(state), cap, _p(base), int(stride), B, _p(n_frames), rows, _p(table), int(table.numel()),
+              int(thr), int(hold), int(grow), int(h), int(w), *weak, _p(out), 4 + 8 * R, _stream())
     return out
 
 
@@ -1607,7 +1634,8 @@ def track_motion_reset(mstate):
     return mstate
 
 
-def track_update_motion(state, mstate, frames_u8, frame_stride, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, radius=8, out=None):
+def track_update_motion(state, mstate, frames_u8, frame_stride, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, radius=8, out=None,
+                        strong=None):
     """``track_update`` with the motion step in front of every frame's match (DESIGN §8 "Motion rule", frcnn_track_update_motion): every
     live slot's box is first moved by the best integer shift of the pixels under it, found by a block match of radius ``radius`` between
     the frame before and this one, so that a held box follows its object.  ``mstate`` (``track_motion_state(h, w)``) carries the last frame
@@ -1618,8 +1646,10 @@ def track_update_motion(state, mstate, frames_u8, frame_stride, det_packed, n_fr
     base, stride, B, words = _track_packed(det_packed)
     _track_motion_args(mstate, frames_u8, frame_stride, B, h, w)
     cap, rows, R, out = _track_update_args(state, n_frames, table, words, B, out)
-    _lib.call("frcnn_track_update_motion", _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), B, _p(n_frames),
-              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), int(h), int(w), _p(out), 4 + 8 * R, _stream())
+    name, weak = _weak("frcnn_track_update_motion", strong)
+    _lib.call(name, _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), B, _p(n_frames),
+              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), int(h), int(w), *weak, _p(out), 4 + 8 * R,
+              _stream())
     return out
 
 
@@ -1635,7 +1665,7 @@ def track_interval_option(k):
 
 
 def track_update_interval(state, mstate, frames_u8, frame_stride, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, radius=8, interval=1,
-                          out=None):
+                          out=None, strong=None):
     """``track_update_motion`` with the detector on every ``interval``-th frame only (DESIGN §8 "Interval rule", frcnn_track_update_interval):
     ``det_packed`` holds the packed buffers of the KEY frames 0, interval, 2 interval, ... of the call -- B of them, as ``track_update``
     takes them --, ``frames_u8`` the F source frames, key and between, ``frame_stride`` bytes apart, with (F + interval - 1) // interval ==
@@ -1652,9 +1682,10 @@ def track_update_interval(state, mstate, frames_u8, frame_stride, det_packed, n_
                               % (interval, _lib.TRACK_INTERVAL[1], F, B))
     _track_motion_args(mstate, frames_u8, frame_stride, F, h, w)
     cap, rows, R, out = _track_update_args(state, n_frames, table, words, F, out)
-    _lib.call("frcnn_track_update_interval", _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), F, _p(n_frames),
-              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), interval, int(h), int(w), _p(out), 4 + 8 * R,
-              _stream())
+    name, weak = _weak("frcnn_track_update_interval", strong)
+    _lib.call(name, _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), F, _p(n_frames),
+              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), interval, int(h), int(w), *weak, _p(out),
+              4 + 8 * R, _stream())
     return out
 
 
@@ -1683,7 +1714,7 @@ def track_cut_workspace(frames):
 
 
 def track_update_cut(state, mstate, frames_u8, frame_stride, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, radius=8, interval=1,
-                     pct=None, out=None, cuts=None, workspace=None):
+                     pct=None, out=None, cuts=None, workspace=None, strong=None):
     """``track_update_interval`` (``interval`` 1: ``track_update_motion``) with the cut step in front of every frame (DESIGN §8 "Cut rule",
     frcnn_track_update_cut): a frame whose 4 x 4-region luma histogram differs from that of the frame before -- for the call's first
     frame: the kept frame of ``mstate``, when it is the frame before -- by ``pct`` percent (``track_cut_option``) of the largest distance
@@ -1707,9 +1738,10 @@ def track_update_cut(state, mstate, frames_u8, frame_stride, det_packed, n_frame
         workspace = track_cut_workspace(F)
     assert cuts.is_cuda and cuts.dtype == torch.int32 and cuts.is_contiguous() and cuts.numel() == F
     assert workspace.is_cuda and workspace.dtype == torch.int32 and workspace.is_contiguous() and workspace.numel() >= 512 * (F + 1)
-    _lib.call("frcnn_track_update_cut", _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), F, _p(n_frames),
-              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), interval, int(h), int(w), _p(out), 4 + 8 * R,
-              pct, _p(workspace), _p(cuts), _stream())
+    name, weak = _weak("frcnn_track_update_cut", strong)
+    _lib.call(name, _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), F, _p(n_frames),
+              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), interval, int(h), int(w), *weak, _p(out),
+              4 + 8 * R, pct, _p(workspace), _p(cuts), _stream())
     return out, cuts
 
 

@@ -32,7 +32,7 @@ without and with ``--detect_every 4``.  ``--track_backtrack`` (``run_track_backt
 ``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
 look-back call of one pass alone.  ``--track_scene_cut`` (``run_track_scene_cut``) runs the ``--track --track_motion 8`` leg without and with
 ``--track_scene_cut`` at its default.  ``--track_trails`` (``run_track_trails``) runs the same leg without and with ``--track_trails`` at its
-defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--out_scale`` (``run_out_scale``) runs in-memory annotating passes, the PNG-file to PNG-file leg (device encoder, huffman) and y4m to y4m, each without and with ``--out_scale 2``.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).  ``--redact_shape`` (``run_redact_shape``) runs the ``--redact all --redact_mode blur`` passes without and with ``--redact_shape ellipse --redact_feather 8``.
+defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--out_scale`` (``run_out_scale``) runs in-memory annotating passes, the PNG-file to PNG-file leg (device encoder, huffman) and y4m to y4m, each without and with ``--out_scale 2``.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).  ``--redact_shape`` (``run_redact_shape``) runs the ``--redact all --redact_mode blur`` passes without and with ``--redact_shape ellipse --redact_feather 8``.  ``--track_low`` (``run_track_low``) runs the ``--det_threshold 0.5 --track --track_motion 8`` leg without and with ``--track_low 0.1``.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
@@ -86,16 +86,17 @@ def annotate_in_memory(eng, resized, ratios, **kwargs):
     """(b): the frames through annotating passes, eng.batch per pass, eng.in_flight passes in flight (annotate_images' loop
     without the files).  ``kwargs``: further arguments of submit_batch (``redact``).  With ``track_lookback`` a flush submit ends the
     list: the passes return the frames of the pass before.  With ``detect_every`` = K a pass takes eng.batch * K frames and every K-th
-    of them is one of its images."""
+    of them is one of its images.  ``det_threshold`` (0.0): the score threshold every pass uploads."""
     B, window, frames = eng.batch, [], []
+    thr = kwargs.pop("det_threshold", 0.0)
     K = kwargs.get("detect_every") or 1
     for i in range(0, len(resized), B * K):
         part = resized[i:i + B * K]
-        window.append(eng.submit_batch(part[::K], ratios[i:i + B * K:K], 0.0, [eng.host_pixels(r) for r in part], batch=B, annotate=True, **kwargs))
+        window.append(eng.submit_batch(part[::K], ratios[i:i + B * K:K], thr, [eng.host_pixels(r) for r in part], batch=B, annotate=True, **kwargs))
         if len(window) >= eng.in_flight:
             frames += [r[2] for r in eng.collect_batch(window.pop(0))]
     if kwargs.get("track_lookback") is not None or kwargs.get("track_backtrack") is not None:
-        window.append(eng.submit_batch([], [], 0.0, [], batch=B, annotate=True, **kwargs))
+        window.append(eng.submit_batch([], [], thr, [], batch=B, annotate=True, **kwargs))
     while window:
         frames += [r[2] for r in eng.collect_batch(window.pop(0))]
     assert len(frames) == len(resized)
@@ -640,6 +641,55 @@ def run_track_trails(name, cfg, n_frames, reps, content="noise"):
         res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
         res[k + "_runs_s"] = [round(t, 4) for t in ts]
     res["trails_over_motion"] = round(statistics.median(times["track_motion"]) / statistics.median(times["track_trails"]), 3)
+    return res
+
+
+WEAK_LEG = (0.5, 0.1)                                     # --det_threshold T --track_low L
+
+
+def run_track_low(name, cfg, n_frames, reps, content="noise"):
+    """``--track_low``: what the weak rule costs on top of ``--det_threshold 0.5 --track --track_motion 8 --redact all --redact_mode blur``.
+    One pair of legs in ONE session, alternating inside every repetition: the passes at det_threshold 0.5, and the passes at det_threshold
+    0.1 with ``track_strong=0.5`` (the tracker is reset in front of every run).  Reports frames/s of both, their ratio, and the rows the
+    last weak run emitted.  The second leg's post-process emits MORE rows (everything down to 0.1), so the figure is the cost of the
+    option as a user meets it, not of the kernel's stage B alone.  Not measured: real footage (missed frames, id switches)."""
+    import numpy as np
+    from faster_rcnn_amd import entry, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+    T, L = WEAK_LEG
+
+    def leg(**kw):
+        def run():
+            eng.track_reset()
+            return annotate_in_memory(eng, resized, ratios, redact=REDACT_LEG, track=TRACK_LEG, track_motion=MOTION_LEG, **kw)
+        return run
+
+    legs = {"det_threshold": leg(det_threshold=T), "track_low": leg(det_threshold=L, track_strong=T)}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    import torch
+    torch.cuda.synchronize()
+    state = eng.track_state().cpu().numpy()
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact": ["all", "blur", 12, 0], "track": list(TRACK_LEG), "track_motion": MOTION_LEG, "det_threshold": T, "track_low": L,
+           "images_per_pass": eng.batch, "in_flight": eng.in_flight,
+           "tracker_after_track_low": {"slots": int(state[0]), "ids_issued": int(state[1]), "overflow": int(state[2]), "frames": int(state[3])}}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["track_low_over_det_threshold"] = round(statistics.median(times["det_threshold"]) / statistics.median(times["track_low"]), 3)
     return res
 
 
@@ -1200,6 +1250,8 @@ def main():
                                                              "alternating in one session")
     ap.add_argument("--redact_shape", action="store_true", help="instead of the legs above: the --redact all --redact_mode blur leg without and "
                                                                 "with --redact_shape ellipse --redact_feather 8, alternating in one session")
+    ap.add_argument("--track_low", action="store_true", help="instead of the legs above: the --det_threshold 0.5 --track --track_motion 8 "
+                                                             "leg without and with --track_low 0.1, alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -1208,6 +1260,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.track_low:
+            out[name] = run_track_low(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.redact_shape:
             out[name] = run_redact_shape(name, PAIRS[name], args.frames, args.reps, args.content)
