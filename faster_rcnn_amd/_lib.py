@@ -411,6 +411,18 @@ REDACT_SHAPE_SIGNATURES = {
 REDACT_SHAPES = {"box": 0, "ellipse": 1}                                           # FRCNN_REDACT_SHAPE_BOX / _ELLIPSE
 REDACT_FEATHER = (0, 32)                                                           # 0..FRCNN_REDACT_FEATHER_MAX
 
+REDACT_REGION_VERSION = 1       # include/ext/frcnn_hip_redact_region.h FRCNN_REDACT_REGION_VERSION
+REDACT_REGION_SIGNATURES = {
+    "frcnn_redact_region_version": (I, []),
+    "frcnn_redact_region_plane_bytes": (c_size_t, [I, I]),
+    "frcnn_redact_region_build": (I, [P, I, I, P, P, I, P, I, P]),
+    "frcnn_redact_region_prepare": (I, [P, I, I, P, I, I, P, c_size_t, P]),
+    "frcnn_redact_region_apply_u8": (I, [P, I, I, P, I, I, P, c_size_t, P]),
+}
+REDACT_REGION_MAX = 8                                                              # FRCNN_REDACT_REGION_MAX
+REDACT_REGION_FEATHER = (0, 32)                                                    # 0..FRCNN_REDACT_REGION_FEATHER_MAX
+REDACT_REGION_HEAD_WORDS = 8                                                       # FRCNN_REDACT_REGION_HEAD_WORDS
+
 TRACK_VERSION = 1               # include/ext/frcnn_hip_track.h FRCNN_TRACK_VERSION
 TRACK_MAX = 128                 # ... FRCNN_TRACK_MAX: slots of a state
 TRACK_MAX_FRAMES = 64           # ... FRCNN_TRACK_MAX_FRAMES: frames of one call
@@ -862,6 +874,15 @@ def load():
     if lib.frcnn_redact_shape_version() != REDACT_SHAPE_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_shape_version()} of the shaped-redaction extension, this binding "
                          f"{REDACT_SHAPE_VERSION} (include/ext/frcnn_hip_redact_shape.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in REDACT_REGION_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_redact_region.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_redact_region_version() != REDACT_REGION_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_region_version()} of the region-redaction extension, this binding "
+                         f"{REDACT_REGION_VERSION} (include/ext/frcnn_hip_redact_region.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -146,6 +146,19 @@ measured) is the weak rule (DESIGN §8 "Weak rule", the ``strong=`` form of the 
 with det_threshold=L and track_strong=T, a detection with a score in [L, T) may only continue a track no stronger one continued and is
 dropped otherwise, and every printed line and ``tracks_out`` show the kept rows.  The eager path (a foreign model) takes
 ``det_threshold`` and refuses ``track_low`` by name.  Without the two, no pass, key, printed line or output byte changes.
+``redact_region=(regions, mask, mode, size, feather)`` (``--redact_region X1,Y1,X2,Y2,X3,Y3[,...]``, repeatable up to 8 times, ``--zone``'s
+grammar; ``--redact_mask PATH.png``, any file PIL opens, read as grey, >= 128 hides; ``--region_mode pixelate|blur|fill``, default fill;
+``--region_size N``; ``--region_feather N``, 0..32, default 0) hides PLACES, not objects: a burnt-in timestamp, a monitor, a window, the
+bonnet (ops.redact_region_plane / ops.redact_region_prepare / ops.redact_region_apply_u8, csrc/redact_region.hip; DESIGN §8 "Region
+rule").  Polygons -- exact even-odd interior, a polygon owns its left and top boundary -- and the mask become one plane of weights per
+frame size on the device, once; every frame is then blended under it inside its pass with no detection row involved: what replaces an
+area comes from the untouched frame, the area goes on behind the plate fill of ``--remove`` (no learned background returns into it) and
+under the heat map, lines, boxes and labels, and the edge fades OUTWARDS over the feather.  It needs neither ``--redact`` nor
+``--track`` and works with every option, input and encoder.  Polygons apply to every frame size; a mask is held to one size, and a frame
+it does not fit is refused by name.  ``--plate_out`` shows every pixel of an area black; ``--heatmap_out``, ``--tracks_out`` and every
+per-frame line are unchanged; at the end one line per frame size is printed: ``redact regions 1242x375: 2 regions + mask, 12.3 % of the
+frame hidden``.  The three ``--region_*`` flags are refused by name without an area.  Without the option, no pass, key, printed line or
+output byte changes.
 """
 import collections
 import os
@@ -343,7 +356,7 @@ def _eager_heat_state(class_mapping, h, w):
 
 def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
                track_trails=None, rgb=False, heatmap=None, count=None, zone=None, remove=None, track_reid=None, out_size=None,
-               redact_shape=None):
+               redact_shape=None, redact_region=None):
     """The editing chain over ONE frame and its host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is edited in
     place, by a one-frame ``frame_edit.EditChain`` -- its docstring states the calls and their order -- on this class mapping's eager
     states (``reset_tracks``, ``reset_heat`` and ``reset_counts`` empty them); ``rgb``: the frame's channel order (False: B, G, R).
@@ -364,9 +377,14 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     ``out_size`` = ("size", W, H) or ("scale", N): the LAST step (DESIGN §8 "Scale rule", ops.downscale_u8): the edited frame scaled down
     on the device is what is returned, a new (H, W, 3) array; ``frame`` is edited in place as without it.
     ``redact_shape`` = (shape, feather) (with ``redact``): the redaction hides ellipses and fades out over ``feather`` pixels (DESIGN §8
-    "Shape rule", ops.redact_shaped_u8); ("box", 0) is the call without it."""
+    "Shape rule", ops.redact_shaped_u8); ("box", 0) is the call without it.
+    ``redact_region`` = (regions, mask, mode, size, feather): the static areas are hidden whatever ``dets`` holds (DESIGN §8 "Region
+    rule", ops.redact_region_prepare / ops.redact_region_apply_u8); the plane of the frame's size is this class mapping's."""
     import torch
     redact_shape = _redact_shape(redact_shape, redact)
+    redact_region = _redact_region(redact_region)
+    if redact_region is not None and redact_region[1] is not None and redact_region[1].shape != tuple(frame.shape[:2]):
+        raise ValueError("redact_region: the mask is %dx%d, the frame %dx%d" % (redact_region[1].shape[::-1] + (frame.shape[1], frame.shape[0])))
     scaled_hw = None if out_size is None else ops.scale_option(out_size, frame.shape[:2])
     track_reid = _track_reid(track_reid, track)
     track_trails = _track_trails(track_trails, track, draw)
@@ -376,7 +394,7 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     zone = _zone(zone, track)
     radius = _track_motion(track_motion, track)
     track_scene_cut = _track_scene_cut(track_scene_cut, track, track_motion, None, None)
-    if track is not None or heatmap is not None or remove is not None or (dets and (draw or redact is not None)):      # (else the frame stays as it is)
+    if track is not None or heatmap is not None or remove is not None or redact_region is not None or (dets and (draw or redact is not None)):      # (else the frame stays as it is)
         dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
         packed = torch.from_numpy(_pack_dets(dets, class_mapping)).cuda()
         if redact is not None:
@@ -384,7 +402,7 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
         states = _eager_states(class_mapping)
         spec = entry.PassSpec(annotate=True, redact=redact, draw=draw, track=track, track_scene_cut=track_scene_cut, track_trails=track_trails,
                               track_motion=radius, heat=heatmap, count=count, zone=zone, remove=remove, track_reid=track_reid,
-                              redact_shape=redact_shape)
+                              redact_shape=redact_shape, redact_region=redact_region)
         chain = EditChain(states, spec, 1, 1, frame.shape[:2], rgb)
         chain.update(dev.view(-1), 0, packed, states.one_frame())         # (in front of the edits: ``dev`` is still the frame as it came)
         chain.edit(0, dev)
@@ -446,6 +464,72 @@ def _redact_shape(redact_shape, redact):
         raise ValueError("redact_shape=%r: (shape, feather)" % (redact_shape,)) from None
     option = ops.redact_shape_option(shape, feather)
     return None if option == ("box", 0) else option
+
+
+def _redact_region(redact_region):
+    """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame`` / ``draw_eager``'s ``redact_region`` checked -> (regions, mask,
+    mode, size, feather) in ops.redact_region_option's form, or None.  ValueError with the reason."""
+    if redact_region is None:
+        return None
+    try:
+        regions, mask, mode, size, feather = redact_region
+    except (TypeError, ValueError):
+        raise ValueError("redact_region=%r: (regions, mask, mode, size, feather)" % (redact_region,)) from None
+    return ops.redact_region_option(regions, mask, mode, size, feather)
+
+
+def redact_region_from_args(args):
+    """(host only) The static areas the command line asks for -> (regions, mask, mode, size, feather) as
+    ``submit_batch(redact_region=...)`` takes it, or None without ``--redact_region`` / ``--redact_mask``.  Every ``--redact_region``
+    takes ``--zone``'s grammar; ``--redact_mask`` is read through PIL, ``convert("L")``.  ValueError, with the reason, for
+    ``--region_mode`` / ``--region_size`` / ``--region_feather`` without either, for a polygon the rule refuses, a file PIL cannot open
+    and a value out of range."""
+    specs, path = args.redact_region or [], args.redact_mask
+    if not specs and path is None:
+        for flag, value in (("--region_mode", args.region_mode), ("--region_size", args.region_size), ("--region_feather", args.region_feather)):
+            if value is not None:
+                raise ValueError("%s=%s is a setting of the static areas: it needs --redact_region X1,Y1,X2,Y2,X3,Y3[,...] or --redact_mask "
+                                 "PATH" % (flag, value))
+        return None
+    regions = []
+    for spec in specs:
+        parts = [v.strip() for v in spec.split(",")]
+        if len(parts) < 6 or len(parts) % 2 or not all(re.fullmatch(r"[+-]?\d+", v) for v in parts):
+            raise ValueError("--redact_region=%s: X1,Y1,X2,Y2,X3,Y3[,...], an even number of integers, six at least" % spec)
+        v = [int(x) for x in parts]
+        regions.append(tuple(zip(v[0::2], v[1::2])))
+    mask = None
+    if path is not None:
+        from PIL import Image
+        try:
+            with Image.open(path) as im:
+                mask = np.asarray(im.convert("L"), dtype=np.uint8)
+        except (OSError, ValueError) as e:
+            raise ValueError("--redact_mask=%s: %s" % (path, e)) from None
+    try:
+        return ops.redact_region_option(tuple(regions), mask, args.region_mode, args.region_size, args.region_feather)
+    except ValueError as e:
+        raise ValueError("--redact_region / --redact_mask: %s" % e) from None
+
+
+def region_line(w, h, option, stats):
+    """The line printed at the end for the frame size (w, h): ``redact regions 1242x375: 2 regions + mask, 12.3 % of the frame hidden``
+    -- ``stats``: ops.redact_region_stats of the size's plane; hidden counts every pixel with W > 0."""
+    regions, mask = option[0], option[1]
+    what = []
+    if regions:
+        what.append("%d region%s" % (len(regions), "" if len(regions) == 1 else "s"))
+    if mask is not None:
+        what.append("mask")
+    return "redact regions %dx%d: %s, %.1f %% of the frame hidden" % (w, h, " + ".join(what), 100.0 * stats["covered"] / (w * h))
+
+
+def blacken_plate(image, weights):
+    """(host only) ``image``, an (h, w, 3) plate picture, with every pixel whose region weight in ``weights`` ((h, w), W of the plane) is
+    > 0 written black -> a new array: the plate picture never shows a static area in clear."""
+    out = np.array(image, copy=True)
+    out[np.asarray(weights) > 0] = 0
+    return out
 
 
 def redact_shape_from_args(args):
@@ -1173,6 +1257,13 @@ def _plate_states(training_manager, eng):
     return {key: st.cpu().numpy() for key, st in states.plate.items()}
 
 
+def _region_weights(training_manager, eng, h, w, option):
+    """W, (h, w) uint16, of the plane of the region option ``option`` for frames of (h, w) in the states of ``eng``, or of the eager
+    path with None."""
+    states = eng.edit_states if eng is not None else _eager_states(training_manager.class_mapping)
+    return ops.redact_region_weights(states.region_plane(h, w, option))
+
+
 def reset_plate(training_manager, detector, in_flight=1, post=None):
     """An empty plate before a new sequence: the states of the engine ``in_flight`` names, or the eager path's."""
     eng = _engine(training_manager, detector, in_flight, post)
@@ -1235,7 +1326,7 @@ def _print_drawn(dets, width, height):
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
                         track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, track_reid=None,
-                        reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None):
+                        reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None):
     """(``det_threshold`` / ``track_low``: as ``annotate_images``.)
     annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
@@ -1268,9 +1359,15 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     rule") and the scaled frame, a new (H, W, 3) array, is returned in ``frame``'s place; the dets, the printed lines and every file
     written stay in the coordinates of ``frame``.  ValueError for a target the rule refuses for this frame.
     ``redact_shape`` = (shape, feather) (with ``redact``): the boxes hide the ellipses inscribed in them and the replacement fades out
-    over ``feather`` pixels outside the shape (DESIGN §8 "Shape rule"); ("box", 0) and None: every byte is what it was."""
+    over ``feather`` pixels outside the shape (DESIGN §8 "Shape rule"); ("box", 0) and None: every byte is what it was.
+    ``redact_region`` = (regions, mask, mode, size, feather): the static areas are hidden in the frame whatever is detected (DESIGN §8
+    "Region rule"); a mask must have the frame's size.  None: every byte is what it was."""
     post = None if post is None else ops.det_post_option(post)
     redact_shape = _redact_shape(redact_shape, redact)
+    redact_region = _redact_region(redact_region)
+    if redact_region is not None and redact_region[1] is not None and redact_region[1].shape != tuple(frame.shape[:2]):
+        raise ValueError("redact_region: the mask is %dx%d, frame %s is %dx%d"
+                         % (redact_region[1].shape[1], redact_region[1].shape[0], frame_no, frame.shape[1], frame.shape[0]))
     if out_size is not None:
         scaled_size(out_size, frame_no, frame.shape[1], frame.shape[0])
     track_reid = _track_reid(track_reid, track)
@@ -1313,6 +1410,8 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         motion["track_reid"] = track_reid
     if redact_shape is not None:
         motion["redact_shape"] = redact_shape
+    if redact_region is not None:
+        motion["redact_region"] = redact_region
     strong, low = _det_thresholds(det_threshold, track_low, track)    # (the pair itself, in front of the engine)
     eng = _engine(training_manager, detector, 1, post)
     _det_thresholds(det_threshold, track_low, track, eager=eng is None)      # (a foreign model refuses an L, in front of any work)
@@ -1756,7 +1855,7 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
               track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None,
               plate_out=None, track_reid=None, reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None,
-              track_low=None):
+              track_low=None, redact_region=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
@@ -1791,8 +1890,22 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     redact_shape = _redact_shape(redact_shape, redact)    # (refused here, in front of any capture)
     if redact_shape is not None:
         motion["redact_shape"] = redact_shape
+    redact_region = _redact_region(redact_region)         # (refused here, in front of any capture)
+    if redact_region is not None:
+        motion["redact_region"] = redact_region
     counts_log = zones_log = reid_log = None
     sink = make_sink()
+    region_sizes = set()                                  # the (h, w) of the frames met: a line per size at the end
+    if redact_region is not None:                         # a frame the mask does not fit is refused by name, on both paths
+        region_check, region_mask = sink.check, redact_region[1]
+
+        def check_region(label, frame):
+            if region_mask is not None and region_mask.shape != (frame.height, frame.width):
+                raise ValueError("redact_region: the mask is %dx%d, %s is %dx%d: a mask is held to one frame size"
+                                 % (region_mask.shape[1], region_mask.shape[0], label, frame.width, frame.height))
+            region_sizes.add((frame.height, frame.width))
+            region_check(label, frame)
+        sink.check = check_region
     if out_size is not None:                              # a frame the target does not fit is refused by name, on both paths
         sink_check = sink.check
 
@@ -1848,6 +1961,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
                 kwargs.update(out_size=out_size)
             if redact_shape is not None:
                 kwargs.update(redact_shape=redact_shape)
+            if redact_region is not None:
+                kwargs.update(redact_region=redact_region)
             mapping = training_manager.class_mapping
 
             def prepare(label, frame):                    # (read-ahead thread) -> (label, frame, resized, ratio, pixels)
@@ -1892,7 +2007,14 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             plates = plate_summaries(_plate_states(training_manager, eng))
             print_plates(plates)
             if plate_out is not None:
+                if redact_region is not None:             # the plate picture never shows a static area in clear
+                    plates = {key: (frames_, known, blacken_plate(plate, _region_weights(training_manager, eng, key[0], key[1], redact_region)))
+                              for key, (frames_, known, plate) in plates.items()}
                 write_plates(plate_out, plates)
+        if redact_region is not None:                     # (host only: the planes' headers read back)
+            for h, w in sorted(region_sizes):
+                states = eng.edit_states if eng is not None else _eager_states(training_manager.class_mapping)
+                print(region_line(w, h, redact_region, ops.redact_region_stats(states.region_plane(h, w, redact_region))))
     finally:
         if counts_log is not None:
             counts_log.close()
@@ -1908,8 +2030,9 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
                     track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
                     counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None, reid_out=None, post=None,
-                    out_size=None, redact_shape=None, det_threshold=None, track_low=None):
-    """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
+                    out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None):
+    """(``redact_region``: as ``annotate_images``.)
+    ``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
     every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
@@ -1926,7 +2049,7 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
               detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
               heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out, remove=remove,
               plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size, redact_shape=redact_shape,
-              det_threshold=det_threshold, track_low=track_low)
+              det_threshold=det_threshold, track_low=track_low, redact_region=redact_region)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
@@ -1934,7 +2057,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
                     heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None,
-                    reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None):
+                    reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -2010,7 +2133,15 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     track_strong = T), a row with a score in [L, T) may only continue a track that no row of T or more continued, and every other such
     row is dropped -- so an object whose score dips stays covered by the detector's own box, under its id, and nothing new is reported
     under T.  "num dets", the printed lines and ``tracks_out`` show the kept rows.  Refused by name without ``track``, for L >= T and
-    outside 0..1, and on the eager path (a foreign model).  None and None: no pass, key, printed line or output byte changes."""
+    outside 0..1, and on the eager path (a foreign model).  None and None: no pass, key, printed line or output byte changes.
+    ``redact_region``: (regions, mask, mode, size, feather) as ``redact_region_from_args`` returns it (with every option above, with and
+    without ``redact`` and ``track``) -- static areas, polygons in source-frame pixels and a painted mask whose bytes >= 128 hide, are
+    hidden in EVERY frame whatever the detector says (DESIGN §8 "Region rule"): what replaces them comes from the untouched frame, they
+    are blended in behind the plate fill of ``remove`` and under the heat map and everything drawn, and the edge fades outwards over
+    ``feather`` pixels.  Polygons apply to every frame size; a mask is held to one, and a frame it does not fit is refused by name.
+    ``plate_out`` then shows every pixel of an area black.  A line ``redact regions 1242x375: 2 regions + mask, 12.3 % of the frame
+    hidden`` is printed per frame size at the end; every other printed line and file is unchanged.  None: no pass, key, printed line or
+    output byte changes."""
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
@@ -2025,7 +2156,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
               track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out,
               remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size,
-              redact_shape=redact_shape, det_threshold=det_threshold, track_low=track_low)
+              redact_shape=redact_shape, det_threshold=det_threshold, track_low=track_low, redact_region=redact_region)
 
 
 def build_parser():
@@ -2101,6 +2232,21 @@ def build_parser():
                         "grown by --redact_margin, not clipped to the frame (needs --redact)")
     p.add_argument("--redact_feather", dest="redact_feather", type=int, default=None, metavar="N",
                    help="the redaction fades into the scene over N pixels OUTSIDE the shape, 0..32 (default 0: a hard edge; needs --redact)")
+    p.add_argument("--redact_region", dest="redact_region", action="append", default=None, metavar="X1,Y1,X2,Y2,X3,Y3[,...]",
+                   help="hide a static area in EVERY frame, whatever is detected: a polygon of 3..16 vertices in source-frame pixels, each "
+                        "coordinate -32768..65535, even-odd interior; repeatable up to 8 times; a value that begins with a minus sign needs "
+                        "the = form (--redact_region=-5,0,9,0,9,9)")
+    p.add_argument("--redact_mask", dest="redact_mask", default=None, metavar="PATH.png",
+                   help="a painted mask of the frames' size, any file PIL opens, read as 8-bit grey: every pixel >= 128 is hidden in every "
+                        "frame; with or without --redact_region")
+    p.add_argument("--region_mode", dest="region_mode", choices=REDACT_MODES, default=None,
+                   help="what replaces a static area (default: fill; needs --redact_region or --redact_mask)")
+    p.add_argument("--region_size", dest="region_size", type=int, default=None, metavar="N",
+                   help="pixelate: the cell's side, 2..64 (default 16); blur: the radius, 1..32 (default 12); none with fill (needs "
+                        "--redact_region or --redact_mask)")
+    p.add_argument("--region_feather", dest="region_feather", type=int, default=None, metavar="N",
+                   help="a static area fades into the scene over N pixels OUTSIDE it, 0..32 (default 0; needs --redact_region or "
+                        "--redact_mask)")
     p.add_argument("--no_draw", dest="no_draw", action="store_true", help="draw no boxes and no labels (with --redact: only hide)")
     p.add_argument("--track", dest="track", action="store_true",
                    help="join the detections of consecutive frames into tracks: labels read cls#id, and a track the detector loses is held "
@@ -2349,6 +2495,9 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     redact_shape = redact_shape_from_args(args)           # (before any model is loaded)
     if redact_shape is not None:
         tracking["redact_shape"] = redact_shape
+    redact_region = redact_region_from_args(args)         # (before any model is loaded)
+    if redact_region is not None:
+        tracking["redact_region"] = redact_region
     tracking.update(det_thresholds_from_args(args))       # (before any model is loaded)
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":

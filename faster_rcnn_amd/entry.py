@@ -322,12 +322,13 @@ class PassSpec:
     track_reid: object = None                            # (pct, keep), ops.track_reid_option's form
     out_size: object = None                              # ("size", W, H) or ("scale", N), ops.scale_form's form: the scale step's target
     track_strong: object = None                          # T, a float: the Weak rule's ``strong`` (the uploaded det_threshold is then the LOW one)
+    redact_region: object = None                         # (regions, mask, mode, size, feather), ops.redact_region_option's form
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
                 track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
                 track_trails=None, heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None,
-                track_strong=None):
+                track_strong=None, redact_region=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -426,6 +427,10 @@ class PassSpec:
             if redact is None:
                 raise FrcnnError("submit_batch: redact_shape= shapes the redaction: pass redact=(classes, mode, size, margin) too")
             redact_shape = engine.redact_shape_option(redact_shape)
+        if redact_region is not None:
+            if not annotate:
+                raise FrcnnError("submit_batch: redact_region= hides static areas in the frame an ANNOTATING pass returns: pass annotate=True")
+            redact_region = engine.redact_region_option(redact_region)
         if out_size is not None:
             if not annotate:
                 raise FrcnnError("submit_batch: out_size= scales the frame an ANNOTATING pass returns: pass annotate=True")
@@ -466,7 +471,15 @@ class PassSpec:
         return cls(annotate=annotate, encode=encode, quality=quality, jpeg_mode=jpeg_mode, y4m_mode=y4m_mode, redact=redact, draw=draw, track=track,
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
                    track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove,
-                   track_reid=track_reid, out_size=out_size, redact_shape=redact_shape, track_strong=track_strong)
+                   track_reid=track_reid, out_size=out_size, redact_shape=redact_shape, track_strong=track_strong,
+                   redact_region=redact_region)
+
+    def region_fits(self, hw):
+        """FrcnnError, by name, when the mask of ``redact_region`` is not the size ``hw`` = (h, w) of the pass's source frames."""
+        mask = self.redact_region[1] if self.redact_region is not None else None
+        if mask is not None and mask.shape != (int(hw[0]), int(hw[1])):
+            raise FrcnnError("submit_batch: redact_region: the mask is %dx%d, the pass's source frames are %dx%d"
+                             % (mask.shape[1], mask.shape[0], hw[1], hw[0]))
 
     def out_hw(self, hw):
         """The size (H, W) of the frames a pass over source frames of ``hw`` = (h, w) encodes and returns: the scale step's target, or
@@ -539,6 +552,8 @@ class PassSpec:
             key = key + ("scale",) + self.out_size
         if self.track_strong is not None:
             key = key + ("weak", self.track_strong)
+        if self.redact_region is not None:
+            key = key + ("region",) + ops.redact_region_key(self.redact_region)
         return key
 
 
@@ -753,6 +768,18 @@ class DetectionEntry:
         except ValueError as e:
             raise FrcnnError("submit_batch: %s" % e) from None
         return None if option == ("box", 0) else option
+
+    def redact_region_option(self, redact_region):
+        """``submit_batch``'s ``redact_region`` checked and normalised -> (regions, mask, mode, size, feather)
+        (ops.redact_region_option).  FrcnnError, with the reason, for anything else."""
+        try:
+            regions, mask, mode, size, feather = redact_region
+        except (TypeError, ValueError):
+            raise FrcnnError("submit_batch: redact_region=%r: (regions, mask, mode, size, feather)" % (redact_region,)) from None
+        try:
+            return ops.redact_region_option(regions, mask, mode, size, feather)
+        except ValueError as e:
+            raise FrcnnError("submit_batch: %s" % e) from None
 
     # ------------------------------------------------------------------ heat map
     def heat_state(self, h, w):
@@ -1459,7 +1486,8 @@ class DetectionEntry:
     def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
                      track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
-                     heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None, track_strong=None):
+                     heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None, track_strong=None,
+                     redact_region=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1616,12 +1644,22 @@ class DetectionEntry:
         rows only; every consumer of the tracked buffer (redaction, plate, heat, trails, count, zone, reid, look-back, back-track,
         drawing) reads it as it is.  Refused by name without ``track`` and for a T outside 0..1.  Without it every key and byte is what
         it was.
+        ``redact_region`` = (regions, mask, mode, size, feather) (annotating passes, with every other option, with and without ``redact``
+        and ``track``; ("region", regions, the mask's digest or None, mode, size, feather) appended LAST, behind ("weak", ...); regions
+        0..8 polygons in ``zone``'s grammar, mask None or a (h, w) uint8 array of the pass's SOURCE size whose bytes >= 128 hide, at
+        least one of the two; mode "fill" / "pixelate" / "blur", None: "fill"; size None: the mode's default; feather 0..32, None: 0):
+        the region rule (DESIGN §8 "Region rule") hides static areas whatever the detector says: one plane of weights per source size
+        is built once in the engine's editing states, each frame's ops.redact_region_prepare reads the UNTOUCHED frame beside the plate
+        update, and its ops.redact_region_apply_u8 blends behind the plate fill and under the heat map and everything drawn.  A
+        delayed pass hides the areas in the frames it emits.  The results are what they are without it: only the frames' bytes change.
+        Refused by name, in front of any capture: without ``annotate``, for values out of range, with neither polygons nor mask, and
+        for a mask that is not the pass's source size.  Without it every key and byte is what it was.
         The order of all these steps in a pass is stated once, in ``frame_edit.EditChain``'s docstring."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
                                 track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove, track_reid=track_reid,
-                                out_size=out_size, redact_shape=redact_shape, track_strong=track_strong)
+                                out_size=out_size, redact_shape=redact_shape, track_strong=track_strong, redact_region=redact_region)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1640,6 +1678,7 @@ class DetectionEntry:
         _, H, W, src, flip = pixels[0]
         spec = spec.sized(self, B)
         spec.out_hw(src if src is not None else (H, W))            # (refuses a target this frame size or the encoder cannot take)
+        spec.region_fits(src if src is not None else (H, W))       # (refuses a mask of another size)
         if annotate:
             if not self.device_preprocess:
                 raise FrcnnError("annotating passes need the device-side preprocess (a foreign preprocess_func uploads float pixels)")

@@ -28,6 +28,7 @@ class EditStates:
         self.trails = {}                                 # length N -> ops.track_trails_state
         self.heat = {}                                   # (h, w) of the source frames -> ops.heat_state
         self.plate = {}                                  # (h, w, rgb) of the source frames -> ops.plate_state
+        self.region = {}                                 # (h, w) of the source frames + the option's areas and feather -> ops.redact_region_plane
         self._annotate, self._redact, self._track, self._track_remove = {}, {}, {}, {}
 
     def tracker(self):
@@ -91,6 +92,12 @@ class EditStates:
         """The plate state for source frames of (h, w) whose bytes are R, G, B (``rgb``) or B, G, R: one per size and channel order --
         the plate is kept in the frames' own byte order --, whatever the other options of the calls that learn it."""
         return _made(self.plate, (int(h), int(w), bool(rgb)), lambda: ops.plate_state(h, w))
+
+    def region_plane(self, h, w, option):
+        """The plane of the region option ``option`` (ops.redact_region_option's form) for source frames of (h, w), built on first use
+        on the current stream: one per size and (polygons, mask, feather) -- the mode and the size are not the plane's."""
+        regions, mask_digest, _, _, feather = ops.redact_region_key(option)
+        return _made(self.region, (int(h), int(w), regions, mask_digest, feather), lambda: ops.redact_region_plane(h, w, option))
 
     def annotate_tables(self, draw=True):
         """The drawing tables of ops.annotate_u8 (uploaded once).  ``draw`` False: the same tables with no drawable class -- the drawing
@@ -178,10 +185,14 @@ class EditChain:
     ``edit``, once per frame, on ``rows(i)`` -- the frame's emitted buffer, else its tracked buffer, else its packed detections:
      5b. ops.plate_update, on the frame NO edit has touched: every row blocks, the held and back-filled ones too, whatever its class;
          with ``track_scene_cut`` the frame's cut word empties the plate first;
+     5c. ops.redact_region_prepare, on that same untouched frame: what will replace the static areas of ``redact_region`` (DESIGN §8
+         "Region rule") is a function of the source frame alone, in a workspace of its own (its mode need not be the redaction's);
       6. ops.redact_u8: every tracked row, the held ones too; with ``redact_shape`` ops.redact_shaped_u8 in its place (DESIGN §8 "Shape
          rule"), and nowhere else: the plate steps on either side of it keep their rectangles;
      6b. ops.plate_fill_u8, over the redaction: the rows of the remove classes become the plate.  Where the plate is not known yet
          the redaction shows, if the chain redacts all the remove classes (``keep_unknown``); else black;
+     6c. ops.redact_region_apply_u8, over the plate fill: a remove box over a static area cannot put learned background back into
+         it, and everything drawn below stays legible on top of it;
       7. ops.heat_update (the live rows) and ops.heat_draw_u8;
       8. ops.zone_draw_u8, unless nothing is drawn: a tinted area lies under every line;
       9. ops.track_trails_draw_u8;
@@ -251,6 +262,10 @@ class EditChain:
             # the redaction shows until the background is known where it covers the remove classes ("all" stands for its names); else black
             covered = spec.redact and set(ops.redact_class_list(names, classes)) <= set(ops.redact_class_list(names, spec.redact[0]))
             self.keep_unknown = bool(covered)
+        if spec.redact_region:
+            _, _, mode, size, _ = spec.redact_region
+            self.region_plane = states.region_plane(h, w, spec.redact_region)
+            self.region_ws = torch.empty(max(ops.redact_ws_bytes(h, w, mode, size), 16), dtype=torch.uint8, device="cuda")
         if self.lookback:
             self.lb_frames = torch.zeros((F, h, w, 3), dtype=torch.uint8, device="cuda")
 
@@ -320,12 +335,15 @@ class EditChain:
         return self.packed[i] if self.F > 1 else self.packed
 
     def edit(self, i, frame):
-        """Steps 5b-11 on ``frame``, an (h, w, 3) uint8 device tensor: frame i of the pass, or of the pass before it in a delayed pass."""
+        """Steps 5b-11 (5c and 6c too) on ``frame``, an (h, w, 3) uint8 device tensor: frame i of the pass, or of the pass before it in a delayed pass."""
         sp, (h, w), rows, tracked = self.spec, self.hw, self.rows(i), bool(self.spec.track)
         if sp.remove:
             _, settle, tol, p_margin = sp.remove
             ops.plate_update(self.plate, frame, rows, settle, tol, p_margin, i, self.n_frames, gate=self.gate,
                              cut=None if self.cuts is None else self.cuts[i], tracked=tracked)
+        if sp.redact_region:
+            _, _, r_mode, r_size, _ = sp.redact_region
+            ops.redact_region_prepare(frame, self.region_plane, r_mode, r_size, workspace=self.region_ws)
         if sp.redact:
             _, mode, size, margin = sp.redact
             if sp.redact_shape:
@@ -335,6 +353,8 @@ class EditChain:
                 ops.redact_u8(frame, rows, self.redact_table, mode, size, margin, workspace=self.redact_ws, tracked=tracked)
         if sp.remove:
             ops.plate_fill_u8(frame, self.plate, rows, self.remove_table, p_margin, keep_unknown=self.keep_unknown, tracked=tracked)
+        if sp.redact_region:
+            ops.redact_region_apply_u8(frame, self.region_plane, r_mode, r_size, workspace=self.region_ws)
         if sp.heat:
             _, alpha, decay = sp.heat
             ops.heat_update(self.heat, h, w, rows, self.heat_table, decay, i, self.n_frames, gate=self.gate, tracked=tracked)

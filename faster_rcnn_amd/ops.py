@@ -2267,6 +2267,157 @@ def zone_events(zlist):
     return [tuple(int(v) for v in c[ZONE_LIST_HEAD + 5 * k:ZONE_LIST_HEAD + 5 * k + 5]) for k in range(min(max(int(c[0]), 0), ZONE_MAX_EVENTS))]
 
 
+# ----------------------------------------------------------------------------- static regions
+REDACT_REGION_MAX = _lib.REDACT_REGION_MAX          # polygons of one option, at most
+REDACT_REGION_FEATHER = _lib.REDACT_REGION_FEATHER  # (smallest, largest) feather in pixels
+REDACT_REGION_MODE = "fill"                         # the default mode: a static area has nothing worth hinting at
+
+
+class RegionMask:
+    """(host only) A painted mask of the region rule: ``array`` a read-only contiguous (h, w) uint8 array -- >= 128 hides --, ``digest``
+    the SHA-1 of its size and bytes.  Two masks are equal when their digests are, so an option that holds one hashes and compares."""
+    __slots__ = ("array", "digest")
+
+    def __init__(self, array):
+        import hashlib
+        a = np.asarray(array)
+        if a.dtype == np.bool_:
+            a = a.astype(np.uint8) * 255
+        if a.ndim != 2 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
+            raise ValueError("redact region mask: a (h, w) uint8 array (>= 128 hides), got %s %s" % (a.dtype, tuple(a.shape)))
+        a = np.array(a, dtype=np.uint8, order="C")      # (a copy of the caller's: nobody writes it behind the digest)
+        a.setflags(write=False)
+        self.array = a
+        self.digest = hashlib.sha1(b"%dx%d:" % (a.shape[1], a.shape[0]) + a.tobytes()).hexdigest()
+
+    shape = property(lambda self: tuple(self.array.shape))
+
+    def __eq__(self, other):
+        return isinstance(other, RegionMask) and other.digest == self.digest
+
+    def __hash__(self):
+        return hash(self.digest)
+
+    def __repr__(self):
+        return "RegionMask(%dx%d, %s)" % (self.array.shape[1], self.array.shape[0], self.digest[:12])
+
+
+def redact_region_option(regions=None, mask=None, mode=None, size=None, feather=None):
+    """(host only) The region option checked -> (regions, mask, mode, size, feather) (DESIGN §8 "Region rule"): regions a tuple of 0..8
+    polygons in ``zone_option``'s grammar and limits (3..16 vertices (x, y) of integers in -32768..65535, no two consecutive ones equal; a
+    polygon as its vertices or flat; one polygon alone is one region; None: none), mask None or a (h, w) uint8 array (a ``RegionMask``
+    in the result), at least one of the two; mode "fill" / "pixelate" / "blur" (None: "fill"), size as ``redact_size`` (None: the
+    mode's default), feather 0..32 (None: 0).  ValueError with the reason."""
+    polys = ()
+    try:
+        regions = () if regions is None else tuple(regions)
+    except TypeError:
+        raise ValueError("redact regions=%r: a list of polygons, each a list of (x, y)" % (regions,)) from None
+    if regions:
+        try:
+            polys = zone_option(regions)[0]
+        except ValueError as e:
+            raise ValueError("redact region: %s" % str(e).replace("zones", "regions").replace("zone", "region")) from None
+    if mask is not None and not isinstance(mask, RegionMask):
+        mask = RegionMask(mask)
+    if not polys and mask is None:
+        raise ValueError("redact region: neither a polygon nor a mask: nothing to hide")
+    mode = REDACT_REGION_MODE if mode is None else mode
+    if not isinstance(mode, str) or mode not in _lib.REDACT_MODES:
+        raise ValueError("redact region mode %r: one of %s" % (mode, ", ".join(REDACT_MODES)))
+    try:
+        size = redact_size(mode, size)
+    except ValueError as e:
+        raise ValueError("redact region: %s" % e) from None
+    lo, hi = REDACT_REGION_FEATHER
+    feather = 0 if feather is None else feather
+    if not _is_int(feather) or not lo <= int(feather) <= hi:
+        raise ValueError("redact region feather %r: an integer in %d..%d" % (feather, lo, hi))
+    return polys, mask, mode, size, int(feather)
+
+
+def redact_region_key(option):
+    """(host only) ``option`` (``redact_region_option``'s form) as a cache key holds it: the mask as its digest, or None."""
+    regions, mask, mode, size, feather = option
+    return regions, (None if mask is None else mask.digest), mode, size, feather
+
+
+def redact_region_plane_bytes(h, w):
+    """Bytes of a plane for frames of (h, w) (frcnn_redact_region_plane_bytes); FrcnnError for a side out of range."""
+    n = int(_lib.load().frcnn_redact_region_plane_bytes(int(h), int(w)))
+    if n == 0:
+        raise _lib.FrcnnError("redact region plane: frame %rx%r out of range (sides 1..%d)" % (h, w, _lib.REDACT_MAX_SIDE))
+    return n
+
+
+def redact_region_plane(h, w, option, out=None):
+    """The plane of ``option`` (``redact_region_option``'s form) for frames of (h, w): a uint8 device tensor, [int32 h, w, feather,
+    covered, full, 1, 0, 0 | uint16 W[h][w] | tile flags | private] (include/ext/frcnn_hip_redact_region.h), built by three launches
+    on the current stream (frcnn_redact_region_build): once per frame size.  The mode and size of the option are not the plane's: they
+    go to ``redact_region_prepare`` / ``redact_region_apply_u8``.  ``out``: a 16-byte aligned u8 device tensor of
+    ``redact_region_plane_bytes(h, w)`` bytes to build into; None allocates one.  ValueError for a mask that is not (h, w)."""
+    _require_gpu()
+    regions, mask, _, _, feather = option
+    h, w = int(h), int(w)
+    if mask is not None and mask.shape != (h, w):
+        raise ValueError("redact region mask of %dx%d for frames of %dx%d" % (mask.shape[1], mask.shape[0], w, h))
+    plane = torch.zeros(redact_region_plane_bytes(h, w), dtype=torch.uint8, device="cuda") if out is None else out
+    assert plane.is_cuda and plane.dtype == torch.uint8 and plane.dim() == 1 and plane.is_contiguous() and plane.data_ptr() % 16 == 0
+    assert int(plane.numel()) == redact_region_plane_bytes(h, w)
+    mask_dev = None if mask is None else torch.from_numpy(mask.array.copy()).cuda()        # (the option's array is read-only)
+    keep, verts_p, nv_p, n = _zone_verts_arg(regions) if regions else (None, None, None, 0)   # (``keep``: the host arrays, alive over the call)
+    _lib.call("frcnn_redact_region_build", _p(plane), h, w, verts_p, nv_p, n, _p(mask_dev), int(feather), _stream())
+    return plane
+
+
+def _region_call(name, frame, plane, mode, size, workspace):
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert plane.is_cuda and plane.dtype == torch.uint8 and plane.dim() == 1 and plane.is_contiguous()
+    if mode not in _lib.REDACT_MODES:
+        raise ValueError("redact region mode %r: one of %s" % (mode, ", ".join(REDACT_MODES)))
+    size = REDACT_SIZES[mode][2] if size is None else int(size)            # (the range is the library's to check)
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    if workspace is None:
+        workspace = _ws(_lib.load().frcnn_redact_ws_bytes(h, w, _lib.REDACT_MODES[mode], size))
+    assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    _lib.call(name, _p(frame), h, w, _p(plane), _lib.REDACT_MODES[mode], size, _p(workspace), int(workspace.numel()), _stream())
+    return workspace
+
+
+def redact_region_prepare(frame, plane, mode=REDACT_REGION_MODE, size=None, workspace=None):
+    """What replaces the hidden pixels, from ``frame`` -- the (h, w, 3) uint8 device frame NO edit has touched -- into ``workspace``
+    (a u8 device tensor of ``redact_ws_bytes(h, w, mode, size)`` bytes; None allocates one) -> the workspace: the Redaction rule's phase
+    one, run whatever the detections say (frcnn_redact_region_prepare).  Nothing for "fill".  The call can be captured in a graph."""
+    return _region_call("frcnn_redact_region_prepare", frame, plane, mode, size, workspace)
+
+
+def redact_region_apply_u8(frame, plane, mode=REDACT_REGION_MODE, size=None, workspace=None):
+    """Hide the static areas of ``plane`` (``redact_region_plane``) in ``frame``, an (h, w, 3) uint8 device tensor, edited in place
+    and returned: every byte with W > 0 becomes (W R + (256 - W) C + 128) >> 8, R from ``workspace`` as ``redact_region_prepare`` filled
+    it from the untouched frame (DESIGN §8 "Region rule"; frcnn_redact_region_apply_u8, one launch).  A plane of another frame size
+    writes nothing.  The call can be captured in a graph."""
+    _region_call("frcnn_redact_region_apply_u8", frame, plane, mode, size, workspace)
+    return frame
+
+
+def redact_region_stats(plane):
+    """(host only; reads the header back) -> {"h", "w", "feather", "covered": the pixels with W > 0, "full": those with W = 256} of a
+    plane, device tensor or host copy."""
+    p = plane[:4 * _lib.REDACT_REGION_HEAD_WORDS].cpu().numpy() if isinstance(plane, torch.Tensor) else np.asarray(plane)[:4 * _lib.REDACT_REGION_HEAD_WORDS]
+    head = np.ascontiguousarray(p).view(np.int32)
+    return {"h": int(head[0]), "w": int(head[1]), "feather": int(head[2]), "covered": int(head[3]), "full": int(head[4])}
+
+
+def redact_region_weights(plane):
+    """(host only; reads the plane back) W of a plane, device tensor or host copy -> a (h, w) uint16 array, 0..256."""
+    p = plane.cpu().numpy() if isinstance(plane, torch.Tensor) else np.ascontiguousarray(plane)
+    head = p[:8].view(np.int32)
+    h, w = int(head[0]), int(head[1])
+    at = 4 * _lib.REDACT_REGION_HEAD_WORDS
+    return p[at:at + 2 * h * w].view(np.uint16).reshape(h, w).copy()
+
+
 # ----------------------------------------------------------------------------- background plate
 # (smallest, largest, the default) of the settle S, the tolerance T and the margin M.  The defaults are PROVISIONAL: nobody has measured
 # them on real footage.

@@ -32,7 +32,7 @@ without and with ``--detect_every 4``.  ``--track_backtrack`` (``run_track_backt
 ``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
 look-back call of one pass alone.  ``--track_scene_cut`` (``run_track_scene_cut``) runs the ``--track --track_motion 8`` leg without and with
 ``--track_scene_cut`` at its default.  ``--track_trails`` (``run_track_trails``) runs the same leg without and with ``--track_trails`` at its
-defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--out_scale`` (``run_out_scale``) runs in-memory annotating passes, the PNG-file to PNG-file leg (device encoder, huffman) and y4m to y4m, each without and with ``--out_scale 2``.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).  ``--redact_shape`` (``run_redact_shape``) runs the ``--redact all --redact_mode blur`` passes without and with ``--redact_shape ellipse --redact_feather 8``.  ``--track_low`` (``run_track_low``) runs the ``--det_threshold 0.5 --track --track_motion 8`` leg without and with ``--track_low 0.1``.
+defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--out_scale`` (``run_out_scale``) runs in-memory annotating passes, the PNG-file to PNG-file leg (device encoder, huffman) and y4m to y4m, each without and with ``--out_scale 2``.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).  ``--redact_shape`` (``run_redact_shape``) runs the ``--redact all --redact_mode blur`` passes without and with ``--redact_shape ellipse --redact_feather 8``.  ``--track_low`` (``run_track_low``) runs the ``--det_threshold 0.5 --track --track_motion 8`` leg without and with ``--track_low 0.1``.  ``--redact_region`` (``run_redact_region``) runs in-memory annotating passes without and with two ``--redact_region`` polygons of a tenth of the frame each, ``--region_mode blur --region_feather 8``.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
@@ -406,6 +406,52 @@ def run_redact_shape(name, cfg, n_frames, reps, content="noise"):
         res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
         res[k + "_runs_s"] = [round(t, 4) for t in ts]
     res["shape_over_redact"] = round(statistics.median(times["redact"]) / statistics.median(times["redact_shape"]), 3)
+    return res
+
+
+def region_leg(h, w):
+    """Two polygons of about a tenth of the frame each -- a band along the bottom (a bonnet) and a triangle in the top right corner (a
+    house window seen at an angle) --, ``--region_mode blur --region_feather 8``."""
+    band = ((0, h - h // 10), (w, h - h // 10), (w, h), (0, h))
+    side = int((0.2 * h * w) ** 0.5)                     # a right triangle of legs ``side``: a tenth of the frame
+    corner = ((w - side, 0), (w, 0), (w, side))
+    return (band, corner), None, "blur", None, 8
+
+
+def run_redact_region(name, cfg, n_frames, reps, content="noise"):
+    """``--redact_region``: what hiding static areas (DESIGN §8 "Region rule") costs.  One pair of legs in ONE session, alternating inside
+    every repetition: in-memory annotating passes without and with ``redact_region=region_leg(h, w)``.  Reports frames/s of both, their
+    ratio and the share of the pixels the option changes.  Not separated: the apply kernel alone, and photo content."""
+    import numpy as np
+    from faster_rcnn_amd import entry, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    rs = np.random.RandomState(5)
+    srcs = photo_frames(h, w, n_frames) if content == "photo" else [rs.randint(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n_frames)]
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+    leg = region_leg(h, w)
+    legs = {"plain": lambda: annotate_in_memory(eng, resized, ratios),
+            "redact_region": lambda: annotate_in_memory(eng, resized, ratios, redact_region=leg)}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures, and the plane
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    few = slice(0, eng.batch)
+    plain = annotate_in_memory(eng, resized[few], ratios[few])
+    share = float(np.mean([(a != b).any(axis=2).mean() for a, b in zip(annotate_in_memory(eng, resized[few], ratios[few], redact_region=leg), plain)]))
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"], "content": content,
+           "redact_region": {"regions": [list(map(list, p)) for p in leg[0]], "mode": "blur", "size": 12, "feather": 8},
+           "images_per_pass": eng.batch, "in_flight": eng.in_flight, "pixels_changed_share": round(share, 3)}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["region_over_plain"] = round(statistics.median(times["plain"]) / statistics.median(times["redact_region"]), 3)
     return res
 
 
@@ -1252,6 +1298,9 @@ def main():
                                                                 "with --redact_shape ellipse --redact_feather 8, alternating in one session")
     ap.add_argument("--track_low", action="store_true", help="instead of the legs above: the --det_threshold 0.5 --track --track_motion 8 "
                                                              "leg without and with --track_low 0.1, alternating in one session")
+    ap.add_argument("--redact_region", action="store_true", help="instead of the legs above: in-memory annotating passes without and with two "
+                                                                 "--redact_region polygons of a tenth of the frame each, --region_mode blur "
+                                                                 "--region_feather 8, alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -1260,6 +1309,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.redact_region:
+            out[name] = run_redact_region(name, PAIRS[name], args.frames, args.reps, args.content)
             continue
         if args.track_low:
             out[name] = run_track_low(name, PAIRS[name], args.frames, args.reps, args.content)
