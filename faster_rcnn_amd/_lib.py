@@ -423,6 +423,22 @@ REDACT_REGION_MAX = 8                                                           
 REDACT_REGION_FEATHER = (0, 32)                                                    # 0..FRCNN_REDACT_REGION_FEATHER_MAX
 REDACT_REGION_HEAD_WORDS = 8                                                       # FRCNN_REDACT_REGION_HEAD_WORDS
 
+REDACT_MOVING_VERSION = 1       # include/ext/frcnn_hip_redact_moving.h FRCNN_REDACT_MOVING_VERSION
+REDACT_MOVING_SIGNATURES = {
+    "frcnn_redact_moving_version": (I, []),
+    "frcnn_redact_moving_state_bytes": (c_size_t, [I, I]),
+    "frcnn_redact_moving_build": (I, [P, P, P, I, I, P, P, P, I, I, P, I, I, I, I, I, I, I, I, I, P, P, P, P]),
+}
+# (smallest, largest, the default) tolerance D, vote K, hold H, grow G and feather F (FRCNN_REDACT_MOVING_*): the defaults of the first
+# four are PROVISIONAL, not measured on real footage
+REDACT_MOVING_TOL = (0, 255, 24)
+REDACT_MOVING_VOTE = (1, 64, 8)
+REDACT_MOVING_HOLD = (0, 255, 4)
+REDACT_MOVING_GROW = (0, 32, 8)
+REDACT_MOVING_FEATHER = (0, 32, 0)
+REDACT_MOVING_CELL = 8                                                             # FRCNN_REDACT_MOVING_CELL
+REDACT_MOVING_STATS_WORDS = 4                                                      # FRCNN_REDACT_MOVING_STATS_WORDS
+
 TRACK_VERSION = 1               # include/ext/frcnn_hip_track.h FRCNN_TRACK_VERSION
 TRACK_MAX = 128                 # ... FRCNN_TRACK_MAX: slots of a state
 TRACK_MAX_FRAMES = 64           # ... FRCNN_TRACK_MAX_FRAMES: frames of one call
@@ -883,6 +899,15 @@ def load():
     if lib.frcnn_redact_region_version() != REDACT_REGION_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_region_version()} of the region-redaction extension, this binding "
                          f"{REDACT_REGION_VERSION} (include/ext/frcnn_hip_redact_region.h): rebuild with `python -m faster_rcnn_amd.build`")
+    for name, (res, args) in REDACT_MOVING_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise FrcnnError(f"{LIB_PATH} has no {name} (include/ext/frcnn_hip_redact_moving.h): rebuild with `python -m faster_rcnn_amd.build`")
+        fn.restype = res
+        fn.argtypes = args
+    if lib.frcnn_redact_moving_version() != REDACT_MOVING_VERSION:
+        raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_moving_version()} of the moving-redaction extension, this binding "
+                         f"{REDACT_MOVING_VERSION} (include/ext/frcnn_hip_redact_moving.h): rebuild with `python -m faster_rcnn_amd.build`")
     if lib.frcnn_redact_version() != REDACT_VERSION:
         raise FrcnnError(f"{LIB_PATH} speaks revision {lib.frcnn_redact_version()} of the redaction extension, this binding "
                          f"{REDACT_VERSION} (include/ext/frcnn_hip_redact.h): rebuild with `python -m faster_rcnn_amd.build`")

@@ -159,6 +159,18 @@ it does not fit is refused by name.  ``--plate_out`` shows every pixel of an are
 per-frame line are unchanged; at the end one line per frame size is printed: ``redact regions 1242x375: 2 regions + mask, 12.3 % of the
 frame hidden``.  The three ``--region_*`` flags are refused by name without an area.  Without the option, no pass, key, printed line or
 output byte changes.
+``redact_moving=True | {keywords} | 12 values`` (``--redact_moving``; ``--moving_tol D``, 0..255; ``--moving_min K``, 1..64;
+``--moving_hold H``, 0..255 frames; ``--moving_grow G`` and ``--moving_feather F``, 0..32 pixels; ``--moving_unknown show|hide``;
+``--moving_except CLASSES``; ``--moving_mode pixelate|blur|fill``, default pixelate; ``--moving_size N``; ``--moving_out PATH``, a CSV
+``frame,cells,covered``; the defaults 24, 8, 4 and 8 are PROVISIONAL: nobody has measured them on real footage) is a safety net under the
+detector for fixed-camera footage: whatever differs from the plate of ``--remove`` is hidden, detected or not (ops.redact_moving_build,
+csrc/redact_moving.hip; DESIGN §8 "Moving rule").  A run without ``--remove`` learns the plate all the same -- ``--remove_settle`` /
+``--remove_tol`` / ``--remove_margin`` go with either flag -- and paints nothing out.  A list starts from an empty plate and an empty
+moving state; ``get_annotated_frame(redact_moving=)`` and the eager path continue them as one-frame calls (``reset_moving`` and
+``reset_plate`` empty them).  Until a pixel's background is known it is shown (``--moving_unknown hide`` blanks the start instead):
+the first S frames are not protected by the net under the default; use a large ``--remove_settle``, since the net does not block
+learning.  At the end one line per frame size is printed: ``moving net 1242x375: 128 frames, mean 3.2 % hidden, peak 17.0 %``.  The
+satellite flags are refused by name without ``--redact_moving``.  Without the option, no pass, key, printed line or output byte changes.
 """
 import collections
 import os
@@ -356,7 +368,7 @@ def _eager_heat_state(class_mapping, h, w):
 
 def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
                track_trails=None, rgb=False, heatmap=None, count=None, zone=None, remove=None, track_reid=None, out_size=None,
-               redact_shape=None, redact_region=None):
+               redact_shape=None, redact_region=None, redact_moving=None):
     """The editing chain over ONE frame and its host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is edited in
     place, by a one-frame ``frame_edit.EditChain`` -- its docstring states the calls and their order -- on this class mapping's eager
     states (``reset_tracks``, ``reset_heat`` and ``reset_counts`` empty them); ``rgb``: the frame's channel order (False: B, G, R).
@@ -379,7 +391,11 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     ``redact_shape`` = (shape, feather) (with ``redact``): the redaction hides ellipses and fades out over ``feather`` pixels (DESIGN §8
     "Shape rule", ops.redact_shaped_u8); ("box", 0) is the call without it.
     ``redact_region`` = (regions, mask, mode, size, feather): the static areas are hidden whatever ``dets`` holds (DESIGN §8 "Region
-    rule", ops.redact_region_prepare / ops.redact_region_apply_u8); the plane of the frame's size is this class mapping's."""
+    rule", ops.redact_region_prepare / ops.redact_region_apply_u8); the plane of the frame's size is this class mapping's.
+    ``redact_moving`` = True, a dict of ops.redact_moving_option's keywords or its 12 values: the frame teaches this class mapping's plate
+    (as with ``remove``, without a fill when there is none) and whatever differs from it is hidden (DESIGN §8 "Moving rule"); the moving
+    state of the frame's size and channel order goes on from the call before (``reset_moving`` empties it); ``info`` receives "moving":
+    {"cells", "covered"}."""
     import torch
     redact_shape = _redact_shape(redact_shape, redact)
     redact_region = _redact_region(redact_region)
@@ -390,11 +406,12 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
     track_trails = _track_trails(track_trails, track, draw)
     heatmap = _heatmap(heatmap)
     remove = _remove(remove)
+    redact_moving = _redact_moving(redact_moving, remove, class_mapping)
     count = _count(count, track)
     zone = _zone(zone, track)
     radius = _track_motion(track_motion, track)
     track_scene_cut = _track_scene_cut(track_scene_cut, track, track_motion, None, None)
-    if track is not None or heatmap is not None or remove is not None or redact_region is not None or (dets and (draw or redact is not None)):      # (else the frame stays as it is)
+    if track is not None or heatmap is not None or remove is not None or redact_region is not None or redact_moving is not None or (dets and (draw or redact is not None)):      # (else the frame stays as it is)
         dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
         packed = torch.from_numpy(_pack_dets(dets, class_mapping)).cuda()
         if redact is not None:
@@ -402,7 +419,7 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
         states = _eager_states(class_mapping)
         spec = entry.PassSpec(annotate=True, redact=redact, draw=draw, track=track, track_scene_cut=track_scene_cut, track_trails=track_trails,
                               track_motion=radius, heat=heatmap, count=count, zone=zone, remove=remove, track_reid=track_reid,
-                              redact_shape=redact_shape, redact_region=redact_region)
+                              redact_shape=redact_shape, redact_region=redact_region, redact_moving=redact_moving)
         chain = EditChain(states, spec, 1, 1, frame.shape[:2], rgb)
         chain.update(dev.view(-1), 0, packed, states.one_frame())         # (in front of the edits: ``dev`` is still the frame as it came)
         chain.edit(0, dev)
@@ -420,6 +437,9 @@ def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, t
             info["zones"] = {"occupancy": ops.zone_occupancy(zlist, len(zone[0])), "events": ops.zone_events(zlist)}
         if info is not None and track_reid is not None:
             info["reid"] = ops.track_reid_events(chain.reid_lists[0].cpu().numpy())
+        if info is not None and redact_moving is not None:
+            stats = ops.redact_moving_stats(chain.moving_stats[0])
+            info["moving"] = {"cells": stats["cells"], "covered": stats["covered"]}
         frame[...] = dev.cpu().numpy()
     if scaled_hw is not None:
         return ops.downscale_u8(torch.from_numpy(np.ascontiguousarray(frame)).cuda(), *scaled_hw).cpu().numpy()
@@ -476,6 +496,88 @@ def _redact_region(redact_region):
     except (TypeError, ValueError):
         raise ValueError("redact_region=%r: (regions, mask, mode, size, feather)" % (redact_region,)) from None
     return ops.redact_region_option(regions, mask, mode, size, feather)
+
+
+def _redact_moving(redact_moving, remove, owner):
+    """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame`` / ``draw_eager``'s ``redact_moving`` checked against the
+    normalised ``remove`` -> ops.redact_moving_option's form, or None (ops.redact_moving_form).  ``owner``: the class mapping, or the
+    training manager that holds it (read only when there is an option to check).  ValueError with the reason."""
+    if redact_moving is None or redact_moving is False:
+        return None
+    mapping = owner if isinstance(owner, dict) else owner.class_mapping
+    return ops.redact_moving_form(redact_moving, remove, _names_by_index(mapping))
+
+
+MOVING_SATELLITES = ("moving_tol", "moving_min", "moving_hold", "moving_grow", "moving_feather", "moving_unknown", "moving_except",
+                     "moving_mode", "moving_size", "moving_out")
+
+
+def redact_moving_from_args(args, class_mapping, remove=None):
+    """(host only) The moving net the command line asks for -> (the option in ops.redact_moving_option's form as
+    ``submit_batch(redact_moving=...)`` takes it, the path of ``--moving_out`` or None), or (None, None) without ``--redact_moving``.
+    ``remove``: what ``remove_from_args`` returned -- with it the plate's settle, tolerance and margin are its own; without it they are
+    ``--remove_settle`` / ``--remove_tol`` / ``--remove_margin``, which go with either flag.  ValueError, with the reason, for any
+    ``--moving_*`` flag without ``--redact_moving`` (by its name), an unknown class name and a value out of range."""
+    if not getattr(args, "redact_moving", False):
+        for name in MOVING_SATELLITES:
+            value = getattr(args, name, None)
+            if value is not None:
+                raise ValueError("--%s=%s is a setting of the moving net: it needs --redact_moving" % (name, value))
+        return None, None
+    classes = None
+    if args.moving_except is not None:
+        classes = tuple(n.strip() for n in args.moving_except.split(",") if n.strip())
+        if not classes:
+            raise ValueError("--moving_except takes comma-separated class names, or all")
+    kw = dict(tol=args.moving_tol, vote=args.moving_min, hold=args.moving_hold, grow=args.moving_grow, feather=args.moving_feather,
+              unknown=args.moving_unknown, except_classes=classes, mode=args.moving_mode, size=args.moving_size)
+    if remove is None:
+        kw.update(settle=args.remove_settle, plate_tol=args.remove_tol, margin=args.remove_margin)
+    try:
+        option = ops.redact_moving_form(kw, remove, _names_by_index(class_mapping))
+    except ValueError as e:
+        raise ValueError("--redact_moving / --moving_* / --remove_settle / --remove_tol / --remove_margin: %s" % e) from None
+    return option, _moving_out(args.moving_out, option)
+
+
+def _moving_out(moving_out, redact_moving):
+    """``moving_out`` checked against ``redact_moving`` -> the path, or None."""
+    if moving_out is None:
+        return None
+    if redact_moving is None:
+        raise ValueError("moving_out=%r is where the moving net's counts are written: it needs redact_moving=" % (moving_out,))
+    return moving_out
+
+
+def moving_line(w, h, covered):
+    """The line printed at the end for the frame size (w, h): ``moving net 1242x375: 128 frames, mean 3.2 % hidden, peak 17.0 %`` --
+    ``covered``: the pixels with W > 0 of every frame of that size, in order."""
+    pct = [100.0 * c / (w * h) for c in covered]
+    return "moving net %dx%d: %d frames, mean %.1f %% hidden, peak %.1f %%" % (w, h, len(pct), sum(pct) / max(len(pct), 1), max(pct + [0.0]))
+
+
+class MovingLog:
+    """Where the moving net's counts of a sequence go: the ``--moving_out`` CSV ``frame,cells,covered`` (``path`` None: none) and the
+    covered pixels per frame size, for the lines at the end."""
+
+    def __init__(self, path):
+        self.file = open(path, "w") if path is not None else None
+        if self.file is not None:
+            self.file.write("frame,cells,covered\n")
+        self.per_size = collections.OrderedDict()         # (h, w) -> [covered of every frame of that size]
+
+    def add(self, frame_no, h, w, moving):
+        self.per_size.setdefault((int(h), int(w)), []).append(int(moving["covered"]))
+        if self.file is not None:
+            self.file.write("%d,%d,%d\n" % (frame_no, moving["cells"], moving["covered"]))
+
+    def lines(self):
+        return [moving_line(w, h, covered) for (h, w), covered in sorted(self.per_size.items())]
+
+    def close(self):
+        if self.file is not None:
+            self.file.close()
+            self.file = None
 
 
 def redact_region_from_args(args):
@@ -1168,10 +1270,12 @@ def remove_from_args(args, class_mapping):
     ``--plate_out`` without ``--remove``, an unknown class name, an S outside 1..255, a T outside 0..255, an M outside 0..64 and a
     ``--plate_out`` that does not end in .png."""
     if args.remove is None:
+        moving = bool(getattr(args, "redact_moving", False))          # (the plate's three settings go with either flag)
         for flag, value in (("--remove_settle", args.remove_settle), ("--remove_tol", args.remove_tol), ("--remove_margin", args.remove_margin),
                             ("--plate_out", args.plate_out)):
-            if value is not None:
-                raise ValueError("%s=%s is a setting of the removal: it needs --remove CLASSES" % (flag, value))
+            if value is not None and not (moving and flag != "--plate_out"):
+                raise ValueError("%s=%s is a setting of the removal: it needs --remove CLASSES" % (flag, value)
+                                 + ("" if flag == "--plate_out" else " (or --redact_moving)"))
         return None, None
     names = [n.strip() for n in args.remove.split(",") if n.strip()]
     if not names:
@@ -1273,6 +1377,16 @@ def reset_plate(training_manager, detector, in_flight=1, post=None):
         _eager_states(training_manager.class_mapping).reset_plate()
 
 
+def reset_moving(training_manager, detector, in_flight=1, post=None):
+    """An empty moving state before a new sequence: the states of the engine ``in_flight`` names, or the eager path's.  (The plate the
+    net compares with is ``reset_plate``'s.)"""
+    eng = _engine(training_manager, detector, in_flight, post)
+    if eng is not None:
+        eng.moving_reset()
+    else:
+        _eager_states(training_manager.class_mapping).reset_moving()
+
+
 def _lookback_frames(track_lookback, track, eng, B):
     """``annotate_images`` / ``annotate_stream``'s ``track_lookback`` checked -> the look-back of their passes, or None."""
     if track_lookback is None:
@@ -1326,8 +1440,13 @@ def _print_drawn(dets, width, height):
 def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
                         frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
                         track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, track_reid=None,
-                        reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None):
+                        reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None,
+                        redact_moving=None, moving_out=None):
     """(``det_threshold`` / ``track_low``: as ``annotate_images``.)
+    ``redact_moving``: True, a dict of ops.redact_moving_option's keywords or its 12 values -- the moving net (DESIGN §8 "Moving rule"):
+    the frame teaches the plate of the calls before this one and whatever differs from it is hidden; the moving state CONTINUES from
+    the call before (``reset_moving`` empties it, ``reset_plate`` the plate).  ``moving_out``: a ``MovingLog`` that receives the frame's
+    counts.  None: every byte is what it was.
     annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
     ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
     ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
@@ -1406,6 +1525,9 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
     remove = _remove(remove)
     if remove is not None:
         motion["remove"] = remove
+    redact_moving = _redact_moving(redact_moving, remove, training_manager)
+    if redact_moving is not None:
+        motion["redact_moving"] = redact_moving
     if track_reid is not None:
         motion["track_reid"] = track_reid
     if redact_shape is not None:
@@ -1451,6 +1573,8 @@ def get_annotated_frame(training_manager, detector, frame, img, resize_min, resi
         _write_counts(counts_out, frame_no, info["crossings"], training_manager.class_mapping)
     if zone is not None:
         _write_zones(zones_out, frame_no, info["zones"]["events"], training_manager.class_mapping)
+    if redact_moving is not None and moving_out is not None:
+        moving_out.add(frame_no, img.height, img.width, info["moving"])
     _print_drawn(dets, img.width, img.height)
     return frame
 
@@ -1855,7 +1979,7 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
               tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
               track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None,
               plate_out=None, track_reid=None, reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None,
-              track_low=None, redact_region=None):
+              track_low=None, redact_region=None, redact_moving=None, moving_out=None):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
     ``make_sink()``: the ``_Sink``."""
@@ -1872,6 +1996,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     plate_out = _plate_out(plate_out, remove)
     if remove is not None and remove[0] != "all":         # (unknown names are refused here, in front of any capture)
         ops.plate_class_list(_names_by_index(training_manager.class_mapping), remove[0])
+    redact_moving = _redact_moving(redact_moving, remove, training_manager)      # (refused here, in front of any capture)
+    moving_out = _moving_out(moving_out, redact_moving)
     count = _count(count, track)
     if counts_out is not None and count is None:
         raise ValueError("counts_out=%r is where the crossings are written: it needs count=(lines, classes, width)" % (counts_out,))
@@ -1893,7 +2019,7 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
     redact_region = _redact_region(redact_region)         # (refused here, in front of any capture)
     if redact_region is not None:
         motion["redact_region"] = redact_region
-    counts_log = zones_log = reid_log = None
+    counts_log = zones_log = reid_log = moving_log = None
     sink = make_sink()
     region_sizes = set()                                  # the (h, w) of the frames met: a line per size at the end
     if redact_region is not None:                         # a frame the mask does not fit is refused by name, on both paths
@@ -1930,6 +2056,13 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
         if remove is not None:                            # an empty plate for the list
             motion["remove"] = tracking["remove"] = remove
             reset_plate(training_manager, detector, 1 if eng is None else eng.in_flight, post)
+        if redact_moving is not None:                     # an empty moving state for the list, and an empty plate under it
+            motion["redact_moving"] = tracking["redact_moving"] = redact_moving
+            reset_moving(training_manager, detector, 1 if eng is None else eng.in_flight, post)
+            if remove is None:
+                reset_plate(training_manager, detector, 1 if eng is None else eng.in_flight, post)
+            moving_log = MovingLog(moving_out)
+            motion["moving_out"] = moving_log
         if track is not None:                             # a new sequence; its frames are submitted in input order, as every list's are
             reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight, post)
         if count is not None:                             # zero totals for the list
@@ -1981,6 +2114,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
                 if track_reid is not None:
                     reid_log.add(pos + 1, marks[0]["reid"])
                     _print_reid(label, marks[0]["reid"])
+                if redact_moving is not None:
+                    moving_log.add(pos + 1, frame.height, frame.width, marks[0]["moving"])
                 print("processing {}".format(label))
                 print("num rois: {}".format(num_rois))
                 if track is not None:
@@ -2011,6 +2146,9 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
                     plates = {key: (frames_, known, blacken_plate(plate, _region_weights(training_manager, eng, key[0], key[1], redact_region)))
                               for key, (frames_, known, plate) in plates.items()}
                 write_plates(plate_out, plates)
+        if redact_moving is not None:                     # (host only: what the passes returned; the file is closed below)
+            for line in moving_log.lines():
+                print(line)
         if redact_region is not None:                     # (host only: the planes' headers read back)
             for h, w in sorted(region_sizes):
                 states = eng.edit_states if eng is not None else _eager_states(training_manager.class_mapping)
@@ -2022,6 +2160,8 @@ def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize
             zones_log.close()
         if reid_log is not None:
             reid_log.close()
+        if moving_log is not None:
+            moving_log.close()
         sink.close()
 
 
@@ -2030,8 +2170,9 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
                     redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
                     track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
                     counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None, reid_out=None, post=None,
-                    out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None):
-    """(``redact_region``: as ``annotate_images``.)
+                    out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None, redact_moving=None,
+                    moving_out=None):
+    """(``redact_region``, ``redact_moving`` / ``moving_out``: as ``annotate_images``.)
     ``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
@@ -2049,7 +2190,8 @@ def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resiz
               detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
               heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out, remove=remove,
               plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size, redact_shape=redact_shape,
-              det_threshold=det_threshold, track_low=track_low, redact_region=redact_region)
+              det_threshold=det_threshold, track_low=track_low, redact_region=redact_region, redact_moving=redact_moving,
+              moving_out=moving_out)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
@@ -2057,7 +2199,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
                     jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
                     heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None,
-                    reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None):
+                    reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None,
+                    redact_moving=None, moving_out=None):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -2141,7 +2284,16 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     ``feather`` pixels.  Polygons apply to every frame size; a mask is held to one, and a frame it does not fit is refused by name.
     ``plate_out`` then shows every pixel of an area black.  A line ``redact regions 1242x375: 2 regions + mask, 12.3 % of the frame
     hidden`` is printed per frame size at the end; every other printed line and file is unchanged.  None: no pass, key, printed line or
-    output byte changes."""
+    output byte changes.
+    ``redact_moving``: True, a dict of ops.redact_moving_option's keywords or its 12 values, as ``redact_moving_from_args`` returns it
+    (with every option above, with and without ``remove`` and ``track``) -- the moving net (DESIGN §8 "Moving rule"): on fixed-camera
+    footage whatever differs from the plate is hidden in every frame, detected or not.  The list starts from an EMPTY moving state and
+    an empty plate; without ``remove`` the plate is learned all the same, with the option's (S, T, M), and nothing is painted out; with
+    it the three are ``remove``'s, and one stated here that differs is refused by name.  The defaults 24, 8, 4 and 8 are PROVISIONAL.
+    Until a pixel's background is known it is shown (unknown "hide" blanks it instead): the first S frames are not protected by the
+    net under the default.  Delayed passes run the net on the frames they emit.  ``moving_out``: a path; a CSV ``frame,cells,covered``
+    is written there.  A line ``moving net 1242x375: 128 frames, mean 3.2 % hidden, peak 17.0 %`` is printed per frame size at the
+    end.  None: no pass, key, printed line or output byte changes."""
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
@@ -2156,7 +2308,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
               track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
               track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out,
               remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size,
-              redact_shape=redact_shape, det_threshold=det_threshold, track_low=track_low, redact_region=redact_region)
+              redact_shape=redact_shape, det_threshold=det_threshold, track_low=track_low, redact_region=redact_region,
+              redact_moving=redact_moving, moving_out=moving_out)
 
 
 def build_parser():
@@ -2247,6 +2400,33 @@ def build_parser():
     p.add_argument("--region_feather", dest="region_feather", type=int, default=None, metavar="N",
                    help="a static area fades into the scene over N pixels OUTSIDE it, 0..32 (default 0; needs --redact_region or "
                         "--redact_mask)")
+    p.add_argument("--redact_moving", dest="redact_moving", action="store_true",
+                   help="fixed-camera footage: hide whatever differs from the learned background plate, whether the detector saw it or "
+                        "not; the first --remove_settle frames are not protected (the background is not known yet)")
+    p.add_argument("--moving_tol", dest="moving_tol", type=int, default=None, metavar="D",
+                   help="how far a channel may lie from the plate, 0..255 (default 24, provisional: not measured on real footage; needs "
+                        "--redact_moving)")
+    p.add_argument("--moving_min", dest="moving_min", type=int, default=None, metavar="K",
+                   help="the differing pixels that make an 8 x 8 cell vote, 1..64 (default 8, provisional; needs --redact_moving)")
+    p.add_argument("--moving_hold", dest="moving_hold", type=int, default=None, metavar="H",
+                   help="the frames a cell stays hidden behind its last vote, 0..255 (default 4, provisional; needs --redact_moving)")
+    p.add_argument("--moving_grow", dest="moving_grow", type=int, default=None, metavar="G",
+                   help="the pixels the hidden cells grow by, 0..32 (default 8, provisional; needs --redact_moving)")
+    p.add_argument("--moving_feather", dest="moving_feather", type=int, default=None, metavar="F",
+                   help="the hidden set fades into the scene over F pixels OUTSIDE it, 0..32 (default 0; needs --redact_moving)")
+    p.add_argument("--moving_unknown", dest="moving_unknown", choices=("show", "hide"), default=None,
+                   help="a pixel whose background is not known yet: show it (default) or hide it, which blanks the start of a sequence "
+                        "(needs --redact_moving)")
+    p.add_argument("--moving_except", dest="moving_except", default=None, metavar="CLASSES",
+                   help="comma-separated class names, or all: the boxes of these classes are never hidden by the net (needs "
+                        "--redact_moving)")
+    p.add_argument("--moving_mode", dest="moving_mode", choices=REDACT_MODES, default=None,
+                   help="what replaces what the net hides (default: pixelate; needs --redact_moving)")
+    p.add_argument("--moving_size", dest="moving_size", type=int, default=None, metavar="N",
+                   help="pixelate: the cell's side, 2..64 (default 16); blur: the radius, 1..32 (default 12); none with fill (needs "
+                        "--redact_moving)")
+    p.add_argument("--moving_out", dest="moving_out", default=None, metavar="PATH",
+                   help="write a CSV frame,cells,covered: the moving cells and the hidden pixels of every frame (needs --redact_moving)")
     p.add_argument("--no_draw", dest="no_draw", action="store_true", help="draw no boxes and no labels (with --redact: only hide)")
     p.add_argument("--track", dest="track", action="store_true",
                    help="join the detections of consecutive frames into tracks: labels read cls#id, and a track the detector loses is held "
@@ -2321,11 +2501,11 @@ def build_parser():
                         "detected becomes background")
     p.add_argument("--remove_settle", dest="remove_settle", type=int, default=None, metavar="S",
                    help="the frames a pixel must hold still to become background, 1..255 (default 8, provisional: not measured on real "
-                        "footage; needs --remove)")
+                        "footage; needs --remove or --redact_moving)")
     p.add_argument("--remove_tol", dest="remove_tol", type=int, default=None, metavar="T",
-                   help="how far a channel may lie from the value its run began with, 0..255 (default 10, provisional; needs --remove)")
+                   help="how far a channel may lie from the value its run began with, 0..255 (default 10, provisional; needs --remove or --redact_moving)")
     p.add_argument("--remove_margin", dest="remove_margin", type=int, default=None, metavar="M",
-                   help="the pixels every box grows by, 0..64 (default 8, provisional; needs --remove)")
+                   help="the pixels every box grows by, 0..64 (default 8, provisional; needs --remove or --redact_moving)")
     p.add_argument("--plate_out", dest="plate_out", default=None, metavar="PATH.png",
                    help="write the plate at the end of the list as an RGB PNG with unknown pixels black, one per frame size met (needs --remove)")
     p.add_argument("--count_line", dest="count_line", action="append", default=None, metavar="X1,Y1,X2,Y2",
@@ -2471,6 +2651,11 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
         tracking["remove"] = remove
     if plate_out is not None:
         tracking["plate_out"] = plate_out
+    redact_moving, moving_out = redact_moving_from_args(args, class_mapping, remove)      # (before any model is loaded)
+    if redact_moving is not None:
+        tracking["redact_moving"] = redact_moving
+    if moving_out is not None:
+        tracking["moving_out"] = moving_out
     count, counts_out = count_from_args(args, class_mapping)
     if count is not None:
         tracking["count"] = count

@@ -12,36 +12,18 @@
 //     its pixel and blends; the vertical blur sum slides while consecutive rows have W > 0.  No LDS, one writer per byte, plain byte
 //     stores, no atomics, no floats.
 // The kernels of prepare and apply compare the plane's header with (h, w) and return without writing when it is another size's.
-#include "redact.h"
-#include "../../include/ext/frcnn_hip_redact_region.h"
+#include "redact_region.h"                                                  // (the plane: its header words and its layout)
 #include "../../include/ext/frcnn_hip_zone.h"
 
 namespace frcnn {
 
-constexpr int RR_REGIONS = FRCNN_REDACT_REGION_MAX, RR_VERTS = FRCNN_ZONE_MAX_VERTS, RR_FMAX = FRCNN_REDACT_REGION_FEATHER_MAX;
-constexpr int RR_HEAD = FRCNN_REDACT_REGION_HEAD_WORDS;
-enum { RR_H, RR_W, RR_F, RR_COVERED, RR_FULL, RR_ONE };                     // words of the header
-static_assert(RR_HEAD == 8 && RR_FMAX + 1 <= 255, "d1 is a byte");
+constexpr int RR_REGIONS = FRCNN_REDACT_REGION_MAX, RR_VERTS = FRCNN_ZONE_MAX_VERTS;
 
 struct RegionSet {                                                          // passed by value as a kernel argument
     int n;
     int nv[RR_REGIONS];
     int v[RR_REGIONS * RR_VERTS * 2];                                       // region z's vertex i at v[2 (16 z + i)], (x, y)
 };
-
-// where the pieces of a plane lie, in bytes from its start
-struct RegionLayout { size_t w_at, flags_at, hard_at, d1_at, total; };
-
-__host__ __device__ inline RegionLayout region_layout(int h, int w) {
-    RegionLayout L;
-    const size_t cols = ((size_t)3 * w + RD_THREADS - 1) / RD_THREADS, rows = ((size_t)h + RD_TILE_ROWS - 1) / RD_TILE_ROWS;
-    L.w_at = 4 * RR_HEAD;
-    L.flags_at = align16(L.w_at + 2 * (size_t)h * w);
-    L.hard_at = align16(L.flags_at + cols * rows);
-    L.d1_at = align16(L.hard_at + ((size_t)h + 2 * RR_FMAX) * ((size_t)w + 2 * RR_FMAX));    // (sized for the largest feather)
-    L.total = align16(L.d1_at + ((size_t)h + 2 * RR_FMAX) * (size_t)w);
-    return L;
-}
 
 // INSIDE of the polygon of ``nv`` vertices at ``v`` (x, y pairs in LDS): csrc/zone.hip's test, word for word
 __device__ inline bool rr_inside(const int* v, int nv, int px, int py) {

@@ -323,12 +323,13 @@ class PassSpec:
     out_size: object = None                              # ("size", W, H) or ("scale", N), ops.scale_form's form: the scale step's target
     track_strong: object = None                          # T, a float: the Weak rule's ``strong`` (the uploaded det_threshold is then the LOW one)
     redact_region: object = None                         # (regions, mask, mode, size, feather), ops.redact_region_option's form
+    redact_moving: object = None                         # (D, K, H, G, F, unknown, EXCEPT, mode, size, S, T, M), ops.redact_moving_option's form
 
     @classmethod
     def checked(cls, engine, batch, annotate=False, encode=None, quality=None, subsampling=None, huffman=None, y4m=None, redact=None, draw=True,
                 track=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
                 track_trails=None, heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None,
-                track_strong=None, redact_region=None):
+                track_strong=None, redact_region=None, redact_moving=None):
         """``submit_batch``'s keywords (its docstring says what each means) for a pass of ``batch`` images (None: ``engine.batch``) on
         ``engine`` -> the spec.  FrcnnError with the reason.  ``track_lookback`` / ``track_backtrack`` are still as given: ``sized`` checks
         them, behind ``submit_batch``'s flush, which reads neither."""
@@ -431,6 +432,14 @@ class PassSpec:
             if not annotate:
                 raise FrcnnError("submit_batch: redact_region= hides static areas in the frame an ANNOTATING pass returns: pass annotate=True")
             redact_region = engine.redact_region_option(redact_region)
+        if redact_moving is not None:
+            if not annotate:
+                raise FrcnnError("submit_batch: redact_moving= hides what differs from the plate in the frame an ANNOTATING pass returns: "
+                                 "pass annotate=True")
+            if not engine.device_preprocess:
+                raise FrcnnError("submit_batch: redact_moving= needs the device-side preprocess: a foreign preprocess_func uploads float "
+                                 "pixels, and the plate is learned from the uint8 source frame")
+            redact_moving = engine.redact_moving_option(redact_moving, remove)
         if out_size is not None:
             if not annotate:
                 raise FrcnnError("submit_batch: out_size= scales the frame an ANNOTATING pass returns: pass annotate=True")
@@ -472,7 +481,7 @@ class PassSpec:
                    track_motion=track_motion, track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack,
                    track_scene_cut=track_scene_cut, track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove,
                    track_reid=track_reid, out_size=out_size, redact_shape=redact_shape, track_strong=track_strong,
-                   redact_region=redact_region)
+                   redact_region=redact_region, redact_moving=redact_moving)
 
     def region_fits(self, hw):
         """FrcnnError, by name, when the mask of ``redact_region`` is not the size ``hw`` = (h, w) of the pass's source frames."""
@@ -554,6 +563,8 @@ class PassSpec:
             key = key + ("weak", self.track_strong)
         if self.redact_region is not None:
             key = key + ("region",) + ops.redact_region_key(self.redact_region)
+        if self.redact_moving is not None:
+            key = key + ("moving",) + self.redact_moving
         return key
 
 
@@ -571,7 +582,7 @@ class _Slot:
                  "track", "track_pin", "_track_raw", "n_frames_host", "n_frames_dev", "track_motion",
                  "track_lookback", "lb_pin", "_lb_raw", "every", "frames", "track_backtrack", "spec",
                  "track_scene_cut", "cuts_pin", "_cuts_raw", "track_trails", "heat", "count", "count_pin", "_count_raw", "zone", "zone_pin", "_zone_raw",
-                 "remove", "track_reid", "reid_pin", "_reid_raw", "out_size", "scale_dev", "pix_out")
+                 "remove", "track_reid", "reid_pin", "_reid_raw", "out_size", "scale_dev", "pix_out", "moving", "moving_pin", "_moving_raw")
 
     def __init__(self):
         for name in self.__slots__:
@@ -884,6 +895,35 @@ class DetectionEntry:
         with torch.cuda.stream(self.track_stream):
             self.edit_states.reset_plate()
 
+    # ------------------------------------------------------------------ moving net
+    def moving_state(self, h, w, rgb=None):
+        """The engine's moving state for source frames of (h, w) (device uint8, ops.redact_moving_state; ``ops.redact_moving_left``
+        reads it): one per size and channel order, beside the plate state of the same key, shared by every pass submitted with
+        ``redact_moving=``.  ``rgb`` as ``plate_state``'s.  ``moving_reset()`` empties it; ``track_reset()`` does not."""
+        if rgb is None:
+            made = [k[2] for k in self.edit_states.moving if k[:2] == (int(h), int(w))]
+            if len(made) > 1:
+                raise FrcnnError("moving_state: frames of %dx%d were met in both channel orders: say rgb=True or rgb=False" % (w, h))
+            rgb = made[0] if made else False
+        return self.edit_states.moving_state(h, w, rgb)
+
+    def moving_reset(self):
+        """No cell held, for every size: the states are zeroed on the ordered stream, behind the passes submitted so far.  (The plate the
+        net compares with is ``plate_reset()``'s.)"""
+        with torch.cuda.stream(self.track_stream):
+            self.edit_states.reset_moving()
+
+    def redact_moving_option(self, redact_moving, remove=None):
+        """``submit_batch``'s ``redact_moving`` checked and normalised -> ops.redact_moving_option's form: True or () for every default,
+        else a dict of ops.redact_moving_option's keywords or its 12-tuple; the EXCEPT names must be this engine's; with ``remove``
+        (normalised) the plate's (S, T, M) are the remove option's -- a pass has one plate update --, and a settle, plate_tol or margin
+        stated here that differs is refused by name (ops.redact_moving_form).  FrcnnError, with the reason."""
+        try:
+            return ops.redact_moving_form(redact_moving, remove, self.class_names())
+        except ValueError as e:
+            text = str(e)
+            raise FrcnnError("submit_batch: %s" % (text if text.startswith("redact_moving") else "redact_moving: " + text)) from None
+
     def remove_option(self, remove):
         """``submit_batch``'s ``remove`` checked and normalised -> (classes, S, T, M): classes "all" or a tuple of this engine's class
         names, None for S, T or M replaced by the (provisional) defaults (8, 10, 8).  FrcnnError, with the reason, for anything else."""
@@ -1060,7 +1100,7 @@ class DetectionEntry:
         -> (the pinned side as a numpy array, the device view the pass reads the pairs from: (B, 2) f64, one image's (2,) for B = 1)."""
         B, off = s.batch, s.frames * seg
         s.seg = seg
-        tail = 16 if s.track or s.heat or s.remove else 0     # a tracking, heat or remove pass: | the count of real frames, int32 (ops.track_update's n_frames)]
+        tail = 16 if s.track or s.heat or s.remove or s.moving else 0     # a tracking, heat or remove pass: | the count of real frames, int32 (ops.track_update's n_frames)]
         s.io_dev = torch.zeros(off + 16 * B + tail, dtype=torch.uint8, device="cuda")
         fine("buffers: device staging")
         s.io_pin = self._pinned.take(off + 16 * B + tail, zero=True)
@@ -1239,6 +1279,7 @@ class DetectionEntry:
             s.every, s.frames = spec.detect_every, B * (spec.detect_every or 1)
             s.track_scene_cut, s.track_trails, s.heat, s.count = spec.track_scene_cut, spec.track_trails, spec.heat, spec.count
             s.zone, s.remove, s.track_reid, s.out_size = spec.zone, spec.remove, spec.track_reid, spec.out_size
+            s.moving = spec.redact_moving
             run = self._canvas_pass(s, fine, H, W) if canvas else self._exact_pass(s, fine, H, W, src, flip)
             shared = self.in_flight > 1
             # one image in flight: split-K on the small grids (a latency tool); several: plain launches, tiles for a shared chip
@@ -1298,6 +1339,10 @@ class DetectionEntry:
                 reid_lists = s.chain.reid_lists
                 s._reid_raw = self._pinned.take(4 * reid_lists.numel())
                 s.reid_pin = s._reid_raw.view(torch.int32)[:reid_lists.numel()].view(tuple(reid_lists.shape))
+            if s.moving:
+                moving_stats = s.chain.moving_stats
+                s._moving_raw = self._pinned.take(4 * moving_stats.numel())
+                s.moving_pin = s._moving_raw.view(torch.int32)[:moving_stats.numel()].view(tuple(moving_stats.shape))
             if s.track_lookback:                                    # [the B emitted buffers | the count word]
                 words = s.chain.lb_out[1].numel() + 4
                 s._lb_raw = self._pinned.take(4 * words)
@@ -1487,7 +1532,7 @@ class DetectionEntry:
                      subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
                      track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
                      heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None, track_strong=None,
-                     redact_region=None):
+                     redact_region=None, redact_moving=None):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1654,12 +1699,25 @@ class DetectionEntry:
         delayed pass hides the areas in the frames it emits.  The results are what they are without it: only the frames' bytes change.
         Refused by name, in front of any capture: without ``annotate``, for values out of range, with neither polygons nor mask, and
         for a mask that is not the pass's source size.  Without it every key and byte is what it was.
+        ``redact_moving`` = True, a dict of ops.redact_moving_option's keywords or its 12 values (annotating passes with the device
+        preprocess, with every other option, with and without ``remove`` and ``track``; ("moving", D, K, H, G, F, unknown, EXCEPT, mode,
+        size, S, T, M) appended LAST, behind ("region", ...); the defaults D 24, K 8, H 4, G 8 are PROVISIONAL, nobody has measured them on
+        real footage): the moving rule (DESIGN §8 "Moving rule") hides whatever differs from the plate, detected or not.  Each frame's
+        ops.redact_moving_build runs right behind its plate update -- which a pass without ``remove`` runs too, with the option's (S, T, M)
+        and no fill; with ``remove`` the three are the remove option's -- into the engine's moving state of the frame size and channel
+        order (``moving_state``; it lives across passes until ``moving_reset()``; ``track_reset()`` leaves it), and the frame is blended
+        under the resulting plane behind the static regions and under everything drawn.  Like remove passes these replay in input order
+        on the ordered stream and carry the real-frame count word; a delayed pass runs the net on the frames it emits.  Each result's
+        trailing dict carries "moving": {"cells": n, "covered": n}.  Refused by name, in front of any capture: without ``annotate``,
+        with a foreign preprocess, for values out of range and for an EXCEPT name that is no class.  Without it every key and byte is
+        what it was.
         The order of all these steps in a pass is stated once, in ``frame_edit.EditChain``'s docstring."""
         spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
                                 redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
                                 detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
                                 track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove, track_reid=track_reid,
-                                out_size=out_size, redact_shape=redact_shape, track_strong=track_strong, redact_region=redact_region)
+                                out_size=out_size, redact_shape=redact_shape, track_strong=track_strong, redact_region=redact_region,
+                                redact_moving=redact_moving)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1713,7 +1771,7 @@ class DetectionEntry:
                 metas.append(self._canvas_frame(s, i, pixels[j]))
             elif not isinstance(pixels[j][0], JpegFile):
                 np.copyto(s.pix_hosts[i], pixels[j][0], casting="same_kind")      # into pinned memory (f64 -> f32 cast for a foreign preprocess)
-        if s.track or s.heat or s.remove:                           # (a heat or remove pass too: their states depend on the order of the frames)
+        if s.track or s.heat or s.remove or s.moving:               # (a heat, remove or moving pass too: their states depend on the order of the frames)
             s.n_frames_host[0] = len(pixels) if images else -1      # goes up with the frames: the padding does not advance the tracker; -1: a flush
             st = self.track_stream
         else:
@@ -1757,6 +1815,8 @@ class DetectionEntry:
                 s.zone_pin.copy_(s.chain.zone_lists, non_blocking=True)
             if s.track_reid:
                 s.reid_pin.copy_(s.chain.reid_lists, non_blocking=True)
+            if s.moving:                                            # the frames' moving stats come back with the dets
+                s.moving_pin.copy_(s.chain.moving_stats, non_blocking=True)
             for i in range(emitted["frames"] if emitted else 0 if s.track_lookback else len(pixels)):
                 if s.encode == JPEG_ENCODE:
                     s.png_pin[i].copy_(s.png_dev[i][:s.first_copy], non_blocking=True)
@@ -1953,9 +2013,10 @@ class DetectionEntry:
         """What frame i of a collected ``track_scene_cut``, ``count`` or ``zone`` pass returns behind its payload: ONE dict -- "scene_cut":
         True for a frame that is a cut, "crossings": [(line, dir, id, cls)] in a counting pass (the events of the frame's count list, dir 1
         for +), "zones": {"occupancy": [per zone], "events": [(zone, kind, id, cls, dwell)]} in a zone pass (the frame's zone list), "reid":
-        [(pid, tid, cls, distance, gap)] in a ``track_reid`` pass (the frame's reid list) --;
+        [(pid, tid, cls, distance, gap)] in a ``track_reid`` pass (the frame's reid list), "moving": {"cells", "covered"} in a
+        ``redact_moving`` pass (the frame's moving stats) --;
         () for every other pass."""
-        if not s.track_scene_cut and not s.count and not s.zone and not s.track_reid:
+        if not s.track_scene_cut and not s.count and not s.zone and not s.track_reid and not s.moving:
             return ()
         marks = {"scene_cut": True} if s.track_scene_cut and int(s.cuts_pin[i]) else {}
         if s.count:
@@ -1965,6 +2026,9 @@ class DetectionEntry:
             marks["zones"] = {"occupancy": ops.zone_occupancy(zlist, len(s.zone[0])), "events": ops.zone_events(zlist)}
         if s.track_reid:                                 # "reid": the frame's re-identifications (pid, tid, cls, distance, gap)
             marks["reid"] = ops.track_reid_events(s.reid_pin[i].numpy())
+        if s.moving:                                     # "moving": the moving cells of the frame and the pixels hidden under its plane
+            stats = s.moving_pin[i].numpy()
+            marks["moving"] = {"cells": int(stats[1]), "covered": int(stats[2])}
         return (marks,)
 
     def _payload(self, s, i):

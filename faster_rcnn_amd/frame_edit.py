@@ -29,6 +29,7 @@ class EditStates:
         self.heat = {}                                   # (h, w) of the source frames -> ops.heat_state
         self.plate = {}                                  # (h, w, rgb) of the source frames -> ops.plate_state
         self.region = {}                                 # (h, w) of the source frames + the option's areas and feather -> ops.redact_region_plane
+        self.moving = {}                                 # (h, w, rgb) of the source frames -> ops.redact_moving_state
         self._annotate, self._redact, self._track, self._track_remove = {}, {}, {}, {}
 
     def tracker(self):
@@ -99,6 +100,11 @@ class EditStates:
         regions, mask_digest, _, _, feather = ops.redact_region_key(option)
         return _made(self.region, (int(h), int(w), regions, mask_digest, feather), lambda: ops.redact_region_plane(h, w, option))
 
+    def moving_state(self, h, w, rgb):
+        """The moving state (DESIGN §8 "Moving rule") for source frames of (h, w) in the channel order ``rgb``: one per size and channel
+        order, beside the plate state it is compared with, whatever the other options of the calls that advance it."""
+        return _made(self.moving, (int(h), int(w), bool(rgb)), lambda: ops.redact_moving_state(h, w))
+
     def annotate_tables(self, draw=True):
         """The drawing tables of ops.annotate_u8 (uploaded once).  ``draw`` False: the same tables with no drawable class -- the drawing
         step of a chain that only redacts paints nothing, with no branch in the chain."""
@@ -153,6 +159,11 @@ class EditStates:
         for state in self.plate.values():
             ops.plate_reset(state)
 
+    def reset_moving(self):
+        """No cell held, for every size and channel order.  (The plate the net compares with is ``reset_plate``'s.)"""
+        for state in self.moving.values():
+            ops.redact_moving_reset(state)
+
     def reset_counts(self):
         """Zero totals and no entries."""
         if self._count is not None:
@@ -185,14 +196,20 @@ class EditChain:
     ``edit``, once per frame, on ``rows(i)`` -- the frame's emitted buffer, else its tracked buffer, else its packed detections:
      5b. ops.plate_update, on the frame NO edit has touched: every row blocks, the held and back-filled ones too, whatever its class;
          with ``track_scene_cut`` the frame's cut word empties the plate first;
+    5b2. ops.redact_moving_build, right behind the plate update and on that same untouched frame (DESIGN §8 "Moving rule"): the frame
+         against the plate as step 5b left it becomes the pass's moving plane and the frame's stats.  A chain with ``redact_moving``
+         but without ``remove`` still runs step 5b, with the option's (S, T, M), and runs no fill;
      5c. ops.redact_region_prepare, on that same untouched frame: what will replace the static areas of ``redact_region`` (DESIGN §8
          "Region rule") is a function of the source frame alone, in a workspace of its own (its mode need not be the redaction's);
+    5c2. ops.redact_region_prepare once more, with the moving plane, into a workspace of its own;
       6. ops.redact_u8: every tracked row, the held ones too; with ``redact_shape`` ops.redact_shaped_u8 in its place (DESIGN §8 "Shape
          rule"), and nowhere else: the plate steps on either side of it keep their rectangles;
      6b. ops.plate_fill_u8, over the redaction: the rows of the remove classes become the plate.  Where the plate is not known yet
          the redaction shows, if the chain redacts all the remove classes (``keep_unknown``); else black;
      6c. ops.redact_region_apply_u8, over the plate fill: a remove box over a static area cannot put learned background back into
          it, and everything drawn below stays legible on top of it;
+     6d. ops.redact_region_apply_u8 with the moving plane, behind 6c and under everything drawn.  One plane and one workspace serve
+         the frames of a pass, which are edited one after another; ``moving_stats`` is [F][4];
       7. ops.heat_update (the live rows) and ops.heat_draw_u8;
       8. ops.zone_draw_u8, unless nothing is drawn: a tinted area lies under every line;
       9. ops.track_trails_draw_u8;
@@ -266,6 +283,13 @@ class EditChain:
             _, _, mode, size, _ = spec.redact_region
             self.region_plane = states.region_plane(h, w, spec.redact_region)
             self.region_ws = torch.empty(max(ops.redact_ws_bytes(h, w, mode, size), 16), dtype=torch.uint8, device="cuda")
+        if spec.redact_moving:
+            mv = spec.redact_moving
+            self.plate = states.plate_state(h, w, self.rgb)
+            self.moving, self.moving_table = states.moving_state(h, w, self.rgb), ops.redact_moving_table(states.class_names, mv[6])
+            self.moving_plane = torch.zeros(ops.redact_region_plane_bytes(h, w), dtype=torch.uint8, device="cuda")
+            self.moving_ws = torch.empty(max(ops.redact_ws_bytes(h, w, mv[7], mv[8]), 16), dtype=torch.uint8, device="cuda")
+            self.moving_stats = torch.zeros((F, _lib.REDACT_MOVING_STATS_WORDS), dtype=torch.int32, device="cuda")
         if self.lookback:
             self.lb_frames = torch.zeros((F, h, w, 3), dtype=torch.uint8, device="cuda")
 
@@ -335,15 +359,21 @@ class EditChain:
         return self.packed[i] if self.F > 1 else self.packed
 
     def edit(self, i, frame):
-        """Steps 5b-11 (5c and 6c too) on ``frame``, an (h, w, 3) uint8 device tensor: frame i of the pass, or of the pass before it in a delayed pass."""
+        """Steps 5b-11 (5b2, 5c, 5c2, 6c and 6d too) on ``frame``, an (h, w, 3) uint8 device tensor: frame i of the pass, or of the pass before it in a delayed pass."""
         sp, (h, w), rows, tracked = self.spec, self.hw, self.rows(i), bool(self.spec.track)
-        if sp.remove:
-            _, settle, tol, p_margin = sp.remove
-            ops.plate_update(self.plate, frame, rows, settle, tol, p_margin, i, self.n_frames, gate=self.gate,
-                             cut=None if self.cuts is None else self.cuts[i], tracked=tracked)
+        mv = sp.redact_moving
+        if sp.remove or mv:
+            _, settle, tol, p_margin = sp.remove if sp.remove else (None,) + mv[9:12]
+            cut = None if self.cuts is None else self.cuts[i]
+            ops.plate_update(self.plate, frame, rows, settle, tol, p_margin, i, self.n_frames, gate=self.gate, cut=cut, tracked=tracked)
+        if mv:
+            ops.redact_moving_build(self.moving, self.moving_plane, self.moving_stats[i], frame, self.plate, rows, self.moving_table, mv, i,
+                                    self.n_frames, gate=self.gate, cut=cut, tracked=tracked)
         if sp.redact_region:
             _, _, r_mode, r_size, _ = sp.redact_region
             ops.redact_region_prepare(frame, self.region_plane, r_mode, r_size, workspace=self.region_ws)
+        if mv:
+            ops.redact_region_prepare(frame, self.moving_plane, mv[7], mv[8], workspace=self.moving_ws)
         if sp.redact:
             _, mode, size, margin = sp.redact
             if sp.redact_shape:
@@ -355,6 +385,8 @@ class EditChain:
             ops.plate_fill_u8(frame, self.plate, rows, self.remove_table, p_margin, keep_unknown=self.keep_unknown, tracked=tracked)
         if sp.redact_region:
             ops.redact_region_apply_u8(frame, self.region_plane, r_mode, r_size, workspace=self.region_ws)
+        if mv:
+            ops.redact_region_apply_u8(frame, self.moving_plane, mv[7], mv[8], workspace=self.moving_ws)
         if sp.heat:
             _, alpha, decay = sp.heat
             ops.heat_update(self.heat, h, w, rows, self.heat_table, decay, i, self.n_frames, gate=self.gate, tracked=tracked)

@@ -2540,6 +2540,180 @@ def plate_fill_u8(frame, state, det_packed, table, margin=None, keep_unknown=Fal
     return frame
 
 
+# ----------------------------------------------------------------------------- moving net
+# (smallest, largest, the default) of the tolerance D, the vote K, the hold H, the grow G and the feather F.  The defaults of D, K, H and G
+# are PROVISIONAL: nobody has measured them on real footage.
+REDACT_MOVING_TOL, REDACT_MOVING_VOTE, REDACT_MOVING_HOLD = _lib.REDACT_MOVING_TOL, _lib.REDACT_MOVING_VOTE, _lib.REDACT_MOVING_HOLD
+REDACT_MOVING_GROW, REDACT_MOVING_FEATHER = _lib.REDACT_MOVING_GROW, _lib.REDACT_MOVING_FEATHER
+REDACT_MOVING_MODE = "pixelate"
+REDACT_MOVING_UNKNOWN = ("show", "hide")            # index = the rule's ``unknown``
+REDACT_MOVING_KEYWORDS = ("tol", "vote", "hold", "grow", "feather", "unknown", "except_classes", "mode", "size", "settle", "plate_tol", "margin")
+
+
+def redact_moving_option(tol=None, vote=None, hold=None, grow=None, feather=None, unknown=None, except_classes=None, mode=None, size=None,
+                         settle=None, plate_tol=None, margin=None):
+    """(host only) The moving option checked -> (D, K, H, G, F, unknown, EXCEPT, mode, size, S, T, M) (DESIGN §8 "Moving rule"): D how far
+    a channel may lie from the plate, 0..255 (None: 24); K the foreground pixels that make an 8 x 8 cell vote, 1..64 (None: 8); H the
+    frames a cell stays hidden behind its last vote, 0..255 (None: 4); G the pixels the hidden set grows by, 0..32 (None: 8); F the feather
+    beyond that, 0..32 (None: 0); unknown "show" or "hide" (None: "show") -- what a pixel whose background is not known yet counts as --;
+    EXCEPT () or a tuple of class names, "all" for every class (which names there are is the caller's to check: ``redact_class_list``):
+    the boxes of those classes are never foreground; mode "fill" / "pixelate" / "blur" (None: "pixelate"), size as ``redact_size``
+    (None: the mode's default); S, T, M the plate's settle, tolerance and margin as ``plate_option`` takes them (None: its defaults).
+    The defaults of D, K, H and G are provisional.  ValueError with the reason."""
+    out = []
+    for name, v, (lo, hi, default) in (("tol", tol, REDACT_MOVING_TOL), ("vote", vote, REDACT_MOVING_VOTE), ("hold", hold, REDACT_MOVING_HOLD),
+                                       ("grow", grow, REDACT_MOVING_GROW), ("feather", feather, REDACT_MOVING_FEATHER)):
+        v = default if v is None else v
+        if not _is_int(v) or not lo <= int(v) <= hi:
+            raise ValueError("redact moving %s=%r: an integer in %d..%d" % (name, v, lo, hi))
+        out.append(int(v))
+    unknown = REDACT_MOVING_UNKNOWN[0] if unknown is None else unknown
+    if not isinstance(unknown, str) or unknown not in REDACT_MOVING_UNKNOWN:
+        raise ValueError("redact moving unknown=%r: one of %s" % (unknown, ", ".join(REDACT_MOVING_UNKNOWN)))
+    classes = () if except_classes is None else except_classes
+    if isinstance(classes, str):
+        classes = (classes,)
+    try:
+        classes = tuple(classes)
+    except TypeError:
+        raise ValueError("redact moving except_classes=%r: \"all\", a class name or a list of class names" % (except_classes,)) from None
+    if not all(isinstance(c, str) and c for c in classes):
+        raise ValueError("redact moving except_classes=%r: \"all\", a class name or a list of class names" % (except_classes,))
+    classes = "all" if classes == ("all",) else classes
+    mode = REDACT_MOVING_MODE if mode is None else mode
+    if not isinstance(mode, str) or mode not in _lib.REDACT_MODES:
+        raise ValueError("redact moving mode %r: one of %s" % (mode, ", ".join(REDACT_MODES)))
+    try:
+        size = redact_size(mode, size)
+    except ValueError as e:
+        raise ValueError("redact moving: %s" % e) from None
+    try:
+        _, settle, plate_tol, margin = plate_option("all", settle, plate_tol, margin)
+    except ValueError as e:
+        text = str(e).replace("remove ", "", 1)
+        raise ValueError("redact moving %s" % ("plate_" + text if text.startswith("tol=") else text)) from None
+    return tuple(out) + (unknown, classes, mode, size, settle, plate_tol, margin)
+
+
+def redact_moving_form(redact_moving, remove=None, class_names=None):
+    """(host only) What the entry points take as ``redact_moving`` -> ``redact_moving_option``'s form: True or () for every default, a
+    dict of ``redact_moving_option``'s keywords, or its 12 values in order.  ``remove``: the pass's normalised remove option or None --
+    a pass has ONE plate update, so with it the plate's (S, T, M) are the remove option's, and a ``settle`` / ``plate_tol`` / ``margin``
+    stated here that differs is refused by name.  ``class_names`` (index = class index): the EXCEPT names must be among them.
+    ValueError with the reason."""
+    if redact_moving is True or (isinstance(redact_moving, tuple) and not redact_moving):
+        kw = {}
+    elif isinstance(redact_moving, dict):
+        kw = dict(redact_moving)
+    else:
+        try:
+            values = tuple(redact_moving)
+        except TypeError:
+            values = None
+        if values is None or isinstance(redact_moving, str) or len(values) != len(REDACT_MOVING_KEYWORDS):
+            raise ValueError("redact_moving=%r: True, a dict of the keywords %s, or their %d values"
+                             % (redact_moving, ", ".join(REDACT_MOVING_KEYWORDS), len(REDACT_MOVING_KEYWORDS)))
+        kw = dict(zip(REDACT_MOVING_KEYWORDS, values))
+    unknown = [k for k in kw if k not in REDACT_MOVING_KEYWORDS]
+    if unknown:
+        raise ValueError("redact_moving: unknown keyword%s %s; the keywords are %s"
+                         % ("s" if len(unknown) > 1 else "", ", ".join(repr(k) for k in unknown), ", ".join(REDACT_MOVING_KEYWORDS)))
+    if remove is not None:
+        for name, value in zip(("settle", "plate_tol", "margin"), remove[1:4]):
+            if kw.get(name) is not None and kw[name] != value:
+                raise ValueError("redact_moving: %s=%r, but remove= says %d: a pass has one plate update, state it once" % (name, kw[name], value))
+            kw[name] = value
+    option = redact_moving_option(**kw)
+    if class_names is not None and option[6] not in ((), "all"):
+        try:
+            option = option[:6] + (redact_class_list(class_names, option[6]),) + option[7:]
+        except ValueError as e:
+            text = str(e)
+            raise ValueError("redact moving except_classes: " + (text[len("redact: "):] if text.startswith("redact: ") else text)) from None
+    return option
+
+
+def redact_moving_table(class_names, except_classes):
+    """The EXCEPT table ``redact_moving_build`` reads: device u8 [C], 1 where ``class_names[i]`` is excepted; () excepts nothing."""
+    if except_classes == ():
+        _require_gpu()
+        return torch.zeros(len(class_names), dtype=torch.uint8, device="cuda")
+    return redact_table(class_names, except_classes)
+
+
+def redact_moving_state_bytes(h, w):
+    """(host only) Bytes of a moving state BUFFER for frames of (h, w) (frcnn_redact_moving_state_bytes); FrcnnError for a side out of range."""
+    n = int(_lib.load().frcnn_redact_moving_state_bytes(int(h), int(w)))
+    if n == 0:
+        raise _lib.FrcnnError("redact moving state: frame %rx%r out of range (sides 1..%d)" % (h, w, _lib.REDACT_MAX_SIDE))
+    return n
+
+
+def redact_moving_state(h, w):
+    """An empty moving state for frames of (h, w): a zeroed uint8 device tensor, [int32 frames, cells_now, 0, 0 | uint8 left[ch][cw] |
+    scratch] (include/ext/frcnn_hip_redact_moving.h).  Zeroing it (``redact_moving_reset``) empties it; ``redact_moving_left`` reads it."""
+    _require_gpu()
+    return torch.zeros(redact_moving_state_bytes(h, w), dtype=torch.uint8, device="cuda")
+
+
+def redact_moving_reset(state):
+    """Empty the state (on the current stream): no frames, no cell held."""
+    state.zero_()
+    return state
+
+
+def redact_moving_left(state, h, w):
+    """(host only; reads the state back) -> (frames, cells_now, the (ch, cw) uint8 array ``left``) of a moving state, device tensor or host copy."""
+    host = state.detach().cpu().numpy() if isinstance(state, torch.Tensor) else np.ascontiguousarray(state)
+    cell = _lib.REDACT_MOVING_CELL
+    ch, cw = -(-int(h) // cell), -(-int(w) // cell)
+    head = host[:16].view(np.int32)
+    return int(head[0]), int(head[1]), host[16:16 + ch * cw].reshape(ch, cw).copy()
+
+
+def redact_moving_build(state, plane, stats, frame, plate, det_packed, table, option, frame_index=0, n_frames=None, gate=None, cut=None,
+                        tracked=False):
+    """The plane of weights of one frame under the moving rule (DESIGN §8 "Moving rule", frcnn_redact_moving_build) -> ``plane``:
+    ``frame``, an (h, w, 3) uint8 device tensor that no edit has touched, is compared with the plate of ``plate`` (``plate_state``, already
+    updated with this same frame); a pixel that differs by more than D, outside the boxes of ``det_packed`` (as ``plate_update`` reads it)
+    whose class is set in ``table`` (``redact_moving_table``), is foreground; cells of 8 x 8 vote and hold in ``state``
+    (``redact_moving_state``); the moving cells grown by G and feathered by F become ``plane``, a u8 device tensor of
+    ``redact_region_plane_bytes(h, w)`` bytes that ``redact_region_prepare`` / ``redact_region_apply_u8`` take; ``stats``: int32 [4]
+    device, [real, cells_now, covered, full].  ``option``: ``redact_moving_option``'s form.  ``frame_index`` / ``n_frames`` / ``gate`` /
+    ``cut`` as ``plate_update``'s.  Three launches, everything guarded on the device: the call can be captured in a graph."""
+    _require_gpu()
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    assert state.is_cuda and state.dtype == torch.uint8 and state.dim() == 1 and state.is_contiguous()
+    assert plane.is_cuda and plane.dtype == torch.uint8 and plane.dim() == 1 and plane.is_contiguous()
+    assert plate.is_cuda and plate.dtype == torch.int32 and plate.dim() == 1 and plate.is_contiguous()
+    assert stats.is_cuda and stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() == _lib.REDACT_MOVING_STATS_WORDS
+    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    assert int(state.numel()) == redact_moving_state_bytes(h, w) and int(plane.numel()) == redact_region_plane_bytes(h, w)
+    assert int(plate.numel()) == plate_state_words(h, w)
+    rows = _plate_rows(det_packed, tracked)
+    if n_frames is None:
+        n_frames = torch.ones(1, dtype=torch.int32, device="cuda")
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert gate is None or (gate.is_cuda and gate.dtype == torch.int32 and gate.numel() >= 1)
+    assert cut is None or (cut.is_cuda and cut.dtype == torch.int32 and cut.numel() >= 1)
+    D, K, H, G, F, unknown = option[:6]
+    margin = option[11]
+    _lib.call("frcnn_redact_moving_build", _p(state), _p(plane), _p(stats), h, w, _p(frame), _p(plate), _p(det_packed), rows,
+              int(bool(tracked)), _p(table), int(table.numel()), int(margin), int(D), int(K), int(H), int(G), int(F),
+              unknown if isinstance(unknown, int) else REDACT_MOVING_UNKNOWN.index(unknown), int(frame_index), _p(n_frames), _p(gate), _p(cut),
+              _stream())
+    return plane
+
+
+def redact_moving_stats(stats):
+    """(host only; reads the stats back) -> {"real", "cells", "covered", "full"} of one frame's stats, or a list of them for an [F][4]
+    tensor, device tensor or host copy."""
+    host = stats.detach().cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    one = lambda s: {"real": int(s[0]), "cells": int(s[1]), "covered": int(s[2]), "full": int(s[3])}
+    return one(host) if host.ndim == 1 else [one(s) for s in host]
+
+
 # ----------------------------------------------------------------------------- output scale
 SCALE_MAX_RATIO = _lib.SCALE_MAX_RATIO
 

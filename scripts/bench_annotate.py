@@ -32,7 +32,7 @@ without and with ``--detect_every 4``.  ``--track_backtrack`` (``run_track_backt
 ``--track --track_motion 8`` leg without and with ``--track_lookback`` at its default (as many frames as a pass holds, at most 8), and the
 look-back call of one pass alone.  ``--track_scene_cut`` (``run_track_scene_cut``) runs the ``--track --track_motion 8`` leg without and with
 ``--track_scene_cut`` at its default.  ``--track_trails`` (``run_track_trails``) runs the same leg without and with ``--track_trails`` at its
-defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--out_scale`` (``run_out_scale``) runs in-memory annotating passes, the PNG-file to PNG-file leg (device encoder, huffman) and y4m to y4m, each without and with ``--out_scale 2``.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).  ``--redact_shape`` (``run_redact_shape``) runs the ``--redact all --redact_mode blur`` passes without and with ``--redact_shape ellipse --redact_feather 8``.  ``--track_low`` (``run_track_low``) runs the ``--det_threshold 0.5 --track --track_motion 8`` leg without and with ``--track_low 0.1``.  ``--redact_region`` (``run_redact_region``) runs in-memory annotating passes without and with two ``--redact_region`` polygons of a tenth of the frame each, ``--region_mode blur --region_feather 8``.
+defaults.  ``--count_line`` (``run_count_line``) runs the same leg without and with two counting lines.  ``--zone`` (``run_zone``) runs the same leg without and with two rectangular zones of a quarter of the frame each.  ``--heatmap`` (``run_heatmap``) runs the same leg without and with ``--heatmap all`` at its defaults.  ``--remove`` (``run_remove``) runs the same leg without and with ``--remove all`` at its (provisional) defaults.  ``--track_reid`` (``run_track_reid``; ``--track --track_reid`` says the same) runs the same leg without and with ``--track_reid`` at its (provisional) defaults.  ``--out_scale`` (``run_out_scale``) runs in-memory annotating passes, the PNG-file to PNG-file leg (device encoder, huffman) and y4m to y4m, each without and with ``--out_scale 2``.  ``--post`` (``run_post``) runs in-memory annotating passes without and with ``--nms soft_gaussian --box_vote`` (the post-process option, an engine of its own).  ``--redact_shape`` (``run_redact_shape``) runs the ``--redact all --redact_mode blur`` passes without and with ``--redact_shape ellipse --redact_feather 8``.  ``--track_low`` (``run_track_low``) runs the ``--det_threshold 0.5 --track --track_motion 8`` leg without and with ``--track_low 0.1``.  ``--redact_region`` (``run_redact_region``) runs in-memory annotating passes without and with two ``--redact_region`` polygons of a tenth of the frame each, ``--region_mode blur --region_feather 8``.  ``--redact_moving`` (``run_redact_moving``) runs in-memory annotating passes plain, with ``--redact_moving`` (S = 8) and with ``--remove all`` on a generated sequence -- a noise background with a 64 x 64 block that moves 4 pixels a frame.
 
     python scripts/bench_annotate.py [--frames 256] [--reps 3] [--pairs kitti_r101_bf16,voc_r50_f32] [--png_encoder host|device|both|all]
                                      [--legs host,device_huffman,jpeg_host,jpeg_device,jpeg_host_420_opt,jpeg_device_420_opt,pngdec_host,pngdec_device,pngdec_device_full] [--content noise|photo]
@@ -452,6 +452,65 @@ def run_redact_region(name, cfg, n_frames, reps, content="noise"):
         res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
         res[k + "_runs_s"] = [round(t, 4) for t in ts]
     res["region_over_plain"] = round(statistics.median(times["plain"]) / statistics.median(times["redact_region"]), 3)
+    return res
+
+
+def moving_frames(h, w, n):
+    """A generated fixed-camera sequence: one noise background, and a 64 x 64 block of other noise that moves 4 pixels a frame along a
+    row in the middle (wrapping), so that the plate settles and the net really hides something."""
+    import numpy as np
+    rs = np.random.RandomState(5)
+    back, block = rs.randint(0, 256, (h, w, 3)).astype(np.uint8), rs.randint(0, 256, (64, 64, 3)).astype(np.uint8)
+    y, out = max((h - 64) // 2, 0), []
+    for i in range(n):
+        a, x = back.copy(), (4 * i) % max(w - 64, 1)
+        a[y:y + 64, x:x + 64] = block[:min(64, h - y), :min(64, w - x)]
+        out.append(a)
+    return out
+
+
+def run_redact_moving(name, cfg, n_frames, reps, content="generated"):
+    """``--redact_moving``: what the moving net (DESIGN §8 "Moving rule") costs.  Three legs in ONE session, alternating inside every
+    repetition, on ``moving_frames`` (noise frames never settle a plate): in-memory annotating passes plain, with ``redact_moving`` at its
+    defaults and S = 8, and with ``remove=("all", 8, 10, 8)`` on the same frames; plate and moving state are reset in front of every run.
+    Reports frames/s of each, the ratios and the mean share of the frame the net hid.  Not separated: the three build kernels alone, the
+    plate update a pass without ``remove`` now runs, and real content."""
+    import numpy as np
+    from faster_rcnn_amd import entry, ops, shapes, util
+    mgr, det = build(cfg)
+    h, w = cfg["hw"]
+    srcs = moving_frames(h, w, n_frames)
+    imgs = [shapes.Image(shapes.Metadata("f%04d" % i, w, h, [], "none"), s) for i, s in enumerate(srcs)]
+    resized, ratios = util.resize_imgs(imgs, min_size=cfg["resize"][0], max_size=cfg["resize"][1])
+    eng = entry.for_models(mgr, det, 64, 16, in_flight=entry.default_in_flight(cfg["dtype"]))
+    moving = ops.redact_moving_option(settle=8)
+
+    def leg(**kw):
+        def run():
+            eng.plate_reset()
+            eng.moving_reset()
+            return annotate_in_memory(eng, resized, ratios, **kw)
+        return run
+
+    legs = {"plain": leg(), "redact_moving": leg(redact_moving=moving), "remove": leg(remove=ops.plate_option("all"))}
+    times = {k: [] for k in legs}
+    for fn in legs.values():                                        # warm-up: captures
+        fn()
+    for _ in range(reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    hidden = [float((a != b).any(axis=2).mean()) for a, b in zip(legs["redact_moving"](), legs["plain"]())]      # (both draw the same boxes)
+    res = {"frames": n_frames, "frame_hw": [h, w], "resize_dims": list(cfg["resize"]), "dtype": cfg["dtype"], "depth": cfg["depth"],
+           "content": "generated: noise background, a 64x64 block moving 4 px a frame", "redact_moving": list(moving),
+           "images_per_pass": eng.batch, "in_flight": eng.in_flight, "pixels_changed_share_mean": round(float(np.mean(hidden)), 4),
+           "pixels_changed_share_peak": round(max(hidden), 4)}
+    for k, ts in times.items():
+        res[k + "_fps"] = round(n_frames / statistics.median(ts), 1)
+        res[k + "_runs_s"] = [round(t, 4) for t in ts]
+    res["moving_over_plain"] = round(statistics.median(times["plain"]) / statistics.median(times["redact_moving"]), 3)
+    res["moving_over_remove"] = round(statistics.median(times["remove"]) / statistics.median(times["redact_moving"]), 3)
     return res
 
 
@@ -1301,6 +1360,9 @@ def main():
     ap.add_argument("--redact_region", action="store_true", help="instead of the legs above: in-memory annotating passes without and with two "
                                                                  "--redact_region polygons of a tenth of the frame each, --region_mode blur "
                                                                  "--region_feather 8, alternating in one session")
+    ap.add_argument("--redact_moving", action="store_true", help="instead of the legs above: in-memory annotating passes plain, with "
+                                                                 "--redact_moving (S = 8) and with --remove all, on a generated sequence "
+                                                                 "with a moving block, alternating in one session")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -1309,6 +1371,9 @@ def main():
     for name in args.pairs.split(","):
         if args.y4m:
             out[name] = run_y4m(name, PAIRS[name], args.frames, args.reps, args.content)
+            continue
+        if args.redact_moving:
+            out[name] = run_redact_moving(name, PAIRS[name], args.frames, args.reps)
             continue
         if args.redact_region:
             out[name] = run_redact_region(name, PAIRS[name], args.frames, args.reps, args.content)
