@@ -43,136 +43,16 @@ for a frame directory, whose frames must then share one size) instead of frame f
 frames' chroma upsampling and colour matrix, and the inverse on the way out, run inside the passes (csrc/y4m.hip, DESIGN §8); a frame's
 "path" in the printed lines is ``<name>#<frame index>``.
 
-``redact=(classes, mode, size, margin)`` (``--redact CLASSES [--redact_mode pixelate|blur|fill] [--redact_size N] [--redact_margin N]``)
-HIDES the detected objects of those classes -- names of the active class mapping, or "all" -- instead of, or as well as, outlining them:
-every pixel inside a box (grown by ``margin``, clipped to the frame) becomes the mean of its cell of an N x N grid ("pixelate", N = 2..64,
-default 16), a box blur of radius N ("blur", 1..32, default 12) or black ("fill"), computed from the untouched frame (ops.redact_u8,
-csrc/redact.hip; the rule is DESIGN §8's).  Unlike the drawing, a box that crosses the frame's border IS redacted, and 'DontCare' / 'Misc'
-are when named.  It runs inside the pass in front of the drawing step, so before every encoder and for every input format.
-``draw=False`` (``--no_draw``) leaves the boxes and labels out.  The printed lines do not change with either.
-
-``redact_shape=(shape, feather)`` (``--redact_shape {box,ellipse} --redact_feather N``, with ``--redact`` only) shapes what the redaction
-puts on the picture (ops.redact_shaped_u8, csrc/redact_shape.hip; DESIGN §8 "Shape rule"): "ellipse" hides the ellipse inscribed in each
-box grown by the margin -- the box is NOT clipped, so an ellipse across the border stays that of the whole box --, and a feather of N
-pixels (0..32) lets the replacement fade into the scene OUTSIDE the shape: what the hard shape hides stays fully hidden.  Held and
-back-filled boxes are shaped like live ones; the plate of ``--remove``, the tracker, the heat map and the drawn boxes keep their
-rectangles.  It works for file, y4m and stdin input and with every encoder, as the redaction does.  "box" with feather 0 is the default
-and IS the plain redaction: no pass, key, printed line or output byte changes.
-
-``track=(thr, hold, grow)`` (``--track [--track_iou PCT] [--track_hold N] [--track_grow N]``) joins the detections of consecutive frames
-into tracks on the device (ops.track_update, csrc/track.hip; DESIGN §8 "Tracking rule"): a detection whose box overlaps a track's last
-box of the same class by at least PCT percent IoU (default 30) continues it and is labelled ``cls#id``; a track the detector loses is HELD
-for N frames (default 8), its box growing by ``grow`` pixels per frame (default 0) -- held boxes are redacted with ``--redact`` (so the
-redaction does not flicker off when the detector misses a frame) and never drawn.  Frames are tracked in input order; the tracked classes
-are the drawable ones and the redacted ones.  ``--tracks_out PATH`` writes one MOTChallenge line per live tracked row
-(``frame,id,left,top,width,height,prob,cls,-1,-1``, frames counted from 1).  The printed dets then carry "track_id".
-``track_motion=R`` (``--track_motion [R]``, with ``--track``; 1..16, 8 when bare) moves every track's box with the pixels under it between
-consecutive frames (ops.track_update_motion, csrc/track_motion.hip; DESIGN §8 "Motion rule": an integer block match of at most R pixels
-either way on a 32 x 32 sample grid of the box, taken only when it gains a grey level per sample): a held box follows its object instead
-of standing still, and a fast object is matched where it now is.  The printed lines and ``--tracks_out`` keep their form: held rows are
-still not written.
-``detect_every=K`` (``--detect_every K``, with ``--track --track_motion``; 2..16) runs the detector on every K-th frame only
-(ops.track_update_interval, csrc/track_interval.hip; DESIGN §8 "Interval rule"): a pass takes B * K frames, and on the frames between
-two detected ones every track's box follows the pixels under it by the block match alone -- drawn, redacted and written to
-``--tracks_out`` with the prob of its last match, printed with "propagated": True.  Nothing is matched, aged or born there: ``hold``
-counts detected frames.  The K-th frames are counted within each group of at most B * K consecutive frames of one geometry: in a video
-that is every K-th frame, in a list of mixed sizes a detected frame follows every change of size.  Not together with
-``--track_lookback``, and not on the one-frame-at-a-time paths.
-``track_backtrack=N`` (``--track_backtrack [N]``, with ``--detect_every K``; 1..16, at least K - 1, at most B * K; bare: as many as a
-pass holds, at most 16) follows every track of a detected frame BACK through the frames in front of it (ops.track_backtrack,
-csrc/track_backtrack.hip; DESIGN §8 "Back-track rule") -- a continued track as far as the detected frame before, a new one over N frames
--- and hides the boxes found there too: a frame between two detections is covered from both sides.  The output then runs one pass
-behind the input, as with ``--track_lookback``; the back-filled rows are printed with "backfilled": k, never drawn and not written to
-``--tracks_out``.
-``track_scene_cut=PCT`` (``--track_scene_cut [PCT]``, with ``--track --track_motion``, with or without ``--detect_every K``; 1..100; bare:
-40, a provisional default that no real footage has been measured for) ends every track at a hard cut (ops.track_update_cut,
-csrc/track_cut.hip; DESIGN §8 "Cut rule"): a frame whose 4 x 4-region luma histogram differs from that of the frame before by PCT percent
-of the largest distance there is starts a new scene -- no id is carried into it, no held box of the old scene is redacted in it, and
-between two detected frames nothing is shown behind a cut until the next detected frame.  A line ``scene cut: <path>`` is printed in front
-of that frame's lines; ``--tracks_out`` keeps its format.  Fades and dissolves are not detected.  Not together with ``--track_lookback``
-or ``--track_backtrack``: their backward chains would have to stop at a cut.
-``track_trails=(N, W)`` (``--track_trails [N]``, with ``--track`` in any of the forms above; 2..64 points, 16 when bare; ``--trail_width W``,
-1..9 pixels, default 3) draws the path every track took (ops.track_trails_update / ops.track_trails_draw_u8, csrc/track_trails.hip; DESIGN
-§8 "Trail rule"): the centre of every live tracked box joins the trail of its id, and each frame shows the last N points of the ids live
-in it as a line W pixels wide in the colour of the id, over the redaction and under the boxes and labels.  A trail ends where its id
-ends -- at a scene cut, or when the tracker gives the id up.  The printed lines and ``--tracks_out`` are unchanged.  Not with ``--no_draw``.
-``heatmap=(classes, A, S)`` (``--heatmap CLASSES``, class names of the active mapping or ``all``; ``--heatmap_alpha A``, 1..255, default 160;
-``--heatmap_decay S``, 0..15, default 0 = none) shows where the objects of those classes have been over the whole list (ops.heat_update /
-ops.heat_draw_u8, csrc/heat.hip; DESIGN §8 "Heat rule"): every pixel of a map on the device gains 256 per box that covers it in every frame
--- every detection, or with ``--track`` the live tracked rows; held and back-filled boxes are guesses and do not count -- loses
-ceil(v / 2^S) per frame, and is blended into each frame over the redaction and under the trails, boxes and labels, black through red and
-yellow to white at the hottest pixel.  ``annotate_images`` / ``annotate_stream`` start with a cold map, ``get_annotated_frame`` continues
-the map of the calls before it (``reset_heat`` starts anew).  ``heatmap_out=PATH.png`` (``--heatmap_out``) writes the map at the end of
-the list as an 8-bit grey PNG, one per frame size met (``PATH_<w>x<h>.png`` when there are several).  With every other option.
-``count=(lines, classes, W)`` (``--count_line X1,Y1,X2,Y2``, repeatable up to 8 times, with ``--track`` in any of the forms above;
-``--count_classes``, ``--count_width``) counts the tracks whose box centre crosses a line, once per id, line and direction
-(ops.count_update / ops.count_draw_u8, csrc/count.hip; DESIGN §8 "Count rule"): each frame shows the lines and a label ``L{l} +{pos}
--{neg}`` per line over the redaction, heat map and trails and under the boxes, ``counts_out=PATH`` (``--counts_out``) receives a CSV row
-``frame,line,direction,id,cls`` per crossing, and at the end one line per counting line and the totals per class are printed.  A list
-starts from zero totals; ``get_annotated_frame(count=, counts_out=)`` and the eager path take the option as one-frame calls that continue
-the state (``reset_counts`` zeroes it).  On the command line a value that begins with a minus sign needs the ``=`` form:
-``--count_line=-5,0,-5,100``.
-``zone=(zones, classes, W, anchor)`` (``--zone X1,Y1,X2,Y2,X3,Y3[,...]``, repeatable up to 8 times, with ``--track`` in any of the forms
-above; ``--zone_classes``, ``--zone_width``, ``--zone_anchor centre|bottom``) tests every track's box centre, or the middle of its bottom
-edge, against polygon zones with an exact even-odd rule (ops.zone_update / ops.zone_draw_u8, csrc/zone.hip; DESIGN §8 "Zone rule"): each
-frame shows the occupied zones tinted, every zone's outline and a label ``Z{z} {occupancy}/{visitors}`` behind the heat map and under
-every line, ``zones_out=PATH`` (``--zones_out``) receives a CSV row ``frame,zone,kind,id,cls,dwell`` per event, kind enter, exit or lost,
-and at the end one line per zone is printed: visitors, peak, stays and the mean dwell of the completed stays.  A list starts from an
-empty state; ``get_annotated_frame(zone=, zones_out=)`` and the eager path take the option as one-frame calls that continue the state
-(``reset_zones`` starts over).  ``--no_draw`` still counts.  A value that begins with a minus sign needs the ``=`` form: ``--zone=-5,0,9,0,9,9``.
-``remove=(classes, S, T, M)`` (``--remove CLASSES``, class names of the active mapping or ``all``; ``--remove_settle S``, 1..255;
-``--remove_tol T``, 0..255; ``--remove_margin M``, 0..64; the defaults 8, 10 and 8 are PROVISIONAL: nobody has measured them on real
-footage) paints the objects of those classes out of fixed-camera footage (ops.plate_update / ops.plate_fill_u8, csrc/plate.hip; DESIGN §8
-"Plate rule"): a background plate on the device learns every pixel that no box of ANY class touches -- held and back-filled tracked rows
-too -- and that stays within T of the value its run began with for S frames, and the boxes of the classes, grown by M, are filled with
-it.  Where the plate is not known yet the redaction shows, if ``--redact`` covers the classes, else black.  An object that stands still
-and is never detected becomes background after S frames: that is the rule's limit.  A ``--track_scene_cut`` cut empties the plate.  A
-list starts from an empty plate; ``get_annotated_frame(remove=)`` and the eager path continue it as one-frame calls (``reset_plate``
-empties it).  ``plate_out=PATH.png`` (``--plate_out``) writes the plate at the end as an RGB PNG with unknown pixels black, one per
-frame size met, named as ``--heatmap_out`` names its files, and one line per size is printed: ``plate 1242x375: 128 frames, 97.3 %
-known`` (a size met in both channel orders has two plates: a line and a file for each).  With every other option, ``--no_draw`` included, with and without ``--track``.
-``track_reid=(pct, keep)`` (``--track_reid [PCT]``, 1..100, bare: 25; ``--reid_keep N``, 1..4095 frames, default 250; both defaults are
-PROVISIONAL: nobody has measured them on real footage; with ``--track`` in every form but ``--track_lookback`` / ``--track_backtrack``)
-gives an object that was hidden for longer than ``--track_hold`` frames its old id back (ops.track_reid_update, csrc/track_reid.hip;
-DESIGN §8 "Re-identify rule"): every live tracked row gets a colour signature, and a new track whose signature lies within PCT percent
-of that of an id the tracker gave up at most N frames ago carries that id -- in the labels, ``--tracks_out``, the printed ``track_id``,
-the trails, the count lines (which then count it once) and the zones.  A line ``re-identified: <path> id <pid>`` is printed in front
-of that frame's lines and ``re-identified: N`` at the end; ``reid_out=PATH`` (``--reid_out``) receives a CSV row
-``frame,id,tracker_id,cls,distance,gap`` per event.  A list starts from an empty memory; ``get_annotated_frame(track_reid=)`` and the
-eager path continue it as one-frame calls (``reset_tracks`` empties it).  A ``--track_scene_cut`` cut empties it too.
-``det_threshold=T`` (``--det_threshold T``, 0..1; default DET_THRESHOLD = 0.0, the reference script's) reports detections of score T or
-more only, with or without ``track``.  ``track_low=L`` (``--track_low L``, with ``--track``, L < T; no bare form: no default has been
-measured) is the weak rule (DESIGN §8 "Weak rule", the ``strong=`` form of the tracker calls, csrc/track.hip): the passes are submitted
-with det_threshold=L and track_strong=T, a detection with a score in [L, T) may only continue a track no stronger one continued and is
-dropped otherwise, and every printed line and ``tracks_out`` show the kept rows.  The eager path (a foreign model) takes
-``det_threshold`` and refuses ``track_low`` by name.  Without the two, no pass, key, printed line or output byte changes.
-``redact_region=(regions, mask, mode, size, feather)`` (``--redact_region X1,Y1,X2,Y2,X3,Y3[,...]``, repeatable up to 8 times, ``--zone``'s
-grammar; ``--redact_mask PATH.png``, any file PIL opens, read as grey, >= 128 hides; ``--region_mode pixelate|blur|fill``, default fill;
-``--region_size N``; ``--region_feather N``, 0..32, default 0) hides PLACES, not objects: a burnt-in timestamp, a monitor, a window, the
-bonnet (ops.redact_region_plane / ops.redact_region_prepare / ops.redact_region_apply_u8, csrc/redact_region.hip; DESIGN §8 "Region
-rule").  Polygons -- exact even-odd interior, a polygon owns its left and top boundary -- and the mask become one plane of weights per
-frame size on the device, once; every frame is then blended under it inside its pass with no detection row involved: what replaces an
-area comes from the untouched frame, the area goes on behind the plate fill of ``--remove`` (no learned background returns into it) and
-under the heat map, lines, boxes and labels, and the edge fades OUTWARDS over the feather.  It needs neither ``--redact`` nor
-``--track`` and works with every option, input and encoder.  Polygons apply to every frame size; a mask is held to one size, and a frame
-it does not fit is refused by name.  ``--plate_out`` shows every pixel of an area black; ``--heatmap_out``, ``--tracks_out`` and every
-per-frame line are unchanged; at the end one line per frame size is printed: ``redact regions 1242x375: 2 regions + mask, 12.3 % of the
-frame hidden``.  The three ``--region_*`` flags are refused by name without an area.  Without the option, no pass, key, printed line or
-output byte changes.
-``redact_moving=True | {keywords} | 12 values`` (``--redact_moving``; ``--moving_tol D``, 0..255; ``--moving_min K``, 1..64;
-``--moving_hold H``, 0..255 frames; ``--moving_grow G`` and ``--moving_feather F``, 0..32 pixels; ``--moving_unknown show|hide``;
-``--moving_except CLASSES``; ``--moving_mode pixelate|blur|fill``, default pixelate; ``--moving_size N``; ``--moving_out PATH``, a CSV
-``frame,cells,covered``; the defaults 24, 8, 4 and 8 are PROVISIONAL: nobody has measured them on real footage) is a safety net under the
-detector for fixed-camera footage: whatever differs from the plate of ``--remove`` is hidden, detected or not (ops.redact_moving_build,
-csrc/redact_moving.hip; DESIGN §8 "Moving rule").  A run without ``--remove`` learns the plate all the same -- ``--remove_settle`` /
-``--remove_tol`` / ``--remove_margin`` go with either flag -- and paints nothing out.  A list starts from an empty plate and an empty
-moving state; ``get_annotated_frame(redact_moving=)`` and the eager path continue them as one-frame calls (``reset_moving`` and
-``reset_plate`` empty them).  Until a pixel's background is known it is shown (``--moving_unknown hide`` blanks the start instead):
-the first S frames are not protected by the net under the default; use a large ``--remove_settle``, since the net does not block
-learning.  At the end one line per frame size is printed: ``moving net 1242x375: 128 frames, mean 3.2 % hidden, peak 17.0 %``.  The
-satellite flags are refused by name without ``--redact_moving``.  Without the option, no pass, key, printed line or output byte changes.
+What is DONE to the frames on the way -- hiding objects (``redact``, ``redact_shape``, ``remove``), hiding places (``redact_region``) and
+whatever moves (``redact_moving``), tracking (``track`` and its ``track_*`` forms, ``detect_every``), the heat map, count lines and
+zones, the thresholds, the post-process and the output size -- is one value, ``AnnotateOptions``: its docstring describes every option
+once, every entry point takes its fields as keywords, and ``build_parser``'s help texts state the flag of each (``--redact CLASSES``,
+``--track``, ``--count_line X1,Y1,X2,Y2``, ...) with its range and default.  All of it runs inside the passes, in front of every encoder
+and for every input format, in the order ``frame_edit.EditChain``'s docstring states; without an option no pass, key, printed line or
+output byte is another.
 """
 import collections
+import dataclasses
 import os
 import pathlib
 import re
@@ -366,78 +246,48 @@ def _eager_heat_state(class_mapping, h, w):
     return _eager_states(class_mapping).heat_state(h, w)
 
 
-def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, track_motion=None, track_scene_cut=None, info=None,
-               track_trails=None, rgb=False, heatmap=None, count=None, zone=None, remove=None, track_reid=None, out_size=None,
-               redact_shape=None, redact_region=None, redact_moving=None):
+def draw_eager(frame, dets, class_mapping, redact=None, draw=True, track=None, info=None, rgb=False, **options):
     """The editing chain over ONE frame and its host dets (the eager path, foreign models): ``frame`` (h, w, 3) uint8 is edited in
     place, by a one-frame ``frame_edit.EditChain`` -- its docstring states the calls and their order -- on this class mapping's eager
-    states (``reset_tracks``, ``reset_heat`` and ``reset_counts`` empty them); ``rgb``: the frame's channel order (False: B, G, R).
-    ``redact`` = (classes, mode, size, margin); ``draw`` False: nothing is drawn.
-    ``track`` = (thr, hold, grow): ``dets`` is edited in place as ``collect_batch`` returns it: "track_id" on every det, the held rows
-    appended with "held".  ``track_motion`` = R: the motion step, with the frame as it came and this class mapping's motion state for the
-    frame's size.  ``track_scene_cut`` = PCT (with ``track_motion``): the cut step -- the kept frame is the reference --, and ``info``, a
-    dict, receives "scene_cut": True when the frame is a cut.
-    ``track_trails`` = (N, W) (with ``track``, not with ``draw`` False).
-    ``heatmap`` = (classes, A, S): the detections, or with ``track`` the live tracked rows, heat this class mapping's state for the
-    frame's size; a frame without detections is blended too.
-    ``count`` = (lines, classes, W) (with ``track``): ``info`` receives "crossings": [(line, dir, id, cls)].
-    ``zone`` = (zones, classes, W, anchor) (with ``track``): ``info`` receives "zones": {"occupancy", "events"} as a pass's result does.
-    ``remove`` = (classes, S, T, M): the frame teaches this class mapping's plate state for its size and channel order, and the boxes of
-    those classes are painted out with it (``reset_plate`` empties it); a frame without detections teaches it too.
-    ``track_reid`` = (pct, keep) (with ``track``): the ids are those of the re-identify rule, and ``info`` receives "reid": [(pid, tid,
-    cls, distance, gap)].
-    ``out_size`` = ("size", W, H) or ("scale", N): the LAST step (DESIGN §8 "Scale rule", ops.downscale_u8): the edited frame scaled down
-    on the device is what is returned, a new (H, W, 3) array; ``frame`` is edited in place as without it.
-    ``redact_shape`` = (shape, feather) (with ``redact``): the redaction hides ellipses and fades out over ``feather`` pixels (DESIGN §8
-    "Shape rule", ops.redact_shaped_u8); ("box", 0) is the call without it.
-    ``redact_region`` = (regions, mask, mode, size, feather): the static areas are hidden whatever ``dets`` holds (DESIGN §8 "Region
-    rule", ops.redact_region_prepare / ops.redact_region_apply_u8); the plane of the frame's size is this class mapping's.
-    ``redact_moving`` = True, a dict of ops.redact_moving_option's keywords or its 12 values: the frame teaches this class mapping's plate
-    (as with ``remove``, without a fill when there is none) and whatever differs from it is hidden (DESIGN §8 "Moving rule"); the moving
-    state of the frame's size and channel order goes on from the call before (``reset_moving`` empties it); ``info`` receives "moving":
-    {"cells", "covered"}."""
+    states, which go on from the call before (``reset_tracks``, ``reset_heat``, ``reset_counts``, ``reset_zones``, ``reset_plate`` and
+    ``reset_moving`` empty them); ``rgb``: the frame's channel order (False: B, G, R).  ``redact``, ``draw``, ``track`` and ``options``:
+    the options of ``AnnotateOptions`` that edit a frame -- no ``track_lookback`` / ``detect_every`` / ``track_backtrack``, no ``post``
+    and no output.  A frame without detections still teaches the heat map, the plate and the moving net.
+    With ``track``, ``dets`` is edited in place as ``collect_batch`` returns it: "track_id" on every det, the held rows appended with
+    "held".  ``info``, a dict, receives the frame's marks as a pass's result carries them: "scene_cut": True when the frame is a cut,
+    "crossings": [(line, dir, id, cls)], "zones": {"occupancy", "events"}, "reid": [(pid, tid, cls, distance, gap)] and "moving":
+    {"cells", "covered"}, each with its option.  With ``out_size`` the edited frame scaled down on the device is what is returned, a new
+    (H, W, 3) array; ``frame`` is edited in place as without it."""
+    return _edit_eager(frame, dets, class_mapping, AnnotateOptions.checked(class_mapping, "draw", frame, redact=redact, draw=draw, track=track,
+                                                                           **options), info, rgb)
+
+
+def _edit_eager(frame, dets, class_mapping, o, info=None, rgb=False):
+    """``draw_eager`` with its options checked: ``o``, an ``AnnotateOptions``."""
     import torch
-    redact_shape = _redact_shape(redact_shape, redact)
-    redact_region = _redact_region(redact_region)
-    if redact_region is not None and redact_region[1] is not None and redact_region[1].shape != tuple(frame.shape[:2]):
-        raise ValueError("redact_region: the mask is %dx%d, the frame %dx%d" % (redact_region[1].shape[::-1] + (frame.shape[1], frame.shape[0])))
-    scaled_hw = None if out_size is None else ops.scale_option(out_size, frame.shape[:2])
-    track_reid = _track_reid(track_reid, track)
-    track_trails = _track_trails(track_trails, track, draw)
-    heatmap = _heatmap(heatmap)
-    remove = _remove(remove)
-    redact_moving = _redact_moving(redact_moving, remove, class_mapping)
-    count = _count(count, track)
-    zone = _zone(zone, track)
-    radius = _track_motion(track_motion, track)
-    track_scene_cut = _track_scene_cut(track_scene_cut, track, track_motion, None, None)
-    if track is not None or heatmap is not None or remove is not None or redact_region is not None or redact_moving is not None or (dets and (draw or redact is not None)):      # (else the frame stays as it is)
-        dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
+    scaled_hw = None if o.out_size is None else ops.scale_option(o.out_size, frame.shape[:2])
+    if dets and (o.draw or o.redact is not None) or any(v is not None for v in (o.track, o.heatmap, o.remove, o.redact_region, o.redact_moving)):
+        dev = torch.from_numpy(np.ascontiguousarray(frame)).cuda()      # (else the frame stays as it is)
         packed = torch.from_numpy(_pack_dets(dets, class_mapping)).cuda()
-        if redact is not None:
-            redact = (redact[0] if redact[0] == "all" else tuple(redact[0]),) + tuple(redact[1:])
         states = _eager_states(class_mapping)
-        spec = entry.PassSpec(annotate=True, redact=redact, draw=draw, track=track, track_scene_cut=track_scene_cut, track_trails=track_trails,
-                              track_motion=radius, heat=heatmap, count=count, zone=zone, remove=remove, track_reid=track_reid,
-                              redact_shape=redact_shape, redact_region=redact_region, redact_moving=redact_moving)
-        chain = EditChain(states, spec, 1, 1, frame.shape[:2], rgb)
+        chain = EditChain(states, entry.PassSpec(**o.edit_keywords()), 1, 1, frame.shape[:2], rgb)
         chain.update(dev.view(-1), 0, packed, states.one_frame())         # (in front of the edits: ``dev`` is still the frame as it came)
         chain.edit(0, dev)
-        if track is not None:
+        if o.track is not None:
             _, ids, held = ops.tracked_dets(chain.host_tracked[0].cpu().numpy(), _names_by_index(class_mapping), start=len(dets))
             for k, d in enumerate(dets):
                 d["track_id"] = int(ids[k])
             dets += held
-        if info is not None and track_scene_cut is not None and int(chain.cuts[0]):
+        if info is not None and o.track_scene_cut is not None and int(chain.cuts[0]):
             info["scene_cut"] = True
-        if info is not None and count is not None:
+        if info is not None and o.count is not None:
             info["crossings"] = ops.count_events(chain.count_lists[0].cpu().numpy())
-        if info is not None and zone is not None:
+        if info is not None and o.zone is not None:
             zlist = chain.zone_lists[0].cpu().numpy()
-            info["zones"] = {"occupancy": ops.zone_occupancy(zlist, len(zone[0])), "events": ops.zone_events(zlist)}
-        if info is not None and track_reid is not None:
+            info["zones"] = {"occupancy": ops.zone_occupancy(zlist, len(o.zone[0])), "events": ops.zone_events(zlist)}
+        if info is not None and o.track_reid is not None:
             info["reid"] = ops.track_reid_events(chain.reid_lists[0].cpu().numpy())
-        if info is not None and redact_moving is not None:
+        if info is not None and o.redact_moving is not None:
             stats = ops.redact_moving_stats(chain.moving_stats[0])
             info["moving"] = {"cells": stats["cells"], "covered": stats["covered"]}
         frame[...] = dev.cpu().numpy()
@@ -558,7 +408,8 @@ def moving_line(w, h, covered):
 
 class MovingLog:
     """Where the moving net's counts of a sequence go: the ``--moving_out`` CSV ``frame,cells,covered`` (``path`` None: none) and the
-    covered pixels per frame size, for the lines at the end."""
+    covered pixels per frame size, for the lines at the end.  A sequence report (``_reports``)."""
+    output = "moving_out"
 
     def __init__(self, path):
         self.file = open(path, "w") if path is not None else None
@@ -573,6 +424,13 @@ class MovingLog:
 
     def lines(self):
         return [moving_line(w, h, covered) for (h, w), covered in sorted(self.per_size.items())]
+
+    def frame(self, pos, label, frame, dets, marks):
+        self.add(pos + 1, frame.height, frame.width, marks["moving"])
+
+    def end(self):                                        # (host only: what the passes returned; ``close`` closes the file)
+        for line in self.lines():
+            print(line)
 
     def close(self):
         if self.file is not None:
@@ -808,15 +666,6 @@ def track_scene_cut_from_args(args):
         raise ValueError("--track_scene_cut: %s" % e) from None
 
 
-def _track_motion(track_motion, track):
-    """``draw_eager``'s ``track_motion`` checked -> the search radius, or None."""
-    if track_motion is None:
-        return None
-    if track is None:
-        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
-    return ops.track_motion_radius(track_motion)
-
-
 def _track_scene_cut(track_scene_cut, track, track_motion, track_lookback, track_backtrack):
     """``annotate_images`` / ``annotate_stream`` / ``get_annotated_frame``'s ``track_scene_cut`` checked -> the percentage, or None."""
     if track_scene_cut is None:
@@ -928,10 +777,12 @@ def print_counts(n_lines, totals, per_class, events_dropped):
 
 
 class CountsLog:
-    """Where the crossings of a counted sequence go: the ``--counts_out`` file (``path`` None: none) and the totals per class name."""
+    """Where the crossings of a counted sequence go: the ``--counts_out`` file (``path`` None: none) and the totals per class name.  A
+    sequence report (``_reports``): ``n_lines`` and ``state()``, the count state, are what its summary is printed from."""
+    output = "counts_out"
 
-    def __init__(self, path, names):
-        self.names, self.per_class = list(names), {}
+    def __init__(self, path, names, n_lines=0, state=None):
+        self.names, self.per_class, self.n_lines, self.state = list(names), {}, n_lines, state
         self.file = open(path, "w") if path is not None else None
         if self.file is not None:
             self.file.write(COUNTS_HEADER + "\n")
@@ -941,6 +792,14 @@ class CountsLog:
             self.per_class.setdefault(self.names[cls] if 0 <= cls < len(self.names) else str(cls), [0, 0])[d] += 1
         if self.file is not None:
             self.file.writelines(row + "\n" for row in counts_rows(frame_no, crossings, self.names))
+
+    def frame(self, pos, label, frame, dets, marks):
+        self.add(pos + 1, marks["crossings"])
+
+    def end(self):                                        # (host only: the state read back)
+        self.close()
+        totals = ops.count_totals(self.state())
+        print_counts(self.n_lines, totals["totals"], self.per_class, totals["events_dropped"])
 
     def close(self):
         if self.file is not None:
@@ -1039,10 +898,12 @@ def print_zones(n_zones, totals):
 
 
 class ZonesLog:
-    """Where the zone events of a sequence go: the ``--zones_out`` file (``path`` None: none)."""
+    """Where the zone events of a sequence go: the ``--zones_out`` file (``path`` None: none).  A sequence report (``_reports``):
+    ``n_zones`` and ``state()``, the zone state, are what its summary is printed from."""
+    output = "zones_out"
 
-    def __init__(self, path, names):
-        self.names = list(names)
+    def __init__(self, path, names, n_zones=0, state=None):
+        self.names, self.n_zones, self.state = list(names), n_zones, state
         self.file = open(path, "w") if path is not None else None
         if self.file is not None:
             self.file.write(ZONES_HEADER + "\n")
@@ -1050,6 +911,13 @@ class ZonesLog:
     def add(self, frame_no, events):
         if self.file is not None:
             self.file.writelines(row + "\n" for row in zones_rows(frame_no, events, self.names))
+
+    def frame(self, pos, label, frame, dets, marks):
+        self.add(pos + 1, marks["zones"]["events"])
+
+    def end(self):                                        # (host only: the state read back)
+        self.close()
+        print_zones(self.n_zones, ops.zone_totals(self.state()))
 
     def close(self):
         if self.file is not None:
@@ -1076,7 +944,9 @@ def reid_rows(frame_no, events, names):
 
 
 class ReidLog:
-    """Where the re-identifications of a sequence go: the ``--reid_out`` file (``path`` None: none), and how many there were."""
+    """Where the re-identifications of a sequence go: the ``--reid_out`` file (``path`` None: none), and how many there were.  A
+    sequence report (``_reports``)."""
+    output = "reid_out"
 
     def __init__(self, path, names):
         self.names, self.total = list(names), 0
@@ -1088,6 +958,14 @@ class ReidLog:
         self.total += len(events)
         if self.file is not None:
             self.file.writelines(row + "\n" for row in reid_rows(frame_no, events, self.names))
+
+    def frame(self, pos, label, frame, dets, marks):
+        self.add(pos + 1, marks["reid"])
+        _print_reid(label, marks["reid"])
+
+    def end(self):
+        self.close()
+        print("re-identified: {}".format(self.total))
 
     def close(self):
         if self.file is not None:
@@ -1437,144 +1315,464 @@ def _print_drawn(dets, width, height):
             print(det)
 
 
-def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, redact=None, draw=True, track=None, tracks_out=None,
-                        frame_no=1, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-                        track_trails=None, heatmap=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, track_reid=None,
-                        reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None,
-                        redact_moving=None, moving_out=None):
-    """(``det_threshold`` / ``track_low``: as ``annotate_images``.)
-    ``redact_moving``: True, a dict of ops.redact_moving_option's keywords or its 12 values -- the moving net (DESIGN §8 "Moving rule"):
-    the frame teaches the plate of the calls before this one and whatever differs from it is hidden; the moving state CONTINUES from
-    the call before (``reset_moving`` empties it, ``reset_plate`` the plate).  ``moving_out``: a ``MovingLog`` that receives the frame's
-    counts.  None: every byte is what it was.
-    annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it.
-    ``redact`` = (classes, mode, size, margin): those classes' boxes are hidden first; ``draw`` False: nothing is drawn.
-    ``track`` = (thr, hold, grow): the frame continues the tracks of the frames before it (``reset_tracks`` starts a sequence);
-    ``tracks_out``: a text file that receives the frame's MOT lines under the number ``frame_no``.  ``track_motion`` = R (with
-    ``track``): the tracks' boxes are first moved with the pixels under them, at most R pixels either way (DESIGN §8 "Motion rule").
-    ``track_scene_cut`` = PCT (with ``track_motion``): every track ends when the frame is a hard cut against the frame before it (DESIGN
-    §8 "Cut rule"); a line ``scene cut: <frame_no>`` is then printed in front of the frame's lines.
-    ``track_trails`` = (N, W) (with ``track``): the path of every id live in the frame is drawn, its last N points, W pixels wide (DESIGN
-    §8 "Trail rule"); the frames before this one are the calls before this one.
-    ``heatmap`` = (classes, A, S): the frame's boxes of those classes heat the map of the calls before this one (``reset_heat`` starts a
-    cold one), which is blended into the frame (DESIGN §8 "Heat rule").
-    ``count`` = (lines, classes, W) (with ``track``): the frame is one more step of the count state the calls before it left (DESIGN §8
-    "Count rule"; ``reset_counts`` starts from zero totals, ``reset_tracks`` ends the ids and keeps them): the lines and their totals are
-    drawn unless ``draw`` is False, and ``counts_out``, a text file, receives the frame's rows ``frame,line,direction,id,cls`` under the
-    number ``frame_no``.
-    ``zone`` = (zones, classes, W, anchor) (with ``track``): the frame is one more step of the zone state the calls before it left (DESIGN
-    §8 "Zone rule"; ``reset_zones`` starts over, ``reset_tracks`` ends the ids and keeps the totals): the zones are drawn unless ``draw``
-    is False, and ``zones_out``, a text file, receives the frame's rows ``frame,zone,kind,id,cls,dwell``.
-    ``remove`` = (classes, S, T, M): the frame teaches the background plate of the calls before this one (``reset_plate`` starts an empty
-    one), and the boxes of those classes are painted out with it (DESIGN §8 "Plate rule").
-    ``track_reid`` = (pct, keep) (with ``track``): the frame continues the appearance memory of the calls before it (DESIGN §8
-    "Re-identify rule"; ``reset_tracks`` empties it): a track that returns carries its old id everywhere, a line ``re-identified:
-    <frame_no> id <pid>`` is printed in front of the frame's lines, and ``reid_out``, a text file, receives the frame's rows
-    ``frame,id,tracker_id,cls,distance,gap``.
-    ``post``: the post-process option (``ops.det_post_option``: soft-NMS / box voting, DESIGN §8 "Post-process rule") -- which boxes the
-    detector reports, in front of everything above; the engine with the option keeps editing states of its own (``reset_tracks(...,
-    post=)``).  None: every byte and line is what it was.
-    ``out_size`` = ("size", W, H) or ("scale", N): the annotated frame is scaled down on the device behind every edit (DESIGN §8 "Scale
-    rule") and the scaled frame, a new (H, W, 3) array, is returned in ``frame``'s place; the dets, the printed lines and every file
-    written stay in the coordinates of ``frame``.  ValueError for a target the rule refuses for this frame.
-    ``redact_shape`` = (shape, feather) (with ``redact``): the boxes hide the ellipses inscribed in them and the replacement fades out
-    over ``feather`` pixels outside the shape (DESIGN §8 "Shape rule"); ("box", 0) and None: every byte is what it was.
-    ``redact_region`` = (regions, mask, mode, size, feather): the static areas are hidden in the frame whatever is detected (DESIGN §8
-    "Region rule"); a mask must have the frame's size.  None: every byte is what it was."""
-    post = None if post is None else ops.det_post_option(post)
-    redact_shape = _redact_shape(redact_shape, redact)
-    redact_region = _redact_region(redact_region)
-    if redact_region is not None and redact_region[1] is not None and redact_region[1].shape != tuple(frame.shape[:2]):
-        raise ValueError("redact_region: the mask is %dx%d, frame %s is %dx%d"
-                         % (redact_region[1].shape[1], redact_region[1].shape[0], frame_no, frame.shape[1], frame.shape[0]))
-    if out_size is not None:
-        scaled_size(out_size, frame_no, frame.shape[1], frame.shape[0])
-    track_reid = _track_reid(track_reid, track)
-    if reid_out is not None and track_reid is None:
-        raise ValueError("reid_out is where the re-identifications are written: it needs track_reid=(pct, keep)")
-    if track_reid is not None and track_lookback is not None:
-        raise ValueError("track_reid=%r together with track_lookback= is not supported" % (track_reid,))
-    count = _count(count, track)
-    if counts_out is not None and count is None:
-        raise ValueError("counts_out is where the crossings are written: it needs count=(lines, classes, width)")
-    zone = _zone(zone, track)
-    if zones_out is not None and zone is None:
-        raise ValueError("zones_out is where the zone events are written: it needs zone=(zones, classes, width, anchor)")
-    if detect_every is not None:
+def _output_needs(name, option, text):
+    """The check of an output against its option; the one-frame form's wording leaves the value out."""
+    def check(v, c):
+        if v[name] is not None and v[option] is None:
+            raise ValueError((name if c.form == "frame" else "%s=%r" % (name, v[name])) + text)
+    return check
+
+
+def _normalised(name, check, *others):
+    """The step that replaces option ``name`` by ``check(its value, the values of the options ``others``)``."""
+    def step(v, c):
+        v[name] = check(v[name], *(v[o] for o in others))
+    return step
+
+
+def _check_motion(v, c):
+    if v["track_motion"] is not None and v["track"] is None:
+        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (v["track_motion"],))
+    if c.form == "draw" and v["track_motion"] is not None:
+        v["track_motion"] = ops.track_motion_radius(v["track_motion"])
+
+
+def _check_thresholds(v, c):
+    v["det_threshold"], v["track_low"] = _det_thresholds(v["det_threshold"], v["track_low"], v["track"])
+
+
+def _check_remove_names(v, c):
+    if v["remove"] is not None and v["remove"][0] != "all":
+        ops.plate_class_list(_names_by_index(c.owner if isinstance(c.owner, dict) else c.owner.class_mapping), v["remove"][0])
+
+
+def _check_moving(v, c):
+    v["redact_moving"] = _redact_moving(v["redact_moving"], v["remove"], c.owner)
+
+
+def _check_reid_delayed(v, c):
+    if v["track_reid"] is not None and c.form == "frame" and v["track_lookback"] is not None:
+        raise ValueError("track_reid=%r together with track_lookback= is not supported" % (v["track_reid"],))
+    if v["track_reid"] is not None and c.form == "list" and (v["track_lookback"] is not None or v["track_backtrack"] is not None):
+        raise ValueError("track_reid=%r together with track_lookback= / track_backtrack= is not supported: the window of a delayed pass "
+                         "holds the tracker's own ids" % (v["track_reid"],))
+
+
+def _check_region_fits(v, c):
+    mask = None if v["redact_region"] is None else v["redact_region"][1]
+    if mask is not None and mask.shape != tuple(c.frame.shape[:2]):
+        raise ValueError("redact_region: the mask is %dx%d, %s %dx%d" % (mask.shape[1], mask.shape[0], "the frame" if c.form == "draw" else
+                                                                          "frame %s is" % (c.label,), c.frame.shape[1], c.frame.shape[0]))
+
+
+def _check_out_fits(v, c):
+    if v["out_size"] is not None:
+        if c.form == "draw":
+            ops.scale_option(v["out_size"], c.frame.shape[:2])
+        else:
+            scaled_size(v["out_size"], c.label, c.frame.shape[1], c.frame.shape[0])
+        v["out_size"] = ops.scale_form(v["out_size"])
+
+
+def _check_one_frame(v, c):
+    if v["detect_every"] is not None:
         raise ValueError("detect_every=%r runs the detector once per pass of several frames: get_annotated_frame detects its one frame and "
-                         "cannot; use annotate_images or annotate_stream" % (detect_every,))
-    if track_backtrack is not None:
-        raise ValueError("track_backtrack=%r delays the output: get_annotated_frame returns its frame at once and cannot; use annotate_images "
-                         "or annotate_stream" % (track_backtrack,))
-    if track_lookback is not None:
-        raise ValueError("track_lookback=%r delays the output: get_annotated_frame returns its frame at once and cannot; use annotate_images "
-                         "or annotate_stream" % (track_lookback,))
-    if track_motion is not None and track is None:
-        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
-    motion = {} if track_motion is None else {"track_motion": track_motion}
-    if _track_scene_cut(track_scene_cut, track, track_motion, None, None) is not None:
-        motion["track_scene_cut"] = track_scene_cut
-    trails = _track_trails(track_trails, track, draw)
-    if trails is not None:
-        motion["track_trails"] = trails
-    if count is not None:
-        motion["count"] = count
-    if zone is not None:
-        motion["zone"] = zone
-    heatmap = _heatmap(heatmap)
-    remove = _remove(remove)
-    if remove is not None:
-        motion["remove"] = remove
-    redact_moving = _redact_moving(redact_moving, remove, training_manager)
-    if redact_moving is not None:
-        motion["redact_moving"] = redact_moving
-    if track_reid is not None:
-        motion["track_reid"] = track_reid
-    if redact_shape is not None:
-        motion["redact_shape"] = redact_shape
-    if redact_region is not None:
-        motion["redact_region"] = redact_region
-    strong, low = _det_thresholds(det_threshold, track_low, track)    # (the pair itself, in front of the engine)
-    eng = _engine(training_manager, detector, 1, post)
-    _det_thresholds(det_threshold, track_low, track, eager=eng is None)      # (a foreign model refuses an L, in front of any work)
+                         "cannot; use annotate_images or annotate_stream" % (v["detect_every"],))
+    for name in ("track_backtrack", "track_lookback"):
+        if v[name] is not None:
+            raise ValueError("%s=%r delays the output: get_annotated_frame returns its frame at once and cannot; use annotate_images "
+                             "or annotate_stream" % (name, v[name]))
+
+
+_check_post = _normalised("post", lambda post: None if post is None else ops.det_post_option(post))
+_check_out_size = _normalised("out_size", lambda out_size: None if out_size is None else ops.scale_form(out_size))
+_check_cut = _normalised("track_scene_cut", lambda cut, track, motion: _track_scene_cut(cut, track, motion, None, None), "track", "track_motion")
+_check_counts_out = _output_needs("counts_out", "count", " is where the crossings are written: it needs count=(lines, classes, width)")
+_check_zones_out = _output_needs("zones_out", "zone", " is where the zone events are written: it needs zone=(zones, classes, width, anchor)")
+_check_reid_out = _output_needs("reid_out", "track_reid", " is where the re-identifications are written: it needs track_reid=(pct, keep)")
+_check_shape, _check_region = _normalised("redact_shape", _redact_shape, "redact"), _normalised("redact_region", _redact_region)
+_check_reid, _check_count, _check_zone = _normalised("track_reid", _track_reid, "track"), _normalised("count", _count, "track"), _normalised("zone", _zone, "track")
+_check_trails = _normalised("track_trails", _track_trails, "track", "draw")
+_check_heatmap, _check_remove = _normalised("heatmap", _heatmap), _normalised("remove", _remove)
+# The engine-independent checks of each form, IN THE ORDER the form has always run them: with two violations the first one is reported,
+# and the three entry points grew different orders.  A list leaves ``detect_every``, ``track_lookback``, ``track_backtrack``,
+# ``track_scene_cut`` and, behind them, ``track_trails`` to ``_tracking_options``, where the engine is known.
+_CHECKS = {
+    "list": (_check_motion, _check_thresholds, _check_post, _check_heatmap, _normalised("heatmap_out", _heatmap_out, "heatmap"), _check_remove,
+             _normalised("plate_out", _plate_out, "remove"), _check_remove_names, _check_moving, _normalised("moving_out", _moving_out, "redact_moving"),
+             _check_count, _check_counts_out, _check_zone, _check_zones_out, _check_reid, _check_reid_out, _check_reid_delayed,
+             _check_out_size, _check_shape, _check_region),
+    "frame": (_check_post, _check_shape, _check_region, _check_region_fits, _check_out_fits, _check_reid, _check_reid_out,
+              _check_reid_delayed, _check_count, _check_counts_out, _check_zone, _check_zones_out, _check_one_frame, _check_motion,
+              _check_cut, _check_trails, _check_heatmap, _check_remove, _check_moving, _check_thresholds),
+    "draw": (_check_shape, _check_region, _check_region_fits, _check_out_fits, _check_reid, _check_trails, _check_heatmap, _check_remove,
+             _check_moving, _check_count, _check_zone, _check_motion, _check_cut),
+}
+OPTION_OUTPUTS = ("tracks_out", "heatmap_out", "counts_out", "zones_out", "plate_out", "reid_out", "moving_out")
+# what a form does not take: an unknown keyword there, as it always was
+_NOT_TAKEN = {"list": (), "frame": ("heatmap_out", "plate_out"),
+              "draw": ("track_lookback", "detect_every", "track_backtrack", "post", "det_threshold", "track_low") + OPTION_OUTPUTS}
+# option -> submit_batch's keyword, for every option that is one, in the order the passes' keywords were always built in
+_PASS_KEYWORDS = {"track": "track", "track_motion": "track_motion", "track_lookback": "track_lookback", "detect_every": "detect_every",
+                  "track_backtrack": "track_backtrack", "track_scene_cut": "track_scene_cut", "track_trails": "track_trails", "heatmap": "heat",
+                  "remove": "remove", "redact_moving": "redact_moving", "count": "count", "zone": "zone", "track_reid": "track_reid",
+                  "out_size": "out_size", "redact_shape": "redact_shape", "redact_region": "redact_region"}
+_PASS_ONLY = ("track_lookback", "detect_every", "track_backtrack", "out_size")      # steps of a pass, not of a frame's editing chain
+
+
+@dataclasses.dataclass(frozen=True)
+class AnnotateOptions:
+    """The options of one annotated sequence, checked and normalised: what ``annotate_images``, ``annotate_stream``,
+    ``get_annotated_frame`` and ``draw_eager`` take as keywords (``checked``), what the command line states (``from_args``), and what
+    they hand on: the keywords of ``submit_batch`` (``pass_keywords``) and of a one-frame edit (``edit_keywords``).  It mirrors
+    ``entry.PassSpec`` on the caller's side: a new option is a field here, its check in ``_CHECKS``, its keyword in ``_PASS_KEYWORDS``
+    and, when it keeps state over a sequence, its report in ``_reports``.  Without an option no pass, key, printed line or output byte
+    is another.
+    ``redact``: (classes, mode, size, margin) as ``redact_from_args`` returns it -- those classes' boxes are hidden in every frame inside
+    its pass, in front of the drawing step and of whichever encoder writes the frame; None: nothing is.  ``draw`` False: no boxes, no labels.
+    ``track``: (thr, hold, grow) as ``track_from_args`` returns it -- the list is ONE sequence in list order: the tracker's state is reset
+    at the start, every tracked detection is labelled ``cls#id`` and lost tracks are held (and redacted) for ``hold`` frames; None: no
+    tracking.  ``tracks_out``: a text file that receives the MOT lines, frame i of the list under the number i + 1.
+    ``track_motion``: the search radius as ``track_motion_from_args`` returns it (with ``track``) -- every track's box is moved with the
+    pixels under it from frame to frame, so a held box follows its object; None: held boxes stand still.
+    ``track_lookback``: the frames as ``track_lookback_from_args`` returns them (with ``track``; TRACK_LOOKBACK_AUTO: as many as a pass
+    holds, at most 8) -- every new track is followed BACK over that many frames and hidden there too (DESIGN §8 "Look-back rule").  Every
+    group then goes through a full pass of B frames, a pass returns the frames of the pass before it and a flush ends the list: each
+    frame is written and printed when it is emitted, the same lines in the same order.  The eager path refuses it.
+    ``detect_every``: K as ``detect_every_from_args`` returns it (with ``track`` and ``track_motion``, not with ``track_lookback``) -- the
+    detector runs on every K-th frame only and a pass takes B * K frames; on the frames between, every track's box follows the pixels under
+    it (DESIGN §8 "Interval rule"), is drawn, redacted and written to ``tracks_out`` with the prob of its last match.  Nothing is matched,
+    aged or born between two detected frames: ``hold`` counts detected frames.  The K-th frames are counted per GROUP, not over the list:
+    a group is a run of at most B * K consecutive frames of one geometry, it is cut where the geometry changes, and its frames 0, K,
+    2K, ... are the detected ones (a group whose key frames fill under half a pass goes through one-image passes of K frames, the same
+    key frames).  With frames of one size, a video, every group but the last is full and that is every K-th frame of the list; in a list
+    of mixed sizes a detected frame follows every change of geometry.  The eager path refuses it.
+    ``track_backtrack``: the frames as ``track_backtrack_from_args`` returns them (with ``detect_every``, not with ``track_lookback``;
+    TRACK_BACKTRACK_AUTO: as many as a pass of B * K frames holds, at most 16; at least K - 1) -- at every detected frame every track is
+    followed BACK through the frames in front of it (DESIGN §8 "Back-track rule"): a continued track as far as the detected frame before,
+    a new one over that many frames, and the boxes found are hidden there too, so a frame between two detections is covered from both
+    sides.  Every group of at most B * K frames then goes through one full (padded) pass, a pass returns the frames of the pass before it
+    and a flush follows a change of geometry and the end of the list, as with ``track_lookback``.  The eager path refuses it.
+    ``track_scene_cut``: the percentage as ``track_scene_cut_from_args`` returns it (with ``track`` and ``track_motion``, with or without
+    ``detect_every``; not with ``track_lookback`` or ``track_backtrack``, whose backward chains would have to stop at a cut) -- a frame
+    whose 4 x 4-region luma histogram differs from the frame before by that share of the largest distance there is, is a hard cut (DESIGN
+    §8 "Cut rule"): every track ends in front of it, so no id is inherited by the new scene and no held box of the old scene is redacted
+    in it; between two detected frames nothing is shown behind a cut until the next detected frame.  A line ``scene cut: <path>`` is
+    printed in front of that frame's lines.  A fade or a dissolve is not detected.  None: every byte and line is what it was.
+    ``track_trails``: (N, W) as ``track_trails_from_args`` returns it (with ``track``, in every form above; not with ``draw`` False) -- the
+    path of every id is kept on the device and each frame shows the last N points of the ids live in it as a line W pixels wide in the
+    colour of the id (DESIGN §8 "Trail rule"), over the redaction and under the boxes; a delayed pass draws them in the order its frames
+    are emitted.  The printed lines and ``tracks_out`` are unchanged.  None: every byte and line is what it was.
+    ``heatmap``: (classes, A, S) as ``heatmap_from_args`` returns it (with every option above, ``draw`` False included) -- a map on the
+    device that starts cold with the list gains 256 per box of those classes in every frame (every detection; with ``track`` the live
+    tracked rows, in a delayed pass the emitted frames'), loses ceil(v / 2^S) per frame, and is blended into each frame at weight A for
+    the hottest pixel, over the redaction and under the trails, boxes and labels (DESIGN §8 "Heat rule").  ``heatmap_out``: a path ending
+    in .png that receives the map at the end of the list, 8-bit grey, one file per frame size met (``<stem>_<w>x<h>.png`` for several).
+    The printed lines and ``tracks_out`` are unchanged.  None: every byte and line is what it was.
+    ``count=(lines, classes, W)`` (``--count_line X1,Y1,X2,Y2``, repeatable up to 8 times, with ``--track`` in any of the forms above;
+    ``--count_classes``, ``--count_width``) counts the tracks whose box centre crosses a line, once per id, line and direction
+    (ops.count_update / ops.count_draw_u8, csrc/count.hip; DESIGN §8 "Count rule"): each frame shows the lines and a label ``L{l} +{pos}
+    -{neg}`` per line over the redaction, heat map and trails and under the boxes, ``counts_out=PATH`` (``--counts_out``) receives a CSV row
+    ``frame,line,direction,id,cls`` per crossing, and at the end one line per counting line and the totals per class are printed.  A list
+    starts from zero totals; ``get_annotated_frame(count=, counts_out=)`` and the eager path take the option as one-frame calls that continue
+    the state (``reset_counts`` zeroes it).  On the command line a value that begins with a minus sign needs the ``=`` form:
+    ``--count_line=-5,0,-5,100``.
+    ``zone=(zones, classes, W, anchor)`` (``--zone X1,Y1,X2,Y2,X3,Y3[,...]``, repeatable up to 8 times, with ``--track`` in any of the forms
+    above; ``--zone_classes``, ``--zone_width``, ``--zone_anchor centre|bottom``) tests every track's box centre, or the middle of its bottom
+    edge, against polygon zones with an exact even-odd rule (ops.zone_update / ops.zone_draw_u8, csrc/zone.hip; DESIGN §8 "Zone rule"): each
+    frame shows the occupied zones tinted, every zone's outline and a label ``Z{z} {occupancy}/{visitors}`` behind the heat map and under
+    every line, ``zones_out=PATH`` (``--zones_out``) receives a CSV row ``frame,zone,kind,id,cls,dwell`` per event, kind enter, exit or lost,
+    and at the end one line per zone is printed: visitors, peak, stays and the mean dwell of the completed stays.  A list starts from an
+    empty state; ``get_annotated_frame(zone=, zones_out=)`` and the eager path take the option as one-frame calls that continue the state
+    (``reset_zones`` starts over).  ``--no_draw`` still counts.  A value that begins with a minus sign needs the ``=`` form: ``--zone=-5,0,9,0,9,9``.
+    ``remove=(classes, S, T, M)`` (``--remove CLASSES``, class names of the active mapping or ``all``; ``--remove_settle S``, 1..255;
+    ``--remove_tol T``, 0..255; ``--remove_margin M``, 0..64; the defaults 8, 10 and 8 are PROVISIONAL: nobody has measured them on real
+    footage) paints the objects of those classes out of fixed-camera footage (ops.plate_update / ops.plate_fill_u8, csrc/plate.hip; DESIGN §8
+    "Plate rule"): a background plate on the device learns every pixel that no box of ANY class touches -- held and back-filled tracked rows
+    too -- and that stays within T of the value its run began with for S frames, and the boxes of the classes, grown by M, are filled with
+    it.  Where the plate is not known yet the redaction shows, if ``--redact`` covers the classes, else black.  An object that stands still
+    and is never detected becomes background after S frames: that is the rule's limit.  A ``--track_scene_cut`` cut empties the plate.  A
+    list starts from an empty plate; ``get_annotated_frame(remove=)`` and the eager path continue it as one-frame calls (``reset_plate``
+    empties it).  ``plate_out=PATH.png`` (``--plate_out``) writes the plate at the end as an RGB PNG with unknown pixels black, one per
+    frame size met, named as ``--heatmap_out`` names its files, and one line per size is printed: ``plate 1242x375: 128 frames, 97.3 %
+    known`` (a size met in both channel orders has two plates: a line and a file for each).  With every other option, ``--no_draw`` included, with and without ``--track``.
+    ``track_reid=(pct, keep)`` (``--track_reid [PCT]``, 1..100, bare: 25; ``--reid_keep N``, 1..4095 frames, default 250; both defaults are
+    PROVISIONAL: nobody has measured them on real footage; with ``--track`` in every form but ``--track_lookback`` / ``--track_backtrack``)
+    gives an object that was hidden for longer than ``--track_hold`` frames its old id back (ops.track_reid_update, csrc/track_reid.hip;
+    DESIGN §8 "Re-identify rule"): every live tracked row gets a colour signature, and a new track whose signature lies within PCT percent
+    of that of an id the tracker gave up at most N frames ago carries that id -- in the labels, ``--tracks_out``, the printed ``track_id``,
+    the trails, the count lines (which then count it once) and the zones.  A line ``re-identified: <path> id <pid>`` is printed in front
+    of that frame's lines and ``re-identified: N`` at the end; ``reid_out=PATH`` (``--reid_out``) receives a CSV row
+    ``frame,id,tracker_id,cls,distance,gap`` per event.  A list starts from an empty memory; ``get_annotated_frame(track_reid=)`` and the
+    eager path continue it as one-frame calls (``reset_tracks`` empties it).  A ``--track_scene_cut`` cut empties it too.
+    ``post``: the post-process option as ``args_util.post_from_args`` returns it (``ops.det_post_option``: mode, nms_thresh, sigma,
+    min_score, vote_iou) -- soft-NMS and box voting inside the captured passes (DESIGN §8 "Post-process rule"), on the eager path through
+    ``ops.detections_post``: which boxes every frame reports, with decayed scores in the soft modes; everything above then works on those
+    boxes.  The passes belong to an engine of their own.  None: no pass, engine key, printed line or output byte changes.
+    ``out_size``: ("size", W, H) or ("scale", N) as ``out_size_from_args`` returns it -- every frame is scaled DOWN on the device as the
+    last step of its pass, behind every edit and in front of whichever encoder writes it (DESIGN §8 "Scale rule": the exact area mean, in
+    integers; labels shrink with the picture): the device encoders encode, and the read-back copies, the smaller frame; the host encoders
+    simply receive it.  ("scale", N) applies per frame size in a list of mixed sizes; ("size", W, H) is refused with the name of the
+    first frame that is smaller than it (or more than 16 times its size along a side).  The printed lines, ``tracks_out``, ``counts_out``
+    and ``zones_out`` stay in SOURCE coordinates.  None: no pass, key, printed line or output byte changes.
+    ``redact_shape``: (shape, feather) as ``redact_shape_from_args`` returns it (with ``redact``, and with every option above) -- every
+    box the redaction hides, held and back-filled ones too, hides the ellipse inscribed in the box grown by the margin ("ellipse"), and
+    the replacement fades into the scene over ``feather`` pixels OUTSIDE the shape, so nothing the hard shape hides shows (DESIGN §8
+    "Shape rule", ops.redact_shaped_u8).  The plate of ``remove``, the tracker, the heat map and the drawn boxes keep their rectangles.
+    None and ("box", 0): no pass, key, printed line or output byte changes.
+    ``det_threshold``: T, a float in 0..1 (``--det_threshold``; None: DET_THRESHOLD = 0.0, the reference script's): the score under which
+    a detection is not reported; with or without ``track``.  ``track_low``: L < T (``--track_low``, with ``track``): the weak rule
+    (DESIGN §8 "Weak rule", the ``strong=`` form of the tracker call): the passes emit rows down to L (submit_batch's det_threshold = L,
+    track_strong = T), a row with a score in [L, T) may only continue a track that no row of T or more continued, and every other such
+    row is dropped -- so an object whose score dips stays covered by the detector's own box, under its id, and nothing new is reported
+    under T.  "num dets", the printed lines and ``tracks_out`` show the kept rows.  Refused by name without ``track``, for L >= T and
+    outside 0..1, and on the eager path (a foreign model).  None and None: no pass, key, printed line or output byte changes.
+    ``redact_region``: (regions, mask, mode, size, feather) as ``redact_region_from_args`` returns it (with every option above, with and
+    without ``redact`` and ``track``) -- static areas, polygons in source-frame pixels and a painted mask whose bytes >= 128 hide, are
+    hidden in EVERY frame whatever the detector says (DESIGN §8 "Region rule"): what replaces them comes from the untouched frame, they
+    are blended in behind the plate fill of ``remove`` and under the heat map and everything drawn, and the edge fades outwards over
+    ``feather`` pixels.  Polygons apply to every frame size; a mask is held to one, and a frame it does not fit is refused by name.
+    ``plate_out`` then shows every pixel of an area black.  A line ``redact regions 1242x375: 2 regions + mask, 12.3 % of the frame
+    hidden`` is printed per frame size at the end; every other printed line and file is unchanged.  None: no pass, key, printed line or
+    output byte changes.
+    ``redact_moving``: True, a dict of ops.redact_moving_option's keywords or its 12 values, as ``redact_moving_from_args`` returns it
+    (with every option above, with and without ``remove`` and ``track``) -- the moving net (DESIGN §8 "Moving rule"): on fixed-camera
+    footage whatever differs from the plate is hidden in every frame, detected or not.  The list starts from an EMPTY moving state and
+    an empty plate; without ``remove`` the plate is learned all the same, with the option's (S, T, M), and nothing is painted out; with
+    it the three are ``remove``'s, and one stated here that differs is refused by name.  The defaults 24, 8, 4 and 8 are PROVISIONAL.
+    Until a pixel's background is known it is shown (unknown "hide" blanks it instead): the first S frames are not protected by the
+    net under the default.  Delayed passes run the net on the frames they emit.  ``moving_out``: a path; a CSV ``frame,cells,covered``
+    is written there.  A line ``moving net 1242x375: 128 frames, mean 3.2 % hidden, peak 17.0 %`` is printed per frame size at the
+    end.  None: no pass, key, printed line or output byte changes.
+    The outputs: ``tracks_out`` an open text file, the others paths (``heatmap_out`` / ``plate_out``: ending in .png).
+    One frame at a time (``get_annotated_frame``, ``draw_eager``) every state CONTINUES from the call before: ``reset_tracks`` (ids,
+    trails, the re-identify memory), ``reset_heat``, ``reset_counts``, ``reset_zones``, ``reset_plate`` and ``reset_moving`` start a
+    new sequence; ``counts_out`` / ``zones_out`` / ``reid_out`` are then open text files that receive the frame's rows without a header,
+    ``moving_out`` a ``MovingLog``; a mask of ``redact_region`` must have the frame's size."""
+    redact: object = None
+    draw: bool = True
+    track: object = None
+    track_motion: object = None
+    track_lookback: object = None
+    detect_every: object = None
+    track_backtrack: object = None
+    track_scene_cut: object = None
+    track_trails: object = None
+    heatmap: object = None
+    count: object = None
+    zone: object = None
+    remove: object = None
+    track_reid: object = None
+    post: object = None
+    out_size: object = None
+    redact_shape: object = None
+    det_threshold: object = None                          # checked: T, a float (DET_THRESHOLD when not stated)
+    track_low: object = None
+    redact_region: object = None
+    redact_moving: object = None
+    tracks_out: object = None
+    heatmap_out: object = None
+    counts_out: object = None
+    zones_out: object = None
+    plate_out: object = None
+    reid_out: object = None
+    moving_out: object = None
+
+    @classmethod
+    def checked(cls, owner, form="list", frame=None, label=None, **stated):
+        """The keywords of an entry point -> the value, every engine-independent check run once (``_CHECKS``).  ``owner``: the class
+        mapping, or the training manager that holds it (read only by the options that name classes).  ``form``: "list"
+        (``annotate_images`` / ``annotate_stream``), "frame" (``get_annotated_frame``, which refuses ``detect_every``, ``track_lookback``
+        and ``track_backtrack``) or "draw" (``draw_eager``); the last two check a mask and an ``out_size`` against ``frame``, the frame
+        ``label``.  TypeError for a keyword the form does not take, ValueError with the reason for everything else."""
+        values = dict(vars(cls(**stated)))
+        for name in _NOT_TAKEN[form]:
+            if name in stated:
+                raise TypeError("got an unexpected keyword argument %r" % name)
+        context = _Context(owner, form, frame, label)
+        for check in _CHECKS[form]:
+            check(values, context)
+        return cls(**values)
+
+    @classmethod
+    def from_args(cls, args, class_mapping, stack):
+        """(host only) What the command line states -> the value, through the ``*_from_args`` functions (each ValueError names the
+        flag); ``tracks_out`` is opened on ``stack``.  The entry point that takes the value's fields checks them against each other."""
+        v = dict(redact=redact_from_args(args, class_mapping), draw=not args.no_draw, track=track_from_args(args))
+        v["track_motion"] = track_motion_from_args(args)
+        if v["track"] is not None and args.tracks_out:
+            v["tracks_out"] = stack.enter_context(open(args.tracks_out, "w"))
+        v["track_lookback"] = track_lookback_from_args(args)
+        v["detect_every"] = detect_every_from_args(args)
+        v["track_backtrack"] = track_backtrack_from_args(args)
+        v["track_scene_cut"] = track_scene_cut_from_args(args)
+        v["track_trails"] = track_trails_from_args(args)
+        v["heatmap"], v["heatmap_out"] = heatmap_from_args(args, class_mapping)
+        v["remove"], v["plate_out"] = remove_from_args(args, class_mapping)
+        v["redact_moving"], v["moving_out"] = redact_moving_from_args(args, class_mapping, v["remove"])
+        v["count"], v["counts_out"] = count_from_args(args, class_mapping)
+        v["track_reid"], v["reid_out"] = track_reid_from_args(args)
+        v["zone"], v["zones_out"] = zone_from_args(args, class_mapping)
+        from .args_util import post_from_args
+        v["post"] = post_from_args(args)                  # (dependent options are refused by name)
+        v["out_size"] = out_size_from_args(args)
+        v["redact_shape"] = redact_shape_from_args(args)
+        v["redact_region"] = redact_region_from_args(args)
+        return cls(**v, **det_thresholds_from_args(args))
+
+    @property
+    def uploaded_threshold(self):
+        """The score threshold the passes upload: under the weak rule the LOW one (the tracker is told ``det_threshold``)."""
+        return self.det_threshold if self.track_low is None else self.track_low
+
+    def pass_keywords(self, sink_keywords=()):
+        """The keywords of ``submit_batch`` behind ``batch``, for a sink's encoder keywords.  An option that is not stated is absent,
+        ``redact`` and ``draw`` too unless one is: the pass, and its key, are then the ones without the argument."""
+        kw = dict(sink_keywords, annotate=True)
+        kw.update((keyword, getattr(self, name)) for name, keyword in _PASS_KEYWORDS.items() if getattr(self, name) is not None)
+        if self.track_low is not None:                    # the weak rule: the passes emit rows down to ``track_low``
+            kw["track_strong"] = self.det_threshold
+        if self.redact is not None or not self.draw:
+            kw.update(redact=self.redact, draw=self.draw)
+        return kw
+
+    def edit_keywords(self):
+        """The fields of the ``entry.PassSpec`` of a one-frame edit (``frame_edit.EditChain``): ``pass_keywords`` without the steps that
+        belong to a pass."""
+        kw = {k: v for k, v in self.pass_keywords().items() if k not in _PASS_ONLY and k != "track_strong"}
+        if self.track_motion is not None:
+            kw["track_motion"] = ops.track_motion_radius(self.track_motion)
+        redact = self.redact if self.redact is None else (self.redact[0] if self.redact[0] == "all" else tuple(self.redact[0]),) + tuple(self.redact[1:])
+        return dict(kw, redact=redact, draw=self.draw)
+
+
+_Context = collections.namedtuple("_Context", "owner form frame label")
+
+
+class TracksLog:
+    """A sequence report (``_reports``): the MOT lines of a tracked sequence go to ``file`` (None: none)."""
+    output = None
+
+    def __init__(self, file, class_mapping):
+        self.file, self.class_mapping = file, class_mapping
+
+    def frame(self, pos, label, frame, dets, marks):
+        _write_tracks(self.file, pos + 1, dets, self.class_mapping)
+
+    def end(self):
+        pass
+
+    close = end
+
+
+class _EndReport:
+    """A sequence report (``_reports``) that only speaks at the end of the list: ``end`` is the function given."""
+    output = None
+
+    def __init__(self, end):
+        self.end = end
+
+    def frame(self, pos, label, frame, dets, marks):
+        pass
+
+    def close(self):
+        pass
+
+
+def _reports(o, training_manager, detector, eng, region_sizes):
+    """The reports of a sequence with the options ``o``: one object per active feature that keeps state over the sequence, yielded
+    behind the reset of that state, with ``frame(pos, label, frame, dets, marks)`` for every frame a pass returns, ``end()`` for the
+    summary and ``close()``; ``output`` names the option under which the eager path's frames find it.  THE ORDER IS BEHAVIOUR: it is
+    the order of a frame's printed lines and of the summaries at the end of the list.  (The resets run in it too; they empty
+    independent states on one stream, so their order does not show.)  ``region_sizes``: the set of (h, w) the sink's check fills."""
+    mapping = training_manager.class_mapping
+    states = lambda: eng.edit_states if eng is not None else _eager_states(mapping)
+    reset = lambda of: of(training_manager, detector, 1 if eng is None else eng.in_flight, o.post)
+    if o.track is not None:                               # a new sequence; its frames are submitted in input order, as every list's are
+        reset(reset_tracks)
+        yield TracksLog(o.tracks_out, mapping)
+    if o.count is not None:                               # zero totals for the list
+        reset(reset_counts)
+        yield CountsLog(o.counts_out, _names_by_index(mapping), len(o.count[0]), lambda: _count_state(training_manager, eng))
+    if o.zone is not None:                                # an empty state for the list
+        reset(reset_zones)
+        yield ZonesLog(o.zones_out, _names_by_index(mapping), len(o.zone[0]), lambda: _zone_state(training_manager, eng))
+    if o.track_reid is not None:                          # (an empty memory for the list: reset_tracks above emptied it)
+        yield ReidLog(o.reid_out, _names_by_index(mapping))
+    if o.heatmap is not None:                             # a cold map for the list; its t values as grey PNG files at the end
+        reset(reset_heat)
+        if o.heatmap_out is not None:
+            yield _EndReport(lambda: write_heatmaps(o.heatmap_out, _heat_states(training_manager, eng)))
+    if o.remove is not None or o.redact_moving is not None:      # an empty plate for the list, under the moving net too
+        reset(reset_plate)
+    if o.remove is not None:                              # the plate as an RGB PNG at the end, unknown pixels black
+
+        def plates():
+            summaries = plate_summaries(_plate_states(training_manager, eng))
+            print_plates(summaries)
+            if o.plate_out is not None:
+                if o.redact_region is not None:           # the plate picture never shows a static area in clear
+                    summaries = {key: (n, known, blacken_plate(plate, ops.redact_region_weights(states().region_plane(key[0], key[1], o.redact_region))))
+                                 for key, (n, known, plate) in summaries.items()}
+                write_plates(o.plate_out, summaries)
+        yield _EndReport(plates)
+    if o.redact_moving is not None:                       # an empty moving state for the list
+        reset(reset_moving)
+        yield MovingLog(o.moving_out)
+    if o.redact_region is not None:                       # (the planes' headers read back)
+
+        def regions():
+            for h, w in sorted(region_sizes):
+                print(region_line(w, h, o.redact_region, ops.redact_region_stats(states().region_plane(h, w, o.redact_region))))
+        yield _EndReport(regions)
+
+
+def get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, frame_no=1, **options):
+    """annotate_video.py:27-44: detect on ``img`` (an InMemoryImage of ``frame``), draw into ``frame`` in place, return it -- with
+    ``out_size`` the scaled frame, a new (H, W, 3) array, in its place.  ``options``: the options of ``AnnotateOptions`` in their
+    one-frame form; the frame's rows go to the outputs under the number ``frame_no``, which also stands where a list prints the path
+    (``scene cut: <frame_no>``, ``re-identified: <frame_no> id <pid>``)."""
+    return _annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, frame_no,
+                            AnnotateOptions.checked(training_manager, "frame", frame, frame_no, **options))
+
+
+def _annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, frame_no, o):
+    """``get_annotated_frame`` with its options checked: ``o``, an ``AnnotateOptions``."""
+    eng = _engine(training_manager, detector, 1, o.post)
+    _det_thresholds(o.det_threshold, o.track_low, o.track, eager=eng is None)      # (a foreign model refuses an L, in front of any work)
     resized_imgs, resized_ratios = resize_imgs([img], min_size=resize_min, max_size=resize_max)
     info = {}
-    if low is not None:
-        motion["track_strong"] = strong
     if eng is not None:
         pixels = eng.host_pixels(resized_imgs[0])
-        num_rois, dets, out, *more = eng.collect_batch(eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], strong if low is None else low,
-                                                                        [pixels],
-                                                                        batch=1, annotate=True, redact=redact, draw=draw,
-                                                                        **({} if track is None else {"track": track}), **motion,
-                                                                        **({} if heatmap is None else {"heat": heatmap}),
-                                                                        **({} if out_size is None else {"out_size": out_size})))[0]
+        ticket = eng.submit_batch([resized_imgs[0]], [resized_ratios[0]], o.uploaded_threshold, [pixels], batch=1,
+                                  **dict(o.pass_keywords(), redact=o.redact, draw=o.draw))
+        num_rois, dets, out, *more = eng.collect_batch(ticket)[0]
         info = more[0] if more else info                          # (a ``track_scene_cut`` pass: the frame's marks behind its payload)
         if info.get("scene_cut"):
             print("scene cut: {}".format(frame_no))
         _print_reid(frame_no, info.get("reid", ()))
         print("num rois: {}".format(num_rois))
-        if out_size is None:
+        if o.out_size is None:
             frame[...] = out
         else:
             frame = out
     else:
-        dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=strong, post=post)
-        frame = draw_eager(frame, dets, training_manager.class_mapping, redact, draw, track, info=info, heatmap=heatmap, out_size=out_size,
-                           **motion)
+        dets = voc_dets.get_dets(training_manager, detector, resized_imgs[0], resized_ratios[0], stride=STRIDE, det_threshold=o.det_threshold,
+                                 post=o.post)
+        frame = _edit_eager(frame, dets, training_manager.class_mapping, o, info)
         if info.get("scene_cut"):
             print("scene cut: {}".format(frame_no))
         _print_reid(frame_no, info.get("reid", ()))
-    if track is not None:
-        _write_tracks(tracks_out, frame_no, dets, training_manager.class_mapping)
-    if track_reid is not None:
-        _write_reid(reid_out, frame_no, info["reid"], training_manager.class_mapping)
-    if count is not None:
-        _write_counts(counts_out, frame_no, info["crossings"], training_manager.class_mapping)
-    if zone is not None:
-        _write_zones(zones_out, frame_no, info["zones"]["events"], training_manager.class_mapping)
-    if redact_moving is not None and moving_out is not None:
-        moving_out.add(frame_no, img.height, img.width, info["moving"])
+    if o.track is not None:
+        _write_tracks(o.tracks_out, frame_no, dets, training_manager.class_mapping)
+    if o.track_reid is not None:
+        _write_reid(o.reid_out, frame_no, info["reid"], training_manager.class_mapping)
+    if o.count is not None:
+        _write_counts(o.counts_out, frame_no, info["crossings"], training_manager.class_mapping)
+    if o.zone is not None:
+        _write_zones(o.zones_out, frame_no, info["zones"]["events"], training_manager.class_mapping)
+    if o.redact_moving is not None and o.moving_out is not None:
+        o.moving_out.add(frame_no, img.height, img.width, info["moving"])
     _print_drawn(dets, img.width, img.height)
     return frame
 
@@ -1771,21 +1969,18 @@ def _encoder_options(png_encoder, png_compress, frame_format, jpeg_encoder, jpeg
     return kwargs, on_device, jpg, write_host, encode
 
 
-def _tracking_options(eng, track, track_motion, track_lookback, detect_every, track_backtrack, track_scene_cut=None):
-    """The tracking arguments of ``annotate_images`` checked against the engine (None: the eager path) -> (their keywords of submit_batch,
-    the K of a ``detect_every`` pass or None, do the passes return the frames of the pass before them?, the look-back of a
-    ``track_backtrack`` pass or None)."""
+def _tracking_options(eng, o):
+    """The tracking options of a list, ``o``'s, checked against the engine (None: the eager path) -> (``o`` with them as the passes
+    take them: the K of a ``detect_every`` pass, the look-back of a ``track_lookback`` / ``track_backtrack`` pass, ...; do the passes
+    return the frames of the pass before them?)."""
     B = None if eng is None else eng.batch
-    every = _detect_every(detect_every, track, track_motion, track_lookback, eng, B)
-    lookback = _lookback_frames(track_lookback, track, eng, B)
-    backtrack = _backtrack_frames(track_backtrack, every, track_lookback, eng, B)
-    cut = _track_scene_cut(track_scene_cut, track, track_motion, track_lookback, track_backtrack)
-    kwargs = {} if track is None else {"track": track}
-    for name, value in (("track_motion", track_motion), ("track_lookback", lookback), ("detect_every", every), ("track_backtrack", backtrack),
-                        ("track_scene_cut", cut)):
-        if value is not None:
-            kwargs[name] = value
-    return kwargs, every, lookback is not None or backtrack is not None, backtrack
+    every = _detect_every(o.detect_every, o.track, o.track_motion, o.track_lookback, eng, B)
+    lookback = _lookback_frames(o.track_lookback, o.track, eng, B)
+    backtrack = _backtrack_frames(o.track_backtrack, every, o.track_lookback, eng, B)
+    cut = _track_scene_cut(o.track_scene_cut, o.track, o.track_motion, o.track_lookback, o.track_backtrack)
+    trails = _track_trails(o.track_trails, o.track, o.draw)
+    return (dataclasses.replace(o, detect_every=every, track_lookback=lookback, track_backtrack=backtrack, track_scene_cut=cut, track_trails=trails),
+            lookback is not None or backtrack is not None)
 
 
 class _Sink:
@@ -1961,9 +2156,9 @@ def _run_passes(eng, loaded, emit, pass_kwargs, every, delayed, backtrack, det_t
             ticket.slot.busy = False
 
 
-def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max, **kwargs):
-    """The eager path (foreign models): the reference's loop, one (label, frame) of ``frames`` at a time through ``get_annotated_frame``
-    (``kwargs``: its arguments behind the sizes); a stream's frame is converted on the device."""
+def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max, o):
+    """The eager path (foreign models): the reference's loop, one (label, frame) of ``frames`` at a time through ``get_annotated_frame``'s
+    work (``o``: the checked options, their outputs the sequence's reports); a stream's frame is converted on the device."""
     for pos, (label, src) in enumerate(frames):
         sink.check(label, src)
         print("processing {}".format(label))
@@ -1972,235 +2167,97 @@ def _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
         else:
             frame = np.ascontiguousarray(src.raw)
         img = shapes.InMemoryImage(data=frame, width=frame.shape[1], height=frame.shape[0])
-        sink.emit_eager(pos, get_annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, frame_no=pos + 1, **kwargs))
+        sink.emit_eager(pos, _annotated_frame(training_manager, detector, frame, img, resize_min, resize_max, pos + 1, o))
 
 
-def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, redact=None, draw=True, track=None,
-              tracks_out=None, track_motion=None, track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None,
-              track_trails=None, heatmap=None, heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None,
-              plate_out=None, track_reid=None, reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None,
-              track_low=None, redact_region=None, redact_moving=None, moving_out=None):
+def _sized_check(sink, o, region_sizes):
+    """``sink.check`` with the options' own checks of a frame's size in front of it, on both paths: a frame the ``out_size`` target or
+    the ``redact_region`` mask does not fit is refused by name.  ``region_sizes`` receives the (h, w) of the frames met."""
+    check, mask = sink.check, None if o.redact_region is None else o.redact_region[1]
+
+    def sized(label, frame):
+        if o.out_size is not None:
+            scaled_size(o.out_size, label, frame.width, frame.height)
+        if mask is not None and mask.shape != (frame.height, frame.width):
+            raise ValueError("redact_region: the mask is %dx%d, %s is %dx%d: a mask is held to one frame size"
+                             % (mask.shape[1], mask.shape[0], label, frame.width, frame.height))
+        region_sizes.add((frame.height, frame.width))
+        check(label, frame)
+    return sized
+
+
+def _annotate(training_manager, detector, frames, loaded_from, make_sink, resize_min, resize_max, options=None, **stated):
     """What ``annotate_images`` and ``annotate_stream`` share.  ``frames``: the (label, frame) iterator the eager path reads;
     ``loaded_from(prepare, ahead)``: the read-ahead generator of the captured path (``_loaded_stream`` / ``_loaded_files``);
-    ``make_sink()``: the ``_Sink``."""
-    if track_motion is not None and track is None:
-        raise ValueError("track_motion=%r moves the boxes of the tracker: it needs track=(thr, hold, grow)" % (track_motion,))
-    motion = {} if track_motion is None else {"track_motion": track_motion}
-    strong, low = _det_thresholds(det_threshold, track_low, track)    # (refused here, in front of any capture)
-    post = None if post is None else ops.det_post_option(post)        # (refused here, in front of any capture)
-    if post is not None:
-        motion["post"] = post
-    heatmap = _heatmap(heatmap)
-    heatmap_out = _heatmap_out(heatmap_out, heatmap)
-    remove = _remove(remove)
-    plate_out = _plate_out(plate_out, remove)
-    if remove is not None and remove[0] != "all":         # (unknown names are refused here, in front of any capture)
-        ops.plate_class_list(_names_by_index(training_manager.class_mapping), remove[0])
-    redact_moving = _redact_moving(redact_moving, remove, training_manager)      # (refused here, in front of any capture)
-    moving_out = _moving_out(moving_out, redact_moving)
-    count = _count(count, track)
-    if counts_out is not None and count is None:
-        raise ValueError("counts_out=%r is where the crossings are written: it needs count=(lines, classes, width)" % (counts_out,))
-    zone = _zone(zone, track)
-    if zones_out is not None and zone is None:
-        raise ValueError("zones_out=%r is where the zone events are written: it needs zone=(zones, classes, width, anchor)" % (zones_out,))
-    track_reid = _track_reid(track_reid, track)
-    if reid_out is not None and track_reid is None:
-        raise ValueError("reid_out=%r is where the re-identifications are written: it needs track_reid=(pct, keep)" % (reid_out,))
-    if track_reid is not None and (track_lookback is not None or track_backtrack is not None):
-        raise ValueError("track_reid=%r together with track_lookback= / track_backtrack= is not supported: the window of a delayed pass "
-                         "holds the tracker's own ids" % (track_reid,))
-    out_size = None if out_size is None else ops.scale_form(out_size)      # (refused here, in front of any capture)
-    if out_size is not None:
-        motion["out_size"] = out_size
-    redact_shape = _redact_shape(redact_shape, redact)    # (refused here, in front of any capture)
-    if redact_shape is not None:
-        motion["redact_shape"] = redact_shape
-    redact_region = _redact_region(redact_region)         # (refused here, in front of any capture)
-    if redact_region is not None:
-        motion["redact_region"] = redact_region
-    counts_log = zones_log = reid_log = moving_log = None
-    sink = make_sink()
-    region_sizes = set()                                  # the (h, w) of the frames met: a line per size at the end
-    if redact_region is not None:                         # a frame the mask does not fit is refused by name, on both paths
-        region_check, region_mask = sink.check, redact_region[1]
-
-        def check_region(label, frame):
-            if region_mask is not None and region_mask.shape != (frame.height, frame.width):
-                raise ValueError("redact_region: the mask is %dx%d, %s is %dx%d: a mask is held to one frame size"
-                                 % (region_mask.shape[1], region_mask.shape[0], label, frame.width, frame.height))
-            region_sizes.add((frame.height, frame.width))
-            region_check(label, frame)
-        sink.check = check_region
-    if out_size is not None:                              # a frame the target does not fit is refused by name, on both paths
-        sink_check = sink.check
-
-        def check(label, frame):
-            scaled_size(out_size, label, frame.width, frame.height)
-            sink_check(label, frame)
-        sink.check = check
+    ``make_sink()``: the ``_Sink``; ``options``: the checked ``AnnotateOptions`` (None: ``stated``, its keywords, checked here -- in
+    front of any capture)."""
+    o = options if options is not None else AnnotateOptions.checked(training_manager, **stated)
+    sink, reports, region_sizes = make_sink(), [], set()
+    if o.out_size is not None or o.redact_region is not None:
+        sink.check = _sized_check(sink, o, region_sizes)
     try:
         dtype = getattr(getattr(detector, "head", None), "dtype", "f32")
-        eng = _engine(training_manager, detector, entry.default_in_flight(dtype), post)
-        _det_thresholds(det_threshold, track_low, track, eager=eng is None)      # (a foreign model refuses an L)
-        tracking, every, delayed, backtrack = _tracking_options(eng, track, track_motion, track_lookback, detect_every, track_backtrack,
-                                                                track_scene_cut)
-        if track_scene_cut is not None:                   # (the eager path: one frame at a time against the kept frame)
-            motion["track_scene_cut"] = track_scene_cut
-        trails = _track_trails(track_trails, track, draw)
-        if trails is not None:
-            motion["track_trails"] = tracking["track_trails"] = trails
-        if heatmap is not None:                           # a cold map for the list
-            motion["heatmap"] = tracking["heat"] = heatmap
-            reset_heat(training_manager, detector, 1 if eng is None else eng.in_flight, post)
-        if remove is not None:                            # an empty plate for the list
-            motion["remove"] = tracking["remove"] = remove
-            reset_plate(training_manager, detector, 1 if eng is None else eng.in_flight, post)
-        if redact_moving is not None:                     # an empty moving state for the list, and an empty plate under it
-            motion["redact_moving"] = tracking["redact_moving"] = redact_moving
-            reset_moving(training_manager, detector, 1 if eng is None else eng.in_flight, post)
-            if remove is None:
-                reset_plate(training_manager, detector, 1 if eng is None else eng.in_flight, post)
-            moving_log = MovingLog(moving_out)
-            motion["moving_out"] = moving_log
-        if track is not None:                             # a new sequence; its frames are submitted in input order, as every list's are
-            reset_tracks(training_manager, detector, 1 if eng is None else eng.in_flight, post)
-        if count is not None:                             # zero totals for the list
-            motion["count"] = tracking["count"] = count
-            reset_counts(training_manager, detector, 1 if eng is None else eng.in_flight, post)
-            counts_log = CountsLog(counts_out, _names_by_index(training_manager.class_mapping))
-            motion["counts_out"] = counts_log
-        if zone is not None:                              # an empty state for the list
-            motion["zone"] = tracking["zone"] = zone
-            reset_zones(training_manager, detector, 1 if eng is None else eng.in_flight, post)
-            zones_log = ZonesLog(zones_out, _names_by_index(training_manager.class_mapping))
-            motion["zones_out"] = zones_log
-        if track_reid is not None:                        # (an empty memory for the list: reset_tracks above emptied it)
-            motion["track_reid"] = tracking["track_reid"] = track_reid
-            reid_log = ReidLog(reid_out, _names_by_index(training_manager.class_mapping))
-            motion["reid_out"] = reid_log
-        if low is not None:                               # the weak rule: the passes emit rows down to ``low``, the tracker is told ``strong``
-            tracking["track_strong"] = strong
+        eng = _engine(training_manager, detector, entry.default_in_flight(dtype), o.post)
+        _det_thresholds(o.det_threshold, o.track_low, o.track, eager=eng is None)      # (a foreign model refuses an L)
+        o, delayed = _tracking_options(eng, o)
+        for report in _reports(o, training_manager, detector, eng, region_sizes):
+            reports.append(report)
         if eng is None:
-            if strong != DET_THRESHOLD:
-                motion["det_threshold"] = strong
-            _run_eager(training_manager, detector, frames, sink, resize_min, resize_max, redact=redact, draw=draw, track=track,
-                       tracks_out=tracks_out, **motion)
+            _run_eager(training_manager, detector, frames, sink, resize_min, resize_max,
+                       dataclasses.replace(o, **{r.output: r for r in reports if r.output is not None}))
         else:
-            kwargs = dict(sink.kwargs, annotate=True, **tracking)
-            if redact is not None or not draw:            # (else the passes, and their keys, are the ones without the arguments)
-                kwargs.update(redact=redact, draw=draw)
-            if out_size is not None:
-                kwargs.update(out_size=out_size)
-            if redact_shape is not None:
-                kwargs.update(redact_shape=redact_shape)
-            if redact_region is not None:
-                kwargs.update(redact_region=redact_region)
-            mapping = training_manager.class_mapping
-
             def prepare(label, frame):                    # (read-ahead thread) -> (label, frame, resized, ratio, pixels)
                 sink.check(label, frame)
                 resized, ratio = frame.resize_within_bounds(resize_min, resize_max)
                 return label, frame, resized, ratio, eng.host_pixels(resized)
 
             def emit(pos, label, frame, result):
-                num_rois, dets, out, *marks = result      # (a ``track_scene_cut`` pass: the frame's marks behind its payload)
-                if marks and marks[0].get("scene_cut"):
+                num_rois, dets, out, *marks = result      # (the frame's marks behind its payload, when an option leaves any)
+                marks = marks[0] if marks else {}
+                if marks.get("scene_cut"):
                     print("scene cut: {}".format(label))
-                if count is not None:
-                    counts_log.add(pos + 1, marks[0]["crossings"])
-                if zone is not None:
-                    zones_log.add(pos + 1, marks[0]["zones"]["events"])
-                if track_reid is not None:
-                    reid_log.add(pos + 1, marks[0]["reid"])
-                    _print_reid(label, marks[0]["reid"])
-                if redact_moving is not None:
-                    moving_log.add(pos + 1, frame.height, frame.width, marks[0]["moving"])
+                for report in reports:
+                    report.frame(pos, label, frame, dets, marks)
                 print("processing {}".format(label))
                 print("num rois: {}".format(num_rois))
-                if track is not None:
-                    _write_tracks(tracks_out, pos + 1, dets, mapping)
                 _print_drawn(dets, frame.width, frame.height)
                 sink.emit(pos, out)
 
-            _run_passes(eng, loaded_from(prepare, 2 * eng.in_flight * eng.batch * (every or 1)), emit, kwargs, every, delayed, backtrack,
-                        det_threshold=strong if low is None else low)
+            every = o.detect_every
+            _run_passes(eng, loaded_from(prepare, 2 * eng.in_flight * eng.batch * (every or 1)), emit, o.pass_keywords(sink.kwargs), every, delayed,
+                        o.track_backtrack, det_threshold=o.uploaded_threshold)
         sink.finish()
-        if count is not None:                             # (host only: the state read back)
-            counts_log.close()
-            state = ops.count_totals(_count_state(training_manager, eng))
-            print_counts(len(count[0]), state["totals"], counts_log.per_class, state["events_dropped"])
-        if zone is not None:                              # (host only: the state read back)
-            zones_log.close()
-            print_zones(len(zone[0]), ops.zone_totals(_zone_state(training_manager, eng)))
-        if track_reid is not None:
-            reid_log.close()
-            print("re-identified: {}".format(reid_log.total))
-        if heatmap_out is not None:                       # (host only: the states read back, their t values as grey PNG files)
-            write_heatmaps(heatmap_out, _heat_states(training_manager, eng))
-        if remove is not None:                            # (host only: the states read back; the plate as an RGB PNG, unknown pixels black)
-            plates = plate_summaries(_plate_states(training_manager, eng))
-            print_plates(plates)
-            if plate_out is not None:
-                if redact_region is not None:             # the plate picture never shows a static area in clear
-                    plates = {key: (frames_, known, blacken_plate(plate, _region_weights(training_manager, eng, key[0], key[1], redact_region)))
-                              for key, (frames_, known, plate) in plates.items()}
-                write_plates(plate_out, plates)
-        if redact_moving is not None:                     # (host only: what the passes returned; the file is closed below)
-            for line in moving_log.lines():
-                print(line)
-        if redact_region is not None:                     # (host only: the planes' headers read back)
-            for h, w in sorted(region_sizes):
-                states = eng.edit_states if eng is not None else _eager_states(training_manager.class_mapping)
-                print(region_line(w, h, redact_region, ops.redact_region_stats(states.region_plane(h, w, redact_region))))
+        for report in reports:                            # (host only: the states read back)
+            report.end()
     finally:
-        if counts_log is not None:
-            counts_log.close()
-        if zones_log is not None:
-            zones_log.close()
-        if reid_log is not None:
-            reid_log.close()
-        if moving_log is not None:
-            moving_log.close()
+        for report in reports:
+            report.close()
         sink.close()
 
 
 def annotate_stream(training_manager, detector, reader, writer_or_out_dir, resize_min, resize_max, video_chroma=None, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_subsampling=None, jpeg_huffman=None,
-                    redact=None, draw=True, track=None, tracks_out=None, track_motion=None, track_lookback=None, detect_every=None,
-                    track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None, heatmap_out=None, count=None,
-                    counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None, reid_out=None, post=None,
-                    out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None, redact_moving=None,
-                    moving_out=None):
-    """(``redact_region``, ``redact_moving`` / ``moving_out``: as ``annotate_images``.)
-    ``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
+                    **options):
+    """``annotate_images`` for a video stream.  ``reader``: a ``y4m.Y4mReader`` (its frames are converted on the device inside the
     passes), or any iterable of (label, frame) such as ``directory_frames``.  ``writer_or_out_dir``: a ``y4m.Y4mWriter`` -- every
     annotated frame is converted to the writer's chroma mode and range inside its pass (submit_batch(encode="y4m")) and written in order;
-    every frame must then have the writer's size -- or a directory, which receives ``frame_%06d.png`` / ``.jpg`` through the encoders the
-    other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead bounded at 2 * in_flight * B frames, passes
-    of B frames of one geometry, output in stream order.  Prints what ``annotate_images`` prints, the label in the path's place.  ``redact`` / ``draw`` / ``track`` / ``tracks_out`` / ``track_motion`` / ``track_lookback`` / ``detect_every`` / ``track_backtrack`` / ``track_scene_cut`` / ``track_trails`` / ``heatmap`` / ``heatmap_out`` / ``count`` / ``counts_out`` / ``remove`` / ``plate_out`` / ``track_reid`` / ``reid_out`` / ``post`` / ``out_size`` / ``redact_shape``: as ``annotate_images`` (a ``Y4mWriter``'s size is then the SCALED size).  """
+    every frame must then have the writer's size, with ``out_size`` its SCALED size -- or a directory, which receives ``frame_%06d.png``
+    / ``.jpg`` through the encoders the other arguments choose, as ``annotate_images`` writes them.  The same pipeline: look-ahead
+    bounded at 2 * in_flight * B frames, passes of B frames of one geometry, output in stream order.  Prints what ``annotate_images``
+    prints, the label in the path's place.  ``options``: the options of ``AnnotateOptions``, as ``annotate_images`` takes them."""
     source = stream_frames(reader) if isinstance(reader, y4m.Y4mReader) else iter(reader)
+    o = AnnotateOptions.checked(training_manager, **options)
     if isinstance(writer_or_out_dir, y4m.Y4mWriter):
-        make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma, out_size)
+        make_sink = lambda: _y4m_sink(writer_or_out_dir, video_chroma, o.out_size)
     else:
         make_sink = lambda: _file_sink(writer_or_out_dir, None, png_encoder, png_compress, frame_format, jpeg_encoder, jpeg_quality, jpeg_subsampling,
                                       jpeg_huffman)
-    _annotate(training_manager, detector, source, lambda prepare, ahead: _loaded_stream(source, prepare, ahead), make_sink, resize_min, resize_max,
-              redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion, track_lookback=track_lookback,
-              detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut, track_trails=track_trails,
-              heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out, remove=remove,
-              plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size, redact_shape=redact_shape,
-              det_threshold=det_threshold, track_low=track_low, redact_region=redact_region, redact_moving=redact_moving,
-              moving_out=moving_out)
+    _annotate(training_manager, detector, source, lambda prepare, ahead: _loaded_stream(source, prepare, ahead), make_sink, resize_min, resize_max, o)
 
 
 def annotate_images(training_manager, detector, input_dir, out_dir, image_filenames, resize_min, resize_max, png_encoder=None,
                     png_compress=None, frame_format=None, jpeg_encoder=None, jpeg_quality=None, jpeg_decoder=None, jpeg_subsampling=None,
-                    jpeg_huffman=None, png_decoder=None, redact=None, draw=True, track=None, tracks_out=None, track_motion=None,
-                    track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None, heatmap=None,
-                    heatmap_out=None, count=None, counts_out=None, zone=None, zones_out=None, remove=None, plate_out=None, track_reid=None,
-                    reid_out=None, post=None, out_size=None, redact_shape=None, det_threshold=None, track_low=None, redact_region=None,
-                    redact_moving=None, moving_out=None):
+                    jpeg_huffman=None, png_decoder=None, **options):
     """annotate_video.py:15-24, pipelined (see the module docstring); output and printed lines as the one-by-one loop.
     ``png_encoder``: "host" (PIL on the writer threads) or "device" (encoded inside the pass); None = ``default_png_encoder()``.
     ``png_compress``: the device encoder's mode, "runs" or "huffman"; None = ``default_png_compress()``.
@@ -2214,86 +2271,8 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
     ``png_decoder``: "host", "device" or "device_full" (csrc/png_dec_full.hip: palette, 1/2/4/16-bit, grey + alpha and Adam7 files too):
     who decodes ``.png`` INPUT frames the device decoder supports (captured path only; the decode
     threads then only read the file and check its chunks); None = what ``entry.png_decoder()`` says (FRCNN_ENTRY_PNG_DECODER, default "host").
-    ``redact``: (classes, mode, size, margin) as ``redact_from_args`` returns it -- those classes' boxes are hidden in every frame inside
-    its pass, in front of the drawing step and of whichever encoder writes the frame; None: nothing is.  ``draw`` False: no boxes, no labels.
-    ``track``: (thr, hold, grow) as ``track_from_args`` returns it -- the list is ONE sequence in list order: the tracker's state is reset
-    at the start, every tracked detection is labelled ``cls#id`` and lost tracks are held (and redacted) for ``hold`` frames; None: no
-    tracking.  ``tracks_out``: a text file that receives the MOT lines, frame i of the list under the number i + 1.
-    ``track_motion``: the search radius as ``track_motion_from_args`` returns it (with ``track``) -- every track's box is moved with the
-    pixels under it from frame to frame, so a held box follows its object; None: held boxes stand still.
-    ``track_lookback``: the frames as ``track_lookback_from_args`` returns them (with ``track``; TRACK_LOOKBACK_AUTO: as many as a pass
-    holds, at most 8) -- every new track is followed BACK over that many frames and hidden there too (DESIGN §8 "Look-back rule").  Every
-    group then goes through a full pass of B frames, a pass returns the frames of the pass before it and a flush ends the list: each
-    frame is written and printed when it is emitted, the same lines in the same order.  The eager path refuses it.
-    ``detect_every``: K as ``detect_every_from_args`` returns it (with ``track`` and ``track_motion``, not with ``track_lookback``) -- the
-    detector runs on every K-th frame only and a pass takes B * K frames; on the frames between, every track's box follows the pixels under
-    it (DESIGN §8 "Interval rule"), is drawn, redacted and written to ``tracks_out`` with the prob of its last match.  Nothing is matched,
-    aged or born between two detected frames: ``hold`` counts detected frames.  The K-th frames are counted per GROUP, not over the list:
-    a group is a run of at most B * K consecutive frames of one geometry, it is cut where the geometry changes, and its frames 0, K,
-    2K, ... are the detected ones (a group whose key frames fill under half a pass goes through one-image passes of K frames, the same
-    key frames).  With frames of one size, a video, every group but the last is full and that is every K-th frame of the list; in a list
-    of mixed sizes a detected frame follows every change of geometry.  The eager path refuses it.
-    ``track_backtrack``: the frames as ``track_backtrack_from_args`` returns them (with ``detect_every``, not with ``track_lookback``;
-    TRACK_BACKTRACK_AUTO: as many as a pass of B * K frames holds, at most 16; at least K - 1) -- at every detected frame every track is
-    followed BACK through the frames in front of it (DESIGN §8 "Back-track rule"): a continued track as far as the detected frame before,
-    a new one over that many frames, and the boxes found are hidden there too, so a frame between two detections is covered from both
-    sides.  Every group of at most B * K frames then goes through one full (padded) pass, a pass returns the frames of the pass before it
-    and a flush follows a change of geometry and the end of the list, as with ``track_lookback``.  The eager path refuses it.
-    ``track_scene_cut``: the percentage as ``track_scene_cut_from_args`` returns it (with ``track`` and ``track_motion``, with or without
-    ``detect_every``; not with ``track_lookback`` or ``track_backtrack``, whose backward chains would have to stop at a cut) -- a frame
-    whose 4 x 4-region luma histogram differs from the frame before by that share of the largest distance there is, is a hard cut (DESIGN
-    §8 "Cut rule"): every track ends in front of it, so no id is inherited by the new scene and no held box of the old scene is redacted
-    in it; between two detected frames nothing is shown behind a cut until the next detected frame.  A line ``scene cut: <path>`` is
-    printed in front of that frame's lines.  A fade or a dissolve is not detected.  None: every byte and line is what it was.
-    ``track_trails``: (N, W) as ``track_trails_from_args`` returns it (with ``track``, in every form above; not with ``draw`` False) -- the
-    path of every id is kept on the device and each frame shows the last N points of the ids live in it as a line W pixels wide in the
-    colour of the id (DESIGN §8 "Trail rule"), over the redaction and under the boxes; a delayed pass draws them in the order its frames
-    are emitted.  The printed lines and ``tracks_out`` are unchanged.  None: every byte and line is what it was.
-    ``heatmap``: (classes, A, S) as ``heatmap_from_args`` returns it (with every option above, ``draw`` False included) -- a map on the
-    device that starts cold with the list gains 256 per box of those classes in every frame (every detection; with ``track`` the live
-    tracked rows, in a delayed pass the emitted frames'), loses ceil(v / 2^S) per frame, and is blended into each frame at weight A for
-    the hottest pixel, over the redaction and under the trails, boxes and labels (DESIGN §8 "Heat rule").  ``heatmap_out``: a path ending
-    in .png that receives the map at the end of the list, 8-bit grey, one file per frame size met (``<stem>_<w>x<h>.png`` for several).
-    The printed lines and ``tracks_out`` are unchanged.  None: every byte and line is what it was.
-    ``post``: the post-process option as ``args_util.post_from_args`` returns it (``ops.det_post_option``: mode, nms_thresh, sigma,
-    min_score, vote_iou) -- soft-NMS and box voting inside the captured passes (DESIGN §8 "Post-process rule"), on the eager path through
-    ``ops.detections_post``: which boxes every frame reports, with decayed scores in the soft modes; everything above then works on those
-    boxes.  The passes belong to an engine of their own.  None: no pass, engine key, printed line or output byte changes.
-    ``out_size``: ("size", W, H) or ("scale", N) as ``out_size_from_args`` returns it -- every frame is scaled DOWN on the device as the
-    last step of its pass, behind every edit and in front of whichever encoder writes it (DESIGN §8 "Scale rule": the exact area mean, in
-    integers; labels shrink with the picture): the device encoders encode, and the read-back copies, the smaller frame; the host encoders
-    simply receive it.  ("scale", N) applies per frame size in a list of mixed sizes; ("size", W, H) is refused with the name of the
-    first frame that is smaller than it (or more than 16 times its size along a side).  The printed lines, ``tracks_out``, ``counts_out``
-    and ``zones_out`` stay in SOURCE coordinates.  None: no pass, key, printed line or output byte changes.
-    ``redact_shape``: (shape, feather) as ``redact_shape_from_args`` returns it (with ``redact``, and with every option above) -- every
-    box the redaction hides, held and back-filled ones too, hides the ellipse inscribed in the box grown by the margin ("ellipse"), and
-    the replacement fades into the scene over ``feather`` pixels OUTSIDE the shape, so nothing the hard shape hides shows (DESIGN §8
-    "Shape rule", ops.redact_shaped_u8).  The plate of ``remove``, the tracker, the heat map and the drawn boxes keep their rectangles.
-    None and ("box", 0): no pass, key, printed line or output byte changes.
-    ``det_threshold``: T, a float in 0..1 (``--det_threshold``; None: DET_THRESHOLD = 0.0, the reference script's): the score under which
-    a detection is not reported; with or without ``track``.  ``track_low``: L < T (``--track_low``, with ``track``): the weak rule
-    (DESIGN §8 "Weak rule", the ``strong=`` form of the tracker call): the passes emit rows down to L (submit_batch's det_threshold = L,
-    track_strong = T), a row with a score in [L, T) may only continue a track that no row of T or more continued, and every other such
-    row is dropped -- so an object whose score dips stays covered by the detector's own box, under its id, and nothing new is reported
-    under T.  "num dets", the printed lines and ``tracks_out`` show the kept rows.  Refused by name without ``track``, for L >= T and
-    outside 0..1, and on the eager path (a foreign model).  None and None: no pass, key, printed line or output byte changes.
-    ``redact_region``: (regions, mask, mode, size, feather) as ``redact_region_from_args`` returns it (with every option above, with and
-    without ``redact`` and ``track``) -- static areas, polygons in source-frame pixels and a painted mask whose bytes >= 128 hide, are
-    hidden in EVERY frame whatever the detector says (DESIGN §8 "Region rule"): what replaces them comes from the untouched frame, they
-    are blended in behind the plate fill of ``remove`` and under the heat map and everything drawn, and the edge fades outwards over
-    ``feather`` pixels.  Polygons apply to every frame size; a mask is held to one, and a frame it does not fit is refused by name.
-    ``plate_out`` then shows every pixel of an area black.  A line ``redact regions 1242x375: 2 regions + mask, 12.3 % of the frame
-    hidden`` is printed per frame size at the end; every other printed line and file is unchanged.  None: no pass, key, printed line or
-    output byte changes.
-    ``redact_moving``: True, a dict of ops.redact_moving_option's keywords or its 12 values, as ``redact_moving_from_args`` returns it
-    (with every option above, with and without ``remove`` and ``track``) -- the moving net (DESIGN §8 "Moving rule"): on fixed-camera
-    footage whatever differs from the plate is hidden in every frame, detected or not.  The list starts from an EMPTY moving state and
-    an empty plate; without ``remove`` the plate is learned all the same, with the option's (S, T, M), and nothing is painted out; with
-    it the three are ``remove``'s, and one stated here that differs is refused by name.  The defaults 24, 8, 4 and 8 are PROVISIONAL.
-    Until a pixel's background is known it is shown (unknown "hide" blanks it instead): the first S frames are not protected by the
-    net under the default.  Delayed passes run the net on the frames they emit.  ``moving_out``: a path; a CSV ``frame,cells,covered``
-    is written there.  A line ``moving net 1242x375: 128 frames, mean 3.2 % hidden, peak 17.0 %`` is printed per frame size at the
-    end.  None: no pass, key, printed line or output byte changes."""
+    ``options``: what is done to the frames -- redaction, tracking, counting and the rest --, as keywords: the fields of
+    ``AnnotateOptions``, whose docstring describes each.  ValueError, in front of any capture, for what they refuse."""
     if jpeg_decoder is not None:
         entry.set_jpeg_decoder(jpeg_decoder)
     if png_decoder is not None:
@@ -2304,12 +2283,7 @@ def annotate_images(training_manager, detector, input_dir, out_dir, image_filena
                                   jpeg_huffman)
     _annotate(training_manager, detector, ((path, _Frame(_read_rgb(path))) for path in paths),
               lambda prepare, ahead: _loaded_files(paths, lambda path: prepare(path, _load_frame(path, device_decode, device_png)), ahead),
-              make_sink, resize_min, resize_max, redact=redact, draw=draw, track=track, tracks_out=tracks_out, track_motion=track_motion,
-              track_lookback=track_lookback, detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-              track_trails=track_trails, heatmap=heatmap, heatmap_out=heatmap_out, count=count, counts_out=counts_out, zone=zone, zones_out=zones_out,
-              remove=remove, plate_out=plate_out, track_reid=track_reid, reid_out=reid_out, post=post, out_size=out_size,
-              redact_shape=redact_shape, det_threshold=det_threshold, track_low=track_low, redact_region=redact_region,
-              redact_moving=redact_moving, moving_out=moving_out)
+              make_sink, resize_min, resize_max, AnnotateOptions.checked(training_manager, **options))
 
 
 def build_parser():
@@ -2611,7 +2585,7 @@ def main(argv=None):
 def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     import sys
     from . import resnet, vgg
-    from .args_util import anchor_scales_from_str, post_from_args, resize_dims_from_str
+    from .args_util import anchor_scales_from_str, resize_dims_from_str
     from .data.voc_data_helpers import KITTI_CLASS_MAPPING, VOC_CLASS_MAPPING
     from .det_util import DetTrainingManager
     from .util import get_anchors
@@ -2620,70 +2594,7 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
     jpeg_size_options(frame_format, args.jpeg_subsampling, args.jpeg_huffman)
     os.environ.setdefault("GPU_MAX_HW_QUEUES", voc_dets.ENTRY_HW_QUEUES)      # (as voc_dets.main: passes in flight want > 4 queues)
     class_mapping = KITTI_CLASS_MAPPING if args.kitti else VOC_CLASS_MAPPING
-    redact, draw = redact_from_args(args, class_mapping), not args.no_draw                                  # (before any model is loaded)
-    track = track_from_args(args)
-    track_motion = track_motion_from_args(args)
-    tracking = {} if track is None else {"track": track, "tracks_out": stack.enter_context(open(args.tracks_out, "w")) if args.tracks_out else None}
-    if track_motion is not None:
-        tracking["track_motion"] = track_motion
-    track_lookback = track_lookback_from_args(args)
-    if track_lookback is not None:
-        tracking["track_lookback"] = track_lookback
-    detect_every = detect_every_from_args(args)
-    if detect_every is not None:
-        tracking["detect_every"] = detect_every
-    track_backtrack = track_backtrack_from_args(args)
-    if track_backtrack is not None:
-        tracking["track_backtrack"] = track_backtrack
-    track_scene_cut = track_scene_cut_from_args(args)
-    if track_scene_cut is not None:
-        tracking["track_scene_cut"] = track_scene_cut
-    track_trails = track_trails_from_args(args)
-    if track_trails is not None:
-        tracking["track_trails"] = track_trails
-    heatmap, heatmap_out = heatmap_from_args(args, class_mapping)
-    if heatmap is not None:
-        tracking["heatmap"] = heatmap
-    if heatmap_out is not None:
-        tracking["heatmap_out"] = heatmap_out
-    remove, plate_out = remove_from_args(args, class_mapping)
-    if remove is not None:
-        tracking["remove"] = remove
-    if plate_out is not None:
-        tracking["plate_out"] = plate_out
-    redact_moving, moving_out = redact_moving_from_args(args, class_mapping, remove)      # (before any model is loaded)
-    if redact_moving is not None:
-        tracking["redact_moving"] = redact_moving
-    if moving_out is not None:
-        tracking["moving_out"] = moving_out
-    count, counts_out = count_from_args(args, class_mapping)
-    if count is not None:
-        tracking["count"] = count
-    if counts_out is not None:
-        tracking["counts_out"] = counts_out
-    track_reid, reid_out = track_reid_from_args(args)
-    if track_reid is not None:
-        tracking["track_reid"] = track_reid
-    if reid_out is not None:
-        tracking["reid_out"] = reid_out
-    zone, zones_out = zone_from_args(args, class_mapping)
-    if zone is not None:
-        tracking["zone"] = zone
-    if zones_out is not None:
-        tracking["zones_out"] = zones_out
-    post = post_from_args(args)                           # (before any model is loaded: dependent options are refused by name)
-    if post is not None:
-        tracking["post"] = post
-    out_size = out_size_from_args(args)                   # (before any model is loaded)
-    if out_size is not None:
-        tracking["out_size"] = out_size
-    redact_shape = redact_shape_from_args(args)           # (before any model is loaded)
-    if redact_shape is not None:
-        tracking["redact_shape"] = redact_shape
-    redact_region = redact_region_from_args(args)         # (before any model is loaded)
-    if redact_region is not None:
-        tracking["redact_region"] = redact_region
-    tracking.update(det_thresholds_from_args(args))       # (before any model is loaded)
+    options = AnnotateOptions.from_args(args, class_mapping, stack)                                         # (before any model is loaded)
     anchors = get_anchors(anchor_scales_from_str(args.anchor_scales))
     if args.network == "vgg16":
         rpn = vgg.rpn_from_h5(args.step3_model_path, anchors_per_loc=len(anchors), dtype=args.dtype)
@@ -2709,22 +2620,22 @@ def _main(args, stream_in, out_video, video_chroma, video_out, stack):
             (w, h), yrange, tags = _frame_size(os.path.join(args.input_dir, names[0])), "limited", {"F": "25:1"}
         if out_video is not None:
             fout = video_out if video_out is not None else stack.enter_context(open(out_video, "wb"))
-            if out_size is not None:                      # the header carries the scaled size
-                w, h = scaled_size(out_size, "<stdin>" if args.input_dir == "-" else args.input_dir, w, h)
+            if options.out_size is not None:              # the header carries the scaled size
+                w, h = scaled_size(options.out_size, "<stdin>" if args.input_dir == "-" else args.input_dir, w, h)
             sink = y4m.Y4mWriter(fout, w, h, video_chroma, yrange, {k: tags[k] for k in ("F", "A") if k in tags})
-            annotate_stream(manager, detector, reader, sink, resize_min, resize_max, redact=redact, draw=draw, **tracking)
+            annotate_stream(manager, detector, reader, sink, resize_min, resize_max, **vars(options))
         else:
             annotate_stream(manager, detector, reader, args.out_dir, resize_min, resize_max, png_encoder=args.png_encoder,
                             png_compress=args.png_compress, frame_format=args.frame_format, jpeg_encoder=args.jpeg_encoder,
                             jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, jpeg_huffman=args.jpeg_huffman,
-                            redact=redact, draw=draw, **tracking)
+                            **vars(options))
         return
     annotate_images(training_manager=manager, detector=detector, input_dir=args.input_dir, out_dir=args.out_dir,
                     image_filenames=frame_filenames(args.input_dir, args.jpeg_decoder or entry.jpeg_decoder()), resize_min=resize_min,
                     resize_max=resize_max, jpeg_decoder=args.jpeg_decoder, png_decoder=args.png_decoder,
                     png_encoder=args.png_encoder, png_compress=args.png_compress, frame_format=args.frame_format,
                     jpeg_encoder=args.jpeg_encoder, jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling,
-                    jpeg_huffman=args.jpeg_huffman, redact=redact, draw=draw, **tracking)
+                    jpeg_huffman=args.jpeg_huffman, **vars(options))
 
 
 if __name__ == "__main__":

@@ -1528,11 +1528,7 @@ class DetectionEntry:
         """``pixels``: the result of ``host_pixels(image)`` when the caller fetched it ahead of time."""
         return self.submit_batch([image], [resize_ratio], det_threshold, [self.host_pixels(image) if pixels is None else pixels], batch=1)
 
-    def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, annotate=False, encode=None, quality=None,
-                     subsampling=None, huffman=None, y4m=None, redact=None, draw=True, track=None, track_motion=None,
-                     track_lookback=None, detect_every=None, track_backtrack=None, track_scene_cut=None, track_trails=None,
-                     heat=None, count=None, zone=None, remove=None, track_reid=None, out_size=None, redact_shape=None, track_strong=None,
-                     redact_region=None, redact_moving=None):
+    def submit_batch(self, images, resize_ratios, det_threshold, pixels, batch=None, **options):
         """Up to ``batch`` images of ONE geometry (``geometry(pixels[i])`` equal) in one captured pass; a short group is padded with
         copies of its first frame, whose results nobody reads.  ``collect_batch`` returns the images' results in order.
         ``annotate``: a pass of its own (cache key tagged "annotate", never a canvas pass) that also draws the detections into each
@@ -1712,12 +1708,7 @@ class DetectionEntry:
         with a foreign preprocess, for values out of range and for an EXCEPT name that is no class.  Without it every key and byte is
         what it was.
         The order of all these steps in a pass is stated once, in ``frame_edit.EditChain``'s docstring."""
-        spec = PassSpec.checked(self, batch, annotate=annotate, encode=encode, quality=quality, subsampling=subsampling, huffman=huffman, y4m=y4m,
-                                redact=redact, draw=draw, track=track, track_motion=track_motion, track_lookback=track_lookback,
-                                detect_every=detect_every, track_backtrack=track_backtrack, track_scene_cut=track_scene_cut,
-                                track_trails=track_trails, heat=heat, count=count, zone=zone, remove=remove, track_reid=track_reid,
-                                out_size=out_size, redact_shape=redact_shape, track_strong=track_strong, redact_region=redact_region,
-                                redact_moving=redact_moving)
+        spec = PassSpec.checked(self, batch, **options)            # (an unknown keyword: its TypeError)
         self._check_epoch()
         B = self.batch if batch is None else batch
         if spec.delayed and len(images) == 0:                       # the flush
@@ -1737,7 +1728,7 @@ class DetectionEntry:
         spec = spec.sized(self, B)
         spec.out_hw(src if src is not None else (H, W))            # (refuses a target this frame size or the encoder cannot take)
         spec.region_fits(src if src is not None else (H, W))       # (refuses a mask of another size)
-        if annotate:
+        if spec.annotate:
             if not self.device_preprocess:
                 raise FrcnnError("annotating passes need the device-side preprocess (a foreign preprocess_func uploads float pixels)")
             key = self.geometry_of(pixels[0])
