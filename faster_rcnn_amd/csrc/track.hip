@@ -6,11 +6,16 @@
 // best, four LDS records (double-buffered: one barrier per slot) the workgroup's, and the thread that owns the winning row updates the
 // slot.  Ageing with compaction, births and the held rows' places in the output are exclusive prefix sums over the workgroup, so ids and
 // places do not depend on which thread runs when.  Every output word has one writer; no atomics.
+// The host half is the whole family's (csrc/track_call.h): the one check of a call's arguments and the one walk over its frames, which the
+// motion, interval and cut entries (csrc/track_motion.hip, track_interval.hip, track_cut.hip) go through as frcnn_track_update does.
 #include "common.h"
 #include "../../include/ext/frcnn_hip_redact.h"
 #include "../../include/ext/frcnn_hip_track.h"
+#include "../../include/ext/frcnn_hip_track_cut.h"
+#include "../../include/ext/frcnn_hip_track_interval.h"
+#include "../../include/ext/frcnn_hip_track_motion.h"
 #include "../../include/ext/frcnn_hip_track_weak.h"
-#include "track.h"
+#include "track_call.h"
 
 namespace frcnn {
 
@@ -281,49 +286,72 @@ __global__ void __launch_bounds__(TR_THREADS) k_track_update(int32_t* state, int
     }
 }
 
-int track_check(const char* who, const int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int frames,
-                const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
-                const int32_t* out, long long out_stride) {
-    if (!state || !det_packed || !n_frames || !tracked || !out) return fail(FRCNN_E_ARG, "%s: null pointer", who);
-    if (capacity < 1 || capacity > FRCNN_TRACK_MAX) return fail(FRCNN_E_ARG, "%s: capacity=%d not in [1, %d]", who, capacity, FRCNN_TRACK_MAX);
-    if (frames < 1 || frames > FRCNN_TRACK_MAX_FRAMES) return fail(FRCNN_E_ARG, "%s: frames=%d not in [1, %d]", who, frames, FRCNN_TRACK_MAX_FRAMES);
-    if (max_rows <= 0 || max_rows > FRCNN_REDACT_MAX_ROWS - capacity)
-        return fail(FRCNN_E_ARG, "%s: max_rows=%d: max_rows + capacity (%d) not in [2, %d]", who, max_rows, capacity, FRCNN_REDACT_MAX_ROWS);
-    const long long det_words = 4 + 7LL * max_rows, out_words = 4 + 8LL * (max_rows + capacity);
-    if (frames > 1 && det_stride < det_words)
-        return fail(FRCNN_E_ARG, "%s: det_stride=%lld words, a packed buffer of %d rows has %lld", who, det_stride, max_rows, det_words);
-    if (frames > 1 && out_stride < out_words)
-        return fail(FRCNN_E_ARG, "%s: out_stride=%lld words, a tracked buffer has %lld", who, out_stride, out_words);
-    if (num_classes <= 0 || num_classes > 256) return fail(FRCNN_E_ARG, "%s: num_classes=%d not in [1, 256]", who, num_classes);
-    if (thr < 1 || thr > 100) return fail(FRCNN_E_ARG, "%s: thr=%d not in [1, 100] (percent)", who, thr);
-    if (hold < 0 || hold > FRCNN_TRACK_MAX_HOLD) return fail(FRCNN_E_ARG, "%s: hold=%d not in [0, %d]", who, hold, FRCNN_TRACK_MAX_HOLD);
-    if (grow < 0 || grow > FRCNN_TRACK_MAX_GROW) return fail(FRCNN_E_ARG, "%s: grow=%d not in [0, %d]", who, grow, FRCNN_TRACK_MAX_GROW);
-    if (h < 1 || h > FRCNN_REDACT_MAX_SIDE || w < 1 || w > FRCNN_REDACT_MAX_SIDE)
-        return fail(FRCNN_E_ARG, "%s: frame %dx%d out of range (sides 1..%d)", who, h, w, FRCNN_REDACT_MAX_SIDE);
+int track_call_check(const char* who, const TrackCall& c) {
+    if (c.interval < FRCNN_TRACK_INTERVAL_MIN || c.interval > FRCNN_TRACK_INTERVAL_MAX)
+        return fail(FRCNN_E_ARG, "%s: interval=%d not in [%d, %d]", who, c.interval, FRCNN_TRACK_INTERVAL_MIN, FRCNN_TRACK_INTERVAL_MAX);
+    if (!c.state || !c.det_packed || !c.n_frames || !c.tracked || !c.out) return fail(FRCNN_E_ARG, "%s: null pointer", who);
+    if (c.capacity < 1 || c.capacity > FRCNN_TRACK_MAX)
+        return fail(FRCNN_E_ARG, "%s: capacity=%d not in [1, %d]", who, c.capacity, FRCNN_TRACK_MAX);
+    if (c.frames < 1 || c.frames > FRCNN_TRACK_MAX_FRAMES)
+        return fail(FRCNN_E_ARG, "%s: frames=%d not in [1, %d]", who, c.frames, FRCNN_TRACK_MAX_FRAMES);
+    if (c.max_rows <= 0 || c.max_rows > FRCNN_REDACT_MAX_ROWS - c.capacity)
+        return fail(FRCNN_E_ARG, "%s: max_rows=%d: max_rows + capacity (%d) not in [2, %d]", who, c.max_rows, c.capacity, FRCNN_REDACT_MAX_ROWS);
+    // the packed buffers are one per KEY frame: their distance is read only when the call has more than one of them
+    const long long det_words = 4 + 7LL * c.max_rows, out_words = 4 + 8LL * (c.max_rows + c.capacity);
+    if ((c.frames + c.interval - 1) / c.interval > 1 && c.det_stride < det_words)
+        return fail(FRCNN_E_ARG, "%s: det_stride=%lld words, a packed buffer of %d rows has %lld", who, c.det_stride, c.max_rows, det_words);
+    if (c.frames > 1 && c.out_stride < out_words)
+        return fail(FRCNN_E_ARG, "%s: out_stride=%lld words, a tracked buffer has %lld", who, c.out_stride, out_words);
+    if (c.num_classes <= 0 || c.num_classes > 256) return fail(FRCNN_E_ARG, "%s: num_classes=%d not in [1, 256]", who, c.num_classes);
+    if (c.thr < 1 || c.thr > 100) return fail(FRCNN_E_ARG, "%s: thr=%d not in [1, 100] (percent)", who, c.thr);
+    if (c.hold < 0 || c.hold > FRCNN_TRACK_MAX_HOLD) return fail(FRCNN_E_ARG, "%s: hold=%d not in [0, %d]", who, c.hold, FRCNN_TRACK_MAX_HOLD);
+    if (c.grow < 0 || c.grow > FRCNN_TRACK_MAX_GROW) return fail(FRCNN_E_ARG, "%s: grow=%d not in [0, %d]", who, c.grow, FRCNN_TRACK_MAX_GROW);
+    if (c.h < 1 || c.h > FRCNN_REDACT_MAX_SIDE || c.w < 1 || c.w > FRCNN_REDACT_MAX_SIDE)
+        return fail(FRCNN_E_ARG, "%s: frame %dx%d out of range (sides 1..%d)", who, c.h, c.w, FRCNN_REDACT_MAX_SIDE);
+    if (c.form != TRACK_PLAIN) {
+        if (!c.motion_state || !c.frames_u8) return fail(FRCNN_E_ARG, "%s: null pointer", who);
+        if (reinterpret_cast<uintptr_t>(c.motion_state) & 3) return fail(FRCNN_E_ARG, "%s: motion_state is not 4-byte aligned", who);
+        if (c.radius < FRCNN_TRACK_MOTION_MIN_RADIUS || c.radius > FRCNN_TRACK_MOTION_MAX_RADIUS)
+            return fail(FRCNN_E_ARG, "%s: radius=%d not in [%d, %d]", who, c.radius, FRCNN_TRACK_MOTION_MIN_RADIUS, FRCNN_TRACK_MOTION_MAX_RADIUS);
+        const long long frame_bytes = 3LL * c.h * c.w;
+        if (c.frames > 1 && c.frame_stride < frame_bytes)
+            return fail(FRCNN_E_ARG, "%s: frame_stride=%lld bytes, a %dx%d frame has %lld", who, c.frame_stride, c.h, c.w, frame_bytes);
+    }
+    if (c.form == TRACK_CUT) {
+        if (c.pct < FRCNN_TRACK_CUT_MIN_PCT || c.pct > FRCNN_TRACK_CUT_MAX_PCT)
+            return fail(FRCNN_E_ARG, "%s: pct=%d not in [%d, %d]", who, c.pct, FRCNN_TRACK_CUT_MIN_PCT, FRCNN_TRACK_CUT_MAX_PCT);
+        if (!c.workspace || !c.cuts) return fail(FRCNN_E_ARG, "%s: null pointer", who);
+        if (reinterpret_cast<uintptr_t>(c.workspace) & 3) return fail(FRCNN_E_ARG, "%s: workspace is not 4-byte aligned", who);
+    }
+    if (c.strong && *c.strong != *c.strong) return fail(FRCNN_E_ARG, "%s: strong is NaN", who);
     return FRCNN_OK;
 }
 
-void track_launch_at(int32_t* state, int capacity, const int32_t* det, long long det_stride, int first, int frames, int total,
-                     const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
-                     int32_t* out, long long out_stride, hipStream_t stream, const float* strong) {
-    if (strong)
-        k_track_update<true><<<1, TR_THREADS, 0, stream>>>(state, capacity, det, det_stride, first, frames, total, n_frames, max_rows, tracked,
-                                                           num_classes, thr, hold, grow, h, w, *strong, out, out_stride);
+void track_launch(const TrackCall& c, int first, int frames, const int32_t* det, int32_t* out, hipStream_t stream) {
+    if (c.strong)
+        k_track_update<true><<<1, TR_THREADS, 0, stream>>>(c.state, c.capacity, det, c.det_stride, first, frames, c.frames, c.n_frames, c.max_rows,
+                                                           c.tracked, c.num_classes, c.thr, c.hold, c.grow, c.h, c.w, *c.strong, out, c.out_stride);
     else
-        k_track_update<false><<<1, TR_THREADS, 0, stream>>>(state, capacity, det, det_stride, first, frames, total, n_frames, max_rows, tracked,
-                                                            num_classes, thr, hold, grow, h, w, 0.0f, out, out_stride);
+        k_track_update<false><<<1, TR_THREADS, 0, stream>>>(c.state, c.capacity, det, c.det_stride, first, frames, c.frames, c.n_frames, c.max_rows,
+                                                            c.tracked, c.num_classes, c.thr, c.hold, c.grow, c.h, c.w, 0.0f, out, c.out_stride);
 }
 
-int weak_check(const char* who, float strong) {
-    if (strong != strong) return fail(FRCNN_E_ARG, "%s: strong is NaN", who);
-    return FRCNN_OK;
-}
-
-void track_launch(int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int first, int frames, int total,
-                  const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h, int w,
-                  int32_t* out, long long out_stride, hipStream_t stream, const float* strong) {
-    track_launch_at(state, capacity, det_packed + (long long)first * det_stride, det_stride, first, frames, total, n_frames, max_rows, tracked,
-                    num_classes, thr, hold, grow, h, w, out + (long long)first * out_stride, out_stride, stream, strong);
+int track_walk(const char* who, const TrackCall& c, hipStream_t stream) {
+    if (c.form == TRACK_PLAIN) {
+        track_launch(c, 0, c.frames, c.det_packed, c.out, stream);
+        return check_launch(who);
+    }
+    for (int f = 0; f < c.frames; ++f) {                                    // (the search of frame f + 1 needs the boxes after frame f)
+        if (c.form == TRACK_CUT) cut_apply_launch(c, f, stream);
+        motion_search_launch(c, f, stream);
+        int32_t* o = c.out + (long long)f * c.out_stride;
+        if (f % c.interval == 0)
+            track_launch(c, f, 1, c.det_packed + (long long)(f / c.interval) * c.det_stride, o, stream);
+        else
+            interval_between_launch(c, f, o, stream);
+    }
+    motion_keep_launch(c, stream);
+    return check_launch(who);
 }
 
 }  // namespace frcnn
@@ -337,24 +365,15 @@ extern "C" size_t frcnn_track_state_bytes(int capacity) {
     return 4 * (4 + 8 * (size_t)capacity);
 }
 
-// frcnn_track_update (strong null) and frcnn_track_update_weak
-static int track_update_call(const char* who, int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int frames,
-                             const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int h,
-                             int w, const float* strong, int32_t* out, long long out_stride, void* stream) {
-    int bad = track_check(who, state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr,
-                                hold, grow, h, w, out, out_stride);
-    if (!bad && strong) bad = weak_check(who, *strong);
-    if (bad) return bad;
-    track_launch(state, capacity, det_packed, det_stride, 0, frames, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow, h, w, out,
-                 out_stride, as_stream(stream), strong);
-    return check_launch(who);
-}
-
 extern "C" int frcnn_track_update(int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int frames,
                                   const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold, int grow,
                                   int h, int w, int32_t* out, long long out_stride, void* stream) {
-    return track_update_call("track_update", state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr, hold,
-                             grow, h, w, nullptr, out, out_stride, stream);
+    TrackCall c{};
+    c.form = TRACK_PLAIN; c.state = state; c.capacity = capacity; c.det_packed = det_packed; c.det_stride = det_stride; c.frames = frames;
+    c.n_frames = n_frames; c.max_rows = max_rows; c.tracked = tracked; c.num_classes = num_classes; c.thr = thr; c.hold = hold; c.grow = grow;
+    c.interval = 1; c.h = h; c.w = w; c.out = out; c.out_stride = out_stride;
+    const int bad = track_call_check("track_update", c);
+    return bad ? bad : track_walk("track_update", c, as_stream(stream));
 }
 
 extern "C" int frcnn_track_weak_version(void) { return FRCNN_TRACK_WEAK_VERSION; }
@@ -362,6 +381,10 @@ extern "C" int frcnn_track_weak_version(void) { return FRCNN_TRACK_WEAK_VERSION;
 extern "C" int frcnn_track_update_weak(int32_t* state, int capacity, const int32_t* det_packed, long long det_stride, int frames,
                                        const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold,
                                        int grow, int h, int w, float strong, int32_t* out, long long out_stride, void* stream) {
-    return track_update_call("track_update_weak", state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr,
-                             hold, grow, h, w, &strong, out, out_stride, stream);
+    TrackCall c{};
+    c.form = TRACK_PLAIN; c.state = state; c.capacity = capacity; c.det_packed = det_packed; c.det_stride = det_stride; c.frames = frames;
+    c.n_frames = n_frames; c.max_rows = max_rows; c.tracked = tracked; c.num_classes = num_classes; c.thr = thr; c.hold = hold; c.grow = grow;
+    c.interval = 1; c.h = h; c.w = w; c.strong = &strong; c.out = out; c.out_stride = out_stride;
+    const int bad = track_call_check("track_update_weak", c);
+    return bad ? bad : track_walk("track_update_weak", c, as_stream(stream));
 }

@@ -3,18 +3,17 @@
 // distance there is are a cut.  A call clears its workspace (k_cut_clear), builds the signatures of the kept frame and of every frame
 // (k_cut_signatures: a workgroup per row band of a frame, each wave counting whole rows into a histogram of its own in LDS with integer LDS
 // atomics; the workgroup's sums go out with integer global atomics, so the result does not depend on any order), decides (k_cut_decide: a
-// workgroup per frame; the reference of frame 0 is read from the motion state's header here) and then walks its frames exactly as
-// csrc/track_interval.hip does, with k_cut_apply in front of each frame's search: it frees the slots where cuts[f] is set, and the search,
-// which returns behind n_slots, the tracker's kernel and the between-frame kernel are the interval form's, unchanged.
+// workgroup per frame; the reference of frame 0 is read from the motion state's header here) and then hands its frames to the one walk
+// every form has (csrc/track.hip's track_walk, csrc/track_call.h), which puts k_cut_apply in front of each frame's search: it frees the
+// slots where cuts[f] is set, and the search, which returns behind n_slots, the tracker's kernel and the between-frame kernel are the
+// interval form's, unchanged.
 #include "common.h"
 #include "../../include/ext/frcnn_hip_redact.h"
 #include "../../include/ext/frcnn_hip_track.h"
 #include "../../include/ext/frcnn_hip_track_cut.h"
 #include "../../include/ext/frcnn_hip_track_interval.h"
 #include "../../include/ext/frcnn_hip_track_weak.h"
-#include "track.h"
-#include "track_interval.h"
-#include "track_motion.h"
+#include "track_call.h"
 
 namespace frcnn {
 
@@ -104,6 +103,20 @@ __global__ void __launch_bounds__(TC_THREADS) k_cut_apply(int32_t* state, int ca
     for (int i = threadIdx.x; i < 8 * cap; i += TC_THREADS) state[4 + i] = 0;
 }
 
+void cut_apply_launch(const TrackCall& c, int f, hipStream_t stream) {
+    k_cut_apply<<<1, TC_THREADS, 0, stream>>>(c.state, c.capacity, c.cuts, f);
+}
+
+// In front of the walk: cuts[f] of every frame of the call, through the workspace
+static void cut_decide_launch(const TrackCall& c, hipStream_t st) {
+    const int words = (c.frames + 1) * TC_WORDS;
+    k_cut_clear<<<(words + TC_THREADS - 1) / TC_THREADS, TC_THREADS, 0, st>>>(c.workspace, words);
+    const int band = (c.h + TC_BANDS - 1) / TC_BANDS, bands = (c.h + band - 1) / band;
+    k_cut_signatures<<<dim3(bands, c.frames + 1), TC_THREADS, 0, st>>>(c.state, c.motion_state, c.frames_u8, c.frame_stride, c.frames, c.n_frames,
+                                                                       c.h, c.w, band, c.workspace);
+    k_cut_decide<<<c.frames, TC_THREADS, 0, st>>>(c.state, c.motion_state, c.frames, c.n_frames, c.h, c.w, c.pct, c.workspace, c.cuts);
+}
+
 }  // namespace frcnn
 
 using namespace frcnn;
@@ -115,46 +128,19 @@ extern "C" size_t frcnn_track_cut_workspace_bytes(int frames) {
     return (size_t)(frames + 1) * TC_WORDS * sizeof(int32_t);
 }
 
-// frcnn_track_update_cut (strong null) and frcnn_track_update_cut_weak
-static int cut_call(const char* who, int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
-                    const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows, const uint8_t* tracked,
-                    int num_classes, int thr, int hold, int grow, int radius, int interval, int h, int w, const float* strong, int32_t* out,
-                    long long out_stride, int pct, int32_t* workspace, int32_t* cuts, void* stream) {
-    const int bad = interval_check(who, state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames, max_rows,
-                                   tracked, num_classes, thr, hold, grow, radius, interval, h, w, out, out_stride);
-    if (bad) return bad;
-    if (pct < FRCNN_TRACK_CUT_MIN_PCT || pct > FRCNN_TRACK_CUT_MAX_PCT)
-        return fail(FRCNN_E_ARG, "%s: pct=%d not in [%d, %d]", who, pct, FRCNN_TRACK_CUT_MIN_PCT, FRCNN_TRACK_CUT_MAX_PCT);
-    if (!workspace || !cuts) return fail(FRCNN_E_ARG, "%s: null pointer", who);
-    if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(FRCNN_E_ARG, "%s: workspace is not 4-byte aligned", who);
-    if (strong && weak_check(who, *strong)) return FRCNN_E_ARG;
-    hipStream_t st = as_stream(stream);
-    const int words = (frames + 1) * TC_WORDS;
-    k_cut_clear<<<(words + TC_THREADS - 1) / TC_THREADS, TC_THREADS, 0, st>>>(workspace, words);
-    const int band = (h + TC_BANDS - 1) / TC_BANDS, bands = (h + band - 1) / band;
-    k_cut_signatures<<<dim3(bands, frames + 1), TC_THREADS, 0, st>>>(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w, band,
-                                                                     workspace);
-    k_cut_decide<<<frames, TC_THREADS, 0, st>>>(state, motion_state, frames, n_frames, h, w, pct, workspace, cuts);
-    for (int f = 0; f < frames; ++f) {
-        k_cut_apply<<<1, TC_THREADS, 0, st>>>(state, capacity, cuts, f);
-        motion_search_launch(state, capacity, motion_state, frames_u8, frame_stride, f, frames, n_frames, radius, h, w, st);
-        int32_t* o = out + (long long)f * out_stride;
-        if (f % interval == 0)
-            track_launch_at(state, capacity, det_packed + (long long)(f / interval) * det_stride, det_stride, f, 1, frames, n_frames, max_rows,
-                            tracked, num_classes, thr, hold, grow, h, w, o, out_stride, st, strong);
-        else
-            interval_between_launch(state, capacity, f, frames, n_frames, max_rows, grow, h, w, o, st);
-    }
-    motion_keep_launch(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w, st);
-    return check_launch(who);
-}
-
 extern "C" int frcnn_track_update_cut(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
                                       const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
                                       const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h, int w,
                                       int32_t* out, long long out_stride, int pct, int32_t* workspace, int32_t* cuts, void* stream) {
-    return cut_call("track_update_cut", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames, max_rows,
-                    tracked, num_classes, thr, hold, grow, radius, interval, h, w, nullptr, out, out_stride, pct, workspace, cuts, stream);
+    TrackCall c{};
+    c.form = TRACK_CUT; c.state = state; c.capacity = capacity; c.motion_state = motion_state; c.frames_u8 = frames_u8;
+    c.frame_stride = frame_stride; c.det_packed = det_packed; c.det_stride = det_stride; c.frames = frames; c.n_frames = n_frames;
+    c.max_rows = max_rows; c.tracked = tracked; c.num_classes = num_classes; c.thr = thr; c.hold = hold; c.grow = grow; c.radius = radius;
+    c.interval = interval; c.h = h; c.w = w; c.out = out; c.out_stride = out_stride; c.pct = pct; c.workspace = workspace; c.cuts = cuts;
+    const int bad = track_call_check("track_update_cut", c);
+    if (bad) return bad;
+    cut_decide_launch(c, as_stream(stream));
+    return track_walk("track_update_cut", c, as_stream(stream));
 }
 
 extern "C" int frcnn_track_update_cut_weak(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
@@ -162,6 +148,14 @@ extern "C" int frcnn_track_update_cut_weak(int32_t* state, int capacity, uint8_t
                                            const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h,
                                            int w, float strong, int32_t* out, long long out_stride, int pct, int32_t* workspace, int32_t* cuts,
                                            void* stream) {
-    return cut_call("track_update_cut_weak", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames,
-                    max_rows, tracked, num_classes, thr, hold, grow, radius, interval, h, w, &strong, out, out_stride, pct, workspace, cuts, stream);
+    TrackCall c{};
+    c.form = TRACK_CUT; c.state = state; c.capacity = capacity; c.motion_state = motion_state; c.frames_u8 = frames_u8;
+    c.frame_stride = frame_stride; c.det_packed = det_packed; c.det_stride = det_stride; c.frames = frames; c.n_frames = n_frames;
+    c.max_rows = max_rows; c.tracked = tracked; c.num_classes = num_classes; c.thr = thr; c.hold = hold; c.grow = grow; c.radius = radius;
+    c.interval = interval; c.h = h; c.w = w; c.strong = &strong; c.out = out; c.out_stride = out_stride; c.pct = pct; c.workspace = workspace;
+    c.cuts = cuts;
+    const int bad = track_call_check("track_update_cut_weak", c);
+    if (bad) return bad;
+    cut_decide_launch(c, as_stream(stream));
+    return track_walk("track_update_cut_weak", c, as_stream(stream));
 }

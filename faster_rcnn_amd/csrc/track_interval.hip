@@ -1,7 +1,8 @@
 // The detector on every K-th frame of a call, the block match alone in between (include/ext/frcnn_hip_track_interval.h states the rule,
-// DESIGN §8 "Interval rule").  gfx950 (CDNA4) only.  A call walks its frames one by one: csrc/track_motion.hip's search, then on a key
-// frame csrc/track.hip's kernel with that key frame's detections, on a between frame k_interval_between, which writes the frame's tracked
-// buffer from the slots as the search left them and counts the frame; track_motion.hip's keep kernel closes the call.  k_interval_between
+// DESIGN §8 "Interval rule").  gfx950 (CDNA4) only.  csrc/track.hip's track_walk (csrc/track_call.h) walks a call's frames one by one:
+// csrc/track_motion.hip's search, then on a key frame track.hip's kernel with that key frame's detections, on a between frame
+// k_interval_between, defined here, which writes the frame's tracked buffer from the slots as the search left them and counts the frame;
+// track_motion.hip's keep kernel closes the call.  The motion form is this one with interval 1: no frame is a between frame.  k_interval_between
 // is one workgroup with a thread per slot: a row's place is a prefix count of the slots in front of it (a ballot per wave, the waves'
 // counts through LDS), so places do not depend on which thread runs when.  One writer per word; no atomics.
 #include "common.h"
@@ -9,9 +10,7 @@
 #include "../../include/ext/frcnn_hip_track.h"
 #include "../../include/ext/frcnn_hip_track_interval.h"
 #include "../../include/ext/frcnn_hip_track_weak.h"
-#include "track.h"
-#include "track_interval.h"
-#include "track_motion.h"
+#include "track_call.h"
 
 namespace frcnn {
 
@@ -68,24 +67,8 @@ __global__ void __launch_bounds__(TI_THREADS) k_interval_between(int32_t* state,
     }
 }
 
-int interval_check(const char* who, const int32_t* state, int capacity, const uint8_t* motion_state, const uint8_t* frames_u8,
-                   long long frame_stride, const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
-                   const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h, int w,
-                   const int32_t* out, long long out_stride) {
-    if (interval < FRCNN_TRACK_INTERVAL_MIN || interval > FRCNN_TRACK_INTERVAL_MAX)
-        return fail(FRCNN_E_ARG, "%s: interval=%d not in [%d, %d]", who, interval, FRCNN_TRACK_INTERVAL_MIN, FRCNN_TRACK_INTERVAL_MAX);
-    // the packed buffers are one per KEY frame: their distance is read only when the call has more than one of them
-    const long long det_words = 4 + 7LL * max_rows;
-    const bool keys = frames >= 1 && (frames + interval - 1) / interval > 1;
-    int bad = track_check(who, state, capacity, det_packed, keys ? det_stride : det_words, frames, n_frames, max_rows, tracked, num_classes, thr,
-                          hold, grow, h, w, out, out_stride);
-    if (!bad) bad = motion_check(who, motion_state, frames_u8, frame_stride, frames, radius, h, w);
-    return bad;
-}
-
-void interval_between_launch(int32_t* state, int capacity, int f, int total, const int32_t* n_frames, int max_rows, int grow, int h, int w,
-                             int32_t* o, hipStream_t stream) {
-    k_interval_between<<<1, TI_THREADS, 0, stream>>>(state, capacity, f, total, n_frames, max_rows, grow, h, w, o);
+void interval_between_launch(const TrackCall& c, int f, int32_t* out, hipStream_t stream) {
+    k_interval_between<<<1, TI_THREADS, 0, stream>>>(c.state, c.capacity, f, c.frames, c.n_frames, c.max_rows, c.grow, c.h, c.w, out);
 }
 
 }  // namespace frcnn
@@ -94,35 +77,17 @@ using namespace frcnn;
 
 extern "C" int frcnn_track_interval_version(void) { return FRCNN_TRACK_INTERVAL_VERSION; }
 
-// frcnn_track_update_interval (strong null) and frcnn_track_update_interval_weak
-static int interval_call(const char* who, int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
-                         const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
-                         const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h, int w,
-                         const float* strong, int32_t* out, long long out_stride, void* stream) {
-    int bad = interval_check(who, state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames, max_rows,
-                                   tracked, num_classes, thr, hold, grow, radius, interval, h, w, out, out_stride);
-    if (!bad && strong) bad = weak_check(who, *strong);
-    if (bad) return bad;
-    hipStream_t st = as_stream(stream);
-    for (int f = 0; f < frames; ++f) {
-        motion_search_launch(state, capacity, motion_state, frames_u8, frame_stride, f, frames, n_frames, radius, h, w, st);
-        int32_t* o = out + (long long)f * out_stride;
-        if (f % interval == 0)
-            track_launch_at(state, capacity, det_packed + (long long)(f / interval) * det_stride, det_stride, f, 1, frames, n_frames, max_rows,
-                            tracked, num_classes, thr, hold, grow, h, w, o, out_stride, st, strong);
-        else
-            interval_between_launch(state, capacity, f, frames, n_frames, max_rows, grow, h, w, o, st);
-    }
-    motion_keep_launch(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w, st);
-    return check_launch(who);
-}
-
 extern "C" int frcnn_track_update_interval(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
                                            const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
                                            const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int interval, int h,
                                            int w, int32_t* out, long long out_stride, void* stream) {
-    return interval_call("track_update_interval", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames,
-                         max_rows, tracked, num_classes, thr, hold, grow, radius, interval, h, w, nullptr, out, out_stride, stream);
+    TrackCall c{};
+    c.form = TRACK_MOTION; c.state = state; c.capacity = capacity; c.motion_state = motion_state; c.frames_u8 = frames_u8;
+    c.frame_stride = frame_stride; c.det_packed = det_packed; c.det_stride = det_stride; c.frames = frames; c.n_frames = n_frames;
+    c.max_rows = max_rows; c.tracked = tracked; c.num_classes = num_classes; c.thr = thr; c.hold = hold; c.grow = grow; c.radius = radius;
+    c.interval = interval; c.h = h; c.w = w; c.out = out; c.out_stride = out_stride;
+    const int bad = track_call_check("track_update_interval", c);
+    return bad ? bad : track_walk("track_update_interval", c, as_stream(stream));
 }
 
 extern "C" int frcnn_track_update_interval_weak(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8,
@@ -130,6 +95,11 @@ extern "C" int frcnn_track_update_interval_weak(int32_t* state, int capacity, ui
                                                 const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr,
                                                 int hold, int grow, int radius, int interval, int h, int w, float strong, int32_t* out,
                                                 long long out_stride, void* stream) {
-    return interval_call("track_update_interval_weak", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames,
-                         n_frames, max_rows, tracked, num_classes, thr, hold, grow, radius, interval, h, w, &strong, out, out_stride, stream);
+    TrackCall c{};
+    c.form = TRACK_MOTION; c.state = state; c.capacity = capacity; c.motion_state = motion_state; c.frames_u8 = frames_u8;
+    c.frame_stride = frame_stride; c.det_packed = det_packed; c.det_stride = det_stride; c.frames = frames; c.n_frames = n_frames;
+    c.max_rows = max_rows; c.tracked = tracked; c.num_classes = num_classes; c.thr = thr; c.hold = hold; c.grow = grow; c.radius = radius;
+    c.interval = interval; c.h = h; c.w = w; c.strong = &strong; c.out = out; c.out_stride = out_stride;
+    const int bad = track_call_check("track_update_interval_weak", c);
+    return bad ? bad : track_walk("track_update_interval_weak", c, as_stream(stream));
 }

@@ -1,16 +1,15 @@
 // The tracker's slots moved with the pixels under them (include/ext/frcnn_hip_track_motion.h states the rule, DESIGN §8 "Motion rule"): an
 // integer block match per live slot between two frames, in front of csrc/track.hip's steps 1-4.  gfx950 (CDNA4) only.
-// A call walks its frames one by one -- the search of frame f + 1 needs the boxes after frame f --: k_motion_search (one workgroup per
-// slot of the state; one past n_slots, read on the device, returns at once) and then track.hip's kernel on that frame; k_motion_keep
-// closes the call.  The search itself is csrc/track_motion_search.h's (shared with csrc/track_lookback.hip).  One writer per slot word;
-// no atomics.
+// A call's frames are walked one by one by csrc/track.hip's track_walk (csrc/track_call.h) -- the search of frame f + 1 needs the boxes
+// after frame f --: k_motion_search (one workgroup per slot of the state; one past n_slots, read on the device, returns at once) and then
+// track.hip's kernel on that frame; k_motion_keep closes the call.  This file defines the two kernels, their launches and the entries.  The
+// search itself is csrc/track_motion_search.h's (shared with csrc/track_lookback.hip).  One writer per slot word; no atomics.
 #include "common.h"
 #include "../../include/ext/frcnn_hip_redact.h"
 #include "../../include/ext/frcnn_hip_track.h"
 #include "../../include/ext/frcnn_hip_track_motion.h"
 #include "../../include/ext/frcnn_hip_track_weak.h"
-#include "track.h"
-#include "track_motion.h"
+#include "track_call.h"
 #include "track_motion_search.h"
 
 namespace frcnn {
@@ -62,32 +61,15 @@ __global__ void __launch_bounds__(256) k_motion_keep(const int32_t* state, uint8
     }
 }
 
-}  // namespace frcnn
-
-namespace frcnn {
-
-int motion_check(const char* who, const uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride, int frames, int radius, int h,
-                 int w) {
-    if (!motion_state || !frames_u8) return fail(FRCNN_E_ARG, "%s: null pointer", who);
-    if (reinterpret_cast<uintptr_t>(motion_state) & 3) return fail(FRCNN_E_ARG, "%s: motion_state is not 4-byte aligned", who);
-    if (radius < FRCNN_TRACK_MOTION_MIN_RADIUS || radius > FRCNN_TRACK_MOTION_MAX_RADIUS)
-        return fail(FRCNN_E_ARG, "%s: radius=%d not in [%d, %d]", who, radius, FRCNN_TRACK_MOTION_MIN_RADIUS, FRCNN_TRACK_MOTION_MAX_RADIUS);
-    const long long frame_bytes = 3LL * h * w;
-    if (frames > 1 && frame_stride < frame_bytes)
-        return fail(FRCNN_E_ARG, "%s: frame_stride=%lld bytes, a %dx%d frame has %lld", who, frame_stride, h, w, frame_bytes);
-    return FRCNN_OK;
+void motion_search_launch(const TrackCall& c, int f, hipStream_t stream) {
+    k_motion_search<<<c.capacity, TM_THREADS, 0, stream>>>(c.state, c.capacity, c.motion_state, c.frames_u8, c.frame_stride, f, c.frames, c.n_frames,
+                                                           c.radius, c.h, c.w);
 }
 
-void motion_search_launch(int32_t* state, int capacity, const uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride, int f,
-                          int frames, const int32_t* n_frames, int radius, int h, int w, hipStream_t stream) {
-    k_motion_search<<<capacity, TM_THREADS, 0, stream>>>(state, capacity, motion_state, frames_u8, frame_stride, f, frames, n_frames, radius, h, w);
-}
-
-void motion_keep_launch(const int32_t* state, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride, int frames,
-                        const int32_t* n_frames, int h, int w, hipStream_t stream) {
-    const long long frame_bytes = 3LL * h * w;
+void motion_keep_launch(const TrackCall& c, hipStream_t stream) {
+    const long long frame_bytes = 3LL * c.h * c.w;
     const int blocks = (int)((frame_bytes / 16 + 255) / 256 < 1024 ? (frame_bytes / 16 + 255) / 256 : 1024);
-    k_motion_keep<<<blocks < 1 ? 1 : blocks, 256, 0, stream>>>(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w);
+    k_motion_keep<<<blocks < 1 ? 1 : blocks, 256, 0, stream>>>(c.state, c.motion_state, c.frames_u8, c.frame_stride, c.frames, c.n_frames, c.h, c.w);
 }
 
 }  // namespace frcnn
@@ -101,32 +83,17 @@ extern "C" size_t frcnn_track_motion_state_bytes(int h, int w) {
     return TM_HEADER + (size_t)3 * h * w;
 }
 
-// frcnn_track_update_motion (strong null) and frcnn_track_update_motion_weak
-static int motion_call(const char* who, int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
-                       const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows, const uint8_t* tracked,
-                       int num_classes, int thr, int hold, int grow, int radius, int h, int w, const float* strong, int32_t* out,
-                       long long out_stride, void* stream) {
-    int bad = track_check(who, state, capacity, det_packed, det_stride, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow,
-                          h, w, out, out_stride);
-    if (!bad) bad = motion_check(who, motion_state, frames_u8, frame_stride, frames, radius, h, w);
-    if (!bad && strong) bad = weak_check(who, *strong);
-    if (bad) return bad;
-    hipStream_t st = as_stream(stream);
-    for (int f = 0; f < frames; ++f) {
-        motion_search_launch(state, capacity, motion_state, frames_u8, frame_stride, f, frames, n_frames, radius, h, w, st);
-        track_launch(state, capacity, det_packed, det_stride, f, 1, frames, n_frames, max_rows, tracked, num_classes, thr, hold, grow, h, w, out,
-                     out_stride, st, strong);
-    }
-    motion_keep_launch(state, motion_state, frames_u8, frame_stride, frames, n_frames, h, w, st);
-    return check_launch(who);
-}
-
 extern "C" int frcnn_track_update_motion(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8, long long frame_stride,
                                          const int32_t* det_packed, long long det_stride, int frames, const int32_t* n_frames, int max_rows,
                                          const uint8_t* tracked, int num_classes, int thr, int hold, int grow, int radius, int h, int w,
                                          int32_t* out, long long out_stride, void* stream) {
-    return motion_call("track_update_motion", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames, n_frames,
-                       max_rows, tracked, num_classes, thr, hold, grow, radius, h, w, nullptr, out, out_stride, stream);
+    TrackCall c{};
+    c.form = TRACK_MOTION; c.state = state; c.capacity = capacity; c.motion_state = motion_state; c.frames_u8 = frames_u8;
+    c.frame_stride = frame_stride; c.det_packed = det_packed; c.det_stride = det_stride; c.frames = frames; c.n_frames = n_frames;
+    c.max_rows = max_rows; c.tracked = tracked; c.num_classes = num_classes; c.thr = thr; c.hold = hold; c.grow = grow; c.radius = radius;
+    c.interval = 1; c.h = h; c.w = w; c.out = out; c.out_stride = out_stride;
+    const int bad = track_call_check("track_update_motion", c);
+    return bad ? bad : track_walk("track_update_motion", c, as_stream(stream));
 }
 
 extern "C" int frcnn_track_update_motion_weak(int32_t* state, int capacity, uint8_t* motion_state, const uint8_t* frames_u8,
@@ -134,6 +101,11 @@ extern "C" int frcnn_track_update_motion_weak(int32_t* state, int capacity, uint
                                               const int32_t* n_frames, int max_rows, const uint8_t* tracked, int num_classes, int thr, int hold,
                                               int grow, int radius, int h, int w, float strong, int32_t* out, long long out_stride,
                                               void* stream) {
-    return motion_call("track_update_motion_weak", state, capacity, motion_state, frames_u8, frame_stride, det_packed, det_stride, frames,
-                       n_frames, max_rows, tracked, num_classes, thr, hold, grow, radius, h, w, &strong, out, out_stride, stream);
+    TrackCall c{};
+    c.form = TRACK_MOTION; c.state = state; c.capacity = capacity; c.motion_state = motion_state; c.frames_u8 = frames_u8;
+    c.frame_stride = frame_stride; c.det_packed = det_packed; c.det_stride = det_stride; c.frames = frames; c.n_frames = n_frames;
+    c.max_rows = max_rows; c.tracked = tracked; c.num_classes = num_classes; c.thr = thr; c.hold = hold; c.grow = grow; c.radius = radius;
+    c.interval = 1; c.h = h; c.w = w; c.strong = &strong; c.out = out; c.out_stride = out_stride;
+    const int bad = track_call_check("track_update_motion_weak", c);
+    return bad ? bad : track_walk("track_update_motion_weak", c, as_stream(stream));
 }

@@ -1475,16 +1475,20 @@ TRACK_MAX = _lib.TRACK_MAX                     # slots of a state, at most
 TRACK_DEFAULTS = _lib.TRACK_DEFAULTS            # (thr, hold, grow)
 
 
+def _int_option(what, v, lo, hi, default=None, note=""):
+    """(host only) What the tracker's option validators share: ``v`` as an int in lo..hi, None read as ``default``; else ValueError
+    "<what>=<v>: an integer in lo..hi<note>"."""
+    v = default if v is None else v
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError("%s=%r: an integer in %d..%d%s" % (what, v, lo, hi, note))
+    return int(v)
+
+
 def track_option(thr=None, hold=None, grow=None):
     """(host only) (thr, hold, grow) checked, None replaced by the default (30, 8, 0): thr the IoU threshold in percent, 1..100; hold the
     frames a lost track is kept, 0..255; grow the pixels a held box grows by per frame of age, 0..64.  ValueError with the reason."""
-    out = []
-    for name, v, default, (lo, hi) in zip(("thr", "hold", "grow"), (thr, hold, grow), TRACK_DEFAULTS, _lib.TRACK_RANGES):
-        v = default if v is None else v
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-            raise ValueError("track %s=%r: an integer in %d..%d" % (name, v, lo, hi))
-        out.append(int(v))
-    return tuple(out)
+    return tuple(_int_option("track " + name, v, lo, hi, default)
+                 for name, v, default, (lo, hi) in zip(("thr", "hold", "grow"), (thr, hold, grow), TRACK_DEFAULTS, _lib.TRACK_RANGES))
 
 
 def track_state(capacity=64):
@@ -1521,8 +1525,15 @@ def track_rows(det_packed):
     return (int(one.numel()) - 4) // 7
 
 
-def _track_packed(det_packed):
-    """``track_update``'s ``det_packed`` -> (the tensor frame 0 starts at, the frames' distance in words, B, a buffer's words)."""
+def _track_call(who, state, det_packed, n_frames, table, h, w, thr, hold, grow, out, strong, motion=None, radius=None, interval=None,
+                cut=None):
+    """What the four ``track_update*`` functions do, ``who`` being the one that asks: the call prepared, checked and made -- frcnn_<who>,
+    or with a ``strong`` its _weak twin -- with each optional group of the argument list stated once.  ``motion``: (mstate, frames_u8,
+    frame_stride), and ``radius`` with it; ``interval``: not None where ``det_packed`` holds the KEY frames' buffers, B of them for the
+    call's F frames; ``cut``: (pct, cuts, workspace).  ``out``, ``cuts`` and ``workspace`` are allocated here when None.
+    -> (``out``, ``cuts``), ``cuts`` None without ``cut``."""
+    _require_gpu()
+    # the tensor frame 0's packed buffer starts at, the buffers' distance in words, B of them, a buffer's words
     if isinstance(det_packed, (list, tuple)):
         bufs = list(det_packed)
         assert bufs and all(b.is_cuda and b.dtype == torch.int32 and b.dim() == 1 and b.is_contiguous() and b.numel() == bufs[0].numel() for b in bufs)
@@ -1537,28 +1548,43 @@ def _track_packed(det_packed):
         base = det_packed
         B, words = (1, int(base.numel())) if base.dim() == 1 else (int(base.shape[0]), int(base.shape[1]))
         stride = words
-    return base, stride, B, words
-
-
-def _track_update_args(state, n_frames, table, words, frames, out):
-    """What the ``track_update*`` calls check alike: ``state``, ``n_frames``, ``table`` and ``out`` -- allocated here when None,
-    (``frames``, 4 + 8R) int32 -- for packed buffers of ``words`` words -> (the state's capacity, the buffers' rows, R, ``out``)."""
+    mstate, frames_u8, frame_stride = motion if motion is not None else (None, None, None)
+    F = B                                               # the call's frames: one per packed buffer, unless those are the key frames'
+    if interval is not None:                            # -- then ``out`` or ``frames_u8`` says how many, and B has to go with it
+        interval = int(interval)
+        F = int(out.shape[0]) if out is not None else int(frames_u8.shape[0]) if frames_u8.dim() > 1 else B * interval
+        if not _lib.TRACK_INTERVAL[0] <= interval <= _lib.TRACK_INTERVAL[1] or (F + interval - 1) // interval != B:
+            raise _lib.FrcnnError("%s: interval=%d (1..%d) and %d frames do not go with %d key frames' detections"
+                                  % (who, interval, _lib.TRACK_INTERVAL[1], F, B))
+    motion_args = options = cut_args = ()
+    if motion is not None:
+        assert mstate.is_cuda and mstate.dtype == torch.uint8 and mstate.dim() == 1 and mstate.is_contiguous() and mstate.numel() == 16 + 3 * int(h) * int(w)
+        assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
+        assert int(frames_u8.numel()) >= (F - 1) * int(frame_stride) + 3 * int(h) * int(w) and int(frame_stride) >= 0
+        motion_args = (_p(mstate), _p(frames_u8), int(frame_stride))
+        options = (int(radius),) if interval is None else (int(radius), interval)
     assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
     assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
     assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
     cap, rows = track_capacity(state), (words - 4) // 7
     R = rows + cap
     if out is None:
-        out = torch.empty((frames, 4 + 8 * R), dtype=torch.int32, device="cuda")
-    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (frames, 4 + 8 * R)
-    return cap, rows, R, out
-
-
-def _track_motion_args(mstate, frames_u8, frame_stride, frames, h, w):
-    """What the two motion forms check of ``mstate`` and of the ``frames`` source frames in ``frames_u8``."""
-    assert mstate.is_cuda and mstate.dtype == torch.uint8 and mstate.dim() == 1 and mstate.is_contiguous() and mstate.numel() == 16 + 3 * int(h) * int(w)
-    assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
-    assert int(frames_u8.numel()) >= (frames - 1) * int(frame_stride) + 3 * int(h) * int(w) and int(frame_stride) >= 0
+        out = torch.empty((F, 4 + 8 * R), dtype=torch.int32, device="cuda")
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (F, 4 + 8 * R)
+    cuts = None
+    if cut is not None:
+        pct, cuts, workspace = cut
+        if cuts is None:
+            cuts = torch.empty(F, dtype=torch.int32, device="cuda")
+        if workspace is None:
+            workspace = track_cut_workspace(F)
+        assert cuts.is_cuda and cuts.dtype == torch.int32 and cuts.is_contiguous() and cuts.numel() == F
+        assert workspace.is_cuda and workspace.dtype == torch.int32 and workspace.is_contiguous() and workspace.numel() >= 512 * (F + 1)
+        cut_args = (pct, _p(workspace), _p(cuts))
+    name, weak = ("frcnn_" + who, ()) if strong is None else ("frcnn_" + who + "_weak", (float(strong),))
+    _lib.call(name, _p(state), cap, *motion_args, _p(base), int(stride), F, _p(n_frames), rows, _p(table), int(table.numel()),
+              int(thr), int(hold), int(grow), *options, int(h), int(w), *weak, _p(out), 4 + 8 * R, *cut_args, _stream())
+    return out, cuts
 
 
 def track_weak_option(det_threshold=None, low=None, track=True):
@@ -1580,11 +1606,6 @@ def track_weak_option(det_threshold=None, low=None, track=True):
     return T, L
 
 
-def _weak(name, strong):
-    """The entry point and the arguments in front of ``out`` for ``strong``: None is the parent call."""
-    return (name, ()) if strong is None else (name + "_weak", (float(strong),))
-
-
 def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, out=None, strong=None):
     """The tracking rule (DESIGN §8 "Tracking rule", frcnn_track_update) over the frames of ``det_packed`` IN ORDER, in one launch:
     ``state`` (``track_state``) is read and advanced, and frame f's tracked buffer lands in ``out[f]`` -- -> ``out``, a (B, 4 + 8R) int32
@@ -1596,13 +1617,7 @@ def track_update(state, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=
     ``strong``: None, or a float for the Weak rule (DESIGN §8 "Weak rule", frcnn_track_update_weak; the same argument of the three forms
     below): a row with a score under it may only continue a track that no other row continued, and is dropped from the live part otherwise,
     so n_live <= *n_dets.  Reads *n_dets and *n_frames on the device: the call can be captured in a graph."""
-    _require_gpu()
-    base, stride, B, words = _track_packed(det_packed)
-    cap, rows, R, out = _track_update_args(state, n_frames, table, words, B, out)
-    name, weak = _weak("frcnn_track_update", strong)
-    _lib.call(name, _p(state), cap, _p(base), int(stride), B, _p(n_frames), rows, _p(table), int(table.numel()),
-              int(thr), int(hold), int(grow), int(h), int(w), *weak, _p(out), 4 + 8 * R, _stream())
-    return out
+    return _track_call("track_update", state, det_packed, n_frames, table, h, w, thr, hold, grow, out, strong)[0]
 
 
 TRACK_MOTION_RADIUS = _lib.TRACK_MOTION_RADIUS  # (smallest, largest, the default) search radius of ``track_update_motion``
@@ -1611,11 +1626,7 @@ TRACK_MOTION_RADIUS = _lib.TRACK_MOTION_RADIUS  # (smallest, largest, the defaul
 def track_motion_radius(r=None):
     """(host only) The block match's search radius checked, None replaced by the default 8: an integer in 1..16.  ValueError with the
     reason."""
-    lo, hi, default = TRACK_MOTION_RADIUS
-    r = default if r is None else r
-    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not lo <= int(r) <= hi:
-        raise ValueError("track motion radius=%r: an integer in %d..%d" % (r, lo, hi))
-    return int(r)
+    return _int_option("track motion radius", r, *TRACK_MOTION_RADIUS)
 
 
 def track_motion_state(h, w):
@@ -1642,15 +1653,8 @@ def track_update_motion(state, mstate, frames_u8, frame_stride, det_packed, n_fr
     of one call to the next.  ``frames_u8``: a uint8 device tensor that holds frame f of the call, (h, w, 3) in any channel order, at
     byte ``f * frame_stride``; read only.  Everything else, ``out`` and the return value: as ``track_update``.  At most two launches per
     frame and one more per call; reads *n_dets, *n_frames and the slot count on the device: the call can be captured in a graph."""
-    _require_gpu()
-    base, stride, B, words = _track_packed(det_packed)
-    _track_motion_args(mstate, frames_u8, frame_stride, B, h, w)
-    cap, rows, R, out = _track_update_args(state, n_frames, table, words, B, out)
-    name, weak = _weak("frcnn_track_update_motion", strong)
-    _lib.call(name, _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), B, _p(n_frames),
-              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), int(h), int(w), *weak, _p(out), 4 + 8 * R,
-              _stream())
-    return out
+    return _track_call("track_update_motion", state, det_packed, n_frames, table, h, w, thr, hold, grow, out, strong,
+                       motion=(mstate, frames_u8, frame_stride), radius=radius)[0]
 
 
 TRACK_INTERVAL = _lib.TRACK_INTERVAL            # (smallest, largest) interval of ``track_update_interval``; the public option starts at 2
@@ -1659,9 +1663,7 @@ TRACK_INTERVAL = _lib.TRACK_INTERVAL            # (smallest, largest) interval o
 def track_interval_option(k):
     """(host only) ``detect_every`` checked: an integer in 2..16, the frames from one detected frame to the next (1 is plain tracking and
     exists at the ABI only).  ValueError with the reason."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= int(k) <= TRACK_INTERVAL[1]:
-        raise ValueError("detect every=%r: an integer in 2..%d (the frames from one detected frame to the next)" % (k, TRACK_INTERVAL[1]))
-    return int(k)
+    return _int_option("detect every", k, 2, TRACK_INTERVAL[1], note=" (the frames from one detected frame to the next)")
 
 
 def track_update_interval(state, mstate, frames_u8, frame_stride, det_packed, n_frames, table, h, w, thr=30, hold=8, grow=0, radius=8, interval=1,
@@ -1673,20 +1675,8 @@ def track_update_interval(state, mstate, frames_u8, frame_stride, det_packed, n_
     frame moves every slot by the block match and writes the slots of age 0 as live rows (their moved boxes) and the held ones behind them:
     no match, no ageing, no births, so ``hold`` counts key frames.  ``n_frames``: how many of the F frames are real.  -> ``out``.  At most
     two launches per frame and one more per call; the call can be captured in a graph."""
-    _require_gpu()
-    base, stride, B, words = _track_packed(det_packed)
-    interval = int(interval)
-    F = int(out.shape[0]) if out is not None else int(frames_u8.shape[0]) if frames_u8.dim() > 1 else B * interval
-    if not _lib.TRACK_INTERVAL[0] <= interval <= _lib.TRACK_INTERVAL[1] or (F + interval - 1) // interval != B:
-        raise _lib.FrcnnError("track_update_interval: interval=%d (1..%d) and %d frames do not go with %d key frames' detections"
-                              % (interval, _lib.TRACK_INTERVAL[1], F, B))
-    _track_motion_args(mstate, frames_u8, frame_stride, F, h, w)
-    cap, rows, R, out = _track_update_args(state, n_frames, table, words, F, out)
-    name, weak = _weak("frcnn_track_update_interval", strong)
-    _lib.call(name, _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), F, _p(n_frames),
-              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), interval, int(h), int(w), *weak, _p(out),
-              4 + 8 * R, _stream())
-    return out
+    return _track_call("track_update_interval", state, det_packed, n_frames, table, h, w, thr, hold, grow, out, strong,
+                       motion=(mstate, frames_u8, frame_stride), radius=radius, interval=interval)[0]
 
 
 TRACK_CUT_PCT = _lib.TRACK_CUT_PCT              # (smallest, largest, the default) threshold of ``track_update_cut``, in percent
@@ -1696,11 +1686,7 @@ def track_cut_option(pct=None):
     """(host only) The scene-cut threshold checked, None replaced by the default 40: an integer in 1..100, the share of the largest
     distance two frames' signatures can have at which the later frame is a cut.  The default is PROVISIONAL: no threshold has been
     measured on real footage.  ValueError with the reason."""
-    lo, hi, default = TRACK_CUT_PCT
-    pct = default if pct is None else pct
-    if isinstance(pct, bool) or not isinstance(pct, (int, np.integer)) or not lo <= int(pct) <= hi:
-        raise ValueError("track scene cut=%r: an integer in %d..%d (percent)" % (pct, lo, hi))
-    return int(pct)
+    return _int_option("track scene cut", pct, *TRACK_CUT_PCT, note=" (percent)")
 
 
 def track_cut_workspace(frames):
@@ -1723,26 +1709,9 @@ def track_update_cut(state, mstate, frames_u8, frame_stride, det_packed, n_frame
     a captured call passes them).  Everything else as ``track_update_interval``.  -> (``out``, ``cuts``).  With no cut every byte of
     ``state``, ``mstate`` and ``out`` is ``track_update_interval``'s.  Four launches per call and one per frame on top of those; the
     call can be captured in a graph."""
-    _require_gpu()
-    base, stride, B, words = _track_packed(det_packed)
-    interval, pct = int(interval), track_cut_option(pct) if pct is None else int(pct)
-    F = int(out.shape[0]) if out is not None else int(frames_u8.shape[0]) if frames_u8.dim() > 1 else B * interval
-    if not _lib.TRACK_INTERVAL[0] <= interval <= _lib.TRACK_INTERVAL[1] or (F + interval - 1) // interval != B:
-        raise _lib.FrcnnError("track_update_cut: interval=%d (1..%d) and %d frames do not go with %d key frames' detections"
-                              % (interval, _lib.TRACK_INTERVAL[1], F, B))
-    _track_motion_args(mstate, frames_u8, frame_stride, F, h, w)
-    cap, rows, R, out = _track_update_args(state, n_frames, table, words, F, out)
-    if cuts is None:
-        cuts = torch.empty(F, dtype=torch.int32, device="cuda")
-    if workspace is None:
-        workspace = track_cut_workspace(F)
-    assert cuts.is_cuda and cuts.dtype == torch.int32 and cuts.is_contiguous() and cuts.numel() == F
-    assert workspace.is_cuda and workspace.dtype == torch.int32 and workspace.is_contiguous() and workspace.numel() >= 512 * (F + 1)
-    name, weak = _weak("frcnn_track_update_cut", strong)
-    _lib.call(name, _p(state), cap, _p(mstate), _p(frames_u8), int(frame_stride), _p(base), int(stride), F, _p(n_frames),
-              rows, _p(table), int(table.numel()), int(thr), int(hold), int(grow), int(radius), interval, int(h), int(w), *weak, _p(out),
-              4 + 8 * R, pct, _p(workspace), _p(cuts), _stream())
-    return out, cuts
+    pct = track_cut_option(pct) if pct is None else int(pct)
+    return _track_call("track_update_cut", state, det_packed, n_frames, table, h, w, thr, hold, grow, out, strong,
+                       motion=(mstate, frames_u8, frame_stride), radius=radius, interval=interval, cut=(pct, cuts, workspace))
 
 
 TRACK_TRAILS = _lib.TRACK_TRAILS                # ((smallest, largest, default) length N, the same of the width W, the largest expire)
