@@ -1326,7 +1326,7 @@ def annotate_u8(frame, det_packed, tables, ids=None, tracked=False):
     id behind the class name (frcnn_annotate_ids_u8); None: the call and its output are what they were.
     ``tracked`` True: ``det_packed`` is one tracked buffer of ``track_update`` instead; its LIVE rows are drawn, with their ids."""
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    _frame_u8(frame)
     assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.is_contiguous()
     labels = tables["labels"]
     if tracked:
@@ -1403,13 +1403,12 @@ def redact_u8(frame, det_packed, table, mode="pixelate", size=None, margin=0, wo
     call can be captured in a graph.  ``tracked`` True: ``det_packed`` is one tracked buffer of ``track_update`` instead, and the boxes
     are all its rows, the held ones included."""
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    h, w = _frame_u8(frame)
     assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.is_contiguous()
     assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
     if mode not in _lib.REDACT_MODES:
         raise ValueError("redact mode %r: one of %s" % (mode, ", ".join(REDACT_MODES)))
     size = REDACT_SIZES[mode][2] if size is None else int(size)            # (the range is the library's to check)
-    h, w = int(frame.shape[0]), int(frame.shape[1])
     if workspace is None:
         workspace = _ws(_lib.load().frcnn_redact_ws_bytes(h, w, _lib.REDACT_MODES[mode], size))
     assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
@@ -1447,7 +1446,7 @@ def redact_shaped_u8(frame, det_packed, table, mode="pixelate", size=None, margi
     winning.  ("box", 0) gives ``redact_u8``'s bytes.  Every other argument, the workspace (``redact_ws_bytes``) and the return are
     ``redact_u8``'s; the shape and the feather range are the library's to check."""
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    h, w = _frame_u8(frame)
     assert det_packed.is_cuda and det_packed.dtype == torch.int32 and det_packed.is_contiguous()
     assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
     if mode not in _lib.REDACT_MODES:
@@ -1455,7 +1454,6 @@ def redact_shaped_u8(frame, det_packed, table, mode="pixelate", size=None, margi
     if shape not in _lib.REDACT_SHAPES:
         raise ValueError("redact shape %r: one of %s" % (shape, ", ".join(REDACT_SHAPES)))
     size = REDACT_SIZES[mode][2] if size is None else int(size)            # (the range is the library's to check)
-    h, w = int(frame.shape[0]), int(frame.shape[1])
     if workspace is None:
         workspace = _ws(_lib.load().frcnn_redact_ws_bytes(h, w, _lib.REDACT_MODES[mode], size))
     assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
@@ -1482,6 +1480,41 @@ def _int_option(what, v, lo, hi, default=None, note=""):
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
         raise ValueError("%s=%r: an integer in %d..%d%s" % (what, v, lo, hi, note))
     return int(v)
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _width_option(what, v, spec):
+    """(host only) The width something is drawn with, ``spec`` its (smallest, largest, default)."""
+    lo, hi, default = spec
+    return _int_option(what, v, lo, hi, default, " (pixels)")
+
+
+def _classes_option(what, classes, none_is_all, empty_ok=False):
+    """(host only) The classes of an option checked -> "all" or a tuple of class names (which names there are is the caller's to check:
+    ``redact_class_list``).  ``classes``: "all", one name or a list of names; None reads as "all" with ``none_is_all`` and is refused
+    without.  ``empty_ok``: no name at all is a value too, and a refusal shows ``classes`` as given, not as a tuple.  ValueError
+    "<what>=<classes>: ..." with the reason."""
+    given = classes
+    if classes is None and none_is_all:
+        classes = "all"
+    if isinstance(classes, str):
+        classes = (classes,)
+    try:
+        classes = tuple(classes)
+    except TypeError:
+        raise ValueError("%s=%r: \"all\", a class name or a list of class names" % (what, given)) from None
+    if not (classes or empty_ok) or not all(isinstance(c, str) and c for c in classes):
+        raise ValueError("%s=%r: \"all\", a class name or a list of class names" % (what, given if empty_ok else classes))
+    return "all" if classes == ("all",) else classes
+
+
+def _frame_u8(frame):
+    """What the calls that edit a frame in place take: an (h, w, 3) uint8 device tensor, contiguous -> (h, w)."""
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    return int(frame.shape[0]), int(frame.shape[1])
 
 
 def track_option(thr=None, hold=None, grow=None):
@@ -1714,25 +1747,57 @@ def track_update_cut(state, mstate, frames_u8, frame_stride, det_packed, n_frame
                        motion=(mstate, frames_u8, frame_stride), radius=radius, interval=interval, cut=(pct, cuts, workspace))
 
 
+def _id_update_args(state, tracked, n_frames, gate, table=None):
+    """What ``track_trails_update``, ``count_update`` and ``zone_update`` take alike, checked -> (frames, words of a tracked buffer, its
+    rows): the state, the (frames, 4 + 8 rows) tracked buffers, the device words ``n_frames`` and ``gate`` (or None), a class table."""
+    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
+    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.dim() == 2 and tracked.is_contiguous()
+    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
+    assert gate is None or (gate.is_cuda and gate.dtype == torch.int32 and gate.numel() >= 1)
+    assert table is None or (table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous())
+    frames, words = int(tracked.shape[0]), int(tracked.shape[1])
+    assert (words - 4) % 8 == 0
+    return frames, words, (words - 4) // 8
+
+
+def _lists_workspace(who, frames, words):
+    """The lists of one of those calls of ``frames`` frames: an int32 device tensor (frames, ``words``) that every call writes whole."""
+    _require_gpu()
+    if not 1 <= int(frames) <= _lib.TRACK_MAX_FRAMES:
+        raise _lib.FrcnnError("%s: frames=%r out of range (1..%d)" % (who, frames, _lib.TRACK_MAX_FRAMES))
+    return torch.empty((int(frames), int(words)), dtype=torch.int32, device="cuda")
+
+
+def _lists_arg(lists, frames, words):
+    assert lists.is_cuda and lists.dtype == torch.int32 and lists.is_contiguous() and tuple(lists.shape) == (frames, words)
+    return lists
+
+
+def _reset_keeping_totals(state, head, keep_totals):
+    """Empty a count or zone state (on the current stream); ``keep_totals``: only the count of entries and the entries behind the
+    ``head`` words are zeroed."""
+    if keep_totals:
+        state[0:1].zero_()
+        state[head:].zero_()
+    else:
+        state.zero_()
+    return state
+
+
 TRACK_TRAILS = _lib.TRACK_TRAILS                # ((smallest, largest, default) length N, the same of the width W, the largest expire)
 
 
 def track_trails_option(value=None):
     """(host only) The trail option checked -> (N, W): N the points a trail keeps, 2..64, W the width it is drawn with, 1..9.  ``value``:
     None (the defaults, 16 and 3), an integer N, or a pair (N, W) either of which may be None.  ValueError with the reason."""
-    (n_lo, n_hi, n_def), (w_lo, w_hi, w_def), _ = TRACK_TRAILS
+    (n_lo, n_hi, n_def), _, _ = TRACK_TRAILS
     if value is None or isinstance(value, (int, np.integer)):
         value = (value, None)
     try:
         n, wd = value
     except (TypeError, ValueError):
         raise ValueError("track trails=%r: N, or (N, W)" % (value,)) from None
-    n, wd = n_def if n is None else n, w_def if wd is None else wd
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not n_lo <= int(n) <= n_hi:
-        raise ValueError("track trails length=%r: an integer in %d..%d (points)" % (n, n_lo, n_hi))
-    if isinstance(wd, bool) or not isinstance(wd, (int, np.integer)) or not w_lo <= int(wd) <= w_hi:
-        raise ValueError("track trails width=%r: an integer in %d..%d (pixels)" % (wd, w_lo, w_hi))
-    return int(n), int(wd)
+    return _int_option("track trails length", n, n_lo, n_hi, n_def, " (points)"), _width_option("track trails width", wd, TRACK_TRAILS[1])
 
 
 def _track_trails_words(capacity, length):
@@ -1754,10 +1819,7 @@ def track_trails_state(capacity, length):
 def track_trails_workspace(frames, capacity, length):
     """The point lists of a ``track_trails_update`` call of ``frames`` frames: an int32 device tensor (frames, list words), a list
     [n_trails, 0, 0, 0 | per trail: id, cls, n, 0, pts[length][2]].  Every word is written by every call."""
-    _require_gpu()
-    if not 1 <= int(frames) <= _lib.TRACK_MAX_FRAMES:
-        raise _lib.FrcnnError("track_trails_workspace: frames=%r out of range (1..%d)" % (frames, _lib.TRACK_MAX_FRAMES))
-    return torch.empty((int(frames), _track_trails_words(capacity, length)), dtype=torch.int32, device="cuda")
+    return _lists_workspace("track_trails_workspace", frames, _track_trails_words(capacity, length))
 
 
 def track_trails_update(state, tracked, n_frames, length, expire, h, w, capacity=None, lists=None, gate=None):
@@ -1770,20 +1832,15 @@ def track_trails_update(state, tracked, n_frames, length, expire, h, w, capacity
     whatever ``n_frames`` says (a pass whose ``n_frames`` is the count a look-back emitted passes its own frame count: a warm-up
     replay emits the same frames again).  The call can be captured in a graph."""
     _require_gpu()
-    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
-    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.dim() == 2 and tracked.is_contiguous()
-    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
-    assert gate is None or (gate.is_cuda and gate.dtype == torch.int32 and gate.numel() >= 1)
+    frames, words, rows = _id_update_args(state, tracked, n_frames, gate)
     length = int(length)
     if capacity is None:
         capacity = (int(state.numel()) - 4) // (4 + 2 * max(length, 1))
-    frames, words = int(tracked.shape[0]), int(tracked.shape[1])
-    assert (words - 4) % 8 == 0
     if lists is None:
         lists = track_trails_workspace(frames, capacity, length)
     assert int(state.numel()) == _track_trails_words(capacity, length)
-    assert lists.is_cuda and lists.dtype == torch.int32 and lists.is_contiguous() and tuple(lists.shape) == (frames, int(state.numel()))
-    _lib.call("frcnn_track_trails_update", _p(state), int(capacity), _p(tracked), words, (words - 4) // 8, frames, _p(n_frames), _p(gate), length,
+    _lists_arg(lists, frames, int(state.numel()))
+    _lib.call("frcnn_track_trails_update", _p(state), int(capacity), _p(tracked), words, rows, frames, _p(n_frames), _p(gate), length,
               int(expire), int(h), int(w), _p(lists), _stream())
     return lists
 
@@ -1794,12 +1851,11 @@ def track_trails_draw_u8(frame, plist, length, width=None, rgb=False):
     segment, in the colour of the trail's id, the highest id on top.  ``rgb``: the frame's bytes are R, G, B (False: B, G, R, as the
     encoders' ``bgr=True``).  One launch; reads the list's count from device memory, so the call can be captured in a graph."""
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    h, w = _frame_u8(frame)
     assert plist.is_cuda and plist.dtype == torch.int32 and plist.dim() == 1 and plist.is_contiguous()
     length, width = int(length), TRACK_TRAILS[1][2] if width is None else int(width)
     assert int(plist.numel()) >= 4 and (int(plist.numel()) - 4) % (4 + 2 * max(length, 1)) == 0
-    _lib.call("frcnn_track_trails_draw_u8", _p(frame), int(frame.shape[0]), int(frame.shape[1]), _p(plist), length, width, int(bool(rgb)),
-              _stream())
+    _lib.call("frcnn_track_trails_draw_u8", _p(frame), h, w, _p(plist), length, width, int(bool(rgb)), _stream())
     return frame
 
 
@@ -1812,15 +1868,7 @@ def heat_option(classes, alpha=None, decay=None):
     """(host only) The heat-map option checked -> (classes, A, S): classes "all" or a tuple of class names (which names there are is the
     caller's to check: ``redact_class_list``), A the blend weight of the hottest pixel, 1..255 (None: 160), S the decay, 0..15 (None: 0,
     none): every frame takes ceil(v / 2^S) off every pixel.  ValueError with the reason."""
-    if isinstance(classes, str):
-        classes = (classes,)
-    try:
-        classes = tuple(classes)
-    except TypeError:
-        raise ValueError("heat classes=%r: \"all\", a class name or a list of class names" % (classes,)) from None
-    if not classes or not all(isinstance(c, str) and c for c in classes):
-        raise ValueError("heat classes=%r: \"all\", a class name or a list of class names" % (classes,))
-    classes = "all" if classes == ("all",) else classes
+    classes = _classes_option("heat classes", classes, False)
     out = []
     for name, v, (lo, hi, default) in (("alpha", alpha, HEAT_ALPHA), ("decay", decay, HEAT_DECAY)):
         v = default if v is None else v
@@ -1897,9 +1945,8 @@ def heat_draw_u8(frame, state, alpha=None, rgb=False):
     (``alpha`` * t) // 255 (None: 160); a cold map writes nothing.  ``rgb``: the frame's bytes are R, G, B (False: B, G, R, as the
     encoders' ``bgr=True``).  One launch; reads ``peak`` from device memory, so the call can be captured in a graph."""
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    h, w = _frame_u8(frame)
     assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
-    h, w = int(frame.shape[0]), int(frame.shape[1])
     assert int(state.numel()) == heat_state_words(h, w)
     _lib.call("frcnn_heat_draw_u8", _p(frame), h, w, _p(state), HEAT_ALPHA[2] if alpha is None else int(alpha), int(bool(rgb)), _stream())
     return frame
@@ -1932,22 +1979,7 @@ def count_option(lines, classes="all", width=None):
         if (int(ln[0]), int(ln[1])) == (int(ln[2]), int(ln[3])):
             raise ValueError("count line %r: A = B is a point, not a line" % (ln,))
     lines = tuple(tuple(int(v) for v in ln) for ln in lines)
-    if classes is None:
-        classes = "all"
-    if isinstance(classes, str):
-        classes = (classes,)
-    try:
-        classes = tuple(classes)
-    except TypeError:
-        raise ValueError("count classes=%r: \"all\", a class name or a list of class names" % (classes,)) from None
-    if not classes or not all(isinstance(c, str) and c for c in classes):
-        raise ValueError("count classes=%r: \"all\", a class name or a list of class names" % (classes,))
-    classes = "all" if classes == ("all",) else classes
-    w_lo, w_hi, w_def = COUNT_WIDTH
-    width = w_def if width is None else width
-    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or not w_lo <= int(width) <= w_hi:
-        raise ValueError("count width=%r: an integer in %d..%d (pixels)" % (width, w_lo, w_hi))
-    return lines, classes, int(width)
+    return lines, _classes_option("count classes", classes, True), _width_option("count width", width, COUNT_WIDTH)
 
 
 def _count_lines_arg(lines):
@@ -1975,22 +2007,15 @@ def count_state(capacity):
 def count_reset(state, keep_totals=False):
     """Empty the state (on the current stream): no entries, no frames, totals 0.  ``keep_totals``: only the entries leave -- the ids end,
     what was counted stays counted (``frames``, the sticky sums and the totals are kept)."""
-    if keep_totals:
-        state[0:1].zero_()
-        state[COUNT_HEAD:].zero_()
-    else:
-        state.zero_()
-    return state
+    return _reset_keeping_totals(state, COUNT_HEAD, keep_totals)
 
 
 def count_workspace(frames):
     """The count lists of a ``count_update`` call of ``frames`` frames: an int32 device tensor (frames, COUNT_LIST_WORDS).  Every word is
     written by every call."""
-    _require_gpu()
-    if not 1 <= int(frames) <= _lib.TRACK_MAX_FRAMES:
-        raise _lib.FrcnnError("count_workspace: frames=%r out of range (1..%d)" % (frames, _lib.TRACK_MAX_FRAMES))
+    lists = _lists_workspace("count_workspace", frames, COUNT_LIST_WORDS)
     assert int(_lib.load().frcnn_count_list_words()) == COUNT_LIST_WORDS
-    return torch.empty((int(frames), COUNT_LIST_WORDS), dtype=torch.int32, device="cuda")
+    return lists
 
 
 def count_update(state, tracked, n_frames, lines, table, expire, h, w, capacity=None, lists=None, gate=None):
@@ -2003,21 +2028,15 @@ def count_update(state, tracked, n_frames, lines, table, expire, h, w, capacity=
     lands in ``lists[f]`` (``count_workspace``; allocated here when None; a captured call passes it) -> ``lists``.  ``gate``: None, or a
     device word that is 0 when no frame of the call is real, whatever ``n_frames`` says.  The call can be captured in a graph."""
     _require_gpu()
-    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
-    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.dim() == 2 and tracked.is_contiguous()
-    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
-    assert gate is None or (gate.is_cuda and gate.dtype == torch.int32 and gate.numel() >= 1)
-    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    frames, words, rows = _id_update_args(state, tracked, n_frames, gate, table)
     if capacity is None:
         capacity = (int(state.numel()) - COUNT_HEAD) // COUNT_ENTRY
-    frames, words = int(tracked.shape[0]), int(tracked.shape[1])
-    assert (words - 4) % 8 == 0
     if lists is None:
         lists = count_workspace(frames)
     assert int(state.numel()) == count_state_words(capacity)
-    assert lists.is_cuda and lists.dtype == torch.int32 and lists.is_contiguous() and tuple(lists.shape) == (frames, COUNT_LIST_WORDS)
+    _lists_arg(lists, frames, COUNT_LIST_WORDS)
     keep, lines_p, n_lines = _count_lines_arg(lines)
-    _lib.call("frcnn_count_update", _p(state), int(capacity), _p(tracked), words, (words - 4) // 8, frames, _p(n_frames), _p(gate), lines_p,
+    _lib.call("frcnn_count_update", _p(state), int(capacity), _p(tracked), words, rows, frames, _p(n_frames), _p(gate), lines_p,
               n_lines, _p(table), int(table.numel()), int(expire), int(h), int(w), _p(lists), _stream())
     return lists
 
@@ -2029,10 +2048,10 @@ def count_draw_u8(frame, clist, lines, width=None, rgb=False):
     draws nothing.  ``rgb``: the frame's bytes are R, G, B (False: B, G, R).  One launch; the list is read on the device, so the call can
     be captured in a graph."""
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    h, w = _frame_u8(frame)
     assert clist.is_cuda and clist.dtype == torch.int32 and clist.dim() == 1 and clist.is_contiguous() and int(clist.numel()) == COUNT_LIST_WORDS
     keep, lines_p, n_lines = _count_lines_arg(lines)
-    _lib.call("frcnn_count_draw_u8", _p(frame), int(frame.shape[0]), int(frame.shape[1]), _p(clist), lines_p, n_lines,
+    _lib.call("frcnn_count_draw_u8", _p(frame), h, w, _p(clist), lines_p, n_lines,
               COUNT_WIDTH[2] if width is None else int(width), int(bool(rgb)), _stream())
     return frame
 
@@ -2059,10 +2078,6 @@ ZONE_KINDS = ("exit", "enter", "lost")          # index = an event's kind
 # words of a zone list: [n_events, frames, 0, 0 | occupancy[8] | visitors[8] | stays[8] | dwell[8] | peak[8] | events[64][5]]; of a
 # state in front of its entries; of an entry; of a list in front of its events
 ZONE_LIST_WORDS, ZONE_HEAD, ZONE_ENTRY, ZONE_LIST_HEAD = _lib.ZONE_LIST_WORDS, _lib.ZONE_HEAD_WORDS, _lib.ZONE_ENTRY_WORDS, 4 + 5 * _lib.ZONE_MAX_ZONES
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
 
 
 def zone_option(zones, classes="all", width=None, anchor=None):
@@ -2099,27 +2114,13 @@ def zone_option(zones, classes="all", width=None, anchor=None):
             if (int(p[0]), int(p[1])) == (int(q[0]), int(q[1])):
                 raise ValueError("zone %r: two consecutive vertices at (%d, %d)" % (zn, p[0], p[1]))
     polys = tuple(tuple((int(x), int(y)) for x, y in zn) for zn in polys)
-    if classes is None:
-        classes = "all"
-    if isinstance(classes, str):
-        classes = (classes,)
-    try:
-        classes = tuple(classes)
-    except TypeError:
-        raise ValueError("zone classes=%r: \"all\", a class name or a list of class names" % (classes,)) from None
-    if not classes or not all(isinstance(c, str) and c for c in classes):
-        raise ValueError("zone classes=%r: \"all\", a class name or a list of class names" % (classes,))
-    classes = "all" if classes == ("all",) else classes
-    w_lo, w_hi, w_def = ZONE_WIDTH
-    width = w_def if width is None else width
-    if not _is_int(width) or not w_lo <= int(width) <= w_hi:
-        raise ValueError("zone width=%r: an integer in %d..%d (pixels)" % (width, w_lo, w_hi))
+    classes, width = _classes_option("zone classes", classes, True), _width_option("zone width", width, ZONE_WIDTH)
     anchor = 0 if anchor is None else anchor
     if isinstance(anchor, str):
         anchor = {"centre": 0, "center": 0, "bottom": 1}.get(anchor, anchor)
     if not _is_int(anchor) or int(anchor) not in (0, 1):
         raise ValueError("zone anchor=%r: \"centre\" or \"bottom\"" % (anchor,))
-    return polys, classes, int(width), int(anchor)
+    return polys, classes, width, int(anchor)
 
 
 def _zone_verts_arg(zones):
@@ -2150,22 +2151,15 @@ def zone_state(capacity):
 def zone_reset(state, keep_totals=False):
     """Empty the state (on the current stream): no entries, no frames, totals 0.  ``keep_totals``: only the entries leave -- the ids end
     without an event, their open stays are not counted, and ``frames``, the sticky sums, visitors, stays, dwell and peak are kept."""
-    if keep_totals:
-        state[0:1].zero_()
-        state[ZONE_HEAD:].zero_()
-    else:
-        state.zero_()
-    return state
+    return _reset_keeping_totals(state, ZONE_HEAD, keep_totals)
 
 
 def zone_workspace(frames):
     """The zone lists of a ``zone_update`` call of ``frames`` frames: an int32 device tensor (frames, ZONE_LIST_WORDS).  Every word is
     written by every call."""
-    _require_gpu()
-    if not 1 <= int(frames) <= _lib.TRACK_MAX_FRAMES:
-        raise _lib.FrcnnError("zone_workspace: frames=%r out of range (1..%d)" % (frames, _lib.TRACK_MAX_FRAMES))
+    lists = _lists_workspace("zone_workspace", frames, ZONE_LIST_WORDS)
     assert int(_lib.load().frcnn_zone_list_words()) == ZONE_LIST_WORDS
-    return torch.empty((int(frames), ZONE_LIST_WORDS), dtype=torch.int32, device="cuda")
+    return lists
 
 
 def zone_update(state, tracked, n_frames, zones, table, expire, h, w, anchor=0, capacity=None, lists=None, gate=None):
@@ -2178,21 +2172,15 @@ def zone_update(state, tracked, n_frames, zones, table, expire, h, w, anchor=0, 
     here when None; a captured call passes it) -> ``lists``.  ``gate``: None, or a device word that is 0 when no frame of the call is
     real, whatever ``n_frames`` says.  The call can be captured in a graph."""
     _require_gpu()
-    assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
-    assert tracked.is_cuda and tracked.dtype == torch.int32 and tracked.dim() == 2 and tracked.is_contiguous()
-    assert n_frames.is_cuda and n_frames.dtype == torch.int32 and n_frames.numel() >= 1
-    assert gate is None or (gate.is_cuda and gate.dtype == torch.int32 and gate.numel() >= 1)
-    assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
+    frames, words, rows = _id_update_args(state, tracked, n_frames, gate, table)
     if capacity is None:
         capacity = (int(state.numel()) - ZONE_HEAD) // ZONE_ENTRY
-    frames, words = int(tracked.shape[0]), int(tracked.shape[1])
-    assert (words - 4) % 8 == 0
     if lists is None:
         lists = zone_workspace(frames)
     assert int(state.numel()) == zone_state_words(capacity)
-    assert lists.is_cuda and lists.dtype == torch.int32 and lists.is_contiguous() and tuple(lists.shape) == (frames, ZONE_LIST_WORDS)
+    _lists_arg(lists, frames, ZONE_LIST_WORDS)
     keep, verts_p, nv_p, n_zones = _zone_verts_arg(zones)           # (``keep`` owns the host arrays the two pointers point into: alive over the call)
-    _lib.call("frcnn_zone_update", _p(state), int(capacity), _p(tracked), words, (words - 4) // 8, frames, _p(n_frames), _p(gate), verts_p, nv_p,
+    _lib.call("frcnn_zone_update", _p(state), int(capacity), _p(tracked), words, rows, frames, _p(n_frames), _p(gate), verts_p, nv_p,
               n_zones, _p(table), int(table.numel()), int(anchor), int(expire), int(h), int(w), _p(lists), _stream())
     return lists
 
@@ -2204,10 +2192,10 @@ def zone_draw_u8(frame, zlist, zones, width=None, rgb=False):
     list of a frame that is not real draws nothing.  ``rgb``: the frame's bytes are R, G, B (False: B, G, R).  One launch; the list is
     read on the device, so the call can be captured in a graph."""
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    h, w = _frame_u8(frame)
     assert zlist.is_cuda and zlist.dtype == torch.int32 and zlist.dim() == 1 and zlist.is_contiguous() and int(zlist.numel()) == ZONE_LIST_WORDS
     keep, verts_p, nv_p, n_zones = _zone_verts_arg(zones)           # (``keep`` owns the host arrays the two pointers point into: alive over the call)
-    _lib.call("frcnn_zone_draw_u8", _p(frame), int(frame.shape[0]), int(frame.shape[1]), _p(zlist), verts_p, nv_p, n_zones,
+    _lib.call("frcnn_zone_draw_u8", _p(frame), h, w, _p(zlist), verts_p, nv_p, n_zones,
               ZONE_WIDTH[2] if width is None else int(width), int(bool(rgb)), _stream())
     return frame
 
@@ -2341,12 +2329,11 @@ def redact_region_plane(h, w, option, out=None):
 
 def _region_call(name, frame, plane, mode, size, workspace):
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    h, w = _frame_u8(frame)
     assert plane.is_cuda and plane.dtype == torch.uint8 and plane.dim() == 1 and plane.is_contiguous()
     if mode not in _lib.REDACT_MODES:
         raise ValueError("redact region mode %r: one of %s" % (mode, ", ".join(REDACT_MODES)))
     size = REDACT_SIZES[mode][2] if size is None else int(size)            # (the range is the library's to check)
-    h, w = int(frame.shape[0]), int(frame.shape[1])
     if workspace is None:
         workspace = _ws(_lib.load().frcnn_redact_ws_bytes(h, w, _lib.REDACT_MODES[mode], size))
     assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
@@ -2398,15 +2385,7 @@ def plate_option(classes, settle=None, tol=None, margin=None):
     caller's to check: ``redact_class_list``), S the frames a pixel must hold still to become background, 1..255 (None: 8), T how far
     a channel may lie from the run's anchor, 0..255 (None: 10), M the pixels a box grows by, 0..64 (None: 8).  The defaults are
     provisional.  ValueError with the reason."""
-    if isinstance(classes, str):
-        classes = (classes,)
-    try:
-        classes = tuple(classes)
-    except TypeError:
-        raise ValueError("remove classes=%r: \"all\", a class name or a list of class names" % (classes,)) from None
-    if not classes or not all(isinstance(c, str) and c for c in classes):
-        raise ValueError("remove classes=%r: \"all\", a class name or a list of class names" % (classes,))
-    classes = "all" if classes == ("all",) else classes
+    classes = _classes_option("remove classes", classes, False)
     out = []
     for name, v, (lo, hi, default) in (("settle", settle, PLATE_SETTLE), ("tol", tol, PLATE_TOL), ("margin", margin, PLATE_MARGIN)):
         v = default if v is None else v
@@ -2476,9 +2455,8 @@ def plate_update(state, frame, det_packed, settle=None, tol=None, margin=None, f
     *gate != 0; else nothing is written.  ``cut``: a device int32 word; non-zero empties the plate in front of the update.  Two
     launches, everything guarded on the device: the call can be captured in a graph -> ``state``."""
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    h, w = _frame_u8(frame)
     assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
-    h, w = int(frame.shape[0]), int(frame.shape[1])
     assert int(state.numel()) == plate_state_words(h, w)
     rows = _plate_rows(det_packed, tracked)
     if n_frames is None:
@@ -2498,10 +2476,9 @@ def plate_fill_u8(frame, state, det_packed, table, margin=None, keep_unknown=Fal
     grown by ``margin``, becomes the plate's where ``state`` knows it; where it does not, black, or with ``keep_unknown`` what it is.
     One launch; reads the counts from device memory, so the call can be captured in a graph."""
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    h, w = _frame_u8(frame)
     assert state.is_cuda and state.dtype == torch.int32 and state.dim() == 1 and state.is_contiguous()
     assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
-    h, w = int(frame.shape[0]), int(frame.shape[1])
     assert int(state.numel()) == plate_state_words(h, w)
     rows = _plate_rows(det_packed, tracked)
     _lib.call("frcnn_plate_fill_u8", _p(frame), h, w, _p(state), _p(det_packed), rows, int(bool(tracked)), _p(table), int(table.numel()),
@@ -2539,16 +2516,7 @@ def redact_moving_option(tol=None, vote=None, hold=None, grow=None, feather=None
     unknown = REDACT_MOVING_UNKNOWN[0] if unknown is None else unknown
     if not isinstance(unknown, str) or unknown not in REDACT_MOVING_UNKNOWN:
         raise ValueError("redact moving unknown=%r: one of %s" % (unknown, ", ".join(REDACT_MOVING_UNKNOWN)))
-    classes = () if except_classes is None else except_classes
-    if isinstance(classes, str):
-        classes = (classes,)
-    try:
-        classes = tuple(classes)
-    except TypeError:
-        raise ValueError("redact moving except_classes=%r: \"all\", a class name or a list of class names" % (except_classes,)) from None
-    if not all(isinstance(c, str) and c for c in classes):
-        raise ValueError("redact moving except_classes=%r: \"all\", a class name or a list of class names" % (except_classes,))
-    classes = "all" if classes == ("all",) else classes
+    classes = _classes_option("redact moving except_classes", () if except_classes is None else except_classes, False, empty_ok=True)
     mode = REDACT_MOVING_MODE if mode is None else mode
     if not isinstance(mode, str) or mode not in _lib.REDACT_MODES:
         raise ValueError("redact moving mode %r: one of %s" % (mode, ", ".join(REDACT_MODES)))
@@ -2651,13 +2619,12 @@ def redact_moving_build(state, plane, stats, frame, plate, det_packed, table, op
     device, [real, cells_now, covered, full].  ``option``: ``redact_moving_option``'s form.  ``frame_index`` / ``n_frames`` / ``gate`` /
     ``cut`` as ``plate_update``'s.  Three launches, everything guarded on the device: the call can be captured in a graph."""
     _require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    h, w = _frame_u8(frame)
     assert state.is_cuda and state.dtype == torch.uint8 and state.dim() == 1 and state.is_contiguous()
     assert plane.is_cuda and plane.dtype == torch.uint8 and plane.dim() == 1 and plane.is_contiguous()
     assert plate.is_cuda and plate.dtype == torch.int32 and plate.dim() == 1 and plate.is_contiguous()
     assert stats.is_cuda and stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() == _lib.REDACT_MOVING_STATS_WORDS
     assert table.is_cuda and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()
-    h, w = int(frame.shape[0]), int(frame.shape[1])
     assert int(state.numel()) == redact_moving_state_bytes(h, w) and int(plane.numel()) == redact_region_plane_bytes(h, w)
     assert int(plate.numel()) == plate_state_words(h, w)
     rows = _plate_rows(det_packed, tracked)

@@ -216,13 +216,13 @@ def test_header_binding_and_library_agree():
     assert loaded.frcnn_version() == _lib.ABI_VERSION == int(re.search(r"#define FRCNN_ABI_VERSION (\d+)", core).group(1))
     size = loaded.frcnn_count_state_bytes
     assert size(1) == 4 * 26 and size(128) == 4 * (20 + 6 * 128) and size(0) == size(129) == size(-1) == 0
-    # the kernel's glyph rows are the font's
-    src = open(os.path.join(ROOT, "faster_rcnn_amd", "csrc", "count.hip")).read()
+    # the draw kernels' glyph rows (csrc/overlay.h: the count and the zone labels' glyphs in one table) are the font's
+    src = open(os.path.join(ROOT, "faster_rcnn_amd", "csrc", "overlay.h")).read()
     from faster_rcnn_amd import annotate_font
-    table = re.search(r"CT_GLYPHS\[14\]\[7\] = \{(.*?)\};", src, flags=re.S).group(1)
-    rows = np.array([int(v, 16) for v in re.findall(r"0x[0-9A-Fa-f]{2}", table)]).reshape(14, 7)
-    assert np.array_equal(rows, np.stack([annotate_font.glyph(c) for c in " +-0123456789L"]))
-    palette = re.search(r"CT_PALETTE\[8\]\[3\] = \{(.*?)\};", src, flags=re.S).group(1)
+    table = re.search(r"OV_GLYPHS\[16\]\[7\] = \{(.*?)\};", src, flags=re.S).group(1)
+    rows = np.array([int(v, 16) for v in re.findall(r"0x[0-9A-Fa-f]{2}", table)]).reshape(16, 7)
+    assert np.array_equal(rows, np.stack([annotate_font.glyph(c) for c in " +-/0123456789LZ"]))
+    palette = re.search(r"OV_PALETTE\[8\]\[3\] = \{(.*?)\};", src, flags=re.S).group(1)
     assert tuple(map(tuple, np.array(re.findall(r"\d+", palette), dtype=int).reshape(8, 3))) == R.PALETTE
 
 

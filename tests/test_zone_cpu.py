@@ -84,6 +84,34 @@ def test_zone_option_refuses(bad):
         ops.zone_option(**args)
 
 
+def test_the_five_options_with_classes_read_them_alike_each_under_its_own_name():
+    from faster_rcnn_amd import ops
+    tri, line = ((1, 2), (30, 4), (5, 60)), (1, 2, 30, 4)
+    tail = ': "all", a class name or a list of class names'
+    callers = {"heat classes": lambda c: ops.heat_option(c)[0], "remove classes": lambda c: ops.plate_option(c)[0],
+               "count classes": lambda c: ops.count_option(line, c)[1], "zone classes": lambda c: ops.zone_option(tri, c)[1],
+               "redact moving except_classes": lambda c: ops.redact_moving_option(except_classes=c)[6]}
+    for what, call in callers.items():
+        assert call("all") == call(["all"]) == "all" and call("car") == ("car",) and call(["car", "all"]) == ("car", "all")
+        moving = what.startswith("redact moving")
+        for bad, shown in ((3, "3"), (["car", ""], "['car', '']" if moving else "('car', '')"), ([7], "[7]" if moving else "(7,)")):
+            with pytest.raises(ValueError) as e:
+                call(bad)
+            assert str(e.value) == "%s=%s%s" % (what, shown, tail)
+    # None: "all" for count and zone, no class for the moving option's exceptions, refused by heat and remove; no name at all likewise
+    assert callers["count classes"](None) == callers["zone classes"](None) == "all"
+    assert callers["redact moving except_classes"](None) == callers["redact moving except_classes"]([]) == ()
+    for what in ("heat classes", "remove classes"):
+        for bad, shown in ((None, "None"), ([], "()")):
+            with pytest.raises(ValueError) as e:
+                callers[what](bad)
+            assert str(e.value) == "%s=%s%s" % (what, shown, tail)
+    for what in ("count classes", "zone classes"):
+        with pytest.raises(ValueError) as e:
+            callers[what](())
+        assert str(e.value) == "%s=()%s" % (what, tail)
+
+
 def test_the_lists_and_totals_read_back():
     from faster_rcnn_amd import ops
     case = next(c for c in R.HAND_CASES if c[0].startswith("two ids"))
